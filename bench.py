@@ -14,11 +14,17 @@ One "posterior update" = one regressor's full (mw', T, logpdf).
     python bench.py --gpus N ...          (no launcher: bench.py starts that launcher itself as a child process and relays rank 0's
                                            line; a launcher that cannot start, or WORLD_SIZE != --gpus, is a non-zero exit)
 
-Output on rank 0 (contract in the task statement): the LAST stdout line is ONE compact JSON object (< 3 KB: metric, value, unit,
-n_gpus, steps, warmup, ms_per_step, dtype, config, roofline, cpu_baseline, scaling, vs_baseline).  At one GPU the other BASELINE
-shapes and hot-path rows (c2 in fp32, c4, c3, c5 end to end, marginals, rand, gradient, ...) are timed the same way in the same
-process AFTER the timed region; each prints one short JSON line ({"secondary": name, ms, per_s, bound, frac, traffic_x, kernel})
-BEFORE the headline line, and their full records go to gpurun_out/bench_secondary_latest.json.
+Output on rank 0: the LAST stdout line is ONE compact JSON object (< 3 KB: metric, value, unit, n_gpus, steps, warmup,
+ms_per_step, dtype, config, roofline, scaling, vs_baseline; cpu_baseline with --full).  A plain run does only what that line needs: set-up, pre-heat and
+W warm-up steps, the K timed steps, the line.
+
+    --dump-outputs DIR   after the timed steps, what the last timed step handed its caller goes to DIR/<name>.npy (see
+                         dump_outputs); the inputs are seeded, so two builds can be compared output for output
+    --full               everything else: the cpu_baseline leg (--cpu-seconds) and, at one GPU, the other BASELINE shapes and
+                         hot-path rows (c2 in fp32, c4, c3, c5 end to end, marginals, rand, gradient, ...; --secondary), timed
+                         the same way in the same process AFTER the timed region.  Each prints one short JSON line ({"secondary":
+                         name, ms, per_s, bound, frac, traffic_x, kernel}) BEFORE the headline line; their full records go to the
+                         side file the line names in secondary_file.  --secondary-only needs it too.
 """
 import argparse
 import glob
@@ -364,6 +370,32 @@ def headline_line(out):
     line = json.dumps(d)
     assert len(line) < 3072, f"headline line is {len(line)} bytes"
     return line
+
+
+DUMP_BYTES = 64 << 20  # all files of --dump-outputs together
+DUMP_SEED = 20240917   # the rows kept of an output too large to write whole
+
+
+def dump_outputs(dirname, wl, total_evidence):
+    """--dump-outputs: what the last timed step handed its caller -- the total log evidence of the batch, the per-regressor log
+    evidences and status codes, mw' and T -- as DIR/<name>.npy, float64 (the evidences, the status codes) or the workload's dtype.
+    Each output gets an equal share of DUMP_BYTES.  One that does not fit its share (T at the headline shape: B x D x D, 512 MB)
+    is written as a fixed, seeded sample of its rows over the last dimension (of its elements, when it has one dimension), in
+    order, and <name>_rows.npy holds their indices into the output viewed as (rows, last dimension)."""
+    torch = wl.torch
+    outs = {"total_log_evidence": torch.tensor([total_evidence], dtype=torch.float64), "logpdf": wl.lp,
+            "info": wl.info.to(torch.float64), "mw_post": wl.mw_post, "T_post": wl.T_post}
+    share = (DUMP_BYTES - 4096 * 2 * len(outs)) // len(outs)  # (headroom for the .npy headers)
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in outs.items():
+        rows = a.reshape(-1, a.shape[-1]) if a.dim() > 1 else a.reshape(-1, 1)
+        if rows.numel() * rows.element_size() <= share:
+            np.save(os.path.join(dirname, name + ".npy"), a.cpu().numpy())
+            continue
+        k = share // (rows.shape[1] * rows.element_size() + 8)
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(rows.shape[0], size=k, replace=False))
+        np.save(os.path.join(dirname, name + ".npy"), rows[torch.from_numpy(idx).to(a.device)].cpu().numpy())
+        np.save(os.path.join(dirname, name + "_rows.npy"), idx.astype(np.float64))
 
 
 class Op:
@@ -712,13 +744,20 @@ def main():
     ap.add_argument("--preheat-seconds", type=float, default=None,
                     help="untimed back-to-back steps BEFORE the W warm-up steps, so that the K timed steps run at the clock the part "
                          "SUSTAINS under this load rather than at a cold burst clock (default: 2 s on the headline workload, else 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the cpu_baseline leg and, at one GPU on the headline "
+                         "workload, the secondary entries; --cpu-seconds, --secondary and --secondary-only act only with it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0's block) as DIR/<name>.npy, "
+                         f"{DUMP_BYTES >> 20} MB at most")
     ap.add_argument("--cpu-seconds", type=float, default=None,
-                    help="wall budget of the cpu_baseline leg (0 = skip; default: 24 s at the headline shape, skipped otherwise)")
+                    help="with --full: wall budget of the cpu_baseline leg (0 = skip; default: 24 s at the headline shape, skipped "
+                         "otherwise)")
     ap.add_argument("--secondary", type=int, default=None,
-                    help="1: also time the other BASELINE shapes (default at one GPU on the headline workload), 0: skip")
+                    help="with --full: 1: also time the other BASELINE shapes (default at one GPU on the headline workload), 0: skip")
     ap.add_argument("--secondary-only", default=None,
-                    help="comma-separated names of secondary entries (or 'all'): time ONLY those (no headline workload, no CPU leg) and "
-                         "print {\"secondary\": ...}; tools/collect_profiles.sh profiles them one by one this way")
+                    help="with --full: comma-separated names of secondary entries (or 'all'): time ONLY those (no headline workload, "
+                         "no CPU leg) and print {\"secondary\": ...}; tools/collect_profiles.sh profiles them one by one this way")
     ap.add_argument("--config", choices=["c2", "c3", "c4", "c5"], default=None,
                     help="make one of the secondary BASELINE shapes the measured workload; c4 is BASELINE's STRONG-scaling "
                          "case: a fixed batch of 8192 regressors sharded over the ranks (8192 / N per GPU)")
@@ -729,6 +768,8 @@ def main():
                     help="N > 1: the evidence exchange through the library's own RCCL binding (blr_comm_init + "
                          "blr_logpdf_allgather_sum; torch.distributed only ships the unique id) or through torch.distributed")
     args = ap.parse_args()
+    if not args.full and (args.cpu_seconds or args.secondary or args.secondary_only):
+        ap.error("--cpu-seconds, --secondary and --secondary-only measure beyond the headline: add --full")
     Din = None
     if args.config == "c3":
         args.D, args.N, args.dtype, args.noise, args.batch = 1024, 65536, "f32", "diagonal", 1
@@ -740,7 +781,7 @@ def main():
         args.D, args.N, args.dtype, args.noise, args.batch, Din = 2048, 16384, "f32", "isotropic", 1, 8
     headline = (args.D, args.N, args.dtype, args.noise, Din) == (128, 4096, "f64", "isotropic", None)
     if args.cpu_seconds is None:
-        args.cpu_seconds = 24.0 if headline else 0.0
+        args.cpu_seconds = 24.0 if (headline and args.full) else 0.0
     if args.secondary_only:
         args.cpu_seconds = 0.0
     if args.preheat_seconds is None:
@@ -757,7 +798,7 @@ def main():
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}: launch one rank per GPU "
                          f"(python -m torch.distributed.run --nproc-per-node {args.gpus} bench.py --gpus {args.gpus} ...)")
     if args.secondary is None:
-        args.secondary = 1 if (headline and world == 1) else 0
+        args.secondary = 1 if (args.full and headline and world == 1) else 0
     cpu_leg = None
     if args.cpu_seconds > 0 and world == 1 and rank == 0:
         cpu_leg = cpu_baseline(args.D, args.N, args.cpu_seconds, 123456)  # before any GPU initialisation
@@ -965,6 +1006,8 @@ def main():
         lp_sum = lp_sums[(nstep[0] - 1) & 1]  # the last step's exchange
     total_evidence = float(lp_sum.item())
     assert np.isfinite(total_evidence)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, wl, total_evidence)
 
     out = None
     if rank == 0:

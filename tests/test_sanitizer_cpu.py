@@ -28,8 +28,11 @@ def test_abi_layer_under_address_and_ub_sanitizer():
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lib = os.path.join(CSRC, "san", "libblr_mi355x_asan.so")
     env = dict(os.environ)
-    env.update({"LD_PRELOAD": rt, "ASAN_OPTIONS": "detect_leaks=0:halt_on_error=1", "UBSAN_OPTIONS": "print_stacktrace=1:halt_on_error=1",
-                "BLR_MI355X_LIB": lib})
+    # the ASan runtime goes first, in front of anything the environment already preloads; the child sees no GPU, on a GPU box too:
+    # the sanitized host code runs the paths a machine without one takes, and never starts the device runtime under ASan
+    preload = rt + (":" + env["LD_PRELOAD"] if env.get("LD_PRELOAD") else "")
+    env.update({"LD_PRELOAD": preload, "ASAN_OPTIONS": "detect_leaks=0:halt_on_error=1", "UBSAN_OPTIONS": "print_stacktrace=1:halt_on_error=1",
+                "BLR_MI355X_LIB": lib, "ROCR_VISIBLE_DEVICES": "-1", "HIP_VISIBLE_DEVICES": "-1"})
     r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_abi_cpu.py"), "-q", "-x", "-p", "no:cacheprovider"],
                        capture_output=True, text=True, env=env, cwd=ROOT)
     out = r.stdout + r.stderr

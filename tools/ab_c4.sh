@@ -2,7 +2,7 @@
 # same-box A/B of two builds of the library on bench entries: tools/ab_c4.sh <libA> <libB> entry...
 A=$1; B=$2; shift 2
 for i in 1 2; do for lib in $A $B; do for s in "$@"; do
-  BLR_MI355X_LIB=$PWD/$lib python bench.py --secondary-only $s 2>/dev/null | tail -1 | python3 -c "
+  BLR_MI355X_LIB=$PWD/$lib python bench.py --full --secondary-only $s 2>/dev/null | tail -1 | python3 -c "
 import sys,json
 d=json.loads(sys.stdin.readline())['secondary']
 for k,v in d.items():

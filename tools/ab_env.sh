@@ -3,7 +3,7 @@
 V=$1; shift
 for i in 1 2; do for on in 0 1; do for s in "$@"; do
   if [ $on = 1 ]; then export BLR_MI355X_$V=1; else unset BLR_MI355X_$V; fi
-  python bench.py --secondary-only $s 2>/dev/null | tail -1 | python3 -c "
+  python bench.py --full --secondary-only $s 2>/dev/null | tail -1 | python3 -c "
 import sys,json
 d=json.loads(sys.stdin.readline())['secondary']
 for k,v in d.items():

@@ -7,7 +7,7 @@ for rep in 1 2; do
   for lib in "$@"; do
     if [ "$lib" = "-" ]; then unset BLR_MI355X_LIB; else export BLR_MI355X_LIB=$R/$lib; fi
     echo "--- $lib (rep $rep)"
-    python bench.py --secondary-only $e 2>/dev/null | grep '^{"secondary": "' | python -c "
+    python bench.py --full --secondary-only $e 2>/dev/null | grep '^{"secondary": "' | python -c "
 import sys,json
 for l in sys.stdin:
     d=json.loads(l); print('   %-28s %9.4f ms  frac %.3f  %s' % (d['secondary'], d['ms'], d['frac'], d['kernel'][:40]))"

@@ -7,9 +7,9 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/profiles_raw
 rm -rf "$OUT"; mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-B="python3 $R/bench.py --cpu-seconds 0 --secondary 0 --preheat-seconds 0"
-# the driver's command: one short line per secondary entry, then the headline as the LAST line; full secondary records in a side file
-python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_c2_f64.out 2> $OUT/bench_c2_f64.err
+B="python3 $R/bench.py --full --cpu-seconds 0 --secondary 0 --preheat-seconds 0"
+# the full benchmark: one short line per secondary entry, then the headline as the LAST line; full secondary records in a side file
+python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench_c2_f64.out 2> $OUT/bench_c2_f64.err
 tail -1 $OUT/bench_c2_f64.out > $OUT/bench_c2_f64.json
 cp $R/gpurun_out/bench_secondary_latest.json $OUT/bench_c2_f64_secondary.json 2>/dev/null
 $B --dtype f32 > $OUT/bench_c2_f32.json 2>/dev/null

@@ -4,7 +4,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 e=$1; shift
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/kprof_$e
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kprof_$e -- python3 $R/bench.py --secondary-only $e "$@" > /tmp/kprof_$e.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kprof_$e -- python3 $R/bench.py --full --secondary-only $e "$@" > /tmp/kprof_$e.log 2>&1
 f=$(find /tmp/kprof_$e -name "*kernel_stats.csv" | head -1)
 mkdir -p $R/gpurun_out
 python3 - "$f" > $R/gpurun_out/kprof_$e.txt <<'PY'

@@ -5,7 +5,7 @@ if [ "$1" != "-" ]; then export BLR_MI355X_LIB=$R/$1; fi
 e=$2
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/kp_$e
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kp_$e -- python3 $R/bench.py --secondary-only $e > /tmp/kp_$e.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kp_$e -- python3 $R/bench.py --full --secondary-only $e > /tmp/kp_$e.log 2>&1
 f=$(find /tmp/kp_$e -name "*kernel_stats.csv" | head -1)
 echo "== $1 $e"
 python3 - "$f" <<'PY'

@@ -4,7 +4,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 e=$1; k=$2
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/pmc1
-rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY --kernel-trace --output-format csv -d /tmp/pmc1 -- python3 $R/bench.py --secondary-only $e > /tmp/pmc1.log 2>&1
+rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY --kernel-trace --output-format csv -d /tmp/pmc1 -- python3 $R/bench.py --full --secondary-only $e > /tmp/pmc1.log 2>&1
 f=$(find /tmp/pmc1 -name "*counter_collection.csv" | head -1)
 python3 - "$f" "$k" <<'PY'
 import csv,sys,collections
