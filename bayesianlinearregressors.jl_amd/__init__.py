@@ -35,6 +35,7 @@ from .regressor import (
     rand,
     rand_and_pullback,
     rand_b,
+    rand_map,
     std,
     var,
 )
@@ -42,5 +43,5 @@ from .regressor import (
 __all__ = [
     "logpdf", "rand", "mean", "std", "cov", "var", "BayesianLinearRegressor", "marginals", "posterior",
     "BasisFunctionRegressor", "ColVecs", "RowVecs", "Diagonal", "Symmetric", "PDMat", "Normal", "FiniteGP",
-    "BLRFunctionSample", "RandomFourierFeatures", "mean_and_var", "mean_and_cov", "rand_b", "rand_and_pullback", "evaluate", "logpdf_columns", "logpdf_and_gradient", "logpdf_map", "posterior_map", "BLRError", "PosDefException", "ResidentPosterior",
+    "BLRFunctionSample", "RandomFourierFeatures", "mean_and_var", "mean_and_cov", "rand_b", "rand_and_pullback", "evaluate", "logpdf_columns", "logpdf_and_gradient", "logpdf_map", "posterior_map", "rand_map", "BLRError", "PosDefException", "ResidentPosterior",
 ]

@@ -85,6 +85,9 @@ for _suf in ("f64", "f32"):
          _vp, _i64, _vp, _i64, _vp], _int)
     _SIGS[f"blr_rand_{_suf}"] = (
         [_H, _int, _int, _i64, _i64, _i64, _vp, _i64, _int, _vp, _int, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64], _int)
+    _SIGS[f"blr_rand_batched_{_suf}"] = (
+        [_H, _int, _int, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _int, _vp, _i64, _int, _vp, _i64, _vp, _i64, _i64,
+         _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp], _int)
     _SIGS[f"blr_apply_weights_{_suf}"] = ([_H, _int, _int, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64], _int)
     _SIGS[f"blr_sample_weights_{_suf}"] = (
         [_H, _int, _i64, _i64, _int, _vp, _vp, _i64, _vp, _i64, _vp, _i64], _int)
@@ -337,6 +340,14 @@ class Handle:
         if rc > 0:
             raise PosDefException(rc)
         return rc
+
+    def rand_batched(self, dtype, memspace, layout, B, D, N, S, X, ldx, strideX, noise_kind, s, strides, prior_kind, mw, stridemw,
+                     Lw, ldl, strideLw, Z1, ldz1, strideZ1, Z2, ldz2, strideZ2, W, ldw, strideW, Y, ldy, strideY, info):
+        """Draws from B regressors in one call; include/blr_mi355x.h blr_rand_batched_* (per-regressor status in info)."""
+        fn = getattr(self.lib, f"blr_rand_batched_{suffix(dtype)}")
+        return self.check(fn(self._h, memspace, layout, B, D, N, S, _ptr(X), ldx, strideX, noise_kind, _ptr(s), strides, prior_kind,
+                             _ptr(mw), stridemw, _ptr(Lw), ldl, strideLw, _ptr(Z1), ldz1, strideZ1, _ptr(Z2), ldz2, strideZ2,
+                             _ptr(W), ldw, strideW, _ptr(Y), ldy, strideY, _ptr(info)))
 
     def apply_weights(self, dtype, memspace, layout, D, N, S, X, ldx, W, ldw, Y, ldy):
         """Y (N x S) = X'W for S given weight vectors; include/blr_mi355x.h blr_apply_weights_*."""

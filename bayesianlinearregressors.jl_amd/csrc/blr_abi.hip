@@ -28,6 +28,7 @@
 #include "blr_fused_wave.hpp"
 #include "blr_fused_i8.hpp"
 #include "blr_marginals.hpp"
+#include "blr_rand_batched.hpp"
 
 using namespace blr;
 
@@ -2571,6 +2572,163 @@ int rand_impl(blr_handle* h, int memspace, int layout, int64_t D, int64_t N, int
   return 0;
 }
 
+// ---- draws from B regressors in one call (blr_rand_batched_*; reference :49-53 and sampling_functions.jl:27-49 under a map) ------
+// D <= 128: [one batched Cholesky of a dense prior] + rand_batched_solve_kernel (+ one projection launch unless it is fused): the
+// launch count does not depend on B, and nothing a launch computes for regressor b depends on B or on the other regressors.
+// D > 128: one regressor at a time on sample_weights_large + launch_project (correct, not fast; synchronises for the status).
+template <typename T>
+int rand_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t N, int64_t S, const T* X, int64_t ldx,
+                 int64_t strideX, int noise_kind, const T* s, int64_t strides, int prior_kind, const T* mw, int64_t stridemw,
+                 const T* Lw, int64_t ldl, int64_t strideLw, const T* Z1, int64_t ldz1, int64_t strideZ1, const T* Z2, int64_t ldz2,
+                 int64_t strideZ2, T* W, int64_t ldw, int64_t strideW, T* Y, int64_t ldy, int64_t strideY, int32_t* info) {
+  if (!h) return -1;
+  h->err.clear();
+  if (memspace != BLR_MEM_HOST && memspace != BLR_MEM_DEVICE) return bad_arg(h, 2, "memspace");
+  if (layout != BLR_LAYOUT_COLVECS && layout != BLR_LAYOUT_ROWVECS) return bad_arg(h, 3, "unknown layout (reference :26-31)");
+  if (B < 0 || B > (1 << 30)) return bad_arg(h, 4, "B out of range (0..2^30)");
+  if (D < 1 || D > kMaxLargeD) return bad_arg(h, 5, "D out of range for this build (1..8192)");
+  if (N < 0 || N > (1 << 30)) return bad_arg(h, 6, "N out of range");
+  if (S < 0 || S > (1 << 30)) return bad_arg(h, 7, "S out of range");
+  const bool proj = Y && N > 0;  // Y = NULL: weights only
+  const bool noisy = proj && Z2;  // Z2 = NULL: noise-free function values, noise_kind and s ignored
+  if (proj && !X) return bad_arg(h, 8, "X is NULL");
+  if (proj && (layout == BLR_LAYOUT_COLVECS ? ldx < D : ldx < N)) return bad_arg(h, 9, "ldx too small");
+  if (strideX < 0) return bad_arg(h, 10, "strideX < 0");
+  if (noisy && noise_kind != BLR_NOISE_ISOTROPIC && noise_kind != BLR_NOISE_DIAGONAL) return bad_arg(h, 11, "noise_kind");
+  if (noisy && !s) return bad_arg(h, 12, "s is NULL");
+  if (strides < 0) return bad_arg(h, 13, "strides < 0");
+  if (prior_kind != BLR_PRIOR_DENSE && prior_kind != BLR_PRIOR_UPPER_FACTOR && prior_kind != BLR_PRIOR_DIAGONAL)
+    return bad_arg(h, 14, "prior_kind");
+  if (!mw) return bad_arg(h, 15, "mw is NULL");
+  if (stridemw < 0) return bad_arg(h, 16, "stridemw < 0");
+  if (!Lw) return bad_arg(h, 17, "Lw is NULL");
+  if (prior_kind != BLR_PRIOR_DIAGONAL && ldl < D) return bad_arg(h, 18, "ldl < D");
+  if (strideLw < 0) return bad_arg(h, 19, "strideLw < 0");
+  if (!Z1) return bad_arg(h, 20, "Z1 is NULL");
+  if (ldz1 < D) return bad_arg(h, 21, "ldz1 < D");
+  if (strideZ1 < 0) return bad_arg(h, 22, "strideZ1 < 0");
+  if (noisy && ldz2 < N) return bad_arg(h, 24, "ldz2 < N");
+  if (strideZ2 < 0) return bad_arg(h, 25, "strideZ2 < 0");
+  if (W && ldw < D) return bad_arg(h, 27, "ldw < D");
+  if (W && B > 1 && strideW < ldw * S) return bad_arg(h, 28, "strideW < ldw * S: the outputs of two regressors overlap");
+  if (Y && ldy < N) return bad_arg(h, 30, "ldy < N");
+  if (Y && B > 1 && strideY < ldy * S) return bad_arg(h, 31, "strideY < ldy * S: the outputs of two regressors overlap");
+  if (!info) return bad_arg(h, 32, "info is NULL");
+  if (B == 0 || S == 0) return 0;
+  HIP_TRY(h, hipSetDevice(h->device));
+
+  Staging guard(h);
+  const T *X_d = X, *s_d = s, *mw_d = mw, *Lw_d = Lw, *Z1_d = Z1, *Z2_d = noisy ? Z2 : nullptr;
+  T *W_d = W, *Y_d = proj ? Y : nullptr;
+  int32_t* info_d = info;
+  int rc;
+  const size_t nW = W ? extent(B, strideW, mat_extent(D, S, ldw)) : 0, nY = proj ? extent(B, strideY, mat_extent(N, S, ldy)) : 0;
+  if (memspace == BLR_MEM_HOST) {
+    const size_t x_one = layout == BLR_LAYOUT_COLVECS ? mat_extent(D, N, ldx) : mat_extent(N, D, ldx);
+    const size_t lw_one = prior_kind == BLR_PRIOR_DIAGONAL ? (size_t)D : mat_extent(D, D, ldl);
+    if ((rc = stage_in(h, proj ? X : nullptr, extent(B, strideX, x_one), &X_d))) return rc;
+    if ((rc = stage_in(h, noisy ? s : nullptr, extent(B, strides, noise_kind == BLR_NOISE_DIAGONAL ? (size_t)N : 1), &s_d))) return rc;
+    if ((rc = stage_in(h, mw, extent(B, stridemw, (size_t)D), &mw_d))) return rc;
+    if ((rc = stage_in(h, Lw, extent(B, strideLw, lw_one), &Lw_d))) return rc;
+    if ((rc = stage_in(h, Z1, extent(B, strideZ1, mat_extent(D, S, ldz1)), &Z1_d))) return rc;
+    if ((rc = stage_in(h, Z2_d, extent(B, strideZ2, mat_extent(N, S, ldz2)), &Z2_d))) return rc;
+    if ((rc = stage_out_alloc(h, W, nW, &W_d))) return rc;
+    if ((rc = stage_out_alloc(h, Y_d, nY, &Y_d))) return rc;
+    if ((rc = stage_out_alloc(h, info, (size_t)B, &info_d))) return rc;
+  }
+  auto finish = [&]() -> int {
+    HIP_TRY(h, hipGetLastError());
+    if (memspace == BLR_MEM_HOST) {
+      if (W) HIP_TRY(h, hipMemcpyAsync(W, W_d, nW * sizeof(T), hipMemcpyDeviceToHost, h->stream));
+      if (proj) HIP_TRY(h, hipMemcpyAsync(Y, Y_d, nY * sizeof(T), hipMemcpyDeviceToHost, h->stream));
+      HIP_TRY(h, hipMemcpyAsync(info, info_d, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    }
+    if (memspace == BLR_MEM_HOST || !h->async) HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return 0;
+  };
+
+  if (D > kMaxSmallD) {
+    std::vector<int32_t> hinfo((size_t)B, 0);
+    if (prior_kind != BLR_PRIOR_DENSE) {
+      hipLaunchKernelGGL(rand_batched_status_kernel<T>, dim3((unsigned)std::min<int64_t>((B + kWaves - 1) / kWaves, 1 << 16)),
+                         dim3(kThreads), 0, h->stream, Lw_d, ldl, strideLw, prior_kind == BLR_PRIOR_DIAGONAL ? 1 : 0, (int)D, B, info_d);
+      HIP_TRY(h, hipGetLastError());
+      HIP_TRY(h, hipMemcpyAsync(hinfo.data(), info_d, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+      HIP_TRY(h, hipStreamSynchronize(h->stream));
+    }
+    T* Wtmp = nullptr;
+    if (!W_d) {
+      if ((rc = ensure_aux(h, (size_t)D * S * sizeof(T)))) return rc;
+      Wtmp = reinterpret_cast<T*>(h->aux);
+    }
+    for (int64_t b = 0; b < B; ++b) {
+      if (hinfo[b]) continue;
+      T* Wb = W_d ? W_d + b * strideW : Wtmp;
+      const int64_t ldwb = W_d ? ldw : D;
+      rc = sample_weights_large<T>(h, D, S, prior_kind, mw_d + b * stridemw, Lw_d + b * strideLw, ldl, Z1_d + b * strideZ1, ldz1, Wb, ldwb);
+      if (rc < 0) return rc;
+      if (rc > 0) { hinfo[b] = rc; continue; }  // a dense prior that is not positive definite: nothing was written
+      if (proj)
+        launch_project<T>(h, layout, D, N, S, X_d + b * strideX, ldx, (const T*)Wb, ldwb, noisy ? s_d + b * strides : nullptr, noise_kind,
+                          Z2_d ? Z2_d + b * strideZ2 : nullptr, ldz2, Y_d + b * strideY, ldy);
+      HIP_TRY(h, hipGetLastError());
+    }
+    HIP_TRY(h, hipMemcpyAsync(info_d, hinfo.data(), (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));  // (hinfo is a host temporary)
+    return finish();
+  }
+
+  RandBatchedArgs<T> a{};
+  a.layout = layout; a.noise_kind = noise_kind; a.D = (int)D; a.N = (int)N; a.S = S; a.B = B;
+  a.X = X_d; a.ldx = ldx; a.strideX = strideX;
+  a.s = s_d; a.strides = strides;
+  a.mw = mw_d; a.stridemw = stridemw;
+  a.Z1 = Z1_d; a.ldz1 = ldz1; a.strideZ1 = strideZ1;
+  a.Z2 = Z2_d; a.ldz2 = ldz2; a.strideZ2 = strideZ2;
+  a.W = W_d; a.ldw = ldw; a.strideW = strideW;
+  a.Y = Y_d; a.ldy = ldy; a.strideY = strideY;
+  a.info = info_d;
+  int kind = prior_kind;
+  int32_t* chol_info = nullptr;
+  if ((rc = prior_factor<T>(h, B, D, prior_kind, Lw_d, ldl, strideLw, &a.U, &a.ldu, &a.strideU, &kind, &chol_info))) return rc;
+  a.prior_kind = kind;
+  a.chol_info = chol_info;
+  // the route depends on N, S, D, the layout and the alignment of X -- never on B
+  const bool fuse = proj && N * S <= 512;
+  const int ns = S == 1 ? 1 : 4;
+  a.nsb = (S + ns - 1) / ns;
+  if (proj && !fuse) {  // the weights for the projection launch: ld rounded to 16 bytes, so its operand loads are aligned
+    a.ldwt = (D + 3) & ~(int64_t)3;
+    a.strideWt = a.ldwt * S;
+    if ((rc = ensure_aux(h, (size_t)B * a.strideWt * sizeof(T)))) return rc;
+    a.Wt = reinterpret_cast<T*>(h->aux);
+  }
+  const bool mfma = !h->opt.no_mfma_project && layout == BLR_LAYOUT_COLVECS && D % Mfma<T>::VEC == 0 && aligned16(X_d, ldx, strideX);
+  const int tn = mfma ? ProjCfg<T>::TN : 64, ts = mfma ? ProjCfg<T>::TS : 64;
+  const int ntn = (int)((N + tn - 1) / tn);
+  const int64_t nts = (S + ts - 1) / ts;
+  if (proj && !fuse && nts > 65535) return bad_arg(h, 7, "S too large for the projection grid");
+  const unsigned blocks = (unsigned)std::min<int64_t>((B * a.nsb + kWaves - 1) / kWaves, 1 << 20);
+  void (*solve)(RandBatchedArgs<T>);
+  if (ns == 1) solve = fuse ? rand_batched_solve_kernel<T, 1, true> : rand_batched_solve_kernel<T, 1, false>;
+  else         solve = fuse ? rand_batched_solve_kernel<T, 4, true> : rand_batched_solve_kernel<T, 4, false>;
+  hipLaunchKernelGGL(solve, dim3(blocks), dim3(kThreads), 0, h->stream, a);
+  HIP_TRY(h, hipGetLastError());
+  if (proj && !fuse) {
+    const int64_t per_launch = std::max<int64_t>(1, ((int64_t)1 << 24) / ntn);
+    for (int64_t b0 = 0; b0 < B; b0 += per_launch) {
+      const int64_t nreg = std::min<int64_t>(per_launch, B - b0);
+      const dim3 grid((unsigned)(nreg * ntn), (unsigned)nts);
+      if (mfma)
+        hipLaunchKernelGGL(rand_batched_project_mfma_kernel<T>, grid, dim3(kThreads), ProjCfg<T>::LDS_BYTES, h->stream, a, ntn, b0, nreg);
+      else
+        hipLaunchKernelGGL(rand_batched_project_kernel<T>, grid, dim3(kThreads), 0, h->stream, a, ntn, b0, nreg);
+      HIP_TRY(h, hipGetLastError());
+    }
+  }
+  return finish();
+}
+
 
 template <typename T>
 int rff_features(blr_handle* h, int memspace, int64_t Din, int64_t D, int64_t N, const T* Xin, int64_t ldxin,
@@ -3415,6 +3573,16 @@ int blr_timer_stop(blr_handle* h, float* elapsed_ms) {
   int blr_sample_weights_##SUF(blr_handle* h, int memspace, int64_t D, int64_t S, int prior_kind, const T* mw,      \
                                const T* Lw, int64_t ldl, const T* Z, int64_t ldz, T* W, int64_t ldw) {              \
     return sample_weights<T>(h, memspace, D, S, prior_kind, mw, Lw, ldl, Z, ldz, W, ldw);                           \
+  }                                                                                                                 \
+  int blr_rand_batched_##SUF(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t N, int64_t S,   \
+                             const T* X, int64_t ldx, int64_t strideX, int noise_kind, const T* s, int64_t strides, \
+                             int prior_kind, const T* mw, int64_t stridemw, const T* Lw, int64_t ldl,              \
+                             int64_t strideLw, const T* Z1, int64_t ldz1, int64_t strideZ1, const T* Z2,           \
+                             int64_t ldz2, int64_t strideZ2, T* W, int64_t ldw, int64_t strideW, T* Y,             \
+                             int64_t ldy, int64_t strideY, int32_t* info) {                                        \
+    return rand_batched<T>(h, memspace, layout, B, D, N, S, X, ldx, strideX, noise_kind, s, strides, prior_kind, mw, \
+                           stridemw, Lw, ldl, strideLw, Z1, ldz1, strideZ1, Z2, ldz2, strideZ2, W, ldw, strideW, Y,  \
+                           ldy, strideY, info);                                                                     \
   }                                                                                                                 \
   int blr_rff_features_##SUF(blr_handle* h, int memspace, int64_t Din, int64_t D, int64_t N, const T* Xin,          \
                              int64_t ldxin, const T* Omega, int64_t ldo, const T* phase, T scale, T* Phi,           \

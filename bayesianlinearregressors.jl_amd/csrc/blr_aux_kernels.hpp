@@ -54,17 +54,16 @@ struct MarginalArgs {
 
 // ---- Y = X'W .+ sqrt.(s) .* Z2   (:52) ---------------------------------------------------------------
 // 64 x 64 output tile per workgroup, 256 threads, X and W tiles staged in LDS in chunks of 32 rows of d.
+// (the body is a tile function: rand_batched_project_kernel runs the same tiles for a batch of regressors, blr_rand_batched.hpp)
 template <typename T>
-__global__ __launch_bounds__(kThreads) void rand_project_kernel(const T* __restrict__ X, int64_t ldx, int layout,
-                                                                const T* __restrict__ W, int64_t ldw,
-                                                                const T* __restrict__ s, int noise_kind,
-                                                                const T* __restrict__ Z2, int64_t ldz2,
-                                                                T* __restrict__ Y, int64_t ldy, int D, int N, int64_t S) {
+__device__ __forceinline__ void rand_project_tile(const T* __restrict__ X, int64_t ldx, int layout, const T* __restrict__ W, int64_t ldw,
+                                                  const T* __restrict__ s, int noise_kind, const T* __restrict__ Z2, int64_t ldz2,
+                                                  T* __restrict__ Y, int64_t ldy, int D, int N, int64_t S, int tile_n, int64_t tile_s) {
   __shared__ T xs[32][65];
   __shared__ T ws[32][65];
   const int tid = threadIdx.x;
-  const int n0 = blockIdx.x * 64;
-  const int64_t s0 = (int64_t)blockIdx.y * 64;
+  const int n0 = tile_n * 64;
+  const int64_t s0 = tile_s * 64;
   const int tn = tid & 63, ts = tid >> 6;  // thread computes n = n0+tn, samples s0 + ts + 4*j, j < 16
   T accv[16];
 #pragma unroll
@@ -122,6 +121,14 @@ __global__ __launch_bounds__(kThreads) void rand_project_kernel(const T* __restr
     }
   }
 }
+template <typename T>
+__global__ __launch_bounds__(kThreads) void rand_project_kernel(const T* __restrict__ X, int64_t ldx, int layout,
+                                                                const T* __restrict__ W, int64_t ldw,
+                                                                const T* __restrict__ s, int noise_kind,
+                                                                const T* __restrict__ Z2, int64_t ldz2,
+                                                                T* __restrict__ Y, int64_t ldy, int D, int N, int64_t S) {
+  rand_project_tile<T>(X, ldx, layout, W, ldw, s, noise_kind, Z2, ldz2, Y, ldy, D, N, S, blockIdx.x, blockIdx.y);
+}
 
 // ---- the same projection on the matrix cores: ColVecs inputs with 16-byte aligned columns ---------------------------------
 // Y (N x S) = X' W is a tall-skinny GEMM that reads X once: 128 inputs x 64 draws per workgroup, the contraction over d in
@@ -143,10 +150,9 @@ struct ProjCfg {
 };
 
 template <typename T>
-__global__ __launch_bounds__(kThreads, 2) void rand_project_mfma_kernel(const T* __restrict__ X, int64_t ldx, const T* __restrict__ W,
-                                                                        int64_t ldw, const T* __restrict__ s, int noise_kind,
-                                                                        const T* __restrict__ Z2, int64_t ldz2, T* __restrict__ Y,
-                                                                        int64_t ldy, int D, int N, int64_t S) {
+__device__ __forceinline__ void rand_project_mfma_tile(const T* __restrict__ X, int64_t ldx, const T* __restrict__ W, int64_t ldw,
+                                                       const T* __restrict__ s, int noise_kind, const T* __restrict__ Z2, int64_t ldz2,
+                                                       T* __restrict__ Y, int64_t ldy, int D, int N, int64_t S, int tile_n, int64_t tile_s) {
   using Cf = ProjCfg<T>;
   using acc4 = typename Mfma<T>::acc4;
   constexpr int VEC = Cf::VEC, VPR = Cf::KC / VEC;  // vectors per row and chunk
@@ -155,8 +161,8 @@ __global__ __launch_bounds__(kThreads, 2) void rand_project_mfma_kernel(const T*
   T* const base = reinterpret_cast<T*>(smem);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int n0 = blockIdx.x * Cf::TN;
-  const int64_t s0 = (int64_t)blockIdx.y * Cf::TS;
+  const int n0 = tile_n * Cf::TN;
+  const int64_t s0 = tile_s * Cf::TS;
   acc4 acc[2][4];
 #pragma unroll
   for (int i = 0; i < 2; ++i)
@@ -263,6 +269,14 @@ __global__ __launch_bounds__(kThreads, 2) void rand_project_mfma_kernel(const T*
         }
       }
     }
+}
+
+template <typename T>
+__global__ __launch_bounds__(kThreads, 2) void rand_project_mfma_kernel(const T* __restrict__ X, int64_t ldx, const T* __restrict__ W,
+                                                                        int64_t ldw, const T* __restrict__ s, int noise_kind,
+                                                                        const T* __restrict__ Z2, int64_t ldz2, T* __restrict__ Y,
+                                                                        int64_t ldy, int D, int N, int64_t S) {
+  rand_project_mfma_tile<T>(X, ldx, W, ldw, s, noise_kind, Z2, ldz2, Y, ldy, D, N, S, blockIdx.x, blockIdx.y);
 }
 
 // ---- random-Fourier feature map (BASELINE config 5): Phi[f, n] = scale * cos(sum_k Omega[k, f] x[k, n] + phase[f]) ----

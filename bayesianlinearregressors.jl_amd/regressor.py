@@ -697,6 +697,22 @@ class ResidentPosterior:
         if info[0] != 0:
             raise _abi.PosDefException(int(info[0]))
 
+    def _inputs(self, x, dev, temps):
+        """-> (device pointer, layout, ldx, number of inputs) of phi(x) (RandomFourierFeatures: evaluated on the device)."""
+        dtype, h, D = self.dtype, self._h, self.D
+        if isinstance(self.phi, RandomFourierFeatures):
+            Xin, ldxin, Din, k, Om, ph = self.phi._operands(x, dtype)
+            if Om.shape[1] != D:
+                raise ValueError(f"number of features ({Om.shape[1]}) != length(mw) = {D}")
+            temps.append(_DeviceBuffer(h, D * max(k, 1) * np.dtype(dtype).itemsize))
+            dX, ldx = temps[-1].ptr, max(D, 1)
+            h.rff_features(dtype, _abi.MEM_DEVICE, Din, D, k, dev(Xin), ldxin, dev(Om), max(Din, 1), dev(ph), self.phi.scale, dX, ldx)
+            return dX, _abi.LAYOUT_COLVECS, ldx, k
+        X, layout, ldx, Dx, k = _x_layout(self.phi(x) if self.phi is not None else x, dtype)
+        if Dx != D:
+            raise ValueError(f"dimension of the inputs ({Dx}) != length(mw) = {D}")
+        return dev(X), layout, ldx, k
+
     def condition(self, x, Sy, y):
         """In-place update with the observations (x, Sy, y); returns log p(y | everything conditioned on so far)."""
         dtype, h, D = self.dtype, self._h, self.D
@@ -707,19 +723,7 @@ class ResidentPosterior:
             return temps[-1].ptr
 
         try:
-            if isinstance(self.phi, RandomFourierFeatures):
-                Xin, ldxin, Din, k, Om, ph = self.phi._operands(x, dtype)
-                if Om.shape[1] != D:
-                    raise ValueError(f"number of features ({Om.shape[1]}) != length(mw) = {D}")
-                temps.append(_DeviceBuffer(h, D * max(k, 1) * np.dtype(dtype).itemsize))
-                dX, layout, ldx = temps[-1].ptr, _abi.LAYOUT_COLVECS, max(D, 1)
-                h.rff_features(dtype, _abi.MEM_DEVICE, Din, D, k, dev(Xin), ldxin, dev(Om), max(Din, 1), dev(ph), self.phi.scale,
-                               dX, ldx)
-            else:
-                X, layout, ldx, Dx, k = _x_layout(self.phi(x) if self.phi is not None else x, dtype)
-                if Dx != D:
-                    raise ValueError(f"dimension of the inputs ({Dx}) != length(mw) = {D}")
-                dX = dev(X)
+            dX, layout, ldx, k = self._inputs(x, dev, temps)
             y = np.ascontiguousarray(y, dtype=dtype)
             if y.shape != (k,):
                 raise ValueError("length(y) != number of inputs")  # reference :74
@@ -740,6 +744,43 @@ class ResidentPosterior:
         if info[0] != 0:
             raise _abi.PosDefException(int(info[0]))
         return float(lp[0])
+
+    def rand(self, rng, x, S, Sy=None):
+        """S draws at the inputs x from the resident state (N x S), without copying T to the host (blr_rand_batched_*, B = 1):
+        with Sy, ``rand(rng, st.regressor()(x, Sy), S)`` (reference :49-53: Z1 drawn first, then Z2); without it the noise-free
+        function values ``evaluate(rand(rng, st.regressor(), S), x)`` (sampling_functions.jl:16-18, 27-38: Z1 only)."""
+        dtype, h, D, S = self.dtype, self._h, self.D, int(S)
+        temps = []
+
+        def dev(a):
+            temps.append(_DeviceBuffer.of(h, a))
+            return temps[-1].ptr
+
+        try:
+            dX, layout, ldx, N = self._inputs(x, dev, temps)
+            s, noise_kind = (np.ones(1, dtype=dtype), _abi.NOISE_ISOTROPIC) if Sy is None else _noise(Sy, N, dtype, need_cholesky=True)
+            if noise_kind == _abi.NOISE_DENSE:
+                raise NotImplementedError("ResidentPosterior.rand takes scalar or diagonal noise")
+            Z1 = _randn(rng, D, S, dtype)
+            Z2 = _randn(rng, N, S, dtype) if Sy is not None else None
+            Y = np.empty((N, S), dtype=dtype, order="F")
+            if N == 0 or S == 0:
+                return Y
+            temps.append(_DeviceBuffer(h, Y.nbytes))
+            dY = temps[-1].ptr
+            d_info = dev(np.zeros(1, dtype=np.int32))
+            h.rand_batched(dtype, _abi.MEM_DEVICE, layout, 1, D, N, S, dX, ldx, 0, noise_kind, dev(s), 0, _abi.PRIOR_UPPER_FACTOR,
+                           self._mw.ptr, 0, self._T.ptr, max(D, 1), 0, dev(Z1), D, 0, dev(Z2) if Z2 is not None else None, N, 0,
+                           None, D, 0, dY, N, 0, d_info)
+            info = np.zeros(1, dtype=np.int32)
+            h.memcpy_d2h(info, d_info)
+            if info[0] != 0:
+                raise _abi.PosDefException(int(info[0]))
+            h.memcpy_d2h(Y, dY)
+            return Y
+        finally:
+            for b in temps:
+                b.free()
 
     def state(self):
         """host copies (mw, T) of the resident state; T column-major upper"""
@@ -1009,3 +1050,126 @@ def _rand_finite(rng, fx, S):
     _handle().rand(dtype, _abi.MEM_HOST, layout, D, N, S, X, ldx, noise_kind, s, prior_kind, mw, Lw, ldl, Z1, D, Z2, N,
                    Y, N)
     return Y
+
+
+# ---------------------------------------------------------------------------------------------------
+# draws from many regressors in ONE library call: `[rand(rng, f, S) for f in fs]` (reference :49-53 / sampling_functions.jl:27-38
+# under a map) through blr_rand_batched_*
+# ---------------------------------------------------------------------------------------------------
+def _draw_problem(rng, f, S, finite):
+    """The operands of one draw, with its normals taken from rng in the reference's order (Z1 first, then Z2 for a FiniteGP)."""
+    if finite:
+        fx = _to_finite_blr(f)
+        blr = fx.f
+        dtype = _dtype_of(blr.mw)
+        X, layout, ldx, D, N = _x_layout(fx.x, dtype)
+        x_obj = fx.x
+    else:
+        blr, _ = _blr_and_mapping(f)
+        dtype = _dtype_of(blr.mw)
+        X, layout, ldx, D, N, x_obj = None, _abi.LAYOUT_COLVECS, 1, blr.mw.shape[0], 0, None
+    mw = _mean_vector(blr.mw, D, dtype)
+    Lw, prior_kind, ldl = _prior(blr.Lw, D, dtype, need_cholesky=True)
+    s, noise_kind = _noise(fx.Sy, N, dtype, need_cholesky=True) if finite else (None, _abi.NOISE_ISOTROPIC)
+    Z1 = _randn(rng, D, S, dtype)
+    Z2 = _randn(rng, N, S, dtype) if finite else None
+    return dict(dtype=dtype, X=X, layout=layout, ldx=ldx, D=D, N=N, mw=mw, Lw=Lw, prior_kind=prior_kind, ldl=ldl, s=s,
+                noise_kind=noise_kind, Z1=Z1, Z2=Z2, x_obj=x_obj)
+
+
+def _draw_one(q, S):
+    """One problem through the single-regressor entry points, exactly as `rand` runs it."""
+    h = _handle()
+    dt, D, N = q["dtype"], q["D"], q["N"]
+    if q["Z2"] is None:
+        W = np.empty((D, S), dtype=dt, order="F")
+        h.sample_weights(dt, _abi.MEM_HOST, D, S, q["prior_kind"], q["mw"], q["Lw"], q["ldl"], q["Z1"], D, W, D)
+        return W
+    Y = np.empty((N, S), dtype=dt, order="F")
+    if q["noise_kind"] == _abi.NOISE_DENSE:
+        h.rand_dense_noise(dt, _abi.MEM_HOST, q["layout"], D, N, S, q["X"], q["ldx"], q["s"], max(N, 1), q["prior_kind"], q["mw"],
+                           q["Lw"], q["ldl"], q["Z1"], D, q["Z2"], N, Y, N)
+    else:
+        h.rand(dt, _abi.MEM_HOST, q["layout"], D, N, S, q["X"], q["ldx"], q["noise_kind"], q["s"], q["prior_kind"], q["mw"], q["Lw"],
+               q["ldl"], q["Z1"], D, q["Z2"], N, Y, N)
+    return Y
+
+
+def _draw_many(qs, S):
+    """[Y_b] (FiniteGPs) or [W_b] (regressors): equally shaped problems through ONE blr_rand_batched_* call (the grouping of
+    _fused_many); differing dtypes, shapes, layouts, noise or prior kinds, or a dense noise covariance, fall back to one call per
+    problem.  An input X that is the same object for every problem is passed once (strideX = 0)."""
+    sig = {(q["dtype"], None if q["X"] is None else (q["X"].shape, q["X"].flags.f_contiguous), q["layout"], q["D"], q["N"],
+            q["noise_kind"], q["prior_kind"], None if q["s"] is None else q["s"].shape) for q in qs}
+    finite = qs[0]["Z2"] is not None
+    q0 = qs[0]
+    if len(sig) != 1 or q0["noise_kind"] == _abi.NOISE_DENSE or (finite and q0["N"] == 0):
+        out = []
+        for b, q in enumerate(qs):
+            try:
+                out.append(_draw_one(q, S))
+            except _abi.PosDefException as e:
+                e.index = b
+                raise
+        return out
+    dt, D, N, nb = q0["dtype"], q0["D"], q0["N"], len(qs)
+    mwb = np.stack([q["mw"] for q in qs])
+    Lb = np.stack([q["Lw"].reshape(-1, order="A") for q in qs])
+    Z1b = np.stack([q["Z1"].reshape(-1, order="F") for q in qs])
+    info = np.zeros(nb, dtype=np.int32)
+    if finite:
+        if all(q["x_obj"] is q0["x_obj"] for q in qs):
+            Xb, strideX = q0["X"], 0
+        else:
+            Xb = np.stack([q["X"].reshape(-1, order="A") for q in qs])
+            strideX = Xb.shape[1]
+        sb = np.stack([q["s"] for q in qs])
+        Z2b = np.stack([q["Z2"].reshape(-1, order="F") for q in qs])
+        Yb = np.empty((nb, N * S), dtype=dt)
+        _handle().rand_batched(dt, _abi.MEM_HOST, q0["layout"], nb, D, N, S, Xb, q0["ldx"], strideX, q0["noise_kind"], sb, sb.shape[1],
+                               q0["prior_kind"], mwb, D, Lb, q0["ldl"], Lb.shape[1], Z1b, D, D * S, Z2b, N, N * S, None, D, D * S,
+                               Yb, N, N * S, info)
+        out = [Yb[b].reshape((N, S), order="F") for b in range(nb)]
+    else:
+        Wb = np.empty((nb, D * S), dtype=dt)
+        _handle().rand_batched(dt, _abi.MEM_HOST, _abi.LAYOUT_COLVECS, nb, D, 0, S, None, D, 0, _abi.NOISE_ISOTROPIC, None, 0,
+                               q0["prior_kind"], mwb, D, Lb, q0["ldl"], Lb.shape[1], Z1b, D, D * S, None, 1, 0, Wb, D, D * S,
+                               None, 1, 0, info)
+        out = [Wb[b].reshape((D, S), order="F") for b in range(nb)]
+    bad = np.flatnonzero(info > 0)
+    if bad.size:
+        e = _abi.PosDefException(int(info[bad[0]]))
+        e.index = int(bad[0])
+        raise e
+    return out
+
+
+def rand_map(rng, fs, S):
+    """``[rand(rng, f, S) for f in fs]`` in one library call (blr_rand_batched_*), with the normals drawn from rng in exactly that
+    order (problem by problem: Z1_b, then Z2_b -- reference :51-52).  A list of FiniteGPs gives a list of N_b x S arrays; a list of
+    regressors (BayesianLinearRegressor / BasisFunctionRegressor) gives a list of arrays of S BLRFunctionSamples.  The first problem
+    whose prior (or noise) is not positive definite raises PosDefException; its position is the exception's ``index``."""
+    fs, S = list(fs), int(S)
+    if not fs:
+        return []
+    finite = isinstance(fs[0], FiniteGP)
+    if any(isinstance(f, FiniteGP) != finite for f in fs):
+        raise TypeError("rand_map takes a list of FiniteGPs or a list of regressors, not a mixture")
+    qs = []
+    for b, f in enumerate(fs):
+        try:
+            qs.append(_draw_problem(rng, f, S, finite))
+        except _abi.PosDefException as e:
+            e.index = b
+            raise
+    res = _draw_many(qs, S)
+    if finite:
+        return res
+    out = []
+    for f, W in zip(fs, res):
+        _, phi = _blr_and_mapping(f)
+        arr = np.empty(S, dtype=object)
+        for i in range(S):
+            arr[i] = BLRFunctionSample(W[:, i].copy(), phi)
+        out.append(arr)
+    return out

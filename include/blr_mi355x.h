@@ -241,6 +241,44 @@ int blr_sample_weights_f32(blr_handle* h, int memspace, int64_t D, int64_t S,
                            int prior_kind, const float* mw, const float* Lw, int64_t ldl,
                            const float* Z, int64_t ldz, float* W, int64_t ldw);
 
+/* ---- draws from B regressors in one call: rand (:49-53) and the weight draws of sampling_functions.jl:27-49 under a map ----
+ * For each regressor b (inputs at ptr + b*stride; a stride of 0 shares an input, e.g. one candidate set X or one prior):
+ *   W_b = mw_b + U_b \ Z1_b         (D x S; U_b the upper factor of Lw_b, of whichever prior kind)
+ *   Y_b = X_b' W_b + sqrt.(s_b) .* Z2_b   (N x S; the host's normals, as blr_rand_*)
+ *   Z2 == NULL: noise-free function values Y_b = X_b' W_b (Thompson sampling, BLRFunctionSample evaluation at
+ *     sampling_functions.jl:16-18); noise_kind and s are then ignored.
+ *   W == NULL: the weights are not returned.  Y == NULL: weights only.  N == 0 is allowed (X may then be NULL).  S == 0: no-op.
+ *   Output strides of B > 1 must not overlap: strideW >= ldw*S, strideY >= ldy*S (else the negative argument index).
+ *   info[B]: 0, or k > 0 -- a dense Lw_b not positive definite at leading minor k, or the first non-positive diagonal entry k
+ *   of an upper factor / Diagonal prior.  A failed regressor's outputs are left untouched and the call still returns 0.
+ *   s is not checked (as blr_rand_*).  Both memspaces; DEVICE memspace in async mode only enqueues.
+ * The bits of W_b and Y_b do not depend on B, on b's position or on the other regressors' data, and repeat from call to call.
+ * D <= 128: [one batched Cholesky of a dense prior] + one launch of the weight solve, with the projection fused into it when
+ *   N*S <= 512, else one more launch; the launch count does not depend on B.
+ * D > 128 (up to 8192): one regressor after the other on the blr_sample_weights_* / blr_rand_* kernels -- correct, not fast,
+ *   and it synchronises (the status of every regressor is needed on the host before the loop).
+ */
+int blr_rand_batched_f64(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t N, int64_t S,
+                         const double* X, int64_t ldx, int64_t strideX,
+                         int noise_kind, const double* s, int64_t strides,
+                         int prior_kind, const double* mw, int64_t stridemw,
+                         const double* Lw, int64_t ldl, int64_t strideLw,
+                         const double* Z1, int64_t ldz1, int64_t strideZ1,
+                         const double* Z2, int64_t ldz2, int64_t strideZ2,
+                         double* W, int64_t ldw, int64_t strideW,
+                         double* Y, int64_t ldy, int64_t strideY,
+                         int32_t* info);
+int blr_rand_batched_f32(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t N, int64_t S,
+                         const float* X, int64_t ldx, int64_t strideX,
+                         int noise_kind, const float* s, int64_t strides,
+                         int prior_kind, const float* mw, int64_t stridemw,
+                         const float* Lw, int64_t ldl, int64_t strideLw,
+                         const float* Z1, int64_t ldz1, int64_t strideZ1,
+                         const float* Z2, int64_t ldz2, int64_t strideZ2,
+                         float* W, int64_t ldw, int64_t strideW,
+                         float* Y, int64_t ldy, int64_t strideY,
+                         int32_t* info);
+
 /* ---- random-Fourier basis (BASELINE config 5): phi(x) = scale * cos(Omega' x + phase) ---------------------
  * The reference's BasisFunctionRegressor takes any callable phi (src/basis_function_regression.jl:7-9,41) and ships
  * none; this is the feature map of config 5, applied on the device so Phi never crosses PCIe.

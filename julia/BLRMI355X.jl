@@ -638,6 +638,72 @@ function logpdf(fx::FiniteBLR, Y::AbstractMatrix{<:Real})
     return lp
 end
 
+# ---- draws from many regressors in ONE call (blr_rand_batched_*): `[rand(rng, fx, S) for fx in fxs]` with the normals drawn in
+# exactly that order (Z1_b, then Z2_b, problem by problem -- reference :51-52).  Problems the batched entry point does not take
+# (mixed shapes / layouts / kinds, dense noise) are mapped one by one.  `info` of the first failing problem -> PosDefException.
+function rand_batched_call(h, memspace, layout, B, D, N, S, X, ldx, strideX, nk, s, strides, pk, mw, stridemw, Lw, ldl, strideLw,
+                           Z1, ldz1, strideZ1, Z2, ldz2, strideZ2, W, ldw, strideW, Y, ldy, strideY, info, ::Type{T}) where {T<:Elt}
+    if T === Float64
+        ccall((:blr_rand_batched_f64, LIB), Cint,
+              (Ptr{Cvoid}, Cint, Cint, Int64, Int64, Int64, Int64, Ptr{T}, Int64, Int64, Cint, Ptr{T}, Int64, Cint, Ptr{T}, Int64,
+               Ptr{T}, Int64, Int64, Ptr{T}, Int64, Int64, Ptr{T}, Int64, Int64, Ptr{T}, Int64, Int64, Ptr{T}, Int64, Int64, Ptr{Int32}),
+              h, memspace, layout, B, D, N, S, X, ldx, strideX, nk, s, strides, pk, mw, stridemw, Lw, ldl, strideLw,
+              Z1, ldz1, strideZ1, Z2, ldz2, strideZ2, W, ldw, strideW, Y, ldy, strideY, info)
+    else
+        ccall((:blr_rand_batched_f32, LIB), Cint,
+              (Ptr{Cvoid}, Cint, Cint, Int64, Int64, Int64, Int64, Ptr{T}, Int64, Int64, Cint, Ptr{T}, Int64, Cint, Ptr{T}, Int64,
+               Ptr{T}, Int64, Int64, Ptr{T}, Int64, Int64, Ptr{T}, Int64, Int64, Ptr{T}, Int64, Int64, Ptr{T}, Int64, Int64, Ptr{Int32}),
+              h, memspace, layout, B, D, N, S, X, ldx, strideX, nk, s, strides, pk, mw, stridemw, Lw, ldl, strideLw,
+              Z1, ldz1, strideZ1, Z2, ldz2, strideZ2, W, ldw, strideW, Y, ldy, strideY, info)
+    end
+end
+
+function rand_map(rng::AbstractRNG, fxs::AbstractVector{<:FiniteGP}, S::Int)
+    B = length(fxs)
+    B == 0 && return Matrix[]
+    fbs = map(to_blr, fxs)
+    xls, nzs, prs = map(fb -> xlayout(fb.x), fbs), map(fb -> noise(fb.Σy), fbs), map(fb -> prior(fb.f.Λw), fbs)
+    one_by_one() = [rand(rng, fx, S) for fx in fxs]
+    (any(isnothing, xls) || any(isnothing, nzs) || any(isnothing, prs)) && return one_by_one()
+    X1, layout, ldx, D, N = xls[1]
+    T = eltype(X1)
+    nk, pk = nzs[1][2], prs[1][2]
+    (nk == DENSEN || N == 0) && return one_by_one()
+    same = all(b -> eltype(xls[b][1]) === T && xls[b][2] == layout && xls[b][4] == D && xls[b][5] == N && nzs[b][2] == nk &&
+                    prs[b][2] == pk && length(fbs[b].f.mw) == D, 1:B)
+    same || return one_by_one()
+    rows, cols = layout == COLVECS ? (D, N) : (N, D)
+    shared = all(b -> fbs[b].x === fbs[1].x, 1:B)               # one candidate set for the whole batch: passed once
+    Xb = shared ? X1 : Array{T}(undef, rows, cols, B)
+    if !shared
+        for b in 1:B
+            copyto!(view(Xb, :, :, b), xls[b][1])
+        end
+    end
+    ns = nk == ISOTROPIC ? 1 : N
+    sb, mwb = Matrix{T}(undef, ns, B), Matrix{T}(undef, D, B)
+    Lb = pk == P_DIAG ? Matrix{T}(undef, D, B) : Array{T}(undef, D, D, B)
+    Z1, Z2 = Array{T}(undef, D, S, B), Array{T}(undef, N, S, B)
+    for b in 1:B
+        sb[:, b] .= view(nzs[b][1], 1:ns)
+        mwb[:, b] .= fbs[b].f.mw
+        pk == P_DIAG ? (Lb[:, b] .= prs[b][1]) : copyto!(view(Lb, :, :, b), prs[b][1])
+        Z1[:, :, b] .= randn(rng, T, D, S)                    # reference :51
+        Z2[:, :, b] .= randn(rng, T, N, S)                    # reference :52
+    end
+    ldl, strideL = pk == P_DIAG ? (1, D) : (D, D * D)
+    Y = Array{T}(undef, N, S, B)
+    info = zeros(Int32, B)
+    h = handle()
+    rc = GC.@preserve Xb sb mwb Lb Z1 Z2 Y info rand_batched_call(h, MEM_HOST, layout, B, D, N, S, Xb, shared ? ldx : rows, shared ? 0 : rows * cols, nk,
+                                                                  sb, ns, pk, mwb, D, Lb, ldl, strideL, Z1, D, D * S, Z2, N, N * S,
+                                                                  Ptr{T}(C_NULL), D, D * S, Y, N, N * S, info, T)
+    check(h, rc)
+    bad = findfirst(>(0), info)
+    bad === nothing || throw(PosDefException(Int(info[bad])))
+    return [Y[:, :, b] for b in 1:B]
+end
+
 # ---- device-resident batches: the form every throughput number is measured on ------------------------------------------
 # A DeviceArray owns hipMalloc'd memory through the library's own helpers (no AMDGPU.jl needed); AMDGPU.jl users pass
 # `Ptr{T}(pointer(roc_array))` instead.  Layout = Julia's: X is D x N x B column-major (regressor b at offset (b-1) D N).
@@ -742,6 +808,29 @@ function update_factor!(mw::DeviceArray{T}, Tf::DeviceArray{T}, lp::DeviceArray{
               h, MEM_DEVICE, COLVECS, B, D, k, X.ptr, D, D * k, y.ptr, k, nk, s.ptr, isotropic ? 0 : k, mw.ptr, D, Tf.ptr, D, D * D,
               lp.ptr, info.ptr)
     end
+    check(h, rc)
+    return nothing
+end
+
+"""
+    rand_batched!(Y, W, info, X, mw, Tf, Z1, Z2; D, N, S, B, shared_x=false, s=nothing)
+
+Draws from B device-resident states, the step that closes a Thompson-sampling loop around `update_factor!` on `DeviceArray`s:
+W_b = mw_b + T_b \ Z1_b (D×S) and Y_b = X_b' W_b (N×S), plus sqrt.(s) .* Z2_b when `s` (one variance, a `DeviceArray` of
+length 1) is given.  mw is D×B and Tf D×D×B exactly as `posterior_batched!` / `update_factor!` keep them; X is D×N×B, or one
+D×N candidate set for the whole batch (`shared_x`); Z1 D×S×B and Z2 N×S×B hold the normals (drawn on the host, reference
+:51-52).  `Y`, `W` or `Z2` may be `nothing`.  info[b] > 0: that state's factor has a non-positive diagonal entry; its outputs
+are left untouched.  Reference semantics per regressor: `:49-53`, `sampling_functions.jl:16-49`.
+"""
+function rand_batched!(Y::Union{Nothing,DeviceArray{T}}, W::Union{Nothing,DeviceArray{T}}, info::DeviceArray{Int32}, X::DeviceArray{T},
+                       mw::DeviceArray{T}, Tf::DeviceArray{T}, Z1::DeviceArray{T}, Z2::Union{Nothing,DeviceArray{T}};
+                       D::Int, N::Int, S::Int, B::Int, shared_x::Bool=false, s::Union{Nothing,DeviceArray{T}}=nothing) where {T<:Elt}
+    h = handle()
+    ptr(a) = a === nothing ? Ptr{T}(C_NULL) : a.ptr
+    noisy = Z2 !== nothing && s !== nothing
+    rc = rand_batched_call(h, MEM_DEVICE, COLVECS, B, D, N, S, X.ptr, D, shared_x ? 0 : D * N, ISOTROPIC, noisy ? s.ptr : Ptr{T}(C_NULL),
+                           0, P_UPPER, mw.ptr, D, Tf.ptr, D, D * D, Z1.ptr, D, D * S, noisy ? Z2.ptr : Ptr{T}(C_NULL), N, N * S,
+                           ptr(W), D, D * S, ptr(Y), N, N * S, info.ptr, T)
     check(h, rc)
     return nothing
 end
