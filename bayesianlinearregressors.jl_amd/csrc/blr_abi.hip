@@ -25,6 +25,7 @@
 #include "blr_planes.hpp"
 #include "blr_dense.hpp"
 #include "blr_update.hpp"
+#include "blr_downdate.hpp"
 #include "blr_fused_wave.hpp"
 #include "blr_fused_i8.hpp"
 #include "blr_marginals.hpp"
@@ -36,7 +37,7 @@ using namespace blr;
 // handle is created (BLR_MI355X_<KEY>), and settable per handle with blr_set_option: no getenv on any launch path.
 struct BlrOptions {
   bool no_ldsdma = false, no_wave_kernel = false, no_gram_ring = false, no_diag_split = false, no_xcd_swizzle = false,
-       no_mfma_project = false, plan_debug = false, no_i8_gram = false, no_marg_gemm = false, no_i8_diag = false, no_i8_factor = false, no_i8_rowvecs = false, no_grad_gemm = false, no_i8_dense = false, no_i8_fallback = false, no_bf16x3 = false, no_planes = false, no_fp16_planes = false, planes8 = false, no_spec_rowmax = false, no_multi_planes = false;
+       no_mfma_project = false, plan_debug = false, no_i8_gram = false, no_marg_gemm = false, no_i8_diag = false, no_i8_factor = false, no_i8_rowvecs = false, no_grad_gemm = false, no_i8_dense = false, no_i8_fallback = false, no_bf16x3 = false, no_planes = false, no_fp16_planes = false, planes8 = false, no_spec_rowmax = false, no_multi_planes = false, no_downdate_lds = false;
   int wave_split = 0;     // waves per regressor of the wave kernel: 0 = router, else 1 | 2 | 4
   int chain_batch = 0;    // regressors per shared launch at D > 128: 0 = as many as the workspace holds
   int i8_probe_min = 0;   // int8 route: batches beyond this many regressors start with a probe slice; 0 = kI8ProbeMin
@@ -78,6 +79,7 @@ struct BlrOptions {
     if (!strcmp(key, "NO_FP16_PLANES")) return flag(no_fp16_planes);
     if (!strcmp(key, "PLANES8")) return flag(planes8);
     if (!strcmp(key, "NO_I8_FALLBACK")) return flag(no_i8_fallback);
+    if (!strcmp(key, "NO_DOWNDATE_LDS")) return flag(no_downdate_lds);  // blr_downdate_factor_*: the global-memory kernel at every D
     long v = 0;
     if (!strcmp(key, "WAVE_SPLIT")) {
       if (!on) { wave_split = 0; return 0; }
@@ -126,7 +128,7 @@ struct BlrOptions {
     // boolean flags: a variable that is set -- even to the empty string -- switches the flag on
     for (const char* k : {"NO_LDSDMA", "NO_WAVE_KERNEL", "NO_GRAM_RING", "NO_DIAG_SPLIT", "NO_XCD_SWIZZLE", "NO_MFMA_PROJECT", "PLAN_DEBUG",
                           "NO_I8_GRAM", "NO_MARG_GEMM", "NO_GRAD_GEMM", "NO_I8_DIAG", "NO_I8_FACTOR", "NO_I8_ROWVECS", "NO_I8_DENSE", "NO_I8_FALLBACK", "NO_BF16X3",
-                          "NO_PLANES", "NO_FP16_PLANES", "PLANES8", "NO_SPEC_ROWMAX", "NO_MULTI_PLANES"}) {
+                          "NO_PLANES", "NO_FP16_PLANES", "PLANES8", "NO_SPEC_ROWMAX", "NO_MULTI_PLANES", "NO_DOWNDATE_LDS"}) {
       const std::string name = std::string("BLR_MI355X_") + k;
       if (const char* v = getenv(name.c_str())) (void)set(k, *v ? v : "1");
     }
@@ -3314,6 +3316,122 @@ int update_factor(blr_handle* h, int memspace, int layout, int64_t B, int64_t D,
   return 0;
 }
 
+// ---- rank-k downdate of a resident state (blr_downdate.hpp) -----------------------------------------------------------
+constexpr size_t kDowndateWorkspace = (size_t)2 << 30;  // bound of the global route's per-chunk workspace (at least one regressor)
+
+template <typename T>
+int downdate_launch(blr_handle* h, const SweepArgs<T>& a0, int64_t B) {
+  const int D = a0.D;
+  if (D <= kDowndateLdsMaxD && !h->opt.no_downdate_lds) {
+    const int lds = downdate_lds_bytes<T>(D);
+    { const int rc_lds = set_lds_once(h, reinterpret_cast<const void*>(downdate_lds_kernel<T>), (size_t)lds); if (rc_lds) return rc_lds; }
+    hipLaunchKernelGGL(downdate_lds_kernel<T>, dim3((unsigned)B), dim3(kThreads), lds, h->stream, a0);
+    HIP_TRY(h, hipGetLastError());
+    return 0;
+  }
+  // global route: chunks of regressors, each with a row-major copy of its factor and the per-observation vectors
+  const size_t item = sizeof(T), vec = ((size_t)D * item + 255) & ~(size_t)255, mat = ((size_t)D * D * item + 255) & ~(size_t)255;
+  const size_t per = mat + 3 * vec + 4 * sizeof(double) + sizeof(int);
+  const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(B, (int64_t)(kDowndateWorkspace / per)));
+  const size_t off_v = (size_t)chunk * mat, off_sc = off_v + 3 * (size_t)chunk * vec, off_st = off_sc + (size_t)chunk * 4 * sizeof(double);
+  int rc = ensure_ws(h, off_st + (size_t)chunk * sizeof(int) + 256);
+  if (rc) return rc;
+  char* base = reinterpret_cast<char*>(h->ws);
+  DowndateWs<T> w{};
+  w.W = reinterpret_cast<T*>(base);
+  w.strideW = (int64_t)(mat / item);
+  w.stridev = (int64_t)(vec / item);
+  w.u = reinterpret_cast<T*>(base + off_v);
+  w.cs = w.u + chunk * w.stridev;
+  w.sn = w.cs + chunk * w.stridev;
+  w.sc = reinterpret_cast<double*>(base + off_sc);
+  w.st = reinterpret_cast<int*>(base + off_st);
+  const int nt = (D + kDdTile - 1) / kDdTile;
+  const int solve_lds = downdate_g_solve_lds<T>(D), finish_lds = downdate_g_finish_lds<T>(D);
+  { const int rc_lds = set_lds_once(h, reinterpret_cast<const void*>(downdate_g_solve_kernel<T>), (size_t)solve_lds); if (rc_lds) return rc_lds; }
+  { const int rc_lds = set_lds_once(h, reinterpret_cast<const void*>(downdate_g_finish_kernel<T>), (size_t)finish_lds); if (rc_lds) return rc_lds; }
+  for (int64_t b0 = 0; b0 < B; b0 += chunk) {
+    const unsigned nb = (unsigned)std::min<int64_t>(chunk, B - b0);
+    SweepArgs<T> a = a0;
+    a.X += b0 * a.strideX; a.y += b0 * a.stridey; a.s += b0 * a.strides;
+    a.mw += b0 * a.stridemw; a.Tf += b0 * a.strideT;
+    if (a.logpdf) a.logpdf += b0;
+    a.info += b0;
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(downdate_g_copy_kernel<T, true>), dim3(nb, (unsigned)(nt * nt)), dim3(kThreads), 0, h->stream, a, w);
+    hipLaunchKernelGGL(downdate_g_prep_kernel<T>, dim3(nb), dim3(kThreads), 0, h->stream, a, w);
+    for (int i = 0; i < a.k; ++i) {
+      hipLaunchKernelGGL(downdate_g_solve_kernel<T>, dim3(nb), dim3(kThreads), solve_lds, h->stream, a, w, i);
+      hipLaunchKernelGGL(downdate_g_apply_kernel<T>, dim3(nb, (unsigned)((D + 1 + kThreads - 1) / kThreads)), dim3(kThreads), 0, h->stream, a, w);
+    }
+    hipLaunchKernelGGL(downdate_g_finish_kernel<T>, dim3(nb), dim3(kThreads), finish_lds, h->stream, a, w);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(downdate_g_copy_kernel<T, false>), dim3(nb, (unsigned)(nt * nt)), dim3(kThreads), 0, h->stream, a, w);
+    HIP_TRY(h, hipGetLastError());
+  }
+  return 0;
+}
+
+template <typename T>
+int downdate_factor(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t k, const T* X, int64_t ldx,
+                    int64_t strideX, const T* y, int64_t stridey, int noise_kind, const T* s, int64_t strides, T* mw,
+                    int64_t stridemw, T* Tf, int64_t ldt, int64_t strideT, double* logpdf, int32_t* info) {
+  if (!h) return -1;
+  h->err.clear();
+  if (memspace != BLR_MEM_HOST && memspace != BLR_MEM_DEVICE) return bad_arg(h, 2, "memspace");
+  if (layout != BLR_LAYOUT_COLVECS && layout != BLR_LAYOUT_ROWVECS) return bad_arg(h, 3, "unknown layout (reference :26-31)");
+  if (B < 0 || B > (1 << 30)) return bad_arg(h, 4, "B out of range (0..2^30)");
+  if (D < 1 || D > 8192) return bad_arg(h, 5, "D out of range (1..8192)");
+  if (k < 0 || k > (1 << 30)) return bad_arg(h, 6, "k out of range (0..2^30)");
+  if (B == 0) return 0;
+  if (k > 0 && !X) return bad_arg(h, 7, "X is NULL");
+  if (layout == BLR_LAYOUT_COLVECS ? ldx < D : ldx < std::max<int64_t>(k, 1)) return bad_arg(h, 8, "ldx too small");
+  if (strideX < 0) return bad_arg(h, 9, "strideX < 0");
+  if (k > 0 && !y) return bad_arg(h, 10, "y is NULL (reference :74 length check)");
+  if (stridey < 0) return bad_arg(h, 11, "stridey < 0");
+  if (noise_kind != BLR_NOISE_ISOTROPIC && noise_kind != BLR_NOISE_DIAGONAL) return bad_arg(h, 12, "noise_kind (dense noise is not downdated)");
+  if (!s) return bad_arg(h, 13, "s is NULL");
+  if (strides < 0) return bad_arg(h, 14, "strides < 0");
+  if (!mw) return bad_arg(h, 15, "mw is NULL");
+  if (B > 1 && stridemw < D) return bad_arg(h, 16, "stridemw < D");
+  if (!Tf) return bad_arg(h, 17, "T is NULL");
+  if (ldt < D) return bad_arg(h, 18, "ldt < D");
+  if (B > 1 && strideT < (int64_t)mat_extent(D, D, ldt)) return bad_arg(h, 19, "strideT too small");
+  if (!info) return bad_arg(h, 21, "info is NULL");
+  HIP_TRY(h, hipSetDevice(h->device));
+  SweepArgs<T> a{};
+  a.ldx = ldx; a.strideX = strideX; a.layout = layout; a.stridey = stridey; a.strides = strides; a.noise_kind = noise_kind;
+  a.stridemw = stridemw; a.ldt = ldt; a.strideT = strideT; a.D = (int)D; a.k = (int)k;
+  if (memspace == BLR_MEM_DEVICE) {
+    a.X = X; a.y = y; a.s = s; a.mw = mw; a.Tf = Tf; a.logpdf = logpdf; a.info = info;
+    if (k == 0) { if (!a.X) a.X = mw; if (!a.y) a.y = mw; }
+    int rc = downdate_launch<T>(h, a, B);
+    if (rc) return rc;
+    if (!h->async) HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return 0;
+  }
+  Staging guard(h);
+  const size_t x_one = layout == BLR_LAYOUT_COLVECS ? mat_extent(D, k, ldx) : mat_extent(k, D, ldx);
+  const size_t s_one = noise_kind == BLR_NOISE_DIAGONAL ? (size_t)k : 1;
+  const size_t n_mw = extent(B, stridemw, (size_t)D), n_T = extent(B, strideT, mat_extent(D, D, ldt));
+  int rc;
+  const T *dmw = nullptr, *dT = nullptr;
+  if ((rc = stage_in(h, X, extent(B, strideX, x_one), &a.X))) return rc;
+  if ((rc = stage_in(h, y, extent(B, stridey, (size_t)k), &a.y))) return rc;
+  if ((rc = stage_in(h, s, extent(B, strides, s_one), &a.s))) return rc;
+  if ((rc = stage_in(h, (const T*)mw, n_mw, &dmw))) return rc;
+  if ((rc = stage_in(h, (const T*)Tf, n_T, &dT))) return rc;
+  a.mw = const_cast<T*>(dmw); a.Tf = const_cast<T*>(dT);
+  if ((rc = stage_out_alloc(h, logpdf, (size_t)B, &a.logpdf))) return rc;
+  if ((rc = stage_out_alloc(h, info, (size_t)B, &a.info))) return rc;
+  if (k == 0) { if (!a.X) a.X = a.mw; if (!a.y) a.y = a.mw; }
+  if ((rc = downdate_launch<T>(h, a, B))) return rc;
+  HIP_TRY(h, hipMemcpyAsync(mw, a.mw, n_mw * sizeof(T), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(Tf, a.Tf, n_T * sizeof(T), hipMemcpyDeviceToHost, h->stream));
+  if (logpdf) HIP_TRY(h, hipMemcpyAsync(logpdf, a.logpdf, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(info, a.info, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  return 0;
+}
+
 }  // namespace
 
 // =======================================================================================================
@@ -3549,6 +3667,13 @@ int blr_timer_stop(blr_handle* h, float* elapsed_ms) {
                               double* logpdf, int32_t* info) {                                                       \
     return update_factor<T>(h, memspace, layout, B, D, k, X, ldx, strideX, y, stridey, noise_kind, s, strides, mw,   \
                             stridemw, Tf, ldt, strideT, logpdf, info);                                               \
+  }                                                                                                                 \
+  int blr_downdate_factor_##SUF(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t k,           \
+                                const T* X, int64_t ldx, int64_t strideX, const T* y, int64_t stridey,              \
+                                int noise_kind, const T* s, int64_t strides, T* mw, int64_t stridemw, T* Tf,        \
+                                int64_t ldt, int64_t strideT, double* logpdf, int32_t* info) {                      \
+    return downdate_factor<T>(h, memspace, layout, B, D, k, X, ldx, strideX, y, stridey, noise_kind, s, strides,    \
+                              mw, stridemw, Tf, ldt, strideT, logpdf, info);                                         \
   }                                                                                                                 \
   int blr_posterior_##SUF(blr_handle* h, int layout, int64_t D, int64_t N, const T* X, int64_t ldx, const T* y,     \
                           int noise_kind, const T* s, int prior_kind, const T* mw, const T* Lw, int64_t ldl,        \

@@ -650,6 +650,15 @@ class ResidentPosterior:
         lp2 = st.condition(X2, S2, y2)                         # log p(y2 | y1); state now = posterior given y1 and y2
         f12 = st.regressor()                                   # BayesianLinearRegressor(mw, PDMat(T))
 
+    `forget` is the inverse of `condition` (blr_downdate_factor_*): it removes observations the state contains and returns
+    their log density given the data that remains -- a sliding window over a stream, retraction of bad records, and the
+    leave-k-out predictive density:
+
+        st = ResidentPosterior(posterior(f(X[:, :W], S), y[:W]))   # window of the first W observations
+        for t in range(W, N):
+            st.condition(X[:, t:t+1], S, y[t:t+1])                 # the newest observation in
+            lp_old = st.forget(X[:, t-W:t-W+1], S, y[t-W:t-W+1])   # the oldest out: log p(y_old | the window without it)
+
     The state is created by the library (a Diagonal or dense prior precision is factorised on the device -- reference :78, the
     failing leading minor comes back as PosDefException(info) exactly as from `posterior`), lives in device buffers owned
     through blr_device_alloc and is only copied back by `regressor()`.  A BasisFunctionRegressor keeps its basis: `condition`
@@ -734,6 +743,41 @@ class ResidentPosterior:
             d_info = dev(np.zeros(1, dtype=np.int32))
             h.update_factor(dtype, _abi.MEM_DEVICE, layout, 1, D, k, dX, ldx, 0, dev(y), 0, noise_kind, dev(s), 0, self._mw.ptr, 0,
                             self._T.ptr, max(D, 1), 0, d_lp, d_info)
+            lp = np.zeros(1, dtype=np.float64)
+            info = np.zeros(1, dtype=np.int32)
+            h.memcpy_d2h(lp, d_lp)
+            h.memcpy_d2h(info, d_info)
+        finally:
+            for b in temps:
+                b.free()
+        if info[0] != 0:
+            raise _abi.PosDefException(int(info[0]))
+        return float(lp[0])
+
+    def forget(self, x, Sy, y):
+        """In-place DOWNDATE: removes the observations (x, Sy, y), which the state must contain; returns log p(y | the data that
+        remains) -- at one observation its leave-one-out predictive density.  A removal that would leave a precision that is not
+        positive definite raises PosDefException(info) (include/blr_mi355x.h blr_downdate_factor_*) and leaves the state as it
+        was."""
+        dtype, h, D = self.dtype, self._h, self.D
+        temps = []
+
+        def dev(a):
+            temps.append(_DeviceBuffer.of(h, a))
+            return temps[-1].ptr
+
+        try:
+            dX, layout, ldx, k = self._inputs(x, dev, temps)
+            y = np.ascontiguousarray(y, dtype=dtype)
+            if y.shape != (k,):
+                raise ValueError("length(y) != number of inputs")  # reference :74
+            s, noise_kind = _noise(Sy, k, dtype)
+            if noise_kind == _abi.NOISE_DENSE:
+                raise NotImplementedError("ResidentPosterior.forget takes scalar or diagonal noise (whiten a dense block first)")
+            d_lp = dev(np.zeros(1, dtype=np.float64))
+            d_info = dev(np.zeros(1, dtype=np.int32))
+            h.downdate_factor(dtype, _abi.MEM_DEVICE, layout, 1, D, k, dX, ldx, 0, dev(y), 0, noise_kind, dev(s), 0, self._mw.ptr, 0,
+                              self._T.ptr, max(D, 1), 0, d_lp, d_info)
             lp = np.zeros(1, dtype=np.float64)
             info = np.zeros(1, dtype=np.int32)
             h.memcpy_d2h(lp, d_lp)

@@ -75,7 +75,7 @@ int blr_reset_stream(blr_handle* h);              /* back to the handle's own (n
 int blr_set_async(blr_handle* h, int async);      /* 1: DEVICE-memspace calls return after enqueue       */
 int blr_synchronize(blr_handle* h);
 /* Run-time switches of the handle (A/B measurements and tests; the defaults are the measured best).  `key` is one of NO_LDSDMA,
- * NO_WAVE_KERNEL, NO_GRAM_RING, NO_DIAG_SPLIT, NO_XCD_SWIZZLE, NO_MFMA_PROJECT, NO_I8_GRAM, NO_I8_DIAG, NO_I8_FACTOR, NO_I8_ROWVECS, NO_I8_DENSE, NO_I8_FALLBACK, NO_BF16X3, NO_PLANES, NO_FP16_PLANES, PLANES8, NO_SPEC_ROWMAX, NO_MULTI_PLANES, NO_MARG_GEMM, NO_GRAD_GEMM, PLAN_DEBUG (flags: any non-empty value = on),
+ * NO_WAVE_KERNEL, NO_GRAM_RING, NO_DIAG_SPLIT, NO_XCD_SWIZZLE, NO_MFMA_PROJECT, NO_I8_GRAM, NO_I8_DIAG, NO_I8_FACTOR, NO_I8_ROWVECS, NO_I8_DENSE, NO_I8_FALLBACK, NO_BF16X3, NO_PLANES, NO_FP16_PLANES, PLANES8, NO_SPEC_ROWMAX, NO_MULTI_PLANES, NO_MARG_GEMM, NO_GRAD_GEMM, NO_DOWNDATE_LDS, PLAN_DEBUG (flags: any non-empty value = on),
  * WAVE_SPLIT = 1|2|4, CHAIN_BATCH = 1..128, CHAIN_WS_MB, I8_PROBE_MIN = 256..2^20, I8_GROUPS = 6|7, SWEEP = always|never|auto, GRAM_SPLITS = "o,d[,nlong]" (README.md);
  * a "BLR_MI355X_" prefix is accepted.  value NULL or "" restores the built-in default.  The environment variables
  * BLR_MI355X_<KEY> are read ONCE, by blr_create -- no entry point reads the environment.  -> 0, or -2 / -3 (unknown key /
@@ -425,6 +425,35 @@ int blr_update_factor_f32(blr_handle* h, int memspace, int layout, int64_t B, in
                           int64_t ldx, int64_t strideX, const float* y, int64_t stridey, int noise_kind, const float* s,
                           int64_t strides, float* mw, int64_t stridemw, float* T, int64_t ldt, int64_t strideT,
                           double* logpdf, int32_t* info);
+
+/* ---- rank-k DOWNDATE of a resident posterior state: forget observations --------------------------------------------
+ * Undoes: reference test/bayesian_linear_regression.jl:49-70 ("repeated conditioning"): the inverse of blr_update_factor_*.
+ * Reports: src/bayesian_linear_regression.jl:55-58 (logpdf), for the REMOVED data given the data that remains.
+ * Arguments exactly as blr_update_factor_* (memspace, layout, B, D, k, X / ldx / strideX, y / stridey, noise_kind / s /
+ * strides, mw / stridemw, T / ldt / strideT, logpdf, info; a stride of 0 shares an input).  If the state (mw, T) is the
+ * posterior given a data set that contains the k observations (X, y, s), it becomes, IN PLACE, the posterior without them:
+ * T''T' = T'T - X S^-1 X' (T' upper with a positive diagonal) and T''T' mw' = T'T mw - X S^-1 y.
+ * logpdf[B] (may be NULL) = log p(y_k | state after the call), in double: at k = 1 the exact leave-one-out predictive density;
+ * update(X, y) followed by downdate(X, y) reports the same number twice, up to rounding.
+ * info[B], checked in this order: T has a non-positive diagonal entry j (the update's code, and it wins), else s_i is not
+ * positive -> i, else removing an observation leaves a precision that is not positive definite -> j, the leading minor of
+ * that precision which fails, at the first observation (in order) whose removal fails.  On any info != 0 the state is
+ * bit-for-bit untouched and logpdf is NaN.
+ * Limits: 1 <= D <= 8192, any k >= 0 (k = 0 is a no-op), isotropic or diagonal noise (dense noise: argument error), host or
+ * device memspace; an async handle returns after enqueue, as for the update.  Results are bit-reproducible and do not depend
+ * on B or on a regressor's position in the batch.
+ * Kernels (csrc/blr_downdate.hpp): per observation a forward solve, then D rotations applied column by column
+ * (LINPACK dchdd), O(k D^2).  D <= 128: one workgroup per regressor with [T | u] in LDS; larger D: a row-major workspace copy
+ * of the state in global memory, the rotations spread over several workgroups per regressor.  Option NO_DOWNDATE_LDS
+ * (blr_set_option / BLR_MI355X_NO_DOWNDATE_LDS) forces the global-memory kernel at D <= 128. */
+int blr_downdate_factor_f64(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t k, const double* X,
+                            int64_t ldx, int64_t strideX, const double* y, int64_t stridey, int noise_kind, const double* s,
+                            int64_t strides, double* mw, int64_t stridemw, double* T, int64_t ldt, int64_t strideT,
+                            double* logpdf, int32_t* info);
+int blr_downdate_factor_f32(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t k, const float* X,
+                            int64_t ldx, int64_t strideX, const float* y, int64_t stridey, int noise_kind, const float* s,
+                            int64_t strides, float* mw, int64_t stridemw, float* T, int64_t ldt, int64_t strideT,
+                            double* logpdf, int32_t* info);
 
 /* ---- sharded log-evidence: fixed-order sum of logpdf[B] on the device ----------
  * Deterministic (no float atomics): the same bits for the same B regardless of launch geometry.

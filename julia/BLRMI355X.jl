@@ -813,6 +813,36 @@ function update_factor!(mw::DeviceArray{T}, Tf::DeviceArray{T}, lp::DeviceArray{
 end
 
 """
+    downdate_factor!(mw, T, logpdf, info, X, y, s; D, k, B, isotropic)
+
+The inverse of `update_factor!`: remove k observations from each of B device-resident posterior states IN PLACE (a sliding
+window, retracted records), undoing the "repeated conditioning" of reference `test/bayesian_linear_regression.jl:49-70`.
+Operands exactly as for `update_factor!`.  `logpdf[b]` = log p(y_b | state after the call), the density of the removed data
+given what remains (reference `src/bayesian_linear_regression.jl:55-58`; at k = 1 the leave-one-out density).  info[b] > 0:
+a bad factor, a bad variance, or a removal that leaves no positive definite precision; that state is left untouched.
+"""
+function downdate_factor!(mw::DeviceArray{T}, Tf::DeviceArray{T}, lp::DeviceArray{Float64}, info::DeviceArray{Int32},
+                          X::DeviceArray{T}, y::DeviceArray{T}, s::DeviceArray{T}; D::Int, k::Int, B::Int, isotropic::Bool) where {T<:Elt}
+    h = handle()
+    nk = isotropic ? ISOTROPIC : DIAGONALN
+    rc = if T === Float64
+        ccall((:blr_downdate_factor_f64, LIB), Cint,
+              (Ptr{Cvoid}, Cint, Cint, Int64, Int64, Int64, Ptr{T}, Int64, Int64, Ptr{T}, Int64, Cint, Ptr{T}, Int64, Ptr{T}, Int64,
+               Ptr{T}, Int64, Int64, Ptr{Cdouble}, Ptr{Int32}),
+              h, MEM_DEVICE, COLVECS, B, D, k, X.ptr, D, D * k, y.ptr, k, nk, s.ptr, isotropic ? 0 : k, mw.ptr, D, Tf.ptr, D, D * D,
+              lp.ptr, info.ptr)
+    else
+        ccall((:blr_downdate_factor_f32, LIB), Cint,
+              (Ptr{Cvoid}, Cint, Cint, Int64, Int64, Int64, Ptr{T}, Int64, Int64, Ptr{T}, Int64, Cint, Ptr{T}, Int64, Ptr{T}, Int64,
+               Ptr{T}, Int64, Int64, Ptr{Cdouble}, Ptr{Int32}),
+              h, MEM_DEVICE, COLVECS, B, D, k, X.ptr, D, D * k, y.ptr, k, nk, s.ptr, isotropic ? 0 : k, mw.ptr, D, Tf.ptr, D, D * D,
+              lp.ptr, info.ptr)
+    end
+    check(h, rc)
+    return nothing
+end
+
+"""
     rand_batched!(Y, W, info, X, mw, Tf, Z1, Z2; D, N, S, B, shared_x=false, s=nothing)
 
 Draws from B device-resident states, the step that closes a Thompson-sampling loop around `update_factor!` on `DeviceArray`s:
