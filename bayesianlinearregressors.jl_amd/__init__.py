@@ -14,6 +14,7 @@ from .regressor import (
     ColVecs,
     Diagonal,
     FiniteGP,
+    LOO,
     Normal,
     PDMat,
     RandomFourierFeatures,
@@ -26,6 +27,8 @@ from .regressor import (
     logpdf_and_gradient,
     logpdf_columns,
     logpdf_map,
+    loo,
+    loo_map,
     marginals,
     mean,
     mean_and_cov,
@@ -44,4 +47,5 @@ __all__ = [
     "logpdf", "rand", "mean", "std", "cov", "var", "BayesianLinearRegressor", "marginals", "posterior",
     "BasisFunctionRegressor", "ColVecs", "RowVecs", "Diagonal", "Symmetric", "PDMat", "Normal", "FiniteGP",
     "BLRFunctionSample", "RandomFourierFeatures", "mean_and_var", "mean_and_cov", "rand_b", "rand_and_pullback", "evaluate", "logpdf_columns", "logpdf_and_gradient", "logpdf_map", "posterior_map", "rand_map", "BLRError", "PosDefException", "ResidentPosterior",
+    "LOO", "loo", "loo_map",
 ]

@@ -79,6 +79,9 @@ for _suf in ("f64", "f32"):
     _SIGS[f"blr_update_factor_{_suf}"] = (
         [_H, _int, _int, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _int, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _vp], _int)
     _SIGS[f"blr_downdate_factor_{_suf}"] = _SIGS[f"blr_update_factor_{_suf}"]  # the same signature
+    _SIGS[f"blr_loo_batched_{_suf}"] = (
+        [_H, _int, _int, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _int, _vp, _i64, _vp, _i64, _vp, _i64, _i64,
+         _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp], _int)
     _SIGS[f"blr_posterior_{_suf}"] = (
         [_H, _int, _i64, _i64, _vp, _i64, _vp, _int, _vp, _int, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp], _int)
     _SIGS[f"blr_marginals_batched_{_suf}"] = (
@@ -227,7 +230,8 @@ class Handle:
         return self.lib.blr_last_route(self._h).decode()
 
     def get_stat(self, key):
-        """Counter of this handle: "i8_regressors", "i8_handed_back", "planes_redone", "workspace_bytes" (blr_get_stat)."""
+        """Counter of this handle: "i8_regressors", "i8_handed_back", "planes_redone", "loo_degenerate", "workspace_bytes"
+        (blr_get_stat)."""
         v = _i64()
         self.check(self.lib.blr_get_stat(self._h, str(key).encode(), C.byref(v)))
         return int(v.value)
@@ -299,6 +303,15 @@ class Handle:
         fn = getattr(self.lib, f"blr_downdate_factor_{suffix(dtype)}")
         return self.check(fn(self._h, memspace, layout, B, D, k, _ptr(X), ldx, strideX, _ptr(y), stridey, noise_kind, _ptr(s),
                              strides, _ptr(mw), stridemw, _ptr(T), ldt, strideT, _ptr(logpdf), _ptr(info)))
+
+    def loo(self, dtype, memspace, layout, B, D, N, X, ldx, strideX, y, stridey, noise_kind, s, strides, mw, stridemw, T, ldt,
+            strideT, loo_mean, stride_lm, loo_var, stride_lv, loo_logpdf, stride_ll, loo_total, info):
+        """Exact leave-one-out predictives of the observations the states (mw, T) contain; include/blr_mi355x.h
+        blr_loo_batched_*."""
+        fn = getattr(self.lib, f"blr_loo_batched_{suffix(dtype)}")
+        return self.check(fn(self._h, memspace, layout, B, D, N, _ptr(X), ldx, strideX, _ptr(y), stridey, noise_kind, _ptr(s),
+                             strides, _ptr(mw), stridemw, _ptr(T), ldt, strideT, _ptr(loo_mean), stride_lm, _ptr(loo_var),
+                             stride_lv, _ptr(loo_logpdf), stride_ll, _ptr(loo_total), _ptr(info)))
 
     def posterior(self, dtype, layout, D, N, X, ldx, y, noise_kind, s, prior_kind, mw, Lw, ldl, mw_post, T_post, ldt,
                   Lw_post, ldlp, logpdf):

@@ -159,7 +159,10 @@ struct blr_handle {
   size_t aux_bytes = 0;
   char* i8side = nullptr;      // grow-only: what the int8 route prepares per call (y / sqrt(s), 1 / sqrt(s), ... -- launch_fused_i8); a buffer of
   size_t i8side_bytes = 0;     // its own because logpdf_multi carves ITS temporaries from `aux` around a nested update that may take that route
-  // counters behind blr_get_stat: [0] regressors the int8 route handed back to the fp64 kernel (cumulative); [8 + 2 k + {0, 1}]:
+  char* loo_ws = nullptr;      // grow-only: chunk of mean / latent variance / logpdf of blr_loo_batched_* (the marginal routes it calls
+  size_t loo_ws_bytes = 0;     // use ws and aux themselves)
+  // counters behind blr_get_stat: [0] regressors the int8 route handed back to the fp64 kernel (cumulative); [3] degenerate
+  // leverages of blr_loo_batched_* (cumulative); [8 + 2 k + {0, 1}]:
   // hand-backs of slice k of the current call (two banks, alternating), read by the NEXT slice's launch (launch_fused_i8)
   unsigned long long* stats_dev = nullptr;
   unsigned long long i8_attempted = 0;   // regressors sent down the int8 route (host count)
@@ -3432,6 +3435,180 @@ int downdate_factor(blr_handle* h, int memspace, int layout, int64_t B, int64_t 
   return 0;
 }
 
+// ---- exact leave-one-out predictives of a state's observations (blr_loo.hpp) -------------------------------------------------
+constexpr size_t kLooWorkspace = (size_t)256 << 20;  // bound of the per-chunk intermediates (at least one regressor)
+
+int ensure_loo_ws(blr_handle* h, size_t bytes) {
+  if (bytes <= h->loo_ws_bytes) return 0;
+  if (h->loo_ws) {
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, hipFree(h->loo_ws));
+    h->loo_ws = nullptr;
+    h->loo_ws_bytes = 0;
+  }
+  HIP_TRY(h, hipMalloc((void**)&h->loo_ws, bytes));
+  h->loo_ws_bytes = bytes;
+  return 0;
+}
+
+// device operands; l carries y, s, the three outputs and info (global regressor indexing)
+template <typename T>
+int loo_launch(blr_handle* h, int layout, int64_t B, int64_t D, int64_t N, const T* X, int64_t ldx, int64_t strideX, LooArgs<T> l,
+               const T* mw, int64_t stridemw, const T* Tf, int64_t ldt, int64_t strideT, double* total) {
+  using G = MargGemmCfg<T>;
+  using TC = TrsmCfg<T>;
+  int rc;
+  if ((rc = ensure_stats(h))) return rc;
+  l.degenerate = h->stats_dev + 3;
+  int32_t* const info = const_cast<int32_t*>(l.info);
+  for (int64_t b0 = 0; b0 < B; b0 += 65535)
+    hipLaunchKernelGGL(loo_check_kernel<T>, dim3((unsigned)std::min<int64_t>(65535, B - b0)), dim3(kThreads), 0, h->stream, Tf + b0 * strideT,
+                       ldt, strideT, (int)D, l.s + b0 * l.strides, l.strides, l.noise_kind, (int)N, info + b0);
+  HIP_TRY(h, hipGetLastError());
+  // the route follows from the shape, as the marginals' does: the fused product stream at D = 128
+  const bool rowv = layout == BLR_LAYOUT_ROWVECS;
+  const bool fused = N >= 64 && D == kPB && !h->opt.no_marg_gemm &&
+                     (rowv || ((ldx % Mfma<T>::VEC) == 0 && ((uintptr_t)X % 16) == 0 && ((strideX * (int64_t)sizeof(T)) % 16) == 0));
+  const bool ll_ws = total && !l.ll;  // the totals need the log densities somewhere
+  const size_t item = sizeof(T), row = ((size_t)N * item + 255) & ~(size_t)255, row_ll = ((size_t)N * sizeof(double) + 255) & ~(size_t)255;
+  const size_t per = (fused ? 0 : 2 * row) + (ll_ws ? row_ll : 0) + sizeof(int32_t);
+  int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(B, 65535), (int64_t)(kLooWorkspace / per)));
+  if (fused) chunk = std::min<int64_t>(chunk, ((int64_t)256 << 20) / (G::IMG_ELEMS * (int64_t)sizeof(T)));
+  const size_t off_var = (size_t)chunk * row, off_ll = fused ? 0 : 2 * (size_t)chunk * row;
+  const size_t off_zero = off_ll + (ll_ws ? (size_t)chunk * row_ll : 0), off_inf = off_zero + 256;
+  if (N > 0 && (rc = ensure_loo_ws(h, off_inf + (size_t)chunk * sizeof(int32_t) + 256))) return rc;
+  char* const ws = h->loo_ws;
+  const int64_t ldw = (int64_t)(row / item);
+  if (N > 0 && !fused) HIP_TRY(h, hipMemsetAsync(ws + off_zero, 0, sizeof(T), h->stream));  // the composed route's zero noise
+  if (N > 0 && fused) {
+    if ((rc = ensure_aux(h, (size_t)chunk * G::IMG_ELEMS * sizeof(T)))) return rc;
+    if ((rc = set_lds_once(h, reinterpret_cast<const void*>(marg_image_kernel<T>), (size_t)TC::LDS_BYTES))) return rc;
+    void (*const kern)(LooGemmArgs<T>, const T*) = rowv ? marginals_gemm_kernel<T, true, LooGemmArgs<T>> : marginals_gemm_kernel<T, false, LooGemmArgs<T>>;
+    if ((rc = set_lds_once(h, reinterpret_cast<const void*>(kern), (size_t)G::LDS_BYTES))) return rc;
+  }
+  T* const img = reinterpret_cast<T*>(h->aux);
+  const int64_t ldll = ll_ws ? (int64_t)(row_ll / sizeof(double)) : l.stride_ll;
+  for (int64_t b0 = 0; N > 0 && b0 < B; b0 += chunk) {
+    const int64_t nb = std::min<int64_t>(chunk, B - b0);
+    LooArgs<T> lc = l;
+    if (ll_ws) { lc.ll = reinterpret_cast<double*>(ws + off_ll) - b0 * ldll; lc.stride_ll = ldll; }  // (indexed by the global regressor)
+    if (fused) {
+      // M = T^-T once per regressor, then the product stream with the epilogue at the store (blr_marginals.hpp)
+      hipLaunchKernelGGL(marg_image_kernel<T>, dim3((unsigned)nb, 2), dim3(kThreads), TC::LDS_BYTES, h->stream, Tf, ldt, strideT, (int)D,
+                         img - b0 * G::IMG_ELEMS, l.info, (int)b0);
+      LooGemmArgs<T> a{};
+      a.X = X; a.ldx = ldx; a.strideX = strideX; a.s = l.s; a.strides = l.strides; a.mw = mw; a.stridemw = stridemw;
+      a.info = l.info; a.layout = layout; a.noise_kind = l.noise_kind; a.prior_kind = BLR_PRIOR_UPPER_FACTOR;
+      a.D = (int)D; a.N = (int)N; a.B = (int)B; a.reg0 = (int)b0;
+      const int64_t ntiles = (N + 15) / 16;
+      const int64_t per_reg = std::max<int64_t>(1, std::min<int64_t>((ntiles + 15) / 16, (2 * (int64_t)h->cus + nb - 1) / nb));
+      a.l = lc;
+      void (*const kern)(LooGemmArgs<T>, const T*) = rowv ? marginals_gemm_kernel<T, true, LooGemmArgs<T>> : marginals_gemm_kernel<T, false, LooGemmArgs<T>>;
+      hipLaunchKernelGGL(kern, dim3((unsigned)per_reg, (unsigned)nb), dim3(kThreads), G::LDS_BYTES, h->stream, a,
+                         (const T*)(img - b0 * G::IMG_ELEMS));
+    } else {
+      // mean and LATENT variance (zero noise) by whichever marginal route the shape takes, then the epilogue
+      T* const mean = reinterpret_cast<T*>(ws);
+      T* const var = reinterpret_cast<T*>(ws + off_var);
+      const bool was_async = h->async;
+      h->async = true;  // (no drain between the two halves)
+      rc = marginals_batched<T>(h, BLR_MEM_DEVICE, layout, nb, D, N, X + b0 * strideX, ldx, strideX, BLR_NOISE_ISOTROPIC,
+                                reinterpret_cast<const T*>(ws + off_zero), 0, BLR_PRIOR_UPPER_FACTOR, mw + b0 * stridemw, stridemw,
+                                Tf + b0 * strideT, ldt, strideT, mean, ldw, var, ldw, reinterpret_cast<int32_t*>(ws + off_inf));
+      h->async = was_async;
+      if (rc) return rc;
+      h->err.clear();
+      const int64_t gx = std::max<int64_t>(1, std::min<int64_t>((N + kThreads - 1) / kThreads, (4 * (int64_t)h->cus + nb - 1) / nb));
+      hipLaunchKernelGGL(loo_finish_kernel<T>, dim3((unsigned)gx, (unsigned)nb), dim3(kThreads), 0, h->stream, lc, (const T*)mean,
+                         (const T*)var, ldw, (int)b0);
+    }
+    if (total)
+      hipLaunchKernelGGL(loo_total_kernel, dim3((unsigned)nb), dim3(kThreads), 0, h->stream, (const double*)lc.ll, lc.stride_ll, (int)N,
+                         total, l.info, (int)b0);
+    HIP_TRY(h, hipGetLastError());
+  }
+  if (N == 0 && total) {  // an empty sum, for the regressors whose state passed the check
+    for (int64_t b0 = 0; b0 < B; b0 += 65535)
+      hipLaunchKernelGGL(loo_total_kernel, dim3((unsigned)std::min<int64_t>(65535, B - b0)), dim3(kThreads), 0, h->stream,
+                         (const double*)nullptr, (int64_t)0, 0, total, l.info, (int)b0);
+    HIP_TRY(h, hipGetLastError());
+  }
+  return 0;
+}
+
+template <typename T>
+int loo_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t N, const T* X, int64_t ldx, int64_t strideX,
+                const T* y, int64_t stridey, int noise_kind, const T* s, int64_t strides, const T* mw, int64_t stridemw, const T* Tf,
+                int64_t ldt, int64_t strideT, T* loo_mean, int64_t stride_lm, T* loo_var, int64_t stride_lv, double* loo_logpdf,
+                int64_t stride_ll, double* loo_total, int32_t* info) {
+  // (the argument checks come before the handle's: they need no device)
+  if (h) h->err.clear();
+  if (memspace != BLR_MEM_HOST && memspace != BLR_MEM_DEVICE) return bad_arg(h, 2, "memspace");
+  if (layout != BLR_LAYOUT_COLVECS && layout != BLR_LAYOUT_ROWVECS) return bad_arg(h, 3, "unknown layout (reference :26-31)");
+  if (B < 0 || B > (1 << 30)) return bad_arg(h, 4, "B out of range (0..2^30)");
+  if (D < 1 || D > kMaxLargeD) return bad_arg(h, 5, "D out of range (1..8192)");
+  if (N < 0 || N > (1 << 30)) return bad_arg(h, 6, "N out of range (0..2^30)");
+  if (N > 0 && !X) return bad_arg(h, 7, "X is NULL");
+  if (layout == BLR_LAYOUT_COLVECS ? ldx < D : ldx < std::max<int64_t>(N, 1)) return bad_arg(h, 8, "ldx too small");
+  if (strideX < 0) return bad_arg(h, 9, "strideX < 0");
+  if (N > 0 && !y) return bad_arg(h, 10, "y is NULL (reference :74 length check)");
+  if (stridey < 0) return bad_arg(h, 11, "stridey < 0");
+  if (noise_kind != BLR_NOISE_ISOTROPIC && noise_kind != BLR_NOISE_DIAGONAL)
+    return bad_arg(h, 12, "noise_kind (dense noise has no single-observation LOO: that is a block LOO)");
+  if (N > 0 && !s) return bad_arg(h, 13, "s is NULL");
+  if (strides < 0) return bad_arg(h, 14, "strides < 0");
+  if (!mw) return bad_arg(h, 15, "mw is NULL");
+  if (B > 1 && stridemw < D) return bad_arg(h, 16, "stridemw < D");
+  if (!Tf) return bad_arg(h, 17, "T is NULL");
+  if (ldt < D) return bad_arg(h, 18, "ldt < D");
+  if (B > 1 && strideT < (int64_t)mat_extent(D, D, ldt)) return bad_arg(h, 19, "strideT too small");
+  if (loo_mean && B > 1 && stride_lm < N) return bad_arg(h, 21, "stride_lm < N");
+  if (loo_var && B > 1 && stride_lv < N) return bad_arg(h, 23, "stride_lv < N");
+  if (loo_logpdf && B > 1 && stride_ll < N) return bad_arg(h, 25, "stride_ll < N");
+  if (!info) return bad_arg(h, 27, "info is NULL");
+  if (!h) return -1;
+  if (B == 0) return 0;
+  HIP_TRY(h, hipSetDevice(h->device));
+  LooArgs<T> l{};
+  l.stridey = stridey; l.strides = strides; l.noise_kind = noise_kind; l.stride_lm = stride_lm; l.stride_lv = stride_lv;
+  l.stride_ll = stride_ll; l.N = (int)N;
+  if (memspace == BLR_MEM_DEVICE) {
+    l.y = y; l.s = s; l.lm = loo_mean; l.lv = loo_var; l.ll = loo_logpdf; l.info = info;
+    const int rc = loo_launch<T>(h, layout, B, D, N, X, ldx, strideX, l, mw, stridemw, Tf, ldt, strideT, loo_total);
+    if (rc) return rc;
+    if (!h->async) HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return 0;
+  }
+  Staging guard(h);
+  const size_t x_one = N == 0 ? 0 : (layout == BLR_LAYOUT_COLVECS ? mat_extent(D, N, ldx) : mat_extent(N, D, ldx));
+  const size_t s_one = N == 0 ? 0 : (noise_kind == BLR_NOISE_DIAGONAL ? (size_t)N : 1);
+  const size_t n_out = N == 0 ? 0 : (size_t)N;
+  int rc;
+  const T *dX = nullptr, *dy = nullptr, *ds = nullptr, *dmw = nullptr, *dT = nullptr;
+  T *dlm = nullptr, *dlv = nullptr;
+  double *dll = nullptr, *dtot = nullptr;
+  int32_t* dinfo = nullptr;
+  if ((rc = stage_in(h, X, x_one ? extent(B, strideX, x_one) : 0, &dX))) return rc;
+  if ((rc = stage_in(h, y, n_out ? extent(B, stridey, n_out) : 0, &dy))) return rc;
+  if ((rc = stage_in(h, s, s_one ? extent(B, strides, s_one) : 0, &ds))) return rc;
+  if ((rc = stage_in(h, mw, extent(B, stridemw, (size_t)D), &dmw))) return rc;
+  if ((rc = stage_in(h, Tf, extent(B, strideT, mat_extent(D, D, ldt)), &dT))) return rc;
+  if ((rc = stage_out_alloc(h, loo_mean, n_out ? extent(B, stride_lm, n_out) : 0, &dlm))) return rc;
+  if ((rc = stage_out_alloc(h, loo_var, n_out ? extent(B, stride_lv, n_out) : 0, &dlv))) return rc;
+  if ((rc = stage_out_alloc(h, loo_logpdf, n_out ? extent(B, stride_ll, n_out) : 0, &dll))) return rc;
+  if ((rc = stage_out_alloc(h, loo_total, (size_t)B, &dtot))) return rc;
+  if ((rc = stage_out_alloc(h, info, (size_t)B, &dinfo))) return rc;
+  l.y = dy; l.s = ds; l.lm = dlm; l.lv = dlv; l.ll = dll; l.info = dinfo;
+  if ((rc = loo_launch<T>(h, layout, B, D, N, dX, ldx, strideX, l, dmw, stridemw, dT, ldt, strideT, dtot))) return rc;
+  if (dlm) HIP_TRY(h, hipMemcpyAsync(loo_mean, dlm, extent(B, stride_lm, n_out) * sizeof(T), hipMemcpyDeviceToHost, h->stream));
+  if (dlv) HIP_TRY(h, hipMemcpyAsync(loo_var, dlv, extent(B, stride_lv, n_out) * sizeof(T), hipMemcpyDeviceToHost, h->stream));
+  if (dll) HIP_TRY(h, hipMemcpyAsync(loo_logpdf, dll, extent(B, stride_ll, n_out) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (dtot) HIP_TRY(h, hipMemcpyAsync(loo_total, dtot, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(info, dinfo, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  return 0;
+}
+
 }  // namespace
 
 // =======================================================================================================
@@ -3477,6 +3654,7 @@ int blr_destroy(blr_handle* h) {
   if (h->feat) (void)hipFree(h->feat);
   if (h->aux) (void)hipFree(h->aux);
   if (h->i8side) (void)hipFree(h->i8side);
+  if (h->loo_ws) (void)hipFree(h->loo_ws);
   if (h->stats_dev) (void)hipFree(h->stats_dev);
   if (h->xchg) (void)hipFree(h->xchg);
   if (h->ticket) (void)hipFree(h->ticket);
@@ -3498,6 +3676,7 @@ int blr_release_workspace(blr_handle* h) {
   if (h->feat) { HIP_TRY(h, hipFree(h->feat)); h->feat = nullptr; h->feat_bytes = 0; }
   if (h->aux) { HIP_TRY(h, hipFree(h->aux)); h->aux = nullptr; h->aux_bytes = 0; }
   if (h->i8side) { HIP_TRY(h, hipFree(h->i8side)); h->i8side = nullptr; h->i8side_bytes = 0; }
+  if (h->loo_ws) { HIP_TRY(h, hipFree(h->loo_ws)); h->loo_ws = nullptr; h->loo_ws_bytes = 0; }
   return 0;
 }
 
@@ -3585,7 +3764,20 @@ int blr_get_stat(blr_handle* h, const char* key, int64_t* value) {
     *value = (int64_t)v;
     return 0;
   }
-  if (!strcmp(key, "workspace_bytes")) { *value = (int64_t)(h->ws_bytes + h->feat_bytes + h->aux_bytes + h->i8side_bytes + h->xchg_bytes); return 0; }
+  if (!strcmp(key, "loo_degenerate")) {  // observations blr_loo_batched_* gave NaN: 1 - h_n <= 0 or not finite (cumulative)
+    unsigned long long v = 0;
+    if (h->stats_dev) {
+      HIP_TRY(h, hipSetDevice(h->device));
+      HIP_TRY(h, hipMemcpyAsync(&v, h->stats_dev + 3, sizeof(v), hipMemcpyDeviceToHost, h->stream));
+      HIP_TRY(h, hipStreamSynchronize(h->stream));
+    }
+    *value = (int64_t)v;
+    return 0;
+  }
+  if (!strcmp(key, "workspace_bytes")) {
+    *value = (int64_t)(h->ws_bytes + h->feat_bytes + h->aux_bytes + h->i8side_bytes + h->xchg_bytes + h->loo_ws_bytes);
+    return 0;
+  }
   return bad_arg(h, 2, "unknown statistic");
 }
 int blr_reset_stats(blr_handle* h) {
@@ -3593,7 +3785,7 @@ int blr_reset_stats(blr_handle* h) {
   h->err.clear();
   if (h->stats_dev) {  // (device counter first: a failure must not leave the two counters apart)
     HIP_TRY(h, hipSetDevice(h->device));
-    HIP_TRY(h, hipMemsetAsync(h->stats_dev, 0, 3 * sizeof(unsigned long long), h->stream));  // (total, planes made twice, the last call's base)
+    HIP_TRY(h, hipMemsetAsync(h->stats_dev, 0, 4 * sizeof(unsigned long long), h->stream));  // (total, planes made twice, the last call's base, LOO degenerate)
   }
   h->i8_attempted = 0;
   return 0;
@@ -3674,6 +3866,15 @@ int blr_timer_stop(blr_handle* h, float* elapsed_ms) {
                                 int64_t ldt, int64_t strideT, double* logpdf, int32_t* info) {                      \
     return downdate_factor<T>(h, memspace, layout, B, D, k, X, ldx, strideX, y, stridey, noise_kind, s, strides,    \
                               mw, stridemw, Tf, ldt, strideT, logpdf, info);                                         \
+  }                                                                                                                 \
+  int blr_loo_batched_##SUF(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t N, const T* X,  \
+                            int64_t ldx, int64_t strideX, const T* y, int64_t stridey, int noise_kind, const T* s, \
+                            int64_t strides, const T* mw, int64_t stridemw, const T* Tf, int64_t ldt,               \
+                            int64_t strideT, T* loo_mean, int64_t stride_lm, T* loo_var, int64_t stride_lv,         \
+                            double* loo_logpdf, int64_t stride_ll, double* loo_total, int32_t* info) {              \
+    return loo_batched<T>(h, memspace, layout, B, D, N, X, ldx, strideX, y, stridey, noise_kind, s, strides, mw,     \
+                          stridemw, Tf, ldt, strideT, loo_mean, stride_lm, loo_var, stride_lv, loo_logpdf,          \
+                          stride_ll, loo_total, info);                                                             \
   }                                                                                                                 \
   int blr_posterior_##SUF(blr_handle* h, int layout, int64_t D, int64_t N, const T* X, int64_t ldx, const T* y,     \
                           int noise_kind, const T* s, int prior_kind, const T* mw, const T* Lw, int64_t ldl,        \

@@ -334,9 +334,9 @@ __global__ __launch_bounds__(kThreads) void rff_features_kernel(const T* __restr
 
 // ---- fixed-order sum of logpdf[B] --------------------------------------------------------
 // One workgroup.  Thread t sums elements t, t+256, ... in order, then a fixed tree over threads: the
-// result depends only on B and the values, never on launch geometry.
-__global__ __launch_bounds__(kThreads) void logpdf_sum_kernel(const double* __restrict__ lp, int64_t B,
-                                                              double* __restrict__ total) {
+// result depends only on B and the values, never on launch geometry.  The body is a block function (the leave-one-out
+// totals of blr_loo.hpp run it once per regressor); the sum is valid in thread 0.
+__device__ __forceinline__ double fixed_order_sum(const double* __restrict__ lp, int64_t B) {
   __shared__ double part[kThreads];
   const int tid = threadIdx.x;
   double v = 0.0;
@@ -355,7 +355,12 @@ __global__ __launch_bounds__(kThreads) void logpdf_sum_kernel(const double* __re
     if (tid < m) part[tid] += part[tid + m];
     __syncthreads();
   }
-  if (tid == 0) *total = part[0];
+  return tid == 0 ? part[0] : 0.0;
+}
+__global__ __launch_bounds__(kThreads) void logpdf_sum_kernel(const double* __restrict__ lp, int64_t B,
+                                                              double* __restrict__ total) {
+  const double t = fixed_order_sum(lp, B);
+  if (threadIdx.x == 0) *total = t;
 }
 
 }  // namespace blr

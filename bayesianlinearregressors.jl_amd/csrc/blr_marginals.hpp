@@ -16,6 +16,7 @@
 // were inverted explicitly already.  Routed for D = 128, aligned ColVecs or RowVecs (scalar loads); everything else stays on the sweep kernel.
 #pragma once
 #include "blr_large.hpp"
+#include "blr_loo.hpp"
 
 namespace blr {
 
@@ -140,8 +141,16 @@ __global__ __launch_bounds__(kThreads) void marg_image_kernel(const T* __restric
 // ---- the stream ------------------------------------------------------------------------------------------------------------------
 // ROWV: RowVecs inputs (N x D column-major): the same registers filled by scalar loads -- for a fixed d the sixteen inputs of a tile
 // are consecutive (128 bytes in fp64), so the loads stay whole cache lines; twice (fp64) / four times (fp32) the load instructions.
-template <typename T, bool ROWV = false>
-__global__ __launch_bounds__(kThreads, 2) void marginals_gemm_kernel(MarginalArgs<T> a, const T* __restrict__ img_all) {
+// A = LooGemmArgs<T>: the leave-one-out form (blr_loo.hpp, blr_loo_batched_*) -- the tile loads also fetch y_n, and the LOO epilogue
+// replaces the mean / var stores (mean and latent variance straight from the registers; a.mean / a.var are not used).  A
+// compile-time flag on the kernel itself: the body stays one, and the code of the MarginalArgs instantiations stays as it was.
+template <typename T>
+struct LooGemmArgs : MarginalArgs<T> {
+  LooArgs<T> l;
+};
+template <typename T, bool ROWV = false, typename A = MarginalArgs<T>>
+__global__ __launch_bounds__(kThreads, 2) void marginals_gemm_kernel(A a, const T* __restrict__ img_all) {
+  constexpr bool LOO = !std::is_same<A, MarginalArgs<T>>::value;
   using G = MargGemmCfg<T>;
   using acc4 = typename Mfma<T>::acc4;
   constexpr int VEC = G::VEC, NL = G::NLOAD;
@@ -170,7 +179,10 @@ __global__ __launch_bounds__(kThreads, 2) void marginals_gemm_kernel(MarginalArg
   //  entries of ITS input's z, so the row sum needs two shuffles instead of sixteen DPP adds, and noise value and store are one
   //  coalesced access of the sixteen g = 0 lanes instead of four scattered ones)
   T sv, sn;
-  auto fetch = [&](int tile, vecT (&dst)[NL], T& sd) {
+  T yv = T(0), yn = T(0);
+  const BLR_GLOBAL T* yg = nullptr;
+  if constexpr (LOO) yg = as_global(a.l.y + (int64_t)reg * a.l.stridey);
+  auto fetch = [&](int tile, vecT (&dst)[NL], T& sd, T& yd) {
     const int n = min(tile * 16 + li, N - 1);  // (inputs past the end re-read the last one; never stored)
     if constexpr (ROWV) {
       const BLR_GLOBAL T* p = X + n + (int64_t)(VEC * g) * a.ldx;
@@ -183,9 +195,10 @@ __global__ __launch_bounds__(kThreads, 2) void marginals_gemm_kernel(MarginalArg
 #pragma unroll
       for (int u = 0; u < NL; ++u) dst[u] = p[4 * u];  // (4 VEC elements = 4 vectors apart)
     }
-    sd = (diag_noise && a.var) ? s[n] : s_iso;
+    sd = (diag_noise && (LOO || a.var)) ? s[n] : s_iso;
+    if constexpr (LOO) yd = yg[n];
   };
-  if (t0 < ntiles) fetch(t0, av, sv);
+  if (t0 < ntiles) fetch(t0, av, sv, yv);
   // the image and the prior mean: once per workgroup
   {
     const BLR_GLOBAL vecT* src = reinterpret_cast<const BLR_GLOBAL vecT*>(as_global(img_all + (int64_t)reg * G::IMG_ELEMS));
@@ -194,12 +207,13 @@ __global__ __launch_bounds__(kThreads, 2) void marginals_gemm_kernel(MarginalArg
     if (tid < kPB) mwl[tid] = mw[tid];
   }
   __syncthreads();
+  int ndeg = 0;  // (LOO: degenerate leverages this lane stored)
   for (int tile = t0; tile < ntiles; tile += tstep) {
     const bool more = tile + tstep < ntiles;
-    if (more) fetch(tile + tstep, an, sn);  // in flight during this tile's 144 MFMAs
+    if (more) fetch(tile + tstep, an, sn, yn);  // in flight during this tile's 144 MFMAs
     // mean_n = x_n'mw (:33): this lane's 4 VEC NL / ... entries, then over the four lane groups of an input
     T macc = T(0);
-    if (a.mean) {
+    if (LOO || a.mean) {
 #pragma unroll
       for (int u = 0; u < NL; ++u)
 #pragma unroll
@@ -209,7 +223,7 @@ __global__ __launch_bounds__(kThreads, 2) void marginals_gemm_kernel(MarginalArg
     }
     // z = x'M column block by column block; var_n = |z_n|^2
     T sq = T(0);
-    if (a.var) {
+    if (LOO || a.var) {
 #pragma unroll
       for (int J = 0; J < 8; ++J) {
         acc4 acc = {T(0), T(0), T(0), T(0)};
@@ -224,15 +238,24 @@ __global__ __launch_bounds__(kThreads, 2) void marginals_gemm_kernel(MarginalArg
     }
     const int n0 = tile * 16;
     if (g == 0 && n0 + li < N) {
-      if (a.mean) a.mean[(int64_t)reg * a.stridemean + n0 + li] = macc;
-      if (a.var) a.var[(int64_t)reg * a.stridevar + n0 + li] = sq + sv;
+      if constexpr (LOO) {
+        // (fenced: scheduled into the next tile's product, the epilogue's double log and divisions spilled 268 registers)
+        __builtin_amdgcn_sched_barrier(0);
+        if (!loo_store(a.l, reg, n0 + li, (double)yv, (double)macc, (double)sq, (double)sv)) ++ndeg;
+        __builtin_amdgcn_sched_barrier(0);
+      } else {
+        if (a.mean) a.mean[(int64_t)reg * a.stridemean + n0 + li] = macc;
+        if (a.var) a.var[(int64_t)reg * a.stridevar + n0 + li] = sq + sv;
+      }
     }
     if (more) {
 #pragma unroll
       for (int u = 0; u < NL; ++u) av[u] = an[u];
       sv = sn;
+      if constexpr (LOO) yv = yn;
     }
   }
+  if constexpr (LOO) loo_count(ndeg, a.l.degenerate);
 }
 
 // ---- the evidence gradient at D = 128 as two products with the same inverse (reference :55-58 through its reverse rule) ------------------

@@ -16,6 +16,7 @@ CPU fallback.
 from __future__ import annotations
 
 import math
+from collections import namedtuple
 
 import numpy as np
 
@@ -25,6 +26,7 @@ __all__ = [
     "ColVecs", "RowVecs", "Diagonal", "Symmetric", "PDMat", "Normal", "RandomFourierFeatures",
     "BayesianLinearRegressor", "BasisFunctionRegressor", "BLRFunctionSample", "FiniteGP",
     "mean", "var", "cov", "std", "mean_and_var", "mean_and_cov", "marginals", "rand", "rand_b", "logpdf", "posterior",
+    "LOO", "loo", "loo_map",
 ]
 
 
@@ -613,6 +615,125 @@ def posterior_map(fxs, ys):
     return posts
 
 
+LOO = namedtuple("LOO", ["mean", "var", "logpdf", "total"])
+LOO.__doc__ = """Exact leave-one-out predictives: per observation n the predictive of y_n given all the other data (mean and var,
+var including the noise as var(fx) does, in the element type; logpdf in float64) and total = sum_n logpdf_n (the LOO-CV
+score).  An observation whose leverage is within rounding of 1 has NaN entries (blr_get_stat "loo_degenerate")."""
+
+
+def _loo_problem(fx, y, dtype):
+    """(X, layout, ldx, D, N, y, s, noise_kind, mw, Lw, prior_kind, ldl) of one finite regressor, validated as `_fused` does."""
+    fb = _to_finite_blr(fx)
+    X, layout, ldx, D, N = _x_layout(fb.x, dtype)
+    y = np.ascontiguousarray(y, dtype=dtype)
+    if y.ndim != 1:
+        raise ValueError("y must be a vector")
+    if y.shape[0] != N:
+        raise ValueError("length(y) != size(fx.x.X, 2)")  # reference :74
+    s, noise_kind = _noise(fb.Sy, N, dtype)
+    if noise_kind == _abi.NOISE_DENSE:
+        raise NotImplementedError("loo: with a dense noise covariance one observation is not independent of the rest (that is a "
+                                  "block leave-out); isotropic or diagonal noise only")
+    Lw, prior_kind, ldl = _prior(fb.f.Lw, D, dtype)
+    return X, layout, ldx, D, N, y, s, noise_kind, _mean_vector(fb.f.mw, D, dtype), Lw, prior_kind, ldl
+
+
+def _loo_call(h, dtype, layout, B, D, N, dX, ldx, strideX, dy, stridey, noise_kind, ds, strides, d_mw, stridemw, d_T, strideT, temps):
+    """blr_loo_batched_* on device operands -> (mean [B, N], var [B, N], logpdf [B, N], total [B], info [B]) on the host."""
+    item = np.dtype(dtype).itemsize
+    outs = [_DeviceBuffer(h, B * N * item), _DeviceBuffer(h, B * N * item), _DeviceBuffer(h, B * N * 8), _DeviceBuffer(h, B * 8),
+            _DeviceBuffer.of(h, np.zeros(B, dtype=np.int32))]
+    temps.extend(outs)
+    d_lm, d_lv, d_ll, d_tot, d_info = (b.ptr for b in outs)
+    h.loo(dtype, _abi.MEM_DEVICE, layout, B, D, N, dX, ldx, strideX, dy, stridey, noise_kind, ds, strides, d_mw, stridemw, d_T,
+          max(D, 1), strideT, d_lm, N, d_lv, N, d_ll, N, d_tot, d_info)
+    m, v = np.empty((B, N), dtype=dtype), np.empty((B, N), dtype=dtype)
+    lp, tot, info = np.empty((B, N), dtype=np.float64), np.empty(B, dtype=np.float64), np.zeros(B, dtype=np.int32)
+    for host, dptr in ((m, d_lm), (v, d_lv), (lp, d_ll), (tot, d_tot), (info, d_info)):
+        h.memcpy_d2h(host, dptr)
+    return m, v, lp, tot, info
+
+
+def _loo_batch(probs, dtype):
+    """LOO of equally shaped problems: their data staged once, blr_posterior_batched_* into device buffers (mw', T) -- any prior
+    kind, the usual routes -- then blr_loo_batched_* on the same device inputs.  Nothing D x D comes back to the host."""
+    X0, layout, ldx, D, N, _, _, noise_kind, _, _, prior_kind, ldl = probs[0]
+    nb, h, item = len(probs), _handle(), np.dtype(dtype).itemsize
+    Xb = np.stack([q[0].reshape(-1, order="A") for q in probs])
+    yb = np.stack([q[5] for q in probs])
+    sb = np.stack([q[6] for q in probs])
+    mwb = np.stack([q[8] for q in probs])
+    Lb = np.stack([q[9].reshape(-1, order="A") for q in probs])
+    temps = []
+
+    def dev(a):
+        temps.append(_DeviceBuffer.of(h, a))
+        return temps[-1].ptr
+
+    try:
+        dX, dy, ds = dev(Xb), dev(yb), dev(sb)
+        temps.extend([_DeviceBuffer(h, nb * D * item), _DeviceBuffer(h, nb * D * D * item)])
+        d_mwp, d_T = temps[-2].ptr, temps[-1].ptr
+        d_info = dev(np.zeros(nb, dtype=np.int32))
+        h.posterior_batched(dtype, _abi.MEM_DEVICE, layout, nb, D, N, dX, ldx, Xb.shape[1], dy, yb.shape[1], noise_kind, ds,
+                            sb.shape[1], prior_kind, dev(mwb), D, dev(Lb), ldl, Lb.shape[1], d_mwp, D, d_T, max(D, 1), D * D,
+                            None, max(D, 1), D * D, None, d_info)
+        info = np.zeros(nb, dtype=np.int32)
+        h.memcpy_d2h(info, d_info)
+        if not np.any(info):
+            m, v, lp, tot, info = _loo_call(h, dtype, layout, nb, D, N, dX, ldx, Xb.shape[1], dy, yb.shape[1], noise_kind, ds,
+                                            sb.shape[1], d_mwp, D, d_T, D * D, temps)
+    finally:
+        for b in temps:
+            b.free()
+    bad = np.flatnonzero(info)
+    if bad.size:
+        e = _abi.PosDefException(int(info[bad[0]]))
+        e.index = int(bad[0])
+        raise e
+    return [LOO(m[b], v[b], lp[b], float(tot[b])) for b in range(nb)]
+
+
+def loo(fx, y):
+    """Exact leave-one-out predictives of the observations y at fx.x (include/blr_mi355x.h blr_loo_batched_*): for every n the
+    predictive of y_n under posterior(fx without observation n) -- what a loop of forget / condition gives, from one marginal
+    pass over the inputs.  Returns LOO(mean, var, logpdf, total).  Dense noise raises NotImplementedError (a block LOO)."""
+    dtype = _dtype_of(fx.f.blr.mw if isinstance(fx.f, BasisFunctionRegressor) else fx.f.mw, y)
+    return _loo_batch([_loo_problem(fx, y, dtype)], dtype)[0]
+
+
+def loo_map(fxs, ys):
+    """[loo(fx, y) for fx, y in zip(fxs, ys)] in one posterior call and one LOO call for equally shaped problems (else one call
+    per problem, as `posterior_map`).  The first problem whose prior, noise or posterior is not positive definite raises
+    PosDefException with its position as ``index``."""
+    fxs, ys = list(fxs), list(ys)
+    if len(fxs) != len(ys):
+        raise ValueError("as many observation vectors as finite regressors are needed")
+    if not fxs:
+        return []
+    dtype = np.float32 if all(_dtype_of(fx.f.blr.mw if isinstance(fx.f, BasisFunctionRegressor) else fx.f.mw, y) == np.float32
+                              for fx, y in zip(fxs, ys)) else np.float64
+
+    def one_by_one(probs):
+        out = []
+        for i, q in enumerate(probs):
+            try:
+                out.append(_loo_batch([q], dtype)[0])
+            except _abi.PosDefException as e:
+                e.index = i
+                raise
+        return out
+
+    probs = [_loo_problem(fx, y, dtype) for fx, y in zip(fxs, ys)]
+    if any(isinstance(fx.f, BasisFunctionRegressor) and isinstance(fx.f.phi, RandomFourierFeatures) for fx in fxs):
+        return one_by_one(probs)
+    sig = {(q[0].shape, q[0].flags.f_contiguous, q[1], q[3], q[4], q[7], q[10],
+            isinstance((fx.f.blr if isinstance(fx.f, BasisFunctionRegressor) else fx.f).Lw, PDMat)) for q, fx in zip(probs, fxs)}
+    if len(sig) != 1 or probs[0][3] == 0 or probs[0][4] == 0:
+        return one_by_one(probs)
+    return _loo_batch(probs, dtype)
+
+
 class _DeviceBuffer:
     """device memory owned through the C ABI (blr_device_alloc): no GPU array library involved"""
 
@@ -788,6 +909,35 @@ class ResidentPosterior:
         if info[0] != 0:
             raise _abi.PosDefException(int(info[0]))
         return float(lp[0])
+
+    def loo(self, x, Sy, y):
+        """Exact leave-one-out predictives of the observations (x, Sy, y), which the caller vouches the state contains: for each
+        n what ``forget`` of observation n alone would report, without touching the state (blr_loo_batched_*, B = 1).  Returns
+        LOO(mean, var, logpdf, total); a state with a non-positive diagonal entry or a non-positive variance raises
+        PosDefException(info)."""
+        dtype, h, D = self.dtype, self._h, self.D
+        temps = []
+
+        def dev(a):
+            temps.append(_DeviceBuffer.of(h, a))
+            return temps[-1].ptr
+
+        try:
+            dX, layout, ldx, N = self._inputs(x, dev, temps)
+            y = np.ascontiguousarray(y, dtype=dtype)
+            if y.shape != (N,):
+                raise ValueError("length(y) != number of inputs")  # reference :74
+            s, noise_kind = _noise(Sy, N, dtype)
+            if noise_kind == _abi.NOISE_DENSE:
+                raise NotImplementedError("ResidentPosterior.loo takes scalar or diagonal noise (dense noise: a block leave-out)")
+            m, v, lp, tot, info = _loo_call(h, dtype, layout, 1, D, N, dX, ldx, 0, dev(y), 0, noise_kind, dev(s), 0, self._mw.ptr, 0,
+                                            self._T.ptr, 0, temps)
+        finally:
+            for b in temps:
+                b.free()
+        if info[0] != 0:
+            raise _abi.PosDefException(int(info[0]))
+        return LOO(m[0], v[0], lp[0], float(tot[0]))
 
     def rand(self, rng, x, S, Sy=None):
         """S draws at the inputs x from the resident state (N x S), without copying T to the host (blr_rand_batched_*, B = 1):

@@ -96,7 +96,8 @@ const char* blr_last_route(blr_handle* h);
  * SAMPLED row scales did not hold -- the operand planes of the Gram product are scaled per row by a power of two taken from the first 32
  * columns of every column chunk (doubled: an entry up to 16 x the sample's largest still fits); an entry beyond that sends the call
  * through the exact row maxima and the planes pass a second time (one more read of X; option NO_SPEC_ROWMAX = 1 always takes the exact
- * maxima: one more read of X on every call); "workspace_bytes" = device scratch the handle holds now.
+ * maxima: one more read of X on every call); "loo_degenerate" = observations blr_loo_batched_* gave NaN because their 1 - h_n was
+ * <= 0 or not finite (reading it synchronises the handle's stream); "workspace_bytes" = device scratch the handle holds now.
  * -> 0, -2 unknown key, -3 NULL value. */
 int blr_get_stat(blr_handle* h, const char* key, int64_t* value);
 int blr_reset_stats(blr_handle* h);
@@ -454,6 +455,40 @@ int blr_downdate_factor_f32(blr_handle* h, int memspace, int layout, int64_t B, 
                             int64_t ldx, int64_t strideX, const float* y, int64_t stridey, int noise_kind, const float* s,
                             int64_t strides, float* mw, int64_t stridemw, float* T, int64_t ldt, int64_t strideT,
                             double* logpdf, int32_t* info);
+
+/* ---- exact LEAVE-ONE-OUT predictives of the observations a posterior state contains -----------------------------------
+ * Replaces: a loop of blr_downdate_factor_* at k = 1 (then blr_update_factor_* to put the observation back) per observation,
+ * and reference src/bayesian_linear_regression.jl:55-58 (logpdf) applied to each held-out point given the rest.
+ * State (mw, T) as blr_posterior_batched_* writes it (mw_post, T_post) or a resident state holds it: T upper, only its upper
+ * triangle is read; NOT modified.  It must be conditioned on a data set that contains the N observations (X, y, s); the
+ * outputs are then, for every n, the predictive of y_n given everything else the state holds.  With A = T'T, mw' = mw:
+ *   sigma2_n = x_n'A^-1 x_n,  m_n = x_n'mw',  r_n = y_n - m_n,  1 - h_n = (s_n - sigma2_n) / s_n
+ *   loo_var_n = s_n / (1 - h_n)  (noise included, as var(fx) includes Sigma_y),  loo_mean_n = y_n - r_n / (1 - h_n)
+ *   loo_logpdf_n = -1/2 [log 2 pi + log s_n - log(1 - h_n) + r_n^2 / (s_n (1 - h_n))]   (double, whatever the element type)
+ *   loo_total[b] = sum_n loo_logpdf_n in a fixed order (the LOO-CV score).
+ * Any of loo_mean, loo_var, loo_logpdf, loo_total may be NULL.  sigma2_n and m_n are computed in the element type, the rest in
+ * double.  Results are bit-reproducible, independent of B and of a regressor's position in the batch; no float atomics.
+ * NaN rule: an observation whose 1 - h_n is <= 0 in floating point or not finite (the state does not contain it, or h_n is
+ * within rounding of 1) gets NaN in its three outputs (so loo_total is NaN) and is counted by blr_get_stat "loo_degenerate".
+ * info[B], checked in the update's and downdate's order: T has a non-positive diagonal entry j -> j, else s_i is not
+ * positive -> i; the outputs of such a regressor are left untouched.  The call returns 0 (negative on argument errors, which
+ * are checked before the handle).
+ * Limits: 1 <= D <= 8192, N >= 0 (N = 0: loo_total = 0), isotropic or diagonal noise (dense noise is an argument error: its
+ * "one observation" is a block), ColVecs or RowVecs, host or device memspace; an async handle only enqueues (device memspace).
+ * Kernels (csrc/blr_loo.hpp): one marginal pass.  D = 128, aligned ColVecs or RowVecs, N >= 64: the triangular
+ * inverse image and the product stream of blr_marginals_batched_* with the epilogue at the store; any other shape: the
+ * marginal routes with zero noise into handle workspace (chunks of regressors), then an epilogue kernel.
+ * _f32: X, y, s, mw, T, loo_mean, loo_var are float; loo_logpdf and loo_total stay double. */
+int blr_loo_batched_f64(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t N, const double* X,
+                        int64_t ldx, int64_t strideX, const double* y, int64_t stridey, int noise_kind, const double* s,
+                        int64_t strides, const double* mw, int64_t stridemw, const double* T, int64_t ldt, int64_t strideT,
+                        double* loo_mean, int64_t stride_lm, double* loo_var, int64_t stride_lv, double* loo_logpdf,
+                        int64_t stride_ll, double* loo_total, int32_t* info);
+int blr_loo_batched_f32(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t N, const float* X,
+                        int64_t ldx, int64_t strideX, const float* y, int64_t stridey, int noise_kind, const float* s,
+                        int64_t strides, const float* mw, int64_t stridemw, const float* T, int64_t ldt, int64_t strideT,
+                        float* loo_mean, int64_t stride_lm, float* loo_var, int64_t stride_lv, double* loo_logpdf,
+                        int64_t stride_ll, double* loo_total, int32_t* info);
 
 /* ---- sharded log-evidence: fixed-order sum of logpdf[B] on the device ----------
  * Deterministic (no float atomics): the same bits for the same B regardless of launch geometry.

@@ -843,6 +843,80 @@ function downdate_factor!(mw::DeviceArray{T}, Tf::DeviceArray{T}, lp::DeviceArra
 end
 
 """
+    loo!(lmean, lvar, llogpdf, total, info, X, y, s, mw, T; D, N, B, isotropic)
+
+Exact leave-one-out predictives of the N observations each of B device-resident states contains (`blr_loo_batched_*`): for
+every n the predictive of y_n given all the other data -- what a `downdate_factor!` of observation n alone (followed by an
+`update_factor!` to put it back) reports, and reference `src/bayesian_linear_regression.jl:55-58` applied to the held-out
+point -- from one marginal pass, the states untouched.  Operands as for `downdate_factor!` with k = N; lmean, lvar (element
+type) and llogpdf (Float64) are N×B or `nothing`, total (Float64, Σ_n llogpdf in a fixed order) B or `nothing`.  A
+leverage within rounding of 1 gives NaN (`get_stat("loo_degenerate")` counts them); info[b] > 0: a bad factor, else a bad
+variance, and that state's outputs are left untouched.
+"""
+function loo!(lm::Union{Nothing,DeviceArray{T}}, lv::Union{Nothing,DeviceArray{T}}, ll::Union{Nothing,DeviceArray{Float64}},
+              total::Union{Nothing,DeviceArray{Float64}}, info::DeviceArray{Int32}, X::DeviceArray{T}, y::DeviceArray{T},
+              s::DeviceArray{T}, mw::DeviceArray{T}, Tf::DeviceArray{T}; D::Int, N::Int, B::Int, isotropic::Bool) where {T<:Elt}
+    h = handle()
+    nk = isotropic ? ISOTROPIC : DIAGONALN
+    ptr(a) = a === nothing ? Ptr{T}(C_NULL) : a.ptr
+    dptr(a) = a === nothing ? Ptr{Cdouble}(C_NULL) : a.ptr
+    rc = if T === Float64
+        ccall((:blr_loo_batched_f64, LIB), Cint,
+              (Ptr{Cvoid}, Cint, Cint, Int64, Int64, Int64, Ptr{T}, Int64, Int64, Ptr{T}, Int64, Cint, Ptr{T}, Int64, Ptr{T}, Int64,
+               Ptr{T}, Int64, Int64, Ptr{T}, Int64, Ptr{T}, Int64, Ptr{Cdouble}, Int64, Ptr{Cdouble}, Ptr{Int32}),
+              h, MEM_DEVICE, COLVECS, B, D, N, X.ptr, D, D * N, y.ptr, N, nk, s.ptr, isotropic ? 0 : N, mw.ptr, D, Tf.ptr, D, D * D,
+              ptr(lm), N, ptr(lv), N, dptr(ll), N, dptr(total), info.ptr)
+    else
+        ccall((:blr_loo_batched_f32, LIB), Cint,
+              (Ptr{Cvoid}, Cint, Cint, Int64, Int64, Int64, Ptr{T}, Int64, Int64, Ptr{T}, Int64, Cint, Ptr{T}, Int64, Ptr{T}, Int64,
+               Ptr{T}, Int64, Int64, Ptr{T}, Int64, Ptr{T}, Int64, Ptr{Cdouble}, Int64, Ptr{Cdouble}, Ptr{Int32}),
+              h, MEM_DEVICE, COLVECS, B, D, N, X.ptr, D, D * N, y.ptr, N, nk, s.ptr, isotropic ? 0 : N, mw.ptr, D, Tf.ptr, D, D * D,
+              ptr(lm), N, ptr(lv), N, dptr(ll), N, dptr(total), info.ptr)
+    end
+    check(h, rc)
+    return nothing
+end
+
+"""
+    loo(fx, y) -> (mean, var, logpdf)
+
+Leave-one-out predictives of the observations y at fx.x: the posterior of `fused` (reference `:60-69`), then one
+`blr_loo_batched_*` call on it (host memspace) -- what a loop of `forget` / `condition` per observation gives.  var includes
+the noise, as `var(fx)` does; logpdf is Float64 (`sum(logpdf)` is the LOO-CV score).  Dense noise is not offloaded.
+"""
+function loo(fx::FiniteGP, y::AbstractVector{<:Real})
+    fb = to_blr(fx)
+    xl, nz = xlayout(fb.x), noise(fb.Σy)
+    (xl === nothing || nz === nothing || nz[2] == DENSEN) && throw(ArgumentError("loo: ColVecs / RowVecs inputs and isotropic or Diagonal noise"))
+    X, layout, ldx, D, N = xl
+    T = eltype(X)
+    r = fused(fb, y, true)
+    r === nothing && throw(ArgumentError("loo: the prior is not offloadable"))
+    _, mw′, Tp, _ = r
+    yv = convert(Vector{T}, y)
+    s, nk, _ = nz
+    lm, lv, ll = Vector{T}(undef, N), Vector{T}(undef, N), Vector{Float64}(undef, N)
+    total = Ref{Cdouble}(0.0); info = Ref{Int32}(0)
+    h = handle()
+    rc = GC.@preserve X yv s mw′ Tp lm lv ll begin
+        if T === Float64
+            ccall((:blr_loo_batched_f64, LIB), Cint,
+                  (Ptr{Cvoid}, Cint, Cint, Int64, Int64, Int64, Ptr{T}, Int64, Int64, Ptr{T}, Int64, Cint, Ptr{T}, Int64, Ptr{T}, Int64,
+                   Ptr{T}, Int64, Int64, Ptr{T}, Int64, Ptr{T}, Int64, Ptr{Cdouble}, Int64, Ref{Cdouble}, Ref{Int32}),
+                  h, MEM_HOST, layout, 1, D, N, X, ldx, 0, yv, 0, nk, s, 0, mw′, 0, Tp, D, 0, lm, N, lv, N, ll, N, total, info)
+        else
+            ccall((:blr_loo_batched_f32, LIB), Cint,
+                  (Ptr{Cvoid}, Cint, Cint, Int64, Int64, Int64, Ptr{T}, Int64, Int64, Ptr{T}, Int64, Cint, Ptr{T}, Int64, Ptr{T}, Int64,
+                   Ptr{T}, Int64, Int64, Ptr{T}, Int64, Ptr{T}, Int64, Ptr{Cdouble}, Int64, Ref{Cdouble}, Ref{Int32}),
+                  h, MEM_HOST, layout, 1, D, N, X, ldx, 0, yv, 0, nk, s, 0, mw′, 0, Tp, D, 0, lm, N, lv, N, ll, N, total, info)
+        end
+    end
+    check(h, rc)
+    check(h, info[])
+    return lm, lv, ll
+end
+
+"""
     rand_batched!(Y, W, info, X, mw, Tf, Z1, Z2; D, N, S, B, shared_x=false, s=nothing)
 
 Draws from B device-resident states, the step that closes a Thompson-sampling loop around `update_factor!` on `DeviceArray`s:
