@@ -236,6 +236,21 @@ int rccl_fail(blr_handle* h, ncclResult_t r, const char* what) {
 constexpr int kMaxSmallD = 128;
 constexpr int kMaxLargeD = 8192;
 
+// Dynamic LDS of planes_kernel: the chunk's r, sqrt(w) and mu (16 floats per k-block each), then for a basis its raw inputs --
+// the whole chunk's, padded to 8 input dimensions (xs_chunk), or one k-block's [Din][16].
+constexpr size_t planes_pass_lds(bool rff, bool xs_chunk, int din) {
+  return (size_t)(3 * 16 * kPlanesChunkKb + (rff ? (xs_chunk ? 8 * 16 * kPlanesChunkKb : din * 16) : 0)) * sizeof(float);
+}
+// blr_posterior_rff_f32 evaluates the basis inside the planes pass up to this input dimension: the largest whose pass fits in
+// 64 KiB of LDS.  A conservative choice, not the hardware's limit: a gfx950 workgroup may use up to 160 KiB (D_in 2368), and the
+// pass was measured to launch beyond 64 KiB without a raised attribute; 64 KiB is what HIP grants by default.
+// A larger D_in materialises the features (rff_features_kernel) and runs the planes Gram on them -- so do D_in 833 .. 2368,
+// which used to run fused (D_in >= 2369 failed to launch).
+constexpr int kRffFusedMaxDin = 832;
+static_assert(planes_pass_lds(true, true, 8) <= 65536 && planes_pass_lds(true, false, kRffFusedMaxDin) <= 65536 &&
+                  planes_pass_lds(true, false, kRffFusedMaxDin + 1) > 65536,
+              "kRffFusedMaxDin: the largest D_in whose planes pass fits in 64 KiB of LDS (the chosen cap)");
+
 int hip_fail(blr_handle* h, hipError_t e, const char* what) {
   if (h) {
     h->err = std::string(what) + ": " + hipGetErrorString(e);
@@ -734,11 +749,15 @@ int posterior_large_group(blr_handle* h, const PosteriorArgs<T>& a, int64_t reg0
   const bool rff = a.rff_Omega != nullptr;
   const bool planes = sizeof(T) == 4 && !h->opt.no_bf16x3 && !h->opt.no_planes && a.layout == LAYOUT_COLVECS && a.N > 0;
   if (rff && !planes) return hip_fail(h, hipErrorInvalidValue, "a basis that is not materialised needs the planes path");
+  if (rff && a.rff_Din > kRffFusedMaxDin) return hip_fail(h, hipErrorInvalidValue, "a basis of D_in > kRffFusedMaxDin must be materialised");
   h->route_i8_B = 0;
   const int NP = h->opt.no_fp16_planes ? 3 : 2;  // planes per operand: two fp16 (three products) or three bf16 (six)
   h->route = sizeof(T) == 8 ? "gram_tile_kernel<double>"
                             : (planes ? (NP == 2 ? (h->opt.planes8 ? "gram_planes_kernel<2>" : "gram_planes4_kernel") : "gram_planes_kernel<3>")
                                       : (bf3 ? "gram_tile_kernel<float, true>" : "gram_tile_kernel<float>"));  // (large-D pipeline: the Gram launch dominates; <float, true>: full tiles on the bf16 matrix cores)
+  if (rff)  // (the basis evaluated inside the planes pass: distinguishable from the same Gram kernel on materialised features)
+    h->route = NP == 2 ? (h->opt.planes8 ? "gram_planes_kernel<2> (basis in planes pass)" : "gram_planes4_kernel (basis in planes pass)")
+                       : "gram_planes_kernel<3> (basis in planes pass)";
   using LC = LargeCfg<T>;
   const int D = a.D, N = a.N;
   const int DP = (D + kPB - 1) / kPB * kPB, NC = DP / kPB;
@@ -1041,7 +1060,7 @@ int posterior_large_group(blr_handle* h, const PosteriorArgs<T>& a, int64_t reg0
       }
       // a basis of up to 8 input dimensions: the raw inputs of a workgroup's whole column chunk are staged once (blr_planes.hpp, xs_chunk)
       pa.xs_chunk = (rff && a.rff_Din <= 8) ? 1 : 0;
-      const size_t plds = (size_t)(3 * 16 * kPlanesChunkKb + (rff ? (pa.xs_chunk ? 8 * 16 * kPlanesChunkKb : a.rff_Din * 16) : 0)) * sizeof(float);
+      const size_t plds = planes_pass_lds(rff, pa.xs_chunk != 0, a.rff_Din);
       if (NP == 2) {  // the rows' power-of-two scales need (a bound of) the rows' largest entries first
         if (rff) {  // a basis: its bound
           hipLaunchKernelGGL(rowmax_kernel<true>, dim3(nbchunks, 1, G), dim3(kThreads), 0, h->stream, pa);
@@ -1067,6 +1086,7 @@ int posterior_large_group(blr_handle* h, const PosteriorArgs<T>& a, int64_t reg0
         if (rff) hipLaunchKernelGGL((planes_kernel<3, true>), dim3(nbchunks, NC, G), dim3(kThreads), plds, h->stream, pa);
         else hipLaunchKernelGGL((planes_kernel<3, false>), dim3(nbchunks, NC, G), dim3(kThreads), plds, h->stream, pa);
       }
+      HIP_TRY(h, hipGetLastError());  // (a failed planes launch leaves the last call's planes in the workspace: never a posterior from them)
       GramPlanesArgs ga{};
       ga.Xp = Xp; ga.NC = NCA; ga.NKB = NKB; ga.Gpart = Gpart; ga.ntiles = ntiles_g; ga.nsplit = nsplit;
       ga.s_iso = a.noise_kind == NOISE_DIAGONAL ? nullptr : s;
@@ -2794,9 +2814,10 @@ int posterior_rff(blr_handle* h, int memspace, int64_t Din, int64_t D, int64_t N
   if (ldo < Din) return bad_arg(h, 9, "ldo < Din");
   if (!phase) return bad_arg(h, 10, "phase is NULL");
   HIP_TRY(h, hipSetDevice(h->device));
-  // fp32 at D > 128: the basis is never materialised -- the planes pass of the large-D pipeline evaluates phi once per element and
-  // writes the bf16 planes of the Gram operands directly (blr_planes.hpp; reference src/basis_function_regression.jl:41 builds phi(x))
-  if (sizeof(T) == 4 && D > kMaxSmallD && N > 0 && !h->opt.no_planes && !h->opt.no_bf16x3) {
+  // fp32 at D > 128, D_in <= kRffFusedMaxDin: the basis is never materialised -- the planes pass of the large-D pipeline evaluates phi
+  // once per element and writes the bf16 planes of the Gram operands directly (blr_planes.hpp; reference
+  // src/basis_function_regression.jl:41 builds phi(x)).  A wider input materialises the features below (the planes Gram still runs on them).
+  if (sizeof(T) == 4 && D > kMaxSmallD && N > 0 && Din <= kRffFusedMaxDin && !h->opt.no_planes && !h->opt.no_bf16x3) {
     Staging guard(h);
     const T *Xd = Xin, *Od = Omega, *Pd = phase;
     const T *yd = y, *sd = s, *mwd = mw, *Lwd = Lw;

@@ -286,7 +286,9 @@ int blr_rand_batched_f32(blr_handle* h, int memspace, int layout, int64_t B, int
  *   Xin: Din x N column-major (ColVecs of the raw inputs), Omega: Din x D column-major, phase[D];
  *   Phi : D x N column-major (ldphi >= D).
  * blr_posterior_rff_* = features + fused inference in one call (Phi lives in the handle's workspace):
- * the remaining arguments are those of blr_posterior_batched_* with B = 1.
+ * the remaining arguments are those of blr_posterior_batched_* with B = 1.  fp32 at D > 128 with Din <= 832 evaluates
+ * the basis inside the Gram's operand pass (Phi never exists; blr_last_route ends in " (basis in planes pass)"); a wider
+ * input (a conservative cap: that pass then stays within 64 KiB of LDS), fp64 and D <= 128 materialise Phi first.
  */
 int blr_rff_features_f64(blr_handle* h, int memspace, int64_t Din, int64_t D, int64_t N,
                          const double* Xin, int64_t ldxin, const double* Omega, int64_t ldo, const double* phase,
