@@ -13,6 +13,7 @@ from .regressor import (
     BLRFunctionSample,
     ColVecs,
     Diagonal,
+    EvidenceGrid,
     FiniteGP,
     LOO,
     Normal,
@@ -26,6 +27,8 @@ from .regressor import (
     logpdf,
     logpdf_and_gradient,
     logpdf_columns,
+    logpdf_grid,
+    logpdf_grid_map,
     logpdf_map,
     loo,
     loo_map,
@@ -34,6 +37,7 @@ from .regressor import (
     mean_and_cov,
     mean_and_var,
     posterior,
+    posterior_best,
     posterior_map,
     rand,
     rand_and_pullback,
@@ -48,4 +52,5 @@ __all__ = [
     "BasisFunctionRegressor", "ColVecs", "RowVecs", "Diagonal", "Symmetric", "PDMat", "Normal", "FiniteGP",
     "BLRFunctionSample", "RandomFourierFeatures", "mean_and_var", "mean_and_cov", "rand_b", "rand_and_pullback", "evaluate", "logpdf_columns", "logpdf_and_gradient", "logpdf_map", "posterior_map", "rand_map", "BLRError", "PosDefException", "ResidentPosterior",
     "LOO", "loo", "loo_map",
+    "EvidenceGrid", "logpdf_grid", "posterior_best", "logpdf_grid_map",
 ]

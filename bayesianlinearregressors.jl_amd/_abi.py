@@ -82,6 +82,9 @@ for _suf in ("f64", "f32"):
     _SIGS[f"blr_loo_batched_{_suf}"] = (
         [_H, _int, _int, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _int, _vp, _i64, _vp, _i64, _vp, _i64, _i64,
          _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp], _int)
+    _SIGS[f"blr_logpdf_grid_{_suf}"] = (
+        [_H, _int, _int, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _int, _vp, _i64, _int, _vp, _i64, _vp, _i64, _i64,
+         _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _i64], _int)
     _SIGS[f"blr_posterior_{_suf}"] = (
         [_H, _int, _i64, _i64, _vp, _i64, _vp, _int, _vp, _int, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp], _int)
     _SIGS[f"blr_marginals_batched_{_suf}"] = (
@@ -312,6 +315,17 @@ class Handle:
         return self.check(fn(self._h, memspace, layout, B, D, N, _ptr(X), ldx, strideX, _ptr(y), stridey, noise_kind, _ptr(s),
                              strides, _ptr(mw), stridemw, _ptr(T), ldt, strideT, _ptr(loo_mean), stride_lm, _ptr(loo_var),
                              stride_lv, _ptr(loo_logpdf), stride_ll, _ptr(loo_total), _ptr(info)))
+
+    def logpdf_grid(self, dtype, memspace, layout, B, D, N, X, ldx, strideX, y, stridey, noise_kind, s, strides, prior_kind, mw,
+                    stridemw, Lw, ldl, strideLw, G, alpha, stride_alpha, tau, stride_tau, logpdf, stride_lp, best, mw_best,
+                    stride_mwbest, T_best, ldt, strideT, info, stride_info):
+        """Evidence of every regressor under G settings (Lw = alpha Lw, s = tau s) from one pass over X, the best setting and
+        its posterior; include/blr_mi355x.h blr_logpdf_grid_*."""
+        fn = getattr(self.lib, f"blr_logpdf_grid_{suffix(dtype)}")
+        return self.check(fn(self._h, memspace, layout, B, D, N, _ptr(X), ldx, strideX, _ptr(y), stridey, noise_kind, _ptr(s),
+                             strides, prior_kind, _ptr(mw), stridemw, _ptr(Lw), ldl, strideLw, G, _ptr(alpha), stride_alpha,
+                             _ptr(tau), stride_tau, _ptr(logpdf), stride_lp, _ptr(best), _ptr(mw_best), stride_mwbest,
+                             _ptr(T_best), ldt, strideT, _ptr(info), stride_info))
 
     def posterior(self, dtype, layout, D, N, X, ldx, y, noise_kind, s, prior_kind, mw, Lw, ldl, mw_post, T_post, ldt,
                   Lw_post, ldlp, logpdf):

@@ -30,6 +30,7 @@
 #include "blr_fused_i8.hpp"
 #include "blr_marginals.hpp"
 #include "blr_rand_batched.hpp"
+#include "blr_grid.hpp"
 
 using namespace blr;
 
@@ -3630,6 +3631,227 @@ int loo_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, i
   return 0;
 }
 
+// ---- evidence over a grid of (prior scale, noise scale) settings (blr_grid.hpp) --------------------------------------------------
+template <typename T, int NB, int MODE>
+int launch_grid_stats(blr_handle* h, const GridArgs<T>& a) {
+  using C = SmallCfg<T, NB>;
+  auto kern = grid_stats_kernel<T, NB, MODE>;
+  { const int rc = set_lds_once(h, reinterpret_cast<const void*>(kern), (size_t)C::LDS_BYTES); if (rc) return rc; }
+  hipLaunchKernelGGL(kern, dim3((unsigned)((int64_t)a.B * a.S)), dim3(kThreads), C::LDS_BYTES, h->stream, a);
+  HIP_TRY(h, hipGetLastError());
+  return 0;
+}
+
+// device operands, D <= 128: prior, statistics (+ reduce), settings, argmax, refit -- the same launches whatever B and G are
+template <typename T, int NB>
+int grid_small_nb(blr_handle* h, GridArgs<T> a, bool vec_ok) {
+  using C = SmallCfg<T, NB>;
+  constexpr int SZ = grid_stat_elems<T, NB>();
+  int rc;
+  size_t off = 0;
+  auto carve = [&](size_t bytes) { size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
+  const size_t nblk = (size_t)a.B * a.S;
+  const size_t o_st = carve(nblk * SZ * sizeof(T)), o_sc = carve(nblk * 2 * sizeof(double)), o_bad = carve(nblk * sizeof(int32_t));
+  const size_t o_pl = carve((size_t)a.B * sizeof(double)), o_pi = carve((size_t)a.B * sizeof(int32_t)), o_best = carve((size_t)a.B * sizeof(int64_t));
+  if ((rc = ensure_loo_ws(h, off))) return rc;
+  char* const ws = h->loo_ws;
+  a.stats = reinterpret_cast<T*>(ws + o_st); a.scal = reinterpret_cast<double*>(ws + o_sc); a.bad = reinterpret_cast<int32_t*>(ws + o_bad);
+  a.prior_logdet = reinterpret_cast<double*>(ws + o_pl); a.prior_info = reinterpret_cast<int32_t*>(ws + o_pi);
+  a.best = reinterpret_cast<int64_t*>(ws + o_best);
+  if ((rc = set_lds_once(h, reinterpret_cast<const void*>(grid_prior_kernel<T, NB>), (size_t)C::LDS_BYTES))) return rc;
+  if ((rc = set_lds_once(h, reinterpret_cast<const void*>(grid_eval_kernel<T, NB>), (size_t)C::LDS_BYTES))) return rc;
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(grid_prior_kernel<T, NB>), dim3((unsigned)a.B), dim3(kThreads), C::LDS_BYTES, h->stream, a);
+  HIP_TRY(h, hipGetLastError());  // (every launch is checked before the ones that read its output are enqueued)
+  if (a.layout == BLR_LAYOUT_ROWVECS) rc = launch_grid_stats<T, NB, 1>(h, a);
+  else if (vec_ok) rc = launch_grid_stats<T, NB, 4>(h, a);
+  else rc = launch_grid_stats<T, NB, 0>(h, a);
+  if (rc) return rc;
+  if (a.S > 1) {
+    hipLaunchKernelGGL(grid_reduce_kernel<T>, dim3((unsigned)a.B, 8), dim3(kThreads), 0, h->stream, a, SZ);
+    HIP_TRY(h, hipGetLastError());
+  }
+  a.refit = 0;
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(grid_eval_kernel<T, NB>), dim3((unsigned)((int64_t)a.B * a.G)), dim3(kThreads), C::LDS_BYTES, h->stream, a);
+  HIP_TRY(h, hipGetLastError());
+  hipLaunchKernelGGL(grid_argmax_kernel, dim3((unsigned)((a.B + kThreads - 1) / kThreads)), dim3(kThreads), 0, h->stream,
+                     (const double*)a.logpdf, a.stride_lp, a.G, a.B, a.best, a.best_out);
+  HIP_TRY(h, hipGetLastError());
+  if (a.mw_best || a.T_best) {
+    a.refit = 1;
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(grid_eval_kernel<T, NB>), dim3((unsigned)a.B), dim3(kThreads), C::LDS_BYTES, h->stream, a);
+  }
+  HIP_TRY(h, hipGetLastError());
+  return 0;
+}
+
+// D > 128: correct, not fast.  Per setting the scaled operands (grid_scale_kernel) go through the existing pipeline, all B regressors
+// at once; then the argmax, and one more pass per regressor that has a winner.  Synchronises.
+template <typename T>
+int grid_large(blr_handle* h, GridArgs<T> a) {
+  int rc;
+  const int64_t B = a.B, D = a.D, N = a.N;
+  const int64_t s_one = a.noise_kind == BLR_NOISE_DIAGONAL ? std::max<int64_t>(N, 1) : 1;
+  const int64_t lw_one = a.prior_kind == BLR_PRIOR_DENSE ? D * D : D;
+  size_t off = 0;
+  auto carve = [&](size_t bytes) { size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
+  const size_t o_s = carve((size_t)B * s_one * sizeof(T)), o_l = carve((size_t)B * lw_one * sizeof(T));
+  const size_t o_lp = carve((size_t)B * sizeof(double)), o_in = carve((size_t)B * sizeof(int32_t)), o_best = carve((size_t)B * sizeof(int64_t));
+  if ((rc = ensure_loo_ws(h, off))) return rc;
+  char* const ws = h->loo_ws;
+  T* const s_g = reinterpret_cast<T*>(ws + o_s);
+  T* const Lw_g = reinterpret_cast<T*>(ws + o_l);
+  double* const lp_g = reinterpret_cast<double*>(ws + o_lp);
+  int32_t* const in_g = reinterpret_cast<int32_t*>(ws + o_in);
+  a.best = reinterpret_cast<int64_t*>(ws + o_best);
+  const bool was_async = h->async;
+  const int64_t ldl_g = a.prior_kind == BLR_PRIOR_DENSE ? D : 0;
+  for (int g = 0; g < a.G; ++g) {
+    for (int64_t b0 = 0; b0 < B; b0 += 65535) {
+      const int64_t nb = std::min<int64_t>(65535, B - b0);
+      hipLaunchKernelGGL(grid_scale_kernel<T>, dim3(64, (unsigned)nb), dim3(kThreads), 0, h->stream, a, b0, g, s_g + b0 * s_one, s_one,
+                         Lw_g + b0 * lw_one, lw_one);
+    }
+    HIP_TRY(h, hipGetLastError());
+    h->async = true;
+    rc = posterior_batched<T>(h, BLR_MEM_DEVICE, a.layout, B, D, N, a.X, a.ldx, a.strideX, a.y, a.stridey, a.noise_kind, s_g, s_one,
+                              a.prior_kind, a.mw, a.stridemw, Lw_g, ldl_g, lw_one, (T*)nullptr, 0, (T*)nullptr, 0, 0, (T*)nullptr, 0, 0,
+                              lp_g, in_g);
+    h->async = was_async;
+    if (rc) return rc;
+    hipLaunchKernelGGL(grid_scatter_kernel, dim3((unsigned)((B + kThreads - 1) / kThreads)), dim3(kThreads), 0, h->stream,
+                       (const double*)lp_g, (const int32_t*)in_g, (int)B, g, a.logpdf, a.stride_lp, a.info, a.stride_info);
+  }
+  hipLaunchKernelGGL(grid_argmax_kernel, dim3((unsigned)((B + kThreads - 1) / kThreads)), dim3(kThreads), 0, h->stream,
+                     (const double*)a.logpdf, a.stride_lp, a.G, a.B, a.best, a.best_out);
+  HIP_TRY(h, hipGetLastError());
+  if (a.mw_best || a.T_best) {
+    std::vector<int64_t> best((size_t)B);
+    HIP_TRY(h, hipMemcpyAsync(best.data(), a.best, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    for (int64_t b = 0; b < B; ++b) {
+      if (best[(size_t)b] < 0) continue;  // nothing succeeded: mw_best / T_best stay as they are
+      hipLaunchKernelGGL(grid_scale_kernel<T>, dim3(64, 1), dim3(kThreads), 0, h->stream, a, b, (int)best[(size_t)b], s_g, s_one, Lw_g, lw_one);
+      h->async = true;
+      rc = posterior_batched<T>(h, BLR_MEM_DEVICE, a.layout, 1, D, N, a.X + b * a.strideX, a.ldx, 0, a.y + b * a.stridey, 0, a.noise_kind,
+                                s_g, 0, a.prior_kind, a.mw + b * a.stridemw, 0, Lw_g, ldl_g, 0,
+                                a.mw_best ? a.mw_best + b * a.stride_mwbest : (T*)nullptr, 0, a.T_best ? a.T_best + b * a.strideT : (T*)nullptr,
+                                a.ldt, 0, (T*)nullptr, 0, 0, lp_g, in_g);
+      h->async = was_async;
+      if (rc) return rc;
+    }
+  }
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  h->err.clear();
+  return 0;
+}
+
+template <typename T>
+int grid_launch(blr_handle* h, const GridArgs<T>& a) {
+  if (a.D > kMaxSmallD) return grid_large<T>(h, a);
+  const bool vec_ok = a.layout == BLR_LAYOUT_COLVECS && a.D % Mfma<T>::VEC == 0 && aligned16(a.X, a.ldx, a.strideX);
+  switch ((a.D + 15) / 16) {
+    case 1: return grid_small_nb<T, 1>(h, a, vec_ok);
+    case 2: return grid_small_nb<T, 2>(h, a, vec_ok);
+    case 3: return grid_small_nb<T, 3>(h, a, vec_ok);
+    case 4: return grid_small_nb<T, 4>(h, a, vec_ok);
+    case 5: return grid_small_nb<T, 5>(h, a, vec_ok);
+    case 6: return grid_small_nb<T, 6>(h, a, vec_ok);
+    case 7: return grid_small_nb<T, 7>(h, a, vec_ok);
+    default: return grid_small_nb<T, 8>(h, a, vec_ok);
+  }
+}
+
+template <typename T>
+int logpdf_grid(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t N, const T* X, int64_t ldx, int64_t strideX,
+                const T* y, int64_t stridey, int noise_kind, const T* s, int64_t strides, int prior_kind, const T* mw, int64_t stridemw,
+                const T* Lw, int64_t ldl, int64_t strideLw, int64_t G, const T* alpha, int64_t stride_alpha, const T* tau,
+                int64_t stride_tau, double* logpdf, int64_t stride_lp, int64_t* best, T* mw_best, int64_t stride_mwbest, T* T_best,
+                int64_t ldt, int64_t strideT, int32_t* info, int64_t stride_info) {
+  // (the argument checks come before the handle's: they need no device)
+  if (h) h->err.clear();
+  if (memspace != BLR_MEM_HOST && memspace != BLR_MEM_DEVICE) return bad_arg(h, 2, "memspace");
+  if (layout != BLR_LAYOUT_COLVECS && layout != BLR_LAYOUT_ROWVECS) return bad_arg(h, 3, "unknown layout (reference :26-31)");
+  if (B < 0 || B > (1 << 30)) return bad_arg(h, 4, "B out of range (0..2^30)");
+  if (D < 1 || D > kMaxLargeD) return bad_arg(h, 5, "D out of range (1..8192)");
+  if (N < 0 || N > (1 << 30)) return bad_arg(h, 6, "N out of range (0..2^30)");
+  if (N > 0 && !X) return bad_arg(h, 7, "X is NULL");
+  if (layout == BLR_LAYOUT_COLVECS ? ldx < D : ldx < std::max<int64_t>(N, 1)) return bad_arg(h, 8, "ldx too small");
+  if (strideX < 0) return bad_arg(h, 9, "strideX < 0");
+  if (N > 0 && !y) return bad_arg(h, 10, "y is NULL (reference :74 length check)");
+  if (stridey < 0) return bad_arg(h, 11, "stridey < 0");
+  if (noise_kind != BLR_NOISE_ISOTROPIC && noise_kind != BLR_NOISE_DIAGONAL)
+    return bad_arg(h, 12, "noise_kind (the grid scales an isotropic or diagonal base noise; dense Sigma_y is not supported)");
+  if (!s) return bad_arg(h, 13, "s is NULL");
+  if (strides < 0) return bad_arg(h, 14, "strides < 0");
+  if (prior_kind != BLR_PRIOR_DENSE && prior_kind != BLR_PRIOR_DIAGONAL)
+    return bad_arg(h, 15, "prior_kind (dense or diagonal precision; pass a carried-forward factor as U'U)");
+  if (!mw) return bad_arg(h, 16, "mw is NULL");
+  if (stridemw < 0) return bad_arg(h, 17, "stridemw < 0");
+  if (!Lw) return bad_arg(h, 18, "Lw is NULL");
+  if (prior_kind == BLR_PRIOR_DENSE && ldl < D) return bad_arg(h, 19, "ldl < D");
+  if (strideLw < 0) return bad_arg(h, 20, "strideLw < 0");
+  if (G < 0 || G > (1 << 20)) return bad_arg(h, 21, "G out of range (0..2^20)");
+  if (alpha && stride_alpha != 0 && stride_alpha < G) return bad_arg(h, 23, "stride_alpha (0 = one grid for every regressor, else >= G)");
+  if (tau && stride_tau != 0 && stride_tau < G) return bad_arg(h, 25, "stride_tau (0 = one grid for every regressor, else >= G)");
+  if (G > 0 && !logpdf) return bad_arg(h, 26, "logpdf is NULL");
+  if (stride_lp < G) return bad_arg(h, 27, "stride_lp < G");
+  if (mw_best && B > 1 && stride_mwbest < D) return bad_arg(h, 30, "stride_mwbest < D");
+  if (T_best && ldt < D) return bad_arg(h, 32, "ldt < D");
+  if (T_best && B > 1 && strideT < (int64_t)mat_extent(D, D, ldt)) return bad_arg(h, 33, "strideT too small");
+  if (G > 0 && !info) return bad_arg(h, 34, "info is NULL");
+  if (stride_info < G) return bad_arg(h, 35, "stride_info < G");
+  int S = 1, chunk = 64;
+  if (D <= kMaxSmallD) grid_splits(N, &S, &chunk);
+  // one workgroup of 256 threads per (regressor, setting) / (regressor, column block): a launch takes fewer than 2^32 threads
+  if (B * std::max<int64_t>(G, S) >= ((int64_t)1 << 24)) return bad_arg(h, 21, "B * max(G, 8) too large (< 2^24)");
+  if (!h) return -1;
+  if (B == 0 || G == 0) return 0;
+  HIP_TRY(h, hipSetDevice(h->device));
+  GridArgs<T> a{};
+  a.ldx = ldx; a.strideX = strideX; a.stridey = stridey; a.strides = strides; a.stridemw = stridemw; a.ldl = ldl; a.strideLw = strideLw;
+  a.stride_alpha = stride_alpha; a.stride_tau = stride_tau; a.stride_lp = stride_lp; a.stride_info = stride_info;
+  a.stride_mwbest = stride_mwbest; a.ldt = ldt; a.strideT = strideT;
+  a.layout = layout; a.noise_kind = noise_kind; a.prior_kind = prior_kind;
+  a.D = (int)D; a.N = (int)N; a.B = (int)B; a.G = (int)G; a.S = S; a.chunk = chunk;
+  if (memspace == BLR_MEM_DEVICE) {
+    a.X = X; a.y = y; a.s = s; a.mw = mw; a.Lw = Lw; a.alpha = alpha; a.tau = tau; a.logpdf = logpdf; a.info = info; a.best_out = best;
+    a.mw_best = mw_best; a.T_best = T_best;
+    if (N == 0) { if (!a.X) a.X = mw; if (!a.y) a.y = mw; }
+    const int rc = grid_launch<T>(h, a);
+    if (rc) return rc;
+    if (!h->async) HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return 0;
+  }
+  Staging guard(h);
+  const size_t x_one = N == 0 ? 0 : (layout == BLR_LAYOUT_COLVECS ? mat_extent(D, N, ldx) : mat_extent(N, D, ldx));
+  const size_t lw_one = prior_kind == BLR_PRIOR_DIAGONAL ? (size_t)D : mat_extent(D, D, ldl);
+  const size_t s_one = noise_kind == BLR_NOISE_DIAGONAL ? (size_t)N : 1;
+  const size_t n_lp = extent(B, stride_lp, (size_t)G), n_in = extent(B, stride_info, (size_t)G);
+  const size_t n_mw = extent(B, stride_mwbest, (size_t)D), n_T = extent(B, strideT, mat_extent(D, D, ldt));
+  int rc;
+  if ((rc = stage_in(h, X, x_one ? extent(B, strideX, x_one) : 0, &a.X))) return rc;
+  if ((rc = stage_in(h, y, N ? extent(B, stridey, (size_t)N) : 0, &a.y))) return rc;
+  if ((rc = stage_in(h, s, std::max<size_t>(extent(B, strides, s_one), 1), &a.s))) return rc;
+  if ((rc = stage_in(h, mw, extent(B, stridemw, (size_t)D), &a.mw))) return rc;
+  if ((rc = stage_in(h, Lw, extent(B, strideLw, lw_one), &a.Lw))) return rc;
+  if ((rc = stage_in(h, alpha, extent(B, stride_alpha, (size_t)G), &a.alpha))) return rc;
+  if ((rc = stage_in(h, tau, extent(B, stride_tau, (size_t)G), &a.tau))) return rc;
+  if ((rc = stage_out_alloc(h, logpdf, n_lp, &a.logpdf))) return rc;
+  if ((rc = stage_out_alloc(h, info, n_in, &a.info))) return rc;
+  if ((rc = stage_out_alloc(h, best, (size_t)B, &a.best_out))) return rc;
+  if ((rc = stage_out_alloc(h, mw_best, n_mw, &a.mw_best))) return rc;
+  if ((rc = stage_out_alloc(h, T_best, n_T, &a.T_best))) return rc;
+  if (N == 0) { if (!a.X) a.X = a.mw; if (!a.y) a.y = a.mw; }
+  if ((rc = grid_launch<T>(h, a))) return rc;
+  HIP_TRY(h, hipMemcpyAsync(logpdf, a.logpdf, n_lp * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(info, a.info, n_in * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  if (best) HIP_TRY(h, hipMemcpyAsync(best, a.best_out, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+  if (mw_best) HIP_TRY(h, hipMemcpyAsync(mw_best, a.mw_best, n_mw * sizeof(T), hipMemcpyDeviceToHost, h->stream));
+  if (T_best) HIP_TRY(h, hipMemcpyAsync(T_best, a.T_best, n_T * sizeof(T), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  return 0;
+}
+
 }  // namespace
 
 // =======================================================================================================
@@ -3896,6 +4118,17 @@ int blr_timer_stop(blr_handle* h, float* elapsed_ms) {
     return loo_batched<T>(h, memspace, layout, B, D, N, X, ldx, strideX, y, stridey, noise_kind, s, strides, mw,     \
                           stridemw, Tf, ldt, strideT, loo_mean, stride_lm, loo_var, stride_lv, loo_logpdf,          \
                           stride_ll, loo_total, info);                                                             \
+  }                                                                                                                 \
+  int blr_logpdf_grid_##SUF(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t N, const T* X,  \
+                            int64_t ldx, int64_t strideX, const T* y, int64_t stridey, int noise_kind, const T* s, \
+                            int64_t strides, int prior_kind, const T* mw, int64_t stridemw, const T* Lw,            \
+                            int64_t ldl, int64_t strideLw, int64_t G, const T* alpha, int64_t stride_alpha,         \
+                            const T* tau, int64_t stride_tau, double* logpdf, int64_t stride_lp, int64_t* best,     \
+                            T* mw_best, int64_t stride_mwbest, T* T_best, int64_t ldt, int64_t strideT,             \
+                            int32_t* info, int64_t stride_info) {                                                   \
+    return logpdf_grid<T>(h, memspace, layout, B, D, N, X, ldx, strideX, y, stridey, noise_kind, s, strides,        \
+                          prior_kind, mw, stridemw, Lw, ldl, strideLw, G, alpha, stride_alpha, tau, stride_tau,     \
+                          logpdf, stride_lp, best, mw_best, stride_mwbest, T_best, ldt, strideT, info, stride_info);\
   }                                                                                                                 \
   int blr_posterior_##SUF(blr_handle* h, int layout, int64_t D, int64_t N, const T* X, int64_t ldx, const T* y,     \
                           int noise_kind, const T* s, int prior_kind, const T* mw, const T* Lw, int64_t ldl,        \

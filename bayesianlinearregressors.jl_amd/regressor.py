@@ -27,6 +27,7 @@ __all__ = [
     "BayesianLinearRegressor", "BasisFunctionRegressor", "BLRFunctionSample", "FiniteGP",
     "mean", "var", "cov", "std", "mean_and_var", "mean_and_cov", "marginals", "rand", "rand_b", "logpdf", "posterior",
     "LOO", "loo", "loo_map",
+    "EvidenceGrid", "logpdf_grid", "posterior_best", "logpdf_grid_map",
 ]
 
 
@@ -732,6 +733,119 @@ def loo_map(fxs, ys):
     if len(sig) != 1 or probs[0][3] == 0 or probs[0][4] == 0:
         return one_by_one(probs)
     return _loo_batch(probs, dtype)
+
+
+EvidenceGrid = namedtuple("EvidenceGrid", ["logpdf", "best", "alpha", "tau"])
+EvidenceGrid.__doc__ = """Evidence of one data set under every (prior scale alpha_i, noise scale tau_j): logpdf[i, j] is
+logpdf(BayesianLinearRegressor(mw, alpha_i Lw)(x, tau_j Sy), y) (NaN where that setting is not positive definite), best the
+(i, j) of the largest finite one (None when no setting succeeded), alpha and tau the two scale vectors."""
+
+
+def _grid_problem(fx, y, dtype):
+    """Operands of one finite regressor for blr_logpdf_grid_*, validated as `_fused` does.  A PDMat prior is passed as U'U formed
+    on the host (a small D x D product): the entry scales a precision, not a carried-forward factor."""
+    fb = _to_finite_blr(fx)
+    X, layout, ldx, D, N = _x_layout(fb.x, dtype)
+    y = np.ascontiguousarray(y, dtype=dtype)
+    if y.ndim != 1:
+        raise ValueError("y must be a vector")
+    if y.shape[0] != N:
+        raise ValueError("length(y) != size(fx.x.X, 2)")  # reference :74
+    s, noise_kind = _noise(fb.Sy, N, dtype)
+    if noise_kind == _abi.NOISE_DENSE:
+        raise ValueError("logpdf_grid: isotropic or diagonal noise only (a dense noise covariance is not supported by "
+                         "blr_logpdf_grid_*)")
+    Lw = fb.f.Lw
+    if isinstance(Lw, PDMat):
+        U = np.triu(np.asarray(Lw.U, dtype=np.float64))
+        Lw = U.T @ U
+    Lw, prior_kind, ldl = _prior(Lw, D, dtype)
+    return X, layout, ldx, D, N, y, s, noise_kind, _mean_vector(fb.f.mw, D, dtype), Lw, prior_kind, ldl
+
+
+def _grid_scales(prior_scales, noise_scales, dtype):
+    a = np.atleast_1d(np.asarray([1.0] if prior_scales is None else prior_scales, dtype=dtype))
+    t = np.atleast_1d(np.asarray([1.0] if noise_scales is None else noise_scales, dtype=dtype))
+    if a.ndim != 1 or t.ndim != 1 or a.size == 0 or t.size == 0:
+        raise ValueError("prior_scales and noise_scales must be non-empty vectors")
+    return a, t
+
+
+def _grid_batch(probs, a, t, dtype, want_posterior):
+    """blr_logpdf_grid_* over equally shaped problems: the outer product of the scales flattened to G settings, prior scale
+    slowest.  -> [(EvidenceGrid, mw_best, T_best)]"""
+    X0, layout, ldx, D, N, _, _, noise_kind, _, _, prior_kind, ldl = probs[0]
+    nb, G = len(probs), a.size * t.size
+    Xb = np.stack([q[0].reshape(-1, order="A") for q in probs])
+    yb = np.stack([q[5] for q in probs])
+    sb = np.stack([q[6] for q in probs])
+    mwb = np.stack([q[8] for q in probs])
+    Lb = np.stack([q[9].reshape(-1, order="A") for q in probs])
+    alpha = np.ascontiguousarray(np.repeat(a, t.size))
+    tau = np.ascontiguousarray(np.tile(t, a.size))
+    lp = np.full((nb, G), np.nan, dtype=np.float64)
+    info = np.zeros((nb, G), dtype=np.int32)
+    best = np.full(nb, -1, dtype=np.int64)
+    mw_best = np.empty((nb, D), dtype=dtype) if want_posterior else None
+    T_best = np.empty((nb, D * D), dtype=dtype) if want_posterior else None
+    _handle().logpdf_grid(dtype, _abi.MEM_HOST, layout, nb, D, N, Xb, ldx, Xb.shape[1], yb, yb.shape[1], noise_kind, sb,
+                          sb.shape[1], prior_kind, mwb, D, Lb, ldl, Lb.shape[1], G, alpha, 0, tau, 0, lp, G, best, mw_best, D,
+                          T_best, max(D, 1), D * D, info, G)
+    out = []
+    for b in range(nb):
+        k = int(best[b])
+        grid = EvidenceGrid(lp[b].reshape(a.size, t.size), divmod(k, t.size) if k >= 0 else None, a, t)
+        if want_posterior and k < 0:
+            e = _abi.PosDefException(int(info[b][0]))  # no setting is positive definite: the first setting's status, as a loop would raise
+            e.index = b
+            raise e
+        out.append((grid, mw_best[b] if want_posterior else None,
+                    T_best[b].reshape((D, D), order="F") if want_posterior else None))
+    return out
+
+
+def _grid_dtype(fx, y):
+    return _dtype_of(fx.f.blr.mw if isinstance(fx.f, BasisFunctionRegressor) else fx.f.mw, y)
+
+
+def logpdf_grid(fx, y, prior_scales=None, noise_scales=None):
+    """Evidence of (fx, y) under every setting Lw -> alpha Lw, Sy -> tau Sy of the two scale vectors, from ONE pass over the
+    inputs (include/blr_mi355x.h blr_logpdf_grid_*): the inner loop of type-II maximum likelihood.  ``None`` means [1.0].
+    Returns EvidenceGrid(logpdf [len(prior_scales), len(noise_scales)], best (i, j), alpha, tau)."""
+    dtype = _grid_dtype(fx, y)
+    a, t = _grid_scales(prior_scales, noise_scales, dtype)
+    return _grid_batch([_grid_problem(fx, y, dtype)], a, t, dtype, False)[0][0]
+
+
+def posterior_best(fx, y, prior_scales=None, noise_scales=None):
+    """(posterior at the evidence-maximising setting, EvidenceGrid) in the same library call; the posterior is wrapped like
+    `posterior` wraps it (PDMat prior -> PDMat, else Symmetric).  Raises PosDefException when no setting succeeded."""
+    dtype = _grid_dtype(fx, y)
+    a, t = _grid_scales(prior_scales, noise_scales, dtype)
+    grid, mw_best, T = _grid_batch([_grid_problem(fx, y, dtype)], a, t, dtype, True)[0]
+    base = fx.f.blr if isinstance(fx.f, BasisFunctionRegressor) else fx.f
+    Tu = np.triu(T)
+    post = BayesianLinearRegressor(mw_best, _wrap_like(base.Lw, Tu, None if isinstance(base.Lw, PDMat) else Tu.T @ Tu))
+    if isinstance(fx.f, BasisFunctionRegressor):
+        post = BasisFunctionRegressor(post, fx.f.phi)
+    return post, grid
+
+
+def logpdf_grid_map(fxs, ys, prior_scales=None, noise_scales=None):
+    """[logpdf_grid(fx, y, prior_scales, noise_scales) for fx, y in zip(fxs, ys)] in one library call for equally shaped
+    problems (the B axis of blr_logpdf_grid_*); one call per problem when shapes, layouts or kinds differ."""
+    fxs, ys = list(fxs), list(ys)
+    if len(fxs) != len(ys):
+        raise ValueError("as many observation vectors as finite regressors are needed")
+    if not fxs:
+        return []
+    dtype = np.float32 if all(_grid_dtype(fx, y) == np.float32 for fx, y in zip(fxs, ys)) else np.float64
+    a, t = _grid_scales(prior_scales, noise_scales, dtype)
+    probs = [_grid_problem(fx, y, dtype) for fx, y in zip(fxs, ys)]
+    sig = {(q[0].shape, q[0].flags.f_contiguous, q[1], q[3], q[4], q[7], q[10]) for q in probs}
+    if len(sig) != 1:
+        return [_grid_batch([q], a, t, dtype, False)[0][0] for q in probs]
+    return [r[0] for r in _grid_batch(probs, a, t, dtype, False)]
 
 
 class _DeviceBuffer:

@@ -102,7 +102,7 @@ const char* blr_last_route(blr_handle* h);
 int blr_get_stat(blr_handle* h, const char* key, int64_t* value);
 int blr_reset_stats(blr_handle* h);
 /* The handle's device scratch (factorisation workspaces of D > 128 calls -- up to 8 GiB for a large batched call, see CHAIN_WS_MB --
- * the feature matrix of blr_posterior_rff_*, the int8 / marginal side buffers) only ever GROWS between calls; this drains the
+ * the feature matrix of blr_posterior_rff_*, the int8 / marginal side buffers, the statistics buffer of blr_logpdf_grid_*) only ever GROWS between calls; this drains the
  * stream and frees all of it.  The next call allocates what it needs again. */
 int blr_release_workspace(blr_handle* h);
 
@@ -491,6 +491,51 @@ int blr_loo_batched_f32(blr_handle* h, int memspace, int layout, int64_t B, int6
                         int64_t strides, const float* mw, int64_t stridemw, const float* T, int64_t ldt, int64_t strideT,
                         float* loo_mean, int64_t stride_lm, float* loo_var, int64_t stride_lv, double* loo_logpdf,
                         int64_t stride_ll, double* loo_total, int32_t* info);
+
+/* ---- evidence of one data set under a GRID of (prior scale, noise scale) settings, from one pass over the data ------------
+ * Replaces: blr_posterior_batched_* called with strideX = 0, stridey = 0 and one scaled (s, Lw) pair per setting, which re-forms
+ * the D x D Gram matrix per setting; reference src/bayesian_linear_regression.jl:55-58 (logpdf) on
+ * BayesianLinearRegressor(mw, alpha L0)(x, tau S0) -- type-II maximum likelihood over (alpha, tau), Bishop 3.5.
+ * Base prior precision L0 = Lw (DENSE: upper triangle read; DIAGONAL), base noise S0 = s (isotropic or diagonal); setting g of
+ * regressor b is Lw = alpha[b][g] L0, Sy = tau[b][g] S0 (stride_alpha / stride_tau = 0: one grid shared by all regressors; alpha or
+ * tau NULL: all ones).  With
+ *   G0 = X S0^-1 X'    b0 = X S0^-1 (y - X'mw)    q0 = (y - X'mw)' S0^-1 (y - X'mw)    l0 = logdet S0
+ *   A = alpha L0 + G0 / tau      T = chol(A).U      u = T^-T b0 / tau      mw' = mw + T^-1 u
+ *   logpdf[b][g] = -1/2 [N log 2 pi + N log tau + l0 + q0 / tau + logdet A - D log alpha - logdet L0 - |u|^2]
+ * which is what blr_posterior_batched_* returns for that (s, Lw) pair.  best[b] (may be NULL) = the smallest g among the settings
+ * with the largest finite evidence, -1 when no setting succeeded.  mw_best, T_best (each may be NULL): (mw_post, T_post) exactly as
+ * blr_posterior_batched_* writes them (T upper, strictly-lower part zero) for the setting best[b]; left untouched when best[b] = -1.
+ * info[b][g], LAPACK style, in the reference's order (:78 prior, :79 noise, :86 posterior): alpha_g not positive or not finite -> 1
+ * (leading minor 1 of the prior), a base prior that is not positive definite -> its failing leading minor for all G settings of
+ * that regressor, tau_g not positive or not finite -> 1 (observation 1), a base noise entry s_i not positive -> i for all G
+ * settings, else the failing leading minor of A; logpdf of a failed setting is NaN.  The call returns 0 (negative argument
+ * indices on argument errors, which are checked before the handle; output strides that overlap for B > 1 are argument errors).
+ * Limits: 1 <= D <= 8192, N >= 0, 0 <= G <= 2^20 (G = 0 or B = 0: no-op), B max(G, 8) < 2^24 (argument error 21 beyond), stride_lp >= G, stride_info >= G;
+ * isotropic or diagonal base noise (dense: argument error), DENSE or DIAGONAL base prior (BLR_PRIOR_UPPER_FACTOR is an argument
+ * error: pass a carried-forward factor as U'U); ColVecs or RowVecs, any ldx; host or device memspace; an async handle only enqueues
+ * (device memspace, D <= 128).  Bit-reproducible; the bits of regressor b do not depend on B or on its position, those of setting
+ * g not on G or on its position (no float atomics, fixed summation orders).
+ * Kernels (csrc/blr_grid.hpp).  D <= 128: X is read ONCE per regressor by the streaming Gram phase of the fused
+ * kernel (fp64 / fp32 matrix cores; never the int8-sliced Gram) into a statistics buffer of the handle -- N is cut into column
+ * blocks of about 1024 (at most 8, a function of N alone) that are added in a fixed order; then one workgroup per (regressor,
+ * setting) builds A in LDS, factors it and writes the evidence; one argmax launch; one more launch over the B winners for mw_best /
+ * T_best.  The launches do not depend on B or G.  The statistics buffer takes ceil(D/16)*16 * (ceil(D/16)*16 + 3) / 2 elements per
+ * column block and regressor (blr_release_workspace frees it).
+ * D > 128: correct, not fast -- every setting's scaled operands go through the pipeline of blr_posterior_batched_* (the Gram matrix
+ * is formed again per setting), the winners once more; the call synchronises whatever the handle's async flag says.
+ * _f32: X, y, s, mw, Lw, alpha, tau, mw_best, T_best are float; logpdf stays double. */
+int blr_logpdf_grid_f64(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t N, const double* X, int64_t ldx,
+                        int64_t strideX, const double* y, int64_t stridey, int noise_kind, const double* s, int64_t strides,
+                        int prior_kind, const double* mw, int64_t stridemw, const double* Lw, int64_t ldl, int64_t strideLw,
+                        int64_t G, const double* alpha, int64_t stride_alpha, const double* tau, int64_t stride_tau,
+                        double* logpdf, int64_t stride_lp, int64_t* best, double* mw_best, int64_t stride_mwbest,
+                        double* T_best, int64_t ldt, int64_t strideT, int32_t* info, int64_t stride_info);
+int blr_logpdf_grid_f32(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t N, const float* X, int64_t ldx,
+                        int64_t strideX, const float* y, int64_t stridey, int noise_kind, const float* s, int64_t strides,
+                        int prior_kind, const float* mw, int64_t stridemw, const float* Lw, int64_t ldl, int64_t strideLw,
+                        int64_t G, const float* alpha, int64_t stride_alpha, const float* tau, int64_t stride_tau,
+                        double* logpdf, int64_t stride_lp, int64_t* best, float* mw_best, int64_t stride_mwbest,
+                        float* T_best, int64_t ldt, int64_t strideT, int32_t* info, int64_t stride_info);
 
 /* ---- sharded log-evidence: fixed-order sum of logpdf[B] on the device ----------
  * Deterministic (no float atomics): the same bits for the same B regardless of launch geometry.

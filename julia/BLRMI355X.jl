@@ -917,6 +917,97 @@ function loo(fx::FiniteGP, y::AbstractVector{<:Real})
 end
 
 """
+    logpdf_grid!(lp, best, mw_best, T_best, info, X, y, s, mw, Lw, alpha, tau; D, N, B, G, isotropic, diagonal_prior,
+                 noise_stride = isotropic ? 1 : N)
+
+Evidence of each of B device-resident data sets under G settings Λw = alpha[g] Lw, Σy = tau[g] s (one grid shared by all data
+sets) from ONE pass over X (`blr_logpdf_grid_*`; reference `src/bayesian_linear_regression.jl:55-58` per setting): lp is G×B
+(Float64), info G×B, best (Int64, 0-based setting of the largest finite evidence, -1 if none) B or `nothing`, mw_best D×B and
+T_best D×D×B the posterior at that setting or `nothing`.  Lw is D×B (`diagonal_prior`) or D×D×B.  s holds one variance per data
+set (`isotropic`, length B) or N×B; `noise_stride = 0` makes all data sets share the first one (or the first N).
+"""
+function logpdf_grid!(lp::DeviceArray{Float64}, best::Union{Nothing,DeviceArray{Int64}}, mw_best::Union{Nothing,DeviceArray{T}},
+                      T_best::Union{Nothing,DeviceArray{T}}, info::DeviceArray{Int32}, X::DeviceArray{T}, y::DeviceArray{T},
+                      s::DeviceArray{T}, mw::DeviceArray{T}, Lw::DeviceArray{T}, alpha::DeviceArray{T}, tau::DeviceArray{T};
+                      D::Int, N::Int, B::Int, G::Int, isotropic::Bool, diagonal_prior::Bool,
+                      noise_stride::Int = isotropic ? 1 : N) where {T<:Elt}
+    h = handle()
+    nk = isotropic ? ISOTROPIC : DIAGONALN
+    pk = diagonal_prior ? P_DIAG : P_DENSE
+    ptr(a) = a === nothing ? Ptr{T}(C_NULL) : a.ptr
+    iptr(a) = a === nothing ? Ptr{Int64}(C_NULL) : a.ptr
+    rc = if T === Float64
+        ccall((:blr_logpdf_grid_f64, LIB), Cint,
+              (Ptr{Cvoid}, Cint, Cint, Int64, Int64, Int64, Ptr{T}, Int64, Int64, Ptr{T}, Int64, Cint, Ptr{T}, Int64, Cint, Ptr{T}, Int64,
+               Ptr{T}, Int64, Int64, Int64, Ptr{T}, Int64, Ptr{T}, Int64, Ptr{Cdouble}, Int64, Ptr{Int64}, Ptr{T}, Int64, Ptr{T}, Int64,
+               Int64, Ptr{Int32}, Int64),
+              h, MEM_DEVICE, COLVECS, B, D, N, X.ptr, D, D * N, y.ptr, N, nk, s.ptr, noise_stride, pk, mw.ptr, D, Lw.ptr, D,
+              diagonal_prior ? D : D * D, G, alpha.ptr, 0, tau.ptr, 0, lp.ptr, G, iptr(best), ptr(mw_best), D, ptr(T_best), D, D * D,
+              info.ptr, G)
+    else
+        ccall((:blr_logpdf_grid_f32, LIB), Cint,
+              (Ptr{Cvoid}, Cint, Cint, Int64, Int64, Int64, Ptr{T}, Int64, Int64, Ptr{T}, Int64, Cint, Ptr{T}, Int64, Cint, Ptr{T}, Int64,
+               Ptr{T}, Int64, Int64, Int64, Ptr{T}, Int64, Ptr{T}, Int64, Ptr{Cdouble}, Int64, Ptr{Int64}, Ptr{T}, Int64, Ptr{T}, Int64,
+               Int64, Ptr{Int32}, Int64),
+              h, MEM_DEVICE, COLVECS, B, D, N, X.ptr, D, D * N, y.ptr, N, nk, s.ptr, noise_stride, pk, mw.ptr, D, Lw.ptr, D,
+              diagonal_prior ? D : D * D, G, alpha.ptr, 0, tau.ptr, 0, lp.ptr, G, iptr(best), ptr(mw_best), D, ptr(T_best), D, D * D,
+              info.ptr, G)
+    end
+    check(h, rc)
+    return nothing
+end
+
+"""
+    logpdf_grid(fx, y, prior_scales, noise_scales) -> (logpdf, best, mw_best, T_best)
+
+Evidence of (fx, y) under every (prior scale, noise scale) pair -- logpdf[j, i] for noise_scales[j], prior_scales[i] -- the
+1-based (j, i) of the largest finite one, and the posterior mean and factor at that setting, in one library call (host
+memspace).  Isotropic or Diagonal noise; a Diagonal or dense prior precision (a PDMat prior is passed as U'U).
+"""
+function logpdf_grid(fx::FiniteGP, y::AbstractVector{<:Real}, prior_scales::AbstractVector{<:Real}, noise_scales::AbstractVector{<:Real})
+    fb = to_blr(fx)
+    xl, nz = xlayout(fb.x), noise(fb.Σy)
+    Λ = fb.f.Λw isa AbstractPDMat ? Symmetric(Matrix(fb.f.Λw)) : fb.f.Λw   # U'U, a small D x D product on the host
+    pr = prior(Λ)
+    (xl === nothing || nz === nothing || pr === nothing || nz[2] == DENSEN) &&
+        throw(ArgumentError("logpdf_grid: ColVecs / RowVecs inputs, isotropic or Diagonal noise, Diagonal or dense prior"))
+    X, layout, ldx, D, N = xl
+    T = eltype(X)
+    yv, mw = convert(Vector{T}, y), convert(Vector{T}, fb.f.mw)
+    s, nk, _ = nz
+    Lw, pk, ldl = pr
+    na, nt = length(prior_scales), length(noise_scales)
+    G = na * nt
+    G == 0 && throw(ArgumentError("logpdf_grid: prior_scales and noise_scales must not be empty"))
+    a = T[prior_scales[i] for i in 1:na for _ in 1:nt]   # prior scale slowest
+    t = T[noise_scales[j] for _ in 1:na for j in 1:nt]
+    lp = Vector{Float64}(undef, G); info = zeros(Int32, G); best = Int64[-1]
+    mw′ = Vector{T}(undef, D); Tp = Matrix{T}(undef, D, D)
+    h = handle()
+    rc = GC.@preserve X yv s mw Lw a t lp info best mw′ Tp begin
+        if T === Float64
+            ccall((:blr_logpdf_grid_f64, LIB), Cint,
+                  (Ptr{Cvoid}, Cint, Cint, Int64, Int64, Int64, Ptr{T}, Int64, Int64, Ptr{T}, Int64, Cint, Ptr{T}, Int64, Cint, Ptr{T}, Int64,
+               Ptr{T}, Int64, Int64, Int64, Ptr{T}, Int64, Ptr{T}, Int64, Ptr{Cdouble}, Int64, Ptr{Int64}, Ptr{T}, Int64, Ptr{T}, Int64,
+               Int64, Ptr{Int32}, Int64),
+                  h, MEM_HOST, layout, 1, D, N, X, ldx, 0, yv, 0, nk, s, 0, pk, mw, 0, Lw, ldl, 0, G, a, 0, t, 0, lp, G, best, mw′, 0, Tp, D, 0,
+                  info, G)
+        else
+            ccall((:blr_logpdf_grid_f32, LIB), Cint,
+                  (Ptr{Cvoid}, Cint, Cint, Int64, Int64, Int64, Ptr{T}, Int64, Int64, Ptr{T}, Int64, Cint, Ptr{T}, Int64, Cint, Ptr{T}, Int64,
+               Ptr{T}, Int64, Int64, Int64, Ptr{T}, Int64, Ptr{T}, Int64, Ptr{Cdouble}, Int64, Ptr{Int64}, Ptr{T}, Int64, Ptr{T}, Int64,
+               Int64, Ptr{Int32}, Int64),
+                  h, MEM_HOST, layout, 1, D, N, X, ldx, 0, yv, 0, nk, s, 0, pk, mw, 0, Lw, ldl, 0, G, a, 0, t, 0, lp, G, best, mw′, 0, Tp, D, 0,
+                  info, G)
+        end
+    end
+    check(h, rc)
+    best[1] < 0 && check(h, info[1])
+    k = Int(best[1])
+    return reshape(lp, nt, na), (k % nt + 1, k ÷ nt + 1), mw′, Tp
+end
+
+"""
     rand_batched!(Y, W, info, X, mw, Tf, Z1, Z2; D, N, S, B, shared_x=false, s=nothing)
 
 Draws from B device-resident states, the step that closes a Thompson-sampling loop around `update_factor!` on `DeviceArray`s:
