@@ -31,166 +31,9 @@
 #include "blr_marginals.hpp"
 #include "blr_rand_batched.hpp"
 #include "blr_grid.hpp"
+#include "blr_host.hpp"
 
 using namespace blr;
-
-// Run-time switches (A/B experiments and tests; the defaults are the measured best).  Read from the environment ONCE, when the
-// handle is created (BLR_MI355X_<KEY>), and settable per handle with blr_set_option: no getenv on any launch path.
-struct BlrOptions {
-  bool no_ldsdma = false, no_wave_kernel = false, no_gram_ring = false, no_diag_split = false, no_xcd_swizzle = false,
-       no_mfma_project = false, plan_debug = false, no_i8_gram = false, no_marg_gemm = false, no_i8_diag = false, no_i8_factor = false, no_i8_rowvecs = false, no_grad_gemm = false, no_i8_dense = false, no_i8_fallback = false, no_bf16x3 = false, no_planes = false, no_fp16_planes = false, planes8 = false, no_spec_rowmax = false, no_multi_planes = false, no_downdate_lds = false;
-  int wave_split = 0;     // waves per regressor of the wave kernel: 0 = router, else 1 | 2 | 4
-  int chain_batch = 0;    // regressors per shared launch at D > 128: 0 = as many as the workspace holds
-  int i8_probe_min = 0;   // int8 route: batches beyond this many regressors start with a probe slice; 0 = kI8ProbeMin
-  int i8_groups = 0;      // int8 route: digit groups kept, 0 = six under isotropic noise and seven under diagonal noise; 6 | 7 = that plan for both noise kinds
-  long chain_ws_mb = 0;   // workspace bound of such a group in MiB: 0 = kChainWorkspace
-  int sweep = 0;          // blr_update_factor_* route: 0 = router, 1 = always the Givens sweep, 2 = never
-  int gs_fields = 0, gs_so = 0, gs_sd = 0, gs_nl = 0;  // GRAM_SPLITS = "off-diagonal,diagonal[,nlong]" (gs_fields = numbers parsed)
-  // -> 0, -2 for an unknown key, -3 for a malformed value (the codes blr_set_option documents).  value NULL or "" = the built-in default
-  static bool parse_long(const char* v, long& out) {  // the whole string must be a decimal number
-    char* end = nullptr;
-    const long x = strtol(v, &end, 10);
-    if (end == v || *end != '\0') return false;
-    out = x;
-    return true;
-  }
-  int set(const char* key, const char* value) {
-    if (!key) return -2;
-    if (!strncmp(key, "BLR_MI355X_", 11)) key += 11;
-    const bool on = value && *value;
-    auto flag = [&](bool& f) { f = on; return 0; };
-    if (!strcmp(key, "NO_LDSDMA")) return flag(no_ldsdma);
-    if (!strcmp(key, "NO_WAVE_KERNEL")) return flag(no_wave_kernel);
-    if (!strcmp(key, "NO_GRAM_RING")) return flag(no_gram_ring);
-    if (!strcmp(key, "NO_DIAG_SPLIT")) return flag(no_diag_split);
-    if (!strcmp(key, "NO_XCD_SWIZZLE")) return flag(no_xcd_swizzle);
-    if (!strcmp(key, "NO_MFMA_PROJECT")) return flag(no_mfma_project);
-    if (!strcmp(key, "PLAN_DEBUG")) return flag(plan_debug);
-    if (!strcmp(key, "NO_I8_GRAM")) return flag(no_i8_gram);
-    if (!strcmp(key, "NO_MARG_GEMM")) return flag(no_marg_gemm);
-    if (!strcmp(key, "NO_GRAD_GEMM")) return flag(no_grad_gemm);
-    if (!strcmp(key, "NO_I8_DIAG")) return flag(no_i8_diag);
-    if (!strcmp(key, "NO_I8_FACTOR")) return flag(no_i8_factor);
-    if (!strcmp(key, "NO_I8_ROWVECS")) return flag(no_i8_rowvecs);
-    if (!strcmp(key, "NO_I8_DENSE")) return flag(no_i8_dense);
-    if (!strcmp(key, "NO_BF16X3")) return flag(no_bf16x3);
-    if (!strcmp(key, "NO_PLANES")) return flag(no_planes);
-    if (!strcmp(key, "NO_MULTI_PLANES")) return flag(no_multi_planes);  // logpdf_multi at D > 128, fp32: the separate residual product + panel sweep
-    if (!strcmp(key, "NO_SPEC_ROWMAX")) return flag(no_spec_rowmax);  // exact row maxima (one more pass over X) instead of the sampled ones
-    if (!strcmp(key, "NO_FP16_PLANES")) return flag(no_fp16_planes);
-    if (!strcmp(key, "PLANES8")) return flag(planes8);
-    if (!strcmp(key, "NO_I8_FALLBACK")) return flag(no_i8_fallback);
-    if (!strcmp(key, "NO_DOWNDATE_LDS")) return flag(no_downdate_lds);  // blr_downdate_factor_*: the global-memory kernel at every D
-    long v = 0;
-    if (!strcmp(key, "WAVE_SPLIT")) {
-      if (!on) { wave_split = 0; return 0; }
-      if (!parse_long(value, v) || !(v == 1 || v == 2 || v == 4)) return -3;
-      wave_split = (int)v;
-      return 0;
-    }
-    if (!strcmp(key, "CHAIN_BATCH")) {
-      if (!on) { chain_batch = 0; return 0; }
-      if (!parse_long(value, v) || v < 1 || v > 128) return -3;
-      chain_batch = (int)v;
-      return 0;
-    }
-    if (!strcmp(key, "I8_PROBE_MIN")) {
-      if (!on) { i8_probe_min = 0; return 0; }
-      if (!parse_long(value, v) || v < 256 || v > (1 << 20)) return -3;
-      i8_probe_min = (int)v;
-      return 0;
-    }
-    if (!strcmp(key, "I8_GROUPS")) {
-      if (!on) { i8_groups = 0; return 0; }
-      if (!parse_long(value, v) || !(v == 6 || v == 7)) return -3;
-      i8_groups = (int)v;
-      return 0;
-    }
-    if (!strcmp(key, "CHAIN_WS_MB")) {
-      if (!on) { chain_ws_mb = 0; return 0; }
-      if (!parse_long(value, v) || v < 1) return -3;
-      chain_ws_mb = v;
-      return 0;
-    }
-    if (!strcmp(key, "SWEEP")) {
-      if (!on || !strcmp(value, "auto")) { sweep = 0; return 0; }
-      if (!strcmp(value, "always")) { sweep = 1; return 0; }
-      if (!strcmp(value, "never")) { sweep = 2; return 0; }
-      return -3;
-    }
-    if (!strcmp(key, "GRAM_SPLITS")) {
-      gs_fields = gs_so = gs_sd = gs_nl = 0;
-      if (on) gs_fields = sscanf(value, "%d,%d,%d", &gs_so, &gs_sd, &gs_nl);
-      return (!on || gs_fields >= 2) ? 0 : -3;
-    }
-    return -2;
-  }
-  void from_environment() {
-    // boolean flags: a variable that is set -- even to the empty string -- switches the flag on
-    for (const char* k : {"NO_LDSDMA", "NO_WAVE_KERNEL", "NO_GRAM_RING", "NO_DIAG_SPLIT", "NO_XCD_SWIZZLE", "NO_MFMA_PROJECT", "PLAN_DEBUG",
-                          "NO_I8_GRAM", "NO_MARG_GEMM", "NO_GRAD_GEMM", "NO_I8_DIAG", "NO_I8_FACTOR", "NO_I8_ROWVECS", "NO_I8_DENSE", "NO_I8_FALLBACK", "NO_BF16X3",
-                          "NO_PLANES", "NO_FP16_PLANES", "PLANES8", "NO_SPEC_ROWMAX", "NO_MULTI_PLANES", "NO_DOWNDATE_LDS"}) {
-      const std::string name = std::string("BLR_MI355X_") + k;
-      if (const char* v = getenv(name.c_str())) (void)set(k, *v ? v : "1");
-    }
-    // valued options: an empty variable is ignored (the built-in default stays), a malformed one too
-    for (const char* k : {"WAVE_SPLIT", "CHAIN_BATCH", "CHAIN_WS_MB", "SWEEP", "GRAM_SPLITS", "I8_PROBE_MIN", "I8_GROUPS"}) {
-      const std::string name = std::string("BLR_MI355X_") + k;
-      if (const char* v = getenv(name.c_str()))
-        if (*v) (void)set(k, v);
-    }
-  }
-};
-
-struct blr_handle {
-  BlrOptions opt;
-  int device = 0;
-  int cus = 256;  // compute units of the device (MI355X: 256; a partitioned part reports its share)
-  hipStream_t own_stream = nullptr;
-  hipStream_t stream = nullptr;
-  bool async = false;
-  std::string err = "";
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  std::vector<void*> staged;  // device buffers of the current HOST-memspace call
-  char* ws = nullptr;          // grow-only scratch (factors, info)
-  size_t ws_bytes = 0;
-  char* feat = nullptr;        // grow-only feature matrix of blr_posterior_rff_*
-  size_t feat_bytes = 0;
-  char* aux = nullptr;         // grow-only: triangular-inverse images of the marginal stream (blr_marginals.hpp), temporaries of logpdf_multi
-  size_t aux_bytes = 0;
-  char* i8side = nullptr;      // grow-only: what the int8 route prepares per call (y / sqrt(s), 1 / sqrt(s), ... -- launch_fused_i8); a buffer of
-  size_t i8side_bytes = 0;     // its own because logpdf_multi carves ITS temporaries from `aux` around a nested update that may take that route
-  char* loo_ws = nullptr;      // grow-only: chunk of mean / latent variance / logpdf of blr_loo_batched_* (the marginal routes it calls
-  size_t loo_ws_bytes = 0;     // use ws and aux themselves)
-  // counters behind blr_get_stat: [0] regressors the int8 route handed back to the fp64 kernel (cumulative); [3] degenerate
-  // leverages of blr_loo_batched_* (cumulative); [8 + 2 k + {0, 1}]:
-  // hand-backs of slice k of the current call (two banks, alternating), read by the NEXT slice's launch (launch_fused_i8)
-  unsigned long long* stats_dev = nullptr;
-  unsigned long long i8_attempted = 0;   // regressors sent down the int8 route (host count)
-  unsigned i8_slices = 0;                // parity = bank of the per-slice hand-back counter
-  const char* route = "none";            // kernel family the most recent posterior dispatch launched (blr_last_route)
-  struct RffSrc { const void *Xin, *Omega, *phase; int64_t ldxin, ldo; double scale; int Din; };
-  const RffSrc* rff_src = nullptr;       // set by posterior_rff around its posterior_batched call: the basis is evaluated inside the planes pass
-  // set by logpdf_multi around its update of column 0 (fp32, ColVecs, D > 128, S <= 128): the other columns of Y ride through the SAME
-  // planes pass, Gram launch and factorisation as one more row block (blr_planes.hpp); the group function leaves what the finish needs
-  struct MultiSrc { const void* Y; int64_t ldY; int S; void* Abar; int64_t lda; void* Tfull; int DP; double* qsp; int nq; bool done; };
-  MultiSrc* multi_src = nullptr;
-  int64_t route_i8_B = 0;                // > 0: that dispatch took the int8 route with this many regressors (blr_last_route looks at its hand-backs)
-  std::string route_buf;
-  // wavefront back substitution (D > 128): tagged exchange buffer, start-order ticket counter, launch epoch
-  unsigned long long* xchg = nullptr;
-  size_t xchg_bytes = 0;
-  unsigned* ticket = nullptr;     // [0], [2], [3]: wavefront solve (tickets, done, launch count); [16 + 128 bank + g]: arrivals of panel_chain_kernel
-  unsigned panel_launches = 0;    // parity = the bank of arrival words the next panel launch counts in (it clears the other one)
-  // kernels whose dynamic-LDS limit has been raised on this handle's device (hipFuncSetAttribute is per device and costs a
-  // driver call: once per (handle, kernel), not once per launch -- it sat on the launch path of the 5 us wave kernel)
-  std::unordered_map<const void*, size_t> lds_limit;
-  // multi-round Gram launches: (row blocks, N, slots) -> (off-diagonal ranges, diagonal ranges, tiles with one range less)
-  std::map<std::array<int, 3>, std::array<int, 3>> gram_plans;
-  // RCCL communicator of blr_comm_init (one rank per handle / GPU); NULL until then
-  ncclComm_t comm = nullptr;
-  int comm_size = 0, comm_rank = 0;
-};
 
 namespace {
 
@@ -252,18 +95,6 @@ static_assert(planes_pass_lds(true, true, 8) <= 65536 && planes_pass_lds(true, f
                   planes_pass_lds(true, false, kRffFusedMaxDin + 1) > 65536,
               "kRffFusedMaxDin: the largest D_in whose planes pass fits in 64 KiB of LDS (the chosen cap)");
 
-int hip_fail(blr_handle* h, hipError_t e, const char* what) {
-  if (h) {
-    h->err = std::string(what) + ": " + hipGetErrorString(e);
-  }
-  return -(1000 + (int)e);
-}
-#define HIP_TRY(h, expr)                                   \
-  do {                                                     \
-    hipError_t e__ = (expr);                               \
-    if (e__ != hipSuccess) return hip_fail(h, e__, #expr); \
-  } while (0)
-
 int set_lds_once(blr_handle* h, const void* kern, size_t bytes) {
   auto it = h->lds_limit.find(kern);
   if (it != h->lds_limit.end() && it->second >= bytes) return 0;
@@ -277,67 +108,6 @@ int bad_arg(blr_handle* h, int pos, const char* why) {
   return -pos;
 }
 
-struct Staging {  // RAII for the device temporaries of one call; nests (an inner guard frees only what it added)
-  blr_handle* h;
-  size_t base;
-  explicit Staging(blr_handle* hh) : h(hh), base(hh->staged.size()) {}
-  ~Staging() {
-    for (size_t i = base; i < h->staged.size(); ++i) (void)hipFree(h->staged[i]);
-    h->staged.resize(base);
-  }
-};
-
-template <typename T>
-int stage_in(blr_handle* h, const T* host, size_t count, const T** dev) {
-  *dev = nullptr;
-  if (!host || count == 0) return 0;
-  void* p = nullptr;
-  HIP_TRY(h, hipMalloc(&p, count * sizeof(T)));
-  h->staged.push_back(p);
-  HIP_TRY(h, hipMemcpyAsync(p, host, count * sizeof(T), hipMemcpyHostToDevice, h->stream));
-  *dev = static_cast<const T*>(p);
-  return 0;
-}
-template <typename T>
-int stage_out_alloc(blr_handle* h, const T* host_initial, size_t count, T** dev) {
-  // outputs with gaps (ld > rows, stride > extent) keep the caller's bytes in the gaps: copy the
-  // current host contents in first.
-  *dev = nullptr;
-  if (!host_initial || count == 0) return 0;
-  void* p = nullptr;
-  HIP_TRY(h, hipMalloc(&p, count * sizeof(T)));
-  h->staged.push_back(p);
-  HIP_TRY(h, hipMemcpyAsync(p, host_initial, count * sizeof(T), hipMemcpyHostToDevice, h->stream));
-  *dev = static_cast<T*>(p);
-  return 0;
-}
-
-int ensure_ws(blr_handle* h, size_t bytes) {
-  if (bytes <= h->ws_bytes) return 0;
-  if (h->ws) {
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    HIP_TRY(h, hipFree(h->ws));
-    h->ws = nullptr;
-    h->ws_bytes = 0;
-  }
-  size_t want = std::max(bytes, (size_t)1 << 20);
-  HIP_TRY(h, hipMalloc((void**)&h->ws, want));
-  h->ws_bytes = want;
-  return 0;
-}
-
-int ensure_i8side(blr_handle* h, size_t bytes) {
-  if (bytes <= h->i8side_bytes) return 0;
-  if (h->i8side) {
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    HIP_TRY(h, hipFree(h->i8side));
-    h->i8side = nullptr;
-    h->i8side_bytes = 0;
-  }
-  HIP_TRY(h, hipMalloc((void**)&h->i8side, bytes));
-  h->i8side_bytes = bytes;
-  return 0;
-}
 int ensure_stats(blr_handle* h) {
   if (h->stats_dev) return 0;
   HIP_TRY(h, hipMalloc((void**)&h->stats_dev, 16 * sizeof(unsigned long long)));
@@ -345,38 +115,14 @@ int ensure_stats(blr_handle* h) {
   return 0;
 }
 
-int ensure_aux(blr_handle* h, size_t bytes) {
-  if (bytes <= h->aux_bytes) return 0;
-  if (h->aux) {
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    HIP_TRY(h, hipFree(h->aux));
-    h->aux = nullptr;
-    h->aux_bytes = 0;
-  }
-  HIP_TRY(h, hipMalloc((void**)&h->aux, bytes));
-  h->aux_bytes = bytes;
-  return 0;
-}
-
-// Exchange buffer of backsolve_wave_kernel: zero at allocation, afterwards only written by that kernel with launch
-// epochs that are never reused, so a stale granule can never carry the current tag.
+// The handle's counter words and the exchange buffer of backsolve_wave_kernel: zero at allocation, afterwards only written by
+// that kernel with launch epochs that are never reused, so a stale granule can never carry the current tag.
 int ensure_xchg(blr_handle* h, size_t bytes) {
   if (!h->ticket) {
     HIP_TRY(h, hipMalloc((void**)&h->ticket, 2048));
     HIP_TRY(h, hipMemsetAsync(h->ticket, 0, 2048, h->stream));
   }
-  if (bytes <= h->xchg_bytes) return 0;
-  if (h->xchg) {
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    HIP_TRY(h, hipFree(h->xchg));
-    h->xchg = nullptr;
-    h->xchg_bytes = 0;
-  }
-  size_t want = std::max(bytes, (size_t)1 << 18);
-  HIP_TRY(h, hipMalloc((void**)&h->xchg, want));
-  HIP_TRY(h, hipMemsetAsync(h->xchg, 0, want, h->stream));
-  h->xchg_bytes = want;
-  return 0;
+  return h->xchg.reserve(h, bytes, blr_handle::kXchgFloor, true);
 }
 template <typename T>
 constexpr size_t wave_solve_lds() {
@@ -387,7 +133,7 @@ template <typename T>
 int launch_wave_solve(blr_handle* h, WaveSolveArgs<T>& b, int NC, int64_t S) {
   int rc = ensure_xchg(h, (size_t)S * b.DP * 2 * sizeof(unsigned long long));
   if (rc) return rc;
-  b.xchg = h->xchg; b.ticket = h->ticket;  // tickets, the launch count behind the granule tags: device-side (WaveSolveArgs)
+  b.xchg = reinterpret_cast<unsigned long long*>(h->xchg.p); b.ticket = h->ticket;  // tickets, the launch count behind the granule tags: device-side (WaveSolveArgs)
   { const int rc_lds = set_lds_once(h, reinterpret_cast<const void*>(backsolve_wave_kernel<T>), (size_t)((int)wave_solve_lds<T>())); if (rc_lds) return rc_lds; }
   hipLaunchKernelGGL(backsolve_wave_kernel<T>, dim3(NC, (unsigned)S), dim3(kThreads), wave_solve_lds<T>(), h->stream, b);
   const hipError_t le = hipGetLastError();
@@ -503,16 +249,16 @@ int launch_fused_i8(blr_handle* h, const PosteriorArgs<double>& a) {
   }
   if (dense) {
     const size_t np = shared_prior ? 1 : (size_t)grid;
-    if ((rc = ensure_i8side(h, o_prior + ((np * sizeof(double) + 255) & ~(size_t)255) + np * sizeof(int32_t)))) return rc;
+    if ((rc = h->i8side.reserve(h, o_prior + ((np * sizeof(double) + 255) & ~(size_t)255) + np * sizeof(int32_t)))) return rc;
     if ((rc = set_lds_once(h, reinterpret_cast<const void*>(i8_prior_logdet_kernel), kSmall8Lds))) return rc;
   }
   if (diag) {
     const size_t o_rw = (((size_t)grid * a.N * sizeof(double)) + 255) & ~(size_t)255;
     const size_t o_ld = 2 * o_rw, o_mx = o_ld + (((size_t)grid * sizeof(double) + 255) & ~(size_t)255);
     const size_t o_bad = o_mx + (((size_t)grid * sizeof(double) + 255) & ~(size_t)255);
-    if (!dense && (rc = ensure_i8side(h, o_bad + (size_t)grid * sizeof(int32_t)))) return rc;
-    yt = reinterpret_cast<double*>(h->i8side); rw = reinterpret_cast<double*>(h->i8side + o_rw);
-    ld = reinterpret_cast<double*>(h->i8side + o_ld); rmx = reinterpret_cast<double*>(h->i8side + o_mx); bad = reinterpret_cast<int32_t*>(h->i8side + o_bad);
+    if (!dense && (rc = h->i8side.reserve(h, o_bad + (size_t)grid * sizeof(int32_t)))) return rc;
+    yt = reinterpret_cast<double*>(h->i8side.p); rw = reinterpret_cast<double*>(h->i8side.p + o_rw);
+    ld = reinterpret_cast<double*>(h->i8side.p + o_ld); rmx = reinterpret_cast<double*>(h->i8side.p + o_mx); bad = reinterpret_cast<int32_t*>(h->i8side.p + o_bad);
   }
   // Slices: one workgroup per regressor (batches beyond 2^20, or beyond the side buffer, in several launches).  A batch of more than
   // kI8ProbeMin = 4096 regressors (option I8_PROBE_MIN) starts with a PROBE slice of kI8Probe (one round of workgroups on the chip): every later slice reads how
@@ -521,8 +267,8 @@ int launch_fused_i8(blr_handle* h, const PosteriorArgs<double>& a) {
   // "i8_handed_back").  The decision depends on the data of the previous slice only: same inputs, same bits.
   if (dense) {
     const size_t np = shared_prior ? 1 : (size_t)grid;
-    pld = reinterpret_cast<double*>(h->i8side + o_prior);
-    pinfo = reinterpret_cast<int32_t*>(h->i8side + o_prior + ((np * sizeof(double) + 255) & ~(size_t)255));
+    pld = reinterpret_cast<double*>(h->i8side.p + o_prior);
+    pinfo = reinterpret_cast<int32_t*>(h->i8side.p + o_prior + ((np * sizeof(double) + 255) & ~(size_t)255));
     if (shared_prior) {
       hipLaunchKernelGGL(i8_prior_logdet_kernel, dim3(1), dim3(kThreads), kSmall8Lds, h->stream, a.Lw, a.ldl, (int64_t)0, 1, pld, pinfo);
       HIP_TRY(h, hipGetLastError());
@@ -916,7 +662,7 @@ int posterior_large_group(blr_handle* h, const PosteriorArgs<T>& a, int64_t reg0
   G = (int)std::max<size_t>(1, std::min<size_t>((size_t)G, ws_cap / per));  // (the re-planned split may need a little more per regressor)
   int rc;
   for (;;) {  // (a device too full for the whole group's workspace: smaller groups, down to one regressor at a time)
-    rc = ensure_ws(h, per * (size_t)G);
+    rc = h->ws.reserve(h, per * (size_t)G, blr_handle::kWsFloor);
     if (rc == 0 || G == 1) break;
     (void)hipGetLastError();
     h->err.clear();
@@ -927,7 +673,7 @@ int posterior_large_group(blr_handle* h, const PosteriorArgs<T>& a, int64_t reg0
   // Every launch below covers the whole group: regressor g from blockIdx.y / .z, its caller-side arrays by the batch strides
   // and its workspace `per` bytes after its predecessor's (the pointers here are regressor reg0's).
   const int64_t reg = reg0;
-  char* ws = h->ws;
+  char* ws = h->ws.p;
   T* Abar = reinterpret_cast<T*>(ws + o_abar);
   T* W = reinterpret_cast<T*>(ws + o_w);
   T* Gpart = reinterpret_cast<T*>(ws + o_gp);
@@ -1135,7 +881,7 @@ int posterior_large_group(blr_handle* h, const PosteriorArgs<T>& a, int64_t reg0
   // ---- T = L' (for the caller and for the AXPY-form back substitution), then m, posterior mean, evidence: one launch each
   // over the group (blockIdx.z / WaveSolveArgs::group)
   {
-    char* ws = h->ws;
+    char* ws = h->ws.p;
     T* Abar = reinterpret_cast<T*>(ws + o_abar);
     T* Tfull = reinterpret_cast<T*>(ws + o_m);
     // logpdf alone (no posterior mean, no factor wanted): the evidence is complete with the factorisation -- no transpose, no
@@ -1192,8 +938,9 @@ int dispatch_posterior(blr_handle* h, const PosteriorArgs<T>& a) {
   return 0;
 }
 
+// The argument checks of blr_posterior_batched_* (the positions are the documented ABI).  1: nothing to do (B == 0)
 template <typename T>
-int posterior_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t N, const T* X,
+int posterior_check(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t N, const T* X,
                       int64_t ldx, int64_t strideX, const T* y, int64_t stridey, int noise_kind, const T* s,
                       int64_t strides, int prior_kind, const T* mw, int64_t stridemw, const T* Lw, int64_t ldl,
                       int64_t strideLw, T* mw_post, int64_t stride_mwpost, T* T_post, int64_t ldt, int64_t strideT,
@@ -1206,7 +953,7 @@ int posterior_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_
   if (D < 1) return bad_arg(h, 5, "D < 1");
   if (D > kMaxLargeD) return bad_arg(h, 5, "D > 8192 is not supported by this build");
   if (N < 0 || N > (1 << 30)) return bad_arg(h, 6, "N out of range");
-  if (B == 0) return 0;
+  if (B == 0) return 1;
   if (N > 0 && !X) return bad_arg(h, 7, "X is NULL");
   if (layout == BLR_LAYOUT_COLVECS ? ldx < D : ldx < std::max<int64_t>(N, 1)) return bad_arg(h, 8, "ldx too small");
   if (strideX < 0) return bad_arg(h, 9, "strideX < 0");
@@ -1229,7 +976,30 @@ int posterior_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_
   if (Lw_post && ldlp < D) return bad_arg(h, 27, "ldlp < D");
   if (Lw_post && B > 1 && strideLp < (int64_t)mat_extent(D, D, ldlp)) return bad_arg(h, 28, "strideLp too small");
   if (!info) return bad_arg(h, 30, "info is NULL");
+  return 0;
+}
 
+// The update on device pointers: `a` carries them with every dimension, leading dimension and stride (and the rff_* fields of a
+// basis that the planes pass evaluates itself)
+template <typename T>
+int posterior_run(blr_handle* h, PosteriorArgs<T>& a) {
+  a.vec_ok = (a.layout == BLR_LAYOUT_COLVECS && a.D % Mfma<T>::VEC == 0 && aligned16(a.X, a.ldx, a.strideX)) ? 1 : 0;
+  if (a.N == 0) {  // no data: the kernel never dereferences X / y, but keep the pointers valid
+    if (!a.X) a.X = a.mw;
+    if (!a.y) a.y = a.mw;
+  }
+  return dispatch_posterior<T>(h, a);
+}
+
+template <typename T>
+int posterior_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t N, const T* X,
+                      int64_t ldx, int64_t strideX, const T* y, int64_t stridey, int noise_kind, const T* s,
+                      int64_t strides, int prior_kind, const T* mw, int64_t stridemw, const T* Lw, int64_t ldl,
+                      int64_t strideLw, T* mw_post, int64_t stride_mwpost, T* T_post, int64_t ldt, int64_t strideT,
+                      T* Lw_post, int64_t ldlp, int64_t strideLp, double* logpdf, int32_t* info) {
+  int rc = posterior_check<T>(h, memspace, layout, B, D, N, X, ldx, strideX, y, stridey, noise_kind, s, strides, prior_kind, mw, stridemw, Lw,
+                              ldl, strideLw, mw_post, stride_mwpost, T_post, ldt, strideT, Lw_post, ldlp, strideLp, logpdf, info);
+  if (rc) return rc < 0 ? rc : 0;
   HIP_TRY(h, hipSetDevice(h->device));
   PosteriorArgs<T> a{};
   a.ldx = ldx; a.strideX = strideX; a.stridey = stridey; a.strides = strides; a.stridemw = stridemw;
@@ -1238,53 +1008,22 @@ int posterior_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_
   a.layout = layout; a.noise_kind = noise_kind; a.prior_kind = prior_kind;
   a.D = (int)D; a.N = (int)N; a.B = (int)B;
 
-  if (memspace == BLR_MEM_DEVICE) {
-    a.X = X; a.y = y; a.s = s; a.mw = mw; a.Lw = Lw;
-    a.mw_post = mw_post; a.T_post = T_post; a.Lw_post = Lw_post; a.logpdf = logpdf; a.info = info;
-    a.vec_ok = (layout == BLR_LAYOUT_COLVECS && D % Mfma<T>::VEC == 0 && aligned16(X, ldx, strideX)) ? 1 : 0;
-    if (h->rff_src) {
-      a.rff_Xin = static_cast<const T*>(h->rff_src->Xin); a.rff_ldxin = h->rff_src->ldxin;
-      a.rff_Omega = static_cast<const T*>(h->rff_src->Omega); a.rff_ldo = h->rff_src->ldo;
-      a.rff_phase = static_cast<const T*>(h->rff_src->phase); a.rff_scale = (T)h->rff_src->scale; a.rff_Din = h->rff_src->Din;
-    }
-    int rc = dispatch_posterior<T>(h, a);
-    if (rc) return rc;
-    if (!h->async) HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return 0;
-  }
-
-  // host pointers: stage through device copies
-  Staging guard(h);
+  CallIO io(h, memspace);
   const size_t x_one = layout == BLR_LAYOUT_COLVECS ? mat_extent(D, N, ldx) : mat_extent(N, D, ldx);
   const size_t lw_one = prior_kind == BLR_PRIOR_DIAGONAL ? (size_t)D : mat_extent(D, D, ldl);
   const size_t s_one = noise_kind == BLR_NOISE_DIAGONAL ? (size_t)N : 1;
-  int rc;
-  if ((rc = stage_in(h, X, extent(B, strideX, x_one), &a.X))) return rc;
-  if ((rc = stage_in(h, y, extent(B, stridey, (size_t)N), &a.y))) return rc;
-  if ((rc = stage_in(h, s, extent(B, strides, s_one), &a.s))) return rc;
-  if ((rc = stage_in(h, mw, extent(B, stridemw, (size_t)D), &a.mw))) return rc;
-  if ((rc = stage_in(h, Lw, extent(B, strideLw, lw_one), &a.Lw))) return rc;
-  const size_t n_mw = extent(B, stride_mwpost, (size_t)D);
-  const size_t n_T = extent(B, strideT, mat_extent(D, D, ldt));
-  const size_t n_Lp = extent(B, strideLp, mat_extent(D, D, ldlp));
-  if ((rc = stage_out_alloc(h, mw_post, n_mw, &a.mw_post))) return rc;
-  if ((rc = stage_out_alloc(h, T_post, n_T, &a.T_post))) return rc;
-  if ((rc = stage_out_alloc(h, Lw_post, n_Lp, &a.Lw_post))) return rc;
-  if ((rc = stage_out_alloc(h, logpdf, (size_t)B, &a.logpdf))) return rc;
-  if ((rc = stage_out_alloc(h, info, (size_t)B, &a.info))) return rc;
-  if (N == 0) {  // no data: the kernel never dereferences X / y, but keep the pointers valid
-    if (!a.X) a.X = a.mw;
-    if (!a.y) a.y = a.mw;
-  }
-  a.vec_ok = (layout == BLR_LAYOUT_COLVECS && D % Mfma<T>::VEC == 0 && aligned16(a.X, ldx, strideX)) ? 1 : 0;
-  if ((rc = dispatch_posterior<T>(h, a))) return rc;
-  if (mw_post) HIP_TRY(h, hipMemcpyAsync(mw_post, a.mw_post, n_mw * sizeof(T), hipMemcpyDeviceToHost, h->stream));
-  if (T_post) HIP_TRY(h, hipMemcpyAsync(T_post, a.T_post, n_T * sizeof(T), hipMemcpyDeviceToHost, h->stream));
-  if (Lw_post) HIP_TRY(h, hipMemcpyAsync(Lw_post, a.Lw_post, n_Lp * sizeof(T), hipMemcpyDeviceToHost, h->stream));
-  if (logpdf) HIP_TRY(h, hipMemcpyAsync(logpdf, a.logpdf, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(h, hipMemcpyAsync(info, a.info, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(h, hipStreamSynchronize(h->stream));
-  return 0;
+  if ((rc = io.in(X, extent(B, strideX, x_one), &a.X))) return rc;
+  if ((rc = io.in(y, extent(B, stridey, (size_t)N), &a.y))) return rc;
+  if ((rc = io.in(s, extent(B, strides, s_one), &a.s))) return rc;
+  if ((rc = io.in(mw, extent(B, stridemw, (size_t)D), &a.mw))) return rc;
+  if ((rc = io.in(Lw, extent(B, strideLw, lw_one), &a.Lw))) return rc;
+  if ((rc = io.out(mw_post, extent(B, stride_mwpost, (size_t)D), &a.mw_post))) return rc;
+  if ((rc = io.out(T_post, extent(B, strideT, mat_extent(D, D, ldt)), &a.T_post))) return rc;
+  if ((rc = io.out(Lw_post, extent(B, strideLp, mat_extent(D, D, ldlp)), &a.Lw_post))) return rc;
+  if ((rc = io.out(logpdf, (size_t)B, &a.logpdf))) return rc;
+  if ((rc = io.out(info, (size_t)B, &a.info))) return rc;
+  if ((rc = posterior_run<T>(h, a))) return rc;
+  return io.finish();
 }
 
 template <typename T>
@@ -1315,10 +1054,10 @@ int prior_factor(blr_handle* h, int64_t B, int64_t D, int prior_kind, const T* L
     return 0;
   }
   size_t need = (size_t)B * D * D * sizeof(T) + (size_t)B * sizeof(int32_t) + 64;
-  int rc = ensure_ws(h, need);
+  int rc = h->ws.reserve(h, need, blr_handle::kWsFloor);
   if (rc) return rc;
-  T* Uw = reinterpret_cast<T*>(h->ws);
-  int32_t* inf = reinterpret_cast<int32_t*>(h->ws + (((size_t)B * D * D * sizeof(T) + 15) & ~(size_t)15));
+  T* Uw = reinterpret_cast<T*>(h->ws.p);
+  int32_t* inf = reinterpret_cast<int32_t*>(h->ws.p + (((size_t)B * D * D * sizeof(T) + 15) & ~(size_t)15));
   size_t lds = ((size_t)D * (D + 1) / 2 + D) * sizeof(T) + 16;
   auto kern = chol_small_kernel<T>;
   { const int rc_lds = set_lds_once(h, reinterpret_cast<const void*>(kern), (size_t)((int)lds)); if (rc_lds) return rc_lds; }
@@ -1365,9 +1104,9 @@ int marginals_large_group(blr_handle* h, int layout, int64_t B, int64_t D, int64
   const size_t mat = (((size_t)DP * DP * sizeof(T)) + 255) & ~(size_t)255;
   int64_t chunk = std::min<int64_t>(B, std::min<int64_t>(65535, ((int64_t)256 << 20) / ((int64_t)NC * MG::IMG_ELEMS * (int64_t)sizeof(T))));
   if (!u_given) chunk = std::min<int64_t>(chunk, std::min<int64_t>(kChainBatchMax, std::max<int64_t>(1, ((int64_t)1 << 30) / (int64_t)(2 * mat))));
-  if ((rc = ensure_aux(h, (size_t)chunk * NC * MG::IMG_ELEMS * sizeof(T)))) return rc;
-  if (!u_given && (rc = ensure_ws(h, (size_t)chunk * 2 * mat + 256))) return rc;
-  T* const img = reinterpret_cast<T*>(h->aux);
+  if ((rc = h->aux.reserve(h, (size_t)chunk * NC * MG::IMG_ELEMS * sizeof(T)))) return rc;
+  if (!u_given && (rc = h->ws.reserve(h, (size_t)chunk * 2 * mat + 256, blr_handle::kWsFloor))) return rc;
+  T* const img = reinterpret_cast<T*>(h->aux.p);
   HIP_TRY(h, hipMemsetAsync(info_dev, 0, (size_t)B * sizeof(int32_t), h->stream));
   for (int64_t b0 = 0; b0 < B; b0 += chunk) {
     const int nb = (int)std::min<int64_t>(chunk, B - b0);
@@ -1378,8 +1117,8 @@ int marginals_large_group(blr_handle* h, int layout, int64_t B, int64_t D, int64
       hipLaunchKernelGGL(prior_diag_kernel<T>, dim3(1, nb), dim3(kThreads), 0, h->stream, U, ldl, (int)PRIOR_UPPER_FACTOR, (int)D,
                          (double*)nullptr, inf, ScratchInit(), strideLw, (int64_t)sizeof(int32_t));
     } else {  // dense precision: L = chol(Lw) (reference :41), then U = L' with the contraction index contiguous
-      T* Lf = reinterpret_cast<T*>(h->ws);
-      T* Ut = reinterpret_cast<T*>(h->ws + (size_t)chunk * mat);
+      T* Lf = reinterpret_cast<T*>(h->ws.p);
+      T* Ut = reinterpret_cast<T*>(h->ws.p + (size_t)chunk * mat);
       const int64_t mstride = (int64_t)(mat / sizeof(T));
       hipLaunchKernelGGL(prior_copy_kernel<T>, dim3(256, nb), dim3(kThreads), 0, h->stream, Lw + b0 * strideLw, ldl, (int)D, DP, Lf, (int64_t)DP,
                          strideLw, mstride);
@@ -1435,8 +1174,8 @@ int marginals_large_one(blr_handle* h, int layout, int64_t D, int64_t N, const T
   T* Ybar = nullptr;
   if (need_tall) {
     const size_t bytes = (((size_t)ldy * DP * sizeof(T) + 255) & ~(size_t)255) + (size_t)NP * sizeof(double);
-    if ((rc = ensure_ws(h, bytes + 256))) return rc;
-    Ybar = reinterpret_cast<T*>(h->ws);
+    if ((rc = h->ws.reserve(h, bytes + 256, blr_handle::kWsFloor))) return rc;
+    Ybar = reinterpret_cast<T*>(h->ws.p);
   }
   {
     MeanFillArgs<T> m{};
@@ -1470,7 +1209,7 @@ int marginals_large_one(blr_handle* h, int layout, int64_t D, int64_t N, const T
     if ((rc = set_lds<T>(h, reinterpret_cast<const void*>(trsm_block_kernel<T>), TC::LDS_BYTES))) return rc;
     if ((rc = set_lds<T>(h, reinterpret_cast<const void*>(gram_tile_kernel<T>), LC::LDS_BYTES))) return rc;
     const int nyb = NP / kPB;  // row blocks of the input part
-    double* rowsq = reinterpret_cast<double*>(h->ws + (((size_t)ldy * DP * sizeof(T) + 255) & ~(size_t)255));
+    double* rowsq = reinterpret_cast<double*>(h->ws.p + (((size_t)ldy * DP * sizeof(T) + 255) & ~(size_t)255));
     for (int p = 0; p < NC; ++p) {
       const int nblk = (NP + TC::RB - 1) / TC::RB;
       RowSqArgs<T> rs{};  // the row sums of squares ride on the TRSM: block p of a row is final after panel p
@@ -1521,27 +1260,23 @@ int marginals_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_
   if (!info) return bad_arg(h, 23, "info is NULL");
   HIP_TRY(h, hipSetDevice(h->device));
 
-  Staging guard(h);
+  CallIO io(h, memspace);
   MarginalArgs<T> a{};
   a.ldx = ldx; a.strideX = strideX; a.strides = strides; a.stridemw = stridemw;
   a.stridemean = stridemean; a.stridevar = stridevar;
   a.layout = layout; a.noise_kind = noise_kind; a.D = (int)D; a.N = (int)N; a.B = (int)B;
-  const T* Lw_dev = Lw;
-  int32_t* info_out_dev = info;
+  const T* Lw_dev = nullptr;
+  int32_t* info_out_dev = nullptr;
   int rc;
-  if (memspace == BLR_MEM_HOST) {
-    const size_t x_one = layout == BLR_LAYOUT_COLVECS ? mat_extent(D, N, ldx) : mat_extent(N, D, ldx);
-    const size_t lw_one = prior_kind == BLR_PRIOR_DIAGONAL ? (size_t)D : mat_extent(D, D, ldl);
-    if ((rc = stage_in(h, X, extent(B, strideX, x_one), &a.X))) return rc;
-    if ((rc = stage_in(h, s, s ? extent(B, strides, noise_kind == BLR_NOISE_DIAGONAL ? (size_t)N : 1) : 0, &a.s))) return rc;
-    if ((rc = stage_in(h, mw, extent(B, stridemw, (size_t)D), &a.mw))) return rc;
-    if ((rc = stage_in(h, Lw, Lw ? extent(B, strideLw, lw_one) : 0, &Lw_dev))) return rc;
-    if ((rc = stage_out_alloc(h, mean, extent(B, stridemean, (size_t)N), &a.mean))) return rc;
-    if ((rc = stage_out_alloc(h, var, extent(B, stridevar, (size_t)N), &a.var))) return rc;
-    if ((rc = stage_out_alloc(h, info, (size_t)B, &info_out_dev))) return rc;
-  } else {
-    a.X = X; a.s = s; a.mw = mw; a.mean = mean; a.var = var;
-  }
+  const size_t x_one = layout == BLR_LAYOUT_COLVECS ? mat_extent(D, N, ldx) : mat_extent(N, D, ldx);
+  const size_t lw_one = prior_kind == BLR_PRIOR_DIAGONAL ? (size_t)D : mat_extent(D, D, ldl);
+  if ((rc = io.in(X, extent(B, strideX, x_one), &a.X))) return rc;
+  if ((rc = io.in(s, extent(B, strides, noise_kind == BLR_NOISE_DIAGONAL ? (size_t)N : 1), &a.s))) return rc;
+  if ((rc = io.in(mw, extent(B, stridemw, (size_t)D), &a.mw))) return rc;
+  if ((rc = io.in(Lw, extent(B, strideLw, lw_one), &Lw_dev))) return rc;
+  if ((rc = io.out(mean, extent(B, stridemean, (size_t)N), &a.mean))) return rc;
+  if ((rc = io.out(var, extent(B, stridevar, (size_t)N), &a.var))) return rc;
+  if ((rc = io.out(info, (size_t)B, &info_out_dev))) return rc;
   if (D > kMaxSmallD) {  // large-D path: the whole batch on LDS-resident tiles if it qualifies, else one regressor at a time
     if (h->opt.chain_batch == 1 && B > 1) {  // measurements only (tools/group_scan.py): the same kernels, one regressor per set of launches
       rc = 0;
@@ -1563,15 +1298,7 @@ int marginals_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_
       if (rc) return rc;
       rc = 1;
     }
-    if (memspace == BLR_MEM_HOST) {
-      if (mean) HIP_TRY(h, hipMemcpyAsync(mean, a.mean, extent(B, stridemean, (size_t)N) * sizeof(T), hipMemcpyDeviceToHost, h->stream));
-      if (var) HIP_TRY(h, hipMemcpyAsync(var, a.var, extent(B, stridevar, (size_t)N) * sizeof(T), hipMemcpyDeviceToHost, h->stream));
-      HIP_TRY(h, hipMemcpyAsync(info, info_out_dev, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-      HIP_TRY(h, hipStreamSynchronize(h->stream));
-    } else if (!h->async) {
-      HIP_TRY(h, hipStreamSynchronize(h->stream));
-    }
-    return 0;
+    return io.finish();
   }
   int32_t* chol_info = nullptr;
   int kind = prior_kind;
@@ -1593,11 +1320,11 @@ int marginals_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_
     using G = MargGemmCfg<T>;
     using TC = TrsmCfg<T>;
     const int64_t chunk = std::min<int64_t>(std::min<int64_t>(B, 65535), ((int64_t)256 << 20) / (G::IMG_ELEMS * (int64_t)sizeof(T)));
-    if ((rc = ensure_aux(h, (size_t)chunk * G::IMG_ELEMS * sizeof(T)))) return rc;
+    if ((rc = h->aux.reserve(h, (size_t)chunk * G::IMG_ELEMS * sizeof(T)))) return rc;
     if ((rc = set_lds_once(h, reinterpret_cast<const void*>(marg_image_kernel<T>), (size_t)TC::LDS_BYTES))) return rc;
     void (*const gemm_kern)(MarginalArgs<T>, const T*) = rowv ? marginals_gemm_kernel<T, true> : marginals_gemm_kernel<T, false>;
     if ((rc = set_lds_once(h, reinterpret_cast<const void*>(gemm_kern), (size_t)G::LDS_BYTES))) return rc;
-    T* const img = reinterpret_cast<T*>(h->aux);
+    T* const img = reinterpret_cast<T*>(h->aux.p);
     const int64_t ntiles = (N + 15) / 16;
     for (int64_t b0 = 0; b0 < B; b0 += chunk) {
       const int64_t nb = std::min<int64_t>(chunk, B - b0);
@@ -1632,15 +1359,7 @@ int marginals_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_
     }
   }
   HIP_TRY(h, hipGetLastError());
-  if (memspace == BLR_MEM_HOST) {
-    if (mean) HIP_TRY(h, hipMemcpyAsync(mean, a.mean, extent(B, stridemean, (size_t)N) * sizeof(T), hipMemcpyDeviceToHost, h->stream));
-    if (var) HIP_TRY(h, hipMemcpyAsync(var, a.var, extent(B, stridevar, (size_t)N) * sizeof(T), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(info, info_out_dev, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-  } else if (!h->async) {
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-  }
-  return 0;
+  return io.finish();
 }
 
 // ---- N-sharded single regressor: additive statistics of a column block, and the finish from their sum ----
@@ -1684,9 +1403,9 @@ int gram_stats(blr_handle* h, int layout, int64_t D64, int64_t N64, const T* X, 
   const size_t o_wv = carve(noise_kind == BLR_NOISE_DIAGONAL ? (size_t)N * sizeof(T) : 0);  // 1 / s_n for the Gram launch
   const size_t o_q = carve((size_t)gridc * sizeof(double));
   const size_t o_l = carve((size_t)gridc * sizeof(double));
-  int rc = ensure_ws(h, off);
+  int rc = h->ws.reserve(h, off, blr_handle::kWsFloor);
   if (rc) return rc;
-  char* ws = h->ws;
+  char* ws = h->ws.p;
   T* Gpart = reinterpret_cast<T*>(ws + o_gp);
   double* bpart = reinterpret_cast<double*>(ws + o_bp);
   T* rvec = reinterpret_cast<T*>(ws + o_r);
@@ -1751,9 +1470,9 @@ int posterior_from_stats(blr_handle* h, int64_t D64, int64_t N_total, T* stats, 
   const size_t o_w = carve(prior_kind == BLR_PRIOR_DENSE ? (size_t)DP * DP * sizeof(T) : 0);
   const size_t o_m = carve((size_t)DP * DP * sizeof(T));
   const size_t o_sc = carve(64);
-  int rc = ensure_ws(h, off);
+  int rc = h->ws.reserve(h, off, blr_handle::kWsFloor);
   if (rc) return rc;
-  char* ws = h->ws;
+  char* ws = h->ws.p;
   T* W = reinterpret_cast<T*>(ws + o_w);
   T* Tfull = reinterpret_cast<T*>(ws + o_m);
   double* logdetLw = reinterpret_cast<double*>(ws + o_sc);
@@ -1827,15 +1546,15 @@ int logpdf_grad_large_group(blr_handle* h, int G, int layout, int64_t D, int64_t
   const size_t o_w = carve((size_t)NP * sizeof(T));
   const size_t o_part = carve(dmw ? (size_t)(NP / 64) * DP * sizeof(double) : 0);
   const int64_t wsb = (int64_t)off;  // one regressor's slice
-  int rc = ensure_ws(h, off * (size_t)G);
+  int rc = h->ws.reserve(h, off * (size_t)G, blr_handle::kWsFloor);
   if (rc) return rc;
-  T* Ybar = reinterpret_cast<T*>(h->ws + o_y);
-  double* rowsq = reinterpret_cast<double*>(h->ws + o_sq);
-  T* mu = reinterpret_cast<T*>(h->ws + o_mu);
-  T* var = reinterpret_cast<T*>(h->ws + o_var);
-  T* rvec = reinterpret_cast<T*>(h->ws + o_r);
-  T* wvec = reinterpret_cast<T*>(h->ws + o_w);
-  double* part = dmw ? reinterpret_cast<double*>(h->ws + o_part) : nullptr;
+  T* Ybar = reinterpret_cast<T*>(h->ws.p + o_y);
+  double* rowsq = reinterpret_cast<double*>(h->ws.p + o_sq);
+  T* mu = reinterpret_cast<T*>(h->ws.p + o_mu);
+  T* var = reinterpret_cast<T*>(h->ws.p + o_var);
+  T* rvec = reinterpret_cast<T*>(h->ws.p + o_r);
+  T* wvec = reinterpret_cast<T*>(h->ws.p + o_w);
+  double* part = dmw ? reinterpret_cast<double*>(h->ws.p + o_part) : nullptr;
   const unsigned ug = (unsigned)G;
 
   {
@@ -1935,7 +1654,7 @@ int logpdf_grad_batched(blr_handle* h, int memspace, int layout, int64_t B, int6
   if (!info) return bad_arg(h, 36, "info is NULL");
   HIP_TRY(h, hipSetDevice(h->device));
 
-  Staging guard(h);
+  CallIO io(h, memspace);
   PosteriorArgs<T> a{};
   a.ldx = ldx; a.strideX = strideX; a.stridey = stridey; a.strides = strides; a.stridemw = stridemw;
   a.ldl = ldl; a.strideLw = strideLw;
@@ -1947,26 +1666,22 @@ int logpdf_grad_batched(blr_handle* h, int memspace, int layout, int64_t B, int6
   const size_t lw_one = prior_kind == BLR_PRIOR_DIAGONAL ? (size_t)D : mat_extent(D, D, ldl);
   const size_t s_one = noise_kind == BLR_NOISE_DIAGONAL ? (size_t)N : 1;
   int rc;
-  T *dX_d = dX, *dy_d = dy, *ds_d = ds, *dmw_d = dmw, *mwp_d = mw_post, *Ai_d = Ainv;
-  double* lp_d = logpdf;
-  int32_t* info_d = info;
-  if (memspace == BLR_MEM_HOST) {
-    if ((rc = stage_in(h, X, extent(B, strideX, x_one), &a.X))) return rc;
-    if ((rc = stage_in(h, y, extent(B, stridey, (size_t)N), &a.y))) return rc;
-    if ((rc = stage_in(h, s, extent(B, strides, s_one), &a.s))) return rc;
-    if ((rc = stage_in(h, mw, extent(B, stridemw, (size_t)D), &a.mw))) return rc;
-    if ((rc = stage_in(h, Lw, extent(B, strideLw, lw_one), &a.Lw))) return rc;
-    if ((rc = stage_out_alloc(h, dX, extent(B, stridedX, dx_one), &dX_d))) return rc;
-    if ((rc = stage_out_alloc(h, dy, extent(B, stridedy, (size_t)N), &dy_d))) return rc;
-    if ((rc = stage_out_alloc(h, ds, extent(B, strideds, (size_t)N), &ds_d))) return rc;
-    if ((rc = stage_out_alloc(h, dmw, extent(B, stridedmw, (size_t)D), &dmw_d))) return rc;
-    if ((rc = stage_out_alloc(h, mw_post, extent(B, stride_mwpost, (size_t)D), &mwp_d))) return rc;
-    if ((rc = stage_out_alloc(h, Ainv, extent(B, strideAi, mat_extent(D, D, ldai)), &Ai_d))) return rc;
-    if ((rc = stage_out_alloc(h, logpdf, (size_t)B, &lp_d))) return rc;
-    if ((rc = stage_out_alloc(h, info, (size_t)B, &info_d))) return rc;
-  } else {
-    a.X = X; a.y = y; a.s = s; a.mw = mw; a.Lw = Lw;
-  }
+  T *dX_d = nullptr, *dy_d = nullptr, *ds_d = nullptr, *dmw_d = nullptr, *mwp_d = nullptr, *Ai_d = nullptr;
+  double* lp_d = nullptr;
+  int32_t* info_d = nullptr;
+  if ((rc = io.in(X, extent(B, strideX, x_one), &a.X))) return rc;
+  if ((rc = io.in(y, extent(B, stridey, (size_t)N), &a.y))) return rc;
+  if ((rc = io.in(s, extent(B, strides, s_one), &a.s))) return rc;
+  if ((rc = io.in(mw, extent(B, stridemw, (size_t)D), &a.mw))) return rc;
+  if ((rc = io.in(Lw, extent(B, strideLw, lw_one), &a.Lw))) return rc;
+  if ((rc = io.out(dX, extent(B, stridedX, dx_one), &dX_d))) return rc;
+  if ((rc = io.out(dy, extent(B, stridedy, (size_t)N), &dy_d))) return rc;
+  if ((rc = io.out(ds, extent(B, strideds, (size_t)N), &ds_d))) return rc;
+  if ((rc = io.out(dmw, extent(B, stridedmw, (size_t)D), &dmw_d))) return rc;
+  if ((rc = io.out(mw_post, extent(B, stride_mwpost, (size_t)D), &mwp_d))) return rc;
+  if ((rc = io.out(Ainv, extent(B, strideAi, mat_extent(D, D, ldai)), &Ai_d))) return rc;
+  if ((rc = io.out(logpdf, (size_t)B, &lp_d))) return rc;
+  if ((rc = io.out(info, (size_t)B, &info_d))) return rc;
   if (D > kMaxSmallD) {
     // large-D path: the regressors go through the update (posterior_large_group) and through the sweeps over the tall matrix in
     // groups that share every launch; factors and posterior means of a group in buffers of their own
@@ -1983,16 +1698,8 @@ int logpdf_grad_batched(blr_handle* h, int memspace, int layout, int64_t B, int6
     }
     T* Tf = nullptr;
     T* mp = nullptr;
-    {
-      void* p0 = nullptr;
-      HIP_TRY(h, hipMalloc(&p0, (size_t)gmax * D * D * sizeof(T)));
-      h->staged.push_back(p0);
-      Tf = static_cast<T*>(p0);
-      void* p1 = nullptr;
-      HIP_TRY(h, hipMalloc(&p1, (size_t)gmax * D * sizeof(T)));
-      h->staged.push_back(p1);
-      mp = static_cast<T*>(p1);
-    }
+    if ((rc = io.tmp((size_t)gmax * D * D, &Tf))) return rc;
+    if ((rc = io.tmp((size_t)gmax * D, &mp))) return rc;
     a.vec_ok = 0;
     for (int64_t reg = 0; reg < B;) {
       PosteriorArgs<T> one = a;
@@ -2013,22 +1720,7 @@ int logpdf_grad_batched(blr_handle* h, int memspace, int layout, int64_t B, int6
         return rc;
       reg += done;
     }
-    HIP_TRY(h, hipStreamSynchronize(h->stream));  // Tf / mp are temporaries of this call
-    if (memspace == BLR_MEM_HOST) {
-      auto back = [&](void* dst, const void* src, size_t bytes) -> int {
-        if (dst && bytes) HIP_TRY(h, hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
-        return 0;
-      };
-      if ((rc = back(dX, dX_d, extent(B, stridedX, dx_one) * sizeof(T)))) return rc;
-      if ((rc = back(dy, dy_d, extent(B, stridedy, (size_t)N) * sizeof(T)))) return rc;
-      if ((rc = back(ds, ds_d, extent(B, strideds, (size_t)N) * sizeof(T)))) return rc;
-      if ((rc = back(dmw, dmw_d, extent(B, stridedmw, (size_t)D) * sizeof(T)))) return rc;
-      if ((rc = back(mw_post, mwp_d, extent(B, stride_mwpost, (size_t)D) * sizeof(T)))) return rc;
-      if ((rc = back(Ainv, Ai_d, extent(B, strideAi, mat_extent(D, D, ldai)) * sizeof(T)))) return rc;
-      if ((rc = back(logpdf, lp_d, (size_t)B * sizeof(double)))) return rc;
-      if ((rc = back(info, info_d, (size_t)B * sizeof(int32_t)))) return rc;
-    }
-    return 0;
+    return io.finish();  // (drains the stream in either memspace: Tf / mp are temporaries of this call)
   }
   // workspace: factor T [B][D x D], posterior mean (if the caller does not want it), dmw partials
   using TC = TrsmCfg<T>;
@@ -2049,11 +1741,11 @@ int logpdf_grad_batched(blr_handle* h, int memspace, int layout, int64_t B, int6
   const size_t o_mp = carve(mwp_d ? 0 : (size_t)B * D * sizeof(T));
   const size_t o_part = carve(dmw_d ? (size_t)B * per_reg * kPB * sizeof(double) : 0);
   const size_t o_img = carve(gemm ? (size_t)B * 2 * MG::IMG_ELEMS * sizeof(T) : 0);
-  if ((rc = ensure_ws(h, off))) return rc;
-  T* Tf = reinterpret_cast<T*>(h->ws + o_T);
+  if ((rc = h->ws.reserve(h, off, blr_handle::kWsFloor))) return rc;
+  T* Tf = reinterpret_cast<T*>(h->ws.p + o_T);
   int64_t smp = stride_mwpost;
-  if (!mwp_d) { mwp_d = reinterpret_cast<T*>(h->ws + o_mp); smp = D; }
-  double* part = dmw_d ? reinterpret_cast<double*>(h->ws + o_part) : nullptr;
+  if (!mwp_d) { mwp_d = reinterpret_cast<T*>(h->ws.p + o_mp); smp = D; }
+  double* part = dmw_d ? reinterpret_cast<double*>(h->ws.p + o_part) : nullptr;
 
   a.mw_post = mwp_d; a.stride_mwpost = smp;
   a.T_post = Tf; a.ldt = D; a.strideT = D * D;
@@ -2071,7 +1763,7 @@ int logpdf_grad_batched(blr_handle* h, int memspace, int layout, int64_t B, int6
     if ((rc = set_lds_once(h, reinterpret_cast<const void*>(marg_image_kernel<T>), (size_t)TC::LDS_BYTES))) return rc;
     void (*const gg_kern)(GradArgs<T>, const T*, const T*) = rowv ? grad_gemm_kernel<T, true> : grad_gemm_kernel<T, false>;
     if ((rc = set_lds_once(h, reinterpret_cast<const void*>(gg_kern), (size_t)GG::LDS_BYTES))) return rc;
-    T* const img = reinterpret_cast<T*>(h->ws + o_img);
+    T* const img = reinterpret_cast<T*>(h->ws.p + o_img);
     T* const img2 = img + B * MG::IMG_ELEMS;
     hipLaunchKernelGGL(marg_image_kernel<T>, dim3((unsigned)B, 2), dim3(kThreads), TC::LDS_BYTES, h->stream, (const T*)Tf, D, D * D, (int)D, img,
                        (const int32_t*)info_d, 0, 0, 1, (int64_t)0, img2);
@@ -2094,24 +1786,7 @@ int logpdf_grad_batched(blr_handle* h, int memspace, int layout, int64_t B, int6
                          dmw_d, stridedmw, (int)D);
   }
   HIP_TRY(h, hipGetLastError());
-  if (memspace == BLR_MEM_HOST) {
-    auto back = [&](void* dst, const void* src, size_t bytes) -> int {
-      if (dst && bytes) HIP_TRY(h, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream));
-      return 0;
-    };
-    if ((rc = back(dX, dX_d, extent(B, stridedX, dx_one) * sizeof(T)))) return rc;
-    if ((rc = back(dy, dy_d, extent(B, stridedy, (size_t)N) * sizeof(T)))) return rc;
-    if ((rc = back(ds, ds_d, extent(B, strideds, (size_t)N) * sizeof(T)))) return rc;
-    if ((rc = back(dmw, dmw_d, extent(B, stridedmw, (size_t)D) * sizeof(T)))) return rc;
-    if ((rc = back(mw_post, mwp_d, extent(B, stride_mwpost, (size_t)D) * sizeof(T)))) return rc;
-    if ((rc = back(Ainv, Ai_d, extent(B, strideAi, mat_extent(D, D, ldai)) * sizeof(T)))) return rc;
-    if ((rc = back(logpdf, lp_d, (size_t)B * sizeof(double)))) return rc;
-    if ((rc = back(info, info_d, (size_t)B * sizeof(int32_t)))) return rc;
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-  } else if (!h->async) {
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-  }
-  return 0;
+  return io.finish();
 }
 
 // ---- shared-X multi-output evidence: logpdf(fx, Y::Matrix), optional per-column posterior means ----
@@ -2145,24 +1820,22 @@ int logpdf_multi(blr_handle* h, int memspace, int layout, int64_t D, int64_t N, 
 
   using TC = TrsmCfg<T>;
   using LC = LargeCfg<T>;
-  Staging guard(h);
+  CallIO io(h, memspace);
   int rc;
-  const T *X_d = X, *Y_d = Y, *s_d = s, *mw_d = mw, *Lw_d = Lw;
-  double* lp_d = logpdf;
-  T* mp_d = mw_post;
-  int32_t* info_d = info;
-  if (memspace == BLR_MEM_HOST) {
-    const size_t x_one = layout == BLR_LAYOUT_COLVECS ? mat_extent(D, N, ldx) : mat_extent(N, D, ldx);
-    const size_t lw_one = prior_kind == BLR_PRIOR_DIAGONAL ? (size_t)D : mat_extent(D, D, ldl);
-    if ((rc = stage_in(h, X, x_one, &X_d))) return rc;
-    if ((rc = stage_in(h, Y, mat_extent(N, S, ldY), &Y_d))) return rc;
-    if ((rc = stage_in(h, s, noise_kind == BLR_NOISE_DIAGONAL ? (size_t)N : 1, &s_d))) return rc;
-    if ((rc = stage_in(h, mw, (size_t)D, &mw_d))) return rc;
-    if ((rc = stage_in(h, Lw, lw_one, &Lw_d))) return rc;
-    if ((rc = stage_out_alloc(h, logpdf, (size_t)S, &lp_d))) return rc;
-    if ((rc = stage_out_alloc(h, mw_post, mw_post ? mat_extent(D, S, ldmp) : 0, &mp_d))) return rc;
-    if ((rc = stage_out_alloc(h, info, (size_t)1, &info_d))) return rc;
-  }
+  const T *X_d = nullptr, *Y_d = nullptr, *s_d = nullptr, *mw_d = nullptr, *Lw_d = nullptr;
+  double* lp_d = nullptr;
+  T* mp_d = nullptr;
+  int32_t* info_d = nullptr;
+  const size_t x_one = layout == BLR_LAYOUT_COLVECS ? mat_extent(D, N, ldx) : mat_extent(N, D, ldx);
+  const size_t lw_one = prior_kind == BLR_PRIOR_DIAGONAL ? (size_t)D : mat_extent(D, D, ldl);
+  if ((rc = io.in(X, x_one, &X_d))) return rc;
+  if ((rc = io.in(Y, mat_extent(N, S, ldY), &Y_d))) return rc;
+  if ((rc = io.in(s, noise_kind == BLR_NOISE_DIAGONAL ? (size_t)N : 1, &s_d))) return rc;
+  if ((rc = io.in(mw, (size_t)D, &mw_d))) return rc;
+  if ((rc = io.in(Lw, lw_one, &Lw_d))) return rc;
+  if ((rc = io.out(logpdf, (size_t)S, &lp_d))) return rc;
+  if ((rc = io.out(mw_post, mat_extent(D, S, ldmp), &mp_d))) return rc;
+  if ((rc = io.out(info, (size_t)1, &info_d))) return rc;
   const int DP = (int)((D + kPB - 1) / kPB * kPB), NC = DP / kPB;
   // fp32, ColVecs, D > 128, up to 128 columns: the residuals of ALL columns ride through the update of column 0 as one more row block of
   // operand planes -- their b_s = X Sigma^-1 (y_s - mu) come out of the same Gram launch (NC + 1 more macro tiles), their u_s = L^-1 b_s
@@ -2175,8 +1848,8 @@ int logpdf_multi(blr_handle* h, int memspace, int layout, int64_t D, int64_t N, 
       void *vTf, *vlp0;
       {
         const size_t sz_tf = mp_d ? (((size_t)D * D * sizeof(T) + 255) & ~(size_t)255) : 0;
-        if ((rc = ensure_aux(h, sz_tf + 256))) return rc;
-        vTf = h->aux; vlp0 = h->aux + sz_tf;
+        if ((rc = h->aux.reserve(h, sz_tf + 256))) return rc;
+        vTf = h->aux.p; vlp0 = h->aux.p + sz_tf;
       }
       T* Tf = static_cast<T*>(vTf);
       double* lp0 = static_cast<double*>(vlp0);
@@ -2204,15 +1877,7 @@ int logpdf_multi(blr_handle* h, int memspace, int layout, int64_t D, int64_t N, 
         if ((rc = launch_wave_solve<T>(h, b, NC, S))) return rc;
       }
       HIP_TRY(h, hipGetLastError());
-      if (memspace == BLR_MEM_HOST) {
-        HIP_TRY(h, hipMemcpyAsync(logpdf, lp_d, (size_t)S * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        if (mw_post) HIP_TRY(h, hipMemcpyAsync(mw_post, mp_d, mat_extent(D, S, ldmp) * sizeof(T), hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(h, hipMemcpyAsync(info, info_d, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-      } else if (!h->async) {
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-      }
-      return 0;
+      return io.finish();
     }
   }
   const int SP = (int)((S + kPB - 1) / kPB * kPB);
@@ -2233,10 +1898,10 @@ int logpdf_multi(blr_handle* h, int memspace, int layout, int64_t D, int64_t N, 
     void** const outs[11] = {&vTf, &vlp0, &vmu, &vR, &vq, &vG, &vY, &vsq, &vuu, &vzero, &vinfo2};
     size_t total = 0;
     for (size_t b : sizes) total += (b + 255) & ~(size_t)255;
-    if ((rc = ensure_aux(h, total))) return rc;
+    if ((rc = h->aux.reserve(h, total))) return rc;
     size_t off = 0;
     for (int i = 0; i < 11; ++i) {
-      *outs[i] = h->aux + off;
+      *outs[i] = h->aux.p + off;
       off += (sizes[i] + 255) & ~(size_t)255;
     }
   }
@@ -2333,15 +1998,7 @@ int logpdf_multi(blr_handle* h, int memspace, int layout, int64_t D, int64_t N, 
                        mp_d, ldmp);
   }
   HIP_TRY(h, hipGetLastError());
-  if (memspace == BLR_MEM_HOST) {
-    HIP_TRY(h, hipMemcpyAsync(logpdf, lp_d, (size_t)S * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (mw_post) HIP_TRY(h, hipMemcpyAsync(mw_post, mp_d, mat_extent(D, S, ldmp) * sizeof(T), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(info, info_d, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-  } else if (!h->async) {
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-  }
-  return 0;
+  return io.finish();
 }
 
 // D > 128: W[:, s] = mw + U^-1 Z[:, s] with U = chol(Lw).U -- the wavefront back substitution of the posterior path with
@@ -2361,9 +2018,9 @@ int sample_weights_large(blr_handle* h, int64_t D, int64_t S, int prior_kind, co
   const size_t o_tf = carve((size_t)DP * DP * sizeof(T));
   const size_t o_wk = carve(prior_kind == BLR_PRIOR_DENSE ? (size_t)DP * DP * sizeof(T) : 0);
   const size_t o_info = carve(64);
-  int rc = ensure_ws(h, off);
+  int rc = h->ws.reserve(h, off, blr_handle::kWsFloor);
   if (rc) return rc;
-  char* ws = h->ws;
+  char* ws = h->ws.p;
   T* Tf = reinterpret_cast<T*>(ws + o_tf);
   int32_t* info_dev = reinterpret_cast<int32_t*>(ws + o_info);
   if (prior_kind == BLR_PRIOR_UPPER_FACTOR) {
@@ -2394,39 +2051,25 @@ int sample_weights_large(blr_handle* h, int64_t D, int64_t S, int prior_kind, co
 }
 
 template <typename T>
-int sample_weights_impl(blr_handle* h, int memspace, int64_t D, int64_t S, int prior_kind, const T* mw, const T* Lw,
-                        int64_t ldl, const T* Z, int64_t ldz, T* W, int64_t ldw, bool sync_and_copy, T** W_dev_out,
-                        Staging* outer) {
-  (void)outer;
-  const T *mw_d = mw, *Lw_d = Lw, *Z_d = Z;
-  T* W_d = W;
+int sample_weights_impl(blr_handle* h, CallIO& io, int64_t D, int64_t S, int prior_kind, const T* mw, const T* Lw,
+                        int64_t ldl, const T* Z, int64_t ldz, T* W, int64_t ldw, T** W_dev_out) {  // (the caller's io.finish() ends the call)
+  const T *mw_d = nullptr, *Lw_d = nullptr, *Z_d = nullptr;
+  T* W_d = nullptr;
   int rc;
-  if (memspace == BLR_MEM_HOST) {
-    const size_t lw_one = prior_kind == BLR_PRIOR_DIAGONAL ? (size_t)D : mat_extent(D, D, ldl);
-    if ((rc = stage_in(h, mw, (size_t)D, &mw_d))) return rc;
-    if ((rc = stage_in(h, Lw, lw_one, &Lw_d))) return rc;
-    if ((rc = stage_in(h, Z, mat_extent(D, S, ldz), &Z_d))) return rc;
-    if (W) {
-      if ((rc = stage_out_alloc(h, W, mat_extent(D, S, ldw), &W_d))) return rc;
-    }
-  }
+  const size_t lw_one = prior_kind == BLR_PRIOR_DIAGONAL ? (size_t)D : mat_extent(D, D, ldl);
+  if ((rc = io.in(mw, (size_t)D, &mw_d))) return rc;
+  if ((rc = io.in(Lw, lw_one, &Lw_d))) return rc;
+  if ((rc = io.in(Z, mat_extent(D, S, ldz), &Z_d))) return rc;
+  if ((rc = io.out(W, mat_extent(D, S, ldw), &W_d))) return rc;
   if (!W_d) {  // internal temporary (rand): dense D x S, in the handle's grow-only side buffer -- a hipMalloc / hipFree pair and
                // the drain in front of the free were most of a small call (64 draws at D = 128: 68 us, the kernels 20)
-    if ((rc = ensure_aux(h, (size_t)D * S * sizeof(T)))) return rc;
-    W_d = reinterpret_cast<T*>(h->aux);
+    if ((rc = h->aux.reserve(h, (size_t)D * S * sizeof(T)))) return rc;
+    W_d = reinterpret_cast<T*>(h->aux.p);
     ldw = D;
   }
   if (D > kMaxSmallD) {
     if ((rc = sample_weights_large<T>(h, D, S, prior_kind, mw_d, Lw_d, ldl, Z_d, ldz, W_d, ldw))) return rc;
     if (W_dev_out) *W_dev_out = W_d;
-    if (sync_and_copy) {
-      if (memspace == BLR_MEM_HOST) {
-        HIP_TRY(h, hipMemcpyAsync(W, W_d, mat_extent(D, S, ldw) * sizeof(T), hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-      } else if (!h->async) {
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-      }
-    }
     return 0;
   }
   const T* U;
@@ -2453,14 +2096,6 @@ int sample_weights_impl(blr_handle* h, int memspace, int64_t D, int64_t S, int p
   }
   HIP_TRY(h, hipGetLastError());
   if (W_dev_out) *W_dev_out = W_d;
-  if (sync_and_copy) {
-    if (memspace == BLR_MEM_HOST) {
-      HIP_TRY(h, hipMemcpyAsync(W, W_d, mat_extent(D, S, ldw) * sizeof(T), hipMemcpyDeviceToHost, h->stream));
-      HIP_TRY(h, hipStreamSynchronize(h->stream));
-    } else if (!h->async) {
-      HIP_TRY(h, hipStreamSynchronize(h->stream));
-    }
-  }
   return 0;
 }
 
@@ -2483,8 +2118,9 @@ int sample_weights(blr_handle* h, int memspace, int64_t D, int64_t S, int prior_
   if (!W) return bad_arg(h, 11, "W is NULL");
   if (ldw < D) return bad_arg(h, 12, "ldw < D");
   HIP_TRY(h, hipSetDevice(h->device));
-  Staging guard(h);
-  return sample_weights_impl<T>(h, memspace, D, S, prior_kind, mw, Lw, ldl, Z, ldz, W, ldw, true, nullptr, &guard);
+  CallIO io(h, memspace);
+  const int rc = sample_weights_impl<T>(h, io, D, S, prior_kind, mw, Lw, ldl, Z, ldz, W, ldw, nullptr);
+  return rc ? rc : io.finish();
 }
 
 // Y (N x S) = X'W (+ sqrt.(s) .* Z2 when Z2 != NULL): device pointers
@@ -2525,25 +2161,17 @@ int apply_weights(blr_handle* h, int memspace, int layout, int64_t D, int64_t N,
   if (!Y) return bad_arg(h, 11, "Y is NULL");
   if (ldy < N) return bad_arg(h, 12, "ldy < N");
   HIP_TRY(h, hipSetDevice(h->device));
-  Staging guard(h);
-  const T *X_d = X, *W_d = W;
-  T* Y_d = Y;
+  CallIO io(h, memspace);
+  const T *X_d = nullptr, *W_d = nullptr;
+  T* Y_d = nullptr;
   int rc;
-  if (memspace == BLR_MEM_HOST) {
-    const size_t x_one = layout == BLR_LAYOUT_COLVECS ? mat_extent(D, N, ldx) : mat_extent(N, D, ldx);
-    if ((rc = stage_in(h, X, x_one, &X_d))) return rc;
-    if ((rc = stage_in(h, W, mat_extent(D, S, ldw), &W_d))) return rc;
-    if ((rc = stage_out_alloc(h, Y, mat_extent(N, S, ldy), &Y_d))) return rc;
-  }
+  const size_t x_one = layout == BLR_LAYOUT_COLVECS ? mat_extent(D, N, ldx) : mat_extent(N, D, ldx);
+  if ((rc = io.in(X, x_one, &X_d))) return rc;
+  if ((rc = io.in(W, mat_extent(D, S, ldw), &W_d))) return rc;
+  if ((rc = io.out(Y, mat_extent(N, S, ldy), &Y_d))) return rc;
   launch_project<T>(h, layout, D, N, S, X_d, ldx, W_d, ldw, (const T*)nullptr, BLR_NOISE_ISOTROPIC, (const T*)nullptr, 0, Y_d, ldy);
   HIP_TRY(h, hipGetLastError());
-  if (memspace == BLR_MEM_HOST) {
-    HIP_TRY(h, hipMemcpyAsync(Y, Y_d, mat_extent(N, S, ldy) * sizeof(T), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-  } else if (!h->async) {
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-  }
-  return 0;
+  return io.finish();
 }
 
 template <typename T>
@@ -2574,28 +2202,22 @@ int rand_impl(blr_handle* h, int memspace, int layout, int64_t D, int64_t N, int
   if (!Y) return bad_arg(h, 19, "Y is NULL");
   if (ldy < N) return bad_arg(h, 20, "ldy < N");
   HIP_TRY(h, hipSetDevice(h->device));
-  Staging guard(h);
+  CallIO io(h, memspace);
   T* W_dev = nullptr;
   // weights first (Z1 is the FIRST randn draw of reference :51), host staging handled inside
-  int rc = sample_weights_impl<T>(h, memspace, D, S, prior_kind, mw, Lw, ldl, Z1, ldz1, (T*)nullptr, D, false, &W_dev, &guard);
+  int rc = sample_weights_impl<T>(h, io, D, S, prior_kind, mw, Lw, ldl, Z1, ldz1, (T*)nullptr, D, &W_dev);
   if (rc) return rc;
-  const T *X_d = X, *s_d = s, *Z2_d = Z2;
-  T* Y_d = Y;
-  if (memspace == BLR_MEM_HOST) {
-    const size_t x_one = layout == BLR_LAYOUT_COLVECS ? mat_extent(D, N, ldx) : mat_extent(N, D, ldx);
-    if ((rc = stage_in(h, X, x_one, &X_d))) return rc;
-    if ((rc = stage_in(h, s, noise_kind == BLR_NOISE_DIAGONAL ? (size_t)N : 1, &s_d))) return rc;
-    if ((rc = stage_in(h, Z2, mat_extent(N, S, ldz2), &Z2_d))) return rc;
-    if ((rc = stage_out_alloc(h, Y, mat_extent(N, S, ldy), &Y_d))) return rc;
-  }
+  const T *X_d = nullptr, *s_d = nullptr, *Z2_d = nullptr;
+  T* Y_d = nullptr;
+  const size_t x_one = layout == BLR_LAYOUT_COLVECS ? mat_extent(D, N, ldx) : mat_extent(N, D, ldx);
+  if ((rc = io.in(X, x_one, &X_d))) return rc;
+  if ((rc = io.in(s, noise_kind == BLR_NOISE_DIAGONAL ? (size_t)N : 1, &s_d))) return rc;
+  if ((rc = io.in(Z2, mat_extent(N, S, ldz2), &Z2_d))) return rc;
+  if ((rc = io.out(Y, mat_extent(N, S, ldy), &Y_d))) return rc;
   launch_project<T>(h, layout, D, N, S, X_d, ldx, (const T*)W_dev, (int64_t)D, s_d, noise_kind, Z2_d, ldz2, Y_d, ldy);
   HIP_TRY(h, hipGetLastError());
-  if (memspace == BLR_MEM_HOST) {
-    HIP_TRY(h, hipMemcpyAsync(Y, Y_d, mat_extent(N, S, ldy) * sizeof(T), hipMemcpyDeviceToHost, h->stream));
-  }
   // (W_dev lives in the handle's side buffer, which is only ever replaced behind a stream synchronisation)
-  if (memspace == BLR_MEM_HOST || !h->async) HIP_TRY(h, hipStreamSynchronize(h->stream));
-  return 0;
+  return io.finish();
 }
 
 // ---- draws from B regressors in one call (blr_rand_batched_*; reference :49-53 and sampling_functions.jl:27-49 under a map) ------
@@ -2643,35 +2265,23 @@ int rand_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, 
   if (B == 0 || S == 0) return 0;
   HIP_TRY(h, hipSetDevice(h->device));
 
-  Staging guard(h);
-  const T *X_d = X, *s_d = s, *mw_d = mw, *Lw_d = Lw, *Z1_d = Z1, *Z2_d = noisy ? Z2 : nullptr;
-  T *W_d = W, *Y_d = proj ? Y : nullptr;
-  int32_t* info_d = info;
+  CallIO io(h, memspace);
+  const T *X_d = nullptr, *s_d = nullptr, *mw_d = nullptr, *Lw_d = nullptr, *Z1_d = nullptr, *Z2_d = nullptr;
+  T *W_d = nullptr, *Y_d = nullptr;
+  int32_t* info_d = nullptr;
   int rc;
-  const size_t nW = W ? extent(B, strideW, mat_extent(D, S, ldw)) : 0, nY = proj ? extent(B, strideY, mat_extent(N, S, ldy)) : 0;
-  if (memspace == BLR_MEM_HOST) {
-    const size_t x_one = layout == BLR_LAYOUT_COLVECS ? mat_extent(D, N, ldx) : mat_extent(N, D, ldx);
-    const size_t lw_one = prior_kind == BLR_PRIOR_DIAGONAL ? (size_t)D : mat_extent(D, D, ldl);
-    if ((rc = stage_in(h, proj ? X : nullptr, extent(B, strideX, x_one), &X_d))) return rc;
-    if ((rc = stage_in(h, noisy ? s : nullptr, extent(B, strides, noise_kind == BLR_NOISE_DIAGONAL ? (size_t)N : 1), &s_d))) return rc;
-    if ((rc = stage_in(h, mw, extent(B, stridemw, (size_t)D), &mw_d))) return rc;
-    if ((rc = stage_in(h, Lw, extent(B, strideLw, lw_one), &Lw_d))) return rc;
-    if ((rc = stage_in(h, Z1, extent(B, strideZ1, mat_extent(D, S, ldz1)), &Z1_d))) return rc;
-    if ((rc = stage_in(h, Z2_d, extent(B, strideZ2, mat_extent(N, S, ldz2)), &Z2_d))) return rc;
-    if ((rc = stage_out_alloc(h, W, nW, &W_d))) return rc;
-    if ((rc = stage_out_alloc(h, Y_d, nY, &Y_d))) return rc;
-    if ((rc = stage_out_alloc(h, info, (size_t)B, &info_d))) return rc;
-  }
-  auto finish = [&]() -> int {
-    HIP_TRY(h, hipGetLastError());
-    if (memspace == BLR_MEM_HOST) {
-      if (W) HIP_TRY(h, hipMemcpyAsync(W, W_d, nW * sizeof(T), hipMemcpyDeviceToHost, h->stream));
-      if (proj) HIP_TRY(h, hipMemcpyAsync(Y, Y_d, nY * sizeof(T), hipMemcpyDeviceToHost, h->stream));
-      HIP_TRY(h, hipMemcpyAsync(info, info_d, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    }
-    if (memspace == BLR_MEM_HOST || !h->async) HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return 0;
-  };
+  const size_t x_one = layout == BLR_LAYOUT_COLVECS ? mat_extent(D, N, ldx) : mat_extent(N, D, ldx);
+  const size_t lw_one = prior_kind == BLR_PRIOR_DIAGONAL ? (size_t)D : mat_extent(D, D, ldl);
+  // (X without a projection and s without noise are not staged: a count of 0)
+  if ((rc = io.in(X, proj ? extent(B, strideX, x_one) : 0, &X_d))) return rc;
+  if ((rc = io.in(s, noisy ? extent(B, strides, noise_kind == BLR_NOISE_DIAGONAL ? (size_t)N : 1) : 0, &s_d))) return rc;
+  if ((rc = io.in(mw, extent(B, stridemw, (size_t)D), &mw_d))) return rc;
+  if ((rc = io.in(Lw, extent(B, strideLw, lw_one), &Lw_d))) return rc;
+  if ((rc = io.in(Z1, extent(B, strideZ1, mat_extent(D, S, ldz1)), &Z1_d))) return rc;
+  if ((rc = io.in(noisy ? Z2 : (const T*)nullptr, extent(B, strideZ2, mat_extent(N, S, ldz2)), &Z2_d))) return rc;
+  if ((rc = io.out(W, extent(B, strideW, mat_extent(D, S, ldw)), &W_d))) return rc;
+  if ((rc = io.out(proj ? Y : (T*)nullptr, extent(B, strideY, mat_extent(N, S, ldy)), &Y_d))) return rc;
+  if ((rc = io.out(info, (size_t)B, &info_d))) return rc;
 
   if (D > kMaxSmallD) {
     std::vector<int32_t> hinfo((size_t)B, 0);
@@ -2684,8 +2294,8 @@ int rand_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, 
     }
     T* Wtmp = nullptr;
     if (!W_d) {
-      if ((rc = ensure_aux(h, (size_t)D * S * sizeof(T)))) return rc;
-      Wtmp = reinterpret_cast<T*>(h->aux);
+      if ((rc = h->aux.reserve(h, (size_t)D * S * sizeof(T)))) return rc;
+      Wtmp = reinterpret_cast<T*>(h->aux.p);
     }
     for (int64_t b = 0; b < B; ++b) {
       if (hinfo[b]) continue;
@@ -2701,7 +2311,7 @@ int rand_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, 
     }
     HIP_TRY(h, hipMemcpyAsync(info_d, hinfo.data(), (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));  // (hinfo is a host temporary)
-    return finish();
+    return io.finish();
   }
 
   RandBatchedArgs<T> a{};
@@ -2726,8 +2336,8 @@ int rand_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, 
   if (proj && !fuse) {  // the weights for the projection launch: ld rounded to 16 bytes, so its operand loads are aligned
     a.ldwt = (D + 3) & ~(int64_t)3;
     a.strideWt = a.ldwt * S;
-    if ((rc = ensure_aux(h, (size_t)B * a.strideWt * sizeof(T)))) return rc;
-    a.Wt = reinterpret_cast<T*>(h->aux);
+    if ((rc = h->aux.reserve(h, (size_t)B * a.strideWt * sizeof(T)))) return rc;
+    a.Wt = reinterpret_cast<T*>(h->aux.p);
   }
   const bool mfma = !h->opt.no_mfma_project && layout == BLR_LAYOUT_COLVECS && D % Mfma<T>::VEC == 0 && aligned16(X_d, ldx, strideX);
   const int tn = mfma ? ProjCfg<T>::TN : 64, ts = mfma ? ProjCfg<T>::TS : 64;
@@ -2752,7 +2362,7 @@ int rand_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, 
       HIP_TRY(h, hipGetLastError());
     }
   }
-  return finish();
+  return io.finish();
 }
 
 
@@ -2775,27 +2385,19 @@ int rff_features(blr_handle* h, int memspace, int64_t Din, int64_t D, int64_t N,
   if (!Phi) return bad_arg(h, 12, "Phi is NULL");
   if (ldphi < D) return bad_arg(h, 13, "ldphi < D");
   HIP_TRY(h, hipSetDevice(h->device));
-  Staging guard(h);
-  const T *Xd = Xin, *Od = Omega, *Pd = phase;
-  T* Fd = Phi;
+  CallIO io(h, memspace);
+  const T *Xd = nullptr, *Od = nullptr, *Pd = nullptr;
+  T* Fd = nullptr;
   int rc;
-  if (memspace == BLR_MEM_HOST) {
-    if ((rc = stage_in(h, Xin, mat_extent(Din, N, ldxin), &Xd))) return rc;
-    if ((rc = stage_in(h, Omega, mat_extent(Din, D, ldo), &Od))) return rc;
-    if ((rc = stage_in(h, phase, (size_t)D, &Pd))) return rc;
-    if ((rc = stage_out_alloc(h, Phi, mat_extent(D, N, ldphi), &Fd))) return rc;
-  }
+  if ((rc = io.in(Xin, mat_extent(Din, N, ldxin), &Xd))) return rc;
+  if ((rc = io.in(Omega, mat_extent(Din, D, ldo), &Od))) return rc;
+  if ((rc = io.in(phase, (size_t)D, &Pd))) return rc;
+  if ((rc = io.out(Phi, mat_extent(D, N, ldphi), &Fd))) return rc;
   dim3 grid((unsigned)((D + kThreads - 1) / kThreads), (unsigned)((N + 31) / 32));  // 32 columns per workgroup (rff_features_kernel NT)
   hipLaunchKernelGGL(rff_features_kernel<T>, grid, dim3(kThreads), 0, h->stream, Xd, ldxin, Od, ldo, Pd, scale, (int)Din,
                      (int)D, (int)N, Fd, ldphi);
   HIP_TRY(h, hipGetLastError());
-  if (memspace == BLR_MEM_HOST) {
-    HIP_TRY(h, hipMemcpyAsync(Phi, Fd, mat_extent(D, N, ldphi) * sizeof(T), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-  } else if (!h->async) {
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-  }
-  return 0;
+  return io.finish();
 }
 
 template <typename T>
@@ -2818,126 +2420,56 @@ int posterior_rff(blr_handle* h, int memspace, int64_t Din, int64_t D, int64_t N
   // fp32 at D > 128, D_in <= kRffFusedMaxDin: the basis is never materialised -- the planes pass of the large-D pipeline evaluates phi
   // once per element and writes the bf16 planes of the Gram operands directly (blr_planes.hpp; reference
   // src/basis_function_regression.jl:41 builds phi(x)).  A wider input materialises the features below (the planes Gram still runs on them).
-  if (sizeof(T) == 4 && D > kMaxSmallD && N > 0 && Din <= kRffFusedMaxDin && !h->opt.no_planes && !h->opt.no_bf16x3) {
-    Staging guard(h);
-    const T *Xd = Xin, *Od = Omega, *Pd = phase;
-    const T *yd = y, *sd = s, *mwd = mw, *Lwd = Lw;
-    T *mwp = mw_post, *Tp = T_post, *Ap = Lw_post;
-    double* lpd = logpdf;
-    int32_t* infod = info;
-    int rc;
-    const bool host = memspace == BLR_MEM_HOST;
-    if (host) {
-      const size_t lw_one = prior_kind == BLR_PRIOR_DIAGONAL ? (size_t)D : mat_extent(D, D, ldl);
-      if (noise_kind != BLR_NOISE_ISOTROPIC && noise_kind != BLR_NOISE_DIAGONAL) return bad_arg(h, 13, "noise_kind");
-      if (!y) return bad_arg(h, 12, "y is NULL");
-      if (!s) return bad_arg(h, 14, "s is NULL");
-      if (!mw) return bad_arg(h, 16, "mw is NULL");
-      if (!Lw) return bad_arg(h, 17, "Lw is NULL");
-      if (!info) return bad_arg(h, 25, "info is NULL");
-      if ((rc = stage_in(h, Xin, mat_extent(Din, N, ldxin), &Xd))) return rc;
-      if ((rc = stage_in(h, Omega, mat_extent(Din, D, ldo), &Od))) return rc;
-      if ((rc = stage_in(h, phase, (size_t)D, &Pd))) return rc;
-      if ((rc = stage_in(h, y, (size_t)N, &yd))) return rc;
-      if ((rc = stage_in(h, s, noise_kind == BLR_NOISE_DIAGONAL ? (size_t)N : 1, &sd))) return rc;
-      if ((rc = stage_in(h, mw, (size_t)D, &mwd))) return rc;
-      if ((rc = stage_in(h, Lw, lw_one, &Lwd))) return rc;
-      if ((rc = stage_out_alloc(h, mw_post, (size_t)D, &mwp))) return rc;
-      if ((rc = stage_out_alloc(h, T_post, mat_extent(D, D, ldt), &Tp))) return rc;
-      if ((rc = stage_out_alloc(h, Lw_post, mat_extent(D, D, ldlp), &Ap))) return rc;
-      if ((rc = stage_out_alloc(h, logpdf, 1, &lpd))) return rc;
-      if ((rc = stage_out_alloc(h, info, 1, &infod))) return rc;
-    }
-    const blr_handle::RffSrc src{Xd, Od, Pd, ldxin, ldo, (double)scale, (int)Din};
-    const bool was_async = h->async;
-    if (host) h->async = true;
-    h->rff_src = &src;
-    // (X: any non-NULL device pointer -- with a basis source attached nothing dereferences it; ldx = D passes the argument checks)
-    rc = posterior_batched<T>(h, BLR_MEM_DEVICE, BLR_LAYOUT_COLVECS, 1, D, N, Xd, D, 0, yd, 0, noise_kind, sd, 0, prior_kind, mwd, 0,
-                              Lwd, ldl, 0, mwp, D, Tp, ldt, ldt * D, Ap, ldlp, ldlp * D, lpd, infod);
-    h->rff_src = nullptr;
-    h->async = was_async;
-    if (rc) return rc;
-    if (host) {
-      if (mw_post) HIP_TRY(h, hipMemcpyAsync(mw_post, mwp, (size_t)D * sizeof(T), hipMemcpyDeviceToHost, h->stream));
-      if (T_post) HIP_TRY(h, hipMemcpyAsync(T_post, Tp, mat_extent(D, D, ldt) * sizeof(T), hipMemcpyDeviceToHost, h->stream));
-      if (Lw_post) HIP_TRY(h, hipMemcpyAsync(Lw_post, Ap, mat_extent(D, D, ldlp) * sizeof(T), hipMemcpyDeviceToHost, h->stream));
-      if (logpdf) HIP_TRY(h, hipMemcpyAsync(logpdf, lpd, sizeof(double), hipMemcpyDeviceToHost, h->stream));
-      HIP_TRY(h, hipMemcpyAsync(info, infod, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-      HIP_TRY(h, hipStreamSynchronize(h->stream));
-    }
-    return 0;
+  const bool fused = sizeof(T) == 4 && D > kMaxSmallD && N > 0 && Din <= kRffFusedMaxDin && !h->opt.no_planes && !h->opt.no_bf16x3;
+  if (memspace == BLR_MEM_HOST) {
+    if (noise_kind != BLR_NOISE_ISOTROPIC && noise_kind != BLR_NOISE_DIAGONAL) return bad_arg(h, 13, "noise_kind");
+    if (!y && N > 0) return bad_arg(h, 12, "y is NULL");
+    if (!s) return bad_arg(h, 14, "s is NULL");
+    if (!mw) return bad_arg(h, 16, "mw is NULL");
+    if (!Lw) return bad_arg(h, 17, "Lw is NULL");
+    if (!info) return bad_arg(h, 25, "info is NULL");
   }
-  const int64_t ldphi = (D + 3) / 4 * 4;  // keeps every feature column 16-byte aligned for the LDS-DMA loader
-  const size_t need = (size_t)ldphi * (size_t)std::max<int64_t>(N, 1) * sizeof(T);
-  if (need > h->feat_bytes) {
-    if (h->feat) {
-      HIP_TRY(h, hipStreamSynchronize(h->stream));
-      HIP_TRY(h, hipFree(h->feat));
-      h->feat = nullptr;
-      h->feat_bytes = 0;
-    }
-    HIP_TRY(h, hipMalloc((void**)&h->feat, need));
-    h->feat_bytes = need;
-  }
-  T* Phi = reinterpret_cast<T*>(h->feat);
-  const bool was_async = h->async;
+  CallIO io(h, memspace);
   int rc;
-  {
-    Staging guard(h);
-    const T *Xd = Xin, *Od = Omega, *Pd = phase;
-    if (memspace == BLR_MEM_HOST) {
-      if ((rc = stage_in(h, Xin, mat_extent(Din, N, ldxin), &Xd))) return rc;
-      if ((rc = stage_in(h, Omega, mat_extent(Din, D, ldo), &Od))) return rc;
-      if ((rc = stage_in(h, phase, (size_t)D, &Pd))) return rc;
-    }
-    if (N > 0) {
-      dim3 grid((unsigned)((D + kThreads - 1) / kThreads), (unsigned)((N + 31) / 32));  // 32 columns per workgroup (rff_features_kernel NT)
-      hipLaunchKernelGGL(rff_features_kernel<T>, grid, dim3(kThreads), 0, h->stream, Xd, ldxin, Od, ldo, Pd, scale,
-                         (int)Din, (int)D, (int)N, Phi, ldphi);
-      HIP_TRY(h, hipGetLastError());
-    }
-    if (memspace == BLR_MEM_HOST) HIP_TRY(h, hipStreamSynchronize(h->stream));  // staged inputs die with `guard`
+  const T *Xd = nullptr, *Od = nullptr, *Pd = nullptr;
+  PosteriorArgs<T> a{};
+  a.strideX = 0; a.stridey = 0; a.strides = 0; a.stridemw = 0; a.ldl = ldl; a.strideLw = 0;
+  a.stride_mwpost = D; a.ldt = ldt; a.strideT = ldt * D; a.ldlp = ldlp; a.strideLp = ldlp * D;
+  a.layout = BLR_LAYOUT_COLVECS; a.noise_kind = noise_kind; a.prior_kind = prior_kind;
+  a.D = (int)D; a.N = (int)N; a.B = 1;
+  if ((rc = io.in(Xin, mat_extent(Din, N, ldxin), &Xd))) return rc;
+  if ((rc = io.in(Omega, mat_extent(Din, D, ldo), &Od))) return rc;
+  if ((rc = io.in(phase, (size_t)D, &Pd))) return rc;
+  if ((rc = io.in(y, (size_t)N, &a.y))) return rc;
+  if ((rc = io.in(s, noise_kind == BLR_NOISE_DIAGONAL ? (size_t)N : 1, &a.s))) return rc;
+  if ((rc = io.in(mw, (size_t)D, &a.mw))) return rc;
+  if ((rc = io.in(Lw, prior_kind == BLR_PRIOR_DIAGONAL ? (size_t)D : mat_extent(D, D, ldl), &a.Lw))) return rc;
+  if ((rc = io.out(mw_post, (size_t)D, &a.mw_post))) return rc;
+  if ((rc = io.out(T_post, mat_extent(D, D, ldt), &a.T_post))) return rc;
+  if ((rc = io.out(Lw_post, mat_extent(D, D, ldlp), &a.Lw_post))) return rc;
+  if ((rc = io.out(logpdf, 1, &a.logpdf))) return rc;
+  if ((rc = io.out(info, 1, &a.info))) return rc;
+  if (fused) {
+    // (X: any non-NULL device pointer -- with a basis source attached nothing dereferences it; ldx = D passes the argument checks)
+    a.X = Xd; a.ldx = D;
+    a.rff_Xin = Xd; a.rff_ldxin = ldxin; a.rff_Omega = Od; a.rff_ldo = ldo; a.rff_phase = Pd; a.rff_scale = scale; a.rff_Din = (int)Din;
+  } else {
+    a.ldx = (D + 3) / 4 * 4;  // keeps every feature column 16-byte aligned for the LDS-DMA loader
+    if ((rc = h->feat.reserve(h, (size_t)a.ldx * (size_t)std::max<int64_t>(N, 1) * sizeof(T)))) return rc;
+    a.X = reinterpret_cast<T*>(h->feat.p);
   }
-  if (memspace == BLR_MEM_DEVICE) {
-    return posterior_batched<T>(h, BLR_MEM_DEVICE, BLR_LAYOUT_COLVECS, 1, D, N, Phi, ldphi, 0, y, 0, noise_kind, s, 0,
-                                prior_kind, mw, 0, Lw, ldl, 0, mw_post, D, T_post, ldt, ldt * D, Lw_post, ldlp, ldlp * D,
-                                logpdf, info);
-  }
-  // host pointers for everything except Phi: stage the rest here, then run on device pointers
-  Staging guard(h);
-  const T *yd, *sd, *mwd, *Lwd;
-  const size_t lw_one = prior_kind == BLR_PRIOR_DIAGONAL ? (size_t)D : mat_extent(D, D, ldl);
-  if (noise_kind != BLR_NOISE_ISOTROPIC && noise_kind != BLR_NOISE_DIAGONAL) return bad_arg(h, 13, "noise_kind");
-  if (!y && N > 0) return bad_arg(h, 12, "y is NULL");
-  if (!s) return bad_arg(h, 14, "s is NULL");
-  if (!mw) return bad_arg(h, 16, "mw is NULL");
-  if (!Lw) return bad_arg(h, 17, "Lw is NULL");
-  if (!info) return bad_arg(h, 25, "info is NULL");
-  if ((rc = stage_in(h, y, (size_t)N, &yd))) return rc;
-  if ((rc = stage_in(h, s, noise_kind == BLR_NOISE_DIAGONAL ? (size_t)N : 1, &sd))) return rc;
-  if ((rc = stage_in(h, mw, (size_t)D, &mwd))) return rc;
-  if ((rc = stage_in(h, Lw, lw_one, &Lwd))) return rc;
-  T *mwp = nullptr, *Tp = nullptr, *Ap = nullptr;
-  double* lpd = nullptr;
-  int32_t* infod = nullptr;
-  if ((rc = stage_out_alloc(h, mw_post, (size_t)D, &mwp))) return rc;
-  if ((rc = stage_out_alloc(h, T_post, mat_extent(D, D, ldt), &Tp))) return rc;
-  if ((rc = stage_out_alloc(h, Lw_post, mat_extent(D, D, ldlp), &Ap))) return rc;
-  if ((rc = stage_out_alloc(h, logpdf, 1, &lpd))) return rc;
-  if ((rc = stage_out_alloc(h, info, 1, &infod))) return rc;
-  h->async = true;
-  rc = posterior_batched<T>(h, BLR_MEM_DEVICE, BLR_LAYOUT_COLVECS, 1, D, N, Phi, ldphi, 0, yd ? yd : mwd, 0, noise_kind, sd,
-                            0, prior_kind, mwd, 0, Lwd, ldl, 0, mwp, D, Tp, ldt, ldt * D, Ap, ldlp, ldlp * D, lpd, infod);
-  h->async = was_async;
+  // the rest of the arguments: the checks of the batched update on the device pointers, with its positions
+  rc = posterior_check<T>(h, BLR_MEM_DEVICE, a.layout, 1, D, N, a.X, a.ldx, 0, a.y, 0, noise_kind, a.s, 0, prior_kind, a.mw, 0, a.Lw, ldl, 0,
+                          a.mw_post, D, a.T_post, ldt, a.strideT, a.Lw_post, ldlp, a.strideLp, a.logpdf, a.info);
   if (rc) return rc;
-  if (mw_post) HIP_TRY(h, hipMemcpyAsync(mw_post, mwp, (size_t)D * sizeof(T), hipMemcpyDeviceToHost, h->stream));
-  if (T_post) HIP_TRY(h, hipMemcpyAsync(T_post, Tp, mat_extent(D, D, ldt) * sizeof(T), hipMemcpyDeviceToHost, h->stream));
-  if (Lw_post) HIP_TRY(h, hipMemcpyAsync(Lw_post, Ap, mat_extent(D, D, ldlp) * sizeof(T), hipMemcpyDeviceToHost, h->stream));
-  if (logpdf) HIP_TRY(h, hipMemcpyAsync(logpdf, lpd, sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(h, hipMemcpyAsync(info, infod, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(h, hipStreamSynchronize(h->stream));
-  return 0;
+  if (!fused && N > 0) {
+    dim3 grid((unsigned)((D + kThreads - 1) / kThreads), (unsigned)((N + 31) / 32));  // 32 columns per workgroup (rff_features_kernel NT)
+    hipLaunchKernelGGL(rff_features_kernel<T>, grid, dim3(kThreads), 0, h->stream, Xd, ldxin, Od, ldo, Pd, scale,
+                       (int)Din, (int)D, (int)N, reinterpret_cast<T*>(h->feat.p), a.ldx);
+    HIP_TRY(h, hipGetLastError());
+  }
+  if ((rc = posterior_run<T>(h, a))) return rc;
+  return io.finish();
 }
 
 
@@ -2945,15 +2477,6 @@ int posterior_rff(blr_handle* h, int memspace, int64_t Din, int64_t D, int64_t N
 // Dense Sigma_y and full predictive covariance: see blr_dense.hpp for the scheme
 // ================================================================================================================
 constexpr int64_t kMaxDenseN = 16384;  // N x N work matrices: 2 GiB in fp64 at this size
-
-template <typename T>
-int dev_alloc_tmp(blr_handle* h, size_t count, T** out) {  // freed by the enclosing Staging guard
-  void* p = nullptr;
-  HIP_TRY(h, hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T)));
-  h->staged.push_back(p);
-  *out = static_cast<T*>(p);
-  return 0;
-}
 
 // x_n' mw for D <= 128 (one thread per input; the mean of mean_and_cov -- N <= 16384, not a hot path)
 template <typename T>
@@ -3003,36 +2526,34 @@ int posterior_dense_noise(blr_handle* h, int memspace, int layout, int64_t D64, 
   const int NP = (N + kPB - 1) / kPB * kPB;
   const int R = (D + 1 + kPB - 1) / kPB * kPB;  // X rows + the y row, padded to whole TRSM row blocks
   const int64_t ld = (int64_t)NP + R;
-  Staging guard(h);
+  CallIO io(h, memspace);
   int rc;
-  const T *X_d = X, *y_d = y, *Sy_d = Sy, *mw_d = mw, *Lw_d = Lw;
-  T *mwp_d = mw_post, *Tp_d = T_post, *Lp_d = Lw_post;
-  double* lp_d = logpdf;
-  int32_t* info_d = info;
-  if (memspace == BLR_MEM_HOST) {
-    const size_t x_one = layout == BLR_LAYOUT_COLVECS ? mat_extent(D, N, ldx) : mat_extent(N, D, ldx);
-    const size_t lw_one = prior_kind == BLR_PRIOR_DIAGONAL ? (size_t)D : mat_extent(D, D, ldl);
-    if ((rc = stage_in(h, X, x_one, &X_d))) return rc;
-    if ((rc = stage_in(h, y, (size_t)N, &y_d))) return rc;
-    if ((rc = stage_in(h, Sy, mat_extent(N, N, ldsy), &Sy_d))) return rc;
-    if ((rc = stage_in(h, mw, (size_t)D, &mw_d))) return rc;
-    if ((rc = stage_in(h, Lw, lw_one, &Lw_d))) return rc;
-    if ((rc = stage_out_alloc(h, mw_post, (size_t)D, &mwp_d))) return rc;
-    if ((rc = stage_out_alloc(h, T_post, mat_extent(D, D, ldt), &Tp_d))) return rc;
-    if ((rc = stage_out_alloc(h, Lw_post, mat_extent(D, D, ldlp), &Lp_d))) return rc;
-    if ((rc = stage_out_alloc(h, logpdf, (size_t)1, &lp_d))) return rc;
-    if ((rc = stage_out_alloc(h, info, (size_t)1, &info_d))) return rc;
-  }
+  const T *X_d = nullptr, *y_d = nullptr, *Sy_d = nullptr, *mw_d = nullptr, *Lw_d = nullptr;
+  T *mwp_d = nullptr, *Tp_d = nullptr, *Lp_d = nullptr;
+  double* lp_d = nullptr;
+  int32_t* info_d = nullptr;
+  const size_t x_one = layout == BLR_LAYOUT_COLVECS ? mat_extent(D, N, ldx) : mat_extent(N, D, ldx);
+  const size_t lw_one = prior_kind == BLR_PRIOR_DIAGONAL ? (size_t)D : mat_extent(D, D, ldl);
+  if ((rc = io.in(X, x_one, &X_d))) return rc;
+  if ((rc = io.in(y, (size_t)N, &y_d))) return rc;
+  if ((rc = io.in(Sy, mat_extent(N, N, ldsy), &Sy_d))) return rc;
+  if ((rc = io.in(mw, (size_t)D, &mw_d))) return rc;
+  if ((rc = io.in(Lw, lw_one, &Lw_d))) return rc;
+  if ((rc = io.out(mw_post, (size_t)D, &mwp_d))) return rc;
+  if ((rc = io.out(T_post, mat_extent(D, D, ldt), &Tp_d))) return rc;
+  if ((rc = io.out(Lw_post, mat_extent(D, D, ldlp), &Lp_d))) return rc;
+  if ((rc = io.out(logpdf, (size_t)1, &lp_d))) return rc;
+  if ((rc = io.out(info, (size_t)1, &info_d))) return rc;
   T *M = nullptr, *ytil = nullptr, *one = nullptr;
   double* logdet = nullptr;
   int32_t* noise_info = nullptr;
-  if ((rc = dev_alloc_tmp(h, (size_t)ld * NP, &M))) return rc;
-  if ((rc = dev_alloc_tmp(h, (size_t)N, &ytil))) return rc;
-  if ((rc = dev_alloc_tmp(h, 1, &one))) return rc;
-  if ((rc = dev_alloc_tmp(h, 1, &logdet))) return rc;
-  if ((rc = dev_alloc_tmp(h, 1, &noise_info))) return rc;
+  if ((rc = io.tmp((size_t)ld * NP, &M))) return rc;
+  if ((rc = io.tmp((size_t)N, &ytil))) return rc;
+  if ((rc = io.tmp(1, &one))) return rc;
+  if ((rc = io.tmp(1, &logdet))) return rc;
+  if ((rc = io.tmp(1, &noise_info))) return rc;
   double* lp_tmp = lp_d;
-  if (!lp_tmp && (rc = dev_alloc_tmp(h, 1, &lp_tmp))) return rc;
+  if (!lp_tmp && (rc = io.tmp(1, &lp_tmp))) return rc;
   const T one_h = T(1);
   HIP_TRY(h, hipMemcpyAsync(one, &one_h, sizeof(T), hipMemcpyHostToDevice, h->stream));
   // [Sigma_y; X; y'] -> [L; X L^-T; (L^-1 y)']   (reference :79, :81 outer solve, :82)
@@ -3053,7 +2574,7 @@ int posterior_dense_noise(blr_handle* h, int memspace, int layout, int64_t D64, 
   // inner update cannot tell a prior failure from a posterior one once the whitened data are garbage, so the prior's status
   // comes from an update on ZERO observations (A = Lw: D^3 / 3 flops, nothing next to the N^3 / 3 of the whitening)
   int32_t* prior_info = nullptr;
-  if ((rc = dev_alloc_tmp(h, 1, &prior_info))) return rc;
+  if ((rc = io.tmp(1, &prior_info))) return rc;
   {
     PosteriorArgs<T> p0 = a;
     p0.N = 0; p0.mw_post = nullptr; p0.T_post = nullptr; p0.Lw_post = nullptr; p0.logpdf = nullptr; p0.info = prior_info;
@@ -3063,15 +2584,7 @@ int posterior_dense_noise(blr_handle* h, int memspace, int layout, int64_t D64, 
   hipLaunchKernelGGL(dense_finish_kernel, dim3(1), dim3(64), 0, h->stream, lp_tmp, info_d, (const double*)logdet, (const int32_t*)noise_info,
                      (const int32_t*)prior_info);
   HIP_TRY(h, hipGetLastError());
-  if (memspace == BLR_MEM_HOST) {
-    if (mw_post) HIP_TRY(h, hipMemcpyAsync(mw_post, mwp_d, (size_t)D * sizeof(T), hipMemcpyDeviceToHost, h->stream));
-    if (T_post) HIP_TRY(h, hipMemcpyAsync(T_post, Tp_d, mat_extent(D, D, ldt) * sizeof(T), hipMemcpyDeviceToHost, h->stream));
-    if (Lw_post) HIP_TRY(h, hipMemcpyAsync(Lw_post, Lp_d, mat_extent(D, D, ldlp) * sizeof(T), hipMemcpyDeviceToHost, h->stream));
-    if (logpdf) HIP_TRY(h, hipMemcpyAsync(logpdf, lp_d, sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(info, info_d, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-  }
-  HIP_TRY(h, hipStreamSynchronize(h->stream));  // temporaries are freed on return
-  return 0;
+  return io.finish();  // (drains the stream in either memspace: the temporaries are freed on return)
 }
 
 // Y = X' Lw^-T (N rows x D columns, column-major with leading dimension ldy, rows [DP, DP + NP) of Ybar) for a factored or
@@ -3149,29 +2662,27 @@ int mean_and_cov(blr_handle* h, int memspace, int layout, int64_t D64, int64_t N
   const int D = (int)D64, N = (int)N64;
   const int DP = (D + kPB - 1) / kPB * kPB, NP = (N + kPB - 1) / kPB * kPB;
   const int64_t ldy = (int64_t)DP + NP;
-  Staging guard(h);
+  CallIO io(h, memspace);
   int rc;
-  const T *X_d = X, *s_d = s, *mw_d = mw, *Lw_d = Lw;
-  T *mean_d = mean, *C_d = C;
-  int32_t* info_d = info;
-  if (memspace == BLR_MEM_HOST) {
-    const size_t x_one = layout == BLR_LAYOUT_COLVECS ? mat_extent(D, N, ldx) : mat_extent(N, D, ldx);
-    const size_t lw_one = prior_kind == BLR_PRIOR_DIAGONAL ? (size_t)D : mat_extent(D, D, ldl);
-    const size_t s_one = noise_kind == BLR_NOISE_DENSE ? mat_extent(N, N, lds) : (noise_kind == BLR_NOISE_DIAGONAL ? (size_t)N : 1);
-    if ((rc = stage_in(h, X, x_one, &X_d))) return rc;
-    if ((rc = stage_in(h, s, s_one, &s_d))) return rc;
-    if ((rc = stage_in(h, mw, mw ? (size_t)D : 0, &mw_d))) return rc;
-    if ((rc = stage_in(h, Lw, lw_one, &Lw_d))) return rc;
-    if ((rc = stage_out_alloc(h, mean, (size_t)N, &mean_d))) return rc;
-    if ((rc = stage_out_alloc(h, C, mat_extent(N, N, ldc), &C_d))) return rc;
-    if ((rc = stage_out_alloc(h, info, (size_t)1, &info_d))) return rc;
-  }
+  const T *X_d = nullptr, *s_d = nullptr, *mw_d = nullptr, *Lw_d = nullptr;
+  T *mean_d = nullptr, *C_d = nullptr;
+  int32_t* info_d = nullptr;
+  const size_t x_one = layout == BLR_LAYOUT_COLVECS ? mat_extent(D, N, ldx) : mat_extent(N, D, ldx);
+  const size_t lw_one = prior_kind == BLR_PRIOR_DIAGONAL ? (size_t)D : mat_extent(D, D, ldl);
+  const size_t s_one = noise_kind == BLR_NOISE_DENSE ? mat_extent(N, N, lds) : (noise_kind == BLR_NOISE_DIAGONAL ? (size_t)N : 1);
+  if ((rc = io.in(X, x_one, &X_d))) return rc;
+  if ((rc = io.in(s, s_one, &s_d))) return rc;
+  if ((rc = io.in(mw, (size_t)D, &mw_d))) return rc;
+  if ((rc = io.in(Lw, lw_one, &Lw_d))) return rc;
+  if ((rc = io.out(mean, (size_t)N, &mean_d))) return rc;
+  if ((rc = io.out(C, mat_extent(N, N, ldc), &C_d))) return rc;
+  if ((rc = io.out(info, (size_t)1, &info_d))) return rc;
   T *Ybar = nullptr, *Gpart = nullptr;
   double* scratch = nullptr;
   const int nb = NP / kPB, ntiles = nb * (nb + 1) / 2;
-  if ((rc = dev_alloc_tmp(h, (size_t)ldy * DP, &Ybar))) return rc;
-  if ((rc = dev_alloc_tmp(h, (size_t)ntiles * kPB * kPB, &Gpart))) return rc;
-  if ((rc = dev_alloc_tmp(h, 1, &scratch))) return rc;
+  if ((rc = io.tmp((size_t)ldy * DP, &Ybar))) return rc;
+  if ((rc = io.tmp((size_t)ntiles * kPB * kPB, &Gpart))) return rc;
+  if ((rc = io.tmp(1, &scratch))) return rc;
   // ---- Y = alpha' = X' Uw^-1   (reference :36 alpha = Uw' \ X)
   if (prior_kind == BLR_PRIOR_DIAGONAL) {
     hipLaunchKernelGGL(prior_diag_kernel<T>, dim3(1), dim3(kThreads), 0, h->stream, Lw_d, (int64_t)1, prior_kind, D, scratch, info_d);
@@ -3197,13 +2708,7 @@ int mean_and_cov(blr_handle* h, int memspace, int layout, int64_t D64, int64_t N
   if (mean)
     hipLaunchKernelGGL(mean_small_kernel<T>, dim3((unsigned)((N + 255) / 256)), dim3(kThreads), 0, h->stream, X_d, ldx, layout, mw_d, D, N, mean_d);
   HIP_TRY(h, hipGetLastError());
-  if (memspace == BLR_MEM_HOST) {
-    if (mean) HIP_TRY(h, hipMemcpyAsync(mean, mean_d, (size_t)N * sizeof(T), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(C, C_d, mat_extent(N, N, ldc) * sizeof(T), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(info, info_d, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-  }
-  HIP_TRY(h, hipStreamSynchronize(h->stream));
-  return 0;
+  return io.finish();  // (drains the stream in either memspace: the temporaries are freed on return)
 }
 
 // rand with a dense noise covariance: Y = X'(mw + Uw \ Z1) + Us' Z2   (reference :49-53).  Returns info (> 0: Sigma_y or Lw
@@ -3221,13 +2726,13 @@ int rand_dense_noise(blr_handle* h, int memspace, int layout, int64_t D, int64_t
   if (S == 0) return 0;
   // X' W with the noise term switched off (sigma^2 = 0), through the ordinary entry point (validates everything else)
   const T zero = T(0);
-  Staging guard(h);
+  CallIO io(h, memspace);
   int rc;
   const T* zero_d = &zero;
   if (memspace == BLR_MEM_DEVICE) {
     T* z = nullptr;
     HIP_TRY(h, hipSetDevice(h->device));
-    if ((rc = dev_alloc_tmp(h, 1, &z))) return rc;
+    if ((rc = io.tmp(1, &z))) return rc;
     HIP_TRY(h, hipMemsetAsync(z, 0, sizeof(T), h->stream));
     zero_d = z;
   }
@@ -3235,25 +2740,22 @@ int rand_dense_noise(blr_handle* h, int memspace, int layout, int64_t D, int64_t
   if (rc) return rc;
   // + L Z2 with L L' = Sigma_y
   const int NP = (int)((N + kPB - 1) / kPB * kPB);
-  const T *Sy_d = Sy, *Z2_d = Z2;
-  T* Y_d = Y;
-  if (memspace == BLR_MEM_HOST) {
-    if ((rc = stage_in(h, Sy, mat_extent(N, N, ldsy), &Sy_d))) return rc;
-    if ((rc = stage_in(h, Z2, mat_extent(N, S, ldz2), &Z2_d))) return rc;
-    if ((rc = stage_out_alloc(h, Y, mat_extent(N, S, ldy), &Y_d))) return rc;  // copies the X'W part back in
-  }
+  const T *Sy_d = nullptr, *Z2_d = nullptr;
+  T* Y_d = nullptr;
+  if ((rc = io.in(Sy, mat_extent(N, N, ldsy), &Sy_d))) return rc;
+  if ((rc = io.in(Z2, mat_extent(N, S, ldz2), &Z2_d))) return rc;
+  if ((rc = io.out(Y, mat_extent(N, S, ldy), &Y_d))) return rc;  // copies the X'W part back in
   T* M = nullptr;
   int32_t* ninfo = nullptr;
-  if ((rc = dev_alloc_tmp(h, (size_t)NP * NP, &M))) return rc;
-  if ((rc = dev_alloc_tmp(h, 1, &ninfo))) return rc;
+  if ((rc = io.tmp((size_t)NP * NP, &M))) return rc;
+  if ((rc = io.tmp(1, &ninfo))) return rc;
   if ((rc = chol_noise<T>(h, Sy_d, ldsy, (int)N, NP, 0, M, (int64_t)NP, ninfo))) return rc;
   dim3 grid((unsigned)((N + 63) / 64), (unsigned)((S + 15) / 16));
   hipLaunchKernelGGL(lower_mult_add_kernel<T>, grid, dim3(kThreads), 0, h->stream, (const T*)M, (int64_t)NP, (int)N, Z2_d, ldz2, Y_d, ldy, S);
   HIP_TRY(h, hipGetLastError());
   int32_t hinfo = 0;
   HIP_TRY(h, hipMemcpyAsync(&hinfo, ninfo, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-  if (memspace == BLR_MEM_HOST) HIP_TRY(h, hipMemcpyAsync(Y, Y_d, mat_extent(N, S, ldy) * sizeof(T), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  if ((rc = io.finish())) return rc;  // (drains the stream in either memspace: hinfo, the temporaries)
   return hinfo;
 }
 
@@ -3309,36 +2811,21 @@ int update_factor(blr_handle* h, int memspace, int layout, int64_t B, int64_t D,
   a.stridemw = stridemw; a.ldt = ldt; a.strideT = strideT; a.D = (int)D; a.k = (int)k;
   const int lds = sweep_lds_bytes<T>((int)D);
   { const int rc_lds = set_lds_once(h, reinterpret_cast<const void*>(rank1_sweep_kernel<T>), (size_t)(lds)); if (rc_lds) return rc_lds; }
-  if (memspace == BLR_MEM_DEVICE) {
-    a.X = X; a.y = y; a.s = s; a.mw = mw; a.Tf = Tf; a.logpdf = logpdf; a.info = info;
-    hipLaunchKernelGGL(rank1_sweep_kernel<T>, dim3((unsigned)B), dim3(kThreads), lds, h->stream, a);
-    HIP_TRY(h, hipGetLastError());
-    if (!h->async) HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return 0;
-  }
-  Staging guard(h);
+  CallIO io(h, memspace);
   const size_t x_one = layout == BLR_LAYOUT_COLVECS ? mat_extent(D, k, ldx) : mat_extent(k, D, ldx);
   const size_t s_one = noise_kind == BLR_NOISE_DIAGONAL ? (size_t)k : 1;
-  const size_t n_mw = extent(B, stridemw, (size_t)D), n_T = extent(B, strideT, mat_extent(D, D, ldt));
   int rc;
-  const T *dmw = nullptr, *dT = nullptr;
-  if ((rc = stage_in(h, X, extent(B, strideX, x_one), &a.X))) return rc;
-  if ((rc = stage_in(h, y, extent(B, stridey, (size_t)k), &a.y))) return rc;
-  if ((rc = stage_in(h, s, extent(B, strides, s_one), &a.s))) return rc;
-  if ((rc = stage_in(h, (const T*)mw, n_mw, &dmw))) return rc;
-  if ((rc = stage_in(h, (const T*)Tf, n_T, &dT))) return rc;
-  a.mw = const_cast<T*>(dmw); a.Tf = const_cast<T*>(dT);
-  if ((rc = stage_out_alloc(h, logpdf, (size_t)B, &a.logpdf))) return rc;
-  if ((rc = stage_out_alloc(h, info, (size_t)B, &a.info))) return rc;
+  if ((rc = io.in(X, extent(B, strideX, x_one), &a.X))) return rc;
+  if ((rc = io.in(y, extent(B, stridey, (size_t)k), &a.y))) return rc;
+  if ((rc = io.in(s, extent(B, strides, s_one), &a.s))) return rc;
+  if ((rc = io.out(mw, extent(B, stridemw, (size_t)D), &a.mw))) return rc;  // (updated in place)
+  if ((rc = io.out(Tf, extent(B, strideT, mat_extent(D, D, ldt)), &a.Tf))) return rc;
+  if ((rc = io.out(logpdf, (size_t)B, &a.logpdf))) return rc;
+  if ((rc = io.out(info, (size_t)B, &a.info))) return rc;
   if (k == 0) { if (!a.X) a.X = a.mw; if (!a.y) a.y = a.mw; }
   hipLaunchKernelGGL(rank1_sweep_kernel<T>, dim3((unsigned)B), dim3(kThreads), lds, h->stream, a);
   HIP_TRY(h, hipGetLastError());
-  HIP_TRY(h, hipMemcpyAsync(mw, a.mw, n_mw * sizeof(T), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(h, hipMemcpyAsync(Tf, a.Tf, n_T * sizeof(T), hipMemcpyDeviceToHost, h->stream));
-  if (logpdf) HIP_TRY(h, hipMemcpyAsync(logpdf, a.logpdf, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(h, hipMemcpyAsync(info, a.info, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(h, hipStreamSynchronize(h->stream));
-  return 0;
+  return io.finish();
 }
 
 // ---- rank-k downdate of a resident state (blr_downdate.hpp) -----------------------------------------------------------
@@ -3359,9 +2846,9 @@ int downdate_launch(blr_handle* h, const SweepArgs<T>& a0, int64_t B) {
   const size_t per = mat + 3 * vec + 4 * sizeof(double) + sizeof(int);
   const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(B, (int64_t)(kDowndateWorkspace / per)));
   const size_t off_v = (size_t)chunk * mat, off_sc = off_v + 3 * (size_t)chunk * vec, off_st = off_sc + (size_t)chunk * 4 * sizeof(double);
-  int rc = ensure_ws(h, off_st + (size_t)chunk * sizeof(int) + 256);
+  int rc = h->ws.reserve(h, off_st + (size_t)chunk * sizeof(int) + 256, blr_handle::kWsFloor);
   if (rc) return rc;
-  char* base = reinterpret_cast<char*>(h->ws);
+  char* base = h->ws.p;
   DowndateWs<T> w{};
   w.W = reinterpret_cast<T*>(base);
   w.strideW = (int64_t)(mat / item);
@@ -3425,53 +2912,24 @@ int downdate_factor(blr_handle* h, int memspace, int layout, int64_t B, int64_t 
   SweepArgs<T> a{};
   a.ldx = ldx; a.strideX = strideX; a.layout = layout; a.stridey = stridey; a.strides = strides; a.noise_kind = noise_kind;
   a.stridemw = stridemw; a.ldt = ldt; a.strideT = strideT; a.D = (int)D; a.k = (int)k;
-  if (memspace == BLR_MEM_DEVICE) {
-    a.X = X; a.y = y; a.s = s; a.mw = mw; a.Tf = Tf; a.logpdf = logpdf; a.info = info;
-    if (k == 0) { if (!a.X) a.X = mw; if (!a.y) a.y = mw; }
-    int rc = downdate_launch<T>(h, a, B);
-    if (rc) return rc;
-    if (!h->async) HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return 0;
-  }
-  Staging guard(h);
+  CallIO io(h, memspace);
   const size_t x_one = layout == BLR_LAYOUT_COLVECS ? mat_extent(D, k, ldx) : mat_extent(k, D, ldx);
   const size_t s_one = noise_kind == BLR_NOISE_DIAGONAL ? (size_t)k : 1;
-  const size_t n_mw = extent(B, stridemw, (size_t)D), n_T = extent(B, strideT, mat_extent(D, D, ldt));
   int rc;
-  const T *dmw = nullptr, *dT = nullptr;
-  if ((rc = stage_in(h, X, extent(B, strideX, x_one), &a.X))) return rc;
-  if ((rc = stage_in(h, y, extent(B, stridey, (size_t)k), &a.y))) return rc;
-  if ((rc = stage_in(h, s, extent(B, strides, s_one), &a.s))) return rc;
-  if ((rc = stage_in(h, (const T*)mw, n_mw, &dmw))) return rc;
-  if ((rc = stage_in(h, (const T*)Tf, n_T, &dT))) return rc;
-  a.mw = const_cast<T*>(dmw); a.Tf = const_cast<T*>(dT);
-  if ((rc = stage_out_alloc(h, logpdf, (size_t)B, &a.logpdf))) return rc;
-  if ((rc = stage_out_alloc(h, info, (size_t)B, &a.info))) return rc;
+  if ((rc = io.in(X, extent(B, strideX, x_one), &a.X))) return rc;
+  if ((rc = io.in(y, extent(B, stridey, (size_t)k), &a.y))) return rc;
+  if ((rc = io.in(s, extent(B, strides, s_one), &a.s))) return rc;
+  if ((rc = io.out(mw, extent(B, stridemw, (size_t)D), &a.mw))) return rc;  // (updated in place)
+  if ((rc = io.out(Tf, extent(B, strideT, mat_extent(D, D, ldt)), &a.Tf))) return rc;
+  if ((rc = io.out(logpdf, (size_t)B, &a.logpdf))) return rc;
+  if ((rc = io.out(info, (size_t)B, &a.info))) return rc;
   if (k == 0) { if (!a.X) a.X = a.mw; if (!a.y) a.y = a.mw; }
   if ((rc = downdate_launch<T>(h, a, B))) return rc;
-  HIP_TRY(h, hipMemcpyAsync(mw, a.mw, n_mw * sizeof(T), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(h, hipMemcpyAsync(Tf, a.Tf, n_T * sizeof(T), hipMemcpyDeviceToHost, h->stream));
-  if (logpdf) HIP_TRY(h, hipMemcpyAsync(logpdf, a.logpdf, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(h, hipMemcpyAsync(info, a.info, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(h, hipStreamSynchronize(h->stream));
-  return 0;
+  return io.finish();
 }
 
 // ---- exact leave-one-out predictives of a state's observations (blr_loo.hpp) -------------------------------------------------
 constexpr size_t kLooWorkspace = (size_t)256 << 20;  // bound of the per-chunk intermediates (at least one regressor)
-
-int ensure_loo_ws(blr_handle* h, size_t bytes) {
-  if (bytes <= h->loo_ws_bytes) return 0;
-  if (h->loo_ws) {
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    HIP_TRY(h, hipFree(h->loo_ws));
-    h->loo_ws = nullptr;
-    h->loo_ws_bytes = 0;
-  }
-  HIP_TRY(h, hipMalloc((void**)&h->loo_ws, bytes));
-  h->loo_ws_bytes = bytes;
-  return 0;
-}
 
 // device operands; l carries y, s, the three outputs and info (global regressor indexing)
 template <typename T>
@@ -3498,17 +2956,17 @@ int loo_launch(blr_handle* h, int layout, int64_t B, int64_t D, int64_t N, const
   if (fused) chunk = std::min<int64_t>(chunk, ((int64_t)256 << 20) / (G::IMG_ELEMS * (int64_t)sizeof(T)));
   const size_t off_var = (size_t)chunk * row, off_ll = fused ? 0 : 2 * (size_t)chunk * row;
   const size_t off_zero = off_ll + (ll_ws ? (size_t)chunk * row_ll : 0), off_inf = off_zero + 256;
-  if (N > 0 && (rc = ensure_loo_ws(h, off_inf + (size_t)chunk * sizeof(int32_t) + 256))) return rc;
-  char* const ws = h->loo_ws;
+  if (N > 0 && (rc = h->loo_ws.reserve(h, off_inf + (size_t)chunk * sizeof(int32_t) + 256))) return rc;
+  char* const ws = h->loo_ws.p;
   const int64_t ldw = (int64_t)(row / item);
   if (N > 0 && !fused) HIP_TRY(h, hipMemsetAsync(ws + off_zero, 0, sizeof(T), h->stream));  // the composed route's zero noise
   if (N > 0 && fused) {
-    if ((rc = ensure_aux(h, (size_t)chunk * G::IMG_ELEMS * sizeof(T)))) return rc;
+    if ((rc = h->aux.reserve(h, (size_t)chunk * G::IMG_ELEMS * sizeof(T)))) return rc;
     if ((rc = set_lds_once(h, reinterpret_cast<const void*>(marg_image_kernel<T>), (size_t)TC::LDS_BYTES))) return rc;
     void (*const kern)(LooGemmArgs<T>, const T*) = rowv ? marginals_gemm_kernel<T, true, LooGemmArgs<T>> : marginals_gemm_kernel<T, false, LooGemmArgs<T>>;
     if ((rc = set_lds_once(h, reinterpret_cast<const void*>(kern), (size_t)G::LDS_BYTES))) return rc;
   }
-  T* const img = reinterpret_cast<T*>(h->aux);
+  T* const img = reinterpret_cast<T*>(h->aux.p);
   const int64_t ldll = ll_ws ? (int64_t)(row_ll / sizeof(double)) : l.stride_ll;
   for (int64_t b0 = 0; N > 0 && b0 < B; b0 += chunk) {
     const int64_t nb = std::min<int64_t>(chunk, B - b0);
@@ -3594,41 +3052,27 @@ int loo_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, i
   LooArgs<T> l{};
   l.stridey = stridey; l.strides = strides; l.noise_kind = noise_kind; l.stride_lm = stride_lm; l.stride_lv = stride_lv;
   l.stride_ll = stride_ll; l.N = (int)N;
-  if (memspace == BLR_MEM_DEVICE) {
-    l.y = y; l.s = s; l.lm = loo_mean; l.lv = loo_var; l.ll = loo_logpdf; l.info = info;
-    const int rc = loo_launch<T>(h, layout, B, D, N, X, ldx, strideX, l, mw, stridemw, Tf, ldt, strideT, loo_total);
-    if (rc) return rc;
-    if (!h->async) HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return 0;
-  }
-  Staging guard(h);
+  CallIO io(h, memspace);
   const size_t x_one = N == 0 ? 0 : (layout == BLR_LAYOUT_COLVECS ? mat_extent(D, N, ldx) : mat_extent(N, D, ldx));
   const size_t s_one = N == 0 ? 0 : (noise_kind == BLR_NOISE_DIAGONAL ? (size_t)N : 1);
-  const size_t n_out = N == 0 ? 0 : (size_t)N;
+  const size_t n_out = (size_t)N;
   int rc;
-  const T *dX = nullptr, *dy = nullptr, *ds = nullptr, *dmw = nullptr, *dT = nullptr;
-  T *dlm = nullptr, *dlv = nullptr;
-  double *dll = nullptr, *dtot = nullptr;
+  const T *dX = nullptr, *dmw = nullptr, *dT = nullptr;
+  double* dtot = nullptr;
   int32_t* dinfo = nullptr;
-  if ((rc = stage_in(h, X, x_one ? extent(B, strideX, x_one) : 0, &dX))) return rc;
-  if ((rc = stage_in(h, y, n_out ? extent(B, stridey, n_out) : 0, &dy))) return rc;
-  if ((rc = stage_in(h, s, s_one ? extent(B, strides, s_one) : 0, &ds))) return rc;
-  if ((rc = stage_in(h, mw, extent(B, stridemw, (size_t)D), &dmw))) return rc;
-  if ((rc = stage_in(h, Tf, extent(B, strideT, mat_extent(D, D, ldt)), &dT))) return rc;
-  if ((rc = stage_out_alloc(h, loo_mean, n_out ? extent(B, stride_lm, n_out) : 0, &dlm))) return rc;
-  if ((rc = stage_out_alloc(h, loo_var, n_out ? extent(B, stride_lv, n_out) : 0, &dlv))) return rc;
-  if ((rc = stage_out_alloc(h, loo_logpdf, n_out ? extent(B, stride_ll, n_out) : 0, &dll))) return rc;
-  if ((rc = stage_out_alloc(h, loo_total, (size_t)B, &dtot))) return rc;
-  if ((rc = stage_out_alloc(h, info, (size_t)B, &dinfo))) return rc;
-  l.y = dy; l.s = ds; l.lm = dlm; l.lv = dlv; l.ll = dll; l.info = dinfo;
+  if ((rc = io.in(X, x_one ? extent(B, strideX, x_one) : 0, &dX))) return rc;
+  if ((rc = io.in(y, n_out ? extent(B, stridey, n_out) : 0, &l.y))) return rc;
+  if ((rc = io.in(s, s_one ? extent(B, strides, s_one) : 0, &l.s))) return rc;
+  if ((rc = io.in(mw, extent(B, stridemw, (size_t)D), &dmw))) return rc;
+  if ((rc = io.in(Tf, extent(B, strideT, mat_extent(D, D, ldt)), &dT))) return rc;
+  if ((rc = io.out(loo_mean, n_out ? extent(B, stride_lm, n_out) : 0, &l.lm))) return rc;
+  if ((rc = io.out(loo_var, n_out ? extent(B, stride_lv, n_out) : 0, &l.lv))) return rc;
+  if ((rc = io.out(loo_logpdf, n_out ? extent(B, stride_ll, n_out) : 0, &l.ll))) return rc;
+  if ((rc = io.out(loo_total, (size_t)B, &dtot))) return rc;
+  if ((rc = io.out(info, (size_t)B, &dinfo))) return rc;
+  l.info = dinfo;
   if ((rc = loo_launch<T>(h, layout, B, D, N, dX, ldx, strideX, l, dmw, stridemw, dT, ldt, strideT, dtot))) return rc;
-  if (dlm) HIP_TRY(h, hipMemcpyAsync(loo_mean, dlm, extent(B, stride_lm, n_out) * sizeof(T), hipMemcpyDeviceToHost, h->stream));
-  if (dlv) HIP_TRY(h, hipMemcpyAsync(loo_var, dlv, extent(B, stride_lv, n_out) * sizeof(T), hipMemcpyDeviceToHost, h->stream));
-  if (dll) HIP_TRY(h, hipMemcpyAsync(loo_logpdf, dll, extent(B, stride_ll, n_out) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (dtot) HIP_TRY(h, hipMemcpyAsync(loo_total, dtot, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(h, hipMemcpyAsync(info, dinfo, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(h, hipStreamSynchronize(h->stream));
-  return 0;
+  return io.finish();
 }
 
 // ---- evidence over a grid of (prior scale, noise scale) settings (blr_grid.hpp) --------------------------------------------------
@@ -3653,8 +3097,8 @@ int grid_small_nb(blr_handle* h, GridArgs<T> a, bool vec_ok) {
   const size_t nblk = (size_t)a.B * a.S;
   const size_t o_st = carve(nblk * SZ * sizeof(T)), o_sc = carve(nblk * 2 * sizeof(double)), o_bad = carve(nblk * sizeof(int32_t));
   const size_t o_pl = carve((size_t)a.B * sizeof(double)), o_pi = carve((size_t)a.B * sizeof(int32_t)), o_best = carve((size_t)a.B * sizeof(int64_t));
-  if ((rc = ensure_loo_ws(h, off))) return rc;
-  char* const ws = h->loo_ws;
+  if ((rc = h->loo_ws.reserve(h, off))) return rc;
+  char* const ws = h->loo_ws.p;
   a.stats = reinterpret_cast<T*>(ws + o_st); a.scal = reinterpret_cast<double*>(ws + o_sc); a.bad = reinterpret_cast<int32_t*>(ws + o_bad);
   a.prior_logdet = reinterpret_cast<double*>(ws + o_pl); a.prior_info = reinterpret_cast<int32_t*>(ws + o_pi);
   a.best = reinterpret_cast<int64_t*>(ws + o_best);
@@ -3696,8 +3140,8 @@ int grid_large(blr_handle* h, GridArgs<T> a) {
   auto carve = [&](size_t bytes) { size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
   const size_t o_s = carve((size_t)B * s_one * sizeof(T)), o_l = carve((size_t)B * lw_one * sizeof(T));
   const size_t o_lp = carve((size_t)B * sizeof(double)), o_in = carve((size_t)B * sizeof(int32_t)), o_best = carve((size_t)B * sizeof(int64_t));
-  if ((rc = ensure_loo_ws(h, off))) return rc;
-  char* const ws = h->loo_ws;
+  if ((rc = h->loo_ws.reserve(h, off))) return rc;
+  char* const ws = h->loo_ws.p;
   T* const s_g = reinterpret_cast<T*>(ws + o_s);
   T* const Lw_g = reinterpret_cast<T*>(ws + o_l);
   double* const lp_g = reinterpret_cast<double*>(ws + o_lp);
@@ -3813,43 +3257,26 @@ int logpdf_grid(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, i
   a.stride_mwbest = stride_mwbest; a.ldt = ldt; a.strideT = strideT;
   a.layout = layout; a.noise_kind = noise_kind; a.prior_kind = prior_kind;
   a.D = (int)D; a.N = (int)N; a.B = (int)B; a.G = (int)G; a.S = S; a.chunk = chunk;
-  if (memspace == BLR_MEM_DEVICE) {
-    a.X = X; a.y = y; a.s = s; a.mw = mw; a.Lw = Lw; a.alpha = alpha; a.tau = tau; a.logpdf = logpdf; a.info = info; a.best_out = best;
-    a.mw_best = mw_best; a.T_best = T_best;
-    if (N == 0) { if (!a.X) a.X = mw; if (!a.y) a.y = mw; }
-    const int rc = grid_launch<T>(h, a);
-    if (rc) return rc;
-    if (!h->async) HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return 0;
-  }
-  Staging guard(h);
+  CallIO io(h, memspace);
   const size_t x_one = N == 0 ? 0 : (layout == BLR_LAYOUT_COLVECS ? mat_extent(D, N, ldx) : mat_extent(N, D, ldx));
   const size_t lw_one = prior_kind == BLR_PRIOR_DIAGONAL ? (size_t)D : mat_extent(D, D, ldl);
   const size_t s_one = noise_kind == BLR_NOISE_DIAGONAL ? (size_t)N : 1;
-  const size_t n_lp = extent(B, stride_lp, (size_t)G), n_in = extent(B, stride_info, (size_t)G);
-  const size_t n_mw = extent(B, stride_mwbest, (size_t)D), n_T = extent(B, strideT, mat_extent(D, D, ldt));
   int rc;
-  if ((rc = stage_in(h, X, x_one ? extent(B, strideX, x_one) : 0, &a.X))) return rc;
-  if ((rc = stage_in(h, y, N ? extent(B, stridey, (size_t)N) : 0, &a.y))) return rc;
-  if ((rc = stage_in(h, s, std::max<size_t>(extent(B, strides, s_one), 1), &a.s))) return rc;
-  if ((rc = stage_in(h, mw, extent(B, stridemw, (size_t)D), &a.mw))) return rc;
-  if ((rc = stage_in(h, Lw, extent(B, strideLw, lw_one), &a.Lw))) return rc;
-  if ((rc = stage_in(h, alpha, extent(B, stride_alpha, (size_t)G), &a.alpha))) return rc;
-  if ((rc = stage_in(h, tau, extent(B, stride_tau, (size_t)G), &a.tau))) return rc;
-  if ((rc = stage_out_alloc(h, logpdf, n_lp, &a.logpdf))) return rc;
-  if ((rc = stage_out_alloc(h, info, n_in, &a.info))) return rc;
-  if ((rc = stage_out_alloc(h, best, (size_t)B, &a.best_out))) return rc;
-  if ((rc = stage_out_alloc(h, mw_best, n_mw, &a.mw_best))) return rc;
-  if ((rc = stage_out_alloc(h, T_best, n_T, &a.T_best))) return rc;
+  if ((rc = io.in(X, x_one ? extent(B, strideX, x_one) : 0, &a.X))) return rc;
+  if ((rc = io.in(y, N ? extent(B, stridey, (size_t)N) : 0, &a.y))) return rc;
+  if ((rc = io.in(s, std::max<size_t>(extent(B, strides, s_one), 1), &a.s))) return rc;
+  if ((rc = io.in(mw, extent(B, stridemw, (size_t)D), &a.mw))) return rc;
+  if ((rc = io.in(Lw, extent(B, strideLw, lw_one), &a.Lw))) return rc;
+  if ((rc = io.in(alpha, extent(B, stride_alpha, (size_t)G), &a.alpha))) return rc;
+  if ((rc = io.in(tau, extent(B, stride_tau, (size_t)G), &a.tau))) return rc;
+  if ((rc = io.out(logpdf, extent(B, stride_lp, (size_t)G), &a.logpdf))) return rc;
+  if ((rc = io.out(info, extent(B, stride_info, (size_t)G), &a.info))) return rc;
+  if ((rc = io.out(best, (size_t)B, &a.best_out))) return rc;
+  if ((rc = io.out(mw_best, extent(B, stride_mwbest, (size_t)D), &a.mw_best))) return rc;
+  if ((rc = io.out(T_best, extent(B, strideT, mat_extent(D, D, ldt)), &a.T_best))) return rc;
   if (N == 0) { if (!a.X) a.X = a.mw; if (!a.y) a.y = a.mw; }
   if ((rc = grid_launch<T>(h, a))) return rc;
-  HIP_TRY(h, hipMemcpyAsync(logpdf, a.logpdf, n_lp * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(h, hipMemcpyAsync(info, a.info, n_in * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-  if (best) HIP_TRY(h, hipMemcpyAsync(best, a.best_out, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
-  if (mw_best) HIP_TRY(h, hipMemcpyAsync(mw_best, a.mw_best, n_mw * sizeof(T), hipMemcpyDeviceToHost, h->stream));
-  if (T_best) HIP_TRY(h, hipMemcpyAsync(T_best, a.T_best, n_T * sizeof(T), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(h, hipStreamSynchronize(h->stream));
-  return 0;
+  return io.finish();
 }
 
 }  // namespace
@@ -3893,13 +3320,9 @@ int blr_destroy(blr_handle* h) {
   (void)hipSetDevice(h->device);
   (void)hipStreamSynchronize(h->stream);
   if (h->comm && rccl().ok) (void)rccl().CommDestroy(h->comm);
-  if (h->ws) (void)hipFree(h->ws);
-  if (h->feat) (void)hipFree(h->feat);
-  if (h->aux) (void)hipFree(h->aux);
-  if (h->i8side) (void)hipFree(h->i8side);
-  if (h->loo_ws) (void)hipFree(h->loo_ws);
+  for (DevBuf* b : h->releasable()) (void)hipFree(b->p);
+  (void)hipFree(h->xchg.p);
   if (h->stats_dev) (void)hipFree(h->stats_dev);
-  if (h->xchg) (void)hipFree(h->xchg);
   if (h->ticket) (void)hipFree(h->ticket);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
@@ -3915,11 +3338,10 @@ int blr_release_workspace(blr_handle* h) {
   h->err.clear();
   HIP_TRY(h, hipSetDevice(h->device));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
-  if (h->ws) { HIP_TRY(h, hipFree(h->ws)); h->ws = nullptr; h->ws_bytes = 0; }
-  if (h->feat) { HIP_TRY(h, hipFree(h->feat)); h->feat = nullptr; h->feat_bytes = 0; }
-  if (h->aux) { HIP_TRY(h, hipFree(h->aux)); h->aux = nullptr; h->aux_bytes = 0; }
-  if (h->i8side) { HIP_TRY(h, hipFree(h->i8side)); h->i8side = nullptr; h->i8side_bytes = 0; }
-  if (h->loo_ws) { HIP_TRY(h, hipFree(h->loo_ws)); h->loo_ws = nullptr; h->loo_ws_bytes = 0; }
+  for (DevBuf* b : h->releasable()) {
+    const int rc = b->release(h);
+    if (rc) return rc;
+  }
   return 0;
 }
 
@@ -4018,7 +3440,7 @@ int blr_get_stat(blr_handle* h, const char* key, int64_t* value) {
     return 0;
   }
   if (!strcmp(key, "workspace_bytes")) {
-    *value = (int64_t)(h->ws_bytes + h->feat_bytes + h->aux_bytes + h->i8side_bytes + h->xchg_bytes + h->loo_ws_bytes);
+    *value = (int64_t)(h->ws.bytes + h->feat.bytes + h->aux.bytes + h->i8side.bytes + h->xchg.bytes + h->loo_ws.bytes);
     return 0;
   }
   return bad_arg(h, 2, "unknown statistic");
@@ -4343,26 +3765,15 @@ int blr_logpdf_sum(blr_handle* h, int memspace, int64_t B, const double* logpdf,
   if (B > 0 && !logpdf) return bad_arg(h, 4, "logpdf is NULL");
   if (!total) return bad_arg(h, 5, "total is NULL");
   HIP_TRY(h, hipSetDevice(h->device));
-  Staging guard(h);
-  const double* lp = logpdf;
-  double* tot = total;
+  CallIO io(h, memspace);
+  const double* lp = nullptr;
+  double* tot = nullptr;
   int rc;
-  if (memspace == BLR_MEM_HOST) {
-    if ((rc = stage_in(h, logpdf, (size_t)B, &lp))) return rc;
-    void* p = nullptr;
-    HIP_TRY(h, hipMalloc(&p, sizeof(double)));
-    h->staged.push_back(p);
-    tot = static_cast<double*>(p);
-  }
+  if ((rc = io.in(logpdf, (size_t)B, &lp))) return rc;
+  if ((rc = io.out(total, 1, &tot))) return rc;
   hipLaunchKernelGGL(logpdf_sum_kernel, dim3(1), dim3(kThreads), 0, h->stream, lp, B, tot);
   HIP_TRY(h, hipGetLastError());
-  if (memspace == BLR_MEM_HOST) {
-    HIP_TRY(h, hipMemcpyAsync(total, tot, sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-  } else if (!h->async) {
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-  }
-  return 0;
+  return io.finish();
 }
 
 }  // extern "C"

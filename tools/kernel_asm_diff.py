@@ -54,6 +54,7 @@ def key(dm):
     """demangled name without a defaulted MarginalArgs template argument and without the return type / parameter list"""
     dm = re.sub(r", blr::MarginalArgs<(double|float)> >", ">", dm)
     dm = re.sub(r"^void ", "", dm)
+    dm = dm.replace("(anonymous namespace)::", "")  # (its parenthesis is not the parameter list's: mean_small_kernel<double> / <float>)
     return dm.split("(")[0]
 
 
