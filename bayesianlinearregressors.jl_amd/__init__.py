@@ -30,6 +30,7 @@ from .regressor import (
     logpdf_grid,
     logpdf_grid_map,
     logpdf_map,
+    logpdf_ragged,
     loo,
     loo_map,
     marginals,
@@ -39,6 +40,7 @@ from .regressor import (
     posterior,
     posterior_best,
     posterior_map,
+    posterior_ragged,
     rand,
     rand_and_pullback,
     rand_b,
@@ -53,4 +55,5 @@ __all__ = [
     "BLRFunctionSample", "RandomFourierFeatures", "mean_and_var", "mean_and_cov", "rand_b", "rand_and_pullback", "evaluate", "logpdf_columns", "logpdf_and_gradient", "logpdf_map", "posterior_map", "rand_map", "BLRError", "PosDefException", "ResidentPosterior",
     "LOO", "loo", "loo_map",
     "EvidenceGrid", "logpdf_grid", "posterior_best", "logpdf_grid_map",
+    "posterior_ragged", "logpdf_ragged",
 ]

@@ -74,6 +74,9 @@ for _suf in ("f64", "f32"):
     _SIGS[f"blr_posterior_batched_{_suf}"] = (
         [_H, _int, _int, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _int, _vp, _i64, _int, _vp, _i64, _vp, _i64, _i64,
          _vp, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp], _int)
+    _SIGS[f"blr_posterior_ragged_{_suf}"] = (
+        [_H, _int, _int, _i64, _i64, _vp, _vp, _i64, _vp, _int, _vp, _i64, _int, _vp, _i64, _vp, _i64, _i64,
+         _vp, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp], _int)
     _SIGS[f"blr_posterior_nsharded_{_suf}"] = (
         [_H, _int, _i64, _i64, _i64, _vp, _i64, _vp, _int, _vp, _int, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp], _int)
     _SIGS[f"blr_update_factor_{_suf}"] = (
@@ -283,6 +286,18 @@ class Handle:
                              _ptr(s), strides, prior_kind, _ptr(mw), stridemw, _ptr(Lw), ldl, strideLw,
                              _ptr(mw_post), stride_mwpost, _ptr(T_post), ldt, strideT, _ptr(Lw_post), ldlp, strideLp,
                              _ptr(logpdf), _ptr(info)))
+
+    def posterior_ragged(self, dtype, memspace, layout, B, D, offsets, X, ldx, y, noise_kind, s, strides, prior_kind, mw, stridemw,
+                         Lw, ldl, strideLw, mw_post, stride_mwpost, T_post, ldt, strideT, Lw_post, ldlp, strideLp, logpdf, info):
+        """B regressors with unequal observation counts, packed side by side, in one call; include/blr_mi355x.h
+        blr_posterior_ragged_*.  offsets: B + 1 non-decreasing entries, always on the host (any integer sequence)."""
+        fn = getattr(self.lib, f"blr_posterior_ragged_{suffix(dtype)}")
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        if offsets.shape != (B + 1,):
+            raise ValueError(f"offsets must have B + 1 = {B + 1} entries, got shape {offsets.shape}")
+        return self.check(fn(self._h, memspace, layout, B, D, _ptr(offsets), _ptr(X), ldx, _ptr(y), noise_kind, _ptr(s), strides,
+                             prior_kind, _ptr(mw), stridemw, _ptr(Lw), ldl, strideLw, _ptr(mw_post), stride_mwpost, _ptr(T_post),
+                             ldt, strideT, _ptr(Lw_post), ldlp, strideLp, _ptr(logpdf), _ptr(info)))
 
     def posterior_nsharded(self, dtype, layout, D, N_local, N_total, X, ldx, y, noise_kind, s, prior_kind, mw, Lw, ldl, stats, lds,
                            scal, mw_post, T_post, ldt, Lw_post, ldlp, logpdf, info):

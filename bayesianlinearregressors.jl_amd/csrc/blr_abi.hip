@@ -31,6 +31,7 @@
 #include "blr_marginals.hpp"
 #include "blr_rand_batched.hpp"
 #include "blr_grid.hpp"
+#include "blr_ragged.hpp"
 #include "blr_host.hpp"
 
 using namespace blr;
@@ -3279,6 +3280,136 @@ int logpdf_grid(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, i
   return io.finish();
 }
 
+// ---- regressors with unequal observation counts (blr_ragged.hpp) ---------------------------------------------------
+inline const void* ragged_kernel_ptr(double, int NB, int mode) { return ragged_kernel_ptr_f64(NB, mode); }
+inline const void* ragged_kernel_ptr(float, int NB, int mode) { return ragged_kernel_ptr_f32(NB, mode); }
+inline size_t ragged_kernel_lds(double, int NB) { return ragged_kernel_lds_f64(NB); }
+inline size_t ragged_kernel_lds(float, int NB) { return ragged_kernel_lds_f32(NB); }
+inline void ragged_kernel_launch(int NB, int mode, unsigned grid, hipStream_t st, const RaggedArgs<double>& a) { ragged_kernel_launch_f64(NB, mode, grid, st, a); }
+inline void ragged_kernel_launch(int NB, int mode, unsigned grid, hipStream_t st, const RaggedArgs<float>& a) { ragged_kernel_launch_f32(NB, mode, grid, st, a); }
+
+// D <= 128: offsets and the longest-first order go to the handle's metadata buffer, then ONE launch.  The upload drains the
+// stream (the host image belongs to the handle and the next call rewrites it); the kernel is only enqueued.
+template <typename T>
+int ragged_launch(blr_handle* h, RaggedArgs<T>& r, const int64_t* offsets) {
+  const int64_t B = r.p.B;
+  const size_t order_at = (size_t)(B + 1) * sizeof(int64_t), bytes = order_at + (size_t)B * sizeof(int32_t);
+  h->ragged_host.resize((bytes + 7) / 8);
+  std::memcpy(h->ragged_host.data(), offsets, order_at);
+  int32_t* const order = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(h->ragged_host.data()) + order_at);
+  for (int64_t b = 0; b < B; ++b) order[b] = (int32_t)b;
+  std::stable_sort(order, order + B, [offsets](int32_t i, int32_t j) { return offsets[i + 1] - offsets[i] > offsets[j + 1] - offsets[j]; });
+  int rc = h->ragged_meta.reserve(h, bytes, (size_t)1 << 16);
+  if (rc) return rc;
+  HIP_TRY(h, hipMemcpyAsync(h->ragged_meta.p, h->ragged_host.data(), bytes, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  r.offsets = reinterpret_cast<const int64_t*>(h->ragged_meta.p);
+  r.order = reinterpret_cast<const int32_t*>(h->ragged_meta.p + order_at);
+
+  const int NB = (r.p.D + 15) / 16;
+  const bool vec_ok = r.p.layout == BLR_LAYOUT_COLVECS && r.p.D % Mfma<T>::VEC == 0 && aligned16(r.p.X, r.p.ldx, 0) && !h->opt.no_ldsdma;
+  const int mode = r.p.layout == BLR_LAYOUT_ROWVECS ? 1 : (vec_ok ? 4 : 0);
+  r.p.vec_ok = vec_ok ? 1 : 0;
+  const void* const kern = ragged_kernel_ptr(T(0), NB, mode);
+  if (!kern) return bad_arg(h, 5, "this build carries no unequal-count kernel for this D and element type (BLR_DEV_FAST)");
+  if ((rc = set_lds_once(h, kern, ragged_kernel_lds(T(0), NB)))) return rc;
+  ragged_kernel_launch(NB, mode, (unsigned)std::min<int64_t>(B, 1 << 20), h->stream, r);
+  HIP_TRY(h, hipGetLastError());
+  h->route_buf = std::string("fused_ragged_kernel<") + (sizeof(T) == 8 ? "double" : "float") + ", " + std::to_string(NB) + ", " + std::to_string(mode) + ">";
+  h->route = h->route_buf.c_str();
+  h->route_i8_B = 0;
+  return 0;
+}
+
+template <typename T>
+int posterior_ragged(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, const int64_t* offsets, const T* X, int64_t ldx,
+                     const T* y, int noise_kind, const T* s, int64_t strides, int prior_kind, const T* mw, int64_t stridemw,
+                     const T* Lw, int64_t ldl, int64_t strideLw, T* mw_post, int64_t stride_mwpost, T* T_post, int64_t ldt,
+                     int64_t strideT, T* Lw_post, int64_t ldlp, int64_t strideLp, double* logpdf, int32_t* info) {
+  // (the argument checks come before the handle's: they need no device)
+  if (h) h->err.clear();
+  if (memspace != BLR_MEM_HOST && memspace != BLR_MEM_DEVICE) return bad_arg(h, 2, "memspace");
+  if (layout != BLR_LAYOUT_COLVECS && layout != BLR_LAYOUT_ROWVECS) return bad_arg(h, 3, "unknown layout (reference :26-31)");
+  if (B < 0 || B > (1 << 30)) return bad_arg(h, 4, "B out of range (0..2^30)");
+  if (D < 1 || D > kMaxLargeD) return bad_arg(h, 5, "D out of range (1..8192)");
+  if (B > 0 && !offsets) return bad_arg(h, 6, "offsets is NULL (a host array of B + 1 entries)");
+  if (B > 0 && offsets[0] < 0) return bad_arg(h, 6, "offsets[0] < 0");
+  for (int64_t b = 0; b < B; ++b) {
+    if (offsets[b + 1] < offsets[b]) return bad_arg(h, 6, "offsets must be non-decreasing");
+    if (offsets[b + 1] - offsets[b] > (1 << 30)) return bad_arg(h, 6, "a regressor with more than 2^30 observations");
+  }
+  const int64_t total = B > 0 ? offsets[B] : 0;              // columns of the packed arrays
+  const bool any = B > 0 && offsets[B] > offsets[0];
+  if (any && !X) return bad_arg(h, 7, "X is NULL");
+  if (layout == BLR_LAYOUT_COLVECS ? ldx < D : ldx < std::max<int64_t>(total, 1)) return bad_arg(h, 8, "ldx too small");
+  if (any && !y) return bad_arg(h, 9, "y is NULL (reference :74 length check)");
+  if (noise_kind != BLR_NOISE_ISOTROPIC && noise_kind != BLR_NOISE_DIAGONAL)
+    return bad_arg(h, 10, "noise_kind (isotropic or diagonal; dense Sigma_y is not supported for unequal counts)");
+  if (!s && (noise_kind == BLR_NOISE_ISOTROPIC || any)) return bad_arg(h, 11, "s is NULL");
+  if (strides < 0) return bad_arg(h, 12, "strides < 0");
+  if (prior_kind != BLR_PRIOR_DENSE && prior_kind != BLR_PRIOR_UPPER_FACTOR && prior_kind != BLR_PRIOR_DIAGONAL)
+    return bad_arg(h, 13, "prior_kind");
+  if (!mw) return bad_arg(h, 14, "mw is NULL");
+  if (stridemw < 0) return bad_arg(h, 15, "stridemw < 0");
+  if (!Lw) return bad_arg(h, 16, "Lw is NULL");
+  if (prior_kind != BLR_PRIOR_DIAGONAL && ldl < D) return bad_arg(h, 17, "ldl < D");
+  if (strideLw < 0) return bad_arg(h, 18, "strideLw < 0");
+  if (mw_post && B > 1 && stride_mwpost < D) return bad_arg(h, 20, "stride_mwpost < D");
+  if (T_post && ldt < D) return bad_arg(h, 22, "ldt < D");
+  if (T_post && B > 1 && strideT < (int64_t)mat_extent(D, D, ldt)) return bad_arg(h, 23, "strideT too small");
+  if (Lw_post && ldlp < D) return bad_arg(h, 25, "ldlp < D");
+  if (Lw_post && B > 1 && strideLp < (int64_t)mat_extent(D, D, ldlp)) return bad_arg(h, 26, "strideLp too small");
+  if (B > 0 && !info) return bad_arg(h, 28, "info is NULL");
+  if (B == 0) return 0;
+  if (!h) return -1;
+  HIP_TRY(h, hipSetDevice(h->device));
+  const bool diag = noise_kind == BLR_NOISE_DIAGONAL;
+  RaggedArgs<T> r{};
+  PosteriorArgs<T>& a = r.p;
+  a.ldx = ldx; a.strides = diag ? 0 : strides; a.stridemw = stridemw; a.ldl = ldl; a.strideLw = strideLw;
+  a.stride_mwpost = stride_mwpost; a.ldt = ldt; a.strideT = strideT; a.ldlp = ldlp; a.strideLp = strideLp;
+  a.layout = layout; a.noise_kind = noise_kind; a.prior_kind = prior_kind;
+  a.D = (int)D; a.B = (int)B;
+
+  CallIO io(h, memspace);
+  const size_t x_all = !any ? 0 : (layout == BLR_LAYOUT_COLVECS ? mat_extent(D, total, ldx) : mat_extent(total, D, ldx));
+  const size_t lw_one = prior_kind == BLR_PRIOR_DIAGONAL ? (size_t)D : mat_extent(D, D, ldl);
+  int rc;
+  if ((rc = io.in(X, x_all, &a.X))) return rc;
+  if ((rc = io.in(y, any ? (size_t)total : 0, &a.y))) return rc;
+  if ((rc = io.in(s, diag ? (any ? (size_t)total : 0) : extent(B, strides, 1), &a.s))) return rc;
+  if ((rc = io.in(mw, extent(B, stridemw, (size_t)D), &a.mw))) return rc;
+  if ((rc = io.in(Lw, extent(B, strideLw, lw_one), &a.Lw))) return rc;
+  if ((rc = io.out(mw_post, extent(B, stride_mwpost, (size_t)D), &a.mw_post))) return rc;
+  if ((rc = io.out(T_post, extent(B, strideT, mat_extent(D, D, ldt)), &a.T_post))) return rc;
+  if ((rc = io.out(Lw_post, extent(B, strideLp, mat_extent(D, D, ldlp)), &a.Lw_post))) return rc;
+  if ((rc = io.out(logpdf, (size_t)B, &a.logpdf))) return rc;
+  if ((rc = io.out(info, (size_t)B, &a.info))) return rc;
+  // no data at all (or, host memspace, nothing staged): the kernel never dereferences these, but keep the pointers valid
+  if (!a.X) a.X = a.mw;
+  if (!a.y) a.y = a.mw;
+  if (!a.s) a.s = a.mw;
+  if (D <= kMaxSmallD) {
+    if ((rc = ragged_launch<T>(h, r, offsets))) return rc;
+    return io.finish();
+  }
+  // D > 128: correct, not fast -- one regressor after the other through the pipeline of blr_posterior_batched_*; the call synchronises
+  const bool was_async = h->async;
+  h->async = false;
+  for (int64_t b = 0; b < B && rc == 0; ++b) {
+    const int64_t o = offsets[b], n = offsets[b + 1] - o;
+    rc = posterior_batched<T>(h, BLR_MEM_DEVICE, layout, 1, D, n, a.X + (layout == BLR_LAYOUT_COLVECS ? o * ldx : o), ldx, 0, a.y + o, 0,
+                              noise_kind, diag ? a.s + o : a.s + b * strides, 0, prior_kind, a.mw + b * stridemw, 0, a.Lw + b * strideLw,
+                              ldl, 0, a.mw_post ? a.mw_post + b * stride_mwpost : (T*)nullptr, 0, a.T_post ? a.T_post + b * strideT : (T*)nullptr,
+                              ldt, 0, a.Lw_post ? a.Lw_post + b * strideLp : (T*)nullptr, ldlp, 0, a.logpdf ? a.logpdf + b : (double*)nullptr,
+                              a.info + b);
+  }
+  h->async = was_async;
+  if (rc) return rc;  // (device pointers and in-range sizes: a HIP failure, not an argument index of the inner call)
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  return io.finish();
+}
+
 }  // namespace
 
 // =======================================================================================================
@@ -3440,7 +3571,7 @@ int blr_get_stat(blr_handle* h, const char* key, int64_t* value) {
     return 0;
   }
   if (!strcmp(key, "workspace_bytes")) {
-    *value = (int64_t)(h->ws.bytes + h->feat.bytes + h->aux.bytes + h->i8side.bytes + h->xchg.bytes + h->loo_ws.bytes);
+    *value = (int64_t)(h->ws.bytes + h->feat.bytes + h->aux.bytes + h->i8side.bytes + h->xchg.bytes + h->loo_ws.bytes + h->ragged_meta.bytes);
     return 0;
   }
   return bad_arg(h, 2, "unknown statistic");
@@ -3551,6 +3682,16 @@ int blr_timer_stop(blr_handle* h, float* elapsed_ms) {
     return logpdf_grid<T>(h, memspace, layout, B, D, N, X, ldx, strideX, y, stridey, noise_kind, s, strides,        \
                           prior_kind, mw, stridemw, Lw, ldl, strideLw, G, alpha, stride_alpha, tau, stride_tau,     \
                           logpdf, stride_lp, best, mw_best, stride_mwbest, T_best, ldt, strideT, info, stride_info);\
+  }                                                                                                                 \
+  int blr_posterior_ragged_##SUF(blr_handle* h, int memspace, int layout, int64_t B, int64_t D,                     \
+                                 const int64_t* offsets, const T* X, int64_t ldx, const T* y, int noise_kind,       \
+                                 const T* s, int64_t strides, int prior_kind, const T* mw, int64_t stridemw,        \
+                                 const T* Lw, int64_t ldl, int64_t strideLw, T* mw_post, int64_t stride_mwpost,     \
+                                 T* T_post, int64_t ldt, int64_t strideT, T* Lw_post, int64_t ldlp,                 \
+                                 int64_t strideLp, double* logpdf, int32_t* info) {                                 \
+    return posterior_ragged<T>(h, memspace, layout, B, D, offsets, X, ldx, y, noise_kind, s, strides, prior_kind,   \
+                               mw, stridemw, Lw, ldl, strideLw, mw_post, stride_mwpost, T_post, ldt, strideT,       \
+                               Lw_post, ldlp, strideLp, logpdf, info);                                              \
   }                                                                                                                 \
   int blr_posterior_##SUF(blr_handle* h, int layout, int64_t D, int64_t N, const T* X, int64_t ldx, const T* y,     \
                           int noise_kind, const T* s, int prior_kind, const T* mw, const T* Lw, int64_t ldl,        \

@@ -28,6 +28,7 @@ __all__ = [
     "mean", "var", "cov", "std", "mean_and_var", "mean_and_cov", "marginals", "rand", "rand_b", "logpdf", "posterior",
     "LOO", "loo", "loo_map",
     "EvidenceGrid", "logpdf_grid", "posterior_best", "logpdf_grid_map",
+    "posterior_ragged", "logpdf_ragged",
 ]
 
 
@@ -539,8 +540,10 @@ def posterior(fx, y):
 # (config 4 of BASELINE.json is this with 8192 regressors; at D > 128 the regressors share every launch of the update)
 # ---------------------------------------------------------------------------------------------------
 def _fused_many(fxs, ys, want_posterior):
-    """[(logpdf, mw', T, A)] for equally shaped problems through blr_posterior_batched_*; shapes, layouts, noise or prior
-    kinds that differ (or a dense noise covariance, or a fused random-Fourier basis) fall back to one call per problem.
+    """[(logpdf, mw', T, A)] in ONE library call: equally shaped problems through blr_posterior_batched_*, problems that agree
+    on everything but the number of observations (same D, layout, isotropic or diagonal noise, prior kind, dtype) packed side
+    by side through blr_posterior_ragged_*.  Layouts, noise or prior kinds that differ (or a dense noise covariance, or a
+    fused random-Fourier basis) fall back to one call per problem.
     The first problem (in order) whose prior, noise or posterior precision is not positive definite raises
     PosDefException, as the map over the reference's methods would; its position is the exception's ``index``."""
     fxs, ys = list(fxs), list(ys)
@@ -565,15 +568,16 @@ def _fused_many(fxs, ys, want_posterior):
         Lw, prior_kind, ldl = _prior(fb.f.Lw, D, dtype)
         probs.append((X, layout, ldx, D, N, y, s, noise_kind, _mean_vector(fb.f.mw, D, dtype), Lw, prior_kind, ldl,
                       isinstance(fb.f.Lw, PDMat)))
-    sig = {(q[0].shape, q[0].flags.f_contiguous, q[1], q[3], q[4], q[7], q[10], q[12]) for q in probs}
-    if len(sig) != 1 or probs[0][7] == _abi.NOISE_DENSE or probs[0][3] == 0 or probs[0][4] == 0:
-        return one_by_one()
     X0, layout, ldx, D, N, _, s0, noise_kind, _, _, prior_kind, ldl, pdmat = probs[0]
+    if noise_kind == _abi.NOISE_DENSE or D == 0:
+        return one_by_one()
+    sig = {(q[0].shape, q[0].flags.f_contiguous, q[1], q[3], q[4], q[7], q[10], q[12]) for q in probs}
+    ragged = len(sig) != 1
+    if ragged and len({(q[1], q[3], q[7], q[10], q[12]) for q in probs}) != 1:
+        return one_by_one()
+    if not ragged and N == 0:
+        return one_by_one()
     nb = len(probs)
-    # one contiguous block per operand: problem b at b * stride (each X already is ldx x cols column-major in memory)
-    Xb = np.stack([q[0].reshape(-1, order="A") for q in probs])
-    yb = np.stack([q[5] for q in probs])
-    sb = np.stack([q[6] for q in probs])
     mwb = np.stack([q[8] for q in probs])
     Lb = np.stack([q[9].reshape(-1, order="A") for q in probs])  # D, or D x D column-major
     lp = np.zeros(nb, dtype=np.float64)
@@ -584,20 +588,109 @@ def _fused_many(fxs, ys, want_posterior):
         Ab = np.empty((nb, D * D), dtype=dtype) if not pdmat else None
     else:
         mw_post = Tb = Ab = None
-    _handle().posterior_batched(dtype, _abi.MEM_HOST, layout, nb, D, N, Xb, ldx, Xb.shape[1], yb, yb.shape[1], noise_kind, sb,
-                                sb.shape[1], prior_kind, mwb, D, Lb, ldl, Lb.shape[1], mw_post, D, Tb, D, D * D, Ab, D, D * D, lp, info)
+    if ragged:
+        # the observations side by side: ColVecs problems are D x N_b column-major each (their columns simply follow one
+        # another), RowVecs problems N_b x D column-major (stacked by rows into one offsets[-1] x D column-major matrix)
+        offsets = np.concatenate(([0], np.cumsum([q[4] for q in probs]))).astype(np.int64)
+        if layout == _abi.LAYOUT_COLVECS:
+            Xp, ldxp = np.concatenate([q[0].reshape(-1, order="A") for q in probs]), D
+        else:
+            Xp = np.asfortranarray(np.concatenate([q[0].reshape(-1, order="A").reshape((q[4], D), order="F") for q in probs]))
+            ldxp = max(int(offsets[-1]), 1)
+        yp = np.concatenate([q[5] for q in probs])
+        sp = np.concatenate([q[6] for q in probs])  # isotropic: one variance per problem (strides = 1); diagonal: packed like y
+        _handle().posterior_ragged(dtype, _abi.MEM_HOST, layout, nb, D, offsets, Xp, ldxp, yp, noise_kind, sp, 1, prior_kind, mwb, D,
+                                   Lb, ldl, Lb.shape[1], mw_post, D, Tb, D, D * D, Ab, D, D * D, lp, info)
+    else:
+        # one contiguous block per operand: problem b at b * stride (each X already is ldx x cols column-major in memory)
+        Xb = np.stack([q[0].reshape(-1, order="A") for q in probs])
+        yb = np.stack([q[5] for q in probs])
+        sb = np.stack([q[6] for q in probs])
+        _handle().posterior_batched(dtype, _abi.MEM_HOST, layout, nb, D, N, Xb, ldx, Xb.shape[1], yb, yb.shape[1], noise_kind, sb,
+                                    sb.shape[1], prior_kind, mwb, D, Lb, ldl, Lb.shape[1], mw_post, D, Tb, D, D * D, Ab, D, D * D, lp, info)
+    return _unpack_many(lp, info, mw_post, Tb, Ab, D)
+
+
+def _unpack_many(lp, info, mw_post, Tb, Ab, D):
+    """Per-problem results of a batched / ragged call; the first failed problem raises PosDefException with its ``index``."""
     bad = np.flatnonzero(info > 0)
     if bad.size:
         e = _abi.PosDefException(int(info[bad[0]]))
         e.index = int(bad[0])
         raise e
     out = []
-    for b in range(nb):
-        if want_posterior:
+    for b in range(lp.shape[0]):
+        if mw_post is not None:
             out.append((float(lp[b]), mw_post[b], Tb[b].reshape((D, D), order="F"), Ab[b].reshape((D, D), order="F") if Ab is not None else None))
         else:
             out.append((float(lp[b]), None, None, None))
     return out
+
+
+def _ragged_packed(f, x, offsets, Sy, y, want_posterior):
+    """The packed form behind posterior_ragged / logpdf_ragged -> ([(logpdf, mw', T, A)], the B prior regressors)."""
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    if offsets.ndim != 1 or offsets.shape[0] < 1:
+        raise ValueError("offsets must be a vector of B + 1 entries")
+    nb, total = offsets.shape[0] - 1, int(offsets[-1])
+    fs = [f] * nb if isinstance(f, BayesianLinearRegressor) else list(f)
+    if len(fs) != nb or not all(isinstance(g, BayesianLinearRegressor) for g in fs):
+        raise ValueError("f must be one BayesianLinearRegressor or B = len(offsets) - 1 of them")
+    if nb == 0:
+        return [], fs
+    dtype = np.float32 if all(_dtype_of(g.mw, y) == np.float32 for g in fs) else np.float64
+    X, layout, ldx, D, N = _x_layout(x, dtype)
+    if N != total:
+        raise ValueError("offsets[-1] != number of inputs")
+    y = np.ascontiguousarray(y, dtype=dtype)
+    if y.ndim != 1 or y.shape[0] != N:
+        raise ValueError("length(y) != size(fx.x.X, 2)")  # reference :74
+    if isinstance(Sy, Diagonal):
+        s, noise_kind = _noise(Sy, N, dtype)
+    else:
+        Sy = np.asarray(Sy, dtype=dtype)
+        if Sy.ndim == 1 and Sy.shape[0] != N and Sy.shape[0] == nb:  # one variance per regressor
+            s, noise_kind = np.ascontiguousarray(Sy), _abi.NOISE_ISOTROPIC
+        else:
+            s, noise_kind = _noise(Sy, N, dtype)
+    if noise_kind == _abi.NOISE_DENSE:
+        raise ValueError("a dense noise covariance is not supported for packed regressors")
+    shared = isinstance(f, BayesianLinearRegressor)
+    priors = [_prior(g.Lw, D, dtype) for g in ([f] if shared else fs)]
+    if len({(k, isinstance(g.Lw, PDMat)) for (_, k, _), g in zip(priors, fs)}) != 1:
+        raise ValueError("the regressors must share one kind of prior precision")
+    _, prior_kind, ldl = priors[0]
+    pdmat = isinstance(fs[0].Lw, PDMat)
+    mwb = np.stack([_mean_vector(g.mw, D, dtype) for g in ([f] if shared else fs)])
+    Lb = np.stack([q[0].reshape(-1, order="A") for q in priors])
+    lp = np.zeros(nb, dtype=np.float64)
+    info = np.zeros(nb, dtype=np.int32)
+    if want_posterior:
+        mw_post = np.empty((nb, D), dtype=dtype)
+        Tb = np.empty((nb, D * D), dtype=dtype)
+        Ab = np.empty((nb, D * D), dtype=dtype) if not pdmat else None
+    else:
+        mw_post = Tb = Ab = None
+    _handle().posterior_ragged(dtype, _abi.MEM_HOST, layout, nb, D, offsets, X, ldx, y, noise_kind, s, 1 if s.shape[0] == nb and noise_kind == _abi.NOISE_ISOTROPIC else 0,
+                               prior_kind, mwb, 0 if shared else D, Lb, ldl, 0 if shared else Lb.shape[1], mw_post, D, Tb, D, D * D, Ab, D,
+                               D * D, lp, info)
+    return _unpack_many(lp, info, mw_post, Tb, Ab, D), fs
+
+
+def logpdf_ragged(f, x, offsets, Sy, y):
+    """Log evidence of B regressors whose observations are already packed side by side: regressor b owns the inputs / entries
+    of y ``offsets[b]:offsets[b+1]`` (reference :55-58 under a map over fxs of different lengths), one library call.
+    ``f``: one BayesianLinearRegressor shared by all, or B of them with one kind of prior precision.  ``Sy``: a scalar (one
+    variance for all), a vector of B variances (one per regressor), or a vector / Diagonal of ``offsets[-1]``
+    per-observation variances (a plain vector whose length equals both is read per observation)."""
+    return np.array([r[0] for r in _ragged_packed(f, x, offsets, Sy, y, want_posterior=False)[0]])
+
+
+def posterior_ragged(f, x, offsets, Sy, y):
+    """[posterior(f_b(x[offsets[b]:offsets[b+1]], Sy_b), y[...])] (reference :60-69 under a map) from packed arrays in one
+    library call; arguments as logpdf_ragged."""
+    res, fs = _ragged_packed(f, x, offsets, Sy, y, want_posterior=True)
+    return [BayesianLinearRegressor(mw_post, _wrap_like(g.Lw, T, A)) for g, (_, mw_post, T, A) in zip(fs, res)]
 
 
 def logpdf_map(fxs, ys):

@@ -102,7 +102,7 @@ const char* blr_last_route(blr_handle* h);
 int blr_get_stat(blr_handle* h, const char* key, int64_t* value);
 int blr_reset_stats(blr_handle* h);
 /* The handle's device scratch (factorisation workspaces of D > 128 calls -- up to 8 GiB for a large batched call, see CHAIN_WS_MB --
- * the feature matrix of blr_posterior_rff_*, the int8 / marginal side buffers, the statistics buffer of blr_logpdf_grid_*) only ever GROWS between calls; this drains the
+ * the feature matrix of blr_posterior_rff_*, the int8 / marginal side buffers, the statistics buffer of blr_logpdf_grid_*, the offsets / order of blr_posterior_ragged_*) only ever GROWS between calls; this drains the
  * stream and frees all of it.  The next call allocates what it needs again. */
 int blr_release_workspace(blr_handle* h);
 
@@ -179,6 +179,57 @@ int blr_posterior_batched_f32(blr_handle* h, int memspace, int layout, int64_t B
                               float* T_post, int64_t ldt, int64_t strideT,
                               float* Lw_post, int64_t ldlp, int64_t strideLp,
                               double* logpdf, int32_t* info);
+
+/* ---- regressors with UNEQUAL observation counts in one call -----------------------------------------------------
+ * Replaces: reference src/bayesian_linear_regression.jl:55-58 (logpdf), :60-69 (posterior) and :72-89 (shared quantities) under a
+ * map over fxs of different lengths -- which blr_posterior_batched_* (one N for the batch) serves only by a loop of calls or by
+ * padding every regressor to the longest one.
+ * The observations of all regressors are packed side by side: regressor b owns observations [offsets[b], offsets[b+1]), N_b =
+ * offsets[b+1] - offsets[b].  ColVecs: X is D x offsets[B] column-major, ldx >= D, regressor b starts at X + offsets[b]*ldx.
+ * RowVecs: X is offsets[B] x D column-major, ldx >= offsets[B], regressor b starts at X + offsets[b], its element (d,n) at
+ * + n + d*ldx.  y + offsets[b].  Diagonal noise: s + offsets[b] (strides ignored); isotropic noise: s + b*strides (0: one variance
+ * for all regressors); dense noise is an argument error.  The prior, the prior mean, the outputs (each may be NULL), info[B], the
+ * in-place form under BLR_PRIOR_UPPER_FACTOR and the return codes are those of blr_posterior_batched_*: every regressor has its own
+ * status, mw_post and T_post of a regressor with info != 0 are left untouched and its logpdf is NaN, the call returns 0 when the
+ * launch succeeded; output strides that overlap for B > 1 are argument errors.
+ * offsets is shape metadata like N: ALWAYS a host array of B + 1 entries, in both memspaces; offsets[0] >= 0, non-decreasing (N_b = 0
+ * is allowed: the posterior is the prior, the evidence 0), every N_b <= 2^30 (the bound on N of blr_posterior_batched_*); a
+ * violation is argument error -6.  The argument checks come before the handle's.  B = 0 is a no-op.
+ * D <= 128 (csrc/blr_ragged.hpp): ONE launch of one workgroup per regressor running the phases of the fused kernel --
+ * streaming Gram on the fp64 / fp32 matrix cores, blocked Cholesky, back substitution -- on the regressor's slice.  The host orders
+ * the regressors by descending N_b (ties by index), workgroup i takes the i-th longest: with the hardware's in-order dispatch that is
+ * longest-first list scheduling.  offsets and that order (12 bytes per regressor) are uploaded to the handle's workspace
+ * (blr_release_workspace frees it).  This route always uses these phases: the int8-sliced Gram and the one-wave kernel stay with the
+ * equal-count entry point.  The LDS-DMA loader needs ColVecs with 16-byte aligned X and ldx (no condition on offsets); other ColVecs
+ * data and RowVecs take the generic loaders.
+ * Numerics: the outputs of regressor b are bit for bit those of blr_posterior_batched_* with B = 1 on its slice on a handle with
+ * NO_I8_GRAM = 1 and NO_WAVE_KERNEL = 1 (the same code on the same data); bit-reproducible from call to call, independent of B, of
+ * the other regressors' data and of any permutation of the batch.
+ * Async handle, device memspace: the call only enqueues the kernel, but the upload of offsets / order drains the handle's stream
+ * first (it may block the host); the library is finished with the caller's offsets array when the call returns.
+ * D > 128: correct, not fast -- one regressor after the other through the pipeline of blr_posterior_batched_* with B = 1; the call
+ * synchronises whatever the handle's async flag says.
+ * _f32: X, y, s, mw, Lw, mw_post, T_post, Lw_post are float; logpdf stays double. */
+int blr_posterior_ragged_f64(blr_handle* h, int memspace, int layout, int64_t B, int64_t D,
+                             const int64_t* offsets, /* HOST array of B + 1 entries in both memspaces */
+                             const double* X, int64_t ldx, const double* y,
+                             int noise_kind, const double* s, int64_t strides,
+                             int prior_kind, const double* mw, int64_t stridemw,
+                             const double* Lw, int64_t ldl, int64_t strideLw,
+                             double* mw_post, int64_t stride_mwpost,
+                             double* T_post, int64_t ldt, int64_t strideT,
+                             double* Lw_post, int64_t ldlp, int64_t strideLp,
+                             double* logpdf, int32_t* info);
+int blr_posterior_ragged_f32(blr_handle* h, int memspace, int layout, int64_t B, int64_t D,
+                             const int64_t* offsets, /* HOST array of B + 1 entries in both memspaces */
+                             const float* X, int64_t ldx, const float* y,
+                             int noise_kind, const float* s, int64_t strides,
+                             int prior_kind, const float* mw, int64_t stridemw,
+                             const float* Lw, int64_t ldl, int64_t strideLw,
+                             float* mw_post, int64_t stride_mwpost,
+                             float* T_post, int64_t ldt, int64_t strideT,
+                             float* Lw_post, int64_t ldlp, int64_t strideLp,
+                             double* logpdf, int32_t* info);
 
 /* single regressor, host pointers; returns info (see "Return codes") */
 int blr_posterior_f64(blr_handle* h, int layout, int64_t D, int64_t N, const double* X, int64_t ldx,

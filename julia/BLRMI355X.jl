@@ -194,11 +194,11 @@ function posterior(fx::FiniteGP, y::AbstractVector{<:Real})
     fx.f isa BasisFunctionRegressor ? BasisFunctionRegressor(post, fx.f.ϕ) : post           # :62-65
 end
 
-# ---- many equally shaped problems in ONE library call: `map(posterior, fxs, ys)` / `logpdf.(fxs, ys)` -------------------
+# ---- many problems in ONE library call: `map(posterior, fxs, ys)` / `logpdf.(fxs, ys)` -------------------
 # (BASELINE config 4 is this with 8192 regressors; at D > 128 the regressors share every launch of the update.)  Host arrays
-# are packed side by side -- problem b at b * stride -- and handed to blr_posterior_batched_* with BLR_MEM_HOST.  Collections
-# the batched entry point does not take (mixed shapes / layouts / kinds, dense noise, a fused random-Fourier basis) are
-# mapped one by one.  The first problem that is not positive definite throws PosDefException, as the map would.
+# are packed side by side -- problem b at b * stride -- and handed to blr_posterior_batched_* with BLR_MEM_HOST; problems that
+# differ only in their number of observations go to blr_posterior_ragged_* (fused_ragged).  Collections neither entry point
+# takes (mixed layouts / kinds, dense noise, a fused random-Fourier basis) are mapped one by one.  The first problem that is not positive definite throws PosDefException, as the map would.
 function fused_many(fxs::AbstractVector{<:FiniteGP}, ys::AbstractVector{<:AbstractVector{<:Real}}, want_posterior::Bool)
     length(fxs) == length(ys) || throw(DimensionMismatch("as many observation vectors as finite regressors are needed"))
     B = length(fxs)
@@ -210,10 +210,13 @@ function fused_many(fxs::AbstractVector{<:FiniteGP}, ys::AbstractVector{<:Abstra
     X1, layout, _, D, N = xls[1]
     T = eltype(X1)
     nk, pk = nzs[1][2], prs[1][2]
-    (nk == DENSEN || D == 0 || N == 0) && return nothing
-    same = all(b -> eltype(xls[b][1]) === T && xls[b][2] == layout && xls[b][4] == D && xls[b][5] == N && nzs[b][2] == nk &&
-                    prs[b][2] == pk && length(ys[b]) == N && length(fbs[b].f.mw) == D, 1:B)
-    same || return nothing
+    (nk == DENSEN || D == 0) && return nothing
+    alike = all(b -> eltype(xls[b][1]) === T && xls[b][2] == layout && xls[b][4] == D && nzs[b][2] == nk &&
+                     prs[b][2] == pk && length(ys[b]) == xls[b][5] && length(fbs[b].f.mw) == D, 1:B)
+    alike || return nothing
+    # everything but the number of observations agrees: ONE blr_posterior_ragged_* call on the packed observations
+    all(b -> xls[b][5] == N, 1:B) || return fused_ragged(fbs, ys, xls, nzs, prs, want_posterior)
+    N == 0 && return nothing
     rows, cols = layout == COLVECS ? (D, N) : (N, D)
     Xb = Array{T}(undef, rows, cols, B)
     for b in 1:B
@@ -259,6 +262,68 @@ function fused_many(fxs::AbstractVector{<:FiniteGP}, ys::AbstractVector{<:Abstra
         end
     end
     check(h, rc)
+    bad = findfirst(>(0), info)
+    bad === nothing || throw(PosDefException(Int(info[bad])))
+    want_posterior || return [(lp[b], nothing, nothing, nothing) for b in 1:B]
+    return [(lp[b], mw_post[:, b], Tp[:, :, b], Ap isa Ptr ? Ap : Ap[:, :, b]) for b in 1:B]
+end
+
+# blr_posterior_ragged_* (include/blr_mi355x.h): B regressors with unequal observation counts, packed side by side; `offsets`
+# (B + 1 entries, zero based) is ALWAYS a host array.  The other arrays are host Arrays (MEM_HOST) or raw device pointers.
+function posterior_ragged_call(h, ::Type{T}, memspace, layout, B, D, offsets::Vector{Int64}, X, ldx, y, nk, s, strides, pk, mw, stridemw,
+                               Lw, ldl, strideLw, mw_post, stride_mwpost, Tp, ldt, strideT, Ap, ldlp, strideLp, lp, info) where {T<:Elt}
+    GC.@preserve offsets X y s mw Lw mw_post Tp Ap lp info begin
+        if T === Float64
+            ccall((:blr_posterior_ragged_f64, LIB), Cint,
+                  (Ptr{Cvoid}, Cint, Cint, Int64, Int64, Ptr{Int64}, Ptr{T}, Int64, Ptr{T}, Cint, Ptr{T}, Int64, Cint, Ptr{T}, Int64,
+                   Ptr{T}, Int64, Int64, Ptr{T}, Int64, Ptr{T}, Int64, Int64, Ptr{T}, Int64, Int64, Ptr{Cdouble}, Ptr{Int32}),
+                  h, memspace, layout, B, D, offsets, X, ldx, y, nk, s, strides, pk, mw, stridemw,
+                  Lw, ldl, strideLw, mw_post, stride_mwpost, Tp, ldt, strideT, Ap, ldlp, strideLp, lp, info)
+        else
+            ccall((:blr_posterior_ragged_f32, LIB), Cint,
+                  (Ptr{Cvoid}, Cint, Cint, Int64, Int64, Ptr{Int64}, Ptr{T}, Int64, Ptr{T}, Cint, Ptr{T}, Int64, Cint, Ptr{T}, Int64,
+                   Ptr{T}, Int64, Int64, Ptr{T}, Int64, Ptr{T}, Int64, Int64, Ptr{T}, Int64, Int64, Ptr{Cdouble}, Ptr{Int32}),
+                  h, memspace, layout, B, D, offsets, X, ldx, y, nk, s, strides, pk, mw, stridemw,
+                  Lw, ldl, strideLw, mw_post, stride_mwpost, Tp, ldt, strideT, Ap, ldlp, strideLp, lp, info)
+        end
+    end
+end
+
+# fused_many for problems that differ only in their number of observations (xls / nzs / prs: their xlayout / noise / prior)
+function fused_ragged(fbs, ys, xls, nzs, prs, want_posterior::Bool)
+    B = length(fbs)
+    X1, layout, _, D, _ = xls[1]
+    T = eltype(X1)
+    nk, pk = nzs[1][2], prs[1][2]
+    offsets = Int64[0; cumsum(Int64[xl[5] for xl in xls])]
+    total = Int(offsets[end])
+    # ColVecs: D x N_b blocks side by side; RowVecs: N_b x D blocks stacked by rows (one total x D column-major matrix)
+    Xp = layout == COLVECS ? Matrix{T}(undef, D, total) : Matrix{T}(undef, total, D)
+    yp = Vector{T}(undef, total)
+    sp = Vector{T}(undef, nk == ISOTROPIC ? B : total)
+    for b in 1:B
+        r = (offsets[b] + 1):offsets[b + 1]
+        copyto!(layout == COLVECS ? view(Xp, :, r) : view(Xp, r, :), xls[b][1])
+        yp[r] .= ys[b]
+        nk == ISOTROPIC ? (sp[b] = nzs[b][1][1]) : (sp[r] .= view(nzs[b][1], 1:length(r)))
+    end
+    mwb = Matrix{T}(undef, D, B)
+    for b in 1:B
+        mwb[:, b] .= fbs[b].f.mw
+    end
+    Lb = pk == P_DIAG ? Matrix{T}(undef, D, B) : Array{T}(undef, D, D, B)
+    for b in 1:B
+        pk == P_DIAG ? (Lb[:, b] .= prs[b][1]) : copyto!(view(Lb, :, :, b), prs[b][1])
+    end
+    ldl, strideL = pk == P_DIAG ? (1, D) : (D, D * D)
+    mw_post = want_posterior ? Matrix{T}(undef, D, B) : Ptr{T}(C_NULL)
+    Tp = want_posterior ? Array{T}(undef, D, D, B) : Ptr{T}(C_NULL)
+    Ap = (want_posterior && pk != P_UPPER) ? Array{T}(undef, D, D, B) : Ptr{T}(C_NULL)
+    lp = zeros(Cdouble, B)
+    info = zeros(Int32, B)
+    h = handle()
+    check(h, posterior_ragged_call(h, T, MEM_HOST, layout, B, D, offsets, Xp, layout == COLVECS ? D : max(total, 1), yp, nk, sp, 1, pk, mwb, D,
+                                   Lb, ldl, strideL, mw_post, D, Tp, D, D * D, Ap, D, D * D, lp, info))
     bad = findfirst(>(0), info)
     bad === nothing || throw(PosDefException(Int(info[bad])))
     want_posterior || return [(lp[b], nothing, nothing, nothing) for b in 1:B]
@@ -752,6 +817,26 @@ function download!(a::Array{T}, d::DeviceArray{T}) where {T}
     h = handle()
     GC.@preserve a check(h, ccall((:blr_memcpy_d2h, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Csize_t), h, a, d.ptr, sizeof(a)))
     a
+end
+
+"""
+    posterior_ragged!(mw_post, T_post, logpdf, info, X, offsets, y, s, mw, Λdiag; D, isotropic)
+
+B = length(offsets) - 1 regressors with UNEQUAL observation counts in ONE launch (D ≤ 128), everything device resident except
+`offsets` (a host `Vector{Int64}`, zero based, B + 1 non-decreasing entries): regressor b owns the columns offsets[b]+1:offsets[b+1]
+of X (D×offsets[end], ColVecs) and the same entries of y; s holds B variances (`isotropic`) or offsets[end]; mw is D×B, Λdiag the
+D diagonal entries of a prior precision shared by the batch; outputs as `posterior_batched!`.  Reference semantics per regressor:
+`:55-69` under a map over fxs of different lengths.
+"""
+function posterior_ragged!(mw_post::DeviceArray{T}, T_post::DeviceArray{T}, lp::DeviceArray{Float64}, info::DeviceArray{Int32},
+                           X::DeviceArray{T}, offsets::Vector{Int64}, y::DeviceArray{T}, s::DeviceArray{T}, mw::DeviceArray{T},
+                           Λdiag::DeviceArray{T}; D::Int, isotropic::Bool) where {T<:Elt}
+    h = handle()
+    B = length(offsets) - 1
+    check(h, posterior_ragged_call(h, T, MEM_DEVICE, COLVECS, B, D, offsets, X.ptr, D, y.ptr, isotropic ? ISOTROPIC : DIAGONALN, s.ptr,
+                                   isotropic ? 1 : 0, P_DIAG, mw.ptr, D, Λdiag.ptr, 1, 0, mw_post.ptr, D, T_post.ptr, D, D * D,
+                                   Ptr{T}(C_NULL), D, D * D, lp.ptr, info.ptr))
+    return nothing
 end
 
 """
