@@ -1521,13 +1521,16 @@ BLR_PHASE int glue_prior(char* smem, KernArgPtr<T> ap, int reg) {
     int bad = 0x7fffffff;
     if (tid < D) {
       T dv = (a.prior_kind == PRIOR_DIAGONAL) ? Lw[tid] : Lw[(int64_t)tid * a.ldl + tid];
-      if (dv > T(0)) v = log((double)dv);
+      // DIAGONAL: the diagonal of chol(diag(d)) as phase_chol rounds it (d rsqrt(d)), so that logdet Lw carries the rounding
+      // logdet A carries and the evidence of a regressor without observations is 0 to the rounding of the two double sums (1e-14),
+      // as it is for a dense prior -- not the few fp32 ulps per row that log d against 2 log(d rsqrt(d)) leaves
+      if (dv > T(0)) v = log((double)((a.prior_kind == PRIOR_DIAGONAL) ? dv * fast_rsqrt(dv) : dv));
       else bad = tid + 1;
     }
     bad = block_min_int(bad, iscr, tid);
     if (bad != 0x7fffffff) info = bad;
     v = block_allreduce(v, scr, tid);
-    logdet_Lw = (a.prior_kind == PRIOR_DIAGONAL) ? v : 2.0 * v;
+    logdet_Lw = 2.0 * v;
   }
   if (info != 0) {  // block-uniform
     if (tid == 0) {

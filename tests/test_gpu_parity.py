@@ -247,7 +247,8 @@ def test_pdmat_symmetric_closure(B):
     np.testing.assert_allclose(B.var(p_pd(Xp, s)), B.var(p_sym(Xp, s)), rtol=1.5e-8)
 
 
-@pytest.mark.parametrize("D,N", [(3, 11), (7, 200), (64, 1000), (128, 130)])
+# (33 .. 113 at N = 70: widths of 3 .. 8 blocks of 16 rows, both ends of a block, for the kernels that take D at run time)
+@pytest.mark.parametrize("D,N", [(3, 11), (7, 200), (64, 1000), (128, 130), (33, 70), (47, 70), (65, 70), (80, 70), (95, 70), (113, 70)])
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
 def test_marginals_vs_oracle(B, D, N, dtype):
     rng = _rng(8 + D)
@@ -1052,7 +1053,8 @@ def test_large_d_many_draws_wavefront_oversubscribed(B, dtype, D, S):
 
 # ---- gradient of the log marginal likelihood: closed form vs the oracle (itself pinned against
 # ---- finite differences of the literal op sequence in tests/test_oracle_pins.py) ------------------------------------
-@pytest.mark.parametrize("N,D", [(11, 3), (200, 17), (333, 64), (777, 128), (64, 128)])
+@pytest.mark.parametrize("N,D", [(11, 3), (200, 17), (333, 64), (777, 128), (64, 128), (200, 33), (200, 47), (200, 65), (200, 80), (200, 95),
+                                 (200, 113)])
 @pytest.mark.parametrize("noise", ["diagonal", "isotropic"])
 def test_logpdf_gradient_vs_oracle_f64(B, N, D, noise):
     rng = _rng(9500 + N + D)
@@ -1082,12 +1084,11 @@ def test_logpdf_gradient_vs_oracle_f64(B, N, D, noise):
             np.testing.assert_allclose(g["Lw"], gL_ref, rtol=1e-7, atol=1e-9 * np.abs(gL_ref).max())
 
 
-def test_logpdf_gradient_batched_device_f32_and_errors(B):
+def _gradient_batch_device_f32(B, rng, Bn, D, N):
+    """Bn fp32 problems resident on the device through blr_logpdf_grad_batched_f32, every output against the oracle"""
     import torch
     from blr_amd import _abi
 
-    rng = _rng(9600)
-    Bn, D, N = 5, 96, 700
     dev = torch.device("cuda:0")
     X = torch.tensor(rng.standard_normal((Bn, N, D)), dtype=torch.float32, device=dev)  # [N, D] row-major == D x N col-major
     y = torch.tensor(rng.standard_normal((Bn, N)), dtype=torch.float32, device=dev)
@@ -1117,12 +1118,22 @@ def test_logpdf_gradient_batched_device_f32_and_errors(B):
         np.testing.assert_allclose(dmw[b].cpu().numpy(), g_o["mw"], rtol=2e-3, atol=2e-4 * np.abs(g_o["mw"]).max())
         np.testing.assert_allclose(Ai[b].cpu().numpy(), g_o["Ainv"], rtol=2e-3, atol=2e-4 * np.abs(g_o["Ainv"]).max())
         np.testing.assert_allclose(mwp[b].cpu().numpy(), g_o["mw_post"], rtol=2e-3, atol=1e-4)
+
+
+def test_logpdf_gradient_batched_device_f32_and_errors(B):
+    rng = _rng(9600)
+    _gradient_batch_device_f32(B, rng, 5, 96, 700)
     # a non-SPD prior raises like cholesky() in the reference; D > 8192 is rejected with the argument position
     Xs, mws, Lws, ss = O.generate_toy_problem(rng, 20, 4, dense_noise_cov=False)
     with pytest.raises(B.PosDefException):
         B.logpdf_and_gradient(B.BayesianLinearRegressor(mws, -Lws)(Xs, ss), rng.standard_normal(20))
     with pytest.raises(B.BLRError):
         B.logpdf_and_gradient(B.BayesianLinearRegressor(np.zeros(9000), B.Diagonal(np.ones(9000)))(np.zeros((9000, 8)), 0.1), np.zeros(8))
+
+
+def test_logpdf_gradient_batched_device_f32_d72(B):
+    """D = 72: five blocks of 16 rows, a width nothing else runs in fp32; the bounds of the D = 96 batch"""
+    _gradient_batch_device_f32(B, _rng(9672), 3, 72, 200)
 
 
 @pytest.mark.parametrize("dtype,D,N", [(np.float64, 130, 77), (np.float64, 300, 500), (np.float32, 1024, 700)])

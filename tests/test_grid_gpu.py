@@ -105,7 +105,8 @@ def _assert_conditioned(p, a, t):
 
 
 # (D, N, layout, noise, prior, zero mean, nb, shared grid): every shape of the issue; layouts, noise and prior kinds, means, B in
-# {1, 5} and shared / per-regressor grids rotate over them
+# {1, 5} and shared / per-regressor grids rotate over them; 40, 72 and 90 are the widths of 3, 5 and 6 blocks of 16 rows, which
+# no other shape runs (grid_small_nb<T, NB>)
 CASES = [
     (7, 13, "col", "iso", "diag", True, 1, True),
     (7, 13, "row", "diag", "dense", False, 5, False),
@@ -113,8 +114,14 @@ CASES = [
     (3, 11, "row", "iso", "diag", True, 1, False),
     (32, 150, "col", "diag", "dense", False, 1, True),
     (32, 150, "row", "iso", "diag", False, 5, False),
+    (40, 150, "col", "iso", "dense", False, 5, True),
+    (40, 150, "row", "diag", "diag", True, 1, False),
     (64, 700, "col", "diag", "dense", True, 5, True),
     (64, 700, "row", "iso", "dense", False, 1, True),
+    (72, 700, "col", "diag", "diag", False, 1, True),
+    (72, 700, "row", "iso", "dense", False, 5, False),
+    (90, 150, "col", "iso", "diag", True, 5, False),
+    (90, 150, "row", "diag", "dense", False, 1, True),
     (100, 150, "col", "iso", "dense", False, 1, True),
     (100, 150, "row", "diag", "diag", True, 5, False),
     (128, 700, "col", "iso", "diag", False, 5, False),
@@ -206,7 +213,7 @@ def _fp32_one_setting(B, p32, a32, t32, layout, what):
 
 
 # every shape of the issue's list in fp32, the same rotation of layouts / kinds as the fp64 cases; (1024, 1100) with G = 4
-FP32_CASES = [c[:6] for c in CASES if c[6] == 1 or c[0] in (3, 100, 200)] + [(1024, 1100, "col", "diag", "dense", False)]
+FP32_CASES = [c[:6] for c in CASES if c[6] == 1 or c[0] in (3, 40, 72, 90, 100, 200)] + [(1024, 1100, "col", "diag", "dense", False)]
 
 
 @pytest.mark.parametrize("case", FP32_CASES, ids=lambda c: "-".join(map(str, c)))

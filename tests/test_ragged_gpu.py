@@ -5,14 +5,11 @@ import numpy as np
 import pytest
 
 import blr_amd as B
-from _yardsticks import _assert_fp32_within_lapack
+from _small_d_problems import COUNTS, _batch, _check_oracle, _outputs, _result, _same_bits, _single
 from blr_amd import _abi
 from oracle import blr_oracle as O
 
 pytestmark = pytest.mark.gpu
-
-# empty, one column, both sides of the 32- and 64-column stage, several stages, a tail that is no multiple of the 4-column k-step
-COUNTS = [0, 1, 31, 32, 33, 64, 200, 5, 129]
 
 
 @pytest.fixture(scope="module")
@@ -32,74 +29,6 @@ def h1():
     hd.close()
 
 
-def _batch(D, dtype, xkind, noise, prior, shared_prior, counts=COUNTS, seed=0, pad_value=np.nan):
-    """One packed batch.  xkind: "col16" (ColVecs, ldx = D rounded up to 16 bytes), "colpad" (16 bytes more), "colodd" (ColVecs, odd ldx > D), "row"
-    (RowVecs, ldx = offsets[B] + 3).  noise: "iso" (one variance per regressor), "iso0" (one for all), "diag".  prior: "diag",
-    "dense", "factor" (entries that are multiples of 1/8: U'U is exact in fp32 too).  Padding elements of X hold pad_value."""
-    rng = np.random.Generator(np.random.PCG64(1000 * D + seed))
-    nb = len(counts)
-    offsets = np.concatenate(([0], np.cumsum(counts))).astype(np.int64)
-    total = int(offsets[-1])
-    Xd = rng.standard_normal((D, total)).astype(dtype)  # the data, D x total
-    if xkind == "row":
-        layout, ldx = _abi.LAYOUT_ROWVECS, total + 3
-        Xp = np.full((ldx, D), pad_value, dtype=dtype, order="F")
-        Xp[:total, :] = Xd.T
-    else:
-        layout = _abi.LAYOUT_COLVECS
-        per16 = 16 // np.dtype(dtype).itemsize
-        ldx = (D + 1) | 1 if xkind == "colodd" else -(-D // per16) * per16 + (per16 if xkind == "colpad" else 0)
-        Xp = np.full((ldx, total), pad_value, dtype=dtype, order="F")
-        Xp[:D, :] = Xd
-    w = rng.standard_normal(D) / np.sqrt(D)
-    if noise == "diag":
-        s = np.exp(0.3 * rng.standard_normal(total)).astype(dtype)
-        strides = 0
-        s_of = lambda b: s[offsets[b]:offsets[b + 1]]  # noqa: E731
-    elif noise == "iso":
-        s = np.exp(0.3 * rng.standard_normal(nb)).astype(dtype)
-        strides = 1
-        s_of = lambda b: s[b]  # noqa: E731
-    else:
-        s = np.array([0.7], dtype=dtype)
-        strides = 0
-        s_of = lambda b: s[0]  # noqa: E731
-    y = (Xd.astype(float).T @ w + 0.8 * rng.standard_normal(total)).astype(dtype)
-    npri = 1 if shared_prior else nb
-    mw = (0.2 * rng.standard_normal((npri, D))).astype(dtype)
-    if prior == "diag":
-        Lw = np.exp(0.3 * rng.standard_normal((npri, D))).astype(dtype)
-        ldl, dense_of = 1, lambda p: Lw[p]  # noqa: E731
-    else:
-        Lw = np.zeros((npri, D * D), dtype=dtype)
-        mats = []
-        for p in range(npri):
-            if prior == "factor":
-                U = np.triu(rng.integers(-1, 2, size=(D, D)) / 8.0, 1) + np.diag(1.0 + rng.integers(0, 5, size=D) / 8.0)
-                Lw[p] = U.reshape(-1, order="F")
-                mats.append((U.T @ U).astype(dtype))
-            else:
-                Bm = rng.standard_normal((D, D)) / np.sqrt(D)
-                M = (Bm @ Bm.T + np.eye(D)).astype(dtype)
-                M = np.triu(M) + np.triu(M, 1).T
-                Lw[p] = M.reshape(-1, order="F")
-                mats.append(M)
-        ldl, dense_of = D, lambda p: mats[p]  # noqa: E731
-    kind = {"diag": _abi.PRIOR_DIAGONAL, "dense": _abi.PRIOR_DENSE, "factor": _abi.PRIOR_UPPER_FACTOR}[prior]
-    return dict(D=D, dtype=dtype, nb=nb, offsets=offsets, layout=layout, ldx=ldx, X=Xp, Xd=Xd, y=y, s=s, strides=strides, s_of=s_of,
-                noise_kind=_abi.NOISE_DIAGONAL if noise == "diag" else _abi.NOISE_ISOTROPIC, prior_kind=kind, mw=mw, Lw=Lw, ldl=ldl,
-                stridemw=0 if shared_prior else D, strideLw=0 if shared_prior else Lw.shape[1], dense_of=dense_of,
-                pri=(lambda b: 0) if shared_prior else (lambda b: b))
-
-
-def _outputs(nb, D, dtype, gaps=False, fill=np.nan):
-    ldt = D + 2 if gaps else D
-    st_m = D + 3 if gaps else D
-    st_T = ldt * D + (5 if gaps else 0)
-    return dict(mw_post=np.full(nb * st_m, fill, dtype=dtype), stride_mwpost=st_m, T=np.full(nb * st_T, fill, dtype=dtype), ldt=ldt,
-                strideT=st_T, A=np.full(nb * st_T, fill, dtype=dtype), lp=np.full(nb, 123.0), info=np.full(nb, -7, dtype=np.int32))
-
-
 def _ragged(hd, q, o, memspace=_abi.MEM_HOST, arrays=None):
     a = arrays or dict(X=q["X"], y=q["y"], s=q["s"], mw=q["mw"], Lw=q["Lw"], mw_post=o["mw_post"], T=o["T"], A=o["A"], lp=o["lp"],
                        info=o["info"])
@@ -109,66 +38,13 @@ def _ragged(hd, q, o, memspace=_abi.MEM_HOST, arrays=None):
                                a["info"])
 
 
-def _mat(buf, b, D, ld, stride):
-    return buf[b * stride + np.arange(D)[None, :] * ld + np.arange(D)[:, None]]
-
-
-def _result(q, o, b):
-    D = q["D"]
-    return (o["mw_post"][b * o["stride_mwpost"]:b * o["stride_mwpost"] + D].copy(), _mat(o["T"], b, D, o["ldt"], o["strideT"]),
-            _mat(o["A"], b, D, o["ldt"], o["strideT"]), float(o["lp"][b]), int(o["info"][b]))
-
-
-def _single(hd, q, b):
-    """regressor b alone: blr_posterior_batched_* with B = 1 on its slice of the packed arrays (same ldx, same alignment class)"""
-    D, dtype = q["D"], q["dtype"]
-    o0, o1 = int(q["offsets"][b]), int(q["offsets"][b + 1])
-    Xs = q["X"][o0:, :] if q["layout"] == _abi.LAYOUT_ROWVECS else q["X"][:, o0:]
-    s = q["s"][o0:] if q["noise_kind"] == _abi.NOISE_DIAGONAL else q["s"][b * q["strides"]:]
-    if s.size == 0:
-        s = np.ones(1, dtype=dtype)
-    if Xs.size == 0:
-        Xs = np.zeros((1, 1), dtype=dtype)
-    p = q["pri"](b)
-    mw_post, T, A = np.full(D, np.nan, dtype=dtype), np.full((D, D), np.nan, dtype=dtype, order="F"), np.full((D, D), np.nan, dtype=dtype, order="F")
-    lp, info = np.zeros(1), np.zeros(1, dtype=np.int32)
-    hd.posterior_batched(dtype, _abi.MEM_HOST, q["layout"], 1, D, o1 - o0, Xs, q["ldx"], 0, q["y"][o0:] if o1 > o0 else np.zeros(1, dtype=dtype),
-                         0, q["noise_kind"], s, 0, q["prior_kind"], q["mw"][p], 0, q["Lw"][p], q["ldl"], 0, mw_post, D, T, D, D * D, A, D,
-                         D * D, lp, info)
-    return mw_post, T, A, float(lp[0]), int(info[0])
-
-
-def _same_bits(r1, r2, what=""):
-    for x, y_, name in zip(r1, r2, ("mw'", "T", "Lw'", "logpdf", "info")):
-        assert np.array_equal(np.asarray(x), np.asarray(y_), equal_nan=True), (what, name)
-
-
-def _check_oracle(q, b, res):
-    mw_p, T, A, lp, info = res
-    assert info == 0
-    o0, o1 = int(q["offsets"][b]), int(q["offsets"][b + 1])
-    p = q["pri"](b)
-    Xb, yb, sb, Lw = q["Xd"][:, o0:o1], q["y"][o0:o1], q["s_of"](b), q["dense_of"](p)
-    if q["dtype"] == np.float32:
-        _assert_fp32_within_lapack(q["mw"][p], Lw, np.asfortranarray(Xb), np.asarray(sb, dtype=np.float32), yb, mw_p, A, lp, got_T=T,
-                                   what=f"regressor {b}")
-        return
-    f64 = lambda a: np.asarray(a, dtype=np.float64)  # noqa: E731
-    mw_o, T_o, A_o = O.posterior_literal(f64(q["mw"][p]), f64(Lw), f64(Xb), f64(sb), f64(yb))
-    lp_o = O.logpdf_literal(f64(q["mw"][p]), f64(Lw), f64(Xb), f64(sb), f64(yb))
-    assert abs(lp - lp_o) <= 1e-10 * max(1.0, abs(lp_o)), (b, lp, lp_o)
-    np.testing.assert_allclose(mw_p, mw_o, rtol=1e-9, atol=1e-11, err_msg=f"mw' of regressor {b}")
-    np.testing.assert_allclose(T, T_o, rtol=1e-9, atol=1e-11, err_msg=f"T of regressor {b}")
-    np.testing.assert_allclose(A, A_o, rtol=1e-9, atol=1e-11, err_msg=f"Lw' of regressor {b}")
-
-
 # (data layout, noise, prior, shared prior): every value of every axis, five sets per (D, dtype)
 VARIANTS = [("col16", "iso", "diag", False), ("colodd", "diag", "dense", True), ("row", "iso0", "factor", False),
             ("col16", "diag", "factor", True), ("row", "diag", "dense", False)]
 
 
 @pytest.mark.parametrize("dtype", [np.float64, np.float32], ids=["f64", "f32"])
-@pytest.mark.parametrize("D", [5, 16, 40, 128])
+@pytest.mark.parametrize("D", [5, 16, 40, 56, 72, 90, 100, 128])
 @pytest.mark.parametrize("variant", VARIANTS, ids=["-".join(map(str, v)) for v in VARIANTS])
 def test_every_regressor_matches_the_oracle_and_the_single_call_bit_for_bit(h, h1, D, dtype, variant):
     q = _batch(D, dtype, *variant)
