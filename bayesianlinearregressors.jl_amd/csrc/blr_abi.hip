@@ -33,6 +33,7 @@
 #include "blr_grid.hpp"
 #include "blr_ragged.hpp"
 #include "blr_host.hpp"
+#include "blr_large_plan.hpp"
 
 using namespace blr;
 
@@ -81,20 +82,6 @@ int rccl_fail(blr_handle* h, ncclResult_t r, const char* what) {
 constexpr int kMaxSmallD = 128;
 constexpr int kMaxLargeD = 8192;
 
-// Dynamic LDS of planes_kernel: the chunk's r, sqrt(w) and mu (16 floats per k-block each), then for a basis its raw inputs --
-// the whole chunk's, padded to 8 input dimensions (xs_chunk), or one k-block's [Din][16].
-constexpr size_t planes_pass_lds(bool rff, bool xs_chunk, int din) {
-  return (size_t)(3 * 16 * kPlanesChunkKb + (rff ? (xs_chunk ? 8 * 16 * kPlanesChunkKb : din * 16) : 0)) * sizeof(float);
-}
-// blr_posterior_rff_f32 evaluates the basis inside the planes pass up to this input dimension: the largest whose pass fits in
-// 64 KiB of LDS.  A conservative choice, not the hardware's limit: a gfx950 workgroup may use up to 160 KiB (D_in 2368), and the
-// pass was measured to launch beyond 64 KiB without a raised attribute; 64 KiB is what HIP grants by default.
-// A larger D_in materialises the features (rff_features_kernel) and runs the planes Gram on them -- so do D_in 833 .. 2368,
-// which used to run fused (D_in >= 2369 failed to launch).
-constexpr int kRffFusedMaxDin = 832;
-static_assert(planes_pass_lds(true, true, 8) <= 65536 && planes_pass_lds(true, false, kRffFusedMaxDin) <= 65536 &&
-                  planes_pass_lds(true, false, kRffFusedMaxDin + 1) > 65536,
-              "kRffFusedMaxDin: the largest D_in whose planes pass fits in 64 KiB of LDS (the chosen cap)");
 
 int set_lds_once(blr_handle* h, const void* kern, size_t bytes) {
   auto it = h->lds_limit.find(kern);
@@ -389,9 +376,6 @@ int launch_panel(blr_handle* h, T* M, int64_t ld, int p, int nrows_total, int nb
   return 0;
 }
 
-// ... as long as their workspaces fit this many bytes (per handle; option CHAIN_WS_MB lowers the bound, blr_release_workspace
-// hands the memory back: the scratch buffers of a handle only ever grow otherwise)
-constexpr size_t kChainWorkspace = (size_t)8 << 30;
 constexpr int kChainBatchMax = kChainBatchMaxWords;  // factorisations that step through their panels in shared launches (one arrival word each per bank)
 
 // Blocked Cholesky of G independent matrices M + g * batch_stride (status words info_dev + g * info_stride), panel by panel,
@@ -429,241 +413,314 @@ int chol_large(blr_handle* h, T* M, int64_t ld, int DP, int nrows_total, int32_t
   return 0;
 }
 
-// Multi-round Gram launch of ONE regressor (c5: 136 tiles on 512 slots): with one split factor the launch takes whole rounds of
-// the off-diagonal workgroup length (952 workgroups = 2 rounds at 93 % fill).  Three kinds of work items, dispatched longest
-// first -- diagonal tiles with `sd` column ranges, `nlong` strictly lower tiles with so - 1 ranges, the others with so -- let
-// a second round of SHORTER workgroups follow a first round of longer ones (c5: 64 x 3205 + 448 x 2597, then 448 x 2304 column
-// units instead of 2 x 2597 everywhere).  The plan is the makespan of list scheduling on `slots` slots over a small neighbourhood
-// of the one-factor choice s0 (10 ms of host time, once per shape and handle); `unit` = cost of a diagonal column / off-diagonal.
-struct GramPlan { int so, sd, nlong; double makespan; };
-inline double gram_makespan(int n_off, int NC, int so, int sd, int nlong, int N, int nsc, int slots, double unit, bool interleaved) {
-  auto cols = [&](int sp) { return (double)(((N + sp - 1) / sp + nsc - 1) / nsc * nsc); };
-  std::priority_queue<double, std::vector<double>, std::greater<double>> free_at;
-  for (int i = 0; i < slots; ++i) free_at.push(0.0);
-  double end = 0.0;
-  auto run = [&](double cost) { double t = free_at.top() + cost; free_at.pop(); free_at.push(t); end = std::max(end, t); };
-  if (interleaved) {  // one factor: item w -> tile w % ntiles, diagonal tiles spread over the launch
-    const int ntiles = n_off + NC;
-    for (int w = 0; w < ntiles * so; ++w) {
-      const int t = w % ntiles;
-      int ii = 0;
-      while ((ii + 1) * (ii + 2) / 2 <= t) ++ii;
-      const bool diag = t - ii * (ii + 1) / 2 == ii;
-      run((diag ? unit : 1.0) * cols(so) + 256.0);
-    }
-    return end;
-  }
-  for (int i = 0; i < NC * sd; ++i) run(unit * cols(sd) + 256.0);
-  for (int i = 0; i < nlong * (so - 1); ++i) run(cols(so - 1) + 256.0);
-  for (int i = 0; i < (n_off - nlong) * so; ++i) run(cols(so) + 256.0);
-  return end;
+// ---- the update of a group: plan (blr_large_plan.hpp: route, splits, workspace layout, group size -- no device needed), reserve,
+// bind the workspace, run the stages.  What every stage sees: the call, the plan and the typed workspace pointers.  Every launch
+// covers the whole group: regressor g from blockIdx.y / .z, its caller-side arrays by the batch strides and its workspace `wsb`
+// bytes after its predecessor's (the pointers here are regressor reg0's).
+template <typename T>
+struct LargeRun {
+  blr_handle* h;
+  const PosteriorArgs<T>& a;
+  const LargePlan& p;
+  blr_handle::MultiSrc* ms;
+  int64_t reg0;
+  int G;
+  const T *X, *y, *s, *mw, *Lw;
+  T *Abar, *W, *Gpart, *mu, *rvec, *wvec, *Tfull;  // (mu: multi-output only; wvec: diagonal noise only)
+  unsigned short* Xp;
+  double *bpart, *qsp, *qpart, *lpart;
+  unsigned* rowmax;  // behind the b partials: DPA words, then the planes pass's redo flag
+  unsigned* scratch;  // LargeScratch
+  double *logdetLw, *spare_logdet;
+  int32_t *info_prior, *info_chol, *spare_info;
+  unsigned* info_noise;
+  int64_t wsb, wse;  // stride between the regressors' workspaces in bytes and in elements (a multiple of 256 bytes)
+  int info_stride;   // ... and in status words
+};
+template <typename T>
+LargeRun<T> bind_large(blr_handle* h, const PosteriorArgs<T>& a, const LargePlan& p, int64_t reg0, int G) {
+  LargeRun<T> u{h, a, p, h->multi_src, reg0, G};
+  u.X = a.X + reg0 * a.strideX; u.y = a.y + reg0 * a.stridey; u.s = a.s + reg0 * a.strides;
+  u.mw = a.mw + reg0 * a.stridemw; u.Lw = a.Lw + reg0 * a.strideLw;
+  char* const ws = h->ws.p;
+  const LargeLayout& o = p.o;
+  u.Abar = reinterpret_cast<T*>(ws + o.abar);
+  u.W = reinterpret_cast<T*>(ws + o.w);
+  u.Xp = reinterpret_cast<unsigned short*>(ws + o.xp);
+  u.Gpart = reinterpret_cast<T*>(ws + o.gp);
+  u.bpart = reinterpret_cast<double*>(ws + o.bp);
+  u.rowmax = reinterpret_cast<unsigned*>(u.bpart + (int64_t)p.bslots * p.NCA * kPB);
+  u.mu = u.ms ? reinterpret_cast<T*>(ws + o.mu) : nullptr;
+  u.qsp = u.ms ? reinterpret_cast<double*>(ws + o.qs) : nullptr;
+  u.rvec = reinterpret_cast<T*>(ws + o.r);
+  u.wvec = a.noise_kind == NOISE_DIAGONAL ? reinterpret_cast<T*>(ws + o.wv) : nullptr;
+  u.qpart = reinterpret_cast<double*>(ws + o.q);
+  u.lpart = reinterpret_cast<double*>(ws + o.l);
+  u.Tfull = reinterpret_cast<T*>(ws + o.m);
+  char* const sc = ws + o.sc;
+  u.scratch = reinterpret_cast<unsigned*>(sc);
+  u.logdetLw = reinterpret_cast<double*>(sc + LargeScratch::logdet);
+  u.info_prior = reinterpret_cast<int32_t*>(sc + LargeScratch::info_prior);
+  u.info_chol = reinterpret_cast<int32_t*>(sc + LargeScratch::info_chol);
+  u.info_noise = reinterpret_cast<unsigned*>(sc + LargeScratch::info_noise);
+  u.spare_info = reinterpret_cast<int32_t*>(sc + LargeScratch::spare_info);
+  u.spare_logdet = reinterpret_cast<double*>(sc + LargeScratch::spare_logdet);
+  u.wsb = (int64_t)o.per;
+  u.wse = (int64_t)(o.per / sizeof(T));
+  u.info_stride = (int)(o.per / sizeof(int32_t));
+  return u;
 }
-inline GramPlan plan_gram_rounds(int n_off, int NC, int s0, int N, int nsc, int slots, int max_split, double unit) {
-  const double base = gram_makespan(n_off, NC, s0, s0, 0, N, nsc, slots, unit, true);
-  // Candidates are the family that measured well on c5 (tools/scan_splits.sh): one or two ranges more than the one-factor choice,
-  // diagonal tiles with as many ranges as the short tiles or half as many, the long tiles in sixteenths of the triangle.
-  // (Measured against the model at D = 2048, N = 16384, ms per update: 7 | 7 -> 1.045; 8 | 8, 64 long -> 0.999; 8 | 4, 64 ->
-  // 0.997; 8 | 6, 56 -> 0.999; 8 | 8, 56 (1032 workgroups: a third round) -> 1.065; 8 | 7, 64 -> 1.076 against a modelled tie.)
-  GramPlan best{s0, 0, 0, base};
-  for (int so = std::max(2, s0); so <= std::min(max_split, s0 + 2); ++so)
-    for (int sd : {so, so / 2}) {
-      if (sd < 1) continue;
-      // the run of nlong values that tie for the best makespan of this (so, sd): take its middle (both ends sit next to a cliff)
-      double m_best = 1e300;
-      int first = -1, last = -1;
-      for (int f = 0; f <= 16; ++f) {
-        const double m = gram_makespan(n_off, NC, so, sd, n_off * f / 16, N, nsc, slots, unit, false);
-        if (m < m_best * 0.995) { m_best = m; first = last = f; }
-        else if (m <= m_best * 1.005 && f == last + 1) last = f;
-      }
-      if (m_best < best.makespan * 0.995) best = GramPlan{so, sd, n_off * ((first + last) / 2) / 16, m_best};
+
+// ---- prior: SPD check + logdet (reference :78).  One launch clears the scratch words, sets the noise flag and zeroes the
+// b partials; for a diagonal / factor prior it also checks the diagonal and seeds info_chol with the prior's status (a failed
+// prior short-circuits the factorisation), for a dense one the blocked factorisation of W does that.
+template <typename T>
+int large_prior(const LargeRun<T>& u) {
+  blr_handle* const h = u.h;
+  const PosteriorArgs<T>& a = u.a;
+  const LargePlan& p = u.p;
+  const bool dense = a.prior_kind == PRIOR_DENSE;
+  ScratchInit init;
+  init.words16 = u.scratch;
+  init.ones = u.info_noise;
+  init.zeros = u.bpart;
+  init.nzeros = (long long)p.bslots * p.NCA * kPB + p.DPA / 2 + 1;  // (+ the row maxima behind the b partials: DP words, + the redo flag)
+  init.info_copy = dense ? nullptr : u.info_chol;
+  const int gridp = (int)std::min<long long>(64, 1 + init.nzeros / (8 * kThreads));
+  // (dense: the kernel's own look at Lw's diagonal is not the answer -- status and logdet go to spare scratch words)
+  hipLaunchKernelGGL(prior_diag_kernel<T>, dim3(gridp, u.G), dim3(kThreads), 0, h->stream, u.Lw, a.ldl, a.prior_kind, a.D,
+                     dense ? u.spare_logdet : u.logdetLw, dense ? u.spare_info : u.info_prior, init, a.strideLw, u.wsb);
+  if (dense) {
+    hipLaunchKernelGGL(prior_copy_kernel<T>, dim3(1024, u.G), dim3(kThreads), 0, h->stream, u.Lw, a.ldl, a.D, p.DP, u.W, (int64_t)p.DP, a.strideLw, u.wse);
+    const int rc = chol_large<T>(h, u.W, p.DP, p.DP, p.DP, u.info_prior, u.G, u.wse, u.info_stride);
+    if (rc) return rc;
+    hipLaunchKernelGGL(logdet_kernel<T>, dim3(u.G), dim3(kThreads), 0, h->stream, (const T*)u.W, (int64_t)p.DP, a.D, u.logdetLw, u.wsb,
+                       (const int32_t*)u.info_prior, u.info_chol);
+  }
+  return 0;
+}
+
+// ---- column statistics (reference :82-84)
+template <typename T>
+void large_colstats(const LargeRun<T>& u) {
+  const PosteriorArgs<T>& a = u.a;
+  ColstatsArgs<T> c{};
+  c.X = u.X; c.ldx = a.ldx; c.y = u.y; c.s = u.s; c.mw = u.mw; c.r = u.rvec; c.w = u.wvec; c.qpart = u.qpart; c.lpart = u.lpart;
+  c.noise_info = u.info_noise;
+  c.layout = a.layout; c.noise_kind = a.noise_kind; c.D = a.D; c.N = a.N;
+  c.grp_X = a.strideX; c.grp_y = a.stridey; c.grp_s = a.strides; c.grp_mw = a.stridemw; c.grp_ws = u.wsb;
+  c.w_sqrt = u.p.planes ? 1 : 0;
+  c.mu = u.mu;
+  if (u.p.rff) {
+    c.X = nullptr;
+    c.rff_Xin = a.rff_Xin; c.rff_ldxin = a.rff_ldxin; c.rff_Omega = a.rff_Omega; c.rff_ldo = a.rff_ldo; c.rff_phase = a.rff_phase;
+    c.rff_scale = a.rff_scale; c.rff_Din = a.rff_Din;
+  }
+  size_t lds = (((size_t)a.D * sizeof(T) + 15) & ~(size_t)15) + 64;
+  hipLaunchKernelGGL(colstats_kernel<T>, dim3(kLargeParts, u.G), dim3(kThreads), lds, u.h->stream, c);
+}
+
+// what every launch of gram_tile_kernel in the update shares: the whole lower triangle of X diag(w) X' (+ the b partials)
+template <typename T>
+GramTileArgs<T> large_gram_args(const LargeRun<T>& u) {
+  const PosteriorArgs<T>& a = u.a;
+  GramTileArgs<T> g{};
+  g.X = u.X; g.ldx = a.ldx; g.layout = a.layout;
+  g.use_dma = u.p.x_ring ? (u.h->opt.no_gram_ring ? 2 : 1) : 0;  // (NO_GRAM_RING: A/B experiments only)
+  g.bf3 = u.p.bf3 ? 1 : 0;  // (f32 + the LDS-DMA ring only: the bf16 x 3 code lives in the ring loop)
+  g.s = u.s; g.noise_kind = a.noise_kind; g.r = u.rvec; g.wpre = u.wvec;
+  g.D = a.D; g.n_begin = 0; g.n_end = a.N; g.nblocks = u.p.NC; g.bpart = u.bpart; g.mode_out = 0;
+  g.grp_X = a.strideX; g.grp_s = a.strides; g.grp_ws = u.wsb;
+  g.tile_i0 = 0; g.tile_j0 = 0; g.tri = 1;
+  return g;
+}
+// The prior factor as pseudo-observations: one more partial per tile behind the nsplit data partials, from the f32 tile kernel on
+// either Gram route.  (r == NULL: the launch writes no b partial, so bpart only has to be a valid pointer; the plain instantiation
+// is chosen by its template argument, GramTileArgs::bf3 is read by nobody.)
+template <typename T>
+void large_prior_pseudo_split(const LargeRun<T>& u) {
+  const LargePlan& p = u.p;
+  GramTileArgs<T> g = large_gram_args(u);
+  g.nsplit = 1; g.ntiles = p.ntiles; g.nsplit_diag = 0; g.nlong = 0;
+  g.xcd_swizzle = 0;
+  g.X = u.Lw; g.ldx = u.a.ldl; g.layout = 2; g.use_dma = 0; g.bf3 = 0; g.s = nullptr; g.r = nullptr; g.wpre = nullptr;
+  g.grp_X = u.a.strideLw; g.grp_s = 0;
+  g.n_begin = 0; g.n_end = u.a.D;
+  g.Gpart = u.Gpart + (int64_t)p.nsplit * p.ntiles * kPB * kPB;
+  hipLaunchKernelGGL(gram_tile_kernel<T>, dim3(p.ntiles, u.G), dim3(kThreads), LargeCfg<T>::LDS_BYTES, u.h->stream, g);
+}
+
+// ---- Gram (reference :86) by tiles: split-K partial tiles, then the prior factor as pseudo-observations
+template <typename T>
+void large_gram_tiles(const LargeRun<T>& u) {
+  using LC = LargeCfg<T>;
+  const LargePlan& p = u.p;
+  GramTileArgs<T> g = large_gram_args(u);
+  g.nsplit = p.nsplit; g.ntiles = p.ntiles; g.Gpart = u.Gpart;
+  g.nsplit_diag = p.nsplit_diag; g.nlong = p.nlong;
+  g.xcd_swizzle = (p.nsplit > 1 && !u.h->opt.no_xcd_swizzle) ? (p.nlong == 0 ? 1 : 2) : 0;  // (three kinds of work items: remapped inside a kind, the dispatch order of the kinds IS the plan)
+  const int nwg = p.nsplit_diag ? (p.ntiles - p.NC) * p.nsplit - p.nlong + p.NC * p.nsplit_diag : p.ntiles * p.nsplit;
+  if constexpr (sizeof(T) == 4) {
+    if (g.bf3) hipLaunchKernelGGL((gram_tile_kernel<T, true>), dim3(nwg, u.G), dim3(kThreads), LC::LDS_BYTES, u.h->stream, g);
+    else hipLaunchKernelGGL(gram_tile_kernel<T>, dim3(nwg, u.G), dim3(kThreads), LC::LDS_BYTES, u.h->stream, g);
+  } else {
+    hipLaunchKernelGGL(gram_tile_kernel<T>, dim3(nwg, u.G), dim3(kThreads), LC::LDS_BYTES, u.h->stream, g);
+  }
+  if (u.a.prior_kind == PRIOR_UPPER_FACTOR) large_prior_pseudo_split(u);
+}
+
+// ---- Gram by planes (fp32): the rows' largest entries, the operand planes (with the b partials), the Gram launch on them, then the
+// prior factor as pseudo-observations
+inline int large_gram_planes(const LargeRun<float>& u) {
+  blr_handle* const h = u.h;
+  const PosteriorArgs<float>& a = u.a;
+  const LargePlan& p = u.p;
+  const int G = u.G, NC = p.NC, NCA = p.NCA, nbchunks = p.nbchunks;
+  const bool rff = p.rff;
+  int rc;
+  if ((rc = set_lds_once(h, reinterpret_cast<const void*>(gram_planes_kernel<2>), (size_t)PlanesCfg<2>::LDS))) return rc;
+  if ((rc = set_lds_once(h, reinterpret_cast<const void*>(gram_planes_kernel<3>), (size_t)PlanesCfg<3>::LDS))) return rc;
+  PlanesArgs pa{};
+  pa.X = rff ? nullptr : u.X; pa.ldx = a.ldx;
+  pa.Xin = a.rff_Xin; pa.ldxin = a.rff_ldxin; pa.Omega = a.rff_Omega; pa.ldo = a.rff_ldo; pa.phase = a.rff_phase; pa.scale = a.rff_scale; pa.Din = a.rff_Din;
+  pa.wsq = u.wvec; pa.r = u.rvec; pa.Xp = u.Xp; pa.bpart = u.bpart; pa.rowmax = u.rowmax;
+  pa.D = a.D; pa.N = a.N; pa.NC = NCA; pa.NKB = p.NKB; pa.nchunks = nbchunks;
+  pa.grp_X = a.strideX; pa.grp_ws = u.wsb;
+  if (u.ms) {
+    pa.Y = static_cast<const float*>(u.ms->Y); pa.ldY = u.ms->ldY; pa.S = u.ms->S;
+    pa.mu = u.mu; pa.qsp = u.qsp;
+  }
+  // a basis of up to 8 input dimensions: the raw inputs of a workgroup's whole column chunk are staged once (blr_planes.hpp, xs_chunk)
+  pa.xs_chunk = (rff && a.rff_Din <= 8) ? 1 : 0;
+  const size_t plds = planes_pass_lds(rff, pa.xs_chunk != 0, a.rff_Din);
+  if (p.NP == 2) {  // the rows' power-of-two scales need (a bound of) the rows' largest entries first
+    if (rff) {  // a basis: its bound
+      hipLaunchKernelGGL(rowmax_kernel<true>, dim3(nbchunks, 1, G), dim3(kThreads), 0, h->stream, pa);
+      hipLaunchKernelGGL((planes_kernel<2, true>), dim3(nbchunks, NC, G), dim3(kThreads), plds, h->stream, pa);
+    } else if (h->opt.no_spec_rowmax) {  // the exact maxima: one more pass over X
+      hipLaunchKernelGGL(rowmax_kernel<false>, dim3(nbchunks, NCA, G), dim3(kThreads), 0, h->stream, pa);
+      hipLaunchKernelGGL((planes_kernel<2, false>), dim3(nbchunks, NCA, G), dim3(kThreads), plds, h->stream, pa);
+    } else {
+      // sampled maxima with head-room, the planes pass checks that every entry fits; the exact pass + the planes again only if one
+      // did not (two launches that return at once otherwise: ~ 5 us against the 58 us of the exact pass at config 3)
+      if ((rc = ensure_stats(h))) return rc;
+      pa.redo = u.rowmax + p.DPA;
+      pa.redo_total = h->stats_dev + 1;
+      pa.sample_kb = 2;
+      hipLaunchKernelGGL(rowmax_kernel<false>, dim3(nbchunks, NCA, G), dim3(kThreads), 0, h->stream, pa);
+      hipLaunchKernelGGL((planes_kernel<2, false>), dim3(nbchunks, NCA, G), dim3(kThreads), plds, h->stream, pa);
+      pa.sample_kb = 0;
+      pa.redo_pass = 1;
+      hipLaunchKernelGGL(rowmax_kernel<false>, dim3(nbchunks, NCA, G), dim3(kThreads), 0, h->stream, pa);
+      hipLaunchKernelGGL((planes_kernel<2, false>), dim3(nbchunks, NCA, G), dim3(kThreads), plds, h->stream, pa);
     }
-  if (best.sd == 0 || best.makespan > 0.96 * base) return GramPlan{s0, 0, 0, base};  // not worth leaving the one-factor launch
-  return best;
+  } else {
+    if (rff) hipLaunchKernelGGL((planes_kernel<3, true>), dim3(nbchunks, NC, G), dim3(kThreads), plds, h->stream, pa);
+    else hipLaunchKernelGGL((planes_kernel<3, false>), dim3(nbchunks, NC, G), dim3(kThreads), plds, h->stream, pa);
+  }
+  HIP_TRY(h, hipGetLastError());  // (a failed planes launch leaves the last call's planes in the workspace: never a posterior from them)
+  GramPlanesArgs ga{};
+  ga.Xp = u.Xp; ga.NC = NCA; ga.NKB = p.NKB; ga.Gpart = u.Gpart; ga.ntiles = p.ntiles_g; ga.nsplit = p.nsplit;
+  ga.s_iso = a.noise_kind == NOISE_DIAGONAL ? nullptr : u.s;
+  ga.rowmax = u.rowmax;
+  ga.xcd_swizzle = (p.nsplit > 1 && !h->opt.no_xcd_swizzle) ? 1 : 0;
+  ga.grp_ws = u.wsb; ga.grp_s = a.strides;
+  const dim3 grid(p.ntiles_g * p.nsplit, G);
+  if (p.planes4) {
+    if ((rc = set_lds_once(h, reinterpret_cast<const void*>(gram_planes4_kernel), (size_t)Planes4Cfg::LDS))) return rc;
+    hipLaunchKernelGGL(gram_planes4_kernel, grid, dim3(kThreads), (size_t)Planes4Cfg::LDS, h->stream, ga);
+  } else if (p.NP == 2) hipLaunchKernelGGL(gram_planes_kernel<2>, grid, dim3(kPlanesThreads), (size_t)PlanesCfg<2>::LDS, h->stream, ga);
+  else hipLaunchKernelGGL(gram_planes_kernel<3>, grid, dim3(kPlanesThreads), (size_t)PlanesCfg<3>::LDS, h->stream, ga);
+  if (a.prior_kind == PRIOR_UPPER_FACTOR) large_prior_pseudo_split(u);  // (one more partial per tile, from the f32 kernel)
+  return 0;
+}
+
+// ---- reduction of the partial tiles and b partials into Abar = [A; b'] (+ the prior; Lw_post for the caller)
+template <typename T>
+void large_reduce(const LargeRun<T>& u) {
+  const PosteriorArgs<T>& a = u.a;
+  const LargePlan& p = u.p;
+  const int pf = a.prior_kind == PRIOR_UPPER_FACTOR ? 1 : 0;
+  ReduceArgs<T> r{};
+  r.bpart = u.bpart;
+  r.Lw = u.Lw; r.ldl = a.ldl; r.prior_kind = a.prior_kind; r.D = a.D; r.DP = p.DP; r.Abar = u.Abar; r.lda = p.lda;
+  r.Lw_post = a.Lw_post ? a.Lw_post + u.reg0 * a.strideLp : nullptr; r.ldlp = a.ldlp;
+  r.grp_Lw = a.strideLw; r.grp_Lp = a.strideLp; r.grp_ws = u.wsb;
+  // (planes path: the planes pass's b partials, one per column chunk, at stride NCA; multi-output: the residuals' row block is block NC)
+  r.nsplit_b = p.nbchunks;
+  r.nblocks = p.NCA;
+  r.multi_block = u.ms ? p.NC : 0;
+  r.Gpart = u.Gpart; r.nsplit_total = p.nsplit + pf; r.ntiles = p.ntiles_g;
+  r.nsplit_diag = p.nsplit_diag; r.pseudo_split = pf; r.nlong = p.nlong;
+  hipLaunchKernelGGL(gram_reduce_kernel<T>, dim3(p.ntiles_g + p.NC, 16, u.G), dim3(kThreads), 0, u.h->stream, r);
+}
+
+// ---- blocked Cholesky of Abar (rows DP.. = rhs) -> L, u  (reference :86, :57)
+// (only the first 64 of the 128 padding rows ride along: row DP is b', the others are zero and nobody reads them back --
+// half the right-hand-side sub-tiles of every trailing update, and c5's first trailing updates fit one round)
+// (multi-output: rows DP + s are b_s' for the columns s < S of Y; more than 64 of them take all 128 rows along)
+template <typename T>
+int large_factor(const LargeRun<T>& u) {
+  const LargePlan& p = u.p;
+  blr_handle::MultiSrc* const ms = u.ms;
+  const int rc = chol_large<T>(u.h, u.Abar, p.lda, p.DP, p.DP + ((ms && ms->S > TrailCfg<T>::SB) ? kPB : TrailCfg<T>::SB), u.info_chol, u.G,
+                               u.wse, u.info_stride);
+  if (rc) return rc;
+  if (ms) {
+    ms->Abar = u.Abar; ms->lda = p.lda; ms->Tfull = u.Tfull; ms->DP = p.DP;
+    ms->qsp = u.qsp; ms->nq = p.nbchunks; ms->done = true;
+  }
+  return 0;
+}
+
+// ---- T = L' (for the caller and for the AXPY-form back substitution), then m, posterior mean, evidence: one launch each
+// over the group (blockIdx.z / WaveSolveArgs::group)
+template <typename T>
+int large_solve(const LargeRun<T>& u) {
+  const PosteriorArgs<T>& a = u.a;
+  const LargePlan& p = u.p;
+  const int G = u.G, DP = p.DP;
+  // logpdf alone (no posterior mean, no factor wanted): the evidence is complete with the factorisation -- no transpose, no
+  // back substitution, the launch below only assembles the scalars
+  const bool evidence_only = a.mw_post == nullptr && a.T_post == nullptr;
+  if (!evidence_only) {
+    dim3 grid((DP + 31) / 32, (DP + 31) / 32, G);
+    hipLaunchKernelGGL(transpose_out_kernel<T>, grid, dim3(kThreads), 0, u.h->stream, (const T*)u.Abar, p.lda, DP, u.Tfull,
+                       (int64_t)DP, a.T_post ? a.T_post + u.reg0 * a.strideT : (T*)nullptr, a.ldt, a.D, u.wse, a.strideT,
+                       (const int32_t*)u.info_prior, (const unsigned*)u.info_noise, (const int32_t*)u.info_chol, u.wsb);
+  }
+  WaveSolveArgs<T> b{};
+  b.Tf = u.Tfull; b.ldtf = DP; b.D = a.D; b.DP = DP;
+  if (evidence_only) { b.Tf = u.Abar; b.ldtf = p.lda; b.evidence_only = 1; }  // (diagonal of L = diagonal of T)
+  b.rhs = u.Abar + DP; b.ldrhs = G > 1 ? u.wse : 0; b.rhs_inc = p.lda;  // u = row DP of the factored Abar
+  b.add = u.mw; b.out = a.mw_post ? a.mw_post + u.reg0 * a.stride_mwpost : nullptr;
+  b.ldout = G > 1 ? a.stride_mwpost : 0;
+  b.qpart = u.qpart; b.lpart = u.lpart; b.nparts = kLargeParts;
+  b.logdet_Lw_dev = u.logdetLw;
+  b.noise_kind = a.noise_kind; b.s = u.s; b.N = a.N;
+  b.logpdf = a.logpdf ? a.logpdf + u.reg0 : nullptr; b.info = a.info + u.reg0;
+  b.chol_info = u.info_chol;
+  b.prior_info = u.info_prior; b.noise_info = u.info_noise;
+  if (G > 1) { b.group = G; b.ws_stride = u.wsb; b.add_stride = a.stridemw; b.s_stride = a.strides; }
+  return launch_wave_solve<T>(u.h, b, p.NC, G);
 }
 
 // `G` regressors reg0 .. reg0 + G - 1 of the batch, each with its own copy of the workspace, in every launch of the update
 // (regressor from blockIdx.y / .z): the ~2 dispatches per panel of the factorisation are latency, not throughput, and so are
-// the small kernels around the Gram launch.  G = 1 is the single-regressor path.
+// the small kernels around the Gram launch.  G = 1 is the single-regressor path.  *G_done: the regressors that ran (the
+// workspace bound or a full device may make the group smaller).
 template <typename T>
 int posterior_large_group(blr_handle* h, const PosteriorArgs<T>& a, int64_t reg0, int G, int* G_done = nullptr) {
-  // fp32 Gram on the bf16 matrix cores: only where the ring loop runs (aligned ColVecs -- use_dma == 1).  RowVecs / unaligned fp32 calls
-  // take the plain-f32 instantiation, its split plan and its label (they used to launch the BF3K instantiation's f32 loops,
-  // 15 % slower, with a plan costed for bf16 diagonal tiles and a route that named a kernel form that never ran).
-  const bool bf3 = sizeof(T) == 4 && !h->opt.no_bf16x3 && !h->opt.no_gram_ring && a.layout == LAYOUT_COLVECS &&
-                   ((uintptr_t)(a.X + reg0 * a.strideX) % 16 == 0) && ((a.ldx * (int64_t)sizeof(T)) % 16 == 0);
-  // fp32, ColVecs (any alignment): the operands of the Gram product are split into their three bf16 planes ONCE, in the fragment order
-  // of the matrix instruction, and the Gram launch only moves and multiplies them (blr_planes.hpp)
-  const bool rff = a.rff_Omega != nullptr;
-  const bool planes = sizeof(T) == 4 && !h->opt.no_bf16x3 && !h->opt.no_planes && a.layout == LAYOUT_COLVECS && a.N > 0;
-  if (rff && !planes) return hip_fail(h, hipErrorInvalidValue, "a basis that is not materialised needs the planes path");
-  if (rff && a.rff_Din > kRffFusedMaxDin) return hip_fail(h, hipErrorInvalidValue, "a basis of D_in > kRffFusedMaxDin must be materialised");
-  h->route_i8_B = 0;
-  const int NP = h->opt.no_fp16_planes ? 3 : 2;  // planes per operand: two fp16 (three products) or three bf16 (six)
-  h->route = sizeof(T) == 8 ? "gram_tile_kernel<double>"
-                            : (planes ? (NP == 2 ? (h->opt.planes8 ? "gram_planes_kernel<2>" : "gram_planes4_kernel") : "gram_planes_kernel<3>")
-                                      : (bf3 ? "gram_tile_kernel<float, true>" : "gram_tile_kernel<float>"));  // (large-D pipeline: the Gram launch dominates; <float, true>: full tiles on the bf16 matrix cores)
-  if (rff)  // (the basis evaluated inside the planes pass: distinguishable from the same Gram kernel on materialised features)
-    h->route = NP == 2 ? (h->opt.planes8 ? "gram_planes_kernel<2> (basis in planes pass)" : "gram_planes4_kernel (basis in planes pass)")
-                       : "gram_planes_kernel<3> (basis in planes pass)";
-  using LC = LargeCfg<T>;
-  const int D = a.D, N = a.N;
-  const int DP = (D + kPB - 1) / kPB * kPB, NC = DP / kPB;
-  const int64_t lda = DP + kPB;
-  const int ntiles = NC * (NC + 1) / 2;
-  // multi-output evidence: one more row block of operand planes (the residuals of Y's columns), its macro tiles in the Gram launch
-  blr_handle::MultiSrc* const ms = h->multi_src;
-  if (ms && !(planes && !rff && !h->opt.no_fp16_planes && G == 1 && a.prior_kind != PRIOR_UPPER_FACTOR && ms->S >= 1 && ms->S <= kPB))
-    return hip_fail(h, hipErrorInvalidValue, "multi-output rows need the fp16 planes path (internal)");
-  const int NCA = NC + (ms ? 1 : 0), DPA = NCA * kPB;
-  const int ntiles_g = NCA * (NCA + 1) / 2;
-  const int nstage_cols = LC::NSC;
-  // The split plan depends on how many regressors share the launch -- and the workspace one regressor needs depends on the
-  // plan.  Plan for the requested group first, clamp the group to the workspace bound, then plan AGAIN for the group that will
-  // really run (a clamped group used to run with the split of the larger one: under-split, fewer rounds than modelled).
-  int nsplit = 1, nsplit_diag = 0, nlong = 0;
-  const int max_split_cols = std::max(1, (N + nstage_cols - 1) / nstage_cols);
-  const int max_split = std::min(64, max_split_cols);
-  auto plan_splits = [&](int G) {
-    // split-K factor: fill the 2 x 256 workgroup slots of the chip in whole rounds (576 workgroups on 512 slots
-    // would take two rounds for 1.125 rounds of work)
-    // model of the launch: rounds x (columns per workgroup + 256) -- the 256 stands for a workgroup's fixed costs (pipeline fill,
-    // the 64 KB partial it writes and the reduction reads back), fitted on c5 (136 tiles: 15 splits 1.232 ms, 11: 1.204, 7: 1.210)
-    nsplit = 1;
-    double best = 1e300;
-    for (int sp = 1; sp <= max_split; ++sp) {
-      const int wgs = ntiles * sp * G;  // (the whole group's tiles are one launch)
-      const int slots = h->cus * (sizeof(T) == 4 ? BLR_GRAM_WGS : 2);
-      const int rounds = (wgs + slots - 1) / slots;
-      const int cols_sp = ((N + sp - 1) / sp + nstage_cols - 1) / nstage_cols * nstage_cols;
-      const double cost = (double)rounds * (cols_sp + 256.0);
-      if (cost < best) { best = cost; nsplit = sp; }
-    }
-    // Diagonal macro tiles cost less per column than off-diagonal ones in the ring loop (only the 36 tiles of 16 x 16 on or below
-    // the diagonal are computed: 10 MFMAs per k-step on the critical waves instead of 16; measured ~11.5 with the b partials
-    // riding along), so in a single-round launch they get their OWN split factor: fewer, longer column ranges, and the
-    // workgroup slots that frees go to the off-diagonal tiles.  Chosen so that the longest workgroup is shortest
-    // (c3: 36 x 14 -> 28 x 15 + 8 x 11, i.e. 16 N / 14 -> 16 N / 15 per workgroup on 508 of 512 slots: 0.963 -> 0.935 ms;
-    // tools/scan_splits.sh).  Multi-round launches (c5: 136 tiles x 15) keep one factor: there the dispatcher balances.
-    // (on the bf16 matrix cores -- gram_tile_kernel<float, true> -- a diagonal tile is 18 matrix instructions and up to four operand
-    // builds per half against 24 and four: the builds dominate and the tiles cost nearly the same per column; tools/scan_splits.sh at
-    // c3: 15 | 11 0.80 ms, 14 | 14 0.75, 14 | 12 and 13 | 13 0.765)
-    const double kDiagCost = bf3 ? 15.5 : 11.5;
-    nsplit_diag = 0;  // 0: one factor for all tiles
-    nlong = 0;        // strictly lower tiles with one column range less (multi-round launches)
-    {
-      const int slots = h->cus * (sizeof(T) == 4 ? BLR_GRAM_WGS : 2);
-      // (only where the diagonal tiles will go through the ring loop: f32, LDS-DMA staging, whole row blocks)
-      const T* X0 = a.X + reg0 * a.strideX;
-      const bool dealt = sizeof(T) == 4 && a.layout == LAYOUT_COLVECS && ((uintptr_t)X0 % 16 == 0) &&
-                         ((a.ldx * (int64_t)sizeof(T)) % 16 == 0) && !h->opt.no_gram_ring &&
-                         !h->opt.no_diag_split && D % kPB == 0 && NC >= 2 && (ntiles * nsplit * G <= slots || h->opt.gs_fields >= 2);
-      if (h->opt.gs_fields >= 2) {  // "off-diagonal,diagonal" (equal: one factor): measurements only
-        const int so = h->opt.gs_so, sd = h->opt.gs_sd, nl = h->opt.gs_nl, nf = h->opt.gs_fields;
-        if (nf >= 2 && so >= 1 && sd >= 1 && sd <= so && so <= max_split) {
-          nsplit = so;
-          nsplit_diag = ((sd < so || nf == 3) && dealt) ? sd : 0;
-          if (nf == 3 && nsplit_diag > 0 && so >= 2) nlong = std::max(0, std::min(nl, ntiles - NC));
-        }
-      } else if (dealt) {
-        auto cols = [&](int sp) { return (double)(((N + sp - 1) / sp + nstage_cols - 1) / nstage_cols * nstage_cols); };
-        const int n_off = ntiles - NC;
-        double best_t = 16.0 * cols(nsplit);  // today's longest workgroup (diagonal tiles shorter, off-diagonal ones set the time)
-        int bo = 0, bd = 0;
-        for (int so = 1; so <= max_split; ++so)
-          for (int sd = 1; sd <= so; ++sd) {
-            if ((n_off * so + NC * sd) * G > slots) break;
-            const double t = std::max(16.0 * cols(so), kDiagCost * cols(sd)) * (1.0 + 0.002 * so);
-            if (t < best_t * 0.995) { best_t = t; bo = so; bd = sd; }
-          }
-        if (bo > 0) { nsplit = bo; nsplit_diag = bd; }
-      }
-      // multi-round launch of one regressor: three kinds of work items (plan_gram_rounds)
-      const bool ring_ok = sizeof(T) == 4 && a.layout == LAYOUT_COLVECS && ((uintptr_t)X0 % 16 == 0) &&
-                           ((a.ldx * (int64_t)sizeof(T)) % 16 == 0) && !h->opt.no_gram_ring &&
-                           !h->opt.no_diag_split && h->opt.gs_fields < 2 && D % kPB == 0 && NC >= 2;
-      if (ring_ok && G == 1 && nsplit_diag == 0 && ntiles * nsplit > slots && nsplit >= 2) {
-        const std::array<int, 3> key{NC, N, slots};
-        auto it = h->gram_plans.find(key);
-        if (it == h->gram_plans.end()) {
-          const GramPlan pl = plan_gram_rounds(ntiles - NC, NC, nsplit, N, nstage_cols, slots, max_split, kDiagCost / 16.0);
-          it = h->gram_plans.emplace(key, std::array<int, 3>{pl.so, pl.sd, pl.nlong}).first;
-          if (h->opt.plan_debug)
-            fprintf(stderr, "blr: Gram plan for %d row blocks, N = %d: one factor %d -> ranges %d (off-diagonal, %d tiles with %d) / %d (diagonal), "
-                            "modelled makespan %.0f column units\n", NC, N, nsplit, pl.so, pl.nlong, pl.so - 1, pl.sd, pl.makespan);
-        }
-        if (it->second[1] > 0) { nsplit = it->second[0]; nsplit_diag = it->second[1]; nlong = it->second[2]; }
-      }
-    }
-  };
-  // the planes path: one 512-thread workgroup per CU, k-blocks of 16 columns, diagonal macro tiles as long as the others
-  const bool planes4 = NP == 2 && !h->opt.planes8;  // 64 x 64 per wave, two 256-thread workgroups per CU (gram_planes4_kernel)
-  const int kbs = NP == 2 ? PlanesCfg<2>::KBS : PlanesCfg<3>::KBS;
-  const int NKB = ((N + 15) / 16 + kbs - 1) / kbs * kbs;  // k-blocks of 16 columns, padded to whole stages of the Gram launch (zero columns)
-  auto plan_splits_planes = [&](int G) {
-    nsplit_diag = 0; nlong = 0; nsplit = 1;
-    double best = 1e300;
-    const int slots = h->cus * (planes4 ? 2 : 1);
-    for (int sp = 1; sp <= std::min(64, std::max(1, NKB)); ++sp) {
-      const int rounds = (ntiles_g * sp * G + slots - 1) / slots;
-      const double cost = (double)rounds * (16.0 * ((NKB + sp - 1) / sp) + 192.0);  // (192: a workgroup's pipeline fill and its 64 KB partial tile, in columns)
-      if (cost < best) { best = cost; nsplit = sp; }
-    }
-    if (h->opt.gs_fields >= 2 && h->opt.gs_so >= 1 && h->opt.gs_so <= 64) nsplit = h->opt.gs_so;  // (GRAM_SPLITS: measurements only)
-  };
-  if (planes) plan_splits_planes(G); else plan_splits(G);
-  // column chunks of the planes pass (one b partial each): ~ 2 workgroups per CU, and no chunk beyond kPlanesChunkKb k-blocks (its
-  // per-column scalars live in LDS)
-  const int nbchunks = planes ? std::max(1, std::min(NKB, std::max((512 + NC - 1) / NC, (NKB + kPlanesChunkKb - 1) / kPlanesChunkKb))) : 0;
-  const bool prior_factor = a.prior_kind == PRIOR_UPPER_FACTOR;
-  const int pf = prior_factor ? 1 : 0;
-  size_t ws_cap = kChainWorkspace;
-  if (h->opt.chain_ws_mb > 0) ws_cap = (size_t)h->opt.chain_ws_mb << 20;  // tests: small groups
-  {
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    auto per_for = [&](int nsp) {  // the carve below, as a function of the split factor
-      const size_t nst = (size_t)(nsp + pf);
-      return al((size_t)lda * DP * sizeof(T)) + al(a.prior_kind == PRIOR_DENSE ? (size_t)DP * DP * sizeof(T) : 0) +
-             al(planes ? (size_t)NKB * NCA * 4 * NP * 1024 : 0) +
-             al(nst * ntiles_g * kPB * kPB * sizeof(T)) + al(std::max<size_t>(nst, (size_t)nbchunks) * NCA * kPB * sizeof(double) + (size_t)DPA * sizeof(unsigned) + 8) + al((size_t)std::max(N, 1) * sizeof(T)) +
-             (ms ? al((size_t)std::max(N, 1) * sizeof(T)) + al((size_t)nbchunks * kPB * sizeof(double)) : 0) +
-             al(a.noise_kind == NOISE_DIAGONAL ? (size_t)std::max(N, 1) * sizeof(T) : 0) + 2 * al((size_t)1024 * sizeof(double)) +
-             al((size_t)DP * DP * sizeof(T)) + al(64);
-    };
-    const int Gc = (int)std::max<size_t>(1, std::min<size_t>((size_t)G, ws_cap / per_for(nsplit)));
-    if (Gc != G) {
-      G = Gc;
-      if (planes) plan_splits_planes(G); else plan_splits(G);
-    }
-  }
-  const int nsplit_total = nsplit + pf;  // (nsplit_diag <= nsplit: the partial workspace is laid out for the larger factor)
-  const int gridc = 1024;
-
-  const int64_t gp_tiles = (int64_t)nsplit_total * ntiles_g;
-
-  // workspace carve
-  size_t off = 0;
-  auto carve = [&](size_t bytes) { size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
-  const size_t o_abar = carve((size_t)lda * DP * sizeof(T));
-  const size_t o_w = carve(a.prior_kind == PRIOR_DENSE ? (size_t)DP * DP * sizeof(T) : 0);
-  const size_t o_xp = carve(planes ? (size_t)NKB * NCA * 4 * NP * 1024 : 0);
-  const size_t o_gp = carve((size_t)gp_tiles * kPB * kPB * sizeof(T));
-  // b partials, then (planes path) the rows' largest entries: both zeroed by the prior launch's scratch initialisation
-  const int bslots = std::max(nsplit_total, nbchunks);
-  const size_t o_bp = carve((size_t)bslots * NCA * kPB * sizeof(double) + (size_t)DPA * sizeof(unsigned) + 8);  // (+ the planes pass's redo flag)
-  const size_t o_mu = carve(ms ? (size_t)std::max(N, 1) * sizeof(T) : 0);           // multi-output: x_n'mw
-  const size_t o_qs = carve(ms ? (size_t)nbchunks * kPB * sizeof(double) : 0);      // multi-output: partial sums of q_s per column chunk
-  const size_t o_r = carve((size_t)std::max(N, 1) * sizeof(T));
-  const size_t o_wv = carve(a.noise_kind == NOISE_DIAGONAL ? (size_t)std::max(N, 1) * sizeof(T) : 0);  // 1 / s_n for the Gram launch
-  const size_t o_q = carve((size_t)gridc * sizeof(double));
-  const size_t o_l = carve((size_t)gridc * sizeof(double));
-  const size_t o_m = carve((size_t)DP * DP * sizeof(T));  // transposed factor for the back substitution
-  const size_t o_sc = carve(64);
-  const size_t per = off;  // one regressor's workspace (a multiple of 256 bytes)
-  G = (int)std::max<size_t>(1, std::min<size_t>((size_t)G, ws_cap / per));  // (the re-planned split may need a little more per regressor)
+  const LargeShape shape{(int)sizeof(T), a.D, a.N, a.layout, a.noise_kind, a.prior_kind, aligned16(a.X + reg0 * a.strideX, a.ldx, (int64_t)0),
+                         a.rff_Omega != nullptr, a.rff_Din, h->multi_src ? h->multi_src->S : 0, G};
+  LargePlan p;
+  const char* const refused = plan_large(shape, h->opt, h->cus, large_ws_cap(h->opt), h->gram_plans, p);
+  if (p.route) { h->route_i8_B = 0; h->route = p.route; }
+  if (refused) return hip_fail(h, hipErrorInvalidValue, refused);
+  G = p.G;
   int rc;
   for (;;) {  // (a device too full for the whole group's workspace: smaller groups, down to one regressor at a time)
-    rc = h->ws.reserve(h, per * (size_t)G, blr_handle::kWsFloor);
+    rc = h->ws.reserve(h, p.o.per * (size_t)G, blr_handle::kWsFloor);
     if (rc == 0 || G == 1) break;
     (void)hipGetLastError();
     h->err.clear();
@@ -671,250 +728,24 @@ int posterior_large_group(blr_handle* h, const PosteriorArgs<T>& a, int64_t reg0
   }
   if (rc) return rc;
   if (G_done) *G_done = G;
-  // Every launch below covers the whole group: regressor g from blockIdx.y / .z, its caller-side arrays by the batch strides
-  // and its workspace `per` bytes after its predecessor's (the pointers here are regressor reg0's).
-  const int64_t reg = reg0;
-  char* ws = h->ws.p;
-  T* Abar = reinterpret_cast<T*>(ws + o_abar);
-  T* W = reinterpret_cast<T*>(ws + o_w);
-  T* Gpart = reinterpret_cast<T*>(ws + o_gp);
-  double* bpart = reinterpret_cast<double*>(ws + o_bp);
-  T* rvec = reinterpret_cast<T*>(ws + o_r);
-  T* wvec = a.noise_kind == NOISE_DIAGONAL ? reinterpret_cast<T*>(ws + o_wv) : nullptr;
-  double* qpart = reinterpret_cast<double*>(ws + o_q);
-  double* lpart = reinterpret_cast<double*>(ws + o_l);
-  double* logdetLw = reinterpret_cast<double*>(ws + o_sc);
-  int32_t* info_prior = reinterpret_cast<int32_t*>(ws + o_sc + 8);
-  int32_t* info_chol = reinterpret_cast<int32_t*>(ws + o_sc + 12);
-  unsigned* info_noise = reinterpret_cast<unsigned*>(ws + o_sc + 16);
-  const int64_t wsb = (int64_t)per;                  // byte stride between the regressors' workspaces
-  const int64_t wse = (int64_t)(per / sizeof(T));    // the same in elements (per is a multiple of 256)
+  const LargeRun<T> u = bind_large<T>(h, a, p, reg0, G);
 
-  const T* X = a.X + reg * a.strideX;
-  const T* y = a.y + reg * a.stridey;
-  const T* s = a.s + reg * a.strides;
-  const T* mw = a.mw + reg * a.stridemw;
-  const T* Lw = a.Lw + reg * a.strideLw;
-
-  // ---- prior: SPD check + logdet (reference :78).  One launch clears the scratch words, sets the noise flag and zeroes the
-  // b partials; for a diagonal / factor prior it also checks the diagonal and seeds info_chol with the prior's status (a failed
-  // prior short-circuits the factorisation), for a dense one the blocked factorisation of W does that.
-  {
-    const bool dense = a.prior_kind == PRIOR_DENSE;
-    ScratchInit init;
-    init.words16 = reinterpret_cast<unsigned*>(ws + o_sc);
-    init.ones = info_noise;
-    init.zeros = bpart;
-    init.nzeros = (long long)bslots * NCA * kPB + DPA / 2 + 1;  // (+ the row maxima behind the b partials: DP words, + the redo flag)
-    init.info_copy = dense ? nullptr : info_chol;
-    const int gridp = (int)std::min<long long>(64, 1 + init.nzeros / (8 * kThreads));
-    // (dense: the kernel's own look at Lw's diagonal is not the answer -- status and logdet go to spare scratch words)
-    hipLaunchKernelGGL(prior_diag_kernel<T>, dim3(gridp, G), dim3(kThreads), 0, h->stream, Lw, a.ldl, a.prior_kind, D,
-                       dense ? reinterpret_cast<double*>(ws + o_sc + 40) : logdetLw,
-                       dense ? reinterpret_cast<int32_t*>(ws + o_sc + 32) : info_prior, init, a.strideLw, wsb);
-    if (dense) {
-      hipLaunchKernelGGL(prior_copy_kernel<T>, dim3(1024, G), dim3(kThreads), 0, h->stream, Lw, a.ldl, D, DP, W, (int64_t)DP, a.strideLw, wse);
-      if ((rc = chol_large<T>(h, W, DP, DP, DP, info_prior, G, wse, (int)(per / sizeof(int32_t))))) return rc;
-      hipLaunchKernelGGL(logdet_kernel<T>, dim3(G), dim3(kThreads), 0, h->stream, (const T*)W, (int64_t)DP, D, logdetLw, wsb,
-                         (const int32_t*)info_prior, info_chol);
-    }
-  }
-
-  // ---- column statistics (reference :82-84)
-  {
-    ColstatsArgs<T> c{};
-    c.X = X; c.ldx = a.ldx; c.y = y; c.s = s; c.mw = mw; c.r = rvec; c.w = wvec; c.qpart = qpart; c.lpart = lpart;
-    c.noise_info = info_noise;
-    c.layout = a.layout; c.noise_kind = a.noise_kind; c.D = D; c.N = N;
-    c.grp_X = a.strideX; c.grp_y = a.stridey; c.grp_s = a.strides; c.grp_mw = a.stridemw; c.grp_ws = wsb;
-    c.w_sqrt = planes ? 1 : 0;
-    c.mu = ms ? reinterpret_cast<T*>(ws + o_mu) : nullptr;
-    if (rff) {
-      c.X = nullptr;
-      c.rff_Xin = a.rff_Xin; c.rff_ldxin = a.rff_ldxin; c.rff_Omega = a.rff_Omega; c.rff_ldo = a.rff_ldo; c.rff_phase = a.rff_phase;
-      c.rff_scale = a.rff_scale; c.rff_Din = a.rff_Din;
-    }
-    size_t lds = (((size_t)D * sizeof(T) + 15) & ~(size_t)15) + 64;
-    hipLaunchKernelGGL(colstats_kernel<T>, dim3(gridc, G), dim3(kThreads), lds, h->stream, c);
-  }
-
-  // ---- Gram (reference :86) : split-K partial tiles, then the prior factor as pseudo-observations
-  if ((rc = set_lds<T>(h, reinterpret_cast<const void*>(gram_tile_kernel<T>), LC::LDS_BYTES))) return rc;
+  if ((rc = large_prior(u))) return rc;
+  large_colstats(u);
+  if ((rc = set_lds<T>(h, reinterpret_cast<const void*>(gram_tile_kernel<T>), LargeCfg<T>::LDS_BYTES))) return rc;
   if constexpr (sizeof(T) == 4) {
-    if ((rc = set_lds<T>(h, reinterpret_cast<const void*>(gram_tile_kernel<T, true>), LC::LDS_BYTES))) return rc;
+    if ((rc = set_lds<T>(h, reinterpret_cast<const void*>(gram_tile_kernel<T, true>), LargeCfg<T>::LDS_BYTES))) return rc;
+    if (p.planes) { if ((rc = large_gram_planes(u))) return rc; }
+    else large_gram_tiles(u);
+  } else {
+    large_gram_tiles(u);
   }
-  GramTileArgs<T> g{};
-  g.X = X; g.ldx = a.ldx; g.layout = a.layout;
-  const bool no_ring = h->opt.no_gram_ring;  // A/B experiments only
-  g.use_dma = (a.layout == LAYOUT_COLVECS && ((uintptr_t)X % 16 == 0) && ((a.ldx * (int64_t)sizeof(T)) % 16 == 0)) ? (no_ring ? 2 : 1) : 0;
-  g.bf3 = bf3 ? 1 : 0;  // (f32 + the LDS-DMA ring only: the bf16 x 3 code lives in the ring loop)
-  g.s = s; g.noise_kind = a.noise_kind; g.r = rvec; g.wpre = wvec;
-  g.D = D; g.n_begin = 0; g.n_end = N; g.nblocks = NC; g.bpart = bpart; g.mode_out = 0;
-  g.grp_X = a.strideX; g.grp_s = a.strides; g.grp_ws = wsb;
-  const bool no_swizzle = h->opt.no_xcd_swizzle;
-  ReduceArgs<T> r{};
-  r.bpart = bpart; r.nblocks = NC;
-  r.Lw = Lw; r.ldl = a.ldl; r.prior_kind = a.prior_kind; r.D = D; r.DP = DP; r.Abar = Abar; r.lda = lda;
-  r.Lw_post = a.Lw_post ? a.Lw_post + reg * a.strideLp : nullptr; r.ldlp = a.ldlp;
-  r.grp_Lw = a.strideLw; r.grp_Lp = a.strideLp; r.grp_ws = wsb;
-  // launches the tiles described by g (+ the prior-factor pseudo split) and their reduction on `st`
-  auto gram_tiles = [&](hipStream_t st, int nsp, int nt, T* gp) {
-    g.nsplit = nsp; g.ntiles = nt; g.Gpart = gp;
-    g.nsplit_diag = nsplit_diag; g.nlong = nlong;
-    g.xcd_swizzle = (nsp > 1 && !no_swizzle) ? (nlong == 0 ? 1 : 2) : 0;  // (three kinds of work items: remapped inside a kind, the dispatch order of the kinds IS the plan)
-    const int nwg = nsplit_diag ? (nt - NC) * nsp - nlong + NC * nsplit_diag : nt * nsp;
-    if constexpr (sizeof(T) == 4) {
-      if (g.bf3) hipLaunchKernelGGL((gram_tile_kernel<T, true>), dim3(nwg, G), dim3(kThreads), LC::LDS_BYTES, st, g);
-      else hipLaunchKernelGGL(gram_tile_kernel<T>, dim3(nwg, G), dim3(kThreads), LC::LDS_BYTES, st, g);
-    } else {
-      hipLaunchKernelGGL(gram_tile_kernel<T>, dim3(nwg, G), dim3(kThreads), LC::LDS_BYTES, st, g);
-    }
-    if (prior_factor) {
-      GramTileArgs<T> u = g;
-      u.xcd_swizzle = 0;
-      u.X = Lw; u.ldx = a.ldl; u.layout = 2; u.use_dma = 0; u.s = nullptr; u.r = nullptr; u.wpre = nullptr;
-      u.grp_X = a.strideLw; u.grp_s = 0;
-      u.n_begin = 0; u.n_end = D; u.nsplit = 1; u.nsplit_diag = 0; u.nlong = 0;
-      u.Gpart = gp + (int64_t)nsp * nt * kPB * kPB;
-      u.bpart = bpart + (int64_t)nsp * NC * kPB;
-      hipLaunchKernelGGL(gram_tile_kernel<T>, dim3(nt, G), dim3(kThreads), LC::LDS_BYTES, st, u);
-    }
-  };
-  auto gram_reduce = [&](hipStream_t st, int nsp, int nt, T* gp, int reduce_blocks) {
-    r.Gpart = gp; r.nsplit_total = nsp + pf; r.ntiles = nt;
-    r.nsplit_diag = nsplit_diag; r.pseudo_split = pf; r.nlong = nlong;
-    hipLaunchKernelGGL(gram_reduce_kernel<T>, dim3(nt + reduce_blocks, 16, G), dim3(kThreads), 0, st, r);
-  };
-
-  g.tile_i0 = 0; g.tile_j0 = 0; g.tri = 1;
-  bool planes_done = false;
-  if constexpr (sizeof(T) == 4) {
-    if (planes) {
-      if ((rc = set_lds_once(h, reinterpret_cast<const void*>(gram_planes_kernel<2>), (size_t)PlanesCfg<2>::LDS))) return rc;
-      if ((rc = set_lds_once(h, reinterpret_cast<const void*>(gram_planes_kernel<3>), (size_t)PlanesCfg<3>::LDS))) return rc;
-      unsigned short* Xp = reinterpret_cast<unsigned short*>(ws + o_xp);
-      unsigned* rowmax = reinterpret_cast<unsigned*>(bpart + (int64_t)bslots * NCA * kPB);
-      PlanesArgs pa{};
-      pa.X = rff ? nullptr : X; pa.ldx = a.ldx;
-      pa.Xin = a.rff_Xin; pa.ldxin = a.rff_ldxin; pa.Omega = a.rff_Omega; pa.ldo = a.rff_ldo; pa.phase = a.rff_phase; pa.scale = a.rff_scale; pa.Din = a.rff_Din;
-      pa.wsq = wvec; pa.r = rvec; pa.Xp = Xp; pa.bpart = bpart; pa.rowmax = rowmax;
-      pa.D = D; pa.N = N; pa.NC = NCA; pa.NKB = NKB; pa.nchunks = nbchunks;
-      pa.grp_X = a.strideX; pa.grp_ws = wsb;
-      if constexpr (sizeof(T) == 4) {
-        if (ms) {
-          pa.Y = static_cast<const float*>(ms->Y); pa.ldY = ms->ldY; pa.S = ms->S;
-          pa.mu = reinterpret_cast<const float*>(ws + o_mu); pa.qsp = reinterpret_cast<double*>(ws + o_qs);
-        }
-      }
-      // a basis of up to 8 input dimensions: the raw inputs of a workgroup's whole column chunk are staged once (blr_planes.hpp, xs_chunk)
-      pa.xs_chunk = (rff && a.rff_Din <= 8) ? 1 : 0;
-      const size_t plds = planes_pass_lds(rff, pa.xs_chunk != 0, a.rff_Din);
-      if (NP == 2) {  // the rows' power-of-two scales need (a bound of) the rows' largest entries first
-        if (rff) {  // a basis: its bound
-          hipLaunchKernelGGL(rowmax_kernel<true>, dim3(nbchunks, 1, G), dim3(kThreads), 0, h->stream, pa);
-          hipLaunchKernelGGL((planes_kernel<2, true>), dim3(nbchunks, NC, G), dim3(kThreads), plds, h->stream, pa);
-        } else if (h->opt.no_spec_rowmax) {  // the exact maxima: one more pass over X
-          hipLaunchKernelGGL(rowmax_kernel<false>, dim3(nbchunks, NCA, G), dim3(kThreads), 0, h->stream, pa);
-          hipLaunchKernelGGL((planes_kernel<2, false>), dim3(nbchunks, NCA, G), dim3(kThreads), plds, h->stream, pa);
-        } else {
-          // sampled maxima with head-room, the planes pass checks that every entry fits; the exact pass + the planes again only if one
-          // did not (two launches that return at once otherwise: ~ 5 us against the 58 us of the exact pass at config 3)
-          if ((rc = ensure_stats(h))) return rc;
-          pa.redo = rowmax + DPA;
-          pa.redo_total = h->stats_dev + 1;
-          pa.sample_kb = 2;
-          hipLaunchKernelGGL(rowmax_kernel<false>, dim3(nbchunks, NCA, G), dim3(kThreads), 0, h->stream, pa);
-          hipLaunchKernelGGL((planes_kernel<2, false>), dim3(nbchunks, NCA, G), dim3(kThreads), plds, h->stream, pa);
-          pa.sample_kb = 0;
-          pa.redo_pass = 1;
-          hipLaunchKernelGGL(rowmax_kernel<false>, dim3(nbchunks, NCA, G), dim3(kThreads), 0, h->stream, pa);
-          hipLaunchKernelGGL((planes_kernel<2, false>), dim3(nbchunks, NCA, G), dim3(kThreads), plds, h->stream, pa);
-        }
-      } else {
-        if (rff) hipLaunchKernelGGL((planes_kernel<3, true>), dim3(nbchunks, NC, G), dim3(kThreads), plds, h->stream, pa);
-        else hipLaunchKernelGGL((planes_kernel<3, false>), dim3(nbchunks, NC, G), dim3(kThreads), plds, h->stream, pa);
-      }
-      HIP_TRY(h, hipGetLastError());  // (a failed planes launch leaves the last call's planes in the workspace: never a posterior from them)
-      GramPlanesArgs ga{};
-      ga.Xp = Xp; ga.NC = NCA; ga.NKB = NKB; ga.Gpart = Gpart; ga.ntiles = ntiles_g; ga.nsplit = nsplit;
-      ga.s_iso = a.noise_kind == NOISE_DIAGONAL ? nullptr : s;
-      ga.rowmax = rowmax;
-      ga.xcd_swizzle = (nsplit > 1 && !no_swizzle) ? 1 : 0;
-      ga.grp_ws = wsb; ga.grp_s = a.strides;
-      if (planes4) {
-        if ((rc = set_lds_once(h, reinterpret_cast<const void*>(gram_planes4_kernel), (size_t)Planes4Cfg::LDS))) return rc;
-        hipLaunchKernelGGL(gram_planes4_kernel, dim3(ntiles_g * nsplit, G), dim3(kThreads), (size_t)Planes4Cfg::LDS, h->stream, ga);
-      } else if (NP == 2) hipLaunchKernelGGL(gram_planes_kernel<2>, dim3(ntiles_g * nsplit, G), dim3(kPlanesThreads), (size_t)PlanesCfg<2>::LDS, h->stream, ga);
-      else hipLaunchKernelGGL(gram_planes_kernel<3>, dim3(ntiles_g * nsplit, G), dim3(kPlanesThreads), (size_t)PlanesCfg<3>::LDS, h->stream, ga);
-      if (prior_factor) {  // the prior factor as pseudo-observations: one more partial per tile, from the f32 kernel
-        GramTileArgs<T> u = g;
-        u.nsplit = 1; u.ntiles = ntiles; u.nsplit_diag = 0; u.nlong = 0;
-        u.xcd_swizzle = 0;
-        u.X = Lw; u.ldx = a.ldl; u.layout = 2; u.use_dma = 0; u.bf3 = 0; u.s = nullptr; u.r = nullptr; u.wpre = nullptr;
-        u.grp_X = a.strideLw; u.grp_s = 0;
-        u.n_begin = 0; u.n_end = D;
-        u.Gpart = Gpart + (int64_t)nsplit * ntiles * kPB * kPB;
-        u.bpart = bpart;  // (never written: r == NULL)
-        hipLaunchKernelGGL(gram_tile_kernel<T>, dim3(ntiles, G), dim3(kThreads), LC::LDS_BYTES, h->stream, u);
-      }
-      r.nsplit_b = nbchunks;
-      r.nblocks = NCA;                 // (stride of the planes pass's b partials)
-      r.multi_block = ms ? NC : 0;
-      gram_reduce(h->stream, nsplit, ntiles_g, Gpart, NC);
-      planes_done = true;
-    }
-  }
-  if (!planes_done) {
-    gram_tiles(h->stream, nsplit, ntiles, Gpart);
-    gram_reduce(h->stream, nsplit, ntiles, Gpart, NC);
-  }
-  // ---- blocked Cholesky of Abar (rows DP.. = rhs) -> L, u  (reference :86, :57)
-  // (only the first 64 of the 128 padding rows ride along: row DP is b', the others are zero and nobody reads them back --
-  // half the right-hand-side sub-tiles of every trailing update, and c5's first trailing updates fit one round)
-  // (multi-output: rows DP + s are b_s' for the columns s < S of Y; more than 64 of them take all 128 rows along)
-  if ((rc = chol_large<T>(h, Abar, lda, DP, DP + ((ms && ms->S > TrailCfg<T>::SB) ? kPB : TrailCfg<T>::SB), info_chol, G, wse,
-                          (int)(per / sizeof(int32_t))))) return rc;
-  if (ms) {
-    ms->Abar = Abar; ms->lda = lda; ms->Tfull = ws + o_m; ms->DP = DP;
-    ms->qsp = reinterpret_cast<double*>(ws + o_qs); ms->nq = nbchunks; ms->done = true;
-  }
-
-  // ---- T = L' (for the caller and for the AXPY-form back substitution), then m, posterior mean, evidence: one launch each
-  // over the group (blockIdx.z / WaveSolveArgs::group)
-  {
-    char* ws = h->ws.p;
-    T* Abar = reinterpret_cast<T*>(ws + o_abar);
-    T* Tfull = reinterpret_cast<T*>(ws + o_m);
-    // logpdf alone (no posterior mean, no factor wanted): the evidence is complete with the factorisation -- no transpose, no
-    // back substitution, the launch below only assembles the scalars
-    const bool evidence_only = a.mw_post == nullptr && a.T_post == nullptr;
-    if (!evidence_only) {
-      dim3 grid((DP + 31) / 32, (DP + 31) / 32, G);
-      hipLaunchKernelGGL(transpose_out_kernel<T>, grid, dim3(kThreads), 0, h->stream, (const T*)Abar, lda, DP, Tfull,
-                         (int64_t)DP, a.T_post ? a.T_post + reg0 * a.strideT : (T*)nullptr, a.ldt, D, (int64_t)(per / sizeof(T)), a.strideT,
-                         (const int32_t*)info_prior, (const unsigned*)info_noise, (const int32_t*)info_chol, (int64_t)per);
-    }
-    WaveSolveArgs<T> b{};
-    b.Tf = Tfull; b.ldtf = DP; b.D = D; b.DP = DP;
-    if (evidence_only) { b.Tf = Abar; b.ldtf = lda; b.evidence_only = 1; }  // (diagonal of L = diagonal of T)
-    b.rhs = Abar + DP; b.ldrhs = G > 1 ? (int64_t)(per / sizeof(T)) : 0; b.rhs_inc = lda;  // u = row DP of the factored Abar
-    b.add = a.mw + reg0 * a.stridemw; b.out = a.mw_post ? a.mw_post + reg0 * a.stride_mwpost : nullptr;
-    b.ldout = G > 1 ? a.stride_mwpost : 0;
-    b.qpart = reinterpret_cast<double*>(ws + o_q); b.lpart = reinterpret_cast<double*>(ws + o_l); b.nparts = gridc;
-    b.logdet_Lw_dev = reinterpret_cast<double*>(ws + o_sc);
-    b.noise_kind = a.noise_kind; b.s = a.s + reg0 * a.strides; b.N = N;
-    b.logpdf = a.logpdf ? a.logpdf + reg0 : nullptr; b.info = a.info + reg0;
-    b.chol_info = reinterpret_cast<int32_t*>(ws + o_sc + 12);
-    b.prior_info = reinterpret_cast<int32_t*>(ws + o_sc + 8); b.noise_info = reinterpret_cast<unsigned*>(ws + o_sc + 16);
-    if (G > 1) { b.group = G; b.ws_stride = (int64_t)per; b.add_stride = a.stridemw; b.s_stride = a.strides; }
-    if ((rc = launch_wave_solve<T>(h, b, NC, G))) return rc;
-  }
+  large_reduce(u);
+  if ((rc = large_factor(u))) return rc;
+  if ((rc = large_solve(u))) return rc;
   HIP_TRY(h, hipGetLastError());
   return 0;
 }
-
-template <typename T>
-int posterior_large_one(blr_handle* h, const PosteriorArgs<T>& a, int64_t reg) { return posterior_large_group<T>(h, a, reg, 1); }
 
 template <typename T>
 int dispatch_posterior(blr_handle* h, const PosteriorArgs<T>& a) {
@@ -1396,15 +1227,14 @@ int gram_stats(blr_handle* h, int layout, int64_t D64, int64_t N64, const T* X, 
     if (eff > best) { best = eff; nsplit = sp; }
   }
   const int gridc = 1024;
-  size_t off = 0;
-  auto carve = [&](size_t bytes) { size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
+  Carve carve;
   const size_t o_gp = carve((size_t)nsplit * ntiles * kPB * kPB * sizeof(T));
   const size_t o_bp = carve((size_t)nsplit * NC * kPB * sizeof(double));
   const size_t o_r = carve((size_t)N * sizeof(T));
   const size_t o_wv = carve(noise_kind == BLR_NOISE_DIAGONAL ? (size_t)N * sizeof(T) : 0);  // 1 / s_n for the Gram launch
   const size_t o_q = carve((size_t)gridc * sizeof(double));
   const size_t o_l = carve((size_t)gridc * sizeof(double));
-  int rc = h->ws.reserve(h, off, blr_handle::kWsFloor);
+  int rc = h->ws.reserve(h, carve.off, blr_handle::kWsFloor);
   if (rc) return rc;
   char* ws = h->ws.p;
   T* Gpart = reinterpret_cast<T*>(ws + o_gp);
@@ -1427,7 +1257,7 @@ int gram_stats(blr_handle* h, int layout, int64_t D64, int64_t N64, const T* X, 
   {
     GramTileArgs<T> g{};
     g.X = X; g.ldx = ldx; g.layout = layout;
-    g.use_dma = (layout == LAYOUT_COLVECS && ((uintptr_t)X % 16 == 0) && ((ldx * (int64_t)sizeof(T)) % 16 == 0)) ? 1 : 0;
+    g.use_dma = x_ring(layout, X, ldx) ? 1 : 0;
     g.s = s; g.noise_kind = noise_kind; g.r = rvec; g.wpre = wvec;
     g.D = D; g.n_begin = 0; g.n_end = N; g.nsplit = nsplit;
     g.tile_i0 = 0; g.tile_j0 = 0; g.tri = 1; g.ntiles = ntiles; g.nblocks = NC;
@@ -1466,19 +1296,18 @@ int posterior_from_stats(blr_handle* h, int64_t D64, int64_t N_total, T* stats, 
   if (Lw_post && ldlp < D) return bad_arg(h, 15, "ldlp < D");
   if (!info) return bad_arg(h, 17, "info is NULL");
   HIP_TRY(h, hipSetDevice(h->device));
-  size_t off = 0;
-  auto carve = [&](size_t bytes) { size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
+  Carve carve;
   const size_t o_w = carve(prior_kind == BLR_PRIOR_DENSE ? (size_t)DP * DP * sizeof(T) : 0);
   const size_t o_m = carve((size_t)DP * DP * sizeof(T));
   const size_t o_sc = carve(64);
-  int rc = h->ws.reserve(h, off, blr_handle::kWsFloor);
+  int rc = h->ws.reserve(h, carve.off, blr_handle::kWsFloor);
   if (rc) return rc;
   char* ws = h->ws.p;
   T* W = reinterpret_cast<T*>(ws + o_w);
   T* Tfull = reinterpret_cast<T*>(ws + o_m);
-  double* logdetLw = reinterpret_cast<double*>(ws + o_sc);
-  int32_t* info_prior = reinterpret_cast<int32_t*>(ws + o_sc + 8);
-  int32_t* info_chol = reinterpret_cast<int32_t*>(ws + o_sc + 12);
+  double* logdetLw = reinterpret_cast<double*>(ws + o_sc + LargeScratch::logdet);
+  int32_t* info_prior = reinterpret_cast<int32_t*>(ws + o_sc + LargeScratch::info_prior);
+  int32_t* info_chol = reinterpret_cast<int32_t*>(ws + o_sc + LargeScratch::info_chol);
   HIP_TRY(h, hipMemsetAsync(ws + o_sc, 0, 64, h->stream));
   if (prior_kind == BLR_PRIOR_DENSE) {
     hipLaunchKernelGGL(prior_copy_kernel<T>, dim3(1024), dim3(kThreads), 0, h->stream, Lw, ldl, D, DP, W, (int64_t)DP);
@@ -1490,7 +1319,7 @@ int posterior_from_stats(blr_handle* h, int64_t D64, int64_t N_total, T* stats, 
   hipLaunchKernelGGL(stats_add_prior_kernel<T>, dim3(1024), dim3(kThreads), 0, h->stream, stats, lds, D, DP, Lw, ldl, prior_kind,
                      Lw_post, ldlp);
   HIP_TRY(h, hipMemcpyAsync(info_chol, info_prior, sizeof(int32_t), hipMemcpyDeviceToDevice, h->stream));
-  if ((rc = chol_large<T>(h, stats, lds, DP, DP + TrailCfg<T>::SB, info_chol))) return rc;  // (see posterior_large_one)
+  if ((rc = chol_large<T>(h, stats, lds, DP, DP + TrailCfg<T>::SB, info_chol))) return rc;  // (the right-hand-side rows that ride along: see large_factor)
   {
     dim3 grid((DP + 31) / 32, (DP + 31) / 32);
     hipLaunchKernelGGL(transpose_out_kernel<T>, grid, dim3(kThreads), 0, h->stream, (const T*)stats, lds, DP, Tfull, (int64_t)DP,
@@ -1537,8 +1366,7 @@ int logpdf_grad_large_group(blr_handle* h, int G, int layout, int64_t D, int64_t
   const int DI = Ainv ? DP : 0;
   const int R = DP + NP + DI;
   const int64_t ldy = R;
-  size_t off = 0;
-  auto carve = [&](size_t bytes) { size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
+  Carve carve;
   const size_t o_y = carve((size_t)ldy * DP * sizeof(T));
   const size_t o_sq = carve((size_t)(NP + DI) * sizeof(double));
   const size_t o_mu = carve((size_t)NP * sizeof(T));
@@ -1546,8 +1374,8 @@ int logpdf_grad_large_group(blr_handle* h, int G, int layout, int64_t D, int64_t
   const size_t o_r = carve((size_t)NP * sizeof(T));
   const size_t o_w = carve((size_t)NP * sizeof(T));
   const size_t o_part = carve(dmw ? (size_t)(NP / 64) * DP * sizeof(double) : 0);
-  const int64_t wsb = (int64_t)off;  // one regressor's slice
-  int rc = h->ws.reserve(h, off * (size_t)G, blr_handle::kWsFloor);
+  const int64_t wsb = (int64_t)carve.off;  // one regressor's slice
+  int rc = h->ws.reserve(h, carve.off * (size_t)G, blr_handle::kWsFloor);
   if (rc) return rc;
   T* Ybar = reinterpret_cast<T*>(h->ws.p + o_y);
   double* rowsq = reinterpret_cast<double*>(h->ws.p + o_sq);
@@ -1736,13 +1564,12 @@ int logpdf_grad_batched(blr_handle* h, int memspace, int layout, int64_t B, int6
                     (rowv || ((ldx % Mfma<T>::VEC) == 0 && ((uintptr_t)a.X % 16) == 0 && ((strideX * (int64_t)sizeof(T)) % 16) == 0)) &&
                     (size_t)B * 2 * MG::IMG_ELEMS * sizeof(T) <= ((size_t)1 << 30);
   if (gemm) per_reg = std::max<int64_t>(1, std::min<int64_t>(((N + 15) / 16 + 4 * GG::WAVES - 1) / (4 * GG::WAVES), ((int64_t)h->cus + B - 1) / B));
-  size_t off = 0;
-  auto carve = [&](size_t bytes) { size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
+  Carve carve;
   const size_t o_T = carve((size_t)B * D * D * sizeof(T));
   const size_t o_mp = carve(mwp_d ? 0 : (size_t)B * D * sizeof(T));
   const size_t o_part = carve(dmw_d ? (size_t)B * per_reg * kPB * sizeof(double) : 0);
   const size_t o_img = carve(gemm ? (size_t)B * 2 * MG::IMG_ELEMS * sizeof(T) : 0);
-  if ((rc = h->ws.reserve(h, off, blr_handle::kWsFloor))) return rc;
+  if ((rc = h->ws.reserve(h, carve.off, blr_handle::kWsFloor))) return rc;
   T* Tf = reinterpret_cast<T*>(h->ws.p + o_T);
   int64_t smp = stride_mwpost;
   if (!mwp_d) { mwp_d = reinterpret_cast<T*>(h->ws.p + o_mp); smp = D; }
@@ -1953,7 +1780,7 @@ int logpdf_multi(blr_handle* h, int memspace, int layout, int64_t D, int64_t N, 
     GramTileArgs<T> g{};
     g.X = R; g.ldx = ldr; g.layout = layout; g.D = SP;
     g.XB = X_d; g.ldxb = ldx; g.DB = (int)D;
-    g.use_dma = (layout == BLR_LAYOUT_COLVECS && ((uintptr_t)X_d % 16 == 0) && ((ldx * (int64_t)sizeof(T)) % 16 == 0)) ? 1 : 0;
+    g.use_dma = x_ring(layout, X_d, ldx) ? 1 : 0;
     g.s = nullptr; g.noise_kind = NOISE_ISOTROPIC; g.r = nullptr;
     g.n_begin = 0; g.n_end = (int)N; g.nsplit = nsplit;
     g.tile_i0 = 0; g.tile_j0 = 0; g.tri = 3; g.ntile_rows = ntile_rows; g.ntiles = ntiles; g.nblocks = NC;
@@ -2014,12 +1841,11 @@ int sample_weights_large(blr_handle* h, int64_t D, int64_t S, int prior_kind, co
   }
   const int DP = (int)((D + kPB - 1) / kPB * kPB), NC = DP / kPB;
   const int64_t chunk = std::min<int64_t>(S, 1024);
-  size_t off = 0;
-  auto carve = [&](size_t bytes) { size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
+  Carve carve;
   const size_t o_tf = carve((size_t)DP * DP * sizeof(T));
   const size_t o_wk = carve(prior_kind == BLR_PRIOR_DENSE ? (size_t)DP * DP * sizeof(T) : 0);
   const size_t o_info = carve(64);
-  int rc = h->ws.reserve(h, off, blr_handle::kWsFloor);
+  int rc = h->ws.reserve(h, carve.off, blr_handle::kWsFloor);
   if (rc) return rc;
   char* ws = h->ws.p;
   T* Tf = reinterpret_cast<T*>(ws + o_tf);
@@ -3093,12 +2919,11 @@ int grid_small_nb(blr_handle* h, GridArgs<T> a, bool vec_ok) {
   using C = SmallCfg<T, NB>;
   constexpr int SZ = grid_stat_elems<T, NB>();
   int rc;
-  size_t off = 0;
-  auto carve = [&](size_t bytes) { size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
+  Carve carve;
   const size_t nblk = (size_t)a.B * a.S;
   const size_t o_st = carve(nblk * SZ * sizeof(T)), o_sc = carve(nblk * 2 * sizeof(double)), o_bad = carve(nblk * sizeof(int32_t));
   const size_t o_pl = carve((size_t)a.B * sizeof(double)), o_pi = carve((size_t)a.B * sizeof(int32_t)), o_best = carve((size_t)a.B * sizeof(int64_t));
-  if ((rc = h->loo_ws.reserve(h, off))) return rc;
+  if ((rc = h->loo_ws.reserve(h, carve.off))) return rc;
   char* const ws = h->loo_ws.p;
   a.stats = reinterpret_cast<T*>(ws + o_st); a.scal = reinterpret_cast<double*>(ws + o_sc); a.bad = reinterpret_cast<int32_t*>(ws + o_bad);
   a.prior_logdet = reinterpret_cast<double*>(ws + o_pl); a.prior_info = reinterpret_cast<int32_t*>(ws + o_pi);
@@ -3137,11 +2962,10 @@ int grid_large(blr_handle* h, GridArgs<T> a) {
   const int64_t B = a.B, D = a.D, N = a.N;
   const int64_t s_one = a.noise_kind == BLR_NOISE_DIAGONAL ? std::max<int64_t>(N, 1) : 1;
   const int64_t lw_one = a.prior_kind == BLR_PRIOR_DENSE ? D * D : D;
-  size_t off = 0;
-  auto carve = [&](size_t bytes) { size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
+  Carve carve;
   const size_t o_s = carve((size_t)B * s_one * sizeof(T)), o_l = carve((size_t)B * lw_one * sizeof(T));
   const size_t o_lp = carve((size_t)B * sizeof(double)), o_in = carve((size_t)B * sizeof(int32_t)), o_best = carve((size_t)B * sizeof(int64_t));
-  if ((rc = h->loo_ws.reserve(h, off))) return rc;
+  if ((rc = h->loo_ws.reserve(h, carve.off))) return rc;
   char* const ws = h->loo_ws.p;
   T* const s_g = reinterpret_cast<T*>(ws + o_s);
   T* const Lw_g = reinterpret_cast<T*>(ws + o_l);

@@ -1,4 +1,4 @@
-// Host-only state of the C ABI (blr_abi.hip includes this, nothing else does): the run-time switches, the handle, its grow-only
+// Host-only state of the C ABI (blr_abi.hip includes this; blr_large_plan.hpp for BlrOptions): the run-time switches, the handle, its grow-only
 // device buffers, and the call-scope object that stages BLR_MEM_HOST calls.  No kernel and no device code lives here.
 #pragma once
 
