@@ -91,6 +91,22 @@ int set_lds_once(blr_handle* h, const void* kern, size_t bytes) {
   return 0;
 }
 
+template <typename... Args>
+int set_lds_once(blr_handle* h, void (*kern)(Args...), size_t bytes) {  // (a kernel by its name: no cast at the call)
+  return set_lds_once(h, reinterpret_cast<const void*>(kern), bytes);
+}
+
+// Calls nested inside an entry point (device operands) must not drain the stream -- or, blr_posterior_ragged_*, must: the handle's
+// mode for the lifetime of this object, the caller's again afterwards.
+struct AsyncScope {
+  blr_handle* const h;
+  const bool was;
+  AsyncScope(blr_handle* hh, bool async) : h(hh), was(hh->async) { h->async = async; }
+  ~AsyncScope() { h->async = was; }
+  AsyncScope(const AsyncScope&) = delete;
+  AsyncScope& operator=(const AsyncScope&) = delete;
+};
+
 int bad_arg(blr_handle* h, int pos, const char* why) {
   if (h) h->err = std::string("argument ") + std::to_string(pos) + ": " + why;
   return -pos;
@@ -122,7 +138,7 @@ int launch_wave_solve(blr_handle* h, WaveSolveArgs<T>& b, int NC, int64_t S) {
   int rc = ensure_xchg(h, (size_t)S * b.DP * 2 * sizeof(unsigned long long));
   if (rc) return rc;
   b.xchg = reinterpret_cast<unsigned long long*>(h->xchg.p); b.ticket = h->ticket;  // tickets, the launch count behind the granule tags: device-side (WaveSolveArgs)
-  { const int rc_lds = set_lds_once(h, reinterpret_cast<const void*>(backsolve_wave_kernel<T>), (size_t)((int)wave_solve_lds<T>())); if (rc_lds) return rc_lds; }
+  if (const int rc_lds = set_lds_once(h, backsolve_wave_kernel<T>, (size_t)((int)wave_solve_lds<T>()))) return rc_lds;
   hipLaunchKernelGGL(backsolve_wave_kernel<T>, dim3(NC, (unsigned)S), dim3(kThreads), wave_solve_lds<T>(), h->stream, b);
   const hipError_t le = hipGetLastError();
   if (le != hipSuccess) return hip_fail(h, le, "launch of backsolve_wave_kernel");  // nothing ran: the counters did not move
@@ -150,7 +166,7 @@ int launch_fused_small(blr_handle* h, const PosteriorArgs<T>& a) {
   auto kern = fused_small_kernel<T, NB, MODE>;
   // every launch: the attribute is per DEVICE, and handles on different devices share this code (a process-wide
   // "already set" flag left the second device at the 64 KB default)
-  { const int rc_lds = set_lds_once(h, reinterpret_cast<const void*>(kern), (size_t)(C::LDS_BYTES)); if (rc_lds) return rc_lds; }
+  if (const int rc_lds = set_lds_once(h, kern, (size_t)(C::LDS_BYTES))) return rc_lds;
   int grid = (int)std::min<int64_t>(a.B, 1 << 20);
   if (a.retry_only) grid = std::min(grid, 2 * h->cus);  // (one round of workgroups, each walking its share: see the kernel's head)
   hipLaunchKernelGGL(kern, dim3(grid), dim3(kThreads), C::LDS_BYTES, h->stream, a);
@@ -180,7 +196,7 @@ int launch_fused_wave_nw(blr_handle* h, const PosteriorArgs<T>& a) {
   using C = WaveCfg<T, NB>;
   const int grid = (int)std::min<int64_t>(a.B, (int64_t)h->cus * 8 / NW);  // 8 waves per CU (18.6 KB of LDS each)
   if (NW * C::LDS_BYTES > 64 * 1024) {
-    int rc = set_lds_once(h, reinterpret_cast<const void*>(fused_wave_kernel<T, NB, NW>), (size_t)NW * C::LDS_BYTES);
+    int rc = set_lds_once(h, fused_wave_kernel<T, NB, NW>, (size_t)NW * C::LDS_BYTES);
     if (rc) return rc;
   }
   hipLaunchKernelGGL((fused_wave_kernel<T, NB, NW>), dim3(grid), dim3(64 * NW), NW * C::LDS_BYTES, h->stream, a);
@@ -238,7 +254,7 @@ int launch_fused_i8(blr_handle* h, const PosteriorArgs<double>& a) {
   if (dense) {
     const size_t np = shared_prior ? 1 : (size_t)grid;
     if ((rc = h->i8side.reserve(h, o_prior + ((np * sizeof(double) + 255) & ~(size_t)255) + np * sizeof(int32_t)))) return rc;
-    if ((rc = set_lds_once(h, reinterpret_cast<const void*>(i8_prior_logdet_kernel), kSmall8Lds))) return rc;
+    if ((rc = set_lds_once(h, i8_prior_logdet_kernel, kSmall8Lds))) return rc;
   }
   if (diag) {
     const size_t o_rw = (((size_t)grid * a.N * sizeof(double)) + 255) & ~(size_t)255;
@@ -578,8 +594,8 @@ inline int large_gram_planes(const LargeRun<float>& u) {
   const int G = u.G, NC = p.NC, NCA = p.NCA, nbchunks = p.nbchunks;
   const bool rff = p.rff;
   int rc;
-  if ((rc = set_lds_once(h, reinterpret_cast<const void*>(gram_planes_kernel<2>), (size_t)PlanesCfg<2>::LDS))) return rc;
-  if ((rc = set_lds_once(h, reinterpret_cast<const void*>(gram_planes_kernel<3>), (size_t)PlanesCfg<3>::LDS))) return rc;
+  if ((rc = set_lds_once(h, gram_planes_kernel<2>, (size_t)PlanesCfg<2>::LDS))) return rc;
+  if ((rc = set_lds_once(h, gram_planes_kernel<3>, (size_t)PlanesCfg<3>::LDS))) return rc;
   PlanesArgs pa{};
   pa.X = rff ? nullptr : u.X; pa.ldx = a.ldx;
   pa.Xin = a.rff_Xin; pa.ldxin = a.rff_ldxin; pa.Omega = a.rff_Omega; pa.ldo = a.rff_ldo; pa.phase = a.rff_phase; pa.scale = a.rff_scale; pa.Din = a.rff_Din;
@@ -627,7 +643,7 @@ inline int large_gram_planes(const LargeRun<float>& u) {
   ga.grp_ws = u.wsb; ga.grp_s = a.strides;
   const dim3 grid(p.ntiles_g * p.nsplit, G);
   if (p.planes4) {
-    if ((rc = set_lds_once(h, reinterpret_cast<const void*>(gram_planes4_kernel), (size_t)Planes4Cfg::LDS))) return rc;
+    if ((rc = set_lds_once(h, gram_planes4_kernel, (size_t)Planes4Cfg::LDS))) return rc;
     hipLaunchKernelGGL(gram_planes4_kernel, grid, dim3(kThreads), (size_t)Planes4Cfg::LDS, h->stream, ga);
   } else if (p.NP == 2) hipLaunchKernelGGL(gram_planes_kernel<2>, grid, dim3(kPlanesThreads), (size_t)PlanesCfg<2>::LDS, h->stream, ga);
   else hipLaunchKernelGGL(gram_planes_kernel<3>, grid, dim3(kPlanesThreads), (size_t)PlanesCfg<3>::LDS, h->stream, ga);
@@ -892,7 +908,7 @@ int prior_factor(blr_handle* h, int64_t B, int64_t D, int prior_kind, const T* L
   int32_t* inf = reinterpret_cast<int32_t*>(h->ws.p + (((size_t)B * D * D * sizeof(T) + 15) & ~(size_t)15));
   size_t lds = ((size_t)D * (D + 1) / 2 + D) * sizeof(T) + 16;
   auto kern = chol_small_kernel<T>;
-  { const int rc_lds = set_lds_once(h, reinterpret_cast<const void*>(kern), (size_t)((int)lds)); if (rc_lds) return rc_lds; }
+  if (const int rc_lds = set_lds_once(h, kern, (size_t)((int)lds))) return rc_lds;
   hipLaunchKernelGGL(kern, dim3((unsigned)std::min<int64_t>(B, 1 << 20)), dim3(kThreads), lds, h->stream, Lw_dev, ldl,
                      strideLw, Uw, D, D * D, inf, (int)D, (int)B);
   HIP_TRY(h, hipGetLastError());
@@ -921,15 +937,15 @@ int marginals_large_group(blr_handle* h, int layout, int64_t B, int64_t D, int64
       MB::lds_bytes(DP) > MB::kMaxLds || !vec_ok(X, ldx, strideX) || (u_given && !vec_ok(Lw, ldl, strideLw)))
     return 1;
   int rc;
-  if ((rc = set_lds_once(h, reinterpret_cast<const void*>(marg_image_kernel<T>), (size_t)TrsmCfg<T>::LDS_BYTES))) return rc;
+  if ((rc = set_lds_once(h, marg_image_kernel<T>, (size_t)TrsmCfg<T>::LDS_BYTES))) return rc;
   // Tile height: 32 inputs on eight waves, one workgroup per CU -- or, when such tiles leave CUs idle (short N), 16 inputs on four
   // waves, two workgroups per CU (twice the factor traffic per input: 1.02 against 0.77 ms at D = 1024, N = 65536, but 0.081
   // against 0.104 ms at N = 999; fp32 only: the fp64 instance does not fit the registers of two workgroups per CU)
   using MB16 = MargBlockCfg<T, 16>;
   const bool small_tiles = sizeof(T) == 4 && ((N + MB::RT - 1) / MB::RT) * B < h->cus;
-  if ((rc = set_lds_once(h, reinterpret_cast<const void*>(marg_blocksub_kernel<T, 32>), (size_t)MB::kMaxLds))) return rc;
+  if ((rc = set_lds_once(h, marg_blocksub_kernel<T, 32>, (size_t)MB::kMaxLds))) return rc;
   if constexpr (sizeof(T) == 4) {
-    if (small_tiles && (rc = set_lds_once(h, reinterpret_cast<const void*>(marg_blocksub_kernel<T, 16>), (size_t)MB16::lds_bytes(DP)))) return rc;
+    if (small_tiles && (rc = set_lds_once(h, marg_blocksub_kernel<T, 16>, (size_t)MB16::lds_bytes(DP)))) return rc;
   }
   // regressors per launch: grid.y, the images (36 / 72 KB per diagonal block) within 256 MiB, a dense prior's two D x D copies
   // within 1 GiB and chol_large's group size
@@ -1065,6 +1081,43 @@ int marginals_large_one(blr_handle* h, int layout, int64_t D, int64_t N, const T
   return 0;
 }
 
+// ---- D = 128 with a factor U (aligned ColVecs, or RowVecs): the triangular inverse once per regressor (marg_image_kernel), then a
+// dependency-free product stream with the epilogue of A at the store (marginals_gemm_kernel<T, ROWV, A>, blr_marginals.hpp).
+// A = MarginalArgs<T>: blr_marginals_batched_*; A = LooGemmArgs<T>: blr_loo_batched_*.  Regressors in chunks whose images fit 256 MiB.
+template <typename T, typename A>
+struct MargProduct {
+  using G = MargGemmCfg<T>;
+  static constexpr int64_t kMaxChunk = ((int64_t)256 << 20) / (G::IMG_ELEMS * (int64_t)sizeof(T));
+  static bool takes(const blr_handle* h, int layout, int64_t D, int64_t N, const T* X, int64_t ldx, int64_t strideX) {
+    const bool rowv = layout == BLR_LAYOUT_ROWVECS;  // (RowVecs: scalar loads, no alignment to ask for)
+    return !h->opt.no_marg_gemm && D == kPB && N >= 64 &&
+           (rowv || ((ldx % Mfma<T>::VEC) == 0 && ((uintptr_t)X % 16) == 0 && ((strideX * (int64_t)sizeof(T)) % 16) == 0));
+  }
+  static auto kernel(int layout) -> void (*)(A, const T*) {
+    return layout == BLR_LAYOUT_ROWVECS ? marginals_gemm_kernel<T, true, A> : marginals_gemm_kernel<T, false, A>;
+  }
+  // the images of `chunk` regressors in the handle's side buffer, the two kernels' LDS limits
+  static int prepare(blr_handle* h, int layout, int64_t chunk) {
+    int rc;
+    if ((rc = h->aux.reserve(h, (size_t)chunk * G::IMG_ELEMS * sizeof(T)))) return rc;
+    if ((rc = set_lds_once(h, marg_image_kernel<T>, (size_t)TrsmCfg<T>::LDS_BYTES))) return rc;
+    return set_lds_once(h, kernel(layout), (size_t)G::LDS_BYTES);
+  }
+  // regressors b0 .. b0 + nb - 1 (the kernels index regressor reg0 + blockIdx; the images of a chunk start at its first regressor)
+  static void launch(blr_handle* h, A& a, const T* U, int64_t ldu, int64_t strideU, const int32_t* info, int64_t b0, int64_t nb) {
+    T* const img = reinterpret_cast<T*>(h->aux.p) - b0 * G::IMG_ELEMS;
+    hipLaunchKernelGGL(marg_image_kernel<T>, dim3((unsigned)nb, 2), dim3(kThreads), TrsmCfg<T>::LDS_BYTES, h->stream, U, ldu, strideU, (int)a.D,
+                       img, info, (int)b0);
+    // two workgroups per CU, ONE round of them (tools/marg128_bench, 64 x 4096 inputs, stream kernel alone: 8 workgroups per
+    // regressor 104.8 us, 16 -- two rounds -- 116.3, 32: 126.9; 256 regressors: 2 per regressor); every workgroup copies the
+    // 74 KB image once: at least four tiles per wave
+    const int64_t ntiles = ((int64_t)a.N + 15) / 16;
+    const int64_t per_reg = std::max<int64_t>(1, std::min<int64_t>((ntiles + 15) / 16, (2 * (int64_t)h->cus + nb - 1) / nb));
+    a.reg0 = (int)b0;
+    hipLaunchKernelGGL(kernel(a.layout), dim3((unsigned)per_reg, (unsigned)nb), dim3(kThreads), G::LDS_BYTES, h->stream, a, (const T*)img);
+  }
+};
+
 template <typename T>
 int marginals_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t N, const T* X, int64_t ldx,
                       int64_t strideX, int noise_kind, const T* s, int64_t strides, int prior_kind, const T* mw,
@@ -1144,33 +1197,11 @@ int marginals_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_
   a.info = chol_info;
   if (chol_info) HIP_TRY(h, hipMemcpyAsync(info_out_dev, chol_info, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, h->stream));
   else HIP_TRY(h, hipMemsetAsync(info_out_dev, 0, (size_t)B * sizeof(int32_t), h->stream));
-  // D = 128 with a factor, aligned ColVecs: the triangular inverse once per regressor, then a dependency-free product
-  // (blr_marginals.hpp); regressors in chunks whose images fit 256 MiB
-  const bool rowv = layout == BLR_LAYOUT_ROWVECS;  // (RowVecs: scalar loads, no alignment to ask for)
-  if (var && kind == BLR_PRIOR_UPPER_FACTOR && !h->opt.no_marg_gemm && D == kPB && N >= 64 &&
-      (rowv || ((ldx % Mfma<T>::VEC) == 0 && ((uintptr_t)a.X % 16) == 0 && ((strideX * (int64_t)sizeof(T)) % 16) == 0))) {
-    using G = MargGemmCfg<T>;
-    using TC = TrsmCfg<T>;
-    const int64_t chunk = std::min<int64_t>(std::min<int64_t>(B, 65535), ((int64_t)256 << 20) / (G::IMG_ELEMS * (int64_t)sizeof(T)));
-    if ((rc = h->aux.reserve(h, (size_t)chunk * G::IMG_ELEMS * sizeof(T)))) return rc;
-    if ((rc = set_lds_once(h, reinterpret_cast<const void*>(marg_image_kernel<T>), (size_t)TC::LDS_BYTES))) return rc;
-    void (*const gemm_kern)(MarginalArgs<T>, const T*) = rowv ? marginals_gemm_kernel<T, true> : marginals_gemm_kernel<T, false>;
-    if ((rc = set_lds_once(h, reinterpret_cast<const void*>(gemm_kern), (size_t)G::LDS_BYTES))) return rc;
-    T* const img = reinterpret_cast<T*>(h->aux.p);
-    const int64_t ntiles = (N + 15) / 16;
-    for (int64_t b0 = 0; b0 < B; b0 += chunk) {
-      const int64_t nb = std::min<int64_t>(chunk, B - b0);
-      // (the kernels index regressor reg0 + blockIdx; the images of a chunk start at its first regressor)
-      hipLaunchKernelGGL(marg_image_kernel<T>, dim3((unsigned)nb, 2), dim3(kThreads), TC::LDS_BYTES, h->stream, a.U, a.ldu, a.strideU, (int)D,
-                         img - b0 * G::IMG_ELEMS, a.info, (int)b0);
-      // two workgroups per CU, ONE round of them (tools/marg128_bench, 64 x 4096 inputs, stream kernel alone: 8 workgroups per
-      // regressor 104.8 us, 16 -- two rounds -- 116.3, 32: 126.9; 256 regressors: 2 per regressor); every workgroup copies the
-      // 74 KB image once: at least four tiles per wave
-      const int64_t per_reg = std::max<int64_t>(1, std::min<int64_t>((ntiles + 15) / 16, (2 * (int64_t)h->cus + nb - 1) / nb));
-      a.reg0 = (int)b0;
-      hipLaunchKernelGGL(gemm_kern, dim3((unsigned)per_reg, (unsigned)nb), dim3(kThreads), G::LDS_BYTES, h->stream, a,
-                         (const T*)(img - b0 * G::IMG_ELEMS));
-    }
+  using MP = MargProduct<T, MarginalArgs<T>>;
+  if (var && kind == BLR_PRIOR_UPPER_FACTOR && MP::takes(h, layout, D, N, a.X, ldx, strideX)) {
+    const int64_t chunk = std::min<int64_t>(std::min<int64_t>(B, 65535), MP::kMaxChunk);
+    if ((rc = MP::prepare(h, layout, chunk))) return rc;
+    for (int64_t b0 = 0; b0 < B; b0 += chunk) MP::launch(h, a, a.U, a.ldu, a.strideU, a.info, b0, std::min<int64_t>(chunk, B - b0));
   } else {
     // inputs as rows of an LDS block; with a factor: Y = X'L^-T by the TRSM sweep (MFMA), fused mean / row sum of squares;
     // mean-only and diagonal-prior calls are pure streams through the same tile loop (smaller LDS image, 2 workgroups/CU)
@@ -1179,7 +1210,7 @@ int marginals_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_
     const bool use_factor = var && kind == BLR_PRIOR_UPPER_FACTOR;
     const int xs_bytes = (TC::RB * TC::LDX * (int)sizeof(T) + 15) & ~15;
     const int lds = use_factor ? TC::LDS_BYTES + kPB * (int)sizeof(T) : xs_bytes + 2 * kPB * (int)sizeof(T) + 16;
-    { const int rc_lds = set_lds_once(h, reinterpret_cast<const void*>(kern), (size_t)(TC::LDS_BYTES + kPB * (int)sizeof(T))); if (rc_lds) return rc_lds; }
+    if (const int rc_lds = set_lds_once(h, kern, (size_t)(TC::LDS_BYTES + kPB * (int)sizeof(T)))) return rc_lds;
     // every workgroup amortises its set-up over several tiles: aim at ~2 rounds of the chip
     const int64_t ntiles = (N + TC::RB - 1) / TC::RB;
     const int64_t slots = use_factor ? 512 : 1024;
@@ -1588,9 +1619,9 @@ int logpdf_grad_batched(blr_handle* h, int memspace, int layout, int64_t B, int6
   g.dmw_part = part; g.Ainv = Ai_d; g.ldai = ldai; g.strideAi = strideAi; g.info = info_d;
   g.layout = layout; g.noise_kind = noise_kind; g.D = (int)D; g.N = (int)N; g.B = (int)B;
   if (gemm) {
-    if ((rc = set_lds_once(h, reinterpret_cast<const void*>(marg_image_kernel<T>), (size_t)TC::LDS_BYTES))) return rc;
+    if ((rc = set_lds_once(h, marg_image_kernel<T>, (size_t)TC::LDS_BYTES))) return rc;
     void (*const gg_kern)(GradArgs<T>, const T*, const T*) = rowv ? grad_gemm_kernel<T, true> : grad_gemm_kernel<T, false>;
-    if ((rc = set_lds_once(h, reinterpret_cast<const void*>(gg_kern), (size_t)GG::LDS_BYTES))) return rc;
+    if ((rc = set_lds_once(h, gg_kern, (size_t)GG::LDS_BYTES))) return rc;
     T* const img = reinterpret_cast<T*>(h->ws.p + o_img);
     T* const img2 = img + B * MG::IMG_ELEMS;
     hipLaunchKernelGGL(marg_image_kernel<T>, dim3((unsigned)B, 2), dim3(kThreads), TC::LDS_BYTES, h->stream, (const T*)Tf, D, D * D, (int)D, img,
@@ -1604,7 +1635,7 @@ int logpdf_grad_batched(blr_handle* h, int memspace, int layout, int64_t B, int6
   } else {
     auto kern = logpdf_grad_kernel<T>;
     const int lds = TC::LDS_BYTES + (kPB + 3 * TC::RB) * (int)sizeof(T);
-    { const int rc_lds = set_lds_once(h, reinterpret_cast<const void*>(kern), (size_t)(lds)); if (rc_lds) return rc_lds; }
+    if (const int rc_lds = set_lds_once(h, kern, (size_t)(lds))) return rc_lds;
     for (int64_t b0 = 0; b0 < B; b0 += 65535) {  // grid.y <= 65535
       g.reg0 = (int)b0;
       hipLaunchKernelGGL(kern, dim3((unsigned)per_reg, (unsigned)std::min<int64_t>(65535, B - b0)), dim3(kThreads), lds, h->stream, g);
@@ -1760,11 +1791,9 @@ int logpdf_multi(blr_handle* h, int memspace, int layout, int64_t D, int64_t N, 
   }
   // (2) mu_n = x_n'mw: the mean-only marginal stream
   {
-    const bool was_async = h->async;
-    h->async = true;
+    const AsyncScope no_drain(h, true);
     rc = marginals_batched<T>(h, BLR_MEM_DEVICE, layout, 1, D, N, X_d, ldx, 0, noise_kind, s_d, 0, BLR_PRIOR_DIAGONAL, mw_d, 0,
                               nullptr, 1, 0, mu, N, nullptr, N, info2);
-    h->async = was_async;
     if (rc) return rc;
   }
   // (3) residuals R = S (Y - mu 1') in X's layout, q partials
@@ -1916,7 +1945,7 @@ int sample_weights_impl(blr_handle* h, CallIO& io, int64_t D, int64_t S, int pri
     using TC = TrsmCfg<T>;
     const int lds = TC::LDS_BYTES + kPB * (int)sizeof(T);
     auto kern = sample_weights_mfma_kernel<T>;
-    { const int rc_lds = set_lds_once(h, reinterpret_cast<const void*>(kern), (size_t)(lds)); if (rc_lds) return rc_lds; }
+    if (const int rc_lds = set_lds_once(h, kern, (size_t)(lds))) return rc_lds;
     const int64_t ntiles = (S + TC::RB - 1) / TC::RB;
     hipLaunchKernelGGL(kern, dim3((unsigned)std::min<int64_t>(ntiles, 512)), dim3(kThreads), lds, h->stream, mw_d, U, ldu, Z_d, ldz,
                        W_d, ldw, (int)D, S);
@@ -2586,7 +2615,51 @@ int rand_dense_noise(blr_handle* h, int memspace, int layout, int64_t D, int64_t
   return hinfo;
 }
 
-// ---- rank-k update of a resident state (blr_update.hpp) ---------------------------------------------------------------
+// ---- rank-k update / downdate of a resident state (blr_update.hpp, blr_downdate.hpp) -----------------------------------------
+// What blr_update_factor_* (on its sweep route) and blr_downdate_factor_* share behind their own checks of the shape: the checks
+// of the operands (positions 7 .. 21; `noise_msg`: the entry point's words for a noise kind it does not take), the device and
+// the kernels' argument record ...
+template <typename T>
+int sweep_begin(blr_handle* h, SweepArgs<T>& a, int layout, int64_t B, int64_t D, int64_t k, const T* X, int64_t ldx, int64_t strideX,
+                const T* y, int64_t stridey, int noise_kind, const char* noise_msg, const T* s, int64_t strides, T* mw, int64_t stridemw,
+                T* Tf, int64_t ldt, int64_t strideT, int32_t* info) {
+  if (k > 0 && !X) return bad_arg(h, 7, "X is NULL");
+  if (layout == BLR_LAYOUT_COLVECS ? ldx < D : ldx < std::max<int64_t>(k, 1)) return bad_arg(h, 8, "ldx too small");
+  if (strideX < 0) return bad_arg(h, 9, "strideX < 0");
+  if (k > 0 && !y) return bad_arg(h, 10, "y is NULL (reference :74 length check)");
+  if (stridey < 0) return bad_arg(h, 11, "stridey < 0");
+  if (noise_kind != BLR_NOISE_ISOTROPIC && noise_kind != BLR_NOISE_DIAGONAL) return bad_arg(h, 12, noise_msg);
+  if (!s) return bad_arg(h, 13, "s is NULL");
+  if (strides < 0) return bad_arg(h, 14, "strides < 0");
+  if (!mw) return bad_arg(h, 15, "mw is NULL");
+  if (B > 1 && stridemw < D) return bad_arg(h, 16, "stridemw < D");
+  if (!Tf) return bad_arg(h, 17, "T is NULL");
+  if (ldt < D) return bad_arg(h, 18, "ldt < D");
+  if (B > 1 && strideT < (int64_t)mat_extent(D, D, ldt)) return bad_arg(h, 19, "strideT too small");
+  if (!info) return bad_arg(h, 21, "info is NULL");
+  HIP_TRY(h, hipSetDevice(h->device));
+  a.ldx = ldx; a.strideX = strideX; a.layout = layout; a.stridey = stridey; a.strides = strides; a.noise_kind = noise_kind;
+  a.stridemw = stridemw; a.ldt = ldt; a.strideT = strideT; a.D = (int)D; a.k = (int)k;
+  return 0;
+}
+// ... and the operands staged through `io` (the state is updated in place), with the k = 0 pointer fix-up
+template <typename T>
+int sweep_stage(CallIO& io, SweepArgs<T>& a, int64_t B, const T* X, const T* y, const T* s, T* mw, T* Tf, double* logpdf, int32_t* info) {
+  const int64_t D = a.D, k = a.k;
+  const size_t x_one = a.layout == BLR_LAYOUT_COLVECS ? mat_extent(D, k, a.ldx) : mat_extent(k, D, a.ldx);
+  const size_t s_one = a.noise_kind == BLR_NOISE_DIAGONAL ? (size_t)k : 1;
+  int rc;
+  if ((rc = io.in(X, extent(B, a.strideX, x_one), &a.X))) return rc;
+  if ((rc = io.in(y, extent(B, a.stridey, (size_t)k), &a.y))) return rc;
+  if ((rc = io.in(s, extent(B, a.strides, s_one), &a.s))) return rc;
+  if ((rc = io.out(mw, extent(B, a.stridemw, (size_t)D), &a.mw))) return rc;
+  if ((rc = io.out(Tf, extent(B, a.strideT, mat_extent(D, D, a.ldt)), &a.Tf))) return rc;
+  if ((rc = io.out(logpdf, (size_t)B, &a.logpdf))) return rc;
+  if ((rc = io.out(info, (size_t)B, &a.info))) return rc;
+  if (k == 0) { if (!a.X) a.X = a.mw; if (!a.y) a.y = a.mw; }
+  return 0;
+}
+
 template <typename T>
 int update_factor(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t k, const T* X, int64_t ldx,
                   int64_t strideX, const T* y, int64_t stridey, int noise_kind, const T* s, int64_t strides, T* mw,
@@ -2618,38 +2691,14 @@ int update_factor(blr_handle* h, int memspace, int layout, int64_t B, int64_t D,
   if (layout != BLR_LAYOUT_COLVECS && layout != BLR_LAYOUT_ROWVECS) return bad_arg(h, 3, "unknown layout (reference :26-31)");
   if (B < 0 || B > (1 << 30)) return bad_arg(h, 4, "B out of range (0..2^30)");
   if (B == 0) return 0;
-  if (k > 0 && !X) return bad_arg(h, 7, "X is NULL");
-  if (layout == BLR_LAYOUT_COLVECS ? ldx < D : ldx < std::max<int64_t>(k, 1)) return bad_arg(h, 8, "ldx too small");
-  if (strideX < 0) return bad_arg(h, 9, "strideX < 0");
-  if (k > 0 && !y) return bad_arg(h, 10, "y is NULL (reference :74 length check)");
-  if (stridey < 0) return bad_arg(h, 11, "stridey < 0");
-  if (noise_kind != BLR_NOISE_ISOTROPIC && noise_kind != BLR_NOISE_DIAGONAL) return bad_arg(h, 12, "noise_kind");
-  if (!s) return bad_arg(h, 13, "s is NULL");
-  if (strides < 0) return bad_arg(h, 14, "strides < 0");
-  if (!mw) return bad_arg(h, 15, "mw is NULL");
-  if (B > 1 && stridemw < D) return bad_arg(h, 16, "stridemw < D");
-  if (!Tf) return bad_arg(h, 17, "T is NULL");
-  if (ldt < D) return bad_arg(h, 18, "ldt < D");
-  if (B > 1 && strideT < (int64_t)mat_extent(D, D, ldt)) return bad_arg(h, 19, "strideT too small");
-  if (!info) return bad_arg(h, 21, "info is NULL");
-  HIP_TRY(h, hipSetDevice(h->device));
   SweepArgs<T> a{};
-  a.ldx = ldx; a.strideX = strideX; a.layout = layout; a.stridey = stridey; a.strides = strides; a.noise_kind = noise_kind;
-  a.stridemw = stridemw; a.ldt = ldt; a.strideT = strideT; a.D = (int)D; a.k = (int)k;
+  int rc = sweep_begin<T>(h, a, layout, B, D, k, X, ldx, strideX, y, stridey, noise_kind, "noise_kind", s, strides, mw, stridemw, Tf, ldt,
+                          strideT, info);
+  if (rc) return rc;
   const int lds = sweep_lds_bytes<T>((int)D);
-  { const int rc_lds = set_lds_once(h, reinterpret_cast<const void*>(rank1_sweep_kernel<T>), (size_t)(lds)); if (rc_lds) return rc_lds; }
+  if ((rc = set_lds_once(h, rank1_sweep_kernel<T>, (size_t)(lds)))) return rc;
   CallIO io(h, memspace);
-  const size_t x_one = layout == BLR_LAYOUT_COLVECS ? mat_extent(D, k, ldx) : mat_extent(k, D, ldx);
-  const size_t s_one = noise_kind == BLR_NOISE_DIAGONAL ? (size_t)k : 1;
-  int rc;
-  if ((rc = io.in(X, extent(B, strideX, x_one), &a.X))) return rc;
-  if ((rc = io.in(y, extent(B, stridey, (size_t)k), &a.y))) return rc;
-  if ((rc = io.in(s, extent(B, strides, s_one), &a.s))) return rc;
-  if ((rc = io.out(mw, extent(B, stridemw, (size_t)D), &a.mw))) return rc;  // (updated in place)
-  if ((rc = io.out(Tf, extent(B, strideT, mat_extent(D, D, ldt)), &a.Tf))) return rc;
-  if ((rc = io.out(logpdf, (size_t)B, &a.logpdf))) return rc;
-  if ((rc = io.out(info, (size_t)B, &a.info))) return rc;
-  if (k == 0) { if (!a.X) a.X = a.mw; if (!a.y) a.y = a.mw; }
+  if ((rc = sweep_stage<T>(io, a, B, X, y, s, mw, Tf, logpdf, info))) return rc;
   hipLaunchKernelGGL(rank1_sweep_kernel<T>, dim3((unsigned)B), dim3(kThreads), lds, h->stream, a);
   HIP_TRY(h, hipGetLastError());
   return io.finish();
@@ -2663,7 +2712,7 @@ int downdate_launch(blr_handle* h, const SweepArgs<T>& a0, int64_t B) {
   const int D = a0.D;
   if (D <= kDowndateLdsMaxD && !h->opt.no_downdate_lds) {
     const int lds = downdate_lds_bytes<T>(D);
-    { const int rc_lds = set_lds_once(h, reinterpret_cast<const void*>(downdate_lds_kernel<T>), (size_t)lds); if (rc_lds) return rc_lds; }
+    if (const int rc_lds = set_lds_once(h, downdate_lds_kernel<T>, (size_t)lds)) return rc_lds;
     hipLaunchKernelGGL(downdate_lds_kernel<T>, dim3((unsigned)B), dim3(kThreads), lds, h->stream, a0);
     HIP_TRY(h, hipGetLastError());
     return 0;
@@ -2687,8 +2736,8 @@ int downdate_launch(blr_handle* h, const SweepArgs<T>& a0, int64_t B) {
   w.st = reinterpret_cast<int*>(base + off_st);
   const int nt = (D + kDdTile - 1) / kDdTile;
   const int solve_lds = downdate_g_solve_lds<T>(D), finish_lds = downdate_g_finish_lds<T>(D);
-  { const int rc_lds = set_lds_once(h, reinterpret_cast<const void*>(downdate_g_solve_kernel<T>), (size_t)solve_lds); if (rc_lds) return rc_lds; }
-  { const int rc_lds = set_lds_once(h, reinterpret_cast<const void*>(downdate_g_finish_kernel<T>), (size_t)finish_lds); if (rc_lds) return rc_lds; }
+  if (const int rc_lds = set_lds_once(h, downdate_g_solve_kernel<T>, (size_t)solve_lds)) return rc_lds;
+  if (const int rc_lds = set_lds_once(h, downdate_g_finish_kernel<T>, (size_t)finish_lds)) return rc_lds;
   for (int64_t b0 = 0; b0 < B; b0 += chunk) {
     const unsigned nb = (unsigned)std::min<int64_t>(chunk, B - b0);
     SweepArgs<T> a = a0;
@@ -2721,36 +2770,12 @@ int downdate_factor(blr_handle* h, int memspace, int layout, int64_t B, int64_t 
   if (D < 1 || D > 8192) return bad_arg(h, 5, "D out of range (1..8192)");
   if (k < 0 || k > (1 << 30)) return bad_arg(h, 6, "k out of range (0..2^30)");
   if (B == 0) return 0;
-  if (k > 0 && !X) return bad_arg(h, 7, "X is NULL");
-  if (layout == BLR_LAYOUT_COLVECS ? ldx < D : ldx < std::max<int64_t>(k, 1)) return bad_arg(h, 8, "ldx too small");
-  if (strideX < 0) return bad_arg(h, 9, "strideX < 0");
-  if (k > 0 && !y) return bad_arg(h, 10, "y is NULL (reference :74 length check)");
-  if (stridey < 0) return bad_arg(h, 11, "stridey < 0");
-  if (noise_kind != BLR_NOISE_ISOTROPIC && noise_kind != BLR_NOISE_DIAGONAL) return bad_arg(h, 12, "noise_kind (dense noise is not downdated)");
-  if (!s) return bad_arg(h, 13, "s is NULL");
-  if (strides < 0) return bad_arg(h, 14, "strides < 0");
-  if (!mw) return bad_arg(h, 15, "mw is NULL");
-  if (B > 1 && stridemw < D) return bad_arg(h, 16, "stridemw < D");
-  if (!Tf) return bad_arg(h, 17, "T is NULL");
-  if (ldt < D) return bad_arg(h, 18, "ldt < D");
-  if (B > 1 && strideT < (int64_t)mat_extent(D, D, ldt)) return bad_arg(h, 19, "strideT too small");
-  if (!info) return bad_arg(h, 21, "info is NULL");
-  HIP_TRY(h, hipSetDevice(h->device));
   SweepArgs<T> a{};
-  a.ldx = ldx; a.strideX = strideX; a.layout = layout; a.stridey = stridey; a.strides = strides; a.noise_kind = noise_kind;
-  a.stridemw = stridemw; a.ldt = ldt; a.strideT = strideT; a.D = (int)D; a.k = (int)k;
+  int rc = sweep_begin<T>(h, a, layout, B, D, k, X, ldx, strideX, y, stridey, noise_kind, "noise_kind (dense noise is not downdated)", s,
+                          strides, mw, stridemw, Tf, ldt, strideT, info);
+  if (rc) return rc;
   CallIO io(h, memspace);
-  const size_t x_one = layout == BLR_LAYOUT_COLVECS ? mat_extent(D, k, ldx) : mat_extent(k, D, ldx);
-  const size_t s_one = noise_kind == BLR_NOISE_DIAGONAL ? (size_t)k : 1;
-  int rc;
-  if ((rc = io.in(X, extent(B, strideX, x_one), &a.X))) return rc;
-  if ((rc = io.in(y, extent(B, stridey, (size_t)k), &a.y))) return rc;
-  if ((rc = io.in(s, extent(B, strides, s_one), &a.s))) return rc;
-  if ((rc = io.out(mw, extent(B, stridemw, (size_t)D), &a.mw))) return rc;  // (updated in place)
-  if ((rc = io.out(Tf, extent(B, strideT, mat_extent(D, D, ldt)), &a.Tf))) return rc;
-  if ((rc = io.out(logpdf, (size_t)B, &a.logpdf))) return rc;
-  if ((rc = io.out(info, (size_t)B, &a.info))) return rc;
-  if (k == 0) { if (!a.X) a.X = a.mw; if (!a.y) a.y = a.mw; }
+  if ((rc = sweep_stage<T>(io, a, B, X, y, s, mw, Tf, logpdf, info))) return rc;
   if ((rc = downdate_launch<T>(h, a, B))) return rc;
   return io.finish();
 }
@@ -2762,8 +2787,7 @@ constexpr size_t kLooWorkspace = (size_t)256 << 20;  // bound of the per-chunk i
 template <typename T>
 int loo_launch(blr_handle* h, int layout, int64_t B, int64_t D, int64_t N, const T* X, int64_t ldx, int64_t strideX, LooArgs<T> l,
                const T* mw, int64_t stridemw, const T* Tf, int64_t ldt, int64_t strideT, double* total) {
-  using G = MargGemmCfg<T>;
-  using TC = TrsmCfg<T>;
+  using MP = MargProduct<T, LooGemmArgs<T>>;
   int rc;
   if ((rc = ensure_stats(h))) return rc;
   l.degenerate = h->stats_dev + 3;
@@ -2773,56 +2797,41 @@ int loo_launch(blr_handle* h, int layout, int64_t B, int64_t D, int64_t N, const
                        ldt, strideT, (int)D, l.s + b0 * l.strides, l.strides, l.noise_kind, (int)N, info + b0);
   HIP_TRY(h, hipGetLastError());
   // the route follows from the shape, as the marginals' does: the fused product stream at D = 128
-  const bool rowv = layout == BLR_LAYOUT_ROWVECS;
-  const bool fused = N >= 64 && D == kPB && !h->opt.no_marg_gemm &&
-                     (rowv || ((ldx % Mfma<T>::VEC) == 0 && ((uintptr_t)X % 16) == 0 && ((strideX * (int64_t)sizeof(T)) % 16) == 0));
+  const bool fused = MP::takes(h, layout, D, N, X, ldx, strideX);
   const bool ll_ws = total && !l.ll;  // the totals need the log densities somewhere
   const size_t item = sizeof(T), row = ((size_t)N * item + 255) & ~(size_t)255, row_ll = ((size_t)N * sizeof(double) + 255) & ~(size_t)255;
   const size_t per = (fused ? 0 : 2 * row) + (ll_ws ? row_ll : 0) + sizeof(int32_t);
   int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(B, 65535), (int64_t)(kLooWorkspace / per)));
-  if (fused) chunk = std::min<int64_t>(chunk, ((int64_t)256 << 20) / (G::IMG_ELEMS * (int64_t)sizeof(T)));
+  if (fused) chunk = std::min<int64_t>(chunk, MP::kMaxChunk);
   const size_t off_var = (size_t)chunk * row, off_ll = fused ? 0 : 2 * (size_t)chunk * row;
   const size_t off_zero = off_ll + (ll_ws ? (size_t)chunk * row_ll : 0), off_inf = off_zero + 256;
   if (N > 0 && (rc = h->loo_ws.reserve(h, off_inf + (size_t)chunk * sizeof(int32_t) + 256))) return rc;
   char* const ws = h->loo_ws.p;
   const int64_t ldw = (int64_t)(row / item);
   if (N > 0 && !fused) HIP_TRY(h, hipMemsetAsync(ws + off_zero, 0, sizeof(T), h->stream));  // the composed route's zero noise
-  if (N > 0 && fused) {
-    if ((rc = h->aux.reserve(h, (size_t)chunk * G::IMG_ELEMS * sizeof(T)))) return rc;
-    if ((rc = set_lds_once(h, reinterpret_cast<const void*>(marg_image_kernel<T>), (size_t)TC::LDS_BYTES))) return rc;
-    void (*const kern)(LooGemmArgs<T>, const T*) = rowv ? marginals_gemm_kernel<T, true, LooGemmArgs<T>> : marginals_gemm_kernel<T, false, LooGemmArgs<T>>;
-    if ((rc = set_lds_once(h, reinterpret_cast<const void*>(kern), (size_t)G::LDS_BYTES))) return rc;
-  }
-  T* const img = reinterpret_cast<T*>(h->aux.p);
+  if (N > 0 && fused && (rc = MP::prepare(h, layout, chunk))) return rc;
   const int64_t ldll = ll_ws ? (int64_t)(row_ll / sizeof(double)) : l.stride_ll;
   for (int64_t b0 = 0; N > 0 && b0 < B; b0 += chunk) {
     const int64_t nb = std::min<int64_t>(chunk, B - b0);
     LooArgs<T> lc = l;
     if (ll_ws) { lc.ll = reinterpret_cast<double*>(ws + off_ll) - b0 * ldll; lc.stride_ll = ldll; }  // (indexed by the global regressor)
     if (fused) {
-      // M = T^-T once per regressor, then the product stream with the epilogue at the store (blr_marginals.hpp)
-      hipLaunchKernelGGL(marg_image_kernel<T>, dim3((unsigned)nb, 2), dim3(kThreads), TC::LDS_BYTES, h->stream, Tf, ldt, strideT, (int)D,
-                         img - b0 * G::IMG_ELEMS, l.info, (int)b0);
       LooGemmArgs<T> a{};
       a.X = X; a.ldx = ldx; a.strideX = strideX; a.s = l.s; a.strides = l.strides; a.mw = mw; a.stridemw = stridemw;
       a.info = l.info; a.layout = layout; a.noise_kind = l.noise_kind; a.prior_kind = BLR_PRIOR_UPPER_FACTOR;
-      a.D = (int)D; a.N = (int)N; a.B = (int)B; a.reg0 = (int)b0;
-      const int64_t ntiles = (N + 15) / 16;
-      const int64_t per_reg = std::max<int64_t>(1, std::min<int64_t>((ntiles + 15) / 16, (2 * (int64_t)h->cus + nb - 1) / nb));
+      a.D = (int)D; a.N = (int)N; a.B = (int)B;
       a.l = lc;
-      void (*const kern)(LooGemmArgs<T>, const T*) = rowv ? marginals_gemm_kernel<T, true, LooGemmArgs<T>> : marginals_gemm_kernel<T, false, LooGemmArgs<T>>;
-      hipLaunchKernelGGL(kern, dim3((unsigned)per_reg, (unsigned)nb), dim3(kThreads), G::LDS_BYTES, h->stream, a,
-                         (const T*)(img - b0 * G::IMG_ELEMS));
+      MP::launch(h, a, Tf, ldt, strideT, l.info, b0, nb);
     } else {
       // mean and LATENT variance (zero noise) by whichever marginal route the shape takes, then the epilogue
       T* const mean = reinterpret_cast<T*>(ws);
       T* const var = reinterpret_cast<T*>(ws + off_var);
-      const bool was_async = h->async;
-      h->async = true;  // (no drain between the two halves)
-      rc = marginals_batched<T>(h, BLR_MEM_DEVICE, layout, nb, D, N, X + b0 * strideX, ldx, strideX, BLR_NOISE_ISOTROPIC,
-                                reinterpret_cast<const T*>(ws + off_zero), 0, BLR_PRIOR_UPPER_FACTOR, mw + b0 * stridemw, stridemw,
-                                Tf + b0 * strideT, ldt, strideT, mean, ldw, var, ldw, reinterpret_cast<int32_t*>(ws + off_inf));
-      h->async = was_async;
+      {
+        const AsyncScope no_drain(h, true);  // (between the two halves)
+        rc = marginals_batched<T>(h, BLR_MEM_DEVICE, layout, nb, D, N, X + b0 * strideX, ldx, strideX, BLR_NOISE_ISOTROPIC,
+                                  reinterpret_cast<const T*>(ws + off_zero), 0, BLR_PRIOR_UPPER_FACTOR, mw + b0 * stridemw, stridemw,
+                                  Tf + b0 * strideT, ldt, strideT, mean, ldw, var, ldw, reinterpret_cast<int32_t*>(ws + off_inf));
+      }
       if (rc) return rc;
       h->err.clear();
       const int64_t gx = std::max<int64_t>(1, std::min<int64_t>((N + kThreads - 1) / kThreads, (4 * (int64_t)h->cus + nb - 1) / nb));
@@ -2907,7 +2916,7 @@ template <typename T, int NB, int MODE>
 int launch_grid_stats(blr_handle* h, const GridArgs<T>& a) {
   using C = SmallCfg<T, NB>;
   auto kern = grid_stats_kernel<T, NB, MODE>;
-  { const int rc = set_lds_once(h, reinterpret_cast<const void*>(kern), (size_t)C::LDS_BYTES); if (rc) return rc; }
+  if (const int rc_lds = set_lds_once(h, kern, (size_t)C::LDS_BYTES)) return rc_lds;
   hipLaunchKernelGGL(kern, dim3((unsigned)((int64_t)a.B * a.S)), dim3(kThreads), C::LDS_BYTES, h->stream, a);
   HIP_TRY(h, hipGetLastError());
   return 0;
@@ -2928,8 +2937,8 @@ int grid_small_nb(blr_handle* h, GridArgs<T> a, bool vec_ok) {
   a.stats = reinterpret_cast<T*>(ws + o_st); a.scal = reinterpret_cast<double*>(ws + o_sc); a.bad = reinterpret_cast<int32_t*>(ws + o_bad);
   a.prior_logdet = reinterpret_cast<double*>(ws + o_pl); a.prior_info = reinterpret_cast<int32_t*>(ws + o_pi);
   a.best = reinterpret_cast<int64_t*>(ws + o_best);
-  if ((rc = set_lds_once(h, reinterpret_cast<const void*>(grid_prior_kernel<T, NB>), (size_t)C::LDS_BYTES))) return rc;
-  if ((rc = set_lds_once(h, reinterpret_cast<const void*>(grid_eval_kernel<T, NB>), (size_t)C::LDS_BYTES))) return rc;
+  if ((rc = set_lds_once(h, grid_prior_kernel<T, NB>, (size_t)C::LDS_BYTES))) return rc;
+  if ((rc = set_lds_once(h, grid_eval_kernel<T, NB>, (size_t)C::LDS_BYTES))) return rc;
   hipLaunchKernelGGL(HIP_KERNEL_NAME(grid_prior_kernel<T, NB>), dim3((unsigned)a.B), dim3(kThreads), C::LDS_BYTES, h->stream, a);
   HIP_TRY(h, hipGetLastError());  // (every launch is checked before the ones that read its output are enqueued)
   if (a.layout == BLR_LAYOUT_ROWVECS) rc = launch_grid_stats<T, NB, 1>(h, a);
@@ -2972,7 +2981,6 @@ int grid_large(blr_handle* h, GridArgs<T> a) {
   double* const lp_g = reinterpret_cast<double*>(ws + o_lp);
   int32_t* const in_g = reinterpret_cast<int32_t*>(ws + o_in);
   a.best = reinterpret_cast<int64_t*>(ws + o_best);
-  const bool was_async = h->async;
   const int64_t ldl_g = a.prior_kind == BLR_PRIOR_DENSE ? D : 0;
   for (int g = 0; g < a.G; ++g) {
     for (int64_t b0 = 0; b0 < B; b0 += 65535) {
@@ -2981,11 +2989,12 @@ int grid_large(blr_handle* h, GridArgs<T> a) {
                          Lw_g + b0 * lw_one, lw_one);
     }
     HIP_TRY(h, hipGetLastError());
-    h->async = true;
-    rc = posterior_batched<T>(h, BLR_MEM_DEVICE, a.layout, B, D, N, a.X, a.ldx, a.strideX, a.y, a.stridey, a.noise_kind, s_g, s_one,
-                              a.prior_kind, a.mw, a.stridemw, Lw_g, ldl_g, lw_one, (T*)nullptr, 0, (T*)nullptr, 0, 0, (T*)nullptr, 0, 0,
-                              lp_g, in_g);
-    h->async = was_async;
+    {
+      const AsyncScope no_drain(h, true);
+      rc = posterior_batched<T>(h, BLR_MEM_DEVICE, a.layout, B, D, N, a.X, a.ldx, a.strideX, a.y, a.stridey, a.noise_kind, s_g, s_one,
+                                a.prior_kind, a.mw, a.stridemw, Lw_g, ldl_g, lw_one, (T*)nullptr, 0, (T*)nullptr, 0, 0, (T*)nullptr, 0, 0,
+                                lp_g, in_g);
+    }
     if (rc) return rc;
     hipLaunchKernelGGL(grid_scatter_kernel, dim3((unsigned)((B + kThreads - 1) / kThreads)), dim3(kThreads), 0, h->stream,
                        (const double*)lp_g, (const int32_t*)in_g, (int)B, g, a.logpdf, a.stride_lp, a.info, a.stride_info);
@@ -3000,12 +3009,11 @@ int grid_large(blr_handle* h, GridArgs<T> a) {
     for (int64_t b = 0; b < B; ++b) {
       if (best[(size_t)b] < 0) continue;  // nothing succeeded: mw_best / T_best stay as they are
       hipLaunchKernelGGL(grid_scale_kernel<T>, dim3(64, 1), dim3(kThreads), 0, h->stream, a, b, (int)best[(size_t)b], s_g, s_one, Lw_g, lw_one);
-      h->async = true;
+      const AsyncScope no_drain(h, true);
       rc = posterior_batched<T>(h, BLR_MEM_DEVICE, a.layout, 1, D, N, a.X + b * a.strideX, a.ldx, 0, a.y + b * a.stridey, 0, a.noise_kind,
                                 s_g, 0, a.prior_kind, a.mw + b * a.stridemw, 0, Lw_g, ldl_g, 0,
                                 a.mw_best ? a.mw_best + b * a.stride_mwbest : (T*)nullptr, 0, a.T_best ? a.T_best + b * a.strideT : (T*)nullptr,
                                 a.ldt, 0, (T*)nullptr, 0, 0, lp_g, in_g);
-      h->async = was_async;
       if (rc) return rc;
     }
   }
@@ -3218,17 +3226,17 @@ int posterior_ragged(blr_handle* h, int memspace, int layout, int64_t B, int64_t
     return io.finish();
   }
   // D > 128: correct, not fast -- one regressor after the other through the pipeline of blr_posterior_batched_*; the call synchronises
-  const bool was_async = h->async;
-  h->async = false;
-  for (int64_t b = 0; b < B && rc == 0; ++b) {
-    const int64_t o = offsets[b], n = offsets[b + 1] - o;
-    rc = posterior_batched<T>(h, BLR_MEM_DEVICE, layout, 1, D, n, a.X + (layout == BLR_LAYOUT_COLVECS ? o * ldx : o), ldx, 0, a.y + o, 0,
-                              noise_kind, diag ? a.s + o : a.s + b * strides, 0, prior_kind, a.mw + b * stridemw, 0, a.Lw + b * strideLw,
-                              ldl, 0, a.mw_post ? a.mw_post + b * stride_mwpost : (T*)nullptr, 0, a.T_post ? a.T_post + b * strideT : (T*)nullptr,
-                              ldt, 0, a.Lw_post ? a.Lw_post + b * strideLp : (T*)nullptr, ldlp, 0, a.logpdf ? a.logpdf + b : (double*)nullptr,
-                              a.info + b);
+  {
+    const AsyncScope drain(h, false);
+    for (int64_t b = 0; b < B && rc == 0; ++b) {
+      const int64_t o = offsets[b], n = offsets[b + 1] - o;
+      rc = posterior_batched<T>(h, BLR_MEM_DEVICE, layout, 1, D, n, a.X + (layout == BLR_LAYOUT_COLVECS ? o * ldx : o), ldx, 0, a.y + o, 0,
+                                noise_kind, diag ? a.s + o : a.s + b * strides, 0, prior_kind, a.mw + b * stridemw, 0, a.Lw + b * strideLw,
+                                ldl, 0, a.mw_post ? a.mw_post + b * stride_mwpost : (T*)nullptr, 0, a.T_post ? a.T_post + b * strideT : (T*)nullptr,
+                                ldt, 0, a.Lw_post ? a.Lw_post + b * strideLp : (T*)nullptr, ldlp, 0, a.logpdf ? a.logpdf + b : (double*)nullptr,
+                                a.info + b);
+    }
   }
-  h->async = was_async;
   if (rc) return rc;  // (device pointers and in-range sizes: a HIP failure, not an argument index of the inner call)
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   return io.finish();
