@@ -363,8 +363,6 @@ int dispatch_fused_small(blr_handle* h, const PosteriorArgs<T>& a) {
 
 // ---- large-D path (D > 128): multi-kernel pipeline of blr_large.hpp ---------------------------------------------
 constexpr int kChainBatchMaxWords = 128;  // = kChainBatchMax below
-template <typename T>
-int set_lds(blr_handle* h, const void* kern, size_t bytes) { return set_lds_once(h, kern, bytes); }
 
 // In-place blocked (128) right-looking Cholesky of the lower triangle of M (nrows_total x DP, ld); rows beyond DP
 // (the right-hand-side block of the augmented matrix) are carried through the TRSM and the trailing updates.
@@ -374,7 +372,7 @@ int launch_panel(blr_handle* h, T* M, int64_t ld, int p, int nrows_total, int nb
   constexpr int NW = BLR_PANEL_WAVES;
   using CC = ChainCfg<T, NW, ER>;
   int rc;
-  if ((rc = set_lds<T>(h, reinterpret_cast<const void*>(panel_chain_kernel<T, NW, ER>), CC::LDS_BYTES))) return rc;
+  if ((rc = set_lds_once(h, panel_chain_kernel<T, NW, ER>, (size_t)CC::LDS_BYTES))) return rc;
   const int nwg = std::max(1, (nbelow + ER - 1) / ER);
   // arrival counters (one per factorisation of the launch): count up to nwg during the launch.  Two banks, used alternately
   // by the launches of this handle (= of its stream, in order); a launch clears the bank of its successor (blr_panel.hpp).
@@ -403,7 +401,7 @@ int chol_large(blr_handle* h, T* M, int64_t ld, int DP, int nrows_total, int32_t
   int rc;
   if (G < 1 || G > kChainBatchMax) return hip_fail(h, hipErrorInvalidValue, "chol_large: too many factorisations per launch");
   if ((rc = ensure_xchg(h, 0))) return rc;  // the handle's counter words (ticket[16 + g]: arrivals of panel_chain_kernel)
-  if ((rc = set_lds<T>(h, reinterpret_cast<const void*>(trail_update_kernel<T>), TrailCfg<T>::LDS_BYTES))) return rc;
+  if ((rc = set_lds_once(h, trail_update_kernel<T>, (size_t)TrailCfg<T>::LDS_BYTES))) return rc;
   for (int p = 0; p < NC; ++p) {
     // L_pp and X <- X L_pp^-T for the rows below.  Every workgroup factors L_pp and takes 16 or 32 of those rows along: the
     // fewer, the shorter the launch (the update waves are its bottleneck) -- as long as every workgroup has a CU to itself
@@ -748,9 +746,9 @@ int posterior_large_group(blr_handle* h, const PosteriorArgs<T>& a, int64_t reg0
 
   if ((rc = large_prior(u))) return rc;
   large_colstats(u);
-  if ((rc = set_lds<T>(h, reinterpret_cast<const void*>(gram_tile_kernel<T>), LargeCfg<T>::LDS_BYTES))) return rc;
+  if ((rc = set_lds_once(h, gram_tile_kernel<T>, (size_t)LargeCfg<T>::LDS_BYTES))) return rc;
   if constexpr (sizeof(T) == 4) {
-    if ((rc = set_lds<T>(h, reinterpret_cast<const void*>(gram_tile_kernel<T, true>), LargeCfg<T>::LDS_BYTES))) return rc;
+    if ((rc = set_lds_once(h, gram_tile_kernel<T, true>, (size_t)LargeCfg<T>::LDS_BYTES))) return rc;
     if (p.planes) { if ((rc = large_gram_planes(u))) return rc; }
     else large_gram_tiles(u);
   } else {
@@ -1005,15 +1003,83 @@ int marginals_large_group(blr_handle* h, int layout, int64_t B, int64_t D, int64
   return 0;
 }
 
+// ---- the tall-matrix panel sweep (kernels: blr_tall.hpp) ---------------------------------------------------------------------
+// Ybar = [ F ; rows ] (column-major, ldy): `below` rows, a multiple of 128, under an already factored DP x DP block F.  One
+// 128-column panel at a time every row x' becomes x'L^-T (forward) and then x'L^-T L^-1 = x'A^-1 (backward, which reads the UPPER
+// triangle of F as T = L').  G matrices per launch (blockIdx.y): matrix g lies grp_ws bytes further and has status word info[g];
+// 1 and 0 for a single matrix.
+template <typename T>
+struct TallSweep {
+  using TC = TrsmCfg<T>;
+  using LC = LargeCfg<T>;
+  blr_handle* h;
+  T* Ybar; int64_t ldy;
+  int DP, below;
+  const int32_t* info;
+  int G; int64_t grp_ws;
+
+  int NC() const { return DP / kPB; }
+  dim3 row_blocks() const { return dim3((below + TC::RB - 1) / TC::RB, (unsigned)G); }
+  int prepare() const {
+    int rc;
+    if ((rc = set_lds_once(h, trsm_block_kernel<T>, (size_t)TC::LDS_BYTES))) return rc;
+    if ((rc = set_lds_once(h, trsm_back_block_kernel<T>, (size_t)TC::LDS_BYTES))) return rc;
+    return set_lds_once(h, gram_tile_kernel<T>, (size_t)LC::LDS_BYTES);
+  }
+  // C(I, J) -= Y(I, p) F(J, p)' for every row block I below F and J = j0 .. j0 + ncolblocks - 1
+  void trailing(int p, int j0, int ncolblocks) const {
+    const int nyb = below / kPB;
+    GramTileArgs<T> g{};
+    g.X = Ybar + (int64_t)p * kPB * ldy; g.ldx = ldy; g.layout = LAYOUT_COLVECS; g.use_dma = 1;
+    g.s = nullptr; g.noise_kind = NOISE_ISOTROPIC; g.r = nullptr;
+    g.D = DP + below; g.n_begin = 0; g.n_end = kPB; g.nsplit = 1;
+    g.tile_i0 = NC(); g.tile_j0 = j0; g.tri = 3; g.ntile_rows = nyb; g.ntiles = nyb * ncolblocks; g.nblocks = NC() + nyb;
+    g.C = Ybar; g.ldc = ldy; g.mode_out = 1;
+    g.grp_X = grp_ws / (int64_t)sizeof(T); g.grp_s = 0; g.grp_ws = grp_ws;
+    hipLaunchKernelGGL(gram_tile_kernel<T>, dim3(g.ntiles, (unsigned)G), dim3(kThreads), LC::LDS_BYTES, h->stream, g);
+  }
+  // rows x' -> x'L^-T.  rs: the row sums of squares that ride along (block p of a row is final after panel p), without first / last
+  void forward(RowSqArgs<T> rs) const {
+    for (int p = 0; p < NC(); ++p) {
+      rs.first = p == 0; rs.last = p == NC() - 1;
+      hipLaunchKernelGGL(trsm_block_kernel<T>, row_blocks(), dim3(kThreads), TC::LDS_BYTES, h->stream, Ybar, ldy, p, DP, DP + below, info, rs,
+                         grp_ws);
+      if (p + 1 < NC()) trailing(p, p + 1, NC() - 1 - p);
+    }
+  }
+  // rows x'L^-T -> x'L^-T L^-1 = x'A^-1
+  void backward() const {
+    for (int p = NC() - 1; p >= 0; --p) {
+      hipLaunchKernelGGL(trsm_back_block_kernel<T>, row_blocks(), dim3(kThreads), TC::LDS_BYTES, h->stream, Ybar, ldy, p, DP, DP + below, info,
+                         grp_ws);
+      if (p > 0) trailing(p, 0, p);
+    }
+  }
+};
+
+// top block of a tall matrix for a factored or dense prior: L = U' (upper factor given) or chol(Lw) (dense precision, reference :41
+// _cholesky(Lw)).  A factor with a non-positive diagonal entry is not a Cholesky factor: LAPACK-style index in *info_dev instead of
+// Inf / NaN results with info = 0; the panel kernels return early on a non-zero status.
+template <typename T>
+int tall_top_block(blr_handle* h, int prior_kind, const T* Lw, int64_t ldl, int D, int DP, T* Ybar, int64_t ldy, int32_t* info_dev) {
+  if (prior_kind == BLR_PRIOR_UPPER_FACTOR) {
+    hipLaunchKernelGGL(prior_diag_kernel<T>, dim3(1), dim3(kThreads), 0, h->stream, Lw, ldl, (int)PRIOR_UPPER_FACTOR, D, (double*)nullptr,
+                       info_dev);
+    dim3 grid((DP + 31) / 32, (DP + 31) / 32);
+    hipLaunchKernelGGL(factor_transpose_fill_kernel<T>, grid, dim3(kThreads), 0, h->stream, Lw, ldl, D, DP, Ybar, ldy);
+    return 0;
+  }
+  hipLaunchKernelGGL(prior_copy_kernel<T>, dim3(1024), dim3(kThreads), 0, h->stream, Lw, ldl, D, DP, Ybar, ldy);
+  return chol_large<T>(h, Ybar, ldy, DP, DP, info_dev);
+}
+
 // ---- large-D marginals: mean stream + (var) tall TRSM through the factorisation's panel machinery -------------------
 template <typename T>
 int marginals_large_one(blr_handle* h, int layout, int64_t D, int64_t N, const T* X, int64_t ldx, int noise_kind,
                         const T* s, int prior_kind, const T* mw, const T* Lw, int64_t ldl, T* mean, T* var,
                         int32_t* info_dev) {
   using SC = SmallCfg<T, 8>;
-  using TC = TrsmCfg<T>;
-  using LC = LargeCfg<T>;
-  const int DP = (int)((D + kPB - 1) / kPB * kPB), NC = DP / kPB;
+  const int DP = (int)((D + kPB - 1) / kPB * kPB);
   const int NP = (int)((N + kPB - 1) / kPB * kPB);
   const int64_t ldy = (int64_t)DP + NP;
   int rc;
@@ -1043,38 +1109,13 @@ int marginals_large_one(blr_handle* h, int layout, int64_t D, int64_t N, const T
     hipLaunchKernelGGL(var_diag_prior_kernel<T>, dim3(2048), dim3(kThreads), 0, h->stream, X, ldx, layout, Lw, (int)D, (int)N, s,
                        noise_kind, var);
   } else if (var) {
-    // top block: L = U' (upper factor given) or chol(Lw) (dense precision, reference :41 _cholesky(Lw))
-    if (prior_kind == BLR_PRIOR_UPPER_FACTOR) {
-      // a factor with a non-positive diagonal entry is not a Cholesky factor: LAPACK-style index instead of Inf / NaN variances
-      hipLaunchKernelGGL(prior_diag_kernel<T>, dim3(1), dim3(kThreads), 0, h->stream, Lw, ldl, (int)PRIOR_UPPER_FACTOR, (int)D,
-                         (double*)nullptr, info_dev);
-      dim3 grid((DP + 31) / 32, (DP + 31) / 32);
-      hipLaunchKernelGGL(factor_transpose_fill_kernel<T>, grid, dim3(kThreads), 0, h->stream, Lw, ldl, (int)D, DP, Ybar, ldy);
-    } else {
-      hipLaunchKernelGGL(prior_copy_kernel<T>, dim3(1024), dim3(kThreads), 0, h->stream, Lw, ldl, (int)D, DP, Ybar, ldy);
-      if ((rc = chol_large<T>(h, Ybar, ldy, DP, DP, info_dev))) return rc;
-    }
-    if ((rc = set_lds<T>(h, reinterpret_cast<const void*>(trsm_block_kernel<T>), TC::LDS_BYTES))) return rc;
-    if ((rc = set_lds<T>(h, reinterpret_cast<const void*>(gram_tile_kernel<T>), LC::LDS_BYTES))) return rc;
-    const int nyb = NP / kPB;  // row blocks of the input part
-    double* rowsq = reinterpret_cast<double*>(h->ws.p + (((size_t)ldy * DP * sizeof(T) + 255) & ~(size_t)255));
-    for (int p = 0; p < NC; ++p) {
-      const int nblk = (NP + TC::RB - 1) / TC::RB;
-      RowSqArgs<T> rs{};  // the row sums of squares ride on the TRSM: block p of a row is final after panel p
-      rs.acc = rowsq; rs.var = var; rs.s = s; rs.noise_kind = noise_kind; rs.N = (int)N; rs.first = p == 0; rs.last = p == NC - 1;
-      hipLaunchKernelGGL(trsm_block_kernel<T>, dim3(nblk), dim3(kThreads), TC::LDS_BYTES, h->stream, Ybar, ldy, p, DP, DP + NP,
-                         (const int32_t*)info_dev, rs);
-      const int m = NC - 1 - p;
-      if (m > 0) {
-        GramTileArgs<T> g{};
-        g.X = Ybar + (int64_t)p * kPB * ldy; g.ldx = ldy; g.layout = LAYOUT_COLVECS; g.use_dma = 1;
-        g.s = nullptr; g.noise_kind = NOISE_ISOTROPIC; g.r = nullptr;
-        g.D = DP + NP; g.n_begin = 0; g.n_end = kPB; g.nsplit = 1;
-        g.tile_i0 = NC; g.tile_j0 = p + 1; g.tri = 3; g.ntile_rows = nyb; g.ntiles = nyb * m; g.nblocks = NC + nyb;
-        g.C = Ybar; g.ldc = ldy; g.mode_out = 1;
-        hipLaunchKernelGGL(gram_tile_kernel<T>, dim3(g.ntiles), dim3(kThreads), LC::LDS_BYTES, h->stream, g);
-      }
-    }
+    if ((rc = tall_top_block<T>(h, prior_kind, Lw, ldl, (int)D, DP, Ybar, ldy, info_dev))) return rc;
+    const TallSweep<T> sweep{h, Ybar, ldy, DP, NP, info_dev, 1, 0};
+    if ((rc = sweep.prepare())) return rc;
+    RowSqArgs<T> rs{};
+    rs.acc = reinterpret_cast<double*>(h->ws.p + (((size_t)ldy * DP * sizeof(T) + 255) & ~(size_t)255));
+    rs.var = var; rs.s = s; rs.noise_kind = noise_kind; rs.N = (int)N;
+    sweep.forward(rs);
   }
   (void)sizeof(SC);
   HIP_TRY(h, hipGetLastError());
@@ -1284,7 +1325,7 @@ int gram_stats(blr_handle* h, int layout, int64_t D64, int64_t N64, const T* X, 
     hipLaunchKernelGGL(stats_scalars_kernel<T>, dim3(1), dim3(kThreads), 0, h->stream, (const double*)qpart, (const double*)lpart, gridc,
                        noise_kind, s, N, scal);
   }
-  if ((rc = set_lds<T>(h, reinterpret_cast<const void*>(gram_tile_kernel<T>), LC::LDS_BYTES))) return rc;
+  if ((rc = set_lds_once(h, gram_tile_kernel<T>, (size_t)LC::LDS_BYTES))) return rc;
   {
     GramTileArgs<T> g{};
     g.X = X; g.ldx = ldx; g.layout = layout;
@@ -1390,9 +1431,7 @@ template <typename T>
 int logpdf_grad_large_group(blr_handle* h, int G, int layout, int64_t D, int64_t N, const T* X, int64_t ldx, const T* y, int noise_kind,
                             const T* s, const T* mwp, const T* Tfac, int64_t ldt, T* dX, int64_t lddx, T* dy, T* ds, T* dmw,
                             T* Ainv, int64_t ldai, int32_t* info_dev, const GradGroupStrides& gs) {
-  using TC = TrsmCfg<T>;
-  using LC = LargeCfg<T>;
-  const int DP = (int)((D + kPB - 1) / kPB * kPB), NC = DP / kPB;
+  const int DP = (int)((D + kPB - 1) / kPB * kPB);
   const int NP = (int)((N + kPB - 1) / kPB * kPB);
   const int DI = Ainv ? DP : 0;
   const int R = DP + NP + DI;
@@ -1427,39 +1466,20 @@ int logpdf_grad_large_group(blr_handle* h, int G, int layout, int64_t D, int64_t
     hipLaunchKernelGGL(mean_fill_kernel<T>, dim3((unsigned)(NP / 64), ug), dim3(kThreads), 0, h->stream, m);
     if (DI) hipLaunchKernelGGL(identity_rows_kernel<T>, dim3(G > 8 ? 128 : 1024, ug), dim3(kThreads), 0, h->stream, Ybar, ldy, DP + NP, DP, wsb);
   }
-  if ((rc = set_lds<T>(h, reinterpret_cast<const void*>(trsm_block_kernel<T>), TC::LDS_BYTES))) return rc;
-  if ((rc = set_lds<T>(h, reinterpret_cast<const void*>(trsm_back_block_kernel<T>), TC::LDS_BYTES))) return rc;
-  if ((rc = set_lds<T>(h, reinterpret_cast<const void*>(gram_tile_kernel<T>), LC::LDS_BYTES))) return rc;
-  const int nyb = (NP + DI) / kPB;                       // row blocks below the factor block
-  const int nblk = (NP + DI + TC::RB - 1) / TC::RB;
-  auto trailing = [&](int p, int j0, int ncolblocks) {   // C(I, J) -= Y(I, p) F(J, p)' for J = j0 .. j0 + ncolblocks - 1
-    GramTileArgs<T> g{};
-    g.X = Ybar + (int64_t)p * kPB * ldy; g.ldx = ldy; g.layout = LAYOUT_COLVECS; g.use_dma = 1;
-    g.s = nullptr; g.noise_kind = NOISE_ISOTROPIC; g.r = nullptr;
-    g.D = R; g.n_begin = 0; g.n_end = kPB; g.nsplit = 1;
-    g.tile_i0 = NC; g.tile_j0 = j0; g.tri = 3; g.ntile_rows = nyb; g.ntiles = nyb * ncolblocks; g.nblocks = NC + nyb;
-    g.C = Ybar; g.ldc = ldy; g.mode_out = 1;
-    g.grp_X = wsb / (int64_t)sizeof(T); g.grp_s = 0; g.grp_ws = wsb;
-    hipLaunchKernelGGL(gram_tile_kernel<T>, dim3(g.ntiles, ug), dim3(kThreads), LC::LDS_BYTES, h->stream, g);
-  };
-  for (int p = 0; p < NC; ++p) {  // forward: rows x' -> x'L^-T, with the row sums of squares riding along
+  const TallSweep<T> sweep{h, Ybar, ldy, DP, NP + DI, info_dev, G, wsb};
+  if ((rc = sweep.prepare())) return rc;
+  {
     RowSqArgs<T> rs{};
-    rs.acc = rowsq; rs.var = var; rs.s = s; rs.noise_kind = noise_kind; rs.N = (int)N; rs.first = p == 0; rs.last = p == NC - 1;
+    rs.acc = rowsq; rs.var = var; rs.s = s; rs.noise_kind = noise_kind; rs.N = (int)N;
     rs.grp_ws = wsb; rs.grp_s = gs.s;
-    hipLaunchKernelGGL(trsm_block_kernel<T>, dim3(nblk, ug), dim3(kThreads), TC::LDS_BYTES, h->stream, Ybar, ldy, p, DP, R,
-                       (const int32_t*)info_dev, rs, wsb);
-    if (p + 1 < NC) trailing(p, p + 1, NC - 1 - p);
+    sweep.forward(rs);
   }
   {
     GradObsGroup og{gs.y, gs.s, gs.dy, gs.ds, wsb};
     hipLaunchKernelGGL(grad_obs_kernel<T>, dim3((unsigned)((N + kThreads - 1) / kThreads), ug), dim3(kThreads), 0, h->stream, y,
                        (const T*)mu, (const T*)var, s, noise_kind, (int)N, rvec, wvec, dy, ds, og);
   }
-  for (int p = NC - 1; p >= 0; --p) {  // backward: x'L^-T -> x'L^-T L^-1 = x'A^-1
-    hipLaunchKernelGGL(trsm_back_block_kernel<T>, dim3(nblk, ug), dim3(kThreads), TC::LDS_BYTES, h->stream, Ybar, ldy, p, DP, R,
-                       (const int32_t*)info_dev, wsb);
-    if (p > 0) trailing(p, 0, p);  // second operand: the UPPER triangle of the factor block (T = L')
-  }
+  sweep.backward();
   if (dX || dmw) {
     GradOutArgs<T> o{};
     o.Ybar = Ybar; o.ldy = ldy; o.row0 = DP; o.X = X; o.ldx = ldx; o.layout = layout;
@@ -1677,7 +1697,6 @@ int logpdf_multi(blr_handle* h, int memspace, int layout, int64_t D, int64_t N, 
   if (!info) return bad_arg(h, 20, "info is NULL");
   HIP_TRY(h, hipSetDevice(h->device));
 
-  using TC = TrsmCfg<T>;
   using LC = LargeCfg<T>;
   CallIO io(h, memspace);
   int rc;
@@ -1804,7 +1823,7 @@ int logpdf_multi(blr_handle* h, int memspace, int layout, int64_t D, int64_t N, 
     hipLaunchKernelGGL(multi_prep_kernel<T>, dim3((unsigned)NP64), dim3(kThreads), 0, h->stream, p);
   }
   // (4) B' = R'X': split-K MFMA tiles, first operand R (rows s), second operand X (rows d)
-  if ((rc = set_lds<T>(h, reinterpret_cast<const void*>(gram_tile_kernel<T>), LC::LDS_BYTES))) return rc;
+  if ((rc = set_lds_once(h, gram_tile_kernel<T>, (size_t)LC::LDS_BYTES))) return rc;
   {
     GramTileArgs<T> g{};
     g.X = R; g.ldx = ldr; g.layout = layout; g.D = SP;
@@ -1823,34 +1842,17 @@ int logpdf_multi(blr_handle* h, int memspace, int layout, int64_t D, int64_t N, 
     dim3 grid((DP + 31) / 32, (DP + 31) / 32);
     hipLaunchKernelGGL(factor_sym_fill_kernel<T>, grid, dim3(kThreads), 0, h->stream, (const T*)Tf, D, (int)D, DP, Ybar, ldy);
   }
-  if ((rc = set_lds<T>(h, reinterpret_cast<const void*>(trsm_block_kernel<T>), TC::LDS_BYTES))) return rc;
-  if ((rc = set_lds<T>(h, reinterpret_cast<const void*>(trsm_back_block_kernel<T>), TC::LDS_BYTES))) return rc;
-  const int R_rows = DP + SP;
-  const int nblk = (SP + TC::RB - 1) / TC::RB;
-  auto trailing = [&](int p, int j0, int ncolblocks) {
-    GramTileArgs<T> g{};
-    g.X = Ybar + (int64_t)p * kPB * ldy; g.ldx = ldy; g.layout = LAYOUT_COLVECS; g.use_dma = 1;
-    g.s = nullptr; g.noise_kind = NOISE_ISOTROPIC; g.r = nullptr;
-    g.D = R_rows; g.n_begin = 0; g.n_end = kPB; g.nsplit = 1;
-    g.tile_i0 = NC; g.tile_j0 = j0; g.tri = 3; g.ntile_rows = ntile_rows; g.ntiles = ntile_rows * ncolblocks; g.nblocks = NC + ntile_rows;
-    g.C = Ybar; g.ldc = ldy; g.mode_out = 1;
-    hipLaunchKernelGGL(gram_tile_kernel<T>, dim3(g.ntiles), dim3(kThreads), LC::LDS_BYTES, h->stream, g);
-  };
-  for (int p = 0; p < NC; ++p) {
+  const TallSweep<T> sweep{h, Ybar, ldy, DP, SP, info_d, 1, 0};
+  if ((rc = sweep.prepare())) return rc;
+  {
     RowSqArgs<T> rs{};
-    rs.acc = rowsq; rs.var = uu; rs.s = zero; rs.noise_kind = BLR_NOISE_ISOTROPIC; rs.N = (int)S; rs.first = p == 0; rs.last = p == NC - 1;
-    hipLaunchKernelGGL(trsm_block_kernel<T>, dim3(nblk), dim3(kThreads), TC::LDS_BYTES, h->stream, Ybar, ldy, p, DP, R_rows,
-                       (const int32_t*)info_d, rs);
-    if (p + 1 < NC) trailing(p, p + 1, NC - 1 - p);
+    rs.acc = rowsq; rs.var = uu; rs.s = zero; rs.noise_kind = BLR_NOISE_ISOTROPIC; rs.N = (int)S;
+    sweep.forward(rs);
   }
   hipLaunchKernelGGL(multi_finish_kernel<T>, dim3((unsigned)S), dim3(kThreads), 0, h->stream,
                      (const double*)lp0, (const double*)qpart, NP64, SP, (const T*)uu, (int)S, lp_d);
   if (mp_d) {
-    for (int p = NC - 1; p >= 0; --p) {
-      hipLaunchKernelGGL(trsm_back_block_kernel<T>, dim3(nblk), dim3(kThreads), TC::LDS_BYTES, h->stream, Ybar, ldy, p, DP, R_rows,
-                         (const int32_t*)info_d);
-      if (p > 0) trailing(p, 0, p);
-    }
+    sweep.backward();
     hipLaunchKernelGGL(multi_means_kernel<T>, dim3(1024), dim3(kThreads), 0, h->stream, (const T*)Ybar, ldy, DP, mw_d, (int)D, (int)S,
                        mp_d, ldmp);
   }
@@ -2448,9 +2450,6 @@ int posterior_dense_noise(blr_handle* h, int memspace, int layout, int64_t D64, 
 template <typename T>
 int tall_solve_rows(blr_handle* h, int layout, int D, int N, const T* X, int64_t ldx, int prior_kind, const T* Lw, int64_t ldl,
                     T* Ybar, int64_t ldy, int DP, int NP, int32_t* info_dev) {
-  using TC = TrsmCfg<T>;
-  using LC = LargeCfg<T>;
-  const int NC = DP / kPB;
   int rc;
   HIP_TRY(h, hipMemsetAsync(info_dev, 0, sizeof(int32_t), h->stream));
   {
@@ -2459,35 +2458,10 @@ int tall_solve_rows(blr_handle* h, int layout, int D, int N, const T* X, int64_t
     m.D = D; m.DP = DP; m.N = N;
     hipLaunchKernelGGL(mean_fill_kernel<T>, dim3((unsigned)(NP / 64)), dim3(kThreads), 0, h->stream, m);
   }
-  if (prior_kind == BLR_PRIOR_UPPER_FACTOR) {
-    // a PDMat whose factor has a non-positive diagonal entry is not a Cholesky factor: report it (LAPACK-style index) instead
-    // of returning Inf / NaN with info = 0; the panel kernels below return early on a non-zero status
-    hipLaunchKernelGGL(prior_diag_kernel<T>, dim3(1), dim3(kThreads), 0, h->stream, Lw, ldl, (int)PRIOR_UPPER_FACTOR, D, (double*)nullptr,
-                       info_dev);
-    dim3 grid((DP + 31) / 32, (DP + 31) / 32);
-    hipLaunchKernelGGL(factor_transpose_fill_kernel<T>, grid, dim3(kThreads), 0, h->stream, Lw, ldl, D, DP, Ybar, ldy);
-  } else {
-    hipLaunchKernelGGL(prior_copy_kernel<T>, dim3(1024), dim3(kThreads), 0, h->stream, Lw, ldl, D, DP, Ybar, ldy);
-    if ((rc = chol_large<T>(h, Ybar, ldy, DP, DP, info_dev))) return rc;
-  }
-  if ((rc = set_lds<T>(h, reinterpret_cast<const void*>(trsm_block_kernel<T>), TC::LDS_BYTES))) return rc;
-  if ((rc = set_lds<T>(h, reinterpret_cast<const void*>(gram_tile_kernel<T>), LC::LDS_BYTES))) return rc;
-  const int nyb = NP / kPB;
-  for (int p = 0; p < NC; ++p) {
-    const int nblk = (NP + TC::RB - 1) / TC::RB;
-    hipLaunchKernelGGL(trsm_block_kernel<T>, dim3(nblk), dim3(kThreads), TC::LDS_BYTES, h->stream, Ybar, ldy, p, DP, DP + NP,
-                       (const int32_t*)info_dev, RowSqArgs<T>{});
-    const int m = NC - 1 - p;
-    if (m > 0) {
-      GramTileArgs<T> g{};
-      g.X = Ybar + (int64_t)p * kPB * ldy; g.ldx = ldy; g.layout = LAYOUT_COLVECS; g.use_dma = 1;
-      g.s = nullptr; g.noise_kind = NOISE_ISOTROPIC; g.r = nullptr;
-      g.D = DP + NP; g.n_begin = 0; g.n_end = kPB; g.nsplit = 1;
-      g.tile_i0 = NC; g.tile_j0 = p + 1; g.tri = 3; g.ntile_rows = nyb; g.ntiles = nyb * m; g.nblocks = NC + nyb;
-      g.C = Ybar; g.ldc = ldy; g.mode_out = 1;
-      hipLaunchKernelGGL(gram_tile_kernel<T>, dim3(g.ntiles), dim3(kThreads), LC::LDS_BYTES, h->stream, g);
-    }
-  }
+  if ((rc = tall_top_block<T>(h, prior_kind, Lw, ldl, D, DP, Ybar, ldy, info_dev))) return rc;
+  const TallSweep<T> sweep{h, Ybar, ldy, DP, NP, info_dev, 1, 0};
+  if ((rc = sweep.prepare())) return rc;
+  sweep.forward(RowSqArgs<T>{});
   HIP_TRY(h, hipGetLastError());
   return 0;
 }
@@ -2549,7 +2523,7 @@ int mean_and_cov(blr_handle* h, int memspace, int layout, int64_t D64, int64_t N
   // ---- Y Y' by the Gram kernel with the roles swapped: NP "rows", D "observations" (columns of Y are contiguous)
   {
     using LC = LargeCfg<T>;
-    if ((rc = set_lds<T>(h, reinterpret_cast<const void*>(gram_tile_kernel<T>), LC::LDS_BYTES))) return rc;
+    if ((rc = set_lds_once(h, gram_tile_kernel<T>, (size_t)LC::LDS_BYTES))) return rc;
     GramTileArgs<T> g{};
     g.X = Ybar + DP; g.ldx = ldy; g.layout = LAYOUT_COLVECS; g.use_dma = 1;
     g.s = nullptr; g.noise_kind = NOISE_ISOTROPIC; g.r = nullptr;

@@ -104,7 +104,7 @@ __global__ __launch_bounds__(kThreads) void marg_image_kernel(const T* __restric
       Xs[r * Cfg::LDX + c] = (c == 64 * half + r) ? T(1) : T(0);
     }
     __syncthreads();
-    trsm_sweep<T>(Xs, P, Linv, nchunks, lane, wave);  // rows 64 half .. + 63 of L^-T (ends with a barrier)
+    trsm_sweep<T, false>(Xs, P, Linv, nchunks, lane, wave);  // rows 64 half .. + 63 of L^-T (ends with a barrier)
     IMG_T();
     // image entries whose contraction index d falls into this half: fragment m of column block J to wave m % 4 (a flat loop over
     // the 9216 entries with a search for J per entry was half of this kernel's time)
