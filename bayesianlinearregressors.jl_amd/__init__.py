@@ -27,6 +27,7 @@ from .regressor import (
     logpdf,
     logpdf_and_gradient,
     logpdf_columns,
+    logpdf_columns_map,
     logpdf_grid,
     logpdf_grid_map,
     logpdf_map,
@@ -39,6 +40,8 @@ from .regressor import (
     mean_and_var,
     posterior,
     posterior_best,
+    posterior_columns,
+    posterior_columns_map,
     posterior_map,
     posterior_ragged,
     rand,
@@ -56,4 +59,5 @@ __all__ = [
     "LOO", "loo", "loo_map",
     "EvidenceGrid", "logpdf_grid", "posterior_best", "logpdf_grid_map",
     "posterior_ragged", "logpdf_ragged",
+    "posterior_columns", "logpdf_columns_map", "posterior_columns_map",
 ]

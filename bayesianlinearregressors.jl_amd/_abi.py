@@ -19,6 +19,7 @@ LAYOUT_COLVECS, LAYOUT_ROWVECS = 0, 1
 NOISE_ISOTROPIC, NOISE_DIAGONAL, NOISE_DENSE = 0, 1, 2
 PRIOR_DENSE, PRIOR_UPPER_FACTOR, PRIOR_DIAGONAL = 0, 1, 2
 MEM_HOST, MEM_DEVICE = 0, 1
+MULTI_COLS_PER_PASS = 64  # csrc/blr_multi.hpp kMultiColsPerPass: column slots of one pass of multi_cols_kernel (slot 0 = column 0)
 
 _i64, _int, _vp = C.c_int64, C.c_int, C.c_void_p
 _H = C.c_void_p
@@ -77,6 +78,9 @@ for _suf in ("f64", "f32"):
     _SIGS[f"blr_posterior_ragged_{_suf}"] = (
         [_H, _int, _int, _i64, _i64, _vp, _vp, _i64, _vp, _int, _vp, _i64, _int, _vp, _i64, _vp, _i64, _i64,
          _vp, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp], _int)
+    _SIGS[f"blr_posterior_multi_batched_{_suf}"] = (
+        [_H, _int, _int, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _int, _vp, _i64, _int, _vp, _i64, _vp, _i64, _i64,
+         _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _vp], _int)
     _SIGS[f"blr_posterior_nsharded_{_suf}"] = (
         [_H, _int, _i64, _i64, _i64, _vp, _i64, _vp, _int, _vp, _int, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp], _int)
     _SIGS[f"blr_update_factor_{_suf}"] = (
@@ -298,6 +302,16 @@ class Handle:
         return self.check(fn(self._h, memspace, layout, B, D, _ptr(offsets), _ptr(X), ldx, _ptr(y), noise_kind, _ptr(s), strides,
                              prior_kind, _ptr(mw), stridemw, _ptr(Lw), ldl, strideLw, _ptr(mw_post), stride_mwpost, _ptr(T_post),
                              ldt, strideT, _ptr(Lw_post), ldlp, strideLp, _ptr(logpdf), _ptr(info)))
+
+    def posterior_multi_batched(self, dtype, memspace, layout, B, D, N, S, X, ldx, strideX, Y, ldY, strideY, noise_kind, s, strides,
+                                prior_kind, mw, stridemw, Lw, ldl, strideLw, mw_post, ldmp, stride_mwpost, T_post, ldt, strideT,
+                                Lw_post, ldlp, strideLp, logpdf, stride_lp, info):
+        """B regressors with S target columns each (Y: N x S per regressor) in one call: one factor per regressor, a mean and an
+        evidence per column; include/blr_mi355x.h blr_posterior_multi_batched_* (one status per regressor in info)."""
+        fn = getattr(self.lib, f"blr_posterior_multi_batched_{suffix(dtype)}")
+        return self.check(fn(self._h, memspace, layout, B, D, N, S, _ptr(X), ldx, strideX, _ptr(Y), ldY, strideY, noise_kind, _ptr(s),
+                             strides, prior_kind, _ptr(mw), stridemw, _ptr(Lw), ldl, strideLw, _ptr(mw_post), ldmp, stride_mwpost,
+                             _ptr(T_post), ldt, strideT, _ptr(Lw_post), ldlp, strideLp, _ptr(logpdf), stride_lp, _ptr(info)))
 
     def posterior_nsharded(self, dtype, layout, D, N_local, N_total, X, ldx, y, noise_kind, s, prior_kind, mw, Lw, ldl, stats, lds,
                            scal, mw_post, T_post, ldt, Lw_post, ldlp, logpdf, info):

@@ -32,6 +32,7 @@
 #include "blr_rand_batched.hpp"
 #include "blr_grid.hpp"
 #include "blr_ragged.hpp"
+#include "blr_multi.hpp"
 #include "blr_host.hpp"
 #include "blr_large_plan.hpp"
 
@@ -3216,6 +3217,149 @@ int posterior_ragged(blr_handle* h, int memspace, int layout, int64_t B, int64_t
   return io.finish();
 }
 
+// ---- batched multi-output posterior: S target columns per regressor (blr_posterior_multi_batched_*) ----------------
+inline const void* multi_cols_kernel_ptr(double, int layout) { return multi_cols_kernel_ptr_f64(layout); }
+inline const void* multi_cols_kernel_ptr(float, int layout) { return multi_cols_kernel_ptr_f32(layout); }
+inline void multi_cols_kernel_launch(int layout, dim3 grid, size_t lds, hipStream_t st, const MultiColsArgs<double>& a) { multi_cols_kernel_launch_f64(layout, grid, lds, st, a); }
+inline void multi_cols_kernel_launch(int layout, dim3 grid, size_t lds, hipStream_t st, const MultiColsArgs<float>& a) { multi_cols_kernel_launch_f32(layout, grid, lds, st, a); }
+
+template <typename T>
+int posterior_multi_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t N, int64_t S, const T* X, int64_t ldx,
+                            int64_t strideX, const T* Y, int64_t ldY, int64_t strideY, int noise_kind, const T* s, int64_t strides,
+                            int prior_kind, const T* mw, int64_t stridemw, const T* Lw, int64_t ldl, int64_t strideLw, T* mw_post,
+                            int64_t ldmp, int64_t stride_mwpost, T* T_post, int64_t ldt, int64_t strideT, T* Lw_post, int64_t ldlp,
+                            int64_t strideLp, double* logpdf, int64_t stride_lp, int32_t* info) {
+  // (the argument checks come before the handle's: they need no device)
+  if (h) h->err.clear();
+  if (memspace != BLR_MEM_HOST && memspace != BLR_MEM_DEVICE) return bad_arg(h, 2, "memspace");
+  if (layout != BLR_LAYOUT_COLVECS && layout != BLR_LAYOUT_ROWVECS) return bad_arg(h, 3, "unknown layout (reference :26-31)");
+  if (B < 0 || B > (1 << 30)) return bad_arg(h, 4, "B out of range (0..2^30)");
+  if (D < 1 || D > kMaxLargeD) return bad_arg(h, 5, "D out of range (1..8192)");
+  if (N < 0 || N > (1 << 30)) return bad_arg(h, 6, "N out of range");
+  if (S < 0 || S > (1 << 20)) return bad_arg(h, 7, "S out of range (0..2^20)");
+  if (B == 0 || S == 0) return 0;
+  if (N > 0 && !X) return bad_arg(h, 8, "X is NULL");
+  if (layout == BLR_LAYOUT_COLVECS ? ldx < D : ldx < std::max<int64_t>(N, 1)) return bad_arg(h, 9, "ldx too small");
+  if (strideX < 0) return bad_arg(h, 10, "strideX < 0");
+  if (N > 0 && !Y) return bad_arg(h, 11, "Y is NULL (reference :74 length check)");
+  if (ldY < N) return bad_arg(h, 12, "ldY < N (reference :74 length check)");
+  if (strideY < 0) return bad_arg(h, 13, "strideY < 0");
+  if (noise_kind != BLR_NOISE_ISOTROPIC && noise_kind != BLR_NOISE_DIAGONAL)
+    return bad_arg(h, 14, "noise_kind (isotropic or diagonal; dense Sigma_y is not supported for batched multi-output targets)");
+  if (!s) return bad_arg(h, 15, "s is NULL");
+  if (strides < 0) return bad_arg(h, 16, "strides < 0");
+  if (prior_kind != BLR_PRIOR_DENSE && prior_kind != BLR_PRIOR_UPPER_FACTOR && prior_kind != BLR_PRIOR_DIAGONAL)
+    return bad_arg(h, 17, "prior_kind");
+  if (!mw) return bad_arg(h, 18, "mw is NULL");
+  if (stridemw < 0) return bad_arg(h, 19, "stridemw < 0");
+  if (!Lw) return bad_arg(h, 20, "Lw is NULL");
+  if (prior_kind != BLR_PRIOR_DIAGONAL && ldl < D) return bad_arg(h, 21, "ldl < D");
+  if (strideLw < 0) return bad_arg(h, 22, "strideLw < 0");
+  if (mw_post && mw_post == mw) return bad_arg(h, 23, "mw_post == mw (the columns after the first still need the prior mean)");
+  if (mw_post && ldmp < D) return bad_arg(h, 24, "ldmp < D");
+  if (mw_post && B > 1 && stride_mwpost < ldmp * S) return bad_arg(h, 25, "stride_mwpost < ldmp * S");
+  if (T_post && T_post == Lw) return bad_arg(h, 26, "T_post == Lw (aliasing an output with an input is not supported)");
+  if (T_post && ldt < D) return bad_arg(h, 27, "ldt < D");
+  if (T_post && B > 1 && strideT < (int64_t)mat_extent(D, D, ldt)) return bad_arg(h, 28, "strideT too small");
+  if (Lw_post && ldlp < D) return bad_arg(h, 30, "ldlp < D");
+  if (Lw_post && B > 1 && strideLp < (int64_t)mat_extent(D, D, ldlp)) return bad_arg(h, 31, "strideLp too small");
+  if (logpdf && B > 1 && stride_lp < S) return bad_arg(h, 33, "stride_lp < S");
+  if (!info) return bad_arg(h, 34, "info is NULL");
+  if (!h) return -1;
+  HIP_TRY(h, hipSetDevice(h->device));
+
+  PosteriorArgs<T> a{};
+  a.ldx = ldx; a.strideX = strideX; a.stridey = strideY; a.strides = strides; a.stridemw = stridemw;
+  a.ldl = ldl; a.strideLw = strideLw; a.stride_mwpost = stride_mwpost; a.ldt = ldt; a.strideT = strideT;
+  a.ldlp = ldlp; a.strideLp = strideLp;
+  a.layout = layout; a.noise_kind = noise_kind; a.prior_kind = prior_kind;
+  a.D = (int)D; a.N = (int)N; a.B = (int)B;
+
+  CallIO io(h, memspace);
+  const size_t x_one = layout == BLR_LAYOUT_COLVECS ? mat_extent(D, N, ldx) : mat_extent(N, D, ldx);
+  const size_t lw_one = prior_kind == BLR_PRIOR_DIAGONAL ? (size_t)D : mat_extent(D, D, ldl);
+  const size_t s_one = noise_kind == BLR_NOISE_DIAGONAL ? (size_t)N : 1;
+  double* lp_d = nullptr;
+  int rc;
+  if ((rc = io.in(X, extent(B, strideX, x_one), &a.X))) return rc;
+  if ((rc = io.in(Y, N > 0 ? extent(B, strideY, mat_extent(N, S, ldY)) : 0, &a.y))) return rc;
+  if ((rc = io.in(s, extent(B, strides, s_one), &a.s))) return rc;
+  if ((rc = io.in(mw, extent(B, stridemw, (size_t)D), &a.mw))) return rc;
+  if ((rc = io.in(Lw, extent(B, strideLw, lw_one), &a.Lw))) return rc;
+  if ((rc = io.out(mw_post, extent(B, stride_mwpost, mat_extent(D, S, ldmp)), &a.mw_post))) return rc;
+  if ((rc = io.out(T_post, extent(B, strideT, mat_extent(D, D, ldt)), &a.T_post))) return rc;
+  if ((rc = io.out(Lw_post, extent(B, strideLp, mat_extent(D, D, ldlp)), &a.Lw_post))) return rc;
+  if ((rc = io.out(logpdf, extent(B, stride_lp, (size_t)S), &lp_d))) return rc;
+  if ((rc = io.out(info, (size_t)B, &a.info))) return rc;
+  const T* const Y_d = a.y;
+
+  if (D > kMaxSmallD) {
+    // correct, not fast: one regressor after the other -- column 0 through the pipeline of blr_posterior_batched_* (which hands out the
+    // factor, the precision and the status), the further columns through the shared-X pipeline of blr_logpdf_multi_*; the call synchronises
+    const AsyncScope drain(h, false);
+    double* lp_tmp = nullptr;
+    int32_t* info_tmp = nullptr;
+    if ((rc = io.tmp((size_t)S, &lp_tmp))) return rc;
+    if ((rc = io.tmp((size_t)1, &info_tmp))) return rc;
+    const std::vector<double> nans((size_t)S, __builtin_nan(""));
+    for (int64_t b = 0; b < B; ++b) {
+      const T* const Xb = a.X ? a.X + b * strideX : (const T*)nullptr;
+      const T* const Yb = Y_d ? Y_d + b * strideY : (const T*)nullptr;
+      T* const mpb = a.mw_post ? a.mw_post + b * stride_mwpost : (T*)nullptr;
+      double* const lpb = lp_d ? lp_d + b * stride_lp : (double*)nullptr;
+      const int64_t first_cols = N == 0 ? S : 1;  // without data there is no shared work: every column is its own (trivial) update
+      for (int64_t c = 0; c < first_cols; ++c) {
+        rc = posterior_batched<T>(h, BLR_MEM_DEVICE, layout, 1, D, N, Xb, ldx, 0, Yb ? Yb + c * ldY : (const T*)nullptr, 0, noise_kind,
+                                  a.s + b * strides, 0, prior_kind, a.mw + b * stridemw, 0, a.Lw + b * strideLw, ldl, 0,
+                                  mpb ? mpb + c * ldmp : (T*)nullptr, 0, c == 0 && a.T_post ? a.T_post + b * strideT : (T*)nullptr, ldt, 0,
+                                  c == 0 && a.Lw_post ? a.Lw_post + b * strideLp : (T*)nullptr, ldlp, 0, lpb ? lpb + c : (double*)nullptr,
+                                  c == 0 ? a.info + b : info_tmp);
+        if (rc) return rc;  // (device pointers and in-range sizes: a HIP failure, not an argument index of the inner call)
+      }
+      int32_t st = 0;
+      HIP_TRY(h, hipMemcpyAsync(&st, a.info + b, sizeof(st), hipMemcpyDeviceToHost, h->stream));
+      HIP_TRY(h, hipStreamSynchronize(h->stream));
+      if (st != 0) {
+        if (lpb) HIP_TRY(h, hipMemcpyAsync(lpb, nans.data(), (size_t)S * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        continue;
+      }
+      for (int64_t c = 1; c < S && N > 0; c += 65536) {  // (blr_logpdf_multi_* takes up to 65536 columns)
+        rc = logpdf_multi<T>(h, BLR_MEM_DEVICE, layout, D, N, std::min<int64_t>(65536, S - c), Xb, ldx, Yb + c * ldY, ldY, noise_kind,
+                             a.s + b * strides, prior_kind, a.mw + b * stridemw, a.Lw + b * strideLw, ldl, lpb ? lpb + c : lp_tmp,
+                             mpb ? mpb + c * ldmp : (T*)nullptr, ldmp, info_tmp);
+        if (rc) return rc;
+      }
+    }
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return io.finish();
+  }
+
+  // D <= 128.  Step 1: column 0 of every regressor through the dispatch of blr_posterior_batched_*, unchanged; its evidence waits in the
+  // handle's workspace (the caller's logpdf has a stride of its own), and so does the factor when the caller does not want it
+  const size_t lp0_bytes = ((size_t)B * sizeof(double) + 255) & ~(size_t)255;
+  const bool own_T = a.T_post == nullptr && S > 1;
+  if ((rc = h->multi_ws.reserve(h, lp0_bytes + (own_T ? (size_t)B * D * D * sizeof(T) : 0)))) return rc;
+  double* const lp0 = reinterpret_cast<double*>(h->multi_ws.p);
+  if (own_T) { a.T_post = reinterpret_cast<T*>(h->multi_ws.p + lp0_bytes); a.ldt = D; a.strideT = D * D; }
+  a.logpdf = lp0;
+  if ((rc = posterior_run<T>(h, a))) return rc;
+  // Step 2: ONE launch for the columns 1 .. S-1 of every regressor (and the copy of column 0's evidence to its place)
+  MultiColsArgs<T> m{};
+  m.X = a.X; m.ldx = ldx; m.strideX = strideX; m.Y = Y_d ? Y_d : a.mw; m.ldY = ldY; m.strideY = strideY; m.s = a.s; m.strides = strides;
+  m.mw = a.mw; m.stridemw = stridemw; m.Tf = a.T_post ? a.T_post : a.mw; m.ldt = a.ldt; m.strideT = a.strideT; m.lp0 = lp0; m.info = a.info;
+  m.mw_post = a.mw_post; m.ldmp = ldmp; m.stride_mwpost = stride_mwpost; m.logpdf = lp_d; m.stride_lp = stride_lp;
+  m.noise_kind = noise_kind; m.D = (int)D; m.N = (int)N; m.S = (int)S;
+  const int per_pass = kMultiColsPerPass - 1;
+  const int64_t passes = std::max<int64_t>(1, (S - 1 + per_pass - 1) / per_pass);
+  const size_t lds = multi_cols_lds_bytes(sizeof(T), (int)D, (int)std::min<int64_t>(S, kMultiColsPerPass));
+  const void* const kern = multi_cols_kernel_ptr(T(0), layout);
+  if ((rc = set_lds_once(h, kern, lds))) return rc;
+  multi_cols_kernel_launch(layout, dim3((unsigned)B, (unsigned)passes), lds, h->stream, m);
+  HIP_TRY(h, hipGetLastError());
+  return io.finish();
+}
+
 }  // namespace
 
 // =======================================================================================================
@@ -3377,7 +3521,7 @@ int blr_get_stat(blr_handle* h, const char* key, int64_t* value) {
     return 0;
   }
   if (!strcmp(key, "workspace_bytes")) {
-    *value = (int64_t)(h->ws.bytes + h->feat.bytes + h->aux.bytes + h->i8side.bytes + h->xchg.bytes + h->loo_ws.bytes + h->ragged_meta.bytes);
+    *value = (int64_t)(h->ws.bytes + h->feat.bytes + h->aux.bytes + h->i8side.bytes + h->xchg.bytes + h->loo_ws.bytes + h->ragged_meta.bytes + h->multi_ws.bytes);
     return 0;
   }
   return bad_arg(h, 2, "unknown statistic");
@@ -3498,6 +3642,18 @@ int blr_timer_stop(blr_handle* h, float* elapsed_ms) {
     return posterior_ragged<T>(h, memspace, layout, B, D, offsets, X, ldx, y, noise_kind, s, strides, prior_kind,   \
                                mw, stridemw, Lw, ldl, strideLw, mw_post, stride_mwpost, T_post, ldt, strideT,       \
                                Lw_post, ldlp, strideLp, logpdf, info);                                              \
+  }                                                                                                                 \
+  int blr_posterior_multi_batched_##SUF(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t N,   \
+                                        int64_t S, const T* X, int64_t ldx, int64_t strideX, const T* Y,            \
+                                        int64_t ldY, int64_t strideY, int noise_kind, const T* s, int64_t strides,  \
+                                        int prior_kind, const T* mw, int64_t stridemw, const T* Lw, int64_t ldl,    \
+                                        int64_t strideLw, T* mw_post, int64_t ldmp, int64_t stride_mwpost,          \
+                                        T* T_post, int64_t ldt, int64_t strideT, T* Lw_post, int64_t ldlp,          \
+                                        int64_t strideLp, double* logpdf, int64_t stride_lp, int32_t* info) {       \
+    return posterior_multi_batched<T>(h, memspace, layout, B, D, N, S, X, ldx, strideX, Y, ldY, strideY, noise_kind, \
+                                      s, strides, prior_kind, mw, stridemw, Lw, ldl, strideLw, mw_post, ldmp,        \
+                                      stride_mwpost, T_post, ldt, strideT, Lw_post, ldlp, strideLp, logpdf,         \
+                                      stride_lp, info);                                                             \
   }                                                                                                                 \
   int blr_posterior_##SUF(blr_handle* h, int layout, int64_t D, int64_t N, const T* X, int64_t ldx, const T* y,     \
                           int noise_kind, const T* s, int prior_kind, const T* mw, const T* Lw, int64_t ldl,        \

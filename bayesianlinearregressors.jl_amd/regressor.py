@@ -29,6 +29,7 @@ __all__ = [
     "LOO", "loo", "loo_map",
     "EvidenceGrid", "logpdf_grid", "posterior_best", "logpdf_grid_map",
     "posterior_ragged", "logpdf_ragged",
+    "posterior_columns", "logpdf_columns_map", "posterior_columns_map",
 ]
 
 
@@ -707,6 +708,120 @@ def posterior_map(fxs, ys):
         post = BayesianLinearRegressor(mw_post, _wrap_like(base.Lw, T, A))
         posts.append(BasisFunctionRegressor(post, fx.f.phi) if isinstance(fx.f, BasisFunctionRegressor) else post)
     return posts
+
+
+# ---------------------------------------------------------------------------------------------------
+# matrix targets: S columns per regressor share the design matrix, the noise and the prior (blr_posterior_multi_batched_*)
+# ---------------------------------------------------------------------------------------------------
+def _columns_many(fxs, Ys, want_posterior):
+    """[(logpdf[S], means D x S, T, A)] per data set.  Equally shaped problems (same D, N, S, layout, noise and prior kind) with
+    isotropic or diagonal noise go through blr_posterior_multi_batched_* in ONE call: one factor per data set, shared by its
+    columns.  Mixed shapes or a dense noise covariance fall back to a loop over logpdf_columns / posterior.  The first data set
+    (in order) that is not positive definite raises PosDefException with its position as ``index``."""
+    fxs, Ys = list(fxs), list(Ys)
+    if len(fxs) != len(Ys):
+        raise ValueError("as many target matrices as finite regressors are needed")
+    if not fxs:
+        return []
+    Ys = [np.asarray(Y) for Y in Ys]
+    if any(Y.ndim != 2 for Y in Ys):
+        raise ValueError("every Y must be an N x S matrix")
+
+    def loop():
+        out = []
+        for fx, Y in zip(fxs, Ys):
+            if not want_posterior:
+                out.append((np.asarray(logpdf_columns(fx, Y)), None, None, None))
+                continue
+            cols = [_fused(fx, Y[:, j], want_posterior=True) for j in range(Y.shape[1])]
+            out.append((np.array([c[0] for c in cols]), np.stack([c[1] for c in cols], axis=1) if cols else None,
+                        cols[0][2] if cols else None, cols[0][3] if cols else None))
+        return out
+
+    if any(isinstance(fx.f, BasisFunctionRegressor) and isinstance(fx.f.phi, RandomFourierFeatures) for fx in fxs):
+        return loop()
+    fbs = [_to_finite_blr(fx) for fx in fxs]
+    dtype = np.float32 if all(_dtype_of(fb.f.mw, Y) == np.float32 for fb, Y in zip(fbs, Ys)) else np.float64
+    probs = []
+    for fb, Y in zip(fbs, Ys):
+        X, layout, ldx, D, N = _x_layout(fb.x, dtype)
+        if Y.shape[0] != N:
+            raise ValueError("length(y) != size(fx.x.X, 2)")  # reference :74
+        s, noise_kind = _noise(fb.Sy, N, dtype)
+        Lw, prior_kind, ldl = _prior(fb.f.Lw, D, dtype)
+        probs.append((X, layout, ldx, D, N, np.asfortranarray(Y, dtype=dtype), s, noise_kind, _mean_vector(fb.f.mw, D, dtype), Lw,
+                      prior_kind, ldl, isinstance(fb.f.Lw, PDMat)))
+    X0, layout, ldx, D, N, Y0, _, noise_kind, _, _, prior_kind, ldl, pdmat = probs[0]
+    S = Y0.shape[1]
+    sig = {(q[0].shape, q[0].flags.f_contiguous, q[1], q[3], q[4], q[5].shape[1], q[7], q[10], q[12]) for q in probs}
+    if noise_kind == _abi.NOISE_DENSE or D == 0 or S == 0 or len(sig) != 1:
+        return loop()
+    nb = len(probs)
+    Xb = np.stack([q[0].reshape(-1, order="A") for q in probs])
+    Yb = np.stack([q[5].reshape(-1, order="F") for q in probs])  # N x S column-major per data set, ldY = N
+    sb = np.stack([q[6] for q in probs])
+    mwb = np.stack([q[8] for q in probs])
+    Lb = np.stack([q[9].reshape(-1, order="A") for q in probs])
+    lp = np.zeros((nb, S), dtype=np.float64)
+    info = np.zeros(nb, dtype=np.int32)
+    if want_posterior:
+        means = np.empty((nb, D * S), dtype=dtype)
+        Tb = np.empty((nb, D * D), dtype=dtype)
+        Ab = np.empty((nb, D * D), dtype=dtype) if not pdmat else None
+    else:
+        means = Tb = Ab = None
+    _handle().posterior_multi_batched(dtype, _abi.MEM_HOST, layout, nb, D, N, S, Xb, ldx, Xb.shape[1], Yb, max(N, 1), Yb.shape[1],
+                                      noise_kind, sb, sb.shape[1], prior_kind, mwb, D, Lb, ldl, Lb.shape[1], means, D, D * S, Tb, D,
+                                      D * D, Ab, D, D * D, lp, S, info)
+    bad = np.flatnonzero(info > 0)
+    if bad.size:
+        e = _abi.PosDefException(int(info[bad[0]]))
+        e.index = int(bad[0])
+        raise e
+    out = []
+    for b in range(nb):
+        if want_posterior:
+            out.append((lp[b], means[b].reshape((D, S), order="F"), Tb[b].reshape((D, D), order="F"),
+                        Ab[b].reshape((D, D), order="F") if Ab is not None else None))
+        else:
+            out.append((lp[b], None, None, None))
+    return out
+
+
+def _column_posteriors(fx, means, T, A):
+    base = fx.f.blr if isinstance(fx.f, BasisFunctionRegressor) else fx.f
+    Lw_post = _wrap_like(base.Lw, T, A)  # ONE precision object: the S posteriors of a data set share the factor
+    posts = [BayesianLinearRegressor(means[:, j], Lw_post) for j in range(means.shape[1])]
+    if isinstance(fx.f, BasisFunctionRegressor):
+        return [BasisFunctionRegressor(p, fx.f.phi) for p in posts]
+    return posts
+
+
+def posterior_columns(fx, Y):
+    """[posterior(fx, Y[:, s]) for s in range(S)] (reference :60-69 per column of a matrix target) in one library call: the S
+    posterior regressors differ in their mean only and share one precision object."""
+    return posterior_columns_map([fx], [Y])[0]
+
+
+def logpdf_columns_map(fxs, Ys):
+    """logpdf(fx, Y::AbstractMatrix) under a map over data sets (reference :55-58): a (B, S) array, from one library call when the
+    problems have one shape (blr_posterior_multi_batched_*)."""
+    res = _columns_many(fxs, Ys, want_posterior=False)
+    if not res:
+        return np.zeros((0, 0))
+    if len({r[0].shape for r in res}) != 1:
+        raise ValueError("the target matrices must have one number of columns for a (B, S) result")
+    return np.stack([r[0] for r in res])
+
+
+def posterior_columns_map(fxs, Ys):
+    """Per data set the S posterior regressors of its target columns, sharing one factor (reference :60-69 under a map over fxs with
+    matrix targets), from one library call when the problems have one shape."""
+    fxs = list(fxs)
+    out = []
+    for fx, (_, means, T, A) in zip(fxs, _columns_many(fxs, Ys, want_posterior=True)):
+        out.append([] if means is None else _column_posteriors(fx, means, T, A))
+    return out
 
 
 LOO = namedtuple("LOO", ["mean", "var", "logpdf", "total"])

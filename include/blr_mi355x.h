@@ -102,7 +102,7 @@ const char* blr_last_route(blr_handle* h);
 int blr_get_stat(blr_handle* h, const char* key, int64_t* value);
 int blr_reset_stats(blr_handle* h);
 /* The handle's device scratch (factorisation workspaces of D > 128 calls -- up to 8 GiB for a large batched call, see CHAIN_WS_MB --
- * the feature matrix of blr_posterior_rff_*, the int8 / marginal side buffers, the statistics buffer of blr_logpdf_grid_*, the offsets / order of blr_posterior_ragged_*) only ever GROWS between calls; this drains the
+ * the feature matrix of blr_posterior_rff_*, the int8 / marginal side buffers, the statistics buffer of blr_logpdf_grid_*, the offsets / order of blr_posterior_ragged_*, column 0's evidences and -- T_post = NULL -- the factors of blr_posterior_multi_batched_*) only ever GROWS between calls; this drains the
  * stream and frees all of it.  The next call allocates what it needs again. */
 int blr_release_workspace(blr_handle* h);
 
@@ -230,6 +230,60 @@ int blr_posterior_ragged_f32(blr_handle* h, int memspace, int layout, int64_t B,
                              float* T_post, int64_t ldt, int64_t strideT,
                              float* Lw_post, int64_t ldlp, int64_t strideLp,
                              double* logpdf, int32_t* info);
+
+/* ---- S target columns per regressor in one call: the batched multi-output posterior ---------------------------------
+ * Replaces: reference src/bayesian_linear_regression.jl:55-58 (logpdf), :60-69 (posterior) and :72-89 (shared quantities) under a
+ * map over fxs with MATRIX targets -- which blr_posterior_batched_* serves only by S calls with the y pointer stepped by one
+ * column (X read S times, the Gram matrix formed and factorised S times) and blr_logpdf_multi_* only for one data set, without the
+ * factor.
+ * Regressor b reads X + b*strideX, Y + b*strideY (N x S column-major, ldY >= N), s + b*strides, mw + b*stridemw, Lw + b*strideLw; a
+ * stride of 0 shares an input (strideX = 0 and strideY = 0 included).  Column s of regressor b gets exactly what
+ * blr_posterior_batched_* gives for (X_b, Y_b[:, s], s_b, mw_b, Lw_b): its mean at mw_post + b*stride_mwpost + s*ldmp (D x S per
+ * regressor, ldmp >= D), its evidence at logpdf[b*stride_lp + s] (double).  T_post (the upper factor) and Lw_post do not depend on
+ * the column: ONE of each per regressor, written as blr_posterior_batched_* writes them.  info[B]: one status per regressor for the
+ * shared factorisation, with that entry point's LAPACK codes; when info[b] != 0 every mean and the factor of that regressor are left
+ * untouched and all S of its evidences are NaN.  The call returns 0 when the launches succeeded.  Any output may be NULL.
+ * Isotropic or diagonal noise (dense noise: argument error), all three prior kinds, both layouts of X, both memspaces.  Aliasing an
+ * output with an input is not supported: mw_post == mw or T_post == Lw is an argument error (the columns after the first still need
+ * the prior mean).  Output strides that overlap for B > 1 are argument errors: stride_mwpost < ldmp*S, stride_lp < S, and the
+ * T_post / Lw_post rules of blr_posterior_batched_*.  The argument checks come before the handle's.  B = 0 or S = 0 is a no-op;
+ * N = 0 is allowed (every column's mean is the prior mean, its evidence 0).  Limits: 1 <= D <= 8192, S <= 2^20, N <= 2^30.
+ * D <= 128 (csrc/blr_multi.hpp).  Step 1: column 0 of every regressor goes through the dispatch of
+ * blr_posterior_batched_*, unchanged -- int8-sliced, one-wave or fused kernel, whatever the shape gets there (blr_last_route names
+ * it); the factor goes to T_post, or to handle workspace when T_post is NULL (B D^2 elements, counted by "workspace_bytes", freed
+ * by blr_release_workspace).  Step 2: ONE launch of multi_cols_kernel over regressors x column passes (63 further columns per pass)
+ * streams X once per pass: residuals of all its columns, b_s = X S^-1 (y_s - X'mw) on the fp64 / fp32 matrix cores, q_s in double;
+ * then the two triangular solves against the finished factor held as a packed triangle in LDS, and
+ *   logpdf_s = logpdf_0 + (q_0 - |u_0|^2) / 2 - (q_s - |u_s|^2) / 2      (u_s = T^-T b_s; the log-determinants are column 0's).
+ * The launch count does not depend on B.  An async handle in device memspace only enqueues; column 0's status is read on the device.
+ * D > 128: correct, not fast -- one regressor after the other, column 0 through the pipeline of blr_posterior_batched_*, the further
+ * columns through that of blr_logpdf_multi_*; the call synchronises whatever the handle's async flag says.
+ * Numerics: bit-reproducible from call to call; the bits of a regressor do not depend on B or on its position; for s >= 1 they do
+ * not depend on S, on the column's position or on the other columns' data.  Column 0, T_post, Lw_post and info are bit for bit what
+ * blr_posterior_batched_* writes on the same handle for (X, Y[:, 0]): with S = 1 the call IS that entry point.  Columns s >= 1 hold
+ * the accuracy stated there for the route column 0 took (the factor is the same; their own products are fp64 / fp32 as the element
+ * type says, never int8).
+ * _f32: X, Y, s, mw, Lw, mw_post, T_post, Lw_post are float; logpdf stays double. */
+int blr_posterior_multi_batched_f64(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t N, int64_t S,
+                                    const double* X, int64_t ldx, int64_t strideX,
+                                    const double* Y, int64_t ldY, int64_t strideY,
+                                    int noise_kind, const double* s, int64_t strides,
+                                    int prior_kind, const double* mw, int64_t stridemw,
+                                    const double* Lw, int64_t ldl, int64_t strideLw,
+                                    double* mw_post, int64_t ldmp, int64_t stride_mwpost,
+                                    double* T_post, int64_t ldt, int64_t strideT,
+                                    double* Lw_post, int64_t ldlp, int64_t strideLp,
+                                    double* logpdf, int64_t stride_lp, int32_t* info);
+int blr_posterior_multi_batched_f32(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t N, int64_t S,
+                                    const float* X, int64_t ldx, int64_t strideX,
+                                    const float* Y, int64_t ldY, int64_t strideY,
+                                    int noise_kind, const float* s, int64_t strides,
+                                    int prior_kind, const float* mw, int64_t stridemw,
+                                    const float* Lw, int64_t ldl, int64_t strideLw,
+                                    float* mw_post, int64_t ldmp, int64_t stride_mwpost,
+                                    float* T_post, int64_t ldt, int64_t strideT,
+                                    float* Lw_post, int64_t ldlp, int64_t strideLp,
+                                    double* logpdf, int64_t stride_lp, int32_t* info);
 
 /* single regressor, host pointers; returns info (see "Return codes") */
 int blr_posterior_f64(blr_handle* h, int layout, int64_t D, int64_t N, const double* X, int64_t ldx,

@@ -345,6 +345,74 @@ function posterior_map(fxs::AbstractVector{<:FiniteGP}, ys::AbstractVector{<:Abs
     end
 end
 
+# blr_posterior_multi_batched_* (include/blr_mi355x.h): B regressors with S target columns each (Y: N x S per regressor, ldY), one
+# factor per regressor shared by its columns, a mean (D x S, ldmp) and an evidence (logpdf[b*stride_lp + s]) per column.  The arrays
+# are host Arrays (MEM_HOST) or raw device pointers.
+function posterior_multi_batched_call(h, ::Type{T}, memspace, layout, B, D, N, S, X, ldx, strideX, Y, ldY, strideY, nk, s, strides, pk,
+                                      mw, stridemw, Lw, ldl, strideLw, mw_post, ldmp, stride_mwpost, Tp, ldt, strideT, Ap, ldlp, strideLp,
+                                      lp, stride_lp, info) where {T<:Elt}
+    GC.@preserve X Y s mw Lw mw_post Tp Ap lp info begin
+        if T === Float64
+            ccall((:blr_posterior_multi_batched_f64, LIB), Cint,
+                  (Ptr{Cvoid}, Cint, Cint, Int64, Int64, Int64, Int64, Ptr{T}, Int64, Int64, Ptr{T}, Int64, Int64, Cint, Ptr{T}, Int64, Cint, Ptr{T}, Int64,
+                   Ptr{T}, Int64, Int64, Ptr{T}, Int64, Int64, Ptr{T}, Int64, Int64, Ptr{T}, Int64, Int64, Ptr{Cdouble}, Int64, Ptr{Int32}),
+                  h, memspace, layout, B, D, N, S, X, ldx, strideX, Y, ldY, strideY, nk, s, strides, pk, mw, stridemw,
+                  Lw, ldl, strideLw, mw_post, ldmp, stride_mwpost, Tp, ldt, strideT, Ap, ldlp, strideLp, lp, stride_lp, info)
+        else
+            ccall((:blr_posterior_multi_batched_f32, LIB), Cint,
+                  (Ptr{Cvoid}, Cint, Cint, Int64, Int64, Int64, Int64, Ptr{T}, Int64, Int64, Ptr{T}, Int64, Int64, Cint, Ptr{T}, Int64, Cint, Ptr{T}, Int64,
+                   Ptr{T}, Int64, Int64, Ptr{T}, Int64, Int64, Ptr{T}, Int64, Int64, Ptr{T}, Int64, Int64, Ptr{Cdouble}, Int64, Ptr{Int32}),
+                  h, memspace, layout, B, D, N, S, X, ldx, strideX, Y, ldY, strideY, nk, s, strides, pk, mw, stridemw,
+                  Lw, ldl, strideLw, mw_post, ldmp, stride_mwpost, Tp, ldt, strideT, Ap, ldlp, strideLp, lp, stride_lp, info)
+        end
+    end
+end
+
+# logpdf(fx, Y::AbstractMatrix) under a map over data sets -> B x S matrix of column evidences.  Equal shapes (D, N, S, layout,
+# isotropic or diagonal noise, prior kind, element type) make ONE blr_posterior_multi_batched_* call; anything else maps column by column.
+function logpdf_map(fxs::AbstractVector{<:FiniteGP}, Ys::AbstractVector{<:AbstractMatrix{<:Real}})
+    length(fxs) == length(Ys) || throw(DimensionMismatch("as many target matrices as finite regressors are needed"))
+    B = length(fxs)
+    B == 0 && return zeros(Float64, 0, 0)
+    loop() = permutedims(reduce(hcat, [Float64[logpdf(fx, view(Y, :, j)) for j in axes(Y, 2)] for (fx, Y) in zip(fxs, Ys)]))
+    any(fx -> fx.f isa BasisFunctionRegressor && fx.f.ϕ isa RandomFourierFeatures, fxs) && return loop()
+    fbs = map(to_blr, fxs)
+    xls, nzs, prs = map(fb -> xlayout(fb.x), fbs), map(fb -> noise(fb.Σy), fbs), map(fb -> prior(fb.f.Λw), fbs)
+    (any(isnothing, xls) || any(isnothing, nzs) || any(isnothing, prs)) && return loop()
+    X1, layout, _, D, N = xls[1]
+    T = eltype(X1)
+    S = size(Ys[1], 2)
+    nk, pk = nzs[1][2], prs[1][2]
+    (nk == DENSEN || D == 0 || S == 0) && return loop()
+    alike = all(b -> eltype(xls[b][1]) === T && xls[b][2] == layout && xls[b][4] == D && xls[b][5] == N && nzs[b][2] == nk &&
+                     prs[b][2] == pk && size(Ys[b]) == (N, S) && length(fbs[b].f.mw) == D, 1:B)
+    alike || return loop()
+    rows, cols = layout == COLVECS ? (D, N) : (N, D)
+    Xb = Array{T}(undef, rows, cols, B)
+    Yb = Array{T}(undef, N, S, B)
+    ns = nk == ISOTROPIC ? 1 : N
+    sb = Matrix{T}(undef, ns, B)
+    mwb = Matrix{T}(undef, D, B)
+    Lb = pk == P_DIAG ? Matrix{T}(undef, D, B) : Array{T}(undef, D, D, B)
+    for b in 1:B
+        copyto!(view(Xb, :, :, b), xls[b][1])
+        Yb[:, :, b] .= Ys[b]
+        sb[:, b] .= view(nzs[b][1], 1:ns)
+        mwb[:, b] .= fbs[b].f.mw
+        pk == P_DIAG ? (Lb[:, b] .= prs[b][1]) : copyto!(view(Lb, :, :, b), prs[b][1])
+    end
+    ldl, strideL = pk == P_DIAG ? (1, D) : (D, D * D)
+    lp = zeros(Cdouble, S, B)
+    info = zeros(Int32, B)
+    h = handle()
+    check(h, posterior_multi_batched_call(h, T, MEM_HOST, layout, B, D, N, S, Xb, rows, rows * cols, Yb, max(N, 1), N * S, nk, sb, ns, pk,
+                                          mwb, D, Lb, ldl, strideL, Ptr{T}(C_NULL), D, D * S, Ptr{T}(C_NULL), D, D * D,
+                                          Ptr{T}(C_NULL), D, D * D, lp, S, info))
+    bad = findfirst(>(0), info)
+    bad === nothing || throw(PosDefException(Int(info[bad])))
+    return permutedims(lp)
+end
+
 # The reference's own methods stay reachable after install_overrides! has replaced them: the fallbacks run in the world age
 # recorded when this module was loaded (i.e. against the method tables as the reference defined them) -- no recursion.
 const REF_WORLD = Ref{UInt}(0)
@@ -836,6 +904,25 @@ function posterior_ragged!(mw_post::DeviceArray{T}, T_post::DeviceArray{T}, lp::
     check(h, posterior_ragged_call(h, T, MEM_DEVICE, COLVECS, B, D, offsets, X.ptr, D, y.ptr, isotropic ? ISOTROPIC : DIAGONALN, s.ptr,
                                    isotropic ? 1 : 0, P_DIAG, mw.ptr, D, Λdiag.ptr, 1, 0, mw_post.ptr, D, T_post.ptr, D, D * D,
                                    Ptr{T}(C_NULL), D, D * D, lp.ptr, info.ptr))
+    return nothing
+end
+
+"""
+    posterior_multi_batched!(mw_post, T_post, logpdf, info, X, Y, s, mw, Λdiag; D, N, S, B, isotropic)
+
+B regressors with S target columns each in ONE call (D ≤ 128: column 0 through the batched update, the other columns in one more
+launch), everything device resident: X is D×N×B (ColVecs), Y N×S×B, s one variance per regressor (`isotropic`) or N×B, mw D×B, Λdiag
+the D diagonal entries of a prior precision shared by the batch; outputs mw_post D×S×B, T_post D×D×B (ONE upper factor per
+regressor, shared by its columns), logpdf S×B (Float64), info B (Int32).  Reference semantics per column: `:55-69` under a map over
+fxs with matrix targets.
+"""
+function posterior_multi_batched!(mw_post::DeviceArray{T}, T_post::DeviceArray{T}, lp::DeviceArray{Float64}, info::DeviceArray{Int32},
+                                  X::DeviceArray{T}, Y::DeviceArray{T}, s::DeviceArray{T}, mw::DeviceArray{T}, Λdiag::DeviceArray{T};
+                                  D::Int, N::Int, S::Int, B::Int, isotropic::Bool) where {T<:Elt}
+    h = handle()
+    check(h, posterior_multi_batched_call(h, T, MEM_DEVICE, COLVECS, B, D, N, S, X.ptr, D, D * N, Y.ptr, max(N, 1), N * S,
+                                          isotropic ? ISOTROPIC : DIAGONALN, s.ptr, isotropic ? 1 : N, P_DIAG, mw.ptr, D, Λdiag.ptr, 1, 0,
+                                          mw_post.ptr, D, D * S, T_post.ptr, D, D * D, Ptr{T}(C_NULL), D, D * D, lp.ptr, S, info.ptr))
     return nothing
 end
 
