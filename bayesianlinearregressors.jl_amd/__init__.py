@@ -38,6 +38,9 @@ from .regressor import (
     mean,
     mean_and_cov,
     mean_and_var,
+    mean_and_var_columns,
+    mean_and_var_columns_map,
+    mean_columns,
     posterior,
     posterior_best,
     posterior_columns,
@@ -60,4 +63,5 @@ __all__ = [
     "EvidenceGrid", "logpdf_grid", "posterior_best", "logpdf_grid_map",
     "posterior_ragged", "logpdf_ragged",
     "posterior_columns", "logpdf_columns_map", "posterior_columns_map",
+    "mean_and_var_columns", "mean_columns", "mean_and_var_columns_map",
 ]

@@ -20,6 +20,7 @@ NOISE_ISOTROPIC, NOISE_DIAGONAL, NOISE_DENSE = 0, 1, 2
 PRIOR_DENSE, PRIOR_UPPER_FACTOR, PRIOR_DIAGONAL = 0, 1, 2
 MEM_HOST, MEM_DEVICE = 0, 1
 MULTI_COLS_PER_PASS = 64  # csrc/blr_multi.hpp kMultiColsPerPass: column slots of one pass of multi_cols_kernel (slot 0 = column 0)
+MARG_COLS_PER_PASS = 16  # csrc/blr_marg_multi.hpp kMargColsPerPass: mean columns of one pass of marginals_cols_kernel
 
 _i64, _int, _vp = C.c_int64, C.c_int, C.c_void_p
 _H = C.c_void_p
@@ -97,6 +98,9 @@ for _suf in ("f64", "f32"):
     _SIGS[f"blr_marginals_batched_{_suf}"] = (
         [_H, _int, _int, _i64, _i64, _i64, _vp, _i64, _i64, _int, _vp, _i64, _int, _vp, _i64, _vp, _i64, _i64,
          _vp, _i64, _vp, _i64, _vp], _int)
+    _SIGS[f"blr_marginals_multi_batched_{_suf}"] = (
+        [_H, _int, _int, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _int, _vp, _i64, _int, _vp, _i64, _i64, _vp, _i64, _i64,
+         _vp, _i64, _i64, _vp, _i64, _vp], _int)
     _SIGS[f"blr_rand_{_suf}"] = (
         [_H, _int, _int, _i64, _i64, _i64, _vp, _i64, _int, _vp, _int, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64], _int)
     _SIGS[f"blr_rand_batched_{_suf}"] = (
@@ -395,6 +399,15 @@ class Handle:
         fn = getattr(self.lib, f"blr_marginals_batched_{suffix(dtype)}")
         return self.check(fn(self._h, memspace, layout, B, D, N, _ptr(X), ldx, strideX, noise_kind, _ptr(s), strides,
                              prior_kind, _ptr(mw), stridemw, _ptr(Lw), ldl, strideLw, _ptr(mean), stridemean,
+                             _ptr(var), stridevar, _ptr(info)))
+
+    def marginals_multi_batched(self, dtype, memspace, layout, B, D, N, S, X, ldx, strideX, noise_kind, s, strides, prior_kind,
+                                M, ldm, strideM, Lw, ldl, strideLw, mean, ldmean, stridemean, var, stridevar, info):
+        """S mean columns (M: D x S per regressor, as blr_posterior_multi_batched_* writes mw_post) and one variance per input
+        for B regressors in one call; include/blr_mi355x.h blr_marginals_multi_batched_* (one status per regressor in info)."""
+        fn = getattr(self.lib, f"blr_marginals_multi_batched_{suffix(dtype)}")
+        return self.check(fn(self._h, memspace, layout, B, D, N, S, _ptr(X), ldx, strideX, noise_kind, _ptr(s), strides,
+                             prior_kind, _ptr(M), ldm, strideM, _ptr(Lw), ldl, strideLw, _ptr(mean), ldmean, stridemean,
                              _ptr(var), stridevar, _ptr(info)))
 
     def rand(self, dtype, memspace, layout, D, N, S, X, ldx, noise_kind, s, prior_kind, mw, Lw, ldl, Z1, ldz1, Z2, ldz2,

@@ -33,6 +33,7 @@
 #include "blr_grid.hpp"
 #include "blr_ragged.hpp"
 #include "blr_multi.hpp"
+#include "blr_marg_multi.hpp"
 #include "blr_host.hpp"
 #include "blr_large_plan.hpp"
 
@@ -3360,6 +3361,139 @@ int posterior_multi_batched(blr_handle* h, int memspace, int layout, int64_t B, 
   return io.finish();
 }
 
+// ---- marginals of a batched multi-output posterior: S mean columns, one variance per input (blr_marginals_multi_batched_*) ----
+inline const void* marginals_cols_kernel_ptr(double, int layout) { return marginals_cols_kernel_ptr_f64(layout); }
+inline const void* marginals_cols_kernel_ptr(float, int layout) { return marginals_cols_kernel_ptr_f32(layout); }
+inline void marginals_cols_kernel_launch(int layout, dim3 grid, size_t lds, hipStream_t st, const MargColsArgs<double>& a) { marginals_cols_kernel_launch_f64(layout, grid, lds, st, a); }
+inline void marginals_cols_kernel_launch(int layout, dim3 grid, size_t lds, hipStream_t st, const MargColsArgs<float>& a) { marginals_cols_kernel_launch_f32(layout, grid, lds, st, a); }
+// marginals_cols_kernel reads the image marg_image_kernel writes: one layout, stated twice
+static_assert(MargColsImg<double>::IMG_ELEMS == MargGemmCfg<double>::IMG_ELEMS && MargColsImg<float>::IMG_ELEMS == MargGemmCfg<float>::IMG_ELEMS &&
+                  MargColsImg<double>::frag0(5) == MargGemmCfg<double>::frag0(5) && MargColsImg<double>::d_of(7, 3) == MargGemmCfg<double>::d_of(7, 3) &&
+                  MargColsImg<float>::d_of(7, 3) == MargGemmCfg<float>::d_of(7, 3) && kMargMaxD == kPB && kMargMaxD == kMaxSmallD,
+              "blr_marg_multi.hpp and blr_marginals.hpp disagree on the image of L^-T");
+
+template <typename T>
+int marginals_multi_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t N, int64_t S, const T* X, int64_t ldx,
+                            int64_t strideX, int noise_kind, const T* s, int64_t strides, int prior_kind, const T* M, int64_t ldm,
+                            int64_t strideM, const T* Lw, int64_t ldl, int64_t strideLw, T* mean, int64_t ldmean, int64_t stridemean,
+                            T* var, int64_t stridevar, int32_t* info) {
+  // (the argument checks come before the handle's: they need no device)
+  if (h) h->err.clear();
+  if (memspace != BLR_MEM_HOST && memspace != BLR_MEM_DEVICE) return bad_arg(h, 2, "memspace");
+  if (layout != BLR_LAYOUT_COLVECS && layout != BLR_LAYOUT_ROWVECS) return bad_arg(h, 3, "unknown layout (reference :26-31)");
+  if (B < 0 || B > (1 << 30)) return bad_arg(h, 4, "B out of range (0..2^30)");
+  if (D < 1 || D > kMaxLargeD) return bad_arg(h, 5, "D out of range (1..8192)");
+  if (N < 0 || N > (1 << 30)) return bad_arg(h, 6, "N out of range");
+  if (S < 0 || S > (1 << 20)) return bad_arg(h, 7, "S out of range (0..2^20)");
+  if (S == 0) mean = nullptr;  // (var only: M and mean are ignored)
+  if (B == 0 || N == 0 || (!mean && !var)) return 0;
+  if (!X) return bad_arg(h, 8, "X is NULL");
+  if (layout == BLR_LAYOUT_COLVECS ? ldx < D : ldx < N) return bad_arg(h, 9, "ldx too small");
+  if (strideX < 0) return bad_arg(h, 10, "strideX < 0");
+  if (noise_kind != BLR_NOISE_ISOTROPIC && noise_kind != BLR_NOISE_DIAGONAL)
+    return bad_arg(h, 11, "noise_kind (isotropic or diagonal; dense Sigma_y is not supported for batched marginals)");
+  if (var && !s) return bad_arg(h, 12, "s is NULL");
+  if (strides < 0) return bad_arg(h, 13, "strides < 0");
+  if (prior_kind != BLR_PRIOR_DENSE && prior_kind != BLR_PRIOR_UPPER_FACTOR && prior_kind != BLR_PRIOR_DIAGONAL)
+    return bad_arg(h, 14, "prior_kind");
+  if (mean && !M) return bad_arg(h, 15, "M is NULL");
+  if (mean && ldm < D) return bad_arg(h, 16, "ldm < D");
+  if (strideM < 0) return bad_arg(h, 17, "strideM < 0");
+  if (var && !Lw) return bad_arg(h, 18, "Lw is NULL");
+  if (var && prior_kind != BLR_PRIOR_DIAGONAL && ldl < D) return bad_arg(h, 19, "ldl < D");
+  if (strideLw < 0) return bad_arg(h, 20, "strideLw < 0");
+  if (mean && ldmean < N) return bad_arg(h, 22, "ldmean < N");
+  if (mean && B > 1 && stridemean < ldmean * S) return bad_arg(h, 23, "stridemean < ldmean * S");
+  if (var && B > 1 && stridevar < N) return bad_arg(h, 25, "stridevar < N");
+  if (!info) return bad_arg(h, 26, "info is NULL");
+  if (!h) return -1;
+  HIP_TRY(h, hipSetDevice(h->device));
+
+  CallIO io(h, memspace);
+  const T *X_d = nullptr, *s_d = nullptr, *M_d = nullptr, *Lw_d = nullptr;
+  T *mean_d = nullptr, *var_d = nullptr;
+  int32_t* info_d = nullptr;
+  int rc;
+  const size_t x_one = layout == BLR_LAYOUT_COLVECS ? mat_extent(D, N, ldx) : mat_extent(N, D, ldx);
+  const size_t lw_one = prior_kind == BLR_PRIOR_DIAGONAL ? (size_t)D : mat_extent(D, D, ldl);
+  if ((rc = io.in(X, extent(B, strideX, x_one), &X_d))) return rc;
+  if ((rc = io.in(var ? s : (const T*)nullptr, extent(B, strides, noise_kind == BLR_NOISE_DIAGONAL ? (size_t)N : 1), &s_d))) return rc;
+  if ((rc = io.in(mean ? M : (const T*)nullptr, extent(B, strideM, mat_extent(D, S, ldm)), &M_d))) return rc;
+  if ((rc = io.in(var ? Lw : (const T*)nullptr, extent(B, strideLw, lw_one), &Lw_d))) return rc;
+  if ((rc = io.out(mean, extent(B, stridemean, mat_extent(N, S, ldmean)), &mean_d))) return rc;
+  if ((rc = io.out(var, extent(B, stridevar, (size_t)N), &var_d))) return rc;
+  if ((rc = io.out(info, (size_t)B, &info_d))) return rc;
+
+  if (D > kMaxSmallD) {
+    // correct, not fast: var of the whole batch through the route of blr_marginals_batched_* (which also writes the status), then the
+    // means one regressor after the other as X'W for S weight vectors (the path of blr_apply_weights_*); the call synchronises
+    const AsyncScope drain(h, false);
+    std::vector<int32_t> st((size_t)B, 0);
+    if (var_d) {
+      // (mw is not read without a mean; X stands in as a non-NULL pointer)
+      rc = marginals_batched<T>(h, BLR_MEM_DEVICE, layout, B, D, N, X_d, ldx, strideX, noise_kind, s_d, strides, prior_kind, X_d, 0, Lw_d, ldl,
+                                strideLw, (T*)nullptr, 0, var_d, stridevar, info_d);
+      if (rc) return rc;  // (device pointers and in-range sizes: a HIP failure, not an argument index of the inner call)
+      HIP_TRY(h, hipMemcpyAsync(st.data(), info_d, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+      HIP_TRY(h, hipStreamSynchronize(h->stream));
+    } else {
+      HIP_TRY(h, hipMemsetAsync(info_d, 0, (size_t)B * sizeof(int32_t), h->stream));
+    }
+    for (int64_t b = 0; mean_d && b < B; ++b) {
+      if (st[(size_t)b] != 0) continue;  // outputs of that regressor stay untouched
+      launch_project<T>(h, layout, D, N, S, X_d + b * strideX, ldx, M_d + b * strideM, ldm, (const T*)nullptr, BLR_NOISE_ISOTROPIC,
+                        (const T*)nullptr, 0, mean_d + b * stridemean, ldmean);
+    }
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return io.finish();
+  }
+
+  // D <= 128: the factor of a dense prior once per regressor (prior_factor), the triangular inverse of every factor as an MFMA image
+  // (marg_image_kernel), then ONE launch of marginals_cols_kernel per chunk of regressors over (column passes x tile groups, regressors)
+  MargColsArgs<T> a{};
+  a.ldx = ldx; a.strideX = strideX; a.strides = strides; a.ldm = ldm; a.strideM = strideM;
+  a.ldmean = ldmean; a.stridemean = stridemean; a.stridevar = stridevar;
+  a.noise_kind = noise_kind; a.D = (int)D; a.N = (int)N; a.S = (int)S;
+  const T* U = nullptr;
+  int64_t ldu = 0, strideU = 0;
+  int kind = prior_kind;
+  int32_t* chol_info = nullptr;
+  if (var_d && (rc = prior_factor<T>(h, B, D, prior_kind, Lw_d, ldl, strideLw, &U, &ldu, &strideU, &kind, &chol_info))) return rc;
+  a.prior_kind = kind;
+  if (chol_info) HIP_TRY(h, hipMemcpyAsync(info_d, chol_info, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, h->stream));
+  else HIP_TRY(h, hipMemsetAsync(info_d, 0, (size_t)B * sizeof(int32_t), h->stream));
+  const bool with_image = var_d && kind == BLR_PRIOR_UPPER_FACTOR;
+  using MG = MargGemmCfg<T>;
+  const int64_t max_chunk = ((int64_t)256 << 20) / (MG::IMG_ELEMS * (int64_t)sizeof(T));  // images of a chunk within 256 MiB
+  const int64_t chunk = std::min<int64_t>(std::min<int64_t>(B, 65535), with_image ? max_chunk : 65535);
+  const size_t lds = marg_cols_lds_bytes(sizeof(T), (int)D, with_image);
+  const void* const kern = marginals_cols_kernel_ptr(T(0), layout);
+  if ((rc = set_lds_once(h, kern, lds))) return rc;
+  if (with_image) {
+    if ((rc = h->aux.reserve(h, (size_t)chunk * MG::IMG_ELEMS * sizeof(T)))) return rc;
+    if ((rc = set_lds_once(h, marg_image_kernel<T>, (size_t)TrsmCfg<T>::LDS_BYTES))) return rc;
+  }
+  const int64_t passes = mean_d ? (S + kMargColsPerPass - 1) / kMargColsPerPass : 1;
+  const int64_t ntiles = (N + kMargTile - 1) / kMargTile;
+  for (int64_t b0 = 0; b0 < B; b0 += chunk) {
+    const int64_t nb = std::min<int64_t>(chunk, B - b0);
+    if (with_image) {
+      T* const img = reinterpret_cast<T*>(h->aux.p);
+      hipLaunchKernelGGL(marg_image_kernel<T>, dim3((unsigned)nb, 2), dim3(kThreads), TrsmCfg<T>::LDS_BYTES, h->stream, U + b0 * strideU, ldu, strideU,
+                         (int)D, img, chol_info ? (const int32_t*)(chol_info + b0) : (const int32_t*)nullptr, 0);
+      a.img = img;
+    }
+    // every workgroup amortises its set-up (the image, the fragments of M) over its tiles: about two workgroups per CU in all
+    const int64_t ngroups = std::max<int64_t>(1, std::min<int64_t>(ntiles, (2 * (int64_t)h->cus + nb * passes - 1) / (nb * passes)));
+    a.X = X_d; a.s = s_d; a.M = M_d; a.dprior = kind == BLR_PRIOR_DIAGONAL ? U : nullptr; a.stridedp = strideU;
+    a.info = chol_info; a.mean = mean_d; a.var = var_d; a.ngroups = (int)ngroups; a.reg0 = (int)b0;
+    marginals_cols_kernel_launch(layout, dim3((unsigned)(passes * ngroups), (unsigned)nb), lds, h->stream, a);
+  }
+  HIP_TRY(h, hipGetLastError());
+  return io.finish();
+}
+
 }  // namespace
 
 // =======================================================================================================
@@ -3654,6 +3788,16 @@ int blr_timer_stop(blr_handle* h, float* elapsed_ms) {
                                       s, strides, prior_kind, mw, stridemw, Lw, ldl, strideLw, mw_post, ldmp,        \
                                       stride_mwpost, T_post, ldt, strideT, Lw_post, ldlp, strideLp, logpdf,         \
                                       stride_lp, info);                                                             \
+  }                                                                                                                 \
+  int blr_marginals_multi_batched_##SUF(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t N,   \
+                                        int64_t S, const T* X, int64_t ldx, int64_t strideX, int noise_kind,        \
+                                        const T* s, int64_t strides, int prior_kind, const T* M, int64_t ldm,       \
+                                        int64_t strideM, const T* Lw, int64_t ldl, int64_t strideLw, T* mean,       \
+                                        int64_t ldmean, int64_t stridemean, T* var, int64_t stridevar,              \
+                                        int32_t* info) {                                                            \
+    return marginals_multi_batched<T>(h, memspace, layout, B, D, N, S, X, ldx, strideX, noise_kind, s, strides,     \
+                                      prior_kind, M, ldm, strideM, Lw, ldl, strideLw, mean, ldmean, stridemean,     \
+                                      var, stridevar, info);                                                        \
   }                                                                                                                 \
   int blr_posterior_##SUF(blr_handle* h, int layout, int64_t D, int64_t N, const T* X, int64_t ldx, const T* y,     \
                           int noise_kind, const T* s, int prior_kind, const T* mw, const T* Lw, int64_t ldl,        \

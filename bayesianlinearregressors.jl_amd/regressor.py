@@ -30,6 +30,7 @@ __all__ = [
     "EvidenceGrid", "logpdf_grid", "posterior_best", "logpdf_grid_map",
     "posterior_ragged", "logpdf_ragged",
     "posterior_columns", "logpdf_columns_map", "posterior_columns_map",
+    "mean_and_var_columns", "mean_columns", "mean_and_var_columns_map",
 ]
 
 
@@ -822,6 +823,96 @@ def posterior_columns_map(fxs, Ys):
     for fx, (_, means, T, A) in zip(fxs, _columns_many(fxs, Ys, want_posterior=True)):
         out.append([] if means is None else _column_posteriors(fx, means, T, A))
     return out
+
+
+# ---------------------------------------------------------------------------------------------------
+# predictions from the S column posteriors of a matrix target: one variance per input, S means (blr_marginals_multi_batched_*)
+# ---------------------------------------------------------------------------------------------------
+def _columns_problem(fs, x, Sy, want_var):
+    """The S regressors of posterior_columns at the inputs x -> (dtype of the weights, operands); they must share one precision."""
+    fs = list(fs)
+    if not fs:
+        raise ValueError("at least one column regressor is needed")
+    blrs = [f.blr if isinstance(f, BasisFunctionRegressor) else f for f in fs]
+    if any(not isinstance(b, BayesianLinearRegressor) for b in blrs):
+        raise TypeError("expected BayesianLinearRegressor or BasisFunctionRegressor columns")
+    if any(b.Lw is not blrs[0].Lw for b in blrs):
+        raise ValueError("the columns must share one precision object")
+    fb = _to_finite_blr(FiniteGP(fs[0], x, Sy))  # (the columns of posterior_columns share phi as they share the factor)
+    return blrs, fb, _dtype_of(*[b.mw for b in blrs])
+
+
+def _columns_operands(blrs, fb, dtype, want_var):
+    X, layout, ldx, D, N = _x_layout(fb.x, dtype)
+    M = np.asfortranarray(np.stack([_mean_vector(b.mw, D, dtype) for b in blrs], axis=1))  # D x S
+    s, noise_kind = _noise(fb.Sy, N, dtype)  # var adds diag(Sigma_y) (:43)
+    if noise_kind == _abi.NOISE_DENSE:
+        s, noise_kind = np.ascontiguousarray(np.diag(s)), _abi.NOISE_DIAGONAL
+    Lw, prior_kind, ldl = _prior(blrs[0].Lw, D, dtype, need_cholesky=want_var)  # :41 _cholesky(Lw)
+    return X, layout, ldx, D, N, M, s, noise_kind, Lw, prior_kind, ldl
+
+
+def _marginals_columns(fs, x, Sy, want_var):
+    blrs, fb, dtype = _columns_problem(fs, x, Sy, want_var)
+    X, layout, ldx, D, N, M, s, noise_kind, Lw, prior_kind, ldl = _columns_operands(blrs, fb, dtype, want_var)
+    S = M.shape[1]
+    m = np.empty((N, S), dtype=dtype, order="F")
+    v = np.empty(N, dtype=dtype) if want_var else None
+    info = np.zeros(1, dtype=np.int32)
+    _handle().marginals_multi_batched(dtype, _abi.MEM_HOST, layout, 1, D, N, S, X, ldx, 0, noise_kind, s if want_var else None, 0,
+                                      prior_kind, M, max(D, 1), 0, Lw if want_var else None, ldl, 0, m, max(N, 1), 0, v, N, info)
+    if info[0] > 0:
+        raise _abi.PosDefException(int(info[0]))
+    return m, v
+
+
+def mean_and_var_columns(fs, x, Sy=1e-18):
+    """mean_and_var(f(x, Sy)) (reference :47) for the S regressors f of posterior_columns -- one precision object, S means -- in one
+    library call: (mean N x S, var N).  The variance does not depend on the column."""
+    return _marginals_columns(fs, x, Sy, True)
+
+
+def mean_columns(fs, x):
+    """mean(f(x)) (reference :33) for the S regressors of posterior_columns in one library call: N x S."""
+    return _marginals_columns(fs, x, 1e-18, False)[0]
+
+
+def mean_and_var_columns_map(fss, xs, Sy=1e-18):
+    """[mean_and_var_columns(fs, x, Sy)] over data sets: one library call when all have the same (D, N, S, layout, noise kind, prior
+    kind, dtype), else a loop.  Sy: one value for all, or a list with one per data set.  The first regressor (in order) whose prior
+    is not positive definite raises PosDefException with its position as ``index``."""
+    fss, xs = [list(fs) for fs in fss], list(xs)
+    if len(fss) != len(xs):
+        raise ValueError("as many input sets as lists of column regressors are needed")
+    if not fss:
+        return []
+    Sys = list(Sy) if isinstance(Sy, (list, tuple)) else [Sy] * len(fss)
+    if len(Sys) != len(fss):
+        raise ValueError("as many noise covariances as lists of column regressors are needed")
+    heads = [_columns_problem(fs, x, sy, True) for fs, x, sy in zip(fss, xs, Sys)]
+    dtype = np.float32 if all(h[2] == np.float32 for h in heads) else np.float64
+    probs = [_columns_operands(h[0], h[1], dtype, True) for h in heads]
+    X0, layout, ldx, D, N, M0, _, noise_kind, _, prior_kind, ldl = probs[0]
+    S = M0.shape[1]
+    sig = {(q[0].shape, q[0].flags.f_contiguous, q[1], q[3], q[4], q[5].shape[1], q[7], q[9]) for q in probs}
+    if len(sig) != 1 or D == 0 or N == 0:
+        return [mean_and_var_columns(fs, x, sy) for fs, x, sy in zip(fss, xs, Sys)]
+    nb = len(probs)
+    Xb = np.stack([q[0].reshape(-1, order="A") for q in probs])
+    Mb = np.stack([q[5].reshape(-1, order="F") for q in probs])  # D x S column-major per data set, ldm = D
+    sb = np.stack([q[6] for q in probs])
+    Lb = np.stack([q[8].reshape(-1, order="A") for q in probs])
+    m = np.empty((nb, N * S), dtype=dtype)
+    v = np.empty((nb, N), dtype=dtype)
+    info = np.zeros(nb, dtype=np.int32)
+    _handle().marginals_multi_batched(dtype, _abi.MEM_HOST, layout, nb, D, N, S, Xb, ldx, Xb.shape[1], noise_kind, sb, sb.shape[1],
+                                      prior_kind, Mb, D, D * S, Lb, ldl, Lb.shape[1], m, N, N * S, v, N, info)
+    bad = np.flatnonzero(info > 0)
+    if bad.size:
+        e = _abi.PosDefException(int(info[bad[0]]))
+        e.index = int(bad[0])
+        raise e
+    return [(m[b].reshape((N, S), order="F"), v[b]) for b in range(nb)]
 
 
 LOO = namedtuple("LOO", ["mean", "var", "logpdf", "total"])

@@ -316,6 +316,53 @@ int blr_marginals_batched_f32(blr_handle* h, int memspace, int layout, int64_t B
                               float* mean, int64_t stridemean, float* var, int64_t stridevar,
                               int32_t* info);
 
+/* ---- S mean columns and one variance per input: marginals of the batched multi-output posterior -------------------
+ * Replaces: reference src/bayesian_linear_regression.jl:33 (mean), :40-43 (var) and :47 (mean_and_var) under a map over fxs whose
+ * regressors come from matrix targets -- the S column posteriors blr_posterior_multi_batched_* returns per regressor share one
+ * factor, which blr_marginals_batched_* serves only by S calls (X read S times, the triangular work redone unless var is NULL on
+ * S - 1 of them) and blr_apply_weights_* only for one regressor, without the variance.
+ * Regressor b reads X + b*strideX, s + b*strides, M + b*strideM (D x S column-major, ldm >= D: exactly the mw_post block of
+ * blr_posterior_multi_batched_*, ldmp / stride_mwpost) and Lw + b*strideLw; a stride of 0 shares an input (strideX = 0 -- one
+ * candidate set -- and strideM = 0 included).
+ *   mean[b*stridemean + n + c*ldmean] = x_n' M_b[:, c]           (N x S column-major per regressor, ldmean >= N; :33 per column)
+ *   var[b*stridevar + n]              = |U_b^-T x_n|^2 + Sy_nn    (:40-43; one per input and regressor: it does not depend on the column)
+ * mean or var may be NULL; with var == NULL, s and Lw may be NULL.  S = 0 computes var only (M and mean are ignored).  No-ops
+ * returning 0: B = 0, N = 0, S = 0 with var == NULL.  Isotropic or diagonal noise (dense noise: argument error), all three prior
+ * kinds (a dense prior is factorised once per regressor, a diagonal one needs no factor), both layouts of X with any ldx, both
+ * memspaces.  info[B]: 0, or the LAPACK code of a dense prior that is not positive definite -- the outputs of that regressor are
+ * then left untouched and the call still returns 0.  Argument errors are the negative position of the offending argument and are
+ * checked before the handle (a NULL handle with valid arguments returns -1); output strides that overlap for B > 1 are argument
+ * errors: stridemean < ldmean*S, stridevar < N.  Limits: 1 <= D <= 8192, N <= 2^30, 0 <= S <= 2^20.
+ * D <= 128 (csrc/blr_marg_multi.hpp): the triangular inverse of every factor once per regressor (the image kernel of
+ * blr_marginals_batched_*), then ONE launch of marginals_cols_kernel per chunk of regressors (at most 65535, images within 256 MiB)
+ * over (column passes x groups of 64-input tiles, regressors); the launch count does not depend on S, and on B only through the
+ * chunks.  A pass takes 16 columns of M, held in registers as matrix-core operands; the tile of inputs sits in LDS as rows; X is
+ * streamed once per pass and var is produced by pass 0 only.  An async handle in device memspace only enqueues.
+ * D > 128: correct, not fast -- var through the route of blr_marginals_batched_* with mean = NULL for the batch, the means one
+ * regressor after the other through the product of blr_apply_weights_*; the call synchronises whatever the handle's async flag says.
+ * Numerics: mean and var hold the bounds of blr_marginals_batched_* against the fp64 reference (rtol = atol = 1e-10 in fp64, 2e-4 in
+ * fp32 on well-conditioned priors); the mean is a matrix-core product here, so no bit-equality with that entry point is promised.
+ * Promised: results are bit-reproducible from call to call; the bits of regressor b do not depend on B or on its position in the
+ * batch; the bits of column c do not depend on S, on c's position (pass included) or on the other columns' data; the bits of var do
+ * not depend on S or on whether mean is requested; host and device memspace give the same bits.
+ * _f32: X, s, M, Lw, mean, var are float. */
+int blr_marginals_multi_batched_f64(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t N, int64_t S,
+                                    const double* X, int64_t ldx, int64_t strideX,
+                                    int noise_kind, const double* s, int64_t strides,
+                                    int prior_kind, const double* M, int64_t ldm, int64_t strideM,
+                                    const double* Lw, int64_t ldl, int64_t strideLw,
+                                    double* mean, int64_t ldmean, int64_t stridemean,
+                                    double* var, int64_t stridevar,
+                                    int32_t* info);
+int blr_marginals_multi_batched_f32(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t N, int64_t S,
+                                    const float* X, int64_t ldx, int64_t strideX,
+                                    int noise_kind, const float* s, int64_t strides,
+                                    int prior_kind, const float* M, int64_t ldm, int64_t strideM,
+                                    const float* Lw, int64_t ldl, int64_t strideLw,
+                                    float* mean, int64_t ldmean, int64_t stridemean,
+                                    float* var, int64_t stridevar,
+                                    int32_t* info);
+
 /* ---- draws: replaces rand (:49-53) and the weight draws of sampling_functions.jl:29,35,44 ------
  * The host keeps drawing the normals so its RNG stream is the reference's:
  *   Z1 = randn(rng, D, S) FIRST, then Z2 = randn(rng, N, S).

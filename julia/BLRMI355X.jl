@@ -457,6 +457,57 @@ mean(fx::FiniteGP) = mean_and_var(fx; want_var=false)[1]
 var(fx::FiniteGP) = mean_and_var(fx; want_mean=false)[2]
 marginals(fx::FiniteGP) = ((m, v) = mean_and_var(fx); AbstractGPs.Normal.(m, sqrt.(v)))
 
+# blr_marginals_multi_batched_* (include/blr_mi355x.h): S mean columns (M: D x S per regressor, ldm -- the mw_post block of
+# blr_posterior_multi_batched_*) and ONE variance per input for B regressors.  The arrays are host Arrays (MEM_HOST) or raw device pointers.
+function marginals_multi_batched_call(h, ::Type{T}, memspace, layout, B, D, N, S, X, ldx, strideX, nk, s, strides, pk, M, ldm, strideM,
+                                      Lw, ldl, strideLw, m, ldmean, stridemean, v, stridevar, info) where {T<:Elt}
+    GC.@preserve X s M Lw m v info begin
+        if T === Float64
+            ccall((:blr_marginals_multi_batched_f64, LIB), Cint,
+                  (Ptr{Cvoid}, Cint, Cint, Int64, Int64, Int64, Int64, Ptr{T}, Int64, Int64, Cint, Ptr{T}, Int64, Cint, Ptr{T}, Int64, Int64,
+                   Ptr{T}, Int64, Int64, Ptr{T}, Int64, Int64, Ptr{T}, Int64, Ptr{Int32}),
+                  h, memspace, layout, B, D, N, S, X, ldx, strideX, nk, s, strides, pk, M, ldm, strideM,
+                  Lw, ldl, strideLw, m, ldmean, stridemean, v, stridevar, info)
+        else
+            ccall((:blr_marginals_multi_batched_f32, LIB), Cint,
+                  (Ptr{Cvoid}, Cint, Cint, Int64, Int64, Int64, Int64, Ptr{T}, Int64, Int64, Cint, Ptr{T}, Int64, Cint, Ptr{T}, Int64, Int64,
+                   Ptr{T}, Int64, Int64, Ptr{T}, Int64, Int64, Ptr{T}, Int64, Ptr{Int32}),
+                  h, memspace, layout, B, D, N, S, X, ldx, strideX, nk, s, strides, pk, M, ldm, strideM,
+                  Lw, ldl, strideLw, m, ldmean, stridemean, v, stridevar, info)
+        end
+    end
+end
+
+# mean_and_var over the S column posteriors of a matrix target (posterior per column: they share the precision) at the inputs and
+# noise of the FiniteGPs `fxs` (all S hold the same x and Σy): (mean N x S, var N) from one library call, :47 per column.
+function mean_and_var(fxs::AbstractVector{<:FiniteGP})
+    isempty(fxs) && throw(ArgumentError("at least one column posterior is needed"))
+    fbs = map(to_blr, fxs)
+    fb = fbs[1]
+    all(f -> f.f.Λw === fb.f.Λw, fbs) || throw(ArgumentError("the columns must share one precision object"))
+    xl, nz, pr = xlayout(fb.x), noise(fb.Σy), prior(fb.f.Λw)
+    (xl === nothing || nz === nothing || pr === nothing) &&
+        return (reduce(hcat, [mean_and_var(fx)[1] for fx in fxs]), mean_and_var(fxs[1])[2])
+    X, layout, ldx, D, N = xl
+    T = eltype(X)
+    S = length(fbs)
+    M = Matrix{T}(undef, D, S)
+    for (j, f) in enumerate(fbs)
+        M[:, j] .= f.f.mw
+    end
+    s, nk, _ = nz
+    nk == DENSEN && ((s, nk) = (collect(diag(s)), DIAGONALN))                              # var adds diag(Σy) only (:43)
+    Lw, pk, ldl = pr
+    m = Matrix{T}(undef, N, S)
+    v = Vector{T}(undef, N)
+    info = zeros(Int32, 1)
+    h = handle()
+    check(h, marginals_multi_batched_call(h, T, MEM_HOST, layout, 1, D, N, S, X, ldx, 0, nk, s, 0, pk, M, max(D, 1), 0, Lw, ldl, 0,
+                                          m, max(N, 1), 0, v, N, info))
+    check(h, info[1])
+    return m, v
+end
+
 # ---- full covariance: reference :35-38, :45 ----------------------------------------------------------------------
 function mean_and_cov(fx::FiniteGP; want_mean::Bool=true)
     fb = to_blr(fx)
@@ -923,6 +974,23 @@ function posterior_multi_batched!(mw_post::DeviceArray{T}, T_post::DeviceArray{T
     check(h, posterior_multi_batched_call(h, T, MEM_DEVICE, COLVECS, B, D, N, S, X.ptr, D, D * N, Y.ptr, max(N, 1), N * S,
                                           isotropic ? ISOTROPIC : DIAGONALN, s.ptr, isotropic ? 1 : N, P_DIAG, mw.ptr, D, Λdiag.ptr, 1, 0,
                                           mw_post.ptr, D, D * S, T_post.ptr, D, D * D, Ptr{T}(C_NULL), D, D * D, lp.ptr, S, info.ptr))
+    return nothing
+end
+
+"""
+    marginals_multi_batched!(mean, var, info, X, M, s, T_post; D, N, S, B, isotropic)
+
+Predictions from the state `posterior_multi_batched!` leaves, in ONE call, everything device resident: X is D×N×B (ColVecs), M the
+D×S×B posterior means (`mw_post`), T_post the D×D×B upper factors, s one variance per regressor (`isotropic`) or N×B; outputs mean
+N×S×B and var N×B (one variance per input: it does not depend on the column), info B (Int32).  Reference semantics per column:
+`:33`, `:40-43`, `:47` under a map over fxs whose regressors come from matrix targets.
+"""
+function marginals_multi_batched!(m::DeviceArray{T}, v::DeviceArray{T}, info::DeviceArray{Int32}, X::DeviceArray{T}, M::DeviceArray{T},
+                                  s::DeviceArray{T}, T_post::DeviceArray{T}; D::Int, N::Int, S::Int, B::Int, isotropic::Bool) where {T<:Elt}
+    h = handle()
+    check(h, marginals_multi_batched_call(h, T, MEM_DEVICE, COLVECS, B, D, N, S, X.ptr, D, D * N, isotropic ? ISOTROPIC : DIAGONALN,
+                                          s.ptr, isotropic ? 1 : N, P_UPPER, M.ptr, D, D * S, T_post.ptr, D, D * D, m.ptr, max(N, 1),
+                                          N * S, v.ptr, N, info.ptr))
     return nothing
 end
 
