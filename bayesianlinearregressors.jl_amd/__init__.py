@@ -20,6 +20,7 @@ from .regressor import (
     PDMat,
     RandomFourierFeatures,
     ResidentPosterior,
+    ResidentColumnsPosterior,
     RowVecs,
     Symmetric,
     cov,
@@ -58,7 +59,7 @@ from .regressor import (
 __all__ = [
     "logpdf", "rand", "mean", "std", "cov", "var", "BayesianLinearRegressor", "marginals", "posterior",
     "BasisFunctionRegressor", "ColVecs", "RowVecs", "Diagonal", "Symmetric", "PDMat", "Normal", "FiniteGP",
-    "BLRFunctionSample", "RandomFourierFeatures", "mean_and_var", "mean_and_cov", "rand_b", "rand_and_pullback", "evaluate", "logpdf_columns", "logpdf_and_gradient", "logpdf_map", "posterior_map", "rand_map", "BLRError", "PosDefException", "ResidentPosterior",
+    "BLRFunctionSample", "RandomFourierFeatures", "mean_and_var", "mean_and_cov", "rand_b", "rand_and_pullback", "evaluate", "logpdf_columns", "logpdf_and_gradient", "logpdf_map", "posterior_map", "rand_map", "BLRError", "PosDefException", "ResidentPosterior", "ResidentColumnsPosterior",
     "LOO", "loo", "loo_map",
     "EvidenceGrid", "logpdf_grid", "posterior_best", "logpdf_grid_map",
     "posterior_ragged", "logpdf_ragged",

@@ -21,6 +21,7 @@ PRIOR_DENSE, PRIOR_UPPER_FACTOR, PRIOR_DIAGONAL = 0, 1, 2
 MEM_HOST, MEM_DEVICE = 0, 1
 MULTI_COLS_PER_PASS = 64  # csrc/blr_multi.hpp kMultiColsPerPass: column slots of one pass of multi_cols_kernel (slot 0 = column 0)
 MARG_COLS_PER_PASS = 16  # csrc/blr_marg_multi.hpp kMargColsPerPass: mean columns of one pass of marginals_cols_kernel
+STATE_COLS_PER_PASS = 16  # csrc/blr_state_cols.hpp kStateColsPerPass: columns of one pass of state_cols_kernel (column 0 is not among them)
 
 _i64, _int, _vp = C.c_int64, C.c_int, C.c_void_p
 _H = C.c_void_p
@@ -87,6 +88,10 @@ for _suf in ("f64", "f32"):
     _SIGS[f"blr_update_factor_{_suf}"] = (
         [_H, _int, _int, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _int, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _vp], _int)
     _SIGS[f"blr_downdate_factor_{_suf}"] = _SIGS[f"blr_update_factor_{_suf}"]  # the same signature
+    _SIGS[f"blr_update_multi_factor_{_suf}"] = (
+        [_H, _int, _int, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _int, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _i64,
+         _vp, _i64, _vp], _int)
+    _SIGS[f"blr_downdate_multi_factor_{_suf}"] = _SIGS[f"blr_update_multi_factor_{_suf}"]  # the same signature
     _SIGS[f"blr_loo_batched_{_suf}"] = (
         [_H, _int, _int, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _int, _vp, _i64, _vp, _i64, _vp, _i64, _i64,
          _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp], _int)
@@ -339,6 +344,22 @@ class Handle:
         fn = getattr(self.lib, f"blr_downdate_factor_{suffix(dtype)}")
         return self.check(fn(self._h, memspace, layout, B, D, k, _ptr(X), ldx, strideX, _ptr(y), stridey, noise_kind, _ptr(s),
                              strides, _ptr(mw), stridemw, _ptr(T), ldt, strideT, _ptr(logpdf), _ptr(info)))
+
+    def update_multi_factor(self, dtype, memspace, layout, B, D, k, S, X, ldx, strideX, Y, ldY, strideY, noise_kind, s, strides, M, ldm,
+                            strideM, T, ldt, strideT, logpdf, stride_lp, info):
+        """In-place rank-k update of the resident multi-output state (M: D x S per regressor, one factor T); include/blr_mi355x.h
+        blr_update_multi_factor_*."""
+        fn = getattr(self.lib, f"blr_update_multi_factor_{suffix(dtype)}")
+        return self.check(fn(self._h, memspace, layout, B, D, k, S, _ptr(X), ldx, strideX, _ptr(Y), ldY, strideY, noise_kind, _ptr(s),
+                             strides, _ptr(M), ldm, strideM, _ptr(T), ldt, strideT, _ptr(logpdf), stride_lp, _ptr(info)))
+
+    def downdate_multi_factor(self, dtype, memspace, layout, B, D, k, S, X, ldx, strideX, Y, ldY, strideY, noise_kind, s, strides, M,
+                              ldm, strideM, T, ldt, strideT, logpdf, stride_lp, info):
+        """In-place rank-k downdate (forget observations) of the resident multi-output state (M, T); include/blr_mi355x.h
+        blr_downdate_multi_factor_*."""
+        fn = getattr(self.lib, f"blr_downdate_multi_factor_{suffix(dtype)}")
+        return self.check(fn(self._h, memspace, layout, B, D, k, S, _ptr(X), ldx, strideX, _ptr(Y), ldY, strideY, noise_kind, _ptr(s),
+                             strides, _ptr(M), ldm, strideM, _ptr(T), ldt, strideT, _ptr(logpdf), stride_lp, _ptr(info)))
 
     def loo(self, dtype, memspace, layout, B, D, N, X, ldx, strideX, y, stridey, noise_kind, s, strides, mw, stridemw, T, ldt,
             strideT, loo_mean, stride_lm, loo_var, stride_lv, loo_logpdf, stride_ll, loo_total, info):

@@ -34,6 +34,7 @@
 #include "blr_ragged.hpp"
 #include "blr_multi.hpp"
 #include "blr_marg_multi.hpp"
+#include "blr_state_cols.hpp"
 #include "blr_host.hpp"
 #include "blr_large_plan.hpp"
 
@@ -3494,6 +3495,137 @@ int marginals_multi_batched(blr_handle* h, int memspace, int layout, int64_t B, 
   return io.finish();
 }
 
+// ---- rank-k update / downdate of a resident MULTI-OUTPUT state: one factor, S mean columns (blr_update_multi_factor_*,
+// blr_downdate_multi_factor_*; blr_state_cols.hpp) ---------------------------------------------------------------------
+inline const void* state_cols_kernel_ptr(double, bool down, bool global) { return state_cols_kernel_ptr_f64(down, global); }
+inline const void* state_cols_kernel_ptr(float, bool down, bool global) { return state_cols_kernel_ptr_f32(down, global); }
+inline void state_cols_kernel_launch(bool down, bool global, dim3 grid, size_t lds, hipStream_t st, const StateColsArgs<double>& a) { state_cols_kernel_launch_f64(down, global, grid, lds, st, a); }
+inline void state_cols_kernel_launch(bool down, bool global, dim3 grid, size_t lds, hipStream_t st, const StateColsArgs<float>& a) { state_cols_kernel_launch_f32(down, global, grid, lds, st, a); }
+inline void state_diag_kernel_launch(hipStream_t st, const double* Tf, int64_t ldt, int64_t strideT, int D, int64_t B, double* d0) { state_diag_kernel_launch_f64(st, Tf, ldt, strideT, D, B, d0); }
+inline void state_diag_kernel_launch(hipStream_t st, const float* Tf, int64_t ldt, int64_t strideT, int D, int64_t B, float* d0) { state_diag_kernel_launch_f32(st, Tf, ldt, strideT, D, B, d0); }
+
+static_assert(kStateChunk == kSweepMaxK, "state_cols_kernel walks the observations in the sweep's chunks");
+
+template <typename T, bool DOWN>
+int state_multi_factor(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t k, int64_t S, const T* X, int64_t ldx,
+                       int64_t strideX, const T* Y, int64_t ldY, int64_t strideY, int noise_kind, const T* s, int64_t strides, T* M,
+                       int64_t ldm, int64_t strideM, T* Tf, int64_t ldt, int64_t strideT, double* logpdf, int64_t stride_lp, int32_t* info) {
+  // (the argument checks come before the handle's: they need no device)
+  if (h) h->err.clear();
+  if (memspace != BLR_MEM_HOST && memspace != BLR_MEM_DEVICE) return bad_arg(h, 2, "memspace");
+  if (layout != BLR_LAYOUT_COLVECS && layout != BLR_LAYOUT_ROWVECS) return bad_arg(h, 3, "unknown layout (reference :26-31)");
+  if (B < 0 || B > (1 << 30)) return bad_arg(h, 4, "B out of range (0..2^30)");
+  if (D < 1 || D > kMaxLargeD) return bad_arg(h, 5, "D out of range (1..8192)");
+  if (k < 0 || k > (1 << 30)) return bad_arg(h, 6, "k out of range (0..2^30)");
+  if (S < 0 || S > (1 << 20)) return bad_arg(h, 7, "S out of range (0..2^20)");
+  if (B == 0 || S == 0) return 0;
+  if (k > 0 && !X) return bad_arg(h, 8, "X is NULL");
+  if (layout == BLR_LAYOUT_COLVECS ? ldx < D : ldx < std::max<int64_t>(k, 1)) return bad_arg(h, 9, "ldx too small");
+  if (strideX < 0) return bad_arg(h, 10, "strideX < 0");
+  if (k > 0 && !Y) return bad_arg(h, 11, "Y is NULL (reference :74 length check)");
+  if (ldY < k) return bad_arg(h, 12, "ldY < k (reference :74 length check)");
+  if (strideY < 0) return bad_arg(h, 13, "strideY < 0");
+  if (noise_kind != BLR_NOISE_ISOTROPIC && noise_kind != BLR_NOISE_DIAGONAL)
+    return bad_arg(h, 14, "noise_kind (isotropic or diagonal; a resident state is not updated or downdated under dense noise)");
+  if (!s) return bad_arg(h, 15, "s is NULL");
+  if (strides < 0) return bad_arg(h, 16, "strides < 0");
+  if (!M) return bad_arg(h, 17, "M is NULL");
+  if (ldm < D) return bad_arg(h, 18, "ldm < D");
+  if (B > 1 && strideM < ldm * S) return bad_arg(h, 19, "strideM < ldm * S");
+  if (!Tf) return bad_arg(h, 20, "T is NULL");
+  if (ldt < D) return bad_arg(h, 21, "ldt < D");
+  if (B > 1 && strideT < (int64_t)mat_extent(D, D, ldt)) return bad_arg(h, 22, "strideT too small");
+  if (logpdf && B > 1 && stride_lp < S) return bad_arg(h, 24, "stride_lp < S");
+  if (!info) return bad_arg(h, 25, "info is NULL");
+  if (!h) return -1;
+  HIP_TRY(h, hipSetDevice(h->device));
+
+  if (k == 0) {  // nothing to condition on or to forget: the state keeps its bits, every evidence is 0
+    if (memspace == BLR_MEM_HOST) {
+      for (int64_t b = 0; b < B; ++b) {
+        info[b] = 0;
+        for (int64_t c = 0; logpdf && c < S; ++c) logpdf[b * stride_lp + c] = 0.0;
+      }
+      return 0;
+    }
+    HIP_TRY(h, hipMemsetAsync(info, 0, (size_t)B * sizeof(int32_t), h->stream));
+    if (logpdf) HIP_TRY(h, hipMemset2DAsync(logpdf, (size_t)std::max<int64_t>(stride_lp, S) * sizeof(double), 0, (size_t)S * sizeof(double), (size_t)B, h->stream));
+    if (!h->async) HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return 0;
+  }
+  auto single = [&](int ms, const T* X_, const T* y_, const T* s_, T* m_, T* T_, double* lp_, int32_t* info_) {
+    if (DOWN) return downdate_factor<T>(h, ms, layout, B, D, k, X_, ldx, strideX, y_, strideY, noise_kind, s_, strides, m_, strideM, T_, ldt, strideT, lp_, info_);
+    return update_factor<T>(h, ms, layout, B, D, k, X_, ldx, strideX, y_, strideY, noise_kind, s_, strides, m_, strideM, T_, ldt, strideT, lp_, info_);
+  };
+  // S = 1 with a dense evidence vector IS the single-column entry point
+  if (S == 1 && (!logpdf || B == 1 || stride_lp == 1)) return single(memspace, X, Y, s, M, Tf, logpdf, info);
+
+  StateColsArgs<T> a{};
+  a.ldx = ldx; a.strideX = strideX; a.layout = layout; a.ldY = ldY; a.strideY = strideY; a.strides = strides; a.noise_kind = noise_kind;
+  a.ldm = ldm; a.strideM = strideM; a.ldt = ldt; a.strideT = strideT; a.stride_lp = stride_lp;
+  a.D = (int)D; a.k = (int)k; a.S = (int)S;
+  CallIO io(h, memspace);
+  const size_t x_one = layout == BLR_LAYOUT_COLVECS ? mat_extent(D, k, ldx) : mat_extent(k, D, ldx);
+  const size_t s_one = noise_kind == BLR_NOISE_DIAGONAL ? (size_t)k : 1;
+  T* T_d = nullptr;
+  int32_t* info_d = nullptr;
+  int rc;
+  if ((rc = io.in(X, extent(B, strideX, x_one), &a.X))) return rc;
+  if ((rc = io.in(Y, extent(B, strideY, mat_extent(k, S, ldY)), &a.Y))) return rc;
+  if ((rc = io.in(s, extent(B, strides, s_one), &a.s))) return rc;
+  if ((rc = io.out(M, extent(B, strideM, mat_extent(D, S, ldm)), &a.M))) return rc;
+  if ((rc = io.out(Tf, extent(B, strideT, mat_extent(D, D, ldt)), &T_d))) return rc;
+  if ((rc = io.out(logpdf, extent(B, stride_lp, (size_t)S), &a.logpdf))) return rc;
+  if ((rc = io.out(info, (size_t)B, &info_d))) return rc;
+  a.Tf = T_d; a.info = info_d;
+
+  // Pre-pass: the old diagonal of T (the log-determinant term of the further columns' evidence) into the handle's workspace, next to
+  // column 0's evidence (the caller's logpdf has a stride of its own)
+  const size_t lp0_bytes = ((size_t)B * sizeof(double) + 255) & ~(size_t)255;
+  const bool global = D > kMaxSmallD;
+  // (fp32, D <= 128: the whole factor too -- state_cols_kernel<float> forms A m_c of the state before the call from it)
+  const bool save_T = sizeof(T) == 4 && !global && S > 1;
+  const size_t diag_bytes = ((size_t)B * D * sizeof(T) + 255) & ~(size_t)255;
+  if ((rc = h->multi_ws.reserve(h, lp0_bytes + diag_bytes + (save_T ? (size_t)B * D * D * sizeof(T) : 0)))) return rc;
+  double* const lp0 = reinterpret_cast<double*>(h->multi_ws.p);
+  T* const diag0 = reinterpret_cast<T*>(h->multi_ws.p + lp0_bytes);
+  a.lp0 = lp0; a.diag0 = diag0;
+  a.T0 = reinterpret_cast<T*>(h->multi_ws.p + lp0_bytes + diag_bytes);
+  state_diag_kernel_launch(h->stream, T_d, ldt, strideT, (int)D, B, diag0);
+  if constexpr (sizeof(T) == 4) {
+    if (save_T) state_save_kernel_launch_f32(h->stream, T_d, ldt, strideT, (int)D, B, const_cast<T*>(a.T0));
+  }
+  HIP_TRY(h, hipGetLastError());
+  {
+    // Step 1: column 0 and the factor through the single-column entry point, unchanged (device operands; at D <= 128 it only enqueues,
+    // at larger D it may synchronise)
+    const AsyncScope nested(h, global ? h->async : true);
+    if ((rc = single(BLR_MEM_DEVICE, a.X, a.Y, a.s, a.M, T_d, lp0, info_d))) return rc;  // (checked operands: a HIP failure)
+  }
+  // Step 2: the columns 1 .. S-1 of every regressor (and the copy of column 0's evidence to its place)
+  const void* const kern = state_cols_kernel_ptr(T(0), DOWN, global);
+  if (!global) {
+    const int64_t passes = std::max<int64_t>(1, (S - 1 + kStateColsPerPass - 1) / kStateColsPerPass);
+    const size_t lds = state_cols_lds_bytes(sizeof(T), (int)D);
+    if ((rc = set_lds_once(h, kern, lds))) return rc;
+    state_cols_kernel_launch(DOWN, false, dim3((unsigned)B, (unsigned)passes), lds, h->stream, a);
+  } else {
+    // correct, not fast: one workgroup per (column, regressor) reading T' from global memory; column 0's evidence is copied by the host
+    const size_t lds = state_cols_global_lds_bytes((int)D);
+    if ((rc = set_lds_once(h, kern, lds))) return rc;
+    if (a.logpdf) HIP_TRY(h, hipMemcpy2DAsync(a.logpdf, (size_t)stride_lp * sizeof(double), lp0, sizeof(double), sizeof(double), (size_t)B, hipMemcpyDeviceToDevice, h->stream));
+    for (int64_t b0 = 0; S > 1 && b0 < B; b0 += 32768) {
+      StateColsArgs<T> g = a;
+      g.X += b0 * strideX; g.Y += b0 * strideY; g.s += b0 * strides; g.M += b0 * strideM; g.Tf += b0 * strideT;
+      g.diag0 += b0 * D; g.info += b0;
+      if (g.logpdf) g.logpdf += b0 * stride_lp;
+      state_cols_kernel_launch(DOWN, true, dim3((unsigned)(S - 1), (unsigned)std::min<int64_t>(32768, B - b0)), lds, h->stream, g);
+    }
+  }
+  HIP_TRY(h, hipGetLastError());
+  return io.finish();
+}
+
 }  // namespace
 
 // =======================================================================================================
@@ -3798,6 +3930,24 @@ int blr_timer_stop(blr_handle* h, float* elapsed_ms) {
     return marginals_multi_batched<T>(h, memspace, layout, B, D, N, S, X, ldx, strideX, noise_kind, s, strides,     \
                                       prior_kind, M, ldm, strideM, Lw, ldl, strideLw, mean, ldmean, stridemean,     \
                                       var, stridevar, info);                                                        \
+  }                                                                                                                 \
+  int blr_update_multi_factor_##SUF(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t k,       \
+                                    int64_t S, const T* X, int64_t ldx, int64_t strideX, const T* Y, int64_t ldY,   \
+                                    int64_t strideY, int noise_kind, const T* s, int64_t strides, T* M,             \
+                                    int64_t ldm, int64_t strideM, T* Tf, int64_t ldt, int64_t strideT,              \
+                                    double* logpdf, int64_t stride_lp, int32_t* info) {                             \
+    return state_multi_factor<T, false>(h, memspace, layout, B, D, k, S, X, ldx, strideX, Y, ldY, strideY,          \
+                                        noise_kind, s, strides, M, ldm, strideM, Tf, ldt, strideT, logpdf,          \
+                                        stride_lp, info);                                                           \
+  }                                                                                                                 \
+  int blr_downdate_multi_factor_##SUF(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t k,     \
+                                      int64_t S, const T* X, int64_t ldx, int64_t strideX, const T* Y, int64_t ldY, \
+                                      int64_t strideY, int noise_kind, const T* s, int64_t strides, T* M,           \
+                                      int64_t ldm, int64_t strideM, T* Tf, int64_t ldt, int64_t strideT,            \
+                                      double* logpdf, int64_t stride_lp, int32_t* info) {                           \
+    return state_multi_factor<T, true>(h, memspace, layout, B, D, k, S, X, ldx, strideX, Y, ldY, strideY,           \
+                                       noise_kind, s, strides, M, ldm, strideM, Tf, ldt, strideT, logpdf,           \
+                                       stride_lp, info);                                                            \
   }                                                                                                                 \
   int blr_posterior_##SUF(blr_handle* h, int layout, int64_t D, int64_t N, const T* X, int64_t ldx, const T* y,     \
                           int noise_kind, const T* s, int prior_kind, const T* mw, const T* Lw, int64_t ldl,        \

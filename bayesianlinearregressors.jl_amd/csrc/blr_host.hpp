@@ -179,7 +179,8 @@ struct blr_handle {
                   // logpdf_multi carves ITS temporaries from `aux` around a nested update that may take that route
   DevBuf loo_ws;  // chunk of mean / latent variance / logpdf of blr_loo_batched_* (the marginal routes it calls use ws and aux themselves)
   DevBuf ragged_meta;  // offsets[B + 1] and the longest-first order[B] of blr_posterior_ragged_* (a buffer of its own: the D > 128 route runs the batched pipeline, which uses ws)
-  DevBuf multi_ws;  // blr_posterior_multi_batched_*: evidence of column 0 per regressor, and the factors when the caller passed T_post = NULL
+  DevBuf multi_ws;  // blr_posterior_multi_batched_*: evidence of column 0 per regressor, and the factors when the caller passed T_post = NULL;
+                    // blr_update_multi_factor_* / blr_downdate_multi_factor_*: that evidence and the diagonal of the factor before the call
   std::vector<int64_t> ragged_host;  // host image of that buffer (kept: no allocation per call in the steady state)
   // wavefront back substitution (D > 128): tagged exchange buffer (unsigned long long granules; never smaller than kXchgFloor),
   // start-order ticket counter, launch epoch

@@ -1404,6 +1404,149 @@ class ResidentPosterior:
         return BasisFunctionRegressor(post, self.phi) if self.phi is not None else post
 
 
+class ResidentColumnsPosterior:
+    """The S column posteriors of a matrix target kept ON THE DEVICE as one state (M, T): M the D x S block of means, T the ONE upper
+    factor of the precision they share -- what `posterior_columns` returns -- conditioned IN PLACE on further observations with S
+    targets each (blr_update_multi_factor_*), and `forget` as its inverse (blr_downdate_multi_factor_*).  One library call per
+    step does the factor work once and costs two triangular solves per further column; fit -> stream -> predict never copies T
+    to the host:
+
+        st = ResidentColumnsPosterior(posterior_columns(f(X1, S1), Y1))   # or a prior: ResidentColumnsPosterior(f, S=3)
+        lp = st.condition(X2, S2, Y2)                                      # (S,) log p(Y2[:, c] | Y1[:, c])
+        lp_old = st.forget(X1[:, :1], S1, Y1[:1])                          # (S,) log density of the removed row given the rest
+        m, v = st.mean_and_var(Xt, 0.1)                                    # (N x S, N) from the resident state
+
+    The S regressors must share one precision object (as those of `posterior_columns` do); a BasisFunctionRegressor keeps its
+    basis, exactly as in ResidentPosterior."""
+
+    def __init__(self, fs, S=None):
+        if isinstance(fs, (BayesianLinearRegressor, BasisFunctionRegressor)):
+            if S is None or int(S) < 1:
+                raise ValueError("a single prior regressor needs the number of columns S >= 1")
+            fs = [fs] * int(S)
+        else:
+            fs = list(fs)
+            if S is not None and int(S) != len(fs):
+                raise ValueError("S != number of column regressors")
+        if not fs:
+            raise ValueError("at least one column regressor is needed")
+        blrs = [f.blr if isinstance(f, BasisFunctionRegressor) else f for f in fs]
+        if any(not isinstance(b, BayesianLinearRegressor) for b in blrs):
+            raise TypeError("expected BayesianLinearRegressor or BasisFunctionRegressor columns")
+        if any(b.Lw is not blrs[0].Lw for b in blrs):
+            raise ValueError("the columns must share one precision object")
+        self._col0 = ResidentPosterior(fs[0])  # the factor (a Diagonal / dense prior precision is factorised by the library), phi, the handle
+        self.phi, self.dtype, self.D, self._h = self._col0.phi, self._col0.dtype, self._col0.D, self._col0._h
+        self.S = len(fs)
+        self._T = self._col0._T
+        M = np.asfortranarray(np.stack([_mean_vector(b.mw, self.D, self.dtype) for b in blrs], axis=1))  # D x S
+        self._M = _DeviceBuffer.of(self._h, M)
+
+    def _step(self, call, what, x, Sy, Y):
+        dtype, h, D, S = self.dtype, self._h, self.D, self.S
+        temps = []
+
+        def dev(a):
+            temps.append(_DeviceBuffer.of(h, a))
+            return temps[-1].ptr
+
+        try:
+            dX, layout, ldx, k = self._col0._inputs(x, dev, temps)
+            Y = np.asfortranarray(Y, dtype=dtype)
+            if Y.shape != (k, S):
+                raise ValueError("Y must be (number of inputs) x S")  # reference :74 per column
+            s, noise_kind = _noise(Sy, k, dtype)
+            if noise_kind == _abi.NOISE_DENSE:
+                raise NotImplementedError(f"ResidentColumnsPosterior.{what} takes scalar or diagonal noise (whiten a dense block first)")
+            lp = np.zeros(S, dtype=np.float64)
+            info = np.zeros(1, dtype=np.int32)
+            d_lp, d_info = dev(lp), dev(info)
+            call(dtype, _abi.MEM_DEVICE, layout, 1, D, k, S, dX, ldx, 0, dev(Y) if k else None, max(k, 1), 0, noise_kind, dev(s), 0,
+                 self._M.ptr, max(D, 1), 0, self._T.ptr, max(D, 1), 0, d_lp, S, d_info)
+            h.memcpy_d2h(lp, d_lp)
+            h.memcpy_d2h(info, d_info)
+        finally:
+            for b in temps:
+                b.free()
+        if info[0] != 0:
+            raise _abi.PosDefException(int(info[0]))
+        return lp
+
+    def condition(self, x, Sy, Y):
+        """In-place update with the observations (x, Sy, Y), Y one row of S targets per input; returns the (S,) array of
+        log p(Y[:, c] | everything column c was conditioned on so far).  PosDefException(info) leaves the state as it was."""
+        return self._step(self._h.update_multi_factor, "condition", x, Sy, Y)
+
+    def forget(self, x, Sy, Y):
+        """In-place DOWNDATE: removes the observations (x, Sy, Y), which the state must contain; returns the (S,) array of
+        log p(Y[:, c] | the data that remains).  A removal that would leave a precision that is not positive definite raises
+        PosDefException(info) and leaves the state as it was."""
+        return self._step(self._h.downdate_multi_factor, "forget", x, Sy, Y)
+
+    def _marginals(self, x, Sy, want_var):
+        dtype, h, D, S = self.dtype, self._h, self.D, self.S
+        temps = []
+
+        def dev(a):
+            temps.append(_DeviceBuffer.of(h, a))
+            return temps[-1].ptr
+
+        try:
+            dX, layout, ldx, N = self._col0._inputs(x, dev, temps)
+            s, noise_kind = _noise(Sy, N, dtype)
+            if noise_kind == _abi.NOISE_DENSE:  # var adds diag(Sigma_y) (:43)
+                s, noise_kind = np.ascontiguousarray(np.diag(s)), _abi.NOISE_DIAGONAL
+            m = np.empty((N, S), dtype=dtype, order="F")
+            v = np.empty(N, dtype=dtype) if want_var else None
+            if N == 0:
+                return m, v
+            temps.append(_DeviceBuffer(h, m.nbytes))
+            d_m = temps[-1].ptr
+            d_v = None
+            if want_var:
+                temps.append(_DeviceBuffer(h, v.nbytes))
+                d_v = temps[-1].ptr
+            info = np.zeros(1, dtype=np.int32)
+            d_info = dev(info)
+            h.marginals_multi_batched(dtype, _abi.MEM_DEVICE, layout, 1, D, N, S, dX, ldx, 0, noise_kind, dev(s) if want_var else None, 0,
+                                      _abi.PRIOR_UPPER_FACTOR, self._M.ptr, max(D, 1), 0, self._T.ptr if want_var else None, max(D, 1), 0,
+                                      d_m, max(N, 1), 0, d_v, N, d_info)
+            h.memcpy_d2h(info, d_info)
+            if info[0] > 0:
+                raise _abi.PosDefException(int(info[0]))
+            h.memcpy_d2h(m, d_m)
+            if want_var:
+                h.memcpy_d2h(v, d_v)
+            return m, v
+        finally:
+            for b in temps:
+                b.free()
+
+    def mean_and_var(self, x, Sy=1e-18):
+        """mean_and_var(f_c(x, Sy)) (reference :47) of the S resident columns: (mean N x S, var N), blr_marginals_multi_batched_* on
+        device pointers to the resident state."""
+        return self._marginals(x, Sy, True)
+
+    def mean(self, x):
+        """mean(f_c(x)) (reference :33) of the S resident columns: N x S."""
+        return self._marginals(x, 1e-18, False)[0]
+
+    def state(self):
+        """host copies (M, T) of the resident state: M D x S, T column-major upper"""
+        M = np.empty((self.D, self.S), dtype=self.dtype, order="F")
+        T = np.empty((self.D, self.D), dtype=self.dtype, order="F")
+        self._h.memcpy_d2h(M, self._M.ptr)
+        self._h.memcpy_d2h(T, self._T.ptr)
+        return M, np.triu(T)
+
+    def regressors(self):
+        """The current state as S regressors of the type it was built from, sharing ONE PDMat (reference :93 per column)."""
+        M, T = self.state()
+        Lw = PDMat(T)
+        posts = [BayesianLinearRegressor(M[:, c].copy(), Lw) for c in range(self.S)]
+        return [BasisFunctionRegressor(p, self.phi) for p in posts] if self.phi is not None else posts
+
+
 def _marginals(fx, want_mean, want_var):
     fx = _to_finite_blr(fx)
     blr = fx.f

@@ -610,6 +610,59 @@ int blr_downdate_factor_f32(blr_handle* h, int memspace, int layout, int64_t B, 
                             int64_t strides, float* mw, int64_t stridemw, float* T, int64_t ldt, int64_t strideT,
                             double* logpdf, int32_t* info);
 
+/* ---- rank-k update / DOWNDATE of a resident MULTI-OUTPUT state: one factor, S mean columns ------------------------------
+ * blr_update_multi_factor_* replaces: reference test/bayesian_linear_regression.jl:49-70 ("repeated conditioning") and
+ * src/bayesian_linear_regression.jl:93 under MATRIX targets -- S calls of blr_update_factor_* on S private copies of the factor, or a
+ * refit with blr_posterior_multi_batched_*.  blr_downdate_multi_factor_* is its inverse and reports :55-58 (logpdf) for the REMOVED
+ * data given the data that remains, per column -- S calls of blr_downdate_factor_*.
+ * State, updated IN PLACE: M (D x S column-major per regressor, ldm >= D, strideM) -- exactly the mw_post block of
+ * blr_posterior_multi_batched_* and the M of blr_marginals_multi_batched_* -- and the ONE upper factor T[B] (D x D, ldt, T'T =
+ * precision; only the upper triangle is read or written, as for blr_update_factor_*).
+ * k observations per regressor: X (D x k ColVecs / k x D RowVecs, ldx), Y (k x S column-major, ldY >= k), isotropic or diagonal
+ * noise s.  A stride of 0 shares an input (strideX, strideY, strides).
+ * With W = X S^-1/2 the new precision T''T' = T'T +- W W' does not involve Y.  Column 0 and the factor are the single-column entry
+ * point's; every further column c costs, with E_c = S^-1/2 (Y_c - X'm_c) against its mean before the call (upper sign: update),
+ *   u_c = T'^-T (W E_c)    m_c' = m_c +- T'^-1 u_c    logpdf_c = -1/2 [k log 2pi + sum log s_i +- 2 sum_j log(T'_jj / T_jj) + |E_c|^2 -+ |u_c|^2].
+ * logpdf[b * stride_lp + c] (double; may be NULL): update: log p(Y_c | state before the call); downdate: log p(Y_c | state after the
+ * call) -- the contract of blr_update_factor_* / blr_downdate_factor_* per column.
+ * info[B]: one status per regressor, the codes of the single-column entry point of the same direction, in its order.  When
+ * info[b] != 0 all S means and the factor of regressor b are bit-for-bit untouched and its S evidences are NaN; the call returns 0.
+ * S = 1 promise: column 0, T and info are bit for bit what blr_update_factor_* / blr_downdate_factor_* write on the same handle for
+ * (X, Y[:, 0]), whatever S is (handle options SWEEP and NO_DOWNDATE_LDS included); with S = 1 the call IS that entry point.
+ * Bit promises: the bits of a regressor do not depend on B or on its position in the batch; for c >= 1 the bits of a column do not
+ * depend on S, on the column's position (pass included) or on the other columns' data; host and device memspace give the same bits;
+ * repeated calls on restored state give the same bits.
+ * Argument errors (negative position; checked before the handle, so a NULL handle with valid arguments returns -1): memspace,
+ * layout, B, D, k, S out of range, dense noise (14), ldY < k (12), ldm < D (18), and for B > 1 strideM < ldm * S (19),
+ * stride_lp < S (24) and the T rules of blr_update_factor_* (21, 22).  B = 0, S = 0 or k = 0 is a no-op returning 0; with k = 0 and
+ * a non-NULL logpdf every evidence is 0 (info 0) and the state keeps its bits.
+ * Limits: 1 <= D <= 8192, 0 <= S <= 2^20, 0 <= k <= 2^30, host or device memspace; an async handle in device memspace only
+ * enqueues at D <= 128.
+ * Kernels (csrc/blr_state_cols.hpp).  D <= 128: three launches (fp32: four) whatever B and S are -- the old diagonal
+ * of T into the handle's workspace (state_diag_kernel; the log-determinant term; fp32 also the whole old factor, state_save_kernel,
+ * B D^2 elements of workspace), the single-column call, then state_cols_kernel over (regressors, passes of 16 columns) with the
+ * finished factor in LDS.  fp32: a column's mean is m_c +- T'^-1 u_c or the solution of A'm_c' = A m_c +- X S^-1 y_c (right-hand
+ * side in double from the old factor), whichever solved vector is smaller: the error of the fp32 factor then enters times
+ * min(|m_c' - m_c|, |m_c'|).  D > 128 is correct, not fast: column 0 through the large-D
+ * update / downdate route (which may synchronise), the other columns one workgroup per (column, regressor) with T' read from global
+ * memory. */
+int blr_update_multi_factor_f64(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t k, int64_t S,
+                                const double* X, int64_t ldx, int64_t strideX, const double* Y, int64_t ldY, int64_t strideY,
+                                int noise_kind, const double* s, int64_t strides, double* M, int64_t ldm, int64_t strideM,
+                                double* T, int64_t ldt, int64_t strideT, double* logpdf, int64_t stride_lp, int32_t* info);
+int blr_update_multi_factor_f32(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t k, int64_t S,
+                                const float* X, int64_t ldx, int64_t strideX, const float* Y, int64_t ldY, int64_t strideY,
+                                int noise_kind, const float* s, int64_t strides, float* M, int64_t ldm, int64_t strideM,
+                                float* T, int64_t ldt, int64_t strideT, double* logpdf, int64_t stride_lp, int32_t* info);
+int blr_downdate_multi_factor_f64(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t k, int64_t S,
+                                  const double* X, int64_t ldx, int64_t strideX, const double* Y, int64_t ldY, int64_t strideY,
+                                  int noise_kind, const double* s, int64_t strides, double* M, int64_t ldm, int64_t strideM,
+                                  double* T, int64_t ldt, int64_t strideT, double* logpdf, int64_t stride_lp, int32_t* info);
+int blr_downdate_multi_factor_f32(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t k, int64_t S,
+                                  const float* X, int64_t ldx, int64_t strideX, const float* Y, int64_t ldY, int64_t strideY,
+                                  int noise_kind, const float* s, int64_t strides, float* M, int64_t ldm, int64_t strideM,
+                                  float* T, int64_t ldt, int64_t strideT, double* logpdf, int64_t stride_lp, int32_t* info);
+
 /* ---- exact LEAVE-ONE-OUT predictives of the observations a posterior state contains -----------------------------------
  * Replaces: a loop of blr_downdate_factor_* at k = 1 (then blr_update_factor_* to put the observation back) per observation,
  * and reference src/bayesian_linear_regression.jl:55-58 (logpdf) applied to each held-out point given the rest.

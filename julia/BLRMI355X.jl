@@ -1083,6 +1083,65 @@ function downdate_factor!(mw::DeviceArray{T}, Tf::DeviceArray{T}, lp::DeviceArra
 end
 
 """
+    update_multi_factor!(M, T, logpdf, info, X, Y, s; D, k, S, B, isotropic)
+
+Condition B device-resident MULTI-OUTPUT states IN PLACE on k further observations with S targets each: M is D×S×B (the means
+`posterior_multi_batched!` wrote), T D×D×B (ONE upper factor per regressor), X D×k×B, Y k×S×B, s one variance (`isotropic`) or
+k×B.  The factor work is done once per regressor (column 1 is `update_factor!`, bit for bit); `logpdf[c, b]` (S×B) =
+log p(Y[:, c, b] | state before the call).  A regressor with `info[b] != 0` keeps its state and gets NaN evidences.
+"""
+function update_multi_factor!(M::DeviceArray{T}, Tf::DeviceArray{T}, lp::DeviceArray{Float64}, info::DeviceArray{Int32},
+                              X::DeviceArray{T}, Y::DeviceArray{T}, s::DeviceArray{T}; D::Int, k::Int, S::Int, B::Int,
+                              isotropic::Bool) where {T<:Elt}
+    h = handle()
+    nk = isotropic ? ISOTROPIC : DIAGONALN
+    rc = if T === Float64
+        ccall((:blr_update_multi_factor_f64, LIB), Cint,
+              (Ptr{Cvoid}, Cint, Cint, Int64, Int64, Int64, Int64, Ptr{T}, Int64, Int64, Ptr{T}, Int64, Int64, Cint, Ptr{T}, Int64,
+               Ptr{T}, Int64, Int64, Ptr{T}, Int64, Int64, Ptr{Cdouble}, Int64, Ptr{Int32}),
+              h, MEM_DEVICE, COLVECS, B, D, k, S, X.ptr, D, D * k, Y.ptr, max(k, 1), k * S, nk, s.ptr, isotropic ? 0 : k, M.ptr, D, D * S,
+              Tf.ptr, D, D * D, lp.ptr, S, info.ptr)
+    else
+        ccall((:blr_update_multi_factor_f32, LIB), Cint,
+              (Ptr{Cvoid}, Cint, Cint, Int64, Int64, Int64, Int64, Ptr{T}, Int64, Int64, Ptr{T}, Int64, Int64, Cint, Ptr{T}, Int64,
+               Ptr{T}, Int64, Int64, Ptr{T}, Int64, Int64, Ptr{Cdouble}, Int64, Ptr{Int32}),
+              h, MEM_DEVICE, COLVECS, B, D, k, S, X.ptr, D, D * k, Y.ptr, max(k, 1), k * S, nk, s.ptr, isotropic ? 0 : k, M.ptr, D, D * S,
+              Tf.ptr, D, D * D, lp.ptr, S, info.ptr)
+    end
+    check(h, rc)
+    return nothing
+end
+
+"""
+    downdate_multi_factor!(M, T, logpdf, info, X, Y, s; D, k, S, B, isotropic)
+
+The inverse of `update_multi_factor!`: remove k observations with S targets each from B device-resident multi-output states IN
+PLACE.  Operands exactly as for `update_multi_factor!`; `logpdf[c, b]` = log p(Y[:, c, b] | state after the call), the contract of
+`downdate_factor!` per column, and its status codes.
+"""
+function downdate_multi_factor!(M::DeviceArray{T}, Tf::DeviceArray{T}, lp::DeviceArray{Float64}, info::DeviceArray{Int32},
+                              X::DeviceArray{T}, Y::DeviceArray{T}, s::DeviceArray{T}; D::Int, k::Int, S::Int, B::Int,
+                              isotropic::Bool) where {T<:Elt}
+    h = handle()
+    nk = isotropic ? ISOTROPIC : DIAGONALN
+    rc = if T === Float64
+        ccall((:blr_downdate_multi_factor_f64, LIB), Cint,
+              (Ptr{Cvoid}, Cint, Cint, Int64, Int64, Int64, Int64, Ptr{T}, Int64, Int64, Ptr{T}, Int64, Int64, Cint, Ptr{T}, Int64,
+               Ptr{T}, Int64, Int64, Ptr{T}, Int64, Int64, Ptr{Cdouble}, Int64, Ptr{Int32}),
+              h, MEM_DEVICE, COLVECS, B, D, k, S, X.ptr, D, D * k, Y.ptr, max(k, 1), k * S, nk, s.ptr, isotropic ? 0 : k, M.ptr, D, D * S,
+              Tf.ptr, D, D * D, lp.ptr, S, info.ptr)
+    else
+        ccall((:blr_downdate_multi_factor_f32, LIB), Cint,
+              (Ptr{Cvoid}, Cint, Cint, Int64, Int64, Int64, Int64, Ptr{T}, Int64, Int64, Ptr{T}, Int64, Int64, Cint, Ptr{T}, Int64,
+               Ptr{T}, Int64, Int64, Ptr{T}, Int64, Int64, Ptr{Cdouble}, Int64, Ptr{Int32}),
+              h, MEM_DEVICE, COLVECS, B, D, k, S, X.ptr, D, D * k, Y.ptr, max(k, 1), k * S, nk, s.ptr, isotropic ? 0 : k, M.ptr, D, D * S,
+              Tf.ptr, D, D * D, lp.ptr, S, info.ptr)
+    end
+    check(h, rc)
+    return nothing
+end
+
+"""
     loo!(lmean, lvar, llogpdf, total, info, X, y, s, mw, T; D, N, B, isotropic)
 
 Exact leave-one-out predictives of the N observations each of B device-resident states contains (`blr_loo_batched_*`): for
