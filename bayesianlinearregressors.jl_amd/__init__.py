@@ -34,6 +34,8 @@ from .regressor import (
     logpdf_map,
     logpdf_ragged,
     loo,
+    loo_columns,
+    loo_columns_map,
     loo_map,
     marginals,
     mean,
@@ -60,7 +62,7 @@ __all__ = [
     "logpdf", "rand", "mean", "std", "cov", "var", "BayesianLinearRegressor", "marginals", "posterior",
     "BasisFunctionRegressor", "ColVecs", "RowVecs", "Diagonal", "Symmetric", "PDMat", "Normal", "FiniteGP",
     "BLRFunctionSample", "RandomFourierFeatures", "mean_and_var", "mean_and_cov", "rand_b", "rand_and_pullback", "evaluate", "logpdf_columns", "logpdf_and_gradient", "logpdf_map", "posterior_map", "rand_map", "BLRError", "PosDefException", "ResidentPosterior", "ResidentColumnsPosterior",
-    "LOO", "loo", "loo_map",
+    "LOO", "loo", "loo_map", "loo_columns", "loo_columns_map",
     "EvidenceGrid", "logpdf_grid", "posterior_best", "logpdf_grid_map",
     "posterior_ragged", "logpdf_ragged",
     "posterior_columns", "logpdf_columns_map", "posterior_columns_map",

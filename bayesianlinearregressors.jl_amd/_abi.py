@@ -21,6 +21,7 @@ PRIOR_DENSE, PRIOR_UPPER_FACTOR, PRIOR_DIAGONAL = 0, 1, 2
 MEM_HOST, MEM_DEVICE = 0, 1
 MULTI_COLS_PER_PASS = 64  # csrc/blr_multi.hpp kMultiColsPerPass: column slots of one pass of multi_cols_kernel (slot 0 = column 0)
 MARG_COLS_PER_PASS = 16  # csrc/blr_marg_multi.hpp kMargColsPerPass: mean columns of one pass of marginals_cols_kernel
+LOO_COLS_PER_PASS = 16  # csrc/blr_loo_multi.hpp kLooColsPerPass (= kMargColsPerPass): columns of one pass of loo_cols_kernel
 STATE_COLS_PER_PASS = 16  # csrc/blr_state_cols.hpp kStateColsPerPass: columns of one pass of state_cols_kernel (column 0 is not among them)
 
 _i64, _int, _vp = C.c_int64, C.c_int, C.c_void_p
@@ -95,6 +96,9 @@ for _suf in ("f64", "f32"):
     _SIGS[f"blr_loo_batched_{_suf}"] = (
         [_H, _int, _int, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _int, _vp, _i64, _vp, _i64, _vp, _i64, _i64,
          _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp], _int)
+    _SIGS[f"blr_loo_multi_batched_{_suf}"] = (
+        [_H, _int, _int, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _int, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _i64,
+         _vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _vp], _int)
     _SIGS[f"blr_logpdf_grid_{_suf}"] = (
         [_H, _int, _int, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _int, _vp, _i64, _int, _vp, _i64, _vp, _i64, _i64,
          _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _i64], _int)
@@ -369,6 +373,16 @@ class Handle:
         return self.check(fn(self._h, memspace, layout, B, D, N, _ptr(X), ldx, strideX, _ptr(y), stridey, noise_kind, _ptr(s),
                              strides, _ptr(mw), stridemw, _ptr(T), ldt, strideT, _ptr(loo_mean), stride_lm, _ptr(loo_var),
                              stride_lv, _ptr(loo_logpdf), stride_ll, _ptr(loo_total), _ptr(info)))
+
+    def loo_multi_batched(self, dtype, memspace, layout, B, D, N, S, X, ldx, strideX, Y, ldY, strideY, noise_kind, s, strides, M, ldm,
+                          strideM, T, ldt, strideT, loo_mean, ld_lm, stride_lm, loo_var, stride_lv, loo_logpdf, ld_ll, stride_ll,
+                          loo_total, stride_lt, info):
+        """Exact leave-one-out predictives of the observations the multi-output states (M: D x S, T) contain: S means and log
+        densities and ONE variance per input, S totals per regressor; include/blr_mi355x.h blr_loo_multi_batched_*."""
+        fn = getattr(self.lib, f"blr_loo_multi_batched_{suffix(dtype)}")
+        return self.check(fn(self._h, memspace, layout, B, D, N, S, _ptr(X), ldx, strideX, _ptr(Y), ldY, strideY, noise_kind, _ptr(s),
+                             strides, _ptr(M), ldm, strideM, _ptr(T), ldt, strideT, _ptr(loo_mean), ld_lm, stride_lm, _ptr(loo_var),
+                             stride_lv, _ptr(loo_logpdf), ld_ll, stride_ll, _ptr(loo_total), stride_lt, _ptr(info)))
 
     def logpdf_grid(self, dtype, memspace, layout, B, D, N, X, ldx, strideX, y, stridey, noise_kind, s, strides, prior_kind, mw,
                     stridemw, Lw, ldl, strideLw, G, alpha, stride_alpha, tau, stride_tau, logpdf, stride_lp, best, mw_best,

@@ -34,6 +34,7 @@
 #include "blr_ragged.hpp"
 #include "blr_multi.hpp"
 #include "blr_marg_multi.hpp"
+#include "blr_loo_multi.hpp"
 #include "blr_state_cols.hpp"
 #include "blr_host.hpp"
 #include "blr_large_plan.hpp"
@@ -3495,6 +3496,163 @@ int marginals_multi_batched(blr_handle* h, int memspace, int layout, int64_t B, 
   return io.finish();
 }
 
+// ---- exact leave-one-out predictives of a batched multi-output state: S columns, one leverage per input (blr_loo_multi_batched_*,
+// DESIGN.md K20; blr_loo_multi.hpp) -------------------------------------------------------------------------------------------------
+inline const void* loo_cols_kernel_ptr(double, int layout) { return loo_cols_kernel_ptr_f64(layout); }
+inline const void* loo_cols_kernel_ptr(float, int layout) { return loo_cols_kernel_ptr_f32(layout); }
+inline void loo_cols_kernel_launch(int layout, dim3 grid, size_t lds, hipStream_t st, const LooColsArgs<double>& a) { loo_cols_kernel_launch_f64(layout, grid, lds, st, a); }
+inline void loo_cols_kernel_launch(int layout, dim3 grid, size_t lds, hipStream_t st, const LooColsArgs<float>& a) { loo_cols_kernel_launch_f32(layout, grid, lds, st, a); }
+inline void loo_cols_finish_launch(dim3 grid, hipStream_t st, const LooColsArgs<double>& a, const double* mean, int64_t ldmn, int64_t stridemn, const double* var, int64_t ldw) { loo_cols_finish_launch_f64(grid, st, a, mean, ldmn, stridemn, var, ldw); }
+inline void loo_cols_finish_launch(dim3 grid, hipStream_t st, const LooColsArgs<float>& a, const float* mean, int64_t ldmn, int64_t stridemn, const float* var, int64_t ldw) { loo_cols_finish_launch_f32(grid, st, a, mean, ldmn, stridemn, var, ldw); }
+
+template <typename T>
+int loo_multi_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t N, int64_t S, const T* X, int64_t ldx,
+                      int64_t strideX, const T* Y, int64_t ldY, int64_t strideY, int noise_kind, const T* s, int64_t strides, const T* M,
+                      int64_t ldm, int64_t strideM, const T* Tf, int64_t ldt, int64_t strideT, T* loo_mean, int64_t ld_lm, int64_t stride_lm,
+                      T* loo_var, int64_t stride_lv, double* loo_logpdf, int64_t ld_ll, int64_t stride_ll, double* loo_total, int64_t stride_lt,
+                      int32_t* info) {
+  // (the argument checks come before the handle's: they need no device)
+  if (h) h->err.clear();
+  if (memspace != BLR_MEM_HOST && memspace != BLR_MEM_DEVICE) return bad_arg(h, 2, "memspace");
+  if (layout != BLR_LAYOUT_COLVECS && layout != BLR_LAYOUT_ROWVECS) return bad_arg(h, 3, "unknown layout (reference :26-31)");
+  if (B < 0 || B > (1 << 30)) return bad_arg(h, 4, "B out of range (0..2^30)");
+  if (D < 1 || D > kMaxLargeD) return bad_arg(h, 5, "D out of range (1..8192)");
+  if (N < 0 || N > (1 << 30)) return bad_arg(h, 6, "N out of range (0..2^30)");
+  if (S < 0 || S > (1 << 20)) return bad_arg(h, 7, "S out of range (0..2^20)");
+  if (B == 0 || S == 0) return 0;
+  if (N > 0 && !X) return bad_arg(h, 8, "X is NULL");
+  if (layout == BLR_LAYOUT_COLVECS ? ldx < D : ldx < std::max<int64_t>(N, 1)) return bad_arg(h, 9, "ldx too small");
+  if (strideX < 0) return bad_arg(h, 10, "strideX < 0");
+  if (N > 0 && !Y) return bad_arg(h, 11, "Y is NULL (reference :74 length check)");
+  if (ldY < N) return bad_arg(h, 12, "ldY < N");
+  if (strideY < 0) return bad_arg(h, 13, "strideY < 0");
+  if (noise_kind != BLR_NOISE_ISOTROPIC && noise_kind != BLR_NOISE_DIAGONAL)
+    return bad_arg(h, 14, "noise_kind (dense noise has no single-observation LOO: that is a block LOO)");
+  if (N > 0 && !s) return bad_arg(h, 15, "s is NULL");
+  if (strides < 0) return bad_arg(h, 16, "strides < 0");
+  if (!M) return bad_arg(h, 17, "M is NULL");
+  if (ldm < D) return bad_arg(h, 18, "ldm < D");
+  if (strideM < 0) return bad_arg(h, 19, "strideM < 0");
+  if (!Tf) return bad_arg(h, 20, "T is NULL");
+  if (ldt < D) return bad_arg(h, 21, "ldt < D");
+  if (strideT < 0) return bad_arg(h, 22, "strideT < 0");
+  if (loo_mean && ld_lm < N) return bad_arg(h, 24, "ld_lm < N");
+  if (loo_mean && B > 1 && stride_lm < ld_lm * S) return bad_arg(h, 25, "stride_lm < ld_lm * S");
+  if (loo_var && B > 1 && stride_lv < N) return bad_arg(h, 27, "stride_lv < N");
+  if (loo_logpdf && ld_ll < N) return bad_arg(h, 29, "ld_ll < N");
+  if (loo_logpdf && B > 1 && stride_ll < ld_ll * S) return bad_arg(h, 30, "stride_ll < ld_ll * S");
+  if (loo_total && B > 1 && stride_lt < S) return bad_arg(h, 32, "stride_lt < S");
+  if (!info) return bad_arg(h, 33, "info is NULL");
+  if (!h) return -1;
+  HIP_TRY(h, hipSetDevice(h->device));
+
+  CallIO io(h, memspace);
+  LooColsArgs<T> a{};
+  a.ldx = ldx; a.strideX = strideX; a.ldY = ldY; a.strideY = strideY; a.strides = strides; a.ldm = ldm; a.strideM = strideM;
+  a.ld_lm = ld_lm; a.stride_lm = stride_lm; a.stride_lv = stride_lv; a.ld_ll = ld_ll; a.stride_ll = stride_ll;
+  a.noise_kind = noise_kind; a.D = (int)D; a.N = (int)N; a.S = (int)S;
+  const size_t x_one = N == 0 ? 0 : (layout == BLR_LAYOUT_COLVECS ? mat_extent(D, N, ldx) : mat_extent(N, D, ldx));
+  const size_t s_one = N == 0 ? 0 : (noise_kind == BLR_NOISE_DIAGONAL ? (size_t)N : 1);
+  const T* T_d = nullptr;
+  double* tot_d = nullptr;
+  int32_t* info_d = nullptr;
+  int rc;
+  if ((rc = io.in(X, x_one ? extent(B, strideX, x_one) : 0, &a.X))) return rc;
+  if ((rc = io.in(Y, N ? extent(B, strideY, mat_extent(N, S, ldY)) : 0, &a.Y))) return rc;
+  if ((rc = io.in(s, s_one ? extent(B, strides, s_one) : 0, &a.s))) return rc;
+  if ((rc = io.in(M, extent(B, strideM, mat_extent(D, S, ldm)), &a.M))) return rc;
+  if ((rc = io.in(Tf, extent(B, strideT, mat_extent(D, D, ldt)), &T_d))) return rc;
+  if ((rc = io.out(loo_mean, N ? extent(B, stride_lm, mat_extent(N, S, ld_lm)) : 0, &a.lm))) return rc;
+  if ((rc = io.out(loo_var, N ? extent(B, stride_lv, (size_t)N) : 0, &a.lv))) return rc;
+  if ((rc = io.out(loo_logpdf, N ? extent(B, stride_ll, mat_extent(N, S, ld_ll)) : 0, &a.ll))) return rc;
+  if ((rc = io.out(loo_total, extent(B, stride_lt, (size_t)S), &tot_d))) return rc;
+  if ((rc = io.out(info, (size_t)B, &info_d))) return rc;
+  a.info = info_d;
+  if ((rc = ensure_stats(h))) return rc;
+  a.degenerate = h->stats_dev + 3;
+
+  // status: loo_check_kernel as blr_loo_batched_* launches it
+  for (int64_t b0 = 0; b0 < B; b0 += 65535)
+    hipLaunchKernelGGL(loo_check_kernel<T>, dim3((unsigned)std::min<int64_t>(65535, B - b0)), dim3(kThreads), 0, h->stream, T_d + b0 * strideT,
+                       ldt, strideT, (int)D, a.s + b0 * strides, strides, noise_kind, (int)N, info_d + b0);
+  HIP_TRY(h, hipGetLastError());
+  if (N == 0) {  // empty sums, for the regressors whose state passed the check
+    for (int64_t b0 = 0; tot_d && b0 < B; b0 += 65535)
+      loo_cols_total_launch(dim3((unsigned)S, (unsigned)std::min<int64_t>(65535, B - b0)), h->stream, (const double*)nullptr, 0, 0, 0, tot_d,
+                            stride_lt, info_d, (int)b0);
+    HIP_TRY(h, hipGetLastError());
+    return io.finish();
+  }
+
+  // chunks of regressors: grid.y, the images (D <= 128) and the per-chunk intermediates each within their bound
+  const bool small = D <= kMaxSmallD;
+  const bool ll_ws = tot_d && !a.ll;  // the totals need the log densities somewhere
+  const size_t item = sizeof(T), row = ((size_t)N * item + 255) & ~(size_t)255, row_ll = ((size_t)N * sizeof(double) + 255) & ~(size_t)255;
+  const size_t per = (small ? 0 : (1 + (size_t)S) * row + sizeof(int32_t)) + (ll_ws ? (size_t)S * row_ll : 0);
+  using MG = MargGemmCfg<T>;
+  int64_t chunk = std::min<int64_t>(B, 65535);
+  if (small) chunk = std::min<int64_t>(chunk, ((int64_t)256 << 20) / (MG::IMG_ELEMS * (int64_t)sizeof(T)));
+  if (per) chunk = std::max<int64_t>(1, std::min<int64_t>(chunk, (int64_t)(kLooWorkspace / per)));
+  const size_t off_mean = (size_t)chunk * row;                                  // (D > 128) var first, then the means
+  const size_t off_ll = small ? 0 : off_mean + (size_t)chunk * S * row;
+  const size_t off_zero = off_ll + (ll_ws ? (size_t)chunk * S * row_ll : 0), off_inf = off_zero + 256;
+  if (per && (rc = h->loo_ws.reserve(h, off_inf + (size_t)chunk * sizeof(int32_t) + 256))) return rc;
+  char* const ws = h->loo_ws.p;
+  const int64_t ldw = (int64_t)(row / item), ldll_ws = (int64_t)(row_ll / sizeof(double));
+  const size_t lds = loo_cols_lds_bytes(sizeof(T), (int)D);
+  if (small) {
+    if ((rc = set_lds_once(h, loo_cols_kernel_ptr(T(0), layout), lds))) return rc;
+    if ((rc = h->aux.reserve(h, (size_t)chunk * MG::IMG_ELEMS * sizeof(T)))) return rc;
+    if ((rc = set_lds_once(h, marg_image_kernel<T>, (size_t)TrsmCfg<T>::LDS_BYTES))) return rc;
+  } else {
+    HIP_TRY(h, hipMemsetAsync(ws + off_zero, 0, sizeof(T), h->stream));  // the variance route's zero noise
+  }
+  const int64_t ntiles = (N + kMargTile - 1) / kMargTile;
+  for (int64_t b0 = 0; b0 < B; b0 += chunk) {
+    const int64_t nb = std::min<int64_t>(chunk, B - b0);
+    LooColsArgs<T> c = a;
+    c.reg0 = (int)b0;
+    if (ll_ws) {  // (indexed by the global regressor)
+      c.ld_ll = ldll_ws; c.stride_ll = ldll_ws * S;
+      c.ll = reinterpret_cast<double*>(ws + off_ll) - b0 * c.stride_ll;
+    }
+    if (small) {
+      // L^-T of every factor as an MFMA image (marg_image_kernel, the existing instantiation), then ONE launch over (tile groups, regressors)
+      T* const img = reinterpret_cast<T*>(h->aux.p);
+      hipLaunchKernelGGL(marg_image_kernel<T>, dim3((unsigned)nb, 2), dim3(kThreads), TrsmCfg<T>::LDS_BYTES, h->stream, T_d + b0 * strideT, ldt,
+                         strideT, (int)D, img, (const int32_t*)(info_d + b0), 0);
+      // every workgroup amortises its set-up (the image) over its tiles: about two workgroups per CU in all
+      const int64_t ngroups = std::max<int64_t>(1, std::min<int64_t>(ntiles, (2 * (int64_t)h->cus + nb - 1) / nb));
+      c.img = img; c.ngroups = (int)ngroups;
+      loo_cols_kernel_launch(layout, dim3((unsigned)ngroups, (unsigned)nb), lds, h->stream, c);
+    } else {
+      // correct, not fast: the LATENT variance (zero noise) of the chunk by the large-D route of blr_marginals_batched_*, the means one
+      // regressor after the other as X'M (launch_project), then the epilogue.  A state that failed the check is skipped by the finish.
+      T* const var = reinterpret_cast<T*>(ws);
+      T* const mean = reinterpret_cast<T*>(ws + off_mean);
+      {
+        const AsyncScope no_drain(h, true);  // (between the halves)
+        // (mw is not read without a mean; X stands in as a non-NULL pointer)
+        rc = marginals_batched<T>(h, BLR_MEM_DEVICE, layout, nb, D, N, a.X + b0 * strideX, ldx, strideX, BLR_NOISE_ISOTROPIC,
+                                  reinterpret_cast<const T*>(ws + off_zero), 0, BLR_PRIOR_UPPER_FACTOR, a.X, 0, T_d + b0 * strideT, ldt, strideT,
+                                  (T*)nullptr, 0, var, ldw, reinterpret_cast<int32_t*>(ws + off_inf));
+      }
+      if (rc) return rc;
+      h->err.clear();
+      for (int64_t b = 0; b < nb; ++b)
+        launch_project<T>(h, layout, D, N, S, a.X + (b0 + b) * strideX, ldx, a.M + (b0 + b) * strideM, ldm, (const T*)nullptr, BLR_NOISE_ISOTROPIC,
+                          (const T*)nullptr, 0, mean + b * S * ldw, ldw);
+      const int64_t gx = std::max<int64_t>(1, std::min<int64_t>((N + kThreads - 1) / kThreads, (4 * (int64_t)h->cus + nb - 1) / nb));
+      loo_cols_finish_launch(dim3((unsigned)gx, (unsigned)nb), h->stream, c, (const T*)mean, ldw, S * ldw, (const T*)var, ldw);
+    }
+    if (tot_d)
+      loo_cols_total_launch(dim3((unsigned)S, (unsigned)nb), h->stream, (const double*)c.ll, c.ld_ll, c.stride_ll, (int)N, tot_d, stride_lt, info_d,
+                            (int)b0);
+    HIP_TRY(h, hipGetLastError());
+  }
+  return io.finish();
+}
+
 // ---- rank-k update / downdate of a resident MULTI-OUTPUT state: one factor, S mean columns (blr_update_multi_factor_*,
 // blr_downdate_multi_factor_*; blr_state_cols.hpp) ---------------------------------------------------------------------
 inline const void* state_cols_kernel_ptr(double, bool down, bool global) { return state_cols_kernel_ptr_f64(down, global); }
@@ -3930,6 +4088,17 @@ int blr_timer_stop(blr_handle* h, float* elapsed_ms) {
     return marginals_multi_batched<T>(h, memspace, layout, B, D, N, S, X, ldx, strideX, noise_kind, s, strides,     \
                                       prior_kind, M, ldm, strideM, Lw, ldl, strideLw, mean, ldmean, stridemean,     \
                                       var, stridevar, info);                                                        \
+  }                                                                                                                 \
+  int blr_loo_multi_batched_##SUF(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t N,         \
+                                  int64_t S, const T* X, int64_t ldx, int64_t strideX, const T* Y, int64_t ldY,     \
+                                  int64_t strideY, int noise_kind, const T* s, int64_t strides, const T* M,         \
+                                  int64_t ldm, int64_t strideM, const T* Tf, int64_t ldt, int64_t strideT,          \
+                                  T* loo_mean, int64_t ld_lm, int64_t stride_lm, T* loo_var, int64_t stride_lv,     \
+                                  double* loo_logpdf, int64_t ld_ll, int64_t stride_ll, double* loo_total,          \
+                                  int64_t stride_lt, int32_t* info) {                                               \
+    return loo_multi_batched<T>(h, memspace, layout, B, D, N, S, X, ldx, strideX, Y, ldY, strideY, noise_kind, s,   \
+                                strides, M, ldm, strideM, Tf, ldt, strideT, loo_mean, ld_lm, stride_lm, loo_var,    \
+                                stride_lv, loo_logpdf, ld_ll, stride_ll, loo_total, stride_lt, info);               \
   }                                                                                                                 \
   int blr_update_multi_factor_##SUF(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t k,       \
                                     int64_t S, const T* X, int64_t ldx, int64_t strideX, const T* Y, int64_t ldY,   \

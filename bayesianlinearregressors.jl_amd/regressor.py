@@ -26,7 +26,7 @@ __all__ = [
     "ColVecs", "RowVecs", "Diagonal", "Symmetric", "PDMat", "Normal", "RandomFourierFeatures",
     "BayesianLinearRegressor", "BasisFunctionRegressor", "BLRFunctionSample", "FiniteGP",
     "mean", "var", "cov", "std", "mean_and_var", "mean_and_cov", "marginals", "rand", "rand_b", "logpdf", "posterior",
-    "LOO", "loo", "loo_map",
+    "LOO", "loo", "loo_map", "loo_columns", "loo_columns_map",
     "EvidenceGrid", "logpdf_grid", "posterior_best", "logpdf_grid_map",
     "posterior_ragged", "logpdf_ragged",
     "posterior_columns", "logpdf_columns_map", "posterior_columns_map",
@@ -1034,6 +1034,136 @@ def loo_map(fxs, ys):
     return _loo_batch(probs, dtype)
 
 
+# ---------------------------------------------------------------------------------------------------
+# exact leave-one-out for matrix targets: S columns share the leverage of an input (blr_loo_multi_batched_*)
+# ---------------------------------------------------------------------------------------------------
+def _loo_columns_call(h, dtype, layout, B, D, N, S, dX, ldx, strideX, dY, strideY, noise_kind, ds, strides, d_M, strideM, d_T, strideT,
+                      temps):
+    """blr_loo_multi_batched_* on device operands -> (mean [B, N, S], var [B, N], logpdf [B, N, S], total [B, S], info [B]) on the
+    host."""
+    item = np.dtype(dtype).itemsize
+    outs = [_DeviceBuffer(h, B * N * S * item), _DeviceBuffer(h, B * N * item), _DeviceBuffer(h, B * N * S * 8), _DeviceBuffer(h, B * S * 8),
+            _DeviceBuffer.of(h, np.zeros(B, dtype=np.int32))]
+    temps.extend(outs)
+    d_lm, d_lv, d_ll, d_tot, d_info = (b.ptr for b in outs)
+    h.loo_multi_batched(dtype, _abi.MEM_DEVICE, layout, B, D, N, S, dX, ldx, strideX, dY, max(N, 1), strideY, noise_kind, ds, strides,
+                        d_M, max(D, 1), strideM, d_T, max(D, 1), strideT, d_lm, max(N, 1), N * S, d_lv, N, d_ll, max(N, 1), N * S, d_tot, S,
+                        d_info)
+    m, v = np.empty((B, N * S), dtype=dtype), np.empty((B, N), dtype=dtype)
+    lp, tot, info = np.empty((B, N * S), dtype=np.float64), np.empty((B, S), dtype=np.float64), np.zeros(B, dtype=np.int32)
+    for host, dptr in ((m, d_lm), (v, d_lv), (lp, d_ll), (tot, d_tot), (info, d_info)):
+        h.memcpy_d2h(host, dptr)
+    return (m.reshape((B, S, N)).transpose(0, 2, 1), v, lp.reshape((B, S, N)).transpose(0, 2, 1), tot, info)  # (column-major N x S)
+
+
+def _loo_columns_problem(fx, Y, dtype):
+    """(X, layout, ldx, D, N, Y, s, noise_kind, mw, Lw, prior_kind, ldl) of one finite regressor with an N x S target matrix."""
+    fb = _to_finite_blr(fx)
+    X, layout, ldx, D, N = _x_layout(fb.x, dtype)
+    Y = np.asfortranarray(Y, dtype=dtype)
+    if Y.ndim != 2:
+        raise ValueError("Y must be an N x S matrix")
+    if Y.shape[0] != N:
+        raise ValueError("length(y) != size(fx.x.X, 2)")  # reference :74
+    s, noise_kind = _noise(fb.Sy, N, dtype)
+    if noise_kind == _abi.NOISE_DENSE:
+        raise NotImplementedError("loo_columns: with a dense noise covariance one observation is not independent of the rest (that "
+                                  "is a block leave-out); isotropic or diagonal noise only")
+    Lw, prior_kind, ldl = _prior(fb.f.Lw, D, dtype)
+    return X, layout, ldx, D, N, Y, s, noise_kind, _mean_vector(fb.f.mw, D, dtype), Lw, prior_kind, ldl
+
+
+def _loo_columns_batch(probs, dtype):
+    """LOO of equally shaped matrix-target problems: their data staged once, blr_posterior_multi_batched_* into device buffers (M, T)
+    -- the pipeline of `loo_map` -- then blr_loo_multi_batched_* on the same device inputs.  Nothing D x D comes back to the host."""
+    X0, layout, ldx, D, N, Y0, _, noise_kind, _, _, prior_kind, ldl = probs[0]
+    S = Y0.shape[1]
+    nb, h, item = len(probs), _handle(), np.dtype(dtype).itemsize
+    Xb = np.stack([q[0].reshape(-1, order="A") for q in probs])
+    Yb = np.stack([q[5].reshape(-1, order="F") for q in probs])  # N x S column-major per data set, ldY = N
+    sb = np.stack([q[6] for q in probs])
+    mwb = np.stack([q[8] for q in probs])
+    Lb = np.stack([q[9].reshape(-1, order="A") for q in probs])
+    temps = []
+
+    def dev(a):
+        temps.append(_DeviceBuffer.of(h, a))
+        return temps[-1].ptr
+
+    try:
+        dX, dY, ds = dev(Xb), dev(Yb), dev(sb)
+        temps.extend([_DeviceBuffer(h, nb * D * S * item), _DeviceBuffer(h, nb * D * D * item)])
+        d_M, d_T = temps[-2].ptr, temps[-1].ptr
+        d_info = dev(np.zeros(nb, dtype=np.int32))
+        h.posterior_multi_batched(dtype, _abi.MEM_DEVICE, layout, nb, D, N, S, dX, ldx, Xb.shape[1], dY, max(N, 1), Yb.shape[1], noise_kind,
+                                  ds, sb.shape[1], prior_kind, dev(mwb), D, dev(Lb), ldl, Lb.shape[1], d_M, D, D * S, d_T, D, D * D, None, D,
+                                  D * D, None, S, d_info)
+        info = np.zeros(nb, dtype=np.int32)
+        h.memcpy_d2h(info, d_info)
+        if not np.any(info):
+            m, v, lp, tot, info = _loo_columns_call(h, dtype, layout, nb, D, N, S, dX, ldx, Xb.shape[1], dY, Yb.shape[1], noise_kind, ds,
+                                                    sb.shape[1], d_M, D * S, d_T, D * D, temps)
+    finally:
+        for b in temps:
+            b.free()
+    bad = np.flatnonzero(info)
+    if bad.size:
+        e = _abi.PosDefException(int(info[bad[0]]))
+        e.index = int(bad[0])
+        raise e
+    return [LOO(m[b], v[b], lp[b], tot[b]) for b in range(nb)]
+
+
+def _loo_columns_dtype(fx, Y):
+    return _dtype_of(fx.f.blr.mw if isinstance(fx.f, BasisFunctionRegressor) else fx.f.mw, Y)
+
+
+def loo_columns(fx, Y):
+    """Exact leave-one-out predictives of a matrix target (include/blr_mi355x.h blr_loo_multi_batched_*): for every observation n and
+    column c the predictive of Y[n, c] under posterior(fx without observation n, Y[:, c]) -- `loo(fx, Y[:, c])` for every c, with the
+    leverage of an input computed once.  Returns LOO(mean N x S, var N -- it does not depend on the column --, logpdf N x S, total S).
+    Dense noise raises NotImplementedError (a block LOO)."""
+    return loo_columns_map([fx], [Y])[0]
+
+
+def loo_columns_map(fxs, Ys):
+    """[loo_columns(fx, Y) for fx, Y in zip(fxs, Ys)] in one posterior call and one LOO call for equally shaped problems (else one
+    pair of calls per problem).  The first problem whose prior, noise or posterior is not positive definite raises PosDefException
+    with its position as ``index``."""
+    fxs, Ys = list(fxs), [np.asarray(Y) for Y in Ys]
+    if len(fxs) != len(Ys):
+        raise ValueError("as many target matrices as finite regressors are needed")
+    if not fxs:
+        return []
+    dtype = np.float32 if all(_loo_columns_dtype(fx, Y) == np.float32 for fx, Y in zip(fxs, Ys)) else np.float64
+    probs = [_loo_columns_problem(fx, Y, dtype) for fx, Y in zip(fxs, Ys)]
+
+    def one(q):
+        N, S = q[5].shape
+        if q[3] == 0 or N == 0 or S == 0:
+            return LOO(np.empty((N, S), dtype=dtype), np.empty(N, dtype=dtype), np.empty((N, S)), np.zeros(S))
+        return _loo_columns_batch([q], dtype)[0]
+
+    def one_by_one():
+        out = []
+        for i, q in enumerate(probs):
+            try:
+                out.append(one(q))
+            except _abi.PosDefException as e:
+                e.index = i
+                raise
+        return out
+
+    if any(isinstance(fx.f, BasisFunctionRegressor) and isinstance(fx.f.phi, RandomFourierFeatures) for fx in fxs):
+        return one_by_one()
+    sig = {(q[0].shape, q[0].flags.f_contiguous, q[1], q[3], q[4], q[5].shape[1], q[7], q[10],
+            isinstance((fx.f.blr if isinstance(fx.f, BasisFunctionRegressor) else fx.f).Lw, PDMat)) for q, fx in zip(probs, fxs)}
+    q0 = probs[0]
+    if len(sig) != 1 or q0[3] == 0 or q0[4] == 0 or q0[5].shape[1] == 0:
+        return one_by_one()
+    return _loo_columns_batch(probs, dtype)
+
+
 EvidenceGrid = namedtuple("EvidenceGrid", ["logpdf", "best", "alpha", "tau"])
 EvidenceGrid.__doc__ = """Evidence of one data set under every (prior scale alpha_i, noise scale tau_j): logpdf[i, j] is
 logpdf(BayesianLinearRegressor(mw, alpha_i Lw)(x, tau_j Sy), y) (NaN where that setting is not positive definite), best the
@@ -1482,6 +1612,35 @@ class ResidentColumnsPosterior:
         log p(Y[:, c] | the data that remains).  A removal that would leave a precision that is not positive definite raises
         PosDefException(info) and leaves the state as it was."""
         return self._step(self._h.downdate_multi_factor, "forget", x, Sy, Y)
+
+    def loo(self, x, Sy, Y):
+        """Exact leave-one-out predictives of the observations (x, Sy, Y), Y one row of S targets per input, which the caller vouches
+        the state contains: per input and column what ``forget`` of that observation alone would report, without touching the state
+        (blr_loo_multi_batched_* on device pointers to the resident state, B = 1).  Returns LOO(mean N x S, var N, logpdf N x S,
+        total S); a state with a non-positive diagonal entry or a non-positive variance raises PosDefException(info)."""
+        dtype, h, D, S = self.dtype, self._h, self.D, self.S
+        temps = []
+
+        def dev(a):
+            temps.append(_DeviceBuffer.of(h, a))
+            return temps[-1].ptr
+
+        try:
+            dX, layout, ldx, N = self._col0._inputs(x, dev, temps)
+            Y = np.asfortranarray(Y, dtype=dtype)
+            if Y.shape != (N, S):
+                raise ValueError("Y must be (number of inputs) x S")  # reference :74 per column
+            s, noise_kind = _noise(Sy, N, dtype)
+            if noise_kind == _abi.NOISE_DENSE:
+                raise NotImplementedError("ResidentColumnsPosterior.loo takes scalar or diagonal noise (dense noise: a block leave-out)")
+            m, v, lp, tot, info = _loo_columns_call(h, dtype, layout, 1, D, N, S, dX, ldx, 0, dev(Y) if N else None, 0, noise_kind, dev(s), 0,
+                                                    self._M.ptr, 0, self._T.ptr, 0, temps)
+        finally:
+            for b in temps:
+                b.free()
+        if info[0] != 0:
+            raise _abi.PosDefException(int(info[0]))
+        return LOO(m[0], v[0], lp[0], tot[0])
 
     def _marginals(self, x, Sy, want_var):
         dtype, h, D, S = self.dtype, self._h, self.D, self.S

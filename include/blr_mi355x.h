@@ -697,6 +697,57 @@ int blr_loo_batched_f32(blr_handle* h, int memspace, int layout, int64_t B, int6
                         float* loo_mean, int64_t stride_lm, float* loo_var, int64_t stride_lv, double* loo_logpdf,
                         int64_t stride_ll, double* loo_total, int32_t* info);
 
+/* ---- exact LEAVE-ONE-OUT predictives of a MULTI-OUTPUT state: S target columns, one leverage per input ----------------------
+ * Replaces: reference src/bayesian_linear_regression.jl:55-58 (logpdf) per held-out point and COLUMN given the rest -- the repeated
+ * conditioning of test/bayesian_linear_regression.jl:49-70 once per observation and column, i.e. a loop of
+ * blr_downdate_multi_factor_* / blr_update_multi_factor_* at k = 1, or S calls of blr_loo_batched_* (which read X S times and redo
+ * |T^-T x_n|^2 S times).
+ * State (M, T) as blr_posterior_multi_batched_* writes it (mw_post block D x S, ldm >= D; T_post) or blr_update_multi_factor_* keeps
+ * it: T upper, only the upper triangle read; NOT modified.  It must be conditioned on a data set that contains the N observations
+ * (X, Y (N x S column-major per regressor, ldY >= N), s).  With A = T'T:
+ *   sigma2_n = |T^-T x_n|^2,  1 - h_n = (s_n - sigma2_n) / s_n,  loo_var[n] = s_n / (1 - h_n)   once per input (noise included)
+ *   m_nc = x_n'M[:, c],  r_nc = Y[n, c] - m_nc,  loo_mean[n, c] = Y[n, c] - r_nc / (1 - h_n)
+ *   loo_logpdf[n, c] = -1/2 [log 2 pi + log s_n - log(1 - h_n) + r_nc^2 / (s_n (1 - h_n))]     (double in both element types)
+ *   loo_total[b * stride_lt + c] = sum_n loo_logpdf[n, c] in a fixed order (the LOO-CV score of column c; double).
+ * sigma2_n and m_nc are computed in the element type, the rest in double.  A stride of 0 shares an input: strideX = 0, strideY = 0,
+ * strideM = 0, strides = 0 and strideT = 0 included.
+ * Outputs: loo_mean (N x S, ld_lm >= N), loo_var (N: ONE per input), loo_logpdf (N x S, ld_ll >= N), loo_total (S per regressor).
+ * Any of them may be NULL; with loo_total requested and loo_logpdf NULL the log densities go through handle workspace.
+ * info[B], as blr_loo_batched_* and in its order: T has a non-positive diagonal entry j -> j, else s_i is not positive -> i; every
+ * output of such a regressor is left untouched; the call returns 0.
+ * NaN rule: an input whose 1 - h_n is <= 0 in floating point or not finite gets NaN in loo_var, in all S of its means and log
+ * densities, and so in every one of the S totals; it is counted ONCE (not S times) by blr_get_stat "loo_degenerate".
+ * Argument errors (negative position; checked before the handle, so a NULL handle with valid arguments returns -1): memspace (2),
+ * layout (3), B (4), D (5), N (6), S (7) out of range, ldx too small (9), ldY < N (12), dense noise (14), ldm < D (18), ldt < D (21),
+ * ld_lm < N (24), ld_ll < N (29), a negative input stride, a NULL X / Y / s (N > 0) / M / T / info, and for B > 1 overlapping
+ * outputs: stride_lm < ld_lm * S (25), stride_lv < N (27), stride_ll < ld_ll * S (30), stride_lt < S (32).  B = 0 or S = 0 is a
+ * no-op returning 0.  N = 0: every requested total is 0 and info is 0 (for a state that passes the check).
+ * Limits: 1 <= D <= 8192, 0 <= N <= 2^30, 0 <= S <= 2^20, ColVecs or RowVecs with any ldx, isotropic or diagonal noise, host or
+ * device memspace; an async handle in device memspace only enqueues at D <= 128.
+ * Bit promises: results are bit-reproducible from call to call; the bits of a regressor do not depend on B or on its position in
+ * the batch; the bits of column c do not depend on S, on c's position (pass included) or on the other columns of Y and M; the bits
+ * of loo_var do not depend on S or on which other outputs are requested; host and device memspace give the same bits.  No
+ * bit-equality with blr_loo_batched_* is promised: the products run in a different order.
+ * Kernels (csrc/blr_loo_multi.hpp).  D <= 128: per chunk of regressors (<= 65535, images within 256 MiB) the status
+ * (loo_check_kernel), the triangular inverse as an MFMA image (marg_image_kernel), loo_cols_kernel over (tile groups, regressors)
+ * -- a workgroup keeps its 64-input tile, forms the leverage once and loops over the passes of 16 columns, so X is read once
+ * whatever S is -- and the totals (loo_cols_total_kernel); the launch count does not depend on S.  D > 128 is correct, not fast:
+ * the large-D variance route of blr_marginals_batched_* with zero noise and the means as X'M into handle workspace (chunks of
+ * regressors), then an epilogue kernel; this route may synchronise.
+ * _f32: X, Y, s, M, T, loo_mean and loo_var are float; loo_logpdf and loo_total stay double. */
+int blr_loo_multi_batched_f64(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t N, int64_t S,
+                              const double* X, int64_t ldx, int64_t strideX, const double* Y, int64_t ldY, int64_t strideY,
+                              int noise_kind, const double* s, int64_t strides, const double* M, int64_t ldm, int64_t strideM,
+                              const double* T, int64_t ldt, int64_t strideT, double* loo_mean, int64_t ld_lm, int64_t stride_lm,
+                              double* loo_var, int64_t stride_lv, double* loo_logpdf, int64_t ld_ll, int64_t stride_ll,
+                              double* loo_total, int64_t stride_lt, int32_t* info);
+int blr_loo_multi_batched_f32(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t N, int64_t S,
+                              const float* X, int64_t ldx, int64_t strideX, const float* Y, int64_t ldY, int64_t strideY,
+                              int noise_kind, const float* s, int64_t strides, const float* M, int64_t ldm, int64_t strideM,
+                              const float* T, int64_t ldt, int64_t strideT, float* loo_mean, int64_t ld_lm, int64_t stride_lm,
+                              float* loo_var, int64_t stride_lv, double* loo_logpdf, int64_t ld_ll, int64_t stride_ll,
+                              double* loo_total, int64_t stride_lt, int32_t* info);
+
 /* ---- evidence of one data set under a GRID of (prior scale, noise scale) settings, from one pass over the data ------------
  * Replaces: blr_posterior_batched_* called with strideX = 0, stridey = 0 and one scaled (s, Lw) pair per setting, which re-forms
  * the D x D Gram matrix per setting; reference src/bayesian_linear_regression.jl:55-58 (logpdf) on

@@ -1177,6 +1177,45 @@ function loo!(lm::Union{Nothing,DeviceArray{T}}, lv::Union{Nothing,DeviceArray{T
 end
 
 """
+    loo_multi_batched!(lmean, lvar, llogpdf, total, info, X, Y, s, M, T; D, N, S, B, isotropic)
+
+Exact leave-one-out predictives of the N observations with S targets each that B device-resident MULTI-OUTPUT states contain
+(`blr_loo_multi_batched_*`): per observation n and column c the predictive of Y[n, c] given all the other data -- reference
+`src/bayesian_linear_regression.jl:55-58` applied to each held-out point and column -- with the leverage of an input computed
+once for its S columns; the states (M D×S×B, T D×D×B as `posterior_multi_batched!` / `update_multi_factor!` leave them) are not
+modified.  X is D×N×B, Y N×S×B, s one variance (`isotropic`) or N×B.  lmean (N×S×B) and lvar (N×B: ONE per input) in the element
+type, llogpdf (N×S×B) and total (S×B, Σ_n llogpdf in a fixed order) in Float64; any of the four may be `nothing`.  A leverage
+within rounding of 1 gives NaN in lvar and in all S columns of that input (`get_stat("loo_degenerate")` counts it once);
+info[b] > 0: a bad factor, else a bad variance, and that state's outputs are left untouched.
+"""
+function loo_multi_batched!(lm::Union{Nothing,DeviceArray{T}}, lv::Union{Nothing,DeviceArray{T}}, ll::Union{Nothing,DeviceArray{Float64}},
+                            total::Union{Nothing,DeviceArray{Float64}}, info::DeviceArray{Int32}, X::DeviceArray{T}, Y::DeviceArray{T},
+                            s::DeviceArray{T}, M::DeviceArray{T}, Tf::DeviceArray{T}; D::Int, N::Int, S::Int, B::Int,
+                            isotropic::Bool) where {T<:Elt}
+    h = handle()
+    nk = isotropic ? ISOTROPIC : DIAGONALN
+    ptr(a) = a === nothing ? Ptr{T}(C_NULL) : a.ptr
+    dptr(a) = a === nothing ? Ptr{Cdouble}(C_NULL) : a.ptr
+    rc = if T === Float64
+        ccall((:blr_loo_multi_batched_f64, LIB), Cint,
+              (Ptr{Cvoid}, Cint, Cint, Int64, Int64, Int64, Int64, Ptr{T}, Int64, Int64, Ptr{T}, Int64, Int64, Cint, Ptr{T}, Int64,
+               Ptr{T}, Int64, Int64, Ptr{T}, Int64, Int64, Ptr{T}, Int64, Int64, Ptr{T}, Int64, Ptr{Cdouble}, Int64, Int64,
+               Ptr{Cdouble}, Int64, Ptr{Int32}),
+              h, MEM_DEVICE, COLVECS, B, D, N, S, X.ptr, D, D * N, Y.ptr, max(N, 1), N * S, nk, s.ptr, isotropic ? 0 : N, M.ptr, D, D * S,
+              Tf.ptr, D, D * D, ptr(lm), max(N, 1), N * S, ptr(lv), N, dptr(ll), max(N, 1), N * S, dptr(total), S, info.ptr)
+    else
+        ccall((:blr_loo_multi_batched_f32, LIB), Cint,
+              (Ptr{Cvoid}, Cint, Cint, Int64, Int64, Int64, Int64, Ptr{T}, Int64, Int64, Ptr{T}, Int64, Int64, Cint, Ptr{T}, Int64,
+               Ptr{T}, Int64, Int64, Ptr{T}, Int64, Int64, Ptr{T}, Int64, Int64, Ptr{T}, Int64, Ptr{Cdouble}, Int64, Int64,
+               Ptr{Cdouble}, Int64, Ptr{Int32}),
+              h, MEM_DEVICE, COLVECS, B, D, N, S, X.ptr, D, D * N, Y.ptr, max(N, 1), N * S, nk, s.ptr, isotropic ? 0 : N, M.ptr, D, D * S,
+              Tf.ptr, D, D * D, ptr(lm), max(N, 1), N * S, ptr(lv), N, dptr(ll), max(N, 1), N * S, dptr(total), S, info.ptr)
+    end
+    check(h, rc)
+    return nothing
+end
+
+"""
     loo(fx, y) -> (mean, var, logpdf)
 
 Leave-one-out predictives of the observations y at fx.x: the posterior of `fused` (reference `:60-69`), then one
