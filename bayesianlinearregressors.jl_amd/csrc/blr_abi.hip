@@ -41,6 +41,26 @@
 
 using namespace blr;
 
+// ---- the non-template kernels declared in blr_aux_kernels.hpp and blr_loo.hpp: their one definition ------------------------------
+namespace blr {
+
+__global__ __launch_bounds__(kThreads) void logpdf_sum_kernel(const double* __restrict__ lp, int64_t B,
+                                                              double* __restrict__ total) {
+  const double t = fixed_order_sum(lp, B);
+  if (threadIdx.x == 0) *total = t;
+}
+
+// loo_total[reg] = sum_n logpdf_n in a fixed order (no float atomics: the same bits at any B and position)
+__global__ __launch_bounds__(kThreads) void loo_total_kernel(const double* __restrict__ ll, int64_t stride_ll, int N,
+                                                             double* __restrict__ total, const int32_t* __restrict__ info, int reg0) {
+  const int64_t reg = reg0 + (int64_t)blockIdx.x;
+  if (info[reg] != 0) return;
+  const double t = fixed_order_sum(ll + reg * stride_ll, N);
+  if (threadIdx.x == 0) total[reg] = t;
+}
+
+}  // namespace blr
+
 namespace {
 
 // ---- RCCL, bound at run time -------------------------------------------------------------------------------------
@@ -1126,13 +1146,34 @@ int marginals_large_one(blr_handle* h, int layout, int64_t D, int64_t N, const T
   return 0;
 }
 
+// ---- the triangular inverses L^-T of a chunk of regressors as MFMA images (marg_image_kernel, blr_marginals.hpp) in the handle's
+// side buffer: what MargProduct, marginals_multi_batched and loo_multi_batched run before their product kernels
+template <typename T>
+struct MargImages {
+  using G = MargGemmCfg<T>;
+  static constexpr int64_t kMaxChunk = ((int64_t)256 << 20) / (G::IMG_ELEMS * (int64_t)sizeof(T));  // images of a chunk within 256 MiB
+  static int reserve(blr_handle* h, int64_t chunk) {
+    int rc;
+    if ((rc = h->aux.reserve(h, (size_t)chunk * G::IMG_ELEMS * sizeof(T)))) return rc;
+    return set_lds_once(h, marg_image_kernel<T>, (size_t)TrsmCfg<T>::LDS_BYTES);
+  }
+  // nb regressors from reg0 on (the kernel indexes U, info and the images by reg0 + blockIdx.x): the chunk's first image lands at the
+  // start of the buffer.  Returns the address the kernels index in the same way.
+  static T* launch(blr_handle* h, const T* U, int64_t ldu, int64_t strideU, int D, const int32_t* info, int64_t reg0, int64_t nb) {
+    T* const img = reinterpret_cast<T*>(h->aux.p) - reg0 * G::IMG_ELEMS;
+    hipLaunchKernelGGL(marg_image_kernel<T>, dim3((unsigned)nb, 2), dim3(kThreads), TrsmCfg<T>::LDS_BYTES, h->stream, U, ldu, strideU, D, img, info,
+                       (int)reg0);
+    return img;
+  }
+};
+
 // ---- D = 128 with a factor U (aligned ColVecs, or RowVecs): the triangular inverse once per regressor (marg_image_kernel), then a
 // dependency-free product stream with the epilogue of A at the store (marginals_gemm_kernel<T, ROWV, A>, blr_marginals.hpp).
 // A = MarginalArgs<T>: blr_marginals_batched_*; A = LooGemmArgs<T>: blr_loo_batched_*.  Regressors in chunks whose images fit 256 MiB.
 template <typename T, typename A>
 struct MargProduct {
   using G = MargGemmCfg<T>;
-  static constexpr int64_t kMaxChunk = ((int64_t)256 << 20) / (G::IMG_ELEMS * (int64_t)sizeof(T));
+  static constexpr int64_t kMaxChunk = MargImages<T>::kMaxChunk;
   static bool takes(const blr_handle* h, int layout, int64_t D, int64_t N, const T* X, int64_t ldx, int64_t strideX) {
     const bool rowv = layout == BLR_LAYOUT_ROWVECS;  // (RowVecs: scalar loads, no alignment to ask for)
     return !h->opt.no_marg_gemm && D == kPB && N >= 64 &&
@@ -1143,16 +1184,12 @@ struct MargProduct {
   }
   // the images of `chunk` regressors in the handle's side buffer, the two kernels' LDS limits
   static int prepare(blr_handle* h, int layout, int64_t chunk) {
-    int rc;
-    if ((rc = h->aux.reserve(h, (size_t)chunk * G::IMG_ELEMS * sizeof(T)))) return rc;
-    if ((rc = set_lds_once(h, marg_image_kernel<T>, (size_t)TrsmCfg<T>::LDS_BYTES))) return rc;
+    if (const int rc = MargImages<T>::reserve(h, chunk)) return rc;
     return set_lds_once(h, kernel(layout), (size_t)G::LDS_BYTES);
   }
   // regressors b0 .. b0 + nb - 1 (the kernels index regressor reg0 + blockIdx; the images of a chunk start at its first regressor)
   static void launch(blr_handle* h, A& a, const T* U, int64_t ldu, int64_t strideU, const int32_t* info, int64_t b0, int64_t nb) {
-    T* const img = reinterpret_cast<T*>(h->aux.p) - b0 * G::IMG_ELEMS;
-    hipLaunchKernelGGL(marg_image_kernel<T>, dim3((unsigned)nb, 2), dim3(kThreads), TrsmCfg<T>::LDS_BYTES, h->stream, U, ldu, strideU, (int)a.D,
-                       img, info, (int)b0);
+    T* const img = MargImages<T>::launch(h, U, ldu, strideU, (int)a.D, info, b0, nb);
     // two workgroups per CU, ONE round of them (tools/marg128_bench, 64 x 4096 inputs, stream kernel alone: 8 workgroups per
     // regressor 104.8 us, 16 -- two rounds -- 116.3, 32: 126.9; 256 regressors: 2 per regressor); every workgroup copies the
     // 74 KB image once: at least four tiles per wave
@@ -3221,10 +3258,6 @@ int posterior_ragged(blr_handle* h, int memspace, int layout, int64_t B, int64_t
 }
 
 // ---- batched multi-output posterior: S target columns per regressor (blr_posterior_multi_batched_*) ----------------
-inline const void* multi_cols_kernel_ptr(double, int layout) { return multi_cols_kernel_ptr_f64(layout); }
-inline const void* multi_cols_kernel_ptr(float, int layout) { return multi_cols_kernel_ptr_f32(layout); }
-inline void multi_cols_kernel_launch(int layout, dim3 grid, size_t lds, hipStream_t st, const MultiColsArgs<double>& a) { multi_cols_kernel_launch_f64(layout, grid, lds, st, a); }
-inline void multi_cols_kernel_launch(int layout, dim3 grid, size_t lds, hipStream_t st, const MultiColsArgs<float>& a) { multi_cols_kernel_launch_f32(layout, grid, lds, st, a); }
 
 template <typename T>
 int posterior_multi_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t N, int64_t S, const T* X, int64_t ldx,
@@ -3356,23 +3389,14 @@ int posterior_multi_batched(blr_handle* h, int memspace, int layout, int64_t B, 
   const int per_pass = kMultiColsPerPass - 1;
   const int64_t passes = std::max<int64_t>(1, (S - 1 + per_pass - 1) / per_pass);
   const size_t lds = multi_cols_lds_bytes(sizeof(T), (int)D, (int)std::min<int64_t>(S, kMultiColsPerPass));
-  const void* const kern = multi_cols_kernel_ptr(T(0), layout);
+  void (*const kern)(MultiColsArgs<T>) = layout == BLR_LAYOUT_ROWVECS ? multi_cols_kernel<T, LAYOUT_ROWVECS> : multi_cols_kernel<T, LAYOUT_COLVECS>;
   if ((rc = set_lds_once(h, kern, lds))) return rc;
-  multi_cols_kernel_launch(layout, dim3((unsigned)B, (unsigned)passes), lds, h->stream, m);
+  hipLaunchKernelGGL(kern, dim3((unsigned)B, (unsigned)passes), dim3(kThreads), lds, h->stream, m);
   HIP_TRY(h, hipGetLastError());
   return io.finish();
 }
 
 // ---- marginals of a batched multi-output posterior: S mean columns, one variance per input (blr_marginals_multi_batched_*) ----
-inline const void* marginals_cols_kernel_ptr(double, int layout) { return marginals_cols_kernel_ptr_f64(layout); }
-inline const void* marginals_cols_kernel_ptr(float, int layout) { return marginals_cols_kernel_ptr_f32(layout); }
-inline void marginals_cols_kernel_launch(int layout, dim3 grid, size_t lds, hipStream_t st, const MargColsArgs<double>& a) { marginals_cols_kernel_launch_f64(layout, grid, lds, st, a); }
-inline void marginals_cols_kernel_launch(int layout, dim3 grid, size_t lds, hipStream_t st, const MargColsArgs<float>& a) { marginals_cols_kernel_launch_f32(layout, grid, lds, st, a); }
-// marginals_cols_kernel reads the image marg_image_kernel writes: one layout, stated twice
-static_assert(MargColsImg<double>::IMG_ELEMS == MargGemmCfg<double>::IMG_ELEMS && MargColsImg<float>::IMG_ELEMS == MargGemmCfg<float>::IMG_ELEMS &&
-                  MargColsImg<double>::frag0(5) == MargGemmCfg<double>::frag0(5) && MargColsImg<double>::d_of(7, 3) == MargGemmCfg<double>::d_of(7, 3) &&
-                  MargColsImg<float>::d_of(7, 3) == MargGemmCfg<float>::d_of(7, 3) && kMargMaxD == kPB && kMargMaxD == kMaxSmallD,
-              "blr_marg_multi.hpp and blr_marginals.hpp disagree on the image of L^-T");
 
 template <typename T>
 int marginals_multi_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t N, int64_t S, const T* X, int64_t ldx,
@@ -3466,31 +3490,22 @@ int marginals_multi_batched(blr_handle* h, int memspace, int layout, int64_t B, 
   if (chol_info) HIP_TRY(h, hipMemcpyAsync(info_d, chol_info, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, h->stream));
   else HIP_TRY(h, hipMemsetAsync(info_d, 0, (size_t)B * sizeof(int32_t), h->stream));
   const bool with_image = var_d && kind == BLR_PRIOR_UPPER_FACTOR;
-  using MG = MargGemmCfg<T>;
-  const int64_t max_chunk = ((int64_t)256 << 20) / (MG::IMG_ELEMS * (int64_t)sizeof(T));  // images of a chunk within 256 MiB
-  const int64_t chunk = std::min<int64_t>(std::min<int64_t>(B, 65535), with_image ? max_chunk : 65535);
+  const int64_t chunk = std::min<int64_t>(std::min<int64_t>(B, 65535), with_image ? MargImages<T>::kMaxChunk : 65535);
   const size_t lds = marg_cols_lds_bytes(sizeof(T), (int)D, with_image);
-  const void* const kern = marginals_cols_kernel_ptr(T(0), layout);
+  void (*const kern)(MargColsArgs<T>) = layout == BLR_LAYOUT_ROWVECS ? marginals_cols_kernel<T, LAYOUT_ROWVECS> : marginals_cols_kernel<T, LAYOUT_COLVECS>;
   if ((rc = set_lds_once(h, kern, lds))) return rc;
-  if (with_image) {
-    if ((rc = h->aux.reserve(h, (size_t)chunk * MG::IMG_ELEMS * sizeof(T)))) return rc;
-    if ((rc = set_lds_once(h, marg_image_kernel<T>, (size_t)TrsmCfg<T>::LDS_BYTES))) return rc;
-  }
+  if (with_image && (rc = MargImages<T>::reserve(h, chunk))) return rc;
   const int64_t passes = mean_d ? (S + kMargColsPerPass - 1) / kMargColsPerPass : 1;
   const int64_t ntiles = (N + kMargTile - 1) / kMargTile;
   for (int64_t b0 = 0; b0 < B; b0 += chunk) {
     const int64_t nb = std::min<int64_t>(chunk, B - b0);
-    if (with_image) {
-      T* const img = reinterpret_cast<T*>(h->aux.p);
-      hipLaunchKernelGGL(marg_image_kernel<T>, dim3((unsigned)nb, 2), dim3(kThreads), TrsmCfg<T>::LDS_BYTES, h->stream, U + b0 * strideU, ldu, strideU,
-                         (int)D, img, chol_info ? (const int32_t*)(chol_info + b0) : (const int32_t*)nullptr, 0);
-      a.img = img;
-    }
+    if (with_image)
+      a.img = MargImages<T>::launch(h, U + b0 * strideU, ldu, strideU, (int)D, chol_info ? (const int32_t*)(chol_info + b0) : (const int32_t*)nullptr, 0, nb);
     // every workgroup amortises its set-up (the image, the fragments of M) over its tiles: about two workgroups per CU in all
     const int64_t ngroups = std::max<int64_t>(1, std::min<int64_t>(ntiles, (2 * (int64_t)h->cus + nb * passes - 1) / (nb * passes)));
     a.X = X_d; a.s = s_d; a.M = M_d; a.dprior = kind == BLR_PRIOR_DIAGONAL ? U : nullptr; a.stridedp = strideU;
     a.info = chol_info; a.mean = mean_d; a.var = var_d; a.ngroups = (int)ngroups; a.reg0 = (int)b0;
-    marginals_cols_kernel_launch(layout, dim3((unsigned)(passes * ngroups), (unsigned)nb), lds, h->stream, a);
+    hipLaunchKernelGGL(kern, dim3((unsigned)(passes * ngroups), (unsigned)nb), dim3(kThreads), lds, h->stream, a);
   }
   HIP_TRY(h, hipGetLastError());
   return io.finish();
@@ -3498,12 +3513,6 @@ int marginals_multi_batched(blr_handle* h, int memspace, int layout, int64_t B, 
 
 // ---- exact leave-one-out predictives of a batched multi-output state: S columns, one leverage per input (blr_loo_multi_batched_*,
 // DESIGN.md K20; blr_loo_multi.hpp) -------------------------------------------------------------------------------------------------
-inline const void* loo_cols_kernel_ptr(double, int layout) { return loo_cols_kernel_ptr_f64(layout); }
-inline const void* loo_cols_kernel_ptr(float, int layout) { return loo_cols_kernel_ptr_f32(layout); }
-inline void loo_cols_kernel_launch(int layout, dim3 grid, size_t lds, hipStream_t st, const LooColsArgs<double>& a) { loo_cols_kernel_launch_f64(layout, grid, lds, st, a); }
-inline void loo_cols_kernel_launch(int layout, dim3 grid, size_t lds, hipStream_t st, const LooColsArgs<float>& a) { loo_cols_kernel_launch_f32(layout, grid, lds, st, a); }
-inline void loo_cols_finish_launch(dim3 grid, hipStream_t st, const LooColsArgs<double>& a, const double* mean, int64_t ldmn, int64_t stridemn, const double* var, int64_t ldw) { loo_cols_finish_launch_f64(grid, st, a, mean, ldmn, stridemn, var, ldw); }
-inline void loo_cols_finish_launch(dim3 grid, hipStream_t st, const LooColsArgs<float>& a, const float* mean, int64_t ldmn, int64_t stridemn, const float* var, int64_t ldw) { loo_cols_finish_launch_f32(grid, st, a, mean, ldmn, stridemn, var, ldw); }
 
 template <typename T>
 int loo_multi_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t N, int64_t S, const T* X, int64_t ldx,
@@ -3578,8 +3587,8 @@ int loo_multi_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_
   HIP_TRY(h, hipGetLastError());
   if (N == 0) {  // empty sums, for the regressors whose state passed the check
     for (int64_t b0 = 0; tot_d && b0 < B; b0 += 65535)
-      loo_cols_total_launch(dim3((unsigned)S, (unsigned)std::min<int64_t>(65535, B - b0)), h->stream, (const double*)nullptr, 0, 0, 0, tot_d,
-                            stride_lt, info_d, (int)b0);
+      hipLaunchKernelGGL(loo_cols_total_kernel, dim3((unsigned)S, (unsigned)std::min<int64_t>(65535, B - b0)), dim3(kThreads), 0, h->stream,
+                         (const double*)nullptr, (int64_t)0, (int64_t)0, 0, tot_d, stride_lt, (const int32_t*)info_d, (int)b0);
     HIP_TRY(h, hipGetLastError());
     return io.finish();
   }
@@ -3589,9 +3598,8 @@ int loo_multi_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_
   const bool ll_ws = tot_d && !a.ll;  // the totals need the log densities somewhere
   const size_t item = sizeof(T), row = ((size_t)N * item + 255) & ~(size_t)255, row_ll = ((size_t)N * sizeof(double) + 255) & ~(size_t)255;
   const size_t per = (small ? 0 : (1 + (size_t)S) * row + sizeof(int32_t)) + (ll_ws ? (size_t)S * row_ll : 0);
-  using MG = MargGemmCfg<T>;
   int64_t chunk = std::min<int64_t>(B, 65535);
-  if (small) chunk = std::min<int64_t>(chunk, ((int64_t)256 << 20) / (MG::IMG_ELEMS * (int64_t)sizeof(T)));
+  if (small) chunk = std::min<int64_t>(chunk, MargImages<T>::kMaxChunk);
   if (per) chunk = std::max<int64_t>(1, std::min<int64_t>(chunk, (int64_t)(kLooWorkspace / per)));
   const size_t off_mean = (size_t)chunk * row;                                  // (D > 128) var first, then the means
   const size_t off_ll = small ? 0 : off_mean + (size_t)chunk * S * row;
@@ -3600,10 +3608,10 @@ int loo_multi_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_
   char* const ws = h->loo_ws.p;
   const int64_t ldw = (int64_t)(row / item), ldll_ws = (int64_t)(row_ll / sizeof(double));
   const size_t lds = loo_cols_lds_bytes(sizeof(T), (int)D);
+  void (*const kern)(LooColsArgs<T>) = layout == BLR_LAYOUT_ROWVECS ? loo_cols_kernel<T, LAYOUT_ROWVECS> : loo_cols_kernel<T, LAYOUT_COLVECS>;
   if (small) {
-    if ((rc = set_lds_once(h, loo_cols_kernel_ptr(T(0), layout), lds))) return rc;
-    if ((rc = h->aux.reserve(h, (size_t)chunk * MG::IMG_ELEMS * sizeof(T)))) return rc;
-    if ((rc = set_lds_once(h, marg_image_kernel<T>, (size_t)TrsmCfg<T>::LDS_BYTES))) return rc;
+    if ((rc = set_lds_once(h, kern, lds))) return rc;
+    if ((rc = MargImages<T>::reserve(h, chunk))) return rc;
   } else {
     HIP_TRY(h, hipMemsetAsync(ws + off_zero, 0, sizeof(T), h->stream));  // the variance route's zero noise
   }
@@ -3618,13 +3626,11 @@ int loo_multi_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_
     }
     if (small) {
       // L^-T of every factor as an MFMA image (marg_image_kernel, the existing instantiation), then ONE launch over (tile groups, regressors)
-      T* const img = reinterpret_cast<T*>(h->aux.p);
-      hipLaunchKernelGGL(marg_image_kernel<T>, dim3((unsigned)nb, 2), dim3(kThreads), TrsmCfg<T>::LDS_BYTES, h->stream, T_d + b0 * strideT, ldt,
-                         strideT, (int)D, img, (const int32_t*)(info_d + b0), 0);
+      c.img = MargImages<T>::launch(h, T_d + b0 * strideT, ldt, strideT, (int)D, (const int32_t*)(info_d + b0), 0, nb);
       // every workgroup amortises its set-up (the image) over its tiles: about two workgroups per CU in all
       const int64_t ngroups = std::max<int64_t>(1, std::min<int64_t>(ntiles, (2 * (int64_t)h->cus + nb - 1) / nb));
-      c.img = img; c.ngroups = (int)ngroups;
-      loo_cols_kernel_launch(layout, dim3((unsigned)ngroups, (unsigned)nb), lds, h->stream, c);
+      c.ngroups = (int)ngroups;
+      hipLaunchKernelGGL(kern, dim3((unsigned)ngroups, (unsigned)nb), dim3(kThreads), lds, h->stream, c);
     } else {
       // correct, not fast: the LATENT variance (zero noise) of the chunk by the large-D route of blr_marginals_batched_*, the means one
       // regressor after the other as X'M (launch_project), then the epilogue.  A state that failed the check is skipped by the finish.
@@ -3643,11 +3649,12 @@ int loo_multi_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_
         launch_project<T>(h, layout, D, N, S, a.X + (b0 + b) * strideX, ldx, a.M + (b0 + b) * strideM, ldm, (const T*)nullptr, BLR_NOISE_ISOTROPIC,
                           (const T*)nullptr, 0, mean + b * S * ldw, ldw);
       const int64_t gx = std::max<int64_t>(1, std::min<int64_t>((N + kThreads - 1) / kThreads, (4 * (int64_t)h->cus + nb - 1) / nb));
-      loo_cols_finish_launch(dim3((unsigned)gx, (unsigned)nb), h->stream, c, (const T*)mean, ldw, S * ldw, (const T*)var, ldw);
+      hipLaunchKernelGGL(loo_cols_finish_kernel<T>, dim3((unsigned)gx, (unsigned)nb), dim3(kThreads), 0, h->stream, c, (const T*)mean, ldw, S * ldw,
+                         (const T*)var, ldw);
     }
     if (tot_d)
-      loo_cols_total_launch(dim3((unsigned)S, (unsigned)nb), h->stream, (const double*)c.ll, c.ld_ll, c.stride_ll, (int)N, tot_d, stride_lt, info_d,
-                            (int)b0);
+      hipLaunchKernelGGL(loo_cols_total_kernel, dim3((unsigned)S, (unsigned)nb), dim3(kThreads), 0, h->stream, (const double*)c.ll, c.ld_ll,
+                         c.stride_ll, (int)N, tot_d, stride_lt, (const int32_t*)info_d, (int)b0);
     HIP_TRY(h, hipGetLastError());
   }
   return io.finish();
@@ -3655,12 +3662,6 @@ int loo_multi_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_
 
 // ---- rank-k update / downdate of a resident MULTI-OUTPUT state: one factor, S mean columns (blr_update_multi_factor_*,
 // blr_downdate_multi_factor_*; blr_state_cols.hpp) ---------------------------------------------------------------------
-inline const void* state_cols_kernel_ptr(double, bool down, bool global) { return state_cols_kernel_ptr_f64(down, global); }
-inline const void* state_cols_kernel_ptr(float, bool down, bool global) { return state_cols_kernel_ptr_f32(down, global); }
-inline void state_cols_kernel_launch(bool down, bool global, dim3 grid, size_t lds, hipStream_t st, const StateColsArgs<double>& a) { state_cols_kernel_launch_f64(down, global, grid, lds, st, a); }
-inline void state_cols_kernel_launch(bool down, bool global, dim3 grid, size_t lds, hipStream_t st, const StateColsArgs<float>& a) { state_cols_kernel_launch_f32(down, global, grid, lds, st, a); }
-inline void state_diag_kernel_launch(hipStream_t st, const double* Tf, int64_t ldt, int64_t strideT, int D, int64_t B, double* d0) { state_diag_kernel_launch_f64(st, Tf, ldt, strideT, D, B, d0); }
-inline void state_diag_kernel_launch(hipStream_t st, const float* Tf, int64_t ldt, int64_t strideT, int D, int64_t B, float* d0) { state_diag_kernel_launch_f32(st, Tf, ldt, strideT, D, B, d0); }
 
 static_assert(kStateChunk == kSweepMaxK, "state_cols_kernel walks the observations in the sweep's chunks");
 
@@ -3749,9 +3750,12 @@ int state_multi_factor(blr_handle* h, int memspace, int layout, int64_t B, int64
   T* const diag0 = reinterpret_cast<T*>(h->multi_ws.p + lp0_bytes);
   a.lp0 = lp0; a.diag0 = diag0;
   a.T0 = reinterpret_cast<T*>(h->multi_ws.p + lp0_bytes + diag_bytes);
-  state_diag_kernel_launch(h->stream, T_d, ldt, strideT, (int)D, B, diag0);
+  hipLaunchKernelGGL(state_diag_kernel<T>, dim3((unsigned)((B * D + kThreads - 1) / kThreads)), dim3(kThreads), 0, h->stream, (const T*)T_d, ldt,
+                     strideT, (int)D, B * D, diag0);
   if constexpr (sizeof(T) == 4) {
-    if (save_T) state_save_kernel_launch_f32(h->stream, T_d, ldt, strideT, (int)D, B, const_cast<T*>(a.T0));
+    if (save_T)
+      hipLaunchKernelGGL(state_save_kernel<T>, dim3((unsigned)((B * D * D + kThreads - 1) / kThreads)), dim3(kThreads), 0, h->stream, (const T*)T_d,
+                         ldt, strideT, (int)D, B * D * D, const_cast<T*>(a.T0));
   }
   HIP_TRY(h, hipGetLastError());
   {
@@ -3761,12 +3765,12 @@ int state_multi_factor(blr_handle* h, int memspace, int layout, int64_t B, int64
     if ((rc = single(BLR_MEM_DEVICE, a.X, a.Y, a.s, a.M, T_d, lp0, info_d))) return rc;  // (checked operands: a HIP failure)
   }
   // Step 2: the columns 1 .. S-1 of every regressor (and the copy of column 0's evidence to its place)
-  const void* const kern = state_cols_kernel_ptr(T(0), DOWN, global);
+  void (*const kern)(StateColsArgs<T>) = global ? state_cols_global_kernel<T, DOWN> : state_cols_kernel<T, DOWN>;
   if (!global) {
     const int64_t passes = std::max<int64_t>(1, (S - 1 + kStateColsPerPass - 1) / kStateColsPerPass);
     const size_t lds = state_cols_lds_bytes(sizeof(T), (int)D);
     if ((rc = set_lds_once(h, kern, lds))) return rc;
-    state_cols_kernel_launch(DOWN, false, dim3((unsigned)B, (unsigned)passes), lds, h->stream, a);
+    hipLaunchKernelGGL(kern, dim3((unsigned)B, (unsigned)passes), dim3(kThreads), lds, h->stream, a);
   } else {
     // correct, not fast: one workgroup per (column, regressor) reading T' from global memory; column 0's evidence is copied by the host
     const size_t lds = state_cols_global_lds_bytes((int)D);
@@ -3777,7 +3781,7 @@ int state_multi_factor(blr_handle* h, int memspace, int layout, int64_t B, int64
       g.X += b0 * strideX; g.Y += b0 * strideY; g.s += b0 * strides; g.M += b0 * strideM; g.Tf += b0 * strideT;
       g.diag0 += b0 * D; g.info += b0;
       if (g.logpdf) g.logpdf += b0 * stride_lp;
-      state_cols_kernel_launch(DOWN, true, dim3((unsigned)(S - 1), (unsigned)std::min<int64_t>(32768, B - b0)), lds, h->stream, g);
+      hipLaunchKernelGGL(kern, dim3((unsigned)(S - 1), (unsigned)std::min<int64_t>(32768, B - b0)), dim3(kThreads), lds, h->stream, g);
     }
   }
   HIP_TRY(h, hipGetLastError());

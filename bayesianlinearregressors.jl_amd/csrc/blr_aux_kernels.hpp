@@ -357,12 +357,7 @@ __device__ __forceinline__ double fixed_order_sum(const double* __restrict__ lp,
   }
   return tid == 0 ? part[0] : 0.0;
 }
-#ifndef BLR_NO_PLAIN_KERNELS  // (a plain kernel has one home, blr_abi.hip; blr_loo_multi.hip includes this header for fixed_order_sum)
-__global__ __launch_bounds__(kThreads) void logpdf_sum_kernel(const double* __restrict__ lp, int64_t B,
-                                                              double* __restrict__ total) {
-  const double t = fixed_order_sum(lp, B);
-  if (threadIdx.x == 0) *total = t;
-}
-#endif
+// (a plain kernel is declared here and defined once, in blr_abi.hip)
+__global__ __launch_bounds__(kThreads) void logpdf_sum_kernel(const double* __restrict__ lp, int64_t B, double* __restrict__ total);
 
 }  // namespace blr

@@ -21,11 +21,10 @@
 #pragma once
 #include "blr_aux_kernels.hpp"
 #include "blr_fused_small.hpp"
+#include "blr_marg_image.hpp"  // kPB, the panel / macro-tile edge
 #include "blr_panel.hpp"
 
 namespace blr {
-
-constexpr int kPB = 128;  // panel / macro-tile edge
 
 // Gram launch geometry (f32): k-steps per stage and workgroups per CU the kernel is compiled for
 #ifndef BLR_GRAM_KS_F32

@@ -106,15 +106,8 @@ __global__ __launch_bounds__(kThreads) void loo_finish_kernel(LooArgs<T> l, cons
 }
 
 // ---- loo_total[reg] = sum_n logpdf_n in a fixed order (no float atomics: the same bits at any B and position) -------------------
-// (a plain kernel has one home, blr_abi.hip: a second translation unit that wants the epilogue only defines BLR_NO_PLAIN_KERNELS)
-#ifndef BLR_NO_PLAIN_KERNELS
-__global__ __launch_bounds__(kThreads) void loo_total_kernel(const double* __restrict__ ll, int64_t stride_ll, int N,
-                                                             double* __restrict__ total, const int32_t* __restrict__ info, int reg0) {
-  const int64_t reg = reg0 + (int64_t)blockIdx.x;
-  if (info[reg] != 0) return;
-  const double t = fixed_order_sum(ll + reg * stride_ll, N);
-  if (threadIdx.x == 0) total[reg] = t;
-}
-#endif
+// (a plain kernel is declared here and defined once, in blr_abi.hip)
+__global__ __launch_bounds__(kThreads) void loo_total_kernel(const double* __restrict__ ll, int64_t stride_ll, int N, double* __restrict__ total,
+                                 const int32_t* __restrict__ info, int reg0);
 
 }  // namespace blr

@@ -54,7 +54,7 @@ template <typename T, int LAYOUT /* LAYOUT_COLVECS | LAYOUT_ROWVECS */>
 __global__ __launch_bounds__(kThreads, 2) void loo_cols_kernel(LooColsArgs<T> a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   using Mf = Mfma<T>;
-  using G = MargColsImg<T>;
+  using G = MargGemmCfg<T>;
   using acc4 = typename Mf::acc4;
   constexpr int W = kLooColsPerPass, TN = kMargTile, VEC = Mf::VEC;
   typedef T vecT __attribute__((ext_vector_type(Mf::VEC)));
@@ -220,16 +220,16 @@ __global__ __launch_bounds__(kThreads) void loo_cols_finish_kernel(LooColsArgs<T
   loo_count(ndeg, a.degenerate);
 }
 
-// ---- host side of the instantiations (blr_loo_multi.hip), used by blr_abi.hip ---------------------------------------------------------
-const void* loo_cols_kernel_ptr_f64(int layout);
-const void* loo_cols_kernel_ptr_f32(int layout);
-void loo_cols_kernel_launch_f64(int layout, dim3 grid, size_t lds, hipStream_t stream, const LooColsArgs<double>& a);
-void loo_cols_kernel_launch_f32(int layout, dim3 grid, size_t lds, hipStream_t stream, const LooColsArgs<float>& a);
-void loo_cols_finish_launch_f64(dim3 grid, hipStream_t stream, const LooColsArgs<double>& a, const double* mean, int64_t ldmn, int64_t stridemn,
-                                const double* var, int64_t ldw);
-void loo_cols_finish_launch_f32(dim3 grid, hipStream_t stream, const LooColsArgs<float>& a, const float* mean, int64_t ldmn, int64_t stridemn,
-                                const float* var, int64_t ldw);
-void loo_cols_total_launch(dim3 grid, hipStream_t stream, const double* ll, int64_t ld_ll, int64_t stride_ll, int N, double* total,
-                           int64_t stride_lt, const int32_t* info, int reg0);
+// ---- loo_total[reg][c] = sum_n logpdf[n, c] in a fixed order: one workgroup per (column, regressor) (defined in blr_loo_multi.hip) ------
+__global__ __launch_bounds__(kThreads) void loo_cols_total_kernel(const double* __restrict__ ll, int64_t ld_ll, int64_t stride_ll, int N, double* __restrict__ total,
+                                      int64_t stride_lt, const int32_t* __restrict__ info, int reg0);
+
+// the instantiations the library uses, defined in blr_loo_multi.hip
+extern template __global__ void loo_cols_kernel<double, LAYOUT_COLVECS>(LooColsArgs<double>);
+extern template __global__ void loo_cols_kernel<double, LAYOUT_ROWVECS>(LooColsArgs<double>);
+extern template __global__ void loo_cols_kernel<float, LAYOUT_COLVECS>(LooColsArgs<float>);
+extern template __global__ void loo_cols_kernel<float, LAYOUT_ROWVECS>(LooColsArgs<float>);
+extern template __global__ void loo_cols_finish_kernel<double>(LooColsArgs<double>, const double*, int64_t, int64_t, const double*, int64_t);
+extern template __global__ void loo_cols_finish_kernel<float>(LooColsArgs<float>, const float*, int64_t, int64_t, const float*, int64_t);
 
 }  // namespace blr

@@ -21,21 +21,13 @@
 // do not depend on S, on its pass or slot or on the other columns; those of var not on S or on whether the means are wanted.
 #pragma once
 #include "blr_common.hpp"
+#include "blr_marg_image.hpp"
 
 namespace blr {
 
 constexpr int kMargColsPerPass = 16;  // columns of M per pass: one 16-row A operand, resident in registers
 constexpr int kMargTile = 64;         // inputs per tile: one 16-input MFMA tile per wave
-constexpr int kMargMaxD = 128;
-
-// the image of L^-T (MargGemmCfg, blr_marginals.hpp; blr_abi.hip asserts that the two agree)
-template <typename T>
-struct MargColsImg {
-  static constexpr int VEC = Mfma<T>::VEC;
-  static constexpr int IMG_ELEMS = 4 * 36 * 64;
-  __host__ __device__ static constexpr int d_of(int m, int g) { return 4 * VEC * (m / VEC) + VEC * g + (m % VEC); }
-  __host__ __device__ static constexpr int frag0(int J) { return 2 * J * (J + 1); }  // first fragment of column block J
-};
+constexpr int kMargMaxD = kPB;        // the image of L^-T (MargGemmCfg, written by marg_image_kernel) covers one 128-block
 
 template <typename T>
 struct MargColsArgs {
@@ -70,7 +62,7 @@ template <typename T, int LAYOUT /* LAYOUT_COLVECS | LAYOUT_ROWVECS */>
 __global__ __launch_bounds__(kThreads, 2) void marginals_cols_kernel(MargColsArgs<T> a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   using Mf = Mfma<T>;
-  using G = MargColsImg<T>;
+  using G = MargGemmCfg<T>;
   using acc4 = typename Mf::acc4;
   constexpr int W = kMargColsPerPass, TN = kMargTile, VEC = Mf::VEC;
   typedef T vecT __attribute__((ext_vector_type(Mf::VEC)));
@@ -198,10 +190,10 @@ __global__ __launch_bounds__(kThreads, 2) void marginals_cols_kernel(MargColsArg
   }
 }
 
-// ---- host side of the instantiations (blr_marg_multi.hip), used by blr_abi.hip ----------------------------------------------------
-const void* marginals_cols_kernel_ptr_f64(int layout);
-const void* marginals_cols_kernel_ptr_f32(int layout);
-void marginals_cols_kernel_launch_f64(int layout, dim3 grid, size_t lds, hipStream_t stream, const MargColsArgs<double>& a);
-void marginals_cols_kernel_launch_f32(int layout, dim3 grid, size_t lds, hipStream_t stream, const MargColsArgs<float>& a);
+// the instantiations the library uses, defined in blr_marg_multi.hip
+extern template __global__ void marginals_cols_kernel<double, LAYOUT_COLVECS>(MargColsArgs<double>);
+extern template __global__ void marginals_cols_kernel<double, LAYOUT_ROWVECS>(MargColsArgs<double>);
+extern template __global__ void marginals_cols_kernel<float, LAYOUT_COLVECS>(MargColsArgs<float>);
+extern template __global__ void marginals_cols_kernel<float, LAYOUT_ROWVECS>(MargColsArgs<float>);
 
 }  // namespace blr

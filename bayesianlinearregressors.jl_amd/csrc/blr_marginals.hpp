@@ -17,23 +17,9 @@
 #pragma once
 #include "blr_large.hpp"
 #include "blr_loo.hpp"
+#include "blr_marg_image.hpp"
 
 namespace blr {
-
-template <typename T>
-struct MargGemmCfg {
-  static constexpr int VEC = Mfma<T>::VEC;             // consecutive d per 16-byte load = MFMAs fed by one load
-  static constexpr int NLOAD = kPB / (4 * VEC);        // loads per lane and tile: 16 (f64) / 8 (f32)
-  static constexpr int NFRAG = 4 * 36;                 // B fragments of the image: sum_J 4 (J + 1)
-  static constexpr int IMG_ELEMS = NFRAG * 64;
-  static constexpr int OFF_MW = IMG_ELEMS * (int)sizeof(T);
-  static constexpr int LDS_BYTES = OFF_MW + kPB * (int)sizeof(T);
-  // contraction index of MFMA m (of a column block), lane group g = lane >> 4:  one 16-byte load covers VEC consecutive d
-  __host__ __device__ static constexpr int d_of(int m, int g) { return 4 * VEC * (m / VEC) + VEC * g + (m % VEC); }
-  __host__ __device__ static constexpr int frag0(int J) { return 2 * J * (J + 1); }  // first fragment of column block J
-  // second image (gradient): groups of four fragments (Jc, J), J = Jc .. 7, in this order; first group of output block Jc
-  __host__ __device__ static constexpr int frag2_0(int Jc) { return 8 * Jc - Jc * (Jc - 1) / 2; }
-};
 
 // ---- M = L^-T in B-fragment order, two workgroups per regressor (blockIdx.y: rows 0..63 / 64..127 of M) ----------------------------
 template <typename T>

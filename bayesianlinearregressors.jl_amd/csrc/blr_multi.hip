@@ -1,32 +1,12 @@
-// multi_cols_kernel (blr_multi.hpp) instantiated in a translation unit of its own, so the code objects of the existing kernels stay
-// as they are: both element types, ColVecs and RowVecs.  Host side: blr_abi.hip (posterior_multi_batched).
-#include <hip/hip_runtime.h>
-
+// The instantiations of multi_cols_kernel (blr_multi.hpp): both element types, ColVecs and RowVecs.  Host side: blr_abi.hip
+// (posterior_multi_batched).
 #include "blr_multi.hpp"
 
 namespace blr {
-namespace {
 
-template <typename T>
-const void* ptr_of(int layout) {
-  return layout == LAYOUT_ROWVECS ? reinterpret_cast<const void*>(multi_cols_kernel<T, LAYOUT_ROWVECS>)
-                                  : reinterpret_cast<const void*>(multi_cols_kernel<T, LAYOUT_COLVECS>);
-}
-template <typename T>
-void launch_of(int layout, dim3 grid, size_t lds, hipStream_t stream, const MultiColsArgs<T>& a) {
-  if (layout == LAYOUT_ROWVECS) hipLaunchKernelGGL((multi_cols_kernel<T, LAYOUT_ROWVECS>), grid, dim3(kThreads), lds, stream, a);
-  else hipLaunchKernelGGL((multi_cols_kernel<T, LAYOUT_COLVECS>), grid, dim3(kThreads), lds, stream, a);
-}
-
-}  // namespace
-
-const void* multi_cols_kernel_ptr_f64(int layout) { return ptr_of<double>(layout); }
-const void* multi_cols_kernel_ptr_f32(int layout) { return ptr_of<float>(layout); }
-void multi_cols_kernel_launch_f64(int layout, dim3 grid, size_t lds, hipStream_t stream, const MultiColsArgs<double>& a) {
-  launch_of<double>(layout, grid, lds, stream, a);
-}
-void multi_cols_kernel_launch_f32(int layout, dim3 grid, size_t lds, hipStream_t stream, const MultiColsArgs<float>& a) {
-  launch_of<float>(layout, grid, lds, stream, a);
-}
+template __global__ void multi_cols_kernel<double, LAYOUT_COLVECS>(MultiColsArgs<double>);
+template __global__ void multi_cols_kernel<double, LAYOUT_ROWVECS>(MultiColsArgs<double>);
+template __global__ void multi_cols_kernel<float, LAYOUT_COLVECS>(MultiColsArgs<float>);
+template __global__ void multi_cols_kernel<float, LAYOUT_ROWVECS>(MultiColsArgs<float>);
 
 }  // namespace blr

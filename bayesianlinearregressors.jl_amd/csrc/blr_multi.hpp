@@ -307,10 +307,10 @@ __global__ __launch_bounds__(kThreads, 2) void multi_cols_kernel(MultiColsArgs<T
   }
 }
 
-// ---- host side of the instantiations (blr_multi.hip), used by blr_abi.hip ----------------------------------------------------------
-const void* multi_cols_kernel_ptr_f64(int layout);
-const void* multi_cols_kernel_ptr_f32(int layout);
-void multi_cols_kernel_launch_f64(int layout, dim3 grid, size_t lds, hipStream_t stream, const MultiColsArgs<double>& a);
-void multi_cols_kernel_launch_f32(int layout, dim3 grid, size_t lds, hipStream_t stream, const MultiColsArgs<float>& a);
+// the instantiations the library uses, defined in blr_multi.hip
+extern template __global__ void multi_cols_kernel<double, LAYOUT_COLVECS>(MultiColsArgs<double>);
+extern template __global__ void multi_cols_kernel<double, LAYOUT_ROWVECS>(MultiColsArgs<double>);
+extern template __global__ void multi_cols_kernel<float, LAYOUT_COLVECS>(MultiColsArgs<float>);
+extern template __global__ void multi_cols_kernel<float, LAYOUT_ROWVECS>(MultiColsArgs<float>);
 
 }  // namespace blr

@@ -442,13 +442,17 @@ __global__ __launch_bounds__(kThreads) void state_cols_global_kernel(StateColsAr
   }
 }
 
-// ---- host side of the instantiations (blr_state_cols.hip), used by blr_abi.hip -------------------------------------------------------
-const void* state_cols_kernel_ptr_f64(bool down, bool global);
-const void* state_cols_kernel_ptr_f32(bool down, bool global);
-void state_cols_kernel_launch_f64(bool down, bool global, dim3 grid, size_t lds, hipStream_t stream, const StateColsArgs<double>& a);
-void state_cols_kernel_launch_f32(bool down, bool global, dim3 grid, size_t lds, hipStream_t stream, const StateColsArgs<float>& a);
-void state_diag_kernel_launch_f64(hipStream_t stream, const double* Tf, int64_t ldt, int64_t strideT, int D, int64_t B, double* diag0);
-void state_diag_kernel_launch_f32(hipStream_t stream, const float* Tf, int64_t ldt, int64_t strideT, int D, int64_t B, float* diag0);
-void state_save_kernel_launch_f32(hipStream_t stream, const float* Tf, int64_t ldt, int64_t strideT, int D, int64_t B, float* T0w);
+// the instantiations the library uses, defined in blr_state_cols.hip (state_save_kernel: fp32 only)
+extern template __global__ void state_cols_kernel<double, false>(StateColsArgs<double>);
+extern template __global__ void state_cols_kernel<double, true>(StateColsArgs<double>);
+extern template __global__ void state_cols_kernel<float, false>(StateColsArgs<float>);
+extern template __global__ void state_cols_kernel<float, true>(StateColsArgs<float>);
+extern template __global__ void state_cols_global_kernel<double, false>(StateColsArgs<double>);
+extern template __global__ void state_cols_global_kernel<double, true>(StateColsArgs<double>);
+extern template __global__ void state_cols_global_kernel<float, false>(StateColsArgs<float>);
+extern template __global__ void state_cols_global_kernel<float, true>(StateColsArgs<float>);
+extern template __global__ void state_diag_kernel<double>(const double*, int64_t, int64_t, int, int64_t, double*);
+extern template __global__ void state_diag_kernel<float>(const float*, int64_t, int64_t, int, int64_t, float*);
+extern template __global__ void state_save_kernel<float>(const float*, int64_t, int64_t, int, int64_t, float*);
 
 }  // namespace blr

@@ -245,6 +245,38 @@ def test_bits_repeat_batch_position_and_shared_inputs(B):
         assert _same([a[k] for a in got[:4]], [a[0] for a in one[:4]])
 
 
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+@pytest.mark.parametrize("layout", ["col", "row"])
+@pytest.mark.parametrize("noise", ["isotropic", "diagonal"])
+def test_a_workgroup_that_walks_several_tiles(B, noise, layout, dtype):
+    """600 regressors over the same inputs, targets and state (all strides 0), D = 20, N = 130 (two full tiles and a tail of two),
+    S = 17 (two passes): regressors >= 2 x CUs, so one workgroup per regressor commits a tile and prefetches the next while it
+    multiplies, three times over.  At B = 1 every workgroup takes one tile: the bits must not depend on which of the two it was.
+    The B = 1 outputs are held to the oracle at the bounds of test_against_nxn_formulas / test_fp32_against_the_fp64_formulas."""
+    Bn, D, N, S = 600, 20, 130, 17
+    M0, U, X, s, Y, M, T = _multi_state(B, D, N, S, noise, dtype=dtype)
+    lay, Xl, ldx = _x_of(B, X, layout)
+    one = _raw(B, dtype, lay, Xl, ldx, Y, s, M, T)
+    lm, lv, ll, tot, info = one
+    assert info[0] == 0
+    U64, X64, M64, Y64, s64 = (np.asarray(a, dtype=np.float64) for a in (U, X, M0, Y, s))
+    m_o, v_o, lp_o = _nxn_cols(M64, U64.T @ U64, X64, s64, Y64)
+    if dtype == np.float64:
+        np.testing.assert_allclose(lm[0], m_o, rtol=1e-9, atol=1e-12)
+        np.testing.assert_allclose(lv[0], v_o, rtol=1e-9)
+        np.testing.assert_allclose(ll[0], lp_o, rtol=1e-9)
+    else:
+        np.testing.assert_allclose(ll[0], lp_o, rtol=1e-3, atol=1e-3)
+        np.testing.assert_allclose(lm[0], m_o, rtol=1e-3, atol=1e-3)
+        np.testing.assert_allclose(lv[0], v_o, rtol=1e-3)
+    for c in range(S):
+        assert tot[0, c] == pytest.approx(math.fsum(ll[0][:, c]), rel=1e-12)
+    got = _raw(B, dtype, lay, Xl, ldx, Y, s, M, T, Bn=Bn)
+    assert not got[4].any()
+    for a, a1 in zip(got[:4], one[:4]):
+        np.testing.assert_array_equal(a, np.broadcast_to(a1[0], a.shape))
+
+
 @pytest.mark.parametrize("layout", ["col", "row"])
 def test_bits_of_a_column_do_not_depend_on_the_others(B, layout):
     D, N, S = 100, 130, 33

@@ -239,6 +239,32 @@ def test_bit_properties(h, dtype):
 
 
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
+@pytest.mark.parametrize("prior", ["factor", "diag"])
+@pytest.mark.parametrize("xkind", ["colodd", "row"])
+def test_a_workgroup_that_walks_several_tiles(h, xkind, prior, dtype):
+    """600 regressors that share every input (all strides 0), D = 20, N = 130 (two full tiles and a tail of two), S = 17 (two passes):
+    regressors x passes >= 2 x CUs, so one workgroup per (regressor, pass) commits a tile and prefetches the next while it
+    multiplies, three times over.  At B = 1 every workgroup takes one tile: the bits must not depend on which of the two it was."""
+    Bn, D, N, S = 600, 20, 130, 17
+    q = _data(D, N, dtype, xkind, prior, "diag")
+    cols = list(range(S))
+    m1, v1, info1 = _call(h, q, cols, regs=[0])
+    assert info1[0] == 0
+    _check(q, cols, m1, v1, regs=[0])
+    M, ldm, _ = _pack_M(q, cols, [0])
+    mo = np.full((Bn, N * S), np.nan, dtype=dtype)
+    vo = np.full((Bn, N), np.nan, dtype=dtype)
+    info = np.full(Bn, -7, dtype=np.int32)
+    rc = h.marginals_multi_batched(dtype, _abi.MEM_HOST, q["layout"], Bn, D, N, S, np.ascontiguousarray(q["X"][0]), q["ldx"], 0, q["noise_kind"],
+                                   np.ascontiguousarray(q["s"][0]), 0, q["prior_kind"], M, ldm, 0, np.ascontiguousarray(q["Lw"][0]), q["ldl"], 0,
+                                   mo, N, N * S, vo, N, info)
+    assert rc == 0 and (info == 0).all()
+    m = np.swapaxes(mo.reshape(Bn, S, N), 1, 2)
+    np.testing.assert_array_equal(m, np.broadcast_to(m1[0], m.shape))
+    np.testing.assert_array_equal(vo, np.broadcast_to(v1[0], vo.shape))
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
 def test_a_prior_that_is_not_positive_definite(h, dtype):
     q = _data(33, 70, dtype, "col16", "dense", "diag")
     D, cols = q["D"], list(range(3))
