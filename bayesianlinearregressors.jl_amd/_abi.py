@@ -245,7 +245,8 @@ class Handle:
         self.check(self.lib.blr_release_workspace(self._h))
 
     def set_option(self, key, value=None):
-        """Run-time switch of this handle (include/blr_mi355x.h blr_set_option); value None = the built-in default."""
+        """Run-time switch of this handle (include/blr_mi355x.h blr_set_option); value None = the built-in default.
+        MAX_CHUNK = 1..65535 (tests) caps the regressors per chunk / slice of every batched entry point."""
         self.check(self.lib.blr_set_option(self._h, str(key).encode(), None if value is None else str(value).encode()))
 
     def last_route(self):
@@ -253,8 +254,8 @@ class Handle:
         return self.lib.blr_last_route(self._h).decode()
 
     def get_stat(self, key):
-        """Counter of this handle: "i8_regressors", "i8_handed_back", "planes_redone", "loo_degenerate", "workspace_bytes"
-        (blr_get_stat)."""
+        """Counter of this handle: "i8_regressors", "i8_handed_back", "planes_redone", "loo_degenerate", "workspace_bytes",
+        "last_chunks" (chunks / slices of regressors of the most recent call: option MAX_CHUNK caps their size) (blr_get_stat)."""
         v = _i64()
         self.check(self.lib.blr_get_stat(self._h, str(key).encode(), C.byref(v)))
         return int(v.value)

@@ -262,7 +262,7 @@ int launch_fused_i8(blr_handle* h, const PosteriorArgs<double>& a) {
   // diagonal noise: y / sqrt(s), 1 / sqrt(s), sum log s and a validity flag per regressor, once per call, in a side buffer of the
   // handle (16 bytes per observation: slices of at most 1 GiB)
   const int64_t per_reg = 2 * (int64_t)a.N * (int64_t)sizeof(double);
-  const int grid = (int)std::min<int64_t>(a.B, diag ? std::max<int64_t>(1, ((int64_t)1 << 30) / per_reg) : (1 << 20));
+  const int grid = (int)h->cap_chunk(std::min<int64_t>(a.B, diag ? std::max<int64_t>(1, ((int64_t)1 << 30) / per_reg) : (1 << 20)));
   double *yt = nullptr, *rw = nullptr, *ld = nullptr, *rmx = nullptr;
   int32_t* bad = nullptr;
   // dense prior: logdet Lw and the status of its Cholesky per prior, from i8_prior_logdet_kernel (ONE prior when the batch shares it)
@@ -304,6 +304,7 @@ int launch_fused_i8(blr_handle* h, const PosteriorArgs<double>& a) {
   }
   int64_t b0 = 0;
   int prev_n = 0;
+  h->last_chunks = 0;
   while (b0 < a.B) {
     PosteriorArgs<double> s = a;
     int64_t want = std::min<int64_t>(grid, a.B - b0);
@@ -344,6 +345,7 @@ int launch_fused_i8(blr_handle* h, const PosteriorArgs<double>& a) {
     h->i8_attempted += (unsigned long long)nb;
     prev_n = nb;
     b0 += nb;
+    ++h->last_chunks;
   }
   h->route = !alt ? "fused_i8_kernel" : (groups == 7 ? "fused_i8_kernel (7 digit groups)" : "fused_i8_kernel (6 digit groups)");
   h->route_i8_B = a.B;
@@ -816,6 +818,7 @@ int posterior_check(blr_handle* h, int memspace, int layout, int64_t B, int64_t 
                       int64_t strideLw, T* mw_post, int64_t stride_mwpost, T* T_post, int64_t ldt, int64_t strideT,
                       T* Lw_post, int64_t ldlp, int64_t strideLp, double* logpdf, int32_t* info) {
   if (!h) return -1;
+  h->last_chunks = 1;  // (a route with a chunk loop counts its own)
   h->err.clear();
   if (memspace != BLR_MEM_HOST && memspace != BLR_MEM_DEVICE) return bad_arg(h, 2, "memspace");
   if (layout != BLR_LAYOUT_COLVECS && layout != BLR_LAYOUT_ROWVECS) return bad_arg(h, 3, "unknown layout (reference :26-31)");
@@ -974,6 +977,8 @@ int marginals_large_group(blr_handle* h, int layout, int64_t B, int64_t D, int64
   const size_t mat = (((size_t)DP * DP * sizeof(T)) + 255) & ~(size_t)255;
   int64_t chunk = std::min<int64_t>(B, std::min<int64_t>(65535, ((int64_t)256 << 20) / ((int64_t)NC * MG::IMG_ELEMS * (int64_t)sizeof(T))));
   if (!u_given) chunk = std::min<int64_t>(chunk, std::min<int64_t>(kChainBatchMax, std::max<int64_t>(1, ((int64_t)1 << 30) / (int64_t)(2 * mat))));
+  chunk = h->cap_chunk(chunk);
+  h->count_chunks(B, chunk);
   if ((rc = h->aux.reserve(h, (size_t)chunk * NC * MG::IMG_ELEMS * sizeof(T)))) return rc;
   if (!u_given && (rc = h->ws.reserve(h, (size_t)chunk * 2 * mat + 256, blr_handle::kWsFloor))) return rc;
   T* const img = reinterpret_cast<T*>(h->aux.p);
@@ -1206,6 +1211,7 @@ int marginals_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_
                       int64_t stridemw, const T* Lw, int64_t ldl, int64_t strideLw, T* mean, int64_t stridemean, T* var,
                       int64_t stridevar, int32_t* info) {
   if (!h) return -1;
+  h->last_chunks = 1;  // (a route with a chunk loop counts its own)
   h->err.clear();
   if (memspace != BLR_MEM_HOST && memspace != BLR_MEM_DEVICE) return bad_arg(h, 2, "memspace");
   if (layout != BLR_LAYOUT_COLVECS && layout != BLR_LAYOUT_ROWVECS) return bad_arg(h, 3, "unknown layout (reference :26-31)");
@@ -1281,7 +1287,8 @@ int marginals_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_
   else HIP_TRY(h, hipMemsetAsync(info_out_dev, 0, (size_t)B * sizeof(int32_t), h->stream));
   using MP = MargProduct<T, MarginalArgs<T>>;
   if (var && kind == BLR_PRIOR_UPPER_FACTOR && MP::takes(h, layout, D, N, a.X, ldx, strideX)) {
-    const int64_t chunk = std::min<int64_t>(std::min<int64_t>(B, 65535), MP::kMaxChunk);
+    const int64_t chunk = h->cap_chunk(std::min<int64_t>(std::min<int64_t>(B, 65535), MP::kMaxChunk));
+    h->count_chunks(B, chunk);
     if ((rc = MP::prepare(h, layout, chunk))) return rc;
     for (int64_t b0 = 0; b0 < B; b0 += chunk) MP::launch(h, a, a.U, a.ldu, a.strideU, a.info, b0, std::min<int64_t>(chunk, B - b0));
   } else {
@@ -1297,9 +1304,11 @@ int marginals_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_
     const int64_t ntiles = (N + TC::RB - 1) / TC::RB;
     const int64_t slots = use_factor ? 512 : 1024;
     const int64_t per_reg = std::max<int64_t>(1, std::min<int64_t>(ntiles, (slots + B - 1) / B));
-    for (int64_t b0 = 0; b0 < B; b0 += 65535) {  // grid.y <= 65535
+    const int64_t chunk = h->cap_chunk(65535);  // grid.y <= 65535
+    h->count_chunks(B, chunk);
+    for (int64_t b0 = 0; b0 < B; b0 += chunk) {
       a.reg0 = (int)b0;
-      dim3 grid((unsigned)per_reg, (unsigned)std::min<int64_t>(65535, B - b0));
+      dim3 grid((unsigned)per_reg, (unsigned)std::min<int64_t>(chunk, B - b0));
       hipLaunchKernelGGL(kern, grid, dim3(kThreads), lds, h->stream, a);
     }
   }
@@ -1312,6 +1321,7 @@ template <typename T>
 int gram_stats(blr_handle* h, int layout, int64_t D64, int64_t N64, const T* X, int64_t ldx, const T* y, int noise_kind,
                const T* s, const T* mw, T* stats, int64_t lds, double* scal) {
   if (!h) return -1;
+  h->last_chunks = 1;  // (a route with a chunk loop counts its own)
   h->err.clear();
   if (layout != BLR_LAYOUT_COLVECS && layout != BLR_LAYOUT_ROWVECS) return bad_arg(h, 2, "unknown layout (reference :26-31)");
   if (D64 < 1 || D64 > kMaxLargeD) return bad_arg(h, 3, "D out of range for this build (1..8192)");
@@ -1392,6 +1402,7 @@ int posterior_from_stats(blr_handle* h, int64_t D64, int64_t N_total, T* stats, 
                          const T* mw, const T* Lw, int64_t ldl, T* mw_post, T* T_post, int64_t ldt, T* Lw_post, int64_t ldlp,
                          double* logpdf, int32_t* info) {
   if (!h) return -1;
+  h->last_chunks = 1;  // (a route with a chunk loop counts its own)
   h->err.clear();
   if (D64 < 1 || D64 > kMaxLargeD) return bad_arg(h, 2, "D out of range for this build (1..8192)");
   if (N_total < 0 || N_total > ((int64_t)1 << 40)) return bad_arg(h, 3, "N_total out of range");
@@ -1548,6 +1559,7 @@ int logpdf_grad_batched(blr_handle* h, int memspace, int layout, int64_t B, int6
                         int64_t strideds, T* dmw, int64_t stridedmw, T* mw_post, int64_t stride_mwpost, T* Ainv,
                         int64_t ldai, int64_t strideAi, int32_t* info) {
   if (!h) return -1;
+  h->last_chunks = 1;  // (a route with a chunk loop counts its own)
   h->err.clear();
   if (memspace != BLR_MEM_HOST && memspace != BLR_MEM_DEVICE) return bad_arg(h, 2, "memspace");
   if (layout != BLR_LAYOUT_COLVECS && layout != BLR_LAYOUT_ROWVECS) return bad_arg(h, 3, "unknown layout (reference :26-31)");
@@ -1697,9 +1709,11 @@ int logpdf_grad_batched(blr_handle* h, int memspace, int layout, int64_t B, int6
     auto kern = logpdf_grad_kernel<T>;
     const int lds = TC::LDS_BYTES + (kPB + 3 * TC::RB) * (int)sizeof(T);
     if (const int rc_lds = set_lds_once(h, kern, (size_t)(lds))) return rc_lds;
-    for (int64_t b0 = 0; b0 < B; b0 += 65535) {  // grid.y <= 65535
+    const int64_t chunk = h->cap_chunk(65535);  // grid.y <= 65535
+    h->count_chunks(B, chunk);
+    for (int64_t b0 = 0; b0 < B; b0 += chunk) {
       g.reg0 = (int)b0;
-      hipLaunchKernelGGL(kern, dim3((unsigned)per_reg, (unsigned)std::min<int64_t>(65535, B - b0)), dim3(kThreads), lds, h->stream, g);
+      hipLaunchKernelGGL(kern, dim3((unsigned)per_reg, (unsigned)std::min<int64_t>(chunk, B - b0)), dim3(kThreads), lds, h->stream, g);
     }
     if (dmw_d)
       hipLaunchKernelGGL(grad_reduce_kernel<T>, dim3((unsigned)B), dim3(kPB), 0, h->stream, (const double*)part, (int)per_reg,
@@ -1715,6 +1729,7 @@ int logpdf_multi(blr_handle* h, int memspace, int layout, int64_t D, int64_t N, 
                  int64_t ldY, int noise_kind, const T* s, int prior_kind, const T* mw, const T* Lw, int64_t ldl, double* logpdf,
                  T* mw_post, int64_t ldmp, int32_t* info) {
   if (!h) return -1;
+  h->last_chunks = 1;  // (a route with a chunk loop counts its own)
   h->err.clear();
   if (memspace != BLR_MEM_HOST && memspace != BLR_MEM_DEVICE) return bad_arg(h, 2, "memspace");
   if (layout != BLR_LAYOUT_COLVECS && layout != BLR_LAYOUT_ROWVECS) return bad_arg(h, 3, "unknown layout (reference :26-31)");
@@ -2002,6 +2017,7 @@ template <typename T>
 int sample_weights(blr_handle* h, int memspace, int64_t D, int64_t S, int prior_kind, const T* mw, const T* Lw,
                    int64_t ldl, const T* Z, int64_t ldz, T* W, int64_t ldw) {
   if (!h) return -1;
+  h->last_chunks = 1;  // (a route with a chunk loop counts its own)
   h->err.clear();
   if (memspace != BLR_MEM_HOST && memspace != BLR_MEM_DEVICE) return bad_arg(h, 2, "memspace");
   if (D < 1 || D > kMaxLargeD) return bad_arg(h, 3, "D out of range for this build (1..8192)");
@@ -2046,6 +2062,7 @@ template <typename T>
 int apply_weights(blr_handle* h, int memspace, int layout, int64_t D, int64_t N, int64_t S, const T* X, int64_t ldx, const T* W,
                   int64_t ldw, T* Y, int64_t ldy) {
   if (!h) return -1;
+  h->last_chunks = 1;  // (a route with a chunk loop counts its own)
   h->err.clear();
   if (memspace != BLR_MEM_HOST && memspace != BLR_MEM_DEVICE) return bad_arg(h, 2, "memspace");
   if (layout != BLR_LAYOUT_COLVECS && layout != BLR_LAYOUT_ROWVECS) return bad_arg(h, 3, "unknown layout (reference :26-31)");
@@ -2078,6 +2095,7 @@ int rand_impl(blr_handle* h, int memspace, int layout, int64_t D, int64_t N, int
               int noise_kind, const T* s, int prior_kind, const T* mw, const T* Lw, int64_t ldl, const T* Z1,
               int64_t ldz1, const T* Z2, int64_t ldz2, T* Y, int64_t ldy) {
   if (!h) return -1;
+  h->last_chunks = 1;  // (a route with a chunk loop counts its own)
   h->err.clear();
   if (memspace != BLR_MEM_HOST && memspace != BLR_MEM_DEVICE) return bad_arg(h, 2, "memspace");
   if (layout != BLR_LAYOUT_COLVECS && layout != BLR_LAYOUT_ROWVECS) return bad_arg(h, 3, "unknown layout (reference :26-31)");
@@ -2129,6 +2147,7 @@ int rand_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, 
                  const T* Lw, int64_t ldl, int64_t strideLw, const T* Z1, int64_t ldz1, int64_t strideZ1, const T* Z2, int64_t ldz2,
                  int64_t strideZ2, T* W, int64_t ldw, int64_t strideW, T* Y, int64_t ldy, int64_t strideY, int32_t* info) {
   if (!h) return -1;
+  h->last_chunks = 1;  // (a route with a chunk loop counts its own)
   h->err.clear();
   if (memspace != BLR_MEM_HOST && memspace != BLR_MEM_DEVICE) return bad_arg(h, 2, "memspace");
   if (layout != BLR_LAYOUT_COLVECS && layout != BLR_LAYOUT_ROWVECS) return bad_arg(h, 3, "unknown layout (reference :26-31)");
@@ -2250,7 +2269,8 @@ int rand_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, 
   hipLaunchKernelGGL(solve, dim3(blocks), dim3(kThreads), 0, h->stream, a);
   HIP_TRY(h, hipGetLastError());
   if (proj && !fuse) {
-    const int64_t per_launch = std::max<int64_t>(1, ((int64_t)1 << 24) / ntn);
+    const int64_t per_launch = h->cap_chunk(std::max<int64_t>(1, ((int64_t)1 << 24) / ntn));
+    h->count_chunks(B, per_launch);
     for (int64_t b0 = 0; b0 < B; b0 += per_launch) {
       const int64_t nreg = std::min<int64_t>(per_launch, B - b0);
       const dim3 grid((unsigned)(nreg * ntn), (unsigned)nts);
@@ -2269,6 +2289,7 @@ template <typename T>
 int rff_features(blr_handle* h, int memspace, int64_t Din, int64_t D, int64_t N, const T* Xin, int64_t ldxin,
                  const T* Omega, int64_t ldo, const T* phase, T scale, T* Phi, int64_t ldphi) {
   if (!h) return -1;
+  h->last_chunks = 1;  // (a route with a chunk loop counts its own)
   h->err.clear();
   if (memspace != BLR_MEM_HOST && memspace != BLR_MEM_DEVICE) return bad_arg(h, 2, "memspace");
   if (Din < 1) return bad_arg(h, 3, "Din < 1");
@@ -2305,6 +2326,7 @@ int posterior_rff(blr_handle* h, int memspace, int64_t Din, int64_t D, int64_t N
                   int prior_kind, const T* mw, const T* Lw, int64_t ldl, T* mw_post, T* T_post, int64_t ldt, T* Lw_post,
                   int64_t ldlp, double* logpdf, int32_t* info) {
   if (!h) return -1;
+  h->last_chunks = 1;  // (a route with a chunk loop counts its own)
   h->err.clear();
   if (memspace != BLR_MEM_HOST && memspace != BLR_MEM_DEVICE) return bad_arg(h, 2, "memspace");
   if (Din < 1) return bad_arg(h, 3, "Din < 1");
@@ -2402,6 +2424,7 @@ int posterior_dense_noise(blr_handle* h, int memspace, int layout, int64_t D64, 
                           const T* Sy, int64_t ldsy, int prior_kind, const T* mw, const T* Lw, int64_t ldl, T* mw_post, T* T_post,
                           int64_t ldt, T* Lw_post, int64_t ldlp, double* logpdf, int32_t* info) {
   if (!h) return -1;
+  h->last_chunks = 1;  // (a route with a chunk loop counts its own)
   h->err.clear();
   if (memspace != BLR_MEM_HOST && memspace != BLR_MEM_DEVICE) return bad_arg(h, 2, "memspace");
   if (layout != BLR_LAYOUT_COLVECS && layout != BLR_LAYOUT_ROWVECS) return bad_arg(h, 3, "unknown layout (reference :26-31)");
@@ -2511,6 +2534,7 @@ template <typename T>
 int mean_and_cov(blr_handle* h, int memspace, int layout, int64_t D64, int64_t N64, const T* X, int64_t ldx, int noise_kind, const T* s,
                  int64_t lds, int prior_kind, const T* mw, const T* Lw, int64_t ldl, T* mean, T* C, int64_t ldc, int32_t* info) {
   if (!h) return -1;
+  h->last_chunks = 1;  // (a route with a chunk loop counts its own)
   h->err.clear();
   if (memspace != BLR_MEM_HOST && memspace != BLR_MEM_DEVICE) return bad_arg(h, 2, "memspace");
   if (layout != BLR_LAYOUT_COLVECS && layout != BLR_LAYOUT_ROWVECS) return bad_arg(h, 3, "unknown layout (reference :26-31)");
@@ -2589,6 +2613,7 @@ int rand_dense_noise(blr_handle* h, int memspace, int layout, int64_t D, int64_t
                      int64_t ldsy, int prior_kind, const T* mw, const T* Lw, int64_t ldl, const T* Z1, int64_t ldz1, const T* Z2,
                      int64_t ldz2, T* Y, int64_t ldy) {
   if (!h) return -1;
+  h->last_chunks = 1;  // (a route with a chunk loop counts its own)
   h->err.clear();
   if (N < 1 || N > kMaxDenseN) return bad_arg(h, 5, "N out of range for a dense noise covariance (1..16384)");
   if (!Sy) return bad_arg(h, 9, "Sy is NULL");
@@ -2680,6 +2705,7 @@ int update_factor(blr_handle* h, int memspace, int layout, int64_t B, int64_t D,
                   int64_t strideX, const T* y, int64_t stridey, int noise_kind, const T* s, int64_t strides, T* mw,
                   int64_t stridemw, T* Tf, int64_t ldt, int64_t strideT, double* logpdf, int32_t* info) {
   if (!h) return -1;
+  h->last_chunks = 1;  // (a route with a chunk loop counts its own)
   h->err.clear();
   // Route (measured, tools/update_bench.py): a sweep costs ~40 us per observation at D = 128 (a serial chain
   // of D rotations), the in-place re-factorisation ~90 us per CALL whatever k is (45 us at D = 64, where batches run on the
@@ -2735,7 +2761,8 @@ int downdate_launch(blr_handle* h, const SweepArgs<T>& a0, int64_t B) {
   // global route: chunks of regressors, each with a row-major copy of its factor and the per-observation vectors
   const size_t item = sizeof(T), vec = ((size_t)D * item + 255) & ~(size_t)255, mat = ((size_t)D * D * item + 255) & ~(size_t)255;
   const size_t per = mat + 3 * vec + 4 * sizeof(double) + sizeof(int);
-  const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(B, (int64_t)(kDowndateWorkspace / per)));
+  const int64_t chunk = h->cap_chunk(std::max<int64_t>(1, std::min<int64_t>(B, (int64_t)(kDowndateWorkspace / per))));
+  h->count_chunks(B, chunk);
   const size_t off_v = (size_t)chunk * mat, off_sc = off_v + 3 * (size_t)chunk * vec, off_st = off_sc + (size_t)chunk * 4 * sizeof(double);
   int rc = h->ws.reserve(h, off_st + (size_t)chunk * sizeof(int) + 256, blr_handle::kWsFloor);
   if (rc) return rc;
@@ -2778,6 +2805,7 @@ int downdate_factor(blr_handle* h, int memspace, int layout, int64_t B, int64_t 
                     int64_t strideX, const T* y, int64_t stridey, int noise_kind, const T* s, int64_t strides, T* mw,
                     int64_t stridemw, T* Tf, int64_t ldt, int64_t strideT, double* logpdf, int32_t* info) {
   if (!h) return -1;
+  h->last_chunks = 1;  // (a route with a chunk loop counts its own)
   h->err.clear();
   if (memspace != BLR_MEM_HOST && memspace != BLR_MEM_DEVICE) return bad_arg(h, 2, "memspace");
   if (layout != BLR_LAYOUT_COLVECS && layout != BLR_LAYOUT_ROWVECS) return bad_arg(h, 3, "unknown layout (reference :26-31)");
@@ -2807,8 +2835,9 @@ int loo_launch(blr_handle* h, int layout, int64_t B, int64_t D, int64_t N, const
   if ((rc = ensure_stats(h))) return rc;
   l.degenerate = h->stats_dev + 3;
   int32_t* const info = const_cast<int32_t*>(l.info);
-  for (int64_t b0 = 0; b0 < B; b0 += 65535)
-    hipLaunchKernelGGL(loo_check_kernel<T>, dim3((unsigned)std::min<int64_t>(65535, B - b0)), dim3(kThreads), 0, h->stream, Tf + b0 * strideT,
+  const int64_t ychunk = h->cap_chunk(65535);  // grid.x / grid.y <= 65535: the check and the empty totals
+  for (int64_t b0 = 0; b0 < B; b0 += ychunk)
+    hipLaunchKernelGGL(loo_check_kernel<T>, dim3((unsigned)std::min<int64_t>(ychunk, B - b0)), dim3(kThreads), 0, h->stream, Tf + b0 * strideT,
                        ldt, strideT, (int)D, l.s + b0 * l.strides, l.strides, l.noise_kind, (int)N, info + b0);
   HIP_TRY(h, hipGetLastError());
   // the route follows from the shape, as the marginals' does: the fused product stream at D = 128
@@ -2818,6 +2847,7 @@ int loo_launch(blr_handle* h, int layout, int64_t B, int64_t D, int64_t N, const
   const size_t per = (fused ? 0 : 2 * row) + (ll_ws ? row_ll : 0) + sizeof(int32_t);
   int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(B, 65535), (int64_t)(kLooWorkspace / per)));
   if (fused) chunk = std::min<int64_t>(chunk, MP::kMaxChunk);
+  chunk = h->cap_chunk(chunk);
   const size_t off_var = (size_t)chunk * row, off_ll = fused ? 0 : 2 * (size_t)chunk * row;
   const size_t off_zero = off_ll + (ll_ws ? (size_t)chunk * row_ll : 0), off_inf = off_zero + 256;
   if (N > 0 && (rc = h->loo_ws.reserve(h, off_inf + (size_t)chunk * sizeof(int32_t) + 256))) return rc;
@@ -2858,9 +2888,10 @@ int loo_launch(blr_handle* h, int layout, int64_t B, int64_t D, int64_t N, const
                          total, l.info, (int)b0);
     HIP_TRY(h, hipGetLastError());
   }
+  h->count_chunks(B, N > 0 ? chunk : ychunk);  // (after the loop: the composed route's marginals count their own)
   if (N == 0 && total) {  // an empty sum, for the regressors whose state passed the check
-    for (int64_t b0 = 0; b0 < B; b0 += 65535)
-      hipLaunchKernelGGL(loo_total_kernel, dim3((unsigned)std::min<int64_t>(65535, B - b0)), dim3(kThreads), 0, h->stream,
+    for (int64_t b0 = 0; b0 < B; b0 += ychunk)
+      hipLaunchKernelGGL(loo_total_kernel, dim3((unsigned)std::min<int64_t>(ychunk, B - b0)), dim3(kThreads), 0, h->stream,
                          (const double*)nullptr, (int64_t)0, 0, total, l.info, (int)b0);
     HIP_TRY(h, hipGetLastError());
   }
@@ -2898,6 +2929,7 @@ int loo_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, i
   if (loo_logpdf && B > 1 && stride_ll < N) return bad_arg(h, 25, "stride_ll < N");
   if (!info) return bad_arg(h, 27, "info is NULL");
   if (!h) return -1;
+  h->last_chunks = 1;  // (a route with a chunk loop counts its own)
   if (B == 0) return 0;
   HIP_TRY(h, hipSetDevice(h->device));
   LooArgs<T> l{};
@@ -2998,8 +3030,9 @@ int grid_large(blr_handle* h, GridArgs<T> a) {
   a.best = reinterpret_cast<int64_t*>(ws + o_best);
   const int64_t ldl_g = a.prior_kind == BLR_PRIOR_DENSE ? D : 0;
   for (int g = 0; g < a.G; ++g) {
-    for (int64_t b0 = 0; b0 < B; b0 += 65535) {
-      const int64_t nb = std::min<int64_t>(65535, B - b0);
+    const int64_t chunk = h->cap_chunk(65535);  // grid.y <= 65535
+    for (int64_t b0 = 0; b0 < B; b0 += chunk) {
+      const int64_t nb = std::min<int64_t>(chunk, B - b0);
       hipLaunchKernelGGL(grid_scale_kernel<T>, dim3(64, (unsigned)nb), dim3(kThreads), 0, h->stream, a, b0, g, s_g + b0 * s_one, s_one,
                          Lw_g + b0 * lw_one, lw_one);
     }
@@ -3014,6 +3047,7 @@ int grid_large(blr_handle* h, GridArgs<T> a) {
     hipLaunchKernelGGL(grid_scatter_kernel, dim3((unsigned)((B + kThreads - 1) / kThreads)), dim3(kThreads), 0, h->stream,
                        (const double*)lp_g, (const int32_t*)in_g, (int)B, g, a.logpdf, a.stride_lp, a.info, a.stride_info);
   }
+  h->count_chunks(B, h->cap_chunk(65535));  // (the scaling launches; the nested updates counted their own)
   hipLaunchKernelGGL(grid_argmax_kernel, dim3((unsigned)((B + kThreads - 1) / kThreads)), dim3(kThreads), 0, h->stream,
                      (const double*)a.logpdf, a.stride_lp, a.G, a.B, a.best, a.best_out);
   HIP_TRY(h, hipGetLastError());
@@ -3097,6 +3131,7 @@ int logpdf_grid(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, i
   // one workgroup of 256 threads per (regressor, setting) / (regressor, column block): a launch takes fewer than 2^32 threads
   if (B * std::max<int64_t>(G, S) >= ((int64_t)1 << 24)) return bad_arg(h, 21, "B * max(G, 8) too large (< 2^24)");
   if (!h) return -1;
+  h->last_chunks = 1;  // (a route with a chunk loop counts its own)
   if (B == 0 || G == 0) return 0;
   HIP_TRY(h, hipSetDevice(h->device));
   GridArgs<T> a{};
@@ -3209,6 +3244,7 @@ int posterior_ragged(blr_handle* h, int memspace, int layout, int64_t B, int64_t
   if (B > 0 && !info) return bad_arg(h, 28, "info is NULL");
   if (B == 0) return 0;
   if (!h) return -1;
+  h->last_chunks = 1;  // (a route with a chunk loop counts its own)
   HIP_TRY(h, hipSetDevice(h->device));
   const bool diag = noise_kind == BLR_NOISE_DIAGONAL;
   RaggedArgs<T> r{};
@@ -3302,6 +3338,7 @@ int posterior_multi_batched(blr_handle* h, int memspace, int layout, int64_t B, 
   if (logpdf && B > 1 && stride_lp < S) return bad_arg(h, 33, "stride_lp < S");
   if (!info) return bad_arg(h, 34, "info is NULL");
   if (!h) return -1;
+  h->last_chunks = 1;  // (a route with a chunk loop counts its own)
   HIP_TRY(h, hipSetDevice(h->device));
 
   PosteriorArgs<T> a{};
@@ -3433,6 +3470,7 @@ int marginals_multi_batched(blr_handle* h, int memspace, int layout, int64_t B, 
   if (var && B > 1 && stridevar < N) return bad_arg(h, 25, "stridevar < N");
   if (!info) return bad_arg(h, 26, "info is NULL");
   if (!h) return -1;
+  h->last_chunks = 1;  // (a route with a chunk loop counts its own)
   HIP_TRY(h, hipSetDevice(h->device));
 
   CallIO io(h, memspace);
@@ -3490,7 +3528,8 @@ int marginals_multi_batched(blr_handle* h, int memspace, int layout, int64_t B, 
   if (chol_info) HIP_TRY(h, hipMemcpyAsync(info_d, chol_info, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, h->stream));
   else HIP_TRY(h, hipMemsetAsync(info_d, 0, (size_t)B * sizeof(int32_t), h->stream));
   const bool with_image = var_d && kind == BLR_PRIOR_UPPER_FACTOR;
-  const int64_t chunk = std::min<int64_t>(std::min<int64_t>(B, 65535), with_image ? MargImages<T>::kMaxChunk : 65535);
+  const int64_t chunk = h->cap_chunk(std::min<int64_t>(std::min<int64_t>(B, 65535), with_image ? MargImages<T>::kMaxChunk : 65535));
+  h->count_chunks(B, chunk);
   const size_t lds = marg_cols_lds_bytes(sizeof(T), (int)D, with_image);
   void (*const kern)(MargColsArgs<T>) = layout == BLR_LAYOUT_ROWVECS ? marginals_cols_kernel<T, LAYOUT_ROWVECS> : marginals_cols_kernel<T, LAYOUT_COLVECS>;
   if ((rc = set_lds_once(h, kern, lds))) return rc;
@@ -3553,6 +3592,7 @@ int loo_multi_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_
   if (loo_total && B > 1 && stride_lt < S) return bad_arg(h, 32, "stride_lt < S");
   if (!info) return bad_arg(h, 33, "info is NULL");
   if (!h) return -1;
+  h->last_chunks = 1;  // (a route with a chunk loop counts its own)
   HIP_TRY(h, hipSetDevice(h->device));
 
   CallIO io(h, memspace);
@@ -3581,13 +3621,15 @@ int loo_multi_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_
   a.degenerate = h->stats_dev + 3;
 
   // status: loo_check_kernel as blr_loo_batched_* launches it
-  for (int64_t b0 = 0; b0 < B; b0 += 65535)
-    hipLaunchKernelGGL(loo_check_kernel<T>, dim3((unsigned)std::min<int64_t>(65535, B - b0)), dim3(kThreads), 0, h->stream, T_d + b0 * strideT,
+  const int64_t ychunk = h->cap_chunk(65535);  // grid.x / grid.y <= 65535: the check and the empty totals
+  h->count_chunks(B, ychunk);
+  for (int64_t b0 = 0; b0 < B; b0 += ychunk)
+    hipLaunchKernelGGL(loo_check_kernel<T>, dim3((unsigned)std::min<int64_t>(ychunk, B - b0)), dim3(kThreads), 0, h->stream, T_d + b0 * strideT,
                        ldt, strideT, (int)D, a.s + b0 * strides, strides, noise_kind, (int)N, info_d + b0);
   HIP_TRY(h, hipGetLastError());
   if (N == 0) {  // empty sums, for the regressors whose state passed the check
-    for (int64_t b0 = 0; tot_d && b0 < B; b0 += 65535)
-      hipLaunchKernelGGL(loo_cols_total_kernel, dim3((unsigned)S, (unsigned)std::min<int64_t>(65535, B - b0)), dim3(kThreads), 0, h->stream,
+    for (int64_t b0 = 0; tot_d && b0 < B; b0 += ychunk)
+      hipLaunchKernelGGL(loo_cols_total_kernel, dim3((unsigned)S, (unsigned)std::min<int64_t>(ychunk, B - b0)), dim3(kThreads), 0, h->stream,
                          (const double*)nullptr, (int64_t)0, (int64_t)0, 0, tot_d, stride_lt, (const int32_t*)info_d, (int)b0);
     HIP_TRY(h, hipGetLastError());
     return io.finish();
@@ -3601,6 +3643,7 @@ int loo_multi_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_
   int64_t chunk = std::min<int64_t>(B, 65535);
   if (small) chunk = std::min<int64_t>(chunk, MargImages<T>::kMaxChunk);
   if (per) chunk = std::max<int64_t>(1, std::min<int64_t>(chunk, (int64_t)(kLooWorkspace / per)));
+  chunk = h->cap_chunk(chunk);
   const size_t off_mean = (size_t)chunk * row;                                  // (D > 128) var first, then the means
   const size_t off_ll = small ? 0 : off_mean + (size_t)chunk * S * row;
   const size_t off_zero = off_ll + (ll_ws ? (size_t)chunk * S * row_ll : 0), off_inf = off_zero + 256;
@@ -3657,6 +3700,7 @@ int loo_multi_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_
                          c.stride_ll, (int)N, tot_d, stride_lt, (const int32_t*)info_d, (int)b0);
     HIP_TRY(h, hipGetLastError());
   }
+  h->count_chunks(B, chunk);  // (after the loop: the large-D route's marginals count their own)
   return io.finish();
 }
 
@@ -3697,6 +3741,7 @@ int state_multi_factor(blr_handle* h, int memspace, int layout, int64_t B, int64
   if (logpdf && B > 1 && stride_lp < S) return bad_arg(h, 24, "stride_lp < S");
   if (!info) return bad_arg(h, 25, "info is NULL");
   if (!h) return -1;
+  h->last_chunks = 1;  // (a route with a chunk loop counts its own)
   HIP_TRY(h, hipSetDevice(h->device));
 
   if (k == 0) {  // nothing to condition on or to forget: the state keeps its bits, every evidence is 0
@@ -3776,12 +3821,14 @@ int state_multi_factor(blr_handle* h, int memspace, int layout, int64_t B, int64
     const size_t lds = state_cols_global_lds_bytes((int)D);
     if ((rc = set_lds_once(h, kern, lds))) return rc;
     if (a.logpdf) HIP_TRY(h, hipMemcpy2DAsync(a.logpdf, (size_t)stride_lp * sizeof(double), lp0, sizeof(double), sizeof(double), (size_t)B, hipMemcpyDeviceToDevice, h->stream));
-    for (int64_t b0 = 0; S > 1 && b0 < B; b0 += 32768) {
+    const int64_t chunk = h->cap_chunk(32768);
+    if (S > 1) h->count_chunks(B, chunk);
+    for (int64_t b0 = 0; S > 1 && b0 < B; b0 += chunk) {
       StateColsArgs<T> g = a;
       g.X += b0 * strideX; g.Y += b0 * strideY; g.s += b0 * strides; g.M += b0 * strideM; g.Tf += b0 * strideT;
       g.diag0 += b0 * D; g.info += b0;
       if (g.logpdf) g.logpdf += b0 * stride_lp;
-      hipLaunchKernelGGL(kern, dim3((unsigned)(S - 1), (unsigned)std::min<int64_t>(32768, B - b0)), dim3(kThreads), lds, h->stream, g);
+      hipLaunchKernelGGL(kern, dim3((unsigned)(S - 1), (unsigned)std::min<int64_t>(chunk, B - b0)), dim3(kThreads), lds, h->stream, g);
     }
   }
   HIP_TRY(h, hipGetLastError());
@@ -3918,6 +3965,7 @@ int blr_get_stat(blr_handle* h, const char* key, int64_t* value) {
   if (!key) return bad_arg(h, 2, "key is NULL");
   if (!value) return bad_arg(h, 3, "value is NULL");
   if (!strcmp(key, "i8_regressors")) { *value = (int64_t)h->i8_attempted; return 0; }
+  if (!strcmp(key, "last_chunks")) { *value = h->last_chunks; return 0; }  // chunks / slices of regressors of the most recent call
   if (!strcmp(key, "i8_handed_back")) {
     unsigned long long v = 0;
     if (h->stats_dev) {

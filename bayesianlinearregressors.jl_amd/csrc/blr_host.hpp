@@ -52,7 +52,8 @@
   X("SWEEP", set_sweep)            \
   X("GRAM_SPLITS", set_gram_splits) \
   X("I8_PROBE_MIN", set_i8_probe_min) \
-  X("I8_GROUPS", set_i8_groups)
+  X("I8_GROUPS", set_i8_groups)   \
+  X("MAX_CHUNK", set_max_chunk)
 
 struct BlrOptions {
 #define BLR_X(member, key) bool member = false;
@@ -62,6 +63,7 @@ struct BlrOptions {
   int chain_batch = 0;    // regressors per shared launch at D > 128: 0 = as many as the workspace holds
   int i8_probe_min = 0;   // int8 route: batches beyond this many regressors start with a probe slice; 0 = kI8ProbeMin
   int i8_groups = 0;      // int8 route: digit groups kept, 0 = six under isotropic noise and seven under diagonal noise; 6 | 7 = that plan for both noise kinds
+  int max_chunk = 0;      // regressors per chunk / slice of every batched entry point: 0 = the launch's own bound (tests: small groups cross every seam)
   long chain_ws_mb = 0;   // workspace bound of such a group in MiB: 0 = kChainWorkspace
   int sweep = 0;          // blr_update_factor_* route: 0 = router, 1 = always the Givens sweep, 2 = never
   int gs_fields = 0, gs_so = 0, gs_sd = 0, gs_nl = 0;  // GRAM_SPLITS = "off-diagonal,diagonal[,nlong]" (gs_fields = numbers parsed)
@@ -99,6 +101,13 @@ struct BlrOptions {
     if (!on) { i8_groups = 0; return 0; }
     if (!parse_long(value, v) || !(v == 6 || v == 7)) return -3;
     i8_groups = (int)v;
+    return 0;
+  }
+  int set_max_chunk(bool on, const char* value) {
+    long v = 0;
+    if (!on) { max_chunk = 0; return 0; }
+    if (!parse_long(value, v) || v < 1 || v > 65535) return -3;
+    max_chunk = (int)v;
     return 0;
   }
   int set_chain_ws_mb(bool on, const char* value) {
@@ -199,6 +208,12 @@ struct blr_handle {
   // planes pass, Gram launch and factorisation as one more row block (blr_planes.hpp); the group function leaves what the finish needs
   struct MultiSrc { const void* Y; int64_t ldY; int S; void* Abar; int64_t lda; void* Tfull; int DP; double* qsp; int nq; bool done; };
   MultiSrc* multi_src = nullptr;
+  // Regressors per launch: every batched entry point cuts its batch by its own bound (grid.y, a workspace, the images) and, when
+  // option MAX_CHUNK is set, by that as well -- the same loop, the same pointer arithmetic, more rounds of it.
+  int64_t cap_chunk(int64_t natural) const { return opt.max_chunk > 0 ? std::min<int64_t>(natural, opt.max_chunk) : natural; }
+  int64_t last_chunks = 0;               // chunks / slices of regressors the most recent call launched (blr_get_stat "last_chunks"): 1 at
+                                         // every entry, then whatever the call's chunk loop counts
+  void count_chunks(int64_t B, int64_t chunk) { last_chunks = (B + chunk - 1) / chunk; }
   int64_t route_i8_B = 0;                // > 0: that dispatch took the int8 route with this many regressors (blr_last_route looks at its hand-backs)
   std::string route_buf;
   unsigned* ticket = nullptr;     // [0], [2], [3]: wavefront solve (tickets, done, launch count); [16 + 128 bank + g]: arrivals of panel_chain_kernel

@@ -76,7 +76,7 @@ int blr_set_async(blr_handle* h, int async);      /* 1: DEVICE-memspace calls re
 int blr_synchronize(blr_handle* h);
 /* Run-time switches of the handle (A/B measurements and tests; the defaults are the measured best).  `key` is one of NO_LDSDMA,
  * NO_WAVE_KERNEL, NO_GRAM_RING, NO_DIAG_SPLIT, NO_XCD_SWIZZLE, NO_MFMA_PROJECT, NO_I8_GRAM, NO_I8_DIAG, NO_I8_FACTOR, NO_I8_ROWVECS, NO_I8_DENSE, NO_I8_FALLBACK, NO_BF16X3, NO_PLANES, NO_FP16_PLANES, PLANES8, NO_SPEC_ROWMAX, NO_MULTI_PLANES, NO_MARG_GEMM, NO_GRAD_GEMM, NO_DOWNDATE_LDS, PLAN_DEBUG (flags: any non-empty value = on),
- * WAVE_SPLIT = 1|2|4, CHAIN_BATCH = 1..128, CHAIN_WS_MB, I8_PROBE_MIN = 256..2^20, I8_GROUPS = 6|7, SWEEP = always|never|auto, GRAM_SPLITS = "o,d[,nlong]" (README.md);
+ * WAVE_SPLIT = 1|2|4, CHAIN_BATCH = 1..128, CHAIN_WS_MB, I8_PROBE_MIN = 256..2^20, I8_GROUPS = 6|7, MAX_CHUNK = 1..65535 (tests: at most that many regressors per chunk / slice of every batched entry point, so that small batches cross the seams over-bound batches cross), SWEEP = always|never|auto, GRAM_SPLITS = "o,d[,nlong]" (README.md);
  * a "BLR_MI355X_" prefix is accepted.  value NULL or "" restores the built-in default.  The environment variables
  * BLR_MI355X_<KEY> are read ONCE, by blr_create -- no entry point reads the environment.  -> 0, or -2 / -3 (unknown key /
  * malformed value). */
@@ -97,7 +97,9 @@ const char* blr_last_route(blr_handle* h);
  * columns of every column chunk (doubled: an entry up to 16 x the sample's largest still fits); an entry beyond that sends the call
  * through the exact row maxima and the planes pass a second time (one more read of X; option NO_SPEC_ROWMAX = 1 always takes the exact
  * maxima: one more read of X on every call); "loo_degenerate" = observations blr_loo_batched_* gave NaN because their 1 - h_n was
- * <= 0 or not finite (reading it synchronises the handle's stream); "workspace_bytes" = device scratch the handle holds now.
+ * <= 0 or not finite (reading it synchronises the handle's stream); "last_chunks" = chunks / slices of regressors the handle's most
+ * recent call launched (NOT cumulative: every entry point starts it at 1; a batch beyond grid.y = 65535, a workspace or image bound, or
+ * option MAX_CHUNK, goes in several); "workspace_bytes" = device scratch the handle holds now.
  * -> 0, -2 unknown key, -3 NULL value. */
 int blr_get_stat(blr_handle* h, const char* key, int64_t* value);
 int blr_reset_stats(blr_handle* h);

@@ -268,6 +268,31 @@ def test_julia_shim_ccall_signatures_match_the_header(repo_root):
     assert seen >= 34  # every entry point a Julia host needs, incl. dense noise, cov, batched device form and the RCCL exchange
 
 
+def test_every_switch_and_counter_is_documented(repo_root):
+    """The option tables of blr_host.hpp and the keys of blr_get_stat against the header, the README's switch paragraph and the
+    Python binding: a switch or counter (MAX_CHUNK and "last_chunks" among them) that is not documented fails here."""
+    src = os.path.join(repo_root, "bayesianlinearregressors.jl_amd")
+    host = open(os.path.join(src, "csrc", "blr_host.hpp")).read()
+    flags = re.findall(r'^\s*X\(\w+, "([A-Z0-9_]+)"\)', host, flags=re.M)
+    valued = re.findall(r'^\s*X\("([A-Z0-9_]+)", set_\w+\)', host, flags=re.M)
+    assert len(flags) >= 22 and "NO_DOWNDATE_LDS" in flags
+    assert {"WAVE_SPLIT", "CHAIN_BATCH", "CHAIN_WS_MB", "SWEEP", "GRAM_SPLITS", "I8_PROBE_MIN", "I8_GROUPS", "MAX_CHUNK"} == set(valued)
+    header = open(os.path.join(repo_root, "include", "blr_mi355x.h")).read()
+    readme = open(os.path.join(repo_root, "README.md")).read()
+    for key in flags + valued:
+        assert re.search(r"\b%s\b" % key, header), f"{key} missing from include/blr_mi355x.h"
+        assert re.search(r"\b%s\b" % key, readme), f"{key} missing from README.md"
+    abi = open(os.path.join(src, "csrc", "blr_abi.hip")).read()
+    body = abi[abi.index("int blr_get_stat(") : abi.index("int blr_reset_stats(")]
+    stats = re.findall(r'strcmp\(key, "(\w+)"\)', body)
+    assert {"i8_regressors", "i8_handed_back", "planes_redone", "loo_degenerate", "workspace_bytes", "last_chunks"} <= set(stats)
+    doc = _abi.Handle.get_stat.__doc__
+    for key in stats:
+        assert '"%s"' % key in header, f"{key} missing from include/blr_mi355x.h"
+        assert '"%s"' % key in doc, f"{key} missing from Handle.get_stat's docstring"
+    assert "MAX_CHUNK" in _abi.Handle.set_option.__doc__
+
+
 def test_comm_entry_points_validate_without_a_gpu():
     """blr_comm_* / blr_logpdf_allgather_sum (RCCL called directly): argument checks need no device."""
     from blr_amd import _abi

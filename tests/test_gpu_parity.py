@@ -937,10 +937,17 @@ def test_release_workspace_and_options_round_trip(B, opt):
     again = everything()
     for u, v in zip(first, again):
         np.testing.assert_array_equal(np.asarray(u), np.asarray(v))
-    for key, value in (("NO_SUCH_SWITCH", "1"), ("WAVE_SPLIT", "3"), ("SWEEP", "sometimes"), ("GRAM_SPLITS", "7")):
+    for key, value in (("NO_SUCH_SWITCH", "1"), ("WAVE_SPLIT", "3"), ("SWEEP", "sometimes"), ("GRAM_SPLITS", "7"), ("MAX_CHUNK", "0"),
+                       ("MAX_CHUNK", "65536"), ("MAX_CHUNK", "-1")):
         with pytest.raises(Exception):
             h.set_option(key, value)
     opt("WAVE_SPLIT", "2")  # a well-formed one round-trips (restored by the fixture)
+    # MAX_CHUNK caps the regressors per launch (here: one regressor, one chunk, whatever the cap) and leaves the bits alone
+    opt("MAX_CHUNK", "1")
+    capped = everything()
+    opt("MAX_CHUNK", "65535")
+    for u, v in zip(first, capped):
+        np.testing.assert_array_equal(np.asarray(u), np.asarray(v))
 
 
 @pytest.mark.parametrize("dtype,D,N,Bn,kind", [(np.float64, 256, 200, 5, "factor"), (np.float32, 400, 333, 3, "dense"), (np.float64, 272, 70, 4, "dense"),
@@ -2942,7 +2949,8 @@ def test_last_route_and_option_codes(B, opt):
     opt("NO_I8_GRAM", "1")
     assert post(128, 512, 2) == "fused_small_kernel<double, 8, 4>"
     for key, value, code in (("NO_SUCH_SWITCH", "1", -2), ("WAVE_SPLIT", "3", -3), ("CHAIN_BATCH", "abc", -3), ("CHAIN_BATCH", "12x", -3),
-                             ("CHAIN_WS_MB", "", 0), ("SWEEP", "sometimes", -3), ("GRAM_SPLITS", "7", -3)):
+                             ("CHAIN_WS_MB", "", 0), ("SWEEP", "sometimes", -3), ("GRAM_SPLITS", "7", -3), ("MAX_CHUNK", "0", -3),
+                             ("MAX_CHUNK", "65536", -3), ("MAX_CHUNK", "3x", -3), ("MAX_CHUNK", "", 0), ("BLR_MI355X_MAX_CHUNK", "", 0)):
         if code == 0:
             h.set_option(key, value)
         else:
@@ -2952,6 +2960,10 @@ def test_last_route_and_option_codes(B, opt):
     with pytest.raises(a.BLRError):
         h.get_stat("no_such_counter")
     assert h.get_stat("workspace_bytes") >= 0
+    assert post(128, 512, 2) == "fused_small_kernel<double, 8, 4>" and h.get_stat("last_chunks") == 1  # (NO_I8_GRAM: one launch)
+    opt("NO_I8_GRAM", None)
+    opt("MAX_CHUNK", "1")
+    assert post(128, 512, 2) == "fused_i8_kernel" and h.get_stat("last_chunks") == 2  # two slices of one regressor
 
 
 @pytest.mark.parametrize("noise", ["iso", "diag"])
