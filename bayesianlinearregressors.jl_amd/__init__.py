@@ -43,6 +43,8 @@ from .regressor import (
     mean_and_var,
     mean_and_var_columns,
     mean_and_var_columns_map,
+    cov_map,
+    mean_and_cov_map,
     mean_columns,
     posterior,
     posterior_best,
@@ -67,4 +69,5 @@ __all__ = [
     "posterior_ragged", "logpdf_ragged",
     "posterior_columns", "logpdf_columns_map", "posterior_columns_map",
     "mean_and_var_columns", "mean_columns", "mean_and_var_columns_map",
+    "cov_map", "mean_and_cov_map",
 ]

@@ -130,6 +130,9 @@ for _suf in ("f64", "f32"):
         [_H, _int, _int, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _int, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp], _int)
     _SIGS[f"blr_mean_and_cov_{_suf}"] = (
         [_H, _int, _int, _i64, _i64, _vp, _i64, _int, _vp, _i64, _int, _vp, _vp, _i64, _vp, _vp, _i64, _vp], _int)
+    _SIGS[f"blr_mean_and_cov_batched_{_suf}"] = (
+        [_H, _int, _int, _i64, _i64, _i64, _vp, _i64, _i64, _int, _vp, _i64, _i64, _int, _vp, _i64, _vp, _i64, _i64,
+         _vp, _i64, _vp, _i64, _i64, _vp], _int)
     _SIGS[f"blr_rand_dense_noise_{_suf}"] = (
         [_H, _int, _int, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _int, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64], _int)
     _fp = C.c_double if _suf == "f64" else C.c_float
@@ -497,6 +500,14 @@ class Handle:
         fn = getattr(self.lib, f"blr_mean_and_cov_{suffix(dtype)}")
         return self.check(fn(self._h, memspace, layout, D, N, _ptr(X), ldx, noise_kind, _ptr(s), lds, prior_kind, _ptr(mw), _ptr(Lw), ldl,
                              _ptr(mean), _ptr(Cov), ldc, _ptr(info)))
+
+    def mean_and_cov_batched(self, dtype, memspace, layout, B, D, N, X, ldx, strideX, noise_kind, s, lds, strides, prior_kind, mw, stridemw,
+                             Lw, ldl, strideLw, mean, stridemean, Cov, ldc, strideC, info):
+        """Mean (may be None) and the full N x N predictive covariance (may be None) of B regressors in one call;
+        include/blr_mi355x.h blr_mean_and_cov_batched_* (one status per regressor in info)."""
+        fn = getattr(self.lib, f"blr_mean_and_cov_batched_{suffix(dtype)}")
+        return self.check(fn(self._h, memspace, layout, B, D, N, _ptr(X), ldx, strideX, noise_kind, _ptr(s), lds, strides, prior_kind,
+                             _ptr(mw), stridemw, _ptr(Lw), ldl, strideLw, _ptr(mean), stridemean, _ptr(Cov), ldc, strideC, _ptr(info)))
 
     def rand_dense_noise(self, dtype, memspace, layout, D, N, S, X, ldx, Sy, ldsy, prior_kind, mw, Lw, ldl, Z1, ldz1, Z2, ldz2, Y, ldy):
         fn = getattr(self.lib, f"blr_rand_dense_noise_{suffix(dtype)}")

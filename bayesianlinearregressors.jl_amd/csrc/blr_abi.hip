@@ -34,6 +34,7 @@
 #include "blr_ragged.hpp"
 #include "blr_multi.hpp"
 #include "blr_marg_multi.hpp"
+#include "blr_cov_batched.hpp"
 #include "blr_loo_multi.hpp"
 #include "blr_state_cols.hpp"
 #include "blr_host.hpp"
@@ -2530,54 +2531,33 @@ int tall_solve_rows(blr_handle* h, int layout, int D, int N, const T* X, int64_t
   return 0;
 }
 
+// The temporaries of one N x N covariance at padded sizes (mean_and_cov_core): the tall matrix, the Gram tiles, a scalar
 template <typename T>
-int mean_and_cov(blr_handle* h, int memspace, int layout, int64_t D64, int64_t N64, const T* X, int64_t ldx, int noise_kind, const T* s,
-                 int64_t lds, int prior_kind, const T* mw, const T* Lw, int64_t ldl, T* mean, T* C, int64_t ldc, int32_t* info) {
-  if (!h) return -1;
-  h->last_chunks = 1;  // (a route with a chunk loop counts its own)
-  h->err.clear();
-  if (memspace != BLR_MEM_HOST && memspace != BLR_MEM_DEVICE) return bad_arg(h, 2, "memspace");
-  if (layout != BLR_LAYOUT_COLVECS && layout != BLR_LAYOUT_ROWVECS) return bad_arg(h, 3, "unknown layout (reference :26-31)");
-  if (D64 < 1 || D64 > kMaxLargeD) return bad_arg(h, 4, "D out of range for this build (1..8192)");
-  if (N64 < 1 || N64 > kMaxDenseN) return bad_arg(h, 5, "N out of range for an N x N covariance (1..16384)");
-  if (!X) return bad_arg(h, 6, "X is NULL");
-  if (layout == BLR_LAYOUT_COLVECS ? ldx < D64 : ldx < N64) return bad_arg(h, 7, "ldx too small");
-  if (noise_kind != BLR_NOISE_ISOTROPIC && noise_kind != BLR_NOISE_DIAGONAL && noise_kind != BLR_NOISE_DENSE) return bad_arg(h, 8, "noise_kind");
-  if (!s) return bad_arg(h, 9, "s is NULL");
-  if (noise_kind == BLR_NOISE_DENSE && lds < N64) return bad_arg(h, 10, "lds < N");
-  if (prior_kind != BLR_PRIOR_DENSE && prior_kind != BLR_PRIOR_UPPER_FACTOR && prior_kind != BLR_PRIOR_DIAGONAL)
-    return bad_arg(h, 11, "prior_kind");
-  if (mean && !mw) return bad_arg(h, 12, "mw is NULL");
-  if (!Lw) return bad_arg(h, 13, "Lw is NULL");
-  if (prior_kind != BLR_PRIOR_DIAGONAL && ldl < D64) return bad_arg(h, 14, "ldl < D");
-  if (!C) return bad_arg(h, 16, "C is NULL");
-  if (ldc < N64) return bad_arg(h, 17, "ldc < N");
-  if (!info) return bad_arg(h, 18, "info is NULL");
-  HIP_TRY(h, hipSetDevice(h->device));
-  const int D = (int)D64, N = (int)N64;
-  const int DP = (D + kPB - 1) / kPB * kPB, NP = (N + kPB - 1) / kPB * kPB;
-  const int64_t ldy = (int64_t)DP + NP;
-  CallIO io(h, memspace);
-  int rc;
-  const T *X_d = nullptr, *s_d = nullptr, *mw_d = nullptr, *Lw_d = nullptr;
-  T *mean_d = nullptr, *C_d = nullptr;
-  int32_t* info_d = nullptr;
-  const size_t x_one = layout == BLR_LAYOUT_COLVECS ? mat_extent(D, N, ldx) : mat_extent(N, D, ldx);
-  const size_t lw_one = prior_kind == BLR_PRIOR_DIAGONAL ? (size_t)D : mat_extent(D, D, ldl);
-  const size_t s_one = noise_kind == BLR_NOISE_DENSE ? mat_extent(N, N, lds) : (noise_kind == BLR_NOISE_DIAGONAL ? (size_t)N : 1);
-  if ((rc = io.in(X, x_one, &X_d))) return rc;
-  if ((rc = io.in(s, s_one, &s_d))) return rc;
-  if ((rc = io.in(mw, (size_t)D, &mw_d))) return rc;
-  if ((rc = io.in(Lw, lw_one, &Lw_d))) return rc;
-  if ((rc = io.out(mean, (size_t)N, &mean_d))) return rc;
-  if ((rc = io.out(C, mat_extent(N, N, ldc), &C_d))) return rc;
-  if ((rc = io.out(info, (size_t)1, &info_d))) return rc;
+struct CovTemps {
   T *Ybar = nullptr, *Gpart = nullptr;
   double* scratch = nullptr;
+  int reserve(CallIO& io, int D, int N) {
+    const int DP = (D + kPB - 1) / kPB * kPB, NP = (N + kPB - 1) / kPB * kPB;
+    const int nb = NP / kPB, ntiles = nb * (nb + 1) / 2;
+    int rc;
+    if ((rc = io.tmp((size_t)((int64_t)DP + NP) * DP, &Ybar))) return rc;
+    if ((rc = io.tmp((size_t)ntiles * kPB * kPB, &Gpart))) return rc;
+    return io.tmp(1, &scratch);
+  }
+};
+
+// mean and covariance of ONE regressor on device operands: what blr_mean_and_cov_* launches, and the D > 128 route of
+// blr_mean_and_cov_batched_* one regressor after the other.  Enqueues only.
+template <typename T>
+int mean_and_cov_core(blr_handle* h, const CovTemps<T>& t, int layout, int D, int N, const T* X_d, int64_t ldx, int noise_kind, const T* s_d,
+                      int64_t lds, int prior_kind, const T* mw_d, const T* Lw_d, int64_t ldl, T* mean_d, T* C_d, int64_t ldc, int32_t* info_d) {
+  const int DP = (D + kPB - 1) / kPB * kPB, NP = (N + kPB - 1) / kPB * kPB;
+  const int64_t ldy = (int64_t)DP + NP;
   const int nb = NP / kPB, ntiles = nb * (nb + 1) / 2;
-  if ((rc = io.tmp((size_t)ldy * DP, &Ybar))) return rc;
-  if ((rc = io.tmp((size_t)ntiles * kPB * kPB, &Gpart))) return rc;
-  if ((rc = io.tmp(1, &scratch))) return rc;
+  T *const Ybar = t.Ybar, *const Gpart = t.Gpart;
+  double* const scratch = t.scratch;
+  const T* const mean = mean_d;
+  int rc;
   // ---- Y = alpha' = X' Uw^-1   (reference :36 alpha = Uw' \ X)
   if (prior_kind == BLR_PRIOR_DIAGONAL) {
     hipLaunchKernelGGL(prior_diag_kernel<T>, dim3(1), dim3(kThreads), 0, h->stream, Lw_d, (int64_t)1, prior_kind, D, scratch, info_d);
@@ -2603,6 +2583,52 @@ int mean_and_cov(blr_handle* h, int memspace, int layout, int64_t D64, int64_t N
   if (mean)
     hipLaunchKernelGGL(mean_small_kernel<T>, dim3((unsigned)((N + 255) / 256)), dim3(kThreads), 0, h->stream, X_d, ldx, layout, mw_d, D, N, mean_d);
   HIP_TRY(h, hipGetLastError());
+  return 0;
+}
+
+template <typename T>
+int mean_and_cov(blr_handle* h, int memspace, int layout, int64_t D64, int64_t N64, const T* X, int64_t ldx, int noise_kind, const T* s,
+                 int64_t lds, int prior_kind, const T* mw, const T* Lw, int64_t ldl, T* mean, T* C, int64_t ldc, int32_t* info) {
+  if (!h) return -1;
+  h->last_chunks = 1;  // (a route with a chunk loop counts its own)
+  h->err.clear();
+  if (memspace != BLR_MEM_HOST && memspace != BLR_MEM_DEVICE) return bad_arg(h, 2, "memspace");
+  if (layout != BLR_LAYOUT_COLVECS && layout != BLR_LAYOUT_ROWVECS) return bad_arg(h, 3, "unknown layout (reference :26-31)");
+  if (D64 < 1 || D64 > kMaxLargeD) return bad_arg(h, 4, "D out of range for this build (1..8192)");
+  if (N64 < 1 || N64 > kMaxDenseN) return bad_arg(h, 5, "N out of range for an N x N covariance (1..16384)");
+  if (!X) return bad_arg(h, 6, "X is NULL");
+  if (layout == BLR_LAYOUT_COLVECS ? ldx < D64 : ldx < N64) return bad_arg(h, 7, "ldx too small");
+  if (noise_kind != BLR_NOISE_ISOTROPIC && noise_kind != BLR_NOISE_DIAGONAL && noise_kind != BLR_NOISE_DENSE) return bad_arg(h, 8, "noise_kind");
+  if (!s) return bad_arg(h, 9, "s is NULL");
+  if (noise_kind == BLR_NOISE_DENSE && lds < N64) return bad_arg(h, 10, "lds < N");
+  if (prior_kind != BLR_PRIOR_DENSE && prior_kind != BLR_PRIOR_UPPER_FACTOR && prior_kind != BLR_PRIOR_DIAGONAL)
+    return bad_arg(h, 11, "prior_kind");
+  if (mean && !mw) return bad_arg(h, 12, "mw is NULL");
+  if (!Lw) return bad_arg(h, 13, "Lw is NULL");
+  if (prior_kind != BLR_PRIOR_DIAGONAL && ldl < D64) return bad_arg(h, 14, "ldl < D");
+  if (!C) return bad_arg(h, 16, "C is NULL");
+  if (ldc < N64) return bad_arg(h, 17, "ldc < N");
+  if (!info) return bad_arg(h, 18, "info is NULL");
+  HIP_TRY(h, hipSetDevice(h->device));
+  const int D = (int)D64, N = (int)N64;
+  CallIO io(h, memspace);
+  int rc;
+  const T *X_d = nullptr, *s_d = nullptr, *mw_d = nullptr, *Lw_d = nullptr;
+  T *mean_d = nullptr, *C_d = nullptr;
+  int32_t* info_d = nullptr;
+  const size_t x_one = layout == BLR_LAYOUT_COLVECS ? mat_extent(D, N, ldx) : mat_extent(N, D, ldx);
+  const size_t lw_one = prior_kind == BLR_PRIOR_DIAGONAL ? (size_t)D : mat_extent(D, D, ldl);
+  const size_t s_one = noise_kind == BLR_NOISE_DENSE ? mat_extent(N, N, lds) : (noise_kind == BLR_NOISE_DIAGONAL ? (size_t)N : 1);
+  if ((rc = io.in(X, x_one, &X_d))) return rc;
+  if ((rc = io.in(s, s_one, &s_d))) return rc;
+  if ((rc = io.in(mw, (size_t)D, &mw_d))) return rc;
+  if ((rc = io.in(Lw, lw_one, &Lw_d))) return rc;
+  if ((rc = io.out(mean, (size_t)N, &mean_d))) return rc;
+  if ((rc = io.out(C, mat_extent(N, N, ldc), &C_d))) return rc;
+  if ((rc = io.out(info, (size_t)1, &info_d))) return rc;
+  CovTemps<T> t;
+  if ((rc = t.reserve(io, D, N))) return rc;
+  if ((rc = mean_and_cov_core<T>(h, t, layout, D, N, X_d, ldx, noise_kind, s_d, lds, prior_kind, mw_d, Lw_d, ldl, mean_d, C_d, ldc, info_d))) return rc;
   return io.finish();  // (drains the stream in either memspace: the temporaries are freed on return)
 }
 
@@ -3550,6 +3576,148 @@ int marginals_multi_batched(blr_handle* h, int memspace, int layout, int64_t B, 
   return io.finish();
 }
 
+// ---- joint predictive covariance of a batch of regressors (blr_mean_and_cov_batched_*; blr_cov_batched.hpp) ----------
+
+template <typename T>
+int mean_and_cov_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t N, const T* X, int64_t ldx, int64_t strideX,
+                         int noise_kind, const T* s, int64_t lds, int64_t strides, int prior_kind, const T* mw, int64_t stridemw, const T* Lw,
+                         int64_t ldl, int64_t strideLw, T* mean, int64_t stridemean, T* C, int64_t ldc, int64_t strideC, int32_t* info) {
+  // (the argument checks come before the handle's: they need no device)
+  if (h) h->err.clear();
+  if (memspace != BLR_MEM_HOST && memspace != BLR_MEM_DEVICE) return bad_arg(h, 2, "memspace");
+  if (layout != BLR_LAYOUT_COLVECS && layout != BLR_LAYOUT_ROWVECS) return bad_arg(h, 3, "unknown layout (reference :26-31)");
+  if (B < 0 || B > (1 << 30)) return bad_arg(h, 4, "B out of range (0..2^30)");
+  if (D < 1 || D > kMaxLargeD) return bad_arg(h, 5, "D out of range (1..8192)");
+  if (N < 0 || N > kMaxDenseN) return bad_arg(h, 6, "N out of range for an N x N covariance (0..16384)");
+  if (B == 0 || N == 0 || (!mean && !C)) return 0;
+  if (!X) return bad_arg(h, 7, "X is NULL");
+  if (layout == BLR_LAYOUT_COLVECS ? ldx < D : ldx < N) return bad_arg(h, 8, "ldx too small");
+  if (strideX < 0) return bad_arg(h, 9, "strideX < 0");
+  if (noise_kind != BLR_NOISE_ISOTROPIC && noise_kind != BLR_NOISE_DIAGONAL && noise_kind != BLR_NOISE_DENSE) return bad_arg(h, 10, "noise_kind");
+  if (C && !s) return bad_arg(h, 11, "s is NULL");
+  if (noise_kind == BLR_NOISE_DENSE && lds < N) return bad_arg(h, 12, "lds < N");
+  if (strides < 0) return bad_arg(h, 13, "strides < 0");
+  if (prior_kind != BLR_PRIOR_DENSE && prior_kind != BLR_PRIOR_UPPER_FACTOR && prior_kind != BLR_PRIOR_DIAGONAL)
+    return bad_arg(h, 14, "prior_kind");
+  if (mean && !mw) return bad_arg(h, 15, "mw is NULL");
+  if (stridemw < 0) return bad_arg(h, 16, "stridemw < 0");
+  if (C && !Lw) return bad_arg(h, 17, "Lw is NULL");
+  if (prior_kind != BLR_PRIOR_DIAGONAL && ldl < D) return bad_arg(h, 18, "ldl < D");
+  if (strideLw < 0) return bad_arg(h, 19, "strideLw < 0");
+  if (mean && B > 1 && stridemean < N) return bad_arg(h, 21, "stridemean < N");
+  if (C && ldc < N) return bad_arg(h, 23, "ldc < N");
+  if (C && B > 1 && strideC < ldc * N) return bad_arg(h, 24, "strideC < ldc * N");
+  if (!info) return bad_arg(h, 25, "info is NULL");
+  if (!h) return -1;
+  h->last_chunks = 1;  // (a route with a chunk loop counts its own)
+  HIP_TRY(h, hipSetDevice(h->device));
+
+  CallIO io(h, memspace);
+  const T *X_d = nullptr, *s_d = nullptr, *mw_d = nullptr, *Lw_d = nullptr;
+  T *mean_d = nullptr, *C_d = nullptr;
+  int32_t* info_d = nullptr;
+  int rc;
+  const size_t x_one = layout == BLR_LAYOUT_COLVECS ? mat_extent(D, N, ldx) : mat_extent(N, D, ldx);
+  const size_t lw_one = prior_kind == BLR_PRIOR_DIAGONAL ? (size_t)D : mat_extent(D, D, ldl);
+  const size_t s_one = noise_kind == BLR_NOISE_DENSE ? mat_extent(N, N, lds) : (noise_kind == BLR_NOISE_DIAGONAL ? (size_t)N : 1);
+  if ((rc = io.in(X, extent(B, strideX, x_one), &X_d))) return rc;
+  if ((rc = io.in(C ? s : (const T*)nullptr, extent(B, strides, s_one), &s_d))) return rc;
+  if ((rc = io.in(mean ? mw : (const T*)nullptr, extent(B, stridemw, (size_t)D), &mw_d))) return rc;
+  if ((rc = io.in(C ? Lw : (const T*)nullptr, extent(B, strideLw, lw_one), &Lw_d))) return rc;
+  if ((rc = io.out(mean, extent(B, stridemean, (size_t)N), &mean_d))) return rc;
+  if ((rc = io.out(C, extent(B, strideC, mat_extent(N, N, ldc)), &C_d))) return rc;
+  if ((rc = io.out(info, (size_t)B, &info_d))) return rc;
+  const unsigned status_grid = (unsigned)std::min<int64_t>((B + kWaves - 1) / kWaves, 1024);
+
+  if (D > kMaxSmallD) {
+    // correct, not fast: one regressor after the other through the launches of blr_mean_and_cov_* (mean_and_cov_core), into a staging
+    // covariance that reaches the caller's only once the regressor's status is known to be 0; the call synchronises per regressor
+    std::vector<int32_t> st((size_t)B, 0);
+    if (C_d) {
+      CovTemps<T> t;
+      T *Ct = nullptr, *mt = nullptr;
+      int32_t* it = nullptr;
+      if ((rc = t.reserve(io, (int)D, (int)N))) return rc;
+      if ((rc = io.tmp((size_t)N * N, &Ct))) return rc;
+      if ((rc = io.tmp((size_t)N, &mt))) return rc;
+      if ((rc = io.tmp(1, &it))) return rc;
+      if (prior_kind != BLR_PRIOR_DENSE) {  // the rule of blr_rand_batched_*: the first non-positive diagonal entry
+        hipLaunchKernelGGL(rand_batched_status_kernel<T>, dim3(status_grid), dim3(kThreads), 0, h->stream, Lw_d, ldl, strideLw,
+                           prior_kind == BLR_PRIOR_DIAGONAL ? 1 : 0, (int)D, B, info_d);
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, hipMemcpyAsync(st.data(), info_d, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+      }
+      for (int64_t b = 0; b < B; ++b) {
+        if (st[(size_t)b] != 0) continue;  // outputs of that regressor stay untouched
+        rc = mean_and_cov_core<T>(h, t, layout, (int)D, (int)N, X_d + b * strideX, ldx, noise_kind, s_d + b * strides, lds, prior_kind,
+                                  mean_d ? mw_d + b * stridemw : (const T*)nullptr, Lw_d + b * strideLw, ldl, mean_d ? mt : (T*)nullptr, Ct, N, it);
+        if (rc) return rc;
+        HIP_TRY(h, hipMemcpyAsync(&st[(size_t)b], it, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        if (st[(size_t)b] != 0) continue;
+        HIP_TRY(h, hipMemcpy2DAsync(C_d + b * strideC, (size_t)ldc * sizeof(T), Ct, (size_t)N * sizeof(T), (size_t)N * sizeof(T), (size_t)N,
+                                    hipMemcpyDeviceToDevice, h->stream));
+        if (mean_d) HIP_TRY(h, hipMemcpyAsync(mean_d + b * stridemean, mt, (size_t)N * sizeof(T), hipMemcpyDeviceToDevice, h->stream));
+      }
+      HIP_TRY(h, hipMemcpyAsync(info_d, st.data(), (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    } else {  // mean only: Lw is not read and every status is 0
+      HIP_TRY(h, hipMemsetAsync(info_d, 0, (size_t)B * sizeof(int32_t), h->stream));
+      for (int64_t b = 0; b < B; ++b)
+        hipLaunchKernelGGL(mean_small_kernel<T>, dim3((unsigned)((N + 255) / 256)), dim3(kThreads), 0, h->stream, X_d + b * strideX, ldx, layout,
+                           mw_d + b * stridemw, (int)D, (int)N, mean_d + b * stridemean);
+      HIP_TRY(h, hipGetLastError());
+    }
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return io.finish();
+  }
+
+  // D <= 128.  Once per call: the factor of a dense prior per regressor (prior_factor) and every regressor's status.  Per chunk of
+  // regressors: the triangular inverses as MFMA images (marg_image_kernel), Z = X'L^-T and the mean (cov_whiten_kernel), C = Z Z' +
+  // Sigma_y (cov_tiles_kernel) -- three launches whatever B
+  CovArgs<T> a{};
+  a.ldx = ldx; a.strideX = strideX; a.lds = lds; a.strides = strides; a.stridemw = stridemw; a.stridemean = stridemean;
+  a.ldc = ldc; a.strideC = strideC; a.noise_kind = noise_kind; a.D = (int)D; a.N = (int)N;
+  const T* U = nullptr;
+  int64_t ldu = 0, strideU = 0;
+  int kind = prior_kind;
+  int32_t* chol_info = nullptr;
+  if (C_d && (rc = prior_factor<T>(h, B, D, prior_kind, Lw_d, ldl, strideLw, &U, &ldu, &strideU, &kind, &chol_info))) return rc;
+  a.prior_kind = kind;
+  if (chol_info) HIP_TRY(h, hipMemcpyAsync(info_d, chol_info, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, h->stream));
+  else if (C_d) hipLaunchKernelGGL(rand_batched_status_kernel<T>, dim3(status_grid), dim3(kThreads), 0, h->stream, U, ldu, strideU,
+                                   kind == BLR_PRIOR_DIAGONAL ? 1 : 0, (int)D, B, info_d);
+  else HIP_TRY(h, hipMemsetAsync(info_d, 0, (size_t)B * sizeof(int32_t), h->stream));  // mean only: Lw is not read
+  const bool with_image = C_d && kind == BLR_PRIOR_UPPER_FACTOR;
+  // regressors per launch: grid.y, the images within 256 MiB, the rows of Z within 256 MiB (at least one regressor: 16 MiB at most)
+  const size_t z_one = cov_z_elems((int)D, (int)N);
+  int64_t chunk = std::min<int64_t>(B, 65535);
+  if (with_image) chunk = std::min<int64_t>(chunk, MargImages<T>::kMaxChunk);
+  if (C_d) chunk = std::min<int64_t>(chunk, std::max<int64_t>(1, (int64_t)(((size_t)256 << 20) / (z_one * sizeof(T)))));
+  chunk = h->cap_chunk(chunk);
+  h->count_chunks(B, chunk);
+  const size_t lds_w = cov_whiten_lds_bytes(sizeof(T), (int)D, with_image), lds_t = cov_tiles_lds_bytes(sizeof(T), (int)D);
+  void (*const whiten)(CovArgs<T>) = layout == BLR_LAYOUT_ROWVECS ? cov_whiten_kernel<T, LAYOUT_ROWVECS> : cov_whiten_kernel<T, LAYOUT_COLVECS>;
+  if ((rc = set_lds_once(h, whiten, lds_w))) return rc;
+  if (C_d && (rc = set_lds_once(h, cov_tiles_kernel<T>, lds_t))) return rc;
+  if (with_image && (rc = MargImages<T>::reserve(h, chunk))) return rc;
+  if (C_d && (rc = h->cov_ws.reserve(h, (size_t)chunk * z_one * sizeof(T)))) return rc;
+  const int64_t ntiles = (N + kCovTile - 1) / kCovTile, npairs = ntiles * (ntiles + 1) / 2;
+  for (int64_t b0 = 0; b0 < B; b0 += chunk) {
+    const int64_t nb = std::min<int64_t>(chunk, B - b0);
+    if (with_image) a.img = MargImages<T>::launch(h, U + b0 * strideU, ldu, strideU, (int)D, (const int32_t*)(info_d + b0), 0, nb);
+    // every workgroup amortises its set-up (the image) over its tiles: about two workgroups per CU in all
+    const int64_t ngroups = std::max<int64_t>(1, std::min<int64_t>(ntiles, (2 * (int64_t)h->cus + nb - 1) / nb));
+    a.X = X_d; a.s = s_d; a.mw = mw_d; a.dprior = kind == BLR_PRIOR_DIAGONAL ? U : nullptr; a.stridedp = strideU;
+    a.info = info_d; a.mean = mean_d; a.C = C_d; a.Z = C_d ? reinterpret_cast<T*>(h->cov_ws.p) : nullptr;
+    a.ngroups = (int)ngroups; a.reg0 = (int)b0;
+    hipLaunchKernelGGL(whiten, dim3((unsigned)ngroups, (unsigned)nb), dim3(kThreads), lds_w, h->stream, a);
+    if (C_d) hipLaunchKernelGGL(cov_tiles_kernel<T>, dim3((unsigned)npairs, (unsigned)nb), dim3(kThreads), lds_t, h->stream, a);
+  }
+  HIP_TRY(h, hipGetLastError());
+  return io.finish();
+}
+
 // ---- exact leave-one-out predictives of a batched multi-output state: S columns, one leverage per input (blr_loo_multi_batched_*,
 // DESIGN.md K20; blr_loo_multi.hpp) -------------------------------------------------------------------------------------------------
 
@@ -3997,7 +4165,7 @@ int blr_get_stat(blr_handle* h, const char* key, int64_t* value) {
     return 0;
   }
   if (!strcmp(key, "workspace_bytes")) {
-    *value = (int64_t)(h->ws.bytes + h->feat.bytes + h->aux.bytes + h->i8side.bytes + h->xchg.bytes + h->loo_ws.bytes + h->ragged_meta.bytes + h->multi_ws.bytes);
+    *value = (int64_t)(h->ws.bytes + h->feat.bytes + h->aux.bytes + h->i8side.bytes + h->xchg.bytes + h->loo_ws.bytes + h->ragged_meta.bytes + h->multi_ws.bytes + h->cov_ws.bytes);
     return 0;
   }
   return bad_arg(h, 2, "unknown statistic");
@@ -4140,6 +4308,15 @@ int blr_timer_stop(blr_handle* h, float* elapsed_ms) {
     return marginals_multi_batched<T>(h, memspace, layout, B, D, N, S, X, ldx, strideX, noise_kind, s, strides,     \
                                       prior_kind, M, ldm, strideM, Lw, ldl, strideLw, mean, ldmean, stridemean,     \
                                       var, stridevar, info);                                                        \
+  }                                                                                                                 \
+  int blr_mean_and_cov_batched_##SUF(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t N,      \
+                                     const T* X, int64_t ldx, int64_t strideX, int noise_kind, const T* s,          \
+                                     int64_t lds, int64_t strides, int prior_kind, const T* mw, int64_t stridemw,  \
+                                     const T* Lw, int64_t ldl, int64_t strideLw, T* mean, int64_t stridemean,       \
+                                     T* C, int64_t ldc, int64_t strideC, int32_t* info) {                           \
+    return mean_and_cov_batched<T>(h, memspace, layout, B, D, N, X, ldx, strideX, noise_kind, s, lds, strides,      \
+                                   prior_kind, mw, stridemw, Lw, ldl, strideLw, mean, stridemean, C, ldc, strideC,  \
+                                   info);                                                                           \
   }                                                                                                                 \
   int blr_loo_multi_batched_##SUF(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t N,         \
                                   int64_t S, const T* X, int64_t ldx, int64_t strideX, const T* Y, int64_t ldY,     \

@@ -10,7 +10,7 @@ constexpr int kThreads = 256;  // 4 waves: one per SIMD of a CU
 constexpr int kWaves = kThreads / kWave;
 
 enum : int { LAYOUT_COLVECS = 0, LAYOUT_ROWVECS = 1 };
-enum : int { NOISE_ISOTROPIC = 0, NOISE_DIAGONAL = 1 };
+enum : int { NOISE_ISOTROPIC = 0, NOISE_DIAGONAL = 1, NOISE_DENSE = 2 };  // (NOISE_DENSE: cov_tiles_kernel only)
 enum : int { PRIOR_DENSE = 0, PRIOR_UPPER_FACTOR = 1, PRIOR_DIAGONAL = 2 };
 
 // ---- MFMA traits ---------------------------------------------------------------------------

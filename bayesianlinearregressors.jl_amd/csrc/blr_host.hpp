@@ -190,13 +190,14 @@ struct blr_handle {
   DevBuf ragged_meta;  // offsets[B + 1] and the longest-first order[B] of blr_posterior_ragged_* (a buffer of its own: the D > 128 route runs the batched pipeline, which uses ws)
   DevBuf multi_ws;  // blr_posterior_multi_batched_*: evidence of column 0 per regressor, and the factors when the caller passed T_post = NULL;
                     // blr_update_multi_factor_* / blr_downdate_multi_factor_*: that evidence and the diagonal of the factor before the call
+  DevBuf cov_ws;    // blr_mean_and_cov_batched_*: the rows Z = X'L^-T of a chunk of regressors (blr_cov_batched.hpp)
   std::vector<int64_t> ragged_host;  // host image of that buffer (kept: no allocation per call in the steady state)
   // wavefront back substitution (D > 128): tagged exchange buffer (unsigned long long granules; never smaller than kXchgFloor),
   // start-order ticket counter, launch epoch
   DevBuf xchg;
   static constexpr size_t kWsFloor = (size_t)1 << 20, kXchgFloor = (size_t)1 << 18;
   // blr_release_workspace hands these back; xchg, ticket and stats_dev stay (their contents carry epochs and counters)
-  std::array<DevBuf*, 7> releasable() { return {&ws, &feat, &aux, &i8side, &loo_ws, &ragged_meta, &multi_ws}; }
+  std::array<DevBuf*, 8> releasable() { return {&ws, &feat, &aux, &i8side, &loo_ws, &ragged_meta, &multi_ws, &cov_ws}; }
   // counters behind blr_get_stat: [0] regressors the int8 route handed back to the fp64 kernel (cumulative); [3] degenerate
   // leverages of blr_loo_batched_* (cumulative); [8 + 2 k + {0, 1}]:
   // hand-backs of slice k of the current call (two banks, alternating), read by the NEXT slice's launch (launch_fused_i8)

@@ -31,6 +31,7 @@ __all__ = [
     "posterior_ragged", "logpdf_ragged",
     "posterior_columns", "logpdf_columns_map", "posterior_columns_map",
     "mean_and_var_columns", "mean_columns", "mean_and_var_columns_map",
+    "cov_map", "mean_and_cov_map",
 ]
 
 
@@ -1519,6 +1520,51 @@ class ResidentPosterior:
             for b in temps:
                 b.free()
 
+    def _cov(self, x, Sy, want_mean):
+        dtype, h, D = self.dtype, self._h, self.D
+        temps = []
+
+        def dev(a):
+            temps.append(_DeviceBuffer.of(h, a))
+            return temps[-1].ptr
+
+        try:
+            dX, layout, ldx, N = self._inputs(x, dev, temps)
+            s, noise_kind = _noise(Sy, N, dtype)
+            m = np.empty(N, dtype=dtype) if want_mean else None
+            Cv = np.empty((N, N), dtype=dtype, order="F")
+            if N == 0:
+                return m, Cv
+            temps.append(_DeviceBuffer(h, Cv.nbytes))
+            d_C = temps[-1].ptr
+            d_m = None
+            if want_mean:
+                temps.append(_DeviceBuffer(h, m.nbytes))
+                d_m = temps[-1].ptr
+            info = np.zeros(1, dtype=np.int32)
+            d_info = dev(info)
+            h.mean_and_cov_batched(dtype, _abi.MEM_DEVICE, layout, 1, D, N, dX, ldx, 0, noise_kind, dev(s), N, 0, _abi.PRIOR_UPPER_FACTOR,
+                                   self._mw.ptr if want_mean else None, 0, self._T.ptr, max(D, 1), 0, d_m, N, d_C, N, 0, d_info)
+            h.memcpy_d2h(info, d_info)
+            if info[0] > 0:
+                raise _abi.PosDefException(int(info[0]))
+            h.memcpy_d2h(Cv, d_C)
+            if want_mean:
+                h.memcpy_d2h(m, d_m)
+            return m, Cv
+        finally:
+            for b in temps:
+                b.free()
+
+    def cov(self, x, Sy=1e-18):
+        """cov(f(x, Sy)) (reference :35-38) from the resident state: the full N x N predictive covariance, without copying T to the
+        host (blr_mean_and_cov_batched_* on device pointers, B = 1).  Sy: scalar, vector / Diagonal, or a dense N x N matrix."""
+        return self._cov(x, Sy, False)[1]
+
+    def mean_and_cov(self, x, Sy=1e-18):
+        """mean_and_cov(f(x, Sy)) (reference :45) from the resident state."""
+        return self._cov(x, Sy, True)
+
     def state(self):
         """host copies (mw, T) of the resident state; T column-major upper"""
         mw = np.empty(self.D, dtype=self.dtype)
@@ -1690,6 +1736,11 @@ class ResidentColumnsPosterior:
         """mean(f_c(x)) (reference :33) of the S resident columns: N x S."""
         return self._marginals(x, 1e-18, False)[0]
 
+    def cov(self, x, Sy=1e-18):
+        """cov(f_c(x, Sy)) (reference :35-38) of the resident columns: ONE N x N matrix -- the covariance does not depend on the column
+        (blr_mean_and_cov_batched_* with mean = NULL on device pointers to the shared factor)."""
+        return self._col0._cov(x, Sy, False)[1]
+
     def state(self):
         """host copies (M, T) of the resident state: M D x S, T column-major upper"""
         M = np.empty((self.D, self.S), dtype=self.dtype, order="F")
@@ -1774,6 +1825,81 @@ def cov(fx):
 def mean_and_cov(fx):
     """reference :45"""
     return _mean_and_cov(fx, True)
+
+
+# ---------------------------------------------------------------------------------------------------
+# joint predictive covariances of many problems in ONE library call: `[mean_and_cov(fx) for fx in fxs]` (reference :35-38 / :45 under
+# a map) through blr_mean_and_cov_batched_*
+# ---------------------------------------------------------------------------------------------------
+def _cov_problem(fx):
+    fx = _to_finite_blr(fx)
+    blr = fx.f
+    dtype = _dtype_of(blr.mw)
+    X, layout, ldx, D, N = _x_layout(fx.x, dtype)
+    mw = _mean_vector(blr.mw, D, dtype)
+    s, noise_kind = _noise(fx.Sy, N, dtype)
+    Lw, prior_kind, ldl = _prior(blr.Lw, D, dtype, need_cholesky=True)  # :36 _cholesky(Lw)
+    return dict(dtype=dtype, X=X, layout=layout, ldx=ldx, D=D, N=N, mw=mw, Lw=Lw, prior_kind=prior_kind, ldl=ldl, s=s,
+                noise_kind=noise_kind, x_obj=fx.x)
+
+
+def _cov_many(fxs, want_mean):
+    """[(mean_b, C_b)]: problems that agree in D, N, dtype, layout, noise kind and prior kind through ONE blr_mean_and_cov_batched_*
+    call (the grouping of _draw_many); anything else falls back to one blr_mean_and_cov_* call per problem.  An input x that is the
+    same object for every problem is passed once (strideX = 0)."""
+    fxs = list(fxs)
+    if not fxs:
+        return []
+    qs = []
+    for b, fx in enumerate(fxs):
+        try:
+            qs.append(_cov_problem(fx))
+        except _abi.PosDefException as e:
+            e.index = b
+            raise
+    sig = {(q["dtype"], q["X"].shape, q["X"].flags.f_contiguous, q["layout"], q["D"], q["N"], q["noise_kind"], q["prior_kind"]) for q in qs}
+    q0 = qs[0]
+    if len(sig) != 1 or q0["N"] == 0:
+        out = []
+        for b, fx in enumerate(fxs):
+            try:
+                out.append(_mean_and_cov(fx, want_mean))
+            except _abi.PosDefException as e:
+                e.index = b
+                raise
+        return out
+    dt, D, N, nb = q0["dtype"], q0["D"], q0["N"], len(qs)
+    if all(q["x_obj"] is q0["x_obj"] for q in qs):
+        Xb, strideX = q0["X"], 0
+    else:
+        Xb = np.stack([q["X"].reshape(-1, order="A") for q in qs])
+        strideX = Xb.shape[1]
+    sb = np.stack([q["s"].reshape(-1, order="A") for q in qs])
+    mwb = np.stack([q["mw"] for q in qs]) if want_mean else None
+    Lb = np.stack([q["Lw"].reshape(-1, order="A") for q in qs])
+    mb = np.empty((nb, N), dtype=dt) if want_mean else None
+    Cb = np.empty((nb, N * N), dtype=dt)
+    info = np.zeros(nb, dtype=np.int32)
+    _handle().mean_and_cov_batched(dt, _abi.MEM_HOST, q0["layout"], nb, D, N, Xb, q0["ldx"], strideX, q0["noise_kind"], sb, N, sb.shape[1],
+                                   q0["prior_kind"], mwb, D, Lb, q0["ldl"], Lb.shape[1], mb, N, Cb, N, N * N, info)
+    bad = np.flatnonzero(info > 0)
+    if bad.size:
+        e = _abi.PosDefException(int(info[bad[0]]))
+        e.index = int(bad[0])
+        raise e
+    return [(mb[b] if want_mean else None, Cb[b].reshape((N, N), order="F")) for b in range(nb)]
+
+
+def cov_map(fxs):
+    """``[cov(fx) for fx in fxs]`` in one library call (blr_mean_and_cov_batched_*) when the problems agree in D, N, dtype, layout,
+    noise kind and prior kind; a shared input object is read once.  The first problem whose prior is not positive definite raises
+    PosDefException; its position is the exception's ``index``."""
+    return [c for _, c in _cov_many(fxs, False)]
+
+
+def mean_and_cov_map(fxs):
+    """``[mean_and_cov(fx) for fx in fxs]`` in one library call (reference :45 under a map); see cov_map."""
+    return _cov_many(fxs, True)
 
 
 def _randn(rng, rows, cols, dtype):

@@ -365,6 +365,58 @@ int blr_marginals_multi_batched_f32(blr_handle* h, int memspace, int layout, int
                                     float* var, int64_t stridevar,
                                     int32_t* info);
 
+/* ---- joint predictive covariance of a batch of regressors: mean and the full N x N covariance per regressor ------------------------
+ * Replaces: reference src/bayesian_linear_regression.jl:33 (mean), :35-38 (cov) and :45 (mean_and_cov) under a map over fxs -- until
+ * now a loop of blr_mean_and_cov_* calls: one regressor per call, a drain of the stream per call, D and N padded to 128 on the
+ * large-D tall-matrix route, temporaries allocated and freed per call.
+ * Regressor b reads X + b*strideX, s + b*strides, mw + b*stridemw and Lw + b*strideLw; a stride of 0 shares an input (strideX = 0 --
+ * one candidate set for all regressors -- and strideLw = 0 included).
+ *   mean[b*stridemean + n] = x_n' mw_b                                                        (:33)
+ *   C + b*strideC          = X_b' Lw_b^-1 X_b + Sigma_y, the FULL symmetric N x N matrix, column-major, ldc >= N   (:35-38, :45)
+ * mean may be NULL (mw may then be NULL); C may be NULL -- a mean-only call: s and Lw are then not read and every status is 0.
+ * Noise: ISOTROPIC (s is one variance), DIAGONAL (s[N]) or DENSE (N x N, lds >= N, upper triangle read, as blr_mean_and_cov_*
+ * takes it; lds is ignored for the other kinds).  All three prior kinds, both layouts of X with any ldx, both memspaces.
+ * info[B]: 0, or k > 0 for a dense Lw_b that is not positive definite at leading minor k, or k > 0 for the first non-positive
+ * diagonal entry k of an upper factor or a diagonal prior (the rule of blr_rand_batched_*); the outputs of that regressor are then
+ * left untouched and the call still returns 0.  Argument errors are the negative position of the offending argument and are
+ * checked before the handle (a NULL handle with valid arguments returns -1); outputs that overlap for B > 1 are argument errors:
+ * stridemean < N, strideC < ldc*N.  No-ops returning 0: B = 0, N = 0, mean and C both NULL.  Limits: 1 <= D <= 8192, N <= 16384
+ * (the bound of blr_mean_and_cov_*).
+ * D <= 128 (csrc/blr_cov_batched.hpp): once per call a dense prior's factor per regressor and every status; then per
+ * chunk of regressors the triangular inverse of every factor (the image kernel of blr_marginals_batched_*), ONE launch of
+ * cov_whiten_kernel (groups of 64-input tiles, regressors: X is read once, z_n = U^-T x_n is formed once per input and kept as a row
+ * of 16 ceil(D/16) elements in the handle's workspace, the mean comes from the same tile) and ONE launch of cov_tiles_kernel (tile
+ * pairs i <= j, regressors: the 64 x 64 block Z_i Z_j' on the matrix cores, k = d ascending, + Sigma_y, stored as block (i, j) and as
+ * its transpose).  The launch count depends on B only through the chunks.  A chunk holds at most 65535 regressors (grid.y), at most
+ * 256 MiB of images (factor priors) and at most 256 MiB of Z rows, but never fewer than one regressor (16 MiB of Z at D = 128,
+ * N = 16384 in fp64); handle option MAX_CHUNK caps it further and blr_get_stat "last_chunks" reports the count.  The workspace is the
+ * handle's: counted by "workspace_bytes", freed by blr_release_workspace.  An async handle in device memspace only enqueues.
+ * D > 128: correct, not fast -- one regressor after the other through the launches of blr_mean_and_cov_* into a staging matrix that
+ * is copied to C only when the regressor's status is 0; the call synchronises per regressor whatever the handle's async flag says.
+ * Numerics: against the fp64 reference on well-conditioned priors rtol 1e-9 / atol 1e-10 in fp64, rtol = atol = 2e-4 in fp32.
+ * Promised: results are bit-reproducible from call to call; the bits of regressor b do not depend on B, on its position in the
+ * batch, on the chunking or on the other regressors' data; host and device memspace give the same bits; C is exactly symmetric
+ * (C[m, n] and C[n, m] carry the same bits: both are stored from one accumulator); the bits of C do not depend on whether mean is
+ * requested.  No float atomics, every sum in a fixed order.  NOT promised: bit-equality with blr_mean_and_cov_* or with var of
+ * blr_marginals_batched_* (the products run in a different order).
+ * _f32: X, s, mw, Lw, mean, C are float. */
+int blr_mean_and_cov_batched_f64(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t N,
+                                 const double* X, int64_t ldx, int64_t strideX,
+                                 int noise_kind, const double* s, int64_t lds, int64_t strides,
+                                 int prior_kind, const double* mw, int64_t stridemw,
+                                 const double* Lw, int64_t ldl, int64_t strideLw,
+                                 double* mean, int64_t stridemean,
+                                 double* C, int64_t ldc, int64_t strideC,
+                                 int32_t* info);
+int blr_mean_and_cov_batched_f32(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t N,
+                                 const float* X, int64_t ldx, int64_t strideX,
+                                 int noise_kind, const float* s, int64_t lds, int64_t strides,
+                                 int prior_kind, const float* mw, int64_t stridemw,
+                                 const float* Lw, int64_t ldl, int64_t strideLw,
+                                 float* mean, int64_t stridemean,
+                                 float* C, int64_t ldc, int64_t strideC,
+                                 int32_t* info);
+
 /* ---- draws: replaces rand (:49-53) and the weight draws of sampling_functions.jl:29,35,44 ------
  * The host keeps drawing the normals so its RNG stream is the reference's:
  *   Z1 = randn(rng, D, S) FIRST, then Z2 = randn(rng, N, S).

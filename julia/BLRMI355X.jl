@@ -541,6 +541,28 @@ function mean_and_cov(fx::FiniteGP; want_mean::Bool=true)
 end
 cov(fx::FiniteGP) = mean_and_cov(fx; want_mean=false)[2]
 
+# blr_mean_and_cov_batched_* (include/blr_mi355x.h): mean[B][N] (may be C_NULL) and the full N x N covariance per regressor (C, ldc,
+# strideC; may be C_NULL) for B regressors in one call, :33 / :35-38 / :45 under a map.  A stride of 0 shares an input (strideX = 0: one
+# candidate set).  The arrays are host Arrays (MEM_HOST) or raw device pointers; one status per regressor lands in info.
+function mean_and_cov_batched!(h, ::Type{T}, memspace, layout, B, D, N, X, ldx, strideX, nk, s, lds, strides, pk, mw, stridemw,
+                               Lw, ldl, strideLw, m, stridemean, C, ldc, strideC, info) where {T<:Elt}
+    GC.@preserve X s mw Lw m C info begin
+        if T === Float64
+            ccall((:blr_mean_and_cov_batched_f64, LIB), Cint,
+                  (Ptr{Cvoid}, Cint, Cint, Int64, Int64, Int64, Ptr{T}, Int64, Int64, Cint, Ptr{T}, Int64, Int64, Cint, Ptr{T}, Int64,
+                   Ptr{T}, Int64, Int64, Ptr{T}, Int64, Ptr{T}, Int64, Int64, Ptr{Int32}),
+                  h, memspace, layout, B, D, N, X, ldx, strideX, nk, s, lds, strides, pk, mw, stridemw,
+                  Lw, ldl, strideLw, m, stridemean, C, ldc, strideC, info)
+        else
+            ccall((:blr_mean_and_cov_batched_f32, LIB), Cint,
+                  (Ptr{Cvoid}, Cint, Cint, Int64, Int64, Int64, Ptr{T}, Int64, Int64, Cint, Ptr{T}, Int64, Int64, Cint, Ptr{T}, Int64,
+                   Ptr{T}, Int64, Int64, Ptr{T}, Int64, Ptr{T}, Int64, Int64, Ptr{Int32}),
+                  h, memspace, layout, B, D, N, X, ldx, strideX, nk, s, lds, strides, pk, mw, stridemw,
+                  Lw, ldl, strideLw, m, stridemean, C, ldc, strideC, info)
+        end
+    end
+end
+
 # ---- draws: reference :49-53 -- the RNG stream stays Julia's: Z1 = randn(rng, D, S) FIRST, then Z2 -------------
 function rand(rng::AbstractRNG, fx::FiniteGP, samples::Int)
     fb = to_blr(fx)
