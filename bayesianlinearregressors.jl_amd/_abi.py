@@ -115,6 +115,9 @@ for _suf in ("f64", "f32"):
     _SIGS[f"blr_rand_batched_{_suf}"] = (
         [_H, _int, _int, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _int, _vp, _i64, _int, _vp, _i64, _vp, _i64, _i64,
          _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp], _int)
+    _SIGS[f"blr_rand_multi_batched_{_suf}"] = (
+        [_H, _int, _int, _i64, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _int, _vp, _i64, _int, _vp, _i64, _i64, _vp, _i64, _i64,
+         _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp], _int)
     _SIGS[f"blr_apply_weights_{_suf}"] = ([_H, _int, _int, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64], _int)
     _SIGS[f"blr_sample_weights_{_suf}"] = (
         [_H, _int, _i64, _i64, _int, _vp, _vp, _i64, _vp, _i64, _vp, _i64], _int)
@@ -464,6 +467,15 @@ class Handle:
         fn = getattr(self.lib, f"blr_rand_batched_{suffix(dtype)}")
         return self.check(fn(self._h, memspace, layout, B, D, N, S, _ptr(X), ldx, strideX, noise_kind, _ptr(s), strides, prior_kind,
                              _ptr(mw), stridemw, _ptr(Lw), ldl, strideLw, _ptr(Z1), ldz1, strideZ1, _ptr(Z2), ldz2, strideZ2,
+                             _ptr(W), ldw, strideW, _ptr(Y), ldy, strideY, _ptr(info)))
+
+    def rand_multi_batched(self, dtype, memspace, layout, B, D, N, S, R, X, ldx, strideX, noise_kind, s, strides, prior_kind, M, ldm,
+                           strideM, Lw, ldl, strideLw, Z1, ldz1, strideZ1, Z2, ldz2, strideZ2, W, ldw, strideW, Y, ldy, strideY, info):
+        """R draws from each of the S column posteriors (M: D x S per regressor, one shared factor) of B regressors in one call, draw
+        j = c R + r; include/blr_mi355x.h blr_rand_multi_batched_* (per-regressor status in info)."""
+        fn = getattr(self.lib, f"blr_rand_multi_batched_{suffix(dtype)}")
+        return self.check(fn(self._h, memspace, layout, B, D, N, S, R, _ptr(X), ldx, strideX, noise_kind, _ptr(s), strides, prior_kind,
+                             _ptr(M), ldm, strideM, _ptr(Lw), ldl, strideLw, _ptr(Z1), ldz1, strideZ1, _ptr(Z2), ldz2, strideZ2,
                              _ptr(W), ldw, strideW, _ptr(Y), ldy, strideY, _ptr(info)))
 
     def apply_weights(self, dtype, memspace, layout, D, N, S, X, ldx, W, ldw, Y, ldy):

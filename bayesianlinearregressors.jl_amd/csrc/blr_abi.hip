@@ -37,6 +37,7 @@
 #include "blr_cov_batched.hpp"
 #include "blr_loo_multi.hpp"
 #include "blr_state_cols.hpp"
+#include "blr_rand_multi.hpp"
 #include "blr_host.hpp"
 #include "blr_large_plan.hpp"
 
@@ -2285,6 +2286,130 @@ int rand_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, 
   return io.finish();
 }
 
+// ---- draws from a batched multi-output state: S column posteriors per regressor share one factor, R draws each
+// (blr_rand_multi_batched_*; blr_rand_multi.hpp) ---------------------------------------------------------------------
+// D <= 128: [one batched Cholesky of a dense prior] + per chunk of regressors rand_cols_solve_kernel (status, factor in LDS, 16 draw
+// columns per pass) + rand_cols_project_kernel (X read once whatever S R is): the launch count depends on B only through the chunks.
+// D > 128: column by column through rand_batched (correct, not fast; synchronises).
+template <typename T>
+int rand_multi_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t N, int64_t S, int64_t R, const T* X,
+                       int64_t ldx, int64_t strideX, int noise_kind, const T* s, int64_t strides, int prior_kind, const T* M, int64_t ldm,
+                       int64_t strideM, const T* Lw, int64_t ldl, int64_t strideLw, const T* Z1, int64_t ldz1, int64_t strideZ1,
+                       const T* Z2, int64_t ldz2, int64_t strideZ2, T* W, int64_t ldw, int64_t strideW, T* Y, int64_t ldy,
+                       int64_t strideY, int32_t* info) {
+  // (the argument checks come before the handle's: they need no device)
+  if (h) h->err.clear();
+  if (memspace != BLR_MEM_HOST && memspace != BLR_MEM_DEVICE) return bad_arg(h, 2, "memspace");
+  if (layout != BLR_LAYOUT_COLVECS && layout != BLR_LAYOUT_ROWVECS) return bad_arg(h, 3, "unknown layout (reference :26-31)");
+  if (B < 0 || B > (1 << 30)) return bad_arg(h, 4, "B out of range (0..2^30)");
+  if (D < 1 || D > kMaxLargeD) return bad_arg(h, 5, "D out of range (1..8192)");
+  if (N < 0 || N > (1 << 30)) return bad_arg(h, 6, "N out of range");
+  if (S < 0 || S > (1 << 20)) return bad_arg(h, 7, "S out of range (0..2^20)");
+  if (R < 0 || R > (1 << 20) || S * R > (1 << 20)) return bad_arg(h, 8, "R out of range (S*R <= 2^20)");
+  const int64_t SR = S * R;
+  const bool proj = Y && N > 0;   // Y = NULL: weights only
+  const bool noisy = proj && Z2;  // Z2 = NULL: noise-free function values, noise_kind and s ignored
+  if (proj && !X) return bad_arg(h, 9, "X is NULL");
+  if (proj && (layout == BLR_LAYOUT_COLVECS ? ldx < D : ldx < N)) return bad_arg(h, 10, "ldx too small");
+  if (strideX < 0) return bad_arg(h, 11, "strideX < 0");
+  if (noisy && noise_kind != BLR_NOISE_ISOTROPIC && noise_kind != BLR_NOISE_DIAGONAL)
+    return bad_arg(h, 12, "noise_kind (isotropic or diagonal; dense Sigma_y is not supported for batched draws)");
+  if (noisy && !s) return bad_arg(h, 13, "s is NULL");
+  if (strides < 0) return bad_arg(h, 14, "strides < 0");
+  if (prior_kind != BLR_PRIOR_DENSE && prior_kind != BLR_PRIOR_UPPER_FACTOR && prior_kind != BLR_PRIOR_DIAGONAL)
+    return bad_arg(h, 15, "prior_kind");
+  if (!M) return bad_arg(h, 16, "M is NULL");
+  if (ldm < D) return bad_arg(h, 17, "ldm < D");
+  if (strideM < 0) return bad_arg(h, 18, "strideM < 0");
+  if (!Lw) return bad_arg(h, 19, "Lw is NULL");
+  if (prior_kind != BLR_PRIOR_DIAGONAL && ldl < D) return bad_arg(h, 20, "ldl < D");
+  if (strideLw < 0) return bad_arg(h, 21, "strideLw < 0");
+  if (!Z1) return bad_arg(h, 22, "Z1 is NULL");
+  if (ldz1 < D) return bad_arg(h, 23, "ldz1 < D");
+  if (strideZ1 < 0) return bad_arg(h, 24, "strideZ1 < 0");
+  if (noisy && ldz2 < N) return bad_arg(h, 26, "ldz2 < N");
+  if (strideZ2 < 0) return bad_arg(h, 27, "strideZ2 < 0");
+  if (W && ldw < D) return bad_arg(h, 29, "ldw < D");
+  if (W && B > 1 && strideW < ldw * SR) return bad_arg(h, 30, "strideW < ldw * S * R: the outputs of two regressors overlap");
+  if (Y && ldy < N) return bad_arg(h, 32, "ldy < N");
+  if (Y && B > 1 && strideY < ldy * SR) return bad_arg(h, 33, "strideY < ldy * S * R: the outputs of two regressors overlap");
+  if (!info) return bad_arg(h, 34, "info is NULL");
+  if (!h) return -1;
+  h->last_chunks = 1;  // (a route with a chunk loop counts its own)
+  if (B == 0 || SR == 0 || (!W && !Y)) return 0;
+  HIP_TRY(h, hipSetDevice(h->device));
+
+  CallIO io(h, memspace);
+  const T *X_d = nullptr, *s_d = nullptr, *M_d = nullptr, *Lw_d = nullptr, *Z1_d = nullptr, *Z2_d = nullptr;
+  T *W_d = nullptr, *Y_d = nullptr;
+  int32_t* info_d = nullptr;
+  int rc;
+  const size_t x_one = layout == BLR_LAYOUT_COLVECS ? mat_extent(D, N, ldx) : mat_extent(N, D, ldx);
+  const size_t lw_one = prior_kind == BLR_PRIOR_DIAGONAL ? (size_t)D : mat_extent(D, D, ldl);
+  // (X without a projection and s without noise are not staged: a count of 0)
+  if ((rc = io.in(X, proj ? extent(B, strideX, x_one) : 0, &X_d))) return rc;
+  if ((rc = io.in(s, noisy ? extent(B, strides, noise_kind == BLR_NOISE_DIAGONAL ? (size_t)N : 1) : 0, &s_d))) return rc;
+  if ((rc = io.in(M, extent(B, strideM, mat_extent(D, S, ldm)), &M_d))) return rc;
+  if ((rc = io.in(Lw, extent(B, strideLw, lw_one), &Lw_d))) return rc;
+  if ((rc = io.in(Z1, extent(B, strideZ1, mat_extent(D, SR, ldz1)), &Z1_d))) return rc;
+  if ((rc = io.in(noisy ? Z2 : (const T*)nullptr, extent(B, strideZ2, mat_extent(N, SR, ldz2)), &Z2_d))) return rc;
+  if ((rc = io.out(W, extent(B, strideW, mat_extent(D, SR, ldw)), &W_d))) return rc;
+  if ((rc = io.out(proj ? Y : (T*)nullptr, extent(B, strideY, mat_extent(N, SR, ldy)), &Y_d))) return rc;
+  if ((rc = io.out(info, (size_t)B, &info_d))) return rc;
+
+  if (D > kMaxSmallD) {
+    // correct, not fast: the R draws of column c are one call of the single-column route with mw = M[:, c]; every such call forms the
+    // same status (a failed regressor's outputs stay untouched in each of them); the route synchronises
+    const AsyncScope drain(h, false);
+    for (int64_t c = 0; c < S; ++c) {
+      rc = rand_batched<T>(h, BLR_MEM_DEVICE, layout, B, D, N, R, X_d, ldx, strideX, noise_kind, s_d, strides, prior_kind, M_d + c * ldm,
+                           strideM, Lw_d, ldl, strideLw, Z1_d + c * R * ldz1, ldz1, strideZ1, Z2_d ? Z2_d + c * R * ldz2 : (const T*)nullptr,
+                           ldz2, strideZ2, W_d ? W_d + c * R * ldw : (T*)nullptr, ldw, strideW, Y_d ? Y_d + c * R * ldy : (T*)nullptr, ldy,
+                           strideY, info_d);
+      if (rc) return rc;  // (device pointers and in-range sizes: a HIP failure, not an argument index of the inner call)
+    }
+    h->last_chunks = 1;
+    return io.finish();
+  }
+
+  RandColsArgs<T> a{};
+  a.noise_kind = noise_kind; a.D = (int)D; a.N = (int)N; a.R = (int)R; a.SR = (int)SR;
+  a.ldx = ldx; a.strideX = strideX; a.strides = strides; a.ldm = ldm; a.strideM = strideM;
+  a.ldz1 = ldz1; a.strideZ1 = strideZ1; a.ldz2 = ldz2; a.strideZ2 = strideZ2;
+  a.ldw = ldw; a.strideW = strideW; a.ldy = ldy; a.strideY = strideY;
+  int kind = prior_kind;
+  int32_t* chol_info = nullptr;
+  if ((rc = prior_factor<T>(h, B, D, prior_kind, Lw_d, ldl, strideLw, &a.U, &a.ldu, &a.strideU, &kind, &chol_info))) return rc;
+  a.prior_kind = kind;
+  a.chol_info = chol_info;
+  // regressors per launch: grid.y, and the fragment images of the weights within 256 MiB (at least one regressor)
+  const size_t img_one = rand_cols_image_elems((int)D, SR);
+  int64_t chunk = std::min<int64_t>(B, 65535);
+  if (proj) chunk = std::min<int64_t>(chunk, std::max<int64_t>(1, (int64_t)(((size_t)256 << 20) / (img_one * sizeof(T)))));
+  chunk = h->cap_chunk(chunk);
+  h->count_chunks(B, chunk);
+  const size_t lds_s = rand_cols_solve_lds_bytes(sizeof(T), (int)D, kind == BLR_PRIOR_DIAGONAL);
+  const size_t lds_p = rand_cols_project_lds_bytes(sizeof(T), (int)D);
+  void (*const project)(RandColsArgs<T>) = layout == BLR_LAYOUT_ROWVECS ? rand_cols_project_kernel<T, LAYOUT_ROWVECS> : rand_cols_project_kernel<T, LAYOUT_COLVECS>;
+  if (lds_s && (rc = set_lds_once(h, rand_cols_solve_kernel<T>, lds_s))) return rc;
+  if (proj && (rc = set_lds_once(h, project, lds_p))) return rc;
+  if (proj && (rc = h->aux.reserve(h, (size_t)chunk * img_one * sizeof(T)))) return rc;
+  const int64_t passes = (SR + kRandColsPerPass - 1) / kRandColsPerPass;
+  const int64_t ntiles = (N + kMargTile - 1) / kMargTile;
+  for (int64_t b0 = 0; b0 < B; b0 += chunk) {
+    const int64_t nb = std::min<int64_t>(chunk, B - b0);
+    // every workgroup of the projection amortises its set-up over its tiles: about two workgroups per CU in all
+    const int64_t ngroups = std::max<int64_t>(1, std::min<int64_t>(ntiles, (2 * (int64_t)h->cus + nb - 1) / nb));
+    a.X = X_d; a.s = s_d; a.M = M_d; a.Z1 = Z1_d; a.Z2 = Z2_d; a.W = W_d; a.Y = Y_d; a.info = info_d;
+    a.Wf = proj ? reinterpret_cast<T*>(h->aux.p) : nullptr;
+    a.ngroups = (int)ngroups; a.reg0 = (int)b0; a.nreg = (int)nb;
+    hipLaunchKernelGGL(rand_cols_solve_kernel<T>, dim3((unsigned)passes, (unsigned)nb), dim3(kThreads), lds_s, h->stream, a);
+    if (proj) hipLaunchKernelGGL(project, dim3((unsigned)(ngroups * nb)), dim3(kThreads), lds_p, h->stream, a);
+  }
+  HIP_TRY(h, hipGetLastError());
+  return io.finish();
+}
+
 
 template <typename T>
 int rff_features(blr_handle* h, int memspace, int64_t Din, int64_t D, int64_t N, const T* Xin, int64_t ldxin,
@@ -4380,6 +4505,17 @@ int blr_timer_stop(blr_handle* h, float* elapsed_ms) {
     return rand_batched<T>(h, memspace, layout, B, D, N, S, X, ldx, strideX, noise_kind, s, strides, prior_kind, mw, \
                            stridemw, Lw, ldl, strideLw, Z1, ldz1, strideZ1, Z2, ldz2, strideZ2, W, ldw, strideW, Y,  \
                            ldy, strideY, info);                                                                     \
+  }                                                                                                                 \
+  int blr_rand_multi_batched_##SUF(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t N,        \
+                                   int64_t S, int64_t R, const T* X, int64_t ldx, int64_t strideX, int noise_kind,  \
+                                   const T* s, int64_t strides, int prior_kind, const T* M, int64_t ldm,            \
+                                   int64_t strideM, const T* Lw, int64_t ldl, int64_t strideLw, const T* Z1,        \
+                                   int64_t ldz1, int64_t strideZ1, const T* Z2, int64_t ldz2, int64_t strideZ2,     \
+                                   T* W, int64_t ldw, int64_t strideW, T* Y, int64_t ldy, int64_t strideY,          \
+                                   int32_t* info) {                                                                 \
+    return rand_multi_batched<T>(h, memspace, layout, B, D, N, S, R, X, ldx, strideX, noise_kind, s, strides,       \
+                                 prior_kind, M, ldm, strideM, Lw, ldl, strideLw, Z1, ldz1, strideZ1, Z2, ldz2,      \
+                                 strideZ2, W, ldw, strideW, Y, ldy, strideY, info);                                 \
   }                                                                                                                 \
   int blr_rff_features_##SUF(blr_handle* h, int memspace, int64_t Din, int64_t D, int64_t N, const T* Xin,          \
                              int64_t ldxin, const T* Omega, int64_t ldo, const T* phase, T scale, T* Phi,           \

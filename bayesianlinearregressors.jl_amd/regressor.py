@@ -32,6 +32,7 @@ __all__ = [
     "posterior_columns", "logpdf_columns_map", "posterior_columns_map",
     "mean_and_var_columns", "mean_columns", "mean_and_var_columns_map",
     "cov_map", "mean_and_cov_map",
+    "rand_columns", "rand_columns_map",
 ]
 
 
@@ -1741,6 +1742,47 @@ class ResidentColumnsPosterior:
         (blr_mean_and_cov_batched_* with mean = NULL on device pointers to the shared factor)."""
         return self._col0._cov(x, Sy, False)[1]
 
+    def rand(self, rng, x, R, Sy=None):
+        """R draws at the inputs x from each of the S resident columns: an (N, S, R) Fortran-ordered array, without copying T to
+        the host (blr_rand_multi_batched_* on device pointers to the resident state, B = 1).  With Sy, ``[:, c, :]`` is
+        ``rand(rng, st.regressors()[c](x, Sy), R)`` with the normals drawn column by column in the reference's order (:49-53: Z1_c,
+        then Z2_c, for c = 0 .. S-1); without it the noise-free function values of sampling_functions.jl:16-18, 27-38 (Z1_c only)."""
+        dtype, h, D, S, R = self.dtype, self._h, self.D, self.S, int(R)
+        temps = []
+
+        def dev(a):
+            temps.append(_DeviceBuffer.of(h, a))
+            return temps[-1].ptr
+
+        try:
+            dX, layout, ldx, N = self._col0._inputs(x, dev, temps)
+            s, noise_kind = (np.ones(1, dtype=dtype), _abi.NOISE_ISOTROPIC) if Sy is None else _noise(Sy, N, dtype, need_cholesky=True)
+            if noise_kind == _abi.NOISE_DENSE:
+                raise NotImplementedError("ResidentColumnsPosterior.rand takes scalar or diagonal noise")
+            Z1 = np.empty((D, S * R), dtype=dtype, order="F")
+            Z2 = np.empty((N, S * R), dtype=dtype, order="F") if Sy is not None else None
+            for c in range(S):
+                Z1[:, c * R:(c + 1) * R] = _randn(rng, D, R, dtype)
+                if Z2 is not None:
+                    Z2[:, c * R:(c + 1) * R] = _randn(rng, N, R, dtype)
+            Y = np.empty((N, S * R), dtype=dtype, order="F")  # draw j = c R + r
+            if N and R:
+                temps.append(_DeviceBuffer(h, Y.nbytes))
+                dY = temps[-1].ptr
+                d_info = dev(np.zeros(1, dtype=np.int32))
+                h.rand_multi_batched(dtype, _abi.MEM_DEVICE, layout, 1, D, N, S, R, dX, ldx, 0, noise_kind, dev(s), 0,
+                                     _abi.PRIOR_UPPER_FACTOR, self._M.ptr, max(D, 1), 0, self._T.ptr, max(D, 1), 0, dev(Z1), D, 0,
+                                     dev(Z2) if Z2 is not None else None, N, 0, None, D, 0, dY, N, 0, d_info)
+                info = np.zeros(1, dtype=np.int32)
+                h.memcpy_d2h(info, d_info)
+                if info[0] != 0:
+                    raise _abi.PosDefException(int(info[0]))
+                h.memcpy_d2h(Y, dY)
+            return np.asfortranarray(Y.reshape((N, R, S), order="F").transpose(0, 2, 1))
+        finally:
+            for b in temps:
+                b.free()
+
     def state(self):
         """host copies (M, T) of the resident state: M D x S, T column-major upper"""
         M = np.empty((self.D, self.S), dtype=self.dtype, order="F")
@@ -2208,3 +2250,119 @@ def rand_map(rng, fs, S):
             arr[i] = BLRFunctionSample(W[:, i].copy(), phi)
         out.append(arr)
     return out
+
+
+# ---------------------------------------------------------------------------------------------------
+# draws from the S column posteriors of a matrix target in ONE library call (blr_rand_multi_batched_*): the columns share one
+# factor, so it is read once and X is projected once for all S R draws
+# ---------------------------------------------------------------------------------------------------
+def _draw_columns_problem(rng, fxs, R):
+    """The S columns of one matrix target -> dict(qs = their draw problems, normals taken from rng in the reference's order: per
+    column Z1_c, then Z2_c for a FiniteGP; joint = they can share one call: one precision object, one basis and, for FiniteGPs, one
+    x object and equal isotropic / diagonal noise)."""
+    fxs = list(fxs)
+    if not fxs:
+        raise ValueError("at least one column is needed")
+    finite = isinstance(fxs[0], FiniteGP)
+    if any(isinstance(f, FiniteGP) != finite for f in fxs):
+        raise TypeError("rand_columns takes the FiniteGPs or the regressors of one matrix target, not a mixture")
+    qs = [_draw_problem(rng, f, R, finite) for f in fxs]
+    pairs = [_blr_and_mapping(f.f if finite else f) for f in fxs]
+    q0, (blr0, phi0) = qs[0], pairs[0]
+    joint = all(b.Lw is blr0.Lw and ph is phi0 for b, ph in pairs) and all(q["dtype"] == q0["dtype"] for q in qs)
+    if joint and finite:
+        joint = (q0["noise_kind"] != _abi.NOISE_DENSE and q0["N"] > 0 and all(f.x is fxs[0].x for f in fxs)
+                 and all(q["noise_kind"] == q0["noise_kind"] and np.array_equal(q["s"], q0["s"]) for q in qs))
+    return dict(qs=qs, joint=joint, finite=finite, phi=phi0, x_src=fxs[0].x if finite else None, phis=[ph for _, ph in pairs])
+
+
+def _draw_columns_call(probs, R):
+    """Equally shaped joint problems through ONE blr_rand_multi_batched_* call -> per problem the list of S arrays (N x R draws of a
+    FiniteGP, D x R weights of a regressor).  Inputs that are one object (and one basis) for every problem are passed once."""
+    q0, finite = probs[0]["qs"][0], probs[0]["finite"]
+    dt, D, N, nb, S = q0["dtype"], q0["D"], q0["N"], len(probs), len(probs[0]["qs"])
+    Mb = np.stack([np.stack([q["mw"] for q in p["qs"]], axis=1).reshape(-1, order="F") for p in probs])  # D x S column-major, ldm = D
+    Lb = np.stack([p["qs"][0]["Lw"].reshape(-1, order="A") for p in probs])
+    Z1b = np.stack([np.concatenate([q["Z1"].reshape(-1, order="F") for q in p["qs"]]) for p in probs])  # D x S R, draw j = c R + r
+    info = np.zeros(nb, dtype=np.int32)
+    if finite:
+        if all(p["x_src"] is probs[0]["x_src"] and p["phi"] is probs[0]["phi"] for p in probs):
+            Xb, strideX = q0["X"], 0
+        else:
+            Xb = np.stack([p["qs"][0]["X"].reshape(-1, order="A") for p in probs])
+            strideX = Xb.shape[1]
+        sb = np.stack([p["qs"][0]["s"] for p in probs])
+        Z2b = np.stack([np.concatenate([q["Z2"].reshape(-1, order="F") for q in p["qs"]]) for p in probs])
+        out, rows = np.empty((nb, N * S * R), dtype=dt), N
+        _handle().rand_multi_batched(dt, _abi.MEM_HOST, q0["layout"], nb, D, N, S, R, Xb, q0["ldx"], strideX, q0["noise_kind"], sb,
+                                     sb.shape[1], q0["prior_kind"], Mb, D, D * S, Lb, q0["ldl"], Lb.shape[1], Z1b, D, D * S * R,
+                                     Z2b, N, N * S * R, None, D, D * S * R, out, N, N * S * R, info)
+    else:
+        out, rows = np.empty((nb, D * S * R), dtype=dt), D
+        _handle().rand_multi_batched(dt, _abi.MEM_HOST, _abi.LAYOUT_COLVECS, nb, D, 0, S, R, None, D, 0, _abi.NOISE_ISOTROPIC, None, 0,
+                                     q0["prior_kind"], Mb, D, D * S, Lb, q0["ldl"], Lb.shape[1], Z1b, D, D * S * R, None, 1, 0,
+                                     out, D, D * S * R, None, 1, 0, info)
+    bad = np.flatnonzero(info > 0)
+    if bad.size:
+        e = _abi.PosDefException(int(info[bad[0]]))
+        e.index = int(bad[0])
+        raise e
+    return [[out[b].reshape((rows, S * R), order="F")[:, c * R:(c + 1) * R] for c in range(S)] for b in range(nb)]
+
+
+def _draw_columns_wrap(p, arrays, R):
+    """FiniteGPs: the N x R arrays themselves; regressors: arrays of R BLRFunctionSamples, as rand_map returns them."""
+    if p["finite"]:
+        return [np.asfortranarray(a) for a in arrays]
+    out = []
+    for W, phi in zip(arrays, p["phis"]):
+        arr = np.empty(R, dtype=object)
+        for i in range(R):
+            arr[i] = BLRFunctionSample(W[:, i].copy(), phi)
+        out.append(arr)
+    return out
+
+
+def rand_columns_map(rng, fxss, R):
+    """``[[rand(rng, fx, R) for fx in fxs] for fxs in fxss]`` for lists of the S columns of matrix targets (FiniteGPs, e.g.
+    ``[p(x, Sy) for p in posterior_columns(...)]``, or regressors), with the normals drawn from rng in exactly that order.  Problems
+    whose columns share one precision object (and, for FiniteGPs, one x object and equal noise) and that have one shape go through
+    ONE blr_rand_multi_batched_* call (the grouping of rand_map); otherwise problem by problem, a problem with mixed columns through
+    the route of rand_map.  The first problem whose prior (or noise) is not positive definite raises PosDefException; its position
+    is the exception's ``index``."""
+    fxss, R = [list(fxs) for fxs in fxss], int(R)
+    if not fxss:
+        return []
+    probs = []
+    for b, fxs in enumerate(fxss):
+        try:
+            probs.append(_draw_columns_problem(rng, fxs, R))
+        except _abi.PosDefException as e:
+            e.index = b
+            raise
+    sig = {(p["finite"], len(p["qs"])) + tuple((q["dtype"], None if q["X"] is None else (q["X"].shape, q["X"].flags.f_contiguous),
+                                                 q["layout"], q["D"], q["N"], q["noise_kind"], q["prior_kind"],
+                                                 None if q["s"] is None else q["s"].shape) for q in p["qs"][:1]) for p in probs}
+    if len(sig) == 1 and all(p["joint"] for p in probs):
+        return [_draw_columns_wrap(p, arrays, R) for p, arrays in zip(probs, _draw_columns_call(probs, R))]
+    out = []
+    for b, p in enumerate(probs):
+        try:
+            arrays = _draw_columns_call([p], R)[0] if p["joint"] else _draw_many(p["qs"], R)
+        except _abi.PosDefException as e:
+            e.index = b
+            raise
+        out.append(_draw_columns_wrap(p, arrays, R))
+    return out
+
+
+def rand_columns(rng, fxs, R):
+    """``[rand(rng, fx, R) for fx in fxs]`` for the S columns of ONE matrix target -- FiniteGPs, e.g.
+    ``[p(x, Sy) for p in posterior_columns(...)]``, or the regressors themselves (arrays of BLRFunctionSamples) -- with the same RNG
+    order (per column Z1_c, then Z2_c).  One blr_rand_multi_batched_* call when the columns share one precision object and, for
+    FiniteGPs, one x object and equal noise: the factor is read once and X is projected once for all S R draws.  Otherwise the route
+    of rand_map."""
+    R = int(R)
+    p = _draw_columns_problem(rng, fxs, R)
+    arrays = _draw_columns_call([p], R)[0] if p["joint"] else _draw_many(p["qs"], R)
+    return _draw_columns_wrap(p, arrays, R)

@@ -486,6 +486,68 @@ int blr_rand_batched_f32(blr_handle* h, int memspace, int layout, int64_t B, int
                          float* Y, int64_t ldy, int64_t strideY,
                          int32_t* info);
 
+/* ---- draws from a batched multi-output state: S column posteriors per regressor share one factor, R draws per column ---------------
+ * Replaces: reference src/bayesian_linear_regression.jl:49-53 (rand) and src/sampling_functions.jl:16-49 (weight draws, function
+ * samples) under a map over fxs whose regressors come from matrix targets -- until now S calls of blr_rand_batched_* with mw stepped
+ * by a column: every call reads every factor again per (regressor, block of draws), reads X again and pays its own launches.
+ * Regressor b reads X + b*strideX, s + b*strides, M + b*strideM (D x S column-major, ldm >= D: exactly the mw_post block of
+ * blr_posterior_multi_batched_* and the M of the other multi entry points), Lw + b*strideLw, Z1 + b*strideZ1 (D x S*R, ldz1 >= D) and
+ * Z2 + b*strideZ2 (N x S*R, ldz2 >= N); a stride of 0 shares an input (strideX = 0, strideLw = 0 and strideM = 0 included).  Its S
+ * column posteriors are N(M_b[:, c], (U_b'U_b)^-1), U_b the upper factor of Lw_b under whichever prior kind.  R draws per column;
+ * draw j = c*R + r (0 <= c < S, 0 <= r < R: the R draws of a column are contiguous):
+ *   W[b*strideW + j*ldw + :] = M_b[:, c] + U_b \ Z1_b[:, j]                  (D x S*R, ldw >= D; :51)
+ *   Y[b*strideY + j*ldy + :] = X_b' W_b[:, j] + sqrt.(s_b) .* Z2_b[:, j]     (N x S*R, ldy >= N; :52-53)
+ * The host draws the normals, so its RNG stream stays the reference's (per column Z1_c FIRST, then Z2_c).
+ *   Z2 == NULL: noise-free function values Y = X'W (sampling_functions.jl:16-18); noise_kind and s are then ignored.
+ *   W == NULL: the weights are not returned.  Y == NULL: weights only (X may be NULL).  N == 0 is allowed.
+ * No-ops returning 0: B = 0, S = 0, R = 0, W and Y both NULL.  Isotropic or diagonal noise (dense noise: argument error), all three
+ * prior kinds, both layouts of X with any ldx, both memspaces.  s is not checked (as blr_rand_batched_*).
+ * info[B]: 0, or k > 0 for a dense Lw_b that is not positive definite at leading minor k, or k > 0 for the first non-positive
+ * diagonal entry k of an upper factor or a diagonal prior (the rule of blr_rand_batched_*); W and Y of that regressor are then left
+ * untouched and the call still returns 0.  Argument errors are the negative position of the offending argument and are checked
+ * before the handle (a NULL handle with valid arguments returns -1); ldm < D is -17; outputs that overlap for B > 1 are argument
+ * errors: strideW < ldw*S*R (-30), strideY < ldy*S*R (-33).  Limits: 1 <= D <= 8192, N <= 2^30, S*R <= 2^20.
+ * D <= 128 (csrc/blr_rand_multi.hpp): [one batched Cholesky of a dense prior], then per chunk of regressors ONE launch
+ * of rand_cols_solve_kernel (passes of 16 draw columns x regressors: the status, the factor once into LDS as a packed triangle, the
+ * back substitution of four columns per wave, + M[:, j / R]; W goes to the caller and, when Y is wanted, as matrix-core operand images
+ * of 16 ceil(D/16) x 16 elements per pass into the handle's workspace) and, when Y is wanted, ONE launch of rand_cols_project_kernel
+ * (groups of 64-input tiles x regressors, the regressor fastest when X is shared: a workgroup keeps its tile of X in LDS and loops
+ * over the passes, so X is read once whatever S*R is; + sqrt(s_n) Z2[n, j] at the store).  The launch count does not depend on S or
+ * R, and on B only through the chunks.  A chunk holds at most 65535 regressors (grid.y) and at most 256 MiB of operand images, but
+ * never fewer than one regressor (1 GiB of images at D = 128, S*R = 2^20 in fp64); handle option MAX_CHUNK caps it further and
+ * blr_get_stat "last_chunks" reports the count.  The workspace is the handle's: counted by "workspace_bytes", freed by
+ * blr_release_workspace.  An async handle in device memspace only enqueues.
+ * D > 128: correct, not fast -- column by column through the route of blr_rand_batched_* (mw = M + c*ldm; Z1, Z2, W, Y stepped by R
+ * columns); the call synchronises whatever the handle's async flag says.
+ * Numerics: against the fp64 reference on well-conditioned priors rtol 1e-10 / atol 1e-11 in fp64, 2e-4 max(1, max|ref|) in fp32.
+ * Promised: results repeat bit for bit from call to call; the bits of regressor b do not depend on B, on b's position, on the
+ * chunking or on the other regressors' data; the bits of draw (c, r) depend only on that regressor's X, s and factor and on M[:, c],
+ * Z1[:, j], Z2[:, j] -- not on S, on R, on j's position (pass and slot included) or on the other columns and draws; host and device
+ * memspace give the same bits; the bits of Y do not depend on whether W is requested.  No float atomics, every sum in a fixed order.
+ * NOT promised: bit-equality with blr_rand_batched_* (the solve multiplies by reciprocal pivots and the projection runs on the
+ * matrix cores).
+ * _f32: X, s, M, Lw, Z1, Z2, W, Y are float. */
+int blr_rand_multi_batched_f64(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t N, int64_t S, int64_t R,
+                               const double* X, int64_t ldx, int64_t strideX,
+                               int noise_kind, const double* s, int64_t strides,
+                               int prior_kind, const double* M, int64_t ldm, int64_t strideM,
+                               const double* Lw, int64_t ldl, int64_t strideLw,
+                               const double* Z1, int64_t ldz1, int64_t strideZ1,
+                               const double* Z2, int64_t ldz2, int64_t strideZ2,
+                               double* W, int64_t ldw, int64_t strideW,
+                               double* Y, int64_t ldy, int64_t strideY,
+                               int32_t* info);
+int blr_rand_multi_batched_f32(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t N, int64_t S, int64_t R,
+                               const float* X, int64_t ldx, int64_t strideX,
+                               int noise_kind, const float* s, int64_t strides,
+                               int prior_kind, const float* M, int64_t ldm, int64_t strideM,
+                               const float* Lw, int64_t ldl, int64_t strideLw,
+                               const float* Z1, int64_t ldz1, int64_t strideZ1,
+                               const float* Z2, int64_t ldz2, int64_t strideZ2,
+                               float* W, int64_t ldw, int64_t strideW,
+                               float* Y, int64_t ldy, int64_t strideY,
+                               int32_t* info);
+
 /* ---- random-Fourier basis (BASELINE config 5): phi(x) = scale * cos(Omega' x + phase) ---------------------
  * The reference's BasisFunctionRegressor takes any callable phi (src/basis_function_regression.jl:7-9,41) and ships
  * none; this is the feature map of config 5, applied on the device so Phi never crosses PCIe.

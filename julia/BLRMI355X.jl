@@ -1390,6 +1390,49 @@ function rand_batched!(Y::Union{Nothing,DeviceArray{T}}, W::Union{Nothing,Device
     return nothing
 end
 
+# blr_rand_multi_batched_* (include/blr_mi355x.h): R draws from each of the S column posteriors (M: D x S per regressor, one shared
+# factor) of B regressors, draw j = c R + r
+function rand_multi_batched_call(h, memspace, layout, B, D, N, S, R, X, ldx, strideX, nk, s, strides, pk, M, ldm, strideM, Lw, ldl, strideLw,
+                                 Z1, ldz1, strideZ1, Z2, ldz2, strideZ2, W, ldw, strideW, Y, ldy, strideY, info, ::Type{T}) where {T<:Elt}
+    if T === Float64
+        ccall((:blr_rand_multi_batched_f64, LIB), Cint,
+              (Ptr{Cvoid}, Cint, Cint, Int64, Int64, Int64, Int64, Int64, Ptr{T}, Int64, Int64, Cint, Ptr{T}, Int64, Cint, Ptr{T}, Int64, Int64,
+               Ptr{T}, Int64, Int64, Ptr{T}, Int64, Int64, Ptr{T}, Int64, Int64, Ptr{T}, Int64, Int64, Ptr{T}, Int64, Int64, Ptr{Int32}),
+              h, memspace, layout, B, D, N, S, R, X, ldx, strideX, nk, s, strides, pk, M, ldm, strideM, Lw, ldl, strideLw,
+              Z1, ldz1, strideZ1, Z2, ldz2, strideZ2, W, ldw, strideW, Y, ldy, strideY, info)
+    else
+        ccall((:blr_rand_multi_batched_f32, LIB), Cint,
+              (Ptr{Cvoid}, Cint, Cint, Int64, Int64, Int64, Int64, Int64, Ptr{T}, Int64, Int64, Cint, Ptr{T}, Int64, Cint, Ptr{T}, Int64, Int64,
+               Ptr{T}, Int64, Int64, Ptr{T}, Int64, Int64, Ptr{T}, Int64, Int64, Ptr{T}, Int64, Int64, Ptr{T}, Int64, Int64, Ptr{Int32}),
+              h, memspace, layout, B, D, N, S, R, X, ldx, strideX, nk, s, strides, pk, M, ldm, strideM, Lw, ldl, strideLw,
+              Z1, ldz1, strideZ1, Z2, ldz2, strideZ2, W, ldw, strideW, Y, ldy, strideY, info)
+    end
+end
+
+"""
+    rand_multi_batched!(Y, W, info, X, M, Tf, Z1, Z2; D, N, S, R, B, shared_x=false, s=nothing)
+
+R draws from each of the S column posteriors of B device-resident multi-output states (M D×S×B and Tf D×D×B exactly as
+`posterior_multi_batched!` / `update_multi_factor!` keep them), draw j = (c-1)R + r: W_b[:, j] = M_b[:, c] + T_b \\ Z1_b[:, j]
+(D×S·R) and Y_b = X_b' W_b (N×S·R), plus sqrt.(s) .* Z2_b when `s` (one variance, a `DeviceArray` of length 1) is given.  X is
+D×N×B, or one D×N candidate set for the whole batch (`shared_x`); Z1 D×S·R×B and Z2 N×S·R×B hold the normals (drawn on the host
+column by column, reference :51-52).  `Y`, `W` or `Z2` may be `nothing`.  info[b] > 0: that state's factor has a non-positive
+diagonal entry; its outputs are left untouched.  Reference semantics per column: `:49-53`, `sampling_functions.jl:16-49`.
+"""
+function rand_multi_batched!(Y::Union{Nothing,DeviceArray{T}}, W::Union{Nothing,DeviceArray{T}}, info::DeviceArray{Int32}, X::DeviceArray{T},
+                             M::DeviceArray{T}, Tf::DeviceArray{T}, Z1::DeviceArray{T}, Z2::Union{Nothing,DeviceArray{T}};
+                             D::Int, N::Int, S::Int, R::Int, B::Int, shared_x::Bool=false,
+                             s::Union{Nothing,DeviceArray{T}}=nothing) where {T<:Elt}
+    h = handle()
+    ptr(a) = a === nothing ? Ptr{T}(C_NULL) : a.ptr
+    noisy = Z2 !== nothing && s !== nothing
+    rc = rand_multi_batched_call(h, MEM_DEVICE, COLVECS, B, D, N, S, R, X.ptr, D, shared_x ? 0 : D * N, ISOTROPIC,
+                                 noisy ? s.ptr : Ptr{T}(C_NULL), 0, P_UPPER, M.ptr, D, D * S, Tf.ptr, D, D * D, Z1.ptr, D, D * S * R,
+                                 noisy ? Z2.ptr : Ptr{T}(C_NULL), N, N * S * R, ptr(W), D, D * S * R, ptr(Y), N, N * S * R, info.ptr, T)
+    check(h, rc)
+    return nothing
+end
+
 # ---- one Julia process per GPU: the path's single exchange through RCCL, called directly (SURVEY.md 8e) ------------------
 "rank 0: 128 opaque bytes to ship to the other ranks (Distributed.jl, a file, MPI ...)"
 function comm_unique_id()
