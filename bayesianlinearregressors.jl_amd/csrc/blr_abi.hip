@@ -667,6 +667,7 @@ inline int large_gram_planes(const LargeRun<float>& u) {
   ga.rowmax = u.rowmax;
   ga.xcd_swizzle = (p.nsplit > 1 && !h->opt.no_xcd_swizzle) ? 1 : 0;
   ga.grp_ws = u.wsb; ga.grp_s = a.strides;
+  ga.ll = (p.NP == 2 && (int64_t)a.N < (int64_t)kPlanesLlFactor * p.DP) ? 1 : 0;
   const dim3 grid(p.ntiles_g * p.nsplit, G);
   if (p.planes4) {
     if ((rc = set_lds_once(h, gram_planes4_kernel, (size_t)Planes4Cfg::LDS))) return rc;

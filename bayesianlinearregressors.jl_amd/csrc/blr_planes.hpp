@@ -17,7 +17,8 @@
 //     an absolute 2^-36 of the row's largest below that (fp16 subnormals) -- against fp32's 24 bits the inputs are perturbed by at most
 //     2^-23 of themselves, signed and zero-mean: over N observations that is 2^-23 sqrt(3 / N) of a diagonal entry, 1e-9 at config 3,
 //     where fp32 LAPACK's own accumulation error is 3e-7;
-//   * three products h h, h l, l h (l l is 2^-22 of the result and dropped) under fp32 accumulation, the product of the leading planes
+//   * three products h h, h l, l h (l l is 2^-22 of the result and dropped, except where the observations are few: GramPlanesArgs::ll)
+//     under fp32 accumulation, the product of the leading planes
 //     in an accumulator of its own (every matrix instruction rounds its accumulator once: the small sum's roundings are 2^-11 of the
 //     large one's);  G_ij = 2^(e_i + e_j) sum_n z'_in z'_jn, the scales applied to the finished tile (exact).
 //   Half the matrix instructions and two thirds of the bytes of NP = 3.  Tests hold both to 4 x the error of fp32 LAPACK on the same
@@ -331,7 +332,13 @@ struct GramPlanesArgs {
   const unsigned* rowmax;  // NP = 2: the rows' largest |z| (bit patterns): the tile leaves scaled by 2^(e_i + e_j)
   int xcd_swizzle;
   int64_t grp_ws, grp_s;   // blockIdx.y = regressor of a group: byte stride of Xp / Gpart / rowmax, element stride of s_iso
+  // NP = 2: the fourth product l l as well.  sum_n l_n l_n' is positive semi-definite and does not lie in the span of the observations:
+  // with fewer observations than rows it falls where A is the prior alone, and a weak prior turns 2^-22 of G into 1e-4 of logdet A
+  // (D = 129, N = 16: evidence off by 1.9e-6, beyond 4 x fp32 LAPACK; tests/test_large_d_lattice_gpu.py).  The host sets it where the
+  // observations do not outnumber the padded rows twice (kPlanesLlFactor): a Gram launch of that size is not what the update takes.
+  int ll;
 };
+constexpr int kPlanesLlFactor = 2;  // the product of the low planes is kept for N < kPlanesLlFactor DP
 
 template <int NP>
 __global__ __launch_bounds__(kPlanesThreads, 2) void gram_planes_kernel(GramPlanesArgs a) {
@@ -451,6 +458,10 @@ __global__ __launch_bounds__(kPlanesThreads, 2) void gram_planes_kernel(GramPlan
           BLR_PM3(accs[0], A(1), B0(1)); BLR_PM3(accs[0], A(1), B0(0)); BLR_PM3(accs[0], A(0), B0(1));
         }
       } else {  // planes h, l
+        if (a.ll) {  // (uniform over the launch) the smallest product first
+          if (t0) BLR_PM2(accs[0], A(1), B0(1));
+          if (t1) BLR_PM2(accs[1], A(1), B1(1));
+        }
         if (t0 && t1) {
           BLR_PM2(accs[0], A(1), B0(0)); BLR_PM2(accs[1], A(1), B1(0));
           BLR_PM2(acc[0], A(0), B0(0));  BLR_PM2(acc[1], A(0), B1(0));
@@ -602,8 +613,9 @@ __global__ __launch_bounds__(kThreads, 2) void gram_planes4_kernel(GramPlanesArg
   uint64_t adv = 0;
   const unsigned voff = (unsigned)lane * 16u;
   int hi = 0;
-  auto run = [&](auto dtag) {
+  auto run = [&](auto dtag, auto ltag) {
     constexpr bool DG = decltype(dtag)::value;
+    constexpr bool LL = decltype(ltag)::value;  // the product of the low planes as well (GramPlanesArgs::ll)
     constexpr int PW = DG ? 2 : 4;  // LDS-DMA pieces per wave and half: its two KiB of the A side (+ of the B side)
     auto issue = [&]() {
       const unsigned slot = ring_addr + (unsigned)((hi % C::SLOTS) * C::HALF + 2 * wave * 1024);
@@ -632,6 +644,12 @@ __global__ __launch_bounds__(kThreads, 2) void gram_planes4_kernel(GramPlanesArg
       __builtin_amdgcn_s_setprio(2);  // over the other workgroup's wave on this SIMD while the matrix instructions issue (same-box A/B: c3 -0.7 %, 8 x c3 -1.5 %)
       // four independent chains interleaved; within a tile the small products, then the leading one
       if (ex10) {  // (wave-uniform; the full quadrant in every off-diagonal macro tile)
+        if constexpr (LL) {
+          if (ex00) BLR_PM2(accs[0][0], A0l, B0l);
+          BLR_PM2(accs[1][0], A1l, B0l);
+          if (ex01) BLR_PM2(accs[0][1], A0l, B1l);
+          if (ex11) BLR_PM2(accs[1][1], A1l, B1l);
+        }
         if (ex00) BLR_PM2(accs[0][0], A0l, B0h);
         BLR_PM2(accs[1][0], A1l, B0h);
         if (ex01) BLR_PM2(accs[0][1], A0l, B1h);
@@ -653,8 +671,13 @@ __global__ __launch_bounds__(kThreads, 2) void gram_planes4_kernel(GramPlanesArg
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   };
   if (nh > 0) {
-    if (diag) run(std::true_type{});
-    else run(std::false_type{});
+    if (a.ll) {
+      if (diag) run(std::true_type{}, std::true_type{});
+      else run(std::false_type{}, std::true_type{});
+    } else {
+      if (diag) run(std::true_type{}, std::false_type{});
+      else run(std::false_type{}, std::false_type{});
+    }
   }
   float* const sI = reinterpret_cast<float*>(smem);
   float* const sJ = sI + kPB;

@@ -3,6 +3,10 @@
 //   hipcc -std=c++17 --offload-arch=gfx950 -o large_plan_dump tools/large_plan_dump.cpp && ./large_plan_dump
 // (also the program to run under -Xarch_host -fsanitize=address,undefined: plain host code, nothing to preload)
 #include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <initializer_list>
+#include <string>
 #include <utility>
 #include <vector>
 
@@ -39,7 +43,50 @@ static void emit(const Case& c, const BlrOptions& opt, const char* err, const La
   printf("\"G\": %d}\n", p.G);
 }
 
-int main() {
+// `large_plan_dump --stdin`: one case per line of standard input,
+//   name elem D N col|row iso|diag diag|dense|factor aligned(0|1) G [KEY=VALUE ...]
+// printed as the same JSON lines (one plan cache for the run, fresh options per line).  tests/test_large_d_lattice_cpu.py holds the
+// route rule of tests/_large_d_problems.py against it.
+static int plan_stdin() {
+  GramPlanCache cache;
+  char line[1024];
+  while (fgets(line, sizeof line, stdin)) {
+    std::vector<std::string> tok;
+    for (char* t = strtok(line, " \t\r\n"); t; t = strtok(nullptr, " \t\r\n")) tok.emplace_back(t);
+    if (tok.empty()) continue;
+    if (tok.size() < 9) { fprintf(stderr, "%s: 9 fields expected\n", tok[0].c_str()); return 1; }
+    auto pick = [&](const std::string& v, std::initializer_list<std::pair<const char*, int>> names, int* out) {
+      for (const auto& kv : names)
+        if (v == kv.first) { *out = kv.second; return true; }
+      fprintf(stderr, "%s: unknown value %s\n", tok[0].c_str(), v.c_str());
+      return false;
+    };
+    LargeShape s{};
+    s.elem = atoi(tok[1].c_str()); s.D = atoi(tok[2].c_str()); s.N = atoi(tok[3].c_str());
+    if (!pick(tok[4], {{"col", LAYOUT_COLVECS}, {"row", LAYOUT_ROWVECS}}, &s.layout)) return 1;
+    if (!pick(tok[5], {{"iso", NOISE_ISOTROPIC}, {"diag", NOISE_DIAGONAL}}, &s.noise_kind)) return 1;
+    if (!pick(tok[6], {{"diag", PRIOR_DIAGONAL}, {"dense", PRIOR_DENSE}, {"factor", PRIOR_UPPER_FACTOR}}, &s.prior_kind)) return 1;
+    s.x_aligned = atoi(tok[7].c_str()) != 0; s.G = atoi(tok[8].c_str());
+    if ((s.elem != 4 && s.elem != 8) || s.D < 1 || s.N < 0 || s.G < 1) { fprintf(stderr, "%s: bad shape\n", tok[0].c_str()); return 1; }
+    BlrOptions opt;
+    for (size_t i = 9; i < tok.size(); ++i) {
+      const size_t eq = tok[i].find('=');
+      if (eq == std::string::npos || opt.set(tok[i].substr(0, eq).c_str(), tok[i].substr(eq + 1).c_str())) {
+        fprintf(stderr, "%s: bad option %s\n", tok[0].c_str(), tok[i].c_str());
+        return 1;
+      }
+    }
+    const Case c{tok[0].c_str(), s, {}};
+    LargePlan p{};
+    const char* err = plan_case(c, opt, cache, p);
+    emit(c, opt, err, p);
+  }
+  return 0;
+}
+
+int main(int argc, char** argv) {
+  if (argc == 2 && std::string(argv[1]) == "--stdin") return plan_stdin();
+  if (argc != 1) { fprintf(stderr, "usage: %s [--stdin]\n", argv[0]); return 2; }
   const int CV = LAYOUT_COLVECS, RV = LAYOUT_ROWVECS, ISO = NOISE_ISOTROPIC, DIAG = NOISE_DIAGONAL;
   const int PD = PRIOR_DIAGONAL, PF = PRIOR_UPPER_FACTOR, PDENSE = PRIOR_DENSE;
   //                                              elem  D     N      layout noise prior aligned rff    Din S  G
