@@ -38,6 +38,7 @@
 #include "blr_loo_multi.hpp"
 #include "blr_state_cols.hpp"
 #include "blr_rand_multi.hpp"
+#include "blr_kfold.hpp"
 #include "blr_host.hpp"
 #include "blr_large_plan.hpp"
 
@@ -3998,6 +3999,169 @@ int loo_multi_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_
   return io.finish();
 }
 
+// ---- exact leave-fold-out predictives of a state's observations, contiguous folds of F <= 64 (blr_kfold_batched_*, DESIGN.md K23;
+// blr_kfold.hpp) ---------------------------------------------------------------------------------------------------------------------
+
+template <typename T>
+int kfold_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t N, int64_t F, const T* X, int64_t ldx, int64_t strideX,
+                  const T* y, int64_t stridey, int noise_kind, const T* s, int64_t strides, const T* mw, int64_t stridemw, const T* Tf,
+                  int64_t ldt, int64_t strideT, T* kf_mean, int64_t stride_km, T* kf_var, int64_t stride_kv, double* kf_logpdf,
+                  int64_t stride_kl, double* kf_total, int32_t* info) {
+  // (the argument checks come before the handle's: they need no device)
+  if (h) h->err.clear();
+  if (memspace != BLR_MEM_HOST && memspace != BLR_MEM_DEVICE) return bad_arg(h, 2, "memspace");
+  if (layout != BLR_LAYOUT_COLVECS && layout != BLR_LAYOUT_ROWVECS) return bad_arg(h, 3, "unknown layout (reference :26-31)");
+  if (B < 0 || B > (1 << 30)) return bad_arg(h, 4, "B out of range (0..2^30)");
+  if (D < 1 || D > kMaxLargeD) return bad_arg(h, 5, "D out of range (1..8192)");
+  if (N < 0 || N > (1 << 30)) return bad_arg(h, 6, "N out of range (0..2^30)");
+  if (D > kMaxSmallD && N > kMaxDenseN) return bad_arg(h, 6, "N out of range at D > 128: the route goes through an N x N covariance (0..16384)");
+  if (F < 1 || F > kFoldMax) return bad_arg(h, 7, "F out of range (1..64)");
+  if (N > 0 && !X) return bad_arg(h, 8, "X is NULL");
+  if (layout == BLR_LAYOUT_COLVECS ? ldx < D : ldx < std::max<int64_t>(N, 1)) return bad_arg(h, 9, "ldx too small");
+  if (strideX < 0) return bad_arg(h, 10, "strideX < 0");
+  if (N > 0 && !y) return bad_arg(h, 11, "y is NULL (reference :74 length check)");
+  if (stridey < 0) return bad_arg(h, 12, "stridey < 0");
+  if (noise_kind != BLR_NOISE_ISOTROPIC && noise_kind != BLR_NOISE_DIAGONAL)
+    return bad_arg(h, 13, "noise_kind (dense noise couples the folds: isotropic or diagonal only)");
+  if (N > 0 && !s) return bad_arg(h, 14, "s is NULL");
+  if (strides < 0) return bad_arg(h, 15, "strides < 0");
+  if (!mw) return bad_arg(h, 16, "mw is NULL");
+  if (stridemw < 0) return bad_arg(h, 17, "stridemw < 0");
+  if (!Tf) return bad_arg(h, 18, "T is NULL");
+  if (ldt < D) return bad_arg(h, 19, "ldt < D");
+  if (strideT < 0) return bad_arg(h, 20, "strideT < 0");
+  const int64_t nfolds = (N + F - 1) / F;
+  if (kf_mean && B > 1 && stride_km < N) return bad_arg(h, 22, "stride_km < N");
+  if (kf_var && B > 1 && stride_kv < N) return bad_arg(h, 24, "stride_kv < N");
+  if (kf_logpdf && B > 1 && stride_kl < nfolds) return bad_arg(h, 26, "stride_kl < ceil(N / F)");
+  if (!info) return bad_arg(h, 28, "info is NULL");
+  if (!h) return -1;
+  h->last_chunks = 1;  // (a route with a chunk loop counts its own)
+  if (B == 0) return 0;
+  HIP_TRY(h, hipSetDevice(h->device));
+
+  CallIO io(h, memspace);
+  KfoldArgs<T> k{};
+  k.stridey = stridey; k.strides = strides; k.noise_kind = noise_kind; k.stride_km = stride_km; k.stride_kv = stride_kv;
+  k.stride_kl = stride_kl; k.D = (int)D; k.N = (int)N; k.F = (int)F;
+  const size_t x_one = N == 0 ? 0 : (layout == BLR_LAYOUT_COLVECS ? mat_extent(D, N, ldx) : mat_extent(N, D, ldx));
+  const size_t s_one = N == 0 ? 0 : (noise_kind == BLR_NOISE_DIAGONAL ? (size_t)N : 1);
+  const size_t n_out = (size_t)N;
+  int rc;
+  const T *X_d = nullptr, *mw_d = nullptr, *T_d = nullptr;
+  double* tot_d = nullptr;
+  int32_t* info_d = nullptr;
+  if ((rc = io.in(X, x_one ? extent(B, strideX, x_one) : 0, &X_d))) return rc;
+  if ((rc = io.in(y, n_out ? extent(B, stridey, n_out) : 0, &k.y))) return rc;
+  if ((rc = io.in(s, s_one ? extent(B, strides, s_one) : 0, &k.s))) return rc;
+  if ((rc = io.in(mw, extent(B, stridemw, (size_t)D), &mw_d))) return rc;
+  if ((rc = io.in(Tf, extent(B, strideT, mat_extent(D, D, ldt)), &T_d))) return rc;
+  if ((rc = io.out(kf_mean, n_out ? extent(B, stride_km, n_out) : 0, &k.km))) return rc;
+  if ((rc = io.out(kf_var, n_out ? extent(B, stride_kv, n_out) : 0, &k.kv))) return rc;
+  if ((rc = io.out(kf_logpdf, n_out ? extent(B, stride_kl, (size_t)nfolds) : 0, &k.kl))) return rc;
+  if ((rc = io.out(kf_total, (size_t)B, &tot_d))) return rc;
+  if ((rc = io.out(info, (size_t)B, &info_d))) return rc;
+  k.info = info_d;
+  if ((rc = ensure_stats(h))) return rc;
+  k.degenerate = h->stats_dev + 4;
+
+  // status: loo_check_kernel as blr_loo_batched_* launches it
+  const int64_t ychunk = h->cap_chunk(65535);  // grid.x <= 65535 here: the check and the empty totals
+  h->count_chunks(B, ychunk);
+  for (int64_t b0 = 0; b0 < B; b0 += ychunk)
+    hipLaunchKernelGGL(loo_check_kernel<T>, dim3((unsigned)std::min<int64_t>(ychunk, B - b0)), dim3(kThreads), 0, h->stream, T_d + b0 * strideT,
+                       ldt, strideT, (int)D, k.s + b0 * strides, strides, noise_kind, (int)N, info_d + b0);
+  HIP_TRY(h, hipGetLastError());
+  if (N == 0) {  // an empty sum, for the regressors whose state passed the check
+    for (int64_t b0 = 0; tot_d && b0 < B; b0 += ychunk)
+      hipLaunchKernelGGL(loo_total_kernel, dim3((unsigned)std::min<int64_t>(ychunk, B - b0)), dim3(kThreads), 0, h->stream,
+                         (const double*)nullptr, (int64_t)0, 0, tot_d, (const int32_t*)info_d, (int)b0);
+    HIP_TRY(h, hipGetLastError());
+    return io.finish();
+  }
+  const int64_t pack_rows = (kFoldMax / F) * F, npacks = (N + pack_rows - 1) / pack_rows;
+  const size_t lds_k = kfold_lds_bytes(sizeof(T), (int)std::min<int64_t>(D, kMaxSmallD));
+  if ((rc = set_lds_once(h, kfold_kernel<T>, lds_k))) return rc;
+  const bool kl_ws = tot_d && !k.kl;  // the totals need the folds' log densities somewhere
+
+  if (D > kMaxSmallD) {
+    // correct, not fast: one regressor after the other through the launches of blr_mean_and_cov_* (mean_and_cov_core) into a staging
+    // covariance C = Z Z' + diag(s), whose diagonal blocks the fold kernel reads instead of forming the product; the call synchronises
+    std::vector<int32_t> st((size_t)B, 0);
+    HIP_TRY(h, hipMemcpyAsync(st.data(), info_d, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    CovTemps<T> t;
+    T *Ct = nullptr, *mt = nullptr;
+    double* klt = nullptr;
+    int32_t* it = nullptr;
+    if ((rc = t.reserve(io, (int)D, (int)N))) return rc;
+    if ((rc = io.tmp((size_t)N * N, &Ct))) return rc;
+    if ((rc = io.tmp((size_t)N, &mt))) return rc;
+    if ((rc = io.tmp(1, &it))) return rc;
+    if (kl_ws && (rc = io.tmp((size_t)nfolds, &klt))) return rc;
+    for (int64_t b = 0; b < B; ++b) {
+      if (st[(size_t)b] != 0) continue;  // outputs of that regressor stay untouched
+      rc = mean_and_cov_core<T>(h, t, layout, (int)D, (int)N, X_d + b * strideX, ldx, noise_kind, k.s + b * strides, 0, BLR_PRIOR_UPPER_FACTOR,
+                                mw_d + b * stridemw, T_d + b * strideT, ldt, mt, Ct, N, it);
+      if (rc) return rc;
+      KfoldArgs<T> c = k;
+      c.C = Ct; c.ldc = N; c.m = mt; c.stridem = 0; c.reg0 = (int)b;
+      if (kl_ws) { c.kl = klt; c.stride_kl = 0; }
+      hipLaunchKernelGGL(kfold_kernel<T>, dim3((unsigned)npacks, 1), dim3(kThreads), lds_k, h->stream, c);
+      if (tot_d)
+        hipLaunchKernelGGL(loo_total_kernel, dim3(1), dim3(kThreads), 0, h->stream, (const double*)c.kl, c.stride_kl, (int)nfolds, tot_d,
+                           (const int32_t*)info_d, (int)b);
+      HIP_TRY(h, hipGetLastError());
+    }
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return io.finish();
+  }
+
+  // D <= 128.  Per chunk of regressors: the triangular inverses as MFMA images (marg_image_kernel), Z = X'T^-1 and x'mw into workspace
+  // (cov_whiten_kernel), the folds (kfold_kernel), the totals -- four launches whatever B.  Chunks by the rules of
+  // blr_mean_and_cov_batched_*: grid.y, the images and the rows of Z within 256 MiB each, the means (and the folds' log densities when
+  // only the totals are wanted) within theirs, at least one regressor
+  const size_t z_one = cov_z_elems((int)D, (int)N);
+  const size_t row = ((size_t)N * sizeof(T) + 255) & ~(size_t)255, row_kl = ((size_t)nfolds * sizeof(double) + 255) & ~(size_t)255;
+  const size_t per = row + (kl_ws ? row_kl : 0);
+  int64_t chunk = std::min<int64_t>(std::min<int64_t>(B, 65535), MargImages<T>::kMaxChunk);
+  chunk = std::min<int64_t>(chunk, std::max<int64_t>(1, (int64_t)(((size_t)256 << 20) / (z_one * sizeof(T)))));
+  chunk = std::max<int64_t>(1, std::min<int64_t>(chunk, (int64_t)(kLooWorkspace / per)));
+  chunk = h->cap_chunk(chunk);
+  h->count_chunks(B, chunk);
+  const size_t lds_w = cov_whiten_lds_bytes(sizeof(T), (int)D, true);
+  void (*const whiten)(CovArgs<T>) = layout == BLR_LAYOUT_ROWVECS ? cov_whiten_kernel<T, LAYOUT_ROWVECS> : cov_whiten_kernel<T, LAYOUT_COLVECS>;
+  if ((rc = set_lds_once(h, whiten, lds_w))) return rc;
+  if ((rc = MargImages<T>::reserve(h, chunk))) return rc;
+  if ((rc = h->cov_ws.reserve(h, (size_t)chunk * z_one * sizeof(T)))) return rc;
+  if ((rc = h->loo_ws.reserve(h, (size_t)chunk * per + 256))) return rc;
+  char* const ws = h->loo_ws.p;
+  const int64_t ldw = (int64_t)(row / sizeof(T)), ldkl = (int64_t)(row_kl / sizeof(double));
+  const int64_t ntiles = (N + kCovTile - 1) / kCovTile;
+  CovArgs<T> a{};
+  a.X = X_d; a.ldx = ldx; a.strideX = strideX; a.mw = mw_d; a.stridemw = stridemw; a.info = info_d; a.stridemean = ldw;
+  a.noise_kind = noise_kind; a.prior_kind = BLR_PRIOR_UPPER_FACTOR; a.D = (int)D; a.N = (int)N;
+  a.Z = reinterpret_cast<T*>(h->cov_ws.p);
+  for (int64_t b0 = 0; b0 < B; b0 += chunk) {
+    const int64_t nb = std::min<int64_t>(chunk, B - b0);
+    a.img = MargImages<T>::launch(h, T_d + b0 * strideT, ldt, strideT, (int)D, (const int32_t*)(info_d + b0), 0, nb);
+    // every workgroup amortises its set-up (the image) over its tiles: about two workgroups per CU in all
+    const int64_t ngroups = std::max<int64_t>(1, std::min<int64_t>(ntiles, (2 * (int64_t)h->cus + nb - 1) / nb));
+    a.mean = reinterpret_cast<T*>(ws) - b0 * ldw;  // (indexed by the global regressor)
+    a.ngroups = (int)ngroups; a.reg0 = (int)b0;
+    hipLaunchKernelGGL(whiten, dim3((unsigned)ngroups, (unsigned)nb), dim3(kThreads), lds_w, h->stream, a);
+    KfoldArgs<T> c = k;
+    c.Z = a.Z; c.strideZ = (int64_t)z_one; c.m = a.mean; c.stridem = ldw; c.reg0 = (int)b0;
+    if (kl_ws) { c.kl = reinterpret_cast<double*>(ws + (size_t)chunk * row) - b0 * ldkl; c.stride_kl = ldkl; }
+    hipLaunchKernelGGL(kfold_kernel<T>, dim3((unsigned)npacks, (unsigned)nb), dim3(kThreads), lds_k, h->stream, c);
+    if (tot_d)
+      hipLaunchKernelGGL(loo_total_kernel, dim3((unsigned)nb), dim3(kThreads), 0, h->stream, (const double*)c.kl, c.stride_kl, (int)nfolds, tot_d,
+                         (const int32_t*)info_d, (int)b0);
+    HIP_TRY(h, hipGetLastError());
+  }
+  return io.finish();
+}
+
 // ---- rank-k update / downdate of a resident MULTI-OUTPUT state: one factor, S mean columns (blr_update_multi_factor_*,
 // blr_downdate_multi_factor_*; blr_state_cols.hpp) ---------------------------------------------------------------------
 
@@ -4290,6 +4454,16 @@ int blr_get_stat(blr_handle* h, const char* key, int64_t* value) {
     *value = (int64_t)v;
     return 0;
   }
+  if (!strcmp(key, "kfold_degenerate")) {  // folds blr_kfold_batched_* gave NaN: a pivot of I - H~ <= 0 or not finite (cumulative)
+    unsigned long long v = 0;
+    if (h->stats_dev) {
+      HIP_TRY(h, hipSetDevice(h->device));
+      HIP_TRY(h, hipMemcpyAsync(&v, h->stats_dev + 4, sizeof(v), hipMemcpyDeviceToHost, h->stream));
+      HIP_TRY(h, hipStreamSynchronize(h->stream));
+    }
+    *value = (int64_t)v;
+    return 0;
+  }
   if (!strcmp(key, "workspace_bytes")) {
     *value = (int64_t)(h->ws.bytes + h->feat.bytes + h->aux.bytes + h->i8side.bytes + h->xchg.bytes + h->loo_ws.bytes + h->ragged_meta.bytes + h->multi_ws.bytes + h->cov_ws.bytes);
     return 0;
@@ -4301,7 +4475,7 @@ int blr_reset_stats(blr_handle* h) {
   h->err.clear();
   if (h->stats_dev) {  // (device counter first: a failure must not leave the two counters apart)
     HIP_TRY(h, hipSetDevice(h->device));
-    HIP_TRY(h, hipMemsetAsync(h->stats_dev, 0, 4 * sizeof(unsigned long long), h->stream));  // (total, planes made twice, the last call's base, LOO degenerate)
+    HIP_TRY(h, hipMemsetAsync(h->stats_dev, 0, 5 * sizeof(unsigned long long), h->stream));  // (total, planes made twice, the last call's base, LOO degenerate, K-fold degenerate)
   }
   h->i8_attempted = 0;
   return 0;
@@ -4391,6 +4565,15 @@ int blr_timer_stop(blr_handle* h, float* elapsed_ms) {
     return loo_batched<T>(h, memspace, layout, B, D, N, X, ldx, strideX, y, stridey, noise_kind, s, strides, mw,     \
                           stridemw, Tf, ldt, strideT, loo_mean, stride_lm, loo_var, stride_lv, loo_logpdf,          \
                           stride_ll, loo_total, info);                                                             \
+  }                                                                                                                 \
+  int blr_kfold_batched_##SUF(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t N, int64_t F, \
+                              const T* X, int64_t ldx, int64_t strideX, const T* y, int64_t stridey, int noise_kind, \
+                              const T* s, int64_t strides, const T* mw, int64_t stridemw, const T* Tf, int64_t ldt,  \
+                              int64_t strideT, T* kf_mean, int64_t stride_km, T* kf_var, int64_t stride_kv,         \
+                              double* kf_logpdf, int64_t stride_kl, double* kf_total, int32_t* info) {              \
+    return kfold_batched<T>(h, memspace, layout, B, D, N, F, X, ldx, strideX, y, stridey, noise_kind, s, strides,    \
+                            mw, stridemw, Tf, ldt, strideT, kf_mean, stride_km, kf_var, stride_kv, kf_logpdf,       \
+                            stride_kl, kf_total, info);                                                            \
   }                                                                                                                 \
   int blr_logpdf_grid_##SUF(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t N, const T* X,  \
                             int64_t ldx, int64_t strideX, const T* y, int64_t stridey, int noise_kind, const T* s, \

@@ -199,7 +199,7 @@ struct blr_handle {
   // blr_release_workspace hands these back; xchg, ticket and stats_dev stay (their contents carry epochs and counters)
   std::array<DevBuf*, 8> releasable() { return {&ws, &feat, &aux, &i8side, &loo_ws, &ragged_meta, &multi_ws, &cov_ws}; }
   // counters behind blr_get_stat: [0] regressors the int8 route handed back to the fp64 kernel (cumulative); [3] degenerate
-  // leverages of blr_loo_batched_* (cumulative); [8 + 2 k + {0, 1}]:
+  // leverages of blr_loo_batched_* (cumulative); [4] degenerate folds of blr_kfold_batched_* (cumulative); [8 + 2 k + {0, 1}]:
   // hand-backs of slice k of the current call (two banks, alternating), read by the NEXT slice's launch (launch_fused_i8)
   unsigned long long* stats_dev = nullptr;
   unsigned long long i8_attempted = 0;   // regressors sent down the int8 route (host count)

@@ -27,6 +27,7 @@ __all__ = [
     "BayesianLinearRegressor", "BasisFunctionRegressor", "BLRFunctionSample", "FiniteGP",
     "mean", "var", "cov", "std", "mean_and_var", "mean_and_cov", "marginals", "rand", "rand_b", "logpdf", "posterior",
     "LOO", "loo", "loo_map", "loo_columns", "loo_columns_map",
+    "KFold", "kfold", "kfold_map",
     "EvidenceGrid", "logpdf_grid", "posterior_best", "logpdf_grid_map",
     "posterior_ragged", "logpdf_ragged",
     "posterior_columns", "logpdf_columns_map", "posterior_columns_map",
@@ -923,8 +924,9 @@ var including the noise as var(fx) does, in the element type; logpdf in float64)
 score).  An observation whose leverage is within rounding of 1 has NaN entries (blr_get_stat "loo_degenerate")."""
 
 
-def _loo_problem(fx, y, dtype):
-    """(X, layout, ldx, D, N, y, s, noise_kind, mw, Lw, prior_kind, ldl) of one finite regressor, validated as `_fused` does."""
+def _loo_problem(fx, y, dtype, what="loo", perm=None):
+    """(X, layout, ldx, D, N, y, s, noise_kind, mw, Lw, prior_kind, ldl) of one finite regressor, validated as `_fused` does.
+    ``perm`` (kfold): observation n of the problem is observation perm[n] of the caller's -- X, y and a noise diagonal gathered here."""
     fb = _to_finite_blr(fx)
     X, layout, ldx, D, N = _x_layout(fb.x, dtype)
     y = np.ascontiguousarray(y, dtype=dtype)
@@ -934,8 +936,14 @@ def _loo_problem(fx, y, dtype):
         raise ValueError("length(y) != size(fx.x.X, 2)")  # reference :74
     s, noise_kind = _noise(fb.Sy, N, dtype)
     if noise_kind == _abi.NOISE_DENSE:
-        raise NotImplementedError("loo: with a dense noise covariance one observation is not independent of the rest (that is a "
+        raise NotImplementedError(f"{what}: with a dense noise covariance one observation is not independent of the rest (that is a "
                                   "block leave-out); isotropic or diagonal noise only")
+    if perm is not None:
+        obs_axis = 0 if isinstance(fb.x, RowVecs) else 1
+        X = np.asarray(np.take(X, perm, axis=obs_axis), order="F" if X.flags.f_contiguous else "C")
+        y = np.ascontiguousarray(y[perm])
+        if noise_kind == _abi.NOISE_DIAGONAL:
+            s = np.ascontiguousarray(s[perm])
     Lw, prior_kind, ldl = _prior(fb.f.Lw, D, dtype)
     return X, layout, ldx, D, N, y, s, noise_kind, _mean_vector(fb.f.mw, D, dtype), Lw, prior_kind, ldl
 
@@ -956,9 +964,41 @@ def _loo_call(h, dtype, layout, B, D, N, dX, ldx, strideX, dy, stridey, noise_ki
     return m, v, lp, tot, info
 
 
-def _loo_batch(probs, dtype):
+KFold = namedtuple("KFold", ["mean", "var", "logpdf", "total"])
+KFold.__doc__ = """Exact leave-fold-out (K-fold) predictives for contiguous folds of ``fold_size`` observations: per observation n the
+predictive of y_n given all the other FOLDS (mean and var, var including the noise, in the element type), per fold the JOINT log
+density of its observations given the rest (logpdf, float64, ceil(N / fold_size) entries) and total = sum_f logpdf_f (the K-fold CV
+score).  A fold the state does not contain (a pivot of I - H~ <= 0) has NaN entries (blr_get_stat "kfold_degenerate")."""
+
+
+def _kfold_call(h, dtype, layout, B, D, N, F, dX, ldx, strideX, dy, stridey, noise_kind, ds, strides, d_mw, stridemw, d_T, strideT, temps):
+    """blr_kfold_batched_* on device operands -> (mean [B, N], var [B, N], logpdf [B, nfolds], total [B], info [B]) on the host."""
+    item = np.dtype(dtype).itemsize
+    nf = -(-N // F)
+    outs = [_DeviceBuffer(h, B * N * item), _DeviceBuffer(h, B * N * item), _DeviceBuffer(h, B * nf * 8), _DeviceBuffer(h, B * 8),
+            _DeviceBuffer.of(h, np.zeros(B, dtype=np.int32))]
+    temps.extend(outs)
+    d_km, d_kv, d_kl, d_tot, d_info = (b.ptr for b in outs)
+    h.kfold(dtype, _abi.MEM_DEVICE, layout, B, D, N, F, dX, ldx, strideX, dy, stridey, noise_kind, ds, strides, d_mw, stridemw, d_T,
+            max(D, 1), strideT, d_km, N, d_kv, N, d_kl, nf, d_tot, d_info)
+    m, v = np.empty((B, N), dtype=dtype), np.empty((B, N), dtype=dtype)
+    lp, tot, info = np.empty((B, nf), dtype=np.float64), np.empty(B, dtype=np.float64), np.zeros(B, dtype=np.int32)
+    for host, dptr in ((m, d_km), (v, d_kv), (lp, d_kl), (tot, d_tot), (info, d_info)):
+        h.memcpy_d2h(host, dptr)
+    return m, v, lp, tot, info
+
+
+def _fold_size(fold_size):
+    F = int(fold_size)
+    if F != fold_size or not 1 <= F <= 64:
+        raise ValueError("fold_size must be an integer in 1..64")
+    return F
+
+
+def _loo_batch(probs, dtype, fold_size=None):
     """LOO of equally shaped problems: their data staged once, blr_posterior_batched_* into device buffers (mw', T) -- any prior
-    kind, the usual routes -- then blr_loo_batched_* on the same device inputs.  Nothing D x D comes back to the host."""
+    kind, the usual routes -- then blr_loo_batched_* on the same device inputs.  Nothing D x D comes back to the host.
+    ``fold_size``: the same pipeline with blr_kfold_batched_* as its second half -> KFold records."""
     X0, layout, ldx, D, N, _, _, noise_kind, _, _, prior_kind, ldl = probs[0]
     nb, h, item = len(probs), _handle(), np.dtype(dtype).itemsize
     Xb = np.stack([q[0].reshape(-1, order="A") for q in probs])
@@ -982,9 +1022,12 @@ def _loo_batch(probs, dtype):
                             None, max(D, 1), D * D, None, d_info)
         info = np.zeros(nb, dtype=np.int32)
         h.memcpy_d2h(info, d_info)
-        if not np.any(info):
+        if not np.any(info) and fold_size is None:
             m, v, lp, tot, info = _loo_call(h, dtype, layout, nb, D, N, dX, ldx, Xb.shape[1], dy, yb.shape[1], noise_kind, ds,
                                             sb.shape[1], d_mwp, D, d_T, D * D, temps)
+        elif not np.any(info):
+            m, v, lp, tot, info = _kfold_call(h, dtype, layout, nb, D, N, fold_size, dX, ldx, Xb.shape[1], dy, yb.shape[1], noise_kind,
+                                              ds, sb.shape[1], d_mwp, D, d_T, D * D, temps)
     finally:
         for b in temps:
             b.free()
@@ -993,7 +1036,7 @@ def _loo_batch(probs, dtype):
         e = _abi.PosDefException(int(info[bad[0]]))
         e.index = int(bad[0])
         raise e
-    return [LOO(m[b], v[b], lp[b], float(tot[b])) for b in range(nb)]
+    return [(LOO if fold_size is None else KFold)(m[b], v[b], lp[b], float(tot[b])) for b in range(nb)]
 
 
 def loo(fx, y):
@@ -1034,6 +1077,61 @@ def loo_map(fxs, ys):
     if len(sig) != 1 or probs[0][3] == 0 or probs[0][4] == 0:
         return one_by_one(probs)
     return _loo_batch(probs, dtype)
+
+
+def kfold(fx, y, fold_size, perm=None):
+    """Exact leave-fold-out (K-fold) predictives of the observations y at fx.x (include/blr_mi355x.h blr_kfold_batched_*): fold f
+    holds the observations [f fold_size, (f + 1) fold_size), and every observation gets its predictive under posterior(fx without
+    its fold) -- what a loop of forget / predict / condition per fold gives, from one call.  1 <= fold_size <= 64; at 1 this is
+    `loo`.  ``perm``, a permutation of range(N), makes the folds random: fold f then holds the observations perm[f fold_size :
+    (f + 1) fold_size]; mean and var come back in the caller's order, logpdf stays in fold order.  Returns KFold(mean, var, logpdf,
+    total).  Dense noise raises NotImplementedError (it couples the folds)."""
+    F = _fold_size(fold_size)
+    dtype = _dtype_of(fx.f.blr.mw if isinstance(fx.f, BasisFunctionRegressor) else fx.f.mw, y)
+    if perm is not None:
+        perm = np.asarray(perm, dtype=np.int64)
+        n = np.asarray(y).shape[0] if np.ndim(y) == 1 else -1
+        if perm.shape != (n,) or not np.array_equal(np.sort(perm), np.arange(n)):
+            raise ValueError("perm must be a permutation of range(N)")
+    r = _loo_batch([_loo_problem(fx, y, dtype, "kfold", perm)], dtype, F)[0]
+    if perm is None:
+        return r
+    m, v = np.empty_like(r.mean), np.empty_like(r.var)
+    m[perm], v[perm] = r.mean, r.var
+    return KFold(m, v, r.logpdf, r.total)
+
+
+def kfold_map(fxs, ys, fold_size):
+    """[kfold(fx, y, fold_size) for fx, y in zip(fxs, ys)] in one posterior call and one K-fold call for equally shaped problems
+    (else one call per problem, as `loo_map`).  The first problem whose prior, noise or posterior is not positive definite raises
+    PosDefException with its position as ``index``."""
+    F = _fold_size(fold_size)
+    fxs, ys = list(fxs), list(ys)
+    if len(fxs) != len(ys):
+        raise ValueError("as many observation vectors as finite regressors are needed")
+    if not fxs:
+        return []
+    dtype = np.float32 if all(_dtype_of(fx.f.blr.mw if isinstance(fx.f, BasisFunctionRegressor) else fx.f.mw, y) == np.float32
+                              for fx, y in zip(fxs, ys)) else np.float64
+
+    def one_by_one(probs):
+        out = []
+        for i, q in enumerate(probs):
+            try:
+                out.append(_loo_batch([q], dtype, F)[0])
+            except _abi.PosDefException as e:
+                e.index = i
+                raise
+        return out
+
+    probs = [_loo_problem(fx, y, dtype, "kfold") for fx, y in zip(fxs, ys)]
+    if any(isinstance(fx.f, BasisFunctionRegressor) and isinstance(fx.f.phi, RandomFourierFeatures) for fx in fxs):
+        return one_by_one(probs)
+    sig = {(q[0].shape, q[0].flags.f_contiguous, q[1], q[3], q[4], q[7], q[10],
+            isinstance((fx.f.blr if isinstance(fx.f, BasisFunctionRegressor) else fx.f).Lw, PDMat)) for q, fx in zip(probs, fxs)}
+    if len(sig) != 1 or probs[0][3] == 0 or probs[0][4] == 0:
+        return one_by_one(probs)
+    return _loo_batch(probs, dtype, F)
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -1483,6 +1581,37 @@ class ResidentPosterior:
         if info[0] != 0:
             raise _abi.PosDefException(int(info[0]))
         return LOO(m[0], v[0], lp[0], float(tot[0]))
+
+    def kfold(self, x, Sy, y, fold_size):
+        """Exact leave-fold-out predictives of the observations (x, Sy, y), which the caller vouches the state contains, for
+        contiguous folds of ``fold_size`` (1..64): per fold what ``forget`` of the fold, a prediction at its inputs and
+        ``condition`` would give, without touching the state (blr_kfold_batched_*, B = 1, on the resident pointers).  Returns
+        KFold(mean, var, logpdf, total); a state with a non-positive diagonal entry or a non-positive variance raises
+        PosDefException(info)."""
+        F = _fold_size(fold_size)
+        dtype, h, D = self.dtype, self._h, self.D
+        temps = []
+
+        def dev(a):
+            temps.append(_DeviceBuffer.of(h, a))
+            return temps[-1].ptr
+
+        try:
+            dX, layout, ldx, N = self._inputs(x, dev, temps)
+            y = np.ascontiguousarray(y, dtype=dtype)
+            if y.shape != (N,):
+                raise ValueError("length(y) != number of inputs")  # reference :74
+            s, noise_kind = _noise(Sy, N, dtype)
+            if noise_kind == _abi.NOISE_DENSE:
+                raise NotImplementedError("ResidentPosterior.kfold takes scalar or diagonal noise (dense noise couples the folds)")
+            m, v, lp, tot, info = _kfold_call(h, dtype, layout, 1, D, N, F, dX, ldx, 0, dev(y), 0, noise_kind, dev(s), 0, self._mw.ptr,
+                                              0, self._T.ptr, 0, temps)
+        finally:
+            for b in temps:
+                b.free()
+        if info[0] != 0:
+            raise _abi.PosDefException(int(info[0]))
+        return KFold(m[0], v[0], lp[0], float(tot[0]))
 
     def rand(self, rng, x, S, Sy=None):
         """S draws at the inputs x from the resident state (N x S), without copying T to the host (blr_rand_batched_*, B = 1):

@@ -97,7 +97,8 @@ const char* blr_last_route(blr_handle* h);
  * columns of every column chunk (doubled: an entry up to 16 x the sample's largest still fits); an entry beyond that sends the call
  * through the exact row maxima and the planes pass a second time (one more read of X; option NO_SPEC_ROWMAX = 1 always takes the exact
  * maxima: one more read of X on every call); "loo_degenerate" = observations blr_loo_batched_* gave NaN because their 1 - h_n was
- * <= 0 or not finite (reading it synchronises the handle's stream); "last_chunks" = chunks / slices of regressors the handle's most
+ * <= 0 or not finite (reading it synchronises the handle's stream); "kfold_degenerate" = folds blr_kfold_batched_* gave NaN because
+ * the Cholesky of their I - H~ met a pivot <= 0 or not finite (reading it synchronises the handle's stream); "last_chunks" = chunks / slices of regressors the handle's most
  * recent call launched (NOT cumulative: every entry point starts it at 1; a batch beyond grid.y = 65535, a workspace or image bound, or
  * option MAX_CHUNK, goes in several); "workspace_bytes" = device scratch the handle holds now.
  * -> 0, -2 unknown key, -3 NULL value. */
@@ -863,6 +864,65 @@ int blr_loo_multi_batched_f32(blr_handle* h, int memspace, int layout, int64_t B
                               const float* T, int64_t ldt, int64_t strideT, float* loo_mean, int64_t ld_lm, int64_t stride_lm,
                               float* loo_var, int64_t stride_lv, double* loo_logpdf, int64_t ld_ll, int64_t stride_ll,
                               double* loo_total, int64_t stride_lt, int32_t* info);
+
+/* ---- exact LEAVE-FOLD-OUT (K-fold) predictives of the observations a posterior state contains ------------------------------
+ * Replaces: a loop of blr_downdate_factor_* (forget the fold) / blr_mean_and_cov_* or blr_marginals_batched_* (predict it) /
+ * blr_update_factor_* (put it back) per fold and regressor, or K refits through blr_posterior_batched_*; reference
+ * src/bayesian_linear_regression.jl:55-58 (logpdf) of each held-out fold given the rest.
+ * State (mw, T) as for blr_loo_batched_*: T upper, only its upper triangle is read; NOT modified.  It must be conditioned on a
+ * data set that contains the N observations (X, y, s).  Folds are contiguous blocks of F observations: fold f is
+ * [f F, min((f + 1) F, N)) with n_f members, nfolds = ceil(N / F).  With A = T'T, z_n = T^-T x_n, q_n = 1 / sqrt(s_n),
+ * r_n = y_n - x_n'mw and Z_f the fold's rows z_n':
+ *   G~ = I - diag(q) Z_f Z_f' diag(q) = L L'     (n_f x n_f; positive definite iff the state really contains the fold)
+ *   u = L^-1 (q .* r),   g = L^-T u
+ *   kf_mean_n = y_n - sqrt(s_n) g_n                     (predictive mean of y_n given all the other FOLDS)
+ *   kf_var_n  = s_n [G~^-1]_nn = s_n |L^-1 e_n|^2       (noise included, as var(fx) includes Sigma_y)
+ *   kf_logpdf[f] = -1/2 [n_f log 2 pi + sum log s_n - 2 sum log L_ii + |u|^2]   (the JOINT density of the fold; double)
+ *   kf_total[b] = sum_f kf_logpdf[f] in a fixed order (the K-fold CV score; double).
+ * At F = 1 these are the numbers of blr_loo_batched_*.  Z Z' and x_n'mw are computed in the element type on the matrix cores; from G~
+ * onwards everything is double in both element types.
+ * Outputs: kf_mean and kf_var [N] per regressor in the element type, kf_logpdf [nfolds] per regressor, kf_total [B].  Any of them may
+ * be NULL; with kf_total requested and kf_logpdf NULL the log densities go through handle workspace.  A stride of 0 shares an input
+ * (strideX, stridey, strides, stridemw and strideT included).
+ * Sizes: 1 <= F <= 64, and F > N is allowed: one fold, the predictive under the state minus ALL of the data.  1 <= D <= 8192;
+ * 0 <= N <= 2^30 at D <= 128 and N <= 16384 at D > 128 (that route goes through an N x N covariance).  Isotropic or diagonal noise;
+ * dense noise is an argument error (it couples the folds).  ColVecs or RowVecs with any ldx, host or device memspace.  At D <= 128 the
+ * rows z_n of a chunk of regressors live in handle workspace: 16 ceil(D / 16) elements per observation.
+ * No-ops: B = 0 returns 0 and touches nothing; N = 0 gives kf_total = 0 and info = 0 (for a state that passes the check).
+ * Argument errors (negative position; checked before the handle, so a NULL handle with valid arguments returns -1): memspace (2),
+ * layout (3), B (4), D (5), N (6; N > 16384 at D > 128 included), F (7) out of range, ldx too small (9), dense noise (13), ldt < D (19),
+ * a negative input stride (10, 12, 15, 17, 20), a NULL X / y / s (N > 0; 8, 11, 14) / mw (16) / T (18) / info (28), and for B > 1
+ * overlapping outputs: stride_km < N (22), stride_kv < N (24), stride_kl < nfolds (26).
+ * info[B], as blr_loo_batched_* and in its order: T has a non-positive diagonal entry j -> j, else s_i is not positive -> i; every
+ * output of such a regressor is left untouched; the call returns 0.
+ * NaN rule: a fold whose Cholesky of G~ meets a pivot <= 0 or not finite (the state does not contain the fold, or a leverage is
+ * within rounding of 1) gets NaN in kf_mean and kf_var of all its members and in its kf_logpdf, and so in kf_total; it is counted
+ * once by blr_get_stat "kfold_degenerate".  Every other fold of the regressor is unaffected, bit for bit.
+ * Bit promises: results are bit-reproducible from call to call; the bits of a regressor do not depend on B, on its position in the
+ * batch, on the chunking or on the other regressors; the bits of fold f depend only on that regressor's T and mw and on the fold's
+ * own X, y and s -- not on N, on the other folds or on where the fold lands inside a workgroup; the bits of one output do not
+ * depend on which others are requested; host and device memspace give the same bits.  No float atomics.  NOT promised:
+ * bit-equality with blr_loo_batched_* at F = 1 (the products run in a different order).
+ * Kernels (csrc/blr_kfold.hpp).  D <= 128, four launches per chunk of regressors (chunks by the rules of
+ * blr_mean_and_cov_batched_*: grid.y <= 65535, 256 MiB of images, 256 MiB of rows z_n, never fewer than one regressor; option
+ * MAX_CHUNK and blr_get_stat "last_chunks" are honoured): the status (loo_check_kernel), the triangular inverse as an MFMA image
+ * (marg_image_kernel), cov_whiten_kernel for the rows z_n and x_n'mw (X is read once), and kfold_kernel over (fold packs,
+ * regressors) -- a workgroup takes floor(64 / F) consecutive folds, forms their 64 x 64 product on the matrix cores, and runs the
+ * Cholesky, L^-1 and the epilogue in double in LDS, every fold bounded to its own rows and columns -- then the totals
+ * (loo_total_kernel).  An async handle in device memspace only enqueues.  D > 128 is correct, not fast: one regressor after the
+ * other through the launches of blr_mean_and_cov_* into a staging covariance whose diagonal blocks the fold kernel reads
+ * (G~_ij = 2 delta_ij - C_ij q_i q_j); this route SYNCHRONISES, async handle or not.
+ * _f32: X, y, s, mw, T, kf_mean, kf_var are float; kf_logpdf and kf_total stay double. */
+int blr_kfold_batched_f64(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t N, int64_t F, const double* X,
+                          int64_t ldx, int64_t strideX, const double* y, int64_t stridey, int noise_kind, const double* s,
+                          int64_t strides, const double* mw, int64_t stridemw, const double* T, int64_t ldt, int64_t strideT,
+                          double* kf_mean, int64_t stride_km, double* kf_var, int64_t stride_kv, double* kf_logpdf,
+                          int64_t stride_kl, double* kf_total, int32_t* info);
+int blr_kfold_batched_f32(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t N, int64_t F, const float* X,
+                          int64_t ldx, int64_t strideX, const float* y, int64_t stridey, int noise_kind, const float* s,
+                          int64_t strides, const float* mw, int64_t stridemw, const float* T, int64_t ldt, int64_t strideT,
+                          float* kf_mean, int64_t stride_km, float* kf_var, int64_t stride_kv, double* kf_logpdf,
+                          int64_t stride_kl, double* kf_total, int32_t* info);
 
 /* ---- evidence of one data set under a GRID of (prior scale, noise scale) settings, from one pass over the data ------------
  * Replaces: blr_posterior_batched_* called with strideX = 0, stridey = 0 and one scaled (s, Lw) pair per setting, which re-forms

@@ -1199,6 +1199,42 @@ function loo!(lm::Union{Nothing,DeviceArray{T}}, lv::Union{Nothing,DeviceArray{T
 end
 
 """
+    kfold!(kmean, kvar, klogpdf, total, info, X, y, s, mw, T; D, N, F, B, isotropic)
+
+Exact leave-fold-out (K-fold) predictives of the N observations each of B device-resident states contains
+(`blr_kfold_batched_*`), for contiguous folds of F ≤ 64 observations: what a `downdate_factor!` of the fold, a prediction at
+its inputs and an `update_factor!` to put it back report, the states untouched.  Operands as for `loo!`; kmean, kvar (element
+type) are N×B or `nothing`, klogpdf (Float64, the JOINT log density of each fold) is cld(N, F)×B or `nothing`, total
+(Float64, Σ_f klogpdf in a fixed order) B or `nothing`.  A fold the state does not contain gives NaN
+(`get_stat("kfold_degenerate")` counts it once); info[b] > 0: a bad factor, else a bad variance, and that state's outputs
+are left untouched.  D > 128 synchronises.
+"""
+function kfold!(km::Union{Nothing,DeviceArray{T}}, kv::Union{Nothing,DeviceArray{T}}, kl::Union{Nothing,DeviceArray{Float64}},
+                total::Union{Nothing,DeviceArray{Float64}}, info::DeviceArray{Int32}, X::DeviceArray{T}, y::DeviceArray{T},
+                s::DeviceArray{T}, mw::DeviceArray{T}, Tf::DeviceArray{T}; D::Int, N::Int, F::Int, B::Int, isotropic::Bool) where {T<:Elt}
+    h = handle()
+    nk = isotropic ? ISOTROPIC : DIAGONALN
+    nf = cld(N, F)
+    ptr(a) = a === nothing ? Ptr{T}(C_NULL) : a.ptr
+    dptr(a) = a === nothing ? Ptr{Cdouble}(C_NULL) : a.ptr
+    rc = if T === Float64
+        ccall((:blr_kfold_batched_f64, LIB), Cint,
+              (Ptr{Cvoid}, Cint, Cint, Int64, Int64, Int64, Int64, Ptr{T}, Int64, Int64, Ptr{T}, Int64, Cint, Ptr{T}, Int64, Ptr{T}, Int64,
+               Ptr{T}, Int64, Int64, Ptr{T}, Int64, Ptr{T}, Int64, Ptr{Cdouble}, Int64, Ptr{Cdouble}, Ptr{Int32}),
+              h, MEM_DEVICE, COLVECS, B, D, N, F, X.ptr, D, D * N, y.ptr, N, nk, s.ptr, isotropic ? 0 : N, mw.ptr, D, Tf.ptr, D, D * D,
+              ptr(km), N, ptr(kv), N, dptr(kl), nf, dptr(total), info.ptr)
+    else
+        ccall((:blr_kfold_batched_f32, LIB), Cint,
+              (Ptr{Cvoid}, Cint, Cint, Int64, Int64, Int64, Int64, Ptr{T}, Int64, Int64, Ptr{T}, Int64, Cint, Ptr{T}, Int64, Ptr{T}, Int64,
+               Ptr{T}, Int64, Int64, Ptr{T}, Int64, Ptr{T}, Int64, Ptr{Cdouble}, Int64, Ptr{Cdouble}, Ptr{Int32}),
+              h, MEM_DEVICE, COLVECS, B, D, N, F, X.ptr, D, D * N, y.ptr, N, nk, s.ptr, isotropic ? 0 : N, mw.ptr, D, Tf.ptr, D, D * D,
+              ptr(km), N, ptr(kv), N, dptr(kl), nf, dptr(total), info.ptr)
+    end
+    check(h, rc)
+    return nothing
+end
+
+"""
     loo_multi_batched!(lmean, lvar, llogpdf, total, info, X, Y, s, M, T; D, N, S, B, isotropic)
 
 Exact leave-one-out predictives of the N observations with S targets each that B device-resident MULTI-OUTPUT states contain
