@@ -99,6 +99,7 @@ for _suf in ("f64", "f32"):
     _SIGS[f"blr_kfold_batched_{_suf}"] = (
         [_H, _int, _int, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _int, _vp, _i64, _vp, _i64, _vp, _i64, _i64,
          _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp], _int)
+    _SIGS[f"blr_kfold_large_batched_{_suf}"] = _SIGS[f"blr_kfold_batched_{_suf}"]  # (the same argument list)
     _SIGS[f"blr_loo_multi_batched_{_suf}"] = (
         [_H, _int, _int, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _int, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _i64,
          _vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _vp], _int)
@@ -264,7 +265,7 @@ class Handle:
 
     def get_stat(self, key):
         """Counter of this handle: "i8_regressors", "i8_handed_back", "planes_redone", "loo_degenerate", "kfold_degenerate" (folds
-        blr_kfold_batched_* gave NaN), "workspace_bytes", "last_chunks" (chunks / slices of regressors of the most recent call: option MAX_CHUNK caps their size) (blr_get_stat)."""
+        blr_kfold_batched_* / blr_kfold_large_batched_* gave NaN), "workspace_bytes", "last_chunks" (chunks / slices of regressors of the most recent call: option MAX_CHUNK caps their size) (blr_get_stat)."""
         v = _i64()
         self.check(self.lib.blr_get_stat(self._h, str(key).encode(), C.byref(v)))
         return int(v.value)
@@ -390,6 +391,15 @@ class Handle:
         mean and variance per observation, ONE joint log density per fold, one total per regressor; include/blr_mi355x.h
         blr_kfold_batched_*."""
         fn = getattr(self.lib, f"blr_kfold_batched_{suffix(dtype)}")
+        return self.check(fn(self._h, memspace, layout, B, D, N, F, _ptr(X), ldx, strideX, _ptr(y), stridey, noise_kind, _ptr(s),
+                             strides, _ptr(mw), stridemw, _ptr(T), ldt, strideT, _ptr(kf_mean), stride_km, _ptr(kf_var),
+                             stride_kv, _ptr(kf_logpdf), stride_kl, _ptr(kf_total), _ptr(info)))
+
+    def kfold_large(self, dtype, memspace, layout, B, D, N, F, X, ldx, strideX, y, stridey, noise_kind, s, strides, mw, stridemw, T,
+                    ldt, strideT, kf_mean, stride_km, kf_var, stride_kv, kf_logpdf, stride_kl, kf_total, info):
+        """The same predictives for LARGE folds, removed in weight space: any F >= 1 with ceil(N / F) <= 1024, D <= 128; arguments
+        and outputs as `kfold`; include/blr_mi355x.h blr_kfold_large_batched_*."""
+        fn = getattr(self.lib, f"blr_kfold_large_batched_{suffix(dtype)}")
         return self.check(fn(self._h, memspace, layout, B, D, N, F, _ptr(X), ldx, strideX, _ptr(y), stridey, noise_kind, _ptr(s),
                              strides, _ptr(mw), stridemw, _ptr(T), ldt, strideT, _ptr(kf_mean), stride_km, _ptr(kf_var),
                              stride_kv, _ptr(kf_logpdf), stride_kl, _ptr(kf_total), _ptr(info)))

@@ -39,6 +39,7 @@
 #include "blr_state_cols.hpp"
 #include "blr_rand_multi.hpp"
 #include "blr_kfold.hpp"
+#include "blr_kfold_large.hpp"
 #include "blr_host.hpp"
 #include "blr_large_plan.hpp"
 
@@ -4162,6 +4163,187 @@ int kfold_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_t D,
   return io.finish();
 }
 
+// ---- exact leave-fold-out predictives for LARGE folds, removed in weight space (blr_kfold_large_batched_*, DESIGN.md K24;
+// blr_kfold_large.hpp) ---------------------------------------------------------------------------------------------------------------
+
+// statistics (+ reduce) and factorisation of one chunk: the launches that depend on the block count
+template <typename T, int NB>
+int kfold_large_nb(blr_handle* h, const KflArgs<T>& a, int64_t nb, bool vec_ok) {
+  using C = SmallCfg<T, NB>;
+  constexpr int SZ = kfl_stat_elems<T, NB>();
+  int rc;
+  void (*const factor)(KflArgs<T>) = kfl_factor_kernel<T, NB>;
+  if ((rc = set_lds_once(h, factor, (size_t)C::LDS_BYTES))) return rc;
+  const dim3 sgrid((unsigned)(a.nfolds * a.S), (unsigned)nb);
+  if constexpr (sizeof(T) == sizeof(double)) {
+    void (*const stats)(KflArgs<T>) = a.layout == BLR_LAYOUT_ROWVECS ? kfl_stats_kernel<T, NB, 1>
+                                      : (vec_ok ? kfl_stats_kernel<T, NB, 4> : kfl_stats_kernel<T, NB, 0>);
+    if ((rc = set_lds_once(h, stats, (size_t)C::LDS_BYTES))) return rc;
+    hipLaunchKernelGGL(stats, sgrid, dim3(kThreads), C::LDS_BYTES, h->stream, a);
+  } else {  // fp32: the statistics accumulated in double from the float rows (blr_kfold_large.hpp, kfl_stats32_kernel)
+    void (*const stats)(KflArgs<T>) = a.layout == BLR_LAYOUT_ROWVECS ? kfl_stats32_kernel<LAYOUT_ROWVECS> : kfl_stats32_kernel<LAYOUT_COLVECS>;
+    const size_t lds = kfl_stats32_lds_bytes(a.D);
+    if ((rc = set_lds_once(h, stats, lds))) return rc;
+    hipLaunchKernelGGL(stats, sgrid, dim3(kThreads), lds, h->stream, a);
+  }
+  HIP_TRY(h, hipGetLastError());
+  if (a.S > 1) {
+    hipLaunchKernelGGL(kfl_reduce_kernel<T>, dim3((unsigned)(nb * a.nfolds), 8), dim3(kThreads), 0, h->stream, a, SZ);
+    HIP_TRY(h, hipGetLastError());
+  }
+  hipLaunchKernelGGL(factor, dim3((unsigned)a.nfolds, (unsigned)nb), dim3(kThreads), C::LDS_BYTES, h->stream, a);
+  HIP_TRY(h, hipGetLastError());
+  return 0;
+}
+
+template <typename T>
+int kfold_large_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t N, int64_t F, const T* X, int64_t ldx,
+                        int64_t strideX, const T* y, int64_t stridey, int noise_kind, const T* s, int64_t strides, const T* mw,
+                        int64_t stridemw, const T* Tf, int64_t ldt, int64_t strideT, T* kf_mean, int64_t stride_km, T* kf_var,
+                        int64_t stride_kv, double* kf_logpdf, int64_t stride_kl, double* kf_total, int32_t* info) {
+  // (the argument checks come before the handle's: they need no device)
+  if (h) h->err.clear();
+  if (memspace != BLR_MEM_HOST && memspace != BLR_MEM_DEVICE) return bad_arg(h, 2, "memspace");
+  if (layout != BLR_LAYOUT_COLVECS && layout != BLR_LAYOUT_ROWVECS) return bad_arg(h, 3, "unknown layout (reference :26-31)");
+  if (B < 0 || B > (1 << 30)) return bad_arg(h, 4, "B out of range (0..2^30)");
+  if (D < 1 || D > kMaxSmallD) return bad_arg(h, 5, "D out of range (1..128)");
+  if (N < 0 || N > (1 << 30)) return bad_arg(h, 6, "N out of range (0..2^30)");
+  if (F < 1) return bad_arg(h, 7, "F < 1");
+  const int64_t nfolds = N == 0 ? 0 : (F >= N ? 1 : (N + F - 1) / F);
+  if (nfolds > kFoldLargeMaxFolds)
+    return bad_arg(h, 7, "ceil(N / F) > 1024: this route is for few, large folds (many small ones: blr_kfold_batched_*)");
+  if (N > 0 && !X) return bad_arg(h, 8, "X is NULL");
+  if (layout == BLR_LAYOUT_COLVECS ? ldx < D : ldx < std::max<int64_t>(N, 1)) return bad_arg(h, 9, "ldx too small");
+  if (strideX < 0) return bad_arg(h, 10, "strideX < 0");
+  if (N > 0 && !y) return bad_arg(h, 11, "y is NULL (reference :74 length check)");
+  if (stridey < 0) return bad_arg(h, 12, "stridey < 0");
+  if (noise_kind != BLR_NOISE_ISOTROPIC && noise_kind != BLR_NOISE_DIAGONAL)
+    return bad_arg(h, 13, "noise_kind (dense noise couples the folds: isotropic or diagonal only)");
+  if (N > 0 && !s) return bad_arg(h, 14, "s is NULL");
+  if (strides < 0) return bad_arg(h, 15, "strides < 0");
+  if (!mw) return bad_arg(h, 16, "mw is NULL");
+  if (stridemw < 0) return bad_arg(h, 17, "stridemw < 0");
+  if (!Tf) return bad_arg(h, 18, "T is NULL");
+  if (ldt < D) return bad_arg(h, 19, "ldt < D");
+  if (strideT < 0) return bad_arg(h, 20, "strideT < 0");
+  if (kf_mean && B > 1 && stride_km < N) return bad_arg(h, 22, "stride_km < N");
+  if (kf_var && B > 1 && stride_kv < N) return bad_arg(h, 24, "stride_kv < N");
+  if (kf_logpdf && B > 1 && stride_kl < nfolds) return bad_arg(h, 26, "stride_kl < ceil(N / F)");
+  if (!info) return bad_arg(h, 28, "info is NULL");
+  if (!h) return -1;
+  h->last_chunks = 1;  // (a route with a chunk loop counts its own)
+  if (B == 0) return 0;
+  HIP_TRY(h, hipSetDevice(h->device));
+
+  CallIO io(h, memspace);
+  KflArgs<T> k{};
+  k.ldx = ldx; k.strideX = strideX; k.stridey = stridey; k.strides = strides; k.stridemw = stridemw; k.ldt = ldt; k.strideT = strideT;
+  k.stride_km = stride_km; k.stride_kv = stride_kv; k.stride_kl = stride_kl;
+  k.layout = layout; k.noise_kind = noise_kind; k.D = (int)D; k.N = (int)N; k.F = (int)std::min<int64_t>(F, std::max<int64_t>(N, 1));
+  k.nfolds = (int)nfolds;
+  const size_t x_one = N == 0 ? 0 : (layout == BLR_LAYOUT_COLVECS ? mat_extent(D, N, ldx) : mat_extent(N, D, ldx));
+  const size_t s_one = N == 0 ? 0 : (noise_kind == BLR_NOISE_DIAGONAL ? (size_t)N : 1);
+  const size_t n_out = (size_t)N;
+  int rc;
+  double* tot_d = nullptr;
+  int32_t* info_d = nullptr;
+  if ((rc = io.in(X, x_one ? extent(B, strideX, x_one) : 0, &k.X))) return rc;
+  if ((rc = io.in(y, n_out ? extent(B, stridey, n_out) : 0, &k.y))) return rc;
+  if ((rc = io.in(s, s_one ? extent(B, strides, s_one) : 0, &k.s))) return rc;
+  if ((rc = io.in(mw, extent(B, stridemw, (size_t)D), &k.mw))) return rc;
+  if ((rc = io.in(Tf, extent(B, strideT, mat_extent(D, D, ldt)), &k.Tf))) return rc;
+  if ((rc = io.out(kf_mean, n_out ? extent(B, stride_km, n_out) : 0, &k.km))) return rc;
+  if ((rc = io.out(kf_var, n_out ? extent(B, stride_kv, n_out) : 0, &k.kv))) return rc;
+  if ((rc = io.out(kf_logpdf, n_out ? extent(B, stride_kl, (size_t)nfolds) : 0, &k.kl))) return rc;
+  if ((rc = io.out(kf_total, (size_t)B, &tot_d))) return rc;
+  if ((rc = io.out(info, (size_t)B, &info_d))) return rc;
+  k.info = info_d;
+  if ((rc = ensure_stats(h))) return rc;
+  k.degenerate = h->stats_dev + 4;
+
+  // status: loo_check_kernel as blr_loo_batched_* launches it
+  const int64_t ychunk = h->cap_chunk(65535);  // grid.x <= 65535 here: the check and the empty totals
+  h->count_chunks(B, ychunk);
+  for (int64_t b0 = 0; b0 < B; b0 += ychunk)
+    hipLaunchKernelGGL(loo_check_kernel<T>, dim3((unsigned)std::min<int64_t>(ychunk, B - b0)), dim3(kThreads), 0, h->stream,
+                       k.Tf + b0 * strideT, ldt, strideT, (int)D, k.s + b0 * strides, strides, noise_kind, (int)N, info_d + b0);
+  HIP_TRY(h, hipGetLastError());
+  if (N == 0) {  // an empty sum, for the regressors whose state passed the check
+    for (int64_t b0 = 0; tot_d && b0 < B; b0 += ychunk)
+      hipLaunchKernelGGL(loo_total_kernel, dim3((unsigned)std::min<int64_t>(ychunk, B - b0)), dim3(kThreads), 0, h->stream,
+                         (const double*)nullptr, (int64_t)0, 0, tot_d, (const int32_t*)info_d, (int)b0);
+    HIP_TRY(h, hipGetLastError());
+    return io.finish();
+  }
+
+  // Per chunk of regressors: the state matrix, the folds' statistics (+ reduce), their factors, the images of the factors, the
+  // predictions, the totals -- the same launches whatever B and the fold count are.  Chunks: grid.y / grid.z <= 65535; the statistics,
+  // the factors and the images within 256 MiB each; at least one regressor
+  int S = 1, cols = 64;
+  kfl_splits(k.F, &S, &cols);
+  k.S = S;
+  const int NB = (int)(D + 15) / 16, DP = 16 * NB;
+  const size_t packed = (size_t)DP * (DP + 1) / 2, SZ = packed + DP;
+  const size_t stats_one = (size_t)nfolds * S * SZ * sizeof(double), U_one = (size_t)nfolds * D * D * sizeof(T);
+  const bool kl_ws = tot_d && !k.kl;  // the totals need the folds' log densities somewhere
+  const bool predict = k.km || k.kv;
+  const size_t bound = (size_t)256 << 20;
+  int64_t chunk = std::min<int64_t>(std::min<int64_t>(B, 65535), MargImages<T>::kMaxChunk / nfolds);
+  chunk = std::min<int64_t>(chunk, (int64_t)(bound / stats_one));
+  chunk = std::max<int64_t>(1, std::min<int64_t>(chunk, (int64_t)(bound / U_one)));
+  chunk = h->cap_chunk(chunk);
+  h->count_chunks(B, chunk);
+  Carve carve;
+  const size_t nrf = (size_t)chunk * nfolds;
+  const size_t o_st = carve((size_t)chunk * stats_one), o_U = carve((size_t)chunk * U_one), o_A = carve((size_t)chunk * packed * sizeof(double));
+  const size_t o_ld = carve((size_t)chunk * sizeof(double)), o_sc = carve(nrf * S * 2 * sizeof(double));
+  const size_t o_mw = carve(nrf * D * sizeof(T)), o_fi = carve(nrf * sizeof(int32_t)), o_kl = carve(kl_ws ? nrf * sizeof(double) : 0);
+  if ((rc = h->cov_ws.reserve(h, carve.off))) return rc;
+  char* const ws = h->cov_ws.p;
+  k.stats = reinterpret_cast<double*>(ws + o_st); k.U = reinterpret_cast<T*>(ws + o_U); k.A = reinterpret_cast<double*>(ws + o_A);
+  k.ldA = reinterpret_cast<double*>(ws + o_ld); k.scal = reinterpret_cast<double*>(ws + o_sc); k.mwf = reinterpret_cast<T*>(ws + o_mw);
+  k.finfo = reinterpret_cast<int32_t*>(ws + o_fi);
+  const size_t lds_s = kfl_state_lds_bytes(sizeof(T), (int)D), lds_p = kfl_predict_lds_bytes(sizeof(T), (int)D);
+  void (*const pred)(KflArgs<T>) = layout == BLR_LAYOUT_ROWVECS ? kfl_predict_kernel<T, LAYOUT_ROWVECS> : kfl_predict_kernel<T, LAYOUT_COLVECS>;
+  void (*const state)(KflArgs<T>) = kfl_state_kernel<T>;
+  if ((rc = set_lds_once(h, state, lds_s))) return rc;
+  if (predict && (rc = set_lds_once(h, pred, lds_p))) return rc;
+  if (predict && (rc = MargImages<T>::reserve(h, chunk * nfolds))) return rc;
+  const bool vec_ok = layout == BLR_LAYOUT_COLVECS && D % Mfma<T>::VEC == 0 && aligned16(k.X, ldx, strideX);
+  const int64_t ntiles = ((int64_t)k.F + kCovTile - 1) / kCovTile;
+  for (int64_t b0 = 0; b0 < B; b0 += chunk) {
+    const int64_t nb = std::min<int64_t>(chunk, B - b0);
+    KflArgs<T> c = k;
+    c.reg0 = (int)b0;
+    if (kl_ws) { c.kl = reinterpret_cast<double*>(ws + o_kl) - b0 * nfolds; c.stride_kl = nfolds; }  // (indexed by the global regressor)
+    hipLaunchKernelGGL(state, dim3((unsigned)nb), dim3(kThreads), lds_s, h->stream, c);
+    HIP_TRY(h, hipGetLastError());
+    switch (NB) {
+      case 1: rc = kfold_large_nb<T, 1>(h, c, nb, vec_ok); break;
+      case 2: rc = kfold_large_nb<T, 2>(h, c, nb, vec_ok); break;
+      case 3: rc = kfold_large_nb<T, 3>(h, c, nb, vec_ok); break;
+      case 4: rc = kfold_large_nb<T, 4>(h, c, nb, vec_ok); break;
+      case 5: rc = kfold_large_nb<T, 5>(h, c, nb, vec_ok); break;
+      case 6: rc = kfold_large_nb<T, 6>(h, c, nb, vec_ok); break;
+      case 7: rc = kfold_large_nb<T, 7>(h, c, nb, vec_ok); break;
+      default: rc = kfold_large_nb<T, 8>(h, c, nb, vec_ok); break;
+    }
+    if (rc) return rc;
+    if (predict) {
+      // the factors of the chunk's folds as images (a fold without a factor is skipped by its status word), then the folds' rows
+      // against them; every workgroup amortises its set-up (the image) over its tiles: about two workgroups per CU in all
+      c.img = MargImages<T>::launch(h, c.U, D, D * D, (int)D, (const int32_t*)c.finfo, 0, nb * nfolds);
+      c.ngroups = (int)std::max<int64_t>(1, std::min<int64_t>(ntiles, (2 * (int64_t)h->cus + nb * nfolds - 1) / (nb * nfolds)));
+      hipLaunchKernelGGL(pred, dim3((unsigned)c.ngroups, (unsigned)nfolds, (unsigned)nb), dim3(kThreads), lds_p, h->stream, c);
+    }
+    if (tot_d)
+      hipLaunchKernelGGL(loo_total_kernel, dim3((unsigned)nb), dim3(kThreads), 0, h->stream, (const double*)c.kl, c.stride_kl, (int)nfolds,
+                         tot_d, (const int32_t*)info_d, (int)b0);
+    HIP_TRY(h, hipGetLastError());
+  }
+  return io.finish();
+}
+
 // ---- rank-k update / downdate of a resident MULTI-OUTPUT state: one factor, S mean columns (blr_update_multi_factor_*,
 // blr_downdate_multi_factor_*; blr_state_cols.hpp) ---------------------------------------------------------------------
 
@@ -4454,7 +4636,7 @@ int blr_get_stat(blr_handle* h, const char* key, int64_t* value) {
     *value = (int64_t)v;
     return 0;
   }
-  if (!strcmp(key, "kfold_degenerate")) {  // folds blr_kfold_batched_* gave NaN: a pivot of I - H~ <= 0 or not finite (cumulative)
+  if (!strcmp(key, "kfold_degenerate")) {  // folds blr_kfold_batched_* / blr_kfold_large_batched_* gave NaN: a pivot <= 0 or not finite (cumulative)
     unsigned long long v = 0;
     if (h->stats_dev) {
       HIP_TRY(h, hipSetDevice(h->device));
@@ -4574,6 +4756,16 @@ int blr_timer_stop(blr_handle* h, float* elapsed_ms) {
     return kfold_batched<T>(h, memspace, layout, B, D, N, F, X, ldx, strideX, y, stridey, noise_kind, s, strides,    \
                             mw, stridemw, Tf, ldt, strideT, kf_mean, stride_km, kf_var, stride_kv, kf_logpdf,       \
                             stride_kl, kf_total, info);                                                            \
+  }                                                                                                                 \
+  int blr_kfold_large_batched_##SUF(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t N,     \
+                                    int64_t F, const T* X, int64_t ldx, int64_t strideX, const T* y, int64_t stridey, \
+                                    int noise_kind, const T* s, int64_t strides, const T* mw, int64_t stridemw,     \
+                                    const T* Tf, int64_t ldt, int64_t strideT, T* kf_mean, int64_t stride_km,       \
+                                    T* kf_var, int64_t stride_kv, double* kf_logpdf, int64_t stride_kl,             \
+                                    double* kf_total, int32_t* info) {                                              \
+    return kfold_large_batched<T>(h, memspace, layout, B, D, N, F, X, ldx, strideX, y, stridey, noise_kind, s,      \
+                                  strides, mw, stridemw, Tf, ldt, strideT, kf_mean, stride_km, kf_var, stride_kv,   \
+                                  kf_logpdf, stride_kl, kf_total, info);                                            \
   }                                                                                                                 \
   int blr_logpdf_grid_##SUF(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t N, const T* X,  \
                             int64_t ldx, int64_t strideX, const T* y, int64_t stridey, int noise_kind, const T* s, \

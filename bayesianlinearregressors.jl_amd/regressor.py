@@ -27,7 +27,7 @@ __all__ = [
     "BayesianLinearRegressor", "BasisFunctionRegressor", "BLRFunctionSample", "FiniteGP",
     "mean", "var", "cov", "std", "mean_and_var", "mean_and_cov", "marginals", "rand", "rand_b", "logpdf", "posterior",
     "LOO", "loo", "loo_map", "loo_columns", "loo_columns_map",
-    "KFold", "kfold", "kfold_map",
+    "KFold", "kfold", "kfold_map", "kfold_large", "kfold_large_map", "cross_validate",
     "EvidenceGrid", "logpdf_grid", "posterior_best", "logpdf_grid_map",
     "posterior_ragged", "logpdf_ragged",
     "posterior_columns", "logpdf_columns_map", "posterior_columns_map",
@@ -971,16 +971,18 @@ density of its observations given the rest (logpdf, float64, ceil(N / fold_size)
 score).  A fold the state does not contain (a pivot of I - H~ <= 0) has NaN entries (blr_get_stat "kfold_degenerate")."""
 
 
-def _kfold_call(h, dtype, layout, B, D, N, F, dX, ldx, strideX, dy, stridey, noise_kind, ds, strides, d_mw, stridemw, d_T, strideT, temps):
-    """blr_kfold_batched_* on device operands -> (mean [B, N], var [B, N], logpdf [B, nfolds], total [B], info [B]) on the host."""
+def _kfold_call(h, dtype, layout, B, D, N, F, dX, ldx, strideX, dy, stridey, noise_kind, ds, strides, d_mw, stridemw, d_T, strideT, temps,
+                large=False):
+    """blr_kfold_batched_* (``large``: blr_kfold_large_batched_*) on device operands -> (mean [B, N], var [B, N], logpdf [B, nfolds],
+    total [B], info [B]) on the host."""
     item = np.dtype(dtype).itemsize
     nf = -(-N // F)
     outs = [_DeviceBuffer(h, B * N * item), _DeviceBuffer(h, B * N * item), _DeviceBuffer(h, B * nf * 8), _DeviceBuffer(h, B * 8),
             _DeviceBuffer.of(h, np.zeros(B, dtype=np.int32))]
     temps.extend(outs)
     d_km, d_kv, d_kl, d_tot, d_info = (b.ptr for b in outs)
-    h.kfold(dtype, _abi.MEM_DEVICE, layout, B, D, N, F, dX, ldx, strideX, dy, stridey, noise_kind, ds, strides, d_mw, stridemw, d_T,
-            max(D, 1), strideT, d_km, N, d_kv, N, d_kl, nf, d_tot, d_info)
+    (h.kfold_large if large else h.kfold)(dtype, _abi.MEM_DEVICE, layout, B, D, N, F, dX, ldx, strideX, dy, stridey, noise_kind, ds, strides,
+                                          d_mw, stridemw, d_T, max(D, 1), strideT, d_km, N, d_kv, N, d_kl, nf, d_tot, d_info)
     m, v = np.empty((B, N), dtype=dtype), np.empty((B, N), dtype=dtype)
     lp, tot, info = np.empty((B, nf), dtype=np.float64), np.empty(B, dtype=np.float64), np.zeros(B, dtype=np.int32)
     for host, dptr in ((m, d_km), (v, d_kv), (lp, d_kl), (tot, d_tot), (info, d_info)):
@@ -995,10 +997,11 @@ def _fold_size(fold_size):
     return F
 
 
-def _loo_batch(probs, dtype, fold_size=None):
+def _loo_batch(probs, dtype, fold_size=None, large=False):
     """LOO of equally shaped problems: their data staged once, blr_posterior_batched_* into device buffers (mw', T) -- any prior
     kind, the usual routes -- then blr_loo_batched_* on the same device inputs.  Nothing D x D comes back to the host.
-    ``fold_size``: the same pipeline with blr_kfold_batched_* as its second half -> KFold records."""
+    ``fold_size``: the same pipeline with blr_kfold_batched_* (``large``: blr_kfold_large_batched_*) as its second half -> KFold
+    records."""
     X0, layout, ldx, D, N, _, _, noise_kind, _, _, prior_kind, ldl = probs[0]
     nb, h, item = len(probs), _handle(), np.dtype(dtype).itemsize
     Xb = np.stack([q[0].reshape(-1, order="A") for q in probs])
@@ -1027,7 +1030,7 @@ def _loo_batch(probs, dtype, fold_size=None):
                                             sb.shape[1], d_mwp, D, d_T, D * D, temps)
         elif not np.any(info):
             m, v, lp, tot, info = _kfold_call(h, dtype, layout, nb, D, N, fold_size, dX, ldx, Xb.shape[1], dy, yb.shape[1], noise_kind,
-                                              ds, sb.shape[1], d_mwp, D, d_T, D * D, temps)
+                                              ds, sb.shape[1], d_mwp, D, d_T, D * D, temps, large)
     finally:
         for b in temps:
             b.free()
@@ -1132,6 +1135,100 @@ def kfold_map(fxs, ys, fold_size):
     if len(sig) != 1 or probs[0][3] == 0 or probs[0][4] == 0:
         return one_by_one(probs)
     return _loo_batch(probs, dtype, F)
+
+
+_KFOLD_LARGE_MAX_D = 128      # blr_kfold_large_batched_*: the fold's D x D factorisation lives in LDS
+_KFOLD_LARGE_MAX_FOLDS = 1024  # ... and the route is for few, large folds
+
+
+def _fold_size_large(fold_size):
+    F = int(fold_size)
+    if F != fold_size or F < 1:
+        raise ValueError("fold_size must be an integer >= 1")
+    return F
+
+
+def _kfold_large_check(D, N, F, what):
+    """The limits of blr_kfold_large_batched_* that depend on the problem, with Python's exceptions instead of argument errors."""
+    if D > _KFOLD_LARGE_MAX_D:
+        raise NotImplementedError(f"{what}: D = {D} is beyond the limit of blr_kfold_large_batched_* (D <= {_KFOLD_LARGE_MAX_D})")
+    if -(-N // F) > _KFOLD_LARGE_MAX_FOLDS:
+        raise ValueError(f"{what}: ceil(N / fold_size) = {-(-N // F)} folds; at most {_KFOLD_LARGE_MAX_FOLDS} (many small folds: kfold)")
+
+
+def _perm_of(perm, y):
+    if perm is None:
+        return None
+    perm = np.asarray(perm, dtype=np.int64)
+    n = np.asarray(y).shape[0] if np.ndim(y) == 1 else -1
+    if perm.shape != (n,) or not np.array_equal(np.sort(perm), np.arange(n)):
+        raise ValueError("perm must be a permutation of range(N)")
+    return perm
+
+
+def kfold_large(fx, y, fold_size, perm=None):
+    """`kfold` for LARGE folds (include/blr_mi355x.h blr_kfold_large_batched_*): any integer fold_size >= 1 with
+    ceil(N / fold_size) <= 1024 -- the K = 5 or 10 folds of N / K observations of ordinary cross-validation.  The fold is removed in
+    weight space (one D x D factorisation per fold), so D <= 128 (NotImplementedError beyond) and a fold that carries nearly all of the
+    state's information loses digits (float32 first).  ``perm`` and the KFold record as for `kfold`; fold_size > N is one fold, the
+    predictive under the prior."""
+    F = _fold_size_large(fold_size)
+    dtype = _dtype_of(fx.f.blr.mw if isinstance(fx.f, BasisFunctionRegressor) else fx.f.mw, y)
+    perm = _perm_of(perm, y)
+    q = _loo_problem(fx, y, dtype, "kfold_large", perm)
+    _kfold_large_check(q[3], q[4], F, "kfold_large")
+    r = _loo_batch([q], dtype, F, large=True)[0]
+    if perm is None:
+        return r
+    m, v = np.empty_like(r.mean), np.empty_like(r.var)
+    m[perm], v[perm] = r.mean, r.var
+    return KFold(m, v, r.logpdf, r.total)
+
+
+def kfold_large_map(fxs, ys, fold_size):
+    """[kfold_large(fx, y, fold_size) for fx, y in zip(fxs, ys)] in one posterior call and one blr_kfold_large_batched_* call for
+    equally shaped problems (else one call per problem, as `kfold_map`).  The first problem whose prior, noise or posterior is not
+    positive definite raises PosDefException with its position as ``index``."""
+    F = _fold_size_large(fold_size)
+    fxs, ys = list(fxs), list(ys)
+    if len(fxs) != len(ys):
+        raise ValueError("as many observation vectors as finite regressors are needed")
+    if not fxs:
+        return []
+    dtype = np.float32 if all(_dtype_of(fx.f.blr.mw if isinstance(fx.f, BasisFunctionRegressor) else fx.f.mw, y) == np.float32
+                              for fx, y in zip(fxs, ys)) else np.float64
+
+    def one_by_one(probs):
+        out = []
+        for i, q in enumerate(probs):
+            try:
+                out.append(_loo_batch([q], dtype, F, large=True)[0])
+            except _abi.PosDefException as e:
+                e.index = i
+                raise
+        return out
+
+    probs = [_loo_problem(fx, y, dtype, "kfold_large") for fx, y in zip(fxs, ys)]
+    for q in probs:
+        _kfold_large_check(q[3], q[4], F, "kfold_large_map")
+    if any(isinstance(fx.f, BasisFunctionRegressor) and isinstance(fx.f.phi, RandomFourierFeatures) for fx in fxs):
+        return one_by_one(probs)
+    sig = {(q[0].shape, q[0].flags.f_contiguous, q[1], q[3], q[4], q[7], q[10],
+            isinstance((fx.f.blr if isinstance(fx.f, BasisFunctionRegressor) else fx.f).Lw, PDMat)) for q, fx in zip(probs, fxs)}
+    if len(sig) != 1 or probs[0][3] == 0 or probs[0][4] == 0:
+        return one_by_one(probs)
+    return _loo_batch(probs, dtype, F, large=True)
+
+
+def cross_validate(fx, y, n_folds, perm=None):
+    """K-fold cross-validation with ``n_folds`` contiguous folds of F = ceil(N / n_folds) observations (random folds with ``perm``):
+    `kfold` when F <= 64, else `kfold_large`.  Returns KFold(mean, var, logpdf, total); total is the CV score."""
+    K = int(n_folds)
+    if K != n_folds or K < 1:
+        raise ValueError("n_folds must be an integer >= 1")
+    N = np.asarray(y).shape[0] if np.ndim(y) == 1 else 0
+    F = max(1, -(-N // K))
+    return kfold(fx, y, F, perm) if F <= 64 else kfold_large(fx, y, F, perm)
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -1606,6 +1703,36 @@ class ResidentPosterior:
                 raise NotImplementedError("ResidentPosterior.kfold takes scalar or diagonal noise (dense noise couples the folds)")
             m, v, lp, tot, info = _kfold_call(h, dtype, layout, 1, D, N, F, dX, ldx, 0, dev(y), 0, noise_kind, dev(s), 0, self._mw.ptr,
                                               0, self._T.ptr, 0, temps)
+        finally:
+            for b in temps:
+                b.free()
+        if info[0] != 0:
+            raise _abi.PosDefException(int(info[0]))
+        return KFold(m[0], v[0], lp[0], float(tot[0]))
+
+    def kfold_large(self, x, Sy, y, fold_size):
+        """`kfold` for LARGE folds: any integer ``fold_size`` >= 1 with ceil(N / fold_size) <= 1024, D <= 128
+        (blr_kfold_large_batched_*, B = 1, on the resident pointers; the state is not touched).  Returns KFold(mean, var, logpdf,
+        total); a state with a non-positive diagonal entry or a non-positive variance raises PosDefException(info)."""
+        F = _fold_size_large(fold_size)
+        dtype, h, D = self.dtype, self._h, self.D
+        temps = []
+
+        def dev(a):
+            temps.append(_DeviceBuffer.of(h, a))
+            return temps[-1].ptr
+
+        try:
+            dX, layout, ldx, N = self._inputs(x, dev, temps)
+            y = np.ascontiguousarray(y, dtype=dtype)
+            if y.shape != (N,):
+                raise ValueError("length(y) != number of inputs")  # reference :74
+            s, noise_kind = _noise(Sy, N, dtype)
+            if noise_kind == _abi.NOISE_DENSE:
+                raise NotImplementedError("ResidentPosterior.kfold_large takes scalar or diagonal noise (dense noise couples the folds)")
+            _kfold_large_check(D, N, F, "ResidentPosterior.kfold_large")
+            m, v, lp, tot, info = _kfold_call(h, dtype, layout, 1, D, N, F, dX, ldx, 0, dev(y), 0, noise_kind, dev(s), 0, self._mw.ptr,
+                                              0, self._T.ptr, 0, temps, large=True)
         finally:
             for b in temps:
                 b.free()

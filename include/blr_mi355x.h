@@ -98,7 +98,8 @@ const char* blr_last_route(blr_handle* h);
  * through the exact row maxima and the planes pass a second time (one more read of X; option NO_SPEC_ROWMAX = 1 always takes the exact
  * maxima: one more read of X on every call); "loo_degenerate" = observations blr_loo_batched_* gave NaN because their 1 - h_n was
  * <= 0 or not finite (reading it synchronises the handle's stream); "kfold_degenerate" = folds blr_kfold_batched_* gave NaN because
- * the Cholesky of their I - H~ met a pivot <= 0 or not finite (reading it synchronises the handle's stream); "last_chunks" = chunks / slices of regressors the handle's most
+ * the Cholesky of their I - H~ met a pivot <= 0 or not finite, and folds blr_kfold_large_batched_* gave NaN because that of their
+ * A - G_f did (reading it synchronises the handle's stream); "last_chunks" = chunks / slices of regressors the handle's most
  * recent call launched (NOT cumulative: every entry point starts it at 1; a batch beyond grid.y = 65535, a workspace or image bound, or
  * option MAX_CHUNK, goes in several); "workspace_bytes" = device scratch the handle holds now.
  * -> 0, -2 unknown key, -3 NULL value. */
@@ -923,6 +924,72 @@ int blr_kfold_batched_f32(blr_handle* h, int memspace, int layout, int64_t B, in
                           int64_t strides, const float* mw, int64_t stridemw, const float* T, int64_t ldt, int64_t strideT,
                           float* kf_mean, int64_t stride_km, float* kf_var, int64_t stride_kv, double* kf_logpdf,
                           int64_t stride_kl, double* kf_total, int32_t* info);
+
+/* ---- exact LEAVE-FOLD-OUT (K-fold) predictives for LARGE folds: the fold is removed in weight space -------------------------
+ * Replaces: a loop of blr_downdate_factor_* (forget the fold) / blr_marginals_batched_* (predict it) / blr_update_factor_* (put it
+ * back) per fold and regressor, or K refits through blr_posterior_batched_* on the other folds' data; reference
+ * src/bayesian_linear_regression.jl:55-58 (logpdf) of each held-out fold given the rest.  blr_kfold_batched_* computes the same
+ * quantities in observation space and stops at folds of 64; the K-fold cross-validation people run has K = 5 or 10, folds of N / K.
+ * Arguments, outputs, shapes and strides are those of blr_kfold_batched_*, in the same order: the state (mw, T), T upper, only its
+ * upper triangle is read, NOT modified, conditioned on a data set that contains the N observations (X, y, s); fold f is
+ * [f F, min((f + 1) F, N)) with n_f members, nfolds = ceil(N / F).  With A = T'T and r0_n = y_n - x_n'mw:
+ *   G_f = X_f S_f^-1 X_f'    d_f = X_f S_f^-1 r0    q_f = r0' S_f^-1 r0    l_f = sum log s_n      (one pass over the fold's rows)
+ *   A_f = A - G_f = U_f'U_f                       (positive definite iff the state really contains the fold)
+ *   u_f = U_f^-T d_f,   mw_f = mw - U_f^-1 u_f
+ *   kf_mean_n = x_n'mw_f                               (predictive mean of y_n given all the other FOLDS)
+ *   kf_var_n  = s_n + |U_f^-T x_n|^2                   (noise included, as var(fx) includes Sigma_y)
+ *   kf_logpdf[f] = -1/2 [n_f log 2 pi + l_f + logdet A - logdet A_f + q_f + |u_f|^2]   (the JOINT density of the fold; double)
+ *   kf_total[b] = sum_f kf_logpdf[f] in a fixed order (the K-fold CV score; double).
+ * Precision: A_f, its factor, mw_f, kf_mean and kf_var are in the element type; A = T'T, G_f and d_f are accumulated in double
+ * from the element-type inputs in both element types and the difference A - G_f is rounded to the element type once; q_f, l_f, the
+ * two logdet, |u_f|^2, kf_logpdf and kf_total are double in both element types.  Cancellation: A - G_f subtracts what the fold contributed from
+ * everything the state knows.  A fold that carries nearly all of the state's information leaves a small difference of large numbers
+ * and loses that many digits (a fold with 19/20 of the information: a factor of about 20 in every output); float32 shows it first.
+ * Outputs: kf_mean and kf_var [N] per regressor in the element type, kf_logpdf [nfolds] per regressor, kf_total [B].  Any of them may
+ * be NULL; with kf_total requested and kf_logpdf NULL the log densities go through handle workspace.  A stride of 0 shares an input
+ * (strideX, stridey, strides, stridemw and strideT included).
+ * Sizes: 1 <= D <= 128.  F >= 1 with ceil(N / F) <= 1024: this route is for few, large folds, many small ones belong to
+ * blr_kfold_batched_*.  F > N is allowed: one fold, the predictive under the state minus ALL of the data.  0 <= N <= 2^30.  Isotropic
+ * or diagonal noise; dense noise is an argument error (it couples the folds).  ColVecs or RowVecs with any ldx, host or device
+ * memspace.
+ * No-ops: B = 0 returns 0 and touches nothing; N = 0 gives kf_total = 0 and info = 0 (for a state that passes the check).
+ * Argument errors (negative position, those of blr_kfold_batched_*; checked before the handle, so a NULL handle with valid arguments
+ * returns -1): memspace (2), layout (3), B (4), D (5; D > 128 included), N (6) out of range, F < 1 or ceil(N / F) > 1024 (7), ldx too
+ * small (9), dense noise (13), ldt < D (19), a negative input stride (10, 12, 15, 17, 20), a NULL X / y / s (N > 0; 8, 11, 14) / mw
+ * (16) / T (18) / info (28), and for B > 1 overlapping outputs: stride_km < N (22), stride_kv < N (24), stride_kl < nfolds (26).
+ * info[B], as blr_loo_batched_* and in its order: T has a non-positive diagonal entry j -> j, else s_i is not positive -> i; every
+ * output of such a regressor is left untouched; the call returns 0.
+ * NaN rule: a fold whose factorisation of A_f meets a pivot <= 0 or not finite (the state does not contain the fold, or the fold
+ * carries all of the state's information to within rounding) gets NaN in kf_mean and kf_var of all its members and in its
+ * kf_logpdf, and so in kf_total; it is counted once by blr_get_stat "kfold_degenerate".  Every other fold of the regressor keeps
+ * its bits.
+ * Bit promises: results are bit-reproducible from call to call; the bits of a regressor do not depend on B, on its position in the
+ * batch, on the chunking or on the other regressors; the bits of fold f depend only on that regressor's T and mw and on the fold's
+ * own X, y, s and row count -- not on N or on the other folds; the bits of one output do not depend on which others are
+ * requested; host and device memspace give the same bits.  No float atomics.  NOT promised: bit-equality with blr_kfold_batched_*
+ * (the two work in different spaces; they agree to rounding at F <= 64).
+ * Kernels (csrc/blr_kfold_large.hpp), a fixed number of launches per chunk of regressors whatever B and the fold
+ * count are: the status (loo_check_kernel); A = T'T in the packed layout and logdet A (kfl_state_kernel); the statistics of every
+ * (regressor, fold, column block), centred at the state's mean: in fp64 by the streaming Gram phase of the posterior kernel without
+ * a prior (kfl_stats_kernel), in fp32 by kfl_stats32_kernel, which widens the float rows and accumulates in double on the fp64
+ * matrix instruction (the column blocks of a fold follow from n_f alone; kfl_reduce_kernel adds them in a fixed order when a fold
+ * has more than one); one workgroup per (regressor, fold) factors A - G_f in LDS, solves for mw_f and writes kf_logpdf[f]
+ * (kfl_factor_kernel); for kf_mean / kf_var the triangular inverses of the U_f as MFMA images (marg_image_kernel) and
+ * kfl_predict_kernel over (64-input tiles of a fold, fold, regressor), rows bounded to the fold; the totals (loo_total_kernel).  X is
+ * read twice per call whatever the fold count is.  Workspace per (regressor, fold): the statistics, D^2 elements of U_f, D of mw_f
+ * and one image; the regressors go in chunks that keep each of these buffers within 256 MiB and grid.y <= 65535, never fewer than
+ * one regressor (option MAX_CHUNK and blr_get_stat "last_chunks" are honoured).  An async handle in device memspace only enqueues.
+ * _f32: X, y, s, mw, T, kf_mean, kf_var are float; kf_logpdf and kf_total stay double. */
+int blr_kfold_large_batched_f64(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t N, int64_t F, const double* X,
+                                int64_t ldx, int64_t strideX, const double* y, int64_t stridey, int noise_kind, const double* s,
+                                int64_t strides, const double* mw, int64_t stridemw, const double* T, int64_t ldt, int64_t strideT,
+                                double* kf_mean, int64_t stride_km, double* kf_var, int64_t stride_kv, double* kf_logpdf,
+                                int64_t stride_kl, double* kf_total, int32_t* info);
+int blr_kfold_large_batched_f32(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t N, int64_t F, const float* X,
+                                int64_t ldx, int64_t strideX, const float* y, int64_t stridey, int noise_kind, const float* s,
+                                int64_t strides, const float* mw, int64_t stridemw, const float* T, int64_t ldt, int64_t strideT,
+                                float* kf_mean, int64_t stride_km, float* kf_var, int64_t stride_kv, double* kf_logpdf,
+                                int64_t stride_kl, double* kf_total, int32_t* info);
 
 /* ---- evidence of one data set under a GRID of (prior scale, noise scale) settings, from one pass over the data ------------
  * Replaces: blr_posterior_batched_* called with strideX = 0, stridey = 0 and one scaled (s, Lw) pair per setting, which re-forms

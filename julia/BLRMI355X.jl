@@ -1235,6 +1235,39 @@ function kfold!(km::Union{Nothing,DeviceArray{T}}, kv::Union{Nothing,DeviceArray
 end
 
 """
+    kfold_large!(kmean, kvar, klogpdf, total, info, X, y, s, mw, T; D, N, F, B, isotropic)
+
+The leave-fold-out predictives of `kfold!` for LARGE folds (`blr_kfold_large_batched_*`): any F ≥ 1 with cld(N, F) ≤ 1024, so the
+K = 5 or 10 folds of N / K observations people cross-validate with; D ≤ 128.  The fold is removed in weight space: one D×D
+factorisation of `T'T − X_f S_f⁻¹ X_f'` per fold from statistics gathered in one pass over X.  Operands, outputs and the NaN
+rule as for `kfold!`; a fold that carries nearly all of the state's information loses digits in the difference (Float32 first).
+"""
+function kfold_large!(km::Union{Nothing,DeviceArray{T}}, kv::Union{Nothing,DeviceArray{T}}, kl::Union{Nothing,DeviceArray{Float64}},
+                      total::Union{Nothing,DeviceArray{Float64}}, info::DeviceArray{Int32}, X::DeviceArray{T}, y::DeviceArray{T},
+                      s::DeviceArray{T}, mw::DeviceArray{T}, Tf::DeviceArray{T}; D::Int, N::Int, F::Int, B::Int, isotropic::Bool) where {T<:Elt}
+    h = handle()
+    nk = isotropic ? ISOTROPIC : DIAGONALN
+    nf = cld(N, F)
+    ptr(a) = a === nothing ? Ptr{T}(C_NULL) : a.ptr
+    dptr(a) = a === nothing ? Ptr{Cdouble}(C_NULL) : a.ptr
+    rc = if T === Float64
+        ccall((:blr_kfold_large_batched_f64, LIB), Cint,
+              (Ptr{Cvoid}, Cint, Cint, Int64, Int64, Int64, Int64, Ptr{T}, Int64, Int64, Ptr{T}, Int64, Cint, Ptr{T}, Int64, Ptr{T}, Int64,
+               Ptr{T}, Int64, Int64, Ptr{T}, Int64, Ptr{T}, Int64, Ptr{Cdouble}, Int64, Ptr{Cdouble}, Ptr{Int32}),
+              h, MEM_DEVICE, COLVECS, B, D, N, F, X.ptr, D, D * N, y.ptr, N, nk, s.ptr, isotropic ? 0 : N, mw.ptr, D, Tf.ptr, D, D * D,
+              ptr(km), N, ptr(kv), N, dptr(kl), nf, dptr(total), info.ptr)
+    else
+        ccall((:blr_kfold_large_batched_f32, LIB), Cint,
+              (Ptr{Cvoid}, Cint, Cint, Int64, Int64, Int64, Int64, Ptr{T}, Int64, Int64, Ptr{T}, Int64, Cint, Ptr{T}, Int64, Ptr{T}, Int64,
+               Ptr{T}, Int64, Int64, Ptr{T}, Int64, Ptr{T}, Int64, Ptr{Cdouble}, Int64, Ptr{Cdouble}, Ptr{Int32}),
+              h, MEM_DEVICE, COLVECS, B, D, N, F, X.ptr, D, D * N, y.ptr, N, nk, s.ptr, isotropic ? 0 : N, mw.ptr, D, Tf.ptr, D, D * D,
+              ptr(km), N, ptr(kv), N, dptr(kl), nf, dptr(total), info.ptr)
+    end
+    check(h, rc)
+    return nothing
+end
+
+"""
     loo_multi_batched!(lmean, lvar, llogpdf, total, info, X, Y, s, M, T; D, N, S, B, isotropic)
 
 Exact leave-one-out predictives of the N observations with S targets each that B device-resident MULTI-OUTPUT states contain
