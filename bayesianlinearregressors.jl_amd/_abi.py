@@ -103,6 +103,9 @@ for _suf in ("f64", "f32"):
     _SIGS[f"blr_loo_multi_batched_{_suf}"] = (
         [_H, _int, _int, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _int, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _i64,
          _vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _vp], _int)
+    _SIGS[f"blr_kfold_multi_batched_{_suf}"] = (
+        [_H, _int, _int, _i64, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _int, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _i64,
+         _vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _vp], _int)
     _SIGS[f"blr_logpdf_grid_{_suf}"] = (
         [_H, _int, _int, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _int, _vp, _i64, _int, _vp, _i64, _vp, _i64, _i64,
          _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _i64], _int)
@@ -265,7 +268,7 @@ class Handle:
 
     def get_stat(self, key):
         """Counter of this handle: "i8_regressors", "i8_handed_back", "planes_redone", "loo_degenerate", "kfold_degenerate" (folds
-        blr_kfold_batched_* / blr_kfold_large_batched_* gave NaN), "workspace_bytes", "last_chunks" (chunks / slices of regressors of the most recent call: option MAX_CHUNK caps their size) (blr_get_stat)."""
+        blr_kfold_batched_* / blr_kfold_multi_batched_* / blr_kfold_large_batched_* gave NaN), "workspace_bytes", "last_chunks" (chunks / slices of regressors of the most recent call: option MAX_CHUNK caps their size) (blr_get_stat)."""
         v = _i64()
         self.check(self.lib.blr_get_stat(self._h, str(key).encode(), C.byref(v)))
         return int(v.value)
@@ -413,6 +416,17 @@ class Handle:
         return self.check(fn(self._h, memspace, layout, B, D, N, S, _ptr(X), ldx, strideX, _ptr(Y), ldY, strideY, noise_kind, _ptr(s),
                              strides, _ptr(M), ldm, strideM, _ptr(T), ldt, strideT, _ptr(loo_mean), ld_lm, stride_lm, _ptr(loo_var),
                              stride_lv, _ptr(loo_logpdf), ld_ll, stride_ll, _ptr(loo_total), stride_lt, _ptr(info)))
+
+    def kfold_multi_batched(self, dtype, memspace, layout, B, D, N, S, F, X, ldx, strideX, Y, ldY, strideY, noise_kind, s, strides, M,
+                            ldm, strideM, T, ldt, strideT, kf_mean, ld_km, stride_km, kf_var, stride_kv, kf_logpdf, ld_kl, stride_kl,
+                            kf_total, stride_kt, info):
+        """Exact leave-fold-out (K-fold) predictives of the observations the multi-output states (M: D x S, T) contain, contiguous
+        folds of F <= 64, D <= 128: S means per observation and ONE variance, S joint log densities per fold, S totals per regressor;
+        include/blr_mi355x.h blr_kfold_multi_batched_*."""
+        fn = getattr(self.lib, f"blr_kfold_multi_batched_{suffix(dtype)}")
+        return self.check(fn(self._h, memspace, layout, B, D, N, S, F, _ptr(X), ldx, strideX, _ptr(Y), ldY, strideY, noise_kind, _ptr(s),
+                             strides, _ptr(M), ldm, strideM, _ptr(T), ldt, strideT, _ptr(kf_mean), ld_km, stride_km, _ptr(kf_var),
+                             stride_kv, _ptr(kf_logpdf), ld_kl, stride_kl, _ptr(kf_total), stride_kt, _ptr(info)))
 
     def logpdf_grid(self, dtype, memspace, layout, B, D, N, X, ldx, strideX, y, stridey, noise_kind, s, strides, prior_kind, mw,
                     stridemw, Lw, ldl, strideLw, G, alpha, stride_alpha, tau, stride_tau, logpdf, stride_lp, best, mw_best,

@@ -40,6 +40,7 @@
 #include "blr_rand_multi.hpp"
 #include "blr_kfold.hpp"
 #include "blr_kfold_large.hpp"
+#include "blr_kfold_multi.hpp"
 #include "blr_host.hpp"
 #include "blr_large_plan.hpp"
 
@@ -4163,6 +4164,148 @@ int kfold_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_t D,
   return io.finish();
 }
 
+// ---- exact leave-fold-out predictives of a batched multi-output state: S columns, one fold factor per fold (blr_kfold_multi_batched_*,
+// DESIGN.md K25; blr_kfold_multi.hpp) ------------------------------------------------------------------------------------------------
+
+template <typename T>
+int kfold_multi_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t N, int64_t S, int64_t F, const T* X, int64_t ldx,
+                        int64_t strideX, const T* Y, int64_t ldY, int64_t strideY, int noise_kind, const T* s, int64_t strides, const T* M,
+                        int64_t ldm, int64_t strideM, const T* Tf, int64_t ldt, int64_t strideT, T* kf_mean, int64_t ld_km, int64_t stride_km,
+                        T* kf_var, int64_t stride_kv, double* kf_logpdf, int64_t ld_kl, int64_t stride_kl, double* kf_total, int64_t stride_kt,
+                        int32_t* info) {
+  // (the argument checks come before the handle's: they need no device)
+  if (h) h->err.clear();
+  if (memspace != BLR_MEM_HOST && memspace != BLR_MEM_DEVICE) return bad_arg(h, 2, "memspace");
+  if (layout != BLR_LAYOUT_COLVECS && layout != BLR_LAYOUT_ROWVECS) return bad_arg(h, 3, "unknown layout (reference :26-31)");
+  if (B < 0 || B > (1 << 30)) return bad_arg(h, 4, "B out of range (0..2^30)");
+  if (D < 1 || D > kMaxSmallD) return bad_arg(h, 5, "D out of range (1..128): the fold's rows of Z live in LDS, there is no slow route");
+  if (N < 0 || N > (1 << 30)) return bad_arg(h, 6, "N out of range (0..2^30)");
+  if (S < 0 || S > (1 << 20)) return bad_arg(h, 7, "S out of range (0..2^20)");
+  const int64_t ldmn = (N + kCovTile - 1) / kCovTile * kCovTile;  // a column of the means workspace
+  if (S * ldmn > ((int64_t)1 << 28)) return bad_arg(h, 7, "S * 64 ceil(N / 64) > 2^28: the means workspace of one regressor");
+  if (F < 1 || F > kFoldMax) return bad_arg(h, 8, "F out of range (1..64)");
+  if (B == 0 || S == 0) return 0;
+  if (N > 0 && !X) return bad_arg(h, 9, "X is NULL");
+  if (layout == BLR_LAYOUT_COLVECS ? ldx < D : ldx < std::max<int64_t>(N, 1)) return bad_arg(h, 10, "ldx too small");
+  if (strideX < 0) return bad_arg(h, 11, "strideX < 0");
+  if (N > 0 && !Y) return bad_arg(h, 12, "Y is NULL (reference :74 length check)");
+  if (ldY < N) return bad_arg(h, 13, "ldY < N");
+  if (strideY < 0) return bad_arg(h, 14, "strideY < 0");
+  if (noise_kind != BLR_NOISE_ISOTROPIC && noise_kind != BLR_NOISE_DIAGONAL)
+    return bad_arg(h, 15, "noise_kind (dense noise couples the folds: isotropic or diagonal only)");
+  if (N > 0 && !s) return bad_arg(h, 16, "s is NULL");
+  if (strides < 0) return bad_arg(h, 17, "strides < 0");
+  if (!M) return bad_arg(h, 18, "M is NULL");
+  if (ldm < D) return bad_arg(h, 19, "ldm < D");
+  if (strideM < 0) return bad_arg(h, 20, "strideM < 0");
+  if (!Tf) return bad_arg(h, 21, "T is NULL");
+  if (ldt < D) return bad_arg(h, 22, "ldt < D");
+  if (strideT < 0) return bad_arg(h, 23, "strideT < 0");
+  const int64_t nfolds = (N + F - 1) / F;
+  if (kf_mean && ld_km < N) return bad_arg(h, 25, "ld_km < N");
+  if (kf_mean && B > 1 && stride_km < ld_km * S) return bad_arg(h, 26, "stride_km < ld_km * S");
+  if (kf_var && B > 1 && stride_kv < N) return bad_arg(h, 28, "stride_kv < N");
+  if (kf_logpdf && ld_kl < nfolds) return bad_arg(h, 30, "ld_kl < ceil(N / F)");
+  if (kf_logpdf && B > 1 && stride_kl < ld_kl * S) return bad_arg(h, 31, "stride_kl < ld_kl * S");
+  if (kf_total && B > 1 && stride_kt < S) return bad_arg(h, 33, "stride_kt < S");
+  if (!info) return bad_arg(h, 34, "info is NULL");
+  if (!h) return -1;
+  h->last_chunks = 1;  // (a route with a chunk loop counts its own)
+  HIP_TRY(h, hipSetDevice(h->device));
+
+  CallIO io(h, memspace);
+  KfoldWhitenArgs<T> a{};
+  KfoldColsArgs<T> k{};
+  a.ldx = ldx; a.strideX = strideX; a.ldm = ldm; a.strideM = strideM; a.ldmn = ldmn; a.D = (int)D; a.N = (int)N; a.S = (int)S;
+  k.ldmn = ldmn; k.ldY = ldY; k.strideY = strideY; k.strides = strides; k.noise_kind = noise_kind; k.ld_km = ld_km; k.stride_km = stride_km;
+  k.stride_kv = stride_kv; k.ld_kl = ld_kl; k.stride_kl = stride_kl; k.D = (int)D; k.N = (int)N; k.F = (int)F; k.S = (int)S;
+  const size_t x_one = N == 0 ? 0 : (layout == BLR_LAYOUT_COLVECS ? mat_extent(D, N, ldx) : mat_extent(N, D, ldx));
+  const size_t s_one = N == 0 ? 0 : (noise_kind == BLR_NOISE_DIAGONAL ? (size_t)N : 1);
+  const T* T_d = nullptr;
+  double* tot_d = nullptr;
+  int32_t* info_d = nullptr;
+  int rc;
+  if ((rc = io.in(X, x_one ? extent(B, strideX, x_one) : 0, &a.X))) return rc;
+  if ((rc = io.in(Y, N ? extent(B, strideY, mat_extent(N, S, ldY)) : 0, &k.Y))) return rc;
+  if ((rc = io.in(s, s_one ? extent(B, strides, s_one) : 0, &k.s))) return rc;
+  if ((rc = io.in(M, extent(B, strideM, mat_extent(D, S, ldm)), &a.M))) return rc;
+  if ((rc = io.in(Tf, extent(B, strideT, mat_extent(D, D, ldt)), &T_d))) return rc;
+  if ((rc = io.out(kf_mean, N ? extent(B, stride_km, mat_extent(N, S, ld_km)) : 0, &k.km))) return rc;
+  if ((rc = io.out(kf_var, N ? extent(B, stride_kv, (size_t)N) : 0, &k.kv))) return rc;
+  if ((rc = io.out(kf_logpdf, N ? extent(B, stride_kl, mat_extent(nfolds, S, ld_kl)) : 0, &k.kl))) return rc;
+  if ((rc = io.out(kf_total, extent(B, stride_kt, (size_t)S), &tot_d))) return rc;
+  if ((rc = io.out(info, (size_t)B, &info_d))) return rc;
+  a.info = info_d; k.info = info_d;
+  if ((rc = ensure_stats(h))) return rc;
+  k.degenerate = h->stats_dev + 4;
+
+  // status: loo_check_kernel as blr_loo_batched_* launches it
+  const int64_t ychunk = h->cap_chunk(65535);  // grid.x / grid.y <= 65535: the check and the empty totals
+  h->count_chunks(B, ychunk);
+  for (int64_t b0 = 0; b0 < B; b0 += ychunk)
+    hipLaunchKernelGGL(loo_check_kernel<T>, dim3((unsigned)std::min<int64_t>(ychunk, B - b0)), dim3(kThreads), 0, h->stream, T_d + b0 * strideT,
+                       ldt, strideT, (int)D, k.s + b0 * strides, strides, noise_kind, (int)N, info_d + b0);
+  HIP_TRY(h, hipGetLastError());
+  if (N == 0) {  // empty sums, for the regressors whose state passed the check
+    for (int64_t b0 = 0; tot_d && b0 < B; b0 += ychunk)
+      hipLaunchKernelGGL(loo_cols_total_kernel, dim3((unsigned)S, (unsigned)std::min<int64_t>(ychunk, B - b0)), dim3(kThreads), 0, h->stream,
+                         (const double*)nullptr, (int64_t)0, (int64_t)0, 0, tot_d, stride_kt, (const int32_t*)info_d, (int)b0);
+    HIP_TRY(h, hipGetLastError());
+    return io.finish();
+  }
+
+  // Per chunk of regressors: the triangular inverses as MFMA images (marg_image_kernel), Z = X'T^-1 and the S means X'M into workspace
+  // (kfold_whiten_cols_kernel), the folds (kfold_cols_kernel), the totals -- four launches whatever B, S and the fold count.  Chunks by
+  // the rules of blr_kfold_batched_*: grid.y, the images, the rows of Z and the means (with the log densities when only the totals are
+  // wanted) within 256 MiB each, at least one regressor
+  const bool kl_ws = tot_d && !k.kl;  // the totals need the folds' log densities somewhere
+  const bool do_cols = k.km || k.kl || kl_ws;
+  const int64_t pack_rows = (kFoldMax / F) * F, npacks = (N + pack_rows - 1) / pack_rows;
+  const size_t z_one = cov_z_elems((int)D, (int)N);
+  const size_t mean_one = do_cols ? (size_t)S * (size_t)ldmn * sizeof(T) : 0;
+  const size_t row_kl = ((size_t)nfolds * sizeof(double) + 255) & ~(size_t)255;
+  const size_t per = mean_one + (kl_ws ? (size_t)S * row_kl : 0);
+  int64_t chunk = std::min<int64_t>(std::min<int64_t>(B, 65535), MargImages<T>::kMaxChunk);
+  chunk = std::min<int64_t>(chunk, std::max<int64_t>(1, (int64_t)(((size_t)256 << 20) / (z_one * sizeof(T)))));
+  if (per) chunk = std::max<int64_t>(1, std::min<int64_t>(chunk, (int64_t)(kLooWorkspace / per)));
+  chunk = h->cap_chunk(chunk);
+  h->count_chunks(B, chunk);
+  const size_t lds_w = kfold_whiten_cols_lds_bytes(sizeof(T), (int)D), lds_k = kfold_cols_lds_bytes(sizeof(T), (int)D);
+  void (*const whiten)(KfoldWhitenArgs<T>) =
+      layout == BLR_LAYOUT_ROWVECS ? kfold_whiten_cols_kernel<T, LAYOUT_ROWVECS> : kfold_whiten_cols_kernel<T, LAYOUT_COLVECS>;
+  if ((rc = set_lds_once(h, whiten, lds_w))) return rc;
+  if ((rc = set_lds_once(h, kfold_cols_kernel<T>, lds_k))) return rc;
+  if ((rc = MargImages<T>::reserve(h, chunk))) return rc;
+  if ((rc = h->cov_ws.reserve(h, (size_t)chunk * z_one * sizeof(T)))) return rc;
+  if (per && (rc = h->loo_ws.reserve(h, (size_t)chunk * per + 256))) return rc;
+  char* const ws = h->loo_ws.p;
+  const int64_t ldkl = (int64_t)(row_kl / sizeof(double));
+  const int64_t ntiles = (N + kCovTile - 1) / kCovTile;
+  a.Z = reinterpret_cast<T*>(h->cov_ws.p);
+  a.mean = do_cols ? reinterpret_cast<T*>(ws) : nullptr;
+  k.Z = a.Z; k.strideZ = (int64_t)z_one; k.mean = a.mean;
+  for (int64_t b0 = 0; b0 < B; b0 += chunk) {
+    const int64_t nb = std::min<int64_t>(chunk, B - b0);
+    a.img = MargImages<T>::launch(h, T_d + b0 * strideT, ldt, strideT, (int)D, (const int32_t*)(info_d + b0), 0, nb);
+    // every workgroup amortises its set-up (the image) over its tiles: about two workgroups per CU in all
+    const int64_t ngroups = std::max<int64_t>(1, std::min<int64_t>(ntiles, (2 * (int64_t)h->cus + nb - 1) / nb));
+    a.ngroups = (int)ngroups; a.reg0 = (int)b0;
+    hipLaunchKernelGGL(whiten, dim3((unsigned)ngroups, (unsigned)nb), dim3(kThreads), lds_w, h->stream, a);
+    KfoldColsArgs<T> c = k;
+    c.reg0 = (int)b0;
+    if (kl_ws) {  // (indexed by the global regressor)
+      c.ld_kl = ldkl; c.stride_kl = ldkl * S;
+      c.kl = reinterpret_cast<double*>(ws + (size_t)chunk * mean_one) - b0 * c.stride_kl;
+    }
+    hipLaunchKernelGGL(kfold_cols_kernel<T>, dim3((unsigned)npacks, (unsigned)nb), dim3(kThreads), lds_k, h->stream, c);
+    if (tot_d)
+      hipLaunchKernelGGL(loo_cols_total_kernel, dim3((unsigned)S, (unsigned)nb), dim3(kThreads), 0, h->stream, (const double*)c.kl, c.ld_kl,
+                         c.stride_kl, (int)nfolds, tot_d, stride_kt, (const int32_t*)info_d, (int)b0);
+    HIP_TRY(h, hipGetLastError());
+  }
+  return io.finish();
+}
+
 // ---- exact leave-fold-out predictives for LARGE folds, removed in weight space (blr_kfold_large_batched_*, DESIGN.md K24;
 // blr_kfold_large.hpp) ---------------------------------------------------------------------------------------------------------------
 
@@ -4636,7 +4779,7 @@ int blr_get_stat(blr_handle* h, const char* key, int64_t* value) {
     *value = (int64_t)v;
     return 0;
   }
-  if (!strcmp(key, "kfold_degenerate")) {  // folds blr_kfold_batched_* / blr_kfold_large_batched_* gave NaN: a pivot <= 0 or not finite (cumulative)
+  if (!strcmp(key, "kfold_degenerate")) {  // folds blr_kfold_batched_* / blr_kfold_multi_batched_* / blr_kfold_large_batched_* gave NaN: a pivot <= 0 or not finite (cumulative)
     unsigned long long v = 0;
     if (h->stats_dev) {
       HIP_TRY(h, hipSetDevice(h->device));
@@ -4829,6 +4972,17 @@ int blr_timer_stop(blr_handle* h, float* elapsed_ms) {
     return loo_multi_batched<T>(h, memspace, layout, B, D, N, S, X, ldx, strideX, Y, ldY, strideY, noise_kind, s,   \
                                 strides, M, ldm, strideM, Tf, ldt, strideT, loo_mean, ld_lm, stride_lm, loo_var,    \
                                 stride_lv, loo_logpdf, ld_ll, stride_ll, loo_total, stride_lt, info);               \
+  }                                                                                                                 \
+  int blr_kfold_multi_batched_##SUF(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t N,       \
+                                    int64_t S, int64_t F, const T* X, int64_t ldx, int64_t strideX, const T* Y,     \
+                                    int64_t ldY, int64_t strideY, int noise_kind, const T* s, int64_t strides,      \
+                                    const T* M, int64_t ldm, int64_t strideM, const T* Tf, int64_t ldt,             \
+                                    int64_t strideT, T* kf_mean, int64_t ld_km, int64_t stride_km, T* kf_var,       \
+                                    int64_t stride_kv, double* kf_logpdf, int64_t ld_kl, int64_t stride_kl,         \
+                                    double* kf_total, int64_t stride_kt, int32_t* info) {                           \
+    return kfold_multi_batched<T>(h, memspace, layout, B, D, N, S, F, X, ldx, strideX, Y, ldY, strideY, noise_kind, \
+                                  s, strides, M, ldm, strideM, Tf, ldt, strideT, kf_mean, ld_km, stride_km, kf_var, \
+                                  stride_kv, kf_logpdf, ld_kl, stride_kl, kf_total, stride_kt, info);               \
   }                                                                                                                 \
   int blr_update_multi_factor_##SUF(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t k,       \
                                     int64_t S, const T* X, int64_t ldx, int64_t strideX, const T* Y, int64_t ldY,   \

@@ -27,7 +27,7 @@ __all__ = [
     "BayesianLinearRegressor", "BasisFunctionRegressor", "BLRFunctionSample", "FiniteGP",
     "mean", "var", "cov", "std", "mean_and_var", "mean_and_cov", "marginals", "rand", "rand_b", "logpdf", "posterior",
     "LOO", "loo", "loo_map", "loo_columns", "loo_columns_map",
-    "KFold", "kfold", "kfold_map", "kfold_large", "kfold_large_map", "cross_validate",
+    "KFold", "kfold", "kfold_map", "kfold_large", "kfold_large_map", "cross_validate", "kfold_columns", "kfold_columns_map",
     "EvidenceGrid", "logpdf_grid", "posterior_best", "logpdf_grid_map",
     "posterior_ragged", "logpdf_ragged",
     "posterior_columns", "logpdf_columns_map", "posterior_columns_map",
@@ -1253,8 +1253,10 @@ def _loo_columns_call(h, dtype, layout, B, D, N, S, dX, ldx, strideX, dY, stride
     return (m.reshape((B, S, N)).transpose(0, 2, 1), v, lp.reshape((B, S, N)).transpose(0, 2, 1), tot, info)  # (column-major N x S)
 
 
-def _loo_columns_problem(fx, Y, dtype):
-    """(X, layout, ldx, D, N, Y, s, noise_kind, mw, Lw, prior_kind, ldl) of one finite regressor with an N x S target matrix."""
+def _loo_columns_problem(fx, Y, dtype, what="loo_columns", perm=None):
+    """(X, layout, ldx, D, N, Y, s, noise_kind, mw, Lw, prior_kind, ldl) of one finite regressor with an N x S target matrix.
+    ``perm`` (kfold_columns): observation n of the problem is observation perm[n] of the caller's -- X, the rows of Y and a noise
+    diagonal gathered here."""
     fb = _to_finite_blr(fx)
     X, layout, ldx, D, N = _x_layout(fb.x, dtype)
     Y = np.asfortranarray(Y, dtype=dtype)
@@ -1264,8 +1266,14 @@ def _loo_columns_problem(fx, Y, dtype):
         raise ValueError("length(y) != size(fx.x.X, 2)")  # reference :74
     s, noise_kind = _noise(fb.Sy, N, dtype)
     if noise_kind == _abi.NOISE_DENSE:
-        raise NotImplementedError("loo_columns: with a dense noise covariance one observation is not independent of the rest (that "
+        raise NotImplementedError(f"{what}: with a dense noise covariance one observation is not independent of the rest (that "
                                   "is a block leave-out); isotropic or diagonal noise only")
+    if perm is not None:
+        obs_axis = 0 if isinstance(fb.x, RowVecs) else 1
+        X = np.asarray(np.take(X, perm, axis=obs_axis), order="F" if X.flags.f_contiguous else "C")
+        Y = np.asfortranarray(Y[perm, :])
+        if noise_kind == _abi.NOISE_DIAGONAL:
+            s = np.ascontiguousarray(s[perm])
     Lw, prior_kind, ldl = _prior(fb.f.Lw, D, dtype)
     return X, layout, ldx, D, N, Y, s, noise_kind, _mean_vector(fb.f.mw, D, dtype), Lw, prior_kind, ldl
 
@@ -1359,6 +1367,145 @@ def loo_columns_map(fxs, Ys):
     if len(sig) != 1 or q0[3] == 0 or q0[4] == 0 or q0[5].shape[1] == 0:
         return one_by_one()
     return _loo_columns_batch(probs, dtype)
+
+
+# ---------------------------------------------------------------------------------------------------
+# exact K-fold for matrix targets: S columns share every fold's factor (blr_kfold_multi_batched_*)
+# ---------------------------------------------------------------------------------------------------
+_KFOLD_COLUMNS_MAX_D = 128  # blr_kfold_multi_batched_*: the fold's rows of Z live in LDS, there is no slow route
+
+
+def _kfold_columns_check(D, what):
+    if D > _KFOLD_COLUMNS_MAX_D:
+        raise ValueError(f"{what}: D = {D} is beyond the limit of blr_kfold_multi_batched_* (D <= {_KFOLD_COLUMNS_MAX_D})")
+
+
+def _kfold_columns_call(h, dtype, layout, B, D, N, S, F, dX, ldx, strideX, dY, strideY, noise_kind, ds, strides, d_M, strideM, d_T, strideT,
+                        temps):
+    """blr_kfold_multi_batched_* on device operands -> (mean [B, N, S], var [B, N], logpdf [B, nfolds, S], total [B, S], info [B]) on
+    the host."""
+    item = np.dtype(dtype).itemsize
+    nf = -(-N // F)
+    outs = [_DeviceBuffer(h, B * N * S * item), _DeviceBuffer(h, B * N * item), _DeviceBuffer(h, B * nf * S * 8), _DeviceBuffer(h, B * S * 8),
+            _DeviceBuffer.of(h, np.zeros(B, dtype=np.int32))]
+    temps.extend(outs)
+    d_km, d_kv, d_kl, d_tot, d_info = (b.ptr for b in outs)
+    h.kfold_multi_batched(dtype, _abi.MEM_DEVICE, layout, B, D, N, S, F, dX, ldx, strideX, dY, max(N, 1), strideY, noise_kind, ds, strides,
+                          d_M, max(D, 1), strideM, d_T, max(D, 1), strideT, d_km, max(N, 1), N * S, d_kv, N, d_kl, max(nf, 1), nf * S, d_tot,
+                          S, d_info)
+    m, v = np.empty((B, N * S), dtype=dtype), np.empty((B, N), dtype=dtype)
+    lp, tot, info = np.empty((B, nf * S), dtype=np.float64), np.empty((B, S), dtype=np.float64), np.zeros(B, dtype=np.int32)
+    for host, dptr in ((m, d_km), (v, d_kv), (lp, d_kl), (tot, d_tot), (info, d_info)):
+        h.memcpy_d2h(host, dptr)
+    return (m.reshape((B, S, N)).transpose(0, 2, 1), v, lp.reshape((B, S, nf)).transpose(0, 2, 1), tot, info)  # (column-major per regressor)
+
+
+def _kfold_columns_batch(probs, dtype, F):
+    """K-fold of equally shaped matrix-target problems: the pipeline of `_loo_columns_batch` with blr_kfold_multi_batched_* as its
+    second half.  Nothing D x D comes back to the host."""
+    X0, layout, ldx, D, N, Y0, _, noise_kind, _, _, prior_kind, ldl = probs[0]
+    S = Y0.shape[1]
+    nb, h, item = len(probs), _handle(), np.dtype(dtype).itemsize
+    Xb = np.stack([q[0].reshape(-1, order="A") for q in probs])
+    Yb = np.stack([q[5].reshape(-1, order="F") for q in probs])  # N x S column-major per data set, ldY = N
+    sb = np.stack([q[6] for q in probs])
+    mwb = np.stack([q[8] for q in probs])
+    Lb = np.stack([q[9].reshape(-1, order="A") for q in probs])
+    temps = []
+
+    def dev(a):
+        temps.append(_DeviceBuffer.of(h, a))
+        return temps[-1].ptr
+
+    try:
+        dX, dY, ds = dev(Xb), dev(Yb), dev(sb)
+        temps.extend([_DeviceBuffer(h, nb * D * S * item), _DeviceBuffer(h, nb * D * D * item)])
+        d_M, d_T = temps[-2].ptr, temps[-1].ptr
+        d_info = dev(np.zeros(nb, dtype=np.int32))
+        h.posterior_multi_batched(dtype, _abi.MEM_DEVICE, layout, nb, D, N, S, dX, ldx, Xb.shape[1], dY, max(N, 1), Yb.shape[1], noise_kind,
+                                  ds, sb.shape[1], prior_kind, dev(mwb), D, dev(Lb), ldl, Lb.shape[1], d_M, D, D * S, d_T, D, D * D, None, D,
+                                  D * D, None, S, d_info)
+        info = np.zeros(nb, dtype=np.int32)
+        h.memcpy_d2h(info, d_info)
+        if not np.any(info):
+            m, v, lp, tot, info = _kfold_columns_call(h, dtype, layout, nb, D, N, S, F, dX, ldx, Xb.shape[1], dY, Yb.shape[1], noise_kind,
+                                                      ds, sb.shape[1], d_M, D * S, d_T, D * D, temps)
+    finally:
+        for b in temps:
+            b.free()
+    bad = np.flatnonzero(info)
+    if bad.size:
+        e = _abi.PosDefException(int(info[bad[0]]))
+        e.index = int(bad[0])
+        raise e
+    return [KFold(m[b], v[b], lp[b], tot[b]) for b in range(nb)]
+
+
+def _kfold_columns_one(q, dtype, F):
+    N, S = q[5].shape
+    if q[3] == 0 or N == 0 or S == 0:
+        return KFold(np.empty((N, S), dtype=dtype), np.empty(N, dtype=dtype), np.empty((-(-N // F), S)), np.zeros(S))
+    return _kfold_columns_batch([q], dtype, F)[0]
+
+
+def kfold_columns(fx, Y, fold_size, perm=None):
+    """Exact leave-fold-out (K-fold) predictives of a matrix target (include/blr_mi355x.h blr_kfold_multi_batched_*): for every
+    column c what `kfold(fx, Y[:, c], fold_size)` gives, with X read once and every fold's hat block factored once for its S columns.
+    1 <= fold_size <= 64 and D <= 128 (ValueError beyond).  ``perm`` as for `kfold`: fold f holds the observations
+    perm[f fold_size : (f + 1) fold_size]; mean and var come back in the caller's order, logpdf stays in fold order.  Returns
+    KFold(mean N x S, var N -- it does not depend on the column --, logpdf nfolds x S, total S).  Dense noise raises
+    NotImplementedError (it couples the folds)."""
+    F = _fold_size(fold_size)
+    Y = np.asarray(Y)
+    dtype = _loo_columns_dtype(fx, Y)
+    if perm is not None:
+        perm = np.asarray(perm, dtype=np.int64)
+        n = Y.shape[0] if Y.ndim == 2 else -1
+        if perm.shape != (n,) or not np.array_equal(np.sort(perm), np.arange(n)):
+            raise ValueError("perm must be a permutation of range(N)")
+    q = _loo_columns_problem(fx, Y, dtype, "kfold_columns", perm)
+    _kfold_columns_check(q[3], "kfold_columns")
+    r = _kfold_columns_one(q, dtype, F)
+    if perm is None:
+        return r
+    m, v = np.empty_like(r.mean), np.empty_like(r.var)
+    m[perm, :], v[perm] = r.mean, r.var
+    return KFold(m, v, r.logpdf, r.total)
+
+
+def kfold_columns_map(fxs, Ys, fold_size):
+    """[kfold_columns(fx, Y, fold_size) for fx, Y in zip(fxs, Ys)] in one posterior call and one K-fold call for equally shaped
+    problems (else one pair of calls per problem).  The first problem whose prior, noise or posterior is not positive definite raises
+    PosDefException with its position as ``index``."""
+    F = _fold_size(fold_size)
+    fxs, Ys = list(fxs), [np.asarray(Y) for Y in Ys]
+    if len(fxs) != len(Ys):
+        raise ValueError("as many target matrices as finite regressors are needed")
+    if not fxs:
+        return []
+    dtype = np.float32 if all(_loo_columns_dtype(fx, Y) == np.float32 for fx, Y in zip(fxs, Ys)) else np.float64
+    probs = [_loo_columns_problem(fx, Y, dtype, "kfold_columns_map") for fx, Y in zip(fxs, Ys)]
+    for q in probs:
+        _kfold_columns_check(q[3], "kfold_columns_map")
+
+    def one_by_one():
+        out = []
+        for i, q in enumerate(probs):
+            try:
+                out.append(_kfold_columns_one(q, dtype, F))
+            except _abi.PosDefException as e:
+                e.index = i
+                raise
+        return out
+
+    if any(isinstance(fx.f, BasisFunctionRegressor) and isinstance(fx.f.phi, RandomFourierFeatures) for fx in fxs):
+        return one_by_one()
+    sig = {(q[0].shape, q[0].flags.f_contiguous, q[1], q[3], q[4], q[5].shape[1], q[7], q[10],
+            isinstance((fx.f.blr if isinstance(fx.f, BasisFunctionRegressor) else fx.f).Lw, PDMat)) for q, fx in zip(probs, fxs)}
+    q0 = probs[0]
+    if len(sig) != 1 or q0[3] == 0 or q0[4] == 0 or q0[5].shape[1] == 0:
+        return one_by_one()
+    return _kfold_columns_batch(probs, dtype, F)
 
 
 EvidenceGrid = namedtuple("EvidenceGrid", ["logpdf", "best", "alpha", "tau"])
@@ -1944,6 +2091,40 @@ class ResidentColumnsPosterior:
         if info[0] != 0:
             raise _abi.PosDefException(int(info[0]))
         return LOO(m[0], v[0], lp[0], tot[0])
+
+    def kfold(self, x, Sy, Y, fold_size):
+        """Exact leave-fold-out (K-fold) predictives of the observations (x, Sy, Y), Y one row of S targets per input, which the
+        caller vouches the state contains, for contiguous folds of ``fold_size`` <= 64 observations (D <= 128): per fold and column
+        what ``forget`` of that fold, a prediction at its inputs and ``condition`` would give, without touching the state
+        (blr_kfold_multi_batched_* on device pointers to the resident state, B = 1).  Returns KFold(mean N x S, var N, logpdf
+        nfolds x S, total S); a state with a non-positive diagonal entry or a non-positive variance raises PosDefException(info)."""
+        F = _fold_size(fold_size)
+        dtype, h, D, S = self.dtype, self._h, self.D, self.S
+        _kfold_columns_check(D, "ResidentColumnsPosterior.kfold")
+        temps = []
+
+        def dev(a):
+            temps.append(_DeviceBuffer.of(h, a))
+            return temps[-1].ptr
+
+        try:
+            dX, layout, ldx, N = self._col0._inputs(x, dev, temps)
+            Y = np.asfortranarray(Y, dtype=dtype)
+            if Y.shape != (N, S):
+                raise ValueError("Y must be (number of inputs) x S")  # reference :74 per column
+            s, noise_kind = _noise(Sy, N, dtype)
+            if noise_kind == _abi.NOISE_DENSE:
+                raise NotImplementedError("ResidentColumnsPosterior.kfold takes scalar or diagonal noise (dense noise couples the folds)")
+            if N == 0:
+                return KFold(np.empty((0, S), dtype=dtype), np.empty(0, dtype=dtype), np.empty((0, S)), np.zeros(S))
+            m, v, lp, tot, info = _kfold_columns_call(h, dtype, layout, 1, D, N, S, F, dX, ldx, 0, dev(Y), 0, noise_kind, dev(s), 0,
+                                                      self._M.ptr, 0, self._T.ptr, 0, temps)
+        finally:
+            for b in temps:
+                b.free()
+        if info[0] != 0:
+            raise _abi.PosDefException(int(info[0]))
+        return KFold(m[0], v[0], lp[0], tot[0])
 
     def _marginals(self, x, Sy, want_var):
         dtype, h, D, S = self.dtype, self._h, self.D, self.S

@@ -97,8 +97,8 @@ const char* blr_last_route(blr_handle* h);
  * columns of every column chunk (doubled: an entry up to 16 x the sample's largest still fits); an entry beyond that sends the call
  * through the exact row maxima and the planes pass a second time (one more read of X; option NO_SPEC_ROWMAX = 1 always takes the exact
  * maxima: one more read of X on every call); "loo_degenerate" = observations blr_loo_batched_* gave NaN because their 1 - h_n was
- * <= 0 or not finite (reading it synchronises the handle's stream); "kfold_degenerate" = folds blr_kfold_batched_* gave NaN because
- * the Cholesky of their I - H~ met a pivot <= 0 or not finite, and folds blr_kfold_large_batched_* gave NaN because that of their
+ * <= 0 or not finite (reading it synchronises the handle's stream); "kfold_degenerate" = folds blr_kfold_batched_* or
+ * blr_kfold_multi_batched_* (once per fold, whatever S is) gave NaN because the Cholesky of their I - H~ met a pivot <= 0 or not finite, and folds blr_kfold_large_batched_* gave NaN because that of their
  * A - G_f did (reading it synchronises the handle's stream); "last_chunks" = chunks / slices of regressors the handle's most
  * recent call launched (NOT cumulative: every entry point starts it at 1; a batch beyond grid.y = 65535, a workspace or image bound, or
  * option MAX_CHUNK, goes in several); "workspace_bytes" = device scratch the handle holds now.
@@ -990,6 +990,69 @@ int blr_kfold_large_batched_f32(blr_handle* h, int memspace, int layout, int64_t
                                 int64_t strides, const float* mw, int64_t stridemw, const float* T, int64_t ldt, int64_t strideT,
                                 float* kf_mean, int64_t stride_km, float* kf_var, int64_t stride_kv, double* kf_logpdf,
                                 int64_t stride_kl, double* kf_total, int32_t* info);
+
+/* ---- exact LEAVE-FOLD-OUT (K-fold) predictives of a MULTI-OUTPUT state: S target columns, one factor per fold ---------------------
+ * Replaces: S calls of blr_kfold_batched_* on the columns (M[:, c], Y[:, c]), which read X S times, form z_n = T^-T x_n S times and
+ * factor every fold's 64 x 64 hat block S times; reference src/bayesian_linear_regression.jl:55-58 (logpdf) of each held-out fold
+ * and COLUMN given the rest.
+ * State (M, T) as for blr_loo_multi_batched_*: M the D x S block of means (ldm >= D), T upper, only its upper triangle is read; NOT
+ * modified.  It must be conditioned on a data set that contains the N observations (X, Y (N x S column-major per regressor,
+ * ldY >= N), s).  Folds as for blr_kfold_batched_*: fold f is [f F, min((f + 1) F, N)) with n_f members, nfolds = ceil(N / F).
+ * With z_n = T^-T x_n, q_n = 1 / sqrt(s_n) and Z_f the fold's rows z_n':
+ *   G~ = I - diag(q) Z_f Z_f' diag(q) = L L'           once per fold (positive definite iff the state really contains the fold)
+ *   kf_var[n] = s_n |L^-1 e_n|^2                       ONE per input: it does not depend on the column (noise included)
+ *   r_nc = Y[n, c] - x_n'M[:, c],   u_c = L^-1 (q .* r_c),   g_c = L^-T u_c
+ *   kf_mean[n, c] = Y[n, c] - sqrt(s_n) g_nc
+ *   kf_logpdf[f, c] = -1/2 [n_f log 2 pi + sum log s_n - 2 sum log L_ii + |u_c|^2]   (the JOINT density of the fold; double)
+ *   kf_total[b * stride_kt + c] = sum_f kf_logpdf[f, c] in a fixed order (the K-fold CV score of column c; double).
+ * At S = 1 these are the numbers of blr_kfold_batched_*, at F = 1 those of blr_loo_multi_batched_*.  Z Z' and x_n'M[:, c] are
+ * computed in the element type on the matrix cores (the means from X and M, not from z_n'(T M)); from G~ onwards everything is
+ * double in both element types.
+ * Outputs: kf_mean (N x S, ld_km >= N) and kf_var (N) in the element type, kf_logpdf (nfolds x S column-major per regressor,
+ * ld_kl >= nfolds, double), kf_total (S per regressor, stride_kt between regressors, double).  Any of them may be NULL; with
+ * kf_total requested and kf_logpdf NULL the log densities go through handle workspace.  A stride of 0 shares an input (strideX,
+ * strideY, strides, strideM and strideT included).
+ * Sizes: 1 <= F <= 64, and F > N is allowed: one fold.  1 <= D <= 128: there is no slow route, D > 128 is an argument error (5).
+ * 0 <= S <= 2^20, 0 <= N <= 2^30, and the means workspace of one regressor must be addressable: S * 64 ceil(N / 64) <= 2^28
+ * elements, else an argument error at S's position (7).  Isotropic or diagonal noise; dense noise is an argument error (it couples
+ * the folds).  ColVecs or RowVecs with any ldx, host or device memspace.
+ * No-ops: B = 0 or S = 0 returns 0 and touches nothing; N = 0 gives every requested total = 0 and info = 0 (for a state that
+ * passes the check).
+ * Argument errors (negative position; checked before the handle, so a NULL handle with valid arguments returns -1): memspace (2),
+ * layout (3), B (4), D (5), N (6), S (7), F (8) out of range, ldx too small (10), ldY < N (13), dense noise (15), ldm < D (19),
+ * ldt < D (22), ld_km < N (25), ld_kl < nfolds (30), a negative input stride (11, 14, 17, 20, 23), a NULL X / Y / s (N > 0; 9, 12,
+ * 16) / M (18) / T (21) / info (34), and for B > 1 overlapping outputs: stride_km < ld_km * S (26), stride_kv < N (28),
+ * stride_kl < ld_kl * S (31), stride_kt < S (33).
+ * info[B], as blr_loo_batched_* and in its order: T has a non-positive diagonal entry j -> j, else s_i is not positive -> i; every
+ * output of such a regressor is left untouched; the call returns 0.
+ * NaN rule: a fold whose Cholesky of G~ meets a pivot <= 0 or not finite gets NaN in kf_var of its members, in all S of their
+ * means and in its S log densities, and so in all S totals; it is counted ONCE (not S times) by blr_get_stat "kfold_degenerate".
+ * Every other fold of the regressor keeps its bits.  A NaN in one column of Y stays in that column.
+ * Bit promises: results are bit-reproducible from call to call; the bits of a regressor do not depend on B, on its position in the
+ * batch, on the chunking or on the memspace; the bits of fold f depend only on that regressor's T and M and on the fold's own rows;
+ * the bits of column c do not depend on S, on c's position (pass and wave included) or on the other columns of Y and M; the bits
+ * of kf_var do not depend on S or on which outputs are requested.  No float atomics.  NOT promised: bit-equality with
+ * blr_kfold_batched_* or blr_loo_multi_batched_*.
+ * Kernels (csrc/blr_kfold_multi.hpp), a launch list per chunk of regressors that does not depend on S or on the fold
+ * count (chunks: grid.y <= 65535, 256 MiB each of images, of rows z_n and of means, never fewer than one regressor; option
+ * MAX_CHUNK and blr_get_stat "last_chunks" are honoured): the status (loo_check_kernel), the triangular inverse as an MFMA image
+ * (marg_image_kernel), kfold_whiten_cols_kernel -- X is read once: the rows z_n and, in passes of 16 columns of M, the S means
+ * into handle workspace --, kfold_cols_kernel over (fold packs, regressors) -- the product, the Cholesky and L^-1 of
+ * blr_kfold_batched_*'s kernel once per pack, then an epilogue over the S columns, four at a time, with L^-1 read-only in LDS --
+ * and the totals (loo_cols_total_kernel).  An async handle in device memspace only enqueues.
+ * _f32: X, Y, s, M, T, kf_mean and kf_var are float; kf_logpdf and kf_total stay double. */
+int blr_kfold_multi_batched_f64(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t N, int64_t S, int64_t F,
+                                const double* X, int64_t ldx, int64_t strideX, const double* Y, int64_t ldY, int64_t strideY,
+                                int noise_kind, const double* s, int64_t strides, const double* M, int64_t ldm, int64_t strideM,
+                                const double* T, int64_t ldt, int64_t strideT, double* kf_mean, int64_t ld_km, int64_t stride_km,
+                                double* kf_var, int64_t stride_kv, double* kf_logpdf, int64_t ld_kl, int64_t stride_kl,
+                                double* kf_total, int64_t stride_kt, int32_t* info);
+int blr_kfold_multi_batched_f32(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t N, int64_t S, int64_t F,
+                                const float* X, int64_t ldx, int64_t strideX, const float* Y, int64_t ldY, int64_t strideY,
+                                int noise_kind, const float* s, int64_t strides, const float* M, int64_t ldm, int64_t strideM,
+                                const float* T, int64_t ldt, int64_t strideT, float* kf_mean, int64_t ld_km, int64_t stride_km,
+                                float* kf_var, int64_t stride_kv, double* kf_logpdf, int64_t ld_kl, int64_t stride_kl,
+                                double* kf_total, int64_t stride_kt, int32_t* info);
 
 /* ---- evidence of one data set under a GRID of (prior scale, noise scale) settings, from one pass over the data ------------
  * Replaces: blr_posterior_batched_* called with strideX = 0, stridey = 0 and one scaled (s, Lw) pair per setting, which re-forms

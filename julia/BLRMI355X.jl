@@ -1307,6 +1307,46 @@ function loo_multi_batched!(lm::Union{Nothing,DeviceArray{T}}, lv::Union{Nothing
 end
 
 """
+    kfold_multi_batched!(kmean, kvar, klogpdf, total, info, X, Y, s, M, T; D, N, S, F, B, isotropic)
+
+Exact leave-fold-out (K-fold) predictives of the N observations with S targets each that B device-resident MULTI-OUTPUT states
+contain (`blr_kfold_multi_batched_*`), for contiguous folds of F ≤ 64 observations and D ≤ 128: per column c what `kfold!` gives
+on (M[:, c], Y[:, c]), with X read once and every fold's hat block factored once for its S columns; the states (M D×S×B, T D×D×B)
+are not modified.  X is D×N×B, Y N×S×B, s one variance (`isotropic`) or N×B.  kmean (N×S×B) and kvar (N×B: ONE per input) in the
+element type, klogpdf (nfolds×S×B, nfolds = cld(N, F): the JOINT log density of each fold and column) and total (S×B, Σ_f klogpdf
+in a fixed order) in Float64; any of the four may be `nothing`.  A fold the state does not contain gives NaN in kvar of its
+members and in all S columns (`get_stat("kfold_degenerate")` counts it once); info[b] > 0: a bad factor, else a bad variance, and
+that state's outputs are left untouched.
+"""
+function kfold_multi_batched!(km::Union{Nothing,DeviceArray{T}}, kv::Union{Nothing,DeviceArray{T}}, kl::Union{Nothing,DeviceArray{Float64}},
+                              total::Union{Nothing,DeviceArray{Float64}}, info::DeviceArray{Int32}, X::DeviceArray{T}, Y::DeviceArray{T},
+                              s::DeviceArray{T}, M::DeviceArray{T}, Tf::DeviceArray{T}; D::Int, N::Int, S::Int, F::Int, B::Int,
+                              isotropic::Bool) where {T<:Elt}
+    h = handle()
+    nk = isotropic ? ISOTROPIC : DIAGONALN
+    nf = max(cld(N, F), 1)
+    ptr(a) = a === nothing ? Ptr{T}(C_NULL) : a.ptr
+    dptr(a) = a === nothing ? Ptr{Cdouble}(C_NULL) : a.ptr
+    rc = if T === Float64
+        ccall((:blr_kfold_multi_batched_f64, LIB), Cint,
+              (Ptr{Cvoid}, Cint, Cint, Int64, Int64, Int64, Int64, Int64, Ptr{T}, Int64, Int64, Ptr{T}, Int64, Int64, Cint, Ptr{T}, Int64,
+               Ptr{T}, Int64, Int64, Ptr{T}, Int64, Int64, Ptr{T}, Int64, Int64, Ptr{T}, Int64, Ptr{Cdouble}, Int64, Int64,
+               Ptr{Cdouble}, Int64, Ptr{Int32}),
+              h, MEM_DEVICE, COLVECS, B, D, N, S, F, X.ptr, D, D * N, Y.ptr, max(N, 1), N * S, nk, s.ptr, isotropic ? 0 : N, M.ptr, D, D * S,
+              Tf.ptr, D, D * D, ptr(km), max(N, 1), N * S, ptr(kv), N, dptr(kl), nf, nf * S, dptr(total), S, info.ptr)
+    else
+        ccall((:blr_kfold_multi_batched_f32, LIB), Cint,
+              (Ptr{Cvoid}, Cint, Cint, Int64, Int64, Int64, Int64, Int64, Ptr{T}, Int64, Int64, Ptr{T}, Int64, Int64, Cint, Ptr{T}, Int64,
+               Ptr{T}, Int64, Int64, Ptr{T}, Int64, Int64, Ptr{T}, Int64, Int64, Ptr{T}, Int64, Ptr{Cdouble}, Int64, Int64,
+               Ptr{Cdouble}, Int64, Ptr{Int32}),
+              h, MEM_DEVICE, COLVECS, B, D, N, S, F, X.ptr, D, D * N, Y.ptr, max(N, 1), N * S, nk, s.ptr, isotropic ? 0 : N, M.ptr, D, D * S,
+              Tf.ptr, D, D * D, ptr(km), max(N, 1), N * S, ptr(kv), N, dptr(kl), nf, nf * S, dptr(total), S, info.ptr)
+    end
+    check(h, rc)
+    return nothing
+end
+
+"""
     loo(fx, y) -> (mean, var, logpdf)
 
 Leave-one-out predictives of the observations y at fx.x: the posterior of `fused` (reference `:60-69`), then one
