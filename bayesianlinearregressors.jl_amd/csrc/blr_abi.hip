@@ -1178,6 +1178,12 @@ struct MargImages {
   }
 };
 
+// Workgroups per regressor of a kernel that walks tiles: every workgroup amortises its set-up (the image) over its tiles, about two
+// workgroups per CU over the launch's nb regressors
+inline int64_t tile_groups(const blr_handle* h, int64_t ntiles, int64_t nb) {
+  return std::max<int64_t>(1, std::min<int64_t>(ntiles, (2 * (int64_t)h->cus + nb - 1) / nb));
+}
+
 // ---- D = 128 with a factor U (aligned ColVecs, or RowVecs): the triangular inverse once per regressor (marg_image_kernel), then a
 // dependency-free product stream with the epilogue of A at the store (marginals_gemm_kernel<T, ROWV, A>, blr_marginals.hpp).
 // A = MarginalArgs<T>: blr_marginals_batched_*; A = LooGemmArgs<T>: blr_loo_batched_*.  Regressors in chunks whose images fit 256 MiB.
@@ -1205,7 +1211,7 @@ struct MargProduct {
     // regressor 104.8 us, 16 -- two rounds -- 116.3, 32: 126.9; 256 regressors: 2 per regressor); every workgroup copies the
     // 74 KB image once: at least four tiles per wave
     const int64_t ntiles = ((int64_t)a.N + 15) / 16;
-    const int64_t per_reg = std::max<int64_t>(1, std::min<int64_t>((ntiles + 15) / 16, (2 * (int64_t)h->cus + nb - 1) / nb));
+    const int64_t per_reg = tile_groups(h, (ntiles + 15) / 16, nb);
     a.reg0 = (int)b0;
     hipLaunchKernelGGL(kernel(a.layout), dim3((unsigned)per_reg, (unsigned)nb), dim3(kThreads), G::LDS_BYTES, h->stream, a, (const T*)img);
   }
@@ -2402,8 +2408,7 @@ int rand_multi_batched(blr_handle* h, int memspace, int layout, int64_t B, int64
   const int64_t ntiles = (N + kMargTile - 1) / kMargTile;
   for (int64_t b0 = 0; b0 < B; b0 += chunk) {
     const int64_t nb = std::min<int64_t>(chunk, B - b0);
-    // every workgroup of the projection amortises its set-up over its tiles: about two workgroups per CU in all
-    const int64_t ngroups = std::max<int64_t>(1, std::min<int64_t>(ntiles, (2 * (int64_t)h->cus + nb - 1) / nb));
+    const int64_t ngroups = tile_groups(h, ntiles, nb);  // (the projection's)
     a.X = X_d; a.s = s_d; a.M = M_d; a.Z1 = Z1_d; a.Z2 = Z2_d; a.W = W_d; a.Y = Y_d; a.info = info_d;
     a.Wf = proj ? reinterpret_cast<T*>(h->aux.p) : nullptr;
     a.ngroups = (int)ngroups; a.reg0 = (int)b0; a.nreg = (int)nb;
@@ -2981,6 +2986,103 @@ int downdate_factor(blr_handle* h, int memspace, int layout, int64_t B, int64_t 
 // ---- exact leave-one-out predictives of a state's observations (blr_loo.hpp) -------------------------------------------------
 constexpr size_t kLooWorkspace = (size_t)256 << 20;  // bound of the per-chunk intermediates (at least one regressor)
 
+// ---- what the held-out entry points share behind their own argument checks (blr_loo_*, blr_kfold_*) ----
+// Status of every state: loo_check_kernel, at most 65535 regressors per launch (grid.x; the empty totals' launches too).  Returns that
+// chunk; the caller asks for the launches' error.
+template <typename T>
+int64_t heldout_status(blr_handle* h, int64_t B, int64_t D, int64_t N, const T* Tf, int64_t ldt, int64_t strideT, const T* s, int64_t strides,
+                       int noise_kind, int32_t* info) {
+  const int64_t ychunk = h->cap_chunk(65535);
+  for (int64_t b0 = 0; b0 < B; b0 += ychunk)
+    hipLaunchKernelGGL(loo_check_kernel<T>, dim3((unsigned)std::min<int64_t>(ychunk, B - b0)), dim3(kThreads), 0, h->stream, Tf + b0 * strideT,
+                       ldt, strideT, (int)D, s + b0 * strides, strides, noise_kind, (int)N, info + b0);
+  return ychunk;
+}
+// One operand of a held-out call: the caller's pointer, its leading dimension and stride per regressor, where the staged pointer goes
+template <typename P>
+struct HeldoutOp { P* p; int64_t ld, stride; P** dev; };
+// The inputs staged through `io`: X, the N x S targets, s (no ld), the D x S mean(s) and T (a single column: S = 1, Y.ld = N,
+// M.ld = D).  At N = 0 nothing of X, the targets and s is read ...
+template <typename T>
+int heldout_stage_in(CallIO& io, int layout, int noise_kind, int64_t B, int64_t D, int64_t N, int64_t S, HeldoutOp<const T> X, HeldoutOp<const T> Y,
+                     HeldoutOp<const T> s, HeldoutOp<const T> M, HeldoutOp<const T> Tf) {
+  const size_t x_one = N == 0 ? 0 : (layout == BLR_LAYOUT_COLVECS ? mat_extent(D, N, X.ld) : mat_extent(N, D, X.ld));
+  const size_t s_one = N == 0 ? 0 : (noise_kind == BLR_NOISE_DIAGONAL ? (size_t)N : 1);
+  int rc;
+  if ((rc = io.in(X.p, x_one ? extent(B, X.stride, x_one) : 0, X.dev))) return rc;
+  if ((rc = io.in(Y.p, N ? extent(B, Y.stride, mat_extent(N, S, Y.ld)) : 0, Y.dev))) return rc;
+  if ((rc = io.in(s.p, s_one ? extent(B, s.stride, s_one) : 0, s.dev))) return rc;
+  if ((rc = io.in(M.p, extent(B, M.stride, mat_extent(D, S, M.ld)), M.dev))) return rc;
+  return io.in(Tf.p, extent(B, Tf.stride, mat_extent(D, D, Tf.ld)), Tf.dev);
+}
+// ... and the outputs: the N x S means, the N variances (no ld), the n_ll x S log densities, the S totals (no ld) and info (a single
+// column: S = 1, mean.ld = N, ll.ld = n_ll, total.stride = 1)
+template <typename T>
+int heldout_stage_out(CallIO& io, int64_t B, int64_t N, int64_t S, int64_t n_ll, HeldoutOp<T> mean, HeldoutOp<T> var, HeldoutOp<double> ll,
+                      HeldoutOp<double> total, int32_t* info, int32_t** info_d) {
+  int rc;
+  if ((rc = io.out(mean.p, N ? extent(B, mean.stride, mat_extent(N, S, mean.ld)) : 0, mean.dev))) return rc;
+  if ((rc = io.out(var.p, N ? extent(B, var.stride, (size_t)N) : 0, var.dev))) return rc;
+  if ((rc = io.out(ll.p, N ? extent(B, ll.stride, mat_extent(n_ll, S, ll.ld)) : 0, ll.dev))) return rc;
+  if ((rc = io.out(total.p, extent(B, total.stride, (size_t)S), total.dev))) return rc;
+  return io.out(info, (size_t)B, info_d);
+}
+// The totals need the log densities somewhere: wanted without them, the log densities go to workspace, S rows of n doubles per
+// regressor, a row rounded up to `pad` bytes.
+struct LogpdfSpill {
+  const bool on;
+  const int64_t ld;  // doubles per row
+  const size_t per;  // bytes per regressor (0: no spill)
+  LogpdfSpill(const double* total, const double* ll, int64_t n, int64_t S = 1, size_t pad = 256)
+      : on(total && !ll), ld((int64_t)(((size_t)n * sizeof(double) + pad - 1) / pad * pad / sizeof(double))), per(on ? (size_t)S * ld * sizeof(double) : 0) {}
+  // a chunk's rows at `base`, indexed by the global regressor as the outputs are (b0: the chunk's first)
+  double* rows(char* base, int64_t b0) const { return reinterpret_cast<double*>(base) - b0 * (int64_t)(per / sizeof(double)); }
+};
+// Totals of regressors b0 .. b0 + nb - 1 over their n log densities (ll NULL, n = 0: empty sums): single-column states ...
+inline void heldout_totals(blr_handle* h, int64_t b0, int64_t nb, const double* ll, int64_t stride_ll, int64_t n, double* total, const int32_t* info) {
+  hipLaunchKernelGGL(loo_total_kernel, dim3((unsigned)nb), dim3(kThreads), 0, h->stream, ll, stride_ll, (int)n, total, info, (int)b0);
+}
+// ... and states of S columns
+inline void heldout_cols_totals(blr_handle* h, int64_t b0, int64_t nb, int64_t S, const double* ll, int64_t ld_ll, int64_t stride_ll, int64_t n,
+                                double* total, int64_t stride_t, const int32_t* info) {
+  hipLaunchKernelGGL(loo_cols_total_kernel, dim3((unsigned)S, (unsigned)nb), dim3(kThreads), 0, h->stream, ll, ld_ll, stride_ll, (int)n, total,
+                     stride_t, info, (int)b0);
+}
+// N = 0: empty sums, for the regressors whose state passed the check (cols: the totals are [S] per regressor, stride_t apart)
+inline int heldout_empty_totals(blr_handle* h, int64_t B, int64_t ychunk, bool cols, int64_t S, double* total, int64_t stride_t, const int32_t* info) {
+  for (int64_t b0 = 0; total && b0 < B; b0 += ychunk) {
+    const int64_t nb = std::min<int64_t>(ychunk, B - b0);
+    if (cols) heldout_cols_totals(h, b0, nb, S, nullptr, 0, 0, 0, total, stride_t, info);
+    else heldout_totals(h, b0, nb, nullptr, 0, 0, total, info);
+  }
+  HIP_TRY(h, hipGetLastError());
+  return 0;
+}
+// Regressors per launch: grid.y; the images if the route builds them; the rows of Z (z_one elements a regressor, 0: none) within
+// 256 MiB; `per` bytes a regressor of the other intermediates (0: none) within kLooWorkspace -- at least one regressor
+template <typename T>
+int64_t whitened_chunk(const blr_handle* h, int64_t B, bool images, size_t z_one, size_t per) {
+  int64_t chunk = std::min<int64_t>(B, 65535);
+  if (images) chunk = std::min<int64_t>(chunk, MargImages<T>::kMaxChunk);
+  if (z_one) chunk = std::min<int64_t>(chunk, std::max<int64_t>(1, (int64_t)(((size_t)256 << 20) / (z_one * sizeof(T)))));
+  if (per) chunk = std::max<int64_t>(1, std::min<int64_t>(chunk, (int64_t)(kLooWorkspace / per)));
+  return h->cap_chunk(chunk);
+}
+// The composed large-D route: a chunk's LATENT variance (the noise is the zero word at `zero`), with the mean if wanted, by whichever
+// route blr_marginals_batched_* takes -- nested: no drain between the halves, its message dropped
+template <typename T>
+int heldout_latent_marginals(blr_handle* h, int layout, int64_t nb, int64_t D, int64_t N, const T* X, int64_t ldx, int64_t strideX, const T* zero,
+                             const T* mw, int64_t stridemw, const T* Tf, int64_t ldt, int64_t strideT, T* mean, T* var, int64_t ldw, int32_t* inf) {
+  int rc;
+  {
+    const AsyncScope no_drain(h, true);
+    rc = marginals_batched<T>(h, BLR_MEM_DEVICE, layout, nb, D, N, X, ldx, strideX, BLR_NOISE_ISOTROPIC, zero, 0, BLR_PRIOR_UPPER_FACTOR, mw,
+                              stridemw, Tf, ldt, strideT, mean, mean ? ldw : 0, var, ldw, inf);
+  }
+  if (!rc) h->err.clear();
+  return rc;
+}
+
 // device operands; l carries y, s, the three outputs and info (global regressor indexing)
 template <typename T>
 int loo_launch(blr_handle* h, int layout, int64_t B, int64_t D, int64_t N, const T* X, int64_t ldx, int64_t strideX, LooArgs<T> l,
@@ -2990,31 +3092,27 @@ int loo_launch(blr_handle* h, int layout, int64_t B, int64_t D, int64_t N, const
   if ((rc = ensure_stats(h))) return rc;
   l.degenerate = h->stats_dev + 3;
   int32_t* const info = const_cast<int32_t*>(l.info);
-  const int64_t ychunk = h->cap_chunk(65535);  // grid.x / grid.y <= 65535: the check and the empty totals
-  for (int64_t b0 = 0; b0 < B; b0 += ychunk)
-    hipLaunchKernelGGL(loo_check_kernel<T>, dim3((unsigned)std::min<int64_t>(ychunk, B - b0)), dim3(kThreads), 0, h->stream, Tf + b0 * strideT,
-                       ldt, strideT, (int)D, l.s + b0 * l.strides, l.strides, l.noise_kind, (int)N, info + b0);
+  const int64_t ychunk = heldout_status<T>(h, B, D, N, Tf, ldt, strideT, l.s, l.strides, l.noise_kind, info);
   HIP_TRY(h, hipGetLastError());
   // the route follows from the shape, as the marginals' does: the fused product stream at D = 128
   const bool fused = MP::takes(h, layout, D, N, X, ldx, strideX);
-  const bool ll_ws = total && !l.ll;  // the totals need the log densities somewhere
-  const size_t item = sizeof(T), row = ((size_t)N * item + 255) & ~(size_t)255, row_ll = ((size_t)N * sizeof(double) + 255) & ~(size_t)255;
-  const size_t per = (fused ? 0 : 2 * row) + (ll_ws ? row_ll : 0) + sizeof(int32_t);
+  const LogpdfSpill spill(total, l.ll, N);
+  const size_t item = sizeof(T), row = ((size_t)N * item + 255) & ~(size_t)255;
+  const size_t per = (fused ? 0 : 2 * row) + spill.per + sizeof(int32_t);
   int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(B, 65535), (int64_t)(kLooWorkspace / per)));
   if (fused) chunk = std::min<int64_t>(chunk, MP::kMaxChunk);
   chunk = h->cap_chunk(chunk);
   const size_t off_var = (size_t)chunk * row, off_ll = fused ? 0 : 2 * (size_t)chunk * row;
-  const size_t off_zero = off_ll + (ll_ws ? (size_t)chunk * row_ll : 0), off_inf = off_zero + 256;
+  const size_t off_zero = off_ll + (size_t)chunk * spill.per, off_inf = off_zero + 256;
   if (N > 0 && (rc = h->loo_ws.reserve(h, off_inf + (size_t)chunk * sizeof(int32_t) + 256))) return rc;
   char* const ws = h->loo_ws.p;
   const int64_t ldw = (int64_t)(row / item);
   if (N > 0 && !fused) HIP_TRY(h, hipMemsetAsync(ws + off_zero, 0, sizeof(T), h->stream));  // the composed route's zero noise
   if (N > 0 && fused && (rc = MP::prepare(h, layout, chunk))) return rc;
-  const int64_t ldll = ll_ws ? (int64_t)(row_ll / sizeof(double)) : l.stride_ll;
   for (int64_t b0 = 0; N > 0 && b0 < B; b0 += chunk) {
     const int64_t nb = std::min<int64_t>(chunk, B - b0);
     LooArgs<T> lc = l;
-    if (ll_ws) { lc.ll = reinterpret_cast<double*>(ws + off_ll) - b0 * ldll; lc.stride_ll = ldll; }  // (indexed by the global regressor)
+    if (spill.on) { lc.ll = spill.rows(ws + off_ll, b0); lc.stride_ll = spill.ld; }
     if (fused) {
       LooGemmArgs<T> a{};
       a.X = X; a.ldx = ldx; a.strideX = strideX; a.s = l.s; a.strides = l.strides; a.mw = mw; a.stridemw = stridemw;
@@ -3026,31 +3124,19 @@ int loo_launch(blr_handle* h, int layout, int64_t B, int64_t D, int64_t N, const
       // mean and LATENT variance (zero noise) by whichever marginal route the shape takes, then the epilogue
       T* const mean = reinterpret_cast<T*>(ws);
       T* const var = reinterpret_cast<T*>(ws + off_var);
-      {
-        const AsyncScope no_drain(h, true);  // (between the two halves)
-        rc = marginals_batched<T>(h, BLR_MEM_DEVICE, layout, nb, D, N, X + b0 * strideX, ldx, strideX, BLR_NOISE_ISOTROPIC,
-                                  reinterpret_cast<const T*>(ws + off_zero), 0, BLR_PRIOR_UPPER_FACTOR, mw + b0 * stridemw, stridemw,
-                                  Tf + b0 * strideT, ldt, strideT, mean, ldw, var, ldw, reinterpret_cast<int32_t*>(ws + off_inf));
-      }
+      rc = heldout_latent_marginals<T>(h, layout, nb, D, N, X + b0 * strideX, ldx, strideX, reinterpret_cast<const T*>(ws + off_zero),
+                                       mw + b0 * stridemw, stridemw, Tf + b0 * strideT, ldt, strideT, mean, var, ldw,
+                                       reinterpret_cast<int32_t*>(ws + off_inf));
       if (rc) return rc;
-      h->err.clear();
       const int64_t gx = std::max<int64_t>(1, std::min<int64_t>((N + kThreads - 1) / kThreads, (4 * (int64_t)h->cus + nb - 1) / nb));
       hipLaunchKernelGGL(loo_finish_kernel<T>, dim3((unsigned)gx, (unsigned)nb), dim3(kThreads), 0, h->stream, lc, (const T*)mean,
                          (const T*)var, ldw, (int)b0);
     }
-    if (total)
-      hipLaunchKernelGGL(loo_total_kernel, dim3((unsigned)nb), dim3(kThreads), 0, h->stream, (const double*)lc.ll, lc.stride_ll, (int)N,
-                         total, l.info, (int)b0);
+    if (total) heldout_totals(h, b0, nb, lc.ll, lc.stride_ll, N, total, l.info);
     HIP_TRY(h, hipGetLastError());
   }
   h->count_chunks(B, N > 0 ? chunk : ychunk);  // (after the loop: the composed route's marginals count their own)
-  if (N == 0 && total) {  // an empty sum, for the regressors whose state passed the check
-    for (int64_t b0 = 0; b0 < B; b0 += ychunk)
-      hipLaunchKernelGGL(loo_total_kernel, dim3((unsigned)std::min<int64_t>(ychunk, B - b0)), dim3(kThreads), 0, h->stream,
-                         (const double*)nullptr, (int64_t)0, 0, total, l.info, (int)b0);
-    HIP_TRY(h, hipGetLastError());
-  }
-  return 0;
+  return N == 0 && total ? heldout_empty_totals(h, B, ychunk, false, 1, total, 1, l.info) : 0;
 }
 
 template <typename T>
@@ -3091,23 +3177,14 @@ int loo_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, i
   l.stridey = stridey; l.strides = strides; l.noise_kind = noise_kind; l.stride_lm = stride_lm; l.stride_lv = stride_lv;
   l.stride_ll = stride_ll; l.N = (int)N;
   CallIO io(h, memspace);
-  const size_t x_one = N == 0 ? 0 : (layout == BLR_LAYOUT_COLVECS ? mat_extent(D, N, ldx) : mat_extent(N, D, ldx));
-  const size_t s_one = N == 0 ? 0 : (noise_kind == BLR_NOISE_DIAGONAL ? (size_t)N : 1);
-  const size_t n_out = (size_t)N;
   int rc;
   const T *dX = nullptr, *dmw = nullptr, *dT = nullptr;
   double* dtot = nullptr;
   int32_t* dinfo = nullptr;
-  if ((rc = io.in(X, x_one ? extent(B, strideX, x_one) : 0, &dX))) return rc;
-  if ((rc = io.in(y, n_out ? extent(B, stridey, n_out) : 0, &l.y))) return rc;
-  if ((rc = io.in(s, s_one ? extent(B, strides, s_one) : 0, &l.s))) return rc;
-  if ((rc = io.in(mw, extent(B, stridemw, (size_t)D), &dmw))) return rc;
-  if ((rc = io.in(Tf, extent(B, strideT, mat_extent(D, D, ldt)), &dT))) return rc;
-  if ((rc = io.out(loo_mean, n_out ? extent(B, stride_lm, n_out) : 0, &l.lm))) return rc;
-  if ((rc = io.out(loo_var, n_out ? extent(B, stride_lv, n_out) : 0, &l.lv))) return rc;
-  if ((rc = io.out(loo_logpdf, n_out ? extent(B, stride_ll, n_out) : 0, &l.ll))) return rc;
-  if ((rc = io.out(loo_total, (size_t)B, &dtot))) return rc;
-  if ((rc = io.out(info, (size_t)B, &dinfo))) return rc;
+  if ((rc = heldout_stage_in<T>(io, layout, noise_kind, B, D, N, 1, {X, ldx, strideX, &dX}, {y, N, stridey, &l.y}, {s, 0, strides, &l.s},
+                                {mw, D, stridemw, &dmw}, {Tf, ldt, strideT, &dT}))) return rc;
+  if ((rc = heldout_stage_out<T>(io, B, N, 1, N, {loo_mean, N, stride_lm, &l.lm}, {loo_var, 0, stride_lv, &l.lv}, {loo_logpdf, N, stride_ll, &l.ll},
+                                 {loo_total, 0, 1, &dtot}, info, &dinfo))) return rc;
   l.info = dinfo;
   if ((rc = loo_launch<T>(h, layout, B, D, N, dX, ldx, strideX, l, dmw, stridemw, dT, ldt, strideT, dtot))) return rc;
   return io.finish();
@@ -3695,8 +3772,7 @@ int marginals_multi_batched(blr_handle* h, int memspace, int layout, int64_t B, 
     const int64_t nb = std::min<int64_t>(chunk, B - b0);
     if (with_image)
       a.img = MargImages<T>::launch(h, U + b0 * strideU, ldu, strideU, (int)D, chol_info ? (const int32_t*)(chol_info + b0) : (const int32_t*)nullptr, 0, nb);
-    // every workgroup amortises its set-up (the image, the fragments of M) over its tiles: about two workgroups per CU in all
-    const int64_t ngroups = std::max<int64_t>(1, std::min<int64_t>(ntiles, (2 * (int64_t)h->cus + nb * passes - 1) / (nb * passes)));
+    const int64_t ngroups = tile_groups(h, ntiles, nb * passes);  // (the set-up: the image, the fragments of M)
     a.X = X_d; a.s = s_d; a.M = M_d; a.dprior = kind == BLR_PRIOR_DIAGONAL ? U : nullptr; a.stridedp = strideU;
     a.info = chol_info; a.mean = mean_d; a.var = var_d; a.ngroups = (int)ngroups; a.reg0 = (int)b0;
     hipLaunchKernelGGL(kern, dim3((unsigned)(passes * ngroups), (unsigned)nb), dim3(kThreads), lds, h->stream, a);
@@ -3820,10 +3896,7 @@ int mean_and_cov_batched(blr_handle* h, int memspace, int layout, int64_t B, int
   const bool with_image = C_d && kind == BLR_PRIOR_UPPER_FACTOR;
   // regressors per launch: grid.y, the images within 256 MiB, the rows of Z within 256 MiB (at least one regressor: 16 MiB at most)
   const size_t z_one = cov_z_elems((int)D, (int)N);
-  int64_t chunk = std::min<int64_t>(B, 65535);
-  if (with_image) chunk = std::min<int64_t>(chunk, MargImages<T>::kMaxChunk);
-  if (C_d) chunk = std::min<int64_t>(chunk, std::max<int64_t>(1, (int64_t)(((size_t)256 << 20) / (z_one * sizeof(T)))));
-  chunk = h->cap_chunk(chunk);
+  const int64_t chunk = whitened_chunk<T>(h, B, with_image, C_d ? z_one : 0, 0);
   h->count_chunks(B, chunk);
   const size_t lds_w = cov_whiten_lds_bytes(sizeof(T), (int)D, with_image), lds_t = cov_tiles_lds_bytes(sizeof(T), (int)D);
   void (*const whiten)(CovArgs<T>) = layout == BLR_LAYOUT_ROWVECS ? cov_whiten_kernel<T, LAYOUT_ROWVECS> : cov_whiten_kernel<T, LAYOUT_COLVECS>;
@@ -3835,8 +3908,7 @@ int mean_and_cov_batched(blr_handle* h, int memspace, int layout, int64_t B, int
   for (int64_t b0 = 0; b0 < B; b0 += chunk) {
     const int64_t nb = std::min<int64_t>(chunk, B - b0);
     if (with_image) a.img = MargImages<T>::launch(h, U + b0 * strideU, ldu, strideU, (int)D, (const int32_t*)(info_d + b0), 0, nb);
-    // every workgroup amortises its set-up (the image) over its tiles: about two workgroups per CU in all
-    const int64_t ngroups = std::max<int64_t>(1, std::min<int64_t>(ntiles, (2 * (int64_t)h->cus + nb - 1) / nb));
+    const int64_t ngroups = tile_groups(h, ntiles, nb);
     a.X = X_d; a.s = s_d; a.mw = mw_d; a.dprior = kind == BLR_PRIOR_DIAGONAL ? U : nullptr; a.stridedp = strideU;
     a.info = info_d; a.mean = mean_d; a.C = C_d; a.Z = C_d ? reinterpret_cast<T*>(h->cov_ws.p) : nullptr;
     a.ngroups = (int)ngroups; a.reg0 = (int)b0;
@@ -3897,56 +3969,35 @@ int loo_multi_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_
   a.ldx = ldx; a.strideX = strideX; a.ldY = ldY; a.strideY = strideY; a.strides = strides; a.ldm = ldm; a.strideM = strideM;
   a.ld_lm = ld_lm; a.stride_lm = stride_lm; a.stride_lv = stride_lv; a.ld_ll = ld_ll; a.stride_ll = stride_ll;
   a.noise_kind = noise_kind; a.D = (int)D; a.N = (int)N; a.S = (int)S;
-  const size_t x_one = N == 0 ? 0 : (layout == BLR_LAYOUT_COLVECS ? mat_extent(D, N, ldx) : mat_extent(N, D, ldx));
-  const size_t s_one = N == 0 ? 0 : (noise_kind == BLR_NOISE_DIAGONAL ? (size_t)N : 1);
   const T* T_d = nullptr;
   double* tot_d = nullptr;
   int32_t* info_d = nullptr;
   int rc;
-  if ((rc = io.in(X, x_one ? extent(B, strideX, x_one) : 0, &a.X))) return rc;
-  if ((rc = io.in(Y, N ? extent(B, strideY, mat_extent(N, S, ldY)) : 0, &a.Y))) return rc;
-  if ((rc = io.in(s, s_one ? extent(B, strides, s_one) : 0, &a.s))) return rc;
-  if ((rc = io.in(M, extent(B, strideM, mat_extent(D, S, ldm)), &a.M))) return rc;
-  if ((rc = io.in(Tf, extent(B, strideT, mat_extent(D, D, ldt)), &T_d))) return rc;
-  if ((rc = io.out(loo_mean, N ? extent(B, stride_lm, mat_extent(N, S, ld_lm)) : 0, &a.lm))) return rc;
-  if ((rc = io.out(loo_var, N ? extent(B, stride_lv, (size_t)N) : 0, &a.lv))) return rc;
-  if ((rc = io.out(loo_logpdf, N ? extent(B, stride_ll, mat_extent(N, S, ld_ll)) : 0, &a.ll))) return rc;
-  if ((rc = io.out(loo_total, extent(B, stride_lt, (size_t)S), &tot_d))) return rc;
-  if ((rc = io.out(info, (size_t)B, &info_d))) return rc;
+  if ((rc = heldout_stage_in<T>(io, layout, noise_kind, B, D, N, S, {X, ldx, strideX, &a.X}, {Y, ldY, strideY, &a.Y}, {s, 0, strides, &a.s},
+                                {M, ldm, strideM, &a.M}, {Tf, ldt, strideT, &T_d}))) return rc;
+  if ((rc = heldout_stage_out<T>(io, B, N, S, N, {loo_mean, ld_lm, stride_lm, &a.lm}, {loo_var, 0, stride_lv, &a.lv}, {loo_logpdf, ld_ll, stride_ll, &a.ll},
+                                 {loo_total, 0, stride_lt, &tot_d}, info, &info_d))) return rc;
   a.info = info_d;
   if ((rc = ensure_stats(h))) return rc;
   a.degenerate = h->stats_dev + 3;
 
-  // status: loo_check_kernel as blr_loo_batched_* launches it
-  const int64_t ychunk = h->cap_chunk(65535);  // grid.x / grid.y <= 65535: the check and the empty totals
+  const int64_t ychunk = heldout_status<T>(h, B, D, N, T_d, ldt, strideT, a.s, strides, noise_kind, info_d);
   h->count_chunks(B, ychunk);
-  for (int64_t b0 = 0; b0 < B; b0 += ychunk)
-    hipLaunchKernelGGL(loo_check_kernel<T>, dim3((unsigned)std::min<int64_t>(ychunk, B - b0)), dim3(kThreads), 0, h->stream, T_d + b0 * strideT,
-                       ldt, strideT, (int)D, a.s + b0 * strides, strides, noise_kind, (int)N, info_d + b0);
   HIP_TRY(h, hipGetLastError());
-  if (N == 0) {  // empty sums, for the regressors whose state passed the check
-    for (int64_t b0 = 0; tot_d && b0 < B; b0 += ychunk)
-      hipLaunchKernelGGL(loo_cols_total_kernel, dim3((unsigned)S, (unsigned)std::min<int64_t>(ychunk, B - b0)), dim3(kThreads), 0, h->stream,
-                         (const double*)nullptr, (int64_t)0, (int64_t)0, 0, tot_d, stride_lt, (const int32_t*)info_d, (int)b0);
-    HIP_TRY(h, hipGetLastError());
-    return io.finish();
-  }
+  if (N == 0) return (rc = heldout_empty_totals(h, B, ychunk, true, S, tot_d, stride_lt, info_d)) ? rc : io.finish();
 
   // chunks of regressors: grid.y, the images (D <= 128) and the per-chunk intermediates each within their bound
   const bool small = D <= kMaxSmallD;
-  const bool ll_ws = tot_d && !a.ll;  // the totals need the log densities somewhere
-  const size_t item = sizeof(T), row = ((size_t)N * item + 255) & ~(size_t)255, row_ll = ((size_t)N * sizeof(double) + 255) & ~(size_t)255;
-  const size_t per = (small ? 0 : (1 + (size_t)S) * row + sizeof(int32_t)) + (ll_ws ? (size_t)S * row_ll : 0);
-  int64_t chunk = std::min<int64_t>(B, 65535);
-  if (small) chunk = std::min<int64_t>(chunk, MargImages<T>::kMaxChunk);
-  if (per) chunk = std::max<int64_t>(1, std::min<int64_t>(chunk, (int64_t)(kLooWorkspace / per)));
-  chunk = h->cap_chunk(chunk);
+  const LogpdfSpill spill(tot_d, a.ll, N, S);
+  const size_t item = sizeof(T), row = ((size_t)N * item + 255) & ~(size_t)255;
+  const size_t per = (small ? 0 : (1 + (size_t)S) * row + sizeof(int32_t)) + spill.per;
+  const int64_t chunk = whitened_chunk<T>(h, B, small, 0, per);
   const size_t off_mean = (size_t)chunk * row;                                  // (D > 128) var first, then the means
   const size_t off_ll = small ? 0 : off_mean + (size_t)chunk * S * row;
-  const size_t off_zero = off_ll + (ll_ws ? (size_t)chunk * S * row_ll : 0), off_inf = off_zero + 256;
+  const size_t off_zero = off_ll + (size_t)chunk * spill.per, off_inf = off_zero + 256;
   if (per && (rc = h->loo_ws.reserve(h, off_inf + (size_t)chunk * sizeof(int32_t) + 256))) return rc;
   char* const ws = h->loo_ws.p;
-  const int64_t ldw = (int64_t)(row / item), ldll_ws = (int64_t)(row_ll / sizeof(double));
+  const int64_t ldw = (int64_t)(row / item);
   const size_t lds = loo_cols_lds_bytes(sizeof(T), (int)D);
   void (*const kern)(LooColsArgs<T>) = layout == BLR_LAYOUT_ROWVECS ? loo_cols_kernel<T, LAYOUT_ROWVECS> : loo_cols_kernel<T, LAYOUT_COLVECS>;
   if (small) {
@@ -3960,31 +4011,21 @@ int loo_multi_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_
     const int64_t nb = std::min<int64_t>(chunk, B - b0);
     LooColsArgs<T> c = a;
     c.reg0 = (int)b0;
-    if (ll_ws) {  // (indexed by the global regressor)
-      c.ld_ll = ldll_ws; c.stride_ll = ldll_ws * S;
-      c.ll = reinterpret_cast<double*>(ws + off_ll) - b0 * c.stride_ll;
-    }
+    if (spill.on) { c.ld_ll = spill.ld; c.stride_ll = spill.ld * S; c.ll = spill.rows(ws + off_ll, b0); }
     if (small) {
       // L^-T of every factor as an MFMA image (marg_image_kernel, the existing instantiation), then ONE launch over (tile groups, regressors)
       c.img = MargImages<T>::launch(h, T_d + b0 * strideT, ldt, strideT, (int)D, (const int32_t*)(info_d + b0), 0, nb);
-      // every workgroup amortises its set-up (the image) over its tiles: about two workgroups per CU in all
-      const int64_t ngroups = std::max<int64_t>(1, std::min<int64_t>(ntiles, (2 * (int64_t)h->cus + nb - 1) / nb));
-      c.ngroups = (int)ngroups;
-      hipLaunchKernelGGL(kern, dim3((unsigned)ngroups, (unsigned)nb), dim3(kThreads), lds, h->stream, c);
+      c.ngroups = (int)tile_groups(h, ntiles, nb);
+      hipLaunchKernelGGL(kern, dim3((unsigned)c.ngroups, (unsigned)nb), dim3(kThreads), lds, h->stream, c);
     } else {
       // correct, not fast: the LATENT variance (zero noise) of the chunk by the large-D route of blr_marginals_batched_*, the means one
       // regressor after the other as X'M (launch_project), then the epilogue.  A state that failed the check is skipped by the finish.
       T* const var = reinterpret_cast<T*>(ws);
       T* const mean = reinterpret_cast<T*>(ws + off_mean);
-      {
-        const AsyncScope no_drain(h, true);  // (between the halves)
-        // (mw is not read without a mean; X stands in as a non-NULL pointer)
-        rc = marginals_batched<T>(h, BLR_MEM_DEVICE, layout, nb, D, N, a.X + b0 * strideX, ldx, strideX, BLR_NOISE_ISOTROPIC,
-                                  reinterpret_cast<const T*>(ws + off_zero), 0, BLR_PRIOR_UPPER_FACTOR, a.X, 0, T_d + b0 * strideT, ldt, strideT,
-                                  (T*)nullptr, 0, var, ldw, reinterpret_cast<int32_t*>(ws + off_inf));
-      }
+      // (mw is not read without a mean; X stands in as a non-NULL pointer)
+      rc = heldout_latent_marginals<T>(h, layout, nb, D, N, a.X + b0 * strideX, ldx, strideX, reinterpret_cast<const T*>(ws + off_zero), a.X, 0,
+                                       T_d + b0 * strideT, ldt, strideT, (T*)nullptr, var, ldw, reinterpret_cast<int32_t*>(ws + off_inf));
       if (rc) return rc;
-      h->err.clear();
       for (int64_t b = 0; b < nb; ++b)
         launch_project<T>(h, layout, D, N, S, a.X + (b0 + b) * strideX, ldx, a.M + (b0 + b) * strideM, ldm, (const T*)nullptr, BLR_NOISE_ISOTROPIC,
                           (const T*)nullptr, 0, mean + b * S * ldw, ldw);
@@ -3992,9 +4033,7 @@ int loo_multi_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_
       hipLaunchKernelGGL(loo_cols_finish_kernel<T>, dim3((unsigned)gx, (unsigned)nb), dim3(kThreads), 0, h->stream, c, (const T*)mean, ldw, S * ldw,
                          (const T*)var, ldw);
     }
-    if (tot_d)
-      hipLaunchKernelGGL(loo_cols_total_kernel, dim3((unsigned)S, (unsigned)nb), dim3(kThreads), 0, h->stream, (const double*)c.ll, c.ld_ll,
-                         c.stride_ll, (int)N, tot_d, stride_lt, (const int32_t*)info_d, (int)b0);
+    if (tot_d) heldout_cols_totals(h, b0, nb, S, c.ll, c.ld_ll, c.stride_ll, N, tot_d, stride_lt, info_d);
     HIP_TRY(h, hipGetLastError());
   }
   h->count_chunks(B, chunk);  // (after the loop: the large-D route's marginals count their own)
@@ -4046,45 +4085,26 @@ int kfold_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_t D,
   KfoldArgs<T> k{};
   k.stridey = stridey; k.strides = strides; k.noise_kind = noise_kind; k.stride_km = stride_km; k.stride_kv = stride_kv;
   k.stride_kl = stride_kl; k.D = (int)D; k.N = (int)N; k.F = (int)F;
-  const size_t x_one = N == 0 ? 0 : (layout == BLR_LAYOUT_COLVECS ? mat_extent(D, N, ldx) : mat_extent(N, D, ldx));
-  const size_t s_one = N == 0 ? 0 : (noise_kind == BLR_NOISE_DIAGONAL ? (size_t)N : 1);
-  const size_t n_out = (size_t)N;
   int rc;
   const T *X_d = nullptr, *mw_d = nullptr, *T_d = nullptr;
   double* tot_d = nullptr;
   int32_t* info_d = nullptr;
-  if ((rc = io.in(X, x_one ? extent(B, strideX, x_one) : 0, &X_d))) return rc;
-  if ((rc = io.in(y, n_out ? extent(B, stridey, n_out) : 0, &k.y))) return rc;
-  if ((rc = io.in(s, s_one ? extent(B, strides, s_one) : 0, &k.s))) return rc;
-  if ((rc = io.in(mw, extent(B, stridemw, (size_t)D), &mw_d))) return rc;
-  if ((rc = io.in(Tf, extent(B, strideT, mat_extent(D, D, ldt)), &T_d))) return rc;
-  if ((rc = io.out(kf_mean, n_out ? extent(B, stride_km, n_out) : 0, &k.km))) return rc;
-  if ((rc = io.out(kf_var, n_out ? extent(B, stride_kv, n_out) : 0, &k.kv))) return rc;
-  if ((rc = io.out(kf_logpdf, n_out ? extent(B, stride_kl, (size_t)nfolds) : 0, &k.kl))) return rc;
-  if ((rc = io.out(kf_total, (size_t)B, &tot_d))) return rc;
-  if ((rc = io.out(info, (size_t)B, &info_d))) return rc;
+  if ((rc = heldout_stage_in<T>(io, layout, noise_kind, B, D, N, 1, {X, ldx, strideX, &X_d}, {y, N, stridey, &k.y}, {s, 0, strides, &k.s},
+                                {mw, D, stridemw, &mw_d}, {Tf, ldt, strideT, &T_d}))) return rc;
+  if ((rc = heldout_stage_out<T>(io, B, N, 1, nfolds, {kf_mean, N, stride_km, &k.km}, {kf_var, 0, stride_kv, &k.kv}, {kf_logpdf, nfolds, stride_kl, &k.kl},
+                                 {kf_total, 0, 1, &tot_d}, info, &info_d))) return rc;
   k.info = info_d;
   if ((rc = ensure_stats(h))) return rc;
   k.degenerate = h->stats_dev + 4;
 
-  // status: loo_check_kernel as blr_loo_batched_* launches it
-  const int64_t ychunk = h->cap_chunk(65535);  // grid.x <= 65535 here: the check and the empty totals
+  const int64_t ychunk = heldout_status<T>(h, B, D, N, T_d, ldt, strideT, k.s, strides, noise_kind, info_d);
   h->count_chunks(B, ychunk);
-  for (int64_t b0 = 0; b0 < B; b0 += ychunk)
-    hipLaunchKernelGGL(loo_check_kernel<T>, dim3((unsigned)std::min<int64_t>(ychunk, B - b0)), dim3(kThreads), 0, h->stream, T_d + b0 * strideT,
-                       ldt, strideT, (int)D, k.s + b0 * strides, strides, noise_kind, (int)N, info_d + b0);
   HIP_TRY(h, hipGetLastError());
-  if (N == 0) {  // an empty sum, for the regressors whose state passed the check
-    for (int64_t b0 = 0; tot_d && b0 < B; b0 += ychunk)
-      hipLaunchKernelGGL(loo_total_kernel, dim3((unsigned)std::min<int64_t>(ychunk, B - b0)), dim3(kThreads), 0, h->stream,
-                         (const double*)nullptr, (int64_t)0, 0, tot_d, (const int32_t*)info_d, (int)b0);
-    HIP_TRY(h, hipGetLastError());
-    return io.finish();
-  }
+  if (N == 0) return (rc = heldout_empty_totals(h, B, ychunk, false, 1, tot_d, 1, info_d)) ? rc : io.finish();
   const int64_t pack_rows = (kFoldMax / F) * F, npacks = (N + pack_rows - 1) / pack_rows;
   const size_t lds_k = kfold_lds_bytes(sizeof(T), (int)std::min<int64_t>(D, kMaxSmallD));
   if ((rc = set_lds_once(h, kfold_kernel<T>, lds_k))) return rc;
-  const bool kl_ws = tot_d && !k.kl;  // the totals need the folds' log densities somewhere
+  const LogpdfSpill spill(tot_d, k.kl, nfolds);
 
   if (D > kMaxSmallD) {
     // correct, not fast: one regressor after the other through the launches of blr_mean_and_cov_* (mean_and_cov_core) into a staging
@@ -4100,7 +4120,7 @@ int kfold_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_t D,
     if ((rc = io.tmp((size_t)N * N, &Ct))) return rc;
     if ((rc = io.tmp((size_t)N, &mt))) return rc;
     if ((rc = io.tmp(1, &it))) return rc;
-    if (kl_ws && (rc = io.tmp((size_t)nfolds, &klt))) return rc;
+    if (spill.on && (rc = io.tmp((size_t)nfolds, &klt))) return rc;
     for (int64_t b = 0; b < B; ++b) {
       if (st[(size_t)b] != 0) continue;  // outputs of that regressor stay untouched
       rc = mean_and_cov_core<T>(h, t, layout, (int)D, (int)N, X_d + b * strideX, ldx, noise_kind, k.s + b * strides, 0, BLR_PRIOR_UPPER_FACTOR,
@@ -4108,11 +4128,9 @@ int kfold_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_t D,
       if (rc) return rc;
       KfoldArgs<T> c = k;
       c.C = Ct; c.ldc = N; c.m = mt; c.stridem = 0; c.reg0 = (int)b;
-      if (kl_ws) { c.kl = klt; c.stride_kl = 0; }
+      if (spill.on) { c.kl = klt; c.stride_kl = 0; }
       hipLaunchKernelGGL(kfold_kernel<T>, dim3((unsigned)npacks, 1), dim3(kThreads), lds_k, h->stream, c);
-      if (tot_d)
-        hipLaunchKernelGGL(loo_total_kernel, dim3(1), dim3(kThreads), 0, h->stream, (const double*)c.kl, c.stride_kl, (int)nfolds, tot_d,
-                           (const int32_t*)info_d, (int)b);
+      if (tot_d) heldout_totals(h, b, 1, c.kl, c.stride_kl, nfolds, tot_d, info_d);
       HIP_TRY(h, hipGetLastError());
     }
     HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -4124,12 +4142,8 @@ int kfold_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_t D,
   // blr_mean_and_cov_batched_*: grid.y, the images and the rows of Z within 256 MiB each, the means (and the folds' log densities when
   // only the totals are wanted) within theirs, at least one regressor
   const size_t z_one = cov_z_elems((int)D, (int)N);
-  const size_t row = ((size_t)N * sizeof(T) + 255) & ~(size_t)255, row_kl = ((size_t)nfolds * sizeof(double) + 255) & ~(size_t)255;
-  const size_t per = row + (kl_ws ? row_kl : 0);
-  int64_t chunk = std::min<int64_t>(std::min<int64_t>(B, 65535), MargImages<T>::kMaxChunk);
-  chunk = std::min<int64_t>(chunk, std::max<int64_t>(1, (int64_t)(((size_t)256 << 20) / (z_one * sizeof(T)))));
-  chunk = std::max<int64_t>(1, std::min<int64_t>(chunk, (int64_t)(kLooWorkspace / per)));
-  chunk = h->cap_chunk(chunk);
+  const size_t row = ((size_t)N * sizeof(T) + 255) & ~(size_t)255, per = row + spill.per;
+  const int64_t chunk = whitened_chunk<T>(h, B, true, z_one, per);
   h->count_chunks(B, chunk);
   const size_t lds_w = cov_whiten_lds_bytes(sizeof(T), (int)D, true);
   void (*const whiten)(CovArgs<T>) = layout == BLR_LAYOUT_ROWVECS ? cov_whiten_kernel<T, LAYOUT_ROWVECS> : cov_whiten_kernel<T, LAYOUT_COLVECS>;
@@ -4138,7 +4152,7 @@ int kfold_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_t D,
   if ((rc = h->cov_ws.reserve(h, (size_t)chunk * z_one * sizeof(T)))) return rc;
   if ((rc = h->loo_ws.reserve(h, (size_t)chunk * per + 256))) return rc;
   char* const ws = h->loo_ws.p;
-  const int64_t ldw = (int64_t)(row / sizeof(T)), ldkl = (int64_t)(row_kl / sizeof(double));
+  const int64_t ldw = (int64_t)(row / sizeof(T));
   const int64_t ntiles = (N + kCovTile - 1) / kCovTile;
   CovArgs<T> a{};
   a.X = X_d; a.ldx = ldx; a.strideX = strideX; a.mw = mw_d; a.stridemw = stridemw; a.info = info_d; a.stridemean = ldw;
@@ -4147,18 +4161,14 @@ int kfold_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_t D,
   for (int64_t b0 = 0; b0 < B; b0 += chunk) {
     const int64_t nb = std::min<int64_t>(chunk, B - b0);
     a.img = MargImages<T>::launch(h, T_d + b0 * strideT, ldt, strideT, (int)D, (const int32_t*)(info_d + b0), 0, nb);
-    // every workgroup amortises its set-up (the image) over its tiles: about two workgroups per CU in all
-    const int64_t ngroups = std::max<int64_t>(1, std::min<int64_t>(ntiles, (2 * (int64_t)h->cus + nb - 1) / nb));
     a.mean = reinterpret_cast<T*>(ws) - b0 * ldw;  // (indexed by the global regressor)
-    a.ngroups = (int)ngroups; a.reg0 = (int)b0;
-    hipLaunchKernelGGL(whiten, dim3((unsigned)ngroups, (unsigned)nb), dim3(kThreads), lds_w, h->stream, a);
+    a.ngroups = (int)tile_groups(h, ntiles, nb); a.reg0 = (int)b0;
+    hipLaunchKernelGGL(whiten, dim3((unsigned)a.ngroups, (unsigned)nb), dim3(kThreads), lds_w, h->stream, a);
     KfoldArgs<T> c = k;
     c.Z = a.Z; c.strideZ = (int64_t)z_one; c.m = a.mean; c.stridem = ldw; c.reg0 = (int)b0;
-    if (kl_ws) { c.kl = reinterpret_cast<double*>(ws + (size_t)chunk * row) - b0 * ldkl; c.stride_kl = ldkl; }
+    if (spill.on) { c.kl = spill.rows(ws + (size_t)chunk * row, b0); c.stride_kl = spill.ld; }
     hipLaunchKernelGGL(kfold_kernel<T>, dim3((unsigned)npacks, (unsigned)nb), dim3(kThreads), lds_k, h->stream, c);
-    if (tot_d)
-      hipLaunchKernelGGL(loo_total_kernel, dim3((unsigned)nb), dim3(kThreads), 0, h->stream, (const double*)c.kl, c.stride_kl, (int)nfolds, tot_d,
-                         (const int32_t*)info_d, (int)b0);
+    if (tot_d) heldout_totals(h, b0, nb, c.kl, c.stride_kl, nfolds, tot_d, info_d);
     HIP_TRY(h, hipGetLastError());
   }
   return io.finish();
@@ -4219,56 +4229,34 @@ int kfold_multi_batched(blr_handle* h, int memspace, int layout, int64_t B, int6
   a.ldx = ldx; a.strideX = strideX; a.ldm = ldm; a.strideM = strideM; a.ldmn = ldmn; a.D = (int)D; a.N = (int)N; a.S = (int)S;
   k.ldmn = ldmn; k.ldY = ldY; k.strideY = strideY; k.strides = strides; k.noise_kind = noise_kind; k.ld_km = ld_km; k.stride_km = stride_km;
   k.stride_kv = stride_kv; k.ld_kl = ld_kl; k.stride_kl = stride_kl; k.D = (int)D; k.N = (int)N; k.F = (int)F; k.S = (int)S;
-  const size_t x_one = N == 0 ? 0 : (layout == BLR_LAYOUT_COLVECS ? mat_extent(D, N, ldx) : mat_extent(N, D, ldx));
-  const size_t s_one = N == 0 ? 0 : (noise_kind == BLR_NOISE_DIAGONAL ? (size_t)N : 1);
   const T* T_d = nullptr;
   double* tot_d = nullptr;
   int32_t* info_d = nullptr;
   int rc;
-  if ((rc = io.in(X, x_one ? extent(B, strideX, x_one) : 0, &a.X))) return rc;
-  if ((rc = io.in(Y, N ? extent(B, strideY, mat_extent(N, S, ldY)) : 0, &k.Y))) return rc;
-  if ((rc = io.in(s, s_one ? extent(B, strides, s_one) : 0, &k.s))) return rc;
-  if ((rc = io.in(M, extent(B, strideM, mat_extent(D, S, ldm)), &a.M))) return rc;
-  if ((rc = io.in(Tf, extent(B, strideT, mat_extent(D, D, ldt)), &T_d))) return rc;
-  if ((rc = io.out(kf_mean, N ? extent(B, stride_km, mat_extent(N, S, ld_km)) : 0, &k.km))) return rc;
-  if ((rc = io.out(kf_var, N ? extent(B, stride_kv, (size_t)N) : 0, &k.kv))) return rc;
-  if ((rc = io.out(kf_logpdf, N ? extent(B, stride_kl, mat_extent(nfolds, S, ld_kl)) : 0, &k.kl))) return rc;
-  if ((rc = io.out(kf_total, extent(B, stride_kt, (size_t)S), &tot_d))) return rc;
-  if ((rc = io.out(info, (size_t)B, &info_d))) return rc;
+  if ((rc = heldout_stage_in<T>(io, layout, noise_kind, B, D, N, S, {X, ldx, strideX, &a.X}, {Y, ldY, strideY, &k.Y}, {s, 0, strides, &k.s},
+                                {M, ldm, strideM, &a.M}, {Tf, ldt, strideT, &T_d}))) return rc;
+  if ((rc = heldout_stage_out<T>(io, B, N, S, nfolds, {kf_mean, ld_km, stride_km, &k.km}, {kf_var, 0, stride_kv, &k.kv}, {kf_logpdf, ld_kl, stride_kl, &k.kl},
+                                 {kf_total, 0, stride_kt, &tot_d}, info, &info_d))) return rc;
   a.info = info_d; k.info = info_d;
   if ((rc = ensure_stats(h))) return rc;
   k.degenerate = h->stats_dev + 4;
 
-  // status: loo_check_kernel as blr_loo_batched_* launches it
-  const int64_t ychunk = h->cap_chunk(65535);  // grid.x / grid.y <= 65535: the check and the empty totals
+  const int64_t ychunk = heldout_status<T>(h, B, D, N, T_d, ldt, strideT, k.s, strides, noise_kind, info_d);
   h->count_chunks(B, ychunk);
-  for (int64_t b0 = 0; b0 < B; b0 += ychunk)
-    hipLaunchKernelGGL(loo_check_kernel<T>, dim3((unsigned)std::min<int64_t>(ychunk, B - b0)), dim3(kThreads), 0, h->stream, T_d + b0 * strideT,
-                       ldt, strideT, (int)D, k.s + b0 * strides, strides, noise_kind, (int)N, info_d + b0);
   HIP_TRY(h, hipGetLastError());
-  if (N == 0) {  // empty sums, for the regressors whose state passed the check
-    for (int64_t b0 = 0; tot_d && b0 < B; b0 += ychunk)
-      hipLaunchKernelGGL(loo_cols_total_kernel, dim3((unsigned)S, (unsigned)std::min<int64_t>(ychunk, B - b0)), dim3(kThreads), 0, h->stream,
-                         (const double*)nullptr, (int64_t)0, (int64_t)0, 0, tot_d, stride_kt, (const int32_t*)info_d, (int)b0);
-    HIP_TRY(h, hipGetLastError());
-    return io.finish();
-  }
+  if (N == 0) return (rc = heldout_empty_totals(h, B, ychunk, true, S, tot_d, stride_kt, info_d)) ? rc : io.finish();
 
   // Per chunk of regressors: the triangular inverses as MFMA images (marg_image_kernel), Z = X'T^-1 and the S means X'M into workspace
   // (kfold_whiten_cols_kernel), the folds (kfold_cols_kernel), the totals -- four launches whatever B, S and the fold count.  Chunks by
   // the rules of blr_kfold_batched_*: grid.y, the images, the rows of Z and the means (with the log densities when only the totals are
   // wanted) within 256 MiB each, at least one regressor
-  const bool kl_ws = tot_d && !k.kl;  // the totals need the folds' log densities somewhere
-  const bool do_cols = k.km || k.kl || kl_ws;
+  const LogpdfSpill spill(tot_d, k.kl, nfolds, S);
+  const bool do_cols = k.km || k.kl || spill.on;
   const int64_t pack_rows = (kFoldMax / F) * F, npacks = (N + pack_rows - 1) / pack_rows;
   const size_t z_one = cov_z_elems((int)D, (int)N);
   const size_t mean_one = do_cols ? (size_t)S * (size_t)ldmn * sizeof(T) : 0;
-  const size_t row_kl = ((size_t)nfolds * sizeof(double) + 255) & ~(size_t)255;
-  const size_t per = mean_one + (kl_ws ? (size_t)S * row_kl : 0);
-  int64_t chunk = std::min<int64_t>(std::min<int64_t>(B, 65535), MargImages<T>::kMaxChunk);
-  chunk = std::min<int64_t>(chunk, std::max<int64_t>(1, (int64_t)(((size_t)256 << 20) / (z_one * sizeof(T)))));
-  if (per) chunk = std::max<int64_t>(1, std::min<int64_t>(chunk, (int64_t)(kLooWorkspace / per)));
-  chunk = h->cap_chunk(chunk);
+  const size_t per = mean_one + spill.per;
+  const int64_t chunk = whitened_chunk<T>(h, B, true, z_one, per);
   h->count_chunks(B, chunk);
   const size_t lds_w = kfold_whiten_cols_lds_bytes(sizeof(T), (int)D), lds_k = kfold_cols_lds_bytes(sizeof(T), (int)D);
   void (*const whiten)(KfoldWhitenArgs<T>) =
@@ -4279,7 +4267,6 @@ int kfold_multi_batched(blr_handle* h, int memspace, int layout, int64_t B, int6
   if ((rc = h->cov_ws.reserve(h, (size_t)chunk * z_one * sizeof(T)))) return rc;
   if (per && (rc = h->loo_ws.reserve(h, (size_t)chunk * per + 256))) return rc;
   char* const ws = h->loo_ws.p;
-  const int64_t ldkl = (int64_t)(row_kl / sizeof(double));
   const int64_t ntiles = (N + kCovTile - 1) / kCovTile;
   a.Z = reinterpret_cast<T*>(h->cov_ws.p);
   a.mean = do_cols ? reinterpret_cast<T*>(ws) : nullptr;
@@ -4287,20 +4274,13 @@ int kfold_multi_batched(blr_handle* h, int memspace, int layout, int64_t B, int6
   for (int64_t b0 = 0; b0 < B; b0 += chunk) {
     const int64_t nb = std::min<int64_t>(chunk, B - b0);
     a.img = MargImages<T>::launch(h, T_d + b0 * strideT, ldt, strideT, (int)D, (const int32_t*)(info_d + b0), 0, nb);
-    // every workgroup amortises its set-up (the image) over its tiles: about two workgroups per CU in all
-    const int64_t ngroups = std::max<int64_t>(1, std::min<int64_t>(ntiles, (2 * (int64_t)h->cus + nb - 1) / nb));
-    a.ngroups = (int)ngroups; a.reg0 = (int)b0;
-    hipLaunchKernelGGL(whiten, dim3((unsigned)ngroups, (unsigned)nb), dim3(kThreads), lds_w, h->stream, a);
+    a.ngroups = (int)tile_groups(h, ntiles, nb); a.reg0 = (int)b0;
+    hipLaunchKernelGGL(whiten, dim3((unsigned)a.ngroups, (unsigned)nb), dim3(kThreads), lds_w, h->stream, a);
     KfoldColsArgs<T> c = k;
     c.reg0 = (int)b0;
-    if (kl_ws) {  // (indexed by the global regressor)
-      c.ld_kl = ldkl; c.stride_kl = ldkl * S;
-      c.kl = reinterpret_cast<double*>(ws + (size_t)chunk * mean_one) - b0 * c.stride_kl;
-    }
+    if (spill.on) { c.ld_kl = spill.ld; c.stride_kl = spill.ld * S; c.kl = spill.rows(ws + (size_t)chunk * mean_one, b0); }
     hipLaunchKernelGGL(kfold_cols_kernel<T>, dim3((unsigned)npacks, (unsigned)nb), dim3(kThreads), lds_k, h->stream, c);
-    if (tot_d)
-      hipLaunchKernelGGL(loo_cols_total_kernel, dim3((unsigned)S, (unsigned)nb), dim3(kThreads), 0, h->stream, (const double*)c.kl, c.ld_kl,
-                         c.stride_kl, (int)nfolds, tot_d, stride_kt, (const int32_t*)info_d, (int)b0);
+    if (tot_d) heldout_cols_totals(h, b0, nb, S, c.kl, c.ld_kl, c.stride_kl, nfolds, tot_d, stride_kt, info_d);
     HIP_TRY(h, hipGetLastError());
   }
   return io.finish();
@@ -4384,40 +4364,21 @@ int kfold_large_batched(blr_handle* h, int memspace, int layout, int64_t B, int6
   k.stride_km = stride_km; k.stride_kv = stride_kv; k.stride_kl = stride_kl;
   k.layout = layout; k.noise_kind = noise_kind; k.D = (int)D; k.N = (int)N; k.F = (int)std::min<int64_t>(F, std::max<int64_t>(N, 1));
   k.nfolds = (int)nfolds;
-  const size_t x_one = N == 0 ? 0 : (layout == BLR_LAYOUT_COLVECS ? mat_extent(D, N, ldx) : mat_extent(N, D, ldx));
-  const size_t s_one = N == 0 ? 0 : (noise_kind == BLR_NOISE_DIAGONAL ? (size_t)N : 1);
-  const size_t n_out = (size_t)N;
   int rc;
   double* tot_d = nullptr;
   int32_t* info_d = nullptr;
-  if ((rc = io.in(X, x_one ? extent(B, strideX, x_one) : 0, &k.X))) return rc;
-  if ((rc = io.in(y, n_out ? extent(B, stridey, n_out) : 0, &k.y))) return rc;
-  if ((rc = io.in(s, s_one ? extent(B, strides, s_one) : 0, &k.s))) return rc;
-  if ((rc = io.in(mw, extent(B, stridemw, (size_t)D), &k.mw))) return rc;
-  if ((rc = io.in(Tf, extent(B, strideT, mat_extent(D, D, ldt)), &k.Tf))) return rc;
-  if ((rc = io.out(kf_mean, n_out ? extent(B, stride_km, n_out) : 0, &k.km))) return rc;
-  if ((rc = io.out(kf_var, n_out ? extent(B, stride_kv, n_out) : 0, &k.kv))) return rc;
-  if ((rc = io.out(kf_logpdf, n_out ? extent(B, stride_kl, (size_t)nfolds) : 0, &k.kl))) return rc;
-  if ((rc = io.out(kf_total, (size_t)B, &tot_d))) return rc;
-  if ((rc = io.out(info, (size_t)B, &info_d))) return rc;
+  if ((rc = heldout_stage_in<T>(io, layout, noise_kind, B, D, N, 1, {X, ldx, strideX, &k.X}, {y, N, stridey, &k.y}, {s, 0, strides, &k.s},
+                                {mw, D, stridemw, &k.mw}, {Tf, ldt, strideT, &k.Tf}))) return rc;
+  if ((rc = heldout_stage_out<T>(io, B, N, 1, nfolds, {kf_mean, N, stride_km, &k.km}, {kf_var, 0, stride_kv, &k.kv}, {kf_logpdf, nfolds, stride_kl, &k.kl},
+                                 {kf_total, 0, 1, &tot_d}, info, &info_d))) return rc;
   k.info = info_d;
   if ((rc = ensure_stats(h))) return rc;
   k.degenerate = h->stats_dev + 4;
 
-  // status: loo_check_kernel as blr_loo_batched_* launches it
-  const int64_t ychunk = h->cap_chunk(65535);  // grid.x <= 65535 here: the check and the empty totals
+  const int64_t ychunk = heldout_status<T>(h, B, D, N, k.Tf, ldt, strideT, k.s, strides, noise_kind, info_d);
   h->count_chunks(B, ychunk);
-  for (int64_t b0 = 0; b0 < B; b0 += ychunk)
-    hipLaunchKernelGGL(loo_check_kernel<T>, dim3((unsigned)std::min<int64_t>(ychunk, B - b0)), dim3(kThreads), 0, h->stream,
-                       k.Tf + b0 * strideT, ldt, strideT, (int)D, k.s + b0 * strides, strides, noise_kind, (int)N, info_d + b0);
   HIP_TRY(h, hipGetLastError());
-  if (N == 0) {  // an empty sum, for the regressors whose state passed the check
-    for (int64_t b0 = 0; tot_d && b0 < B; b0 += ychunk)
-      hipLaunchKernelGGL(loo_total_kernel, dim3((unsigned)std::min<int64_t>(ychunk, B - b0)), dim3(kThreads), 0, h->stream,
-                         (const double*)nullptr, (int64_t)0, 0, tot_d, (const int32_t*)info_d, (int)b0);
-    HIP_TRY(h, hipGetLastError());
-    return io.finish();
-  }
+  if (N == 0) return (rc = heldout_empty_totals(h, B, ychunk, false, 1, tot_d, 1, info_d)) ? rc : io.finish();
 
   // Per chunk of regressors: the state matrix, the folds' statistics (+ reduce), their factors, the images of the factors, the
   // predictions, the totals -- the same launches whatever B and the fold count are.  Chunks: grid.y / grid.z <= 65535; the statistics,
@@ -4428,7 +4389,7 @@ int kfold_large_batched(blr_handle* h, int memspace, int layout, int64_t B, int6
   const int NB = (int)(D + 15) / 16, DP = 16 * NB;
   const size_t packed = (size_t)DP * (DP + 1) / 2, SZ = packed + DP;
   const size_t stats_one = (size_t)nfolds * S * SZ * sizeof(double), U_one = (size_t)nfolds * D * D * sizeof(T);
-  const bool kl_ws = tot_d && !k.kl;  // the totals need the folds' log densities somewhere
+  const LogpdfSpill spill(tot_d, k.kl, nfolds, 1, sizeof(double));  // (rows of nfolds doubles, not padded, in cov_ws)
   const bool predict = k.km || k.kv;
   const size_t bound = (size_t)256 << 20;
   int64_t chunk = std::min<int64_t>(std::min<int64_t>(B, 65535), MargImages<T>::kMaxChunk / nfolds);
@@ -4440,7 +4401,7 @@ int kfold_large_batched(blr_handle* h, int memspace, int layout, int64_t B, int6
   const size_t nrf = (size_t)chunk * nfolds;
   const size_t o_st = carve((size_t)chunk * stats_one), o_U = carve((size_t)chunk * U_one), o_A = carve((size_t)chunk * packed * sizeof(double));
   const size_t o_ld = carve((size_t)chunk * sizeof(double)), o_sc = carve(nrf * S * 2 * sizeof(double));
-  const size_t o_mw = carve(nrf * D * sizeof(T)), o_fi = carve(nrf * sizeof(int32_t)), o_kl = carve(kl_ws ? nrf * sizeof(double) : 0);
+  const size_t o_mw = carve(nrf * D * sizeof(T)), o_fi = carve(nrf * sizeof(int32_t)), o_kl = carve((size_t)chunk * spill.per);
   if ((rc = h->cov_ws.reserve(h, carve.off))) return rc;
   char* const ws = h->cov_ws.p;
   k.stats = reinterpret_cast<double*>(ws + o_st); k.U = reinterpret_cast<T*>(ws + o_U); k.A = reinterpret_cast<double*>(ws + o_A);
@@ -4458,7 +4419,7 @@ int kfold_large_batched(blr_handle* h, int memspace, int layout, int64_t B, int6
     const int64_t nb = std::min<int64_t>(chunk, B - b0);
     KflArgs<T> c = k;
     c.reg0 = (int)b0;
-    if (kl_ws) { c.kl = reinterpret_cast<double*>(ws + o_kl) - b0 * nfolds; c.stride_kl = nfolds; }  // (indexed by the global regressor)
+    if (spill.on) { c.kl = spill.rows(ws + o_kl, b0); c.stride_kl = spill.ld; }
     hipLaunchKernelGGL(state, dim3((unsigned)nb), dim3(kThreads), lds_s, h->stream, c);
     HIP_TRY(h, hipGetLastError());
     switch (NB) {
@@ -4474,14 +4435,12 @@ int kfold_large_batched(blr_handle* h, int memspace, int layout, int64_t B, int6
     if (rc) return rc;
     if (predict) {
       // the factors of the chunk's folds as images (a fold without a factor is skipped by its status word), then the folds' rows
-      // against them; every workgroup amortises its set-up (the image) over its tiles: about two workgroups per CU in all
+      // against them
       c.img = MargImages<T>::launch(h, c.U, D, D * D, (int)D, (const int32_t*)c.finfo, 0, nb * nfolds);
-      c.ngroups = (int)std::max<int64_t>(1, std::min<int64_t>(ntiles, (2 * (int64_t)h->cus + nb * nfolds - 1) / (nb * nfolds)));
+      c.ngroups = (int)tile_groups(h, ntiles, nb * nfolds);
       hipLaunchKernelGGL(pred, dim3((unsigned)c.ngroups, (unsigned)nfolds, (unsigned)nb), dim3(kThreads), lds_p, h->stream, c);
     }
-    if (tot_d)
-      hipLaunchKernelGGL(loo_total_kernel, dim3((unsigned)nb), dim3(kThreads), 0, h->stream, (const double*)c.kl, c.stride_kl, (int)nfolds,
-                         tot_d, (const int32_t*)info_d, (int)b0);
+    if (tot_d) heldout_totals(h, b0, nb, c.kl, c.stride_kl, nfolds, tot_d, info_d);
     HIP_TRY(h, hipGetLastError());
   }
   return io.finish();

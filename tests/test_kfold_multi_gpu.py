@@ -255,6 +255,22 @@ def test_columns_match_the_single_column_call_and_loo_multi(B, h):
     np.testing.assert_allclose(tot1[0], lt, rtol=1e-9)
 
 
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+def test_variances_are_the_single_column_calls_bit_for_bit(B, h, dtype):
+    """kf_var depends on the fold factor alone: kfold_cols_kernel and kfold_kernel form it by the same steps from the same rows of Z"""
+    D, N, F, S = 20, 70, 5, 3
+    A = B._abi
+    X, Y, s, M, T = _problems(1, D, N, S, dtype=dtype)
+    _, v, _, _, info = _run(B, h, X, Y, s, M, T, F)
+    assert not info.any() and not np.isnan(v).any()
+    Xf, Tf = np.ascontiguousarray(X[0].reshape(-1, order="F")), np.ascontiguousarray(T[0].reshape(-1, order="F"))
+    kv, ki = np.empty(N, dtype=dtype), np.zeros(1, dtype=np.int32)
+    h.kfold(dtype, A.MEM_HOST, A.LAYOUT_COLVECS, 1, D, N, F, Xf, D, 0, np.ascontiguousarray(Y[0][:, 0]), 0, A.NOISE_DIAGONAL, s[0], 0,
+            np.ascontiguousarray(M[0][:, 0]), 0, Tf, D, 0, None, N, kv, N, None, -(-N // F), None, ki)
+    assert ki[0] == 0
+    assert np.array_equal(v[0], kv)
+
+
 # ---- 4. bit promises -----------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
 def test_bits_do_not_depend_on_batch_chunks_memspace_outputs_or_the_other_columns(B, h, dtype):
