@@ -268,7 +268,9 @@ class Handle:
 
     def get_stat(self, key):
         """Counter of this handle: "i8_regressors", "i8_handed_back", "planes_redone", "loo_degenerate", "kfold_degenerate" (folds
-        blr_kfold_batched_* / blr_kfold_multi_batched_* / blr_kfold_large_batched_* gave NaN), "workspace_bytes", "last_chunks" (chunks / slices of regressors of the most recent call: option MAX_CHUNK caps their size) (blr_get_stat)."""
+        blr_kfold_batched_* / blr_kfold_multi_batched_* / blr_kfold_large_batched_* gave NaN), "workspace_bytes", "last_chunks" (chunks / slices of regressors of the most recent call: option MAX_CHUNK caps their size), and the variance route of the most recent
+        marginals_batched call: "marg_block_rt" (tile height 32 / 16 of marg_blocksub_kernel, 0 = the call ran elsewhere), "marg_block_walk"
+        (tiles its busiest workgroup walked), "marg_block_renumbered" (1 = a launch renumbered its workgroups per XCD) (blr_get_stat)."""
         v = _i64()
         self.check(self.lib.blr_get_stat(self._h, str(key).encode(), C.byref(v)))
         return int(v.value)

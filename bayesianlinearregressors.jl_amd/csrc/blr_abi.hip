@@ -950,8 +950,8 @@ int prior_factor(blr_handle* h, int64_t B, int64_t D, int prior_kind, const T* L
 
 // ---- large-D marginals with a factor or a dense prior: block forward substitution on LDS-resident tiles of 32 inputs ---------------
 // (marg_blocksub_kernel: X is read once, nothing but the outputs is written).  A whole batch per launch (blockIdx.y = regressor;
-// a dense prior's blocked Cholesky takes the batch through chol_large's groups).  Needs the tile in LDS (D <= 1152 in fp32, 576
-// in fp64) and 16-byte loads along d from X and U.  Returns 1 when the call does not qualify (the caller takes the tall-matrix route).
+// a dense prior's blocked Cholesky takes the batch through chol_large's groups).  Needs the tile in LDS (D <= 1152 in fp32, 512
+// in fp64: the tile is DP = 128 ceil(D / 128) wide, and DP = 640 takes 172 032 bytes in fp64) and 16-byte loads along d from X and U.  Returns 1 when the call does not qualify (the caller takes the tall-matrix route).
 template <typename T>
 int marginals_large_group(blr_handle* h, int layout, int64_t B, int64_t D, int64_t N, const T* X, int64_t ldx, int64_t strideX,
                           int noise_kind, const T* s, int64_t strides, int prior_kind, const T* mw, int64_t stridemw, const T* Lw,
@@ -1025,6 +1025,7 @@ int marginals_large_group(blr_handle* h, int layout, int64_t B, int64_t D, int64
         const int64_t gx = std::min<int64_t>(ntiles, std::max<int64_t>(1, (2 * h->cus + nb - 1) / nb));  // two workgroups per CU
         hipLaunchKernelGGL((marg_blocksub_kernel<T, 16>), dim3((unsigned)gx, (unsigned)nb), dim3(MB16::THREADS), (size_t)MB16::lds_bytes(DP),
                            h->stream, m);
+        h->marg_block.launch(MB16::RT, ntiles, gx, nb);
       }
     }
     if (!small_tiles) {
@@ -1032,6 +1033,7 @@ int marginals_large_group(blr_handle* h, int layout, int64_t B, int64_t D, int64
       const int64_t gx = std::min<int64_t>(ntiles, std::max<int64_t>(1, (h->cus + nb - 1) / nb));  // one workgroup per CU
       hipLaunchKernelGGL((marg_blocksub_kernel<T, 32>), dim3((unsigned)gx, (unsigned)nb), dim3(MB::THREADS), (size_t)MB::lds_bytes(DP),
                          h->stream, m);
+      h->marg_block.launch(MB::RT, ntiles, gx, nb);
     }
   }
   HIP_TRY(h, hipGetLastError());
@@ -1224,6 +1226,7 @@ int marginals_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_
                       int64_t stridevar, int32_t* info) {
   if (!h) return -1;
   h->last_chunks = 1;  // (a route with a chunk loop counts its own)
+  h->marg_block = {};  // (set next to marg_blocksub_kernel's launches)
   h->err.clear();
   if (memspace != BLR_MEM_HOST && memspace != BLR_MEM_DEVICE) return bad_arg(h, 2, "memspace");
   if (layout != BLR_LAYOUT_COLVECS && layout != BLR_LAYOUT_ROWVECS) return bad_arg(h, 3, "unknown layout (reference :26-31)");
@@ -4708,6 +4711,10 @@ int blr_get_stat(blr_handle* h, const char* key, int64_t* value) {
   if (!value) return bad_arg(h, 3, "value is NULL");
   if (!strcmp(key, "i8_regressors")) { *value = (int64_t)h->i8_attempted; return 0; }
   if (!strcmp(key, "last_chunks")) { *value = h->last_chunks; return 0; }  // chunks / slices of regressors of the most recent call
+  // the variance route of the most recent blr_marginals_batched_* call (host-side, set next to marg_blocksub_kernel's launches)
+  if (!strcmp(key, "marg_block_rt")) { *value = h->marg_block.rt; return 0; }
+  if (!strcmp(key, "marg_block_walk")) { *value = h->marg_block.walk; return 0; }
+  if (!strcmp(key, "marg_block_renumbered")) { *value = h->marg_block.renumbered; return 0; }
   if (!strcmp(key, "i8_handed_back")) {
     unsigned long long v = 0;
     if (h->stats_dev) {

@@ -215,6 +215,17 @@ struct blr_handle {
   int64_t last_chunks = 0;               // chunks / slices of regressors the most recent call launched (blr_get_stat "last_chunks"): 1 at
                                          // every entry, then whatever the call's chunk loop counts
   void count_chunks(int64_t B, int64_t chunk) { last_chunks = (B + chunk - 1) / chunk; }
+  // The variance route of the most recent blr_marginals_batched_* call (blr_get_stat "marg_block_rt" / "marg_block_walk" /
+  // "marg_block_renumbered"): tile height of marg_blocksub_kernel (0: the call ran elsewhere), trips of its busiest workgroup
+  // (the largest ceil(ntiles / grid.x) over the call's launches), and whether any launch met the kernel's renumbering condition
+  struct MargBlockRoute {
+    int rt = 0; int64_t walk = 0; int renumbered = 0;
+    void launch(int tile_rows, int64_t ntiles, int64_t gx, int nb) {
+      rt = tile_rows;
+      walk = std::max<int64_t>(walk, (ntiles + gx - 1) / gx);
+      if (nb > 1 && (gx * nb) % 8 == 0) renumbered = 1;
+    }
+  } marg_block;
   int64_t route_i8_B = 0;                // > 0: that dispatch took the int8 route with this many regressors (blr_last_route looks at its hand-backs)
   std::string route_buf;
   unsigned* ticket = nullptr;     // [0], [2], [3]: wavefront solve (tickets, done, launch count); [16 + 128 bank + g]: arrivals of panel_chain_kernel

@@ -102,6 +102,12 @@ const char* blr_last_route(blr_handle* h);
  * A - G_f did (reading it synchronises the handle's stream); "last_chunks" = chunks / slices of regressors the handle's most
  * recent call launched (NOT cumulative: every entry point starts it at 1; a batch beyond grid.y = 65535, a workspace or image bound, or
  * option MAX_CHUNK, goes in several); "workspace_bytes" = device scratch the handle holds now.
+ * The variance route of the handle's most recent blr_marginals_batched_* call (NOT cumulative; host-side integers): "marg_block_rt"
+ * = 32 or 16, the tile height of marg_blocksub_kernel (block forward substitution on LDS-resident tiles of inputs: D > 128, 16 | D,
+ * aligned ColVecs, factor or dense prior, D <= 1152 in fp32 / 512 in fp64), or 0 when the call ran anywhere else (diagonal prior,
+ * D <= 128, the tall-matrix sweep, mean only); "marg_block_walk" = tiles the busiest workgroup of that kernel walked (the largest
+ * ceil(tiles / grid.x) over the call's launches; 0 with "marg_block_rt" = 0); "marg_block_renumbered" = 1 if any of those launches
+ * renumbered its workgroups so that an XCD gets whole regressors (more than one regressor and a grid that is a multiple of 8).
  * -> 0, -2 unknown key, -3 NULL value. */
 int blr_get_stat(blr_handle* h, const char* key, int64_t* value);
 int blr_reset_stats(blr_handle* h);

@@ -885,7 +885,8 @@ def test_padded_leading_dimensions_and_shared_inputs(B):
                                        (np.float32, 1152, 31), (np.float32, 256, 8200)])
 def test_large_d_marginals(B, dtype, D, N):
     # reference :33, :40-43 at D > 128: GEMV stream for the mean; var by block forward substitution on LDS-resident tiles of inputs
-    # (16 | D, tile fits LDS: aligned ColVecs) or by the tall TRSM through the panel machinery of the factorisation (everything else)
+    # (16 | D, tile fits LDS -- D <= 1152 in fp32, 512 in fp64: aligned ColVecs) or by the tall TRSM through the panel machinery of the
+    # factorisation (everything else, the (float64, 576, 95) row among them; tests/test_marg_block_gpu.py asserts which route ran)
     rng = _rng(9000 + D)
     X = rng.standard_normal((D, N)).astype(dtype)
     mw = rng.standard_normal(D).astype(dtype)
