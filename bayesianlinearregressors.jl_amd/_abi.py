@@ -81,6 +81,10 @@ for _suf in ("f64", "f32"):
     _SIGS[f"blr_posterior_ragged_{_suf}"] = (
         [_H, _int, _int, _i64, _i64, _vp, _vp, _i64, _vp, _int, _vp, _i64, _int, _vp, _i64, _vp, _i64, _i64,
          _vp, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp], _int)
+    _SIGS[f"blr_marginals_ragged_{_suf}"] = (
+        [_H, _int, _int, _i64, _i64, _vp, _vp, _i64, _int, _vp, _i64, _int, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp], _int)
+    _SIGS[f"blr_loo_ragged_{_suf}"] = (
+        [_H, _int, _int, _i64, _i64, _vp, _vp, _i64, _vp, _int, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp], _int)
     _SIGS[f"blr_posterior_multi_batched_{_suf}"] = (
         [_H, _int, _int, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _int, _vp, _i64, _int, _vp, _i64, _vp, _i64, _i64,
          _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _vp], _int)
@@ -259,7 +263,8 @@ class Handle:
 
     def set_option(self, key, value=None):
         """Run-time switch of this handle (include/blr_mi355x.h blr_set_option); value None = the built-in default.
-        MAX_CHUNK = 1..65535 (tests) caps the regressors per chunk / slice of every batched entry point."""
+        MAX_CHUNK = 1..65535 (tests) caps the regressors per chunk / slice of every batched entry point; RAGGED_ITEM = 1..2^30 (tests) forces
+        the observations per work item of marginals_ragged / loo_ragged (rounded up to 64)."""
         self.check(self.lib.blr_set_option(self._h, str(key).encode(), None if value is None else str(value).encode()))
 
     def last_route(self):
@@ -331,6 +336,29 @@ class Handle:
         return self.check(fn(self._h, memspace, layout, B, D, _ptr(offsets), _ptr(X), ldx, _ptr(y), noise_kind, _ptr(s), strides,
                              prior_kind, _ptr(mw), stridemw, _ptr(Lw), ldl, strideLw, _ptr(mw_post), stride_mwpost, _ptr(T_post),
                              ldt, strideT, _ptr(Lw_post), ldlp, strideLp, _ptr(logpdf), _ptr(info)))
+
+    def marginals_ragged(self, dtype, memspace, layout, B, D, offsets, X, ldx, noise_kind, s, strides, prior_kind, mw, stridemw,
+                         Lw, ldl, strideLw, mean, var, info):
+        """Marginals of B regressors with unequal observation counts, inputs and outputs packed side by side; include/blr_mi355x.h
+        blr_marginals_ragged_*.  offsets: B + 1 non-decreasing entries, always on the host (any integer sequence)."""
+        fn = getattr(self.lib, f"blr_marginals_ragged_{suffix(dtype)}")
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        if offsets.shape != (B + 1,):
+            raise ValueError(f"offsets must have B + 1 = {B + 1} entries, got shape {offsets.shape}")
+        return self.check(fn(self._h, memspace, layout, B, D, _ptr(offsets), _ptr(X), ldx, noise_kind, _ptr(s), strides, prior_kind,
+                             _ptr(mw), stridemw, _ptr(Lw), ldl, strideLw, _ptr(mean), _ptr(var), _ptr(info)))
+
+    def loo_ragged(self, dtype, memspace, layout, B, D, offsets, X, ldx, y, noise_kind, s, strides, mw, stridemw, T, ldt, strideT,
+                   loo_mean, loo_var, loo_logpdf, loo_total, info):
+        """Exact leave-one-out predictives of B states with unequal observation counts, packed as `posterior_ragged` packs them;
+        include/blr_mi355x.h blr_loo_ragged_*."""
+        fn = getattr(self.lib, f"blr_loo_ragged_{suffix(dtype)}")
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        if offsets.shape != (B + 1,):
+            raise ValueError(f"offsets must have B + 1 = {B + 1} entries, got shape {offsets.shape}")
+        return self.check(fn(self._h, memspace, layout, B, D, _ptr(offsets), _ptr(X), ldx, _ptr(y), noise_kind, _ptr(s), strides,
+                             _ptr(mw), stridemw, _ptr(T), ldt, strideT, _ptr(loo_mean), _ptr(loo_var), _ptr(loo_logpdf),
+                             _ptr(loo_total), _ptr(info)))
 
     def posterior_multi_batched(self, dtype, memspace, layout, B, D, N, S, X, ldx, strideX, Y, ldY, strideY, noise_kind, s, strides,
                                 prior_kind, mw, stridemw, Lw, ldl, strideLw, mw_post, ldmp, stride_mwpost, T_post, ldt, strideT,

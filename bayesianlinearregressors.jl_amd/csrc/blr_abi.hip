@@ -32,6 +32,7 @@
 #include "blr_rand_batched.hpp"
 #include "blr_grid.hpp"
 #include "blr_ragged.hpp"
+#include "blr_marg_ragged.hpp"
 #include "blr_multi.hpp"
 #include "blr_marg_multi.hpp"
 #include "blr_cov_batched.hpp"
@@ -3528,6 +3529,267 @@ int posterior_ragged(blr_handle* h, int memspace, int layout, int64_t B, int64_t
   return io.finish();
 }
 
+// ---- ragged marginals and leave-one-out (blr_marg_ragged.hpp, blr_ragged_items.hpp) ---------------------------------
+// offsets: what blr_posterior_ragged_* asks of it
+inline int ragged_offsets_check(blr_handle* h, int64_t B, const int64_t* offsets) {
+  if (B > 0 && !offsets) return bad_arg(h, 6, "offsets is NULL (a host array of B + 1 entries)");
+  if (B > 0 && offsets[0] < 0) return bad_arg(h, 6, "offsets[0] < 0");
+  for (int64_t b = 0; b < B; ++b) {
+    if (offsets[b + 1] < offsets[b]) return bad_arg(h, 6, "offsets must be non-decreasing");
+    if (offsets[b + 1] - offsets[b] > (1 << 30)) return bad_arg(h, 6, "a regressor with more than 2^30 observations");
+  }
+  return 0;
+}
+
+// offsets and the plan's items go to the handle's metadata buffer (K14's: the two entry points never share a call).  The copy is
+// ordered behind the work in flight and the stream is drained: the host image belongs to the handle and the next call rewrites it.
+inline int ragged_items_upload(blr_handle* h, const int64_t* offsets, int64_t B, const RaggedPlan& p, const int64_t** off_dev,
+                               const RaggedItem** items_dev) {
+  const size_t items_at = (size_t)(B + 1) * sizeof(int64_t), bytes = items_at + p.items.size() * sizeof(RaggedItem);
+  h->ragged_host.resize((bytes + 7) / 8);
+  std::memcpy(h->ragged_host.data(), offsets, items_at);
+  if (!p.items.empty()) std::memcpy(reinterpret_cast<char*>(h->ragged_host.data()) + items_at, p.items.data(), p.items.size() * sizeof(RaggedItem));
+  if (const int rc = h->ragged_meta.reserve(h, bytes, (size_t)1 << 16)) return rc;
+  HIP_TRY(h, hipMemcpyAsync(h->ragged_meta.p, h->ragged_host.data(), bytes, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  *off_dev = reinterpret_cast<const int64_t*>(h->ragged_meta.p);
+  *items_dev = reinterpret_cast<const RaggedItem*>(h->ragged_meta.p + items_at);
+  return 0;
+}
+
+// The product stream takes D = 128 with a factor when the variance is wanted: RowVecs, or ColVecs whose X and ldx are multiples of 16
+// bytes (every regressor's slice then is).  Asked of the caller's pointer as well as of the staged one: a host-memspace call takes the
+// route the same call takes in device memspace, so the two give the same bits
+template <typename T>
+bool marg_ragged_gemm_takes(const blr_handle* h, int layout, int64_t D, const T* X, int64_t ldx) {
+  return !h->opt.no_marg_gemm && D == kPB && (layout == BLR_LAYOUT_ROWVECS || ((ldx % Mfma<T>::VEC) == 0 && ((uintptr_t)X % 16) == 0));
+}
+
+// One workgroup per item, chunk by chunk (a.offsets / a.items: the uploaded tables; everything indexes the global regressor)
+template <typename T, bool LOO>
+int marg_ragged_launch(blr_handle* h, MargRaggedArgs<T> a, const RaggedPlan& p, bool gemm) {
+  using G = MargGemmCfg<T>;
+  using RC = MargRaggedRowsCfg<T>;
+  const bool rowv = a.layout == BLR_LAYOUT_ROWVECS;
+  void (*const gk)(MargRaggedArgs<T>, const T*) = rowv ? marg_ragged_gemm_kernel<T, true, LOO> : marg_ragged_gemm_kernel<T, false, LOO>;
+  void (*const rk)(MargRaggedArgs<T>) = marg_ragged_rows_kernel<T, LOO>;
+  const bool rows_factor = (LOO || a.var) && a.prior_kind == BLR_PRIOR_UPPER_FACTOR;
+  int rc;
+  const bool images = gemm && (LOO || a.var);
+  if (gemm) {
+    int64_t nb_max = 1;
+    for (const RaggedChunk& c : p.chunks) nb_max = std::max(nb_max, c.nb);
+    if (images && (rc = MargImages<T>::reserve(h, nb_max))) return rc;
+    if ((rc = set_lds_once(h, gk, (size_t)G::LDS_BYTES))) return rc;
+  } else if ((rc = set_lds_once(h, rk, (size_t)RC::LDS_FACTOR))) {
+    return rc;
+  }
+  const RaggedItem* const items = a.items;
+  for (const RaggedChunk& c : p.chunks) {
+    if (c.nitems == 0) continue;
+    a.items = items + c.item0;
+    if (gemm) {
+      T* const img = images ? MargImages<T>::launch(h, a.U, a.ldu, a.strideU, a.D, a.info, c.b0, c.nb) : (T*)nullptr;
+      hipLaunchKernelGGL(gk, dim3((unsigned)c.nitems), dim3(kThreads), G::LDS_BYTES, h->stream, a, (const T*)img);
+    } else {
+      hipLaunchKernelGGL(rk, dim3((unsigned)c.nitems), dim3(kThreads), rows_factor ? RC::LDS_FACTOR : RC::LDS_STREAM, h->stream, a);
+    }
+    HIP_TRY(h, hipGetLastError());
+  }
+  h->last_chunks = std::max<int64_t>(1, p.last_chunks);
+  h->route = gemm ? "marg_ragged_gemm_kernel" : "marg_ragged_rows_kernel";
+  h->route_i8_B = 0;
+  return 0;
+}
+
+template <typename T>
+int marginals_ragged(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, const int64_t* offsets, const T* X, int64_t ldx,
+                     int noise_kind, const T* s, int64_t strides, int prior_kind, const T* mw, int64_t stridemw, const T* Lw, int64_t ldl,
+                     int64_t strideLw, T* mean, T* var, int32_t* info) {
+  // (the argument checks come before the handle's: they need no device)
+  if (h) h->err.clear();
+  if (memspace != BLR_MEM_HOST && memspace != BLR_MEM_DEVICE) return bad_arg(h, 2, "memspace");
+  if (layout != BLR_LAYOUT_COLVECS && layout != BLR_LAYOUT_ROWVECS) return bad_arg(h, 3, "unknown layout (reference :26-31)");
+  if (B < 0 || B > (1 << 30)) return bad_arg(h, 4, "B out of range (0..2^30)");
+  if (D < 1 || D > kMaxLargeD) return bad_arg(h, 5, "D out of range (1..8192)");
+  if (const int rc = ragged_offsets_check(h, B, offsets)) return rc;
+  const int64_t total = B > 0 ? offsets[B] : 0;  // columns of the packed arrays
+  const bool any = B > 0 && offsets[B] > offsets[0];
+  if (any && !X) return bad_arg(h, 7, "X is NULL");
+  if (layout == BLR_LAYOUT_COLVECS ? ldx < D : ldx < std::max<int64_t>(total, 1)) return bad_arg(h, 8, "ldx too small");
+  if (noise_kind != BLR_NOISE_ISOTROPIC && noise_kind != BLR_NOISE_DIAGONAL)
+    return bad_arg(h, 9, "noise_kind (isotropic or diagonal; dense Sigma_y is not supported for unequal counts)");
+  if (var && any && !s) return bad_arg(h, 10, "s is NULL");
+  if (strides < 0) return bad_arg(h, 11, "strides < 0");
+  if (prior_kind != BLR_PRIOR_DENSE && prior_kind != BLR_PRIOR_UPPER_FACTOR && prior_kind != BLR_PRIOR_DIAGONAL)
+    return bad_arg(h, 12, "prior_kind");
+  if (!mw) return bad_arg(h, 13, "mw is NULL");
+  if (stridemw < 0) return bad_arg(h, 14, "stridemw < 0");
+  if (var && !Lw) return bad_arg(h, 15, "Lw is NULL");
+  if (prior_kind != BLR_PRIOR_DIAGONAL && ldl < D) return bad_arg(h, 16, "ldl < D");
+  if (strideLw < 0) return bad_arg(h, 17, "strideLw < 0");
+  if (B > 0 && !info) return bad_arg(h, 20, "info is NULL");
+  if (B == 0) return 0;
+  if (!h) return -1;
+  h->last_chunks = 1;  // (a route with a chunk loop counts its own)
+  HIP_TRY(h, hipSetDevice(h->device));
+  const bool diag = noise_kind == BLR_NOISE_DIAGONAL;
+  const bool colv = layout == BLR_LAYOUT_COLVECS;
+
+  CallIO io(h, memspace);
+  MargRaggedArgs<T> a{};
+  a.ldx = ldx; a.strides = strides; a.stridemw = stridemw; a.layout = layout; a.noise_kind = noise_kind; a.D = (int)D;
+  const size_t x_all = !any ? 0 : (colv ? mat_extent(D, total, ldx) : mat_extent(total, D, ldx));
+  const size_t lw_one = prior_kind == BLR_PRIOR_DIAGONAL ? (size_t)D : mat_extent(D, D, ldl);
+  const T* Lw_dev = nullptr;
+  int32_t* info_dev = nullptr;
+  int rc;
+  if ((rc = io.in(X, x_all, &a.X))) return rc;
+  if ((rc = io.in(var ? s : (const T*)nullptr, diag ? (any ? (size_t)total : 0) : extent(B, strides, 1), &a.s))) return rc;
+  if ((rc = io.in(mw, extent(B, stridemw, (size_t)D), &a.mw))) return rc;
+  if ((rc = io.in(var ? Lw : (const T*)nullptr, extent(B, strideLw, lw_one), &Lw_dev))) return rc;
+  if ((rc = io.out(mean, any ? (size_t)total : 0, &a.mean))) return rc;
+  if ((rc = io.out(var, any ? (size_t)total : 0, &a.var))) return rc;
+  if ((rc = io.out(info, (size_t)B, &info_dev))) return rc;
+  if (!any || (!mean && !var)) {  // nothing per observation to write: the status of a call without a factorisation
+    HIP_TRY(h, hipMemsetAsync(info_dev, 0, (size_t)B * sizeof(int32_t), h->stream));
+    return io.finish();
+  }
+  if (D > kMaxSmallD) {  // correct, not fast: one regressor after the other through blr_marginals_batched_*; the call synchronises
+    HIP_TRY(h, hipMemsetAsync(info_dev, 0, (size_t)B * sizeof(int32_t), h->stream));
+    {
+      const AsyncScope drain(h, false);
+      for (int64_t b = 0; b < B && rc == 0; ++b) {
+        const int64_t o = offsets[b], n = offsets[b + 1] - o;
+        if (n == 0) continue;
+        rc = marginals_batched<T>(h, BLR_MEM_DEVICE, layout, 1, D, n, a.X + (colv ? o * ldx : o), ldx, 0, noise_kind,
+                                  a.s ? (diag ? a.s + o : a.s + b * strides) : (const T*)nullptr, 0, prior_kind, a.mw + b * stridemw, 0,
+                                  Lw_dev ? Lw_dev + b * strideLw : (const T*)nullptr, ldl, 0, a.mean ? a.mean + o : (T*)nullptr, 0,
+                                  a.var ? a.var + o : (T*)nullptr, 0, info_dev + b);
+      }
+    }
+    if (rc) return rc;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return io.finish();
+  }
+  RaggedPlan plan;
+  plan_ragged(offsets, B, h->cus, (int)sizeof(T), h->opt, plan);
+  if ((rc = ragged_items_upload(h, offsets, B, plan, &a.offsets, &a.items))) return rc;
+  // a dense prior is factorised once per regressor; its status is the call's
+  int32_t* chol_info = nullptr;
+  int kind = prior_kind;
+  if (var) {
+    if ((rc = prior_factor<T>(h, B, D, prior_kind, Lw_dev, ldl, strideLw, &a.U, &a.ldu, &a.strideU, &kind, &chol_info))) return rc;
+  } else {
+    a.U = Lw_dev; a.ldu = ldl; a.strideU = strideLw;
+  }
+  a.prior_kind = kind;
+  a.info = chol_info;
+  if (chol_info) HIP_TRY(h, hipMemcpyAsync(info_dev, chol_info, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, h->stream));
+  else HIP_TRY(h, hipMemsetAsync(info_dev, 0, (size_t)B * sizeof(int32_t), h->stream));
+  // the route follows from the shape and the prior kind alone -- not from the outputs requested: a mean has the same bits alone
+  // and next to its variance (the stream kernel then runs without image and product)
+  const bool gemm = prior_kind != BLR_PRIOR_DIAGONAL && marg_ragged_gemm_takes<T>(h, layout, D, X, ldx) && marg_ragged_gemm_takes<T>(h, layout, D, a.X, ldx);
+  if ((rc = marg_ragged_launch<T, false>(h, a, plan, gemm))) return rc;
+  return io.finish();
+}
+
+template <typename T>
+int loo_ragged(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, const int64_t* offsets, const T* X, int64_t ldx, const T* y,
+               int noise_kind, const T* s, int64_t strides, const T* mw, int64_t stridemw, const T* Tf, int64_t ldt, int64_t strideT,
+               T* loo_mean, T* loo_var, double* loo_logpdf, double* loo_total, int32_t* info) {
+  // (the argument checks come before the handle's: they need no device)
+  if (h) h->err.clear();
+  if (memspace != BLR_MEM_HOST && memspace != BLR_MEM_DEVICE) return bad_arg(h, 2, "memspace");
+  if (layout != BLR_LAYOUT_COLVECS && layout != BLR_LAYOUT_ROWVECS) return bad_arg(h, 3, "unknown layout (reference :26-31)");
+  if (B < 0 || B > (1 << 30)) return bad_arg(h, 4, "B out of range (0..2^30)");
+  if (D < 1 || D > kMaxLargeD) return bad_arg(h, 5, "D out of range (1..8192)");
+  if (const int rc = ragged_offsets_check(h, B, offsets)) return rc;
+  const int64_t total = B > 0 ? offsets[B] : 0;
+  const bool any = B > 0 && offsets[B] > offsets[0];
+  if (any && !X) return bad_arg(h, 7, "X is NULL");
+  if (layout == BLR_LAYOUT_COLVECS ? ldx < D : ldx < std::max<int64_t>(total, 1)) return bad_arg(h, 8, "ldx too small");
+  if (any && !y) return bad_arg(h, 9, "y is NULL (reference :74 length check)");
+  if (noise_kind != BLR_NOISE_ISOTROPIC && noise_kind != BLR_NOISE_DIAGONAL)
+    return bad_arg(h, 10, "noise_kind (dense noise has no single-observation LOO: that is a block LOO)");
+  if (any && !s) return bad_arg(h, 11, "s is NULL");
+  if (strides < 0) return bad_arg(h, 12, "strides < 0");
+  if (!mw) return bad_arg(h, 13, "mw is NULL");
+  if (stridemw < 0) return bad_arg(h, 14, "stridemw < 0");
+  if (!Tf) return bad_arg(h, 15, "T is NULL");
+  if (ldt < D) return bad_arg(h, 16, "ldt < D");
+  if (strideT < 0) return bad_arg(h, 17, "strideT < 0");
+  if (B > 0 && !info) return bad_arg(h, 22, "info is NULL");
+  if (B == 0) return 0;
+  if (!h) return -1;
+  h->last_chunks = 1;  // (a route with a chunk loop counts its own)
+  HIP_TRY(h, hipSetDevice(h->device));
+  const bool diag = noise_kind == BLR_NOISE_DIAGONAL;
+  const bool colv = layout == BLR_LAYOUT_COLVECS;
+
+  CallIO io(h, memspace);
+  MargRaggedArgs<T> a{};
+  a.ldx = ldx; a.strides = strides; a.stridemw = stridemw; a.layout = layout; a.noise_kind = noise_kind; a.D = (int)D;
+  a.prior_kind = BLR_PRIOR_UPPER_FACTOR; a.ldu = ldt; a.strideU = strideT;
+  const size_t x_all = !any ? 0 : (colv ? mat_extent(D, total, ldx) : mat_extent(total, D, ldx));
+  const size_t n_all = any ? (size_t)total : 0;
+  double* total_dev = nullptr;
+  int32_t* info_dev = nullptr;
+  int rc;
+  if ((rc = io.in(X, x_all, &a.X))) return rc;
+  if ((rc = io.in(y, n_all, &a.y))) return rc;
+  if ((rc = io.in(s, diag ? n_all : (any ? extent(B, strides, 1) : 0), &a.s))) return rc;
+  if ((rc = io.in(mw, extent(B, stridemw, (size_t)D), &a.mw))) return rc;
+  if ((rc = io.in(Tf, extent(B, strideT, mat_extent(D, D, ldt)), &a.U))) return rc;
+  if ((rc = io.out(loo_mean, n_all, &a.lm))) return rc;
+  if ((rc = io.out(loo_var, n_all, &a.lv))) return rc;
+  if ((rc = io.out(loo_logpdf, n_all, &a.ll))) return rc;
+  if ((rc = io.out(loo_total, (size_t)B, &total_dev))) return rc;
+  if ((rc = io.out(info, (size_t)B, &info_dev))) return rc;
+  if (!a.s) a.s = a.mw;  // (no observation at all: never dereferenced, but a valid pointer)
+  if (D > kMaxSmallD) {  // correct, not fast: one regressor after the other through blr_loo_batched_*; the call synchronises
+    {
+      const AsyncScope drain(h, false);
+      for (int64_t b = 0; b < B && rc == 0; ++b) {
+        const int64_t o = offsets[b], n = offsets[b + 1] - o;
+        rc = loo_batched<T>(h, BLR_MEM_DEVICE, layout, 1, D, n, a.X ? a.X + (colv ? o * ldx : o) : (const T*)nullptr, ldx, 0,
+                            a.y ? a.y + o : (const T*)nullptr, 0, noise_kind, diag ? a.s + o : a.s + b * strides, 0, a.mw + b * stridemw, 0,
+                            a.U + b * strideT, ldt, 0, a.lm ? a.lm + o : (T*)nullptr, 0, a.lv ? a.lv + o : (T*)nullptr, 0,
+                            a.ll ? a.ll + o : (double*)nullptr, 0, total_dev ? total_dev + b : (double*)nullptr, info_dev + b);
+      }
+    }
+    if (rc) return rc;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return io.finish();
+  }
+  if ((rc = ensure_stats(h))) return rc;
+  a.degenerate = h->stats_dev + 3;
+  a.info = info_dev;
+  RaggedPlan plan;
+  plan_ragged(offsets, B, h->cus, (int)sizeof(T), h->opt, plan);
+  if ((rc = ragged_items_upload(h, offsets, B, plan, &a.offsets, &a.items))) return rc;
+  // status of every state, the noise scan on its slice (grid.x: at most 65535 regressors per launch)
+  const int64_t ychunk = h->cap_chunk(65535);
+  for (int64_t b0 = 0; b0 < B; b0 += ychunk)
+    hipLaunchKernelGGL(loo_ragged_check_kernel<T>, dim3((unsigned)std::min<int64_t>(ychunk, B - b0)), dim3(kThreads), 0, h->stream, a.U + b0 * strideT,
+                       ldt, strideT, (int)D, diag ? a.s : a.s + b0 * strides, strides, noise_kind, a.offsets + b0, info_dev + b0);
+  HIP_TRY(h, hipGetLastError());
+  // the totals need the log densities somewhere: wanted without them, they go to workspace, packed as the outputs are
+  if (total_dev && !a.ll) {
+    if ((rc = h->loo_ws.reserve(h, (n_all + 1) * sizeof(double)))) return rc;
+    a.ll = reinterpret_cast<double*>(h->loo_ws.p) - offsets[0];
+  }
+  if (any && (a.lm || a.lv || a.ll)) {
+    const bool gemm = marg_ragged_gemm_takes<T>(h, layout, D, X, ldx) && marg_ragged_gemm_takes<T>(h, layout, D, a.X, ldx);
+    if ((rc = marg_ragged_launch<T, true>(h, a, plan, gemm))) return rc;
+  }
+  for (int64_t b0 = 0; total_dev && b0 < B; b0 += ychunk)
+    hipLaunchKernelGGL(loo_ragged_total_kernel, dim3((unsigned)std::min<int64_t>(ychunk, B - b0)), dim3(kThreads), 0, h->stream, (const double*)a.ll,
+                       a.offsets + b0, total_dev + b0, (const int32_t*)info_dev + b0);
+  HIP_TRY(h, hipGetLastError());
+  return io.finish();
+}
+
 // ---- batched multi-output posterior: S target columns per regressor (blr_posterior_multi_batched_*) ----------------
 
 template <typename T>
@@ -4896,6 +5158,20 @@ int blr_timer_stop(blr_handle* h, float* elapsed_ms) {
     return posterior_ragged<T>(h, memspace, layout, B, D, offsets, X, ldx, y, noise_kind, s, strides, prior_kind,   \
                                mw, stridemw, Lw, ldl, strideLw, mw_post, stride_mwpost, T_post, ldt, strideT,       \
                                Lw_post, ldlp, strideLp, logpdf, info);                                              \
+  }                                                                                                                 \
+  int blr_marginals_ragged_##SUF(blr_handle* h, int memspace, int layout, int64_t B, int64_t D,                     \
+                                 const int64_t* offsets, const T* X, int64_t ldx, int noise_kind, const T* s,       \
+                                 int64_t strides, int prior_kind, const T* mw, int64_t stridemw, const T* Lw,       \
+                                 int64_t ldl, int64_t strideLw, T* mean, T* var, int32_t* info) {                   \
+    return marginals_ragged<T>(h, memspace, layout, B, D, offsets, X, ldx, noise_kind, s, strides, prior_kind, mw,  \
+                               stridemw, Lw, ldl, strideLw, mean, var, info);                                       \
+  }                                                                                                                 \
+  int blr_loo_ragged_##SUF(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, const int64_t* offsets,   \
+                           const T* X, int64_t ldx, const T* y, int noise_kind, const T* s, int64_t strides,        \
+                           const T* mw, int64_t stridemw, const T* Tf, int64_t ldt, int64_t strideT, T* loo_mean,   \
+                           T* loo_var, double* loo_logpdf, double* loo_total, int32_t* info) {                      \
+    return loo_ragged<T>(h, memspace, layout, B, D, offsets, X, ldx, y, noise_kind, s, strides, mw, stridemw, Tf,   \
+                         ldt, strideT, loo_mean, loo_var, loo_logpdf, loo_total, info);                             \
   }                                                                                                                 \
   int blr_posterior_multi_batched_##SUF(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t N,   \
                                         int64_t S, const T* X, int64_t ldx, int64_t strideX, const T* Y,            \

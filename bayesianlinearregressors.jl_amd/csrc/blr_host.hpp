@@ -54,6 +54,8 @@
   X("I8_PROBE_MIN", set_i8_probe_min) \
   X("I8_GROUPS", set_i8_groups)   \
   X("MAX_CHUNK", set_max_chunk)
+// valued options of the host-only planners that only tests set (blr_ragged_items.hpp): parsed like the ones above, listed apart
+#define BLR_PLANNER_OPTIONS(Y) Y("RAGGED_ITEM", set_ragged_item)
 
 struct BlrOptions {
 #define BLR_X(member, key) bool member = false;
@@ -64,6 +66,7 @@ struct BlrOptions {
   int i8_probe_min = 0;   // int8 route: batches beyond this many regressors start with a probe slice; 0 = kI8ProbeMin
   int i8_groups = 0;      // int8 route: digit groups kept, 0 = six under isotropic noise and seven under diagonal noise; 6 | 7 = that plan for both noise kinds
   int max_chunk = 0;      // regressors per chunk / slice of every batched entry point: 0 = the launch's own bound (tests: small groups cross every seam)
+  int ragged_item = 0;    // observations per work item of the ragged marginals / LOO (blr_ragged_items.hpp): 0 = the planner's own (tests: short regressors cross item seams)
   long chain_ws_mb = 0;   // workspace bound of such a group in MiB: 0 = kChainWorkspace
   int sweep = 0;          // blr_update_factor_* route: 0 = router, 1 = always the Givens sweep, 2 = never
   int gs_fields = 0, gs_so = 0, gs_sd = 0, gs_nl = 0;  // GRAM_SPLITS = "off-diagonal,diagonal[,nlong]" (gs_fields = numbers parsed)
@@ -110,6 +113,13 @@ struct BlrOptions {
     max_chunk = (int)v;
     return 0;
   }
+  int set_ragged_item(bool on, const char* value) {
+    long v = 0;
+    if (!on) { ragged_item = 0; return 0; }
+    if (!parse_long(value, v) || v < 1 || v > (1 << 30)) return -3;
+    ragged_item = (int)v;
+    return 0;
+  }
   int set_chain_ws_mb(bool on, const char* value) {
     long v = 0;
     if (!on) { chain_ws_mb = 0; return 0; }
@@ -138,6 +148,7 @@ struct BlrOptions {
 #undef BLR_X
 #define BLR_X(k, parser) if (!strcmp(key, k)) return parser(on, value);
     BLR_VALUE_OPTIONS(BLR_X)
+    BLR_PLANNER_OPTIONS(BLR_X)
 #undef BLR_X
     return -2;
   }
@@ -150,6 +161,7 @@ struct BlrOptions {
     // valued options: an empty variable is ignored (the built-in default stays), a malformed one too
 #define BLR_X(k, parser) if (const char* v = env(k)) { if (*v) (void)parser(true, v); }
     BLR_VALUE_OPTIONS(BLR_X)
+    BLR_PLANNER_OPTIONS(BLR_X)
 #undef BLR_X
   }
 };

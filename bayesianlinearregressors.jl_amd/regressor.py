@@ -29,7 +29,7 @@ __all__ = [
     "LOO", "loo", "loo_map", "loo_columns", "loo_columns_map",
     "KFold", "kfold", "kfold_map", "kfold_large", "kfold_large_map", "cross_validate", "kfold_columns", "kfold_columns_map",
     "EvidenceGrid", "logpdf_grid", "posterior_best", "logpdf_grid_map",
-    "posterior_ragged", "logpdf_ragged",
+    "posterior_ragged", "logpdf_ragged", "mean_ragged", "var_ragged", "mean_and_var_ragged", "loo_ragged",
     "posterior_columns", "logpdf_columns_map", "posterior_columns_map",
     "mean_and_var_columns", "mean_columns", "mean_and_var_columns_map",
     "cov_map", "mean_and_cov_map",
@@ -632,8 +632,9 @@ def _unpack_many(lp, info, mw_post, Tb, Ab, D):
     return out
 
 
-def _ragged_packed(f, x, offsets, Sy, y, want_posterior):
-    """The packed form behind posterior_ragged / logpdf_ragged -> ([(logpdf, mw', T, A)], the B prior regressors)."""
+def _ragged_operands(f, x, offsets, Sy, y):
+    """The packed arguments every ragged entry point shares, as the library wants them (``y`` None: a call without targets; ``Sy``
+    None: a call that does not read the noise) -> None for an empty batch."""
     offsets = np.ascontiguousarray(offsets, dtype=np.int64)
     if offsets.ndim != 1 or offsets.shape[0] < 1:
         raise ValueError("offsets must be a vector of B + 1 entries")
@@ -642,15 +643,18 @@ def _ragged_packed(f, x, offsets, Sy, y, want_posterior):
     if len(fs) != nb or not all(isinstance(g, BayesianLinearRegressor) for g in fs):
         raise ValueError("f must be one BayesianLinearRegressor or B = len(offsets) - 1 of them")
     if nb == 0:
-        return [], fs
-    dtype = np.float32 if all(_dtype_of(g.mw, y) == np.float32 for g in fs) else np.float64
+        return None, fs
+    dtype = np.float32 if all(_dtype_of(g.mw, y if y is not None else g.mw) == np.float32 for g in fs) else np.float64
     X, layout, ldx, D, N = _x_layout(x, dtype)
     if N != total:
         raise ValueError("offsets[-1] != number of inputs")
-    y = np.ascontiguousarray(y, dtype=dtype)
-    if y.ndim != 1 or y.shape[0] != N:
-        raise ValueError("length(y) != size(fx.x.X, 2)")  # reference :74
-    if isinstance(Sy, Diagonal):
+    if y is not None:
+        y = np.ascontiguousarray(y, dtype=dtype)
+        if y.ndim != 1 or y.shape[0] != N:
+            raise ValueError("length(y) != size(fx.x.X, 2)")  # reference :74
+    if Sy is None:
+        s, noise_kind = None, _abi.NOISE_ISOTROPIC
+    elif isinstance(Sy, Diagonal):
         s, noise_kind = _noise(Sy, N, dtype)
     else:
         Sy = np.asarray(Sy, dtype=dtype)
@@ -668,6 +672,17 @@ def _ragged_packed(f, x, offsets, Sy, y, want_posterior):
     pdmat = isinstance(fs[0].Lw, PDMat)
     mwb = np.stack([_mean_vector(g.mw, D, dtype) for g in ([f] if shared else fs)])
     Lb = np.stack([q[0].reshape(-1, order="A") for q in priors])
+    strides = 1 if s is not None and s.shape[0] == nb and noise_kind == _abi.NOISE_ISOTROPIC else 0
+    return (dtype, offsets, nb, X, layout, ldx, D, y, s, noise_kind, strides, prior_kind, ldl, pdmat, mwb, 0 if shared else D, Lb,
+            0 if shared else Lb.shape[1]), fs
+
+
+def _ragged_packed(f, x, offsets, Sy, y, want_posterior):
+    """The packed form behind posterior_ragged / logpdf_ragged -> ([(logpdf, mw', T, A)], the B prior regressors)."""
+    ops, fs = _ragged_operands(f, x, offsets, Sy, y)
+    if ops is None:
+        return [], fs
+    dtype, offsets, nb, X, layout, ldx, D, y, s, noise_kind, strides, prior_kind, ldl, pdmat, mwb, stridemw, Lb, strideLw = ops
     lp = np.zeros(nb, dtype=np.float64)
     info = np.zeros(nb, dtype=np.int32)
     if want_posterior:
@@ -676,8 +691,8 @@ def _ragged_packed(f, x, offsets, Sy, y, want_posterior):
         Ab = np.empty((nb, D * D), dtype=dtype) if not pdmat else None
     else:
         mw_post = Tb = Ab = None
-    _handle().posterior_ragged(dtype, _abi.MEM_HOST, layout, nb, D, offsets, X, ldx, y, noise_kind, s, 1 if s.shape[0] == nb and noise_kind == _abi.NOISE_ISOTROPIC else 0,
-                               prior_kind, mwb, 0 if shared else D, Lb, ldl, 0 if shared else Lb.shape[1], mw_post, D, Tb, D, D * D, Ab, D,
+    _handle().posterior_ragged(dtype, _abi.MEM_HOST, layout, nb, D, offsets, X, ldx, y, noise_kind, s, strides,
+                               prior_kind, mwb, stridemw, Lb, ldl, strideLw, mw_post, D, Tb, D, D * D, Ab, D,
                                D * D, lp, info)
     return _unpack_many(lp, info, mw_post, Tb, Ab, D), fs
 
@@ -696,6 +711,91 @@ def posterior_ragged(f, x, offsets, Sy, y):
     library call; arguments as logpdf_ragged."""
     res, fs = _ragged_packed(f, x, offsets, Sy, y, want_posterior=True)
     return [BayesianLinearRegressor(mw_post, _wrap_like(g.Lw, T, A)) for g, (_, mw_post, T, A) in zip(fs, res)]
+
+
+def _marginals_ragged(f, x, offsets, Sy, want_mean, want_var):
+    """The packed form behind mean_ragged / var_ragged / mean_and_var_ragged -> (mean or None, var or None), offsets[-1] long."""
+    ops, _ = _ragged_operands(f, x, offsets, Sy if want_var else None, None)
+    if ops is None:
+        return (np.empty(0) if want_mean else None), (np.empty(0) if want_var else None)
+    dtype, offsets, nb, X, layout, ldx, D, _, s, noise_kind, strides, prior_kind, ldl, _, mwb, stridemw, Lb, strideLw = ops
+    total = int(offsets[-1])
+    mean = np.zeros(total, dtype=dtype) if want_mean else None
+    var = np.zeros(total, dtype=dtype) if want_var else None
+    info = np.zeros(nb, dtype=np.int32)
+    _handle().marginals_ragged(dtype, _abi.MEM_HOST, layout, nb, D, offsets, X, ldx, noise_kind, s, strides, prior_kind, mwb, stridemw,
+                               Lb if want_var else None, ldl, strideLw, mean, var, info)
+    bad = np.flatnonzero(info)
+    if bad.size:
+        e = _abi.PosDefException(int(info[bad[0]]))
+        e.index = int(bad[0])
+        raise e
+    return mean, var
+
+
+def mean_ragged(f, x, offsets):
+    """mean(f_b(x[offsets[b]:offsets[b+1]])) for every b (reference :33 under a map over fxs of different lengths) from packed
+    inputs in one library call (blr_marginals_ragged_*); the result is packed as the inputs are, ``offsets[-1]`` long.  ``f``: one
+    BayesianLinearRegressor shared by all, or B of them with one kind of prior precision."""
+    return _marginals_ragged(f, x, offsets, None, True, False)[0]
+
+
+def var_ragged(f, x, offsets, Sy):
+    """var(f_b(x[offsets[b]:offsets[b+1]], Sy_b)) for every b (reference :40-43 under a map), packed; ``f`` and ``Sy`` as
+    `posterior_ragged` takes them.  A dense prior that is not positive definite raises PosDefException with ``index``."""
+    return _marginals_ragged(f, x, offsets, Sy, False, True)[1]
+
+
+def mean_and_var_ragged(f, x, offsets, Sy):
+    """(mean, var) of every packed regressor at its own inputs (reference :47 under a map) in one library call; arguments as
+    `var_ragged`."""
+    return _marginals_ragged(f, x, offsets, Sy, True, True)
+
+
+def loo_ragged(f, x, offsets, Sy, y):
+    """[loo(f_b(x[offsets[b]:offsets[b+1]], Sy_b), y[...])] from packed arrays: the data staged once, blr_posterior_ragged_* into
+    device buffers (mw', T), then blr_loo_ragged_* on the same device inputs -- `_loo_batch`'s pipeline for unequal counts.
+    Nothing D x D comes back to the host.  Arguments as `posterior_ragged`.  The first regressor whose prior, noise or posterior is
+    not positive definite raises PosDefException with its position as ``index``."""
+    ops, _ = _ragged_operands(f, x, offsets, Sy, y)
+    if ops is None:
+        return []
+    dtype, offsets, nb, X, layout, ldx, D, y, s, noise_kind, strides, prior_kind, ldl, _, mwb, stridemw, Lb, strideLw = ops
+    h, item, total = _handle(), np.dtype(dtype).itemsize, int(offsets[-1])
+    temps = []
+
+    def dev(a):
+        temps.append(_DeviceBuffer.of(h, a))
+        return temps[-1].ptr
+
+    m, v = np.zeros(total, dtype=dtype), np.zeros(total, dtype=dtype)
+    lp, tot, info = np.zeros(total, dtype=np.float64), np.zeros(nb, dtype=np.float64), np.zeros(nb, dtype=np.int32)
+    try:
+        dX, dy, ds = dev(X.reshape(-1, order="A")), dev(y), dev(s)
+        temps.extend([_DeviceBuffer(h, nb * D * item), _DeviceBuffer(h, nb * D * D * item)])
+        d_mwp, d_T = temps[-2].ptr, temps[-1].ptr
+        d_info = dev(info)
+        h.posterior_ragged(dtype, _abi.MEM_DEVICE, layout, nb, D, offsets, dX, ldx, dy, noise_kind, ds, strides, prior_kind, dev(mwb),
+                           stridemw, dev(Lb), ldl, strideLw, d_mwp, D, d_T, max(D, 1), D * D, None, max(D, 1), D * D, None, d_info)
+        h.memcpy_d2h(info, d_info)
+        if not np.any(info):
+            outs = [_DeviceBuffer(h, max(total, 1) * item), _DeviceBuffer(h, max(total, 1) * item), _DeviceBuffer(h, max(total, 1) * 8),
+                    _DeviceBuffer(h, nb * 8)]
+            temps.extend(outs)
+            d_lm, d_lv, d_ll, d_tot = (b.ptr for b in outs)
+            h.loo_ragged(dtype, _abi.MEM_DEVICE, layout, nb, D, offsets, dX, ldx, dy, noise_kind, ds, strides, d_mwp, D, d_T, max(D, 1),
+                         D * D, d_lm, d_lv, d_ll, d_tot, d_info)
+            for host, dptr in ((m, d_lm), (v, d_lv), (lp, d_ll), (tot, d_tot), (info, d_info)):
+                h.memcpy_d2h(host, dptr)
+    finally:
+        for b in temps:
+            b.free()
+    bad = np.flatnonzero(info)
+    if bad.size:
+        e = _abi.PosDefException(int(info[bad[0]]))
+        e.index = int(bad[0])
+        raise e
+    return [LOO(m[o0:o1], v[o0:o1], lp[o0:o1], float(tot[b])) for b, (o0, o1) in enumerate(zip(offsets[:-1], offsets[1:]))]
 
 
 def logpdf_map(fxs, ys):
@@ -1053,7 +1153,8 @@ def loo(fx, y):
 def loo_map(fxs, ys):
     """[loo(fx, y) for fx, y in zip(fxs, ys)] in one posterior call and one LOO call for equally shaped problems (else one call
     per problem, as `posterior_map`).  The first problem whose prior, noise or posterior is not positive definite raises
-    PosDefException with its position as ``index``."""
+    PosDefException with its position as ``index``.  Problems with UNEQUAL observation counts whose data is already packed side
+    by side go through `loo_ragged` in two library calls."""
     fxs, ys = list(fxs), list(ys)
     if len(fxs) != len(ys):
         raise ValueError("as many observation vectors as finite regressors are needed")

@@ -76,7 +76,7 @@ int blr_set_async(blr_handle* h, int async);      /* 1: DEVICE-memspace calls re
 int blr_synchronize(blr_handle* h);
 /* Run-time switches of the handle (A/B measurements and tests; the defaults are the measured best).  `key` is one of NO_LDSDMA,
  * NO_WAVE_KERNEL, NO_GRAM_RING, NO_DIAG_SPLIT, NO_XCD_SWIZZLE, NO_MFMA_PROJECT, NO_I8_GRAM, NO_I8_DIAG, NO_I8_FACTOR, NO_I8_ROWVECS, NO_I8_DENSE, NO_I8_FALLBACK, NO_BF16X3, NO_PLANES, NO_FP16_PLANES, PLANES8, NO_SPEC_ROWMAX, NO_MULTI_PLANES, NO_MARG_GEMM, NO_GRAD_GEMM, NO_DOWNDATE_LDS, PLAN_DEBUG (flags: any non-empty value = on),
- * WAVE_SPLIT = 1|2|4, CHAIN_BATCH = 1..128, CHAIN_WS_MB, I8_PROBE_MIN = 256..2^20, I8_GROUPS = 6|7, MAX_CHUNK = 1..65535 (tests: at most that many regressors per chunk / slice of every batched entry point, so that small batches cross the seams over-bound batches cross), SWEEP = always|never|auto, GRAM_SPLITS = "o,d[,nlong]" (README.md);
+ * WAVE_SPLIT = 1|2|4, CHAIN_BATCH = 1..128, CHAIN_WS_MB, I8_PROBE_MIN = 256..2^20, I8_GROUPS = 6|7, RAGGED_ITEM = 1..2^30 (tests: observations per work item of blr_marginals_ragged_* / blr_loo_ragged_*, rounded up to 64), MAX_CHUNK = 1..65535 (tests: at most that many regressors per chunk / slice of every batched entry point, so that small batches cross the seams over-bound batches cross), SWEEP = always|never|auto, GRAM_SPLITS = "o,d[,nlong]" (README.md);
  * a "BLR_MI355X_" prefix is accepted.  value NULL or "" restores the built-in default.  The environment variables
  * BLR_MI355X_<KEY> are read ONCE, by blr_create -- no entry point reads the environment.  -> 0, or -2 / -3 (unknown key /
  * malformed value). */
@@ -240,6 +240,88 @@ int blr_posterior_ragged_f32(blr_handle* h, int memspace, int layout, int64_t B,
                              float* T_post, int64_t ldt, int64_t strideT,
                              float* Lw_post, int64_t ldlp, int64_t strideLp,
                              double* logpdf, int32_t* info);
+
+/* ---- marginals of regressors with UNEQUAL observation counts in one call ------------------------------------------------------
+ * Replaces: reference src/bayesian_linear_regression.jl:33 (mean), :40-43 (var) and :47 (mean_and_var) under a map over fxs of
+ * different lengths -- which blr_marginals_batched_* (one N for the batch) serves only by a loop of calls or by padding every
+ * regressor to the longest one.
+ * Packing: exactly blr_posterior_ragged_*'s.  offsets is ALWAYS a host array of B + 1 entries, in both memspaces; offsets[0] >= 0,
+ * non-decreasing, every N_b = offsets[b+1] - offsets[b] <= 2^30; a violation is argument error -6.  ColVecs: regressor b's inputs
+ * start at X + offsets[b]*ldx (ldx >= D); RowVecs: at X + offsets[b] (ldx >= offsets[B]).  Diagonal noise: s + offsets[b];
+ * isotropic noise: s + b*strides; dense noise is an argument error.  mw + b*stridemw, Lw + b*strideLw; all three prior kinds, with
+ * the meaning blr_marginals_batched_* gives them.
+ * Outputs: element n of regressor b is written at mean[offsets[b] + n] / var[offsets[b] + n] -- packed as the inputs are; there are
+ * no output strides, so nothing can overlap.  Either may be NULL; with var == NULL neither s nor Lw is read (both may be NULL).
+ * info[B]: the status of a dense prior's factorisation (> 0: not positive definite; the outputs of that regressor are left
+ * untouched), 0 otherwise.  The call returns 0 when the launches succeeded.  N_b = 0 writes nothing for that regressor; B = 0 is a
+ * no-op.  The argument checks come before the handle's: a NULL handle with valid arguments returns -1.
+ * D <= 128 (csrc/blr_marg_ragged.hpp, csrc/blr_ragged_items.hpp): the host cuts every regressor into work items of at
+ * most W observations (W a multiple of 64, about one round of resident workgroups over the call; handle option RAGGED_ITEM forces it
+ * for tests) and launches one workgroup per item -- a regressor far longer than the others is spread over the chip instead of
+ * ending the call alone.  D = 128 with a factor or dense prior, ColVecs with 16-byte aligned X and ldx or RowVecs: the
+ * triangular inverse image once per regressor, then the product stream of blr_marginals_batched_* over the item's tiles (a mean-only
+ * call of such a shape runs the same kernel without image and product: the route never depends on the outputs requested).  Any other
+ * D <= 128 shape: the triangular sweep over LDS-resident tiles of 64 inputs.  offsets and the item table (8 + 12 bytes per
+ * regressor and item) are uploaded to the handle's workspace (counted by blr_get_stat "workspace_bytes", freed by
+ * blr_release_workspace).
+ * Bit promises (to this entry point itself): results are bit-reproducible from call to call; the bits of regressor b are those of
+ * this entry point with B = 1 on its slice -- independent of B, of the other regressors' data and counts, of any permutation of the
+ * batch, of the chunking (option MAX_CHUNK) and of how a regressor is cut into work items; the bits of one output do not depend on
+ * which other outputs are requested; host and device memspace give the same bits; no float atomics.  NOT promised: bit-equality with
+ * blr_marginals_batched_* (it routes by N and runs its products in another order).
+ * Async handle, device memspace: the call only enqueues kernels, but the upload of offsets and the item table drains the handle's
+ * stream first (it may block the host); the library is finished with the caller's offsets array when the call returns.
+ * D > 128: correct, not fast -- one regressor after the other through blr_marginals_batched_* with B = 1; the call synchronises
+ * whatever the handle's async flag says.
+ * _f32: X, s, mw, Lw, mean, var are float. */
+int blr_marginals_ragged_f64(blr_handle* h, int memspace, int layout, int64_t B, int64_t D,
+                             const int64_t* offsets, /* HOST array of B + 1 entries in both memspaces */
+                             const double* X, int64_t ldx,
+                             int noise_kind, const double* s, int64_t strides,
+                             int prior_kind, const double* mw, int64_t stridemw,
+                             const double* Lw, int64_t ldl, int64_t strideLw,
+                             double* mean, double* var, int32_t* info);
+int blr_marginals_ragged_f32(blr_handle* h, int memspace, int layout, int64_t B, int64_t D,
+                             const int64_t* offsets, /* HOST array of B + 1 entries in both memspaces */
+                             const float* X, int64_t ldx,
+                             int noise_kind, const float* s, int64_t strides,
+                             int prior_kind, const float* mw, int64_t stridemw,
+                             const float* Lw, int64_t ldl, int64_t strideLw,
+                             float* mean, float* var, int32_t* info);
+
+/* ---- exact LEAVE-ONE-OUT predictives of regressors with UNEQUAL observation counts in one call ----------------------------------
+ * Replaces: reference src/bayesian_linear_regression.jl:55-58 (logpdf) applied to each held-out point given the rest, under a map
+ * over fxs of different lengths -- blr_loo_batched_* once per regressor, or with every regressor padded to the longest one.
+ * Packing: blr_posterior_ragged_*'s, as for blr_marginals_ragged_* above (offsets: host array, B + 1 entries, violation -6); y and a
+ * diagonal s are read at + offsets[b], isotropic s at b*strides; dense noise is an argument error.
+ * State (mw + b*stridemw, T + b*strideT) as blr_posterior_ragged_* writes it: T upper, only its upper triangle is read; NOT modified.
+ * The formulas, the NaN rule and the "loo_degenerate" statistic are those of blr_loo_batched_*.
+ * Outputs: loo_mean, loo_var, loo_logpdf are packed -- element n of regressor b at index offsets[b] + n, no strides; loo_total[B]
+ * and info[B] are per regressor.  Any of the four may be NULL; with loo_total requested and loo_logpdf NULL the log densities go
+ * through handle workspace.  info rule and order unchanged: T has a non-positive diagonal entry j -> j, else the first non-positive
+ * s_i -> i, for diagonal noise counted WITHIN the regressor's slice; the outputs (loo_total included) of a regressor with info != 0
+ * are left untouched; the call still returns 0.  N_b = 0 writes nothing per observation, loo_total[b] = 0 and info[b] is the state's
+ * status.  B = 0 is a no-op.  The argument checks come before the handle's: a NULL handle with valid arguments returns -1.
+ * Kernels, work items, workspace, the async rule and the D > 128 route (blr_loo_batched_* with B = 1 per regressor; synchronises):
+ * as blr_marginals_ragged_*; the tile loads also fetch y_n and the double-precision epilogue runs at the store.
+ * Bit promises (to this entry point itself): bit-reproducible from call to call; the bits of regressor b are those of this entry
+ * point with B = 1 on its slice -- independent of B, of the other regressors' data and counts, of any permutation of the batch, of
+ * the chunking and of how a regressor is cut into work items; loo_total[b] is a fixed-order sum that depends on N_b only; the bits
+ * of one output do not depend on which other outputs are requested; host and device memspace give the same bits; no float
+ * atomics.  NOT promised: bit-equality with blr_loo_batched_*.
+ * _f32: X, y, s, mw, T, loo_mean, loo_var are float; loo_logpdf and loo_total stay double. */
+int blr_loo_ragged_f64(blr_handle* h, int memspace, int layout, int64_t B, int64_t D,
+                       const int64_t* offsets, /* HOST array of B + 1 entries in both memspaces */
+                       const double* X, int64_t ldx, const double* y,
+                       int noise_kind, const double* s, int64_t strides,
+                       const double* mw, int64_t stridemw, const double* T, int64_t ldt, int64_t strideT,
+                       double* loo_mean, double* loo_var, double* loo_logpdf, double* loo_total, int32_t* info);
+int blr_loo_ragged_f32(blr_handle* h, int memspace, int layout, int64_t B, int64_t D,
+                       const int64_t* offsets, /* HOST array of B + 1 entries in both memspaces */
+                       const float* X, int64_t ldx, const float* y,
+                       int noise_kind, const float* s, int64_t strides,
+                       const float* mw, int64_t stridemw, const float* T, int64_t ldt, int64_t strideT,
+                       float* loo_mean, float* loo_var, double* loo_logpdf, double* loo_total, int32_t* info);
 
 /* ---- S target columns per regressor in one call: the batched multi-output posterior ---------------------------------
  * Replaces: reference src/bayesian_linear_regression.jl:55-58 (logpdf), :60-69 (posterior) and :72-89 (shared quantities) under a

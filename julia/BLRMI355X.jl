@@ -980,6 +980,75 @@ function posterior_ragged!(mw_post::DeviceArray{T}, T_post::DeviceArray{T}, lp::
     return nothing
 end
 
+function marginals_ragged_call(h, ::Type{T}, memspace, layout, B, D, offsets::Vector{Int64}, X, ldx, nk, s, strides, pk, mw, stridemw,
+                               Lw, ldl, strideLw, m, v, info) where {T<:Elt}
+    GC.@preserve offsets X s mw Lw m v info begin
+        if T === Float64
+            ccall((:blr_marginals_ragged_f64, LIB), Cint,
+                  (Ptr{Cvoid}, Cint, Cint, Int64, Int64, Ptr{Int64}, Ptr{T}, Int64, Cint, Ptr{T}, Int64, Cint, Ptr{T}, Int64,
+                   Ptr{T}, Int64, Int64, Ptr{T}, Ptr{T}, Ptr{Int32}),
+                  h, memspace, layout, B, D, offsets, X, ldx, nk, s, strides, pk, mw, stridemw, Lw, ldl, strideLw, m, v, info)
+        else
+            ccall((:blr_marginals_ragged_f32, LIB), Cint,
+                  (Ptr{Cvoid}, Cint, Cint, Int64, Int64, Ptr{Int64}, Ptr{T}, Int64, Cint, Ptr{T}, Int64, Cint, Ptr{T}, Int64,
+                   Ptr{T}, Int64, Int64, Ptr{T}, Ptr{T}, Ptr{Int32}),
+                  h, memspace, layout, B, D, offsets, X, ldx, nk, s, strides, pk, mw, stridemw, Lw, ldl, strideLw, m, v, info)
+        end
+    end
+end
+
+function loo_ragged_call(h, ::Type{T}, memspace, layout, B, D, offsets::Vector{Int64}, X, ldx, y, nk, s, strides, mw, stridemw,
+                         Tf, ldt, strideT, lm, lv, ll, tot, info) where {T<:Elt}
+    GC.@preserve offsets X y s mw Tf lm lv ll tot info begin
+        if T === Float64
+            ccall((:blr_loo_ragged_f64, LIB), Cint,
+                  (Ptr{Cvoid}, Cint, Cint, Int64, Int64, Ptr{Int64}, Ptr{T}, Int64, Ptr{T}, Cint, Ptr{T}, Int64, Ptr{T}, Int64,
+                   Ptr{T}, Int64, Int64, Ptr{T}, Ptr{T}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int32}),
+                  h, memspace, layout, B, D, offsets, X, ldx, y, nk, s, strides, mw, stridemw, Tf, ldt, strideT, lm, lv, ll, tot, info)
+        else
+            ccall((:blr_loo_ragged_f32, LIB), Cint,
+                  (Ptr{Cvoid}, Cint, Cint, Int64, Int64, Ptr{Int64}, Ptr{T}, Int64, Ptr{T}, Cint, Ptr{T}, Int64, Ptr{T}, Int64,
+                   Ptr{T}, Int64, Int64, Ptr{T}, Ptr{T}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int32}),
+                  h, memspace, layout, B, D, offsets, X, ldx, y, nk, s, strides, mw, stridemw, Tf, ldt, strideT, lm, lv, ll, tot, info)
+        end
+    end
+end
+
+"""
+    marginals_ragged!(mean, var, info, X, offsets, s, mw_post, T_post; D, isotropic)
+
+Predictions of B = length(offsets) - 1 regressors with UNEQUAL observation counts at their own inputs, from the state
+`posterior_ragged!` leaves, in one call (D ≤ 128: one workgroup per work item, a long regressor is spread over the chip); `offsets`
+as there.  mean and var are packed as the inputs are (offsets[end] entries); info B (Int32).  Reference semantics per regressor:
+`:33`, `:40-43`, `:47` under a map over fxs of different lengths.
+"""
+function marginals_ragged!(m::DeviceArray{T}, v::DeviceArray{T}, info::DeviceArray{Int32}, X::DeviceArray{T}, offsets::Vector{Int64},
+                           s::DeviceArray{T}, mw_post::DeviceArray{T}, T_post::DeviceArray{T}; D::Int, isotropic::Bool) where {T<:Elt}
+    h = handle()
+    B = length(offsets) - 1
+    check(h, marginals_ragged_call(h, T, MEM_DEVICE, COLVECS, B, D, offsets, X.ptr, D, isotropic ? ISOTROPIC : DIAGONALN, s.ptr,
+                                   isotropic ? 1 : 0, P_UPPER, mw_post.ptr, D, T_post.ptr, D, D * D, m.ptr, v.ptr, info.ptr))
+    return nothing
+end
+
+"""
+    loo_ragged!(loo_mean, loo_var, loo_logpdf, loo_total, info, X, offsets, y, s, mw_post, T_post; D, isotropic)
+
+Exact leave-one-out predictives of the observations the states of `posterior_ragged!` contain, for B = length(offsets) - 1
+regressors with UNEQUAL observation counts in one call; the per-observation outputs are packed as the inputs are, loo_total and
+info have B entries.  Reference semantics: `:55-58` for each held-out point given the rest, under a map over fxs of different
+lengths.
+"""
+function loo_ragged!(lm::DeviceArray{T}, lv::DeviceArray{T}, ll::DeviceArray{Float64}, tot::DeviceArray{Float64}, info::DeviceArray{Int32},
+                     X::DeviceArray{T}, offsets::Vector{Int64}, y::DeviceArray{T}, s::DeviceArray{T}, mw_post::DeviceArray{T},
+                     T_post::DeviceArray{T}; D::Int, isotropic::Bool) where {T<:Elt}
+    h = handle()
+    B = length(offsets) - 1
+    check(h, loo_ragged_call(h, T, MEM_DEVICE, COLVECS, B, D, offsets, X.ptr, D, y.ptr, isotropic ? ISOTROPIC : DIAGONALN, s.ptr,
+                             isotropic ? 1 : 0, mw_post.ptr, D, T_post.ptr, D, D * D, lm.ptr, lv.ptr, ll.ptr, tot.ptr, info.ptr))
+    return nothing
+end
+
 """
     posterior_multi_batched!(mw_post, T_post, logpdf, info, X, Y, s, mw, Λdiag; D, N, S, B, isotropic)
 
