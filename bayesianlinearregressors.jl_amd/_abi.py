@@ -73,6 +73,7 @@ _SIGS = {
     "blr_comm_rank": ([_H], _int),
     "blr_logpdf_allgather_sum": ([_H, _i64, _vp, _vp, _vp], _int),
     "blr_allreduce_sum": ([_H, _int, _vp, _i64], _int),
+    "blr_kfold_ragged_fold_offsets": ([_i64, _vp, _i64, _vp], _int),
 }
 for _suf in ("f64", "f32"):
     _SIGS[f"blr_posterior_batched_{_suf}"] = (
@@ -85,6 +86,8 @@ for _suf in ("f64", "f32"):
         [_H, _int, _int, _i64, _i64, _vp, _vp, _i64, _int, _vp, _i64, _int, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp], _int)
     _SIGS[f"blr_loo_ragged_{_suf}"] = (
         [_H, _int, _int, _i64, _i64, _vp, _vp, _i64, _vp, _int, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp], _int)
+    _SIGS[f"blr_kfold_ragged_{_suf}"] = (
+        [_H, _int, _int, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _int, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp], _int)
     _SIGS[f"blr_posterior_multi_batched_{_suf}"] = (
         [_H, _int, _int, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _int, _vp, _i64, _int, _vp, _i64, _vp, _i64, _i64,
          _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _vp], _int)
@@ -359,6 +362,19 @@ class Handle:
         return self.check(fn(self._h, memspace, layout, B, D, _ptr(offsets), _ptr(X), ldx, _ptr(y), noise_kind, _ptr(s), strides,
                              _ptr(mw), stridemw, _ptr(T), ldt, strideT, _ptr(loo_mean), _ptr(loo_var), _ptr(loo_logpdf),
                              _ptr(loo_total), _ptr(info)))
+
+    def kfold_ragged(self, dtype, memspace, layout, B, D, offsets, F, X, ldx, y, noise_kind, s, strides, mw, stridemw, T, ldt, strideT,
+                     kf_mean, kf_var, kf_logpdf, kf_total, info):
+        """Exact leave-fold-out predictives (folds of F <= 64 observations of each regressor's own slice) of B states with unequal
+        observation counts, packed as `posterior_ragged` packs them; kf_logpdf is packed by folds (`kfold_ragged_fold_offsets`);
+        include/blr_mi355x.h blr_kfold_ragged_*."""
+        fn = getattr(self.lib, f"blr_kfold_ragged_{suffix(dtype)}")
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        if offsets.shape != (B + 1,):
+            raise ValueError(f"offsets must have B + 1 = {B + 1} entries, got shape {offsets.shape}")
+        return self.check(fn(self._h, memspace, layout, B, D, _ptr(offsets), F, _ptr(X), ldx, _ptr(y), noise_kind, _ptr(s), strides,
+                             _ptr(mw), stridemw, _ptr(T), ldt, strideT, _ptr(kf_mean), _ptr(kf_var), _ptr(kf_logpdf),
+                             _ptr(kf_total), _ptr(info)))
 
     def posterior_multi_batched(self, dtype, memspace, layout, B, D, N, S, X, ldx, strideX, Y, ldY, strideY, noise_kind, s, strides,
                                 prior_kind, mw, stridemw, Lw, ldl, strideLw, mw_post, ldmp, stride_mwpost, T_post, ldt, strideT,

@@ -42,6 +42,7 @@
 #include "blr_kfold.hpp"
 #include "blr_kfold_large.hpp"
 #include "blr_kfold_multi.hpp"
+#include "blr_kfold_ragged.hpp"
 #include "blr_host.hpp"
 #include "blr_large_plan.hpp"
 
@@ -4439,6 +4440,159 @@ int kfold_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_t D,
   return io.finish();
 }
 
+// ---- leave-fold-out predictives of regressors with unequal observation counts (blr_kfold_ragged_*; blr_kfold_ragged.hpp,
+// blr_kfold_ragged_plan.hpp) ---------------------------------------------------------------------------------------------------------
+// the arguments blr_kfold_ragged_fold_offsets shares with the entry points, at their positions there
+inline int kfold_ragged_shape_check(blr_handle* h, int64_t B, const int64_t* offsets, int64_t F) {
+  if (B < 0 || B > (1 << 30)) return bad_arg(h, 4, "B out of range (0..2^30)");
+  if (const int rc = ragged_offsets_check(h, B, offsets)) return rc;
+  if (F < 1 || F > kFoldMax) return bad_arg(h, 7, "F out of range (1..64)");
+  return 0;
+}
+
+template <typename T>
+int kfold_ragged(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, const int64_t* offsets, int64_t F, const T* X, int64_t ldx,
+                 const T* y, int noise_kind, const T* s, int64_t strides, const T* mw, int64_t stridemw, const T* Tf, int64_t ldt,
+                 int64_t strideT, T* kf_mean, T* kf_var, double* kf_logpdf, double* kf_total, int32_t* info) {
+  // (the argument checks come before the handle's: they need no device)
+  if (h) h->err.clear();
+  if (memspace != BLR_MEM_HOST && memspace != BLR_MEM_DEVICE) return bad_arg(h, 2, "memspace");
+  if (layout != BLR_LAYOUT_COLVECS && layout != BLR_LAYOUT_ROWVECS) return bad_arg(h, 3, "unknown layout (reference :26-31)");
+  if (B < 0 || B > (1 << 30)) return bad_arg(h, 4, "B out of range (0..2^30)");
+  if (D < 1 || D > kMaxLargeD) return bad_arg(h, 5, "D out of range (1..8192)");
+  if (const int rc = ragged_offsets_check(h, B, offsets)) return rc;
+  for (int64_t b = 0; D > kMaxSmallD && b < B; ++b)
+    if (offsets[b + 1] - offsets[b] > kMaxDenseN)
+      return bad_arg(h, 6, "a regressor with more than 16384 observations at D > 128: the route goes through an N x N covariance");
+  if (F < 1 || F > kFoldMax) return bad_arg(h, 7, "F out of range (1..64)");
+  const int64_t total = B > 0 ? offsets[B] : 0;
+  const bool any = B > 0 && offsets[B] > offsets[0];
+  if (any && !X) return bad_arg(h, 8, "X is NULL");
+  if (layout == BLR_LAYOUT_COLVECS ? ldx < D : ldx < std::max<int64_t>(total, 1)) return bad_arg(h, 9, "ldx too small");
+  if (any && !y) return bad_arg(h, 10, "y is NULL (reference :74 length check)");
+  if (noise_kind != BLR_NOISE_ISOTROPIC && noise_kind != BLR_NOISE_DIAGONAL)
+    return bad_arg(h, 11, "noise_kind (dense noise couples the folds: isotropic or diagonal only)");
+  if (any && !s) return bad_arg(h, 12, "s is NULL");
+  if (strides < 0) return bad_arg(h, 13, "strides < 0");
+  if (!mw) return bad_arg(h, 14, "mw is NULL");
+  if (stridemw < 0) return bad_arg(h, 15, "stridemw < 0");
+  if (!Tf) return bad_arg(h, 16, "T is NULL");
+  if (ldt < D) return bad_arg(h, 17, "ldt < D");
+  if (strideT < 0) return bad_arg(h, 18, "strideT < 0");
+  if (B > 0 && !info) return bad_arg(h, 23, "info is NULL");
+  if (B == 0) return 0;
+  if (!h) return -1;
+  h->last_chunks = 1;  // (a route with a chunk loop counts its own)
+  HIP_TRY(h, hipSetDevice(h->device));
+  const bool diag = noise_kind == BLR_NOISE_DIAGONAL;
+  const bool colv = layout == BLR_LAYOUT_COLVECS;
+
+  KfoldRaggedPlan plan;  // (D > 128: only its fold offsets are used)
+  plan_kfold_ragged(offsets, B, F, (int)std::min<int64_t>(D, kMaxSmallD), h->cus, (int)sizeof(T), h->opt, plan);
+  const std::vector<int64_t>& fo = plan.fold_offsets;
+
+  CallIO io(h, memspace);
+  KfoldRaggedArgs<T> a{};
+  a.ldx = ldx; a.strides = strides; a.noise_kind = noise_kind; a.stridemw = stridemw; a.D = (int)D; a.F = (int)F;
+  const size_t x_all = !any ? 0 : (colv ? mat_extent(D, total, ldx) : mat_extent(total, D, ldx));
+  const size_t n_all = any ? (size_t)total : 0, nf_all = (size_t)fo[(size_t)B];
+  const T* T_d = nullptr;
+  double* total_dev = nullptr;
+  int32_t* info_dev = nullptr;
+  int rc;
+  if ((rc = io.in(X, x_all, &a.X))) return rc;
+  if ((rc = io.in(y, n_all, &a.y))) return rc;
+  if ((rc = io.in(s, diag ? n_all : (any ? extent(B, strides, 1) : 0), &a.s))) return rc;
+  if ((rc = io.in(mw, extent(B, stridemw, (size_t)D), &a.mw))) return rc;
+  if ((rc = io.in(Tf, extent(B, strideT, mat_extent(D, D, ldt)), &T_d))) return rc;
+  if ((rc = io.out(kf_mean, n_all, &a.km))) return rc;
+  if ((rc = io.out(kf_var, n_all, &a.kv))) return rc;
+  if ((rc = io.out(kf_logpdf, nf_all, &a.kl))) return rc;
+  if ((rc = io.out(kf_total, (size_t)B, &total_dev))) return rc;
+  if ((rc = io.out(info, (size_t)B, &info_dev))) return rc;
+  if (!a.s) a.s = a.mw;  // (no observation at all: never dereferenced, but a valid pointer)
+  if (D > kMaxSmallD) {  // correct, not fast: one regressor after the other through blr_kfold_batched_*; the call synchronises
+    {
+      const AsyncScope drain(h, false);
+      for (int64_t b = 0; b < B && rc == 0; ++b) {
+        const int64_t o = offsets[b], n = offsets[b + 1] - o;
+        rc = kfold_batched<T>(h, BLR_MEM_DEVICE, layout, 1, D, n, F, a.X ? a.X + (colv ? o * ldx : o) : (const T*)nullptr, ldx, 0,
+                              a.y ? a.y + o : (const T*)nullptr, 0, noise_kind, diag ? a.s + o : a.s + b * strides, 0, a.mw + b * stridemw, 0,
+                              T_d + b * strideT, ldt, 0, a.km ? a.km + o : (T*)nullptr, 0, a.kv ? a.kv + o : (T*)nullptr, 0,
+                              a.kl ? a.kl + fo[(size_t)b] : (double*)nullptr, 0, total_dev ? total_dev + b : (double*)nullptr, info_dev + b);
+      }
+    }
+    if (rc) return rc;
+    h->last_chunks = 1;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return io.finish();
+  }
+  if ((rc = ensure_stats(h))) return rc;
+  a.degenerate = h->stats_dev + 4;
+  a.info = info_dev;
+
+  // offsets, the two tables and the items go to the handle's metadata buffer; the copy is ordered behind the work in flight and the
+  // stream is drained: the host image belongs to the handle and the next call rewrites it (ragged_items_upload)
+  {
+    const size_t tbl = (size_t)(B + 1) * sizeof(int64_t), items_at = 3 * tbl, bytes = items_at + plan.items.size() * sizeof(RaggedItem);
+    h->ragged_host.resize((bytes + 7) / 8);
+    char* const img = reinterpret_cast<char*>(h->ragged_host.data());
+    std::memcpy(img, offsets, tbl);
+    std::memcpy(img + tbl, plan.pack_offsets.data(), tbl);
+    std::memcpy(img + 2 * tbl, fo.data(), tbl);
+    if (!plan.items.empty()) std::memcpy(img + items_at, plan.items.data(), plan.items.size() * sizeof(RaggedItem));
+    if ((rc = h->ragged_meta.reserve(h, bytes, (size_t)1 << 16))) return rc;
+    HIP_TRY(h, hipMemcpyAsync(h->ragged_meta.p, img, bytes, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    a.offsets = reinterpret_cast<const int64_t*>(h->ragged_meta.p);
+    a.pack_offsets = reinterpret_cast<const int64_t*>(h->ragged_meta.p + tbl);
+    a.fold_offsets = reinterpret_cast<const int64_t*>(h->ragged_meta.p + 2 * tbl);
+    a.items = reinterpret_cast<const RaggedItem*>(h->ragged_meta.p + items_at);
+  }
+  // status of every state, the noise scan on its slice (grid.x: at most 65535 regressors per launch)
+  const int64_t ychunk = h->cap_chunk(65535);
+  for (int64_t b0 = 0; b0 < B; b0 += ychunk)
+    hipLaunchKernelGGL(loo_ragged_check_kernel<T>, dim3((unsigned)std::min<int64_t>(ychunk, B - b0)), dim3(kThreads), 0, h->stream, T_d + b0 * strideT,
+                       ldt, strideT, (int)D, diag ? a.s : a.s + b0 * strides, strides, noise_kind, a.offsets + b0, info_dev + b0);
+  HIP_TRY(h, hipGetLastError());
+  // the totals need the log densities somewhere: wanted without them, they go to workspace, packed as the output is
+  const bool spill = total_dev && !a.kl;
+  const bool folds = any && (a.km || a.kv || a.kl || total_dev);
+  if (folds) {
+    const int DP = 16 * (((int)D + 15) / 16);
+    const size_t m_bytes = ((size_t)plan.max_rows * sizeof(T) + 255) & ~(size_t)255;
+    const size_t lds_w = cov_whiten_lds_bytes(sizeof(T), (int)D, true), lds_k = kfold_lds_bytes(sizeof(T), (int)D);
+    void (*const whiten)(KfoldRaggedArgs<T>) = colv ? kfold_ragged_whiten_kernel<T, LAYOUT_COLVECS> : kfold_ragged_whiten_kernel<T, LAYOUT_ROWVECS>;
+    if ((rc = set_lds_once(h, whiten, lds_w))) return rc;
+    if ((rc = set_lds_once(h, kfold_ragged_kernel<T>, lds_k))) return rc;
+    if ((rc = MargImages<T>::reserve(h, plan.max_nb))) return rc;
+    if ((rc = h->cov_ws.reserve(h, (size_t)plan.max_rows * DP * sizeof(T) + 256))) return rc;
+    if ((rc = h->loo_ws.reserve(h, m_bytes + (spill ? nf_all * sizeof(double) : 0) + 256))) return rc;
+    a.Z = reinterpret_cast<T*>(h->cov_ws.p);
+    a.m = reinterpret_cast<T*>(h->loo_ws.p);
+    if (spill) a.kl = reinterpret_cast<double*>(h->loo_ws.p + m_bytes);
+    const RaggedItem* const items = a.items;
+    for (const RaggedChunk& c : plan.chunks) {
+      if (c.nitems == 0) continue;  // (no observation in the chunk)
+      const int64_t npacks = plan.pack_offsets[(size_t)(c.b0 + c.nb)] - plan.pack_offsets[(size_t)c.b0];
+      a.items = items + c.item0;
+      a.b0 = (int)c.b0; a.nb = (int)c.nb;
+      a.img = MargImages<T>::launch(h, T_d, ldt, strideT, (int)D, (const int32_t*)info_dev, c.b0, c.nb);
+      hipLaunchKernelGGL(whiten, dim3((unsigned)c.nitems), dim3(kThreads), lds_w, h->stream, a);
+      hipLaunchKernelGGL(kfold_ragged_kernel<T>, dim3((unsigned)npacks), dim3(kThreads), lds_k, h->stream, a);
+      HIP_TRY(h, hipGetLastError());
+    }
+    h->route = "kfold_ragged_kernel";
+    h->route_i8_B = 0;
+  }
+  h->last_chunks = std::max<int64_t>(1, plan.last_chunks);
+  for (int64_t b0 = 0; total_dev && b0 < B; b0 += ychunk)
+    hipLaunchKernelGGL(loo_ragged_total_kernel, dim3((unsigned)std::min<int64_t>(ychunk, B - b0)), dim3(kThreads), 0, h->stream, (const double*)a.kl,
+                       a.fold_offsets + b0, total_dev + b0, (const int32_t*)info_dev + b0);
+  HIP_TRY(h, hipGetLastError());
+  return io.finish();
+}
+
 // ---- exact leave-fold-out predictives of a batched multi-output state: S columns, one fold factor per fold (blr_kfold_multi_batched_*,
 // DESIGN.md K25; blr_kfold_multi.hpp) ------------------------------------------------------------------------------------------------
 
@@ -5173,6 +5327,14 @@ int blr_timer_stop(blr_handle* h, float* elapsed_ms) {
     return loo_ragged<T>(h, memspace, layout, B, D, offsets, X, ldx, y, noise_kind, s, strides, mw, stridemw, Tf,   \
                          ldt, strideT, loo_mean, loo_var, loo_logpdf, loo_total, info);                             \
   }                                                                                                                 \
+  int blr_kfold_ragged_##SUF(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, const int64_t* offsets, \
+                             int64_t F, const T* X, int64_t ldx, const T* y, int noise_kind, const T* s,            \
+                             int64_t strides, const T* mw, int64_t stridemw, const T* Tf, int64_t ldt,              \
+                             int64_t strideT, T* kf_mean, T* kf_var, double* kf_logpdf, double* kf_total,           \
+                             int32_t* info) {                                                                       \
+    return kfold_ragged<T>(h, memspace, layout, B, D, offsets, F, X, ldx, y, noise_kind, s, strides, mw, stridemw,  \
+                           Tf, ldt, strideT, kf_mean, kf_var, kf_logpdf, kf_total, info);                           \
+  }                                                                                                                 \
   int blr_posterior_multi_batched_##SUF(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t N,   \
                                         int64_t S, const T* X, int64_t ldx, int64_t strideX, const T* Y,            \
                                         int64_t ldY, int64_t strideY, int noise_kind, const T* s, int64_t strides,  \
@@ -5359,6 +5521,14 @@ int blr_timer_stop(blr_handle* h, float* elapsed_ms) {
 
 BLR_DEFINE(f64, double)
 BLR_DEFINE(f32, float)
+
+// host arithmetic only: no handle, no device (blr_kfold_ragged_plan.hpp)
+int blr_kfold_ragged_fold_offsets(int64_t B, const int64_t* offsets, int64_t F, int64_t* fold_offsets) {
+  if (const int rc = kfold_ragged_shape_check(nullptr, B, offsets, F)) return rc;
+  if (!fold_offsets) return -21;
+  kfold_ragged_fold_offsets(offsets, B, F, fold_offsets);
+  return 0;
+}
 
 // ---- multi-GPU exchange: RCCL called directly ------------------------------------------------------
 int blr_comm_unique_id(void* id128) {

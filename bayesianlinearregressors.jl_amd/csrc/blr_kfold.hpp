@@ -8,7 +8,7 @@
 // At F = 1 this is blr_loo.hpp: G~ = 1 - h_n.  The rows Z and the means x_n'mw come from cov_whiten_kernel (blr_cov_batched.hpp), which
 // reads X once and keeps both in handle workspace.
 //
-// kfold_kernel: grid (fold packs, regressors), 256 threads.  A workgroup takes P = floor(64 / F) consecutive folds, at most 64 rows of Z:
+// kfold_kernel: grid (fold packs, regressors), 256 threads; the pack body is kfold_pack, shared with blr_kfold_ragged.hpp.  A workgroup takes P = floor(64 / F) consecutive folds, at most 64 rows of Z:
 //   1. the rows into an LDS tile as cov_tiles_kernel stages Z_j (rows past the pack or past N are zeros), the 64 x 64 product on the
 //      matrix cores with k = d ascending: wave w owns rows 16 w .. 16 w + 15, its A fragments in registers;
 //   2. G~ in double into LDS, 64 rows of 65 doubles -- the row stride is odd in doubles, so the 64 lanes of a column access (lane = row)
@@ -62,21 +62,32 @@ inline size_t kfold_lds_bytes(size_t elem, int D) {
   return (tile > block ? tile : block) + (size_t)5 * kFoldMax * sizeof(double);
 }
 
+// One pack of folds: steps 1-4 above for `nrows` <= 64 rows that start at observation `row0` of ONE regressor.  Every per-observation
+// pointer is the regressor's first element of the caller's array (formed once by the caller: no offset is carried along), so the equal-count kernel (strides) and the
+// ragged one (blr_kfold_ragged.hpp: packed slices) run the same instructions on the same operands: the bits of a fold are the same.
 template <typename T>
-__global__ __launch_bounds__(kThreads, 2) void kfold_kernel(KfoldArgs<T> a) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
+struct KfoldPack {
+  const BLR_GLOBAL T* Zg;            // row row0 of the regressor's Z, rows of DP elements (product route; unused with C)
+  const T* C; int64_t ldc;           // non-NULL: the regressor's N x N covariance instead of Z (D > 128)
+  const BLR_GLOBAL T* yg;            // the regressor's targets
+  const BLR_GLOBAL T* sg; bool diag;  // its noise: s[n], or one value
+  const BLR_GLOBAL T* mg;            // its x_n'mw
+  T* km; T* kv;                      // outputs (may be NULL): the regressor's first element of each
+  double* kl;                        // (by folds)
+  unsigned long long* degenerate;
+  int D, F, row0, nrows;
+};
+
+template <typename T>
+__device__ __forceinline__ void kfold_pack(char* smem, const KfoldPack<T>& a) {
   using Mf = Mfma<T>;
   using acc4 = typename Mf::acc4;
   constexpr int TN = kFoldMax, VEC = Mf::VEC, LDG = kFoldLdg;
   typedef T vecT __attribute__((ext_vector_type(Mf::VEC)));
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int g = lane >> 4, li = lane & 15;
-  const int64_t reg = (int64_t)a.reg0 + blockIdx.y;
-  if (a.info[reg] != 0) return;  // (block-uniform) outputs untouched
-  const int N = a.N, F = a.F;
-  const int P = TN / F, PF = P * F;             // folds and rows of a full pack
-  const int row0 = (int)blockIdx.x * PF;        // first observation of this pack (< N: the grid has ceil(N / PF) packs)
-  const int nrows = min(PF, N - row0);          // rows in use
+  const int F = a.F;
+  const int row0 = a.row0, nrows = a.nrows;
   const int NB = (a.D + 15) / 16, DP = 16 * NB, NK = DP / 4, LDZ = cov_ldz<T>(DP);
   const bool from_cov = a.C != nullptr;
 
@@ -89,16 +100,16 @@ __global__ __launch_bounds__(kThreads, 2) void kfold_kernel(KfoldArgs<T> a) {
   double* const us = rds + TN;   // u
   double* const ts = us + TN;    // log s_n + 2 log(1 / L_nn) + u_n^2
 
-  const BLR_GLOBAL T* const yg = as_global(a.y + reg * a.stridey);
-  const BLR_GLOBAL T* const sg = as_global(a.s + reg * a.strides);
-  const bool diag = a.noise_kind == NOISE_DIAGONAL;
+  const BLR_GLOBAL T* const yg = a.yg;
+  const BLR_GLOBAL T* const sg = a.sg;
+  const bool diag = a.diag;
 
   // ---- 1. the product Z_p Z_p' (rows row0 .. row0 + nrows - 1; the others are zeros) ----
   acc4 acc[4];
 #pragma unroll
   for (int c = 0; c < 4; ++c) acc[c] = acc4{T(0), T(0), T(0), T(0)};
   if (!from_cov) {
-    const BLR_GLOBAL T* const Zg = as_global(a.Z + (int64_t)blockIdx.y * a.strideZ + (int64_t)row0 * DP);
+    const BLR_GLOBAL T* const Zg = a.Zg;
     {
       const BLR_GLOBAL vecT* const src = reinterpret_cast<const BLR_GLOBAL vecT*>(Zg);
       const int nv = DP / VEC;
@@ -133,7 +144,7 @@ __global__ __launch_bounds__(kThreads, 2) void kfold_kernel(KfoldArgs<T> a) {
     const double sv = (double)(diag ? sg[n] : sg[0]);
     const double q = 1.0 / sqrt(sv);
     qs[tid] = q;
-    bs[tid] = q * ((double)yg[n] - (double)as_global(a.m + reg * a.stridem)[n]);
+    bs[tid] = q * ((double)yg[n] - (double)a.mg[n]);
   }
   __syncthreads();  // every wave is done with the tile: the block takes its bytes; q in place
 
@@ -226,17 +237,39 @@ __global__ __launch_bounds__(kThreads, 2) void kfold_kernel(KfoldArgs<T> a) {
       gi = fused_madd(w, us[i], gi);
       cn = fused_madd(w, w, cn);
     }
-    if (a.km) a.km[reg * a.stride_km + n] = bad ? (T)kNan : (T)(yv - sqrt(sv) * gi);
-    if (a.kv) a.kv[reg * a.stride_kv + n] = bad ? (T)kNan : (T)(sv * cn);
+    if (a.km) a.km[n] = bad ? (T)kNan : (T)(yv - sqrt(sv) * gi);
+    if (a.kv) a.kv[n] = bad ? (T)kNan : (T)(sv * cn);
     if (r == lo) {  // the fold's first row: its joint log density
       const double kLog2Pi = 1.8378770664093454835606594728112;
       double sum = 0.0;
       for (int i = lo; i < hi; ++i) sum += ts[i];
-      if (a.kl) a.kl[reg * a.stride_kl + (row0 + lo) / F] = bad ? kNan : -0.5 * ((double)(hi - lo) * kLog2Pi + sum);
+      if (a.kl) a.kl[(row0 + lo) / F] = bad ? kNan : -0.5 * ((double)(hi - lo) * kLog2Pi + sum);
       ndeg = bad ? 1 : 0;
     }
   }
   if (wave == 0) loo_count(ndeg, a.degenerate);  // (all 64 lanes)
+}
+
+template <typename T>
+__global__ __launch_bounds__(kThreads, 2) void kfold_kernel(KfoldArgs<T> a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int64_t reg = (int64_t)a.reg0 + blockIdx.y;
+  if (a.info[reg] != 0) return;  // (block-uniform) outputs untouched
+  const int PF = (kFoldMax / a.F) * a.F;        // rows of a full pack: floor(64 / F) folds
+  const int row0 = (int)blockIdx.x * PF;        // first observation of this pack (< N: the grid has ceil(N / PF) packs)
+  const int DP = 16 * ((a.D + 15) / 16);
+  KfoldPack<T> p;
+  p.Zg = as_global(a.Z + (int64_t)blockIdx.y * a.strideZ + (int64_t)row0 * DP);
+  p.C = a.C; p.ldc = a.ldc;
+  p.yg = as_global(a.y + reg * a.stridey);
+  p.sg = as_global(a.s + reg * a.strides); p.diag = a.noise_kind == NOISE_DIAGONAL;
+  p.mg = as_global(a.m + reg * a.stridem);
+  p.km = a.km ? a.km + reg * a.stride_km : nullptr;
+  p.kv = a.kv ? a.kv + reg * a.stride_kv : nullptr;
+  p.kl = a.kl ? a.kl + reg * a.stride_kl : nullptr;
+  p.degenerate = a.degenerate;
+  p.D = a.D; p.F = a.F; p.row0 = row0; p.nrows = min(PF, a.N - row0);  // rows in use
+  kfold_pack<T>(smem, p);
 }
 
 // the instantiations the library uses, defined in blr_kfold.hip

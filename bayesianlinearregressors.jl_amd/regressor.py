@@ -29,7 +29,7 @@ __all__ = [
     "LOO", "loo", "loo_map", "loo_columns", "loo_columns_map",
     "KFold", "kfold", "kfold_map", "kfold_large", "kfold_large_map", "cross_validate", "kfold_columns", "kfold_columns_map",
     "EvidenceGrid", "logpdf_grid", "posterior_best", "logpdf_grid_map",
-    "posterior_ragged", "logpdf_ragged", "mean_ragged", "var_ragged", "mean_and_var_ragged", "loo_ragged",
+    "posterior_ragged", "logpdf_ragged", "mean_ragged", "var_ragged", "mean_and_var_ragged", "loo_ragged", "kfold_ragged",
     "posterior_columns", "logpdf_columns_map", "posterior_columns_map",
     "mean_and_var_columns", "mean_columns", "mean_and_var_columns_map",
     "cov_map", "mean_and_cov_map",
@@ -796,6 +796,63 @@ def loo_ragged(f, x, offsets, Sy, y):
         e.index = int(bad[0])
         raise e
     return [LOO(m[o0:o1], v[o0:o1], lp[o0:o1], float(tot[b])) for b, (o0, o1) in enumerate(zip(offsets[:-1], offsets[1:]))]
+
+
+def kfold_ragged(f, x, offsets, Sy, y, fold_size):
+    """[kfold(f_b(x[offsets[b]:offsets[b+1]], Sy_b), y[...], fold_size)] from packed arrays: `loo_ragged`'s pipeline with
+    blr_kfold_ragged_* as its second half -- the data staged once, blr_posterior_ragged_* into device buffers (mw', T), then the
+    leave-fold-out predictives on the same device inputs.  Nothing D x D comes back to the host.  Regressor b has the folds
+    [f fold_size, (f + 1) fold_size) of its own slice, 1 <= fold_size <= 64.  Arguments as `posterior_ragged`; returns a list of
+    KFold(mean, var, logpdf, total).  The first regressor whose prior, noise or posterior is not positive definite raises
+    PosDefException with its position as ``index``.  Given the same state, regressor b's result has the bits of `kfold` on that
+    slice; the states themselves are bit-equal only where blr_posterior_ragged_* and the route `posterior` takes agree to the bit,
+    which the handle options NO_I8_GRAM = 1 and NO_WAVE_KERNEL = 1 ensure (include/blr_mi355x.h, blr_posterior_ragged_*)."""
+    F = _fold_size(fold_size)
+    ops, _ = _ragged_operands(f, x, offsets, Sy, y)
+    if ops is None:
+        return []
+    dtype, offsets, nb, X, layout, ldx, D, y, s, noise_kind, strides, prior_kind, ldl, _, mwb, stridemw, Lb, strideLw = ops
+    h, item, total = _handle(), np.dtype(dtype).itemsize, int(offsets[-1])
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    fo = np.zeros(nb + 1, dtype=np.int64)
+    rc = _abi.load_library().blr_kfold_ragged_fold_offsets(nb, _abi._ptr(offsets), F, _abi._ptr(fo))
+    if rc != 0:
+        raise ValueError(f"blr_kfold_ragged_fold_offsets: argument error {rc}")
+    nf = int(fo[-1])
+    temps = []
+
+    def dev(a):
+        temps.append(_DeviceBuffer.of(h, a))
+        return temps[-1].ptr
+
+    m, v = np.zeros(total, dtype=dtype), np.zeros(total, dtype=dtype)
+    lp, tot, info = np.zeros(nf, dtype=np.float64), np.zeros(nb, dtype=np.float64), np.zeros(nb, dtype=np.int32)
+    try:
+        dX, dy, ds = dev(X.reshape(-1, order="A")), dev(y), dev(s)
+        temps.extend([_DeviceBuffer(h, nb * D * item), _DeviceBuffer(h, nb * D * D * item)])
+        d_mwp, d_T = temps[-2].ptr, temps[-1].ptr
+        d_info = dev(info)
+        h.posterior_ragged(dtype, _abi.MEM_DEVICE, layout, nb, D, offsets, dX, ldx, dy, noise_kind, ds, strides, prior_kind, dev(mwb),
+                           stridemw, dev(Lb), ldl, strideLw, d_mwp, D, d_T, max(D, 1), D * D, None, max(D, 1), D * D, None, d_info)
+        h.memcpy_d2h(info, d_info)
+        if not np.any(info):
+            outs = [_DeviceBuffer(h, max(total, 1) * item), _DeviceBuffer(h, max(total, 1) * item), _DeviceBuffer(h, max(nf, 1) * 8),
+                    _DeviceBuffer(h, nb * 8)]
+            temps.extend(outs)
+            d_km, d_kv, d_kl, d_tot = (b.ptr for b in outs)
+            h.kfold_ragged(dtype, _abi.MEM_DEVICE, layout, nb, D, offsets, F, dX, ldx, dy, noise_kind, ds, strides, d_mwp, D, d_T, max(D, 1),
+                           D * D, d_km, d_kv, d_kl, d_tot, d_info)
+            for host, dptr in ((m, d_km), (v, d_kv), (lp, d_kl), (tot, d_tot), (info, d_info)):
+                h.memcpy_d2h(host, dptr)
+    finally:
+        for b in temps:
+            b.free()
+    bad = np.flatnonzero(info)
+    if bad.size:
+        e = _abi.PosDefException(int(info[bad[0]]))
+        e.index = int(bad[0])
+        raise e
+    return [KFold(m[o0:o1], v[o0:o1], lp[fo[b]:fo[b + 1]], float(tot[b])) for b, (o0, o1) in enumerate(zip(offsets[:-1], offsets[1:]))]
 
 
 def logpdf_map(fxs, ys):

@@ -323,6 +323,64 @@ int blr_loo_ragged_f32(blr_handle* h, int memspace, int layout, int64_t B, int64
                        const float* mw, int64_t stridemw, const float* T, int64_t ldt, int64_t strideT,
                        float* loo_mean, float* loo_var, double* loo_logpdf, double* loo_total, int32_t* info);
 
+/* ---- exact LEAVE-FOLD-OUT (K-fold) predictives of regressors with UNEQUAL observation counts in one call -------------------------
+ * Replaces: reference src/bayesian_linear_regression.jl:55-58 (logpdf) applied to each held-out FOLD given the rest, under a map
+ * over fxs of different lengths -- blr_kfold_batched_* once per regressor (padding to the longest regressor is no alternative here:
+ * it changes the folds).
+ * Packing: blr_posterior_ragged_*'s, as for blr_loo_ragged_* above (offsets: host array, B + 1 entries, violation -6); y and a
+ * diagonal s are read at + offsets[b], isotropic s at b*strides; dense noise is an argument error.
+ * State (mw + b*stridemw, T + b*strideT) as blr_posterior_ragged_* writes it: T upper, only its upper triangle is read; NOT modified.
+ * Folds: regressor b has the folds [f F, min((f + 1) F, N_b)) of ITS OWN slice, nfolds_b = ceil(N_b / F); F > N_b gives one fold.
+ * 1 <= F <= 64.  The formulas, the NaN rule and the "kfold_degenerate" statistic are those of blr_kfold_batched_*.
+ * Outputs: kf_mean and kf_var are packed by observations -- element n of regressor b at index offsets[b] + n; kf_logpdf is packed by
+ * FOLDS -- fold f of regressor b at index fold_offsets[b] + f, fold_offsets[0] = 0, fold_offsets[b + 1] = fold_offsets[b] +
+ * nfolds_b (blr_kfold_ragged_fold_offsets below computes the table; kf_logpdf holds fold_offsets[B] doubles); kf_total[B] and
+ * info[B] are per regressor.  Any of the four may be NULL; with kf_total requested and kf_logpdf NULL the log densities go through
+ * handle workspace.  info rule and order as blr_kfold_batched_*: T has a non-positive diagonal entry j -> j, else the first
+ * non-positive s_i -> i, for diagonal noise counted WITHIN the regressor's slice; the outputs (kf_total included) of a regressor
+ * with info != 0 are left untouched; the call still returns 0.  N_b = 0 writes nothing per observation or fold, kf_total[b] = 0
+ * and info[b] is the state's status.  B = 0 is a no-op that touches nothing.
+ * Argument errors (negative position; checked before the handle, so a NULL handle with valid arguments returns -1): memspace -2;
+ * layout -3; B outside 0..2^30 -4; D outside 1..8192 -5; offsets NULL, offsets[0] < 0, decreasing, a count above 2^30 -- or, at
+ * D > 128, above 16384 -- -6; F outside 1..64 -7; X NULL with observations -8; ldx < D (ColVecs) or < max(offsets[B], 1) (RowVecs)
+ * -9; y NULL with observations -10; noise_kind dense -11; s NULL with observations -12; strides < 0 -13; mw NULL -14; stridemw < 0
+ * -15; T NULL -16; ldt < D -17; strideT < 0 -18; info NULL -23.
+ * D <= 128 (csrc/blr_kfold_ragged.hpp, csrc/blr_kfold_ragged_plan.hpp), per chunk of regressors (at most 65535, 256
+ * MiB of images, 256 MiB of rows of Z but never fewer than one regressor, option MAX_CHUNK; blr_get_stat "last_chunks"): the status
+ * and the triangular inverse image once per regressor; one workgroup per work item of blr_loo_ragged_*'s table (option RAGGED_ITEM)
+ * whitens the item's observations, z_n = T^-T x_n and x_n'mw, into handle workspace, packed as the observations are, reading X once;
+ * then a flat grid of one workgroup per pack of floor(64 / F) consecutive folds of ONE regressor runs blr_kfold_batched_*'s fold
+ * body; then the totals.  The flat grid holds fewer than 2^24 packs: only ONE regressor of more than 2^24 floor(64 / F) F
+ * observations (above 5.5e8, F >= 33) exceeds that, and the call then fails with the launch's HIP runtime error (<= -1000), as
+ * blr_kfold_batched_* does at such an N.  offsets, the pack and fold tables and the items (24 bytes per regressor, 12 per item) are uploaded to the
+ * handle's workspace (counted by blr_get_stat "workspace_bytes", freed by blr_release_workspace).
+ * Bit promises (D <= 128): EVERY output of regressor b -- kf_mean, kf_var, its folds of kf_logpdf and kf_total[b] -- is bit for bit
+ * what blr_kfold_batched_* with B = 1 writes on that slice with the same F.  Hence the bits are independent of B, of the other
+ * regressors' data and counts, of any permutation of the batch, of the chunking (option MAX_CHUNK), of how a regressor is cut into
+ * work items (option RAGGED_ITEM) and of which outputs are requested; host and device memspace give the same bits; results are
+ * bit-reproducible from call to call; no float atomics.
+ * Async handle, device memspace: the call only enqueues kernels, but the upload of the tables drains the handle's stream first (it
+ * may block the host); the library is finished with the caller's offsets array when the call returns.
+ * D > 128: correct, not fast -- one regressor after the other through blr_kfold_batched_* with B = 1; the call synchronises
+ * whatever the handle's async flag says.
+ * _f32: X, y, s, mw, T, kf_mean, kf_var are float; kf_logpdf and kf_total stay double. */
+int blr_kfold_ragged_f64(blr_handle* h, int memspace, int layout, int64_t B, int64_t D,
+                         const int64_t* offsets, /* HOST array of B + 1 entries in both memspaces */
+                         int64_t F, const double* X, int64_t ldx, const double* y,
+                         int noise_kind, const double* s, int64_t strides,
+                         const double* mw, int64_t stridemw, const double* T, int64_t ldt, int64_t strideT,
+                         double* kf_mean, double* kf_var, double* kf_logpdf, double* kf_total, int32_t* info);
+int blr_kfold_ragged_f32(blr_handle* h, int memspace, int layout, int64_t B, int64_t D,
+                         const int64_t* offsets, /* HOST array of B + 1 entries in both memspaces */
+                         int64_t F, const float* X, int64_t ldx, const float* y,
+                         int noise_kind, const float* s, int64_t strides,
+                         const float* mw, int64_t stridemw, const float* T, int64_t ldt, int64_t strideT,
+                         float* kf_mean, float* kf_var, double* kf_logpdf, double* kf_total, int32_t* info);
+/* fold_offsets[B + 1] of blr_kfold_ragged_*: host arithmetic only -- no handle, no device.  What callers size kf_logpdf with
+ * (fold_offsets[B] doubles).  Argument errors at the positions of blr_kfold_ragged_*: B -4, offsets -6, F -7; fold_offsets NULL
+ * -21 (the output it sizes).  B = 0 writes fold_offsets[0] = 0. */
+int blr_kfold_ragged_fold_offsets(int64_t B, const int64_t* offsets, int64_t F, int64_t* fold_offsets /* HOST, B + 1 entries */);
+
 /* ---- S target columns per regressor in one call: the batched multi-output posterior ---------------------------------
  * Replaces: reference src/bayesian_linear_regression.jl:55-58 (logpdf), :60-69 (posterior) and :72-89 (shared quantities) under a
  * map over fxs with MATRIX targets -- which blr_posterior_batched_* serves only by S calls with the y pointer stepped by one

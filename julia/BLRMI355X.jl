@@ -1049,6 +1049,55 @@ function loo_ragged!(lm::DeviceArray{T}, lv::DeviceArray{T}, ll::DeviceArray{Flo
     return nothing
 end
 
+function kfold_ragged_call(h, ::Type{T}, memspace, layout, B, D, offsets::Vector{Int64}, F, X, ldx, y, nk, s, strides, mw, stridemw,
+                           Tf, ldt, strideT, km, kv, kl, tot, info) where {T<:Elt}
+    GC.@preserve offsets X y s mw Tf km kv kl tot info begin
+        if T === Float64
+            ccall((:blr_kfold_ragged_f64, LIB), Cint,
+                  (Ptr{Cvoid}, Cint, Cint, Int64, Int64, Ptr{Int64}, Int64, Ptr{T}, Int64, Ptr{T}, Cint, Ptr{T}, Int64, Ptr{T}, Int64,
+                   Ptr{T}, Int64, Int64, Ptr{T}, Ptr{T}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int32}),
+                  h, memspace, layout, B, D, offsets, F, X, ldx, y, nk, s, strides, mw, stridemw, Tf, ldt, strideT, km, kv, kl, tot, info)
+        else
+            ccall((:blr_kfold_ragged_f32, LIB), Cint,
+                  (Ptr{Cvoid}, Cint, Cint, Int64, Int64, Ptr{Int64}, Int64, Ptr{T}, Int64, Ptr{T}, Cint, Ptr{T}, Int64, Ptr{T}, Int64,
+                   Ptr{T}, Int64, Int64, Ptr{T}, Ptr{T}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int32}),
+                  h, memspace, layout, B, D, offsets, F, X, ldx, y, nk, s, strides, mw, stridemw, Tf, ldt, strideT, km, kv, kl, tot, info)
+        end
+    end
+end
+
+"""
+    kfold_ragged_fold_offsets(offsets, F) -> Vector{Int64}
+
+`fold_offsets` of `kfold_ragged!`: fold f of regressor b is entry `fold_offsets[b] + f` (0-based) of kf_logpdf, which holds
+`fold_offsets[end]` entries.  Host arithmetic only (`blr_kfold_ragged_fold_offsets`).
+"""
+function kfold_ragged_fold_offsets(offsets::Vector{Int64}, F::Integer)
+    B = length(offsets) - 1
+    fo = Vector{Int64}(undef, B + 1)
+    rc = ccall((:blr_kfold_ragged_fold_offsets, LIB), Cint, (Int64, Ptr{Int64}, Int64, Ptr{Int64}), B, offsets, F, fo)
+    rc == 0 || error("blr_kfold_ragged_fold_offsets: argument $(-rc)")
+    return fo
+end
+
+"""
+    kfold_ragged!(kf_mean, kf_var, kf_logpdf, kf_total, info, X, offsets, y, s, mw_post, T_post; D, F, isotropic)
+
+Exact leave-fold-out (K-fold) predictives of the observations the states of `posterior_ragged!` contain, for B = length(offsets) - 1
+regressors with UNEQUAL observation counts in one call: regressor b has the contiguous folds of F ≤ 64 observations of its own
+slice.  kf_mean and kf_var are packed as the inputs are, kf_logpdf by folds (`kfold_ragged_fold_offsets`), kf_total and info have B
+entries.  Reference semantics: `:55-58` for each held-out fold given the rest, under a map over fxs of different lengths.
+"""
+function kfold_ragged!(km::DeviceArray{T}, kv::DeviceArray{T}, kl::DeviceArray{Float64}, tot::DeviceArray{Float64}, info::DeviceArray{Int32},
+                       X::DeviceArray{T}, offsets::Vector{Int64}, y::DeviceArray{T}, s::DeviceArray{T}, mw_post::DeviceArray{T},
+                       T_post::DeviceArray{T}; D::Int, F::Int, isotropic::Bool) where {T<:Elt}
+    h = handle()
+    B = length(offsets) - 1
+    check(h, kfold_ragged_call(h, T, MEM_DEVICE, COLVECS, B, D, offsets, F, X.ptr, D, y.ptr, isotropic ? ISOTROPIC : DIAGONALN, s.ptr,
+                               isotropic ? 1 : 0, mw_post.ptr, D, T_post.ptr, D, D * D, km.ptr, kv.ptr, kl.ptr, tot.ptr, info.ptr))
+    return nothing
+end
+
 """
     posterior_multi_batched!(mw_post, T_post, logpdf, info, X, Y, s, mw, Λdiag; D, N, S, B, isotropic)
 
