@@ -3407,23 +3407,107 @@ inline size_t ragged_kernel_lds(float, int NB) { return ragged_kernel_lds_f32(NB
 inline void ragged_kernel_launch(int NB, int mode, unsigned grid, hipStream_t st, const RaggedArgs<double>& a) { ragged_kernel_launch_f64(NB, mode, grid, st, a); }
 inline void ragged_kernel_launch(int NB, int mode, unsigned grid, hipStream_t st, const RaggedArgs<float>& a) { ragged_kernel_launch_f32(NB, mode, grid, st, a); }
 
-// D <= 128: offsets and the longest-first order go to the handle's metadata buffer, then ONE launch.  The upload drains the
-// stream (the host image belongs to the handle and the next call rewrites it); the kernel is only enqueued.
+// ---- what the packed entry points share: blr_posterior_ragged_*, blr_marginals_ragged_*, blr_loo_ragged_*, blr_kfold_ragged_* ------
+// offsets: what blr_posterior_ragged_* asks of it
+inline int ragged_offsets_check(blr_handle* h, int64_t B, const int64_t* offsets) {
+  if (B > 0 && !offsets) return bad_arg(h, 6, "offsets is NULL (a host array of B + 1 entries)");
+  if (B > 0 && offsets[0] < 0) return bad_arg(h, 6, "offsets[0] < 0");
+  for (int64_t b = 0; b < B; ++b) {
+    if (offsets[b + 1] < offsets[b]) return bad_arg(h, 6, "offsets must be non-decreasing");
+    if (offsets[b + 1] - offsets[b] > (1 << 30)) return bad_arg(h, 6, "a regressor with more than 2^30 observations");
+  }
+  return 0;
+}
+
+// The shape of a packed call, filled by ragged_front
+struct RaggedFront {
+  int64_t total = 0;                       // columns of the packed arrays
+  bool any = false;                        // some regressor has an observation
+  bool colv = false, diag = false;         // layout, noise kind
+  size_t x_all = 0, n_all = 0, s_all = 0;  // elements of X, of a packed vector, of s (diagonal: n_all; isotropic: B entries at strides)
+};
+inline int no_check() { return 0; }
+// The checks every packed entry point starts with, in the order of the arguments: memspace (2), layout, B, D, offsets (6), `mid` --
+// what blr_kfold_ragged_* checks next --, then X and ldx at positions xpos and xpos + 1.  The noise kind and strides are the entry
+// point's to check: `diag` and `s_all` mean something once it has.
+template <typename T, typename Mid = int (*)()>
+int ragged_front(blr_handle* h, RaggedFront& f, int memspace, int layout, int64_t B, int64_t D, const int64_t* offsets, const T* X, int64_t ldx,
+                 int noise_kind, int64_t strides, int xpos = 7, Mid mid = no_check) {
+  // (the argument checks come before the handle's: they need no device)
+  if (h) h->err.clear();
+  if (memspace != BLR_MEM_HOST && memspace != BLR_MEM_DEVICE) return bad_arg(h, 2, "memspace");
+  if (layout != BLR_LAYOUT_COLVECS && layout != BLR_LAYOUT_ROWVECS) return bad_arg(h, 3, "unknown layout (reference :26-31)");
+  if (B < 0 || B > (1 << 30)) return bad_arg(h, 4, "B out of range (0..2^30)");
+  if (D < 1 || D > kMaxLargeD) return bad_arg(h, 5, "D out of range (1..8192)");
+  if (const int rc = ragged_offsets_check(h, B, offsets)) return rc;
+  if (const int rc = mid()) return rc;
+  f.total = B > 0 ? offsets[B] : 0;
+  f.any = B > 0 && offsets[B] > offsets[0];
+  f.colv = layout == BLR_LAYOUT_COLVECS;
+  f.diag = noise_kind == BLR_NOISE_DIAGONAL;
+  if (f.any && !X) return bad_arg(h, xpos, "X is NULL");
+  if (f.colv ? ldx < D : ldx < std::max<int64_t>(f.total, 1)) return bad_arg(h, xpos + 1, "ldx too small");
+  f.x_all = !f.any ? 0 : (f.colv ? mat_extent(D, f.total, ldx) : mat_extent(f.total, D, ldx));
+  f.n_all = f.any ? (size_t)f.total : 0;
+  f.s_all = f.diag ? f.n_all : (strides < 0 ? 0 : extent(B, strides, 1));
+  return 0;
+}
+
+// The host tables of a packed call go one behind the other into the handle's metadata buffer; dev[k]: where spans[k] lies on the
+// device.  The copy is ordered behind the work in flight and the stream is drained: the host image belongs to the handle and the
+// next call rewrites it.
+struct MetaSpan { const void* p; size_t bytes; };
+template <size_t K>
+int ragged_meta_upload(blr_handle* h, const MetaSpan (&spans)[K], const char* (&dev)[K]) {
+  size_t bytes = 0;
+  for (const MetaSpan& s : spans) bytes += s.bytes;
+  h->ragged_host.resize((bytes + 7) / 8);
+  char* const img = reinterpret_cast<char*>(h->ragged_host.data());
+  size_t at = 0;
+  for (const MetaSpan& s : spans) {
+    if (s.bytes) std::memcpy(img + at, s.p, s.bytes);
+    at += s.bytes;
+  }
+  if (const int rc = h->ragged_meta.reserve(h, bytes, (size_t)1 << 16)) return rc;
+  HIP_TRY(h, hipMemcpyAsync(h->ragged_meta.p, img, bytes, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  at = 0;
+  for (size_t k = 0; k < K; ++k) {
+    dev[k] = h->ragged_meta.p + at;
+    at += spans[k].bytes;
+  }
+  return 0;
+}
+inline size_t ragged_table_bytes(int64_t B) { return (size_t)(B + 1) * sizeof(int64_t); }  // offsets and its kin
+
+// D > 128: correct, not fast -- one regressor after the other through the equal-count entry point, `one(b, o, n)`: its call with
+// B = 1 on the device operands of regressor b, whose n observations start at o.  Stops at the first failure (device pointers and
+// in-range sizes: a HIP failure, not an argument index of the inner call); the call synchronises.
+template <typename One>
+int ragged_one_by_one(blr_handle* h, int64_t B, const int64_t* offsets, One one) {
+  int rc = 0;
+  {
+    const AsyncScope drain(h, false);
+    for (int64_t b = 0; b < B && rc == 0; ++b) rc = one(b, offsets[b], offsets[b + 1] - offsets[b]);
+  }
+  if (rc) return rc;
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+// D <= 128: offsets and the longest-first order go to the handle's metadata buffer (ragged_meta_upload), then ONE launch: the
+// kernel is only enqueued.
 template <typename T>
 int ragged_launch(blr_handle* h, RaggedArgs<T>& r, const int64_t* offsets) {
   const int64_t B = r.p.B;
-  const size_t order_at = (size_t)(B + 1) * sizeof(int64_t), bytes = order_at + (size_t)B * sizeof(int32_t);
-  h->ragged_host.resize((bytes + 7) / 8);
-  std::memcpy(h->ragged_host.data(), offsets, order_at);
-  int32_t* const order = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(h->ragged_host.data()) + order_at);
-  for (int64_t b = 0; b < B; ++b) order[b] = (int32_t)b;
-  std::stable_sort(order, order + B, [offsets](int32_t i, int32_t j) { return offsets[i + 1] - offsets[i] > offsets[j + 1] - offsets[j]; });
-  int rc = h->ragged_meta.reserve(h, bytes, (size_t)1 << 16);
+  std::vector<int32_t> order((size_t)B);
+  for (int64_t b = 0; b < B; ++b) order[(size_t)b] = (int32_t)b;
+  std::stable_sort(order.begin(), order.end(), [offsets](int32_t i, int32_t j) { return offsets[i + 1] - offsets[i] > offsets[j + 1] - offsets[j]; });
+  const char* dev[2];
+  int rc = ragged_meta_upload(h, {{offsets, ragged_table_bytes(B)}, {order.data(), (size_t)B * sizeof(int32_t)}}, dev);
   if (rc) return rc;
-  HIP_TRY(h, hipMemcpyAsync(h->ragged_meta.p, h->ragged_host.data(), bytes, hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(h, hipStreamSynchronize(h->stream));
-  r.offsets = reinterpret_cast<const int64_t*>(h->ragged_meta.p);
-  r.order = reinterpret_cast<const int32_t*>(h->ragged_meta.p + order_at);
+  r.offsets = reinterpret_cast<const int64_t*>(dev[0]);
+  r.order = reinterpret_cast<const int32_t*>(dev[1]);
 
   const int NB = (r.p.D + 15) / 16;
   const bool vec_ok = r.p.layout == BLR_LAYOUT_COLVECS && r.p.D % Mfma<T>::VEC == 0 && aligned16(r.p.X, r.p.ldx, 0) && !h->opt.no_ldsdma;
@@ -3445,22 +3529,9 @@ int posterior_ragged(blr_handle* h, int memspace, int layout, int64_t B, int64_t
                      const T* y, int noise_kind, const T* s, int64_t strides, int prior_kind, const T* mw, int64_t stridemw,
                      const T* Lw, int64_t ldl, int64_t strideLw, T* mw_post, int64_t stride_mwpost, T* T_post, int64_t ldt,
                      int64_t strideT, T* Lw_post, int64_t ldlp, int64_t strideLp, double* logpdf, int32_t* info) {
-  // (the argument checks come before the handle's: they need no device)
-  if (h) h->err.clear();
-  if (memspace != BLR_MEM_HOST && memspace != BLR_MEM_DEVICE) return bad_arg(h, 2, "memspace");
-  if (layout != BLR_LAYOUT_COLVECS && layout != BLR_LAYOUT_ROWVECS) return bad_arg(h, 3, "unknown layout (reference :26-31)");
-  if (B < 0 || B > (1 << 30)) return bad_arg(h, 4, "B out of range (0..2^30)");
-  if (D < 1 || D > kMaxLargeD) return bad_arg(h, 5, "D out of range (1..8192)");
-  if (B > 0 && !offsets) return bad_arg(h, 6, "offsets is NULL (a host array of B + 1 entries)");
-  if (B > 0 && offsets[0] < 0) return bad_arg(h, 6, "offsets[0] < 0");
-  for (int64_t b = 0; b < B; ++b) {
-    if (offsets[b + 1] < offsets[b]) return bad_arg(h, 6, "offsets must be non-decreasing");
-    if (offsets[b + 1] - offsets[b] > (1 << 30)) return bad_arg(h, 6, "a regressor with more than 2^30 observations");
-  }
-  const int64_t total = B > 0 ? offsets[B] : 0;              // columns of the packed arrays
-  const bool any = B > 0 && offsets[B] > offsets[0];
-  if (any && !X) return bad_arg(h, 7, "X is NULL");
-  if (layout == BLR_LAYOUT_COLVECS ? ldx < D : ldx < std::max<int64_t>(total, 1)) return bad_arg(h, 8, "ldx too small");
+  RaggedFront f;
+  if (const int rc = ragged_front(h, f, memspace, layout, B, D, offsets, X, ldx, noise_kind, strides)) return rc;
+  const bool any = f.any, diag = f.diag;
   if (any && !y) return bad_arg(h, 9, "y is NULL (reference :74 length check)");
   if (noise_kind != BLR_NOISE_ISOTROPIC && noise_kind != BLR_NOISE_DIAGONAL)
     return bad_arg(h, 10, "noise_kind (isotropic or diagonal; dense Sigma_y is not supported for unequal counts)");
@@ -3483,7 +3554,6 @@ int posterior_ragged(blr_handle* h, int memspace, int layout, int64_t B, int64_t
   if (!h) return -1;
   h->last_chunks = 1;  // (a route with a chunk loop counts its own)
   HIP_TRY(h, hipSetDevice(h->device));
-  const bool diag = noise_kind == BLR_NOISE_DIAGONAL;
   RaggedArgs<T> r{};
   PosteriorArgs<T>& a = r.p;
   a.ldx = ldx; a.strides = diag ? 0 : strides; a.stridemw = stridemw; a.ldl = ldl; a.strideLw = strideLw;
@@ -3492,12 +3562,11 @@ int posterior_ragged(blr_handle* h, int memspace, int layout, int64_t B, int64_t
   a.D = (int)D; a.B = (int)B;
 
   CallIO io(h, memspace);
-  const size_t x_all = !any ? 0 : (layout == BLR_LAYOUT_COLVECS ? mat_extent(D, total, ldx) : mat_extent(total, D, ldx));
   const size_t lw_one = prior_kind == BLR_PRIOR_DIAGONAL ? (size_t)D : mat_extent(D, D, ldl);
   int rc;
-  if ((rc = io.in(X, x_all, &a.X))) return rc;
-  if ((rc = io.in(y, any ? (size_t)total : 0, &a.y))) return rc;
-  if ((rc = io.in(s, diag ? (any ? (size_t)total : 0) : extent(B, strides, 1), &a.s))) return rc;
+  if ((rc = io.in(X, f.x_all, &a.X))) return rc;
+  if ((rc = io.in(y, f.n_all, &a.y))) return rc;
+  if ((rc = io.in(s, f.s_all, &a.s))) return rc;
   if ((rc = io.in(mw, extent(B, stridemw, (size_t)D), &a.mw))) return rc;
   if ((rc = io.in(Lw, extent(B, strideLw, lw_one), &a.Lw))) return rc;
   if ((rc = io.out(mw_post, extent(B, stride_mwpost, (size_t)D), &a.mw_post))) return rc;
@@ -3513,49 +3582,58 @@ int posterior_ragged(blr_handle* h, int memspace, int layout, int64_t B, int64_t
     if ((rc = ragged_launch<T>(h, r, offsets))) return rc;
     return io.finish();
   }
-  // D > 128: correct, not fast -- one regressor after the other through the pipeline of blr_posterior_batched_*; the call synchronises
-  {
-    const AsyncScope drain(h, false);
-    for (int64_t b = 0; b < B && rc == 0; ++b) {
-      const int64_t o = offsets[b], n = offsets[b + 1] - o;
-      rc = posterior_batched<T>(h, BLR_MEM_DEVICE, layout, 1, D, n, a.X + (layout == BLR_LAYOUT_COLVECS ? o * ldx : o), ldx, 0, a.y + o, 0,
-                                noise_kind, diag ? a.s + o : a.s + b * strides, 0, prior_kind, a.mw + b * stridemw, 0, a.Lw + b * strideLw,
-                                ldl, 0, a.mw_post ? a.mw_post + b * stride_mwpost : (T*)nullptr, 0, a.T_post ? a.T_post + b * strideT : (T*)nullptr,
-                                ldt, 0, a.Lw_post ? a.Lw_post + b * strideLp : (T*)nullptr, ldlp, 0, a.logpdf ? a.logpdf + b : (double*)nullptr,
-                                a.info + b);
-    }
-  }
-  if (rc) return rc;  // (device pointers and in-range sizes: a HIP failure, not an argument index of the inner call)
-  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  // D > 128: through the pipeline of blr_posterior_batched_*
+  if ((rc = ragged_one_by_one(h, B, offsets, [&](int64_t b, int64_t o, int64_t n) {
+         return posterior_batched<T>(h, BLR_MEM_DEVICE, layout, 1, D, n, a.X + (f.colv ? o * ldx : o), ldx, 0, a.y + o, 0, noise_kind,
+                                     diag ? a.s + o : a.s + b * strides, 0, prior_kind, a.mw + b * stridemw, 0, a.Lw + b * strideLw, ldl, 0,
+                                     a.mw_post ? a.mw_post + b * stride_mwpost : (T*)nullptr, 0, a.T_post ? a.T_post + b * strideT : (T*)nullptr,
+                                     ldt, 0, a.Lw_post ? a.Lw_post + b * strideLp : (T*)nullptr, ldlp, 0,
+                                     a.logpdf ? a.logpdf + b : (double*)nullptr, a.info + b);
+       })))
+    return rc;
   return io.finish();
 }
 
 // ---- ragged marginals and leave-one-out (blr_marg_ragged.hpp, blr_ragged_items.hpp) ---------------------------------
-// offsets: what blr_posterior_ragged_* asks of it
-inline int ragged_offsets_check(blr_handle* h, int64_t B, const int64_t* offsets) {
-  if (B > 0 && !offsets) return bad_arg(h, 6, "offsets is NULL (a host array of B + 1 entries)");
-  if (B > 0 && offsets[0] < 0) return bad_arg(h, 6, "offsets[0] < 0");
-  for (int64_t b = 0; b < B; ++b) {
-    if (offsets[b + 1] < offsets[b]) return bad_arg(h, 6, "offsets must be non-decreasing");
-    if (offsets[b + 1] - offsets[b] > (1 << 30)) return bad_arg(h, 6, "a regressor with more than 2^30 observations");
-  }
+// The plan of a call, and offsets and its items in the handle's metadata buffer (K14's: the entry points never share a call)
+template <typename T>
+int marg_ragged_plan(blr_handle* h, const int64_t* offsets, int64_t B, RaggedPlan& p, MargRaggedArgs<T>& a) {
+  plan_ragged(offsets, B, h->cus, (int)sizeof(T), h->opt, p);
+  const char* dev[2];
+  if (const int rc = ragged_meta_upload(h, {{offsets, ragged_table_bytes(B)}, {p.items.data(), p.items.size() * sizeof(RaggedItem)}}, dev)) return rc;
+  a.offsets = reinterpret_cast<const int64_t*>(dev[0]);
+  a.items = reinterpret_cast<const RaggedItem*>(dev[1]);
   return 0;
 }
 
-// offsets and the plan's items go to the handle's metadata buffer (K14's: the two entry points never share a call).  The copy is
-// ordered behind the work in flight and the stream is drained: the host image belongs to the handle and the next call rewrites it.
-inline int ragged_items_upload(blr_handle* h, const int64_t* offsets, int64_t B, const RaggedPlan& p, const int64_t** off_dev,
-                               const RaggedItem** items_dev) {
-  const size_t items_at = (size_t)(B + 1) * sizeof(int64_t), bytes = items_at + p.items.size() * sizeof(RaggedItem);
-  h->ragged_host.resize((bytes + 7) / 8);
-  std::memcpy(h->ragged_host.data(), offsets, items_at);
-  if (!p.items.empty()) std::memcpy(reinterpret_cast<char*>(h->ragged_host.data()) + items_at, p.items.data(), p.items.size() * sizeof(RaggedItem));
-  if (const int rc = h->ragged_meta.reserve(h, bytes, (size_t)1 << 16)) return rc;
-  HIP_TRY(h, hipMemcpyAsync(h->ragged_meta.p, h->ragged_host.data(), bytes, hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(h, hipStreamSynchronize(h->stream));
-  *off_dev = reinterpret_cast<const int64_t*>(h->ragged_meta.p);
-  *items_dev = reinterpret_cast<const RaggedItem*>(h->ragged_meta.p + items_at);
+// ---- what the packed held-out entry points share behind their own argument checks (blr_loo_ragged_*, blr_kfold_ragged_*): the
+// counterparts of heldout_status, LogpdfSpill and heldout_totals ----
+// Status of every state, the noise scan on its slice (off_dev: the uploaded offsets): loo_ragged_check_kernel, at most 65535
+// regressors per launch (grid.x).  Returns that chunk; the caller asks for the launches' error.
+template <typename T>
+int64_t heldout_ragged_status(blr_handle* h, int64_t B, int64_t D, const T* Tf, int64_t ldt, int64_t strideT, const T* s, int64_t strides,
+                              int noise_kind, const int64_t* off_dev, int32_t* info) {
+  const int64_t ychunk = h->cap_chunk(65535);
+  for (int64_t b0 = 0; b0 < B; b0 += ychunk)
+    hipLaunchKernelGGL(loo_ragged_check_kernel<T>, dim3((unsigned)std::min<int64_t>(ychunk, B - b0)), dim3(kThreads), 0, h->stream, Tf + b0 * strideT,
+                       ldt, strideT, (int)D, noise_kind == BLR_NOISE_DIAGONAL ? s : s + b0 * strides, strides, noise_kind, off_dev + b0, info + b0);
+  return ychunk;
+}
+// The totals need the log densities somewhere: wanted without them, n doubles go to the held-out workspace behind the `front` bytes
+// the caller uses of it, packed as the output is (first: the index of its first entry).  Reserves front + the spill + pad bytes, if
+// any of the first two.
+inline int heldout_ragged_spill(blr_handle* h, const double* total, size_t front, size_t n, int64_t first, size_t pad, double** ll) {
+  const bool on = total && !*ll;
+  if (!front && !on) return 0;
+  if (const int rc = h->loo_ws.reserve(h, front + (on ? n * sizeof(double) : 0) + pad)) return rc;
+  if (on) *ll = reinterpret_cast<double*>(h->loo_ws.p + front) - first;
   return 0;
+}
+// Totals of every regressor over its log densities ll[ll_off[b] .. ll_off[b + 1]) (ll_off: a device table), in the chunks of the status
+inline void heldout_ragged_totals(blr_handle* h, int64_t B, int64_t ychunk, const double* ll, const int64_t* ll_off, double* total, const int32_t* info) {
+  for (int64_t b0 = 0; b0 < B; b0 += ychunk)
+    hipLaunchKernelGGL(loo_ragged_total_kernel, dim3((unsigned)std::min<int64_t>(ychunk, B - b0)), dim3(kThreads), 0, h->stream, ll, ll_off + b0,
+                       total + b0, info + b0);
 }
 
 // The product stream takes D = 128 with a factor when the variance is wanted: RowVecs, or ColVecs whose X and ldx are multiples of 16
@@ -3578,9 +3656,7 @@ int marg_ragged_launch(blr_handle* h, MargRaggedArgs<T> a, const RaggedPlan& p, 
   int rc;
   const bool images = gemm && (LOO || a.var);
   if (gemm) {
-    int64_t nb_max = 1;
-    for (const RaggedChunk& c : p.chunks) nb_max = std::max(nb_max, c.nb);
-    if (images && (rc = MargImages<T>::reserve(h, nb_max))) return rc;
+    if (images && (rc = MargImages<T>::reserve(h, std::max<int64_t>(1, p.max_nb)))) return rc;
     if ((rc = set_lds_once(h, gk, (size_t)G::LDS_BYTES))) return rc;
   } else if ((rc = set_lds_once(h, rk, (size_t)RC::LDS_FACTOR))) {
     return rc;
@@ -3607,17 +3683,9 @@ template <typename T>
 int marginals_ragged(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, const int64_t* offsets, const T* X, int64_t ldx,
                      int noise_kind, const T* s, int64_t strides, int prior_kind, const T* mw, int64_t stridemw, const T* Lw, int64_t ldl,
                      int64_t strideLw, T* mean, T* var, int32_t* info) {
-  // (the argument checks come before the handle's: they need no device)
-  if (h) h->err.clear();
-  if (memspace != BLR_MEM_HOST && memspace != BLR_MEM_DEVICE) return bad_arg(h, 2, "memspace");
-  if (layout != BLR_LAYOUT_COLVECS && layout != BLR_LAYOUT_ROWVECS) return bad_arg(h, 3, "unknown layout (reference :26-31)");
-  if (B < 0 || B > (1 << 30)) return bad_arg(h, 4, "B out of range (0..2^30)");
-  if (D < 1 || D > kMaxLargeD) return bad_arg(h, 5, "D out of range (1..8192)");
-  if (const int rc = ragged_offsets_check(h, B, offsets)) return rc;
-  const int64_t total = B > 0 ? offsets[B] : 0;  // columns of the packed arrays
-  const bool any = B > 0 && offsets[B] > offsets[0];
-  if (any && !X) return bad_arg(h, 7, "X is NULL");
-  if (layout == BLR_LAYOUT_COLVECS ? ldx < D : ldx < std::max<int64_t>(total, 1)) return bad_arg(h, 8, "ldx too small");
+  RaggedFront f;
+  if (const int rc = ragged_front(h, f, memspace, layout, B, D, offsets, X, ldx, noise_kind, strides)) return rc;
+  const bool any = f.any, colv = f.colv, diag = f.diag;
   if (noise_kind != BLR_NOISE_ISOTROPIC && noise_kind != BLR_NOISE_DIAGONAL)
     return bad_arg(h, 9, "noise_kind (isotropic or diagonal; dense Sigma_y is not supported for unequal counts)");
   if (var && any && !s) return bad_arg(h, 10, "s is NULL");
@@ -3634,48 +3702,39 @@ int marginals_ragged(blr_handle* h, int memspace, int layout, int64_t B, int64_t
   if (!h) return -1;
   h->last_chunks = 1;  // (a route with a chunk loop counts its own)
   HIP_TRY(h, hipSetDevice(h->device));
-  const bool diag = noise_kind == BLR_NOISE_DIAGONAL;
-  const bool colv = layout == BLR_LAYOUT_COLVECS;
 
   CallIO io(h, memspace);
   MargRaggedArgs<T> a{};
   a.ldx = ldx; a.strides = strides; a.stridemw = stridemw; a.layout = layout; a.noise_kind = noise_kind; a.D = (int)D;
-  const size_t x_all = !any ? 0 : (colv ? mat_extent(D, total, ldx) : mat_extent(total, D, ldx));
   const size_t lw_one = prior_kind == BLR_PRIOR_DIAGONAL ? (size_t)D : mat_extent(D, D, ldl);
   const T* Lw_dev = nullptr;
   int32_t* info_dev = nullptr;
   int rc;
-  if ((rc = io.in(X, x_all, &a.X))) return rc;
-  if ((rc = io.in(var ? s : (const T*)nullptr, diag ? (any ? (size_t)total : 0) : extent(B, strides, 1), &a.s))) return rc;
+  if ((rc = io.in(X, f.x_all, &a.X))) return rc;
+  if ((rc = io.in(var ? s : (const T*)nullptr, f.s_all, &a.s))) return rc;
   if ((rc = io.in(mw, extent(B, stridemw, (size_t)D), &a.mw))) return rc;
   if ((rc = io.in(var ? Lw : (const T*)nullptr, extent(B, strideLw, lw_one), &Lw_dev))) return rc;
-  if ((rc = io.out(mean, any ? (size_t)total : 0, &a.mean))) return rc;
-  if ((rc = io.out(var, any ? (size_t)total : 0, &a.var))) return rc;
+  if ((rc = io.out(mean, f.n_all, &a.mean))) return rc;
+  if ((rc = io.out(var, f.n_all, &a.var))) return rc;
   if ((rc = io.out(info, (size_t)B, &info_dev))) return rc;
   if (!any || (!mean && !var)) {  // nothing per observation to write: the status of a call without a factorisation
     HIP_TRY(h, hipMemsetAsync(info_dev, 0, (size_t)B * sizeof(int32_t), h->stream));
     return io.finish();
   }
-  if (D > kMaxSmallD) {  // correct, not fast: one regressor after the other through blr_marginals_batched_*; the call synchronises
+  if (D > kMaxSmallD) {  // through blr_marginals_batched_*: an empty regressor keeps the status of a call without a factorisation
     HIP_TRY(h, hipMemsetAsync(info_dev, 0, (size_t)B * sizeof(int32_t), h->stream));
-    {
-      const AsyncScope drain(h, false);
-      for (int64_t b = 0; b < B && rc == 0; ++b) {
-        const int64_t o = offsets[b], n = offsets[b + 1] - o;
-        if (n == 0) continue;
-        rc = marginals_batched<T>(h, BLR_MEM_DEVICE, layout, 1, D, n, a.X + (colv ? o * ldx : o), ldx, 0, noise_kind,
-                                  a.s ? (diag ? a.s + o : a.s + b * strides) : (const T*)nullptr, 0, prior_kind, a.mw + b * stridemw, 0,
-                                  Lw_dev ? Lw_dev + b * strideLw : (const T*)nullptr, ldl, 0, a.mean ? a.mean + o : (T*)nullptr, 0,
-                                  a.var ? a.var + o : (T*)nullptr, 0, info_dev + b);
-      }
-    }
-    if (rc) return rc;
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if ((rc = ragged_one_by_one(h, B, offsets, [&](int64_t b, int64_t o, int64_t n) {
+           if (n == 0) return 0;
+           return marginals_batched<T>(h, BLR_MEM_DEVICE, layout, 1, D, n, a.X + (colv ? o * ldx : o), ldx, 0, noise_kind,
+                                       a.s ? (diag ? a.s + o : a.s + b * strides) : (const T*)nullptr, 0, prior_kind, a.mw + b * stridemw, 0,
+                                       Lw_dev ? Lw_dev + b * strideLw : (const T*)nullptr, ldl, 0, a.mean ? a.mean + o : (T*)nullptr, 0,
+                                       a.var ? a.var + o : (T*)nullptr, 0, info_dev + b);
+         })))
+      return rc;
     return io.finish();
   }
   RaggedPlan plan;
-  plan_ragged(offsets, B, h->cus, (int)sizeof(T), h->opt, plan);
-  if ((rc = ragged_items_upload(h, offsets, B, plan, &a.offsets, &a.items))) return rc;
+  if ((rc = marg_ragged_plan<T>(h, offsets, B, plan, a))) return rc;
   // a dense prior is factorised once per regressor; its status is the call's
   int32_t* chol_info = nullptr;
   int kind = prior_kind;
@@ -3699,17 +3758,9 @@ template <typename T>
 int loo_ragged(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, const int64_t* offsets, const T* X, int64_t ldx, const T* y,
                int noise_kind, const T* s, int64_t strides, const T* mw, int64_t stridemw, const T* Tf, int64_t ldt, int64_t strideT,
                T* loo_mean, T* loo_var, double* loo_logpdf, double* loo_total, int32_t* info) {
-  // (the argument checks come before the handle's: they need no device)
-  if (h) h->err.clear();
-  if (memspace != BLR_MEM_HOST && memspace != BLR_MEM_DEVICE) return bad_arg(h, 2, "memspace");
-  if (layout != BLR_LAYOUT_COLVECS && layout != BLR_LAYOUT_ROWVECS) return bad_arg(h, 3, "unknown layout (reference :26-31)");
-  if (B < 0 || B > (1 << 30)) return bad_arg(h, 4, "B out of range (0..2^30)");
-  if (D < 1 || D > kMaxLargeD) return bad_arg(h, 5, "D out of range (1..8192)");
-  if (const int rc = ragged_offsets_check(h, B, offsets)) return rc;
-  const int64_t total = B > 0 ? offsets[B] : 0;
-  const bool any = B > 0 && offsets[B] > offsets[0];
-  if (any && !X) return bad_arg(h, 7, "X is NULL");
-  if (layout == BLR_LAYOUT_COLVECS ? ldx < D : ldx < std::max<int64_t>(total, 1)) return bad_arg(h, 8, "ldx too small");
+  RaggedFront f;
+  if (const int rc = ragged_front(h, f, memspace, layout, B, D, offsets, X, ldx, noise_kind, strides)) return rc;
+  const bool any = f.any, colv = f.colv, diag = f.diag;
   if (any && !y) return bad_arg(h, 9, "y is NULL (reference :74 length check)");
   if (noise_kind != BLR_NOISE_ISOTROPIC && noise_kind != BLR_NOISE_DIAGONAL)
     return bad_arg(h, 10, "noise_kind (dense noise has no single-observation LOO: that is a block LOO)");
@@ -3725,21 +3776,18 @@ int loo_ragged(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, co
   if (!h) return -1;
   h->last_chunks = 1;  // (a route with a chunk loop counts its own)
   HIP_TRY(h, hipSetDevice(h->device));
-  const bool diag = noise_kind == BLR_NOISE_DIAGONAL;
-  const bool colv = layout == BLR_LAYOUT_COLVECS;
 
   CallIO io(h, memspace);
   MargRaggedArgs<T> a{};
   a.ldx = ldx; a.strides = strides; a.stridemw = stridemw; a.layout = layout; a.noise_kind = noise_kind; a.D = (int)D;
   a.prior_kind = BLR_PRIOR_UPPER_FACTOR; a.ldu = ldt; a.strideU = strideT;
-  const size_t x_all = !any ? 0 : (colv ? mat_extent(D, total, ldx) : mat_extent(total, D, ldx));
-  const size_t n_all = any ? (size_t)total : 0;
+  const size_t n_all = f.n_all;
   double* total_dev = nullptr;
   int32_t* info_dev = nullptr;
   int rc;
-  if ((rc = io.in(X, x_all, &a.X))) return rc;
+  if ((rc = io.in(X, f.x_all, &a.X))) return rc;
   if ((rc = io.in(y, n_all, &a.y))) return rc;
-  if ((rc = io.in(s, diag ? n_all : (any ? extent(B, strides, 1) : 0), &a.s))) return rc;
+  if ((rc = io.in(s, any ? f.s_all : 0, &a.s))) return rc;
   if ((rc = io.in(mw, extent(B, stridemw, (size_t)D), &a.mw))) return rc;
   if ((rc = io.in(Tf, extent(B, strideT, mat_extent(D, D, ldt)), &a.U))) return rc;
   if ((rc = io.out(loo_mean, n_all, &a.lm))) return rc;
@@ -3748,45 +3796,29 @@ int loo_ragged(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, co
   if ((rc = io.out(loo_total, (size_t)B, &total_dev))) return rc;
   if ((rc = io.out(info, (size_t)B, &info_dev))) return rc;
   if (!a.s) a.s = a.mw;  // (no observation at all: never dereferenced, but a valid pointer)
-  if (D > kMaxSmallD) {  // correct, not fast: one regressor after the other through blr_loo_batched_*; the call synchronises
-    {
-      const AsyncScope drain(h, false);
-      for (int64_t b = 0; b < B && rc == 0; ++b) {
-        const int64_t o = offsets[b], n = offsets[b + 1] - o;
-        rc = loo_batched<T>(h, BLR_MEM_DEVICE, layout, 1, D, n, a.X ? a.X + (colv ? o * ldx : o) : (const T*)nullptr, ldx, 0,
-                            a.y ? a.y + o : (const T*)nullptr, 0, noise_kind, diag ? a.s + o : a.s + b * strides, 0, a.mw + b * stridemw, 0,
-                            a.U + b * strideT, ldt, 0, a.lm ? a.lm + o : (T*)nullptr, 0, a.lv ? a.lv + o : (T*)nullptr, 0,
-                            a.ll ? a.ll + o : (double*)nullptr, 0, total_dev ? total_dev + b : (double*)nullptr, info_dev + b);
-      }
-    }
-    if (rc) return rc;
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
+  if (D > kMaxSmallD) {  // through blr_loo_batched_*
+    if ((rc = ragged_one_by_one(h, B, offsets, [&](int64_t b, int64_t o, int64_t n) {
+           return loo_batched<T>(h, BLR_MEM_DEVICE, layout, 1, D, n, a.X ? a.X + (colv ? o * ldx : o) : (const T*)nullptr, ldx, 0,
+                                 a.y ? a.y + o : (const T*)nullptr, 0, noise_kind, diag ? a.s + o : a.s + b * strides, 0, a.mw + b * stridemw, 0,
+                                 a.U + b * strideT, ldt, 0, a.lm ? a.lm + o : (T*)nullptr, 0, a.lv ? a.lv + o : (T*)nullptr, 0,
+                                 a.ll ? a.ll + o : (double*)nullptr, 0, total_dev ? total_dev + b : (double*)nullptr, info_dev + b);
+         })))
+      return rc;
     return io.finish();
   }
   if ((rc = ensure_stats(h))) return rc;
   a.degenerate = h->stats_dev + 3;
   a.info = info_dev;
   RaggedPlan plan;
-  plan_ragged(offsets, B, h->cus, (int)sizeof(T), h->opt, plan);
-  if ((rc = ragged_items_upload(h, offsets, B, plan, &a.offsets, &a.items))) return rc;
-  // status of every state, the noise scan on its slice (grid.x: at most 65535 regressors per launch)
-  const int64_t ychunk = h->cap_chunk(65535);
-  for (int64_t b0 = 0; b0 < B; b0 += ychunk)
-    hipLaunchKernelGGL(loo_ragged_check_kernel<T>, dim3((unsigned)std::min<int64_t>(ychunk, B - b0)), dim3(kThreads), 0, h->stream, a.U + b0 * strideT,
-                       ldt, strideT, (int)D, diag ? a.s : a.s + b0 * strides, strides, noise_kind, a.offsets + b0, info_dev + b0);
+  if ((rc = marg_ragged_plan<T>(h, offsets, B, plan, a))) return rc;
+  const int64_t ychunk = heldout_ragged_status<T>(h, B, D, a.U, ldt, strideT, a.s, strides, noise_kind, a.offsets, info_dev);
   HIP_TRY(h, hipGetLastError());
-  // the totals need the log densities somewhere: wanted without them, they go to workspace, packed as the outputs are
-  if (total_dev && !a.ll) {
-    if ((rc = h->loo_ws.reserve(h, (n_all + 1) * sizeof(double)))) return rc;
-    a.ll = reinterpret_cast<double*>(h->loo_ws.p) - offsets[0];
-  }
+  if ((rc = heldout_ragged_spill(h, total_dev, 0, n_all, offsets[0], sizeof(double), &a.ll))) return rc;
   if (any && (a.lm || a.lv || a.ll)) {
     const bool gemm = marg_ragged_gemm_takes<T>(h, layout, D, X, ldx) && marg_ragged_gemm_takes<T>(h, layout, D, a.X, ldx);
     if ((rc = marg_ragged_launch<T, true>(h, a, plan, gemm))) return rc;
   }
-  for (int64_t b0 = 0; total_dev && b0 < B; b0 += ychunk)
-    hipLaunchKernelGGL(loo_ragged_total_kernel, dim3((unsigned)std::min<int64_t>(ychunk, B - b0)), dim3(kThreads), 0, h->stream, (const double*)a.ll,
-                       a.offsets + b0, total_dev + b0, (const int32_t*)info_dev + b0);
+  if (total_dev) heldout_ragged_totals(h, B, ychunk, a.ll, a.offsets, total_dev, info_dev);
   HIP_TRY(h, hipGetLastError());
   return io.finish();
 }
@@ -4454,21 +4486,15 @@ template <typename T>
 int kfold_ragged(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, const int64_t* offsets, int64_t F, const T* X, int64_t ldx,
                  const T* y, int noise_kind, const T* s, int64_t strides, const T* mw, int64_t stridemw, const T* Tf, int64_t ldt,
                  int64_t strideT, T* kf_mean, T* kf_var, double* kf_logpdf, double* kf_total, int32_t* info) {
-  // (the argument checks come before the handle's: they need no device)
-  if (h) h->err.clear();
-  if (memspace != BLR_MEM_HOST && memspace != BLR_MEM_DEVICE) return bad_arg(h, 2, "memspace");
-  if (layout != BLR_LAYOUT_COLVECS && layout != BLR_LAYOUT_ROWVECS) return bad_arg(h, 3, "unknown layout (reference :26-31)");
-  if (B < 0 || B > (1 << 30)) return bad_arg(h, 4, "B out of range (0..2^30)");
-  if (D < 1 || D > kMaxLargeD) return bad_arg(h, 5, "D out of range (1..8192)");
-  if (const int rc = ragged_offsets_check(h, B, offsets)) return rc;
-  for (int64_t b = 0; D > kMaxSmallD && b < B; ++b)
-    if (offsets[b + 1] - offsets[b] > kMaxDenseN)
-      return bad_arg(h, 6, "a regressor with more than 16384 observations at D > 128: the route goes through an N x N covariance");
-  if (F < 1 || F > kFoldMax) return bad_arg(h, 7, "F out of range (1..64)");
-  const int64_t total = B > 0 ? offsets[B] : 0;
-  const bool any = B > 0 && offsets[B] > offsets[0];
-  if (any && !X) return bad_arg(h, 8, "X is NULL");
-  if (layout == BLR_LAYOUT_COLVECS ? ldx < D : ldx < std::max<int64_t>(total, 1)) return bad_arg(h, 9, "ldx too small");
+  RaggedFront f;
+  const auto mid = [&] {  // (F sits at position 7: X and ldx one later than in the other entry points)
+    for (int64_t b = 0; D > kMaxSmallD && b < B; ++b)
+      if (offsets[b + 1] - offsets[b] > kMaxDenseN)
+        return bad_arg(h, 6, "a regressor with more than 16384 observations at D > 128: the route goes through an N x N covariance");
+    return F < 1 || F > kFoldMax ? bad_arg(h, 7, "F out of range (1..64)") : 0;
+  };
+  if (const int rc = ragged_front(h, f, memspace, layout, B, D, offsets, X, ldx, noise_kind, strides, 8, mid)) return rc;
+  const bool any = f.any, colv = f.colv, diag = f.diag;
   if (any && !y) return bad_arg(h, 10, "y is NULL (reference :74 length check)");
   if (noise_kind != BLR_NOISE_ISOTROPIC && noise_kind != BLR_NOISE_DIAGONAL)
     return bad_arg(h, 11, "noise_kind (dense noise couples the folds: isotropic or diagonal only)");
@@ -4484,8 +4510,6 @@ int kfold_ragged(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, 
   if (!h) return -1;
   h->last_chunks = 1;  // (a route with a chunk loop counts its own)
   HIP_TRY(h, hipSetDevice(h->device));
-  const bool diag = noise_kind == BLR_NOISE_DIAGONAL;
-  const bool colv = layout == BLR_LAYOUT_COLVECS;
 
   KfoldRaggedPlan plan;  // (D > 128: only its fold offsets are used)
   plan_kfold_ragged(offsets, B, F, (int)std::min<int64_t>(D, kMaxSmallD), h->cus, (int)sizeof(T), h->opt, plan);
@@ -4494,15 +4518,14 @@ int kfold_ragged(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, 
   CallIO io(h, memspace);
   KfoldRaggedArgs<T> a{};
   a.ldx = ldx; a.strides = strides; a.noise_kind = noise_kind; a.stridemw = stridemw; a.D = (int)D; a.F = (int)F;
-  const size_t x_all = !any ? 0 : (colv ? mat_extent(D, total, ldx) : mat_extent(total, D, ldx));
-  const size_t n_all = any ? (size_t)total : 0, nf_all = (size_t)fo[(size_t)B];
+  const size_t n_all = f.n_all, nf_all = (size_t)fo[(size_t)B];
   const T* T_d = nullptr;
   double* total_dev = nullptr;
   int32_t* info_dev = nullptr;
   int rc;
-  if ((rc = io.in(X, x_all, &a.X))) return rc;
+  if ((rc = io.in(X, f.x_all, &a.X))) return rc;
   if ((rc = io.in(y, n_all, &a.y))) return rc;
-  if ((rc = io.in(s, diag ? n_all : (any ? extent(B, strides, 1) : 0), &a.s))) return rc;
+  if ((rc = io.in(s, any ? f.s_all : 0, &a.s))) return rc;
   if ((rc = io.in(mw, extent(B, stridemw, (size_t)D), &a.mw))) return rc;
   if ((rc = io.in(Tf, extent(B, strideT, mat_extent(D, D, ldt)), &T_d))) return rc;
   if ((rc = io.out(kf_mean, n_all, &a.km))) return rc;
@@ -4511,52 +4534,35 @@ int kfold_ragged(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, 
   if ((rc = io.out(kf_total, (size_t)B, &total_dev))) return rc;
   if ((rc = io.out(info, (size_t)B, &info_dev))) return rc;
   if (!a.s) a.s = a.mw;  // (no observation at all: never dereferenced, but a valid pointer)
-  if (D > kMaxSmallD) {  // correct, not fast: one regressor after the other through blr_kfold_batched_*; the call synchronises
-    {
-      const AsyncScope drain(h, false);
-      for (int64_t b = 0; b < B && rc == 0; ++b) {
-        const int64_t o = offsets[b], n = offsets[b + 1] - o;
-        rc = kfold_batched<T>(h, BLR_MEM_DEVICE, layout, 1, D, n, F, a.X ? a.X + (colv ? o * ldx : o) : (const T*)nullptr, ldx, 0,
-                              a.y ? a.y + o : (const T*)nullptr, 0, noise_kind, diag ? a.s + o : a.s + b * strides, 0, a.mw + b * stridemw, 0,
-                              T_d + b * strideT, ldt, 0, a.km ? a.km + o : (T*)nullptr, 0, a.kv ? a.kv + o : (T*)nullptr, 0,
-                              a.kl ? a.kl + fo[(size_t)b] : (double*)nullptr, 0, total_dev ? total_dev + b : (double*)nullptr, info_dev + b);
-      }
-    }
-    if (rc) return rc;
+  if (D > kMaxSmallD) {  // through blr_kfold_batched_*
+    if ((rc = ragged_one_by_one(h, B, offsets, [&](int64_t b, int64_t o, int64_t n) {
+           return kfold_batched<T>(h, BLR_MEM_DEVICE, layout, 1, D, n, F, a.X ? a.X + (colv ? o * ldx : o) : (const T*)nullptr, ldx, 0,
+                                   a.y ? a.y + o : (const T*)nullptr, 0, noise_kind, diag ? a.s + o : a.s + b * strides, 0, a.mw + b * stridemw, 0,
+                                   T_d + b * strideT, ldt, 0, a.km ? a.km + o : (T*)nullptr, 0, a.kv ? a.kv + o : (T*)nullptr, 0,
+                                   a.kl ? a.kl + fo[(size_t)b] : (double*)nullptr, 0, total_dev ? total_dev + b : (double*)nullptr, info_dev + b);
+         })))
+      return rc;
     h->last_chunks = 1;
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
     return io.finish();
   }
   if ((rc = ensure_stats(h))) return rc;
   a.degenerate = h->stats_dev + 4;
   a.info = info_dev;
 
-  // offsets, the two tables and the items go to the handle's metadata buffer; the copy is ordered behind the work in flight and the
-  // stream is drained: the host image belongs to the handle and the next call rewrites it (ragged_items_upload)
+  // offsets, the two tables and the items
   {
-    const size_t tbl = (size_t)(B + 1) * sizeof(int64_t), items_at = 3 * tbl, bytes = items_at + plan.items.size() * sizeof(RaggedItem);
-    h->ragged_host.resize((bytes + 7) / 8);
-    char* const img = reinterpret_cast<char*>(h->ragged_host.data());
-    std::memcpy(img, offsets, tbl);
-    std::memcpy(img + tbl, plan.pack_offsets.data(), tbl);
-    std::memcpy(img + 2 * tbl, fo.data(), tbl);
-    if (!plan.items.empty()) std::memcpy(img + items_at, plan.items.data(), plan.items.size() * sizeof(RaggedItem));
-    if ((rc = h->ragged_meta.reserve(h, bytes, (size_t)1 << 16))) return rc;
-    HIP_TRY(h, hipMemcpyAsync(h->ragged_meta.p, img, bytes, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    a.offsets = reinterpret_cast<const int64_t*>(h->ragged_meta.p);
-    a.pack_offsets = reinterpret_cast<const int64_t*>(h->ragged_meta.p + tbl);
-    a.fold_offsets = reinterpret_cast<const int64_t*>(h->ragged_meta.p + 2 * tbl);
-    a.items = reinterpret_cast<const RaggedItem*>(h->ragged_meta.p + items_at);
+    const size_t tbl = ragged_table_bytes(B);
+    const char* dev[4];
+    if ((rc = ragged_meta_upload(h, {{offsets, tbl}, {plan.pack_offsets.data(), tbl}, {fo.data(), tbl},
+                                     {plan.items.data(), plan.items.size() * sizeof(RaggedItem)}}, dev)))
+      return rc;
+    a.offsets = reinterpret_cast<const int64_t*>(dev[0]);
+    a.pack_offsets = reinterpret_cast<const int64_t*>(dev[1]);
+    a.fold_offsets = reinterpret_cast<const int64_t*>(dev[2]);
+    a.items = reinterpret_cast<const RaggedItem*>(dev[3]);
   }
-  // status of every state, the noise scan on its slice (grid.x: at most 65535 regressors per launch)
-  const int64_t ychunk = h->cap_chunk(65535);
-  for (int64_t b0 = 0; b0 < B; b0 += ychunk)
-    hipLaunchKernelGGL(loo_ragged_check_kernel<T>, dim3((unsigned)std::min<int64_t>(ychunk, B - b0)), dim3(kThreads), 0, h->stream, T_d + b0 * strideT,
-                       ldt, strideT, (int)D, diag ? a.s : a.s + b0 * strides, strides, noise_kind, a.offsets + b0, info_dev + b0);
+  const int64_t ychunk = heldout_ragged_status<T>(h, B, D, T_d, ldt, strideT, a.s, strides, noise_kind, a.offsets, info_dev);
   HIP_TRY(h, hipGetLastError());
-  // the totals need the log densities somewhere: wanted without them, they go to workspace, packed as the output is
-  const bool spill = total_dev && !a.kl;
   const bool folds = any && (a.km || a.kv || a.kl || total_dev);
   if (folds) {
     const int DP = 16 * (((int)D + 15) / 16);
@@ -4567,10 +4573,9 @@ int kfold_ragged(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, 
     if ((rc = set_lds_once(h, kfold_ragged_kernel<T>, lds_k))) return rc;
     if ((rc = MargImages<T>::reserve(h, plan.max_nb))) return rc;
     if ((rc = h->cov_ws.reserve(h, (size_t)plan.max_rows * DP * sizeof(T) + 256))) return rc;
-    if ((rc = h->loo_ws.reserve(h, m_bytes + (spill ? nf_all * sizeof(double) : 0) + 256))) return rc;
+    if ((rc = heldout_ragged_spill(h, total_dev, m_bytes, nf_all, 0, 256, &a.kl))) return rc;  // (m in front of the spill)
     a.Z = reinterpret_cast<T*>(h->cov_ws.p);
     a.m = reinterpret_cast<T*>(h->loo_ws.p);
-    if (spill) a.kl = reinterpret_cast<double*>(h->loo_ws.p + m_bytes);
     const RaggedItem* const items = a.items;
     for (const RaggedChunk& c : plan.chunks) {
       if (c.nitems == 0) continue;  // (no observation in the chunk)
@@ -4586,9 +4591,7 @@ int kfold_ragged(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, 
     h->route_i8_B = 0;
   }
   h->last_chunks = std::max<int64_t>(1, plan.last_chunks);
-  for (int64_t b0 = 0; total_dev && b0 < B; b0 += ychunk)
-    hipLaunchKernelGGL(loo_ragged_total_kernel, dim3((unsigned)std::min<int64_t>(ychunk, B - b0)), dim3(kThreads), 0, h->stream, (const double*)a.kl,
-                       a.fold_offsets + b0, total_dev + b0, (const int32_t*)info_dev + b0);
+  if (total_dev) heldout_ragged_totals(h, B, ychunk, a.kl, a.fold_offsets, total_dev, info_dev);
   HIP_TRY(h, hipGetLastError());
   return io.finish();
 }

@@ -10,6 +10,7 @@
 //                        packed as the observations are) stay within 256 MiB -- never fewer than one regressor -- on top of the
 //                        bounds of blr_ragged_items.hpp (65535 regressors, 256 MiB of images, option MAX_CHUNK);
 //   items                the whitening pass's work items of every chunk: plan_ragged's (the same W, the same cut).
+// plan_kfold_ragged fills the two tables and leaves chunks and items to plan_ragged with the bound on a chunk's rows.
 #pragma once
 
 #include "blr_ragged_items.hpp"
@@ -19,13 +20,8 @@ namespace blr {
 constexpr int kFoldRaggedMaxF = 64;                      // = kFoldMax (asserted in blr_kfold_ragged.hpp)
 constexpr int64_t kFoldRaggedZBytes = (int64_t)256 << 20;  // rows of Z of a chunk
 
-struct KfoldRaggedPlan {
-  int64_t W = 0;                   // observations per whitening item
-  std::vector<RaggedChunk> chunks;
-  std::vector<RaggedItem> items;   // regressor-major, tiles ascending
+struct KfoldRaggedPlan : RaggedPlan {  // W, chunks, items: the whitening pass's
   std::vector<int64_t> pack_offsets, fold_offsets;  // [B + 1]
-  int64_t max_rows = 0, max_nb = 0;  // the most observations / regressors of any chunk: what the workspace is sized for
-  int64_t last_chunks = 0;
 };
 
 inline int64_t kfold_ragged_folds(int64_t n, int64_t F) { return (n + F - 1) / F; }
@@ -39,36 +35,13 @@ inline void kfold_ragged_fold_offsets(const int64_t* offsets, int64_t B, int64_t
 
 // offsets: B + 1 entries, non-decreasing, every count <= 2^30; 1 <= F <= 64; 1 <= D <= 128 (the entry points have checked)
 inline void plan_kfold_ragged(const int64_t* offsets, int64_t B, int64_t F, int D, int cus, int elem, const BlrOptions& opt, KfoldRaggedPlan& p) {
-  p.W = ragged_item_size(offsets, B, cus, opt);
-  p.chunks.clear();
-  p.items.clear();
   p.pack_offsets.assign((size_t)B + 1, 0);
   p.fold_offsets.assign((size_t)B + 1, 0);
-  p.max_rows = p.max_nb = 0;
   const int64_t pr = kfold_ragged_pack_rows(F);
   kfold_ragged_fold_offsets(offsets, B, F, p.fold_offsets.data());
   for (int64_t b = 0; b < B; ++b) p.pack_offsets[(size_t)b + 1] = p.pack_offsets[(size_t)b] + (offsets[b + 1] - offsets[b] + pr - 1) / pr;
-  const int64_t most = ragged_chunk_size(B, elem, opt);
-  const int64_t row_bytes = (int64_t)16 * ((D + 15) / 16) * elem, max_rows = kFoldRaggedZBytes / row_bytes;
-  const int64_t wt = p.W / kRaggedTile;  // tiles per full item
-  for (int64_t b0 = 0; b0 < B;) {
-    RaggedChunk c{b0, 0, (int64_t)p.items.size(), 0};
-    int64_t rows = 0;
-    for (int64_t b = b0; b < B && c.nb < most; ++b) {
-      const int64_t n = offsets[b + 1] - offsets[b];
-      if (c.nb > 0 && rows + n > max_rows) break;  // (never fewer than one regressor)
-      rows += n;
-      ++c.nb;
-      const int64_t nt = (n + kRaggedTile - 1) / kRaggedTile;
-      for (int64_t t = 0; t < nt; t += wt) p.items.push_back(RaggedItem{(int32_t)b, (int32_t)t, (int32_t)std::min<int64_t>(wt, nt - t)});
-    }
-    c.nitems = (int64_t)p.items.size() - c.item0;
-    p.chunks.push_back(c);
-    p.max_rows = std::max(p.max_rows, rows);
-    p.max_nb = std::max(p.max_nb, c.nb);
-    b0 += c.nb;
-  }
-  p.last_chunks = (int64_t)p.chunks.size();
+  const int64_t row_bytes = (int64_t)16 * ((D + 15) / 16) * elem;
+  plan_ragged(offsets, B, cus, elem, opt, p, kFoldRaggedZBytes / row_bytes);
 }
 
 }  // namespace blr

@@ -1,7 +1,8 @@
 // The work items of the ragged marginal stream and the ragged leave-one-out (blr_marginals_ragged_*, blr_loo_ragged_*):
 // from `offsets`, the CU count, the element size and the handle's options alone.  Host arithmetic only -- no HIP call and no
 // handle -- so the plan can be checked without a device (tools/ragged_items_dump.cpp, tests/test_marg_ragged_cpu.py).
-// marg_ragged_launch (blr_abi.hip) turns a plan into launches.
+// marg_ragged_plan (blr_abi.hip) uploads a plan's items, marg_ragged_launch turns it into launches.  plan_ragged is also the chunk walk
+// and the item cut of the ragged leave-fold-out predictives (blr_kfold_ragged_plan.hpp), which bound a chunk's observations as well.
 //
 // A regressor's observations are independent once its triangular inverse exists, so a long regressor is cut into items of at
 // most W observations and the items -- not the regressors -- are what workgroups take: one workgroup per item.  The bits of an
@@ -44,6 +45,7 @@ struct RaggedPlan {
   int64_t W = 0;  // observations per item
   std::vector<RaggedChunk> chunks;
   std::vector<RaggedItem> items;  // regressor-major, tiles ascending
+  int64_t max_rows = 0, max_nb = 0;  // the most observations / regressors of any chunk: what a per-chunk workspace is sized for
   int64_t last_chunks = 0;
 };
 
@@ -65,22 +67,31 @@ inline int64_t ragged_chunk_size(int64_t B, int elem, const BlrOptions& opt) {
   return std::max<int64_t>(chunk, 1);
 }
 
-// offsets: B + 1 entries, non-decreasing, every count <= 2^30 (the entry points have checked)
-inline void plan_ragged(const int64_t* offsets, int64_t B, int cus, int elem, const BlrOptions& opt, RaggedPlan& p) {
+// offsets: B + 1 entries, non-decreasing, every count <= 2^30 (the entry points have checked).  row_bound: the most observations of
+// a chunk (blr_kfold_ragged_plan.hpp: its rows of Z) -- a chunk never has fewer than one regressor
+inline void plan_ragged(const int64_t* offsets, int64_t B, int cus, int elem, const BlrOptions& opt, RaggedPlan& p, int64_t row_bound = INT64_MAX) {
   p.W = ragged_item_size(offsets, B, cus, opt);
   p.chunks.clear();
   p.items.clear();
-  const int64_t chunk = ragged_chunk_size(B, elem, opt);
+  p.max_rows = p.max_nb = 0;
+  const int64_t most = ragged_chunk_size(B, elem, opt);
   const int64_t wt = p.W / kRaggedTile;  // tiles per full item
-  for (int64_t b0 = 0; b0 < B; b0 += chunk) {
-    RaggedChunk c{b0, std::min<int64_t>(chunk, B - b0), (int64_t)p.items.size(), 0};
-    for (int64_t b = b0; b < b0 + c.nb; ++b) {
+  for (int64_t b0 = 0; b0 < B;) {
+    RaggedChunk c{b0, 0, (int64_t)p.items.size(), 0};
+    int64_t rows = 0;
+    for (int64_t b = b0; b < B && c.nb < most; ++b) {
       const int64_t n = offsets[b + 1] - offsets[b];
+      if (c.nb > 0 && n > row_bound - rows) break;
+      rows += n;
+      ++c.nb;
       const int64_t nt = (n + kRaggedTile - 1) / kRaggedTile;
       for (int64_t t = 0; t < nt; t += wt) p.items.push_back(RaggedItem{(int32_t)b, (int32_t)t, (int32_t)std::min<int64_t>(wt, nt - t)});
     }
     c.nitems = (int64_t)p.items.size() - c.item0;
     p.chunks.push_back(c);
+    p.max_rows = std::max(p.max_rows, rows);
+    p.max_nb = std::max(p.max_nb, c.nb);
+    b0 += c.nb;
   }
   p.last_chunks = (int64_t)p.chunks.size();
 }

@@ -713,6 +713,15 @@ def posterior_ragged(f, x, offsets, Sy, y):
     return [BayesianLinearRegressor(mw_post, _wrap_like(g.Lw, T, A)) for g, (_, mw_post, T, A) in zip(fs, res)]
 
 
+def _raise_first_failed(info):
+    """The first non-zero ``info[b]`` raises PosDefException(info[b]) with ``index`` = b."""
+    bad = np.flatnonzero(info)
+    if bad.size:
+        e = _abi.PosDefException(int(info[bad[0]]))
+        e.index = int(bad[0])
+        raise e
+
+
 def _marginals_ragged(f, x, offsets, Sy, want_mean, want_var):
     """The packed form behind mean_ragged / var_ragged / mean_and_var_ragged -> (mean or None, var or None), offsets[-1] long."""
     ops, _ = _ragged_operands(f, x, offsets, Sy if want_var else None, None)
@@ -725,11 +734,7 @@ def _marginals_ragged(f, x, offsets, Sy, want_mean, want_var):
     info = np.zeros(nb, dtype=np.int32)
     _handle().marginals_ragged(dtype, _abi.MEM_HOST, layout, nb, D, offsets, X, ldx, noise_kind, s, strides, prior_kind, mwb, stridemw,
                                Lb if want_var else None, ldl, strideLw, mean, var, info)
-    bad = np.flatnonzero(info)
-    if bad.size:
-        e = _abi.PosDefException(int(info[bad[0]]))
-        e.index = int(bad[0])
-        raise e
+    _raise_first_failed(info)
     return mean, var
 
 
@@ -752,6 +757,46 @@ def mean_and_var_ragged(f, x, offsets, Sy):
     return _marginals_ragged(f, x, offsets, Sy, True, True)
 
 
+def _heldout_ragged(ops, second, ll_offsets, result):
+    """What `loo_ragged` and `kfold_ragged` do with their operands: the data staged once, blr_posterior_ragged_* into device buffers
+    (mw', T), then ``second(h, head, tail)`` -- the held-out entry point on the same device inputs, ``head`` its arguments up to
+    offsets, ``tail`` those from X on -- and the results copied back.  Regressor b owns ``ll_offsets[b]:ll_offsets[b + 1]`` of the
+    log densities, ``ll_offsets[-1]`` in all; ``result``: LOO or KFold."""
+    dtype, offsets, nb, X, layout, ldx, D, y, s, noise_kind, strides, prior_kind, ldl, _, mwb, stridemw, Lb, strideLw = ops
+    h, item, total, n_ll = _handle(), np.dtype(dtype).itemsize, int(offsets[-1]), int(ll_offsets[-1])
+    temps = []
+
+    def dev(a):
+        temps.append(_DeviceBuffer.of(h, a))
+        return temps[-1].ptr
+
+    m, v = np.zeros(total, dtype=dtype), np.zeros(total, dtype=dtype)
+    lp, tot, info = np.zeros(n_ll, dtype=np.float64), np.zeros(nb, dtype=np.float64), np.zeros(nb, dtype=np.int32)
+    try:
+        dX, dy, ds = dev(X.reshape(-1, order="A")), dev(y), dev(s)
+        temps.extend([_DeviceBuffer(h, nb * D * item), _DeviceBuffer(h, nb * D * D * item)])
+        d_mwp, d_T = temps[-2].ptr, temps[-1].ptr
+        d_info = dev(info)
+        head = (dtype, _abi.MEM_DEVICE, layout, nb, D, offsets)
+        h.posterior_ragged(*head, dX, ldx, dy, noise_kind, ds, strides, prior_kind, dev(mwb), stridemw, dev(Lb), ldl, strideLw, d_mwp, D, d_T,
+                           max(D, 1), D * D, None, max(D, 1), D * D, None, d_info)
+        h.memcpy_d2h(info, d_info)
+        if not np.any(info):
+            outs = [_DeviceBuffer(h, max(total, 1) * item), _DeviceBuffer(h, max(total, 1) * item), _DeviceBuffer(h, max(n_ll, 1) * 8),
+                    _DeviceBuffer(h, nb * 8)]
+            temps.extend(outs)
+            d_m, d_v, d_ll, d_tot = (b.ptr for b in outs)
+            second(h, head, (dX, ldx, dy, noise_kind, ds, strides, d_mwp, D, d_T, max(D, 1), D * D, d_m, d_v, d_ll, d_tot, d_info))
+            for host, dptr in ((m, d_m), (v, d_v), (lp, d_ll), (tot, d_tot), (info, d_info)):
+                h.memcpy_d2h(host, dptr)
+    finally:
+        for b in temps:
+            b.free()
+    _raise_first_failed(info)
+    return [result(m[offsets[b]:offsets[b + 1]], v[offsets[b]:offsets[b + 1]], lp[ll_offsets[b]:ll_offsets[b + 1]], float(tot[b]))
+            for b in range(nb)]
+
+
 def loo_ragged(f, x, offsets, Sy, y):
     """[loo(f_b(x[offsets[b]:offsets[b+1]], Sy_b), y[...])] from packed arrays: the data staged once, blr_posterior_ragged_* into
     device buffers (mw', T), then blr_loo_ragged_* on the same device inputs -- `_loo_batch`'s pipeline for unequal counts.
@@ -760,42 +805,7 @@ def loo_ragged(f, x, offsets, Sy, y):
     ops, _ = _ragged_operands(f, x, offsets, Sy, y)
     if ops is None:
         return []
-    dtype, offsets, nb, X, layout, ldx, D, y, s, noise_kind, strides, prior_kind, ldl, _, mwb, stridemw, Lb, strideLw = ops
-    h, item, total = _handle(), np.dtype(dtype).itemsize, int(offsets[-1])
-    temps = []
-
-    def dev(a):
-        temps.append(_DeviceBuffer.of(h, a))
-        return temps[-1].ptr
-
-    m, v = np.zeros(total, dtype=dtype), np.zeros(total, dtype=dtype)
-    lp, tot, info = np.zeros(total, dtype=np.float64), np.zeros(nb, dtype=np.float64), np.zeros(nb, dtype=np.int32)
-    try:
-        dX, dy, ds = dev(X.reshape(-1, order="A")), dev(y), dev(s)
-        temps.extend([_DeviceBuffer(h, nb * D * item), _DeviceBuffer(h, nb * D * D * item)])
-        d_mwp, d_T = temps[-2].ptr, temps[-1].ptr
-        d_info = dev(info)
-        h.posterior_ragged(dtype, _abi.MEM_DEVICE, layout, nb, D, offsets, dX, ldx, dy, noise_kind, ds, strides, prior_kind, dev(mwb),
-                           stridemw, dev(Lb), ldl, strideLw, d_mwp, D, d_T, max(D, 1), D * D, None, max(D, 1), D * D, None, d_info)
-        h.memcpy_d2h(info, d_info)
-        if not np.any(info):
-            outs = [_DeviceBuffer(h, max(total, 1) * item), _DeviceBuffer(h, max(total, 1) * item), _DeviceBuffer(h, max(total, 1) * 8),
-                    _DeviceBuffer(h, nb * 8)]
-            temps.extend(outs)
-            d_lm, d_lv, d_ll, d_tot = (b.ptr for b in outs)
-            h.loo_ragged(dtype, _abi.MEM_DEVICE, layout, nb, D, offsets, dX, ldx, dy, noise_kind, ds, strides, d_mwp, D, d_T, max(D, 1),
-                         D * D, d_lm, d_lv, d_ll, d_tot, d_info)
-            for host, dptr in ((m, d_lm), (v, d_lv), (lp, d_ll), (tot, d_tot), (info, d_info)):
-                h.memcpy_d2h(host, dptr)
-    finally:
-        for b in temps:
-            b.free()
-    bad = np.flatnonzero(info)
-    if bad.size:
-        e = _abi.PosDefException(int(info[bad[0]]))
-        e.index = int(bad[0])
-        raise e
-    return [LOO(m[o0:o1], v[o0:o1], lp[o0:o1], float(tot[b])) for b, (o0, o1) in enumerate(zip(offsets[:-1], offsets[1:]))]
+    return _heldout_ragged(ops, lambda h, head, tail: h.loo_ragged(*head, *tail), ops[1], LOO)
 
 
 def kfold_ragged(f, x, offsets, Sy, y, fold_size):
@@ -811,48 +821,12 @@ def kfold_ragged(f, x, offsets, Sy, y, fold_size):
     ops, _ = _ragged_operands(f, x, offsets, Sy, y)
     if ops is None:
         return []
-    dtype, offsets, nb, X, layout, ldx, D, y, s, noise_kind, strides, prior_kind, ldl, _, mwb, stridemw, Lb, strideLw = ops
-    h, item, total = _handle(), np.dtype(dtype).itemsize, int(offsets[-1])
-    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    offsets, nb = ops[1], ops[2]
     fo = np.zeros(nb + 1, dtype=np.int64)
     rc = _abi.load_library().blr_kfold_ragged_fold_offsets(nb, _abi._ptr(offsets), F, _abi._ptr(fo))
     if rc != 0:
         raise ValueError(f"blr_kfold_ragged_fold_offsets: argument error {rc}")
-    nf = int(fo[-1])
-    temps = []
-
-    def dev(a):
-        temps.append(_DeviceBuffer.of(h, a))
-        return temps[-1].ptr
-
-    m, v = np.zeros(total, dtype=dtype), np.zeros(total, dtype=dtype)
-    lp, tot, info = np.zeros(nf, dtype=np.float64), np.zeros(nb, dtype=np.float64), np.zeros(nb, dtype=np.int32)
-    try:
-        dX, dy, ds = dev(X.reshape(-1, order="A")), dev(y), dev(s)
-        temps.extend([_DeviceBuffer(h, nb * D * item), _DeviceBuffer(h, nb * D * D * item)])
-        d_mwp, d_T = temps[-2].ptr, temps[-1].ptr
-        d_info = dev(info)
-        h.posterior_ragged(dtype, _abi.MEM_DEVICE, layout, nb, D, offsets, dX, ldx, dy, noise_kind, ds, strides, prior_kind, dev(mwb),
-                           stridemw, dev(Lb), ldl, strideLw, d_mwp, D, d_T, max(D, 1), D * D, None, max(D, 1), D * D, None, d_info)
-        h.memcpy_d2h(info, d_info)
-        if not np.any(info):
-            outs = [_DeviceBuffer(h, max(total, 1) * item), _DeviceBuffer(h, max(total, 1) * item), _DeviceBuffer(h, max(nf, 1) * 8),
-                    _DeviceBuffer(h, nb * 8)]
-            temps.extend(outs)
-            d_km, d_kv, d_kl, d_tot = (b.ptr for b in outs)
-            h.kfold_ragged(dtype, _abi.MEM_DEVICE, layout, nb, D, offsets, F, dX, ldx, dy, noise_kind, ds, strides, d_mwp, D, d_T, max(D, 1),
-                           D * D, d_km, d_kv, d_kl, d_tot, d_info)
-            for host, dptr in ((m, d_km), (v, d_kv), (lp, d_kl), (tot, d_tot), (info, d_info)):
-                h.memcpy_d2h(host, dptr)
-    finally:
-        for b in temps:
-            b.free()
-    bad = np.flatnonzero(info)
-    if bad.size:
-        e = _abi.PosDefException(int(info[bad[0]]))
-        e.index = int(bad[0])
-        raise e
-    return [KFold(m[o0:o1], v[o0:o1], lp[fo[b]:fo[b + 1]], float(tot[b])) for b, (o0, o1) in enumerate(zip(offsets[:-1], offsets[1:]))]
+    return _heldout_ragged(ops, lambda h, head, tail: h.kfold_ragged(*head, F, *tail), fo, KFold)
 
 
 def logpdf_map(fxs, ys):
