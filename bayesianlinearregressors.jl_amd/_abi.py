@@ -74,6 +74,8 @@ _SIGS = {
     "blr_logpdf_allgather_sum": ([_H, _i64, _vp, _vp, _vp], _int),
     "blr_allreduce_sum": ([_H, _int, _vp, _i64], _int),
     "blr_kfold_ragged_fold_offsets": ([_i64, _vp, _i64, _vp], _int),
+    "blr_kfold_large_ragged_fold_sizes": ([_i64, _vp, _i64, _vp], _int),
+    "blr_kfold_large_ragged_fold_offsets": ([_i64, _vp, _vp, _vp], _int),
 }
 for _suf in ("f64", "f32"):
     _SIGS[f"blr_posterior_batched_{_suf}"] = (
@@ -88,6 +90,8 @@ for _suf in ("f64", "f32"):
         [_H, _int, _int, _i64, _i64, _vp, _vp, _i64, _vp, _int, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp], _int)
     _SIGS[f"blr_kfold_ragged_{_suf}"] = (
         [_H, _int, _int, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _int, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp], _int)
+    _SIGS[f"blr_kfold_large_ragged_{_suf}"] = (
+        [_H, _int, _int, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _int, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp], _int)
     _SIGS[f"blr_posterior_multi_batched_{_suf}"] = (
         [_H, _int, _int, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _int, _vp, _i64, _int, _vp, _i64, _vp, _i64, _i64,
          _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _vp], _int)
@@ -374,6 +378,20 @@ class Handle:
             raise ValueError(f"offsets must have B + 1 = {B + 1} entries, got shape {offsets.shape}")
         return self.check(fn(self._h, memspace, layout, B, D, _ptr(offsets), F, _ptr(X), ldx, _ptr(y), noise_kind, _ptr(s), strides,
                              _ptr(mw), stridemw, _ptr(T), ldt, strideT, _ptr(kf_mean), _ptr(kf_var), _ptr(kf_logpdf),
+                             _ptr(kf_total), _ptr(info)))
+
+    def kfold_large_ragged(self, dtype, memspace, layout, B, D, offsets, fold_sizes, X, ldx, y, noise_kind, s, strides, mw, stridemw, T, ldt,
+                           strideT, kf_mean, kf_var, kf_logpdf, kf_total, info):
+        """Exact leave-fold-out predictives for LARGE folds of B states with unequal observation counts, packed as `posterior_ragged`
+        packs them: regressor b has folds of ``fold_sizes[b]`` observations of its own slice (an int: the same size for all);
+        kf_logpdf is packed by folds (blr_kfold_large_ragged_fold_offsets); include/blr_mi355x.h blr_kfold_large_ragged_*."""
+        fn = getattr(self.lib, f"blr_kfold_large_ragged_{suffix(dtype)}")
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        if offsets.shape != (B + 1,):
+            raise ValueError(f"offsets must have B + 1 = {B + 1} entries, got shape {offsets.shape}")
+        fold_sizes = np.ascontiguousarray(np.broadcast_to(np.asarray(fold_sizes, dtype=np.int64), (B,)))
+        return self.check(fn(self._h, memspace, layout, B, D, _ptr(offsets), _ptr(fold_sizes), _ptr(X), ldx, _ptr(y), noise_kind, _ptr(s),
+                             strides, _ptr(mw), stridemw, _ptr(T), ldt, strideT, _ptr(kf_mean), _ptr(kf_var), _ptr(kf_logpdf),
                              _ptr(kf_total), _ptr(info)))
 
     def posterior_multi_batched(self, dtype, memspace, layout, B, D, N, S, X, ldx, strideX, Y, ldY, strideY, noise_kind, s, strides,

@@ -43,6 +43,7 @@
 #include "blr_kfold_large.hpp"
 #include "blr_kfold_multi.hpp"
 #include "blr_kfold_ragged.hpp"
+#include "blr_kfold_large_ragged.hpp"
 #include "blr_host.hpp"
 #include "blr_large_plan.hpp"
 
@@ -3432,13 +3433,14 @@ inline int no_check() { return 0; }
 // point's to check: `diag` and `s_all` mean something once it has.
 template <typename T, typename Mid = int (*)()>
 int ragged_front(blr_handle* h, RaggedFront& f, int memspace, int layout, int64_t B, int64_t D, const int64_t* offsets, const T* X, int64_t ldx,
-                 int noise_kind, int64_t strides, int xpos = 7, Mid mid = no_check) {
+                 int noise_kind, int64_t strides, int xpos = 7, Mid mid = no_check, int64_t maxD = kMaxLargeD,
+                 const char* d_text = "D out of range (1..8192)") {
   // (the argument checks come before the handle's: they need no device)
   if (h) h->err.clear();
   if (memspace != BLR_MEM_HOST && memspace != BLR_MEM_DEVICE) return bad_arg(h, 2, "memspace");
   if (layout != BLR_LAYOUT_COLVECS && layout != BLR_LAYOUT_ROWVECS) return bad_arg(h, 3, "unknown layout (reference :26-31)");
   if (B < 0 || B > (1 << 30)) return bad_arg(h, 4, "B out of range (0..2^30)");
-  if (D < 1 || D > kMaxLargeD) return bad_arg(h, 5, "D out of range (1..8192)");
+  if (D < 1 || D > maxD) return bad_arg(h, 5, d_text);
   if (const int rc = ragged_offsets_check(h, B, offsets)) return rc;
   if (const int rc = mid()) return rc;
   f.total = B > 0 ? offsets[B] : 0;
@@ -4868,6 +4870,182 @@ int kfold_large_batched(blr_handle* h, int memspace, int layout, int64_t B, int6
   return io.finish();
 }
 
+// ---- large folds of regressors with unequal observation counts and their own fold sizes (blr_kfold_large_ragged_*, DESIGN.md K28;
+// blr_kfold_large_ragged.hpp, blr_kfold_large_ragged_plan.hpp) ------------------------------------------------------------------------
+// the arguments the two host helpers share with the entry points, at their positions there
+inline int kfold_large_ragged_sizes_check(blr_handle* h, int64_t B, const int64_t* offsets, const int64_t* fold_sizes) {
+  if (B > 0 && !fold_sizes) return bad_arg(h, 7, "fold_sizes is NULL (a host array of B entries)");
+  for (int64_t b = 0; b < B; ++b) {
+    if (fold_sizes[b] < 1) return bad_arg(h, 7, "a fold size < 1");
+    if (kflr_folds(offsets[b + 1] - offsets[b], fold_sizes[b]) > kFoldLargeMaxFolds)
+      return bad_arg(h, 7, "ceil(N_b / F_b) > 1024: this route is for few, large folds (many small ones: blr_kfold_ragged_*)");
+  }
+  return 0;
+}
+
+// statistics (+ reduce) and factorisation of one chunk: the launches that depend on the block count (kfold_large_nb's, flat)
+template <typename T, int NB>
+int kfold_large_ragged_nb(blr_handle* h, KflrArgs<T> a, const KflrChunk& c, const KflrItem* stat, const KflrItem* red, bool vec_ok) {
+  using C = SmallCfg<T, NB>;
+  constexpr int SZ = kfl_stat_elems<T, NB>();
+  int rc;
+  void (*const factor)(KflrArgs<T>) = kflr_factor_kernel<T, NB>;
+  if ((rc = set_lds_once(h, factor, (size_t)C::LDS_BYTES))) return rc;
+  a.items = stat + c.stat0;
+  if constexpr (sizeof(T) == sizeof(double)) {
+    void (*const stats)(KflrArgs<T>) = a.layout == BLR_LAYOUT_ROWVECS ? kflr_stats_kernel<T, NB, 1>
+                                       : (vec_ok ? kflr_stats_kernel<T, NB, 4> : kflr_stats_kernel<T, NB, 0>);
+    if ((rc = set_lds_once(h, stats, (size_t)C::LDS_BYTES))) return rc;
+    hipLaunchKernelGGL(stats, dim3((unsigned)c.nstat), dim3(kThreads), C::LDS_BYTES, h->stream, a);
+  } else {
+    void (*const stats)(KflrArgs<T>) = a.layout == BLR_LAYOUT_ROWVECS ? kflr_stats32_kernel<LAYOUT_ROWVECS> : kflr_stats32_kernel<LAYOUT_COLVECS>;
+    const size_t lds = kfl_stats32_lds_bytes(a.D);
+    if ((rc = set_lds_once(h, stats, lds))) return rc;
+    hipLaunchKernelGGL(stats, dim3((unsigned)c.nstat), dim3(kThreads), lds, h->stream, a);
+  }
+  HIP_TRY(h, hipGetLastError());
+  if (c.nred > 0) {
+    a.items = red + c.red0;
+    hipLaunchKernelGGL(kflr_reduce_kernel<T>, dim3((unsigned)c.nred), dim3(kThreads), 0, h->stream, a, SZ);
+    HIP_TRY(h, hipGetLastError());
+  }
+  hipLaunchKernelGGL(factor, dim3((unsigned)c.nfolds), dim3(kThreads), C::LDS_BYTES, h->stream, a);
+  HIP_TRY(h, hipGetLastError());
+  return 0;
+}
+
+template <typename T>
+int kfold_large_ragged(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, const int64_t* offsets, const int64_t* fold_sizes,
+                       const T* X, int64_t ldx, const T* y, int noise_kind, const T* s, int64_t strides, const T* mw, int64_t stridemw,
+                       const T* Tf, int64_t ldt, int64_t strideT, T* kf_mean, T* kf_var, double* kf_logpdf, double* kf_total, int32_t* info) {
+  RaggedFront f;
+  const auto mid = [&] { return kfold_large_ragged_sizes_check(h, B, offsets, fold_sizes); };  // (position 7: X and ldx one later)
+  if (const int rc = ragged_front(h, f, memspace, layout, B, D, offsets, X, ldx, noise_kind, strides, 8, mid, kMaxSmallD, "D out of range (1..128)")) return rc;
+  const bool any = f.any, colv = f.colv;
+  if (any && !y) return bad_arg(h, 10, "y is NULL (reference :74 length check)");
+  if (noise_kind != BLR_NOISE_ISOTROPIC && noise_kind != BLR_NOISE_DIAGONAL)
+    return bad_arg(h, 11, "noise_kind (dense noise couples the folds: isotropic or diagonal only)");
+  if (any && !s) return bad_arg(h, 12, "s is NULL");
+  if (strides < 0) return bad_arg(h, 13, "strides < 0");
+  if (!mw) return bad_arg(h, 14, "mw is NULL");
+  if (stridemw < 0) return bad_arg(h, 15, "stridemw < 0");
+  if (!Tf) return bad_arg(h, 16, "T is NULL");
+  if (ldt < D) return bad_arg(h, 17, "ldt < D");
+  if (strideT < 0) return bad_arg(h, 18, "strideT < 0");
+  if (B > 0 && !info) return bad_arg(h, 23, "info is NULL");
+  if (B == 0) return 0;
+  if (!h) return -1;
+  h->last_chunks = 1;
+  HIP_TRY(h, hipSetDevice(h->device));
+
+  KflrPlan plan;
+  plan_kfold_large_ragged(offsets, fold_sizes, B, (int)D, h->cus, (int)sizeof(T), h->opt, plan);
+  const std::vector<int64_t>& fo = plan.fold_offsets;
+
+  CallIO io(h, memspace);
+  KflrArgs<T> a{};
+  a.ldx = ldx; a.strides = strides; a.stridemw = stridemw; a.layout = layout; a.noise_kind = noise_kind; a.D = (int)D;
+  const size_t n_all = f.n_all, nf_all = (size_t)fo[(size_t)B];
+  const T* T_d = nullptr;
+  double* total_dev = nullptr;
+  int32_t* info_dev = nullptr;
+  int rc;
+  if ((rc = io.in(X, f.x_all, &a.X))) return rc;
+  if ((rc = io.in(y, n_all, &a.y))) return rc;
+  if ((rc = io.in(s, any ? f.s_all : 0, &a.s))) return rc;
+  if ((rc = io.in(mw, extent(B, stridemw, (size_t)D), &a.mw))) return rc;
+  if ((rc = io.in(Tf, extent(B, strideT, mat_extent(D, D, ldt)), &T_d))) return rc;
+  if ((rc = io.out(kf_mean, n_all, &a.km))) return rc;
+  if ((rc = io.out(kf_var, n_all, &a.kv))) return rc;
+  if ((rc = io.out(kf_logpdf, nf_all, &a.kl))) return rc;
+  if ((rc = io.out(kf_total, (size_t)B, &total_dev))) return rc;
+  if ((rc = io.out(info, (size_t)B, &info_dev))) return rc;
+  if (!a.s) a.s = a.mw;  // (no observation at all: never dereferenced, but a valid pointer)
+  if ((rc = ensure_stats(h))) return rc;
+  a.degenerate = h->stats_dev + 4;
+  a.info = info_dev;
+
+  // offsets, the fold table, the records and the three item tables
+  const int64_t* off_dev;
+  const KflrItem *stat_dev, *red_dev, *pred_dev;
+  {
+    const size_t tbl = ragged_table_bytes(B);
+    const char* dev[6];
+    if ((rc = ragged_meta_upload(h, {{offsets, tbl}, {fo.data(), tbl}, {plan.regs.data(), plan.regs.size() * sizeof(KflrReg)},
+                                     {plan.stat.data(), plan.stat.size() * sizeof(KflrItem)}, {plan.red.data(), plan.red.size() * sizeof(KflrItem)},
+                                     {plan.pred.data(), plan.pred.size() * sizeof(KflrItem)}}, dev)))
+      return rc;
+    off_dev = reinterpret_cast<const int64_t*>(dev[0]);
+    a.fold_offsets = reinterpret_cast<const int64_t*>(dev[1]);
+    a.regs = reinterpret_cast<const KflrReg*>(dev[2]);
+    stat_dev = reinterpret_cast<const KflrItem*>(dev[3]);
+    red_dev = reinterpret_cast<const KflrItem*>(dev[4]);
+    pred_dev = reinterpret_cast<const KflrItem*>(dev[5]);
+  }
+  const int64_t ychunk = heldout_ragged_status<T>(h, B, D, T_d, ldt, strideT, a.s, strides, noise_kind, off_dev, info_dev);
+  HIP_TRY(h, hipGetLastError());
+  const bool predict = a.km || a.kv;
+  if (any && (predict || a.kl || total_dev)) {
+    const int NB = (int)(D + 15) / 16, DP = 16 * NB;
+    const size_t packed = (size_t)DP * (DP + 1) / 2, SZ = packed + DP;
+    if ((rc = heldout_ragged_spill(h, total_dev, 0, nf_all, 0, 256, &a.kl))) return rc;
+    Carve carve;
+    const size_t nrf = (size_t)plan.max_folds, nsl = (size_t)plan.max_slots, nbm = (size_t)plan.max_nb;
+    const size_t o_st = carve(nsl * SZ * sizeof(double)), o_U = carve(nrf * D * D * sizeof(T)), o_A = carve(nbm * packed * sizeof(double));
+    const size_t o_ld = carve(nbm * sizeof(double)), o_sc = carve(nsl * 2 * sizeof(double));
+    const size_t o_mw = carve(nrf * D * sizeof(T)), o_fi = carve(nrf * sizeof(int32_t));
+    if ((rc = h->cov_ws.reserve(h, carve.off))) return rc;
+    char* const ws = h->cov_ws.p;
+    a.stats = reinterpret_cast<double*>(ws + o_st); a.U = reinterpret_cast<T*>(ws + o_U); a.A = reinterpret_cast<double*>(ws + o_A);
+    a.ldA = reinterpret_cast<double*>(ws + o_ld); a.scal = reinterpret_cast<double*>(ws + o_sc); a.mwf = reinterpret_cast<T*>(ws + o_mw);
+    a.finfo = reinterpret_cast<int32_t*>(ws + o_fi);
+    const size_t lds_s = kfl_state_lds_bytes(sizeof(T), (int)D), lds_p = kfl_predict_lds_bytes(sizeof(T), (int)D);
+    void (*const pred)(KflrArgs<T>) = layout == BLR_LAYOUT_ROWVECS ? kflr_predict_kernel<T, LAYOUT_ROWVECS> : kflr_predict_kernel<T, LAYOUT_COLVECS>;
+    void (*const state)(KflArgs<T>) = kfl_state_kernel<T>;
+    if ((rc = set_lds_once(h, state, lds_s))) return rc;
+    if (predict && (rc = set_lds_once(h, pred, lds_p))) return rc;
+    if (predict && (rc = MargImages<T>::reserve(h, std::max<int64_t>(1, plan.max_folds)))) return rc;
+    // (every regressor's slice starts at a multiple of the vector when X and ldx do: ColVecs columns are ldx apart.)  Asked of the
+    // STAGED pointer alone, unlike marg_ragged_gemm_takes: the answer only picks phase_gram's loader (MODE 4 or 0), which moves the
+    // same values into the same LDS places -- the arithmetic and its order do not depend on it, so a host-memspace call whose staged
+    // copy is aligned where the caller's array is not still gives the device-memspace call's bits (as in kfold_large_batched)
+    const bool vec_ok = colv && D % Mfma<T>::VEC == 0 && aligned16(a.X, ldx, 0);
+    KflArgs<T> st{};  // kfl_state_kernel reads the factors and the status and writes A, logdet A: nothing of the folds
+    st.Tf = T_d; st.ldt = ldt; st.strideT = strideT; st.info = info_dev; st.A = a.A; st.ldA = a.ldA; st.D = (int)D;
+    for (const KflrChunk& c : plan.chunks) {
+      if (c.nfolds == 0) continue;  // (no observation in the chunk)
+      KflrArgs<T> k = a;
+      k.b0 = (int)c.b0; k.nb = (int)c.nb; k.fold0 = c.fold0; k.slot0 = c.slot0;
+      st.reg0 = (int)c.b0;
+      hipLaunchKernelGGL(state, dim3((unsigned)c.nb), dim3(kThreads), lds_s, h->stream, st);
+      HIP_TRY(h, hipGetLastError());
+      switch (NB) {
+        case 1: rc = kfold_large_ragged_nb<T, 1>(h, k, c, stat_dev, red_dev, vec_ok); break;
+        case 2: rc = kfold_large_ragged_nb<T, 2>(h, k, c, stat_dev, red_dev, vec_ok); break;
+        case 3: rc = kfold_large_ragged_nb<T, 3>(h, k, c, stat_dev, red_dev, vec_ok); break;
+        case 4: rc = kfold_large_ragged_nb<T, 4>(h, k, c, stat_dev, red_dev, vec_ok); break;
+        case 5: rc = kfold_large_ragged_nb<T, 5>(h, k, c, stat_dev, red_dev, vec_ok); break;
+        case 6: rc = kfold_large_ragged_nb<T, 6>(h, k, c, stat_dev, red_dev, vec_ok); break;
+        case 7: rc = kfold_large_ragged_nb<T, 7>(h, k, c, stat_dev, red_dev, vec_ok); break;
+        default: rc = kfold_large_ragged_nb<T, 8>(h, k, c, stat_dev, red_dev, vec_ok); break;
+      }
+      if (rc) return rc;
+      if (predict) {
+        k.img = MargImages<T>::launch(h, k.U, D, D * D, (int)D, (const int32_t*)k.finfo, 0, c.nfolds);
+        k.items = pred_dev + c.pred0;
+        hipLaunchKernelGGL(pred, dim3((unsigned)c.npred), dim3(kThreads), lds_p, h->stream, k);
+        HIP_TRY(h, hipGetLastError());
+      }
+    }
+    h->route = "kflr_factor_kernel";
+    h->route_i8_B = 0;
+  }
+  h->last_chunks = std::max<int64_t>(1, plan.last_chunks);
+  if (total_dev) heldout_ragged_totals(h, B, ychunk, a.kl, a.fold_offsets, total_dev, info_dev);
+  HIP_TRY(h, hipGetLastError());
+  return io.finish();
+}
+
 // ---- rank-k update / downdate of a resident MULTI-OUTPUT state: one factor, S mean columns (blr_update_multi_factor_*,
 // blr_downdate_multi_factor_*; blr_state_cols.hpp) ---------------------------------------------------------------------
 
@@ -5338,6 +5516,14 @@ int blr_timer_stop(blr_handle* h, float* elapsed_ms) {
     return kfold_ragged<T>(h, memspace, layout, B, D, offsets, F, X, ldx, y, noise_kind, s, strides, mw, stridemw,  \
                            Tf, ldt, strideT, kf_mean, kf_var, kf_logpdf, kf_total, info);                           \
   }                                                                                                                 \
+  int blr_kfold_large_ragged_##SUF(blr_handle* h, int memspace, int layout, int64_t B, int64_t D,                   \
+                                   const int64_t* offsets, const int64_t* fold_sizes, const T* X, int64_t ldx,      \
+                                   const T* y, int noise_kind, const T* s, int64_t strides, const T* mw,            \
+                                   int64_t stridemw, const T* Tf, int64_t ldt, int64_t strideT, T* kf_mean,         \
+                                   T* kf_var, double* kf_logpdf, double* kf_total, int32_t* info) {                 \
+    return kfold_large_ragged<T>(h, memspace, layout, B, D, offsets, fold_sizes, X, ldx, y, noise_kind, s, strides, \
+                                 mw, stridemw, Tf, ldt, strideT, kf_mean, kf_var, kf_logpdf, kf_total, info);       \
+  }                                                                                                                 \
   int blr_posterior_multi_batched_##SUF(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t N,   \
                                         int64_t S, const T* X, int64_t ldx, int64_t strideX, const T* Y,            \
                                         int64_t ldY, int64_t strideY, int noise_kind, const T* s, int64_t strides,  \
@@ -5530,6 +5716,24 @@ int blr_kfold_ragged_fold_offsets(int64_t B, const int64_t* offsets, int64_t F, 
   if (const int rc = kfold_ragged_shape_check(nullptr, B, offsets, F)) return rc;
   if (!fold_offsets) return -21;
   kfold_ragged_fold_offsets(offsets, B, F, fold_offsets);
+  return 0;
+}
+
+// host arithmetic only: no handle, no device (blr_kfold_large_ragged_plan.hpp)
+int blr_kfold_large_ragged_fold_sizes(int64_t B, const int64_t* offsets, int64_t K, int64_t* fold_sizes) {
+  if (B < 0 || B > (1 << 30)) return -4;
+  if (const int rc = ragged_offsets_check(nullptr, B, offsets)) return rc;
+  if (K < 1 || K > kFoldLargeMaxFolds) return -3;
+  if (B > 0 && !fold_sizes) return -7;
+  kflr_fold_sizes(offsets, B, K, fold_sizes);
+  return 0;
+}
+int blr_kfold_large_ragged_fold_offsets(int64_t B, const int64_t* offsets, const int64_t* fold_sizes, int64_t* fold_offsets) {
+  if (B < 0 || B > (1 << 30)) return -4;
+  if (const int rc = ragged_offsets_check(nullptr, B, offsets)) return rc;
+  if (const int rc = kfold_large_ragged_sizes_check(nullptr, B, offsets, fold_sizes)) return rc;
+  if (!fold_offsets) return -21;
+  kflr_fold_offsets(offsets, fold_sizes, B, fold_offsets);
   return 0;
 }
 

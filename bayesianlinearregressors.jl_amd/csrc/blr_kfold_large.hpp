@@ -28,6 +28,7 @@
 #include "blr_fused_small.hpp"
 #include "blr_loo.hpp"
 #include "blr_cov_batched.hpp"
+#include "blr_kfold_large_splits.hpp"
 
 namespace blr {
 
@@ -66,16 +67,28 @@ struct KflArgs {
   int reg0;                          // first regressor of this chunk
 };
 
-// Column blocks of a fold's statistics pass, a function of its own row count alone (grid_splits of blr_grid.hpp on n_f): blocks of
-// about 1024 rows, at most 8, whole stages of 64.  A shorter last fold has no more blocks than a full one.
-__host__ __device__ inline void kfl_splits(int nf, int* S, int* chunk) {
-  int s = nf / 1024;
-  s = s < 1 ? 1 : (s > 8 ? 8 : s);
-  int c = (nf + s - 1) / s;
-  c = (c + 63) / 64 * 64;
-  *S = s;
-  *chunk = c < 64 ? 64 : c;
-}
+// What a body below needs of ONE fold -- the statistics: of one column block of it --: pointers at its first row, its row count, its
+// slots.  The rectangular kernels (kfl_*) and the table-driven ones of the unequal-count form (kflr_*, blr_kfold_large_ragged.hpp) each
+// fill one and run the same body: a fold has the same bits whichever grid it came from.
+template <typename T>
+struct KflFold {
+  const T* X;                      // the first row of the fold (statistics: of the column block)
+  const T* y;                      // likewise
+  const T* s;                      // likewise under diagonal noise; else the regressor's value
+  const T* mw;                     // the state's mean
+  int64_t ldx;
+  int D, n, noise_kind;            // n: rows of the fold (statistics: of the column block)
+  double* stats;                   // PACKED + DP doubles: the block's slot (factor: the fold's block 0, reduced)
+  double* scal;                    // {q_f, l_f} of that slot
+  const double* A;                 // the regressor's A, packed
+  const double* ldA;               // ... and logdet A
+  T* U; T* mwf; int32_t* finfo;    // the fold's factor, mean and status word
+  double* kl;                      // the fold's log density (may be NULL)
+  unsigned long long* degenerate;
+  const T* img;                    // the fold's image
+  T* km; T* kv;                    // at the fold's first row (may be NULL)
+  int grp, ngroups;                // predict: this workgroup takes the tiles grp, grp + ngroups, ...
+};
 
 // dynamic LDS of kfl_state_kernel: the factor's upper triangle, packed by columns
 inline size_t kfl_state_lds_bytes(size_t elem, int D) {
@@ -123,14 +136,40 @@ __global__ __launch_bounds__(kThreads) void kfl_state_kernel(KflArgs<T> a) {
 
 // ---- statistics of one column block of one fold: the streaming Gram phase without a prior, centred at the state's mean -----------
 template <typename T, int NB, int MODE>
-__global__ BLR_KFL_BOUNDS(T, NB) void kfl_stats_kernel(KflArgs<T> a) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
+__device__ __forceinline__ void kfl_stats_body(char* smem, const KflFold<T>& v) {
   using C = SmallCfg<T, NB>;
   T* const P = reinterpret_cast<T*>(smem);
   T* const bvec = reinterpret_cast<T*>(smem + C::OFF_B);
   double* const scr = reinterpret_cast<double*>(smem + C::OFF_SCR);
   RegCtx<T>* ctx = reinterpret_cast<RegCtx<T>*>(smem + C::OFF_CTX);
   const int tid = threadIdx.x;
+  if (tid == 0) {
+    ctx->X = v.X;
+    ctx->y = v.y;
+    ctx->s = v.s;
+    ctx->mw = v.mw;
+    ctx->Lw = ctx->mw;  // (a valid address: phase_gram loads one word of it and drops the value)
+    ctx->ldx = v.ldx;
+    ctx->ldl = 0;
+    ctx->D = v.D;
+    ctx->N = v.n;
+    ctx->noise_kind = v.noise_kind;
+    ctx->prior_kind = kKflPriorNone;
+  }
+  __syncthreads();
+  phase_gram<T, NB, MODE>(smem);
+  BLR_GLOBAL double* const out = as_global(v.stats);
+  for (int idx = tid; idx < C::PACKED; idx += kThreads) out[idx] = (double)P[idx];
+  if (tid < C::DP) out[C::PACKED + tid] = (double)bvec[tid];
+  if (tid == 0) {
+    v.scal[0] = scr[4];
+    v.scal[1] = scr[5];
+  }
+}
+
+template <typename T, int NB, int MODE>
+__global__ BLR_KFL_BOUNDS(T, NB) void kfl_stats_kernel(KflArgs<T> a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
   const int64_t r = blockIdx.y, reg = (int64_t)a.reg0 + r;
   if (a.info[reg] != 0) return;  // (block-uniform)
   const int f = (int)blockIdx.x / a.S, sp = (int)blockIdx.x - f * a.S;
@@ -139,32 +178,18 @@ __global__ BLR_KFL_BOUNDS(T, NB) void kfl_stats_kernel(KflArgs<T> a) {
   kfl_splits(nf, &Sf, &chunk);
   if (sp >= Sf) return;  // (block-uniform) a shorter last fold: fewer blocks
   const int n0 = f0 + sp * chunk;
-  const int n = max(0, min(chunk, nf - sp * chunk));
   const bool diag = a.noise_kind == NOISE_DIAGONAL;
-  if (tid == 0) {
-    ctx->X = a.X + reg * a.strideX + (a.layout == LAYOUT_COLVECS ? (int64_t)n0 * a.ldx : (int64_t)n0);
-    ctx->y = a.y + reg * a.stridey + n0;
-    ctx->s = a.s + reg * a.strides + (diag ? n0 : 0);
-    ctx->mw = a.mw + reg * a.stridemw;
-    ctx->Lw = ctx->mw;  // (a valid address: phase_gram loads one word of it and drops the value)
-    ctx->ldx = a.ldx;
-    ctx->ldl = 0;
-    ctx->D = a.D;
-    ctx->N = n;
-    ctx->noise_kind = a.noise_kind;
-    ctx->prior_kind = kKflPriorNone;
-  }
-  __syncthreads();
-  phase_gram<T, NB, MODE>(smem);
-  constexpr int SZ = kfl_stat_elems<T, NB>();
   const int64_t slot = ((int64_t)r * a.nfolds + f) * a.S + sp;
-  BLR_GLOBAL double* const out = as_global(a.stats + slot * SZ);
-  for (int idx = tid; idx < C::PACKED; idx += kThreads) out[idx] = (double)P[idx];
-  if (tid < C::DP) out[C::PACKED + tid] = (double)bvec[tid];
-  if (tid == 0) {
-    a.scal[2 * slot] = scr[4];
-    a.scal[2 * slot + 1] = scr[5];
-  }
+  KflFold<T> v;
+  v.X = a.X + reg * a.strideX + (a.layout == LAYOUT_COLVECS ? (int64_t)n0 * a.ldx : (int64_t)n0);
+  v.y = a.y + reg * a.stridey + n0;
+  v.s = a.s + reg * a.strides + (diag ? n0 : 0);
+  v.mw = a.mw + reg * a.stridemw;
+  v.ldx = a.ldx; v.D = a.D; v.noise_kind = a.noise_kind;
+  v.n = max(0, min(chunk, nf - sp * chunk));
+  v.stats = a.stats + slot * kfl_stat_elems<T, NB>();
+  v.scal = a.scal + 2 * slot;
+  kfl_stats_body<T, NB, MODE>(smem, v);
 }
 
 // ---- fp32: the same statistics accumulated in DOUBLE on v_mfma_f64_16x16x4 from the float inputs ---------------------------------
@@ -184,23 +209,13 @@ inline size_t kfl_stats32_lds_bytes(int D) {
 }
 
 template <int LAYOUT /* LAYOUT_COLVECS | LAYOUT_ROWVECS */>
-__global__ __launch_bounds__(kThreads, 2) void kfl_stats32_kernel(KflArgs<float> a) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  __shared__ double scr[kWaves];
+__device__ __forceinline__ void kfl_stats32_body(char* smem, double* scr /* [kWaves], LDS */, const KflFold<float>& a) {
   using Mf = Mfma<double>;
   using acc4 = Mf::acc4;
   constexpr int TN = kKflTile, MAXT = 9;  // 36 tiles at DP = 128: nine per wave
   const int tid = threadIdx.x, lane = tid & 63, wave = uni(tid >> 6);
   const int g = lane >> 4, li = lane & 15;
-  const int64_t r = blockIdx.y, reg = (int64_t)a.reg0 + r;
-  if (a.info[reg] != 0) return;  // (block-uniform)
-  const int f = (int)blockIdx.x / a.S, sp = (int)blockIdx.x - f * a.S;
-  const int f0 = f * a.F, nf = min(a.F, a.N - f0);
-  int Sf, chunk;
-  kfl_splits(nf, &Sf, &chunk);
-  if (sp >= Sf) return;  // (block-uniform) a shorter last fold: fewer blocks
-  const int n0 = f0 + sp * chunk;
-  const int nblk = max(0, min(chunk, nf - sp * chunk));  // rows of this block: [n0, n0 + nblk)
+  const int nblk = a.n;  // rows of this block
   const int D = a.D, NB = (D + 15) / 16, DP = 16 * NB, LDX = DP + 1, NT = NB * (NB + 1) / 2;
   const bool diag = a.noise_kind == NOISE_DIAGONAL;
 
@@ -209,10 +224,10 @@ __global__ __launch_bounds__(kThreads, 2) void kfl_stats32_kernel(KflArgs<float>
   double* const rs = ws + TN;                           // [TN] w_n r0_n
   double* const mws = rs + TN;                          // [128]
 
-  const BLR_GLOBAL float* const Xg = as_global(a.X + reg * a.strideX + (LAYOUT == LAYOUT_COLVECS ? (int64_t)n0 * a.ldx : (int64_t)n0));
-  const BLR_GLOBAL float* const yg = as_global(a.y + reg * a.stridey + n0);
-  const BLR_GLOBAL float* const sg = as_global(a.s + reg * a.strides + (diag ? n0 : 0));
-  if (tid < 128) mws[tid] = tid < D ? (double)as_global(a.mw + reg * a.stridemw)[tid] : 0.0;
+  const BLR_GLOBAL float* const Xg = as_global(a.X);
+  const BLR_GLOBAL float* const yg = as_global(a.y);
+  const BLR_GLOBAL float* const sg = as_global(a.s);
+  if (tid < 128) mws[tid] = tid < D ? (double)as_global(a.mw)[tid] : 0.0;
 
   const int xcnt = DP / 4;
   float xreg[32];
@@ -289,9 +304,8 @@ __global__ __launch_bounds__(kThreads, 2) void kfl_stats32_kernel(KflArgs<float>
     }
   }
 
-  const int64_t slot = ((int64_t)r * a.nfolds + f) * a.S + sp;
   const int packed = DP * (DP + 1) / 2;
-  BLR_GLOBAL double* const out = as_global(a.stats + slot * (int64_t)(packed + DP));
+  BLR_GLOBAL double* const out = as_global(a.stats);
 #pragma unroll
   for (int i = 0; i < MAXT; ++i) {
     if (tK[i] >= 0) {
@@ -307,12 +321,56 @@ __global__ __launch_bounds__(kThreads, 2) void kfl_stats32_kernel(KflArgs<float>
   const double q = block_allreduce(qacc, scr, tid);
   const double l = block_allreduce(lacc, scr, tid);
   if (tid == 0) {
-    a.scal[2 * slot] = q;
-    a.scal[2 * slot + 1] = l;
+    a.scal[0] = q;
+    a.scal[1] = l;
   }
 }
 
+template <int LAYOUT /* LAYOUT_COLVECS | LAYOUT_ROWVECS */>
+__global__ __launch_bounds__(kThreads, 2) void kfl_stats32_kernel(KflArgs<float> a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  __shared__ double scr[kWaves];
+  const int64_t r = blockIdx.y, reg = (int64_t)a.reg0 + r;
+  if (a.info[reg] != 0) return;  // (block-uniform)
+  const int f = (int)blockIdx.x / a.S, sp = (int)blockIdx.x - f * a.S;
+  const int f0 = f * a.F, nf = min(a.F, a.N - f0);
+  int Sf, chunk;
+  kfl_splits(nf, &Sf, &chunk);
+  if (sp >= Sf) return;  // (block-uniform) a shorter last fold: fewer blocks
+  const int n0 = f0 + sp * chunk;  // rows of this block: [n0, n0 + v.n)
+  const int DP = 16 * ((a.D + 15) / 16);
+  const int64_t slot = ((int64_t)r * a.nfolds + f) * a.S + sp;
+  KflFold<float> v;
+  v.X = a.X + reg * a.strideX + (LAYOUT == LAYOUT_COLVECS ? (int64_t)n0 * a.ldx : (int64_t)n0);
+  v.y = a.y + reg * a.stridey + n0;
+  v.s = a.s + reg * a.strides + (a.noise_kind == NOISE_DIAGONAL ? n0 : 0);
+  v.mw = a.mw + reg * a.stridemw;
+  v.ldx = a.ldx; v.D = a.D; v.noise_kind = a.noise_kind;
+  v.n = max(0, min(chunk, nf - sp * chunk));
+  v.stats = a.stats + slot * (int64_t)(DP * (DP + 1) / 2 + DP);
+  v.scal = a.scal + 2 * slot;
+  kfl_stats32_body<LAYOUT>(smem, scr, v);
+}
+
 // ---- column blocks 1 .. S_f - 1 of a fold added to block 0, in that order (grid_reduce_kernel's pattern) ---------------------------
+// st, scal: the fold's block 0, its S_f blocks one behind the other; the workgroup's threads take idx = first, first + step, ...
+__device__ __forceinline__ void kfl_reduce_body(double* st, double* scal, int Sf, int SZ, int first, int step, bool lead) {
+  for (int idx = first; idx < SZ; idx += step) {
+    double acc = st[idx];
+    for (int sp = 1; sp < Sf; ++sp) acc += st[(int64_t)sp * SZ + idx];
+    st[idx] = acc;
+  }
+  if (lead) {
+    double q = scal[0], l = scal[1];
+    for (int sp = 1; sp < Sf; ++sp) {
+      q += scal[2 * sp];
+      l += scal[2 * sp + 1];
+    }
+    scal[0] = q;
+    scal[1] = l;
+  }
+}
+
 template <typename T>
 __global__ __launch_bounds__(kThreads) void kfl_reduce_kernel(KflArgs<T> a, int SZ) {
   const int64_t rf = blockIdx.x;  // chunk-local (regressor, fold)
@@ -323,46 +381,24 @@ __global__ __launch_bounds__(kThreads) void kfl_reduce_kernel(KflArgs<T> a, int 
   int Sf, chunk;
   kfl_splits(nf, &Sf, &chunk);
   if (Sf < 2) return;
-  double* const st = a.stats + rf * a.S * (int64_t)SZ;
-  for (int idx = blockIdx.y * kThreads + threadIdx.x; idx < SZ; idx += gridDim.y * kThreads) {
-    double acc = st[idx];
-    for (int sp = 1; sp < Sf; ++sp) acc += st[(int64_t)sp * SZ + idx];
-    st[idx] = acc;
-  }
-  if (blockIdx.y == 0 && threadIdx.x == 0) {
-    double q = a.scal[2 * rf * a.S], l = a.scal[2 * rf * a.S + 1];
-    for (int sp = 1; sp < Sf; ++sp) {
-      q += a.scal[2 * (rf * a.S + sp)];
-      l += a.scal[2 * (rf * a.S + sp) + 1];
-    }
-    a.scal[2 * rf * a.S] = q;
-    a.scal[2 * rf * a.S + 1] = l;
-  }
+  kfl_reduce_body(a.stats + rf * a.S * (int64_t)SZ, a.scal + 2 * rf * a.S, Sf, SZ, blockIdx.y * kThreads + threadIdx.x, gridDim.y * kThreads,
+                  blockIdx.y == 0 && threadIdx.x == 0);
 }
 
 // ---- one fold: A_f = A - G_f, its factor U_f, mw_f, the fold's joint log density ----------------------------------------------------
 // Two workgroups per CU (256 registers per lane) in every instantiation: under the statistics kernel's bounds (four per CU at
 // NB <= 4, three waves per SIMD in fp32) the instantiations <double, 4> and <float, 8> spilled three vector registers each.
 template <typename T, int NB>
-__global__ __launch_bounds__(kThreads, 2) void kfl_factor_kernel(KflArgs<T> a) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
+__device__ __forceinline__ void kfl_factor_body(char* smem, const KflFold<T>& a) {
   using C = SmallCfg<T, NB>;
   static_assert(2 * C::LDS_BYTES <= 160 * 1024, "two workgroups per CU: twice the dynamic LDS of a launch must fit 160 KB");
-  constexpr int SZ = kfl_stat_elems<T, NB>();
   T* const P = reinterpret_cast<T*>(smem);
   T* const bvec = reinterpret_cast<T*>(smem + C::OFF_B);
   double* const scr = reinterpret_cast<double*>(smem + C::OFF_SCR);
   const int tid = threadIdx.x;
   const int D = a.D;
-  const int f = blockIdx.x;
-  const int64_t r = blockIdx.y, reg = (int64_t)a.reg0 + r;
-  const int64_t rf = r * a.nfolds + f;
-  if (a.info[reg] != 0) {  // (block-uniform) nothing of this regressor is computed: no image, no prediction
-    if (tid == 0) a.finfo[rf] = 1;
-    return;
-  }
-  const BLR_GLOBAL double* const st = as_global(a.stats + rf * a.S * (int64_t)SZ);
-  const BLR_GLOBAL double* const Ag = as_global(a.A + r * C::PACKED);
+  const BLR_GLOBAL double* const st = as_global(a.stats);
+  const BLR_GLOBAL double* const Ag = as_global(a.A);
   for (int idx = tid; idx < C::PACKED; idx += kThreads) P[idx] = (T)(Ag[idx] - st[idx]);  // one rounding of the difference
   if (tid < C::DP) bvec[tid] = (T)st[C::PACKED + tid];
   __syncthreads();
@@ -375,36 +411,62 @@ __global__ __launch_bounds__(kThreads, 2) void kfl_factor_kernel(KflArgs<T> a) {
   bool bad = chol_info != 0;                                               // a pivot <= 0 or NaN
   double uu = 0.0, ld = 0.0;
   if (!bad) {
-    [[clang::always_inline]] phase_backsolve<T, NB, 2>(smem, D, a.U + rf * (int64_t)D * D, (int64_t)D);  // bvec <- U_f^-1 u_f; the factor goes out
+    [[clang::always_inline]] phase_backsolve<T, NB, 2>(smem, D, a.U, (int64_t)D);  // bvec <- U_f^-1 u_f; the factor goes out
 #pragma clang diagnostic pop
     uu = scr[6];                                                                  // |u_f|^2
     ld = scr[7];                                                                  // logdet A_f
     bad = !isfinite(uu) || !isfinite(ld);                                         // (an infinite pivot; block-uniform: LDS values)
   }
-  double* const kl = a.kl ? a.kl + reg * a.stride_kl + f : nullptr;
+  double* const kl = a.kl;
   if (bad) {
     if (tid == 0) {
-      a.finfo[rf] = 2;
+      *a.finfo = 2;
       if (kl) *kl = __longlong_as_double(0x7ff8000000000000LL);
       atomicAdd(a.degenerate, 1ull);
     }
     return;
   }
-  if (tid < D) a.mwf[rf * D + tid] = as_global(a.mw + reg * a.stridemw)[tid] - bvec[tid];
+  if (tid < D) a.mwf[tid] = as_global(a.mw)[tid] - bvec[tid];
   if (tid == 0) {
-    a.finfo[rf] = 0;
+    *a.finfo = 0;
     if (kl) {
       const double LOG2PI = 1.8378770664093454835606594728112;
-      const double nf = (double)min(a.F, a.N - f * a.F);
-      *kl = -0.5 * (nf * LOG2PI + a.scal[2 * rf * a.S + 1] + a.ldA[r] - ld + a.scal[2 * rf * a.S] + uu);
+      const double nf = (double)a.n;
+      *kl = -0.5 * (nf * LOG2PI + a.scal[1] + *a.ldA - ld + a.scal[0] + uu);
     }
   }
 }
 
+template <typename T, int NB>
+__global__ __launch_bounds__(kThreads, 2) void kfl_factor_kernel(KflArgs<T> a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  using C = SmallCfg<T, NB>;
+  constexpr int SZ = kfl_stat_elems<T, NB>();
+  const int f = blockIdx.x;
+  const int64_t r = blockIdx.y, reg = (int64_t)a.reg0 + r;
+  const int64_t rf = r * a.nfolds + f;
+  if (a.info[reg] != 0) {  // (block-uniform) nothing of this regressor is computed: no image, no prediction
+    if (threadIdx.x == 0) a.finfo[rf] = 1;
+    return;
+  }
+  KflFold<T> v;
+  v.mw = a.mw + reg * a.stridemw;
+  v.D = a.D; v.n = min(a.F, a.N - f * a.F);
+  v.stats = a.stats + rf * a.S * (int64_t)SZ;
+  v.scal = a.scal + 2 * rf * a.S;
+  v.A = a.A + r * C::PACKED;
+  v.ldA = a.ldA + r;
+  v.U = a.U + rf * (int64_t)a.D * a.D;
+  v.mwf = a.mwf + rf * a.D;
+  v.finfo = a.finfo + rf;
+  v.kl = a.kl ? a.kl + reg * a.stride_kl + f : nullptr;
+  v.degenerate = a.degenerate;
+  kfl_factor_body<T, NB>(smem, v);
+}
+
 // ---- the fold's rows against its own factor: kf_mean_n = x_n'mw_f, kf_var_n = s_n + |U_f^-T x_n|^2 --------------------------------
 template <typename T, int LAYOUT /* LAYOUT_COLVECS | LAYOUT_ROWVECS */>
-__global__ __launch_bounds__(kThreads, 2) void kfl_predict_kernel(KflArgs<T> a) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
+__device__ __forceinline__ void kfl_predict_body(char* smem, const KflFold<T>& a) {
   using Mf = Mfma<T>;
   using G = MargGemmCfg<T>;
   using acc4 = typename Mf::acc4;
@@ -412,16 +474,13 @@ __global__ __launch_bounds__(kThreads, 2) void kfl_predict_kernel(KflArgs<T> a) 
   typedef T vecT __attribute__((ext_vector_type(Mf::VEC)));
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int g = lane >> 4, li = lane & 15;
-  const int grp = blockIdx.x, f = blockIdx.y;
-  const int64_t r = blockIdx.z, reg = (int64_t)a.reg0 + r;
-  if (a.info[reg] != 0) return;  // (block-uniform) outputs untouched
-  const int64_t rf = r * a.nfolds + f;
+  const int grp = a.grp;
   const int D = a.D;
-  const int f0 = f * a.F, nf = min(a.F, a.N - f0);  // the fold's rows: [f0, f0 + nf)
+  const int nf = a.n;  // the fold's rows
   const int NB = (D + 15) / 16, DP = 16 * NB, LDX = cov_ldz<T>(DP);
-  BLR_GLOBAL T* const km = a.km ? as_global(a.km + reg * a.stride_km + f0) : nullptr;
-  BLR_GLOBAL T* const kv = a.kv ? as_global(a.kv + reg * a.stride_kv + f0) : nullptr;
-  if (a.finfo[rf] != 0) {  // (block-uniform) the NaN rule: every member of the fold
+  BLR_GLOBAL T* const km = a.km ? as_global(a.km) : nullptr;
+  BLR_GLOBAL T* const kv = a.kv ? as_global(a.kv) : nullptr;
+  if (*a.finfo != 0) {  // (block-uniform) the NaN rule: every member of the fold
     const T nan = (T)__builtin_nan("");
     for (int n = grp * kThreads + tid; n < nf; n += a.ngroups * kThreads) {
       if (km) km[n] = nan;
@@ -434,8 +493,8 @@ __global__ __launch_bounds__(kThreads, 2) void kfl_predict_kernel(KflArgs<T> a) 
   T* const mws = Xs + TN * LDX;              // [128]
   T* const img = mws + kCovMaxD;             // [2 NB (NB + 1)][64]
 
-  const BLR_GLOBAL T* const Xg = as_global(a.X + reg * a.strideX + (LAYOUT == LAYOUT_COLVECS ? (int64_t)f0 * a.ldx : (int64_t)f0));
-  const BLR_GLOBAL T* const sg = as_global(a.s + reg * a.strides + (a.noise_kind == NOISE_DIAGONAL ? f0 : 0));
+  const BLR_GLOBAL T* const Xg = as_global(a.X);
+  const BLR_GLOBAL T* const sg = as_global(a.s);
   const int ntiles = (nf + TN - 1) / TN;
 
   // the tile through registers, as cov_whiten_kernel loads it; a row past the FOLD's end is not read (zeros)
@@ -459,12 +518,12 @@ __global__ __launch_bounds__(kThreads, 2) void kfl_predict_kernel(KflArgs<T> a) 
 
   // ---- once per workgroup: the fold's image and mean ----
   {
-    const BLR_GLOBAL vecT* const src = reinterpret_cast<const BLR_GLOBAL vecT*>(as_global(a.img + rf * G::IMG_ELEMS));
+    const BLR_GLOBAL vecT* const src = reinterpret_cast<const BLR_GLOBAL vecT*>(as_global(a.img));
     vecT* const dst = reinterpret_cast<vecT*>(img);
     const int nvec = G::frag0(NB) * 64 / VEC;
     for (int e = tid; e < nvec; e += kThreads) dst[e] = src[e];
   }
-  if (tid < kCovMaxD) mws[tid] = tid < D ? as_global(a.mwf + rf * D)[tid] : T(0);
+  if (tid < kCovMaxD) mws[tid] = tid < D ? as_global(a.mwf)[tid] : T(0);
 
   const int row = 16 * wave + li;  // this lane's input of the tile (the same in its four lane groups)
   for (int tile = grp; tile < ntiles; tile += a.ngroups) {
@@ -507,6 +566,28 @@ __global__ __launch_bounds__(kThreads, 2) void kfl_predict_kernel(KflArgs<T> a) 
       if (kv) kv[n] = sg[a.noise_kind == NOISE_DIAGONAL ? n : 0] + zz;
     }
   }
+}
+
+template <typename T, int LAYOUT /* LAYOUT_COLVECS | LAYOUT_ROWVECS */>
+__global__ __launch_bounds__(kThreads, 2) void kfl_predict_kernel(KflArgs<T> a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int f = blockIdx.y;
+  const int64_t r = blockIdx.z, reg = (int64_t)a.reg0 + r;
+  if (a.info[reg] != 0) return;  // (block-uniform) outputs untouched
+  const int64_t rf = r * a.nfolds + f;
+  const int f0 = f * a.F;  // the fold's rows: [f0, f0 + v.n)
+  KflFold<T> v;
+  v.X = a.X + reg * a.strideX + (LAYOUT == LAYOUT_COLVECS ? (int64_t)f0 * a.ldx : (int64_t)f0);
+  v.s = a.s + reg * a.strides + (a.noise_kind == NOISE_DIAGONAL ? f0 : 0);
+  v.ldx = a.ldx; v.D = a.D; v.noise_kind = a.noise_kind;
+  v.n = min(a.F, a.N - f0);
+  v.mwf = a.mwf + rf * a.D;
+  v.finfo = a.finfo + rf;
+  v.img = a.img + rf * MargGemmCfg<T>::IMG_ELEMS;
+  v.km = a.km ? a.km + reg * a.stride_km + f0 : nullptr;
+  v.kv = a.kv ? a.kv + reg * a.stride_kv + f0 : nullptr;
+  v.grp = blockIdx.x; v.ngroups = a.ngroups;
+  kfl_predict_body<T, LAYOUT>(smem, v);
 }
 
 // the instantiations the library uses, defined in blr_kfold_large.hip

@@ -30,6 +30,7 @@ __all__ = [
     "KFold", "kfold", "kfold_map", "kfold_large", "kfold_large_map", "cross_validate", "kfold_columns", "kfold_columns_map",
     "EvidenceGrid", "logpdf_grid", "posterior_best", "logpdf_grid_map",
     "posterior_ragged", "logpdf_ragged", "mean_ragged", "var_ragged", "mean_and_var_ragged", "loo_ragged", "kfold_ragged",
+    "kfold_large_ragged", "cross_validate_ragged",
     "posterior_columns", "logpdf_columns_map", "posterior_columns_map",
     "mean_and_var_columns", "mean_columns", "mean_and_var_columns_map",
     "cov_map", "mean_and_cov_map",
@@ -827,6 +828,53 @@ def kfold_ragged(f, x, offsets, Sy, y, fold_size):
     if rc != 0:
         raise ValueError(f"blr_kfold_ragged_fold_offsets: argument error {rc}")
     return _heldout_ragged(ops, lambda h, head, tail: h.kfold_ragged(*head, F, *tail), fo, KFold)
+
+
+def _kfold_large_ragged(ops, fold_sizes):
+    """`_heldout_ragged` with blr_kfold_large_ragged_* as its second half; ``fold_sizes``: int64 [nb]"""
+    offsets, nb, D = ops[1], ops[2], ops[6]
+    if D > _KFOLD_LARGE_MAX_D:
+        raise NotImplementedError(f"kfold_large_ragged: D = {D} is beyond the limit of blr_kfold_large_ragged_* (D <= {_KFOLD_LARGE_MAX_D})")
+    fo = np.zeros(nb + 1, dtype=np.int64)
+    rc = _abi.load_library().blr_kfold_large_ragged_fold_offsets(nb, _abi._ptr(offsets), _abi._ptr(fold_sizes), _abi._ptr(fo))
+    if rc != 0:
+        raise ValueError(f"blr_kfold_large_ragged_fold_offsets: argument error {rc} (fold sizes >= 1, at most 1024 folds per regressor)")
+    return _heldout_ragged(ops, lambda h, head, tail: h.kfold_large_ragged(*head, fold_sizes, *tail), fo, KFold)
+
+
+def kfold_large_ragged(f, x, offsets, Sy, y, fold_sizes):
+    """[kfold_large(f_b(x[offsets[b]:offsets[b+1]], Sy_b), y[...], fold_sizes[b])] from packed arrays: `kfold_ragged`'s pipeline with
+    blr_kfold_large_ragged_* as its second half.  ``fold_sizes``: an int (one size for all) or a vector of B of them, each >= 1
+    with at most 1024 folds of its regressor; D <= 128.  Arguments otherwise as `posterior_ragged`; returns a list of
+    KFold(mean, var, logpdf, total).  The first regressor whose prior, noise or posterior is not positive definite raises
+    PosDefException with its position as ``index``.  Given the same state, regressor b's result has the bits of `kfold_large` on
+    that slice; for the states see `kfold_ragged` (handle options NO_I8_GRAM = 1 and NO_WAVE_KERNEL = 1)."""
+    ops, _ = _ragged_operands(f, x, offsets, Sy, y)
+    if ops is None:
+        return []
+    nb = ops[2]
+    fs = np.asarray(fold_sizes)
+    if fs.ndim > 1 or (fs.ndim == 1 and fs.shape[0] != nb) or np.any(fs != np.floor(fs)) or np.any(fs < 1):
+        raise ValueError("fold_sizes must be an integer >= 1 or a vector of B such integers")
+    return _kfold_large_ragged(ops, np.ascontiguousarray(np.broadcast_to(fs.astype(np.int64), (nb,))))
+
+
+def cross_validate_ragged(f, x, offsets, Sy, y, n_folds):
+    """K-fold cross-validation of every packed regressor with ``n_folds`` contiguous folds of its own F_b = ceil(N_b / n_folds)
+    observations (blr_kfold_large_ragged_fold_sizes), in one blr_kfold_large_ragged_* call whatever the F_b are.  Arguments as
+    `kfold_large_ragged`; returns a list of KFold(mean, var, logpdf, total), total the regressor's CV score."""
+    K = int(n_folds)
+    if K != n_folds or K < 1:
+        raise ValueError("n_folds must be an integer >= 1")
+    ops, _ = _ragged_operands(f, x, offsets, Sy, y)
+    if ops is None:
+        return []
+    offsets, nb = ops[1], ops[2]
+    fs = np.zeros(nb, dtype=np.int64)
+    rc = _abi.load_library().blr_kfold_large_ragged_fold_sizes(nb, _abi._ptr(offsets), K, _abi._ptr(fs))
+    if rc != 0:
+        raise ValueError(f"blr_kfold_large_ragged_fold_sizes: argument error {rc} (1 <= n_folds <= 1024)")
+    return _kfold_large_ragged(ops, fs)
 
 
 def logpdf_map(fxs, ys):

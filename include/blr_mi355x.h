@@ -381,6 +381,66 @@ int blr_kfold_ragged_f32(blr_handle* h, int memspace, int layout, int64_t B, int
  * -21 (the output it sizes).  B = 0 writes fold_offsets[0] = 0. */
 int blr_kfold_ragged_fold_offsets(int64_t B, const int64_t* offsets, int64_t F, int64_t* fold_offsets /* HOST, B + 1 entries */);
 
+/* ---- exact LEAVE-FOLD-OUT (K-fold) predictives for LARGE folds of regressors with UNEQUAL observation counts in one call ---------
+ * Replaces: reference src/bayesian_linear_regression.jl:55-58 (logpdf) applied to each held-out FOLD given the rest, under a map
+ * over fxs of different lengths with K folds EACH -- blr_kfold_large_batched_* once per regressor: K folds on unequal counts mean a
+ * fold size per regressor, F_b = ceil(N_b / K), usually far above the 64 of blr_kfold_ragged_* (padding changes the folds).
+ * Packing, state, noise: exactly those of blr_kfold_ragged_* above (offsets: host array, B + 1 entries; y and a diagonal s are read
+ * at + offsets[b], isotropic s at b*strides; dense noise is an argument error; T upper, only its triangle is read; NOT modified).
+ * Folds: regressor b has the folds [f F_b, min((f + 1) F_b, N_b)) of ITS OWN slice with F_b = fold_sizes[b] >= 1 (host array, B
+ * entries); F_b > N_b gives one fold; nfolds_b = ceil(N_b / F_b) <= 1024.  blr_kfold_large_ragged_fold_sizes below computes
+ * F_b = max(1, ceil(N_b / K)).
+ * Outputs: kf_mean and kf_var are packed by observations -- element n of regressor b at index offsets[b] + n; kf_logpdf is packed by
+ * FOLDS -- fold f of regressor b at index fold_offsets[b] + f (blr_kfold_large_ragged_fold_offsets below computes the table;
+ * kf_logpdf holds fold_offsets[B] doubles); kf_total[B] and info[B] are per regressor.  Any of the first four may be NULL; with
+ * kf_total requested and kf_logpdf NULL the log densities go through handle workspace.
+ * The formulas and the precision, the NaN rule, the "kfold_degenerate" statistic, the info rule and its order and "the outputs of a
+ * regressor with info != 0 are left untouched" are those of blr_kfold_large_batched_* (its block below); for diagonal noise the index
+ * i of a non-positive s_i is counted WITHIN the regressor's slice, as in blr_kfold_ragged_*.
+ * N_b = 0 writes nothing per observation or fold, kf_total[b] = 0 and info[b] is the state's status.  B = 0 is a no-op that touches
+ * nothing.  1 <= D <= 128, as blr_kfold_large_batched_*.
+ * Argument errors (negative position; checked before the handle, so a NULL handle with valid arguments returns -1): memspace -2;
+ * layout -3; B outside 0..2^30 -4; D outside 1..128 -5; offsets NULL, offsets[0] < 0, decreasing, a count above 2^30 -6; fold_sizes
+ * NULL with B > 0, an entry < 1, or ceil(N_b / F_b) > 1024 -7; X NULL with observations -8; ldx < D (ColVecs) or
+ * < max(offsets[B], 1) (RowVecs) -9; y NULL with observations -10; noise_kind dense -11; s NULL with observations -12; strides < 0
+ * -13; mw NULL -14; stridemw < 0 -15; T NULL -16; ldt < D -17; strideT < 0 -18; info NULL -23.
+ * Route (csrc/blr_kfold_large_ragged.hpp, csrc/blr_kfold_large_ragged_plan.hpp): the launch list of
+ * blr_kfold_large_batched_* per chunk of regressors with flat grids driven by host-planned tables -- one workgroup per (regressor,
+ * fold, column block) for the statistics, per fold for the factors, per (regressor, fold, tile group) for the predictions; the
+ * kernels run the bodies the equal-count kernels run.  Chunks: consecutive regressors whose statistics, factors and images stay
+ * within 256 MiB each, at most 65535, never fewer than one, option MAX_CHUNK; blr_get_stat "last_chunks".  X is read twice.
+ * offsets, the fold table, the records (40 bytes per regressor) and the items (16 bytes each) are uploaded to the handle's workspace
+ * (counted by blr_get_stat "workspace_bytes", freed by blr_release_workspace).
+ * Bit promises: EVERY output of regressor b -- kf_mean, kf_var, its folds of kf_logpdf and kf_total[b] -- is bit for bit what
+ * blr_kfold_large_batched_* with B = 1, N = N_b, F = F_b writes on that slice.  Hence the bits are independent of B, of the other
+ * regressors' data, counts and fold sizes, of any permutation of the batch, of the chunking (option MAX_CHUNK) and of which outputs
+ * are requested; host and device memspace give the same bits; results are bit-reproducible from call to call; no float atomics.
+ * Async handle, device memspace: the call only enqueues kernels, but the upload of the tables drains the handle's stream first (it
+ * may block the host); the library is finished with the caller's offsets and fold_sizes arrays when the call returns.
+ * _f32: X, y, s, mw, T, kf_mean, kf_var are float; kf_logpdf and kf_total stay double. */
+int blr_kfold_large_ragged_f64(blr_handle* h, int memspace, int layout, int64_t B, int64_t D,
+                               const int64_t* offsets,    /* HOST array of B + 1 entries in both memspaces */
+                               const int64_t* fold_sizes, /* HOST array of B entries in both memspaces */
+                               const double* X, int64_t ldx, const double* y,
+                               int noise_kind, const double* s, int64_t strides,
+                               const double* mw, int64_t stridemw, const double* T, int64_t ldt, int64_t strideT,
+                               double* kf_mean, double* kf_var, double* kf_logpdf, double* kf_total, int32_t* info);
+int blr_kfold_large_ragged_f32(blr_handle* h, int memspace, int layout, int64_t B, int64_t D,
+                               const int64_t* offsets,    /* HOST array of B + 1 entries in both memspaces */
+                               const int64_t* fold_sizes, /* HOST array of B entries in both memspaces */
+                               const float* X, int64_t ldx, const float* y,
+                               int noise_kind, const float* s, int64_t strides,
+                               const float* mw, int64_t stridemw, const float* T, int64_t ldt, int64_t strideT,
+                               float* kf_mean, float* kf_var, double* kf_logpdf, double* kf_total, int32_t* info);
+/* The two tables of blr_kfold_large_ragged_*: host arithmetic only -- no handle, no device.
+ * fold_sizes[b] = max(1, ceil(N_b / K)): K folds per regressor (N_b < K: folds of one; N_b = 0: 1, no fold).  Argument errors: B -4
+ * and offsets -6 as in blr_kfold_large_ragged_*; K outside 1..1024 -3 (its own position); fold_sizes NULL with B > 0 -7.
+ * fold_offsets[0] = 0, fold_offsets[b + 1] = fold_offsets[b] + nfolds_b: what callers size kf_logpdf with.  Argument errors at the
+ * positions of blr_kfold_large_ragged_*: B -4, offsets -6, fold_sizes -7; fold_offsets NULL -21 (the output it sizes). */
+int blr_kfold_large_ragged_fold_sizes(int64_t B, const int64_t* offsets, int64_t K, int64_t* fold_sizes /* HOST out, B entries */);
+int blr_kfold_large_ragged_fold_offsets(int64_t B, const int64_t* offsets, const int64_t* fold_sizes,
+                                        int64_t* fold_offsets /* HOST out, B + 1 entries */);
+
 /* ---- S target columns per regressor in one call: the batched multi-output posterior ---------------------------------
  * Replaces: reference src/bayesian_linear_regression.jl:55-58 (logpdf), :60-69 (posterior) and :72-89 (shared quantities) under a
  * map over fxs with MATRIX targets -- which blr_posterior_batched_* serves only by S calls with the y pointer stepped by one

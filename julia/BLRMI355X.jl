@@ -1098,6 +1098,70 @@ function kfold_ragged!(km::DeviceArray{T}, kv::DeviceArray{T}, kl::DeviceArray{F
     return nothing
 end
 
+function kfold_large_ragged_call(h, ::Type{T}, memspace, layout, B, D, offsets::Vector{Int64}, fold_sizes::Vector{Int64}, X, ldx, y, nk, s,
+                                 strides, mw, stridemw, Tf, ldt, strideT, km, kv, kl, tot, info) where {T<:Elt}
+    GC.@preserve offsets fold_sizes X y s mw Tf km kv kl tot info begin
+        if T === Float64
+            ccall((:blr_kfold_large_ragged_f64, LIB), Cint,
+                  (Ptr{Cvoid}, Cint, Cint, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{T}, Int64, Ptr{T}, Cint, Ptr{T}, Int64, Ptr{T}, Int64,
+                   Ptr{T}, Int64, Int64, Ptr{T}, Ptr{T}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int32}),
+                  h, memspace, layout, B, D, offsets, fold_sizes, X, ldx, y, nk, s, strides, mw, stridemw, Tf, ldt, strideT, km, kv, kl, tot, info)
+        else
+            ccall((:blr_kfold_large_ragged_f32, LIB), Cint,
+                  (Ptr{Cvoid}, Cint, Cint, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{T}, Int64, Ptr{T}, Cint, Ptr{T}, Int64, Ptr{T}, Int64,
+                   Ptr{T}, Int64, Int64, Ptr{T}, Ptr{T}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int32}),
+                  h, memspace, layout, B, D, offsets, fold_sizes, X, ldx, y, nk, s, strides, mw, stridemw, Tf, ldt, strideT, km, kv, kl, tot, info)
+        end
+    end
+end
+
+"""
+    kfold_large_ragged_fold_sizes(offsets, K) -> Vector{Int64}
+
+`F_b = max(1, ceil(N_b / K))`: the fold sizes of K folds per regressor (`blr_kfold_large_ragged_fold_sizes`; host arithmetic only).
+"""
+function kfold_large_ragged_fold_sizes(offsets::Vector{Int64}, K::Integer)
+    B = length(offsets) - 1
+    fs = Vector{Int64}(undef, B)
+    rc = ccall((:blr_kfold_large_ragged_fold_sizes, LIB), Cint, (Int64, Ptr{Int64}, Int64, Ptr{Int64}), B, offsets, K, fs)
+    rc == 0 || error("blr_kfold_large_ragged_fold_sizes: argument $(-rc)")
+    return fs
+end
+
+"""
+    kfold_large_ragged_fold_offsets(offsets, fold_sizes) -> Vector{Int64}
+
+`fold_offsets` of `kfold_large_ragged!`: fold f of regressor b is entry `fold_offsets[b] + f` (0-based) of kf_logpdf, which holds
+`fold_offsets[end]` entries.  Host arithmetic only (`blr_kfold_large_ragged_fold_offsets`).
+"""
+function kfold_large_ragged_fold_offsets(offsets::Vector{Int64}, fold_sizes::Vector{Int64})
+    B = length(offsets) - 1
+    fo = Vector{Int64}(undef, B + 1)
+    rc = ccall((:blr_kfold_large_ragged_fold_offsets, LIB), Cint, (Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}), B, offsets, fold_sizes, fo)
+    rc == 0 || error("blr_kfold_large_ragged_fold_offsets: argument $(-rc)")
+    return fo
+end
+
+"""
+    kfold_large_ragged!(kf_mean, kf_var, kf_logpdf, kf_total, info, X, offsets, fold_sizes, y, s, mw_post, T_post; D, isotropic)
+
+Exact leave-fold-out (K-fold) predictives for LARGE folds of the observations the states of `posterior_ragged!` contain, for
+B = length(offsets) - 1 regressors with UNEQUAL observation counts in one call: regressor b has the contiguous folds of
+`fold_sizes[b]` observations of its own slice (`kfold_large_ragged_fold_sizes` for K folds each); D ≤ 128.  kf_mean and kf_var are
+packed as the inputs are, kf_logpdf by folds (`kfold_large_ragged_fold_offsets`), kf_total and info have B entries.  Reference
+semantics: `:55-58` for each held-out fold given the rest, under a map over fxs of different lengths.
+"""
+function kfold_large_ragged!(km::DeviceArray{T}, kv::DeviceArray{T}, kl::DeviceArray{Float64}, tot::DeviceArray{Float64}, info::DeviceArray{Int32},
+                             X::DeviceArray{T}, offsets::Vector{Int64}, fold_sizes::Vector{Int64}, y::DeviceArray{T}, s::DeviceArray{T},
+                             mw_post::DeviceArray{T}, T_post::DeviceArray{T}; D::Int, isotropic::Bool) where {T<:Elt}
+    h = handle()
+    B = length(offsets) - 1
+    length(fold_sizes) == B || error("fold_sizes must have B = $B entries")
+    check(h, kfold_large_ragged_call(h, T, MEM_DEVICE, COLVECS, B, D, offsets, fold_sizes, X.ptr, D, y.ptr, isotropic ? ISOTROPIC : DIAGONALN,
+                                     s.ptr, isotropic ? 1 : 0, mw_post.ptr, D, T_post.ptr, D, D * D, km.ptr, kv.ptr, kl.ptr, tot.ptr, info.ptr))
+    return nothing
+end
+
 """
     posterior_multi_batched!(mw_post, T_post, logpdf, info, X, Y, s, mw, Λdiag; D, N, S, B, isotropic)
 
