@@ -123,8 +123,8 @@ struct I8Cfg {
   static constexpr int RING_BYTES = NSLOT * SLOT_BYTES;         // 96 KiB
   static constexpr int DIG_BUF = S * 4 * 1024;                  // 24 KiB: [slice][row block of 32][1 KiB fragment]
   static constexpr int OFF_DIG = RING_BYTES;
-  static constexpr int OFF_YB = OFF_DIG + 2 * DIG_BUF;          // y ring: NSLOT x 32 doubles
-  static constexpr int OFF_RW = OFF_YB + NSLOT * KC * 8;        // 1 / sqrt(s_n) ring (diagonal noise): NSLOT x 32 doubles
+  static constexpr int OFF_YB = OFF_DIG + 2 * DIG_BUF;          // end of the digit area (layout anchor of the static asserts below); until round 7 the y ring, NSLOT x 32 doubles:
+  static constexpr int OFF_RW = OFF_YB + NSLOT * KC * 8;        // y and 1 / sqrt(s_n) now reach the slicing in SGPRs (I8SliceSteps) and these 2 x 768 bytes are unused
   static constexpr int OFF_XCH = OFF_RW + NSLOT * KC * 8;       // exchange: 4 x 128 ints (row maxima; sums of squares of digit 3; y'y shares)
   static constexpr int OFF_FLAG = OFF_XCH + 4 * 128 * 4;        // 16 ints
   static constexpr int OFF_OFLAG = OFF_FLAG + 64;               // one byte per 32-column block: some entry outgrew its row's capacity (<= 512 blocks + 32)
@@ -285,13 +285,24 @@ struct I8Slice {
 // is then 32 LDS-DMA pieces of FOUR rows d = 4 p .. 4 p + 3 x 32 observations (16 lanes x 16 bytes per row), and within piece p the pair
 // of observations l16 of row q sits at 16-byte position ((l16 + p) mod 16) 4 + q: a wave reads one pair for 64 consecutive rows,
 // and the rotation by p puts the 16 lanes of every ds_read_b128 group on 16 different slots of the 256-byte bank row.
+// y and, under diagonal noise, 1 / sqrt(s_n) of a wave's column octet are the same for all 64 lanes (cq = wave >> 1): they live in SGPRs
+// (I8ScalarOctet, one s_load_dwordx16 from global memory per k-step and vector) and enter the slicing as the scalar operand of
+// v_fma_f64 / v_mul_f64.  (Until round 7 they came HBM -> LDS by a DMA piece of their own and LDS -> VGPR as broadcast ds_reads: 16 / 32
+// live VGPRs and one lgkmcnt dependency per quad in the pinned schedule.)
+typedef double f64x8 __attribute__((ext_vector_type(8)));
+// Hidden from the compiler like the LDS-DMA pieces (glds_s): for a scalar load IT sees pending, hipcc's wait-count insertion turns every
+// LDS wait into lgkmcnt(0) (scalar loads return out of order), which drains the fragment prefetches of the pinned schedule.  The counted
+// LDS waits stay correct beside a hidden scalar load (LDS returns in order: a count that is one too high only waits for more).  The
+// values are not read before the stream's sload_wait, placed behind the k-step's barrier (the LDS queue is empty there anyway).
+__device__ __forceinline__ void i8_sload8(f64x8& v, uint64_t addr_uniform) { asm volatile("s_load_dwordx16 %0, %1, 0x0" : "=s"(v) : "s"(addr_uniform)); }
+constexpr int kI8SliceReload = 10;  // the chunk before which the NEXT block's y / w are requested: chunk 9 is the last one to read the current ones
+
 template <bool WITH_Q, bool DIAG = false, bool ROWV = false, bool WITH_SQ3 = false>
 struct I8SliceSteps {
-  double x[2][4], y[2][4];  // two column quads: the second quad's LDS reads are in flight while the first is sliced
-  double w[DIAG ? 2 : 1][4];  // diagonal noise: 1 / sqrt(s_n) of the columns (x enters the Gram matrix as x / sqrt(s_n), y as y / sqrt(s_n))
+  double x[2][4];  // two column quads: the second quad's LDS reads are in flight while the first is sliced
   unsigned lo[4], hi[4], u[6], p[2][6];
   template <int Q>
-  __device__ __forceinline__ void load(const char* __restrict__ raw, const double* __restrict__ yb, const double* __restrict__ wb, int r, int cq) {
+  __device__ __forceinline__ void load(const char* __restrict__ raw, int r, int cq) {
     if constexpr (ROWV) {
       typedef double d2 __attribute__((ext_vector_type(2)));
       const int p = r >> 2, q = r & 3;
@@ -307,29 +318,25 @@ struct I8SliceSteps {
 #pragma unroll
       for (int j = 0; j < 4; ++j) x[Q][j] = col[j * 128];
     }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      y[Q][j] = yb[cq * 8 + 4 * Q + j];  // (y: one address per wave, a broadcast)
-      if constexpr (DIAG) w[Q][j] = wb[cq * 8 + 4 * Q + j];
-    }
   }
   // chunk 0: reads of quad 0; chunks 1 + 6 q + c: quad q -- c = 0 reads of quad q + 1, c = 1, 2 magic add / bound check / b and q (two
   // columns each), c = 3, 4 byte transposition, c = 5 digit row sums; chunk 13: digit planes out
+  // ys / ws (SGPRs): y and 1 / sqrt(s_n) (diagonal noise: x enters the Gram matrix as x / sqrt(s_n), y as y / sqrt(s_n)) of the thread's 8 columns
   template <int C>
-  __device__ __forceinline__ void step(const char* __restrict__ raw, const double* __restrict__ yb, const double* __restrict__ wb, char* __restrict__ dig, int r,
+  __device__ __forceinline__ void step(const char* __restrict__ raw, const f64x8& ys, const f64x8& ws, char* __restrict__ dig, int r,
                                        int cq, I8Slice& st) {
     if constexpr (C == 0) {
-      load<0>(raw, yb, wb, r, cq);
+      load<0>(raw, r, cq);
     } else if constexpr (C < 13) {
       constexpr int q = (C - 1) / 6, c = (C - 1) % 6;  // column quad q of the thread's 8 columns
-      if constexpr (c == 0 && q < 1) load<q + 1>(raw, yb, wb, r, cq);
+      if constexpr (c == 0 && q < 1) load<q + 1>(raw, r, cq);
       if constexpr (c == 1 || c == 2) {
         constexpr int j0 = c == 1 ? 0 : 2;
 #pragma unroll
         for (int j = j0; j < j0 + 2; ++j) {
           double xv = x[q][j];
-          if constexpr (DIAG) xv = __dmul_rn(xv, w[q][j]);  // (never contracted into the magic addition: the repair recomputes these bits)
-          const double yv = y[q][j];
+          if constexpr (DIAG) xv = __dmul_rn(xv, ws[4 * q + j]);  // (never contracted into the magic addition: the repair recomputes these bits)
+          const double yv = ys[4 * q + j];
           const double t = __dadd_rn(xv, st.C);
           lo[j] = (unsigned)__double2loint(t);
           hi[j] = (unsigned)__double2hiint(t);
@@ -417,10 +424,10 @@ template <int W> struct I8Dma {
 // sched_group_barrier does not move them: the slicing hangs off LDS reads the group solver leaves where they are).  So the
 // k-step is a compile-time list: MFMA i, then (fenced with sched_barrier) the fragment reads MFMA i + 2 is the first to need
 // and the slicing chunks whose turn it is -- reads of the raw columns first, their arithmetic two MFMAs later.
-template <int NG, int W, bool SLICE, bool WITH_Q, bool DIAG, bool ROWV, typename IssueFn>
-__device__ __forceinline__ void i8_kstep(const char* __restrict__ dig, const char* __restrict__ raw, const double* __restrict__ yb,
-                                         const double* __restrict__ wb, char* __restrict__ dign, int lane, int r, int cq, i32x16 (&A)[I8Plan<NG, W>::NACC], I8Slice& st,
-                                         IssueFn issue_next) {
+template <int NG, int W, bool SLICE, bool WITH_Q, bool DIAG, bool ROWV, typename IssueFn, typename ReloadFn>
+__device__ __forceinline__ void i8_kstep(const char* __restrict__ dig, const char* __restrict__ raw, f64x8& ys, f64x8& ws,
+                                         char* __restrict__ dign, int lane, int r, int cq, i32x16 (&A)[I8Plan<NG, W>::NACC], I8Slice& st,
+                                         IssueFn issue_next, ReloadFn reload_yw) {
   using PL = I8Plan<NG, W>;
   constexpr int NM = PL::NM;
   constexpr int NCH = kI8SliceChunks;
@@ -454,9 +461,10 @@ __device__ __forceinline__ void i8_kstep(const char* __restrict__ dig, const cha
   auto chunk = [&](auto ctag) {
     constexpr int c = decltype(ctag)::value;
 #if defined(BLR_I8_EXP) && BLR_I8_EXP == 3  /* timing experiment: no slicing */
-    if constexpr (false) sl.template step<c>(raw, yb, wb, dign, r, cq, st);
+    if constexpr (false) sl.template step<c>(raw, ys, ws, dign, r, cq, st);
 #else
-    if constexpr (SLICE && c >= 0 && c < NCH) sl.template step<c>(raw, yb, wb, dign, r, cq, st);
+    if constexpr (SLICE && c == kI8SliceReload) reload_yw();  // (into the SGPRs chunk 9 has just read for the last time)
+    if constexpr (SLICE && c >= 0 && c < NCH) sl.template step<c>(raw, ys, ws, dign, r, cq, st);
 #endif
   };
   auto unit = [&](auto itag) {
@@ -509,8 +517,6 @@ __device__ __forceinline__ void i8_gram_stream(char* smem, const BLR_GLOBAL doub
   const int r = tid & 127, cq = tid >> 7;
   char* const ring = smem;
   char* const dig0 = smem + C::OFF_DIG;
-  double* const yring = reinterpret_cast<double*>(smem + C::OFF_YB);
-  double* const wring = reinterpret_cast<double*>(smem + C::OFF_RW);
   int* const xch = reinterpret_cast<int*>(smem + C::OFF_XCH);
   unsigned char* const oflag = reinterpret_cast<unsigned char*>(smem + C::OFF_OFLAG);
   const int nk = N / C::KC;
@@ -524,12 +530,41 @@ __device__ __forceinline__ void i8_gram_stream(char* smem, const BLR_GLOBAL doub
     st.hmax = 0u;
   };
   if (tid < 136) reinterpret_cast<int*>(oflag)[tid] = 0;
-  // LDS-DMA pieces per wave and k-step (I8Dma): its columns (+ the y piece of wave 0, + the 1 / sqrt(s) piece of wave 1 under diagonal noise)
+  // Vector-memory operations per wave and k-step (I8Dma): the LDS-DMA pieces of its columns (+ wave 0: one touch load of the k-step's 32
+  // values of y, + wave 1 under diagonal noise: of 1 / sqrt(s)).  The touch -- one dword per lane, result discarded -- brings the two
+  // 128-byte lines into the L2 three k-steps ahead, so that the scalar loads of the slicing (below) never wait for HBM: a scalar load
+  // shares lgkmcnt with the fragment reads, and every lgkmcnt(0) of the pinned schedule would wait for it.  It takes the slot, and the
+  // place in the vmcnt arithmetic, of the y / w DMA piece that was here until round 7.
   constexpr int NCOL = I8Dma<W>::COLS;
   constexpr int PW = NCOL + (W == 0 ? 1 : 0) + (DIAG && W == 1 ? 1 : 0);
   constexpr bool kTouch = BLR_I8_TOUCH > 0 && NCOL == 0;  // this wave issues no piece: it runs ahead of the stream with touch loads
-  unsigned ring_addr = lds_addr_of(ring), y_addr = lds_addr_of(yring), w_addr = lds_addr_of(wring);
-  asm volatile("" : "+v"(ring_addr), "+v"(y_addr), "+v"(w_addr));
+  unsigned ring_addr = lds_addr_of(ring);
+  asm volatile("" : "+v"(ring_addr));
+  // ---- y / w of this wave's column octet cq = W >> 1 (a compile-time constant: wave W is threads 64 W .. 64 W + 63) in SGPRs: block t of
+  // the stream is the 8 doubles at y + 32 t + 8 cq.  Blocks beyond the last one are clamped to it (like the DMA pieces' `adv`): nothing is
+  // read beyond y + N (N a multiple of 32 here; the last columns of a ragged N are the hand-over's).
+  constexpr int CQ = W >> 1;
+  f64x8 ys = {}, ws = {};
+  const uint64_t ysbase = (uint64_t)(uintptr_t)y + (uint64_t)(CQ * 64), wsbase = (uint64_t)(uintptr_t)rw + (uint64_t)(CQ * 64);
+  auto sload_block = [&](int t) {
+    const uint64_t off = (uint64_t)(unsigned)(t < nk ? t : nk - 1) * (uint64_t)(C::KC * 8);
+    i8_sload8(ys, (uint64_t)uni((int64_t)(ysbase + off)));
+    if constexpr (DIAG) i8_sload8(ws, (uint64_t)uni((int64_t)(wsbase + off)));
+  };
+  // The SGPRs are free for the next block only behind chunk 9, some twenty instructions before the k-step's last fragment waits, which
+  // are lgkmcnt(0): the load has to come back from the scalar cache by then.  So the head of the k-step -- the critical waves 4 - 7 have
+  // no lgkmcnt(0) in its first third -- requests one dword of each 64-byte line (result discarded), which pulls the line L2 -> scalar cache.
+  unsigned sdummy = 0;
+  auto stouch_block = [&](int t) {
+    const uint64_t off = (uint64_t)(unsigned)(t < nk ? t : nk - 1) * (uint64_t)(C::KC * 8);
+    asm volatile("s_load_dword %0, %1, 0x0" : "=s"(sdummy) : "s"((uint64_t)uni((int64_t)(ysbase + off))));
+    if constexpr (DIAG) asm volatile("s_load_dword %0, %1, 0x0" : "=s"(sdummy) : "s"((uint64_t)uni((int64_t)(wsbase + off))));
+  };
+  auto sload_wait = [&]() {
+    if constexpr (DIAG) asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(ys), "+s"(ws), "+s"(sdummy));
+    else asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(ys), "+s"(sdummy));
+  };
+  unsigned ywdummy = 0;
   const uint64_t colbytes = (uint64_t)ldx * 8u;
   // ColVecs: this wave's columns of the k-step being issued.  RowVecs: the k-step's 32 observations of row 0; piece c of
   // this wave = rows 4 (NCOL W + c) .. + 3 (colbytes = the distance between two rows), lane -> (row lane & 3, pair of observations
@@ -554,7 +589,7 @@ __device__ __forceinline__ void i8_gram_stream(char* smem, const BLR_GLOBAL doub
   auto touch = [&](uint64_t base) {
     asm volatile("global_load_dword %0, %1, %2" : "+v"(tdummy) : "v"(voffT), "s"(uni((int64_t)base)) : "memory");
   };
-  // piece c of k-step t -> ring slot t % 3: c = 0 .. NCOL - 1 this wave's columns, c = NCOL the y values (wave 0) and the advance to the
+  // piece c of k-step t -> ring slot t % 3: c = 0 .. NCOL - 1 this wave's columns, c = NCOL the touch of the y values (wave 0) and the advance to the
   // next k-step (pieces are issued in order: the global addresses just run on)
   auto issue_piece = [&](int t, auto ctag) {
     constexpr int c = decltype(ctag)::value;
@@ -566,8 +601,8 @@ __device__ __forceinline__ void i8_gram_stream(char* smem, const BLR_GLOBAL doub
       if constexpr (ROWV) glds_s<16, 64, true>(uni((int64_t)(nextX + (uint64_t)(4 * (NCOL * W + c)) * colbytes)), voffR[c], slot);
       else glds_s<16, 64, true>(uni((int64_t)(nextX + (uint64_t)c * colbytes)), voff, slot);
     } else if constexpr (c == NCOL) {
-      if constexpr (W == 0) glds_s<4, 64>(uni((int64_t)nextY), (unsigned)lane * 4u, y_addr + (unsigned)((t % C::NSLOT) * C::KC * 8));
-      if constexpr (DIAG && W == 1) glds_s<4, 64>(uni((int64_t)nextW), (unsigned)lane * 4u, w_addr + (unsigned)((t % C::NSLOT) * C::KC * 8));
+      if constexpr (W == 0) asm volatile("global_load_dword %0, %1, %2" : "+v"(ywdummy) : "v"((unsigned)lane * 4u), "s"(uni((int64_t)nextY)) : "memory");
+      if constexpr (DIAG && W == 1) asm volatile("global_load_dword %0, %1, %2" : "+v"(ywdummy) : "v"((unsigned)lane * 4u), "s"(uni((int64_t)nextW)) : "memory");
       // (pieces are issued for three k-steps beyond the last one too -- a branch per piece in the k-step split its schedule: 4.73 -> 4.62 ms
       // per 4096 updates without them; they load the last block again, from L2: the addresses stop advancing there)
       const uint64_t adv = (t + 1 < nk) ? ~(uint64_t)0 : (uint64_t)0;
@@ -604,6 +639,7 @@ __device__ __forceinline__ void i8_gram_stream(char* smem, const BLR_GLOBAL doub
     for (int v = 0; v < 16; ++v) A[g][v] = 0;
 
   const int nissue0 = nk < 3 ? nk : 3;
+  sload_block(0);
   for (int t = 0; t < nissue0; ++t) issue(t);
   wait_keep(0);
   __syncthreads();  // the first blocks visible
@@ -664,12 +700,18 @@ __device__ __forceinline__ void i8_gram_stream(char* smem, const BLR_GLOBAL doub
     st.sq3 = 0;
   }
   constexpr bool kQ = (W & 1) == 0;  // (rows 64 (W & 1) + lane: row 0 lives in the even waves)
+  sload_wait();
   {  // block 0 -> digit buffer 0 (nothing to overlap with yet)
     I8SliceSteps<kQ, DIAG, ROWV, NG == 6> sl;
     auto rec = [&](auto self, auto ctag) -> void {
       constexpr int c = decltype(ctag)::value;
       if constexpr (c < kI8SliceChunks) {
-        sl.template step<c>(ring, yring, wring, dig0, r, cq, st);
+        if constexpr (c == kI8SliceReload) {  // (pinned behind chunk 9's reads of the SGPRs like in a k-step)
+          __builtin_amdgcn_sched_barrier(0);
+          sload_block(1);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        sl.template step<c>(ring, ys, ws, dig0, r, cq, st);
         self(self, std::integral_constant<int, c + 1>{});
       }
     };
@@ -678,6 +720,7 @@ __device__ __forceinline__ void i8_gram_stream(char* smem, const BLR_GLOBAL doub
   mark_block(0);
   if (nk > 1) wait_keep(nissue0 - 2 > 0 ? nissue0 - 2 : 0);
   __syncthreads();  // digits of block 0 and raw block 1 visible; raw block 0 consumed by everyone
+  sload_wait();     // y / w of block 1
   I8_STAMP_DECL;
 #ifdef BLR_I8_SETPRIO
   // the second-dispatched half of the workgroup (waves 4 - 7) loses the issue arbitration on its SIMD to its older partner in every
@@ -690,19 +733,22 @@ __device__ __forceinline__ void i8_gram_stream(char* smem, const BLR_GLOBAL doub
     const char* dig = dig0 + (j & 1) * C::DIG_BUF;
     char* dign = dig0 + ((j + 1) & 1) * C::DIG_BUF;
     const char* raw = ring + ((j + 1) % C::NSLOT) * C::SLOT_BYTES;
-    const double* yb = yring + ((j + 1) % C::NSLOT) * C::KC;
-    const double* wb = wring + ((j + 1) % C::NSLOT) * C::KC;
-    // k-step j + 3 goes into the slot of block j, which everybody has sliced before the barrier that ended k-step j - 1
-    i8_kstep<NG, W, true, kQ, DIAG, ROWV>(dig, raw, yb, wb, dign, lane, r, cq, A, st, [&](auto ctag) { issue_piece(j + 3, ctag); });
+    // k-step j + 3 goes into the slot of block j, which everybody has sliced before the barrier that ended k-step j - 1;
+    // ys / ws hold y / w of block j + 1, the block being sliced, and are loaded with those of block j + 2 once it has read them
+    stouch_block(j + 2);
+    i8_kstep<NG, W, true, kQ, DIAG, ROWV>(dig, raw, ys, ws, dign, lane, r, cq, A, st, [&](auto ctag) { issue_piece(j + 3, ctag); },
+                                          [&]() { sload_block(j + 2); });
     mark_block(j + 1);
     I8_STAMP(0);
     // end of k-step j: raw block j + 2 must have landed (k-step j + 3 may stay in flight), then everybody's is visible
     wait_keep(1);
     __syncthreads();
+    sload_wait();  // (the barrier has drained the LDS queue: this waits for the scalar loads alone)
     I8_STAMP(2);
   }
-  i8_kstep<NG, W, false, kQ, DIAG, ROWV>(dig0 + ((nk - 1) & 1) * C::DIG_BUF, ring, yring, wring, dig0, lane, r, cq, A, st, [](auto) {});
+  i8_kstep<NG, W, false, kQ, DIAG, ROWV>(dig0 + ((nk - 1) & 1) * C::DIG_BUF, ring, ys, ws, dig0, lane, r, cq, A, st, [](auto) {}, []() {});
   wait_keep(0);  // (the pieces issued beyond the last k-step land in a ring that is about to be reused)
+  if constexpr (W == 0 || (DIAG && W == 1)) asm volatile("" ::"v"(ywdummy));  // (the y / w touch loads' destination register: reserved until they have all returned)
   if constexpr (kTouch) asm volatile("" ::"v"(tdummy));  // (the touch loads' destination register stays reserved until they have all returned)
 #ifdef BLR_I8_SETPRIO
   if constexpr (W >= 4) __builtin_amdgcn_s_setprio(0);
