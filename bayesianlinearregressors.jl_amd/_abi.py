@@ -100,6 +100,9 @@ for _suf in ("f64", "f32"):
     _SIGS[f"blr_update_factor_{_suf}"] = (
         [_H, _int, _int, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _int, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _vp], _int)
     _SIGS[f"blr_downdate_factor_{_suf}"] = _SIGS[f"blr_update_factor_{_suf}"]  # the same signature
+    _SIGS[f"blr_update_factor_ragged_{_suf}"] = (
+        [_H, _int, _int, _i64, _i64, _vp, _vp, _i64, _vp, _int, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _vp], _int)
+    _SIGS[f"blr_downdate_factor_ragged_{_suf}"] = _SIGS[f"blr_update_factor_ragged_{_suf}"]  # the same signature
     _SIGS[f"blr_update_multi_factor_{_suf}"] = (
         [_H, _int, _int, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _int, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _i64,
          _vp, _i64, _vp], _int)
@@ -280,7 +283,8 @@ class Handle:
 
     def get_stat(self, key):
         """Counter of this handle: "i8_regressors", "i8_handed_back", "planes_redone", "loo_degenerate", "kfold_degenerate" (folds
-        blr_kfold_batched_* / blr_kfold_multi_batched_* / blr_kfold_large_batched_* gave NaN), "workspace_bytes", "last_chunks" (chunks / slices of regressors of the most recent call: option MAX_CHUNK caps their size), and the variance route of the most recent
+        blr_kfold_batched_* / blr_kfold_multi_batched_* / blr_kfold_large_batched_* gave NaN), "workspace_bytes", "last_chunks" (chunks / slices of regressors of the most recent call: option MAX_CHUNK caps their size), "ragged_sweep" / "ragged_refit" / "ragged_idle" (regressors on each
+        list of the most recent update_factor_ragged / downdate_factor_ragged call), and the variance route of the most recent
         marginals_batched call: "marg_block_rt" (tile height 32 / 16 of marg_blocksub_kernel, 0 = the call ran elsewhere), "marg_block_walk"
         (tiles its busiest workgroup walked), "marg_block_renumbered" (1 = a launch renumbered its workgroups per XCD) (blr_get_stat)."""
         v = _i64()
@@ -426,6 +430,29 @@ class Handle:
         fn = getattr(self.lib, f"blr_downdate_factor_{suffix(dtype)}")
         return self.check(fn(self._h, memspace, layout, B, D, k, _ptr(X), ldx, strideX, _ptr(y), stridey, noise_kind, _ptr(s),
                              strides, _ptr(mw), stridemw, _ptr(T), ldt, strideT, _ptr(logpdf), _ptr(info)))
+
+    def _revise_ragged(self, name, dtype, memspace, layout, B, D, offsets, X, ldx, y, noise_kind, s, strides, mw, stridemw, T, ldt,
+                       strideT, logpdf, info):
+        fn = getattr(self.lib, f"blr_{name}_factor_ragged_{suffix(dtype)}")
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        if offsets.shape != (B + 1,):
+            raise ValueError(f"offsets must have B + 1 = {B + 1} entries, got shape {offsets.shape}")
+        return self.check(fn(self._h, memspace, layout, B, D, _ptr(offsets), _ptr(X), ldx, _ptr(y), noise_kind, _ptr(s), strides,
+                             _ptr(mw), stridemw, _ptr(T), ldt, strideT, _ptr(logpdf), _ptr(info)))
+
+    def update_factor_ragged(self, dtype, memspace, layout, B, D, offsets, X, ldx, y, noise_kind, s, strides, mw, stridemw, T, ldt,
+                             strideT, logpdf, info):
+        """In-place update of B resident states (mw, T) that received unequal numbers of observations (none included), packed as
+        `posterior_ragged` packs them; include/blr_mi355x.h blr_update_factor_ragged_*."""
+        return self._revise_ragged("update", dtype, memspace, layout, B, D, offsets, X, ldx, y, noise_kind, s, strides, mw, stridemw,
+                                   T, ldt, strideT, logpdf, info)
+
+    def downdate_factor_ragged(self, dtype, memspace, layout, B, D, offsets, X, ldx, y, noise_kind, s, strides, mw, stridemw, T, ldt,
+                               strideT, logpdf, info):
+        """In-place downdate (forget observations) of B resident states (mw, T), unequal numbers of observations per state, packed as
+        `posterior_ragged` packs them; include/blr_mi355x.h blr_downdate_factor_ragged_*."""
+        return self._revise_ragged("downdate", dtype, memspace, layout, B, D, offsets, X, ldx, y, noise_kind, s, strides, mw, stridemw,
+                                   T, ldt, strideT, logpdf, info)
 
     def update_multi_factor(self, dtype, memspace, layout, B, D, k, S, X, ldx, strideX, Y, ldY, strideY, noise_kind, s, strides, M, ldm,
                             strideM, T, ldt, strideT, logpdf, stride_lp, info):

@@ -44,6 +44,7 @@
 #include "blr_kfold_multi.hpp"
 #include "blr_kfold_ragged.hpp"
 #include "blr_kfold_large_ragged.hpp"
+#include "blr_revise_ragged.hpp"
 #include "blr_host.hpp"
 #include "blr_large_plan.hpp"
 
@@ -3497,20 +3498,12 @@ int ragged_one_by_one(blr_handle* h, int64_t B, const int64_t* offsets, One one)
   return 0;
 }
 
-// D <= 128: offsets and the longest-first order go to the handle's metadata buffer (ragged_meta_upload), then ONE launch: the
-// kernel is only enqueued.
+// One launch of fused_ragged_kernel over the r.p.B regressors r.order lists (r.offsets, r.order: on the device); the kernel is only
+// enqueued.  r.p.B is the length of the list and nothing else: the kernel indexes every array by the regressor it reads from the list.
 template <typename T>
-int ragged_launch(blr_handle* h, RaggedArgs<T>& r, const int64_t* offsets) {
+int ragged_enqueue(blr_handle* h, RaggedArgs<T>& r) {
   const int64_t B = r.p.B;
-  std::vector<int32_t> order((size_t)B);
-  for (int64_t b = 0; b < B; ++b) order[(size_t)b] = (int32_t)b;
-  std::stable_sort(order.begin(), order.end(), [offsets](int32_t i, int32_t j) { return offsets[i + 1] - offsets[i] > offsets[j + 1] - offsets[j]; });
-  const char* dev[2];
-  int rc = ragged_meta_upload(h, {{offsets, ragged_table_bytes(B)}, {order.data(), (size_t)B * sizeof(int32_t)}}, dev);
-  if (rc) return rc;
-  r.offsets = reinterpret_cast<const int64_t*>(dev[0]);
-  r.order = reinterpret_cast<const int32_t*>(dev[1]);
-
+  int rc;
   const int NB = (r.p.D + 15) / 16;
   const bool vec_ok = r.p.layout == BLR_LAYOUT_COLVECS && r.p.D % Mfma<T>::VEC == 0 && aligned16(r.p.X, r.p.ldx, 0) && !h->opt.no_ldsdma;
   const int mode = r.p.layout == BLR_LAYOUT_ROWVECS ? 1 : (vec_ok ? 4 : 0);
@@ -3524,6 +3517,20 @@ int ragged_launch(blr_handle* h, RaggedArgs<T>& r, const int64_t* offsets) {
   h->route = h->route_buf.c_str();
   h->route_i8_B = 0;
   return 0;
+}
+
+// D <= 128: offsets and the longest-first order go to the handle's metadata buffer (ragged_meta_upload), then ONE launch
+template <typename T>
+int ragged_launch(blr_handle* h, RaggedArgs<T>& r, const int64_t* offsets) {
+  const int64_t B = r.p.B;
+  std::vector<int32_t> order((size_t)B);
+  for (int64_t b = 0; b < B; ++b) order[(size_t)b] = (int32_t)b;
+  std::stable_sort(order.begin(), order.end(), [offsets](int32_t i, int32_t j) { return offsets[i + 1] - offsets[i] > offsets[j + 1] - offsets[j]; });
+  const char* dev[2];
+  if (const int rc = ragged_meta_upload(h, {{offsets, ragged_table_bytes(B)}, {order.data(), (size_t)B * sizeof(int32_t)}}, dev)) return rc;
+  r.offsets = reinterpret_cast<const int64_t*>(dev[0]);
+  r.order = reinterpret_cast<const int32_t*>(dev[1]);
+  return ragged_enqueue<T>(h, r);
 }
 
 template <typename T>
@@ -3593,6 +3600,110 @@ int posterior_ragged(blr_handle* h, int memspace, int layout, int64_t B, int64_t
                                      a.logpdf ? a.logpdf + b : (double*)nullptr, a.info + b);
        })))
     return rc;
+  return io.finish();
+}
+
+// ---- condition / forget on resident states with unequal counts (blr_revise_ragged.hpp, blr_revise_ragged_plan.hpp) ----
+// One front for the pair (DOWN: forget).  The plan's lists and offsets go to the metadata buffer in one upload; then the idle fill, one
+// launch per chunk of the sweep list and -- update only -- one launch of fused_ragged_kernel per chunk of the refit list, in place.
+template <typename T, bool DOWN>
+int revise_ragged(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, const int64_t* offsets, const T* X, int64_t ldx, const T* y,
+                  int noise_kind, const T* s, int64_t strides, T* mw, int64_t stridemw, T* Tf, int64_t ldt, int64_t strideT, double* logpdf,
+                  int32_t* info) {
+  RaggedFront f;
+  if (const int rc = ragged_front(h, f, memspace, layout, B, D, offsets, X, ldx, noise_kind, strides)) return rc;
+  const bool diag = f.diag;
+  if (f.any && !y) return bad_arg(h, 9, "y is NULL (reference :74 length check)");
+  if (noise_kind != BLR_NOISE_ISOTROPIC && noise_kind != BLR_NOISE_DIAGONAL)
+    return bad_arg(h, 10, "noise_kind (isotropic or diagonal; a resident state is not revised under a dense Sigma_y)");
+  if (!s && (noise_kind == BLR_NOISE_ISOTROPIC || f.any)) return bad_arg(h, 11, "s is NULL");
+  if (strides < 0) return bad_arg(h, 12, "strides < 0");
+  if (!mw) return bad_arg(h, 13, "mw is NULL");
+  if (B > 1 && stridemw < D) return bad_arg(h, 14, "stridemw < D");
+  if (!Tf) return bad_arg(h, 15, "T is NULL");
+  if (ldt < D) return bad_arg(h, 16, "ldt < D");
+  if (B > 1 && strideT < (int64_t)mat_extent(D, D, ldt)) return bad_arg(h, 17, "strideT too small");
+  if (B > 0 && !info) return bad_arg(h, 19, "info is NULL");
+  if (B == 0) return 0;
+  if (!h) return -1;
+  HIP_TRY(h, hipSetDevice(h->device));
+  ReviseRaggedPlan plan;
+  plan_revise_ragged(offsets, B, D, DOWN, h->opt, plan);
+  const int64_t ns = (int64_t)plan.sweep.size(), nr = (int64_t)plan.refit.size();
+  h->ragged_lists = {ns, nr, (int64_t)plan.idle.size()};
+  h->last_chunks = plan.last_chunks;
+
+  ReviseRaggedArgs<T> r{};
+  SweepArgs<T>& a = r.s;
+  a.ldx = ldx; a.layout = layout; a.strides = diag ? 0 : strides; a.noise_kind = noise_kind;
+  a.stridemw = stridemw; a.ldt = ldt; a.strideT = strideT; a.D = (int)D;
+  CallIO io(h, memspace);
+  int rc;
+  if ((rc = io.in(X, f.x_all, &a.X))) return rc;
+  if ((rc = io.in(y, f.n_all, &a.y))) return rc;
+  if ((rc = io.in(s, f.s_all, &a.s))) return rc;
+  if ((rc = io.out(mw, extent(B, stridemw, (size_t)D), &a.mw))) return rc;
+  if ((rc = io.out(Tf, extent(B, strideT, mat_extent(D, D, ldt)), &a.Tf))) return rc;
+  if ((rc = io.out(logpdf, (size_t)B, &a.logpdf))) return rc;
+  if ((rc = io.out(info, (size_t)B, &a.info))) return rc;
+  // no data at all (or, host memspace, nothing staged): never dereferenced, but keep the pointers valid
+  if (!a.X) a.X = a.mw;
+  if (!a.y) a.y = a.mw;
+  if (!a.s) a.s = a.mw;
+
+  const char* dev[3];
+  if ((rc = ragged_meta_upload(h, {{offsets, ragged_table_bytes(B)}, {plan.sweep.data(), (size_t)ns * sizeof(int32_t)},
+                                   {plan.refit.data(), (size_t)nr * sizeof(int32_t)}}, dev)))
+    return rc;
+  r.offsets = reinterpret_cast<const int64_t*>(dev[0]);
+  const int32_t* const sweep_dev = reinterpret_cast<const int32_t*>(dev[1]);
+  const int32_t* const refit_dev = reinterpret_cast<const int32_t*>(dev[2]);
+  if (!plan.idle.empty()) {
+    hipLaunchKernelGGL(revise_ragged_idle_kernel, dim3((unsigned)std::min<int64_t>((B + kThreads - 1) / kThreads, 1024)), dim3(kThreads), 0,
+                       h->stream, r.offsets, B, a.logpdf, a.info);
+    HIP_TRY(h, hipGetLastError());
+  }
+  if (plan.serial) {
+    // correct, not fast: the equal-count entry point with B = 1 on each active regressor's slice and state
+    if ((rc = ragged_one_by_one(h, B, offsets, [&](int64_t b, int64_t o, int64_t n) {
+           if (n == 0) return 0;
+           const auto one = DOWN ? downdate_factor<T> : update_factor<T>;
+           return one(h, BLR_MEM_DEVICE, layout, 1, D, n, a.X + (f.colv ? o * ldx : o), ldx, 0, a.y + o, 0, noise_kind,
+                      diag ? a.s + o : a.s + b * strides, 0, a.mw + b * stridemw, 0, a.Tf + b * strideT, ldt, 0,
+                      a.logpdf ? a.logpdf + b : (double*)nullptr, a.info + b);
+         })))
+      return rc;
+    h->last_chunks = plan.last_chunks;  // (the nested calls counted their own)
+    return io.finish();
+  }
+  if (ns > 0) {
+    void (*const kern)(ReviseRaggedArgs<T>) = DOWN ? downdate_ragged_kernel<T> : update_ragged_sweep_kernel<T>;
+    const int lds = DOWN ? downdate_lds_bytes<T>((int)D) : sweep_lds_bytes<T>((int)D);
+    if ((rc = set_lds_once(h, kern, (size_t)lds))) return rc;
+    for (int64_t c0 = 0; c0 < ns; c0 += plan.chunk) {
+      r.list = sweep_dev + c0;
+      hipLaunchKernelGGL(kern, dim3((unsigned)std::min<int64_t>(plan.chunk, ns - c0)), dim3(kThreads), lds, h->stream, r);
+    }
+    HIP_TRY(h, hipGetLastError());
+    h->route = DOWN ? "downdate_ragged_kernel" : "update_ragged_sweep_kernel";
+    h->route_i8_B = 0;
+  }
+  if (nr > 0) {
+    // the SAME state re-factored in place, the old factor entering as D pseudo-observations (what blr_update_factor_* does for k >= 2)
+    RaggedArgs<T> g{};
+    PosteriorArgs<T>& p = g.p;
+    p.X = a.X; p.ldx = ldx; p.y = a.y; p.s = a.s; p.strides = a.strides;
+    p.mw = a.mw; p.stridemw = stridemw; p.Lw = a.Tf; p.ldl = ldt; p.strideLw = strideT;
+    p.mw_post = a.mw; p.stride_mwpost = stridemw; p.T_post = a.Tf; p.ldt = ldt; p.strideT = strideT;
+    p.logpdf = a.logpdf; p.info = a.info;
+    p.layout = layout; p.noise_kind = noise_kind; p.prior_kind = BLR_PRIOR_UPPER_FACTOR; p.D = (int)D;
+    g.offsets = r.offsets;
+    for (int64_t c0 = 0; c0 < nr; c0 += plan.chunk) {
+      p.B = (int)std::min<int64_t>(plan.chunk, nr - c0);
+      g.order = refit_dev + c0;
+      if ((rc = ragged_enqueue<T>(h, g))) return rc;
+    }
+  }
   return io.finish();
 }
 
@@ -5308,6 +5419,10 @@ int blr_get_stat(blr_handle* h, const char* key, int64_t* value) {
   if (!value) return bad_arg(h, 3, "value is NULL");
   if (!strcmp(key, "i8_regressors")) { *value = (int64_t)h->i8_attempted; return 0; }
   if (!strcmp(key, "last_chunks")) { *value = h->last_chunks; return 0; }  // chunks / slices of regressors of the most recent call
+  // the plan of the most recent blr_update_factor_ragged_* / blr_downdate_factor_ragged_* call: regressors per list
+  if (!strcmp(key, "ragged_sweep")) { *value = h->ragged_lists[0]; return 0; }
+  if (!strcmp(key, "ragged_refit")) { *value = h->ragged_lists[1]; return 0; }
+  if (!strcmp(key, "ragged_idle")) { *value = h->ragged_lists[2]; return 0; }
   // the variance route of the most recent blr_marginals_batched_* call (host-side, set next to marg_blocksub_kernel's launches)
   if (!strcmp(key, "marg_block_rt")) { *value = h->marg_block.rt; return 0; }
   if (!strcmp(key, "marg_block_walk")) { *value = h->marg_block.walk; return 0; }
@@ -5444,6 +5559,20 @@ int blr_timer_stop(blr_handle* h, float* elapsed_ms) {
                                 int64_t ldt, int64_t strideT, double* logpdf, int32_t* info) {                      \
     return downdate_factor<T>(h, memspace, layout, B, D, k, X, ldx, strideX, y, stridey, noise_kind, s, strides,    \
                               mw, stridemw, Tf, ldt, strideT, logpdf, info);                                         \
+  }                                                                                                                 \
+  int blr_update_factor_ragged_##SUF(blr_handle* h, int memspace, int layout, int64_t B, int64_t D,                 \
+                                     const int64_t* offsets, const T* X, int64_t ldx, const T* y, int noise_kind,   \
+                                     const T* s, int64_t strides, T* mw, int64_t stridemw, T* Tf, int64_t ldt,      \
+                                     int64_t strideT, double* logpdf, int32_t* info) {                              \
+    return revise_ragged<T, false>(h, memspace, layout, B, D, offsets, X, ldx, y, noise_kind, s, strides, mw,       \
+                                   stridemw, Tf, ldt, strideT, logpdf, info);                                       \
+  }                                                                                                                 \
+  int blr_downdate_factor_ragged_##SUF(blr_handle* h, int memspace, int layout, int64_t B, int64_t D,               \
+                                       const int64_t* offsets, const T* X, int64_t ldx, const T* y, int noise_kind, \
+                                       const T* s, int64_t strides, T* mw, int64_t stridemw, T* Tf, int64_t ldt,    \
+                                       int64_t strideT, double* logpdf, int32_t* info) {                            \
+    return revise_ragged<T, true>(h, memspace, layout, B, D, offsets, X, ldx, y, noise_kind, s, strides, mw,        \
+                                  stridemw, Tf, ldt, strideT, logpdf, info);                                        \
   }                                                                                                                 \
   int blr_loo_batched_##SUF(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t N, const T* X,  \
                             int64_t ldx, int64_t strideX, const T* y, int64_t stridey, int noise_kind, const T* s, \

@@ -56,12 +56,15 @@ __host__ __device__ constexpr int downdate_lds_scalars(int D, int item) { return
 template <typename T>
 __host__ __device__ constexpr int downdate_lds_bytes(int D) { return downdate_lds_scalars(D, (int)sizeof(T)) + 64; }
 
+// The downdate of ONE regressor by its workgroup: state `reg` of a's arrays, its k observations at Xg / yg / sg (sg: k variances
+// under diagonal noise, one otherwise).  a.X, a.y, a.s, their strides and a.k are not read here: downdate_lds_kernel takes the
+// slice from them, downdate_ragged_kernel (blr_revise_ragged.hpp) from the packed arrays and `offsets`.  k must be uniform over the
+// workgroup: it bounds the loop whose barriers every wave meets, and iscr[1] -- read by every wave after the same barrier -- is
+// the loop's only other exit.
 template <typename T>
-__global__ __launch_bounds__(kThreads) void downdate_lds_kernel(SweepArgs<T> a) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
+__device__ __forceinline__ void downdate_lds_body(char* smem, const SweepArgs<T>& a, int64_t reg, const T* Xg, const T* yg, const T* sg, int k) {
   const int D = a.D, tid = threadIdx.x, lane = tid & 63;
   const int wave = uni(tid >> 6);
-  const int64_t reg = blockIdx.x;
   T* const R = reinterpret_cast<T*>(smem);                // packed rows: row j at off(j), columns j..D (column D = u_j)
   T* const mv = R + (D + 1) * (D + 2) / 2;                // m [D] (the ORIGINAL mean; the offset d goes to column D)
   T* const cs = mv + (D + 1);                             // rotation cosines c_j
@@ -71,9 +74,6 @@ __global__ __launch_bounds__(kThreads) void downdate_lds_kernel(SweepArgs<T> a) 
   auto off = [&](int j) { return j * (D + 1) - (j * (j - 1)) / 2 - j; };  // R[off(j) + col] = element (j, col)
   const T* Tg = a.Tf + reg * a.strideT;
   T* mg = a.mw + reg * a.stridemw;
-  const T* Xg = a.X + reg * a.strideX;
-  const T* yg = a.y + reg * a.stridey;
-  const T* sg = a.s + reg * a.strides;
   const bool diag = a.noise_kind == NOISE_DIAGONAL;
   if (tid == 0) { iscr[0] = 0x7fffffff; iscr[1] = 0; }
   __syncthreads();
@@ -92,7 +92,7 @@ __global__ __launch_bounds__(kThreads) void downdate_lds_kernel(SweepArgs<T> a) 
   if (wave == 0) {
     // the noise is checked for all k observations before any is removed (reference :79 comes before :86)
     int bad_noise = 0x7fffffff;
-    for (int i = lane; i < a.k; i += 64) {
+    for (int i = lane; i < k; i += 64) {
       const T si = diag ? sg[i] : sg[0];
       if (!(si > T(0)) && bad_noise == 0x7fffffff) bad_noise = i + 1;
       logs += log((double)(si > T(0) ? si : T(1)));
@@ -112,7 +112,7 @@ __global__ __launch_bounds__(kThreads) void downdate_lds_kernel(SweepArgs<T> a) 
   }
   __syncthreads();  // (st0 read by every wave before wave 0 may write the status again)
   // iscr[1] changes only in wave 0 between the two barriers of an iteration and is read by all after the first: uniform
-  for (int i = 0; i < (st0 == 0 ? a.k : 0); ++i) {
+  for (int i = 0; i < (st0 == 0 ? k : 0); ++i) {
     if (wave == 0) {
       const T si = diag ? sg[i] : sg[0];
       const T rs = fast_rsqrt(si);
@@ -193,7 +193,7 @@ __global__ __launch_bounds__(kThreads) void downdate_lds_kernel(SweepArgs<T> a) 
     if (has0) mg[c0] = mv[c0] + u0;
     if (has1) mg[c1] = mv[c1] + u1;
     const double kLog2Pi = 1.8378770664093454835606594728112;
-    logpdf = -0.5 * ((double)a.k * kLog2Pi + logs + 2.0 * (logd0 - logd1) + quad);
+    logpdf = -0.5 * ((double)k * kLog2Pi + logs + 2.0 * (logd0 - logd1) + quad);
   }
   if (bad == 0) {
     for (int e = tid; e < D * D; e += kThreads) {
@@ -205,6 +205,13 @@ __global__ __launch_bounds__(kThreads) void downdate_lds_kernel(SweepArgs<T> a) 
     a.info[reg] = bad;
     if (a.logpdf) a.logpdf[reg] = bad ? __longlong_as_double(0x7ff8000000000000LL) : logpdf;
   }
+}
+
+template <typename T>
+__global__ __launch_bounds__(kThreads) void downdate_lds_kernel(SweepArgs<T> a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int64_t reg = blockIdx.x;
+  downdate_lds_body<T>(smem, a, reg, a.X + reg * a.strideX, a.y + reg * a.stridey, a.s + reg * a.strides, a.k);
 }
 
 // ---- global-memory route -------------------------------------------------------------------------------------------------

@@ -227,6 +227,9 @@ struct blr_handle {
   int64_t last_chunks = 0;               // chunks / slices of regressors the most recent call launched (blr_get_stat "last_chunks"): 1 at
                                          // every entry, then whatever the call's chunk loop counts
   void count_chunks(int64_t B, int64_t chunk) { last_chunks = (B + chunk - 1) / chunk; }
+  // blr_update_factor_ragged_* / blr_downdate_factor_ragged_*: the list lengths of the most recent call's plan (blr_get_stat
+  // "ragged_sweep" / "ragged_refit" / "ragged_idle"; blr_revise_ragged_plan.hpp)
+  std::array<int64_t, 3> ragged_lists{};
   // The variance route of the most recent blr_marginals_batched_* call (blr_get_stat "marg_block_rt" / "marg_block_walk" /
   // "marg_block_renumbered"): tile height of marg_blocksub_kernel (0: the call ran elsewhere), trips of its busiest workgroup
   // (the largest ceil(ntiles / grid.x) over the call's launches), and whether any launch met the kernel's renumbering condition

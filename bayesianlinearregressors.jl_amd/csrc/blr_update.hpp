@@ -42,12 +42,14 @@ struct SweepArgs {
 template <typename T>
 __host__ __device__ constexpr int sweep_lds_bytes(int D) { return ((D + 1) * (D + 2) / 2 + 2 * (D + 1)) * (int)sizeof(T) + 64; }  // rows + m + d + flags
 
+// The sweep of ONE regressor by its workgroup: state `reg` of a's arrays, its k observations at Xg / yg / sg (sg: k variances
+// under diagonal noise, one otherwise).  a.X, a.y, a.s, their strides and a.k are not read here: rank1_sweep_kernel takes the
+// slice from them, update_ragged_sweep_kernel (blr_revise_ragged.hpp) from the packed arrays and `offsets`.  k is uniform over the
+// workgroup.
 template <typename T>
-__global__ __launch_bounds__(kThreads) void rank1_sweep_kernel(SweepArgs<T> a) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
+__device__ __forceinline__ void rank1_sweep_body(char* smem, const SweepArgs<T>& a, int64_t reg, const T* Xg, const T* yg, const T* sg, int k) {
   const int D = a.D, tid = threadIdx.x, lane = tid & 63;
   const int wave = uni(tid >> 6);
-  const int64_t reg = blockIdx.x;
   T* const R = reinterpret_cast<T*>(smem);                // packed rows: row j at off(j), columns j..D (column D = u_j)
   T* const mv = R + (D + 1) * (D + 2) / 2;                // m [D]
   T* const dv = mv + (D + 1);                             // d [D]
@@ -75,14 +77,11 @@ __global__ __launch_bounds__(kThreads) void rank1_sweep_kernel(SweepArgs<T> a) {
     double logd0 = 0.0;
     for (int j = lane; j < D; j += 64) logd0 += log((double)R[off(j) + j]);
     logd0 = wave_allreduce(logd0);
-    const T* Xg = a.X + reg * a.strideX;
-    const T* yg = a.y + reg * a.stridey;
-    const T* sg = a.s + reg * a.strides;
     const bool diag = a.noise_kind == NOISE_DIAGONAL;
     const int c0 = lane, c1 = lane + 64;
     const bool has0 = c0 < D, has1 = c1 < D;
     double quad = 0.0, logs = 0.0;
-    for (int i = 0; i < a.k; ++i) {
+    for (int i = 0; i < k; ++i) {
       // the new row, scaled: the lane owns columns lane, lane + 64 and (lane 0 only) column D = the rhs entry e
       const T si = diag ? sg[i] : sg[0];
       if (!(si > T(0)) && bad_noise == 0) bad_noise = i + 1;  // reference :79: cholesky(Sigma_y) throws
@@ -136,7 +135,7 @@ __global__ __launch_bounds__(kThreads) void rank1_sweep_kernel(SweepArgs<T> a) {
     if (has0) dv[c0] = u0;
     if (has1) dv[c1] = u1;
     const double kLog2Pi = 1.8378770664093454835606594728112;
-    logpdf = -0.5 * ((double)a.k * kLog2Pi + logs + 2.0 * (logd1 - logd0) + quad);
+    logpdf = -0.5 * ((double)k * kLog2Pi + logs + 2.0 * (logd1 - logd0) + quad);
     if (lane == 0) iscr[1] = bad_noise;
   }
   __syncthreads();
@@ -153,6 +152,13 @@ __global__ __launch_bounds__(kThreads) void rank1_sweep_kernel(SweepArgs<T> a) {
     a.info[reg] = bad;
     if (a.logpdf) a.logpdf[reg] = bad ? __longlong_as_double(0x7ff8000000000000LL) : logpdf;
   }
+}
+
+template <typename T>
+__global__ __launch_bounds__(kThreads) void rank1_sweep_kernel(SweepArgs<T> a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int64_t reg = blockIdx.x;
+  rank1_sweep_body<T>(smem, a, reg, a.X + reg * a.strideX, a.y + reg * a.stridey, a.s + reg * a.strides, a.k);
 }
 
 }  // namespace blr

@@ -2164,6 +2164,118 @@ class ResidentPosterior:
         return BasisFunctionRegressor(post, self.phi) if self.phi is not None else post
 
 
+class ResidentPosteriorBatch:
+    """B posteriors kept ON THE DEVICE as one pair of buffers (mw [B x D], T [B x D x D]) and conditioned IN PLACE, each on its own
+    number of new observations -- none included -- in one library call: the step an online or bandit loop takes after a round of
+    draws, where most regressors saw nothing, some one observation and a few several (blr_update_factor_ragged_* /
+    blr_downdate_factor_ragged_*).
+
+        st = ResidentPosteriorBatch([f] * B)                        # or B posteriors
+        lp = st.condition(ColVecs(X), offsets, 0.1, y)              # regressor b receives X[:, offsets[b]:offsets[b + 1]]
+        lp = st.forget(ColVecs(X), offsets, 0.1, y)                 # ... and gives them back
+
+    ``fs``: B BayesianLinearRegressors of one dimension with one kind of prior precision; the states are created the way
+    `ResidentPosterior` creates one (a PDMat's factor is copied, a Diagonal or dense precision is factorised by the library on
+    zero observations).  ``x``, ``offsets``, ``Sy``, ``y``: packed as `posterior_ragged` takes them."""
+
+    def __init__(self, fs):
+        fs = list(fs)
+        if not fs or not all(isinstance(g, BayesianLinearRegressor) for g in fs):
+            raise TypeError("ResidentPosteriorBatch wraps a non-empty list of BayesianLinearRegressors")
+        dtype = np.float32 if all(_dtype_of(g.mw) == np.float32 for g in fs) else np.float64
+        B, D = len(fs), fs[0].mw.shape[0]
+        self.dtype, self.D, self.B = dtype, D, B
+        h = self._h = _handle()
+        item = np.dtype(dtype).itemsize
+        self._mw = _DeviceBuffer.of(h, np.stack([_mean_vector(g.mw, D, dtype) for g in fs]))
+        self._T = _DeviceBuffer(h, B * D * D * item)
+        # the packed operands of condition / forget come from _ragged_operands with one stand-in prior: the state is on the device
+        self._proto = BayesianLinearRegressor(np.zeros(D, dtype=dtype), Diagonal(np.ones(D, dtype=dtype)))
+        priors = [_prior(g.Lw, D, dtype) for g in fs]
+        if len({(k, isinstance(g.Lw, PDMat)) for (_, k, _), g in zip(priors, fs)}) != 1:
+            raise ValueError("the regressors must share one kind of prior precision")
+        _, prior_kind, ldl = priors[0]
+        if isinstance(fs[0].Lw, PDMat):
+            for b, (U, _, _) in enumerate(priors):
+                k = _first_nonpositive(np.diag(U))  # a factor with a non-positive diagonal is not a Cholesky factor
+                if k:
+                    e = _abi.PosDefException(k)
+                    e.index = b
+                    raise e
+            h.memcpy_h2d(self._T.ptr, np.stack([np.triu(q[0]).reshape(-1, order="F") for q in priors]))
+            return
+        # Diagonal / dense precisions: T_b = chol(Lw_b).U by the library's own factorisation, the posterior update on ZERO observations
+        Lb = np.stack([q[0].reshape(-1, order="A") for q in priors])
+        d_Lw = _DeviceBuffer.of(h, Lb)
+        d_one = _DeviceBuffer.of(h, np.ones(1, dtype=dtype))
+        d_info = _DeviceBuffer.of(h, np.zeros(B, dtype=np.int32))
+        info = np.zeros(B, dtype=np.int32)
+        try:
+            h.posterior_batched(dtype, _abi.MEM_DEVICE, _abi.LAYOUT_COLVECS, B, D, 0, None, max(D, 1), 0, None, 0,
+                                _abi.NOISE_ISOTROPIC, d_one.ptr, 0, prior_kind, self._mw.ptr, D, d_Lw.ptr, ldl, Lb.shape[1],
+                                None, D, self._T.ptr, max(D, 1), D * D, None, max(D, 1), D * D, None, d_info.ptr)
+            h.memcpy_d2h(info, d_info.ptr)
+        finally:
+            for b in (d_Lw, d_one, d_info):
+                b.free()
+        _raise_first_failed(info)
+
+    def _revise(self, call, x, offsets, Sy, y):
+        dtype, h, D, B = self.dtype, self._h, self.D, self.B
+        if y is None or Sy is None:
+            raise ValueError("condition / forget need the targets y and the noise Sy")
+        ops, _ = _ragged_operands(self._proto, x, offsets, Sy, np.ascontiguousarray(y, dtype=dtype))
+        if ops is None or ops[2] != B:
+            raise ValueError(f"offsets must have B + 1 = {B + 1} entries")
+        _, offsets, _, X, layout, ldx, Dx, y, s, noise_kind, strides = ops[:11]
+        if Dx != D:
+            raise ValueError(f"dimension of the inputs ({Dx}) != length(mw) = {D}")
+        temps = []
+
+        def dev(a):
+            temps.append(_DeviceBuffer.of(h, a))
+            return temps[-1].ptr
+
+        lp, info = np.zeros(B, dtype=np.float64), np.zeros(B, dtype=np.int32)
+        try:
+            d_lp, d_info = dev(lp), dev(info)
+            call(dtype, _abi.MEM_DEVICE, layout, B, D, offsets, dev(X.reshape(-1, order="A")), ldx, dev(y), noise_kind, dev(s), strides,
+                 self._mw.ptr, D, self._T.ptr, max(D, 1), D * D, d_lp, d_info)
+            h.memcpy_d2h(lp, d_lp)
+            h.memcpy_d2h(info, d_info)
+        finally:
+            for b in temps:
+                b.free()
+        _raise_first_failed(info)
+        return lp
+
+    def condition(self, x, offsets, Sy, y):
+        """In-place update of every state with its own slice of the packed observations; returns the B log densities
+        log p(y_b | everything state b was conditioned on so far), 0 for a regressor without observations.  The first regressor whose
+        state or noise is not positive definite raises PosDefException with its position as ``index``: its state is untouched, the
+        other regressors have been updated."""
+        return self._revise(self._h.update_factor_ragged, x, offsets, Sy, y)
+
+    def forget(self, x, offsets, Sy, y):
+        """In-place DOWNDATE of every state by its own slice of the packed observations, which the state must contain; returns the B
+        log densities log p(y_b | the data that remains).  The first regressor whose removal would leave a precision that is not
+        positive definite raises PosDefException with its position as ``index``: its state is untouched, the others are downdated."""
+        return self._revise(self._h.downdate_factor_ragged, x, offsets, Sy, y)
+
+    def state(self):
+        """host copies (mw [B, D], T [B, D, D]) of the resident states; T[b] the upper factor of regressor b"""
+        mw = np.empty((self.B, self.D), dtype=self.dtype)
+        T = np.empty((self.B, self.D, self.D), dtype=self.dtype)
+        self._h.memcpy_d2h(mw, self._mw.ptr)
+        self._h.memcpy_d2h(T, self._T.ptr)
+        return mw, np.triu(T.transpose(0, 2, 1))  # (the device keeps each factor column-major)
+
+    def regressors(self):
+        """The current states as B BayesianLinearRegressors (precision carried by its factor, reference :93)."""
+        mw, T = self.state()
+        return [BayesianLinearRegressor(mw[b], PDMat(np.asfortranarray(T[b]))) for b in range(self.B)]
+
+
 class ResidentColumnsPosterior:
     """The S column posteriors of a matrix target kept ON THE DEVICE as one state (M, T): M the D x S block of means, T the ONE upper
     factor of the precision they share -- what `posterior_columns` returns -- conditioned IN PLACE on further observations with S

@@ -101,7 +101,10 @@ const char* blr_last_route(blr_handle* h);
  * blr_kfold_multi_batched_* (once per fold, whatever S is) gave NaN because the Cholesky of their I - H~ met a pivot <= 0 or not finite, and folds blr_kfold_large_batched_* gave NaN because that of their
  * A - G_f did (reading it synchronises the handle's stream); "last_chunks" = chunks / slices of regressors the handle's most
  * recent call launched (NOT cumulative: every entry point starts it at 1; a batch beyond grid.y = 65535, a workspace or image bound, or
- * option MAX_CHUNK, goes in several); "workspace_bytes" = device scratch the handle holds now.
+ * option MAX_CHUNK, goes in several; blr_update_factor_ragged_* / blr_downdate_factor_ragged_* count the launches of their
+ * regressors with observations, 0 when there is none); "ragged_sweep", "ragged_refit", "ragged_idle" = regressors on each route of
+ * the handle's most recent blr_update_factor_ragged_* / blr_downdate_factor_ragged_* call (NOT cumulative; host-side integers);
+ * "workspace_bytes" = device scratch the handle holds now.
  * The variance route of the handle's most recent blr_marginals_batched_* call (NOT cumulative; host-side integers): "marg_block_rt"
  * = 32 or 16, the tile height of marg_blocksub_kernel (block forward substitution on LDS-resident tiles of inputs: D > 128, 16 | D,
  * aligned ColVecs, factor or dense prior, D <= 1152 in fp32 / 512 in fp64), or 0 when the call ran anywhere else (diagonal prior,
@@ -933,6 +936,67 @@ int blr_downdate_factor_f32(blr_handle* h, int memspace, int layout, int64_t B, 
                             int64_t ldx, int64_t strideX, const float* y, int64_t stridey, int noise_kind, const float* s,
                             int64_t strides, float* mw, int64_t stridemw, float* T, int64_t ldt, int64_t strideT,
                             double* logpdf, int32_t* info);
+
+/* ---- update / DOWNDATE of resident states that received UNEQUAL numbers of observations, in one call ---------------------
+ * Replaces: reference test/bayesian_linear_regression.jl:49-70 ("repeated conditioning", posterior(f'b(X_b, S_b), y_b)) under a map
+ * over posteriors that each received a different number of observations -- most of them none: the step of an online or bandit
+ * loop after a round of draws.  Without it the caller groups the regressors by count, gathers each group's states, calls
+ * blr_update_factor_* / blr_downdate_factor_* once per distinct k and scatters the results back, or loops over B = 1 calls.
+ * Packing of X, y and diagonal s: exactly blr_posterior_ragged_*'s.  offsets: HOST array of B + 1 non-decreasing entries in both
+ * memspaces; regressor b owns observations [offsets[b], offsets[b+1]), k_b = their number (0 allowed; at most 2^30).  Isotropic
+ * noise is read at s + b * strides; dense noise is an argument error.  State, updated IN PLACE: mw[B][D] at stridemw and the upper
+ * factors T[B] (D x D, ldt) at strideT, with the stride rules of blr_update_factor_*; the strictly-lower part of T is never
+ * read (the re-factorisation route overwrites it with zeros, as blr_update_factor_* does; the other routes leave it alone).
+ * Per regressor the call means the equal-count entry point with B = 1, k = k_b on the regressor's slice:
+ *   update:    logpdf[b] = log p(y_b | state before the call);   downdate: logpdf[b] = log p(y_b | state after the call);
+ *   info[b]: the equal-count codes in the same order (factor, noise, posterior), observation indices counted inside the regressor's
+ *   own slice (1-based).  info[b] != 0: the state of b is bit-for-bit untouched and logpdf[b] is NaN; the other regressors are not
+ *   affected and the call returns 0.
+ *   k_b = 0: the state keeps its bits and is not inspected, logpdf[b] = 0, info[b] = 0 (blr_update_multi_factor_*'s k = 0).
+ * Every info[b] and every requested logpdf[b] (logpdf may be NULL) is written, idle regressors included, in both memspaces.
+ * Returns 0 or -(position of the bad argument); the argument checks come before the handle's (a NULL handle with valid arguments:
+ * -1), B = 0 is a no-op.  offsets is copied to the device with the plan's lists: the stream is drained once per call, and the
+ * caller's offsets array is free when the call returns, on an async handle too.
+ * Routes (csrc/blr_revise_ragged_plan.hpp).  The route of a regressor follows from (D, k_b, options) alone, never from
+ * B or from the other regressors.  One workgroup per regressor with observations, longest first; idle regressors cost none.
+ *   update, D <= 128:   k_b = 1: the Givens sweep of blr_update_factor_* (update_ragged_sweep_kernel); k_b >= 2: the state
+ *     re-factored in place by blr_posterior_ragged_*'s kernel.  SWEEP=always: k_b <= 16 sweeps; SWEEP=never: every one re-factors.
+ *   downdate, D <= 128: blr_downdate_factor_*'s LDS body for every k_b (downdate_ragged_kernel).
+ *   D > 128, or a downdate under NO_DOWNDATE_LDS: correct, not fast -- the regressors with observations go one after the other
+ *     through the equal-count entry point with B = 1; the call synchronises.
+ *   Option MAX_CHUNK caps the regressors per launch; blr_get_stat "last_chunks" counts the launches of regressors with observations
+ *   (0 when there is none), "ragged_sweep" / "ragged_refit" / "ragged_idle" the regressors on each route of the most recent call
+ *   (a downdate counts its regressors under "ragged_sweep").
+ * Bit promises.  Sweep route and downdate: regressor b has bit for bit what blr_update_factor_* (on a SWEEP=always handle) /
+ * blr_downdate_factor_* with B = 1, k = k_b writes on its slice.  Re-factorisation route: the bits of blr_posterior_ragged_* with
+ * BLR_PRIOR_UPPER_FACTOR in place (mw_post = mw, T_post = Lw = T) on that slice.  Either way independent of B, of a permutation of
+ * the batch, of the other regressors' data and counts and of MAX_CHUNK; host and device memspace give the same bits; reproducible
+ * from call to call; no float atomics.
+ * Limits: 1 <= D <= 8192, isotropic or diagonal noise, single-output states. */
+int blr_update_factor_ragged_f64(blr_handle* h, int memspace, int layout, int64_t B, int64_t D,
+                                 const int64_t* offsets, /* HOST, B + 1 entries, both memspaces */
+                                 const double* X, int64_t ldx, const double* y,
+                                 int noise_kind, const double* s, int64_t strides,
+                                 double* mw, int64_t stridemw, double* T, int64_t ldt, int64_t strideT,
+                                 double* logpdf, int32_t* info);
+int blr_update_factor_ragged_f32(blr_handle* h, int memspace, int layout, int64_t B, int64_t D,
+                                 const int64_t* offsets, /* HOST, B + 1 entries, both memspaces */
+                                 const float* X, int64_t ldx, const float* y,
+                                 int noise_kind, const float* s, int64_t strides,
+                                 float* mw, int64_t stridemw, float* T, int64_t ldt, int64_t strideT,
+                                 double* logpdf, int32_t* info);
+int blr_downdate_factor_ragged_f64(blr_handle* h, int memspace, int layout, int64_t B, int64_t D,
+                                   const int64_t* offsets, /* HOST, B + 1 entries, both memspaces */
+                                   const double* X, int64_t ldx, const double* y,
+                                   int noise_kind, const double* s, int64_t strides,
+                                   double* mw, int64_t stridemw, double* T, int64_t ldt, int64_t strideT,
+                                   double* logpdf, int32_t* info);
+int blr_downdate_factor_ragged_f32(blr_handle* h, int memspace, int layout, int64_t B, int64_t D,
+                                   const int64_t* offsets, /* HOST, B + 1 entries, both memspaces */
+                                   const float* X, int64_t ldx, const float* y,
+                                   int noise_kind, const float* s, int64_t strides,
+                                   float* mw, int64_t stridemw, float* T, int64_t ldt, int64_t strideT,
+                                   double* logpdf, int32_t* info);
 
 /* ---- rank-k update / DOWNDATE of a resident MULTI-OUTPUT state: one factor, S mean columns ------------------------------
  * blr_update_multi_factor_* replaces: reference test/bayesian_linear_regression.jl:49-70 ("repeated conditioning") and

@@ -1049,6 +1049,65 @@ function loo_ragged!(lm::DeviceArray{T}, lv::DeviceArray{T}, ll::DeviceArray{Flo
     return nothing
 end
 
+# blr_update_factor_ragged_* / blr_downdate_factor_ragged_* (include/blr_mi355x.h): resident states that received unequal numbers
+# of observations, revised in place in one call; `down`: forget
+function revise_ragged_call(h, ::Type{T}, down::Bool, memspace, layout, B, D, offsets::Vector{Int64}, X, ldx, y, nk, s, strides, mw,
+                            stridemw, Tf, ldt, strideT, lp, info) where {T<:Elt}
+    GC.@preserve offsets X y s mw Tf lp info begin
+        if T === Float64 && !down
+            ccall((:blr_update_factor_ragged_f64, LIB), Cint,
+                  (Ptr{Cvoid}, Cint, Cint, Int64, Int64, Ptr{Int64}, Ptr{T}, Int64, Ptr{T}, Cint, Ptr{T}, Int64, Ptr{T}, Int64,
+                   Ptr{T}, Int64, Int64, Ptr{Cdouble}, Ptr{Int32}),
+                  h, memspace, layout, B, D, offsets, X, ldx, y, nk, s, strides, mw, stridemw, Tf, ldt, strideT, lp, info)
+        elseif T === Float64
+            ccall((:blr_downdate_factor_ragged_f64, LIB), Cint,
+                  (Ptr{Cvoid}, Cint, Cint, Int64, Int64, Ptr{Int64}, Ptr{T}, Int64, Ptr{T}, Cint, Ptr{T}, Int64, Ptr{T}, Int64,
+                   Ptr{T}, Int64, Int64, Ptr{Cdouble}, Ptr{Int32}),
+                  h, memspace, layout, B, D, offsets, X, ldx, y, nk, s, strides, mw, stridemw, Tf, ldt, strideT, lp, info)
+        elseif !down
+            ccall((:blr_update_factor_ragged_f32, LIB), Cint,
+                  (Ptr{Cvoid}, Cint, Cint, Int64, Int64, Ptr{Int64}, Ptr{T}, Int64, Ptr{T}, Cint, Ptr{T}, Int64, Ptr{T}, Int64,
+                   Ptr{T}, Int64, Int64, Ptr{Cdouble}, Ptr{Int32}),
+                  h, memspace, layout, B, D, offsets, X, ldx, y, nk, s, strides, mw, stridemw, Tf, ldt, strideT, lp, info)
+        else
+            ccall((:blr_downdate_factor_ragged_f32, LIB), Cint,
+                  (Ptr{Cvoid}, Cint, Cint, Int64, Int64, Ptr{Int64}, Ptr{T}, Int64, Ptr{T}, Cint, Ptr{T}, Int64, Ptr{T}, Int64,
+                   Ptr{T}, Int64, Int64, Ptr{Cdouble}, Ptr{Int32}),
+                  h, memspace, layout, B, D, offsets, X, ldx, y, nk, s, strides, mw, stridemw, Tf, ldt, strideT, lp, info)
+        end
+    end
+end
+
+"""
+    update_factor_ragged!(mw, T_factor, logpdf, info, X, offsets, y, s; D, isotropic)
+    downdate_factor_ragged!(mw, T_factor, logpdf, info, X, offsets, y, s; D, isotropic)
+
+Condition (or forget) B = length(offsets) - 1 RESIDENT states in place, each on its own number of observations -- none included --
+in one call: mw is D×B, T_factor D×D×B (upper factors), X D×offsets[end] (ColVecs), y packed likewise, s holds B variances
+(`isotropic`) or offsets[end]; `offsets` as `posterior_ragged!` takes it.  logpdf (B, Float64): log p(y_b | state before) for the
+update, log p(y_b | state after) for the downdate, 0 for a regressor without observations; info (B, Int32): a state whose info is
+not 0 is untouched.  Reference semantics per regressor: "repeated conditioning", test/bayesian_linear_regression.jl:49-70.
+"""
+function update_factor_ragged!(mw::DeviceArray{T}, Tf::DeviceArray{T}, lp::DeviceArray{Float64}, info::DeviceArray{Int32},
+                               X::DeviceArray{T}, offsets::Vector{Int64}, y::DeviceArray{T}, s::DeviceArray{T}; D::Int,
+                               isotropic::Bool) where {T<:Elt}
+    h = handle()
+    B = length(offsets) - 1
+    check(h, revise_ragged_call(h, T, false, MEM_DEVICE, COLVECS, B, D, offsets, X.ptr, D, y.ptr, isotropic ? ISOTROPIC : DIAGONALN, s.ptr,
+                                isotropic ? 1 : 0, mw.ptr, D, Tf.ptr, D, D * D, lp.ptr, info.ptr))
+    return nothing
+end
+
+function downdate_factor_ragged!(mw::DeviceArray{T}, Tf::DeviceArray{T}, lp::DeviceArray{Float64}, info::DeviceArray{Int32},
+                                 X::DeviceArray{T}, offsets::Vector{Int64}, y::DeviceArray{T}, s::DeviceArray{T}; D::Int,
+                                 isotropic::Bool) where {T<:Elt}
+    h = handle()
+    B = length(offsets) - 1
+    check(h, revise_ragged_call(h, T, true, MEM_DEVICE, COLVECS, B, D, offsets, X.ptr, D, y.ptr, isotropic ? ISOTROPIC : DIAGONALN, s.ptr,
+                                isotropic ? 1 : 0, mw.ptr, D, Tf.ptr, D, D * D, lp.ptr, info.ptr))
+    return nothing
+end
+
 function kfold_ragged_call(h, ::Type{T}, memspace, layout, B, D, offsets::Vector{Int64}, F, X, ldx, y, nk, s, strides, mw, stridemw,
                            Tf, ldt, strideT, km, kv, kl, tot, info) where {T<:Elt}
     GC.@preserve offsets X y s mw Tf km kv kl tot info begin
