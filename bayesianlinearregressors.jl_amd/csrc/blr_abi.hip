@@ -1723,7 +1723,8 @@ int logpdf_grad_batched(blr_handle* h, int memspace, int layout, int64_t B, int6
                        (const T*)img2);
     if (dmw_d)
       hipLaunchKernelGGL(grad_reduce_kernel<T>, dim3((unsigned)B), dim3(kPB), 0, h->stream, (const double*)part, (int)per_reg,
-                         dmw_d, stridedmw, (int)D);
+                         dmw_d, stridedmw, (int)D, (const T*)mwp_d, smp, a.mw, a.Lw, GradPrior{prior_kind, ldl, strideLw, stridemw}, (const T*)Tf,
+                         (const int32_t*)info_d);
   } else {
     auto kern = logpdf_grad_kernel<T>;
     const int lds = TC::LDS_BYTES + (kPB + 3 * TC::RB) * (int)sizeof(T);
@@ -1736,7 +1737,8 @@ int logpdf_grad_batched(blr_handle* h, int memspace, int layout, int64_t B, int6
     }
     if (dmw_d)
       hipLaunchKernelGGL(grad_reduce_kernel<T>, dim3((unsigned)B), dim3(kPB), 0, h->stream, (const double*)part, (int)per_reg,
-                         dmw_d, stridedmw, (int)D);
+                         dmw_d, stridedmw, (int)D, (const T*)mwp_d, smp, a.mw, a.Lw, GradPrior{prior_kind, ldl, strideLw, stridemw}, (const T*)Tf,
+                         (const int32_t*)info_d);
   }
   HIP_TRY(h, hipGetLastError());
   return io.finish();

@@ -2444,14 +2444,99 @@ __global__ __launch_bounds__(kThreads) void logpdf_grad_kernel(GradArgs<T> a) {
   if (a.dmw_part && tid < kPB) a.dmw_part[((int64_t)reg * gridDim.x + blockIdx.x) * kPB + tid] = dmw_acc;
 }
 
-// dmw[reg][c] = sum over the workgroup partials, fixed order
+// dmw[reg] from the workgroup partials (summed in a fixed order) and one step of refinement in double.
+// The sum S = X W (y - X'mw~) is taken at the ROUNDED posterior mean mw~ = mw + m~: with m* the exact shift, S = Lw m* - X W X'(m~ - m*)
+// carries the mean's rounding times the data precision, while P = Lw m~ = Lw m* + Lw (m~ - m*) carries it times the prior precision --
+// where the data dominate (a cancelling sum: D = 1, N = 65 loses 50 ulps in fp32) S is poor, where the prior dominates P is.  Their
+// difference is the residual of the normal equations, S - P = A (m* - m~), so  dmw = Lw m* = P + Lw A^-1 (S - P)  with the factor
+// the sweeps used (A = T'T): D^2 work per regressor, no second pass over X.
+struct GradPrior {
+  int kind; int64_t ldl, strideLw, stridemw;
+};
 template <typename T>
-__global__ __launch_bounds__(kPB) void grad_reduce_kernel(const double* part, int nparts, T* dmw, int64_t stridedmw, int D) {
-  const int reg = blockIdx.x, c = threadIdx.x;
-  if (c >= D) return;
+__device__ void grad_apply_prior(const T* Lw, const GradPrior& p, int D, const double* v, double* t, double* out, int c) {
+  // out = Lw v (dense: the upper triangle of a symmetric matrix; upper factor: U'(U v); diagonal); all threads call
   double acc = 0.0;
-  for (int g = 0; g < nparts; ++g) acc += part[((int64_t)reg * nparts + g) * kPB + c];
-  dmw[(int64_t)reg * stridedmw + c] = (T)acc;
+  if (p.kind == PRIOR_DIAGONAL) {
+    if (c < D) acc = (double)Lw[c] * v[c];
+  } else if (p.kind == PRIOR_DENSE) {
+    if (c < D)
+      for (int j = 0; j < D; ++j) acc += (double)(j >= c ? Lw[(int64_t)j * p.ldl + c] : Lw[(int64_t)c * p.ldl + j]) * v[j];
+  } else {
+    if (c < D)
+      for (int j = c; j < D; ++j) acc += (double)Lw[(int64_t)j * p.ldl + c] * v[j];
+    __syncthreads();
+    if (c < D) t[c] = acc;
+    __syncthreads();
+    acc = 0.0;
+    if (c < D)
+      for (int k = 0; k <= c; ++k) acc += (double)Lw[(int64_t)c * p.ldl + k] * t[k];
+  }
+  __syncthreads();
+  if (c < D) out[c] = acc;
+  __syncthreads();
+}
+
+template <typename T>
+__global__ __launch_bounds__(kPB) void grad_reduce_kernel(const double* part, int nparts, T* dmw, int64_t stridedmw, int D, const T* mwp,
+                                                          int64_t stridemwp, const T* mw, const T* Lw_all, GradPrior p, const T* U_all,
+                                                          const int32_t* info) {
+  __shared__ double m[kPB], P[kPB], rho[kPB], t[kPB];
+  const int reg = blockIdx.x, c = threadIdx.x;
+  if (info[reg] != 0) {  // (uniform per workgroup) a failed regressor: zeros, as the partials of its workgroups are
+    if (c < D) dmw[(int64_t)reg * stridedmw + c] = T(0);
+    return;
+  }
+  const T* Lw = Lw_all + (int64_t)reg * p.strideLw;
+  const T* U = U_all + (int64_t)reg * D * D;  // upper factor, column-major, ld = D: T(k, i) = U[i D + k], k <= i
+  double S = 0.0;
+  if (c < D) {
+    for (int g = 0; g < nparts; ++g) S += part[((int64_t)reg * nparts + g) * kPB + c];
+    m[c] = (double)mwp[(int64_t)reg * stridemwp + c] - (double)mw[(int64_t)reg * p.stridemw + c];
+  }
+  __syncthreads();
+  grad_apply_prior<T>(Lw, p, D, m, t, P, c);
+  if (c < D) rho[c] = S - P[c];
+  __syncthreads();
+  // the two substitutions: one barrier per column (a thread keeps its own entry in a register, the pivot's goes through LDS), the
+  // factor's entries of eight columns loaded ahead of the chain (forward: the thread's own column, contiguous; backward: rows of
+  // eight columns, consecutive threads at consecutive addresses), reciprocal pivots once
+  if (c < D) t[c] = 1.0 / (double)U[(int64_t)c * D + c];
+  double r = c < D ? rho[c] : 0.0;
+  __syncthreads();
+  for (int i0 = 0; i0 < D; i0 += 8) {  // T'u = rho: u_i = rho_i / T_ii, then rho_c -= T(i, c) u_i for c > i
+    double col[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) col[e] = (c < D && i0 + e < c) ? (double)U[(int64_t)c * D + i0 + e] : 0.0;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const int i = i0 + e;
+      if (i < D) {  // (uniform)
+        if (c == i) { r *= t[i]; rho[i] = r; }  // (r stays u_c: the backward substitution starts from it)
+        __syncthreads();
+        if (c > i) r -= col[e] * rho[i];
+      }
+    }
+  }
+  for (int i0 = ((D - 1) | 7); i0 >= 0; i0 -= 8) {  // T d = u, columns i0, i0 - 1, ..: d_i = u_i / T_ii, then u_c -= T(c, i) d_i for c < i
+    double col[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) col[e] = (i0 - e < D && c < i0 - e) ? (double)U[(int64_t)(i0 - e) * D + c] : 0.0;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const int i = i0 - e;
+      if (i < D) {  // (uniform)
+        if (c == i) m[i] = r * t[i];
+        __syncthreads();
+        if (c < i) r -= col[e] * m[i];
+      }
+    }
+  }
+  __syncthreads();
+  if (c < D) rho[c] = m[c];
+  __syncthreads();
+  grad_apply_prior<T>(Lw, p, D, rho, t, m, c);  // (m is free: P holds Lw m~)
+  if (c < D) dmw[(int64_t)reg * stridedmw + c] = (T)(P[c] + m[c]);
 }
 
 // ---- gradient for D > 128: the kernels around the two sweeps over the tall matrix [F ; X' ; I] ---------------------------

@@ -798,7 +798,11 @@ int blr_posterior_rff_f32(blr_handle* h, int memspace, int64_t Din, int64_t D, i
  *   dmw[D]               dL/dmw
  *   mw_post[D], Ainv     posterior mean and A^-1 = (Lw + X S X')^-1 (D x D, ldai): the caller forms
  *                        dL/dLw = -(m m' + Ainv - Lw^-1)/2 with m = mw_post - mw (D x D host work)
- * Any output except logpdf/info may be NULL.  Arguments up to strideLw are those of blr_posterior_batched_*. */
+ * Any output except logpdf/info may be NULL.  Arguments up to strideLw are those of blr_posterior_batched_*, except that N >= 1
+ * (N = 0 is an argument error).  A regressor with info[b] != 0 (as blr_posterior_batched_* reports it) gets logpdf[b] = NaN and
+ * dmw = 0; its dX, dy, ds, mw_post and Ainv are left untouched -- on either device route; the call still returns 0.
+ * mw_post must NOT alias mw here (the in-place form blr_posterior_batched_* allows): dmw is refined from mw_post - mw after the
+ * posterior has been written (one step in double, dmw = P + Lw A^-1 (X S r - P) with P = Lw (mw_post - mw)). */
 int blr_logpdf_grad_batched_f64(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, int64_t N,
                                 const double* X, int64_t ldx, int64_t strideX, const double* y, int64_t stridey,
                                 int noise_kind, const double* s, int64_t strides, int prior_kind, const double* mw,
