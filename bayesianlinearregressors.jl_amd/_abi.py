@@ -19,6 +19,9 @@ LAYOUT_COLVECS, LAYOUT_ROWVECS = 0, 1
 NOISE_ISOTROPIC, NOISE_DIAGONAL, NOISE_DENSE = 0, 1, 2
 PRIOR_DENSE, PRIOR_UPPER_FACTOR, PRIOR_DIAGONAL = 0, 1, 2
 MEM_HOST, MEM_DEVICE = 0, 1
+# bits of Handle.get_stat("draw_route") (csrc/blr_host.hpp DrawRoute): the weights kernel, then the projection
+DRAW_W_DIAG, DRAW_W_MFMA, DRAW_W_UVEC, DRAW_W_LARGE, DRAW_W_BATCHED_NS1, DRAW_W_BATCHED_NS4 = 1, 2, 4, 8, 16, 32
+DRAW_P_FUSED, DRAW_P_SCALAR, DRAW_P_MFMA = 64, 128, 256
 MULTI_COLS_PER_PASS = 64  # csrc/blr_multi.hpp kMultiColsPerPass: column slots of one pass of multi_cols_kernel (slot 0 = column 0)
 MARG_COLS_PER_PASS = 16  # csrc/blr_marg_multi.hpp kMargColsPerPass: mean columns of one pass of marginals_cols_kernel
 LOO_COLS_PER_PASS = 16  # csrc/blr_loo_multi.hpp kLooColsPerPass (= kMargColsPerPass): columns of one pass of loo_cols_kernel
@@ -286,7 +289,10 @@ class Handle:
         blr_kfold_batched_* / blr_kfold_multi_batched_* / blr_kfold_large_batched_* gave NaN), "workspace_bytes", "last_chunks" (chunks / slices of regressors of the most recent call: option MAX_CHUNK caps their size), "ragged_sweep" / "ragged_refit" / "ragged_idle" (regressors on each
         list of the most recent update_factor_ragged / downdate_factor_ragged call), and the variance route of the most recent
         marginals_batched call: "marg_block_rt" (tile height 32 / 16 of marg_blocksub_kernel, 0 = the call ran elsewhere), "marg_block_walk"
-        (tiles its busiest workgroup walked), "marg_block_renumbered" (1 = a launch renumbered its workgroups per XCD) (blr_get_stat)."""
+        (tiles its busiest workgroup walked), "marg_block_renumbered" (1 = a launch renumbered its workgroups per XCD), and the kernels of
+        the most recent sample_weights / apply_weights / rand / rand_batched call: "draw_route", a bitmask of the DRAW_* constants of
+        this module -- one weights bit (DRAW_W_UVEC rides on DRAW_W_MFMA: the 16-byte loader of the factor at D = 128) and at most one
+        projection bit (none: no projection ran) (blr_get_stat)."""
         v = _i64()
         self.check(self.lib.blr_get_stat(self._h, str(key).encode(), C.byref(v)))
         return int(v.value)

@@ -1943,10 +1943,12 @@ template <typename T>
 int sample_weights_large(blr_handle* h, int64_t D, int64_t S, int prior_kind, const T* mw, const T* Lw, int64_t ldl,
                          const T* Z, int64_t ldz, T* W, int64_t ldw) {
   if (prior_kind == BLR_PRIOR_DIAGONAL) {
+    h->draw_route |= blr_handle::DRAW_W_DIAG;
     hipLaunchKernelGGL(diag_sample_kernel<T>, dim3(1024), dim3(kThreads), 0, h->stream, mw, Lw, Z, ldz, W, ldw, (int)D, S);
     HIP_TRY(h, hipGetLastError());
     return 0;
   }
+  h->draw_route |= blr_handle::DRAW_W_LARGE;
   const int DP = (int)((D + kPB - 1) / kPB * kPB), NC = DP / kPB;
   const int64_t chunk = std::min<int64_t>(S, 1024);
   Carve carve;
@@ -2019,8 +2021,12 @@ int sample_weights_impl(blr_handle* h, CallIO& io, int64_t D, int64_t S, int pri
     if (hinfo != 0) return hinfo;
   }
   if (kind == BLR_PRIOR_DIAGONAL) {
+    h->draw_route |= blr_handle::DRAW_W_DIAG;
     hipLaunchKernelGGL(diag_sample_kernel<T>, dim3(1024), dim3(kThreads), 0, h->stream, mw_d, U, Z_d, ldz, W_d, ldw, (int)D, S);
   } else {  // draws as rows of an LDS block, one backward MFMA sweep per tile of draws
+    // (the stat repeats the predicate of the kernel's 16-byte loader of U; the kernel decides for itself)
+    const bool uvec = D == kPB && (ldu % Mfma<T>::VEC) == 0 && ((uintptr_t)U % 16) == 0;
+    h->draw_route |= blr_handle::DRAW_W_MFMA | (uvec ? blr_handle::DRAW_W_UVEC : 0);
     using TC = TrsmCfg<T>;
     const int lds = TC::LDS_BYTES + kPB * (int)sizeof(T);
     auto kern = sample_weights_mfma_kernel<T>;
@@ -2039,6 +2045,7 @@ int sample_weights(blr_handle* h, int memspace, int64_t D, int64_t S, int prior_
                    int64_t ldl, const T* Z, int64_t ldz, T* W, int64_t ldw) {
   if (!h) return -1;
   h->last_chunks = 1;  // (a route with a chunk loop counts its own)
+  h->draw_route = 0;  // (the host code that picks each launch sets its bit)
   h->err.clear();
   if (memspace != BLR_MEM_HOST && memspace != BLR_MEM_DEVICE) return bad_arg(h, 2, "memspace");
   if (D < 1 || D > kMaxLargeD) return bad_arg(h, 3, "D out of range for this build (1..8192)");
@@ -2067,11 +2074,13 @@ void launch_project(blr_handle* h, int layout, int64_t D, int64_t N, int64_t S, 
   const bool no_mfma_proj = h->opt.no_mfma_project;  // A/B experiments only
   if (!no_mfma_proj && layout == BLR_LAYOUT_COLVECS && D % kVec == 0 && aligned16(X_d, ldx, 0) && aligned16(W_d, ldw, 0)) {
     // tall-skinny GEMM on the matrix cores
+    h->draw_route |= blr_handle::DRAW_P_MFMA;
     using PC = ProjCfg<T>;
     dim3 grid((unsigned)((N + PC::TN - 1) / PC::TN), (unsigned)((S + PC::TS - 1) / PC::TS));
     hipLaunchKernelGGL(rand_project_mfma_kernel<T>, grid, dim3(kThreads), PC::LDS_BYTES, h->stream, X_d, ldx, W_d, ldw, s_d, noise_kind,
                        Z2_d, ldz2, Y_d, ldy, (int)D, (int)N, S);
   } else {
+    h->draw_route |= blr_handle::DRAW_P_SCALAR;
     dim3 grid((unsigned)((N + 63) / 64), (unsigned)((S + 63) / 64));
     hipLaunchKernelGGL(rand_project_kernel<T>, grid, dim3(kThreads), 0, h->stream, X_d, ldx, layout, W_d, ldw, s_d, noise_kind, Z2_d,
                        ldz2, Y_d, ldy, (int)D, (int)N, S);
@@ -2084,6 +2093,7 @@ int apply_weights(blr_handle* h, int memspace, int layout, int64_t D, int64_t N,
                   int64_t ldw, T* Y, int64_t ldy) {
   if (!h) return -1;
   h->last_chunks = 1;  // (a route with a chunk loop counts its own)
+  h->draw_route = 0;  // (the host code that picks each launch sets its bit)
   h->err.clear();
   if (memspace != BLR_MEM_HOST && memspace != BLR_MEM_DEVICE) return bad_arg(h, 2, "memspace");
   if (layout != BLR_LAYOUT_COLVECS && layout != BLR_LAYOUT_ROWVECS) return bad_arg(h, 3, "unknown layout (reference :26-31)");
@@ -2117,6 +2127,7 @@ int rand_impl(blr_handle* h, int memspace, int layout, int64_t D, int64_t N, int
               int64_t ldz1, const T* Z2, int64_t ldz2, T* Y, int64_t ldy) {
   if (!h) return -1;
   h->last_chunks = 1;  // (a route with a chunk loop counts its own)
+  h->draw_route = 0;  // (the host code that picks each launch sets its bit)
   h->err.clear();
   if (memspace != BLR_MEM_HOST && memspace != BLR_MEM_DEVICE) return bad_arg(h, 2, "memspace");
   if (layout != BLR_LAYOUT_COLVECS && layout != BLR_LAYOUT_ROWVECS) return bad_arg(h, 3, "unknown layout (reference :26-31)");
@@ -2169,6 +2180,7 @@ int rand_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, 
                  int64_t strideZ2, T* W, int64_t ldw, int64_t strideW, T* Y, int64_t ldy, int64_t strideY, int32_t* info) {
   if (!h) return -1;
   h->last_chunks = 1;  // (a route with a chunk loop counts its own)
+  h->draw_route = 0;  // (the host code that picks each launch sets its bit)
   h->err.clear();
   if (memspace != BLR_MEM_HOST && memspace != BLR_MEM_DEVICE) return bad_arg(h, 2, "memspace");
   if (layout != BLR_LAYOUT_COLVECS && layout != BLR_LAYOUT_ROWVECS) return bad_arg(h, 3, "unknown layout (reference :26-31)");
@@ -2287,11 +2299,13 @@ int rand_batched(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, 
   void (*solve)(RandBatchedArgs<T>);
   if (ns == 1) solve = fuse ? rand_batched_solve_kernel<T, 1, true> : rand_batched_solve_kernel<T, 1, false>;
   else         solve = fuse ? rand_batched_solve_kernel<T, 4, true> : rand_batched_solve_kernel<T, 4, false>;
+  h->draw_route |= (ns == 1 ? blr_handle::DRAW_W_BATCHED_NS1 : blr_handle::DRAW_W_BATCHED_NS4) | (fuse ? blr_handle::DRAW_P_FUSED : 0);
   hipLaunchKernelGGL(solve, dim3(blocks), dim3(kThreads), 0, h->stream, a);
   HIP_TRY(h, hipGetLastError());
   if (proj && !fuse) {
     const int64_t per_launch = h->cap_chunk(std::max<int64_t>(1, ((int64_t)1 << 24) / ntn));
     h->count_chunks(B, per_launch);
+    h->draw_route |= mfma ? blr_handle::DRAW_P_MFMA : blr_handle::DRAW_P_SCALAR;
     for (int64_t b0 = 0; b0 < B; b0 += per_launch) {
       const int64_t nreg = std::min<int64_t>(per_launch, B - b0);
       const dim3 grid((unsigned)(nreg * ntn), (unsigned)nts);
@@ -5421,6 +5435,10 @@ int blr_get_stat(blr_handle* h, const char* key, int64_t* value) {
   if (!value) return bad_arg(h, 3, "value is NULL");
   if (!strcmp(key, "i8_regressors")) { *value = (int64_t)h->i8_attempted; return 0; }
   if (!strcmp(key, "last_chunks")) { *value = h->last_chunks; return 0; }  // chunks / slices of regressors of the most recent call
+  // the kernels of the most recent blr_sample_weights_* / blr_apply_weights_* / blr_rand_* / blr_rand_batched_* call: a bitmask
+  // (weights: 1 diag, 2 mfma, 2 + 4 mfma with the 16-byte loader of U, 8 large, 16 batched NS = 1, 32 batched NS = 4;
+  // projection: 64 fused, 128 scalar, 256 mfma, none of them = no projection; blr_host.hpp DrawRoute)
+  if (!strcmp(key, "draw_route")) { *value = h->draw_route; return 0; }
   // the plan of the most recent blr_update_factor_ragged_* / blr_downdate_factor_ragged_* call: regressors per list
   if (!strcmp(key, "ragged_sweep")) { *value = h->ragged_lists[0]; return 0; }
   if (!strcmp(key, "ragged_refit")) { *value = h->ragged_lists[1]; return 0; }

@@ -241,7 +241,16 @@ struct blr_handle {
       if (nb > 1 && (gx * nb) % 8 == 0) renumbered = 1;
     }
   } marg_block;
-  int64_t route_i8_B = 0;                // > 0: that dispatch took the int8 route with this many regressors (blr_last_route looks at its hand-backs)
+  // The kernels of the most recent blr_sample_weights_* / blr_apply_weights_* / blr_rand_* / blr_rand_batched_* call (blr_get_stat
+  // "draw_route"): cleared at their entry, then or-ed together by the host code that picks each launch.  One weights bit (UVEC rides on
+  // MFMA: sample_weights_mfma_kernel's 16-byte loader of U, the kernel's own predicate evaluated on the host for this stat only)
+  // and at most one projection bit (none: weights only, or N = 0).
+  enum DrawRoute : int64_t {
+    DRAW_W_DIAG = 1, DRAW_W_MFMA = 2, DRAW_W_UVEC = 4, DRAW_W_LARGE = 8, DRAW_W_BATCHED_NS1 = 16, DRAW_W_BATCHED_NS4 = 32,
+    DRAW_P_FUSED = 64, DRAW_P_SCALAR = 128, DRAW_P_MFMA = 256
+  };
+  int64_t draw_route = 0;
+  int64_t route_i8_B = 0;               // > 0: that dispatch took the int8 route with this many regressors (blr_last_route looks at its hand-backs)
   std::string route_buf;
   unsigned* ticket = nullptr;     // [0], [2], [3]: wavefront solve (tickets, done, launch count); [16 + 128 bank + g]: arrivals of panel_chain_kernel
   unsigned panel_launches = 0;    // parity = the bank of arrival words the next panel launch counts in (it clears the other one)

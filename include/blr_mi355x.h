@@ -111,6 +111,12 @@ const char* blr_last_route(blr_handle* h);
  * D <= 128, the tall-matrix sweep, mean only); "marg_block_walk" = tiles the busiest workgroup of that kernel walked (the largest
  * ceil(tiles / grid.x) over the call's launches; 0 with "marg_block_rt" = 0); "marg_block_renumbered" = 1 if any of those launches
  * renumbered its workgroups so that an XCD gets whole regressors (more than one regressor and a grid that is a multiple of 8).
+ * The kernels of the handle's most recent blr_sample_weights_* / blr_apply_weights_* / blr_rand_* / blr_rand_batched_* call (NOT
+ * cumulative; a host-side bitmask, cleared at the entry of these four and set where the launch is picked): "draw_route" = weights
+ * 1 diag_sample_kernel | 2 sample_weights_mfma_kernel (+ 4 when its 16-byte loader of the factor applies: D = 128, ld a multiple
+ * of the vector width, 16-byte aligned pointer) | 8 the D > 128 wave solves | 16 / 32 rand_batched_solve_kernel with one / four
+ * draws per wave, or-ed with the projection 64 fused into the solve | 128 the scalar tiles | 256 the matrix-core tiles | none of the
+ * three: no projection ran (tests assert it, so that a case meant for one kernel cannot pass on another).
  * -> 0, -2 unknown key, -3 NULL value. */
 int blr_get_stat(blr_handle* h, const char* key, int64_t* value);
 int blr_reset_stats(blr_handle* h);

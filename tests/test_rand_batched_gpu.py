@@ -3,6 +3,7 @@ regressor (reference src/bayesian_linear_regression.jl:49-53, src/sampling_funct
 import numpy as np
 import pytest
 
+import _draw_problems as DP
 from oracle import blr_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -121,7 +122,13 @@ def _run(B, nb, D, N, S, dtype=np.float64, layout=0, prior_kind=1, noise_kind=0,
         W_o = O.sample_weights(p[1], p[3], Z1[b])
         s_full = p[4] if noise_kind == _abi.NOISE_DIAGONAL else float(p[4][0])
         Y_o = O.rand(p[1], p[3], p[0], s_full, Z1[b], Z2[b]) if noisy else p[0].T @ W_o
-        refs.append((Y_o, W_o))
+        # the operands as the library saw them (rounded to dtype, in fp64) for the derived bound of _check
+        r64 = lambda a: np.asarray(a, dtype=dtype).astype(np.float64)
+        kind = {_abi.PRIOR_DENSE: "dense", _abi.PRIOR_UPPER_FACTOR: "factor", _abi.PRIOR_DIAGONAL: "diag"}[prior_kind]
+        case = DP.Case("rand_batched", "rand_batched", "f32" if dtype == np.float32 else "f64", D, N=N, S=S, prior=kind,
+                       noise=(("diag" if noise_kind == _abi.NOISE_DIAGONAL else "iso") if noisy else None))
+        ops = dict(X=[r64(p[0])], mw=[r64(p[1])], L=[r64(p[2])], Z1=[r64(Z1[b])], Z2=[r64(Z2[b])], s=[r64(p[4])])
+        refs.append((Y_o, W_o, case, ops))
     return Ys, Ws, info, refs
 
 
@@ -130,14 +137,25 @@ def _check(Ys, Ws, info, refs, dtype):
         if ref is None:
             continue
         assert info[b] == 0, (b, info[b])
-        Y_o, W_o = ref
+        Y_o, W_o, case, ops = ref
         if dtype == np.float64:
             np.testing.assert_allclose(Ys[b], Y_o, rtol=RTOL64, atol=ATOL64)
             if Ws is not None:
                 np.testing.assert_allclose(Ws[b], W_o, rtol=RTOL64, atol=ATOL64)
         else:
             if Y_o.size:
-                assert np.max(np.abs(Ys[b] - Y_o)) <= RTOL32 * max(1.0, np.max(np.abs(Y_o))), b
+                # |Y - Y_ref| <= gamma(D + 2) |X|'|W| + 2 eps |sqrt(s) Z2| elementwise, Y_ref the fp64 product of the same rounded
+                # inputs with the library's own W; without a W output: the reference weights and their bound through |X|'
+                # (tests/_draw_problems.py: projection_bound, weights_tolerance)
+                X, noise = ops["X"][0], DP.noise_term(case, ops, 0)
+                if Ws is not None:
+                    W, slack = Ws[b].astype(np.float64), 0.0
+                else:
+                    W, wb, _ = DP.weights_tolerance(case, ops, 0)
+                    W = np.asarray(W, dtype=np.float64)
+                    slack = np.abs(X).T @ np.broadcast_to(np.asarray(wb, dtype=np.float64), W.shape)
+                bound = DP.projection_bound(case, X, W, noise) + slack
+                assert np.all(np.abs(Ys[b].astype(np.float64) - (X.T @ W + noise)) <= bound), b
             if Ws is not None:
                 assert np.max(np.abs(Ws[b] - W_o)) <= RTOL32 * max(1.0, np.max(np.abs(W_o))), b
 
