@@ -765,34 +765,22 @@ def _heldout_ragged(ops, second, ll_offsets, result):
     log densities, ``ll_offsets[-1]`` in all; ``result``: LOO or KFold."""
     dtype, offsets, nb, X, layout, ldx, D, y, s, noise_kind, strides, prior_kind, ldl, _, mwb, stridemw, Lb, strideLw = ops
     h, item, total, n_ll = _handle(), np.dtype(dtype).itemsize, int(offsets[-1]), int(ll_offsets[-1])
-    temps = []
-
-    def dev(a):
-        temps.append(_DeviceBuffer.of(h, a))
-        return temps[-1].ptr
-
     m, v = np.zeros(total, dtype=dtype), np.zeros(total, dtype=dtype)
     lp, tot, info = np.zeros(n_ll, dtype=np.float64), np.zeros(nb, dtype=np.float64), np.zeros(nb, dtype=np.int32)
-    try:
+    with _DeviceScope(h) as scope:
+        dev, alloc = scope.dev, scope.alloc
         dX, dy, ds = dev(X.reshape(-1, order="A")), dev(y), dev(s)
-        temps.extend([_DeviceBuffer(h, nb * D * item), _DeviceBuffer(h, nb * D * D * item)])
-        d_mwp, d_T = temps[-2].ptr, temps[-1].ptr
+        d_mwp, d_T = alloc(nb * D * item), alloc(nb * D * D * item)
         d_info = dev(info)
         head = (dtype, _abi.MEM_DEVICE, layout, nb, D, offsets)
         h.posterior_ragged(*head, dX, ldx, dy, noise_kind, ds, strides, prior_kind, dev(mwb), stridemw, dev(Lb), ldl, strideLw, d_mwp, D, d_T,
                            max(D, 1), D * D, None, max(D, 1), D * D, None, d_info)
         h.memcpy_d2h(info, d_info)
         if not np.any(info):
-            outs = [_DeviceBuffer(h, max(total, 1) * item), _DeviceBuffer(h, max(total, 1) * item), _DeviceBuffer(h, max(n_ll, 1) * 8),
-                    _DeviceBuffer(h, nb * 8)]
-            temps.extend(outs)
-            d_m, d_v, d_ll, d_tot = (b.ptr for b in outs)
+            d_m, d_v, d_ll, d_tot = alloc(max(total, 1) * item), alloc(max(total, 1) * item), alloc(max(n_ll, 1) * 8), alloc(nb * 8)
             second(h, head, (dX, ldx, dy, noise_kind, ds, strides, d_mwp, D, d_T, max(D, 1), D * D, d_m, d_v, d_ll, d_tot, d_info))
             for host, dptr in ((m, d_m), (v, d_v), (lp, d_ll), (tot, d_tot), (info, d_info)):
                 h.memcpy_d2h(host, dptr)
-    finally:
-        for b in temps:
-            b.free()
     _raise_first_failed(info)
     return [result(m[offsets[b]:offsets[b + 1]], v[offsets[b]:offsets[b + 1]], lp[ll_offsets[b]:ll_offsets[b + 1]], float(tot[b]))
             for b in range(nb)]
@@ -800,7 +788,7 @@ def _heldout_ragged(ops, second, ll_offsets, result):
 
 def loo_ragged(f, x, offsets, Sy, y):
     """[loo(f_b(x[offsets[b]:offsets[b+1]], Sy_b), y[...])] from packed arrays: the data staged once, blr_posterior_ragged_* into
-    device buffers (mw', T), then blr_loo_ragged_* on the same device inputs -- `_loo_batch`'s pipeline for unequal counts.
+    device buffers (mw', T), then blr_loo_ragged_* on the same device inputs -- `_heldout_batch`'s pipeline for unequal counts.
     Nothing D x D comes back to the host.  Arguments as `posterior_ragged`.  The first regressor whose prior, noise or posterior is
     not positive definite raises PosDefException with its position as ``index``."""
     ops, _ = _ragged_operands(f, x, offsets, Sy, y)
@@ -1097,51 +1085,14 @@ def mean_and_var_columns_map(fss, xs, Sy=1e-18):
     return [(m[b].reshape((N, S), order="F"), v[b]) for b in range(nb)]
 
 
+# ---------------------------------------------------------------------------------------------------
+# exact held-out predictives for equal observation counts: one problem record, one fit-then-score pipeline, a row of
+# _HELDOUT per variant (leave-one-out and K-fold; a vector target, or the S columns of a matrix target sharing their factor)
+# ---------------------------------------------------------------------------------------------------
 LOO = namedtuple("LOO", ["mean", "var", "logpdf", "total"])
 LOO.__doc__ = """Exact leave-one-out predictives: per observation n the predictive of y_n given all the other data (mean and var,
 var including the noise as var(fx) does, in the element type; logpdf in float64) and total = sum_n logpdf_n (the LOO-CV
 score).  An observation whose leverage is within rounding of 1 has NaN entries (blr_get_stat "loo_degenerate")."""
-
-
-def _loo_problem(fx, y, dtype, what="loo", perm=None):
-    """(X, layout, ldx, D, N, y, s, noise_kind, mw, Lw, prior_kind, ldl) of one finite regressor, validated as `_fused` does.
-    ``perm`` (kfold): observation n of the problem is observation perm[n] of the caller's -- X, y and a noise diagonal gathered here."""
-    fb = _to_finite_blr(fx)
-    X, layout, ldx, D, N = _x_layout(fb.x, dtype)
-    y = np.ascontiguousarray(y, dtype=dtype)
-    if y.ndim != 1:
-        raise ValueError("y must be a vector")
-    if y.shape[0] != N:
-        raise ValueError("length(y) != size(fx.x.X, 2)")  # reference :74
-    s, noise_kind = _noise(fb.Sy, N, dtype)
-    if noise_kind == _abi.NOISE_DENSE:
-        raise NotImplementedError(f"{what}: with a dense noise covariance one observation is not independent of the rest (that is a "
-                                  "block leave-out); isotropic or diagonal noise only")
-    if perm is not None:
-        obs_axis = 0 if isinstance(fb.x, RowVecs) else 1
-        X = np.asarray(np.take(X, perm, axis=obs_axis), order="F" if X.flags.f_contiguous else "C")
-        y = np.ascontiguousarray(y[perm])
-        if noise_kind == _abi.NOISE_DIAGONAL:
-            s = np.ascontiguousarray(s[perm])
-    Lw, prior_kind, ldl = _prior(fb.f.Lw, D, dtype)
-    return X, layout, ldx, D, N, y, s, noise_kind, _mean_vector(fb.f.mw, D, dtype), Lw, prior_kind, ldl
-
-
-def _loo_call(h, dtype, layout, B, D, N, dX, ldx, strideX, dy, stridey, noise_kind, ds, strides, d_mw, stridemw, d_T, strideT, temps):
-    """blr_loo_batched_* on device operands -> (mean [B, N], var [B, N], logpdf [B, N], total [B], info [B]) on the host."""
-    item = np.dtype(dtype).itemsize
-    outs = [_DeviceBuffer(h, B * N * item), _DeviceBuffer(h, B * N * item), _DeviceBuffer(h, B * N * 8), _DeviceBuffer(h, B * 8),
-            _DeviceBuffer.of(h, np.zeros(B, dtype=np.int32))]
-    temps.extend(outs)
-    d_lm, d_lv, d_ll, d_tot, d_info = (b.ptr for b in outs)
-    h.loo(dtype, _abi.MEM_DEVICE, layout, B, D, N, dX, ldx, strideX, dy, stridey, noise_kind, ds, strides, d_mw, stridemw, d_T,
-          max(D, 1), strideT, d_lm, N, d_lv, N, d_ll, N, d_tot, d_info)
-    m, v = np.empty((B, N), dtype=dtype), np.empty((B, N), dtype=dtype)
-    lp, tot, info = np.empty((B, N), dtype=np.float64), np.empty(B, dtype=np.float64), np.zeros(B, dtype=np.int32)
-    for host, dptr in ((m, d_lm), (v, d_lv), (lp, d_ll), (tot, d_tot), (info, d_info)):
-        h.memcpy_d2h(host, dptr)
-    return m, v, lp, tot, info
-
 
 KFold = namedtuple("KFold", ["mean", "var", "logpdf", "total"])
 KFold.__doc__ = """Exact leave-fold-out (K-fold) predictives for contiguous folds of ``fold_size`` observations: per observation n the
@@ -1150,23 +1101,188 @@ density of its observations given the rest (logpdf, float64, ceil(N / fold_size)
 score).  A fold the state does not contain (a pivot of I - H~ <= 0) has NaN entries (blr_get_stat "kfold_degenerate")."""
 
 
-def _kfold_call(h, dtype, layout, B, D, N, F, dX, ldx, strideX, dy, stridey, noise_kind, ds, strides, d_mw, stridemw, d_T, strideT, temps,
-                large=False):
-    """blr_kfold_batched_* (``large``: blr_kfold_large_batched_*) on device operands -> (mean [B, N], var [B, N], logpdf [B, nfolds],
-    total [B], info [B]) on the host."""
-    item = np.dtype(dtype).itemsize
-    nf = -(-N // F)
-    outs = [_DeviceBuffer(h, B * N * item), _DeviceBuffer(h, B * N * item), _DeviceBuffer(h, B * nf * 8), _DeviceBuffer(h, B * 8),
-            _DeviceBuffer.of(h, np.zeros(B, dtype=np.int32))]
-    temps.extend(outs)
-    d_km, d_kv, d_kl, d_tot, d_info = (b.ptr for b in outs)
-    (h.kfold_large if large else h.kfold)(dtype, _abi.MEM_DEVICE, layout, B, D, N, F, dX, ldx, strideX, dy, stridey, noise_kind, ds, strides,
-                                          d_mw, stridemw, d_T, max(D, 1), strideT, d_km, N, d_kv, N, d_kl, nf, d_tot, d_info)
-    m, v = np.empty((B, N), dtype=dtype), np.empty((B, N), dtype=dtype)
-    lp, tot, info = np.empty((B, nf), dtype=np.float64), np.empty(B, dtype=np.float64), np.zeros(B, dtype=np.int32)
-    for host, dptr in ((m, d_km), (v, d_kv), (lp, d_kl), (tot, d_tot), (info, d_info)):
+class _HeldoutProblem(namedtuple("_HeldoutProblem", "X layout ldx D N target s noise_kind mw Lw prior_kind ldl pdmat")):
+    """One finite regressor with its targets, validated as `_fused` does; ``target``: y [N], or Y [N x S] column-major; ``pdmat``:
+    the prior precision is carried by its factor."""
+    __slots__ = ()
+
+    @property
+    def S(self):
+        return self.target.shape[1] if self.target.ndim == 2 else None
+
+    @property
+    def signature(self):
+        """what problems must share to go through the library in one batch"""
+        return (self.X.shape, self.X.flags.f_contiguous, self.layout, self.D, self.N, self.S, self.noise_kind, self.prior_kind, self.pdmat)
+
+
+def _heldout_problem(fx, target, dtype, what, rank, perm=None):
+    """The record of fx with a vector (``rank`` 1) or N x S matrix (2) of targets.  ``perm`` (K-fold): observation n of the problem
+    is observation perm[n] of the caller's -- X, the targets and a noise diagonal gathered here."""
+    fb = _to_finite_blr(fx)
+    X, layout, ldx, D, N = _x_layout(fb.x, dtype)
+    packed = np.ascontiguousarray if rank == 1 else np.asfortranarray
+    target = packed(target, dtype=dtype)
+    if target.ndim != rank:
+        raise ValueError("y must be a vector" if rank == 1 else "Y must be an N x S matrix")
+    if target.shape[0] != N:
+        raise ValueError("length(y) != size(fx.x.X, 2)")  # reference :74
+    s, noise_kind = _noise(fb.Sy, N, dtype)
+    if noise_kind == _abi.NOISE_DENSE:
+        raise NotImplementedError(f"{what}: with a dense noise covariance one observation is not independent of the rest (that is a "
+                                  "block leave-out); isotropic or diagonal noise only")
+    if perm is not None:
+        obs_axis = 0 if isinstance(fb.x, RowVecs) else 1
+        X = np.asarray(np.take(X, perm, axis=obs_axis), order="F" if X.flags.f_contiguous else "C")
+        target = packed(target[perm])
+        if noise_kind == _abi.NOISE_DIAGONAL:
+            s = np.ascontiguousarray(s[perm])
+    Lw, prior_kind, ldl = _prior(fb.f.Lw, D, dtype)
+    return _HeldoutProblem(X, layout, ldx, D, N, target, s, noise_kind, _mean_vector(fb.f.mw, D, dtype), Lw, prior_kind, ldl,
+                           isinstance(fb.f.Lw, PDMat))
+
+
+# A variant: the entry point that fits the device state and the arguments that follow the prior in its list, the entry point that
+# scores it (``folds``: it takes a fold size) and the arguments that follow the data in its list, the rank of the targets and the
+# record.  st: the means of the state (mw', or M with S columns), nl: log densities per column (N, or the number of folds).
+_Heldout = namedtuple("_Heldout", ["fit", "fit_tail", "score", "score_tail", "folds", "rank", "record"])
+_VECTOR = dict(
+    rank=1, fit="posterior_batched",
+    fit_tail=lambda D, S, st, T, info: (st, D, T, max(D, 1), D * D, None, max(D, 1), D * D, None, info),
+    score_tail=lambda D, N, S, nl, st, stride_st, T, strideT, m, v, ll, tot, info: (
+        st, stride_st, T, max(D, 1), strideT, m, N, v, N, ll, nl, tot, info))
+_COLUMNS = dict(
+    rank=2, fit="posterior_multi_batched",
+    fit_tail=lambda D, S, st, T, info: (st, D, D * S, T, D, D * D, None, D, D * D, None, S, info),
+    score_tail=lambda D, N, S, nl, st, stride_st, T, strideT, m, v, ll, tot, info: (
+        st, max(D, 1), stride_st, T, max(D, 1), strideT, m, max(N, 1), N * S, v, N, ll, max(nl, 1), nl * S, tot, S, info))
+_HELDOUT = {
+    "loo": _Heldout(score="loo", folds=False, record=LOO, **_VECTOR),
+    "kfold": _Heldout(score="kfold", folds=True, record=KFold, **_VECTOR),
+    "kfold_large": _Heldout(score="kfold_large", folds=True, record=KFold, **_VECTOR),
+    "loo_columns": _Heldout(score="loo_multi_batched", folds=False, record=LOO, **_COLUMNS),
+    "kfold_columns": _Heldout(score="kfold_multi_batched", folds=True, record=KFold, **_COLUMNS),
+}
+
+
+def _heldout_operands(row, dtype, layout, B, D, N, S, dX, ldx, strideX, d_target, stride_target, noise_kind, ds, strides):
+    """-> (head, data): the arguments every entry point of ``row`` starts with, and those that describe the staged data"""
+    columns = row.rank == 2
+    return ((dtype, _abi.MEM_DEVICE, layout, B, D, N) + ((S,) if columns else ()),
+            (dX, ldx, strideX, d_target) + ((max(N, 1),) if columns else ()) + (stride_target, noise_kind, ds, strides))
+
+
+def _heldout_call(scope, row, head, F, data, st, stride_st, T, strideT):
+    """The scoring entry point of ``row`` on device operands -> (mean [B, N] or [B, N, S], var [B, N], logpdf [B, nl] or [B, nl, S],
+    total [B] or [B, S], info [B]) on the host; the state (st, T) may be resident (B = 1, strides 0)."""
+    h, dtype, B, D, N = scope.h, head[0], head[3], head[4], head[5]
+    S = head[6] if row.rank == 2 else 1
+    nl = -(-N // F) if row.folds else N
+    m, v = np.empty((B, N * S), dtype=dtype), np.empty((B, N), dtype=dtype)
+    lp, tot = np.empty((B, nl * S), dtype=np.float64), np.empty((B, S) if row.rank == 2 else B, dtype=np.float64)
+    info = np.zeros(B, dtype=np.int32)
+    d_m, d_v, d_ll, d_tot = (scope.alloc(a.nbytes) for a in (m, v, lp, tot))
+    d_info = scope.dev(info)
+    getattr(h, row.score)(*head, *((F,) if row.folds else ()), *data,
+                          *row.score_tail(D, N, S, nl, st, stride_st, T, strideT, d_m, d_v, d_ll, d_tot, d_info))
+    for host, dptr in ((m, d_m), (v, d_v), (lp, d_ll), (tot, d_tot), (info, d_info)):
         h.memcpy_d2h(host, dptr)
+    if row.rank == 2:  # (column-major per regressor)
+        m, lp = m.reshape((B, S, N)).transpose(0, 2, 1), lp.reshape((B, S, nl)).transpose(0, 2, 1)
     return m, v, lp, tot, info
+
+
+def _heldout_records(row, m, v, lp, tot):
+    return [row.record(m[b], v[b], lp[b], float(tot[b]) if row.rank == 1 else tot[b]) for b in range(len(v))]
+
+
+def _heldout_empty(row, dtype, N, S, F):
+    """what a matrix target with no weights, no observations or no columns gets without a call"""
+    return row.record(np.empty((N, S), dtype=dtype), np.empty(N, dtype=dtype), np.empty((-(-N // F) if row.folds else N, S)), np.zeros(S))
+
+
+def _heldout_batch(probs, dtype, row, F=None):
+    """Held-out predictives of equally shaped problems: their data staged once, the fit of ``row`` into device buffers (mw', T) or
+    (M, T) -- any prior kind, the usual routes -- then its scoring entry point on the same device inputs.  Nothing D x D comes back
+    to the host.  The first problem that fails either call raises PosDefException with its position as ``index``."""
+    q = probs[0]
+    D, N, S, nb, item = q.D, q.N, q.S, len(probs), np.dtype(dtype).itemsize
+    if row.rank == 2 and (D == 0 or N == 0 or S == 0):
+        return [_heldout_empty(row, dtype, N, S, F) for _ in probs]
+    h = _handle()
+    Xb = np.stack([p.X.reshape(-1, order="A") for p in probs])
+    tb = np.stack([p.target.reshape(-1, order="F") for p in probs])  # (N x S column-major per data set, ldY = N)
+    sb = np.stack([p.s for p in probs])
+    mwb = np.stack([p.mw for p in probs])
+    Lb = np.stack([p.Lw.reshape(-1, order="A") for p in probs])
+    with _DeviceScope(h) as scope:
+        head, data = _heldout_operands(row, dtype, q.layout, nb, D, N, S, scope.dev(Xb), q.ldx, Xb.shape[1], scope.dev(tb), tb.shape[1],
+                                       q.noise_kind, scope.dev(sb), sb.shape[1])
+        d_st, d_T = scope.alloc(nb * D * (S or 1) * item), scope.alloc(nb * D * D * item)
+        info = np.zeros(nb, dtype=np.int32)
+        d_info = scope.dev(info)
+        getattr(h, row.fit)(*head, *data, q.prior_kind, scope.dev(mwb), D, scope.dev(Lb), q.ldl, Lb.shape[1],
+                            *row.fit_tail(D, S, d_st, d_T, d_info))
+        h.memcpy_d2h(info, d_info)
+        if not np.any(info):
+            m, v, lp, tot, info = _heldout_call(scope, row, head, F, data, d_st, D * (S or 1), d_T, D * D)
+    _raise_first_failed(info)
+    return _heldout_records(row, m, v, lp, tot)
+
+
+def _heldout_dtype(fx, target):
+    return _dtype_of(fx.f.blr.mw if isinstance(fx.f, BasisFunctionRegressor) else fx.f.mw, target)
+
+
+def _perm_of(perm, target, rank=1):
+    if perm is None:
+        return None
+    perm = np.asarray(perm, dtype=np.int64)
+    n = np.asarray(target).shape[0] if np.ndim(target) == rank else -1
+    if perm.shape != (n,) or not np.array_equal(np.sort(perm), np.arange(n)):
+        raise ValueError("perm must be a permutation of range(N)")
+    return perm
+
+
+def _heldout_one(fx, target, row, what, F=None, perm=None, check=None):
+    """One problem through `_heldout_batch`; ``check(problem)`` runs before anything is staged.  With ``perm``, mean and var are
+    scattered back to the caller's order; logpdf stays in fold order."""
+    dtype = _heldout_dtype(fx, target)
+    perm = _perm_of(perm, target, row.rank)
+    q = _heldout_problem(fx, target, dtype, what, row.rank, perm)
+    if check is not None:
+        check(q)
+    r = _heldout_batch([q], dtype, row, F)[0]
+    if perm is None:
+        return r
+    m, v = np.empty_like(r.mean), np.empty_like(r.var)
+    m[perm], v[perm] = r.mean, r.var
+    return r._replace(mean=m, var=v)
+
+
+def _heldout_map(fxs, targets, row, what, F=None, check=None):
+    """The problems in one fit and one scoring call when they are equally shaped, else one pair of calls per problem (a
+    RandomFourierFeatures basis, an empty dimension: always).  ``check(problem)`` runs for every problem before anything is staged."""
+    fxs, targets = list(fxs), list(targets)
+    if len(fxs) != len(targets):
+        raise ValueError(f"as many {'observation vectors' if row.rank == 1 else 'target matrices'} as finite regressors are needed")
+    if not fxs:
+        return []
+    dtype = np.float32 if all(_heldout_dtype(fx, t) == np.float32 for fx, t in zip(fxs, targets)) else np.float64
+    probs = [_heldout_problem(fx, t, dtype, what, row.rank) for fx, t in zip(fxs, targets)]
+    for q in probs if check is not None else ():
+        check(q)
+    rff = any(isinstance(fx.f, BasisFunctionRegressor) and isinstance(fx.f.phi, RandomFourierFeatures) for fx in fxs)
+    if not rff and len({q.signature for q in probs}) == 1 and 0 not in (probs[0].D, probs[0].N, probs[0].S):
+        return _heldout_batch(probs, dtype, row, F)
+    out = []
+    for i, q in enumerate(probs):
+        try:
+            out.append(_heldout_batch([q], dtype, row, F)[0])
+        except _abi.PosDefException as e:
+            e.index = i
+            raise
+    return out
 
 
 def _fold_size(fold_size):
@@ -1176,149 +1292,9 @@ def _fold_size(fold_size):
     return F
 
 
-def _loo_batch(probs, dtype, fold_size=None, large=False):
-    """LOO of equally shaped problems: their data staged once, blr_posterior_batched_* into device buffers (mw', T) -- any prior
-    kind, the usual routes -- then blr_loo_batched_* on the same device inputs.  Nothing D x D comes back to the host.
-    ``fold_size``: the same pipeline with blr_kfold_batched_* (``large``: blr_kfold_large_batched_*) as its second half -> KFold
-    records."""
-    X0, layout, ldx, D, N, _, _, noise_kind, _, _, prior_kind, ldl = probs[0]
-    nb, h, item = len(probs), _handle(), np.dtype(dtype).itemsize
-    Xb = np.stack([q[0].reshape(-1, order="A") for q in probs])
-    yb = np.stack([q[5] for q in probs])
-    sb = np.stack([q[6] for q in probs])
-    mwb = np.stack([q[8] for q in probs])
-    Lb = np.stack([q[9].reshape(-1, order="A") for q in probs])
-    temps = []
-
-    def dev(a):
-        temps.append(_DeviceBuffer.of(h, a))
-        return temps[-1].ptr
-
-    try:
-        dX, dy, ds = dev(Xb), dev(yb), dev(sb)
-        temps.extend([_DeviceBuffer(h, nb * D * item), _DeviceBuffer(h, nb * D * D * item)])
-        d_mwp, d_T = temps[-2].ptr, temps[-1].ptr
-        d_info = dev(np.zeros(nb, dtype=np.int32))
-        h.posterior_batched(dtype, _abi.MEM_DEVICE, layout, nb, D, N, dX, ldx, Xb.shape[1], dy, yb.shape[1], noise_kind, ds,
-                            sb.shape[1], prior_kind, dev(mwb), D, dev(Lb), ldl, Lb.shape[1], d_mwp, D, d_T, max(D, 1), D * D,
-                            None, max(D, 1), D * D, None, d_info)
-        info = np.zeros(nb, dtype=np.int32)
-        h.memcpy_d2h(info, d_info)
-        if not np.any(info) and fold_size is None:
-            m, v, lp, tot, info = _loo_call(h, dtype, layout, nb, D, N, dX, ldx, Xb.shape[1], dy, yb.shape[1], noise_kind, ds,
-                                            sb.shape[1], d_mwp, D, d_T, D * D, temps)
-        elif not np.any(info):
-            m, v, lp, tot, info = _kfold_call(h, dtype, layout, nb, D, N, fold_size, dX, ldx, Xb.shape[1], dy, yb.shape[1], noise_kind,
-                                              ds, sb.shape[1], d_mwp, D, d_T, D * D, temps, large)
-    finally:
-        for b in temps:
-            b.free()
-    bad = np.flatnonzero(info)
-    if bad.size:
-        e = _abi.PosDefException(int(info[bad[0]]))
-        e.index = int(bad[0])
-        raise e
-    return [(LOO if fold_size is None else KFold)(m[b], v[b], lp[b], float(tot[b])) for b in range(nb)]
-
-
-def loo(fx, y):
-    """Exact leave-one-out predictives of the observations y at fx.x (include/blr_mi355x.h blr_loo_batched_*): for every n the
-    predictive of y_n under posterior(fx without observation n) -- what a loop of forget / condition gives, from one marginal
-    pass over the inputs.  Returns LOO(mean, var, logpdf, total).  Dense noise raises NotImplementedError (a block LOO)."""
-    dtype = _dtype_of(fx.f.blr.mw if isinstance(fx.f, BasisFunctionRegressor) else fx.f.mw, y)
-    return _loo_batch([_loo_problem(fx, y, dtype)], dtype)[0]
-
-
-def loo_map(fxs, ys):
-    """[loo(fx, y) for fx, y in zip(fxs, ys)] in one posterior call and one LOO call for equally shaped problems (else one call
-    per problem, as `posterior_map`).  The first problem whose prior, noise or posterior is not positive definite raises
-    PosDefException with its position as ``index``.  Problems with UNEQUAL observation counts whose data is already packed side
-    by side go through `loo_ragged` in two library calls."""
-    fxs, ys = list(fxs), list(ys)
-    if len(fxs) != len(ys):
-        raise ValueError("as many observation vectors as finite regressors are needed")
-    if not fxs:
-        return []
-    dtype = np.float32 if all(_dtype_of(fx.f.blr.mw if isinstance(fx.f, BasisFunctionRegressor) else fx.f.mw, y) == np.float32
-                              for fx, y in zip(fxs, ys)) else np.float64
-
-    def one_by_one(probs):
-        out = []
-        for i, q in enumerate(probs):
-            try:
-                out.append(_loo_batch([q], dtype)[0])
-            except _abi.PosDefException as e:
-                e.index = i
-                raise
-        return out
-
-    probs = [_loo_problem(fx, y, dtype) for fx, y in zip(fxs, ys)]
-    if any(isinstance(fx.f, BasisFunctionRegressor) and isinstance(fx.f.phi, RandomFourierFeatures) for fx in fxs):
-        return one_by_one(probs)
-    sig = {(q[0].shape, q[0].flags.f_contiguous, q[1], q[3], q[4], q[7], q[10],
-            isinstance((fx.f.blr if isinstance(fx.f, BasisFunctionRegressor) else fx.f).Lw, PDMat)) for q, fx in zip(probs, fxs)}
-    if len(sig) != 1 or probs[0][3] == 0 or probs[0][4] == 0:
-        return one_by_one(probs)
-    return _loo_batch(probs, dtype)
-
-
-def kfold(fx, y, fold_size, perm=None):
-    """Exact leave-fold-out (K-fold) predictives of the observations y at fx.x (include/blr_mi355x.h blr_kfold_batched_*): fold f
-    holds the observations [f fold_size, (f + 1) fold_size), and every observation gets its predictive under posterior(fx without
-    its fold) -- what a loop of forget / predict / condition per fold gives, from one call.  1 <= fold_size <= 64; at 1 this is
-    `loo`.  ``perm``, a permutation of range(N), makes the folds random: fold f then holds the observations perm[f fold_size :
-    (f + 1) fold_size]; mean and var come back in the caller's order, logpdf stays in fold order.  Returns KFold(mean, var, logpdf,
-    total).  Dense noise raises NotImplementedError (it couples the folds)."""
-    F = _fold_size(fold_size)
-    dtype = _dtype_of(fx.f.blr.mw if isinstance(fx.f, BasisFunctionRegressor) else fx.f.mw, y)
-    if perm is not None:
-        perm = np.asarray(perm, dtype=np.int64)
-        n = np.asarray(y).shape[0] if np.ndim(y) == 1 else -1
-        if perm.shape != (n,) or not np.array_equal(np.sort(perm), np.arange(n)):
-            raise ValueError("perm must be a permutation of range(N)")
-    r = _loo_batch([_loo_problem(fx, y, dtype, "kfold", perm)], dtype, F)[0]
-    if perm is None:
-        return r
-    m, v = np.empty_like(r.mean), np.empty_like(r.var)
-    m[perm], v[perm] = r.mean, r.var
-    return KFold(m, v, r.logpdf, r.total)
-
-
-def kfold_map(fxs, ys, fold_size):
-    """[kfold(fx, y, fold_size) for fx, y in zip(fxs, ys)] in one posterior call and one K-fold call for equally shaped problems
-    (else one call per problem, as `loo_map`).  The first problem whose prior, noise or posterior is not positive definite raises
-    PosDefException with its position as ``index``."""
-    F = _fold_size(fold_size)
-    fxs, ys = list(fxs), list(ys)
-    if len(fxs) != len(ys):
-        raise ValueError("as many observation vectors as finite regressors are needed")
-    if not fxs:
-        return []
-    dtype = np.float32 if all(_dtype_of(fx.f.blr.mw if isinstance(fx.f, BasisFunctionRegressor) else fx.f.mw, y) == np.float32
-                              for fx, y in zip(fxs, ys)) else np.float64
-
-    def one_by_one(probs):
-        out = []
-        for i, q in enumerate(probs):
-            try:
-                out.append(_loo_batch([q], dtype, F)[0])
-            except _abi.PosDefException as e:
-                e.index = i
-                raise
-        return out
-
-    probs = [_loo_problem(fx, y, dtype, "kfold") for fx, y in zip(fxs, ys)]
-    if any(isinstance(fx.f, BasisFunctionRegressor) and isinstance(fx.f.phi, RandomFourierFeatures) for fx in fxs):
-        return one_by_one(probs)
-    sig = {(q[0].shape, q[0].flags.f_contiguous, q[1], q[3], q[4], q[7], q[10],
-            isinstance((fx.f.blr if isinstance(fx.f, BasisFunctionRegressor) else fx.f).Lw, PDMat)) for q, fx in zip(probs, fxs)}
-    if len(sig) != 1 or probs[0][3] == 0 or probs[0][4] == 0:
-        return one_by_one(probs)
-    return _loo_batch(probs, dtype, F)
-
-
 _KFOLD_LARGE_MAX_D = 128      # blr_kfold_large_batched_*: the fold's D x D factorisation lives in LDS
 _KFOLD_LARGE_MAX_FOLDS = 1024  # ... and the route is for few, large folds
+_KFOLD_COLUMNS_MAX_D = 128    # blr_kfold_multi_batched_*: the fold's rows of Z live in LDS, there is no slow route
 
 
 def _fold_size_large(fold_size):
@@ -1336,14 +1312,41 @@ def _kfold_large_check(D, N, F, what):
         raise ValueError(f"{what}: ceil(N / fold_size) = {-(-N // F)} folds; at most {_KFOLD_LARGE_MAX_FOLDS} (many small folds: kfold)")
 
 
-def _perm_of(perm, y):
-    if perm is None:
-        return None
-    perm = np.asarray(perm, dtype=np.int64)
-    n = np.asarray(y).shape[0] if np.ndim(y) == 1 else -1
-    if perm.shape != (n,) or not np.array_equal(np.sort(perm), np.arange(n)):
-        raise ValueError("perm must be a permutation of range(N)")
-    return perm
+def _kfold_columns_check(D, what):
+    if D > _KFOLD_COLUMNS_MAX_D:
+        raise ValueError(f"{what}: D = {D} is beyond the limit of blr_kfold_multi_batched_* (D <= {_KFOLD_COLUMNS_MAX_D})")
+
+
+def loo(fx, y):
+    """Exact leave-one-out predictives of the observations y at fx.x (include/blr_mi355x.h blr_loo_batched_*): for every n the
+    predictive of y_n under posterior(fx without observation n) -- what a loop of forget / condition gives, from one marginal
+    pass over the inputs.  Returns LOO(mean, var, logpdf, total).  Dense noise raises NotImplementedError (a block LOO)."""
+    return _heldout_one(fx, y, _HELDOUT["loo"], "loo")
+
+
+def loo_map(fxs, ys):
+    """[loo(fx, y) for fx, y in zip(fxs, ys)] in one posterior call and one LOO call for equally shaped problems (else one call
+    per problem, as `posterior_map`).  The first problem whose prior, noise or posterior is not positive definite raises
+    PosDefException with its position as ``index``.  Problems with UNEQUAL observation counts whose data is already packed side
+    by side go through `loo_ragged` in two library calls."""
+    return _heldout_map(fxs, ys, _HELDOUT["loo"], "loo")
+
+
+def kfold(fx, y, fold_size, perm=None):
+    """Exact leave-fold-out (K-fold) predictives of the observations y at fx.x (include/blr_mi355x.h blr_kfold_batched_*): fold f
+    holds the observations [f fold_size, (f + 1) fold_size), and every observation gets its predictive under posterior(fx without
+    its fold) -- what a loop of forget / predict / condition per fold gives, from one call.  1 <= fold_size <= 64; at 1 this is
+    `loo`.  ``perm``, a permutation of range(N), makes the folds random: fold f then holds the observations perm[f fold_size :
+    (f + 1) fold_size]; mean and var come back in the caller's order, logpdf stays in fold order.  Returns KFold(mean, var, logpdf,
+    total).  Dense noise raises NotImplementedError (it couples the folds)."""
+    return _heldout_one(fx, y, _HELDOUT["kfold"], "kfold", _fold_size(fold_size), perm)
+
+
+def kfold_map(fxs, ys, fold_size):
+    """[kfold(fx, y, fold_size) for fx, y in zip(fxs, ys)] in one posterior call and one K-fold call for equally shaped problems
+    (else one call per problem, as `loo_map`).  The first problem whose prior, noise or posterior is not positive definite raises
+    PosDefException with its position as ``index``."""
+    return _heldout_map(fxs, ys, _HELDOUT["kfold"], "kfold", _fold_size(fold_size))
 
 
 def kfold_large(fx, y, fold_size, perm=None):
@@ -1353,16 +1356,7 @@ def kfold_large(fx, y, fold_size, perm=None):
     state's information loses digits (float32 first).  ``perm`` and the KFold record as for `kfold`; fold_size > N is one fold, the
     predictive under the prior."""
     F = _fold_size_large(fold_size)
-    dtype = _dtype_of(fx.f.blr.mw if isinstance(fx.f, BasisFunctionRegressor) else fx.f.mw, y)
-    perm = _perm_of(perm, y)
-    q = _loo_problem(fx, y, dtype, "kfold_large", perm)
-    _kfold_large_check(q[3], q[4], F, "kfold_large")
-    r = _loo_batch([q], dtype, F, large=True)[0]
-    if perm is None:
-        return r
-    m, v = np.empty_like(r.mean), np.empty_like(r.var)
-    m[perm], v[perm] = r.mean, r.var
-    return KFold(m, v, r.logpdf, r.total)
+    return _heldout_one(fx, y, _HELDOUT["kfold_large"], "kfold_large", F, perm, lambda q: _kfold_large_check(q.D, q.N, F, "kfold_large"))
 
 
 def kfold_large_map(fxs, ys, fold_size):
@@ -1370,34 +1364,7 @@ def kfold_large_map(fxs, ys, fold_size):
     equally shaped problems (else one call per problem, as `kfold_map`).  The first problem whose prior, noise or posterior is not
     positive definite raises PosDefException with its position as ``index``."""
     F = _fold_size_large(fold_size)
-    fxs, ys = list(fxs), list(ys)
-    if len(fxs) != len(ys):
-        raise ValueError("as many observation vectors as finite regressors are needed")
-    if not fxs:
-        return []
-    dtype = np.float32 if all(_dtype_of(fx.f.blr.mw if isinstance(fx.f, BasisFunctionRegressor) else fx.f.mw, y) == np.float32
-                              for fx, y in zip(fxs, ys)) else np.float64
-
-    def one_by_one(probs):
-        out = []
-        for i, q in enumerate(probs):
-            try:
-                out.append(_loo_batch([q], dtype, F, large=True)[0])
-            except _abi.PosDefException as e:
-                e.index = i
-                raise
-        return out
-
-    probs = [_loo_problem(fx, y, dtype, "kfold_large") for fx, y in zip(fxs, ys)]
-    for q in probs:
-        _kfold_large_check(q[3], q[4], F, "kfold_large_map")
-    if any(isinstance(fx.f, BasisFunctionRegressor) and isinstance(fx.f.phi, RandomFourierFeatures) for fx in fxs):
-        return one_by_one(probs)
-    sig = {(q[0].shape, q[0].flags.f_contiguous, q[1], q[3], q[4], q[7], q[10],
-            isinstance((fx.f.blr if isinstance(fx.f, BasisFunctionRegressor) else fx.f).Lw, PDMat)) for q, fx in zip(probs, fxs)}
-    if len(sig) != 1 or probs[0][3] == 0 or probs[0][4] == 0:
-        return one_by_one(probs)
-    return _loo_batch(probs, dtype, F, large=True)
+    return _heldout_map(fxs, ys, _HELDOUT["kfold_large"], "kfold_large", F, lambda q: _kfold_large_check(q.D, q.N, F, "kfold_large_map"))
 
 
 def cross_validate(fx, y, n_folds, perm=None):
@@ -1409,98 +1376,6 @@ def cross_validate(fx, y, n_folds, perm=None):
     N = np.asarray(y).shape[0] if np.ndim(y) == 1 else 0
     F = max(1, -(-N // K))
     return kfold(fx, y, F, perm) if F <= 64 else kfold_large(fx, y, F, perm)
-
-
-# ---------------------------------------------------------------------------------------------------
-# exact leave-one-out for matrix targets: S columns share the leverage of an input (blr_loo_multi_batched_*)
-# ---------------------------------------------------------------------------------------------------
-def _loo_columns_call(h, dtype, layout, B, D, N, S, dX, ldx, strideX, dY, strideY, noise_kind, ds, strides, d_M, strideM, d_T, strideT,
-                      temps):
-    """blr_loo_multi_batched_* on device operands -> (mean [B, N, S], var [B, N], logpdf [B, N, S], total [B, S], info [B]) on the
-    host."""
-    item = np.dtype(dtype).itemsize
-    outs = [_DeviceBuffer(h, B * N * S * item), _DeviceBuffer(h, B * N * item), _DeviceBuffer(h, B * N * S * 8), _DeviceBuffer(h, B * S * 8),
-            _DeviceBuffer.of(h, np.zeros(B, dtype=np.int32))]
-    temps.extend(outs)
-    d_lm, d_lv, d_ll, d_tot, d_info = (b.ptr for b in outs)
-    h.loo_multi_batched(dtype, _abi.MEM_DEVICE, layout, B, D, N, S, dX, ldx, strideX, dY, max(N, 1), strideY, noise_kind, ds, strides,
-                        d_M, max(D, 1), strideM, d_T, max(D, 1), strideT, d_lm, max(N, 1), N * S, d_lv, N, d_ll, max(N, 1), N * S, d_tot, S,
-                        d_info)
-    m, v = np.empty((B, N * S), dtype=dtype), np.empty((B, N), dtype=dtype)
-    lp, tot, info = np.empty((B, N * S), dtype=np.float64), np.empty((B, S), dtype=np.float64), np.zeros(B, dtype=np.int32)
-    for host, dptr in ((m, d_lm), (v, d_lv), (lp, d_ll), (tot, d_tot), (info, d_info)):
-        h.memcpy_d2h(host, dptr)
-    return (m.reshape((B, S, N)).transpose(0, 2, 1), v, lp.reshape((B, S, N)).transpose(0, 2, 1), tot, info)  # (column-major N x S)
-
-
-def _loo_columns_problem(fx, Y, dtype, what="loo_columns", perm=None):
-    """(X, layout, ldx, D, N, Y, s, noise_kind, mw, Lw, prior_kind, ldl) of one finite regressor with an N x S target matrix.
-    ``perm`` (kfold_columns): observation n of the problem is observation perm[n] of the caller's -- X, the rows of Y and a noise
-    diagonal gathered here."""
-    fb = _to_finite_blr(fx)
-    X, layout, ldx, D, N = _x_layout(fb.x, dtype)
-    Y = np.asfortranarray(Y, dtype=dtype)
-    if Y.ndim != 2:
-        raise ValueError("Y must be an N x S matrix")
-    if Y.shape[0] != N:
-        raise ValueError("length(y) != size(fx.x.X, 2)")  # reference :74
-    s, noise_kind = _noise(fb.Sy, N, dtype)
-    if noise_kind == _abi.NOISE_DENSE:
-        raise NotImplementedError(f"{what}: with a dense noise covariance one observation is not independent of the rest (that "
-                                  "is a block leave-out); isotropic or diagonal noise only")
-    if perm is not None:
-        obs_axis = 0 if isinstance(fb.x, RowVecs) else 1
-        X = np.asarray(np.take(X, perm, axis=obs_axis), order="F" if X.flags.f_contiguous else "C")
-        Y = np.asfortranarray(Y[perm, :])
-        if noise_kind == _abi.NOISE_DIAGONAL:
-            s = np.ascontiguousarray(s[perm])
-    Lw, prior_kind, ldl = _prior(fb.f.Lw, D, dtype)
-    return X, layout, ldx, D, N, Y, s, noise_kind, _mean_vector(fb.f.mw, D, dtype), Lw, prior_kind, ldl
-
-
-def _loo_columns_batch(probs, dtype):
-    """LOO of equally shaped matrix-target problems: their data staged once, blr_posterior_multi_batched_* into device buffers (M, T)
-    -- the pipeline of `loo_map` -- then blr_loo_multi_batched_* on the same device inputs.  Nothing D x D comes back to the host."""
-    X0, layout, ldx, D, N, Y0, _, noise_kind, _, _, prior_kind, ldl = probs[0]
-    S = Y0.shape[1]
-    nb, h, item = len(probs), _handle(), np.dtype(dtype).itemsize
-    Xb = np.stack([q[0].reshape(-1, order="A") for q in probs])
-    Yb = np.stack([q[5].reshape(-1, order="F") for q in probs])  # N x S column-major per data set, ldY = N
-    sb = np.stack([q[6] for q in probs])
-    mwb = np.stack([q[8] for q in probs])
-    Lb = np.stack([q[9].reshape(-1, order="A") for q in probs])
-    temps = []
-
-    def dev(a):
-        temps.append(_DeviceBuffer.of(h, a))
-        return temps[-1].ptr
-
-    try:
-        dX, dY, ds = dev(Xb), dev(Yb), dev(sb)
-        temps.extend([_DeviceBuffer(h, nb * D * S * item), _DeviceBuffer(h, nb * D * D * item)])
-        d_M, d_T = temps[-2].ptr, temps[-1].ptr
-        d_info = dev(np.zeros(nb, dtype=np.int32))
-        h.posterior_multi_batched(dtype, _abi.MEM_DEVICE, layout, nb, D, N, S, dX, ldx, Xb.shape[1], dY, max(N, 1), Yb.shape[1], noise_kind,
-                                  ds, sb.shape[1], prior_kind, dev(mwb), D, dev(Lb), ldl, Lb.shape[1], d_M, D, D * S, d_T, D, D * D, None, D,
-                                  D * D, None, S, d_info)
-        info = np.zeros(nb, dtype=np.int32)
-        h.memcpy_d2h(info, d_info)
-        if not np.any(info):
-            m, v, lp, tot, info = _loo_columns_call(h, dtype, layout, nb, D, N, S, dX, ldx, Xb.shape[1], dY, Yb.shape[1], noise_kind, ds,
-                                                    sb.shape[1], d_M, D * S, d_T, D * D, temps)
-    finally:
-        for b in temps:
-            b.free()
-    bad = np.flatnonzero(info)
-    if bad.size:
-        e = _abi.PosDefException(int(info[bad[0]]))
-        e.index = int(bad[0])
-        raise e
-    return [LOO(m[b], v[b], lp[b], tot[b]) for b in range(nb)]
-
-
-def _loo_columns_dtype(fx, Y):
-    return _dtype_of(fx.f.blr.mw if isinstance(fx.f, BasisFunctionRegressor) else fx.f.mw, Y)
 
 
 def loo_columns(fx, Y):
@@ -1515,117 +1390,7 @@ def loo_columns_map(fxs, Ys):
     """[loo_columns(fx, Y) for fx, Y in zip(fxs, Ys)] in one posterior call and one LOO call for equally shaped problems (else one
     pair of calls per problem).  The first problem whose prior, noise or posterior is not positive definite raises PosDefException
     with its position as ``index``."""
-    fxs, Ys = list(fxs), [np.asarray(Y) for Y in Ys]
-    if len(fxs) != len(Ys):
-        raise ValueError("as many target matrices as finite regressors are needed")
-    if not fxs:
-        return []
-    dtype = np.float32 if all(_loo_columns_dtype(fx, Y) == np.float32 for fx, Y in zip(fxs, Ys)) else np.float64
-    probs = [_loo_columns_problem(fx, Y, dtype) for fx, Y in zip(fxs, Ys)]
-
-    def one(q):
-        N, S = q[5].shape
-        if q[3] == 0 or N == 0 or S == 0:
-            return LOO(np.empty((N, S), dtype=dtype), np.empty(N, dtype=dtype), np.empty((N, S)), np.zeros(S))
-        return _loo_columns_batch([q], dtype)[0]
-
-    def one_by_one():
-        out = []
-        for i, q in enumerate(probs):
-            try:
-                out.append(one(q))
-            except _abi.PosDefException as e:
-                e.index = i
-                raise
-        return out
-
-    if any(isinstance(fx.f, BasisFunctionRegressor) and isinstance(fx.f.phi, RandomFourierFeatures) for fx in fxs):
-        return one_by_one()
-    sig = {(q[0].shape, q[0].flags.f_contiguous, q[1], q[3], q[4], q[5].shape[1], q[7], q[10],
-            isinstance((fx.f.blr if isinstance(fx.f, BasisFunctionRegressor) else fx.f).Lw, PDMat)) for q, fx in zip(probs, fxs)}
-    q0 = probs[0]
-    if len(sig) != 1 or q0[3] == 0 or q0[4] == 0 or q0[5].shape[1] == 0:
-        return one_by_one()
-    return _loo_columns_batch(probs, dtype)
-
-
-# ---------------------------------------------------------------------------------------------------
-# exact K-fold for matrix targets: S columns share every fold's factor (blr_kfold_multi_batched_*)
-# ---------------------------------------------------------------------------------------------------
-_KFOLD_COLUMNS_MAX_D = 128  # blr_kfold_multi_batched_*: the fold's rows of Z live in LDS, there is no slow route
-
-
-def _kfold_columns_check(D, what):
-    if D > _KFOLD_COLUMNS_MAX_D:
-        raise ValueError(f"{what}: D = {D} is beyond the limit of blr_kfold_multi_batched_* (D <= {_KFOLD_COLUMNS_MAX_D})")
-
-
-def _kfold_columns_call(h, dtype, layout, B, D, N, S, F, dX, ldx, strideX, dY, strideY, noise_kind, ds, strides, d_M, strideM, d_T, strideT,
-                        temps):
-    """blr_kfold_multi_batched_* on device operands -> (mean [B, N, S], var [B, N], logpdf [B, nfolds, S], total [B, S], info [B]) on
-    the host."""
-    item = np.dtype(dtype).itemsize
-    nf = -(-N // F)
-    outs = [_DeviceBuffer(h, B * N * S * item), _DeviceBuffer(h, B * N * item), _DeviceBuffer(h, B * nf * S * 8), _DeviceBuffer(h, B * S * 8),
-            _DeviceBuffer.of(h, np.zeros(B, dtype=np.int32))]
-    temps.extend(outs)
-    d_km, d_kv, d_kl, d_tot, d_info = (b.ptr for b in outs)
-    h.kfold_multi_batched(dtype, _abi.MEM_DEVICE, layout, B, D, N, S, F, dX, ldx, strideX, dY, max(N, 1), strideY, noise_kind, ds, strides,
-                          d_M, max(D, 1), strideM, d_T, max(D, 1), strideT, d_km, max(N, 1), N * S, d_kv, N, d_kl, max(nf, 1), nf * S, d_tot,
-                          S, d_info)
-    m, v = np.empty((B, N * S), dtype=dtype), np.empty((B, N), dtype=dtype)
-    lp, tot, info = np.empty((B, nf * S), dtype=np.float64), np.empty((B, S), dtype=np.float64), np.zeros(B, dtype=np.int32)
-    for host, dptr in ((m, d_km), (v, d_kv), (lp, d_kl), (tot, d_tot), (info, d_info)):
-        h.memcpy_d2h(host, dptr)
-    return (m.reshape((B, S, N)).transpose(0, 2, 1), v, lp.reshape((B, S, nf)).transpose(0, 2, 1), tot, info)  # (column-major per regressor)
-
-
-def _kfold_columns_batch(probs, dtype, F):
-    """K-fold of equally shaped matrix-target problems: the pipeline of `_loo_columns_batch` with blr_kfold_multi_batched_* as its
-    second half.  Nothing D x D comes back to the host."""
-    X0, layout, ldx, D, N, Y0, _, noise_kind, _, _, prior_kind, ldl = probs[0]
-    S = Y0.shape[1]
-    nb, h, item = len(probs), _handle(), np.dtype(dtype).itemsize
-    Xb = np.stack([q[0].reshape(-1, order="A") for q in probs])
-    Yb = np.stack([q[5].reshape(-1, order="F") for q in probs])  # N x S column-major per data set, ldY = N
-    sb = np.stack([q[6] for q in probs])
-    mwb = np.stack([q[8] for q in probs])
-    Lb = np.stack([q[9].reshape(-1, order="A") for q in probs])
-    temps = []
-
-    def dev(a):
-        temps.append(_DeviceBuffer.of(h, a))
-        return temps[-1].ptr
-
-    try:
-        dX, dY, ds = dev(Xb), dev(Yb), dev(sb)
-        temps.extend([_DeviceBuffer(h, nb * D * S * item), _DeviceBuffer(h, nb * D * D * item)])
-        d_M, d_T = temps[-2].ptr, temps[-1].ptr
-        d_info = dev(np.zeros(nb, dtype=np.int32))
-        h.posterior_multi_batched(dtype, _abi.MEM_DEVICE, layout, nb, D, N, S, dX, ldx, Xb.shape[1], dY, max(N, 1), Yb.shape[1], noise_kind,
-                                  ds, sb.shape[1], prior_kind, dev(mwb), D, dev(Lb), ldl, Lb.shape[1], d_M, D, D * S, d_T, D, D * D, None, D,
-                                  D * D, None, S, d_info)
-        info = np.zeros(nb, dtype=np.int32)
-        h.memcpy_d2h(info, d_info)
-        if not np.any(info):
-            m, v, lp, tot, info = _kfold_columns_call(h, dtype, layout, nb, D, N, S, F, dX, ldx, Xb.shape[1], dY, Yb.shape[1], noise_kind,
-                                                      ds, sb.shape[1], d_M, D * S, d_T, D * D, temps)
-    finally:
-        for b in temps:
-            b.free()
-    bad = np.flatnonzero(info)
-    if bad.size:
-        e = _abi.PosDefException(int(info[bad[0]]))
-        e.index = int(bad[0])
-        raise e
-    return [KFold(m[b], v[b], lp[b], tot[b]) for b in range(nb)]
-
-
-def _kfold_columns_one(q, dtype, F):
-    N, S = q[5].shape
-    if q[3] == 0 or N == 0 or S == 0:
-        return KFold(np.empty((N, S), dtype=dtype), np.empty(N, dtype=dtype), np.empty((-(-N // F), S)), np.zeros(S))
-    return _kfold_columns_batch([q], dtype, F)[0]
+    return _heldout_map(fxs, [np.asarray(Y) for Y in Ys], _HELDOUT["loo_columns"], "loo_columns")
 
 
 def kfold_columns(fx, Y, fold_size, perm=None):
@@ -1636,21 +1401,7 @@ def kfold_columns(fx, Y, fold_size, perm=None):
     KFold(mean N x S, var N -- it does not depend on the column --, logpdf nfolds x S, total S).  Dense noise raises
     NotImplementedError (it couples the folds)."""
     F = _fold_size(fold_size)
-    Y = np.asarray(Y)
-    dtype = _loo_columns_dtype(fx, Y)
-    if perm is not None:
-        perm = np.asarray(perm, dtype=np.int64)
-        n = Y.shape[0] if Y.ndim == 2 else -1
-        if perm.shape != (n,) or not np.array_equal(np.sort(perm), np.arange(n)):
-            raise ValueError("perm must be a permutation of range(N)")
-    q = _loo_columns_problem(fx, Y, dtype, "kfold_columns", perm)
-    _kfold_columns_check(q[3], "kfold_columns")
-    r = _kfold_columns_one(q, dtype, F)
-    if perm is None:
-        return r
-    m, v = np.empty_like(r.mean), np.empty_like(r.var)
-    m[perm, :], v[perm] = r.mean, r.var
-    return KFold(m, v, r.logpdf, r.total)
+    return _heldout_one(fx, np.asarray(Y), _HELDOUT["kfold_columns"], "kfold_columns", F, perm, lambda q: _kfold_columns_check(q.D, "kfold_columns"))
 
 
 def kfold_columns_map(fxs, Ys, fold_size):
@@ -1658,34 +1409,8 @@ def kfold_columns_map(fxs, Ys, fold_size):
     problems (else one pair of calls per problem).  The first problem whose prior, noise or posterior is not positive definite raises
     PosDefException with its position as ``index``."""
     F = _fold_size(fold_size)
-    fxs, Ys = list(fxs), [np.asarray(Y) for Y in Ys]
-    if len(fxs) != len(Ys):
-        raise ValueError("as many target matrices as finite regressors are needed")
-    if not fxs:
-        return []
-    dtype = np.float32 if all(_loo_columns_dtype(fx, Y) == np.float32 for fx, Y in zip(fxs, Ys)) else np.float64
-    probs = [_loo_columns_problem(fx, Y, dtype, "kfold_columns_map") for fx, Y in zip(fxs, Ys)]
-    for q in probs:
-        _kfold_columns_check(q[3], "kfold_columns_map")
-
-    def one_by_one():
-        out = []
-        for i, q in enumerate(probs):
-            try:
-                out.append(_kfold_columns_one(q, dtype, F))
-            except _abi.PosDefException as e:
-                e.index = i
-                raise
-        return out
-
-    if any(isinstance(fx.f, BasisFunctionRegressor) and isinstance(fx.f.phi, RandomFourierFeatures) for fx in fxs):
-        return one_by_one()
-    sig = {(q[0].shape, q[0].flags.f_contiguous, q[1], q[3], q[4], q[5].shape[1], q[7], q[10],
-            isinstance((fx.f.blr if isinstance(fx.f, BasisFunctionRegressor) else fx.f).Lw, PDMat)) for q, fx in zip(probs, fxs)}
-    q0 = probs[0]
-    if len(sig) != 1 or q0[3] == 0 or q0[4] == 0 or q0[5].shape[1] == 0:
-        return one_by_one()
-    return _kfold_columns_batch(probs, dtype, F)
+    return _heldout_map(fxs, [np.asarray(Y) for Y in Ys], _HELDOUT["kfold_columns"], "kfold_columns_map", F,
+                        lambda q: _kfold_columns_check(q.D, "kfold_columns_map"))
 
 
 EvidenceGrid = namedtuple("EvidenceGrid", ["logpdf", "best", "alpha", "tau"])
@@ -1828,6 +1553,29 @@ class _DeviceBuffer:
             pass
 
 
+class _DeviceScope:
+    """The device temporaries of one call: ``dev(host_array)`` uploads and ``alloc(nbytes)`` reserves, both -> device pointer;
+    leaving the ``with`` block frees them all, whichever way it is left."""
+
+    def __init__(self, handle):
+        self.h, self._temps = handle, []
+
+    def alloc(self, nbytes):
+        self._temps.append(_DeviceBuffer(self.h, nbytes))
+        return self._temps[-1].ptr
+
+    def dev(self, host_array):
+        self._temps.append(_DeviceBuffer.of(self.h, host_array))
+        return self._temps[-1].ptr
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        for b in self._temps:
+            b.free()
+
+
 class ResidentPosterior:
     """A posterior kept ON THE DEVICE as its state (mw, T) -- T the upper factor of the precision -- and conditioned IN PLACE
     on further batches: the "repeated conditioning" pattern of reference test/bayesian_linear_regression.jl:49-70
@@ -1894,50 +1642,41 @@ class ResidentPosterior:
         if info[0] != 0:
             raise _abi.PosDefException(int(info[0]))
 
-    def _inputs(self, x, dev, temps):
+    def _inputs(self, x, scope):
         """-> (device pointer, layout, ldx, number of inputs) of phi(x) (RandomFourierFeatures: evaluated on the device)."""
         dtype, h, D = self.dtype, self._h, self.D
         if isinstance(self.phi, RandomFourierFeatures):
             Xin, ldxin, Din, k, Om, ph = self.phi._operands(x, dtype)
             if Om.shape[1] != D:
                 raise ValueError(f"number of features ({Om.shape[1]}) != length(mw) = {D}")
-            temps.append(_DeviceBuffer(h, D * max(k, 1) * np.dtype(dtype).itemsize))
-            dX, ldx = temps[-1].ptr, max(D, 1)
-            h.rff_features(dtype, _abi.MEM_DEVICE, Din, D, k, dev(Xin), ldxin, dev(Om), max(Din, 1), dev(ph), self.phi.scale, dX, ldx)
+            dX, ldx = scope.alloc(D * max(k, 1) * np.dtype(dtype).itemsize), max(D, 1)
+            h.rff_features(dtype, _abi.MEM_DEVICE, Din, D, k, scope.dev(Xin), ldxin, scope.dev(Om), max(Din, 1), scope.dev(ph), self.phi.scale,
+                           dX, ldx)
             return dX, _abi.LAYOUT_COLVECS, ldx, k
         X, layout, ldx, Dx, k = _x_layout(self.phi(x) if self.phi is not None else x, dtype)
         if Dx != D:
             raise ValueError(f"dimension of the inputs ({Dx}) != length(mw) = {D}")
-        return dev(X), layout, ldx, k
+        return scope.dev(X), layout, ldx, k
 
     def condition(self, x, Sy, y):
         """In-place update with the observations (x, Sy, y); returns log p(y | everything conditioned on so far)."""
         dtype, h, D = self.dtype, self._h, self.D
-        temps = []
-
-        def dev(a):
-            temps.append(_DeviceBuffer.of(h, a))
-            return temps[-1].ptr
-
-        try:
-            dX, layout, ldx, k = self._inputs(x, dev, temps)
+        with _DeviceScope(h) as scope:
+            dX, layout, ldx, k = self._inputs(x, scope)
             y = np.ascontiguousarray(y, dtype=dtype)
             if y.shape != (k,):
                 raise ValueError("length(y) != number of inputs")  # reference :74
             s, noise_kind = _noise(Sy, k, dtype)
             if noise_kind == _abi.NOISE_DENSE:
                 raise NotImplementedError("ResidentPosterior.condition takes scalar or diagonal noise (whiten a dense block first)")
-            d_lp = dev(np.zeros(1, dtype=np.float64))
-            d_info = dev(np.zeros(1, dtype=np.int32))
-            h.update_factor(dtype, _abi.MEM_DEVICE, layout, 1, D, k, dX, ldx, 0, dev(y), 0, noise_kind, dev(s), 0, self._mw.ptr, 0,
+            d_lp = scope.dev(np.zeros(1, dtype=np.float64))
+            d_info = scope.dev(np.zeros(1, dtype=np.int32))
+            h.update_factor(dtype, _abi.MEM_DEVICE, layout, 1, D, k, dX, ldx, 0, scope.dev(y), 0, noise_kind, scope.dev(s), 0, self._mw.ptr, 0,
                             self._T.ptr, max(D, 1), 0, d_lp, d_info)
             lp = np.zeros(1, dtype=np.float64)
             info = np.zeros(1, dtype=np.int32)
             h.memcpy_d2h(lp, d_lp)
             h.memcpy_d2h(info, d_info)
-        finally:
-            for b in temps:
-                b.free()
         if info[0] != 0:
             raise _abi.PosDefException(int(info[0]))
         return float(lp[0])
@@ -1948,63 +1687,61 @@ class ResidentPosterior:
         positive definite raises PosDefException(info) (include/blr_mi355x.h blr_downdate_factor_*) and leaves the state as it
         was."""
         dtype, h, D = self.dtype, self._h, self.D
-        temps = []
-
-        def dev(a):
-            temps.append(_DeviceBuffer.of(h, a))
-            return temps[-1].ptr
-
-        try:
-            dX, layout, ldx, k = self._inputs(x, dev, temps)
+        with _DeviceScope(h) as scope:
+            dX, layout, ldx, k = self._inputs(x, scope)
             y = np.ascontiguousarray(y, dtype=dtype)
             if y.shape != (k,):
                 raise ValueError("length(y) != number of inputs")  # reference :74
             s, noise_kind = _noise(Sy, k, dtype)
             if noise_kind == _abi.NOISE_DENSE:
                 raise NotImplementedError("ResidentPosterior.forget takes scalar or diagonal noise (whiten a dense block first)")
-            d_lp = dev(np.zeros(1, dtype=np.float64))
-            d_info = dev(np.zeros(1, dtype=np.int32))
-            h.downdate_factor(dtype, _abi.MEM_DEVICE, layout, 1, D, k, dX, ldx, 0, dev(y), 0, noise_kind, dev(s), 0, self._mw.ptr, 0,
+            d_lp = scope.dev(np.zeros(1, dtype=np.float64))
+            d_info = scope.dev(np.zeros(1, dtype=np.int32))
+            h.downdate_factor(dtype, _abi.MEM_DEVICE, layout, 1, D, k, dX, ldx, 0, scope.dev(y), 0, noise_kind, scope.dev(s), 0, self._mw.ptr, 0,
                               self._T.ptr, max(D, 1), 0, d_lp, d_info)
             lp = np.zeros(1, dtype=np.float64)
             info = np.zeros(1, dtype=np.int32)
             h.memcpy_d2h(lp, d_lp)
             h.memcpy_d2h(info, d_info)
-        finally:
-            for b in temps:
-                b.free()
         if info[0] != 0:
             raise _abi.PosDefException(int(info[0]))
         return float(lp[0])
+
+    def _heldout(self, row, what, why, x, Sy, target, F=None, means=None, S=None, check=None):
+        """The scoring entry point of ``row`` on the resident pointers (B = 1, no strides) for the observations (x, Sy, target); the
+        state is not touched.  ``means``, ``S``: the D x S block of a ResidentColumnsPosterior, whose factor this state is, and then
+        ``target`` is N x S; ``check(N)`` runs before the targets and the noise are staged."""
+        dtype, h, D = self.dtype, self._h, self.D
+        with _DeviceScope(h) as scope:
+            dX, layout, ldx, N = self._inputs(x, scope)
+            if S is None:
+                target = np.ascontiguousarray(target, dtype=dtype)
+                if target.shape != (N,):
+                    raise ValueError("length(y) != number of inputs")  # reference :74
+            else:
+                target = np.asfortranarray(target, dtype=dtype)
+                if target.shape != (N, S):
+                    raise ValueError("Y must be (number of inputs) x S")  # reference :74 per column
+            s, noise_kind = _noise(Sy, N, dtype)
+            if noise_kind == _abi.NOISE_DENSE:
+                raise NotImplementedError(f"{what} takes scalar or diagonal noise ({why})")
+            if check is not None:
+                check(N)
+            if S is not None and row.folds and N == 0:
+                return _heldout_empty(row, dtype, 0, S, F)
+            d_target = None if S is not None and N == 0 else scope.dev(target)
+            head, data = _heldout_operands(row, dtype, layout, 1, D, N, S, dX, ldx, 0, d_target, 0, noise_kind, scope.dev(s), 0)
+            m, v, lp, tot, info = _heldout_call(scope, row, head, F, data, self._mw.ptr if means is None else means, 0, self._T.ptr, 0)
+        if info[0] != 0:
+            raise _abi.PosDefException(int(info[0]))
+        return _heldout_records(row, m, v, lp, tot)[0]
 
     def loo(self, x, Sy, y):
         """Exact leave-one-out predictives of the observations (x, Sy, y), which the caller vouches the state contains: for each
         n what ``forget`` of observation n alone would report, without touching the state (blr_loo_batched_*, B = 1).  Returns
         LOO(mean, var, logpdf, total); a state with a non-positive diagonal entry or a non-positive variance raises
         PosDefException(info)."""
-        dtype, h, D = self.dtype, self._h, self.D
-        temps = []
-
-        def dev(a):
-            temps.append(_DeviceBuffer.of(h, a))
-            return temps[-1].ptr
-
-        try:
-            dX, layout, ldx, N = self._inputs(x, dev, temps)
-            y = np.ascontiguousarray(y, dtype=dtype)
-            if y.shape != (N,):
-                raise ValueError("length(y) != number of inputs")  # reference :74
-            s, noise_kind = _noise(Sy, N, dtype)
-            if noise_kind == _abi.NOISE_DENSE:
-                raise NotImplementedError("ResidentPosterior.loo takes scalar or diagonal noise (dense noise: a block leave-out)")
-            m, v, lp, tot, info = _loo_call(h, dtype, layout, 1, D, N, dX, ldx, 0, dev(y), 0, noise_kind, dev(s), 0, self._mw.ptr, 0,
-                                            self._T.ptr, 0, temps)
-        finally:
-            for b in temps:
-                b.free()
-        if info[0] != 0:
-            raise _abi.PosDefException(int(info[0]))
-        return LOO(m[0], v[0], lp[0], float(tot[0]))
+        return self._heldout(_HELDOUT["loo"], "ResidentPosterior.loo", "dense noise: a block leave-out", x, Sy, y)
 
     def kfold(self, x, Sy, y, fold_size):
         """Exact leave-fold-out predictives of the observations (x, Sy, y), which the caller vouches the state contains, for
@@ -2012,74 +1749,23 @@ class ResidentPosterior:
         ``condition`` would give, without touching the state (blr_kfold_batched_*, B = 1, on the resident pointers).  Returns
         KFold(mean, var, logpdf, total); a state with a non-positive diagonal entry or a non-positive variance raises
         PosDefException(info)."""
-        F = _fold_size(fold_size)
-        dtype, h, D = self.dtype, self._h, self.D
-        temps = []
-
-        def dev(a):
-            temps.append(_DeviceBuffer.of(h, a))
-            return temps[-1].ptr
-
-        try:
-            dX, layout, ldx, N = self._inputs(x, dev, temps)
-            y = np.ascontiguousarray(y, dtype=dtype)
-            if y.shape != (N,):
-                raise ValueError("length(y) != number of inputs")  # reference :74
-            s, noise_kind = _noise(Sy, N, dtype)
-            if noise_kind == _abi.NOISE_DENSE:
-                raise NotImplementedError("ResidentPosterior.kfold takes scalar or diagonal noise (dense noise couples the folds)")
-            m, v, lp, tot, info = _kfold_call(h, dtype, layout, 1, D, N, F, dX, ldx, 0, dev(y), 0, noise_kind, dev(s), 0, self._mw.ptr,
-                                              0, self._T.ptr, 0, temps)
-        finally:
-            for b in temps:
-                b.free()
-        if info[0] != 0:
-            raise _abi.PosDefException(int(info[0]))
-        return KFold(m[0], v[0], lp[0], float(tot[0]))
+        return self._heldout(_HELDOUT["kfold"], "ResidentPosterior.kfold", "dense noise couples the folds", x, Sy, y, _fold_size(fold_size))
 
     def kfold_large(self, x, Sy, y, fold_size):
         """`kfold` for LARGE folds: any integer ``fold_size`` >= 1 with ceil(N / fold_size) <= 1024, D <= 128
         (blr_kfold_large_batched_*, B = 1, on the resident pointers; the state is not touched).  Returns KFold(mean, var, logpdf,
         total); a state with a non-positive diagonal entry or a non-positive variance raises PosDefException(info)."""
         F = _fold_size_large(fold_size)
-        dtype, h, D = self.dtype, self._h, self.D
-        temps = []
-
-        def dev(a):
-            temps.append(_DeviceBuffer.of(h, a))
-            return temps[-1].ptr
-
-        try:
-            dX, layout, ldx, N = self._inputs(x, dev, temps)
-            y = np.ascontiguousarray(y, dtype=dtype)
-            if y.shape != (N,):
-                raise ValueError("length(y) != number of inputs")  # reference :74
-            s, noise_kind = _noise(Sy, N, dtype)
-            if noise_kind == _abi.NOISE_DENSE:
-                raise NotImplementedError("ResidentPosterior.kfold_large takes scalar or diagonal noise (dense noise couples the folds)")
-            _kfold_large_check(D, N, F, "ResidentPosterior.kfold_large")
-            m, v, lp, tot, info = _kfold_call(h, dtype, layout, 1, D, N, F, dX, ldx, 0, dev(y), 0, noise_kind, dev(s), 0, self._mw.ptr,
-                                              0, self._T.ptr, 0, temps, large=True)
-        finally:
-            for b in temps:
-                b.free()
-        if info[0] != 0:
-            raise _abi.PosDefException(int(info[0]))
-        return KFold(m[0], v[0], lp[0], float(tot[0]))
+        return self._heldout(_HELDOUT["kfold_large"], "ResidentPosterior.kfold_large", "dense noise couples the folds", x, Sy, y, F,
+                             check=lambda N: _kfold_large_check(self.D, N, F, "ResidentPosterior.kfold_large"))
 
     def rand(self, rng, x, S, Sy=None):
         """S draws at the inputs x from the resident state (N x S), without copying T to the host (blr_rand_batched_*, B = 1):
         with Sy, ``rand(rng, st.regressor()(x, Sy), S)`` (reference :49-53: Z1 drawn first, then Z2); without it the noise-free
         function values ``evaluate(rand(rng, st.regressor(), S), x)`` (sampling_functions.jl:16-18, 27-38: Z1 only)."""
         dtype, h, D, S = self.dtype, self._h, self.D, int(S)
-        temps = []
-
-        def dev(a):
-            temps.append(_DeviceBuffer.of(h, a))
-            return temps[-1].ptr
-
-        try:
-            dX, layout, ldx, N = self._inputs(x, dev, temps)
+        with _DeviceScope(h) as scope:
+            dX, layout, ldx, N = self._inputs(x, scope)
             s, noise_kind = (np.ones(1, dtype=dtype), _abi.NOISE_ISOTROPIC) if Sy is None else _noise(Sy, N, dtype, need_cholesky=True)
             if noise_kind == _abi.NOISE_DENSE:
                 raise NotImplementedError("ResidentPosterior.rand takes scalar or diagonal noise")
@@ -2088,11 +1774,10 @@ class ResidentPosterior:
             Y = np.empty((N, S), dtype=dtype, order="F")
             if N == 0 or S == 0:
                 return Y
-            temps.append(_DeviceBuffer(h, Y.nbytes))
-            dY = temps[-1].ptr
-            d_info = dev(np.zeros(1, dtype=np.int32))
-            h.rand_batched(dtype, _abi.MEM_DEVICE, layout, 1, D, N, S, dX, ldx, 0, noise_kind, dev(s), 0, _abi.PRIOR_UPPER_FACTOR,
-                           self._mw.ptr, 0, self._T.ptr, max(D, 1), 0, dev(Z1), D, 0, dev(Z2) if Z2 is not None else None, N, 0,
+            dY = scope.alloc(Y.nbytes)
+            d_info = scope.dev(np.zeros(1, dtype=np.int32))
+            h.rand_batched(dtype, _abi.MEM_DEVICE, layout, 1, D, N, S, dX, ldx, 0, noise_kind, scope.dev(s), 0, _abi.PRIOR_UPPER_FACTOR,
+                           self._mw.ptr, 0, self._T.ptr, max(D, 1), 0, scope.dev(Z1), D, 0, scope.dev(Z2) if Z2 is not None else None, N, 0,
                            None, D, 0, dY, N, 0, d_info)
             info = np.zeros(1, dtype=np.int32)
             h.memcpy_d2h(info, d_info)
@@ -2100,34 +1785,23 @@ class ResidentPosterior:
                 raise _abi.PosDefException(int(info[0]))
             h.memcpy_d2h(Y, dY)
             return Y
-        finally:
-            for b in temps:
-                b.free()
 
     def _cov(self, x, Sy, want_mean):
         dtype, h, D = self.dtype, self._h, self.D
-        temps = []
-
-        def dev(a):
-            temps.append(_DeviceBuffer.of(h, a))
-            return temps[-1].ptr
-
-        try:
-            dX, layout, ldx, N = self._inputs(x, dev, temps)
+        with _DeviceScope(h) as scope:
+            dX, layout, ldx, N = self._inputs(x, scope)
             s, noise_kind = _noise(Sy, N, dtype)
             m = np.empty(N, dtype=dtype) if want_mean else None
             Cv = np.empty((N, N), dtype=dtype, order="F")
             if N == 0:
                 return m, Cv
-            temps.append(_DeviceBuffer(h, Cv.nbytes))
-            d_C = temps[-1].ptr
+            d_C = scope.alloc(Cv.nbytes)
             d_m = None
             if want_mean:
-                temps.append(_DeviceBuffer(h, m.nbytes))
-                d_m = temps[-1].ptr
+                d_m = scope.alloc(m.nbytes)
             info = np.zeros(1, dtype=np.int32)
-            d_info = dev(info)
-            h.mean_and_cov_batched(dtype, _abi.MEM_DEVICE, layout, 1, D, N, dX, ldx, 0, noise_kind, dev(s), N, 0, _abi.PRIOR_UPPER_FACTOR,
+            d_info = scope.dev(info)
+            h.mean_and_cov_batched(dtype, _abi.MEM_DEVICE, layout, 1, D, N, dX, ldx, 0, noise_kind, scope.dev(s), N, 0, _abi.PRIOR_UPPER_FACTOR,
                                    self._mw.ptr if want_mean else None, 0, self._T.ptr, max(D, 1), 0, d_m, N, d_C, N, 0, d_info)
             h.memcpy_d2h(info, d_info)
             if info[0] > 0:
@@ -2136,9 +1810,6 @@ class ResidentPosterior:
             if want_mean:
                 h.memcpy_d2h(m, d_m)
             return m, Cv
-        finally:
-            for b in temps:
-                b.free()
 
     def cov(self, x, Sy=1e-18):
         """cov(f(x, Sy)) (reference :35-38) from the resident state: the full N x N predictive covariance, without copying T to the
@@ -2230,22 +1901,13 @@ class ResidentPosteriorBatch:
         _, offsets, _, X, layout, ldx, Dx, y, s, noise_kind, strides = ops[:11]
         if Dx != D:
             raise ValueError(f"dimension of the inputs ({Dx}) != length(mw) = {D}")
-        temps = []
-
-        def dev(a):
-            temps.append(_DeviceBuffer.of(h, a))
-            return temps[-1].ptr
-
         lp, info = np.zeros(B, dtype=np.float64), np.zeros(B, dtype=np.int32)
-        try:
-            d_lp, d_info = dev(lp), dev(info)
-            call(dtype, _abi.MEM_DEVICE, layout, B, D, offsets, dev(X.reshape(-1, order="A")), ldx, dev(y), noise_kind, dev(s), strides,
-                 self._mw.ptr, D, self._T.ptr, max(D, 1), D * D, d_lp, d_info)
+        with _DeviceScope(h) as scope:
+            d_lp, d_info = scope.dev(lp), scope.dev(info)
+            call(dtype, _abi.MEM_DEVICE, layout, B, D, offsets, scope.dev(X.reshape(-1, order="A")), ldx, scope.dev(y), noise_kind, scope.dev(s),
+                 strides, self._mw.ptr, D, self._T.ptr, max(D, 1), D * D, d_lp, d_info)
             h.memcpy_d2h(lp, d_lp)
             h.memcpy_d2h(info, d_info)
-        finally:
-            for b in temps:
-                b.free()
         _raise_first_failed(info)
         return lp
 
@@ -2316,14 +1978,8 @@ class ResidentColumnsPosterior:
 
     def _step(self, call, what, x, Sy, Y):
         dtype, h, D, S = self.dtype, self._h, self.D, self.S
-        temps = []
-
-        def dev(a):
-            temps.append(_DeviceBuffer.of(h, a))
-            return temps[-1].ptr
-
-        try:
-            dX, layout, ldx, k = self._col0._inputs(x, dev, temps)
+        with _DeviceScope(h) as scope:
+            dX, layout, ldx, k = self._col0._inputs(x, scope)
             Y = np.asfortranarray(Y, dtype=dtype)
             if Y.shape != (k, S):
                 raise ValueError("Y must be (number of inputs) x S")  # reference :74 per column
@@ -2332,14 +1988,11 @@ class ResidentColumnsPosterior:
                 raise NotImplementedError(f"ResidentColumnsPosterior.{what} takes scalar or diagonal noise (whiten a dense block first)")
             lp = np.zeros(S, dtype=np.float64)
             info = np.zeros(1, dtype=np.int32)
-            d_lp, d_info = dev(lp), dev(info)
-            call(dtype, _abi.MEM_DEVICE, layout, 1, D, k, S, dX, ldx, 0, dev(Y) if k else None, max(k, 1), 0, noise_kind, dev(s), 0,
+            d_lp, d_info = scope.dev(lp), scope.dev(info)
+            call(dtype, _abi.MEM_DEVICE, layout, 1, D, k, S, dX, ldx, 0, scope.dev(Y) if k else None, max(k, 1), 0, noise_kind, scope.dev(s), 0,
                  self._M.ptr, max(D, 1), 0, self._T.ptr, max(D, 1), 0, d_lp, S, d_info)
             h.memcpy_d2h(lp, d_lp)
             h.memcpy_d2h(info, d_info)
-        finally:
-            for b in temps:
-                b.free()
         if info[0] != 0:
             raise _abi.PosDefException(int(info[0]))
         return lp
@@ -2360,29 +2013,8 @@ class ResidentColumnsPosterior:
         the state contains: per input and column what ``forget`` of that observation alone would report, without touching the state
         (blr_loo_multi_batched_* on device pointers to the resident state, B = 1).  Returns LOO(mean N x S, var N, logpdf N x S,
         total S); a state with a non-positive diagonal entry or a non-positive variance raises PosDefException(info)."""
-        dtype, h, D, S = self.dtype, self._h, self.D, self.S
-        temps = []
-
-        def dev(a):
-            temps.append(_DeviceBuffer.of(h, a))
-            return temps[-1].ptr
-
-        try:
-            dX, layout, ldx, N = self._col0._inputs(x, dev, temps)
-            Y = np.asfortranarray(Y, dtype=dtype)
-            if Y.shape != (N, S):
-                raise ValueError("Y must be (number of inputs) x S")  # reference :74 per column
-            s, noise_kind = _noise(Sy, N, dtype)
-            if noise_kind == _abi.NOISE_DENSE:
-                raise NotImplementedError("ResidentColumnsPosterior.loo takes scalar or diagonal noise (dense noise: a block leave-out)")
-            m, v, lp, tot, info = _loo_columns_call(h, dtype, layout, 1, D, N, S, dX, ldx, 0, dev(Y) if N else None, 0, noise_kind, dev(s), 0,
-                                                    self._M.ptr, 0, self._T.ptr, 0, temps)
-        finally:
-            for b in temps:
-                b.free()
-        if info[0] != 0:
-            raise _abi.PosDefException(int(info[0]))
-        return LOO(m[0], v[0], lp[0], tot[0])
+        return self._col0._heldout(_HELDOUT["loo_columns"], "ResidentColumnsPosterior.loo", "dense noise: a block leave-out", x, Sy, Y,
+                                   means=self._M.ptr, S=self.S)
 
     def kfold(self, x, Sy, Y, fold_size):
         """Exact leave-fold-out (K-fold) predictives of the observations (x, Sy, Y), Y one row of S targets per input, which the
@@ -2391,43 +2023,14 @@ class ResidentColumnsPosterior:
         (blr_kfold_multi_batched_* on device pointers to the resident state, B = 1).  Returns KFold(mean N x S, var N, logpdf
         nfolds x S, total S); a state with a non-positive diagonal entry or a non-positive variance raises PosDefException(info)."""
         F = _fold_size(fold_size)
-        dtype, h, D, S = self.dtype, self._h, self.D, self.S
-        _kfold_columns_check(D, "ResidentColumnsPosterior.kfold")
-        temps = []
-
-        def dev(a):
-            temps.append(_DeviceBuffer.of(h, a))
-            return temps[-1].ptr
-
-        try:
-            dX, layout, ldx, N = self._col0._inputs(x, dev, temps)
-            Y = np.asfortranarray(Y, dtype=dtype)
-            if Y.shape != (N, S):
-                raise ValueError("Y must be (number of inputs) x S")  # reference :74 per column
-            s, noise_kind = _noise(Sy, N, dtype)
-            if noise_kind == _abi.NOISE_DENSE:
-                raise NotImplementedError("ResidentColumnsPosterior.kfold takes scalar or diagonal noise (dense noise couples the folds)")
-            if N == 0:
-                return KFold(np.empty((0, S), dtype=dtype), np.empty(0, dtype=dtype), np.empty((0, S)), np.zeros(S))
-            m, v, lp, tot, info = _kfold_columns_call(h, dtype, layout, 1, D, N, S, F, dX, ldx, 0, dev(Y), 0, noise_kind, dev(s), 0,
-                                                      self._M.ptr, 0, self._T.ptr, 0, temps)
-        finally:
-            for b in temps:
-                b.free()
-        if info[0] != 0:
-            raise _abi.PosDefException(int(info[0]))
-        return KFold(m[0], v[0], lp[0], tot[0])
+        _kfold_columns_check(self.D, "ResidentColumnsPosterior.kfold")
+        return self._col0._heldout(_HELDOUT["kfold_columns"], "ResidentColumnsPosterior.kfold", "dense noise couples the folds", x, Sy, Y, F,
+                                   means=self._M.ptr, S=self.S)
 
     def _marginals(self, x, Sy, want_var):
         dtype, h, D, S = self.dtype, self._h, self.D, self.S
-        temps = []
-
-        def dev(a):
-            temps.append(_DeviceBuffer.of(h, a))
-            return temps[-1].ptr
-
-        try:
-            dX, layout, ldx, N = self._col0._inputs(x, dev, temps)
+        with _DeviceScope(h) as scope:
+            dX, layout, ldx, N = self._col0._inputs(x, scope)
             s, noise_kind = _noise(Sy, N, dtype)
             if noise_kind == _abi.NOISE_DENSE:  # var adds diag(Sigma_y) (:43)
                 s, noise_kind = np.ascontiguousarray(np.diag(s)), _abi.NOISE_DIAGONAL
@@ -2435,15 +2038,13 @@ class ResidentColumnsPosterior:
             v = np.empty(N, dtype=dtype) if want_var else None
             if N == 0:
                 return m, v
-            temps.append(_DeviceBuffer(h, m.nbytes))
-            d_m = temps[-1].ptr
+            d_m = scope.alloc(m.nbytes)
             d_v = None
             if want_var:
-                temps.append(_DeviceBuffer(h, v.nbytes))
-                d_v = temps[-1].ptr
+                d_v = scope.alloc(v.nbytes)
             info = np.zeros(1, dtype=np.int32)
-            d_info = dev(info)
-            h.marginals_multi_batched(dtype, _abi.MEM_DEVICE, layout, 1, D, N, S, dX, ldx, 0, noise_kind, dev(s) if want_var else None, 0,
+            d_info = scope.dev(info)
+            h.marginals_multi_batched(dtype, _abi.MEM_DEVICE, layout, 1, D, N, S, dX, ldx, 0, noise_kind, scope.dev(s) if want_var else None, 0,
                                       _abi.PRIOR_UPPER_FACTOR, self._M.ptr, max(D, 1), 0, self._T.ptr if want_var else None, max(D, 1), 0,
                                       d_m, max(N, 1), 0, d_v, N, d_info)
             h.memcpy_d2h(info, d_info)
@@ -2453,9 +2054,6 @@ class ResidentColumnsPosterior:
             if want_var:
                 h.memcpy_d2h(v, d_v)
             return m, v
-        finally:
-            for b in temps:
-                b.free()
 
     def mean_and_var(self, x, Sy=1e-18):
         """mean_and_var(f_c(x, Sy)) (reference :47) of the S resident columns: (mean N x S, var N), blr_marginals_multi_batched_* on
@@ -2477,14 +2075,8 @@ class ResidentColumnsPosterior:
         ``rand(rng, st.regressors()[c](x, Sy), R)`` with the normals drawn column by column in the reference's order (:49-53: Z1_c,
         then Z2_c, for c = 0 .. S-1); without it the noise-free function values of sampling_functions.jl:16-18, 27-38 (Z1_c only)."""
         dtype, h, D, S, R = self.dtype, self._h, self.D, self.S, int(R)
-        temps = []
-
-        def dev(a):
-            temps.append(_DeviceBuffer.of(h, a))
-            return temps[-1].ptr
-
-        try:
-            dX, layout, ldx, N = self._col0._inputs(x, dev, temps)
+        with _DeviceScope(h) as scope:
+            dX, layout, ldx, N = self._col0._inputs(x, scope)
             s, noise_kind = (np.ones(1, dtype=dtype), _abi.NOISE_ISOTROPIC) if Sy is None else _noise(Sy, N, dtype, need_cholesky=True)
             if noise_kind == _abi.NOISE_DENSE:
                 raise NotImplementedError("ResidentColumnsPosterior.rand takes scalar or diagonal noise")
@@ -2496,21 +2088,17 @@ class ResidentColumnsPosterior:
                     Z2[:, c * R:(c + 1) * R] = _randn(rng, N, R, dtype)
             Y = np.empty((N, S * R), dtype=dtype, order="F")  # draw j = c R + r
             if N and R:
-                temps.append(_DeviceBuffer(h, Y.nbytes))
-                dY = temps[-1].ptr
-                d_info = dev(np.zeros(1, dtype=np.int32))
-                h.rand_multi_batched(dtype, _abi.MEM_DEVICE, layout, 1, D, N, S, R, dX, ldx, 0, noise_kind, dev(s), 0,
-                                     _abi.PRIOR_UPPER_FACTOR, self._M.ptr, max(D, 1), 0, self._T.ptr, max(D, 1), 0, dev(Z1), D, 0,
-                                     dev(Z2) if Z2 is not None else None, N, 0, None, D, 0, dY, N, 0, d_info)
+                dY = scope.alloc(Y.nbytes)
+                d_info = scope.dev(np.zeros(1, dtype=np.int32))
+                h.rand_multi_batched(dtype, _abi.MEM_DEVICE, layout, 1, D, N, S, R, dX, ldx, 0, noise_kind, scope.dev(s), 0,
+                                     _abi.PRIOR_UPPER_FACTOR, self._M.ptr, max(D, 1), 0, self._T.ptr, max(D, 1), 0, scope.dev(Z1), D, 0,
+                                     scope.dev(Z2) if Z2 is not None else None, N, 0, None, D, 0, dY, N, 0, d_info)
                 info = np.zeros(1, dtype=np.int32)
                 h.memcpy_d2h(info, d_info)
                 if info[0] != 0:
                     raise _abi.PosDefException(int(info[0]))
                 h.memcpy_d2h(Y, dY)
             return np.asfortranarray(Y.reshape((N, R, S), order="F").transpose(0, 2, 1))
-        finally:
-            for b in temps:
-                b.free()
 
     def state(self):
         """host copies (M, T) of the resident state: M D x S, T column-major upper"""

@@ -15,6 +15,7 @@ from blr_amd import regressor as R
 
 from _kfold_ref import brute_force, closed_form, posterior_state, rng_of, state
 from _kfold_large_ref import SHAPES, closed_form_large, fp32_bounds_large
+from _recorder import Recorder as _Recorder
 
 SYMS = ("blr_kfold_large_batched_f64", "blr_kfold_large_batched_f32")
 ARITY = 28
@@ -135,49 +136,6 @@ def test_argument_errors_without_a_device(name):
     assert _call(name, D=128, ldx=128, ldt=128, T=np.zeros(1), X=np.zeros(1), mw=np.zeros(1), B=1) == -1
     assert _call(name, N=1 << 30, F=1 << 20, X=np.zeros(1), B=1) == -1                  # 1024 folds of 2^20
     assert _call(name, N=1024, F=1, B=1, X=np.zeros(1), y=np.zeros(1), s=np.zeros(1)) == -1
-
-
-class _Recorder:
-    """stands in for the library handle: records the entry points; the zero status lets the unpacking go through"""
-
-    def __init__(self):
-        self.calls = []
-        self.bufs = {}
-
-    # device memory as host arrays, keyed by a made-up pointer
-    def device_alloc(self, nbytes):
-        ptr = 4096 * (len(self.bufs) + 1)
-        self.bufs[ptr] = np.zeros(max(int(nbytes), 1), dtype=np.uint8)
-        return ptr
-
-    def device_free(self, ptr):
-        self.bufs.pop(ptr, None)
-
-    def memcpy_h2d(self, dptr, host):
-        raw = np.asarray(host).reshape(-1, order="A").view(np.uint8)
-        self.bufs[dptr][:raw.size] = raw
-
-    def memcpy_d2h(self, host, dptr):
-        flat = host.reshape(-1, order="A").view(np.uint8)
-        flat[...] = self.bufs[dptr][:flat.size]
-
-    def posterior_batched(self, *args):
-        self.calls.append(("posterior", args))
-        return 0
-
-    def _fold(self, which, args):
-        self.calls.append((which, args))
-        # mean = 10 + n, var = 100 + n per regressor: what the wrapper scatters back
-        dtype, B, N = args[0], args[3], args[5]
-        for ptr, base in ((args[20], 10.0), (args[22], 100.0)):
-            self.memcpy_h2d(ptr, np.tile(base + np.arange(N), B).astype(dtype))
-        return 0
-
-    def kfold(self, *args):
-        return self._fold("kfold", args)
-
-    def kfold_large(self, *args):
-        return self._fold("kfold_large", args)
 
 
 def _problem(rng, D, N, x=None):

@@ -14,6 +14,7 @@ import pytest
 import blr_amd
 from blr_amd import _abi
 from blr_amd import regressor as R
+from _recorder import Recorder as _Recorder
 
 SYMS = ("blr_loo_multi_batched_f64", "blr_loo_multi_batched_f32")
 ARITY = 33
@@ -141,39 +142,6 @@ def test_argument_errors_without_a_device(name):
     assert _call(name, N=0, X=None, Y=None, s=None, ldY=0, ld_lm=0, ld_ll=0) == -1      # N = 0 still writes totals and info
     assert _call(name, noise_kind=_abi.NOISE_DIAGONAL, s=np.ones(10), strides=5) == -1
     assert _call(name, layout=_abi.LAYOUT_ROWVECS, ldx=5) == -1
-
-
-class _Recorder:
-    """stands in for the library handle: records the entry points and fills status and outputs so that the unpacking goes through"""
-
-    def __init__(self):
-        self.calls = []
-        self.bufs = {}
-
-    # device memory as host arrays, keyed by a made-up pointer
-    def device_alloc(self, nbytes):
-        ptr = 4096 * (len(self.bufs) + 1)
-        self.bufs[ptr] = np.zeros(max(int(nbytes), 1), dtype=np.uint8)
-        return ptr
-
-    def device_free(self, ptr):
-        self.bufs.pop(ptr, None)
-
-    def memcpy_h2d(self, dptr, host):
-        raw = np.asarray(host).reshape(-1, order="A").view(np.uint8)
-        self.bufs[dptr][:raw.size] = raw
-
-    def memcpy_d2h(self, host, dptr):
-        flat = host.reshape(-1, order="A").view(np.uint8)
-        flat[...] = self.bufs[dptr][:flat.size]
-
-    def posterior_multi_batched(self, *args):
-        self.calls.append(("fit", args))
-        return 0
-
-    def loo_multi_batched(self, *args):
-        self.calls.append(("loo_multi", args))
-        return 0
 
 
 def _patch(monkeypatch, rec):
