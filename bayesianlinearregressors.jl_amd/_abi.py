@@ -126,6 +126,9 @@ for _suf in ("f64", "f32"):
     _SIGS[f"blr_logpdf_grid_{_suf}"] = (
         [_H, _int, _int, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _int, _vp, _i64, _int, _vp, _i64, _vp, _i64, _i64,
          _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _i64], _int)
+    _SIGS[f"blr_logpdf_grid_ragged_{_suf}"] = (
+        [_H, _int, _int, _i64, _i64, _vp, _vp, _i64, _vp, _int, _vp, _i64, _int, _vp, _i64, _vp, _i64, _i64,
+         _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _i64], _int)
     _SIGS[f"blr_posterior_{_suf}"] = (
         [_H, _int, _i64, _i64, _vp, _i64, _vp, _int, _vp, _int, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp], _int)
     _SIGS[f"blr_marginals_batched_{_suf}"] = (
@@ -535,6 +538,20 @@ class Handle:
                              strides, prior_kind, _ptr(mw), stridemw, _ptr(Lw), ldl, strideLw, G, _ptr(alpha), stride_alpha,
                              _ptr(tau), stride_tau, _ptr(logpdf), stride_lp, _ptr(best), _ptr(mw_best), stride_mwbest,
                              _ptr(T_best), ldt, strideT, _ptr(info), stride_info))
+
+    def logpdf_grid_ragged(self, dtype, memspace, layout, B, D, offsets, X, ldx, y, noise_kind, s, strides, prior_kind, mw, stridemw,
+                           Lw, ldl, strideLw, G, alpha, stride_alpha, tau, stride_tau, logpdf, stride_lp, best, mw_best,
+                           stride_mwbest, T_best, ldt, strideT, info, stride_info):
+        """The evidence grid of B regressors with unequal observation counts, packed side by side, in one call; include/blr_mi355x.h
+        blr_logpdf_grid_ragged_*.  offsets: B + 1 non-decreasing entries, always on the host (any integer sequence)."""
+        fn = getattr(self.lib, f"blr_logpdf_grid_ragged_{suffix(dtype)}")
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        if offsets.shape != (B + 1,):
+            raise ValueError(f"offsets must have B + 1 = {B + 1} entries, got shape {offsets.shape}")
+        return self.check(fn(self._h, memspace, layout, B, D, _ptr(offsets), _ptr(X), ldx, _ptr(y), noise_kind, _ptr(s), strides,
+                             prior_kind, _ptr(mw), stridemw, _ptr(Lw), ldl, strideLw, G, _ptr(alpha), stride_alpha, _ptr(tau),
+                             stride_tau, _ptr(logpdf), stride_lp, _ptr(best), _ptr(mw_best), stride_mwbest, _ptr(T_best), ldt,
+                             strideT, _ptr(info), stride_info))
 
     def posterior(self, dtype, layout, D, N, X, ldx, y, noise_kind, s, prior_kind, mw, Lw, ldl, mw_post, T_post, ldt,
                   Lw_post, ldlp, logpdf):

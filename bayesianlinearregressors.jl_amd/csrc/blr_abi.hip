@@ -45,6 +45,7 @@
 #include "blr_kfold_ragged.hpp"
 #include "blr_kfold_large_ragged.hpp"
 #include "blr_revise_ragged.hpp"
+#include "blr_grid_ragged.hpp"
 #include "blr_host.hpp"
 #include "blr_large_plan.hpp"
 
@@ -3224,6 +3225,18 @@ int launch_grid_stats(blr_handle* h, const GridArgs<T>& a) {
   return 0;
 }
 
+// grid_prior_kernel<T, nb> over p.B regressors (it reads the prior's fields of p and writes prior_info / prior_logdet): the one place
+// that launches it, for blr_logpdf_grid_* (nb known at compile time: NB = nb) and blr_logpdf_grid_ragged_* (nb at run time)
+template <typename T, int NB = 1>
+int grid_prior_enqueue(blr_handle* h, int nb, const GridArgs<T>& p) {
+  if constexpr (NB < 8) if (nb != NB) return grid_prior_enqueue<T, NB + 1>(h, nb, p);
+  using C = SmallCfg<T, NB>;
+  if (const int rc = set_lds_once(h, grid_prior_kernel<T, NB>, (size_t)C::LDS_BYTES)) return rc;
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(grid_prior_kernel<T, NB>), dim3((unsigned)p.B), dim3(kThreads), C::LDS_BYTES, h->stream, p);
+  HIP_TRY(h, hipGetLastError());
+  return 0;
+}
+
 // device operands, D <= 128: prior, statistics (+ reduce), settings, argmax, refit -- the same launches whatever B and G are
 template <typename T, int NB>
 int grid_small_nb(blr_handle* h, GridArgs<T> a, bool vec_ok) {
@@ -3239,10 +3252,8 @@ int grid_small_nb(blr_handle* h, GridArgs<T> a, bool vec_ok) {
   a.stats = reinterpret_cast<T*>(ws + o_st); a.scal = reinterpret_cast<double*>(ws + o_sc); a.bad = reinterpret_cast<int32_t*>(ws + o_bad);
   a.prior_logdet = reinterpret_cast<double*>(ws + o_pl); a.prior_info = reinterpret_cast<int32_t*>(ws + o_pi);
   a.best = reinterpret_cast<int64_t*>(ws + o_best);
-  if ((rc = set_lds_once(h, grid_prior_kernel<T, NB>, (size_t)C::LDS_BYTES))) return rc;
   if ((rc = set_lds_once(h, grid_eval_kernel<T, NB>, (size_t)C::LDS_BYTES))) return rc;
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(grid_prior_kernel<T, NB>), dim3((unsigned)a.B), dim3(kThreads), C::LDS_BYTES, h->stream, a);
-  HIP_TRY(h, hipGetLastError());  // (every launch is checked before the ones that read its output are enqueued)
+  if ((rc = grid_prior_enqueue<T, NB>(h, NB, a))) return rc;  // (every launch is checked before the ones that read its output are enqueued)
   if (a.layout == BLR_LAYOUT_ROWVECS) rc = launch_grid_stats<T, NB, 1>(h, a);
   else if (vec_ok) rc = launch_grid_stats<T, NB, 4>(h, a);
   else rc = launch_grid_stats<T, NB, 0>(h, a);
@@ -3614,6 +3625,168 @@ int posterior_ragged(blr_handle* h, int memspace, int layout, int64_t B, int64_t
                                      a.mw_post ? a.mw_post + b * stride_mwpost : (T*)nullptr, 0, a.T_post ? a.T_post + b * strideT : (T*)nullptr,
                                      ldt, 0, a.Lw_post ? a.Lw_post + b * strideLp : (T*)nullptr, ldlp, 0,
                                      a.logpdf ? a.logpdf + b : (double*)nullptr, a.info + b);
+       })))
+    return rc;
+  return io.finish();
+}
+
+// ---- evidence grid for regressors with unequal counts (blr_grid_ragged.hpp, blr_grid_ragged_plan.hpp) ---------------
+static_assert(kEvidenceNoBad == kGridNoBad && kEvidencePriorNone == kGridPriorNone &&
+                  evidence_stat_elems<double, 8>() == grid_stat_elems<double, 8>() && evidence_stat_elems<float, 3>() == grid_stat_elems<float, 3>(),
+              "blr_grid_ragged.hpp repeats the constants of blr_grid.hpp");
+#define BLR_EVIDENCE_PICK(NAME, RET)                                                                             \
+  template <typename... A> inline RET NAME(double, A... a) { return NAME##_f64(a...); }                          \
+  template <typename... A> inline RET NAME(float, A... a) { return NAME##_f32(a...); }
+BLR_EVIDENCE_PICK(ragged_evidence_stats_ptr, const void*)
+BLR_EVIDENCE_PICK(ragged_evidence_eval_ptr, const void*)
+BLR_EVIDENCE_PICK(ragged_evidence_lds, size_t)
+BLR_EVIDENCE_PICK(ragged_evidence_stat_elems, int)
+#undef BLR_EVIDENCE_PICK
+inline void ragged_evidence_stats_launch(int NB, int mode, unsigned grid, hipStream_t st, const RaggedEvidenceArgs<double>& a) { ragged_evidence_stats_launch_f64(NB, mode, grid, st, a); }
+inline void ragged_evidence_stats_launch(int NB, int mode, unsigned grid, hipStream_t st, const RaggedEvidenceArgs<float>& a) { ragged_evidence_stats_launch_f32(NB, mode, grid, st, a); }
+inline void ragged_evidence_reduce_launch(int NB, unsigned B, hipStream_t st, const RaggedEvidenceArgs<double>& a) { ragged_evidence_reduce_launch_f64(NB, B, st, a); }
+inline void ragged_evidence_reduce_launch(int NB, unsigned B, hipStream_t st, const RaggedEvidenceArgs<float>& a) { ragged_evidence_reduce_launch_f32(NB, B, st, a); }
+inline void ragged_evidence_eval_launch(int NB, unsigned grid, hipStream_t st, const RaggedEvidenceArgs<double>& a) { ragged_evidence_eval_launch_f64(NB, grid, st, a); }
+inline void ragged_evidence_eval_launch(int NB, unsigned grid, hipStream_t st, const RaggedEvidenceArgs<float>& a) { ragged_evidence_eval_launch_f32(NB, grid, st, a); }
+
+// device operands, D <= 128: the launches of grid_small_nb with the statistics pass over the plan's items.  The loader is picked as
+// grid_launch picks it for B = 1 on a slice: every slice of an aligned X with an aligned ldx is aligned, whatever `offsets` holds.
+template <typename T>
+int grid_ragged_small(blr_handle* h, RaggedEvidenceArgs<T> a, const int64_t* offsets, int64_t* best_out) {
+  const int64_t B = a.B;
+  const int NB = (a.D + 15) / 16;
+  const bool vec_ok = a.layout == BLR_LAYOUT_COLVECS && a.D % Mfma<T>::VEC == 0 && aligned16(a.X, a.ldx, 0);
+  const int mode = a.layout == BLR_LAYOUT_ROWVECS ? 1 : (vec_ok ? 4 : 0);
+  const void* const k_stats = ragged_evidence_stats_ptr(T(0), NB, mode);
+  const void* const k_eval = ragged_evidence_eval_ptr(T(0), NB);
+  if (!k_stats || !k_eval) return bad_arg(h, 5, "this build carries no unequal-count evidence kernel for this D and element type (BLR_DEV_FAST)");
+  int rc;
+  GridRaggedPlan plan;
+  plan_grid_ragged(offsets, B, plan);
+  const size_t SZ = (size_t)ragged_evidence_stat_elems(T(0), NB), lds = ragged_evidence_lds(T(0), NB);
+  Carve carve;
+  const size_t nblk = (size_t)plan.slots;
+  const size_t o_st = carve(nblk * SZ * sizeof(T)), o_sc = carve(nblk * 2 * sizeof(double)), o_bad = carve(nblk * sizeof(int32_t));
+  const size_t o_pl = carve((size_t)B * sizeof(double)), o_pi = carve((size_t)B * sizeof(int32_t)), o_best = carve((size_t)B * sizeof(int64_t));
+  if ((rc = h->loo_ws.reserve(h, carve.off))) return rc;
+  char* const ws = h->loo_ws.p;
+  a.stats = reinterpret_cast<T*>(ws + o_st); a.scal = reinterpret_cast<double*>(ws + o_sc); a.bad = reinterpret_cast<int32_t*>(ws + o_bad);
+  double* const prior_logdet = reinterpret_cast<double*>(ws + o_pl);
+  int32_t* const prior_info = reinterpret_cast<int32_t*>(ws + o_pi);
+  int64_t* const best = reinterpret_cast<int64_t*>(ws + o_best);
+  a.prior_logdet = prior_logdet; a.prior_info = prior_info; a.best = best;
+  const char* dev[3];
+  if ((rc = ragged_meta_upload(h, {{offsets, ragged_table_bytes(B)}, {plan.items.data(), plan.items.size() * sizeof(GridRaggedItem)},
+                                   {plan.slot0.data(), (size_t)(B + 1) * sizeof(int32_t)}}, dev)))
+    return rc;
+  a.offsets = reinterpret_cast<const int64_t*>(dev[0]);
+  a.items = reinterpret_cast<const GridRaggedItem*>(dev[1]);
+  a.slot0 = reinterpret_cast<const int32_t*>(dev[2]);
+  if ((rc = set_lds_once(h, k_stats, lds))) return rc;
+  if ((rc = set_lds_once(h, k_eval, lds))) return rc;
+  GridArgs<T> p{};  // what grid_prior_kernel reads
+  p.Lw = a.Lw; p.ldl = a.ldl; p.strideLw = a.strideLw; p.prior_kind = a.prior_kind; p.D = a.D; p.B = a.B;
+  p.prior_logdet = prior_logdet; p.prior_info = prior_info;
+  if ((rc = grid_prior_enqueue<T>(h, NB, p))) return rc;  // (every launch is checked before the ones that read its output are enqueued)
+  ragged_evidence_stats_launch(NB, mode, (unsigned)plan.slots, h->stream, a);
+  HIP_TRY(h, hipGetLastError());
+  if (plan.reduce) {
+    ragged_evidence_reduce_launch(NB, (unsigned)B, h->stream, a);
+    HIP_TRY(h, hipGetLastError());
+  }
+  a.refit = 0;
+  ragged_evidence_eval_launch(NB, (unsigned)(B * a.G), h->stream, a);
+  HIP_TRY(h, hipGetLastError());
+  hipLaunchKernelGGL(grid_argmax_kernel, dim3((unsigned)((B + kThreads - 1) / kThreads)), dim3(kThreads), 0, h->stream,
+                     (const double*)a.logpdf, a.stride_lp, a.G, a.B, best, best_out);
+  HIP_TRY(h, hipGetLastError());
+  if (a.mw_best || a.T_best) {
+    a.refit = 1;
+    ragged_evidence_eval_launch(NB, (unsigned)B, h->stream, a);
+    HIP_TRY(h, hipGetLastError());
+  }
+  h->route_buf = std::string("ragged_evidence_stats_kernel<") + (sizeof(T) == 8 ? "double" : "float") + ", " + std::to_string(NB) + ", " + std::to_string(mode) + ">";
+  h->route = h->route_buf.c_str();
+  h->route_i8_B = 0;
+  return 0;
+}
+
+template <typename T>
+int logpdf_grid_ragged(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, const int64_t* offsets, const T* X, int64_t ldx,
+                       const T* y, int noise_kind, const T* s, int64_t strides, int prior_kind, const T* mw, int64_t stridemw, const T* Lw,
+                       int64_t ldl, int64_t strideLw, int64_t G, const T* alpha, int64_t stride_alpha, const T* tau, int64_t stride_tau,
+                       double* logpdf, int64_t stride_lp, int64_t* best, T* mw_best, int64_t stride_mwbest, T* T_best, int64_t ldt,
+                       int64_t strideT, int32_t* info, int64_t stride_info) {
+  RaggedFront f;
+  if (const int rc = ragged_front(h, f, memspace, layout, B, D, offsets, X, ldx, noise_kind, strides)) return rc;
+  const bool any = f.any, diag = f.diag;
+  if (any && !y) return bad_arg(h, 9, "y is NULL (reference :74 length check)");
+  if (noise_kind != BLR_NOISE_ISOTROPIC && noise_kind != BLR_NOISE_DIAGONAL)
+    return bad_arg(h, 10, "noise_kind (the grid scales an isotropic or diagonal base noise; dense Sigma_y is not supported)");
+  if (!s && (noise_kind == BLR_NOISE_ISOTROPIC || any)) return bad_arg(h, 11, "s is NULL");
+  if (strides < 0) return bad_arg(h, 12, "strides < 0");
+  if (prior_kind != BLR_PRIOR_DENSE && prior_kind != BLR_PRIOR_DIAGONAL)
+    return bad_arg(h, 13, "prior_kind (dense or diagonal precision; pass a carried-forward factor as U'U)");
+  if (!mw) return bad_arg(h, 14, "mw is NULL");
+  if (stridemw < 0) return bad_arg(h, 15, "stridemw < 0");
+  if (!Lw) return bad_arg(h, 16, "Lw is NULL");
+  if (prior_kind == BLR_PRIOR_DENSE && ldl < D) return bad_arg(h, 17, "ldl < D");
+  if (strideLw < 0) return bad_arg(h, 18, "strideLw < 0");
+  if (G < 0 || G > (1 << 20)) return bad_arg(h, 19, "G out of range (0..2^20)");
+  if (alpha && stride_alpha != 0 && stride_alpha < G) return bad_arg(h, 21, "stride_alpha (0 = one grid for every regressor, else >= G)");
+  if (tau && stride_tau != 0 && stride_tau < G) return bad_arg(h, 23, "stride_tau (0 = one grid for every regressor, else >= G)");
+  if (G > 0 && !logpdf) return bad_arg(h, 24, "logpdf is NULL");
+  if (stride_lp < G) return bad_arg(h, 25, "stride_lp < G");
+  if (mw_best && B > 1 && stride_mwbest < D) return bad_arg(h, 28, "stride_mwbest < D");
+  if (T_best && ldt < D) return bad_arg(h, 30, "ldt < D");
+  if (T_best && B > 1 && strideT < (int64_t)mat_extent(D, D, ldt)) return bad_arg(h, 31, "strideT too small");
+  if (G > 0 && !info) return bad_arg(h, 32, "info is NULL");
+  if (stride_info < G) return bad_arg(h, 33, "stride_info < G");
+  // one workgroup of 256 threads per (regressor, setting) / (regressor, column block): a launch takes fewer than 2^32 threads
+  if (B * std::max<int64_t>(G, 1) >= ((int64_t)1 << 24)) return bad_arg(h, 19, "B * G too large (< 2^24)");
+  if (D <= kMaxSmallD && grid_ragged_slots(offsets, B) >= ((int64_t)1 << 24)) return bad_arg(h, 19, "too many column blocks (sum of S_b < 2^24)");
+  if (!h) return -1;
+  h->last_chunks = 1;  // (no chunk loop; the D > 128 route's nested calls set their own)
+  if (B == 0 || G == 0) return 0;
+  HIP_TRY(h, hipSetDevice(h->device));
+  RaggedEvidenceArgs<T> a{};
+  a.ldx = ldx; a.strides = diag ? 0 : strides; a.stridemw = stridemw; a.ldl = ldl; a.strideLw = strideLw;
+  a.stride_alpha = stride_alpha; a.stride_tau = stride_tau; a.stride_lp = stride_lp; a.stride_info = stride_info;
+  a.stride_mwbest = stride_mwbest; a.ldt = ldt; a.strideT = strideT;
+  a.layout = layout; a.noise_kind = noise_kind; a.prior_kind = prior_kind;
+  a.D = (int)D; a.B = (int)B; a.G = (int)G;
+  CallIO io(h, memspace);
+  const size_t lw_one = prior_kind == BLR_PRIOR_DIAGONAL ? (size_t)D : mat_extent(D, D, ldl);
+  int64_t* best_out = nullptr;
+  int rc;
+  if ((rc = io.in(X, f.x_all, &a.X))) return rc;
+  if ((rc = io.in(y, f.n_all, &a.y))) return rc;
+  if ((rc = io.in(s, f.s_all, &a.s))) return rc;
+  if ((rc = io.in(mw, extent(B, stridemw, (size_t)D), &a.mw))) return rc;
+  if ((rc = io.in(Lw, extent(B, strideLw, lw_one), &a.Lw))) return rc;
+  if ((rc = io.in(alpha, extent(B, stride_alpha, (size_t)G), &a.alpha))) return rc;
+  if ((rc = io.in(tau, extent(B, stride_tau, (size_t)G), &a.tau))) return rc;
+  if ((rc = io.out(logpdf, extent(B, stride_lp, (size_t)G), &a.logpdf))) return rc;
+  if ((rc = io.out(info, extent(B, stride_info, (size_t)G), &a.info))) return rc;
+  if ((rc = io.out(best, (size_t)B, &best_out))) return rc;
+  if ((rc = io.out(mw_best, extent(B, stride_mwbest, (size_t)D), &a.mw_best))) return rc;
+  if ((rc = io.out(T_best, extent(B, strideT, mat_extent(D, D, ldt)), &a.T_best))) return rc;
+  // no data at all (or, host memspace, nothing staged): the kernels never dereference these, but keep the pointers valid
+  if (!a.X) a.X = a.mw;
+  if (!a.y) a.y = a.mw;
+  if (!a.s) a.s = a.mw;
+  if (D <= kMaxSmallD) {
+    if ((rc = grid_ragged_small<T>(h, a, offsets, best_out))) return rc;
+    return io.finish();
+  }
+  // D > 128: correct, not fast -- blr_logpdf_grid_* with B = 1 on each slice
+  if ((rc = ragged_one_by_one(h, B, offsets, [&](int64_t b, int64_t o, int64_t n) {
+         return logpdf_grid<T>(h, BLR_MEM_DEVICE, layout, 1, D, n, a.X + (f.colv ? o * ldx : o), ldx, 0, a.y + o, 0, noise_kind,
+                               diag ? a.s + o : a.s + b * strides, 0, prior_kind, a.mw + b * stridemw, 0, a.Lw + b * strideLw, ldl, 0, G,
+                               a.alpha ? a.alpha + b * stride_alpha : (const T*)nullptr, 0, a.tau ? a.tau + b * stride_tau : (const T*)nullptr, 0,
+                               a.logpdf + b * stride_lp, stride_lp, best_out ? best_out + b : (int64_t*)nullptr,
+                               a.mw_best ? a.mw_best + b * stride_mwbest : (T*)nullptr, stride_mwbest, a.T_best ? a.T_best + b * strideT : (T*)nullptr,
+                               ldt, strideT, a.info + b * stride_info, stride_info);
        })))
     return rc;
   return io.finish();
@@ -5632,6 +5805,17 @@ int blr_timer_stop(blr_handle* h, float* elapsed_ms) {
     return logpdf_grid<T>(h, memspace, layout, B, D, N, X, ldx, strideX, y, stridey, noise_kind, s, strides,        \
                           prior_kind, mw, stridemw, Lw, ldl, strideLw, G, alpha, stride_alpha, tau, stride_tau,     \
                           logpdf, stride_lp, best, mw_best, stride_mwbest, T_best, ldt, strideT, info, stride_info);\
+  }                                                                                                                 \
+  int blr_logpdf_grid_ragged_##SUF(blr_handle* h, int memspace, int layout, int64_t B, int64_t D,                   \
+                                   const int64_t* offsets, const T* X, int64_t ldx, const T* y, int noise_kind,     \
+                                   const T* s, int64_t strides, int prior_kind, const T* mw, int64_t stridemw,      \
+                                   const T* Lw, int64_t ldl, int64_t strideLw, int64_t G, const T* alpha,           \
+                                   int64_t stride_alpha, const T* tau, int64_t stride_tau, double* logpdf,          \
+                                   int64_t stride_lp, int64_t* best, T* mw_best, int64_t stride_mwbest, T* T_best,  \
+                                   int64_t ldt, int64_t strideT, int32_t* info, int64_t stride_info) {              \
+    return logpdf_grid_ragged<T>(h, memspace, layout, B, D, offsets, X, ldx, y, noise_kind, s, strides, prior_kind, \
+                                 mw, stridemw, Lw, ldl, strideLw, G, alpha, stride_alpha, tau, stride_tau, logpdf,  \
+                                 stride_lp, best, mw_best, stride_mwbest, T_best, ldt, strideT, info, stride_info); \
   }                                                                                                                 \
   int blr_posterior_ragged_##SUF(blr_handle* h, int memspace, int layout, int64_t B, int64_t D,                     \
                                  const int64_t* offsets, const T* X, int64_t ldx, const T* y, int noise_kind,       \

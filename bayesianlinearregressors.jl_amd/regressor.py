@@ -28,7 +28,7 @@ __all__ = [
     "mean", "var", "cov", "std", "mean_and_var", "mean_and_cov", "marginals", "rand", "rand_b", "logpdf", "posterior",
     "LOO", "loo", "loo_map", "loo_columns", "loo_columns_map",
     "KFold", "kfold", "kfold_map", "kfold_large", "kfold_large_map", "cross_validate", "kfold_columns", "kfold_columns_map",
-    "EvidenceGrid", "logpdf_grid", "posterior_best", "logpdf_grid_map",
+    "EvidenceGrid", "logpdf_grid", "posterior_best", "logpdf_grid_map", "logpdf_grid_ragged", "posterior_best_ragged",
     "posterior_ragged", "logpdf_ragged", "mean_ragged", "var_ragged", "mean_and_var_ragged", "loo_ragged", "kfold_ragged",
     "kfold_large_ragged", "cross_validate_ragged",
     "posterior_columns", "logpdf_columns_map", "posterior_columns_map",
@@ -1509,9 +1509,82 @@ def posterior_best(fx, y, prior_scales=None, noise_scales=None):
     return post, grid
 
 
+def _grid_ragged_call(dtype, layout, nb, D, offsets, X, ldx, y, noise_kind, s, strides, prior_kind, mwb, stridemw, Lb, ldl, strideLw,
+                      a, t, want_posterior):
+    """blr_logpdf_grid_ragged_* on packed operands: the outer product of the scales flattened to G settings, prior scale slowest,
+    one grid shared by all regressors.  -> [(EvidenceGrid, mw_best, T_best)]; ``want_posterior``: the first regressor without a
+    winner raises PosDefException with its position as ``index``, as _grid_batch does."""
+    G = a.size * t.size
+    alpha = np.ascontiguousarray(np.repeat(a, t.size))
+    tau = np.ascontiguousarray(np.tile(t, a.size))
+    lp = np.full((nb, G), np.nan, dtype=np.float64)
+    info = np.zeros((nb, G), dtype=np.int32)
+    best = np.full(nb, -1, dtype=np.int64)
+    mw_best = np.empty((nb, D), dtype=dtype) if want_posterior else None
+    T_best = np.empty((nb, D * D), dtype=dtype) if want_posterior else None
+    _handle().logpdf_grid_ragged(dtype, _abi.MEM_HOST, layout, nb, D, offsets, X, ldx, y, noise_kind, s, strides, prior_kind, mwb,
+                                 stridemw, Lb, ldl, strideLw, G, alpha, 0, tau, 0, lp, G, best, mw_best, D, T_best, max(D, 1), D * D,
+                                 info, G)
+    out = []
+    for b in range(nb):
+        k = int(best[b])
+        grid = EvidenceGrid(lp[b].reshape(a.size, t.size), divmod(k, t.size) if k >= 0 else None, a, t)
+        if want_posterior and k < 0:
+            e = _abi.PosDefException(int(info[b][0]))  # no setting is positive definite: the first setting's status, as a loop would raise
+            e.index = b
+            raise e
+        out.append((grid, mw_best[b] if want_posterior else None,
+                    T_best[b].reshape((D, D), order="F") if want_posterior else None))
+    return out
+
+
+def _grid_ragged(f, x, offsets, Sy, y, prior_scales, noise_scales, want_posterior):
+    """The packed form behind logpdf_grid_ragged / posterior_best_ragged -> ([(EvidenceGrid, mw_best, T_best)], the B priors).  A
+    PDMat prior goes in as U'U formed on the host, as _grid_problem passes it: the entry scales a precision, not a factor."""
+    def as_precision(g):
+        if isinstance(g, BayesianLinearRegressor) and isinstance(g.Lw, PDMat):
+            U = np.triu(np.asarray(g.Lw.U, dtype=np.float64))
+            return BayesianLinearRegressor(g.mw, U.T @ U)
+        return g
+
+    if y is None:
+        raise ValueError("y must be a vector")
+    shared = isinstance(f, BayesianLinearRegressor)
+    fs_in = f if shared else list(f)
+    ops, fs = _ragged_operands(as_precision(fs_in) if shared else [as_precision(g) for g in fs_in], x, offsets, Sy, y)
+    fs = [fs_in] * len(fs) if shared else fs_in
+    if ops is None:
+        return [], fs
+    dtype, offsets, nb, X, layout, ldx, D, y, s, noise_kind, strides, prior_kind, ldl, _, mwb, stridemw, Lb, strideLw = ops
+    a, t = _grid_scales(prior_scales, noise_scales, dtype)
+    return _grid_ragged_call(dtype, layout, nb, D, offsets, X, ldx, y, noise_kind, s, strides, prior_kind, mwb, stridemw, Lb, ldl,
+                             strideLw, a, t, want_posterior), fs
+
+
+def logpdf_grid_ragged(f, x, offsets, Sy, y, prior_scales=None, noise_scales=None):
+    """[logpdf_grid(f_b(x[offsets[b]:offsets[b+1]], Sy_b), y[...], prior_scales, noise_scales)] from packed arrays in ONE library
+    call (include/blr_mi355x.h blr_logpdf_grid_ragged_*; reference :55-58 per setting under a map over fxs of different lengths):
+    a list of EvidenceGrid.  ``f``, ``x``, ``offsets``, ``Sy``, ``y`` as logpdf_ragged takes them (no dense noise)."""
+    return [r[0] for r in _grid_ragged(f, x, offsets, Sy, y, prior_scales, noise_scales, False)[0]]
+
+
+def posterior_best_ragged(f, x, offsets, Sy, y, prior_scales=None, noise_scales=None):
+    """([posterior at the evidence-maximising setting], [EvidenceGrid]) per packed regressor, in the same library call; the
+    posteriors are wrapped as `posterior_best` wraps them.  The first regressor none of whose settings succeeded raises
+    PosDefException with its position as ``index``."""
+    res, fs = _grid_ragged(f, x, offsets, Sy, y, prior_scales, noise_scales, True)
+    posts = []
+    for g, (_, mw_best, T) in zip(fs, res):
+        Tu = np.triu(T)
+        posts.append(BayesianLinearRegressor(mw_best, _wrap_like(g.Lw, Tu, None if isinstance(g.Lw, PDMat) else Tu.T @ Tu)))
+    return posts, [r[0] for r in res]
+
+
 def logpdf_grid_map(fxs, ys, prior_scales=None, noise_scales=None):
     """[logpdf_grid(fx, y, prior_scales, noise_scales) for fx, y in zip(fxs, ys)] in one library call for equally shaped
-    problems (the B axis of blr_logpdf_grid_*); one call per problem when shapes, layouts or kinds differ."""
+    problems (the B axis of blr_logpdf_grid_*), and in one call of blr_logpdf_grid_ragged_* for problems that differ only in
+    their observation counts (a problem without observations goes with any layout); one call per problem when layouts, D or
+    kinds differ."""
     fxs, ys = list(fxs), list(ys)
     if len(fxs) != len(ys):
         raise ValueError("as many observation vectors as finite regressors are needed")
@@ -1522,7 +1595,27 @@ def logpdf_grid_map(fxs, ys, prior_scales=None, noise_scales=None):
     probs = [_grid_problem(fx, y, dtype) for fx, y in zip(fxs, ys)]
     sig = {(q[0].shape, q[0].flags.f_contiguous, q[1], q[3], q[4], q[7], q[10]) for q in probs}
     if len(sig) != 1:
-        return [_grid_batch([q], a, t, dtype, False)[0][0] for q in probs]
+        # Problems that differ only in N go side by side into ONE call of blr_logpdf_grid_ragged_*.  An empty problem has no element
+        # whose order could matter -- its (0, D) or (D, 0) array is C- and F-contiguous at once, so _x_layout's answer for it is
+        # arbitrary -- and takes the layout of the others.  (The contiguity flag of `sig` is not part of this key: with the layout
+        # flag it only says which way the container was written, and the flat reshape(order="A") below reads either way.)
+        full = [q for q in probs if q[4] > 0] or probs
+        _, layout, _, D, _, _, _, noise_kind, _, _, prior_kind, ldl = full[0]
+        if len({(q[1], q[3], q[7], q[10]) for q in full}) != 1 or len({(q[3], q[7], q[10]) for q in probs}) != 1:
+            return [_grid_batch([q], a, t, dtype, False)[0][0] for q in probs]
+        # the observations side by side, as _fused_many packs them for blr_posterior_ragged_*
+        offsets = np.concatenate(([0], np.cumsum([q[4] for q in probs]))).astype(np.int64)
+        if layout == _abi.LAYOUT_COLVECS:
+            Xp, ldxp = np.concatenate([q[0].reshape(-1, order="A") for q in probs]), D
+        else:
+            Xp = np.asfortranarray(np.concatenate([q[0].reshape(-1, order="A").reshape((q[4], D), order="F") for q in probs]))
+            ldxp = max(int(offsets[-1]), 1)
+        yp = np.concatenate([q[5] for q in probs])
+        sp = np.concatenate([q[6] for q in probs])  # isotropic: one variance per problem (strides = 1); diagonal: packed like y
+        mwb = np.stack([q[8] for q in probs])
+        Lb = np.stack([q[9].reshape(-1, order="A") for q in probs])
+        return [r[0] for r in _grid_ragged_call(dtype, layout, len(probs), D, offsets, Xp, ldxp, yp, noise_kind, sp, 1, prior_kind, mwb, D,
+                                                Lb, ldl, Lb.shape[1], a, t, False)]
     return [r[0] for r in _grid_batch(probs, a, t, dtype, False)]
 
 

@@ -1379,6 +1379,49 @@ int blr_logpdf_grid_f32(blr_handle* h, int memspace, int layout, int64_t B, int6
                         double* logpdf, int64_t stride_lp, int64_t* best, float* mw_best, int64_t stride_mwbest,
                         float* T_best, int64_t ldt, int64_t strideT, int32_t* info, int64_t stride_info);
 
+/* ---- the evidence grid for regressors with UNEQUAL observation counts ----------------------------------------------------
+ * Replaces: a loop of B calls of blr_logpdf_grid_* with B = 1 (six launches and a staging round trip each), or G calls of
+ * blr_posterior_ragged_* on scaled operands (the D x D Gram matrices formed G times); reference
+ * src/bayesian_linear_regression.jl:55-58 (logpdf) on BayesianLinearRegressor(mw, alpha L0)(x, tau S0), per setting, under a map
+ * over fxs of different lengths.
+ * Packing exactly as in blr_posterior_ragged_*: `offsets` is a HOST array of B + 1 entries in both memspaces (non-decreasing,
+ * offsets[0] >= 0, every count <= 2^30; a violation is argument error -6); regressor b owns N_b = offsets[b+1] - offsets[b]
+ * observations.  ColVecs slices start at X + offsets[b]*ldx, RowVecs slices at X + offsets[b] with ldx >= offsets[B]; y at
+ * y + offsets[b]; diagonal base noise at s + offsets[b], isotropic base noise at s + b*strides (strides = 0: one shared variance);
+ * dense noise is an argument error.  N_b = 0 is allowed: the statistics are zero and the evidence is what blr_logpdf_grid_*
+ * returns at N = 0.
+ * The prior (DENSE or DIAGONAL; BLR_PRIOR_UPPER_FACTOR is an argument error: pass a carried-forward factor as U'U), the settings
+ * (alpha, tau and their strides; NULL: all ones), logpdf[b][g], info[b][g] with its rules and their order, best[b] and the refit
+ * outputs mw_best / T_best mean what they mean for blr_logpdf_grid_* and are checked in its order; under diagonal noise a base
+ * noise entry s_i <= 0 reports i, 1-based within the regressor's OWN slice.  The argument checks come before the handle's; B = 0 or
+ * G = 0 is a no-op.  Limits: B G < 2^24 and sum_b S_b < 2^24 (S_b: the column blocks of regressor b, at most 8), argument error on
+ * G (-19) beyond either, checked before anything runs.
+ * Bit promise: every output of regressor b -- logpdf[b][.], info[b][.], best[b], mw_best and T_best of b -- has the bits of
+ * blr_logpdf_grid_* with B = 1 on its slice under the same handle options.  The bits are therefore independent of B, of the other
+ * regressors, of any permutation of the batch, and of G and a setting's position; host and device memspace give the same bits; no
+ * float atomics are used.
+ * Kernels (csrc/blr_grid_ragged.hpp).  D <= 128: the launches of blr_logpdf_grid_*, with the statistics pass over a
+ * flat list of (regressor, column block) items -- the blocks blr_logpdf_grid_* cuts at N = N_b -- sorted longest block first: one
+ * regressor of 2^20 observations among short ones streams on eight workgroups at once.  The statistics buffer takes sum_b S_b blocks
+ * (counted by workspace_bytes, freed by blr_release_workspace); there is no chunk loop (last_chunks = 1); blr_last_route names the
+ * statistics kernel.  The host tables travel in one upload, which drains the stream.
+ * D > 128: correct, not fast -- blr_logpdf_grid_* with B = 1 on each slice, one after the other; the call synchronises.
+ * _f32: X, y, s, mw, Lw, alpha, tau, mw_best, T_best are float; logpdf stays double. */
+int blr_logpdf_grid_ragged_f64(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, const int64_t* offsets,
+                               const double* X, int64_t ldx, const double* y, int noise_kind, const double* s, int64_t strides,
+                               int prior_kind, const double* mw, int64_t stridemw, const double* Lw, int64_t ldl,
+                               int64_t strideLw, int64_t G, const double* alpha, int64_t stride_alpha, const double* tau,
+                               int64_t stride_tau, double* logpdf, int64_t stride_lp, int64_t* best, double* mw_best,
+                               int64_t stride_mwbest, double* T_best, int64_t ldt, int64_t strideT, int32_t* info,
+                               int64_t stride_info);
+int blr_logpdf_grid_ragged_f32(blr_handle* h, int memspace, int layout, int64_t B, int64_t D, const int64_t* offsets,
+                               const float* X, int64_t ldx, const float* y, int noise_kind, const float* s, int64_t strides,
+                               int prior_kind, const float* mw, int64_t stridemw, const float* Lw, int64_t ldl,
+                               int64_t strideLw, int64_t G, const float* alpha, int64_t stride_alpha, const float* tau,
+                               int64_t stride_tau, double* logpdf, int64_t stride_lp, int64_t* best, float* mw_best,
+                               int64_t stride_mwbest, float* T_best, int64_t ldt, int64_t strideT, int32_t* info,
+                               int64_t stride_info);
+
 /* ---- sharded log-evidence: fixed-order sum of logpdf[B] on the device ----------
  * Deterministic (no float atomics): the same bits for the same B regardless of launch geometry.
  * The cross-rank step is one RCCL all-gather of these per-rank partials done by the host framework

@@ -1668,6 +1668,49 @@ function logpdf_grid!(lp::DeviceArray{Float64}, best::Union{Nothing,DeviceArray{
 end
 
 """
+    logpdf_grid_ragged!(lp, best, mw_best, T_best, info, X, offsets, y, s, mw, Lw, alpha, tau; D, G, isotropic, diagonal_prior)
+
+`logpdf_grid!` for B = length(offsets) - 1 data sets with UNEQUAL observation counts in one call (`blr_logpdf_grid_ragged_*`;
+reference `src/bayesian_linear_regression.jl:55-58` per setting under a map over fxs of different lengths), everything device
+resident except `offsets` (a host `Vector{Int64}`, zero based, B + 1 non-decreasing entries): data set b owns the columns
+offsets[b]+1:offsets[b+1] of X (D×offsets[end], ColVecs) and the same entries of y; s holds B variances (`isotropic`) or
+offsets[end]; mw is D×B, Lw D×B (`diagonal_prior`) or D×D×B; one grid alpha, tau (length G) shared by all; outputs as
+`logpdf_grid!`.  Every output of data set b has the bits of `logpdf_grid!` with B = 1 on its slice.
+"""
+function logpdf_grid_ragged!(lp::DeviceArray{Float64}, best::Union{Nothing,DeviceArray{Int64}}, mw_best::Union{Nothing,DeviceArray{T}},
+                             T_best::Union{Nothing,DeviceArray{T}}, info::DeviceArray{Int32}, X::DeviceArray{T}, offsets::Vector{Int64},
+                             y::DeviceArray{T}, s::DeviceArray{T}, mw::DeviceArray{T}, Lw::DeviceArray{T}, alpha::DeviceArray{T},
+                             tau::DeviceArray{T}; D::Int, G::Int, isotropic::Bool, diagonal_prior::Bool) where {T<:Elt}
+    h = handle()
+    B = length(offsets) - 1
+    nk = isotropic ? ISOTROPIC : DIAGONALN
+    pk = diagonal_prior ? P_DIAG : P_DENSE
+    ptr(a) = a === nothing ? Ptr{T}(C_NULL) : a.ptr
+    iptr(a) = a === nothing ? Ptr{Int64}(C_NULL) : a.ptr
+    rc = GC.@preserve offsets begin
+        if T === Float64
+            ccall((:blr_logpdf_grid_ragged_f64, LIB), Cint,
+                  (Ptr{Cvoid}, Cint, Cint, Int64, Int64, Ptr{Int64}, Ptr{T}, Int64, Ptr{T}, Cint, Ptr{T}, Int64, Cint, Ptr{T}, Int64,
+                   Ptr{T}, Int64, Int64, Int64, Ptr{T}, Int64, Ptr{T}, Int64, Ptr{Cdouble}, Int64, Ptr{Int64}, Ptr{T}, Int64, Ptr{T}, Int64,
+                   Int64, Ptr{Int32}, Int64),
+                  h, MEM_DEVICE, COLVECS, B, D, offsets, X.ptr, D, y.ptr, nk, s.ptr, isotropic ? 1 : 0, pk, mw.ptr, D, Lw.ptr, D,
+                  diagonal_prior ? D : D * D, G, alpha.ptr, 0, tau.ptr, 0, lp.ptr, G, iptr(best), ptr(mw_best), D, ptr(T_best), D, D * D,
+                  info.ptr, G)
+        else
+            ccall((:blr_logpdf_grid_ragged_f32, LIB), Cint,
+                  (Ptr{Cvoid}, Cint, Cint, Int64, Int64, Ptr{Int64}, Ptr{T}, Int64, Ptr{T}, Cint, Ptr{T}, Int64, Cint, Ptr{T}, Int64,
+                   Ptr{T}, Int64, Int64, Int64, Ptr{T}, Int64, Ptr{T}, Int64, Ptr{Cdouble}, Int64, Ptr{Int64}, Ptr{T}, Int64, Ptr{T}, Int64,
+                   Int64, Ptr{Int32}, Int64),
+                  h, MEM_DEVICE, COLVECS, B, D, offsets, X.ptr, D, y.ptr, nk, s.ptr, isotropic ? 1 : 0, pk, mw.ptr, D, Lw.ptr, D,
+                  diagonal_prior ? D : D * D, G, alpha.ptr, 0, tau.ptr, 0, lp.ptr, G, iptr(best), ptr(mw_best), D, ptr(T_best), D, D * D,
+                  info.ptr, G)
+        end
+    end
+    check(h, rc)
+    return nothing
+end
+
+"""
     logpdf_grid(fx, y, prior_scales, noise_scales) -> (logpdf, best, mw_best, T_best)
 
 Evidence of (fx, y) under every (prior scale, noise scale) pair -- logpdf[j, i] for noise_scales[j], prior_scales[i] -- the
