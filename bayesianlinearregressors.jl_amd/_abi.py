@@ -27,6 +27,7 @@ MARG_COLS_PER_PASS = 16  # csrc/blr_marg_multi.hpp kMargColsPerPass: mean column
 LOO_COLS_PER_PASS = 16  # csrc/blr_loo_multi.hpp kLooColsPerPass (= kMargColsPerPass): columns of one pass of loo_cols_kernel
 STATE_COLS_PER_PASS = 16  # csrc/blr_state_cols.hpp kStateColsPerPass: columns of one pass of state_cols_kernel (column 0 is not among them)
 
+X_BF16, X_F16 = 0, 1  # BLR_X_*: element format of blr_posterior_batched_x16's X
 _i64, _int, _vp = C.c_int64, C.c_int, C.c_void_p
 _H = C.c_void_p
 
@@ -80,6 +81,10 @@ _SIGS = {
     "blr_kfold_large_ragged_fold_sizes": ([_i64, _vp, _i64, _vp], _int),
     "blr_kfold_large_ragged_fold_offsets": ([_i64, _vp, _vp, _vp], _int),
 }
+# 16-bit features (xfmt after layout; X void*, everything else float32): csrc/blr_fused_x16.hpp
+_SIGS["blr_posterior_batched_x16"] = (
+    [_H, _int, _int, _int, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _int, _vp, _i64, _int, _vp, _i64, _vp, _i64, _i64,
+     _vp, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp], _int)
 for _suf in ("f64", "f32"):
     _SIGS[f"blr_posterior_batched_{_suf}"] = (
         [_H, _int, _int, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _int, _vp, _i64, _int, _vp, _i64, _vp, _i64, _i64,
@@ -344,6 +349,16 @@ class Handle:
                              _ptr(s), strides, prior_kind, _ptr(mw), stridemw, _ptr(Lw), ldl, strideLw,
                              _ptr(mw_post), stride_mwpost, _ptr(T_post), ldt, strideT, _ptr(Lw_post), ldlp, strideLp,
                              _ptr(logpdf), _ptr(info)))
+
+    def posterior_batched_x16(self, xfmt, memspace, layout, B, D, N, X, ldx, strideX, y, stridey, noise_kind, s, strides,
+                              prior_kind, mw, stridemw, Lw, ldl, strideLw, mw_post, stride_mwpost, T_post, ldt, strideT,
+                              Lw_post, ldlp, strideLp, logpdf, info):
+        """posterior_batched on 16-bit features: xfmt X_BF16 / X_F16, X of 2-byte elements (ldx, strideX in elements), every other
+        array float32; D <= 128, isotropic noise (include/blr_mi355x.h blr_posterior_batched_x16)."""
+        return self.check(self.lib.blr_posterior_batched_x16(
+            self._h, memspace, layout, xfmt, B, D, N, _ptr(X), ldx, strideX, _ptr(y), stridey, noise_kind, _ptr(s), strides, prior_kind,
+            _ptr(mw), stridemw, _ptr(Lw), ldl, strideLw, _ptr(mw_post), stride_mwpost, _ptr(T_post), ldt, strideT, _ptr(Lw_post), ldlp,
+            strideLp, _ptr(logpdf), _ptr(info)))
 
     def posterior_ragged(self, dtype, memspace, layout, B, D, offsets, X, ldx, y, noise_kind, s, strides, prior_kind, mw, stridemw,
                          Lw, ldl, strideLw, mw_post, stride_mwpost, T_post, ldt, strideT, Lw_post, ldlp, strideLp, logpdf, info):

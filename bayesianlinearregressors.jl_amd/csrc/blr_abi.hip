@@ -46,6 +46,8 @@
 #include "blr_kfold_large_ragged.hpp"
 #include "blr_revise_ragged.hpp"
 #include "blr_grid_ragged.hpp"
+#define BLR_X16_DECLS_ONLY
+#include "blr_fused_x16.hpp"
 #include "blr_host.hpp"
 #include "blr_large_plan.hpp"
 
@@ -6043,6 +6045,81 @@ int blr_timer_stop(blr_handle* h, float* elapsed_ms) {
 
 BLR_DEFINE(f64, double)
 BLR_DEFINE(f32, float)
+
+// 16-bit features (bf16 / fp16), D <= 128, isotropic noise: fused_x16_kernel (blr_fused_x16.hpp).  Everything but X is fp32 with the
+// meaning it has in blr_posterior_batched_f32; argument positions are this entry point's own (xfmt is argument 4).
+int blr_posterior_batched_x16(blr_handle* h, int memspace, int layout, int xfmt, int64_t B, int64_t D, int64_t N, const void* X,
+                              int64_t ldx, int64_t strideX, const float* y, int64_t stridey, int noise_kind, const float* s,
+                              int64_t strides, int prior_kind, const float* mw, int64_t stridemw, const float* Lw, int64_t ldl,
+                              int64_t strideLw, float* mw_post, int64_t stride_mwpost, float* T_post, int64_t ldt, int64_t strideT,
+                              float* Lw_post, int64_t ldlp, int64_t strideLp, double* logpdf, int32_t* info) {
+  int rc = posterior_check<float>(h, memspace, layout, B, D, N, static_cast<const float*>(X), ldx, strideX, y, stridey, noise_kind, s, strides,
+                                  prior_kind, mw, stridemw, Lw, ldl, strideLw, mw_post, stride_mwpost, T_post, ldt, strideT, Lw_post, ldlp,
+                                  strideLp, logpdf, info);
+  if (rc < -3) {  // positions behind `layout` are one further here: re-number, keep the reason
+    const size_t colon = h->err.find(": ");
+    const std::string why = colon == std::string::npos ? h->err : h->err.substr(colon + 2);
+    return bad_arg(h, -rc + 1, why.c_str());
+  }
+  if (rc < 0) return rc;
+  if (xfmt != BLR_X_BF16 && xfmt != BLR_X_F16) return bad_arg(h, 4, "unknown xfmt (BLR_X_BF16 or BLR_X_F16)");
+  if (D > kMaxSmallD) return bad_arg(h, 6, "D > 128 is not served on 16-bit features (widen them and call blr_posterior_batched_f32)");
+  if (noise_kind != BLR_NOISE_ISOTROPIC)
+    return bad_arg(h, 13, "only isotropic noise is served on 16-bit features (widen them and call blr_posterior_batched_f32)");
+  if (rc) return 0;  // B == 0
+  HIP_TRY(h, hipSetDevice(h->device));
+  X16Args a{};
+  PosteriorArgs<float>& p = a.p;
+  p.ldx = ldx; p.strideX = 0; p.stridey = stridey; p.strides = strides; p.stridemw = stridemw;
+  p.ldl = ldl; p.strideLw = strideLw; p.stride_mwpost = stride_mwpost; p.ldt = ldt; p.strideT = strideT;
+  p.ldlp = ldlp; p.strideLp = strideLp;
+  p.layout = layout; p.noise_kind = noise_kind; p.prior_kind = prior_kind;
+  p.D = (int)D; p.N = (int)N; p.B = (int)B;
+  a.strideX = strideX;
+
+  CallIO io(h, memspace);
+  const size_t x_one = layout == BLR_LAYOUT_COLVECS ? mat_extent(D, N, ldx) : mat_extent(N, D, ldx);
+  const size_t lw_one = prior_kind == BLR_PRIOR_DIAGONAL ? (size_t)D : mat_extent(D, D, ldl);
+  if ((rc = io.in(static_cast<const unsigned short*>(X), extent(B, strideX, x_one), &a.X))) return rc;
+  if ((rc = io.in(y, extent(B, stridey, (size_t)N), &p.y))) return rc;
+  if ((rc = io.in(s, extent(B, strides, 1), &p.s))) return rc;
+  if ((rc = io.in(mw, extent(B, stridemw, (size_t)D), &p.mw))) return rc;
+  if ((rc = io.in(Lw, extent(B, strideLw, lw_one), &p.Lw))) return rc;
+  if ((rc = io.out(mw_post, extent(B, stride_mwpost, (size_t)D), &p.mw_post))) return rc;
+  if ((rc = io.out(T_post, extent(B, strideT, mat_extent(D, D, ldt)), &p.T_post))) return rc;
+  if ((rc = io.out(Lw_post, extent(B, strideLp, mat_extent(D, D, ldlp)), &p.Lw_post))) return rc;
+  if ((rc = io.out(logpdf, (size_t)B, &p.logpdf))) return rc;
+  if ((rc = io.out(info, (size_t)B, &p.info))) return rc;
+  if (N == 0 && !p.y) p.y = p.mw;  // no data: the kernel never dereferences X / y, but keep the pointer valid
+
+  // loader: whole stages by LDS-DMA when every 16-byte piece of the image is 16 contiguous, aligned bytes of X
+  const bool al16 = ((uintptr_t)a.X % 16) == 0 && ldx % 8 == 0 && (B == 1 || strideX % 8 == 0);
+  const bool rowv = layout == BLR_LAYOUT_ROWVECS;
+  const bool fast = !h->opt.no_ldsdma && al16 && (rowv || D % 8 == 0);
+  const int mode = (fast ? 2 : 0) + (rowv ? 1 : 0);
+  const int NB = 2 * (int)((D + 31) / 32);  // even block counts only: the padding rows are zero in LDS
+  const void* const kern = x16_kernel_ptr(xfmt, NB, mode);
+  if (kern == nullptr) return hip_fail(h, hipErrorInvalidValue, "this build lacks the requested form of fused_x16_kernel");
+  if ((rc = set_lds_once(h, kern, x16_kernel_lds(NB)))) return rc;
+  const int64_t chunk = h->cap_chunk(std::min<int64_t>(B, 1 << 20));  // one workgroup per regressor
+  h->count_chunks(B, chunk);
+  for (int64_t b0 = 0; b0 < B; b0 += chunk) {
+    X16Args c = a;
+    c.p.B = (int)std::min<int64_t>(chunk, B - b0);
+    c.X += b0 * strideX; c.p.y += b0 * stridey; c.p.s += b0 * strides; c.p.mw += b0 * stridemw; c.p.Lw += b0 * strideLw;
+    if (c.p.mw_post) c.p.mw_post += b0 * stride_mwpost;
+    if (c.p.T_post) c.p.T_post += b0 * strideT;
+    if (c.p.Lw_post) c.p.Lw_post += b0 * strideLp;
+    if (c.p.logpdf) c.p.logpdf += b0;
+    c.p.info += b0;
+    x16_kernel_launch(xfmt, NB, mode, (unsigned)c.p.B, h->stream, c);
+    HIP_TRY(h, hipGetLastError());
+  }
+  h->route_buf = std::string("fused_x16_kernel<") + (xfmt == BLR_X_BF16 ? "bf16" : "f16") + ", " + std::to_string(NB) + ", " + std::to_string(mode) + ">";
+  h->route = h->route_buf.c_str();
+  h->route_i8_B = 0;
+  return io.finish();
+}
 
 // host arithmetic only: no handle, no device (blr_kfold_ragged_plan.hpp)
 int blr_kfold_ragged_fold_offsets(int64_t B, const int64_t* offsets, int64_t F, int64_t* fold_offsets) {

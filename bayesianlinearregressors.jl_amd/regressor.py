@@ -23,7 +23,7 @@ import numpy as np
 from . import _abi
 
 __all__ = [
-    "ColVecs", "RowVecs", "Diagonal", "Symmetric", "PDMat", "Normal", "RandomFourierFeatures",
+    "ColVecs", "RowVecs", "ColVecs16", "RowVecs16", "bf16_bits", "widen16", "Diagonal", "Symmetric", "PDMat", "Normal", "RandomFourierFeatures",
     "BayesianLinearRegressor", "BasisFunctionRegressor", "BLRFunctionSample", "FiniteGP",
     "mean", "var", "cov", "std", "mean_and_var", "mean_and_cov", "marginals", "rand", "rand_b", "logpdf", "posterior",
     "LOO", "loo", "loo_map", "loo_columns", "loo_columns_map",
@@ -154,6 +154,79 @@ def _x_layout(x, dtype):
     if colvecs:
         D, N = M.shape
         # (D, N) Fortran order  == D x N column-major == COLVECS;  C order == N x D column-major == ROWVECS
+        if M.flags.f_contiguous:
+            return M, _abi.LAYOUT_COLVECS, max(D, 1), D, N
+        return M, _abi.LAYOUT_ROWVECS, max(N, 1), D, N
+    N, D = M.shape
+    if M.flags.f_contiguous:
+        return M, _abi.LAYOUT_ROWVECS, max(N, 1), D, N
+    return M, _abi.LAYOUT_COLVECS, max(D, 1), D, N
+
+
+# ---------------------------------------------------------------------------------------------------
+# 16-bit features (bf16 / fp16): what a network's last layer hands over (reference examples/nn-blr.jl), never widened
+# ---------------------------------------------------------------------------------------------------
+def bf16_bits(a):
+    """float32 values rounded to the nearest bfloat16 (ties to even) -> their bit patterns (uint16).  NaN stays NaN."""
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    u = a.view(np.uint32)
+    r = ((u + (np.uint32(0x7FFF) + ((u >> np.uint32(16)) & np.uint32(1)))) >> np.uint32(16)).astype(np.uint16)
+    nan = np.isnan(a)
+    if nan.any():
+        r = np.where(nan, ((u >> np.uint32(16)) | np.uint32(0x0040)).astype(np.uint16), r)
+    return r
+
+
+def widen16(X, fmt):
+    """The exact float32 values of 16-bit features: ``fmt`` "f16" (np.float16 array) or "bf16" (np.uint16 bit patterns)."""
+    if fmt == "f16":
+        return np.asarray(X, dtype=np.float16).astype(np.float32)
+    if fmt == "bf16":
+        return (np.asarray(X, dtype=np.uint16).astype(np.uint32) << np.uint32(16)).view(np.float32)
+    raise ValueError(f"fmt must be 'bf16' or 'f16', got {fmt!r}")
+
+
+class _Vecs16:
+    def __init__(self, X, fmt=None):
+        X = np.asarray(X)
+        if X.ndim != 2:
+            raise ValueError(f"{type(self).__name__} expects a matrix")
+        if fmt is None:
+            fmt = "f16" if X.dtype == np.float16 else "bf16"
+        want = {"f16": np.float16, "bf16": np.uint16}.get(fmt)
+        if want is None:
+            raise ValueError(f"fmt must be 'bf16' or 'f16', got {fmt!r}")
+        if X.dtype != want:
+            raise TypeError(f"{type(self).__name__}(fmt={fmt!r}) expects a {np.dtype(want).name} array "
+                            f"(bf16 as uint16 bit patterns, see bf16_bits), got {X.dtype}")
+        self.X, self.fmt = X, fmt
+
+    def widen(self):
+        """The plain float32 container of the same inputs."""
+        return (ColVecs if isinstance(self, ColVecs16) else RowVecs)(widen16(self.X, self.fmt))
+
+
+class ColVecs16(_Vecs16):
+    """D x N matrix of 16-bit features whose columns are the inputs: np.float16 (fmt "f16") or uint16 bf16 bit patterns (fmt "bf16")."""
+
+    def __len__(self):
+        return self.X.shape[1]
+
+
+class RowVecs16(_Vecs16):
+    """N x D matrix of 16-bit features whose rows are the inputs (see ColVecs16)."""
+
+    def __len__(self):
+        return self.X.shape[0]
+
+
+def _x16_layout(x):
+    """_x_layout for ColVecs16 / RowVecs16: -> (array kept alive, layout flag, ldx, D, N), no copy for C- or F-contiguous input."""
+    M = x.X
+    if not (M.flags.c_contiguous or M.flags.f_contiguous):
+        M = np.ascontiguousarray(M)
+    if isinstance(x, ColVecs16):
+        D, N = M.shape
         if M.flags.f_contiguous:
             return M, _abi.LAYOUT_COLVECS, max(D, 1), D, N
         return M, _abi.LAYOUT_ROWVECS, max(N, 1), D, N
@@ -376,6 +449,8 @@ def _fused(fx, y, want_posterior):
     if isinstance(fx.f, BasisFunctionRegressor) and isinstance(fx.f.phi, RandomFourierFeatures):
         return _fused_rff(fx, y, want_posterior)
     fx = _to_finite_blr(fx)
+    if isinstance(fx.x, _Vecs16):
+        return _fused_x16_many([fx], [y], want_posterior)[0]
     blr = fx.f
     dtype = _dtype_of(blr.mw, y)
     X, layout, ldx, D, N = _x_layout(fx.x, dtype)
@@ -561,6 +636,8 @@ def _fused_many(fxs, ys, want_posterior):
     if any(isinstance(fx.f, BasisFunctionRegressor) and isinstance(fx.f.phi, RandomFourierFeatures) for fx in fxs):
         return one_by_one()
     fbs = [_to_finite_blr(fx) for fx in fxs]
+    if any(isinstance(fb.x, _Vecs16) for fb in fbs):
+        return _fused_x16_many(fbs, ys, want_posterior)
     dtype = np.float32 if all(_dtype_of(fb.f.mw, y) == np.float32 for fb, y in zip(fbs, ys)) else np.float64
     probs = []
     for fb, y in zip(fbs, ys):
@@ -614,6 +691,56 @@ def _fused_many(fxs, ys, want_posterior):
         sb = np.stack([q[6] for q in probs])
         _handle().posterior_batched(dtype, _abi.MEM_HOST, layout, nb, D, N, Xb, ldx, Xb.shape[1], yb, yb.shape[1], noise_kind, sb,
                                     sb.shape[1], prior_kind, mwb, D, Lb, ldl, Lb.shape[1], mw_post, D, Tb, D, D * D, Ab, D, D * D, lp, info)
+    return _unpack_many(lp, info, mw_post, Tb, Ab, D)
+
+
+def _fused_x16_many(fbs, ys, want_posterior):
+    """_fused_many for finite regressors on ColVecs16 / RowVecs16 inputs: equally shaped problems in ONE blr_posterior_batched_x16
+    call, y, mw, Lw and the noise variance as float32.  What that entry point does not serve raises ValueError naming the limit."""
+    if not all(isinstance(fb.x, _Vecs16) for fb in fbs):
+        raise ValueError("16-bit inputs (ColVecs16 / RowVecs16) cannot be mixed with ordinary ColVecs / RowVecs in one map: "
+                         "widen them (x.widen()) or convert the others")
+    dtype = np.float32
+    probs = []
+    for fb, y in zip(fbs, ys):
+        X, layout, ldx, D, N = _x16_layout(fb.x)
+        y = np.ascontiguousarray(y, dtype=dtype)
+        if y.ndim != 1:
+            raise ValueError("y must be a vector")
+        if y.shape[0] != N:
+            raise ValueError("length(y) != size(fx.x.X, 2)")  # reference :74
+        if D > 128:
+            raise ValueError(f"16-bit inputs are served for D <= 128, got D = {D}: widen them (x.widen())")
+        s, noise_kind = _noise(fb.Sy, N, dtype)
+        if noise_kind != _abi.NOISE_ISOTROPIC:
+            raise ValueError("16-bit inputs are served for isotropic noise only (a scalar variance): widen them (x.widen())")
+        Lw, prior_kind, ldl = _prior(fb.f.Lw, D, dtype)
+        probs.append((X, layout, ldx, D, N, y, s, fb.x.fmt, _mean_vector(fb.f.mw, D, dtype), Lw, prior_kind, ldl, isinstance(fb.f.Lw, PDMat)))
+    X0, layout, ldx, D, N, _, _, fmt, _, _, prior_kind, ldl, pdmat = probs[0]
+    if len({q[4] for q in probs}) != 1:
+        raise ValueError("16-bit inputs are served for equal numbers of observations per regressor (unequal N): "
+                         "widen them (x.widen()) for the ragged route")
+    if len({(q[0].shape, q[0].flags.f_contiguous, q[1], q[3], q[7], q[10], q[12]) for q in probs}) != 1:
+        raise ValueError("16-bit inputs in one map must agree in D, layout, format and prior kind")
+    if D == 0:
+        raise ValueError("16-bit inputs need D >= 1")
+    nb = len(probs)
+    mwb = np.stack([q[8] for q in probs])
+    Lb = np.stack([q[9].reshape(-1, order="A") for q in probs])
+    lp = np.zeros(nb, dtype=np.float64)
+    info = np.zeros(nb, dtype=np.int32)
+    if want_posterior:
+        mw_post = np.empty((nb, D), dtype=dtype)
+        Tb = np.empty((nb, D * D), dtype=dtype)
+        Ab = np.empty((nb, D * D), dtype=dtype) if not pdmat else None
+    else:
+        mw_post = Tb = Ab = None
+    Xb = X0.reshape(1, -1, order="A") if nb == 1 else np.stack([q[0].reshape(-1, order="A") for q in probs])
+    yb = np.stack([q[5] for q in probs])
+    sb = np.stack([q[6] for q in probs])
+    _handle().posterior_batched_x16(_abi.X_BF16 if fmt == "bf16" else _abi.X_F16, _abi.MEM_HOST, layout, nb, D, N, Xb, ldx, Xb.shape[1],
+                                    yb, yb.shape[1], _abi.NOISE_ISOTROPIC, sb, sb.shape[1], prior_kind, mwb, D, Lb, ldl, Lb.shape[1],
+                                    mw_post, D, Tb, D, D * D, Ab, D, D * D, lp, info)
     return _unpack_many(lp, info, mw_post, Tb, Ab, D)
 
 

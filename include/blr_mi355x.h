@@ -199,6 +199,36 @@ int blr_posterior_batched_f32(blr_handle* h, int memspace, int layout, int64_t B
                               float* Lw_post, int64_t ldlp, int64_t strideLp,
                               double* logpdf, int32_t* info);
 
+/* ---- the same update on 16-bit features (bf16 / fp16): what a network's last layer hands over ---------------------------------
+ * Replaces reference src/bayesian_linear_regression.jl:72-89, :55-58, :60-69 as blr_posterior_batched_f32 does (examples/nn-blr.jl:
+ * regression on learned features), without the widened copy of X.  xfmt: BLR_X_BF16 or BLR_X_F16; X holds 2-byte elements, ldx and
+ * strideX count elements, any ldx and any 2-byte-aligned base (strideX = 0 shares X).  Every other argument is fp32 / double / int32
+ * with the meaning, strides, NULL-to-skip rule, in-place rule and info semantics of blr_posterior_batched_f32 (a failed regressor leaves
+ * mw_post / T_post untouched); both memspaces; regressors go in chunks of at most 2^20 or option MAX_CHUNK (blr_get_stat "last_chunks").
+ * Served (fused_x16_kernel, csrc/blr_fused_x16.hpp): 1 <= D <= 128, N >= 0, isotropic noise, every prior kind and prior mean, ColVecs and
+ * RowVecs.  Argument errors (return code and blr_last_error; never a silent widening): D > 128 (-6), diagonal or dense noise (-13), an
+ * unknown xfmt (-4).
+ * Numerics: X X' on v_mfma_f32_16x16x32_bf16 / _f16 -- a product of two 16-bit values is exact in fp32, the accumulation is fp32 in a
+ * fixed order, so the Gram matrix loses nothing against the fp32 route on the widened values and the results are bit-reproducible
+ * call to call.  The residual work (y - X'mw, b, the quadratic form) widens in registers and keeps the fp32 route's types; everything
+ * after the Gram matrix is the fp32 route's code.  Held to the fp32 route's tolerance (tests/test_x16_gpu.py).
+ * blr_last_route names the instantiation, "fused_x16_kernel<bf16, 8, 2>": format, 16-row blocks (2, 4, 6, 8: D padded up with zero
+ * rows), loader -- 0 ColVecs / 1 RowVecs through registers (2-byte loads), 2 ColVecs / 3 RowVecs through LDS-DMA (16-byte aligned X,
+ * ldx and strideX multiples of 8; ColVecs: D a multiple of 8 too).
+ * Measured (tools/x16_bench.py, profiles/x16_bench.json): see README.md and DESIGN.md K31. */
+#define BLR_X_BF16 0
+#define BLR_X_F16 1
+int blr_posterior_batched_x16(blr_handle* h, int memspace, int layout, int xfmt, int64_t B, int64_t D, int64_t N,
+                              const void* X, int64_t ldx, int64_t strideX,
+                              const float* y, int64_t stridey,
+                              int noise_kind, const float* s, int64_t strides,
+                              int prior_kind, const float* mw, int64_t stridemw,
+                              const float* Lw, int64_t ldl, int64_t strideLw,
+                              float* mw_post, int64_t stride_mwpost,
+                              float* T_post, int64_t ldt, int64_t strideT,
+                              float* Lw_post, int64_t ldlp, int64_t strideLp,
+                              double* logpdf, int32_t* info);
+
 /* ---- regressors with UNEQUAL observation counts in one call -----------------------------------------------------
  * Replaces: reference src/bayesian_linear_regression.jl:55-58 (logpdf), :60-69 (posterior) and :72-89 (shared quantities) under a
  * map over fxs of different lengths -- which blr_posterior_batched_* (one N for the batch) serves only by a loop of calls or by
