@@ -85,6 +85,9 @@ _SIGS = {
 _SIGS["blr_posterior_batched_x16"] = (
     [_H, _int, _int, _int, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _int, _vp, _i64, _int, _vp, _i64, _vp, _i64, _i64,
      _vp, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp], _int)
+_SIGS["blr_marginals_batched_x16"] = (  # csrc/blr_marg_x16.hpp
+    [_H, _int, _int, _int, _i64, _i64, _i64, _vp, _i64, _i64, _int, _vp, _i64, _int, _vp, _i64, _vp, _i64, _i64,
+     _vp, _i64, _vp, _i64, _vp], _int)
 for _suf in ("f64", "f32"):
     _SIGS[f"blr_posterior_batched_{_suf}"] = (
         [_H, _int, _int, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _int, _vp, _i64, _int, _vp, _i64, _vp, _i64, _i64,
@@ -608,6 +611,14 @@ class Handle:
         return self.check(fn(self._h, memspace, layout, B, D, N, _ptr(X), ldx, strideX, noise_kind, _ptr(s), strides,
                              prior_kind, _ptr(mw), stridemw, _ptr(Lw), ldl, strideLw, _ptr(mean), stridemean,
                              _ptr(var), stridevar, _ptr(info)))
+
+    def marginals_batched_x16(self, xfmt, memspace, layout, B, D, N, X, ldx, strideX, noise_kind, s, strides, prior_kind,
+                              mw, stridemw, Lw, ldl, strideLw, mean, stridemean, var, stridevar, info):
+        """marginals_batched on 16-bit features: xfmt X_BF16 / X_F16, X of 2-byte elements (ldx, strideX in elements), every other
+        array float32; D <= 128, isotropic or diagonal noise (include/blr_mi355x.h blr_marginals_batched_x16)."""
+        return self.check(self.lib.blr_marginals_batched_x16(
+            self._h, memspace, layout, xfmt, B, D, N, _ptr(X), ldx, strideX, noise_kind, _ptr(s), strides, prior_kind, _ptr(mw),
+            stridemw, _ptr(Lw), ldl, strideLw, _ptr(mean), stridemean, _ptr(var), stridevar, _ptr(info)))
 
     def marginals_multi_batched(self, dtype, memspace, layout, B, D, N, S, X, ldx, strideX, noise_kind, s, strides, prior_kind,
                                 M, ldm, strideM, Lw, ldl, strideLw, mean, ldmean, stridemean, var, stridevar, info):

@@ -48,6 +48,7 @@
 #include "blr_grid_ragged.hpp"
 #define BLR_X16_DECLS_ONLY
 #include "blr_fused_x16.hpp"
+#include "blr_marg_x16.hpp"
 #include "blr_host.hpp"
 #include "blr_large_plan.hpp"
 
@@ -6118,6 +6119,114 @@ int blr_posterior_batched_x16(blr_handle* h, int memspace, int layout, int xfmt,
   h->route_buf = std::string("fused_x16_kernel<") + (xfmt == BLR_X_BF16 ? "bf16" : "f16") + ", " + std::to_string(NB) + ", " + std::to_string(mode) + ">";
   h->route = h->route_buf.c_str();
   h->route_i8_B = 0;
+  return io.finish();
+}
+
+// Marginals on 16-bit features, D <= 128: marg_image_kernel<float> (the fp32 triangular inverse, as blr_marginals_batched_f32 forms it),
+// marg_planes_x16_kernel (its exact three-way bf16 split) and marginals_x16_kernel (blr_marg_x16.hpp).  Everything but X is fp32 with
+// the meaning it has in blr_marginals_batched_f32; argument positions are this entry point's own (xfmt is argument 4).  A chunk's fp32
+// images sit at the start of the handle's side buffer, its planes behind them: 96 KiB per regressor, a chunk within 256 MiB.
+int blr_marginals_batched_x16(blr_handle* h, int memspace, int layout, int xfmt, int64_t B, int64_t D, int64_t N, const void* X,
+                              int64_t ldx, int64_t strideX, int noise_kind, const float* s, int64_t strides, int prior_kind,
+                              const float* mw, int64_t stridemw, const float* Lw, int64_t ldl, int64_t strideLw, float* mean,
+                              int64_t stridemean, float* var, int64_t stridevar, int32_t* info) {
+  using XC = MargX16Cfg;
+  using G = MargGemmCfg<float>;
+  if (!h) return -1;
+  h->last_chunks = 1;
+  h->marg_block = {};
+  h->err.clear();
+  if (memspace != BLR_MEM_HOST && memspace != BLR_MEM_DEVICE) return bad_arg(h, 2, "memspace");
+  if (layout != BLR_LAYOUT_COLVECS && layout != BLR_LAYOUT_ROWVECS) return bad_arg(h, 3, "unknown layout (reference :26-31)");
+  if (xfmt != BLR_X_BF16 && xfmt != BLR_X_F16) return bad_arg(h, 4, "unknown xfmt (BLR_X_BF16 or BLR_X_F16)");
+  if (B < 0 || B > (1 << 30)) return bad_arg(h, 5, "B out of range (0..2^30)");
+  if (D < 1) return bad_arg(h, 6, "D < 1");
+  if (D > kMaxSmallD) return bad_arg(h, 6, "D > 128 is not served on 16-bit features (widen them and call blr_marginals_batched_f32)");
+  if (N < 0 || N > (1 << 30)) return bad_arg(h, 7, "N out of range");
+  if (noise_kind == BLR_NOISE_DENSE)
+    return bad_arg(h, 11, "dense noise is not served on 16-bit features (pass its diagonal: only the diagonal enters the marginals)");
+  if (noise_kind != BLR_NOISE_ISOTROPIC && noise_kind != BLR_NOISE_DIAGONAL) return bad_arg(h, 11, "noise_kind");
+  if (prior_kind != BLR_PRIOR_DENSE && prior_kind != BLR_PRIOR_UPPER_FACTOR && prior_kind != BLR_PRIOR_DIAGONAL)
+    return bad_arg(h, 14, "prior_kind");
+  if (B == 0 || N == 0) return 0;
+  if (!X) return bad_arg(h, 8, "X is NULL");
+  if (layout == BLR_LAYOUT_COLVECS ? ldx < D : ldx < N) return bad_arg(h, 9, "ldx too small");
+  if (var && !s) return bad_arg(h, 12, "s is NULL");
+  if (!mw) return bad_arg(h, 15, "mw is NULL");
+  if (var && !Lw) return bad_arg(h, 17, "Lw is NULL");
+  if (prior_kind != BLR_PRIOR_DIAGONAL && ldl < D) return bad_arg(h, 18, "ldl < D");
+  if (mean && B > 1 && stridemean < N) return bad_arg(h, 21, "stridemean < N");
+  if (var && B > 1 && stridevar < N) return bad_arg(h, 23, "stridevar < N");
+  if (!info) return bad_arg(h, 24, "info is NULL");
+  HIP_TRY(h, hipSetDevice(h->device));
+
+  CallIO io(h, memspace);
+  MargX16Args a{};
+  a.ldx = ldx; a.strideX = strideX; a.strides = strides; a.stridemw = stridemw;
+  a.stridemean = stridemean; a.stridevar = stridevar;
+  a.noise_kind = noise_kind; a.D = (int)D; a.N = (int)N;
+  const float* Lw_dev = nullptr;
+  int32_t* info_out_dev = nullptr;
+  int rc;
+  const size_t x_one = layout == BLR_LAYOUT_COLVECS ? mat_extent(D, N, ldx) : mat_extent(N, D, ldx);
+  const size_t lw_one = prior_kind == BLR_PRIOR_DIAGONAL ? (size_t)D : mat_extent(D, D, ldl);
+  if ((rc = io.in(static_cast<const unsigned short*>(X), extent(B, strideX, x_one), &a.X))) return rc;
+  // (a mean-only call reads neither the noise nor the prior's matrix: count 0 stages nothing)
+  if ((rc = io.in(s, var ? extent(B, strides, noise_kind == BLR_NOISE_DIAGONAL ? (size_t)N : 1) : 0, &a.s))) return rc;
+  if ((rc = io.in(mw, extent(B, stridemw, (size_t)D), &a.mw))) return rc;
+  if ((rc = io.in(Lw, var ? extent(B, strideLw, lw_one) : 0, &Lw_dev))) return rc;
+  if ((rc = io.out(mean, extent(B, stridemean, (size_t)N), &a.mean))) return rc;
+  if ((rc = io.out(var, extent(B, stridevar, (size_t)N), &a.var))) return rc;
+  if ((rc = io.out(info, (size_t)B, &info_out_dev))) return rc;
+
+  // the factor of a dense prior once per regressor; a failed regressor keeps its status and its outputs
+  const float* U = Lw_dev;
+  int64_t ldu = ldl, strideU = strideLw;
+  int32_t* chol_info = nullptr;
+  int kind = prior_kind;
+  if (var && (rc = prior_factor<float>(h, B, D, prior_kind, Lw_dev, ldl, strideLw, &U, &ldu, &strideU, &kind, &chol_info))) return rc;
+  a.prior_kind = kind;
+  a.info = chol_info;
+  a.dprior = kind == BLR_PRIOR_DIAGONAL ? U : nullptr;
+  a.stridedp = strideU;
+  if (chol_info) HIP_TRY(h, hipMemcpyAsync(info_out_dev, chol_info, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, h->stream));
+  else HIP_TRY(h, hipMemsetAsync(info_out_dev, 0, (size_t)B * sizeof(int32_t), h->stream));
+
+  // loader: 16-byte loads when every register-of-eight is 16 contiguous, aligned bytes of X
+  const bool rowv = layout == BLR_LAYOUT_ROWVECS;
+  const bool al16 = ((uintptr_t)a.X % 16) == 0 && ldx % 8 == 0 && (B == 1 || strideX % 8 == 0);
+  const int mode = ((al16 && (rowv || D % 8 == 0)) ? 2 : 0) + (rowv ? 1 : 0);
+  const void* const kern = marg_x16_kernel_ptr(xfmt, mode);
+  if ((rc = set_lds_once(h, kern, (size_t)XC::lds_bytes(rowv, true)))) return rc;
+  const bool with_image = var && kind == BLR_PRIOR_UPPER_FACTOR;
+  const size_t lds = (size_t)XC::lds_bytes(rowv, with_image);
+  constexpr int64_t kImg32 = G::IMG_ELEMS * (int64_t)sizeof(float), kPerReg = kImg32 + XC::IMG_BYTES;
+  const int64_t chunk = h->cap_chunk(std::min<int64_t>(std::min<int64_t>(B, 65535), with_image ? ((int64_t)256 << 20) / kPerReg : 65535));
+  h->count_chunks(B, chunk);
+  if (with_image) {
+    if ((rc = h->aux.reserve(h, (size_t)(chunk * kPerReg)))) return rc;
+    if ((rc = MargImages<float>::reserve(h, chunk))) return rc;  // (the buffer is there: marg_image_kernel's LDS limit)
+  }
+  const int64_t ntiles = (N + 15) / 16;
+  for (int64_t b0 = 0; b0 < B; b0 += chunk) {
+    const int64_t nb = std::min<int64_t>(chunk, B - b0);
+    int64_t groups;
+    if (with_image) {  // every workgroup copies up to 60 KiB of image: at least four tiles per wave (as MargProduct::launch)
+      const float* const img32 = MargImages<float>::launch(h, U, ldu, strideU, (int)D, chol_info, b0, nb);
+      char* const img16 = h->aux.p + chunk * kImg32 - b0 * XC::IMG_BYTES;
+      marg_x16_planes_launch(img32, img16, chol_info, (int)D, (int)b0, (unsigned)nb, h->stream);
+      a.img = img16;
+      groups = tile_groups(h, (ntiles + 15) / 16, nb);
+    } else {  // a pure stream: one tile per wave and round is enough set-up to amortise
+      a.img = nullptr;
+      groups = std::max<int64_t>(1, std::min<int64_t>((ntiles + kWaves - 1) / kWaves, (8 * (int64_t)h->cus + nb - 1) / nb));
+    }
+    a.reg0 = (int)b0;
+    marg_x16_launch(xfmt, mode, (unsigned)groups, (unsigned)nb, lds, h->stream, a);
+    HIP_TRY(h, hipGetLastError());
+  }
+  h->route_buf = std::string("marginals_x16_kernel<") + (xfmt == BLR_X_BF16 ? "bf16" : "f16") + ", " + std::to_string(mode) + ">";
+  h->route = h->route_buf.c_str();
   return io.finish();
 }
 

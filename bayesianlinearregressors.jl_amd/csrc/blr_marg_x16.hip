@@ -1,0 +1,45 @@
+// marg_planes_x16_kernel and marginals_x16_kernel (blr_marg_x16.hpp) in a translation unit of their own: the code objects of the
+// existing marginal kernels (blr_marginals.hpp) stay as they are.  Both formats x four loaders.  Host side: blr_abi.hip
+// (blr_marginals_batched_x16).
+#include <hip/hip_runtime.h>
+
+#include "blr_marg_x16.hpp"
+
+namespace blr {
+namespace {
+
+template <int FMT>
+const void* ptr_fmt(int mode) {
+  switch (mode) {
+    case 0: return reinterpret_cast<const void*>(marginals_x16_kernel<FMT, 0>);
+    case 1: return reinterpret_cast<const void*>(marginals_x16_kernel<FMT, 1>);
+    case 2: return reinterpret_cast<const void*>(marginals_x16_kernel<FMT, 2>);
+    case 3: return reinterpret_cast<const void*>(marginals_x16_kernel<FMT, 3>);
+    default: return nullptr;
+  }
+}
+template <int FMT>
+void launch_fmt(int mode, dim3 grid, size_t lds, hipStream_t stream, const MargX16Args& a) {
+  switch (mode) {
+    case 0: hipLaunchKernelGGL((marginals_x16_kernel<FMT, 0>), grid, dim3(kThreads), lds, stream, a); break;
+    case 1: hipLaunchKernelGGL((marginals_x16_kernel<FMT, 1>), grid, dim3(kThreads), lds, stream, a); break;
+    case 2: hipLaunchKernelGGL((marginals_x16_kernel<FMT, 2>), grid, dim3(kThreads), lds, stream, a); break;
+    case 3: hipLaunchKernelGGL((marginals_x16_kernel<FMT, 3>), grid, dim3(kThreads), lds, stream, a); break;
+    default: break;
+  }
+}
+
+}  // namespace
+
+const void* marg_x16_kernel_ptr(int fmt, int mode) { return fmt == 0 ? ptr_fmt<0>(mode) : ptr_fmt<1>(mode); }
+
+void marg_x16_launch(int fmt, int mode, unsigned groups, unsigned nb, size_t lds, hipStream_t stream, const MargX16Args& a) {
+  if (fmt == 0) launch_fmt<0>(mode, dim3(groups, nb), lds, stream, a);
+  else launch_fmt<1>(mode, dim3(groups, nb), lds, stream, a);
+}
+
+void marg_x16_planes_launch(const float* img32, void* img16, const int32_t* info, int D, int reg0, unsigned nb, hipStream_t stream) {
+  hipLaunchKernelGGL(marg_planes_x16_kernel, dim3(nb), dim3(kThreads), 0, stream, img32, static_cast<uint4*>(img16), info, D, reg0);
+}
+
+}  // namespace blr

@@ -2336,8 +2336,56 @@ class ResidentColumnsPosterior:
         return [BasisFunctionRegressor(p, self.phi) for p in posts] if self.phi is not None else posts
 
 
+def _marginals_x16_problem(fb, want_var):
+    """One finite regressor on ColVecs16 / RowVecs16 inputs as blr_marginals_batched_x16 takes it: everything but X as float32, a dense
+    noise covariance reduced to its diagonal (as _marginals does).  The cast is stated in the docstrings of mean, var, mean_and_var."""
+    dtype = np.float32
+    X, layout, ldx, D, N = _x16_layout(fb.x)
+    if D > 128:
+        raise ValueError(f"16-bit inputs are served for D <= 128, got D = {D}: widen them (x.widen())")
+    if D == 0:
+        raise ValueError("16-bit inputs need D >= 1")
+    s, noise_kind = _noise(fb.Sy, N, dtype)
+    if noise_kind == _abi.NOISE_DENSE:
+        s, noise_kind = np.ascontiguousarray(np.diag(s)), _abi.NOISE_DIAGONAL
+    Lw, prior_kind, ldl = _prior(fb.f.Lw, D, dtype, need_cholesky=want_var)  # :41 _cholesky(Lw)
+    return X, layout, ldx, D, N, s, noise_kind, fb.x.fmt, _mean_vector(fb.f.mw, D, dtype), Lw, prior_kind, ldl
+
+
+def _marginals_x16_many(probs, want_mean, want_var):
+    """Equally shaped problems on 16-bit inputs (_marginals_x16_problem records) in ONE blr_marginals_batched_x16 call ->
+    [(mean, var)]."""
+    X0, layout, ldx, D, N, _, noise_kind, fmt, _, _, prior_kind, ldl = probs[0]
+    nb = len(probs)
+    Xb = X0.reshape(1, -1, order="A") if nb == 1 else np.stack([q[0].reshape(-1, order="A") for q in probs])
+    sb = np.stack([q[5] for q in probs])
+    mwb = np.stack([q[8] for q in probs])
+    Lb = np.stack([q[9].reshape(-1, order="A") for q in probs])
+    m = np.empty((nb, N), dtype=np.float32) if want_mean else None
+    v = np.empty((nb, N), dtype=np.float32) if want_var else None
+    info = np.zeros(nb, dtype=np.int32)
+    _handle().marginals_batched_x16(_abi.X_BF16 if fmt == "bf16" else _abi.X_F16, _abi.MEM_HOST, layout, nb, D, N, Xb, ldx, Xb.shape[1],
+                                    noise_kind, sb, sb.shape[1], prior_kind, mwb, D, Lb, ldl, Lb.shape[1], m, N, v, N, info)
+    _raise_first_failed(info)
+    return [(m[b] if want_mean else None, v[b] if want_var else None) for b in range(nb)]
+
+
+def mean_and_var_map(fxs):
+    """[mean_and_var(fx) for fx in fxs].  Problems on 16-bit inputs (ColVecs16 / RowVecs16) that agree in D, N, layout, format, prior
+    kind and noise kind go through ONE blr_marginals_batched_x16 call; anything else through the loop."""
+    fbs = [_to_finite_blr(fx) for fx in fxs]
+    if fbs and all(isinstance(fb.x, _Vecs16) for fb in fbs):
+        probs = [_marginals_x16_problem(fb, True) for fb in fbs]
+        if len({(q[0].shape, q[0].flags.f_contiguous, q[1], q[3], q[4], q[6], q[7], q[10]) for q in probs}) == 1:
+            return _marginals_x16_many(probs, True, True)
+        return [_marginals_x16_many([q], True, True)[0] for q in probs]  # (each problem is prepared once either way)
+    return [mean_and_var(fb) for fb in fbs]
+
+
 def _marginals(fx, want_mean, want_var):
     fx = _to_finite_blr(fx)
+    if isinstance(fx.x, _Vecs16):
+        return _marginals_x16_many([_marginals_x16_problem(fx, want_var)], want_mean, want_var)[0]
     blr = fx.f
     dtype = _dtype_of(blr.mw)
     X, layout, ldx, D, N = _x_layout(fx.x, dtype)
@@ -2357,17 +2405,20 @@ def _marginals(fx, want_mean, want_var):
 
 
 def mean(fx):
-    """reference :33"""
+    """reference :33.  On ColVecs16 / RowVecs16 inputs (D <= 128) the call is blr_marginals_batched_x16: mw, Lw and the noise are cast to
+    float32 whatever their dtype (a float64 regressor included) and the result is float32; x.widen() keeps the regressor's dtype."""
     return _marginals(fx, True, False)[0]
 
 
 def var(fx):
-    """reference :40-43"""
+    """reference :40-43.  On ColVecs16 / RowVecs16 inputs (D <= 128) the call is blr_marginals_batched_x16: mw, Lw and the noise are cast to
+    float32 whatever their dtype (a float64 regressor included) and the result is float32; x.widen() keeps the regressor's dtype."""
     return _marginals(fx, False, True)[1]
 
 
 def mean_and_var(fx):
-    """reference :47"""
+    """reference :47.  On ColVecs16 / RowVecs16 inputs (D <= 128) the call is blr_marginals_batched_x16: mw, Lw and the noise are cast to
+    float32 whatever their dtype (a float64 regressor included) and the result is float32; x.widen() keeps the regressor's dtype."""
     return _marginals(fx, True, True)
 
 

@@ -229,6 +229,35 @@ int blr_posterior_batched_x16(blr_handle* h, int memspace, int layout, int xfmt,
                               float* Lw_post, int64_t ldlp, int64_t strideLp,
                               double* logpdf, int32_t* info);
 
+/* ---- marginals on 16-bit features: the prediction half of the same use ---------------------------------------------------------
+ * Replaces reference src/bayesian_linear_regression.jl:33 (mean), :40-43 (var), :47 (mean_and_var) as blr_marginals_batched_f32 does,
+ * for inputs that arrive as bf16 / fp16, without the widened copy.  xfmt, X, ldx, strideX: as blr_posterior_batched_x16 (2-byte
+ * elements, any ldx, any 2-byte-aligned base, strideX = 0 shares X).  Every other argument is fp32 / int32 with the meaning, strides,
+ * NULL-to-skip rule (mean or var may be NULL) and info semantics of blr_marginals_batched_f32: a dense prior is factorised per
+ * regressor, a regressor whose factorisation fails gets info > 0 and its outputs stay untouched.  Both memspaces.  Regressors go in
+ * chunks bounded by 65535, the image buffer (256 MiB: 96 KiB per regressor) and option MAX_CHUNK (blr_get_stat "last_chunks").
+ * Served (marginals_x16_kernel, csrc/blr_marg_x16.hpp): 1 <= D <= 128, N >= 0, ColVecs and RowVecs, every prior kind, isotropic and
+ * diagonal noise.  Argument errors (return code = position, and blr_last_error; never a silent widening): D > 128 (-6), dense noise
+ * (-11: pass its diagonal), an unknown xfmt (-4).
+ * Numerics: the fp32 triangular inverse M = L^-T (the one blr_marginals_batched_f32 forms at D = 128) is split exactly into three bf16
+ * pieces and z = M'x runs on v_mfma_f32_16x16x32_bf16 (an fp16 input is split exactly into two bf16 values; its low piece against
+ * the lowest piece of M, 2^-24 of |x||M|, is dropped): exact products, fp32 accumulation in a fixed order, the same bits call to call.
+ * Forward accuracy cond(L) eps32 from the explicit inverse, as the fp32 product route.  mean: fp32 products and sums of the widened
+ * values.  A diagonal prior needs no matrix work: var_n = sum x_d^2 / Lw_d + s_n on the vector ALU.
+ * Non-finite features: an Inf meets zero pieces of M (Inf x 0), and the fp16 split of Inf has the low piece Inf - Inf, so with a
+ * factor or dense prior var_n of THAT input is NaN in both formats, where the fp32 route may give Inf; mean_n and the var_n of a
+ * diagonal prior follow fp32 arithmetic on the widened values.  Other inputs of the call are not affected.
+ * blr_last_route names the instantiation, "marginals_x16_kernel<bf16, 0>": format, loader -- 0 ColVecs / 1 RowVecs by 2-byte loads,
+ * 2 ColVecs / 3 RowVecs by 16-byte loads (16-byte aligned X, ldx and strideX multiples of 8; ColVecs: D a multiple of 8 too).
+ * Measured (tools/x16_marg_bench.py, profiles/x16_marg_bench.json): see README.md and DESIGN.md K32. */
+int blr_marginals_batched_x16(blr_handle* h, int memspace, int layout, int xfmt, int64_t B, int64_t D, int64_t N,
+                              const void* X, int64_t ldx, int64_t strideX,
+                              int noise_kind, const float* s, int64_t strides,
+                              int prior_kind, const float* mw, int64_t stridemw,
+                              const float* Lw, int64_t ldl, int64_t strideLw,
+                              float* mean, int64_t stridemean, float* var, int64_t stridevar,
+                              int32_t* info);
+
 /* ---- regressors with UNEQUAL observation counts in one call -----------------------------------------------------
  * Replaces: reference src/bayesian_linear_regression.jl:55-58 (logpdf), :60-69 (posterior) and :72-89 (shared quantities) under a
  * map over fxs of different lengths -- which blr_posterior_batched_* (one N for the batch) serves only by a loop of calls or by
