@@ -6,65 +6,17 @@ import pytest
 
 import blr_amd as R
 from _small_d_problems import _outputs, _result, _same_bits
+from _x16_problems import NB, PRIORS, XKINDS, _problem
 from _yardsticks import _assert_fp32_within_lapack
 from blr_amd import _abi
 
 pytestmark = pytest.mark.gpu
-
-XKINDS = ("col_al", "col_odd", "row_al", "row_odd")
-PRIORS = ("diag", "factor", "dense")
-NB = 5
-
 
 @pytest.fixture(scope="module")
 def hd():
     h = _abi.Handle(0)
     yield h
     h.close()
-
-
-def _problem(fmt, xkind, D, N, prior, ints=False, seed=0):
-    """NB regressors with strides of their own.  *_al: ldx and strideX multiples of 8 elements (16 bytes); *_odd: odd ldx and strideX.
-    Features are float32 draws rounded to the format (ints: (7 d + 3 n + b) mod 17 - 8); gaps of X hold NaN."""
-    rng = np.random.Generator(np.random.PCG64(1000 * D + N + seed))
-    d, n, b = np.arange(D)[None, :, None], np.arange(N)[None, None, :], np.arange(NB)[:, None, None]
-    Xf = ((7 * d + 3 * n + b) % 17 - 8).astype(np.float32) if ints else rng.standard_normal((NB, D, N)).astype(np.float32)
-    X16 = R.bf16_bits(Xf) if fmt == "bf16" else Xf.astype(np.float16)
-    Xw = R.widen16(X16, fmt)  # (NB, D, N): the exact float32 values the kernel sees
-    col, aligned = xkind.startswith("col"), xkind.endswith("_al")
-    rows, cols = (D, N) if col else (N, D)
-    ldx = -(-rows // 8) * 8 if aligned else (rows + 1) | 1
-    strideX = ldx * cols if aligned else (ldx * cols + 2) | 1
-    buf = np.full(NB * strideX, 0x7FC0 if fmt == "bf16" else np.nan, dtype=X16.dtype)
-    for i in range(NB):
-        buf[i * strideX:i * strideX + ldx * cols].reshape((ldx, cols), order="F")[:rows, :] = X16[i] if col else X16[i].T
-    if ints:
-        y = rng.integers(-4, 5, size=(NB, N)).astype(np.float32)
-        mw, s = np.zeros((NB, D), np.float32), np.ones(NB, np.float32)
-    else:
-        w = rng.standard_normal(D) / np.sqrt(D)
-        y = (np.einsum("bdn,d->bn", Xw.astype(float), w) + 0.8 * rng.standard_normal((NB, N))).astype(np.float32)
-        mw, s = (0.2 * rng.standard_normal((NB, D))).astype(np.float32), np.exp(0.3 * rng.standard_normal(NB) - 0.5).astype(np.float32)
-    if prior == "diag":
-        Lw = np.ones((NB, D), np.float32) if ints else np.exp(0.3 * rng.standard_normal((NB, D))).astype(np.float32)
-        dense, ldl = list(Lw), 1
-    else:
-        Lw, dense, ldl = np.zeros((NB, D * D), np.float32), [], D
-        for i in range(NB):
-            if prior == "factor":  # multiples of 1/8: U'U is exact in fp32 too
-                U = np.triu(rng.integers(-1, 2, size=(D, D)) / 8.0, 1) + np.diag(1.0 + rng.integers(0, 5, size=D) / 8.0)
-                Lw[i], M = U.reshape(-1, order="F"), (U.T @ U).astype(np.float32)
-            else:
-                Bm = rng.standard_normal((D, D)) / np.sqrt(D)
-                M = (Bm @ Bm.T + np.eye(D)).astype(np.float32)
-                M = np.triu(M) + np.triu(M, 1).T
-                Lw[i] = M.reshape(-1, order="F")
-            dense.append(M)
-    kind = {"diag": _abi.PRIOR_DIAGONAL, "dense": _abi.PRIOR_DENSE, "factor": _abi.PRIOR_UPPER_FACTOR}[prior]
-    fast = aligned and (not col or D % 8 == 0)
-    return dict(D=D, N=N, nb=NB, dtype=np.float32, xfmt=_abi.X_BF16 if fmt == "bf16" else _abi.X_F16, X=buf, Xw=Xw, ldx=ldx, strideX=strideX,
-                layout=_abi.LAYOUT_COLVECS if col else _abi.LAYOUT_ROWVECS, y=y, s=s, mw=mw, Lw=Lw, ldl=ldl, dense=dense, prior_kind=kind,
-                route=f"fused_x16_kernel<{fmt}, {2 * ((D + 31) // 32)}, {(2 if fast else 0) + (0 if col else 1)}>")
 
 
 def _call(hd, q, o, **over):

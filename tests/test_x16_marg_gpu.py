@@ -7,35 +7,15 @@ import pytest
 import blr_amd as R
 from blr_amd import _abi
 from oracle import blr_oracle as O
-from test_x16_gpu import NB, XKINDS, _problem
+from _x16_problems import EPS32, NB, PRIORS, XKINDS, _assert_within_oracle, _marg_problem, _out, _rel
 
 pytestmark = pytest.mark.gpu
-
-PRIORS = ("diag", "factor", "dense")
-EPS32 = float(np.finfo(np.float32).eps)
-
 
 @pytest.fixture(scope="module")
 def hd():
     h = _abi.Handle(0)
     yield h
     h.close()
-
-
-def _marg_problem(fmt, xkind, D, N, prior, diag_noise, ints=False):
-    """test_x16_gpu's problem (X in every layout with NaN in the gaps, five regressors with strides of their own) with the noise of
-    this entry point and room for its outputs (NaN, strides of their own)."""
-    q = _problem(fmt, xkind, D, N, prior, ints=ints)
-    rng = np.random.Generator(np.random.PCG64(77 * D + N))
-    if diag_noise:
-        q["s"] = np.ones((NB, N), np.float32) if ints else np.exp(0.3 * rng.standard_normal((NB, N)) - 0.5).astype(np.float32)
-    q.update(noise_kind=_abi.NOISE_DIAGONAL if diag_noise else _abi.NOISE_ISOTROPIC, strides=N if diag_noise else 1,
-             route=f"marginals_x16_kernel<{fmt}, {q['route'][-2]}>")
-    return q
-
-
-def _out(N):
-    return dict(mean=np.full((NB, N + 3), np.nan, np.float32), var=np.full((NB, N + 5), np.nan, np.float32), info=np.full(NB, 7, np.int32))
 
 
 def _call(hd, q, o, mean=True, var=True, memspace=_abi.MEM_HOST, **over):
@@ -45,35 +25,6 @@ def _call(hd, q, o, mean=True, var=True, memspace=_abi.MEM_HOST, **over):
                                     a["noise_kind"], ptr(a["s"]), a["strides"], a["prior_kind"], ptr(a["mw"]), a["D"], ptr(a["Lw"]), a["ldl"],
                                     a["Lw"].shape[1], ptr(o["mean"]) if mean else None, o["mean"].shape[1], ptr(o["var"]) if var else None,
                                     o["var"].shape[1], ptr(o["info"]))
-
-
-def _oracle(q, b, dtype):
-    """(mean, var) of regressor b by oracle.blr_oracle in `dtype`, on the exactly widened features and the fp32-rounded mw, Lw, s."""
-    D, X = q["D"], np.asfortranarray(q["Xw"][b], dtype=dtype)
-    mw, s = q["mw"][b].astype(dtype), (q["s"][b] if q["noise_kind"] == _abi.NOISE_DIAGONAL else q["s"][b:b + 1].repeat(q["N"])).astype(dtype)
-    if q["prior_kind"] == _abi.PRIOR_UPPER_FACTOR:
-        return O.marginals_direct(mw, q["Lw"][b].reshape((D, D), order="F").astype(dtype), X, s)
-    Lw = q["Lw"][b].astype(dtype) if q["prior_kind"] == _abi.PRIOR_DIAGONAL else np.asarray(q["dense"][b], dtype=dtype)
-    return O.mean(mw, X), O.var(mw, Lw, X, s)
-
-
-def _rel(got, ref):
-    return float(np.max(np.abs(np.asarray(got, float) - ref)) / np.max(np.abs(ref)))
-
-
-def _assert_within_oracle(q, o, regs=range(NB)):
-    """Regressor by regressor: bound = 4 x the relative error (max abs over max abs) the same oracle function makes in float32 on that
-    regressor's inputs + 4 eps32 (cases fp32 LAPACK solves all but exactly); the yardstick is the reference's own error, not the
-    kernel's, and it is non-zero and finite in every case here."""
-    N = q["N"]
-    for b in regs:
-        ref, f32 = _oracle(q, b, np.float64), _oracle(q, b, np.float32)
-        for k, name in enumerate(("mean", "var")):
-            assert f32[k].dtype == np.float32
-            yard, err = _rel(f32[k], ref[k]), _rel(o[name][b, :N], ref[k])
-            print(f"{q['route']} D={q['D']} N={N} regressor {b} {name}: error {err:.3g}, fp32 oracle {yard:.3g}")
-            assert 0 < yard < np.inf and err <= 4 * yard + 4 * EPS32, (q["route"], b, name, err, yard)
-    assert np.all(np.isnan(o["mean"][:, N:])) and np.all(np.isnan(o["var"][:, N:]))  # nothing written behind the N outputs
 
 
 @pytest.mark.parametrize("N", [1, 29, 131])
