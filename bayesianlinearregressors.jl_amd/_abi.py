@@ -85,6 +85,9 @@ _SIGS = {
 _SIGS["blr_posterior_batched_x16"] = (
     [_H, _int, _int, _int, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _int, _vp, _i64, _int, _vp, _i64, _vp, _i64, _i64,
      _vp, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp], _int)
+_SIGS["blr_posterior_multi_batched_x16"] = (  # csrc/blr_multi_x16.hpp
+    [_H, _int, _int, _int, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _int, _vp, _i64, _int, _vp, _i64, _vp, _i64, _i64,
+     _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _vp], _int)
 _SIGS["blr_marginals_batched_x16"] = (  # csrc/blr_marg_x16.hpp
     [_H, _int, _int, _int, _i64, _i64, _i64, _vp, _i64, _i64, _int, _vp, _i64, _int, _vp, _i64, _vp, _i64, _i64,
      _vp, _i64, _vp, _i64, _vp], _int)
@@ -434,6 +437,16 @@ class Handle:
         return self.check(fn(self._h, memspace, layout, B, D, N, S, _ptr(X), ldx, strideX, _ptr(Y), ldY, strideY, noise_kind, _ptr(s),
                              strides, prior_kind, _ptr(mw), stridemw, _ptr(Lw), ldl, strideLw, _ptr(mw_post), ldmp, stride_mwpost,
                              _ptr(T_post), ldt, strideT, _ptr(Lw_post), ldlp, strideLp, _ptr(logpdf), stride_lp, _ptr(info)))
+
+    def posterior_multi_batched_x16(self, xfmt, memspace, layout, B, D, N, S, X, ldx, strideX, Y, ldY, strideY, noise_kind, s, strides,
+                                    prior_kind, mw, stridemw, Lw, ldl, strideLw, mw_post, ldmp, stride_mwpost, T_post, ldt, strideT,
+                                    Lw_post, ldlp, strideLp, logpdf, stride_lp, info):
+        """posterior_multi_batched on 16-bit features: xfmt X_BF16 / X_F16, X of 2-byte elements (ldx, strideX in elements), every
+        other array float32; D <= 128, isotropic noise (include/blr_mi355x.h blr_posterior_multi_batched_x16)."""
+        return self.check(self.lib.blr_posterior_multi_batched_x16(
+            self._h, memspace, layout, xfmt, B, D, N, S, _ptr(X), ldx, strideX, _ptr(Y), ldY, strideY, noise_kind, _ptr(s), strides,
+            prior_kind, _ptr(mw), stridemw, _ptr(Lw), ldl, strideLw, _ptr(mw_post), ldmp, stride_mwpost, _ptr(T_post), ldt, strideT,
+            _ptr(Lw_post), ldlp, strideLp, _ptr(logpdf), stride_lp, _ptr(info)))
 
     def posterior_nsharded(self, dtype, layout, D, N_local, N_total, X, ldx, y, noise_kind, s, prior_kind, mw, Lw, ldl, stats, lds,
                            scal, mw_post, T_post, ldt, Lw_post, ldlp, logpdf, info):

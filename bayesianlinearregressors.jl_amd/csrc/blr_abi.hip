@@ -49,6 +49,7 @@
 #define BLR_X16_DECLS_ONLY
 #include "blr_fused_x16.hpp"
 #include "blr_marg_x16.hpp"
+#include "blr_multi_x16.hpp"
 #include "blr_host.hpp"
 #include "blr_large_plan.hpp"
 
@@ -6047,6 +6048,60 @@ int blr_timer_stop(blr_handle* h, float* elapsed_ms) {
 BLR_DEFINE(f64, double)
 BLR_DEFINE(f32, float)
 
+// The launches of the 16-bit-feature posterior on device operands (a.p.B regressors, checked by the caller): fused_x16_kernel chunk by
+// chunk and, with `m` (blr_posterior_multi_batched_x16: a.p is column 0, its evidence in m->lp0), multi_cols_x16_kernel behind it in
+// the same chunk, which reads column 0's status on the device.  Sets the route.
+static int posterior_x16_run(blr_handle* h, int xfmt, const X16Args& a, const MultiX16Args* m) {
+  const PosteriorArgs<float>& p = a.p;
+  const int64_t B = p.B, D = p.D, ldx = p.ldx, strideX = a.strideX;
+  int rc;
+  // loader: whole stages by LDS-DMA when every 16-byte piece of the image is 16 contiguous, aligned bytes of X
+  const bool al16 = ((uintptr_t)a.X % 16) == 0 && ldx % 8 == 0 && (B == 1 || strideX % 8 == 0);
+  const bool rowv = p.layout == BLR_LAYOUT_ROWVECS;
+  const bool fast = !h->opt.no_ldsdma && al16 && (rowv || D % 8 == 0);
+  const int mode = (fast ? 2 : 0) + (rowv ? 1 : 0);
+  const int NB = 2 * (int)((D + 31) / 32);  // even block counts only: the padding rows are zero in LDS
+  const void* const kern = x16_kernel_ptr(xfmt, NB, mode);
+  if (kern == nullptr) return hip_fail(h, hipErrorInvalidValue, "this build lacks the requested form of fused_x16_kernel");
+  if ((rc = set_lds_once(h, kern, x16_kernel_lds(NB)))) return rc;
+  const int per_pass = kMultiColsPerPass - 1;
+  const int64_t passes = m ? std::max<int64_t>(1, (m->S - 1 + per_pass - 1) / per_pass) : 0;
+  const size_t mlds = m ? multi_x16_lds_bytes(NB, (int)D, (int)std::min<int64_t>(m->S, kMultiColsPerPass)) : 0;
+  if (m) {
+    const void* const mkern = multi_x16_kernel_ptr(xfmt, NB, mode);
+    if (mkern == nullptr) return hip_fail(h, hipErrorInvalidValue, "this build lacks the requested form of multi_cols_x16_kernel");
+    if ((rc = set_lds_once(h, mkern, mlds))) return rc;
+  }
+  const int64_t chunk = h->cap_chunk(std::min<int64_t>(B, 1 << 20));  // one workgroup per regressor
+  h->count_chunks(B, chunk);
+  for (int64_t b0 = 0; b0 < B; b0 += chunk) {
+    X16Args c = a;
+    c.p.B = (int)std::min<int64_t>(chunk, B - b0);
+    c.X += b0 * strideX; c.p.y += b0 * p.stridey; c.p.s += b0 * p.strides; c.p.mw += b0 * p.stridemw; c.p.Lw += b0 * p.strideLw;
+    if (c.p.mw_post) c.p.mw_post += b0 * p.stride_mwpost;
+    if (c.p.T_post) c.p.T_post += b0 * p.strideT;
+    if (c.p.Lw_post) c.p.Lw_post += b0 * p.strideLp;
+    if (c.p.logpdf) c.p.logpdf += b0;
+    c.p.info += b0;
+    x16_kernel_launch(xfmt, NB, mode, (unsigned)c.p.B, h->stream, c);
+    HIP_TRY(h, hipGetLastError());
+    if (m) {
+      MultiX16Args mc = *m;
+      mc.X += b0 * mc.strideX; mc.Y += b0 * mc.strideY; mc.s += b0 * mc.strides; mc.mw += b0 * mc.stridemw; mc.Tf += b0 * mc.strideT;
+      mc.lp0 += b0; mc.info += b0;
+      if (mc.mw_post) mc.mw_post += b0 * mc.stride_mwpost;
+      if (mc.logpdf) mc.logpdf += b0 * mc.stride_lp;
+      multi_x16_kernel_launch(xfmt, NB, mode, (unsigned)c.p.B, (unsigned)passes, mlds, h->stream, mc);
+      HIP_TRY(h, hipGetLastError());
+    }
+  }
+  const std::string inst = std::string("<") + (xfmt == BLR_X_BF16 ? "bf16" : "f16") + ", " + std::to_string(NB) + ", " + std::to_string(mode) + ">";
+  h->route_buf = "fused_x16_kernel" + inst + (m ? " + multi_cols_x16_kernel" + inst : std::string());
+  h->route = h->route_buf.c_str();
+  h->route_i8_B = 0;
+  return 0;
+}
+
 // 16-bit features (bf16 / fp16), D <= 128, isotropic noise: fused_x16_kernel (blr_fused_x16.hpp).  Everything but X is fp32 with the
 // meaning it has in blr_posterior_batched_f32; argument positions are this entry point's own (xfmt is argument 4).
 int blr_posterior_batched_x16(blr_handle* h, int memspace, int layout, int xfmt, int64_t B, int64_t D, int64_t N, const void* X,
@@ -6092,33 +6147,101 @@ int blr_posterior_batched_x16(blr_handle* h, int memspace, int layout, int xfmt,
   if ((rc = io.out(logpdf, (size_t)B, &p.logpdf))) return rc;
   if ((rc = io.out(info, (size_t)B, &p.info))) return rc;
   if (N == 0 && !p.y) p.y = p.mw;  // no data: the kernel never dereferences X / y, but keep the pointer valid
+  if ((rc = posterior_x16_run(h, xfmt, a, nullptr))) return rc;
+  return io.finish();
+}
 
-  // loader: whole stages by LDS-DMA when every 16-byte piece of the image is 16 contiguous, aligned bytes of X
-  const bool al16 = ((uintptr_t)a.X % 16) == 0 && ldx % 8 == 0 && (B == 1 || strideX % 8 == 0);
-  const bool rowv = layout == BLR_LAYOUT_ROWVECS;
-  const bool fast = !h->opt.no_ldsdma && al16 && (rowv || D % 8 == 0);
-  const int mode = (fast ? 2 : 0) + (rowv ? 1 : 0);
-  const int NB = 2 * (int)((D + 31) / 32);  // even block counts only: the padding rows are zero in LDS
-  const void* const kern = x16_kernel_ptr(xfmt, NB, mode);
-  if (kern == nullptr) return hip_fail(h, hipErrorInvalidValue, "this build lacks the requested form of fused_x16_kernel");
-  if ((rc = set_lds_once(h, kern, x16_kernel_lds(NB)))) return rc;
-  const int64_t chunk = h->cap_chunk(std::min<int64_t>(B, 1 << 20));  // one workgroup per regressor
-  h->count_chunks(B, chunk);
-  for (int64_t b0 = 0; b0 < B; b0 += chunk) {
-    X16Args c = a;
-    c.p.B = (int)std::min<int64_t>(chunk, B - b0);
-    c.X += b0 * strideX; c.p.y += b0 * stridey; c.p.s += b0 * strides; c.p.mw += b0 * stridemw; c.p.Lw += b0 * strideLw;
-    if (c.p.mw_post) c.p.mw_post += b0 * stride_mwpost;
-    if (c.p.T_post) c.p.T_post += b0 * strideT;
-    if (c.p.Lw_post) c.p.Lw_post += b0 * strideLp;
-    if (c.p.logpdf) c.p.logpdf += b0;
-    c.p.info += b0;
-    x16_kernel_launch(xfmt, NB, mode, (unsigned)c.p.B, h->stream, c);
-    HIP_TRY(h, hipGetLastError());
-  }
-  h->route_buf = std::string("fused_x16_kernel<") + (xfmt == BLR_X_BF16 ? "bf16" : "f16") + ", " + std::to_string(NB) + ", " + std::to_string(mode) + ">";
-  h->route = h->route_buf.c_str();
-  h->route_i8_B = 0;
+// S target columns per regressor on 16-bit features: column 0 through posterior_x16_run as blr_posterior_batched_x16
+// runs it, the further columns through multi_cols_x16_kernel (blr_multi_x16.hpp) in the same chunk loop.  Everything but X is fp32 with
+// the meaning it has in blr_posterior_multi_batched_f32; argument positions are this entry point's own (xfmt is argument 4).
+int blr_posterior_multi_batched_x16(blr_handle* h, int memspace, int layout, int xfmt, int64_t B, int64_t D, int64_t N, int64_t S,
+                                    const void* X, int64_t ldx, int64_t strideX, const float* Y, int64_t ldY, int64_t strideY,
+                                    int noise_kind, const float* s, int64_t strides, int prior_kind, const float* mw, int64_t stridemw,
+                                    const float* Lw, int64_t ldl, int64_t strideLw, float* mw_post, int64_t ldmp, int64_t stride_mwpost,
+                                    float* T_post, int64_t ldt, int64_t strideT, float* Lw_post, int64_t ldlp, int64_t strideLp,
+                                    double* logpdf, int64_t stride_lp, int32_t* info) {
+  if (h) h->err.clear();
+  if (memspace != BLR_MEM_HOST && memspace != BLR_MEM_DEVICE) return bad_arg(h, 2, "memspace");
+  if (layout != BLR_LAYOUT_COLVECS && layout != BLR_LAYOUT_ROWVECS) return bad_arg(h, 3, "unknown layout (reference :26-31)");
+  if (xfmt != BLR_X_BF16 && xfmt != BLR_X_F16) return bad_arg(h, 4, "unknown xfmt (BLR_X_BF16 or BLR_X_F16)");
+  if (B < 0 || B > (1 << 30)) return bad_arg(h, 5, "B out of range (0..2^30)");
+  if (D < 1) return bad_arg(h, 6, "D < 1");
+  if (D > kMaxSmallD)
+    return bad_arg(h, 6, "D > 128 is not served on 16-bit features (widen them and call blr_posterior_multi_batched_f32)");
+  if (N < 0 || N > (1 << 30)) return bad_arg(h, 7, "N out of range");
+  if (S < 0 || S > (1 << 20)) return bad_arg(h, 8, "S out of range (0..2^20)");
+  if (noise_kind != BLR_NOISE_ISOTROPIC)
+    return bad_arg(h, 15, "only isotropic noise is served on 16-bit features (widen them and call blr_posterior_multi_batched_f32)");
+  if (prior_kind != BLR_PRIOR_DENSE && prior_kind != BLR_PRIOR_UPPER_FACTOR && prior_kind != BLR_PRIOR_DIAGONAL)
+    return bad_arg(h, 18, "prior_kind");
+  if (B == 0 || S == 0) return 0;
+  if (N > 0 && !X) return bad_arg(h, 9, "X is NULL");
+  if (layout == BLR_LAYOUT_COLVECS ? ldx < D : ldx < std::max<int64_t>(N, 1)) return bad_arg(h, 10, "ldx too small");
+  if (strideX < 0) return bad_arg(h, 11, "strideX < 0");
+  if (N > 0 && !Y) return bad_arg(h, 12, "Y is NULL (reference :74 length check)");
+  if (ldY < N) return bad_arg(h, 13, "ldY < N (reference :74 length check)");
+  if (strideY < 0) return bad_arg(h, 14, "strideY < 0");
+  if (!s) return bad_arg(h, 16, "s is NULL");
+  if (strides < 0) return bad_arg(h, 17, "strides < 0");
+  if (!mw) return bad_arg(h, 19, "mw is NULL");
+  if (stridemw < 0) return bad_arg(h, 20, "stridemw < 0");
+  if (!Lw) return bad_arg(h, 21, "Lw is NULL");
+  if (prior_kind != BLR_PRIOR_DIAGONAL && ldl < D) return bad_arg(h, 22, "ldl < D");
+  if (strideLw < 0) return bad_arg(h, 23, "strideLw < 0");
+  if (mw_post && mw_post == mw) return bad_arg(h, 24, "mw_post == mw (the columns after the first still need the prior mean)");
+  if (mw_post && ldmp < D) return bad_arg(h, 25, "ldmp < D");
+  if (mw_post && B > 1 && stride_mwpost < ldmp * S) return bad_arg(h, 26, "stride_mwpost < ldmp * S");
+  if (T_post && T_post == Lw) return bad_arg(h, 27, "T_post == Lw (aliasing an output with an input is not supported)");
+  if (T_post && ldt < D) return bad_arg(h, 28, "ldt < D");
+  if (T_post && B > 1 && strideT < (int64_t)mat_extent(D, D, ldt)) return bad_arg(h, 29, "strideT too small");
+  if (Lw_post && ldlp < D) return bad_arg(h, 31, "ldlp < D");
+  if (Lw_post && B > 1 && strideLp < (int64_t)mat_extent(D, D, ldlp)) return bad_arg(h, 32, "strideLp too small");
+  if (logpdf && B > 1 && stride_lp < S) return bad_arg(h, 34, "stride_lp < S");
+  if (!info) return bad_arg(h, 35, "info is NULL");
+  if (!h) return -1;
+  h->last_chunks = 1;
+  HIP_TRY(h, hipSetDevice(h->device));
+
+  X16Args a{};
+  PosteriorArgs<float>& p = a.p;
+  p.ldx = ldx; p.strideX = 0; p.stridey = strideY; p.strides = strides; p.stridemw = stridemw;
+  p.ldl = ldl; p.strideLw = strideLw; p.stride_mwpost = stride_mwpost; p.ldt = ldt; p.strideT = strideT;
+  p.ldlp = ldlp; p.strideLp = strideLp;
+  p.layout = layout; p.noise_kind = noise_kind; p.prior_kind = prior_kind;
+  p.D = (int)D; p.N = (int)N; p.B = (int)B;
+  a.strideX = strideX;
+
+  CallIO io(h, memspace);
+  const size_t x_one = layout == BLR_LAYOUT_COLVECS ? mat_extent(D, N, ldx) : mat_extent(N, D, ldx);
+  const size_t lw_one = prior_kind == BLR_PRIOR_DIAGONAL ? (size_t)D : mat_extent(D, D, ldl);
+  double* lp_d = nullptr;
+  int rc;
+  if ((rc = io.in(static_cast<const unsigned short*>(X), extent(B, strideX, x_one), &a.X))) return rc;
+  if ((rc = io.in(Y, N > 0 ? extent(B, strideY, mat_extent(N, S, ldY)) : 0, &p.y))) return rc;
+  if ((rc = io.in(s, extent(B, strides, 1), &p.s))) return rc;
+  if ((rc = io.in(mw, extent(B, stridemw, (size_t)D), &p.mw))) return rc;
+  if ((rc = io.in(Lw, extent(B, strideLw, lw_one), &p.Lw))) return rc;
+  if ((rc = io.out(mw_post, extent(B, stride_mwpost, mat_extent(D, S, ldmp)), &p.mw_post))) return rc;
+  if ((rc = io.out(T_post, extent(B, strideT, mat_extent(D, D, ldt)), &p.T_post))) return rc;
+  if ((rc = io.out(Lw_post, extent(B, strideLp, mat_extent(D, D, ldlp)), &p.Lw_post))) return rc;
+  if ((rc = io.out(logpdf, extent(B, stride_lp, (size_t)S), &lp_d))) return rc;
+  if ((rc = io.out(info, (size_t)B, &p.info))) return rc;
+  if (!p.y) p.y = p.mw;  // N == 0: never dereferenced, but keep the pointer valid
+
+  // column 0's evidence waits in the handle's workspace (the caller's logpdf has a stride of its own), and so does the factor when
+  // the caller does not want it
+  const size_t lp0_bytes = ((size_t)B * sizeof(double) + 255) & ~(size_t)255;
+  const bool own_T = p.T_post == nullptr && S > 1;
+  if ((rc = h->multi_ws.reserve(h, lp0_bytes + (own_T ? (size_t)B * D * D * sizeof(float) : 0)))) return rc;
+  double* const lp0 = reinterpret_cast<double*>(h->multi_ws.p);
+  if (own_T) { p.T_post = reinterpret_cast<float*>(h->multi_ws.p + lp0_bytes); p.ldt = D; p.strideT = D * D; }
+  p.logpdf = lp0;
+  MultiX16Args m{};
+  m.X = a.X; m.ldx = ldx; m.strideX = strideX; m.Y = p.y; m.ldY = ldY; m.strideY = strideY; m.s = p.s; m.strides = strides;
+  m.mw = p.mw; m.stridemw = stridemw; m.Tf = p.T_post ? p.T_post : p.mw; m.ldt = p.ldt; m.strideT = p.strideT; m.lp0 = lp0; m.info = p.info;
+  m.mw_post = p.mw_post; m.ldmp = ldmp; m.stride_mwpost = stride_mwpost; m.logpdf = lp_d; m.stride_lp = stride_lp;
+  m.D = (int)D; m.N = (int)N; m.S = (int)S;
+  if ((rc = posterior_x16_run(h, xfmt, a, &m))) return rc;
   return io.finish();
 }
 

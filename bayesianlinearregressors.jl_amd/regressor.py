@@ -494,6 +494,9 @@ def logpdf_columns(fx, Y, return_means=False):
     formed once, per column only one GEMM column and two triangular solves remain (blr_logpdf_multi_*).
     ``return_means=True`` also returns the D x S matrix of per-column posterior means."""
     fx = _to_finite_blr(fx)
+    if isinstance(fx.x, _Vecs16):
+        lp, means, _, _ = _columns_x16_many([fx], [np.asarray(Y)], want_posterior=return_means)[0]
+        return (lp, means) if return_means else lp
     blr = fx.f
     dtype = _dtype_of(blr.mw, Y)
     X, layout, ldx, D, N = _x_layout(fx.x, dtype)
@@ -742,6 +745,72 @@ def _fused_x16_many(fbs, ys, want_posterior):
                                     yb, yb.shape[1], _abi.NOISE_ISOTROPIC, sb, sb.shape[1], prior_kind, mwb, D, Lb, ldl, Lb.shape[1],
                                     mw_post, D, Tb, D, D * D, Ab, D, D * D, lp, info)
     return _unpack_many(lp, info, mw_post, Tb, Ab, D)
+
+
+def _columns_x16_many(fbs, Ys, want_posterior):
+    """_columns_many for finite regressors on ColVecs16 / RowVecs16 inputs: equally shaped problems (same D, N, S, layout, format and
+    prior kind) in ONE blr_posterior_multi_batched_x16 call, Y, mw, Lw and the noise variance as float32.  What that entry point does
+    not serve raises ValueError naming the limit, in _fused_x16_many's words; there is no widened fall-back."""
+    if not all(isinstance(fb.x, _Vecs16) for fb in fbs):
+        raise ValueError("16-bit inputs (ColVecs16 / RowVecs16) cannot be mixed with ordinary ColVecs / RowVecs in one map: "
+                         "widen them (x.widen()) or convert the others")
+    dtype = np.float32
+    probs = []
+    for fb, Y in zip(fbs, Ys):
+        X, layout, ldx, D, N = _x16_layout(fb.x)
+        if Y.ndim != 2:
+            raise ValueError("every Y must be an N x S matrix")
+        if Y.shape[0] != N:
+            raise ValueError("length(y) != size(fx.x.X, 2)")  # reference :74
+        if D > 128:
+            raise ValueError(f"16-bit inputs are served for D <= 128, got D = {D}: widen them (x.widen())")
+        s, noise_kind = _noise(fb.Sy, N, dtype)
+        if noise_kind != _abi.NOISE_ISOTROPIC:
+            raise ValueError("16-bit inputs are served for isotropic noise only (a scalar variance): widen them (x.widen())")
+        Lw, prior_kind, ldl = _prior(fb.f.Lw, D, dtype)
+        probs.append((X, layout, ldx, D, N, np.asfortranarray(Y, dtype=dtype), s, fb.x.fmt, _mean_vector(fb.f.mw, D, dtype), Lw,
+                      prior_kind, ldl, isinstance(fb.f.Lw, PDMat)))
+    X0, layout, ldx, D, N, Y0, _, fmt, _, _, prior_kind, ldl, pdmat = probs[0]
+    S = Y0.shape[1]
+    if len({q[4] for q in probs}) != 1:
+        raise ValueError("16-bit inputs are served for equal numbers of observations per regressor (unequal N): "
+                         "widen them (x.widen()) for the ragged route")
+    if len({(q[0].shape, q[0].flags.f_contiguous, q[1], q[3], q[5].shape[1], q[7], q[10], q[12]) for q in probs}) != 1:
+        raise ValueError("16-bit inputs in one map must agree in S, D, layout, format and prior kind")
+    if D == 0:
+        raise ValueError("16-bit inputs need D >= 1")
+    nb = len(probs)
+    lp = np.zeros((nb, S), dtype=np.float64)
+    if S == 0:
+        return [(lp[b], np.empty((D, 0), dtype=dtype) if want_posterior else None, None, None) for b in range(nb)]
+    Xb = X0.reshape(1, -1, order="A") if nb == 1 else np.stack([q[0].reshape(-1, order="A") for q in probs])
+    Yb = np.stack([q[5].reshape(-1, order="F") for q in probs])  # N x S column-major per data set, ldY = N
+    sb = np.stack([q[6] for q in probs])
+    mwb = np.stack([q[8] for q in probs])
+    Lb = np.stack([q[9].reshape(-1, order="A") for q in probs])
+    info = np.zeros(nb, dtype=np.int32)
+    if want_posterior:
+        means = np.empty((nb, D * S), dtype=dtype)
+        Tb = np.empty((nb, D * D), dtype=dtype)
+        Ab = np.empty((nb, D * D), dtype=dtype) if not pdmat else None
+    else:
+        means = Tb = Ab = None
+    _handle().posterior_multi_batched_x16(_abi.X_BF16 if fmt == "bf16" else _abi.X_F16, _abi.MEM_HOST, layout, nb, D, N, S, Xb, ldx,
+                                          Xb.shape[1], Yb, max(N, 1), Yb.shape[1], _abi.NOISE_ISOTROPIC, sb, sb.shape[1], prior_kind,
+                                          mwb, D, Lb, ldl, Lb.shape[1], means, D, D * S, Tb, D, D * D, Ab, D, D * D, lp, S, info)
+    bad = np.flatnonzero(info > 0)
+    if bad.size:
+        e = _abi.PosDefException(int(info[bad[0]]))
+        e.index = int(bad[0])
+        raise e
+    out = []
+    for b in range(nb):
+        if want_posterior:
+            out.append((lp[b], means[b].reshape((D, S), order="F"), Tb[b].reshape((D, D), order="F"),
+                        Ab[b].reshape((D, D), order="F") if Ab is not None else None))
+        else:
+            out.append((lp[b], None, None, None))
+    return out
 
 
 def _unpack_many(lp, info, mw_post, Tb, Ab, D):
@@ -1039,6 +1108,8 @@ def _columns_many(fxs, Ys, want_posterior):
     if any(isinstance(fx.f, BasisFunctionRegressor) and isinstance(fx.f.phi, RandomFourierFeatures) for fx in fxs):
         return loop()
     fbs = [_to_finite_blr(fx) for fx in fxs]
+    if any(isinstance(fb.x, _Vecs16) for fb in fbs):
+        return _columns_x16_many(fbs, Ys, want_posterior)
     dtype = np.float32 if all(_dtype_of(fb.f.mw, Y) == np.float32 for fb, Y in zip(fbs, Ys)) else np.float64
     probs = []
     for fb, Y in zip(fbs, Ys):

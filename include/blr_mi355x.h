@@ -229,6 +229,38 @@ int blr_posterior_batched_x16(blr_handle* h, int memspace, int layout, int xfmt,
                               float* Lw_post, int64_t ldlp, int64_t strideLp,
                               double* logpdf, int32_t* info);
 
+/* ---- S target columns per regressor on 16-bit features: a last layer that feeds several heads ------------------------------------
+ * blr_posterior_multi_batched_f32 for inputs that arrive as bf16 / fp16, without the widened copy and with one pass over X for up to
+ * 63 further columns.  xfmt, X, ldx, strideX: as blr_posterior_batched_x16.  Every other argument has the meaning, strides,
+ * NULL-to-skip rule, overlap / in-place rules and info semantics of blr_posterior_multi_batched_f32: one status per regressor, a
+ * failed regressor gets NaN evidences and keeps its means and factor; T_post = NULL keeps the factor in handle workspace (counted in
+ * blr_get_stat "workspace_bytes"); B = 0 or S = 0 is a no-op; N = 0 gives prior means and evidence 0; S = 1 is
+ * blr_posterior_batched_x16.  Both memspaces, async handles (column 0's status is read on the device); regressors go in chunks of
+ * at most 2^20 or option MAX_CHUNK, one chunk loop around both steps.
+ * Served: 1 <= D <= 128, isotropic noise, every prior kind and prior mean, ColVecs and RowVecs.  Argument errors (return code =
+ * minus the position, and blr_last_error; never a silent widening, and nothing runs): D > 128 (-6), diagonal or dense noise (-15),
+ * an unknown xfmt (-4).
+ * Step 1 is fused_x16_kernel on column 0: column 0's mean and evidence, T_post, Lw_post and info are bit for bit what
+ * blr_posterior_batched_x16 writes for (X, Y[:, 0]).  Step 2 is multi_cols_x16_kernel (csrc/blr_multi_x16.hpp): X streams through
+ * the same LDS ring; the residuals (y_ns - x_n'mw) / sigma^2 are formed in fp32, split exactly into three bf16 pieces and multiplied
+ * with the 16-bit X on v_mfma_f32_16x16x32_bf16 (an fp16 X as two exact bf16 values; lowest x lowest, 2^-24 of |x||r|, dropped):
+ * exact products, fp32 accumulation in a fixed order; q_s and |u_s|^2 in double; K17's solve on the fp32 factor.  The bits of a
+ * column do not depend on B, S, chunking, the column's slot or pass, or the other columns.  Held to the fp32 route's tolerance
+ * (tests/test_x16_multi_gpu.py).
+ * blr_last_route names both instantiations, "fused_x16_kernel<bf16, 8, 2> + multi_cols_x16_kernel<bf16, 8, 2>" (format, 16-row
+ * blocks, loader: as blr_posterior_batched_x16).  Measured (tools/x16_multi_bench.py): see README.md and DESIGN.md K33. */
+int blr_posterior_multi_batched_x16(blr_handle* h, int memspace, int layout, int xfmt,
+                                    int64_t B, int64_t D, int64_t N, int64_t S,
+                                    const void* X, int64_t ldx, int64_t strideX,
+                                    const float* Y, int64_t ldY, int64_t strideY,
+                                    int noise_kind, const float* s, int64_t strides,
+                                    int prior_kind, const float* mw, int64_t stridemw,
+                                    const float* Lw, int64_t ldl, int64_t strideLw,
+                                    float* mw_post, int64_t ldmp, int64_t stride_mwpost,
+                                    float* T_post, int64_t ldt, int64_t strideT,
+                                    float* Lw_post, int64_t ldlp, int64_t strideLp,
+                                    double* logpdf, int64_t stride_lp, int32_t* info);
+
 /* ---- marginals on 16-bit features: the prediction half of the same use ---------------------------------------------------------
  * Replaces reference src/bayesian_linear_regression.jl:33 (mean), :40-43 (var), :47 (mean_and_var) as blr_marginals_batched_f32 does,
  * for inputs that arrive as bf16 / fp16, without the widened copy.  xfmt, X, ldx, strideX: as blr_posterior_batched_x16 (2-byte
