@@ -91,6 +91,9 @@ _SIGS["blr_posterior_multi_batched_x16"] = (  # csrc/blr_multi_x16.hpp
 _SIGS["blr_marginals_batched_x16"] = (  # csrc/blr_marg_x16.hpp
     [_H, _int, _int, _int, _i64, _i64, _i64, _vp, _i64, _i64, _int, _vp, _i64, _int, _vp, _i64, _vp, _i64, _i64,
      _vp, _i64, _vp, _i64, _vp], _int)
+_SIGS["blr_posterior_ragged_x16"] = (  # csrc/blr_ragged_x16.hpp
+    [_H, _int, _int, _int, _i64, _i64, _vp, _vp, _i64, _vp, _int, _vp, _i64, _int, _vp, _i64, _vp, _i64, _i64,
+     _vp, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp], _int)
 for _suf in ("f64", "f32"):
     _SIGS[f"blr_posterior_batched_{_suf}"] = (
         [_H, _int, _int, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _int, _vp, _i64, _int, _vp, _i64, _vp, _i64, _i64,
@@ -291,7 +294,7 @@ class Handle:
     def set_option(self, key, value=None):
         """Run-time switch of this handle (include/blr_mi355x.h blr_set_option); value None = the built-in default.
         MAX_CHUNK = 1..65535 (tests) caps the regressors per chunk / slice of every batched entry point; RAGGED_ITEM = 1..2^30 (tests) forces
-        the observations per work item of marginals_ragged / loo_ragged (rounded up to 64)."""
+        the observations per work item of marginals_ragged / loo_ragged / posterior_ragged_x16 (rounded up to 64)."""
         self.check(self.lib.blr_set_option(self._h, str(key).encode(), None if value is None else str(value).encode()))
 
     def last_route(self):
@@ -377,6 +380,18 @@ class Handle:
         return self.check(fn(self._h, memspace, layout, B, D, _ptr(offsets), _ptr(X), ldx, _ptr(y), noise_kind, _ptr(s), strides,
                              prior_kind, _ptr(mw), stridemw, _ptr(Lw), ldl, strideLw, _ptr(mw_post), stride_mwpost, _ptr(T_post),
                              ldt, strideT, _ptr(Lw_post), ldlp, strideLp, _ptr(logpdf), _ptr(info)))
+
+    def posterior_ragged_x16(self, xfmt, memspace, layout, B, D, offsets, X, ldx, y, noise_kind, s, strides, prior_kind, mw, stridemw,
+                             Lw, ldl, strideLw, mw_post, stride_mwpost, T_post, ldt, strideT, Lw_post, ldlp, strideLp, logpdf, info):
+        """posterior_ragged on 16-bit features: xfmt X_BF16 / X_F16, X of 2-byte elements (ldx in elements), every other array float32;
+        D <= 128, isotropic noise with strides 0 or 1 (include/blr_mi355x.h blr_posterior_ragged_x16)."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        if offsets.shape != (B + 1,):
+            raise ValueError(f"offsets must have B + 1 = {B + 1} entries, got shape {offsets.shape}")
+        return self.check(self.lib.blr_posterior_ragged_x16(
+            self._h, memspace, layout, xfmt, B, D, _ptr(offsets), _ptr(X), ldx, _ptr(y), noise_kind, _ptr(s), strides, prior_kind,
+            _ptr(mw), stridemw, _ptr(Lw), ldl, strideLw, _ptr(mw_post), stride_mwpost, _ptr(T_post), ldt, strideT, _ptr(Lw_post), ldlp,
+            strideLp, _ptr(logpdf), _ptr(info)))
 
     def marginals_ragged(self, dtype, memspace, layout, B, D, offsets, X, ldx, noise_kind, s, strides, prior_kind, mw, stridemw,
                          Lw, ldl, strideLw, mean, var, info):

@@ -50,6 +50,7 @@
 #include "blr_fused_x16.hpp"
 #include "blr_marg_x16.hpp"
 #include "blr_multi_x16.hpp"
+#include "blr_ragged_x16.hpp"
 #include "blr_host.hpp"
 #include "blr_large_plan.hpp"
 
@@ -6350,6 +6351,165 @@ int blr_marginals_batched_x16(blr_handle* h, int memspace, int layout, int xfmt,
   }
   h->route_buf = std::string("marginals_x16_kernel<") + (xfmt == BLR_X_BF16 ? "bf16" : "f16") + ", " + std::to_string(mode) + ">";
   h->route = h->route_buf.c_str();
+  return io.finish();
+}
+
+// The work lists of blr_posterior_ragged_x16, chunk by chunk of plan_ragged's chunks: the regressors of at most W
+// observations, longest first (ragged_x16_kernel); the longer ones, longest first, with the first partial slot of each
+// (ragged_x16_finish_kernel), and their items in that order (ragged_x16_part_kernel).  Slots count from 0 in every chunk.
+struct RaggedX16Lists {
+  struct Range { int64_t whole0, nwhole, cut0, ncut, item0, nitems; };
+  std::vector<int32_t> whole, cut, slot0;
+  std::vector<RaggedX16Item> items;
+  std::vector<Range> chunks;
+  int64_t max_slots = 0;
+};
+static void ragged_x16_lists(const int64_t* offsets, const RaggedPlan& plan, RaggedX16Lists& l) {
+  const auto count = [offsets](int32_t b) { return offsets[b + 1] - offsets[b]; };
+  const auto longer = [&count](int32_t i, int32_t j) { return count(i) > count(j); };
+  for (const RaggedChunk& c : plan.chunks) {
+    RaggedX16Lists::Range r{(int64_t)l.whole.size(), 0, (int64_t)l.cut.size(), 0, (int64_t)l.items.size(), 0};
+    for (int64_t b = c.b0; b < c.b0 + c.nb; ++b) (count((int32_t)b) > plan.W ? l.cut : l.whole).push_back((int32_t)b);
+    std::stable_sort(l.whole.begin() + r.whole0, l.whole.end(), longer);
+    std::stable_sort(l.cut.begin() + r.cut0, l.cut.end(), longer);
+    r.nwhole = (int64_t)l.whole.size() - r.whole0;
+    r.ncut = (int64_t)l.cut.size() - r.cut0;
+    int32_t slot = 0;
+    for (int64_t i = r.cut0; i < r.cut0 + r.ncut; ++i) {
+      const int32_t b = l.cut[(size_t)i];
+      l.slot0.push_back(slot);
+      for (int64_t first = 0; first < count(b); first += plan.W)
+        l.items.push_back(RaggedX16Item{b, (int32_t)first, (int32_t)std::min<int64_t>(plan.W, count(b) - first), slot++});
+    }
+    r.nitems = (int64_t)l.items.size() - r.item0;
+    l.max_slots = std::max<int64_t>(l.max_slots, slot);
+    l.chunks.push_back(r);
+  }
+}
+
+// Regressors with unequal counts on 16-bit features, D <= 128, isotropic noise (blr_ragged_x16.hpp).  Everything but X is fp32 with the
+// meaning it has in blr_posterior_ragged_f32; argument positions are this entry point's own (xfmt is argument 4).
+int blr_posterior_ragged_x16(blr_handle* h, int memspace, int layout, int xfmt, int64_t B, int64_t D, const int64_t* offsets,
+                             const void* X, int64_t ldx, const float* y, int noise_kind, const float* s, int64_t strides, int prior_kind,
+                             const float* mw, int64_t stridemw, const float* Lw, int64_t ldl, int64_t strideLw, float* mw_post,
+                             int64_t stride_mwpost, float* T_post, int64_t ldt, int64_t strideT, float* Lw_post, int64_t ldlp,
+                             int64_t strideLp, double* logpdf, int32_t* info) {
+  RaggedFront f;
+  int rc = ragged_front(h, f, memspace, layout, B, D, offsets, static_cast<const float*>(X), ldx, noise_kind, strides);
+  if (rc < -3) {  // positions behind `layout` are one further here: re-number, keep the reason
+    const size_t colon = h ? h->err.find(": ") : std::string::npos;
+    const std::string why = !h ? std::string() : (colon == std::string::npos ? h->err : h->err.substr(colon + 2));
+    return bad_arg(h, -rc + 1, why.c_str());
+  }
+  if (rc < 0) return rc;
+  if (xfmt != BLR_X_BF16 && xfmt != BLR_X_F16) return bad_arg(h, 4, "unknown xfmt (BLR_X_BF16 or BLR_X_F16)");
+  if (D > kMaxSmallD) return bad_arg(h, 6, "D > 128 is not served on 16-bit features (widen them and call blr_posterior_ragged_f32)");
+  if (f.any && !y) return bad_arg(h, 10, "y is NULL (reference :74 length check)");
+  if (noise_kind != BLR_NOISE_ISOTROPIC)
+    return bad_arg(h, 11, "only isotropic noise is served on 16-bit features (widen them and call blr_posterior_ragged_f32)");
+  if (!s) return bad_arg(h, 12, "s is NULL");
+  if (strides != 0 && strides != 1) return bad_arg(h, 13, "strides (0: one variance for all regressors, 1: one per regressor)");
+  if (prior_kind != BLR_PRIOR_DENSE && prior_kind != BLR_PRIOR_UPPER_FACTOR && prior_kind != BLR_PRIOR_DIAGONAL)
+    return bad_arg(h, 14, "prior_kind");
+  if (!mw) return bad_arg(h, 15, "mw is NULL");
+  if (stridemw < 0) return bad_arg(h, 16, "stridemw < 0");
+  if (!Lw) return bad_arg(h, 17, "Lw is NULL");
+  if (prior_kind != BLR_PRIOR_DIAGONAL && ldl < D) return bad_arg(h, 18, "ldl < D");
+  if (strideLw < 0) return bad_arg(h, 19, "strideLw < 0");
+  if (mw_post && B > 1 && stride_mwpost < D) return bad_arg(h, 21, "stride_mwpost < D");
+  if (T_post && ldt < D) return bad_arg(h, 23, "ldt < D");
+  if (T_post && B > 1 && strideT < (int64_t)mat_extent(D, D, ldt)) return bad_arg(h, 24, "strideT too small");
+  if (Lw_post && ldlp < D) return bad_arg(h, 26, "ldlp < D");
+  if (Lw_post && B > 1 && strideLp < (int64_t)mat_extent(D, D, ldlp)) return bad_arg(h, 27, "strideLp too small");
+  if (B > 0 && !info) return bad_arg(h, 29, "info is NULL");
+  if (B == 0) return 0;
+  if (!h) return -1;
+  HIP_TRY(h, hipSetDevice(h->device));
+  RaggedX16Args a{};
+  PosteriorArgs<float>& p = a.p;
+  p.ldx = ldx; p.strides = strides; p.stridemw = stridemw; p.ldl = ldl; p.strideLw = strideLw;
+  p.stride_mwpost = stride_mwpost; p.ldt = ldt; p.strideT = strideT; p.ldlp = ldlp; p.strideLp = strideLp;
+  p.layout = layout; p.noise_kind = noise_kind; p.prior_kind = prior_kind;
+  p.D = (int)D; p.B = (int)B;
+
+  CallIO io(h, memspace);
+  const size_t lw_one = prior_kind == BLR_PRIOR_DIAGONAL ? (size_t)D : mat_extent(D, D, ldl);
+  if ((rc = io.in(static_cast<const unsigned short*>(X), f.x_all, &a.X))) return rc;
+  if ((rc = io.in(y, f.n_all, &p.y))) return rc;
+  if ((rc = io.in(s, extent(B, strides, 1), &p.s))) return rc;
+  if ((rc = io.in(mw, extent(B, stridemw, (size_t)D), &p.mw))) return rc;
+  if ((rc = io.in(Lw, extent(B, strideLw, lw_one), &p.Lw))) return rc;
+  if ((rc = io.out(mw_post, extent(B, stride_mwpost, (size_t)D), &p.mw_post))) return rc;
+  if ((rc = io.out(T_post, extent(B, strideT, mat_extent(D, D, ldt)), &p.T_post))) return rc;
+  if ((rc = io.out(Lw_post, extent(B, strideLp, mat_extent(D, D, ldlp)), &p.Lw_post))) return rc;
+  if ((rc = io.out(logpdf, (size_t)B, &p.logpdf))) return rc;
+  if ((rc = io.out(info, (size_t)B, &p.info))) return rc;
+  // no data at all (or, host memspace, nothing staged): the kernels never dereference these, but keep the pointers valid
+  if (!a.X) a.X = reinterpret_cast<const unsigned short*>(p.mw);
+  if (!p.y) p.y = p.mw;
+
+  // loader: the equal-count dispatch's rule on the call's X; a RowVecs slice adds its own offset (blr_ragged_x16.hpp)
+  const bool rowv = layout == BLR_LAYOUT_ROWVECS;
+  a.dma_ok = (!h->opt.no_ldsdma && ((uintptr_t)a.X % 16) == 0 && ldx % 8 == 0 && (rowv || D % 8 == 0)) ? 1 : 0;
+  const int NB = 2 * (int)((D + 31) / 32);  // even block counts only: the padding rows are zero in LDS
+  const size_t packed = ragged_x16_packed_elems(NB);
+  // a chunk's partials stay within 256 MiB per buffer: a cut regressor of n observations has at most 2 n / W items
+  RaggedPlan plan;
+  const int64_t max_slots = std::max<int64_t>(1, kRaggedImageBytes / (int64_t)(packed * sizeof(float)));
+  plan_ragged(offsets, B, h->cus, (int)sizeof(float), h->opt, plan, max_slots * ragged_item_size(offsets, B, h->cus, h->opt) / 2);
+  a.W = (int32_t)plan.W;
+  RaggedX16Lists l;
+  ragged_x16_lists(offsets, plan, l);
+  const bool any_whole = !l.whole.empty(), any_cut = !l.cut.empty();
+
+  const void* kern[3];
+  for (int which = 0; which < 3; ++which) {
+    kern[which] = ragged_x16_kernel_ptr(which, xfmt, NB, rowv);
+    if (kern[which] == nullptr) return hip_fail(h, hipErrorInvalidValue, "this build lacks the requested form of ragged_x16_kernel");
+    if ((which == 0 ? any_whole : any_cut) && (rc = set_lds_once(h, kern[which], ragged_x16_kernel_lds(which, NB)))) return rc;
+  }
+  if (any_cut) {
+    Carve carve;
+    const size_t slots = (size_t)l.max_slots;
+    const size_t o_g = carve(slots * packed * sizeof(float)), o_b = carve(slots * 16 * NB * sizeof(double)), o_q = carve(slots * sizeof(double));
+    if ((rc = h->loo_ws.reserve(h, carve.off))) return rc;
+    a.partG = reinterpret_cast<float*>(h->loo_ws.p + o_g);
+    a.partB = reinterpret_cast<double*>(h->loo_ws.p + o_b);
+    a.partQ = reinterpret_cast<double*>(h->loo_ws.p + o_q);
+  }
+  const char* dev[5];
+  if ((rc = ragged_meta_upload(h, {{offsets, ragged_table_bytes(B)}, {l.items.data(), l.items.size() * sizeof(RaggedX16Item)},
+                                   {l.whole.data(), l.whole.size() * sizeof(int32_t)}, {l.cut.data(), l.cut.size() * sizeof(int32_t)},
+                                   {l.slot0.data(), l.slot0.size() * sizeof(int32_t)}}, dev)))
+    return rc;
+  a.offsets = reinterpret_cast<const int64_t*>(dev[0]);
+  const RaggedX16Item* const items = reinterpret_cast<const RaggedX16Item*>(dev[1]);
+  const int32_t* const whole = reinterpret_cast<const int32_t*>(dev[2]);
+  const int32_t* const cut = reinterpret_cast<const int32_t*>(dev[3]);
+  const int32_t* const slot0 = reinterpret_cast<const int32_t*>(dev[4]);
+  // per chunk: the items of the long regressors first, their sums behind them, then the whole regressors.  (The partials of a chunk
+  // are read by its finish launch before the next chunk's items overwrite them: one stream, in order)
+  for (const RaggedX16Lists::Range& c : l.chunks) {
+    if (c.ncut > 0) {
+      a.items = items + c.item0; a.nwork = (int32_t)c.nitems;
+      ragged_x16_kernel_launch(1, xfmt, NB, rowv, (unsigned)c.nitems, h->stream, a);
+      HIP_TRY(h, hipGetLastError());
+      a.order = cut + c.cut0; a.slot0 = slot0 + c.cut0; a.nwork = (int32_t)c.ncut;
+      ragged_x16_kernel_launch(2, xfmt, NB, rowv, (unsigned)c.ncut, h->stream, a);
+      HIP_TRY(h, hipGetLastError());
+    }
+    if (c.nwhole > 0) {
+      a.order = whole + c.whole0; a.nwork = (int32_t)c.nwhole;
+      ragged_x16_kernel_launch(0, xfmt, NB, rowv, (unsigned)c.nwhole, h->stream, a);
+      HIP_TRY(h, hipGetLastError());
+    }
+  }
+  h->last_chunks = std::max<int64_t>(1, plan.last_chunks);
+  const std::string inst = std::string("<") + (xfmt == BLR_X_BF16 ? "bf16" : "f16") + ", " + std::to_string(NB) + ", " + (rowv ? "row" : "col") + ">";
+  h->route_buf = any_whole ? "ragged_x16_kernel" + inst : std::string();
+  if (any_cut) h->route_buf += (any_whole ? " + " : "") + ("ragged_x16_part_kernel" + inst) + " + ragged_x16_finish_kernel<" + std::to_string(NB) + ">";
+  h->route = h->route_buf.c_str();
+  h->route_i8_B = 0;
   return io.finish();
 }
 

@@ -829,9 +829,11 @@ def _unpack_many(lp, info, mw_post, Tb, Ab, D):
     return out
 
 
-def _ragged_operands(f, x, offsets, Sy, y):
+def _ragged_operands(f, x, offsets, Sy, y, allow16=False):
     """The packed arguments every ragged entry point shares, as the library wants them (``y`` None: a call without targets; ``Sy``
-    None: a call that does not read the noise) -> None for an empty batch."""
+    None: a call that does not read the noise) -> None for an empty batch.  ``allow16``: ColVecs16 / RowVecs16 inputs are taken as
+    they are, everything else as float32 (blr_posterior_ragged_x16); what that entry point does not serve raises ValueError naming
+    the limit, in _fused_x16_many's words."""
     offsets = np.ascontiguousarray(offsets, dtype=np.int64)
     if offsets.ndim != 1 or offsets.shape[0] < 1:
         raise ValueError("offsets must be a vector of B + 1 entries")
@@ -841,10 +843,15 @@ def _ragged_operands(f, x, offsets, Sy, y):
         raise ValueError("f must be one BayesianLinearRegressor or B = len(offsets) - 1 of them")
     if nb == 0:
         return None, fs
-    dtype = np.float32 if all(_dtype_of(g.mw, y if y is not None else g.mw) == np.float32 for g in fs) else np.float64
-    X, layout, ldx, D, N = _x_layout(x, dtype)
+    x16 = allow16 and isinstance(x, _Vecs16)
+    dtype = np.float32 if x16 or all(_dtype_of(g.mw, y if y is not None else g.mw) == np.float32 for g in fs) else np.float64
+    X, layout, ldx, D, N = _x16_layout(x) if x16 else _x_layout(x, dtype)
     if N != total:
         raise ValueError("offsets[-1] != number of inputs")
+    if x16 and D > 128:
+        raise ValueError(f"16-bit inputs are served for D <= 128, got D = {D}: widen them (x.widen())")
+    if x16 and D == 0:
+        raise ValueError("16-bit inputs need D >= 1")
     if y is not None:
         y = np.ascontiguousarray(y, dtype=dtype)
         if y.ndim != 1 or y.shape[0] != N:
@@ -859,6 +866,9 @@ def _ragged_operands(f, x, offsets, Sy, y):
             s, noise_kind = np.ascontiguousarray(Sy), _abi.NOISE_ISOTROPIC
         else:
             s, noise_kind = _noise(Sy, N, dtype)
+    if x16 and noise_kind != _abi.NOISE_ISOTROPIC:
+        raise ValueError("16-bit inputs are served for isotropic noise only (a scalar variance, or one per regressor): "
+                         "widen them (x.widen())")
     if noise_kind == _abi.NOISE_DENSE:
         raise ValueError("a dense noise covariance is not supported for packed regressors")
     shared = isinstance(f, BayesianLinearRegressor)
@@ -875,8 +885,9 @@ def _ragged_operands(f, x, offsets, Sy, y):
 
 
 def _ragged_packed(f, x, offsets, Sy, y, want_posterior):
-    """The packed form behind posterior_ragged / logpdf_ragged -> ([(logpdf, mw', T, A)], the B prior regressors)."""
-    ops, fs = _ragged_operands(f, x, offsets, Sy, y)
+    """The packed form behind posterior_ragged / logpdf_ragged -> ([(logpdf, mw', T, A)], the B prior regressors).  ColVecs16 /
+    RowVecs16 inputs go to blr_posterior_ragged_x16 as they are; there is no widened fall-back."""
+    ops, fs = _ragged_operands(f, x, offsets, Sy, y, allow16=True)
     if ops is None:
         return [], fs
     dtype, offsets, nb, X, layout, ldx, D, y, s, noise_kind, strides, prior_kind, ldl, pdmat, mwb, stridemw, Lb, strideLw = ops
@@ -888,9 +899,14 @@ def _ragged_packed(f, x, offsets, Sy, y, want_posterior):
         Ab = np.empty((nb, D * D), dtype=dtype) if not pdmat else None
     else:
         mw_post = Tb = Ab = None
-    _handle().posterior_ragged(dtype, _abi.MEM_HOST, layout, nb, D, offsets, X, ldx, y, noise_kind, s, strides,
-                               prior_kind, mwb, stridemw, Lb, ldl, strideLw, mw_post, D, Tb, D, D * D, Ab, D,
-                               D * D, lp, info)
+    if isinstance(x, _Vecs16):
+        _handle().posterior_ragged_x16(_abi.X_BF16 if x.fmt == "bf16" else _abi.X_F16, _abi.MEM_HOST, layout, nb, D, offsets, X, ldx, y,
+                                       noise_kind, s, strides, prior_kind, mwb, stridemw, Lb, ldl, strideLw, mw_post, D, Tb, D, D * D,
+                                       Ab, D, D * D, lp, info)
+    else:
+        _handle().posterior_ragged(dtype, _abi.MEM_HOST, layout, nb, D, offsets, X, ldx, y, noise_kind, s, strides,
+                                   prior_kind, mwb, stridemw, Lb, ldl, strideLw, mw_post, D, Tb, D, D * D, Ab, D,
+                                   D * D, lp, info)
     return _unpack_many(lp, info, mw_post, Tb, Ab, D), fs
 
 
@@ -899,7 +915,8 @@ def logpdf_ragged(f, x, offsets, Sy, y):
     of y ``offsets[b]:offsets[b+1]`` (reference :55-58 under a map over fxs of different lengths), one library call.
     ``f``: one BayesianLinearRegressor shared by all, or B of them with one kind of prior precision.  ``Sy``: a scalar (one
     variance for all), a vector of B variances (one per regressor), or a vector / Diagonal of ``offsets[-1]``
-    per-observation variances (a plain vector whose length equals both is read per observation)."""
+    per-observation variances (a plain vector whose length equals both is read per observation).  ``x`` as ColVecs16 / RowVecs16
+    (D <= 128; a scalar variance or one per regressor) is one blr_posterior_ragged_x16 call on the 16-bit features as they are."""
     return np.array([r[0] for r in _ragged_packed(f, x, offsets, Sy, y, want_posterior=False)[0]])
 
 

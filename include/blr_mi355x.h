@@ -341,6 +341,46 @@ int blr_posterior_ragged_f32(blr_handle* h, int memspace, int layout, int64_t B,
                              float* Lw_post, int64_t ldlp, int64_t strideLp,
                              double* logpdf, int32_t* info);
 
+/* ---- regressors with UNEQUAL observation counts on 16-bit features (bf16 / fp16) ------------------------------------------------
+ * blr_posterior_ragged_f32 for inputs that arrive as bf16 / fp16 -- one regressor per user, arm or task behind a 16-bit last layer --
+ * without the widened copy, without padding to the longest regressor and without a loop of B = 1 calls.  offsets, the packing of X
+ * and y and the order handling are those of blr_posterior_ragged_f32 (offsets: ALWAYS a host array of B + 1 entries; N_b = 0 gives the
+ * prior mean and evidence 0; B = 0 is a no-op); xfmt, the 2-byte elements of X (ldx counts elements, any ldx, any 2-byte-aligned base)
+ * and both memspaces are those of blr_posterior_batched_x16.  From prior_kind on, the arguments are blr_posterior_ragged_f32's,
+ * unchanged: strides, NULL-to-skip rule, in-place rule, info semantics (a failed regressor -- non-positive variance, a prior that does
+ * not factor, a failed Cholesky -- gets its info and a NaN evidence and keeps mw_post / T_post; the others are unaffected).
+ * Served: 1 <= D <= 128, every N_b >= 0, isotropic noise -- s + b*strides with strides = 0 (one variance for all) or 1 (one per
+ * regressor) --, every prior kind and prior mean, ColVecs and RowVecs.  Argument errors (return code = minus the position, and
+ * blr_last_error; never a silent widening, nothing runs, no output is touched): an unknown xfmt (-4), D > 128 (-6), bad offsets (-7),
+ * diagonal or dense noise (-11), strides other than 0 or 1 (-13).
+ * Regressors go in chunks bounded as blr_marginals_ragged_* bounds them (65535, option MAX_CHUNK) and by the partials below, 256 MiB
+ * per buffer (blr_get_stat "last_chunks").  W = about one round of resident workgroups over the call's observations, at least 256, a
+ * multiple of 64 (option RAGGED_ITEM forces it): the item size of blr_marginals_ragged_*.
+ * N_b <= W: ragged_x16_kernel (csrc/blr_ragged_x16.hpp), one workgroup per regressor, longest first: fused_x16_kernel's phases on the
+ * regressor's slice.  The loader is chosen per regressor by blr_posterior_batched_x16's rule on its slice (a RowVecs slice is 16-byte
+ * aligned only when offsets[b] % 8 == 0).  Every output of such a regressor is bit for bit that of blr_posterior_batched_x16 with
+ * B = 1 on its slice: independent of B, of the other regressors and of the order.
+ * N_b > W: the regressor is cut into items of W observations, one workgroup each (ragged_x16_part_kernel): the raw fp32 Gram matrix
+ * of the item, X r in double (r = y - X'mw formed directly) and sum r^2 in double go to handle workspace (counted in blr_get_stat
+ * "workspace_bytes").  ragged_x16_finish_kernel, one workgroup per cut regressor, sums them in item order in double, rounds the Gram
+ * matrix to fp32 once, applies 1 / sigma^2 and the prior and runs the fp32 route's factorisation, solve and evidence.  The bits of a
+ * cut regressor are a function of its slice and W alone -- not of B, the chunking, the other regressors or the handle's history --
+ * and need not equal the B = 1 bits.  Held to the fp32 route's tolerance (tests/test_x16_ragged_gpu.py).
+ * Async handle, device memspace: the upload of offsets and the work lists drains the handle's stream first, as
+ * blr_posterior_ragged_* does.  blr_last_route names what ran, "ragged_x16_kernel<bf16, 8, col> + ragged_x16_part_kernel<bf16, 8,
+ * col> + ragged_x16_finish_kernel<8>" (format, 16-row blocks, layout), without the halves that had no work.
+ * Measured (tools/x16_ragged_bench.py, profiles/x16_ragged_bench.json): see README.md and DESIGN.md K34. */
+int blr_posterior_ragged_x16(blr_handle* h, int memspace, int layout, int xfmt, int64_t B, int64_t D,
+                             const int64_t* offsets, /* HOST array of B + 1 entries in both memspaces */
+                             const void* X, int64_t ldx, const float* y,
+                             int noise_kind, const float* s, int64_t strides,
+                             int prior_kind, const float* mw, int64_t stridemw,
+                             const float* Lw, int64_t ldl, int64_t strideLw,
+                             float* mw_post, int64_t stride_mwpost,
+                             float* T_post, int64_t ldt, int64_t strideT,
+                             float* Lw_post, int64_t ldlp, int64_t strideLp,
+                             double* logpdf, int32_t* info);
+
 /* ---- marginals of regressors with UNEQUAL observation counts in one call ------------------------------------------------------
  * Replaces: reference src/bayesian_linear_regression.jl:33 (mean), :40-43 (var) and :47 (mean_and_var) under a map over fxs of
  * different lengths -- which blr_marginals_batched_* (one N for the batch) serves only by a loop of calls or by padding every
