@@ -91,6 +91,9 @@ _SIGS["blr_posterior_multi_batched_x16"] = (  # csrc/blr_multi_x16.hpp
 _SIGS["blr_marginals_batched_x16"] = (  # csrc/blr_marg_x16.hpp
     [_H, _int, _int, _int, _i64, _i64, _i64, _vp, _i64, _i64, _int, _vp, _i64, _int, _vp, _i64, _vp, _i64, _i64,
      _vp, _i64, _vp, _i64, _vp], _int)
+_SIGS["blr_loo_batched_x16"] = (  # csrc/blr_loo_x16.hpp
+    [_H, _int, _int, _int, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _int, _vp, _i64, _vp, _i64, _vp, _i64, _i64,
+     _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp], _int)
 _SIGS["blr_posterior_ragged_x16"] = (  # csrc/blr_ragged_x16.hpp
     [_H, _int, _int, _int, _i64, _i64, _vp, _vp, _i64, _vp, _int, _vp, _i64, _int, _vp, _i64, _vp, _i64, _i64,
      _vp, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp], _int)
@@ -533,6 +536,15 @@ class Handle:
         return self.check(fn(self._h, memspace, layout, B, D, N, _ptr(X), ldx, strideX, _ptr(y), stridey, noise_kind, _ptr(s),
                              strides, _ptr(mw), stridemw, _ptr(T), ldt, strideT, _ptr(loo_mean), stride_lm, _ptr(loo_var),
                              stride_lv, _ptr(loo_logpdf), stride_ll, _ptr(loo_total), _ptr(info)))
+
+    def loo_batched_x16(self, xfmt, memspace, layout, B, D, N, X, ldx, strideX, y, stridey, noise_kind, s, strides, mw, stridemw, T, ldt,
+                        strideT, loo_mean, stride_lm, loo_var, stride_lv, loo_logpdf, stride_ll, loo_total, info):
+        """loo on 16-bit features: xfmt X_BF16 / X_F16, X of 2-byte elements (ldx, strideX in elements), every other array float32
+        (loo_logpdf, loo_total float64); D <= 128, isotropic or diagonal noise (include/blr_mi355x.h blr_loo_batched_x16)."""
+        return self.check(self.lib.blr_loo_batched_x16(
+            self._h, memspace, layout, xfmt, B, D, N, _ptr(X), ldx, strideX, _ptr(y), stridey, noise_kind, _ptr(s), strides, _ptr(mw),
+            stridemw, _ptr(T), ldt, strideT, _ptr(loo_mean), stride_lm, _ptr(loo_var), stride_lv, _ptr(loo_logpdf), stride_ll,
+            _ptr(loo_total), _ptr(info)))
 
     def kfold(self, dtype, memspace, layout, B, D, N, F, X, ldx, strideX, y, stridey, noise_kind, s, strides, mw, stridemw, T, ldt,
               strideT, kf_mean, stride_km, kf_var, stride_kv, kf_logpdf, stride_kl, kf_total, info):

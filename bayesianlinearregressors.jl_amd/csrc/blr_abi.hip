@@ -49,6 +49,7 @@
 #define BLR_X16_DECLS_ONLY
 #include "blr_fused_x16.hpp"
 #include "blr_marg_x16.hpp"
+#include "blr_loo_x16.hpp"
 #include "blr_multi_x16.hpp"
 #include "blr_ragged_x16.hpp"
 #include "blr_host.hpp"
@@ -6351,6 +6352,116 @@ int blr_marginals_batched_x16(blr_handle* h, int memspace, int layout, int xfmt,
   }
   h->route_buf = std::string("marginals_x16_kernel<") + (xfmt == BLR_X_BF16 ? "bf16" : "f16") + ", " + std::to_string(mode) + ">";
   h->route = h->route_buf.c_str();
+  return io.finish();
+}
+
+// Exact leave-one-out on 16-bit features, D <= 128 (blr_loo_x16.hpp): per chunk of regressors the status
+// (loo_check_kernel<float>), the fp32 triangular inverse of T (marg_image_kernel<float>), its planes (marg_planes_x16_kernel), the paired
+// product stream with the epilogue at its store (loo_x16_kernel) and the fixed-order totals.  Everything but X is fp32 with the meaning
+// it has in blr_loo_batched_f32; argument positions are this entry point's own (xfmt is argument 4).  Images and planes of a chunk sit
+// in the handle's side buffer as blr_marginals_batched_x16 lays them out: 96 KiB per regressor, a chunk within 256 MiB.
+int blr_loo_batched_x16(blr_handle* h, int memspace, int layout, int xfmt, int64_t B, int64_t D, int64_t N, const void* X, int64_t ldx,
+                        int64_t strideX, const float* y, int64_t stridey, int noise_kind, const float* s, int64_t strides, const float* mw,
+                        int64_t stridemw, const float* Tf, int64_t ldt, int64_t strideT, float* loo_mean, int64_t stride_lm, float* loo_var,
+                        int64_t stride_lv, double* loo_logpdf, int64_t stride_ll, double* loo_total, int32_t* info) {
+  using XC = MargX16Cfg;
+  using G = MargGemmCfg<float>;
+  // (the argument checks come before the handle's: they need no device)
+  if (h) h->err.clear();
+  if (memspace != BLR_MEM_HOST && memspace != BLR_MEM_DEVICE) return bad_arg(h, 2, "memspace");
+  if (layout != BLR_LAYOUT_COLVECS && layout != BLR_LAYOUT_ROWVECS) return bad_arg(h, 3, "unknown layout (reference :26-31)");
+  if (xfmt != BLR_X_BF16 && xfmt != BLR_X_F16) return bad_arg(h, 4, "unknown xfmt (BLR_X_BF16 or BLR_X_F16)");
+  if (B < 0 || B > (1 << 30)) return bad_arg(h, 5, "B out of range (0..2^30)");
+  if (D < 1) return bad_arg(h, 6, "D < 1");
+  if (D > kMaxSmallD) return bad_arg(h, 6, "D > 128 is not served on 16-bit features (widen them and call blr_loo_batched_f32)");
+  if (N < 0 || N > (1 << 30)) return bad_arg(h, 7, "N out of range (0..2^30)");
+  if (N > 0 && !X) return bad_arg(h, 8, "X is NULL");
+  if (layout == BLR_LAYOUT_COLVECS ? ldx < D : ldx < std::max<int64_t>(N, 1)) return bad_arg(h, 9, "ldx too small");
+  if (strideX < 0) return bad_arg(h, 10, "strideX < 0");
+  if (N > 0 && !y) return bad_arg(h, 11, "y is NULL (reference :74 length check)");
+  if (stridey < 0) return bad_arg(h, 12, "stridey < 0");
+  if (noise_kind != BLR_NOISE_ISOTROPIC && noise_kind != BLR_NOISE_DIAGONAL)
+    return bad_arg(h, 13, "noise_kind (dense noise has no single-observation LOO: that is a block LOO)");
+  if (N > 0 && !s) return bad_arg(h, 14, "s is NULL");
+  if (strides < 0) return bad_arg(h, 15, "strides < 0");
+  if (!mw) return bad_arg(h, 16, "mw is NULL");
+  if (B > 1 && stridemw < D) return bad_arg(h, 17, "stridemw < D");
+  if (!Tf) return bad_arg(h, 18, "T is NULL");
+  if (ldt < D) return bad_arg(h, 19, "ldt < D");
+  if (B > 1 && strideT < (int64_t)mat_extent(D, D, ldt)) return bad_arg(h, 20, "strideT too small");
+  if (loo_mean && B > 1 && stride_lm < N) return bad_arg(h, 22, "stride_lm < N");
+  if (loo_var && B > 1 && stride_lv < N) return bad_arg(h, 24, "stride_lv < N");
+  if (loo_logpdf && B > 1 && stride_ll < N) return bad_arg(h, 26, "stride_ll < N");
+  if (!info) return bad_arg(h, 28, "info is NULL");
+  if (!h) return -1;
+  h->last_chunks = 1;
+  if (B == 0) return 0;
+  HIP_TRY(h, hipSetDevice(h->device));
+
+  LooX16Args a{};
+  LooArgs<float>& l = a.l;
+  a.ldx = ldx; a.strideX = strideX; a.stridemw = stridemw; a.D = (int)D;
+  l.stridey = stridey; l.strides = strides; l.noise_kind = noise_kind; l.stride_lm = stride_lm; l.stride_lv = stride_lv;
+  l.stride_ll = stride_ll; l.N = (int)N;
+  CallIO io(h, memspace);
+  int rc;
+  const float* dT = nullptr;
+  double* dtot = nullptr;
+  int32_t* dinfo = nullptr;
+  // (at N = 0 nothing of X, y and s is read)
+  const size_t x_one = N == 0 ? 0 : (layout == BLR_LAYOUT_COLVECS ? mat_extent(D, N, ldx) : mat_extent(N, D, ldx));
+  const size_t s_one = N == 0 ? 0 : (noise_kind == BLR_NOISE_DIAGONAL ? (size_t)N : 1);
+  if ((rc = io.in(static_cast<const unsigned short*>(X), x_one ? extent(B, strideX, x_one) : 0, &a.X))) return rc;
+  if ((rc = io.in(y, N ? extent(B, stridey, (size_t)N) : 0, &l.y))) return rc;
+  if ((rc = io.in(s, s_one ? extent(B, strides, s_one) : 0, &l.s))) return rc;
+  if ((rc = io.in(mw, extent(B, stridemw, (size_t)D), &a.mw))) return rc;
+  if ((rc = io.in(Tf, extent(B, strideT, mat_extent(D, D, ldt)), &dT))) return rc;
+  if ((rc = heldout_stage_out<float>(io, B, N, 1, N, {loo_mean, N, stride_lm, &l.lm}, {loo_var, 0, stride_lv, &l.lv},
+                                     {loo_logpdf, N, stride_ll, &l.ll}, {loo_total, 0, 1, &dtot}, info, &dinfo))) return rc;
+  l.info = dinfo;
+  if ((rc = ensure_stats(h))) return rc;
+  l.degenerate = h->stats_dev + 3;
+  const int64_t ychunk = heldout_status<float>(h, B, D, N, dT, ldt, strideT, l.s, strides, noise_kind, dinfo);
+  HIP_TRY(h, hipGetLastError());
+
+  // loader: blr_marginals_batched_x16's rule
+  const bool rowv = layout == BLR_LAYOUT_ROWVECS;
+  const bool al16 = ((uintptr_t)a.X % 16) == 0 && ldx % 8 == 0 && (B == 1 || strideX % 8 == 0);
+  const int mode = ((al16 && (rowv || D % 8 == 0)) ? 2 : 0) + (rowv ? 1 : 0);
+  const size_t lds = (size_t)XC::lds_bytes(rowv, true);
+  const LogpdfSpill spill(dtot, l.ll, N);
+  constexpr int64_t kImg32 = G::IMG_ELEMS * (int64_t)sizeof(float), kPerReg = kImg32 + XC::IMG_BYTES;
+  int64_t chunk = std::min<int64_t>(std::min<int64_t>(B, 65535), ((int64_t)256 << 20) / kPerReg);
+  if (spill.per) chunk = std::max<int64_t>(1, std::min<int64_t>(chunk, (int64_t)(kLooWorkspace / spill.per)));
+  chunk = h->cap_chunk(chunk);
+  if (N > 0) {
+    if ((rc = set_lds_once(h, loo_x16_kernel_ptr(xfmt, mode), lds))) return rc;
+    if ((rc = h->aux.reserve(h, (size_t)(chunk * kPerReg)))) return rc;
+    if ((rc = MargImages<float>::reserve(h, chunk))) return rc;  // (the buffer is there: marg_image_kernel's LDS limit)
+    if (spill.on && (rc = h->loo_ws.reserve(h, (size_t)chunk * spill.per))) return rc;
+  }
+  const int64_t ntiles = (N + 15) / 16;
+  for (int64_t b0 = 0; N > 0 && b0 < B; b0 += chunk) {
+    const int64_t nb = std::min<int64_t>(chunk, B - b0);
+    LooX16Args c = a;
+    if (spill.on) { c.l.ll = spill.rows(h->loo_ws.p, b0); c.l.stride_ll = spill.ld; }
+    const float* const img32 = MargImages<float>::launch(h, dT, ldt, strideT, (int)D, dinfo, b0, nb);
+    char* const img16 = h->aux.p + chunk * kImg32 - b0 * XC::IMG_BYTES;
+    marg_x16_planes_launch(img32, img16, dinfo, (int)D, (int)b0, (unsigned)nb, h->stream);
+    c.img = img16;
+    c.reg0 = (int)b0;
+    // every workgroup copies up to 60 KiB of planes: at least four tiles per wave (as blr_marginals_batched_x16)
+    loo_x16_launch(xfmt, mode, (unsigned)tile_groups(h, (ntiles + 15) / 16, nb), (unsigned)nb, lds, h->stream, c);
+    if (dtot) heldout_totals(h, b0, nb, c.l.ll, c.l.stride_ll, N, dtot, dinfo);
+    HIP_TRY(h, hipGetLastError());
+  }
+  h->count_chunks(B, N > 0 ? chunk : ychunk);
+  if (N > 0) {
+    h->route_buf = std::string("marg_image_kernel<float> + loo_x16_kernel<") + (xfmt == BLR_X_BF16 ? "bf16" : "f16") + ", " + std::to_string(mode) + ">";
+    h->route = h->route_buf.c_str();
+  } else if (dtot && (rc = heldout_empty_totals(h, B, ychunk, false, 1, dtot, 1, dinfo))) {
+    return rc;
+  }
   return io.finish();
 }
 

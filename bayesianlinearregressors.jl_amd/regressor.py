@@ -1483,6 +1483,8 @@ def _heldout_map(fxs, targets, row, what, F=None, check=None):
         raise ValueError(f"as many {'observation vectors' if row.rank == 1 else 'target matrices'} as finite regressors are needed")
     if not fxs:
         return []
+    if row is _HELDOUT["loo"] and any(isinstance(fx.x, _Vecs16) for fx in fxs):
+        return _loo_x16_many([_to_finite_blr(fx) for fx in fxs], targets)
     dtype = np.float32 if all(_heldout_dtype(fx, t) == np.float32 for fx, t in zip(fxs, targets)) else np.float64
     probs = [_heldout_problem(fx, t, dtype, what, row.rank) for fx, t in zip(fxs, targets)]
     for q in probs if check is not None else ():
@@ -1494,6 +1496,73 @@ def _heldout_map(fxs, targets, row, what, F=None, check=None):
     for i, q in enumerate(probs):
         try:
             out.append(_heldout_batch([q], dtype, row, F)[0])
+        except _abi.PosDefException as e:
+            e.index = i
+            raise
+    return out
+
+
+def _loo_x16_batch(probs):
+    """Equally shaped `_loo_x16_many` records: X, y, s, mw and Lw staged once, blr_posterior_batched_x16 into device (mw', T), then
+    blr_loo_batched_x16 on the same device X.  Nothing D x D comes back to the host."""
+    X0, layout, ldx, D, N, _, _, fmt, _, _, prior_kind, ldl, _ = probs[0]
+    nb, dtype, xfmt = len(probs), np.float32, _abi.X_BF16 if fmt == "bf16" else _abi.X_F16
+    h = _handle()
+    Xb = np.stack([q[0].reshape(-1, order="A") for q in probs])
+    yb, sb, mwb = (np.stack([q[k] for q in probs]) for k in (5, 6, 8))
+    Lb = np.stack([q[9].reshape(-1, order="A") for q in probs])
+    m, v = np.empty((nb, N), dtype=dtype), np.empty((nb, N), dtype=dtype)
+    lp, tot, info = np.empty((nb, N), dtype=np.float64), np.empty(nb, dtype=np.float64), np.zeros(nb, dtype=np.int32)
+    with _DeviceScope(h) as scope:
+        dX, dy, ds, d_info = scope.dev(Xb), scope.dev(yb), scope.dev(sb), scope.dev(info)
+        d_st, d_T = scope.alloc(nb * D * 4), scope.alloc(nb * D * D * 4)
+        h.posterior_batched_x16(xfmt, _abi.MEM_DEVICE, layout, nb, D, N, dX, ldx, Xb.shape[1], dy, N, _abi.NOISE_ISOTROPIC, ds, 1, prior_kind,
+                                scope.dev(mwb), D, scope.dev(Lb), ldl, Lb.shape[1], d_st, D, d_T, D, D * D, None, D, D * D, None, d_info)
+        h.memcpy_d2h(info, d_info)
+        if not np.any(info):
+            d_m, d_v, d_ll, d_tot = (scope.alloc(a.nbytes) for a in (m, v, lp, tot))
+            h.loo_batched_x16(xfmt, _abi.MEM_DEVICE, layout, nb, D, N, dX, ldx, Xb.shape[1], dy, N, _abi.NOISE_ISOTROPIC, ds, 1, d_st, D,
+                              d_T, D, D * D, d_m, N, d_v, N, d_ll, N, d_tot, d_info)
+            for host, dptr in ((m, d_m), (v, d_v), (lp, d_ll), (tot, d_tot), (info, d_info)):
+                h.memcpy_d2h(host, dptr)
+    _raise_first_failed(info)
+    return [LOO(m[b], v[b], lp[b], float(tot[b])) for b in range(nb)]
+
+
+def _loo_x16_many(fbs, ys):
+    """loo / loo_map for finite regressors on ColVecs16 / RowVecs16 inputs: the 16-bit features as they are, everything else as
+    float32.  Equally shaped problems go through one fit and one scoring call, else one pair of calls per problem.  What the two entry
+    points do not serve raises ValueError naming the limit, in _fused_x16_many's words, before the handle is asked for; there is no
+    widened fall-back."""
+    if not all(isinstance(fb.x, _Vecs16) for fb in fbs):
+        raise ValueError("16-bit inputs (ColVecs16 / RowVecs16) cannot be mixed with ordinary ColVecs / RowVecs in one map: "
+                         "widen them (x.widen()) or convert the others")
+    dtype, probs = np.float32, []
+    for fb, y in zip(fbs, ys):
+        X, layout, ldx, D, N = _x16_layout(fb.x)
+        y = np.ascontiguousarray(y, dtype=dtype)
+        if y.ndim != 1:
+            raise ValueError("y must be a vector")
+        if y.shape[0] != N:
+            raise ValueError("length(y) != size(fx.x.X, 2)")  # reference :74
+        if D > 128:
+            raise ValueError(f"16-bit inputs are served for D <= 128, got D = {D}: widen them (x.widen())")
+        if D == 0:
+            raise ValueError("16-bit inputs need D >= 1")
+        s, noise_kind = _noise(fb.Sy, N, dtype)
+        if noise_kind == _abi.NOISE_DENSE:
+            raise NotImplementedError("loo: with a dense noise covariance one observation is not independent of the rest (that is a "
+                                      "block leave-out); isotropic or diagonal noise only")
+        if noise_kind != _abi.NOISE_ISOTROPIC:  # (the fit's limit: the scoring pass itself takes a noise diagonal)
+            raise ValueError("16-bit inputs are served for isotropic noise only (a scalar variance): widen them (x.widen())")
+        Lw, prior_kind, ldl = _prior(fb.f.Lw, D, dtype)
+        probs.append((X, layout, ldx, D, N, y, s, fb.x.fmt, _mean_vector(fb.f.mw, D, dtype), Lw, prior_kind, ldl, isinstance(fb.f.Lw, PDMat)))
+    if len({(q[0].shape, q[0].flags.f_contiguous, q[1], q[3], q[4], q[7], q[10], q[12]) for q in probs}) == 1:
+        return _loo_x16_batch(probs)
+    out = []
+    for i, q in enumerate(probs):
+        try:
+            out.append(_loo_x16_batch([q])[0])
         except _abi.PosDefException as e:
             e.index = i
             raise
@@ -1535,7 +1604,11 @@ def _kfold_columns_check(D, what):
 def loo(fx, y):
     """Exact leave-one-out predictives of the observations y at fx.x (include/blr_mi355x.h blr_loo_batched_*): for every n the
     predictive of y_n under posterior(fx without observation n) -- what a loop of forget / condition gives, from one marginal
-    pass over the inputs.  Returns LOO(mean, var, logpdf, total).  Dense noise raises NotImplementedError (a block LOO)."""
+    pass over the inputs.  Returns LOO(mean, var, logpdf, total).  Dense noise raises NotImplementedError (a block LOO).
+    On ColVecs16 / RowVecs16 inputs (D <= 128, a scalar noise variance) the fit is blr_posterior_batched_x16 and the pass
+    blr_loo_batched_x16 on the 16-bit features as they are; mean and var are float32."""
+    if isinstance(fx.x, _Vecs16):
+        return _loo_x16_many([_to_finite_blr(fx)], [y])[0]
     return _heldout_one(fx, y, _HELDOUT["loo"], "loo")
 
 

@@ -290,6 +290,34 @@ int blr_marginals_batched_x16(blr_handle* h, int memspace, int layout, int xfmt,
                               float* mean, int64_t stridemean, float* var, int64_t stridevar,
                               int32_t* info);
 
+/* ---- exact leave-one-out on 16-bit features: scoring a model on a network's last layer -----------------------------------------
+ * blr_loo_batched_f32 for inputs that arrive as bf16 / fp16, without the widened copy: the LOO-CV score of a state (mw, T) that
+ * blr_posterior_batched_x16 wrote, from one pass over the same X.  xfmt, X, ldx, strideX: as blr_posterior_batched_x16 (2-byte
+ * elements, any ldx, any 2-byte-aligned base, strideX = 0 shares X).  Every other argument is fp32 / double / int32 with the meaning,
+ * formulas, NULL-to-skip rule (any of loo_mean, loo_var, loo_logpdf, loo_total), info order (a non-positive diagonal entry j of T ->
+ * j, else a non-positive s_i -> i), untouched-outputs rule, NaN rule (blr_get_stat "loo_degenerate"), N = 0 -> loo_total = 0,
+ * fixed-order total and async behaviour of blr_loo_batched_f32.  Both memspaces.  Regressors go in chunks bounded by 65535, the image
+ * buffer (256 MiB: 96 KiB per regressor), the log densities kept in workspace when loo_total is wanted without loo_logpdf (256 MiB)
+ * and option MAX_CHUNK (blr_get_stat "last_chunks").
+ * Served (loo_x16_kernel, csrc/blr_loo_x16.hpp): 1 <= D <= 128, N >= 0, ColVecs and RowVecs, isotropic and diagonal noise (the noise
+ * enters only in the epilogue).  Argument errors (return code = minus the position, and blr_last_error; never a silent widening,
+ * nothing runs): an unknown xfmt (-4), D > 128 (-6: widen them and call blr_loo_batched_f32), dense noise (-13).
+ * Numerics: z_n = T^-T x_n as blr_marginals_batched_x16 forms it -- the fp32 triangular inverse split exactly into three bf16
+ * pieces, exact products on v_mfma_f32_16x16x32_bf16, fp32 accumulation in a fixed order (two column blocks' chains run side by
+ * side; the order within a chain is that of marginals_x16_kernel); sigma2_n = |z_n|^2 summed in double in that kernel's block order
+ * and NOT rounded to fp32 (so it is not bit for bit var - s of blr_marginals_batched_x16), and m_n = x_n'mw accumulated in double on
+ * the widened values (exact products); the epilogue in double.  The same bits call to call, at any B, batch position and chunking, in both memspaces.  A
+ * non-finite feature makes sigma2_n of THAT input NaN, hence its three outputs (counted as degenerate).
+ * blr_last_route names what ran, "marg_image_kernel<float> + loo_x16_kernel<bf16, 2>": format, loader -- 0 ColVecs / 1 RowVecs by
+ * 2-byte loads, 2 ColVecs / 3 RowVecs by 16-byte loads (the rule of blr_marginals_batched_x16).
+ * Measured (tools/x16_loo_bench.py, profiles/x16_loo_bench.json): see README.md and DESIGN.md K35. */
+int blr_loo_batched_x16(blr_handle* h, int memspace, int layout, int xfmt, int64_t B, int64_t D, int64_t N,
+                        const void* X, int64_t ldx, int64_t strideX, const float* y, int64_t stridey,
+                        int noise_kind, const float* s, int64_t strides, const float* mw, int64_t stridemw,
+                        const float* T, int64_t ldt, int64_t strideT,
+                        float* loo_mean, int64_t stride_lm, float* loo_var, int64_t stride_lv,
+                        double* loo_logpdf, int64_t stride_ll, double* loo_total, int32_t* info);
+
 /* ---- regressors with UNEQUAL observation counts in one call -----------------------------------------------------
  * Replaces: reference src/bayesian_linear_regression.jl:55-58 (logpdf), :60-69 (posterior) and :72-89 (shared quantities) under a
  * map over fxs of different lengths -- which blr_posterior_batched_* (one N for the batch) serves only by a loop of calls or by
